@@ -3,6 +3,8 @@
 
     python bench.py --gpus N --steps K --warmup W          (N > 1: under torch.distributed.run, or alone -- it then starts
                                                              its N ranks itself before touching the GPU)
+    python bench.py ... --dump-outputs DIR                  (also writes the last timed step's outputs as DIR/<name>.npy:
+                                                             same arguments, same inputs -- two builds compare array for array)
 
 One "step" = one training iteration of the reference loop (entrypoints/__test_nerf.py:200-305:
 N_rand rays, coarse 64 + fine 64+128 samples, forward + backward + Adam for both networks) PLUS
@@ -77,7 +79,12 @@ def main():
     ap.add_argument("--n-importance", type=int, default=128, help="0 = coarse-only (BASELINE configs[1] with --hw 400)")
     ap.add_argument("--config", choices=["nerf", "ngp"], default="nerf",
                     help="nerf: 8x256 NeRF, the headline workload (BASELINE configs[1-3]); ngp: hash grid + 2x64 MLP (configs[4])")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps of the headline measurement, write what its last step computed (render rgb, "
+                         "losses, the parameters it left) as DIR/<name>.npy, float32, at most 64 MB (rank 0)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # Not under a launcher: start one rank per GPU ourselves (torch.distributed.run, RCCL rendezvous on 127.0.0.1)
         # BEFORE anything in this process touches the GPU, and leave with the children's exit code.
@@ -200,7 +207,7 @@ def main():
                 "ms_per_step": dt / steps * 1e3, "k_ms": float(np.mean([a.elapsed_time(b) for a, b in ev])),
                 "t_train": t_train, "t_render": t_render, "loss_coarse": float(out["loss_coarse"]),
                 "loss_fine": float(out.get("loss_fine", torch.zeros(1))), "comm_ms_per_step": comm_ms, "rank_ms_per_step": rank_ms,
-                "trainer": tr}
+                "trainer": tr, "last": dict(out, render_rgb=rgb)}
 
     def frame_leg(tr):
         """ONE full frame through the PUBLIC API, `render.render(H, W, K, chunk=32768, c2w=...)` (rendering/render.py:268-345 of
@@ -226,6 +233,8 @@ def main():
 
     HP = args.precision                                            # precision of the headline step (default 22)
     m = measure(HP, args.steps, args.warmup)                       # THE timed region of the contract
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, m["trainer"], m.pop("last"))
     dt, value = m["dt"], m["value"]
     # dominant kernel: fused MLP forward over render_rays x 192 samples
     flop = FLOP_PER_SAMPLE_FWD * args.render_rays * n_fine
@@ -416,7 +425,8 @@ def _latest_profile(pattern):
 
 
 def bench_ngp(args, imgs, poses, rposes, K, rank, world, dev):
-    line = measure_ngp(args, imgs, poses, rposes, K, rank, world, dev, extra_bf16=(world == 1 and not args.no_extra_legs))
+    line = measure_ngp(args, imgs, poses, rposes, K, rank, world, dev, extra_bf16=(world == 1 and not args.no_extra_legs),
+                       dump_dir=args.dump_outputs)
     if rank == 0 and world == 1 and not args.no_cpu_baseline:
         line["cpu_baseline"] = cpu_baseline_ngp(args)
     if rank == 0:
@@ -425,12 +435,13 @@ def bench_ngp(args, imgs, poses, rposes, K, rank, world, dev):
         torch.distributed.destroy_process_group()
 
 
-def measure_ngp(args, imgs, poses, rposes, K, rank, world, dev, precision=None, extra_bf16=False):
+def measure_ngp(args, imgs, poses, rposes, K, rank, world, dev, precision=None, extra_bf16=False, dump_dir=None):
     """BASELINE configs[4]: hash grid (16 levels x 2^19 x 2) + SH + NeRF 2x64, 64 samples per ray, coarse-only loop.
     Same step structure as the headline bench (train N_rand rays + render one chunk); the dominant kernel is the
     hash-grid gradient scatter (float atomics), reported against the HBM roofline with its algorithmic bytes.
     precision: of the 2 x 64 network and its inputs (default: --precision when it is 16 or 22, else 22 -- the reference
-    tolerance: float32 gathers + interpolation, split-bf16 MLP); extra_bf16: also measure the declared bf16 mode as `bf16`."""
+    tolerance: float32 gathers + interpolation, split-bf16 MLP); extra_bf16: also measure the declared bf16 mode as `bf16`;
+    dump_dir: --dump-outputs of this measurement (rank 0)."""
     from nerf_meets_mlx_amd import parallel
     from nerf_meets_mlx_amd.engine.ngp import NGPTrainer
     from nerf_meets_mlx_amd.rendering import ray
@@ -475,6 +486,8 @@ def measure_ngp(args, imgs, poses, rposes, K, rank, world, dev, precision=None, 
         torch.distributed.all_reduce(t, op=torch.distributed.ReduceOp.MAX)
         dt = float(t[0])
     assert torch.isfinite(rgb).all() and torch.isfinite(out["loss_coarse"]).all()
+    if dump_dir and rank == 0:
+        dump_outputs(dump_dir, tr, dict(out, render_rgb=rgb))
     t_train = float(np.mean([a.elapsed_time(b) for a, b in phase["train"]])) * 1e-3
     t_render = float(np.mean([a.elapsed_time(b) for a, b in phase["render"]])) * 1e-3
     k_ms = float(np.mean([a.elapsed_time(b) for a, b in tr.field.timing]))
@@ -516,6 +529,30 @@ def measure_ngp(args, imgs, poses, rposes, K, rank, world, dev, precision=None, 
                                           "dtype", "loss_coarse")}
         line["bf16"]["scatter_ms_per_launch"] = b["roofline"]["ms_per_launch"]
     return line
+
+
+DUMP_MAX_ELEMENTS = 1 << 20          # larger arrays (the 16.8 M-entry hash tables) are dumped as a seeded sample of this many entries
+
+
+def dump_outputs(path, tr, last):
+    """--dump-outputs: the arrays the timed step's caller receives from its LAST step -- `render_rgb` (the render chunk),
+    `loss_coarse` / `loss_fine` -- and the parameters that step left (`<name>_params`, the trainer's checkpoint buffers), as
+    float32 `path/<name>.npy`.  An array above DUMP_MAX_ELEMENTS is stored as `<name>_sample`: the entries at a fixed set of
+    flat indices (numpy default_rng(0), sorted), the same for every run with the same arguments.  Runs after the timed region."""
+    tr._join_comm()
+    arrays = dict(last)
+    arrays.update({f"{name}_params": buf.params for name, buf in tr._checkpoint_buffers().items()})
+    torch.cuda.synchronize()
+    os.makedirs(path, exist_ok=True)
+    total = 0
+    for name, t in sorted(arrays.items()):
+        a = t.detach().to(torch.float32).cpu().numpy()
+        if a.size > DUMP_MAX_ELEMENTS:
+            idx = np.sort(np.random.default_rng(0).choice(a.size, DUMP_MAX_ELEMENTS, replace=False))
+            a, name = a.reshape(-1)[idx], name + "_sample"
+        total += a.nbytes
+        assert total <= 64 << 20, "--dump-outputs: more than 64 MB"
+        np.save(os.path.join(path, name + ".npy"), a)
 
 
 def _host_cores():

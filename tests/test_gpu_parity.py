@@ -780,11 +780,12 @@ def test_native_rccl_allreduce_single_rank():
     comm.close()
 
 
-def test_headless_entrypoint_runs():
-    """entrypoints/__test_nerf.py:main without the GUI / file output: a few iterations on the synthetic scene."""
+def test_headless_entrypoint_runs(tmp_path):
+    """entrypoints/__test_nerf.py:main without the GUI: a few iterations on the synthetic scene (its run log goes under
+    tmp_path, not the working directory)."""
     from nerf_meets_mlx_amd.entrypoints import test_nerf
     res = test_nerf.main(None, max_iter=3, hw_synthetic=32, n_train_synthetic=2, render_every=3, n_render_poses=1,
-                         log_every=1)
+                         log_every=1, argv=["--basedir", str(tmp_path)])
     assert len(res["losses"]) == 3 and all(np.isfinite(l[1]) and np.isfinite(l[2]) for l in res["losses"])
     assert res["frames"][0].shape == (32, 32, 3) and res["video"][0].shape == (32, 32, 3)
     assert res["trainer"].it == 3
@@ -922,3 +923,37 @@ def test_bench_prints_one_contract_json_line(extra):
     if "--config" in extra:
         assert d["config"]["precision"] == 22 and d["dtype"].startswith("split16") and d["bf16"]["value"] > 0
     assert d["rank_ms_per_step"] is None                                   # N = 1
+
+
+@pytest.mark.parametrize("extra", [[], ["--config", "ngp"]])
+def test_bench_dump_outputs_are_reproducible(extra, tmp_path):
+    """--dump-outputs DIR: the last timed step's render rgb, losses and parameters as float32 .npy (hash tables as a seeded
+    sample), 64 MB at most; two runs with the same arguments write the same arrays (losses: up to float-atomic rounding),
+    and --steps is the number of timed steps (a third run with one more step leaves different parameters)."""
+    import json, os, subprocess, sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    dumps = []
+    for run, steps in enumerate((3, 3, 4)):
+        d = tmp_path / f"run{run}"
+        cmd = [sys.executable, os.path.join(root, "bench.py"), "--steps", str(steps), "--warmup", "1", "--n-rand", "256",
+               "--render-rays", "2048", "--hw", "64", "--no-cpu-baseline", "--no-extra-legs", "--dump-outputs", str(d)] + extra
+        out = subprocess.run(cmd, capture_output=True, text=True, timeout=600, cwd=root)
+        assert out.returncode == 0, out.stderr[-2000:]
+        line = json.loads([l for l in out.stdout.splitlines() if l.strip()][-1])
+        assert line["steps"] == steps and line["ms_per_step"] > 0
+        files = sorted(os.listdir(d))
+        assert sum(os.path.getsize(d / f) for f in files) <= 64 << 20
+        dumps.append({f[:-4]: np.load(d / f) for f in files})
+    a, b, c = dumps
+    want = {"render_rgb", "loss_coarse"} | ({"tables_params_sample", "mlp_params"} if extra else {"loss_fine", "coarse_params", "fine_params"})
+    assert set(a) == want, sorted(a)
+    assert a["render_rgb"].shape == (2048, 3)
+    for k in a:
+        assert a[k].dtype == np.float32 and np.isfinite(a[k]).all(), k
+        if k.startswith("loss"):            # summed with float atomics (composite.hip): order-dependent in the last bits
+            np.testing.assert_allclose(a[k], b[k], rtol=1e-5, atol=0, err_msg=k)
+        else:
+            assert np.array_equal(a[k], b[k]), k
+    # one more timed step: different parameters after it
+    key = "mlp_params" if extra else "coarse_params"
+    assert not np.array_equal(a[key], c[key])

@@ -157,6 +157,18 @@ def test_bench_and_entry_scripts_parse_without_a_gpu():
         compile(src, tool, "exec")
 
 
+def test_bench_declares_dump_outputs():
+    """bench.py --dump-outputs DIR (the last timed step's outputs as .npy, for comparing two builds) parses without a GPU,
+    and --steps below 1 is refused before any work."""
+    import os, subprocess, sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--help"], capture_output=True, text=True, timeout=300)
+    assert out.returncode == 0 and "--dump-outputs" in out.stdout, out.stderr[-1000:]
+    out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", "0"], capture_output=True, text=True,
+                         timeout=300)
+    assert out.returncode == 2 and "--steps" in out.stderr
+
+
 def _load_bench():
     import importlib.util, os
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
