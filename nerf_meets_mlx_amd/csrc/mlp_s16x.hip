@@ -36,8 +36,10 @@ static_assert(SM_F_FRAGS == 2 * LN::F_PADDED && SM_B_FRAGS == 2 * LN::B_PADDED, 
 // image model
 // ==========================================================================================
 constexpr int NW = 4;                                    // waves per workgroup: one per SIMD (256 activation registers)
-constexpr int IMG_F_CHUNKS = IMG_F_FRAGS / RING_CHUNK, IMG_B_CHUNKS = IMG_B_PADDED / RING_CHUNK;      // 60, 58
-static_assert(IMG_F_CHUNKS * RING_CHUNK == IMG_F_FRAGS && IMG_B_CHUNKS * RING_CHUNK == IMG_B_PADDED, "whole ring chunks");
+// chunks of ONE pass over a stream (the ring's refills wrap modulo this count into the next pass): the transposed stream's last
+// chunk is half used (1808 = 56.5 x 32 fragments; its DMAs read the zero padding behind it)
+constexpr int IMG_F_CHUNKS = IMG_F_FRAGS / RING_CHUNK, IMG_B_CHUNKS = (IMG_B_FRAGS + RING_CHUNK - 1) / RING_CHUNK;      // 60, 57
+static_assert(IMG_F_CHUNKS * RING_CHUNK == IMG_F_FRAGS && IMG_B_CHUNKS * RING_CHUNK <= IMG_B_PADDED, "ring chunks inside the stream");
 #ifndef NERF_S16X_GROUP
 #define NERF_S16X_GROUP 4
 #endif

@@ -15,6 +15,7 @@ import pytest
 import torch
 
 from oracle import nerf_oracle as O
+from tests._poison import BIG_BYTES, NAN_BYTES, PATTERNS, backward_into, forward_into, unwritten
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda"
@@ -333,9 +334,11 @@ def test_weight_gradients_of_the_two_dw_launch_forms_agree(kind, precision, M):
     try:
         for v in ((0, 4, 4) if key == b"dw_private_tiles" else (0, 1, 1, 3, 3) if precision == 16 else (0, 1, 1)):
             _native.check(lib.nerf_set_option(key, v))
-            m.grads.fill_(float("nan"))
-            m.forward(x.to(DEV), train=True)
-            gr = m.backward(g.to(DEV)).cpu().clone()
+            pat = PATTERNS[len(got) % 2]                 # fresh poison in the workspaces, a sentinel in every gradient slot
+            forward_into(m, x.to(DEV), pat, train=True)
+            gr = backward_into(m, g.to(DEV), pat)
+            assert unwritten(gr) == 0
+            gr = gr.cpu().clone()
             assert torch.isfinite(gr).all()
             if v in got:
                 assert torch.equal(got[v], gr), "not bit-reproducible"
@@ -369,13 +372,16 @@ def test_weight_gradients_do_not_depend_on_the_workgroup_count_beyond_rounding(p
     gen = torch.Generator().manual_seed(5)
     M = 3000 * 32 + 17
     x, g = torch.randn(M, 90, generator=gen).to(DEV), torch.randn(M, 4, generator=gen).to(DEV)
-    m.forward(x, train=True)
-    ref = m.backward(g).cpu().clone()
+    forward_into(m, x, NAN_BYTES, train=True)
+    ref = backward_into(m, g, NAN_BYTES)
+    assert unwritten(ref) == 0
+    ref = ref.cpu().clone()
     try:
         _native.check(lib.nerf_set_option(b"dw_workgroups", wgs))
-        m.grads.fill_(float("nan"))
-        m.forward(x, train=True)
-        got = m.backward(g).cpu()
+        forward_into(m, x, BIG_BYTES, train=True)
+        got = backward_into(m, g, BIG_BYTES)
+        assert unwritten(got) == 0
+        got = got.cpu()
     finally:
         _native.check(lib.nerf_set_option(b"dw_workgroups", 0))
     assert torch.isfinite(got).all()
