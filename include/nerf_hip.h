@@ -317,6 +317,45 @@ int nerf_ngp_query_fused_h(const nerf_mlp_arch* arch, const void* packed, const 
                            const int* resolutions_host, int sh_degree, float pos_scale, float pos_offset, float* raw,
                            void* acts, void* stream);
 
+/* ---------------------------------------------------------------- occupancy grid (no reference counterpart)
+ * Empty-space skipping for the hash-grid model: Instant-NGP's occupancy grid (Mueller et al. 2022, "Instant Neural Graphics
+ * Primitives with a Multiresolution Hash Encoding", section 4), one cascade.  Additive: NERF_ABI_VERSION stays 3.
+ *   grid      R^3 cells, R = 2^log2_res (2 <= log2_res <= 10; the model uses 128), over the unit cube the hash grid sees: a position p
+ *             maps to u = p * pos_scale + pos_offset (the roundings of nerf_ngp_query_fused_h) and lies in cell
+ *             (ix, iy, iz) = floor(u R) per axis, linear index c = ix + R (iy + R iz).  A u outside [0, 1)^3 (NaN included) is in
+ *             no cell: always empty.
+ *   density   float32 [R^3], indexed by c.
+ *   bits      uint32 [R^3 / 32]: cell c is occupied when bit (c & 31) of word c >> 5 is set.
+ * Update (engine/occupancy.py drives it): nerf_occ_points -> nerf_ngp_query_fused_h(B = count, n = 1) -> nerf_occ_merge, over all
+ * cells, then nerf_occ_finalize.  Cull of a batch: nerf_occ_cull -> query of the K kept rows -> nerf_scatter_rows of raw back.   */
+
+/* One jittered point per cell of [cell0, cell0 + count): rays_out [count, 11] = [p, 0, 0, 0, 0, 0, 0, 0, 0] and z_out [count] = 0,
+ * so that the fused query with n = 1 evaluates the field at p.  The jitter is a counter-based stream keyed by (seed, update): the
+ * same arguments give the same points on any device or rank.  p always maps back into its own cell (a jittered point the round
+ * trip would move out of it is replaced by the cell centre).                                                               */
+int nerf_occ_points(int log2_res, int64_t cell0, int64_t count, uint64_t seed, uint64_t update, float pos_scale,
+                    float pos_offset, float* rays_out, float* z_out, void* stream);
+/* density[i] = max(density[i] * decay, relu(raw[i, 3])) for i < count (raw [count, 4]: sigma is column 3; a NaN sigma counts
+ * as 0).  Pass density + cell0 for a slice of the grid.                                                                     */
+int nerf_occ_merge(float* density, const float* raw, int64_t count, float decay, void* stream);
+/* thr = min(thr_cap, mean(density)) with the mean a fixed-order double sum (bit-reproducible), *thr_out = thr (may be NULL),
+ * bits = density > thr.  workspace: nerf_occ_finalize_workspace_bytes(log2_res) bytes of scratch.                           */
+int64_t nerf_occ_finalize_workspace_bytes(int log2_res);
+int nerf_occ_finalize(const float* density, int log2_res, float thr_cap, void* workspace, float* thr_out, uint32_t* bits,
+                      void* stream);
+/* Stable ray-major compaction of the samples (ray b, depth j) -> s = b n + j of rays [B, 11] / z [B, n] whose position
+ * o + z d lies in an occupied cell: idx_out [K] = the kept s in increasing order, rays_out [K, 11] / z_out [K] their ray rows
+ * and depths (a B = K, n = 1 batch for the fused query, nerf_mlp_backward_inputs and nerf_hashgrid_backward_rays_ex), and
+ * *count_out = K (device int64).  The three outputs need room for B n rows; K is known on the device only.  raw_fill
+ * [B, n, 4] (16-byte aligned, or NULL): the rows of the culled samples are set to (0, 0, 0, 0) in the same pass, the kept rows
+ * are not touched.  Block scans, no atomics.  workspace: nerf_occ_cull_workspace_bytes(B, n) bytes of scratch.            */
+int64_t nerf_occ_cull_workspace_bytes(int64_t B, int n);
+int nerf_occ_cull(const float* rays, const float* z, int64_t B, int n, const uint32_t* bits, int log2_res, float pos_scale,
+                  float pos_offset, void* workspace, int64_t* idx_out, int64_t* count_out, float* rays_out, float* z_out,
+                  float* raw_fill, void* stream);
+/* dst[idx[i], :] = src[i, :] for i < n (the inverse of nerf_gather_rows); an idx[i] outside [0, n_dst) is skipped.          */
+int nerf_scatter_rows(const float* src, const int64_t* idx, int64_t n, int channels, float* dst, int64_t n_dst, void* stream);
+
 /* ---------------------------------------------------------------- fused renderer (a14 / a18)
  * replaces: rendering/render.py:164-241 render_rays_eval (coarse pass, importance sampling, sort, second pass)
  * as ONE call that enqueues the fixed kernel sequence on `stream`: nerf_sample_coarse -> nerf_query_fused ->

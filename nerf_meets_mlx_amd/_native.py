@@ -63,6 +63,13 @@ SIGNATURES = {
     "nerf_adam_step": (_I, [_P, _P, _P, _P, _I64, _F, _F, _F, _F, _I, _I, _F, _P]),
     "nerf_adam_step_ex": (_I, [_P, _P, _P, _P, _I64, _F, _F, _F, _F, _I, _I, _F, _I, _I, _P]),
     "nerf_adam_step_shadow": (_I, [_P, _P, _P, _P, _I64, _F, _F, _F, _F, _I, _I, _F, _I, _I, _P, _P]),
+    "nerf_occ_points": (_I, [_I, _I64, _I64, _U64, _U64, _F, _F, _P, _P, _P]),
+    "nerf_occ_merge": (_I, [_P, _P, _I64, _F, _P]),
+    "nerf_occ_finalize_workspace_bytes": (_I64, [_I]),
+    "nerf_occ_finalize": (_I, [_P, _I, _F, _P, _P, _P, _P]),
+    "nerf_occ_cull_workspace_bytes": (_I64, [_I64, _I]),
+    "nerf_occ_cull": (_I, [_P, _P, _I64, _I, _P, _I, _F, _F, _P, _P, _P, _P, _P, _P, _P]),
+    "nerf_scatter_rows": (_I, [_P, _P, _I64, _I, _P, _I64, _P]),
 }
 
 

@@ -1,0 +1,342 @@
+// Occupancy grid for empty-space skipping of the hash-grid model (Instant-NGP, Mueller et al. 2022, section 4): jittered cell
+// points, the EMA-max merge of their density, the fixed-order threshold + bitfield pack, the stable cull / compaction of the samples
+// of a batch, and the row scatter that puts the kept samples' outputs back.  No reference counterpart (include/nerf_hip.h).
+// All of it is HBM- or launch-bound; each kernel's algorithmic bytes are in the comment above it.  No atomics anywhere: the
+// compaction order comes from block scans, the mean from a fixed reduction tree, so every output is bit-reproducible.
+#include "common.h"
+
+namespace nerf {
+namespace {
+
+constexpr int CULL_BLOCK = 256;                     // threads per cull workgroup
+constexpr int CULL_ROUNDS = 4;                      // samples per thread: one block covers 1024 consecutive samples
+constexpr int CULL_SPAN = CULL_BLOCK * CULL_ROUNDS;
+constexpr int SUM_BLOCK = 256;                      // density mean: one partial per 4096 cells (16 per thread)
+constexpr int SUM_SPAN = SUM_BLOCK * 16;
+
+__host__ __device__ __forceinline__ uint64_t mix64(uint64_t z) {      // splitmix64 finaliser
+  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+  z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+  return z ^ (z >> 31);
+}
+
+// cell of a unit-cube coordinate on one axis, or -1 when it lies outside [0, 1) (NaN included)
+__device__ __forceinline__ int cell_1d(float u, float R) {
+  if (!(u >= 0.0f && u < 1.0f)) return -1;
+  const int c = (int)floorf(u * R);               // R a power of two: the product is exact
+  return c;                                       // u < 1 and R * u exact: c <= R - 1
+}
+
+// the sample's cell index ix + R (iy + R iz), or -1 outside the box; the position is computed with exactly the roundings of the
+// hash-grid kernels (hash_common.h point_of, mlp.hip ngp_row_frags): (o + z d) * pos_scale + pos_offset, one rounding per op
+__device__ __forceinline__ int64_t cell_of(const float* __restrict__ rr, float zv, float pos_scale, float pos_offset, int log2R) {
+  const float R = (float)(1 << log2R);
+  const int ix = cell_1d((rr[0] + zv * rr[3]) * pos_scale + pos_offset, R);
+  const int iy = cell_1d((rr[1] + zv * rr[4]) * pos_scale + pos_offset, R);
+  const int iz = cell_1d((rr[2] + zv * rr[5]) * pos_scale + pos_offset, R);
+  if ((ix | iy | iz) < 0) return -1;
+  return (int64_t)ix + ((int64_t)iy << log2R) + ((int64_t)iz << (2 * log2R));
+}
+
+__device__ __forceinline__ bool occupied(const uint32_t* __restrict__ bits, int64_t c) {
+  return c >= 0 && ((bits[c >> 5] >> (c & 31)) & 1u);
+}
+
+// ---- jittered points: 44 + 4 B written per cell, nothing read.  Row = [p, d = 0, near = far = 0, viewdirs = 0], z = 0, so that
+// nerf_ngp_query_fused_h evaluates the field at o + 0 * 0 = p exactly (n = 1).  d = 0 is harmless there: the kernel neither
+// normalises d nor the view direction (sh_eval is a polynomial: SH of 0 is the constant band), near / far are not read, and sigma
+// does not depend on the view branch of the 2 x 64 network.
+__global__ void occ_points_kernel(int log2R, int64_t cell0, int64_t count, uint64_t key, float pos_scale, float pos_offset,
+                                  float* __restrict__ rays, float* __restrict__ z) {
+  const float R = (float)(1 << log2R), inv_R = 1.0f / R;
+  const int64_t mask = (1ll << log2R) - 1;
+  for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < count; i += (int64_t)gridDim.x * blockDim.x) {
+    const int64_t c = cell0 + i;
+    const int ci[3] = {(int)(c & mask), (int)((c >> log2R) & mask), (int)(c >> (2 * log2R))};
+    float p[3];
+#pragma unroll
+    for (int a = 0; a < 3; ++a) {
+      const uint64_t h = mix64(key + (uint64_t)(3 * c + a + 1) * 0x9E3779B97F4A7C15ull);
+      const float u = (float)(h >> 40) * 0x1p-24f;                 // [0, 1), 24 bits
+      float q = ((float)ci[a] + u) * inv_R;
+      p[a] = (q - pos_offset) / pos_scale;
+      // the map back onto the unit cube rounds: a point it would move into a neighbour (or onto 1.0) goes to the cell centre
+      if (cell_1d(p[a] * pos_scale + pos_offset, R) != ci[a]) {
+        q = ((float)ci[a] + 0.5f) * inv_R;
+        p[a] = (q - pos_offset) / pos_scale;
+      }
+    }
+    float* r = rays + i * NERF_RAY_STRIDE;
+    r[0] = p[0]; r[1] = p[1]; r[2] = p[2];
+#pragma unroll
+    for (int k = 3; k < NERF_RAY_STRIDE; ++k) r[k] = 0.0f;
+    z[i] = 0.0f;
+  }
+}
+
+// ---- merge: density = max(density * decay, relu(sigma)); 4 + 4 B read (sigma is one float of each 16-byte raw row, but the
+// whole 64-byte line of 4 rows is fetched: 16 B per cell in practice), 4 B written per cell.
+// NaN sigma counts as 0 (relu by `s > 0 ? s : 0`), so one NaN sample cannot poison the mean and with it the whole grid.
+__global__ void occ_merge_kernel(float* __restrict__ density, const float* __restrict__ raw, int64_t count, float decay) {
+  for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < count; i += (int64_t)gridDim.x * blockDim.x) {
+    const float s = raw[4 * i + 3];
+    const float r = s > 0.0f ? s : 0.0f;
+    const float d = density[i] * decay;
+    density[i] = r > d ? r : d;
+  }
+}
+
+// fixed-order double sum of a block's values: per-thread partial (sequential), wave butterfly, then the waves in order
+__device__ __forceinline__ double block_sum(double v, double* sh) {
+  v = wave_sum(v);
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  if (lane == 0) sh[w] = v;
+  __syncthreads();
+  double t = 0.0;
+  for (int k = 0; k < (int)(blockDim.x >> 6); ++k) t += sh[k];
+  __syncthreads();
+  return t;
+}
+
+// ---- mean, part 1: 4 B read per cell, 8 B written per 4096 cells.  Partial b = sum of cells [4096 b, 4096 (b + 1)) in double.
+__global__ void __launch_bounds__(SUM_BLOCK) occ_partials_kernel(const float* __restrict__ density, int64_t ncells,
+                                                                 double* __restrict__ partials) {
+  __shared__ double sh[SUM_BLOCK / 64];
+  const int64_t base = (int64_t)blockIdx.x * SUM_SPAN;
+  double v = 0.0;
+  for (int k = 0; k < SUM_SPAN / SUM_BLOCK; ++k) {
+    const int64_t c = base + k * SUM_BLOCK + threadIdx.x;
+    if (c < ncells) v += (double)density[c];
+  }
+  v = block_sum(v, sh);
+  if (threadIdx.x == 0) partials[blockIdx.x] = v;
+}
+
+// ---- mean, part 2 + threshold + pack: every workgroup sums the same partials in the same order (8 B each, L2-resident), so all
+// of them derive the same thr = min(thr_cap, float(sum / ncells)); then 4 B read per cell and 1 bit written.  Bit c of the field
+// is bit (c & 31) of 32-bit word c >> 5: one wave ballot covers 64 consecutive cells = two words.
+__global__ void __launch_bounds__(SUM_BLOCK) occ_pack_kernel(const float* __restrict__ density, int64_t ncells,
+                                                             const double* __restrict__ partials, int nparts, float thr_cap,
+                                                             uint32_t* __restrict__ bits, float* __restrict__ thr_out) {
+  __shared__ double sh[SUM_BLOCK / 64];
+  double v = 0.0;
+  for (int k = threadIdx.x; k < nparts; k += SUM_BLOCK) v += partials[k];
+  const double total = block_sum(v, sh);
+  const float mean = (float)(total / (double)ncells);
+  const float thr = mean < thr_cap ? mean : thr_cap;
+  if (blockIdx.x == 0 && threadIdx.x == 0 && thr_out) *thr_out = thr;
+  const int lane = threadIdx.x & 63;
+  for (int64_t c0 = (int64_t)blockIdx.x * SUM_BLOCK; c0 < ncells; c0 += (int64_t)gridDim.x * SUM_BLOCK) {
+    if (c0 + (threadIdx.x & ~63) >= ncells) break;          // ncells is a multiple of 64: whole waves in or out of range
+    const int64_t c = c0 + threadIdx.x;
+    const uint64_t m = __ballot(density[c] > thr);
+    if (lane == 0) { bits[c >> 5] = (uint32_t)m; bits[(c >> 5) + 1] = (uint32_t)(m >> 32); }
+  }
+}
+
+// ---- cull, pass 1: per workgroup of 1024 consecutive samples (ray-major: s = b n + j) the number kept; the raw rows of the culled
+// samples get the (0, 0, 0, 0) fill.  Per sample: 4 B of z read, the ray's 24 B of o / d (shared by the n samples of a ray: cache
+// hits), one bitfield word (the 256 KiB field of a 128^3 grid stays in L2), 16 B written when culled; 8 B per workgroup written.
+__global__ void __launch_bounds__(CULL_BLOCK) occ_cull_count_kernel(const float* __restrict__ rays, const float* __restrict__ z,
+                                                                    int64_t M, int n, const uint32_t* __restrict__ bits, int log2R,
+                                                                    float pos_scale, float pos_offset, int64_t* __restrict__ counts,
+                                                                    float* __restrict__ raw_fill) {
+  __shared__ int sh[CULL_BLOCK / 64];
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  int kept = 0;
+  for (int k = 0; k < CULL_ROUNDS; ++k) {
+    const int64_t s = (int64_t)blockIdx.x * CULL_SPAN + k * CULL_BLOCK + threadIdx.x;
+    if (s >= M) continue;
+    const bool keep = occupied(bits, cell_of(rays + (s / n) * NERF_RAY_STRIDE, z[s], pos_scale, pos_offset, log2R));
+    kept += keep;
+    if (!keep && raw_fill) reinterpret_cast<float4*>(raw_fill)[s] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+  }
+  for (int o = 32; o > 0; o >>= 1) kept += __shfl_xor(kept, o, WAVE);
+  if (lane == 0) sh[w] = kept;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    int64_t t = 0;
+    for (int k = 0; k < CULL_BLOCK / 64; ++k) t += sh[k];
+    counts[blockIdx.x] = t;
+  }
+}
+
+// ---- cull, pass 2 (one workgroup): counts -> exclusive offsets in place, the total K to count_out.  8 + 8 B per 1024 samples.
+__global__ void __launch_bounds__(1024) occ_cull_scan_kernel(int64_t* __restrict__ offs, int64_t nblk, int64_t* __restrict__ count_out) {
+  __shared__ int64_t sh[1024 / 64];
+  __shared__ int64_t carry_sh;
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  int64_t carry = 0;
+  for (int64_t b0 = 0; b0 < nblk; b0 += 1024) {
+    const int64_t b = b0 + threadIdx.x;
+    const int64_t v = b < nblk ? offs[b] : 0;
+    int64_t x = v;                                               // inclusive wave scan
+    for (int o = 1; o < WAVE; o <<= 1) {
+      const int64_t t = __shfl_up(x, o, WAVE);
+      if (lane >= o) x += t;
+    }
+    if (lane == 63) sh[w] = x;
+    __syncthreads();
+    int64_t before = carry;
+    for (int k = 0; k < w; ++k) before += sh[k];
+    if (b < nblk) offs[b] = before + x - v;
+    if (threadIdx.x == 1023) carry_sh = before + x;
+    __syncthreads();
+    carry = carry_sh;
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) *count_out = carry;
+}
+
+// ---- cull, pass 3: the same keep decisions again (same reads as pass 1), their ranks inside the workgroup from wave ballots in
+// sample order, and per kept sample: its index (8 B), its ray row (44 B) and depth (4 B) written at offset + rank.
+__global__ void __launch_bounds__(CULL_BLOCK) occ_cull_compact_kernel(const float* __restrict__ rays, const float* __restrict__ z,
+                                                                      int64_t M, int n, const uint32_t* __restrict__ bits, int log2R,
+                                                                      float pos_scale, float pos_offset,
+                                                                      const int64_t* __restrict__ offs, int64_t* __restrict__ idx_out,
+                                                                      float* __restrict__ rays_out, float* __restrict__ z_out) {
+  __shared__ int sh[CULL_BLOCK / 64];
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  int64_t base = offs[blockIdx.x];
+  for (int k = 0; k < CULL_ROUNDS; ++k) {
+    const int64_t s = (int64_t)blockIdx.x * CULL_SPAN + k * CULL_BLOCK + threadIdx.x;
+    const float* rr = rays + (s < M ? s / n : 0) * NERF_RAY_STRIDE;
+    const float zv = s < M ? z[s] : 0.0f;
+    const bool keep = s < M && occupied(bits, cell_of(rr, zv, pos_scale, pos_offset, log2R));
+    const uint64_t m = __ballot(keep);
+    if (lane == 0) sh[w] = __popcll(m);
+    __syncthreads();
+    int64_t before = base;
+    for (int j = 0; j < w; ++j) before += sh[j];
+    int64_t round_total = 0;
+    for (int j = 0; j < CULL_BLOCK / 64; ++j) round_total += sh[j];
+    if (keep) {
+      const int64_t o = before + __popcll(m & ((1ull << lane) - 1ull));
+      idx_out[o] = s;
+      z_out[o] = zv;
+      float* dst = rays_out + o * NERF_RAY_STRIDE;
+#pragma unroll
+      for (int q = 0; q < NERF_RAY_STRIDE; ++q) dst[q] = rr[q];
+    }
+    base += round_total;
+    __syncthreads();                                            // sh is rewritten by the next round
+  }
+}
+
+// ---- dst[idx[i], :] = src[i, :]: 8 + 4 C B read, 4 C B written per row (C = 4: one float4 each way).
+__global__ void scatter_rows_kernel(const float* __restrict__ src, const int64_t* __restrict__ idx, int64_t n, int C, int vec4,
+                                    float* __restrict__ dst, int64_t n_dst) {
+  if (vec4) {
+    for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
+      const int64_t r = idx[i];
+      if (r >= 0 && r < n_dst) reinterpret_cast<float4*>(dst)[r] = reinterpret_cast<const float4*>(src)[i];
+    }
+    return;
+  }
+  const int64_t total = n * C;
+  for (int64_t t = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; t < total; t += (int64_t)gridDim.x * blockDim.x) {
+    const int64_t i = t / C;
+    const int c = (int)(t - i * C);
+    const int64_t r = idx[i];
+    if (r >= 0 && r < n_dst) dst[r * C + c] = src[t];
+  }
+}
+
+bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
+
+}  // namespace
+}  // namespace nerf
+
+using namespace nerf;
+
+extern "C" int64_t nerf_occ_finalize_workspace_bytes(int log2_res) {
+  if (log2_res < 2 || log2_res > 10) return -1;
+  const int64_t ncells = 1ll << (3 * log2_res);
+  return ((ncells + SUM_SPAN - 1) / SUM_SPAN) * (int64_t)sizeof(double);
+}
+
+extern "C" int64_t nerf_occ_cull_workspace_bytes(int64_t B, int n) {
+  if (B < 0 || n < 0) return -1;
+  const int64_t M = B * (int64_t)n;
+  return ((M + CULL_SPAN - 1) / CULL_SPAN) * (int64_t)sizeof(int64_t);
+}
+
+extern "C" int nerf_occ_points(int log2_res, int64_t cell0, int64_t count, uint64_t seed, uint64_t update, float pos_scale,
+                               float pos_offset, float* rays_out, float* z_out, void* stream) {
+  NERF_REQUIRE(log2_res >= 2 && log2_res <= 10, NERF_E_SHAPE, "nerf_occ_points: need 2 <= log2_res <= 10");
+  const int64_t ncells = 1ll << (3 * log2_res);
+  NERF_REQUIRE(cell0 >= 0 && count >= 0 && cell0 + count <= ncells, NERF_E_SHAPE,
+               "nerf_occ_points: cells [%lld, %lld) outside the grid of %lld", (long long)cell0, (long long)(cell0 + count),
+               (long long)ncells);
+  NERF_REQUIRE(pos_scale != 0.0f, NERF_E_SHAPE, "nerf_occ_points: pos_scale must be nonzero");
+  if (count == 0) return NERF_OK;
+  NERF_REQUIRE(rays_out && z_out, NERF_E_NULL, "nerf_occ_points: NULL pointer");
+  const uint64_t key = mix64(seed ^ mix64(update + 0x632BE59BD9B4E019ull));
+  hipLaunchKernelGGL(occ_points_kernel, dim3(grid_for(count, 256)), dim3(256), 0, as_stream(stream), log2_res, cell0, count, key,
+                     pos_scale, pos_offset, rays_out, z_out);
+  return check_launch("nerf_occ_points");
+}
+
+extern "C" int nerf_occ_merge(float* density, const float* raw, int64_t count, float decay, void* stream) {
+  NERF_REQUIRE(count >= 0, NERF_E_SHAPE, "nerf_occ_merge: bad count");
+  if (count == 0) return NERF_OK;
+  NERF_REQUIRE(density && raw, NERF_E_NULL, "nerf_occ_merge: NULL pointer");
+  hipLaunchKernelGGL(occ_merge_kernel, dim3(grid_for(count, 256)), dim3(256), 0, as_stream(stream), density, raw, count, decay);
+  return check_launch("nerf_occ_merge");
+}
+
+extern "C" int nerf_occ_finalize(const float* density, int log2_res, float thr_cap, void* workspace, float* thr_out,
+                                 uint32_t* bits, void* stream) {
+  NERF_REQUIRE(log2_res >= 2 && log2_res <= 10, NERF_E_SHAPE, "nerf_occ_finalize: need 2 <= log2_res <= 10");
+  NERF_REQUIRE(density && workspace && bits, NERF_E_NULL, "nerf_occ_finalize: NULL pointer");
+  const int64_t ncells = 1ll << (3 * log2_res);
+  const int64_t nparts = (ncells + SUM_SPAN - 1) / SUM_SPAN;
+  double* partials = static_cast<double*>(workspace);
+  hipLaunchKernelGGL(occ_partials_kernel, dim3((unsigned)nparts), dim3(SUM_BLOCK), 0, as_stream(stream), density, ncells, partials);
+  int rc = check_launch("nerf_occ_finalize (partial sums)");
+  if (rc) return rc;
+  hipLaunchKernelGGL(occ_pack_kernel, dim3(grid_for(ncells, SUM_BLOCK, 1024)), dim3(SUM_BLOCK), 0, as_stream(stream), density,
+                     ncells, partials, (int)nparts, thr_cap, bits, thr_out);
+  return check_launch("nerf_occ_finalize (pack)");
+}
+
+extern "C" int nerf_occ_cull(const float* rays, const float* z, int64_t B, int n, const uint32_t* bits, int log2_res,
+                             float pos_scale, float pos_offset, void* workspace, int64_t* idx_out, int64_t* count_out,
+                             float* rays_out, float* z_out, float* raw_fill, void* stream) {
+  NERF_REQUIRE(log2_res >= 2 && log2_res <= 10, NERF_E_SHAPE, "nerf_occ_cull: need 2 <= log2_res <= 10");
+  NERF_REQUIRE(B >= 0 && n >= 0, NERF_E_SHAPE, "nerf_occ_cull: bad sizes");
+  NERF_REQUIRE(count_out, NERF_E_NULL, "nerf_occ_cull: NULL count_out");
+  const int64_t M = B * (int64_t)n;
+  if (M == 0) {
+    hipError_t e = hipMemsetAsync(count_out, 0, sizeof(int64_t), as_stream(stream));
+    if (e != hipSuccess) return fail(NERF_E_HIP, "nerf_occ_cull: %s", hipGetErrorString(e));
+    return NERF_OK;
+  }
+  NERF_REQUIRE(rays && z && bits && workspace && idx_out && rays_out && z_out, NERF_E_NULL, "nerf_occ_cull: NULL pointer");
+  NERF_REQUIRE(!raw_fill || aligned16(raw_fill), NERF_E_SHAPE, "nerf_occ_cull: raw_fill must be 16-byte aligned");
+  const int64_t nblk = (M + CULL_SPAN - 1) / CULL_SPAN;
+  NERF_REQUIRE(nblk < (1ll << 31), NERF_E_SHAPE, "nerf_occ_cull: B*n too large");
+  int64_t* offs = static_cast<int64_t*>(workspace);
+  hipLaunchKernelGGL(occ_cull_count_kernel, dim3((unsigned)nblk), dim3(CULL_BLOCK), 0, as_stream(stream), rays, z, M, n, bits,
+                     log2_res, pos_scale, pos_offset, offs, raw_fill);
+  int rc = check_launch("nerf_occ_cull (count)");
+  if (rc) return rc;
+  hipLaunchKernelGGL(occ_cull_scan_kernel, dim3(1), dim3(1024), 0, as_stream(stream), offs, nblk, count_out);
+  rc = check_launch("nerf_occ_cull (scan)");
+  if (rc) return rc;
+  hipLaunchKernelGGL(occ_cull_compact_kernel, dim3((unsigned)nblk), dim3(CULL_BLOCK), 0, as_stream(stream), rays, z, M, n, bits,
+                     log2_res, pos_scale, pos_offset, offs, idx_out, rays_out, z_out);
+  return check_launch("nerf_occ_cull (compact)");
+}
+
+extern "C" int nerf_scatter_rows(const float* src, const int64_t* idx, int64_t n, int channels, float* dst, int64_t n_dst,
+                                 void* stream) {
+  NERF_REQUIRE(n >= 0 && channels > 0 && n_dst >= 0, NERF_E_SHAPE, "nerf_scatter_rows: bad sizes");
+  if (n == 0) return NERF_OK;
+  NERF_REQUIRE(src && idx && dst, NERF_E_NULL, "nerf_scatter_rows: NULL pointer");
+  const bool vec = channels == 4 && aligned16(src) && aligned16(dst);
+  const int64_t items = vec ? n : n * channels;
+  hipLaunchKernelGGL(scatter_rows_kernel, dim3(grid_for(items, 256)), dim3(256), 0, as_stream(stream), src, idx, n,
+                     channels, (int)vec, dst, n_dst);
+  return check_launch("nerf_scatter_rows");
+}

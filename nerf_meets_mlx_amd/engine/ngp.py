@@ -91,6 +91,7 @@ class HashNeRF:
             half_tables = self.precision == 16
         if half_tables and self.precision != 16:
             raise ValueError("HashNeRF: half_tables (fp16 shadow gathers) is a reduced-precision option of precision=16")
+        self.bound = bound
         self.pos_scale, self.pos_offset = (1.0, 0.0) if bound is None else (1.0 / (2.0 * bound), 0.5)
         # table-gradient accumulator: int64 2^-52 fixed point added with integer atomics (the default: bit-reproducible, and
         # measured no slower than float atomics -- both are bound by the atomic request rate, profiles/r03_ngp_scatter.csv)
@@ -108,6 +109,7 @@ class HashNeRF:
         self.on_group_done = None           # NGPTrainer: called after each level group's scatter is enqueued (lo, hi)
         self.on_mlp_grads = None            # NGPTrainer: called with the MLP gradient as soon as it is enqueued (before the scatters)
         self._pts, self._rz = None, None
+        self._sel = None                    # culled training query: (kept sample indices [K], B, n); None: every sample ran
         self.fused = os.environ.get("NERF_NGP_FUSED", "1") != "0"      # rows inside the forward kernel (default) or through HBM
         self.timing = None                  # bench.py: list that receives (start, end) events around the table scatter
 
@@ -133,12 +135,23 @@ class HashNeRF:
         x = torch.cat([feat.view(B, n, 32), shf[:, None, :].expand(B, n, 16)], dim=-1).reshape(B * n, 48)
         return pts, x
 
-    def query(self, rays: torch.Tensor, z: torch.Tensor, train: bool = False, fused: Optional[bool] = None) -> torch.Tensor:
+    def query(self, rays: torch.Tensor, z: torch.Tensor, train: bool = False, fused: Optional[bool] = None,
+              grid=None) -> torch.Tensor:
         """raw [B,n,4].  fused (default): hash gathers and SH are evaluated inside the 2 x 64 forward kernel
-        (`nerf_ngp_query_fused`), no [B n, 48] rows in HBM; fused=False goes through `features` + `mlp.forward`."""
+        (`nerf_ngp_query_fused`), no [B n, 48] rows in HBM; fused=False goes through `features` + `mlp.forward`.
+        grid (an engine.occupancy.OccupancyGrid): only the samples in occupied cells are evaluated (fused query on the K kept
+        rows, one host read of K); the others get raw (0, 0, 0, 0).  With train=True, backward() follows the kept samples."""
         B, n = z.shape
         if fused is None:
             fused = self.fused
+        if grid is not None:
+            if not fused:
+                raise ValueError("HashNeRF.query: the occupancy-grid path runs on the fused query (fused=False has no culled form)")
+            if self.bound is None:
+                raise ValueError("HashNeRF.query: an occupancy grid needs a scene box (HashNeRF(bound=None) has none)")
+            return self._query_culled(rays, z, train, grid)
+        if train:
+            self._sel = None
         if not fused:
             pts, x = self.features(rays, z, need_pts=train)
             self._pts, self._rz = (pts if train else None), None
@@ -156,6 +169,25 @@ class HashNeRF:
                                                N.ptr(raw), N.ptr(acts), N.stream()))
         return raw
 
+    def _query_culled(self, rays, z, train, grid):
+        from .occupancy import scatter_rows
+        B, n = z.shape
+        idx, rk, zk, raw, K = grid.cull(rays, z)
+        if K > 0:
+            raw_k = self.query(rk, zk, train=train)             # B = K, n = 1: the unchanged fused query (sets _rz when training)
+            if grid.timing is not None:
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                e0.record()
+            scatter_rows(raw_k, idx, raw)
+            if grid.timing is not None:
+                e1.record()
+                grid.timing.append(("scatter", e0, e1))
+        elif train:
+            self._rz, self._pts = None, None
+        if train:
+            self._sel = (idx, B, n)
+        return raw
+
     def table_grad(self) -> torch.Tensor:
         """The accumulated table gradient as float32 [L,T,F] (a copy when the accumulators are int64 fixed point)."""
         g = self.enc.grad
@@ -165,7 +197,18 @@ class HashNeRF:
         """(MLP gradient [13188], table gradient [L,T,F]: float32, or int64 2^-52 fixed point when deterministic) of the
         last query(train=True).  accumulate=True adds into the gradient buffer as it stands (NGPTrainer: the Adam pass that
         consumed the previous gradient left it zeroed); the default clears it first."""
-        grads, d_x = self.mlp.backward(d_raw, need_input_grad=True)
+        K = None
+        if self._sel is not None:                            # culled query: the gradient of the kept samples' raw rows only
+            from .occupancy import gather_rows
+            idx, B, n = self._sel
+            assert d_raw.numel() == B * n * 4, "backward() needs the d_raw of the last query(train=True)"
+            K = idx.numel()
+            d_raw = gather_rows(d_raw.reshape(B * n, 4), idx)
+        if K == 0:                                           # nothing was evaluated: zero MLP gradient, no scatter
+            grads, d_x = self.mlp.grads, None
+            grads.zero_()
+        else:
+            grads, d_x = self.mlp.backward(d_raw, need_input_grad=True)
         if self.on_mlp_grads is not None:
             self.on_mlp_grads(grads)
         e = self.enc
@@ -175,7 +218,11 @@ class HashNeRF:
         if self.timing is not None:
             e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
             e0.record()
-        if self._rz is None:                                 # unfused rows: positions were kept by features()
+        if K == 0:
+            for lo, hi in self.level_groups:                 # the multi-rank hooks still run: every rank joins every collective
+                if self.on_group_done is not None:
+                    self.on_group_done(lo, hi)
+        elif self._rz is None:                               # unfused rows: positions were kept by features()
             e.backward(self._pts, d_x)
             if self.on_group_done is not None:
                 self.on_group_done(0, e.n_levels)
@@ -201,13 +248,19 @@ class NGPTrainer(Trainer):
     def __init__(self, images, poses, K, near: float = 2.0, far: float = 6.0, N_rand: int = 4096,
                  n_depth_samples: int = 64, lrate: float = 5e-4, lrate_decay: int = 500, white_bkgd: bool = True,
                  seed: int = 0, device="cuda", chunk: int = 1024 * 32, table_sync: str = "shard", precision: int = 22,
-                 **hash_kw):
+                 occupancy_grid: bool = False, **hash_kw):
+        """occupancy_grid: empty-space skipping (engine/occupancy.py): the grid is updated every UPDATE_EVERY iterations from the
+        start; from iteration WARMUP on, training and rendering evaluate only the samples in occupied cells.  Off by default."""
         super().__init__(images, poses, K, near=near, far=far, N_rand=N_rand, n_depth_samples=n_depth_samples,
                          N_importance=0, lrate=lrate, lrate_decay=lrate_decay, white_bkgd=white_bkgd, ref_quirks=True,
                          seed=seed, device=device, chunk=chunk, precision=precision)
         self.coarse = None                                   # the 8 x 256 network of the base class is not used
         self._field = HashNeRF(device=self.device, seed=seed, precision=precision, **hash_kw)
         self._field.mlp.name = "mlp"
+        self.grid = None
+        if occupancy_grid:
+            from .occupancy import OccupancyGrid
+            self.grid = OccupancyGrid(self._field, near, far, n_depth_samples, seed=seed, device=self.device)
         # Adam WITH bias correction: without it the first steps are lr * sign(g), which turns bf16 noise in near-zero
         # table gradients into full-size steps and can drive sigma negative everywhere (a dead network under the
         # reference's un-activated sigma, DESIGN.md section 7).  This loop is our wiring, so the choice is ours; lrate is
@@ -248,7 +301,7 @@ class NGPTrainer(Trainer):
         self._opt.learning_rate = self.lrate * (0.1 ** (self.it / (self.lrate_decay * 1000)))
         z = sampling.sample_coarse(rays, self.n)
         self._join_comm()                                    # the previous step's table all-gathers (sharded updates)
-        raw = self._field.query(rays, z, train=True)
+        raw = self._field.query(rays, z, train=True, grid=self._grid_for_step(update=True))
         loss, d_raw, _ = render.composite_mse_backward(raw, z, rays, target, self.white_bkgd)
         pending, mlp_work = [], []
         shard = self.world > 1 and self.table_sync == "shard"
@@ -329,9 +382,19 @@ class NGPTrainer(Trainer):
         for s in range(0, rays.shape[0], self.chunk):
             r = rays[s:s + self.chunk]
             z = sampling.sample_coarse(r, self.n)
-            raw = self._field.query(r, z)
+            raw = self._field.query(r, z, grid=self._grid_for_step())
             outs.append(render.composite(raw, z, r, 0.0, self.white_bkgd, need_weights=False)[0])
         return torch.cat(outs, 0)
+
+    def _grid_for_step(self, update: bool = False):
+        """The occupancy grid to cull with at this iteration (None: every sample runs); update=True (the training step) first
+        updates it when the iteration is a multiple of UPDATE_EVERY."""
+        if self.grid is None:
+            return None
+        from .occupancy import UPDATE_EVERY, WARMUP
+        if update and self.it % UPDATE_EVERY == 0:
+            self.grid.update(self._field, self.it)
+        return self.grid if self.it >= WARMUP else None
 
     def sync_optimizer_state(self):
         """COLLECTIVE (every rank, same iteration): with sharded table updates (table_sync "shard", world_size > 1) a rank's
@@ -354,7 +417,10 @@ class NGPTrainer(Trainer):
             raise RuntimeError("NGPTrainer.state_dict / save: the Adam moments of the hash tables are sharded across ranks "
                                "(table_sync='shard'); call tr.sync_optimizer_state() on EVERY rank first (a collective), then "
                                "save from rank 0")
-        return super().state_dict()
+        sd = super().state_dict()
+        if self.grid is not None:                       # the density grid travels; the bitfield is rebuilt from it on load
+            sd["extra"] = {f"occupancy/{k}": v for k, v in self.grid.state_dict().items()}
+        return sd
 
     def load_state_dict(self, sd, allow_legacy_rng: bool = False):
         """Joins the comm stream first (the table all-gathers of a sharded step may still be writing the buffers this loads into),
@@ -362,6 +428,13 @@ class NGPTrainer(Trainer):
         self._join_comm()
         super().load_state_dict(sd, allow_legacy_rng=allow_legacy_rng)
         self._moments_synced = True
+        if self.grid is not None:
+            self.grid.seed = int(self.seed)             # the update stream follows the adopted run's seed, like the ray streams
+            occ = {k[len("occupancy/"):]: v for k, v in sd.get("extra", {}).items() if k.startswith("occupancy/")}
+            if occ:
+                self.grid.load_state_dict(occ)
+            else:                                       # a checkpoint written without a grid: start from the all-occupied grid
+                self.grid.reset()
 
     def _checkpoint_buffers(self):
         """Trainer.save / load / state_dict / load_state_dict work on these: the 2 x 64 MLP and the hash tables, with

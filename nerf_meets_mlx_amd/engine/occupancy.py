@@ -1,0 +1,187 @@
+"""Occupancy grid for empty-space skipping of the hash-grid model (Instant-NGP, Mueller et al. 2022, section 4; one cascade).
+
+The reference has no such grid; this is the standard companion of a hash-grid NeRF, opt-in through
+`NGPTrainer(occupancy_grid=True)`.  Semantics (include/nerf_hip.h "occupancy grid"):
+
+  * RES^3 float32 densities over the unit cube the hash grid sees (the field's scene box), plus a bitfield.
+  * update (every UPDATE_EVERY training iterations): one jittered point per cell from a counter-based stream keyed by
+    (seed, update index) -- never the rank, so all ranks build identical grids from identical tables --, sigma = raw[..., 3]
+    of the current field there, density = max(density * DECAY, relu(sigma)), thr = min(THRESHOLD / delta, mean(density))
+    with delta = (far - near) / n_depth_samples and the mean a fixed-order reduction, bit = density > thr.
+  * The grid starts all occupied.  A sample whose cell is empty is not evaluated: its raw output is (0, 0, 0, 0).
+  * The constants are module constants, not options.
+
+Device work: nerf_occ_points -> nerf_ngp_query_fused_h (n = 1) -> nerf_occ_merge per chunk of cells, then nerf_occ_finalize;
+a cull is nerf_occ_cull (+ one read of K to the host), the query of the K kept rows, nerf_scatter_rows.
+"""
+import time
+from typing import Dict, Optional, Tuple
+
+import torch
+
+from .. import _native as N
+
+LOG2_RES = 7                 # 128^3 cells
+RES = 1 << LOG2_RES
+DECAY = 0.95
+THRESHOLD = 0.01             # thr cap = THRESHOLD / delta
+UPDATE_EVERY = 16            # training iterations between updates (warm-up included)
+WARMUP = 256                 # training iterations before anything is culled
+_CHUNK = 1 << 19             # cells evaluated per query of an update (23 MB of rows)
+
+
+class OccupancyGrid:
+    """Density grid + bitfield over `field`'s scene box (a HashNeRF built with a `bound`)."""
+
+    def __init__(self, field, near: float, far: float, n_depth_samples: int, seed: int = 0, device=None):
+        if getattr(field, "bound", None) is None:
+            raise ValueError("OccupancyGrid: the field has no scene box (HashNeRF(bound=None) works in world coordinates); "
+                             "an occupancy grid needs a bound")
+        self.device = torch.device(device) if device is not None else field.enc.tables.device
+        self.pos_scale, self.pos_offset = float(field.pos_scale), float(field.pos_offset)
+        self.seed = int(seed)
+        self.delta = (float(far) - float(near)) / int(n_depth_samples)
+        self.thr_cap = THRESHOLD / self.delta
+        ncells = RES ** 3
+        self.density = torch.zeros(ncells, dtype=torch.float32, device=self.device)
+        self.bits = torch.empty(ncells // 32, dtype=torch.int32, device=self.device)
+        self.thr = torch.zeros(1, dtype=torch.float32, device=self.device)
+        self.updates = 0
+        self._fin_ws = torch.empty(N.lib().nerf_occ_finalize_workspace_bytes(LOG2_RES), dtype=torch.uint8, device=self.device)
+        self._pts = None                    # (rays [CHUNK, 11], z [CHUNK, 1]) of the update
+        self._cull = {}                     # capacity buffers of the cull, grown on demand
+        self.timing = None                  # tools/ngp_occupancy.py: list receiving (name, start event, end event)
+        self.reset()
+
+    # ------------------------------------------------------------------ state
+    def reset(self):
+        """Density 0, every cell occupied, no update yet."""
+        self.density.zero_()
+        self.bits.fill_(-1)
+        self.thr.zero_()
+        self.updates = 0
+
+    def occupied_fraction(self) -> float:
+        """Fraction of cells whose bit is set (one host read)."""
+        b = self.bits.view(torch.uint8)
+        ones = sum(int(((b >> k) & 1).sum()) for k in range(8))
+        return ones / float(RES ** 3)
+
+    def state_dict(self) -> Dict[str, torch.Tensor]:
+        return {"density": self.density.detach().cpu().clone(), "updates": torch.tensor(self.updates, dtype=torch.int64)}
+
+    def load_state_dict(self, sd):
+        """The bitfield is not stored: it is rebuilt from the density (the same finalize pass, so the same bits)."""
+        d = torch.as_tensor(sd["density"]).reshape(-1)
+        if d.numel() != RES ** 3:
+            raise ValueError(f"OccupancyGrid.load_state_dict: {d.numel()} densities, the grid has {RES ** 3}")
+        self.density.copy_(d.to(self.device, torch.float32))
+        self.updates = int(sd["updates"])
+        if self.updates == 0:
+            self.bits.fill_(-1)
+            self.thr.zero_()
+        else:
+            self._finalize()
+
+    # ------------------------------------------------------------------ update
+    def points(self, update: int, cell0: int = 0, count: Optional[int] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+        """The jittered points of cells [cell0, cell0 + count) for update index `update`: rays [count, 11] (o = point, the rest 0)
+        and z [count, 1] (0)."""
+        if count is None:
+            count = RES ** 3 - cell0
+        rays = torch.empty(count, 11, dtype=torch.float32, device=self.device)
+        z = torch.empty(count, 1, dtype=torch.float32, device=self.device)
+        self._points_into(update, cell0, count, rays, z)
+        return rays, z
+
+    def _points_into(self, update, cell0, count, rays, z):
+        N.check(N.lib().nerf_occ_points(LOG2_RES, cell0, count, self.seed, int(update), self.pos_scale, self.pos_offset,
+                                        N.ptr(rays), N.ptr(z), N.stream()))
+
+    def merge(self, sigma_raw: torch.Tensor, cell0: int = 0):
+        """density[cell0 : cell0 + count] = max(density * DECAY, relu(raw[:, 3])) for raw [count, 4] (or [count, 1, 4])."""
+        raw = N.f32(sigma_raw).reshape(-1, 4)
+        count = raw.shape[0]
+        assert 0 <= cell0 and cell0 + count <= self.density.numel()
+        N.check(N.lib().nerf_occ_merge(N.ptr(self.density[cell0:cell0 + count]) if count else None, N.ptr(raw) if count else None,
+                                       count, DECAY, N.stream()))
+
+    def _finalize(self):
+        N.check(N.lib().nerf_occ_finalize(N.ptr(self.density), LOG2_RES, self.thr_cap, N.ptr(self._fin_ws), N.ptr(self.thr),
+                                          N.ptr(self.bits), N.stream()))
+
+    def update(self, field, it: int):
+        """One update from the current `field` (a HashNeRF), keyed by (seed, it // UPDATE_EVERY)."""
+        ncells = RES ** 3
+        if self._pts is None:
+            self._pts = (torch.empty(_CHUNK, 11, dtype=torch.float32, device=self.device),
+                         torch.empty(_CHUNK, 1, dtype=torch.float32, device=self.device))
+        u = int(it) // UPDATE_EVERY
+        for c0 in range(0, ncells, _CHUNK):
+            cnt = min(_CHUNK, ncells - c0)
+            rays, z = self._pts[0][:cnt], self._pts[1][:cnt]
+            self._points_into(u, c0, cnt, rays, z)
+            raw = field.query(rays, z)                     # inference query: the training activations are not touched
+            self.merge(raw, c0)
+        self._finalize()
+        self.updates += 1
+
+    # ------------------------------------------------------------------ cull
+    def _buf(self, key, shape, dtype):
+        t = self._cull.get(key)
+        n = 1
+        for s in shape:
+            n *= s
+        if t is None or t.numel() < n:
+            t = torch.empty(n, dtype=dtype, device=self.device)
+            self._cull[key] = t
+        return t[:n].view(*shape)
+
+    def cull(self, rays: torch.Tensor, z: torch.Tensor, raw: Optional[torch.Tensor] = None):
+        """(idx [K] int64, rays_k [K, 11], z_k [K, 1], raw [B, n, 4]) for rays [B, 11], z [B, n]: the kept samples in ray-major
+        order, their ray rows and depths, and raw with (0, 0, 0, 0) at every culled sample (the kept rows unwritten).  One read
+        of K to the host.  rays_k / z_k / idx are views of buffers the next cull overwrites."""
+        rays, z = N.f32(rays), N.f32(z)
+        B, n = z.shape
+        M = B * n
+        if raw is None:
+            raw = torch.empty(B, n, 4, dtype=torch.float32, device=self.device)
+        if self.timing is not None:
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+        ws = self._buf("ws", (max(1, N.lib().nerf_occ_cull_workspace_bytes(B, n)),), torch.uint8)
+        idx = self._buf("idx", (M,), torch.int64)
+        cnt = self._buf("count", (1,), torch.int64)
+        rk = self._buf("rays", (M, 11), torch.float32)
+        zk = self._buf("z", (M, 1), torch.float32)
+        N.check(N.lib().nerf_occ_cull(N.ptr(rays), N.ptr(z), B, n, N.ptr(self.bits), LOG2_RES, self.pos_scale, self.pos_offset,
+                                      N.ptr(ws), N.ptr(idx), N.ptr(cnt), N.ptr(rk), N.ptr(zk), N.ptr(raw), N.stream()))
+        if self.timing is not None:
+            e1.record()
+            self.timing.append(("cull", e0, e1))
+        if self.timing is not None:
+            t0 = time.perf_counter()
+        K = int(cnt.item())                                # the one host sync of a culled query
+        if self.timing is not None:
+            self.timing.append(("sync_host", (time.perf_counter() - t0) * 1e3))
+        return idx[:K], rk[:K], zk[:K], raw, K
+
+
+def scatter_rows(src: torch.Tensor, idx: torch.Tensor, dst: torch.Tensor):
+    """dst.view(-1, C)[idx] = src.view(-1, C) in place (`nerf_scatter_rows`)."""
+    C_ = src.shape[-1]
+    src = N.f32(src).reshape(-1, C_)
+    d2 = dst.view(-1, C_)
+    N.check(N.lib().nerf_scatter_rows(N.ptr(src) if src.shape[0] else None, N.ptr(idx) if idx.numel() else None, idx.numel(),
+                                      C_, N.ptr(d2), d2.shape[0], N.stream()))
+    return dst
+
+
+def gather_rows(src: torch.Tensor, idx: torch.Tensor) -> torch.Tensor:
+    """src.view(-1, C)[idx] (`nerf_gather_rows`)."""
+    C_ = src.shape[-1]
+    s2 = N.f32(src).reshape(-1, C_)
+    out = torch.empty(idx.numel(), C_, dtype=torch.float32, device=src.device)
+    if idx.numel():
+        N.check(N.lib().nerf_gather_rows(N.ptr(s2), s2.shape[0], N.ptr(idx), idx.numel(), C_, N.ptr(out), N.stream()))
+    return out

@@ -246,6 +246,8 @@ class Trainer:
             arrays[f"adam/{k}/m"], arrays[f"adam/{k}/v"] = m.numpy(), v.numpy()
             arrays[f"adam/{k}/steps"] = np.array(sd["adam"]["step_count"].get(k, 0), dtype=np.int64)
         arrays["adam_lr"] = np.array(sd["adam"]["learning_rate"], dtype=np.float64)
+        for k, t in sd.get("extra", {}).items():                # subclass state (NGPTrainer: the occupancy grid's densities)
+            arrays[f"extra/{k}"] = t.numpy()
         path = self._npz_path(path)
         tmp = path + ".tmp.npz"
         np.savez(tmp, **arrays)
@@ -264,6 +266,8 @@ class Trainer:
                 name = k[5:-2]
                 sd["adam"]["state"][name] = [torch.from_numpy(z[k]), torch.from_numpy(z[f"adam/{name}/v"])]
                 sd["adam"]["step_count"][name] = int(z[f"adam/{name}/steps"])
+            elif k.startswith("extra/"):
+                sd.setdefault("extra", {})[k[6:]] = torch.from_numpy(z[k])
         if "adam_lr" in z.files:
             sd["adam"]["learning_rate"] = float(z["adam_lr"])
         if "seed" in z.files:
