@@ -356,6 +356,58 @@ int nerf_occ_cull(const float* rays, const float* z, int64_t B, int n, const uin
 /* dst[idx[i], :] = src[i, :] for i < n (the inverse of nerf_gather_rows); an idx[i] outside [0, n_dst) is skipped.          */
 int nerf_scatter_rows(const float* src, const int64_t* idx, int64_t n, int channels, float* dst, int64_t n_dst, void* stream);
 
+/* ---------------------------------------------------------------- occupancy-guided ray march (no reference counterpart)
+ * Instant-NGP's sampler (Mueller et al. 2022, section 4): every ray is marched at a fixed small step through the scene box, and
+ * only the steps that land in occupied cells of the grid above become samples, packed ray by ray.  Additive: NERF_ABI_VERSION
+ * stays 3.  All float32, one rounding per operation, in this order (tests/_march_ref.py reproduces every depth and every keep
+ * decision bit for bit):
+ *   box       lo = (0 - pos_offset) / pos_scale, hi = (1 - pos_offset) / pos_scale (world units; the unit cube of the grid).
+ *   step      step_world = s_u * 2 bound with s_u = sqrt(3) / march_steps (1 <= march_steps <= NERF_MARCH_MAX_STEPS); the host
+ *             computes it in double and rounds once.  dt = step_world / float(sqrt_double((d0 d0 + d1 d1) + d2 d2)).
+ *   interval  t0 = near, t1 = far; per axis a = 0, 1, 2: ta = (lo - o_a) / d_a, tb = (hi - o_a) / d_a,
+ *             t0 = fmaxf(t0, fminf(ta, tb)), t1 = fminf(t1, fmaxf(ta, tb)).
+ *   no sample a ray with a non-finite o, d, near, far or jitter, a zero component of d, or not (t0 < t1 and dt > 0).
+ *   candidates z_k = t0 + ((float)k + j) * dt for k = 0, 1, ... while z_k < t1 and k < 2 march_steps (never binding: the chord of
+ *             the box is at most sqrt(3) 2 bound = march_steps step_world long).  j in [0, 1): the ray's jitter.
+ *   keep      z_k is kept when its cell (the roundings of nerf_occ_cull) exists and is occupied; with bits == NULL (the warm-up)
+ *             when its cell exists.  At most march_steps samples are kept per ray, the nearest first.
+ * Output, one B = K, n = 1 batch for nerf_ngp_query_fused_h / nerf_mlp_backward_inputs / nerf_hashgrid_backward_rays_ex:
+ * offsets int64 [B + 1] (ray b owns [offsets[b], offsets[b + 1]), offsets[B] = K), rows_out [K, 11] (copies of the ray's row),
+ * z_out [K].  Two calls: nerf_occ_march_count writes offsets[B] = K only (the caller reads K and sizes rows_out / z_out), then
+ * nerf_occ_march_write, with the same arguments and workspace, writes offsets[0 .. B - 1] and the samples.  Count -> block scan
+ * -> write, no atomics: every output is bit-reproducible.  jitter: float32 [B], or NULL for jitter_const on every ray.
+ * workspace: nerf_occ_march_workspace_bytes(B) bytes, kept between the two calls.                                         */
+#define NERF_MARCH_MAX_STEPS 1024
+int64_t nerf_occ_march_workspace_bytes(int64_t B);
+int nerf_occ_march_count(const float* rays, int64_t B, const float* jitter, float jitter_const, const uint32_t* bits, int log2_res,
+                         float pos_scale, float pos_offset, float step_world, int march_steps, void* workspace, int64_t* offsets,
+                         void* stream);
+int nerf_occ_march_write(const float* rays, int64_t B, const float* jitter, float jitter_const, const uint32_t* bits, int log2_res,
+                         float pos_scale, float pos_offset, float step_world, int march_steps, void* workspace, int64_t* offsets,
+                         float* rows_out, float* z_out, void* stream);
+/* Merge with a choice of density activation: NERF_OCC_RELU is nerf_occ_merge exactly; NERF_OCC_EXP (the march mode, whose field
+ * density is trunc_exp(raw)) merges density = max(density * decay, exp(raw[i, 3])), a NaN raw counting as 0.               */
+#define NERF_OCC_RELU 0
+#define NERF_OCC_EXP 1
+int nerf_occ_merge_ex(float* density, const float* raw, int64_t count, float decay, int activation, void* stream);
+
+/* ---------------------------------------------------------------- packed compositing (no reference counterpart)
+ * The reference's raw2outputs arithmetic (rendering/render.py:60-92) over the packed samples of the march, ray b owning raw /
+ * z [offsets[b], offsets[b + 1]) (0 to 1024 samples; 16-byte aligned raw [K, 4]), with two differences: sigma_k =
+ * trunc_exp(raw_k[3]) (forward exp(x), backward exp(min(x, 15))), and every interval is step_world long (no 1e10 on the last):
+ *   x_k = sigma_k step_world, alpha_k = 1 - exp(-x_k), T_k = exp(-sum_{i<k} x_i), w_k = alpha_k T_k,
+ *   rgb = sum w c (+ (1 - acc) with a white background), acc = sum w, depth = sum w z.
+ * A ray without samples gets the background, acc = depth = 0.  sigma = +inf gives finite outputs and gradients; a NaN in a
+ * ray's raw makes that ray's outputs NaN and no other's.  Offsets outside [0, K], decreasing, or a segment above 4096 samples
+ * give NaN outputs for that ray and no access.  The training form is nerf_composite_mse_backward's: loss_out (one float the
+ * caller zeroes, float atomics) += mean over B rays x 3 channels of (rgb - target)^2, upstream gradient grad_scale * 2 (rgb -
+ * target) / (3 B); rgb (may be NULL) and d_raw [K, 4] written, d_raw[k, 3] through the trunc_exp backward.                   */
+int nerf_composite_packed_forward(const float* raw, const float* z, const int64_t* offsets, int64_t B, int64_t K, float step_world,
+                                  int white_bkgd, float* rgb, float* acc, float* depth, void* stream);
+int nerf_composite_packed_mse_backward(const float* raw, const int64_t* offsets, int64_t B, int64_t K, float step_world,
+                                       int white_bkgd, const float* target, float grad_scale, float* loss_out, float* rgb,
+                                       float* d_raw, void* stream);
+
 /* ---------------------------------------------------------------- fused renderer (a14 / a18)
  * replaces: rendering/render.py:164-241 render_rays_eval (coarse pass, importance sampling, sort, second pass)
  * as ONE call that enqueues the fixed kernel sequence on `stream`: nerf_sample_coarse -> nerf_query_fused ->

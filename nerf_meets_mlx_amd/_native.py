@@ -70,6 +70,12 @@ SIGNATURES = {
     "nerf_occ_cull_workspace_bytes": (_I64, [_I64, _I]),
     "nerf_occ_cull": (_I, [_P, _P, _I64, _I, _P, _I, _F, _F, _P, _P, _P, _P, _P, _P, _P]),
     "nerf_scatter_rows": (_I, [_P, _P, _I64, _I, _P, _I64, _P]),
+    "nerf_occ_merge_ex": (_I, [_P, _P, _I64, _F, _I, _P]),
+    "nerf_occ_march_workspace_bytes": (_I64, [_I64]),
+    "nerf_occ_march_count": (_I, [_P, _I64, _P, _F, _P, _I, _F, _F, _F, _I, _P, _P, _P]),
+    "nerf_occ_march_write": (_I, [_P, _I64, _P, _F, _P, _I, _F, _F, _F, _I, _P, _P, _P, _P, _P]),
+    "nerf_composite_packed_forward": (_I, [_P, _P, _P, _I64, _I64, _F, _I, _P, _P, _P, _P]),
+    "nerf_composite_packed_mse_backward": (_I, [_P, _P, _I64, _I64, _F, _I, _P, _F, _P, _P, _P, _P]),
 }
 
 

@@ -1,0 +1,175 @@
+// Compositing of PACKED rays (the output of the occupancy-guided march, include/nerf_hip.h "packed compositing"): ray b owns
+// the samples [offsets[b], offsets[b + 1]) of raw [K, 4] / z [K], 0 to 1024 of them.  sigma = trunc_exp(raw[3]), every interval
+// is step_world long (no 1e10 on the last one).
+//
+// HBM-bound: one wavefront per ray, the segment in chunks of 64 samples (one per lane) with the transmittance exponent carried
+// from chunk to chunk.  Algorithmic traffic per ray of n samples: forward read 20n + 16 B, write 20 B; training read 2 x 16n
+// + 28 B (raw is read again by the reverse pass: L2 hits for a 16 KiB segment), write 16n + 4 B.
+#include "common.h"
+
+namespace nerf {
+namespace {
+
+constexpr int MAX_CHUNKS = 64;          // the reverse pass keeps chunk c's carried exponent in lane c: segments up to 4096 samples
+
+struct PackedQ {
+  float r, g, b, x, alpha, T, w;
+};
+
+// the forward quantities of sample k = c0 + lane of a segment ending at s1 (zeros past the end); `carry` = sum of x before c0
+__device__ __forceinline__ PackedQ packed_chunk(const float* __restrict__ raw, int64_t c0, int64_t s1, int lane, float step,
+                                                float carry, float& chunk_total) {
+  PackedQ q;
+  const int64_t k = c0 + lane;
+  if (k < s1) {
+    const float4 rv = *reinterpret_cast<const float4*>(raw + 4 * k);
+    q.r = rv.x; q.g = rv.y; q.b = rv.z;
+    q.x = expf(rv.w) * step;                                   // trunc_exp forward: exp
+    q.alpha = 1.0f - expf(-q.x);
+  } else {
+    q.r = q.g = q.b = q.x = q.alpha = 0.0f;
+  }
+  const float incl = wave_scan_incl(q.x, lane);
+  const float up = __shfl_up(incl, 1, WAVE);                  // exclusive prefix without incl - x (inf - inf when x = inf)
+  const float excl = lane == 0 ? 0.0f : up;
+  chunk_total = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, incl), 63));
+  q.T = expf(-(carry + excl));
+  q.w = q.alpha * q.T;
+  return q;
+}
+
+// segment of ray b, or (0, 0) with bad = true for offsets outside [0, K] / decreasing / longer than MAX_CHUNKS chunks
+__device__ __forceinline__ void segment(const int64_t* __restrict__ offsets, int64_t b, int64_t K, int64_t& s0, int64_t& s1,
+                                        bool& bad) {
+  s0 = offsets[b];
+  s1 = offsets[b + 1];
+  bad = !(s0 >= 0 && s0 <= s1 && s1 <= K && s1 - s0 <= (int64_t)MAX_CHUNKS * 64);
+  if (bad) s0 = s1 = 0;
+}
+
+__global__ void __launch_bounds__(256) composite_packed_fwd_kernel(const float* __restrict__ raw, const float* __restrict__ z,
+                                                                   const int64_t* __restrict__ offsets, int64_t B, int64_t K,
+                                                                   float step, int white, float* __restrict__ rgb,
+                                                                   float* __restrict__ acc, float* __restrict__ depth) {
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+  for (int64_t ray = blockIdx.x * 4 + wv; ray < B; ray += (int64_t)gridDim.x * 4) {
+    int64_t s0, s1;
+    bool bad;
+    segment(offsets, ray, K, s0, s1, bad);
+    float carry = 0.0f, sr = 0.0f, sg = 0.0f, sb = 0.0f, sa = 0.0f, sd = 0.0f;
+    for (int64_t c0 = s0; c0 < s1; c0 += 64) {
+      float tot;
+      const PackedQ q = packed_chunk(raw, c0, s1, lane, step, carry, tot);
+      const float zk = c0 + lane < s1 ? z[c0 + lane] : 0.0f;
+      sr += q.w * q.r; sg += q.w * q.g; sb += q.w * q.b; sa += q.w; sd += q.w * zk;
+      carry += tot;
+    }
+    sr = wave_sum(sr); sg = wave_sum(sg); sb = wave_sum(sb); sa = wave_sum(sa); sd = wave_sum(sd);
+    if (lane == 0) {
+      if (white) { sr = sr + (1.0f - sa); sg = sg + (1.0f - sa); sb = sb + (1.0f - sa); }
+      if (bad) sr = sg = sb = sa = sd = __builtin_nanf("");
+      rgb[ray * 3 + 0] = sr; rgb[ray * 3 + 1] = sg; rgb[ray * 3 + 2] = sb;
+      if (acc) acc[ray] = sa;
+      if (depth) depth[ray] = sd;
+    }
+  }
+}
+
+// Forward (as above) -> rgb -> squared error against the target -> d loss / d raw of every sample of the ray.  The reverse pass
+// walks the chunks last to first with the suffix sum of G w carried exactly (no total-minus-prefix), and re-derives each chunk's
+// forward quantities from the exponent carried into it, which the forward pass left in lane c of `carries`.
+//   dL/dx_k = G_k T_k exp(-x_k) - sum_{k' > k} G_k' w_k',  G_k = gr r_k + gg g_k + gb b_k + gacc
+//   d_raw[k] = (w_k gr, w_k gg, w_k gb, dL/dx_k * step * exp(min(raw_k[3], 15)))      (trunc_exp backward)
+__global__ void __launch_bounds__(256) composite_packed_train_kernel(const float* __restrict__ raw, const int64_t* __restrict__ offsets,
+                                                                     int64_t B, int64_t K, float step, int white,
+                                                                     const float* __restrict__ target, float grad_scale,
+                                                                     float* __restrict__ loss, float* __restrict__ rgb_out,
+                                                                     float* __restrict__ d_raw) {
+  __shared__ float part[4];
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+  const float inv = 1.0f / (float)(B * 3);
+  float sq = 0.0f;
+  for (int64_t ray = blockIdx.x * 4 + wv; ray < B; ray += (int64_t)gridDim.x * 4) {
+    int64_t s0, s1;
+    bool bad;
+    segment(offsets, ray, K, s0, s1, bad);
+    float carry = 0.0f, carries = 0.0f, sr = 0.0f, sg = 0.0f, sb = 0.0f, sa = 0.0f;
+    int nch = 0;
+    for (int64_t c0 = s0; c0 < s1; c0 += 64, ++nch) {
+      if (lane == nch) carries = carry;
+      float tot;
+      const PackedQ q = packed_chunk(raw, c0, s1, lane, step, carry, tot);
+      sr += q.w * q.r; sg += q.w * q.g; sb += q.w * q.b; sa += q.w;
+      carry += tot;
+    }
+    sr = wave_sum(sr); sg = wave_sum(sg); sb = wave_sum(sb); sa = wave_sum(sa);
+    if (white) { sr = sr + (1.0f - sa); sg = sg + (1.0f - sa); sb = sb + (1.0f - sa); }
+    if (bad) sr = sg = sb = __builtin_nanf("");
+    const float er = sr - target[ray * 3], eg = sg - target[ray * 3 + 1], eb = sb - target[ray * 3 + 2];
+    if (lane == 0) {
+      sq += er * er; sq += eg * eg; sq += eb * eb;
+      if (rgb_out) { rgb_out[ray * 3] = sr; rgb_out[ray * 3 + 1] = sg; rgb_out[ray * 3 + 2] = sb; }
+    }
+    const float gr = grad_scale * 2.0f * er * inv, gg = grad_scale * 2.0f * eg * inv, gb = grad_scale * 2.0f * eb * inv;
+    const float gacc = 0.0f - (white ? (gr + gg + gb) : 0.0f);
+    float suffix = 0.0f;                                         // sum of G w over the chunks after this one
+    for (int c = nch - 1; c >= 0; --c) {
+      const int64_t c0 = s0 + (int64_t)c * 64;
+      const float cin = __shfl(carries, c, WAVE);
+      float tot;
+      const PackedQ q = packed_chunk(raw, c0, s1, lane, step, cin, tot);
+      const float G = gr * q.r + gg * q.g + gb * q.b + gacc;
+      const float gw = G * q.w;
+      const float rincl = wave_rscan_incl(gw, lane);
+      const float dn = __shfl_down(rincl, 1, WAVE);
+      const float after = suffix + (lane == 63 ? 0.0f : dn);   // sum over the samples k' > k of the ray
+      const int64_t k = c0 + lane;
+      if (k < s1) {
+        const float sig = raw[4 * k + 3];
+        const float dx = G * q.T * expf(-q.x) - after;
+        float4 o;
+        o.x = q.w * gr; o.y = q.w * gg; o.z = q.w * gb; o.w = dx * step * expf(fminf(sig, 15.0f));
+        *reinterpret_cast<float4*>(d_raw + 4 * k) = o;
+      }
+      suffix += __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, rincl), 0));
+    }
+  }
+  if (lane == 0) part[wv] = sq;
+  __syncthreads();
+  if (threadIdx.x == 0 && loss) atomicAdd(loss, (part[0] + part[1] + part[2] + part[3]) * inv);
+}
+
+bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
+
+}  // namespace
+}  // namespace nerf
+
+using namespace nerf;
+
+extern "C" int nerf_composite_packed_forward(const float* raw, const float* z, const int64_t* offsets, int64_t B, int64_t K,
+                                             float step_world, int white_bkgd, float* rgb, float* acc, float* depth, void* stream) {
+  NERF_REQUIRE(B >= 0 && K >= 0, NERF_E_SHAPE, "nerf_composite_packed_forward: bad sizes");
+  NERF_REQUIRE(step_world > 0.0f, NERF_E_SHAPE, "nerf_composite_packed_forward: step_world must be > 0");
+  if (B == 0) return NERF_OK;
+  NERF_REQUIRE(offsets && rgb && (K == 0 || (raw && z)), NERF_E_NULL, "nerf_composite_packed_forward: NULL pointer");
+  NERF_REQUIRE(K == 0 || aligned16(raw), NERF_E_SHAPE, "nerf_composite_packed_forward: raw must be 16-byte aligned");
+  const dim3 g((unsigned)((B + 3) / 4 > 8192 ? 8192 : (B + 3) / 4)), b(256);
+  hipLaunchKernelGGL(composite_packed_fwd_kernel, g, b, 0, as_stream(stream), raw, z, offsets, B, K, step_world, white_bkgd, rgb,
+                     acc, depth);
+  return check_launch("nerf_composite_packed_forward");
+}
+
+extern "C" int nerf_composite_packed_mse_backward(const float* raw, const int64_t* offsets, int64_t B, int64_t K, float step_world,
+                                                  int white_bkgd, const float* target, float grad_scale, float* loss_out,
+                                                  float* rgb, float* d_raw, void* stream) {
+  NERF_REQUIRE(B >= 0 && K >= 0, NERF_E_SHAPE, "nerf_composite_packed_mse_backward: bad sizes");
+  NERF_REQUIRE(step_world > 0.0f, NERF_E_SHAPE, "nerf_composite_packed_mse_backward: step_world must be > 0");
+  if (B == 0) return NERF_OK;
+  NERF_REQUIRE(offsets && target && (K == 0 || (raw && d_raw)), NERF_E_NULL, "nerf_composite_packed_mse_backward: NULL pointer");
+  NERF_REQUIRE(K == 0 || (aligned16(raw) && aligned16(d_raw)), NERF_E_SHAPE,
+               "nerf_composite_packed_mse_backward: raw / d_raw must be 16-byte aligned");
+  const dim3 g((unsigned)((B + 3) / 4 > 8192 ? 8192 : (B + 3) / 4)), b(256);
+  hipLaunchKernelGGL(composite_packed_train_kernel, g, b, 0, as_stream(stream), raw, offsets, B, K, step_world, white_bkgd, target,
+                     grad_scale, loss_out, rgb, d_raw);
+  return check_launch("nerf_composite_packed_mse_backward");
+}

@@ -86,6 +86,17 @@ __global__ void occ_merge_kernel(float* __restrict__ density, const float* __res
   }
 }
 
+// ---- merge with the exp activation (the march mode's trunc_exp density): density = max(density * decay, exp(sigma)), NaN sigma
+// counting as 0.  Same bytes as occ_merge_kernel.
+__global__ void occ_merge_exp_kernel(float* __restrict__ density, const float* __restrict__ raw, int64_t count, float decay) {
+  for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < count; i += (int64_t)gridDim.x * blockDim.x) {
+    const float s = raw[4 * i + 3];
+    const float r = (s == s) ? expf(s) : 0.0f;
+    const float d = density[i] * decay;
+    density[i] = r > d ? r : d;
+  }
+}
+
 // fixed-order double sum of a block's values: per-thread partial (sequential), wave butterfly, then the waves in order
 __device__ __forceinline__ double block_sum(double v, double* sh) {
   v = wave_sum(v);
@@ -223,6 +234,137 @@ __global__ void __launch_bounds__(CULL_BLOCK) occ_cull_compact_kernel(const floa
   }
 }
 
+// ---- occupancy-guided ray march (include/nerf_hip.h "ray march" spells out the arithmetic; tests/_march_ref.py reproduces it bit
+// for bit).  One lane per ray.  The candidates of a ray are tested MARCH_GROUP at a time: their cells first, then the bitfield
+// words of all of them in flight at once (independent L2 hits, ~200 cycles each, instead of one dependent hit per step), then
+// the keep / stop decisions in order.  A candidate the decisions never reach is looked up for nothing; its cell is a valid index
+// or -1, so every load stays inside the field.
+constexpr int MARCH_BLOCK = 256;                    // rays per march workgroup
+constexpr int MARCH_GROUP = 8;
+
+struct MarchRay {
+  float t0, t1, dt, j;
+  int kmax;                                         // 0: no sample (axis-parallel, NaN / inf, missed box)
+};
+
+__device__ __forceinline__ MarchRay march_setup(const float* __restrict__ rr, float jitter, float pos_scale, float pos_offset,
+                                                float step_world, int march_steps) {
+  MarchRay m;
+  m.t0 = rr[6]; m.t1 = rr[7]; m.j = jitter; m.kmax = 0; m.dt = 0.0f;
+  bool ok = isfinite(m.t0) && isfinite(m.t1) && isfinite(jitter);
+#pragma unroll
+  for (int a = 0; a < 6; ++a) ok = ok && isfinite(rr[a]);
+  ok = ok && rr[3] != 0.0f && rr[4] != 0.0f && rr[5] != 0.0f;
+  if (!ok) return m;
+  const float lo = (0.0f - pos_offset) / pos_scale, hi = (1.0f - pos_offset) / pos_scale;      // the box, world units
+#pragma unroll
+  for (int a = 0; a < 3; ++a) {
+    const float ta = (lo - rr[a]) / rr[3 + a], tb = (hi - rr[a]) / rr[3 + a];
+    m.t0 = fmaxf(m.t0, fminf(ta, tb));
+    m.t1 = fminf(m.t1, fmaxf(ta, tb));
+  }
+  // |d| through a double square root rounded once to float: the correctly rounded float square root, which the float
+  // instruction sequence is not in every case
+  const float dn = (float)sqrt((double)((rr[3] * rr[3] + rr[4] * rr[4]) + rr[5] * rr[5]));
+  m.dt = step_world / dn;
+  if (m.t0 < m.t1 && m.dt > 0.0f) m.kmax = 2 * march_steps;
+  return m;
+}
+
+// Visits the kept samples of one ray in depth order: fn(k_kept, z).  Returns the number kept (<= march_steps).
+template <class F>
+__device__ __forceinline__ int march_ray(const float* __restrict__ rr, const MarchRay& m, const uint32_t* __restrict__ bits,
+                                         int log2R, float pos_scale, float pos_offset, int march_steps, F&& fn) {
+  int kept = 0;
+  for (int k0 = 0; k0 < m.kmax; k0 += MARCH_GROUP) {
+    float zs[MARCH_GROUP];
+    int64_t cs[MARCH_GROUP];
+    uint32_t ws[MARCH_GROUP];
+#pragma unroll
+    for (int g = 0; g < MARCH_GROUP; ++g) {
+      zs[g] = m.t0 + ((float)(k0 + g) + m.j) * m.dt;
+      cs[g] = cell_of(rr, zs[g], pos_scale, pos_offset, log2R);
+    }
+#pragma unroll
+    for (int g = 0; g < MARCH_GROUP; ++g) ws[g] = (bits && cs[g] >= 0) ? bits[cs[g] >> 5] : 0xFFFFFFFFu;
+#pragma unroll
+    for (int g = 0; g < MARCH_GROUP; ++g) {
+      if (k0 + g >= m.kmax || !(zs[g] < m.t1)) return kept;
+      if (cs[g] >= 0 && ((ws[g] >> (cs[g] & 31)) & 1u)) {
+        fn(kept, zs[g]);
+        if (++kept == march_steps) return kept;
+      }
+    }
+  }
+  return kept;
+}
+
+// ---- march, pass 1: per ray the number of kept samples (int32 to the workspace), per workgroup of 256 rays their sum (int64).
+// Per ray: 44 B of row read (the 32 B of o, d, near, far used), 4 B of jitter, one bitfield word per candidate (the 256 KiB field of
+// a 128^3 grid: L2 hits, not HBM); 4 B written.
+__global__ void __launch_bounds__(MARCH_BLOCK) occ_march_count_kernel(const float* __restrict__ rays, int64_t B,
+                                                                      const float* __restrict__ jitter, float jitter_const,
+                                                                      const uint32_t* __restrict__ bits, int log2R, float pos_scale,
+                                                                      float pos_offset, float step_world, int march_steps,
+                                                                      int* __restrict__ ray_counts, int64_t* __restrict__ blk) {
+  __shared__ int sh[MARCH_BLOCK / 64];
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  const int64_t b = (int64_t)blockIdx.x * MARCH_BLOCK + threadIdx.x;
+  int n = 0;
+  if (b < B) {
+    const float* rr = rays + b * NERF_RAY_STRIDE;
+    const MarchRay m = march_setup(rr, jitter ? jitter[b] : jitter_const, pos_scale, pos_offset, step_world, march_steps);
+    n = march_ray(rr, m, bits, log2R, pos_scale, pos_offset, march_steps, [](int, float) {});
+    ray_counts[b] = n;
+  }
+  int t = n;
+  for (int o = 32; o > 0; o >>= 1) t += __shfl_xor(t, o, WAVE);
+  if (lane == 0) sh[w] = t;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    int64_t s = 0;
+    for (int k = 0; k < MARCH_BLOCK / 64; ++k) s += sh[k];
+    blk[blockIdx.x] = s;
+  }
+}
+
+// ---- march, pass 3 (pass 2 is occ_cull_scan_kernel over the workgroup sums): the ray's offset = its workgroup's offset + the
+// exclusive scan of the counts inside the workgroup (8 B written), then the same march again, and per kept sample its ray row
+// (44 B) and depth (4 B) written at offset + rank.  Reads as pass 1, plus 4 B of count per ray and 8 B per workgroup.
+__global__ void __launch_bounds__(MARCH_BLOCK) occ_march_write_kernel(const float* __restrict__ rays, int64_t B,
+                                                                      const float* __restrict__ jitter, float jitter_const,
+                                                                      const uint32_t* __restrict__ bits, int log2R, float pos_scale,
+                                                                      float pos_offset, float step_world, int march_steps,
+                                                                      const int* __restrict__ ray_counts,
+                                                                      const int64_t* __restrict__ blk, int64_t* __restrict__ offsets,
+                                                                      float* __restrict__ rows_out, float* __restrict__ z_out) {
+  __shared__ int sh[MARCH_BLOCK / 64];
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  const int64_t b = (int64_t)blockIdx.x * MARCH_BLOCK + threadIdx.x;
+  const int n = b < B ? ray_counts[b] : 0;
+  int x = n;                                                    // inclusive wave scan of the counts
+  for (int o = 1; o < WAVE; o <<= 1) {
+    const int t = __shfl_up(x, o, WAVE);
+    if (lane >= o) x += t;
+  }
+  if (lane == 63) sh[w] = x;
+  __syncthreads();
+  int64_t base = blk[blockIdx.x] + (x - n);
+  for (int k = 0; k < w; ++k) base += sh[k];
+  if (b >= B) return;
+  offsets[b] = base;
+  if (n == 0) return;
+  const float* rr = rays + b * NERF_RAY_STRIDE;
+  const MarchRay m = march_setup(rr, jitter ? jitter[b] : jitter_const, pos_scale, pos_offset, step_world, march_steps);
+  march_ray(rr, m, bits, log2R, pos_scale, pos_offset, march_steps, [&](int k, float zv) {
+    const int64_t o = base + k;
+    z_out[o] = zv;
+    float* dst = rows_out + o * NERF_RAY_STRIDE;
+#pragma unroll
+    for (int q = 0; q < NERF_RAY_STRIDE; ++q) dst[q] = rr[q];
+  });
+}
+
 // ---- dst[idx[i], :] = src[i, :]: 8 + 4 C B read, 4 C B written per row (C = 4: one float4 each way).
 __global__ void scatter_rows_kernel(const float* __restrict__ src, const int64_t* __restrict__ idx, int64_t n, int C, int vec4,
                                     float* __restrict__ dst, int64_t n_dst) {
@@ -285,6 +427,17 @@ extern "C" int nerf_occ_merge(float* density, const float* raw, int64_t count, f
   return check_launch("nerf_occ_merge");
 }
 
+extern "C" int nerf_occ_merge_ex(float* density, const float* raw, int64_t count, float decay, int activation, void* stream) {
+  NERF_REQUIRE(count >= 0, NERF_E_SHAPE, "nerf_occ_merge_ex: bad count");
+  NERF_REQUIRE(activation == NERF_OCC_RELU || activation == NERF_OCC_EXP, NERF_E_SHAPE,
+               "nerf_occ_merge_ex: activation must be NERF_OCC_RELU (0) or NERF_OCC_EXP (1), got %d", activation);
+  if (activation == NERF_OCC_RELU) return nerf_occ_merge(density, raw, count, decay, stream);
+  if (count == 0) return NERF_OK;
+  NERF_REQUIRE(density && raw, NERF_E_NULL, "nerf_occ_merge_ex: NULL pointer");
+  hipLaunchKernelGGL(occ_merge_exp_kernel, dim3(grid_for(count, 256)), dim3(256), 0, as_stream(stream), density, raw, count, decay);
+  return check_launch("nerf_occ_merge_ex");
+}
+
 extern "C" int nerf_occ_finalize(const float* density, int log2_res, float thr_cap, void* workspace, float* thr_out,
                                  uint32_t* bits, void* stream) {
   NERF_REQUIRE(log2_res >= 2 && log2_res <= 10, NERF_E_SHAPE, "nerf_occ_finalize: need 2 <= log2_res <= 10");
@@ -327,6 +480,61 @@ extern "C" int nerf_occ_cull(const float* rays, const float* z, int64_t B, int n
   hipLaunchKernelGGL(occ_cull_compact_kernel, dim3((unsigned)nblk), dim3(CULL_BLOCK), 0, as_stream(stream), rays, z, M, n, bits,
                      log2_res, pos_scale, pos_offset, offs, idx_out, rays_out, z_out);
   return check_launch("nerf_occ_cull (compact)");
+}
+
+extern "C" int64_t nerf_occ_march_workspace_bytes(int64_t B) {
+  if (B < 0) return -1;
+  const int64_t nblk = (B + MARCH_BLOCK - 1) / MARCH_BLOCK;
+  return nblk * (int64_t)sizeof(int64_t) + ((B * (int64_t)sizeof(int) + 7) / 8) * 8;
+}
+
+static int march_check(const char* who, const float* rays, int64_t B, int log2_res, float pos_scale, float step_world,
+                       int march_steps, void* workspace, int64_t* offsets) {
+  NERF_REQUIRE(log2_res >= 2 && log2_res <= 10, NERF_E_SHAPE, "%s: need 2 <= log2_res <= 10", who);
+  NERF_REQUIRE(B >= 0 && B < (1ll << 40), NERF_E_SHAPE, "%s: bad B", who);
+  NERF_REQUIRE(march_steps >= 1 && march_steps <= NERF_MARCH_MAX_STEPS, NERF_E_SHAPE, "%s: need 1 <= march_steps <= %d (got %d)",
+               who, NERF_MARCH_MAX_STEPS, march_steps);
+  NERF_REQUIRE(pos_scale != 0.0f && step_world > 0.0f, NERF_E_SHAPE, "%s: need pos_scale != 0 and step_world > 0", who);
+  NERF_REQUIRE(offsets, NERF_E_NULL, "%s: NULL offsets", who);
+  NERF_REQUIRE(B == 0 || (rays && workspace), NERF_E_NULL, "%s: NULL pointer", who);
+  return NERF_OK;
+}
+
+extern "C" int nerf_occ_march_count(const float* rays, int64_t B, const float* jitter, float jitter_const, const uint32_t* bits,
+                                    int log2_res, float pos_scale, float pos_offset, float step_world, int march_steps,
+                                    void* workspace, int64_t* offsets, void* stream) {
+  int rc = march_check("nerf_occ_march_count", rays, B, log2_res, pos_scale, step_world, march_steps, workspace, offsets);
+  if (rc) return rc;
+  if (B == 0) {
+    hipError_t e = hipMemsetAsync(offsets, 0, sizeof(int64_t), as_stream(stream));
+    if (e != hipSuccess) return fail(NERF_E_HIP, "nerf_occ_march_count: %s", hipGetErrorString(e));
+    return NERF_OK;
+  }
+  const int64_t nblk = (B + MARCH_BLOCK - 1) / MARCH_BLOCK;
+  int64_t* blk = static_cast<int64_t*>(workspace);
+  int* counts = reinterpret_cast<int*>(blk + nblk);
+  hipLaunchKernelGGL(occ_march_count_kernel, dim3((unsigned)nblk), dim3(MARCH_BLOCK), 0, as_stream(stream), rays, B, jitter,
+                     jitter_const, bits, log2_res, pos_scale, pos_offset, step_world, march_steps, counts, blk);
+  rc = check_launch("nerf_occ_march_count (count)");
+  if (rc) return rc;
+  hipLaunchKernelGGL(occ_cull_scan_kernel, dim3(1), dim3(1024), 0, as_stream(stream), blk, nblk, offsets + B);
+  return check_launch("nerf_occ_march_count (scan)");
+}
+
+extern "C" int nerf_occ_march_write(const float* rays, int64_t B, const float* jitter, float jitter_const, const uint32_t* bits,
+                                    int log2_res, float pos_scale, float pos_offset, float step_world, int march_steps,
+                                    void* workspace, int64_t* offsets, float* rows_out, float* z_out, void* stream) {
+  int rc = march_check("nerf_occ_march_write", rays, B, log2_res, pos_scale, step_world, march_steps, workspace, offsets);
+  if (rc) return rc;
+  if (B == 0) return NERF_OK;
+  NERF_REQUIRE(rows_out && z_out, NERF_E_NULL, "nerf_occ_march_write: NULL rows_out / z_out");
+  const int64_t nblk = (B + MARCH_BLOCK - 1) / MARCH_BLOCK;
+  const int64_t* blk = static_cast<const int64_t*>(workspace);
+  const int* counts = reinterpret_cast<const int*>(blk + nblk);
+  hipLaunchKernelGGL(occ_march_write_kernel, dim3((unsigned)nblk), dim3(MARCH_BLOCK), 0, as_stream(stream), rays, B, jitter,
+                     jitter_const, bits, log2_res, pos_scale, pos_offset, step_world, march_steps, counts, blk, offsets, rows_out,
+                     z_out);
+  return check_launch("nerf_occ_march_write");
 }
 
 extern "C" int nerf_scatter_rows(const float* src, const int64_t* idx, int64_t n, int channels, float* dst, int64_t n_dst,

@@ -188,6 +188,18 @@ class HashNeRF:
             self._sel = (idx, B, n)
         return raw
 
+    def query_packed(self, rows: torch.Tensor, z: torch.Tensor, train: bool = False) -> torch.Tensor:
+        """raw [K, 1, 4] of K packed samples (rows [K, 11], depths z [K]: the output of OccupancyGrid.march) as one B = K, n = 1
+        fused query.  K = 0 is allowed: with train=True, backward() then gives a zero MLP gradient and still runs every
+        level-group hook."""
+        K = rows.shape[0]
+        if K > 0:
+            return self.query(rows, z.reshape(K, 1), train=train, fused=True)
+        if train:
+            self._sel = (torch.empty(0, dtype=torch.int64, device=rows.device), 0, 1)
+            self._rz, self._pts = None, None
+        return torch.empty(0, 1, 4, dtype=torch.float32, device=rows.device)
+
     def table_grad(self) -> torch.Tensor:
         """The accumulated table gradient as float32 [L,T,F] (a copy when the accumulators are int64 fixed point)."""
         g = self.enc.grad
@@ -248,9 +260,21 @@ class NGPTrainer(Trainer):
     def __init__(self, images, poses, K, near: float = 2.0, far: float = 6.0, N_rand: int = 4096,
                  n_depth_samples: int = 64, lrate: float = 5e-4, lrate_decay: int = 500, white_bkgd: bool = True,
                  seed: int = 0, device="cuda", chunk: int = 1024 * 32, table_sync: str = "shard", precision: int = 22,
-                 occupancy_grid: bool = False, **hash_kw):
+                 occupancy_grid: bool = False, march_steps: Optional[int] = None, **hash_kw):
         """occupancy_grid: empty-space skipping (engine/occupancy.py): the grid is updated every UPDATE_EVERY iterations from the
-        start; from iteration WARMUP on, training and rendering evaluate only the samples in occupied cells.  Off by default."""
+        start; from iteration WARMUP on, training and rendering evaluate only the samples in occupied cells.  Off by default.
+        march_steps (needs occupancy_grid=True and a scene box; 1 ... 1024; None: the n_depth_samples stratified grid): the
+        occupancy-guided ray march of DESIGN.md section 12 replaces the fixed samples -- each ray is stepped at
+        sqrt(3) / march_steps * 2 bound through the box, only the steps in occupied cells (every step inside the box before
+        WARMUP) are evaluated, and they are composited with sigma = trunc_exp(raw)."""
+        if march_steps is not None:
+            from .occupancy import check_march_steps
+            check_march_steps(march_steps)
+            if not occupancy_grid:
+                raise ValueError("NGPTrainer: march_steps needs occupancy_grid=True (the march samples the grid)")
+            if hash_kw.get("bound", 1.5) is None:
+                raise ValueError("NGPTrainer: march_steps needs a scene box (HashNeRF(bound=None) has none)")
+        self.march_steps = march_steps
         super().__init__(images, poses, K, near=near, far=far, N_rand=N_rand, n_depth_samples=n_depth_samples,
                          N_importance=0, lrate=lrate, lrate_decay=lrate_decay, white_bkgd=white_bkgd, ref_quirks=True,
                          seed=seed, device=device, chunk=chunk, precision=precision)
@@ -258,9 +282,12 @@ class NGPTrainer(Trainer):
         self._field = HashNeRF(device=self.device, seed=seed, precision=precision, **hash_kw)
         self._field.mlp.name = "mlp"
         self.grid = None
+        self.last_march = None               # march mode: (rays, kept samples) of the last training march
         if occupancy_grid:
             from .occupancy import OccupancyGrid
-            self.grid = OccupancyGrid(self._field, near, far, n_depth_samples, seed=seed, device=self.device)
+            self.grid = OccupancyGrid(self._field, near, far, n_depth_samples, seed=seed, device=self.device,
+                                      march_steps=march_steps)
+        self._march_gen = torch.Generator(device=self.device) if march_steps is not None else None
         # Adam WITH bias correction: without it the first steps are lr * sign(g), which turns bf16 noise in near-zero
         # table gradients into full-size steps and can drive sigma negative everywhere (a dead network under the
         # reference's un-activated sigma).  This loop is our wiring, so the choice is ours; lrate is
@@ -299,10 +326,14 @@ class NGPTrainer(Trainer):
         if rays is None:
             rays, target = self.sample_batch()
         self._opt.learning_rate = self.lrate * (0.1 ** (self.it / (self.lrate_decay * 1000)))
-        z = sampling.sample_coarse(rays, self.n)
-        self._join_comm()                                    # the previous step's table all-gathers (sharded updates)
-        raw = self._field.query(rays, z, train=True, grid=self._grid_for_step(update=True))
-        loss, d_raw, _ = render.composite_mse_backward(raw, z, rays, target, self.white_bkgd)
+        if self.march_steps is not None:
+            self._join_comm()
+            loss, d_raw = self._march_step_forward(rays, target)
+        else:
+            z = sampling.sample_coarse(rays, self.n)
+            self._join_comm()                                # the previous step's table all-gathers (sharded updates)
+            raw = self._field.query(rays, z, train=True, grid=self._grid_for_step(update=True))
+            loss, d_raw, _ = render.composite_mse_backward(raw, z, rays, target, self.white_bkgd)
         pending, mlp_work = [], []
         shard = self.world > 1 and self.table_sync == "shard"
         if self.world > 1:
@@ -376,9 +407,31 @@ class NGPTrainer(Trainer):
         self.it += 1
         return {"loss_coarse": loss}
 
+    def _march_step_forward(self, rays, target):
+        """March mode, training: grid update -> march (per-ray jitter from counter stream 4) -> fused query of the K packed
+        samples -> packed compositing + MSE backward.  (loss, d_raw [K, 4]); the last query(train=True) is the packed one."""
+        from .occupancy import WARMUP
+        self._grid_for_step(update=True)
+        B = rays.shape[0]
+        self._march_gen.manual_seed(parallel.counter_seed(self.seed, self.rank, 4, self.it))
+        jitter = torch.rand(B, dtype=torch.float32, device=self.device, generator=self._march_gen)
+        offsets, rows, z, K = self.grid.march(rays, jitter, use_bits=self.it >= WARMUP)
+        self.last_march = (B, K)
+        raw = self._field.query_packed(rows, z, train=True)
+        loss, d_raw, _ = render.composite_packed_mse_backward(raw, offsets, B, self.grid.step_world, target, self.white_bkgd)
+        return loss, d_raw
+
     def render_rays(self, rays: torch.Tensor, u=None):
         outs = []
         self._join_comm()
+        if self.march_steps is not None:                     # march mode: jitter 0.5, the bitfield once the warm-up is over
+            from .occupancy import WARMUP
+            for s in range(0, rays.shape[0], self.chunk):
+                r = N.f32(rays[s:s + self.chunk])
+                offsets, rows, z, K = self.grid.march(r, 0.5, use_bits=self.it >= WARMUP)
+                raw = self._field.query_packed(rows, z)
+                outs.append(render.composite_packed(raw, z, offsets, r.shape[0], self.grid.step_world, self.white_bkgd)[0])
+            return torch.cat(outs, 0)
         for s in range(0, rays.shape[0], self.chunk):
             r = rays[s:s + self.chunk]
             z = sampling.sample_coarse(r, self.n)

@@ -13,7 +13,14 @@ The reference has no such grid; this is the standard companion of a hash-grid Ne
 
 Device work: nerf_occ_points -> nerf_ngp_query_fused_h (n = 1) -> nerf_occ_merge per chunk of cells, then nerf_occ_finalize;
 a cull is nerf_occ_cull (+ one read of K to the host), the query of the K kept rows, nerf_scatter_rows.
+
+March mode (`OccupancyGrid(..., march_steps=S)`, `NGPTrainer(occupancy_grid=True, march_steps=S)`; include/nerf_hip.h "ray
+march"): the grid also samples.  `march()` walks each ray through the box at the fixed step
+step_world = sqrt(3) / S * 2 bound and keeps the steps in occupied cells (nerf_occ_march_count, one read of K, nerf_occ_march_write).
+The density of that field is trunc_exp(raw sigma), so the merge uses exp (nerf_occ_merge_ex) and the threshold cap is
+THRESHOLD / step_world.
 """
+import math
 import time
 from typing import Dict, Optional, Tuple
 
@@ -30,17 +37,43 @@ WARMUP = 256                 # training iterations before anything is culled
 _CHUNK = 1 << 19             # cells evaluated per query of an update (23 MB of rows)
 
 
+MAX_MARCH_STEPS = 1024       # NERF_MARCH_MAX_STEPS
+RELU, EXP = 0, 1             # NERF_OCC_RELU / NERF_OCC_EXP: the density activation of the merge
+
+
+def check_march_steps(march_steps) -> int:
+    """march_steps as an int in [1, MAX_MARCH_STEPS], or ValueError."""
+    if isinstance(march_steps, bool) or not isinstance(march_steps, int) or not 1 <= march_steps <= MAX_MARCH_STEPS:
+        raise ValueError(f"march_steps must be an int in [1, {MAX_MARCH_STEPS}], got {march_steps!r}")
+    return march_steps
+
+
+def march_step_world(march_steps: int, bound: float) -> float:
+    """The march's world step sqrt(3) / march_steps * 2 bound, computed in double and rounded once to float32."""
+    return float(torch.tensor(math.sqrt(3.0) / int(march_steps) * 2.0 * float(bound), dtype=torch.float32))
+
+
 class OccupancyGrid:
     """Density grid + bitfield over `field`'s scene box (a HashNeRF built with a `bound`)."""
 
-    def __init__(self, field, near: float, far: float, n_depth_samples: int, seed: int = 0, device=None):
+    def __init__(self, field, near: float, far: float, n_depth_samples: int, seed: int = 0, device=None,
+                 march_steps: Optional[int] = None):
+        """march_steps (None: the culling grid of section 11, unchanged): the grid of the ray march -- sample spacing
+        delta = march_step_world(march_steps, bound) instead of (far - near) / n_depth_samples, and the exp density activation."""
         if getattr(field, "bound", None) is None:
             raise ValueError("OccupancyGrid: the field has no scene box (HashNeRF(bound=None) works in world coordinates); "
                              "an occupancy grid needs a bound")
+        self.march_steps = None if march_steps is None else check_march_steps(march_steps)
         self.device = torch.device(device) if device is not None else field.enc.tables.device
         self.pos_scale, self.pos_offset = float(field.pos_scale), float(field.pos_offset)
         self.seed = int(seed)
-        self.delta = (float(far) - float(near)) / int(n_depth_samples)
+        if self.march_steps is None:
+            self.delta = (float(far) - float(near)) / int(n_depth_samples)
+            self.activation = RELU
+        else:
+            self.delta = march_step_world(self.march_steps, field.bound)
+            self.activation = EXP
+        self.step_world = self.delta
         self.thr_cap = THRESHOLD / self.delta
         ncells = RES ** 3
         self.density = torch.zeros(ncells, dtype=torch.float32, device=self.device)
@@ -99,12 +132,16 @@ class OccupancyGrid:
                                         N.ptr(rays), N.ptr(z), N.stream()))
 
     def merge(self, sigma_raw: torch.Tensor, cell0: int = 0):
-        """density[cell0 : cell0 + count] = max(density * DECAY, relu(raw[:, 3])) for raw [count, 4] (or [count, 1, 4])."""
+        """density[cell0 : cell0 + count] = max(density * DECAY, act(raw[:, 3])) for raw [count, 4] (or [count, 1, 4]); act is relu,
+        or exp in march mode (a NaN counts as 0 either way)."""
         raw = N.f32(sigma_raw).reshape(-1, 4)
         count = raw.shape[0]
         assert 0 <= cell0 and cell0 + count <= self.density.numel()
-        N.check(N.lib().nerf_occ_merge(N.ptr(self.density[cell0:cell0 + count]) if count else None, N.ptr(raw) if count else None,
-                                       count, DECAY, N.stream()))
+        dens = N.ptr(self.density[cell0:cell0 + count]) if count else None
+        if self.activation == RELU:
+            N.check(N.lib().nerf_occ_merge(dens, N.ptr(raw) if count else None, count, DECAY, N.stream()))
+        else:
+            N.check(N.lib().nerf_occ_merge_ex(dens, N.ptr(raw) if count else None, count, DECAY, self.activation, N.stream()))
 
     def _finalize(self):
         N.check(N.lib().nerf_occ_finalize(N.ptr(self.density), LOG2_RES, self.thr_cap, N.ptr(self._fin_ws), N.ptr(self.thr),
@@ -165,6 +202,52 @@ class OccupancyGrid:
         if self.timing is not None:
             self.timing.append(("sync_host", (time.perf_counter() - t0) * 1e3))
         return idx[:K], rk[:K], zk[:K], raw, K
+
+
+    # ------------------------------------------------------------------ march
+    def _grow(self, key, n, dtype):
+        """A capacity buffer of at least n elements (grown by 1.25 x, so that a slowly rising K does not reallocate every step)."""
+        t = self._cull.get(key)
+        if t is None or t.numel() < n:
+            t = torch.empty(max(n, int(1.25 * (t.numel() if t is not None else 0))), dtype=dtype, device=self.device)
+            self._cull[key] = t
+        return t[:n]
+
+    def march(self, rays: torch.Tensor, jitter, use_bits: bool = True):
+        """(offsets [B + 1] int64, rows [K, 11], z [K], K) of the march of rays [B, 11] (march mode only): ray b owns the packed
+        samples [offsets[b], offsets[b + 1]).  jitter: float32 [B] per ray, or one float for every ray (0.5 when rendering).
+        use_bits=False (the warm-up) keeps every step inside the box.  One read of K to the host; the outputs are views of
+        buffers the next march overwrites."""
+        if self.march_steps is None:
+            raise ValueError("OccupancyGrid.march: the grid was built without march_steps")
+        rays = N.f32(rays)
+        B = rays.shape[0]
+        if torch.is_tensor(jitter):
+            jit, jc = N.f32(jitter).reshape(-1), 0.0
+            assert jit.numel() == B, "march: one jitter per ray"
+        else:
+            jit, jc = None, float(jitter)
+        if self.timing is not None:
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+        ws = self._grow("march_ws", max(1, N.lib().nerf_occ_march_workspace_bytes(B)), torch.uint8)
+        offsets = self._grow("march_offsets", B + 1, torch.int64)
+        args = (N.ptr(rays) if B else None, B, N.ptr(jit) if B else None, jc, N.ptr(self.bits) if use_bits else None, LOG2_RES,
+                self.pos_scale, self.pos_offset, self.step_world, self.march_steps, N.ptr(ws), N.ptr(offsets))
+        N.check(N.lib().nerf_occ_march_count(*args, N.stream()))
+        if self.timing is not None:
+            t0 = time.perf_counter()
+        K = int(offsets[B].item())                          # the one host sync of a march
+        if self.timing is not None:
+            self.timing.append(("sync_host", (time.perf_counter() - t0) * 1e3))
+        rows = self._grow("march_rows", max(1, K) * 11, torch.float32)[:K * 11].view(K, 11)
+        z = self._grow("march_z", max(1, K), torch.float32)[:K]
+        N.check(N.lib().nerf_occ_march_write(*args, N.ptr(rows) if K else N.ptr(self._cull["march_rows"]),
+                                             N.ptr(z) if K else N.ptr(self._cull["march_z"]), N.stream()))
+        if self.timing is not None:
+            e1.record()
+            self.timing.append(("march", e0, e1))
+        return offsets, rows, z, K
 
 
 def scatter_rows(src: torch.Tensor, idx: torch.Tensor, dst: torch.Tensor):

@@ -57,6 +57,38 @@ def composite_mse_backward(raw, z_vals, rays, target, white_bkgd=False, grad_sca
     return loss, d_raw, rgb
 
 
+def composite_packed(raw, z, offsets, B: int, step_world: float, white_bkgd=False):
+    """(rgb [B, 3], acc [B], depth [B]) of packed rays (`nerf_composite_packed_forward`): ray b owns raw [K, 4] / z [K] rows
+    [offsets[b], offsets[b + 1]); sigma = trunc_exp(raw[..., 3]), every interval step_world (include/nerf_hip.h)."""
+    raw = N.f32(raw).reshape(-1, 4)
+    z = N.f32(z).reshape(-1)
+    K = raw.shape[0]
+    dev = offsets.device
+    rgb = torch.empty(B, 3, dtype=torch.float32, device=dev)
+    acc = torch.empty(B, dtype=torch.float32, device=dev)
+    depth = torch.empty(B, dtype=torch.float32, device=dev)
+    N.check(N.lib().nerf_composite_packed_forward(N.ptr(raw) if K else None, N.ptr(z) if K else None, N.ptr(offsets), B, K,
+                                                  float(step_world), int(bool(white_bkgd)), N.ptr(rgb), N.ptr(acc), N.ptr(depth),
+                                                  N.stream()))
+    return rgb, acc, depth
+
+
+def composite_packed_mse_backward(raw, offsets, B: int, step_world: float, target, white_bkgd=False, grad_scale: float = 1.0,
+                                  need_rgb: bool = False):
+    """(loss [1], d_raw [K, 4], rgb [B, 3] or None): the packed compositing + MSE + their gradient w.r.t. raw in one launch
+    (`nerf_composite_packed_mse_backward`, the conventions of composite_mse_backward)."""
+    raw = N.f32(raw).reshape(-1, 4)
+    K = raw.shape[0]
+    dev = offsets.device
+    loss = torch.zeros(1, dtype=torch.float32, device=dev)
+    d_raw = torch.empty(K, 4, dtype=torch.float32, device=dev)
+    rgb = torch.empty(B, 3, dtype=torch.float32, device=dev) if need_rgb else None
+    N.check(N.lib().nerf_composite_packed_mse_backward(N.ptr(raw) if K else None, N.ptr(offsets), B, K, float(step_world),
+                                                       int(bool(white_bkgd)), N.ptr(N.f32(target)), float(grad_scale), N.ptr(loss),
+                                                       N.ptr(rgb), N.ptr(d_raw) if K else None, N.stream()))
+    return loss, d_raw, rgb
+
+
 _WS = {}
 
 

@@ -1,0 +1,167 @@
+#!/usr/bin/env python3
+"""Occupancy-guided ray march against the 64-sample arms for BASELINE configs[4] (800 x 800 synthetic Lego, 4 training views,
+N_rand 4096, seed 4, one 32 768-ray render chunk per step), in ONE process:
+
+    python tools/ngp_march.py --out profiles/ngp_march.jsonl                  (GPU; a few minutes)
+
+Arms: "off" (64 stratified samples, no grid), "cull" (64 samples, grid cull) and "march<S>" (the march of
+section 12 with march_steps = S; default 1024 and 512).  Every arm is trained past the grid's warm-up, then the arms alternate
+timed blocks of --block steps until --iters; each step is timed with device events (train step, render chunk).  Per arm: train
+ms / step, render ms / chunk, samples per ray in training and rendering, for march arms the device time of the march (count +
+scan + write) and the host time of the K read-back; after --iters the held-out PSNR on a fifth view, next to the PSNR of an
+all-white frame of that view.  One JSON line per arm and a summary line.
+
+    python tools/ngp_march.py --stats <rocprofv3 results .db>
+
+prints the average time per launch of the march and packed-compositing kernels from a `rocprofv3 --kernel-trace` run of this tool
+(e.g. with --iters 400 --no-psnr)."""
+import argparse
+import json
+import os
+import sys
+import time
+
+import numpy as np
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+
+def _ms(pairs):
+    return float(np.mean([a.elapsed_time(b) for a, b in pairs])) if pairs else 0.0
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--iters", type=int, default=2000)
+    ap.add_argument("--block", type=int, default=50, help="timed steps per arm before switching")
+    ap.add_argument("--hw", type=int, default=800)
+    ap.add_argument("--n-rand", type=int, default=4096)
+    ap.add_argument("--render-rays", type=int, default=32768)
+    ap.add_argument("--no-psnr", action="store_true")
+    ap.add_argument("--arms", default="off,cull,march1024,march512")
+    ap.add_argument("--out", default=None, help="append the JSON lines to this file")
+    ap.add_argument("--stats", default=None, help="summarise a rocprofv3 --kernel-trace results database instead of measuring")
+    a = ap.parse_args()
+    if a.stats:
+        return stats(a)
+    from nerf_meets_mlx_amd.dataset import synthetic
+    from nerf_meets_mlx_amd.engine.ngp import NGPTrainer
+    from nerf_meets_mlx_amd.engine.occupancy import UPDATE_EVERY, WARMUP
+    from nerf_meets_mlx_amd.rendering import ray
+
+    dev = torch.device("cuda", 0)
+    torch.cuda.set_device(dev)
+    H = W = a.hw
+    imgs, poses, rposes, hwf, K = synthetic.make_dataset(H, W, 5, seed=0, device=dev)
+    rrays = ray.gen_rays(H, W, K, rposes[40][:3, :4], 2.0, 6.0, torch.arange(a.render_rays, device=dev, dtype=torch.int64))
+    arms = {}
+    for name in a.arms.split(","):
+        steps = int(name[len("march"):]) if name.startswith("march") else None
+        tr = NGPTrainer(imgs[:4], poses[:4], K, N_rand=a.n_rand, n_depth_samples=64, seed=4, device=dev, chunk=a.render_rays,
+                        occupancy_grid=(name != "off"), march_steps=steps)
+        arms[name] = {"tr": tr, "train": [], "render": [], "spr_train": [], "spr_render": []}
+
+    def step(arm, timed):
+        tr = arm["tr"]
+        e = [torch.cuda.Event(enable_timing=True) for _ in range(3)]
+        e[0].record()
+        tr.train_step()
+        e[1].record()
+        if timed and tr.march_steps is not None:
+            arm["spr_train"].append(tr.last_march[1] / float(a.n_rand))
+        elif timed and tr.grid is not None:
+            arm["spr_train"].append(tr._field._sel[0].numel() / float(a.n_rand))
+        tr.render_rays(rrays)
+        e[2].record()
+        if timed:
+            arm["train"].append((e[0], e[1]))
+            arm["render"].append((e[1], e[2]))
+
+    warm = WARMUP + UPDATE_EVERY
+    for arm in arms.values():
+        for _ in range(warm):
+            step(arm, False)
+    torch.cuda.synchronize()
+    for arm in arms.values():
+        if arm["tr"].grid is not None:
+            arm["tr"].grid.timing = []
+    t_start = time.time()
+    it = warm
+    while it < a.iters:
+        n = min(a.block, a.iters - it)
+        for arm in arms.values():
+            for _ in range(n):
+                step(arm, True)
+            torch.cuda.synchronize()
+        it += n
+    wall = time.time() - t_start
+
+    lines = []
+    for name, arm in arms.items():
+        tr = arm["tr"]
+        nsteps = len(arm["train"])
+        line = {"tool": "ngp_march", "arm": name, "march_steps": tr.march_steps, "hw": H, "n_rand": a.n_rand,
+                "render_rays": a.render_rays, "seed": 4, "iters": tr.it, "timed_steps": nsteps, "block": a.block,
+                "train_ms_per_step": _ms(arm["train"]), "render_ms_per_chunk": _ms(arm["render"]),
+                "device": torch.cuda.get_device_name(dev)}
+        g = tr.grid
+        if g is None:
+            line.update({"samples_per_ray_train": 64.0, "samples_per_ray_render": 64.0})
+        else:
+            timing, g.timing = g.timing, None
+            if tr.march_steps is not None:
+                offs, _, _, Kr = g.march(rrays, 0.5, use_bits=True)
+                marches = [(x, y) for k, x, y in (t for t in timing if len(t) == 3) if k == "march"]
+                line["march_ms_per_step"] = sum(x.elapsed_time(y) for x, y in marches) / nsteps     # train + render marches
+                line["step_world"] = g.step_world
+            else:
+                from nerf_meets_mlx_amd import sampling
+                Kr = g.cull(rrays, sampling.sample_coarse(rrays, 64))[4]
+            syncs = [t[1] for t in timing if t[0] == "sync_host"]
+            line.update({"samples_per_ray_train": float(np.mean(arm["spr_train"])),
+                         "samples_per_ray_train_min_max": [min(arm["spr_train"]), max(arm["spr_train"])],
+                         "samples_per_ray_render": Kr / float(a.render_rays), "occupied_cells": g.occupied_fraction(),
+                         "host_sync_ms_per_step": float(np.sum(syncs)) / nsteps})
+        lines.append(line)
+    if not a.no_psnr:
+        gt = imgs[4]
+        white = float(-10.0 * torch.log10(((1.0 - gt.double()) ** 2).mean()))
+        for name, line in zip(arms, lines):
+            tr = arms[name]["tr"]
+            line["psnr_heldout"] = tr.psnr(poses[4][:3, :4].numpy(), gt)
+            line["psnr_all_white_frame"] = white
+            rgb = tr.render_frame(poses[4][:3, :4].numpy()) if hasattr(tr, "render_frame") else None
+            if rgb is not None:
+                rgb = torch.as_tensor(rgb)
+                line["heldout_frame_white_fraction"] = float((rgb.reshape(-1, 3) > 0.999).all(-1).double().mean())
+    summary = {"tool": "ngp_march", "summary": True, "wall_s_timed": wall}
+    by = dict(zip(arms, lines))
+    for ref in ("off", "cull"):
+        for name in arms:
+            if name.startswith("march") and ref in by:
+                summary[f"{name}_train_vs_{ref}"] = by[name]["train_ms_per_step"] / by[ref]["train_ms_per_step"]
+                summary[f"{name}_render_vs_{ref}"] = by[name]["render_ms_per_chunk"] / by[ref]["render_ms_per_chunk"]
+    lines.append(summary)
+    for line in lines:
+        print(json.dumps(line), flush=True)
+    if a.out:
+        with open(a.out, "a") as fh:
+            for line in lines:
+                fh.write(json.dumps(line) + "\n")
+
+
+def stats(a):
+    """Average device time per launch of the march / packed-compositing kernels in a rocprofv3 --kernel-trace database."""
+    import re
+    import sqlite3
+    db = sqlite3.connect(a.stats)
+    for name, calls, avg_ns in db.execute("select name, count(*), avg(end - start) from kernels group by name"):
+        m = re.search(r"(occ_march_\w+|occ_cull_scan_kernel|occ_merge_exp_kernel|composite_packed_\w+|nerf_ngp\w*|ngp\w*fused\w*|"
+                      r"hashgrid\w*|composite_train_kernel|occ_cull_\w+)", name)
+        if m:
+            print(json.dumps({"kernel": m.group(1), "calls": calls, "avg_us": round(avg_ns * 1e-3, 2)}))
+
+
+if __name__ == "__main__":
+    main()
