@@ -5,6 +5,9 @@
                                                              its N ranks itself before touching the GPU)
     python bench.py ... --dump-outputs DIR                  (also writes the last timed step's outputs as DIR/<name>.npy:
                                                              same arguments, same inputs -- two builds compare array for array)
+    python bench.py ... --full                              (also runs every leg beside the headline measurement: the other
+                                                             precisions, sizes and the frame / ngp legs of the N = 1 line, and
+                                                             the CPU baseline -- minutes; a plain run does only the headline)
 
 One "step" = one training iteration of the reference loop (entrypoints/__test_nerf.py:200-305:
 N_rand rays, coarse 64 + fine 64+128 samples, forward + backward + Adam for both networks) PLUS
@@ -15,12 +18,12 @@ rays shard across ranks with no data-path collective except the gradient all-red
 
 The headline step runs at `--precision 22`: the reference's float32 TOLERANCE on the 16-bit matrix pipe (every float32 GEMM
 operand as a hi + lo pair of 16-bit numbers, three MFMAs per product, fp32 accumulate: csrc/mlp_s16.hip for training,
-csrc/mlp22.hip for rendering), held to the same fixture tolerances as the float32 kernels.  The N = 1 line also carries the
-same step with literal float32 operands on the fp32 MFMA (`fp32`, `reference_precision_value`) and in the declared
-reduced-precision bf16 mode (`bf16`).
+csrc/mlp22.hip for rendering), held to the same fixture tolerances as the float32 kernels.  With --full, the N = 1 line also
+carries the same step with literal float32 operands on the fp32 MFMA (`fp32`, `reference_precision_value`) and in the
+declared reduced-precision bf16 mode (`bf16`).
 
 The JSON line also carries `roofline` for the dominant kernel (the fused MLP forward of the render
-fine pass, MFMA-bound, timed with events on the launch stream inside the timed region) and
+fine pass, MFMA-bound, timed with events on the launch stream inside the timed region) and, with --full,
 `cpu_baseline` (the CPU oracle = op-for-op restatement of the reference, timed on this box's host
 cores on a bounded sample of the same workload; rank 0, N=1 only).
 """
@@ -65,8 +68,12 @@ def main():
     ap.add_argument("--render-rays", type=int, default=32768, help="rays per render chunk per GPU per step")
     ap.add_argument("--hw", type=int, default=800)
     ap.add_argument("--train-images", type=int, default=4)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extra-legs", action="store_true", help="skip the sustained / fp32 / ngp legs of the default N=1 line")
+    ap.add_argument("--full", action="store_true",
+                    help="also run everything beside the headline measurement: the sustained / lego-batch / other-precision / frame / "
+                         "ngp legs (N = 1) and the cpu_baseline (rank 0, N = 1); a plain run sets up, warms up, times --steps, "
+                         "writes --dump-outputs and prints the line")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the cpu_baseline")
+    ap.add_argument("--no-extra-legs", action="store_true", help="with --full: skip the sustained / fp32 / ngp legs of the N=1 line")
     ap.add_argument("--sustain-seconds", type=float, default=10.0, help="length of the sustained bf16 leg")
     ap.add_argument("--fp32-steps", type=int, default=20, help="timed steps of the fp32 (reference arithmetic) leg")
     ap.add_argument("--cpu-seconds", type=float, default=30.0, help="time box of the cpu_baseline render leg (the training leg runs "
@@ -321,7 +328,7 @@ def main():
                          mfma_busy_cycles_frac=busy, mfma_busy_source=busy_src,
                          algorithmic_bytes=args.render_rays * (n_fine * 20 + 44)),
     }
-    if world == 1 and not args.no_extra_legs:
+    if world == 1 and args.full and not args.no_extra_legs:
         # ---- sustained: the same headline step for >= args.sustain_seconds (the burst above is ~2 s of a power-limited
         # kernel; this is what the chip holds, and long enough for an SMI sampler to see the GPU busy)
         n_sus = max(args.steps, int(np.ceil(args.sustain_seconds * 1.05 / (dt / args.steps))))
@@ -368,7 +375,7 @@ def main():
         line["ngp"] = {k: ngp_line[k] for k in ("value", "unit", "ms_per_step", "steps", "train_rays_per_s_per_gpu",
                                                 "render_rays_per_s_per_gpu", "roofline", "dtype", "loss_coarse", "bf16") if k in ngp_line}
         line["ngp"]["workload"] = ngp_line["config"]["workload"]
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline:
         line["cpu_baseline"] = cpu_baseline(args)
     if rank == 0:
         print(json.dumps(line), flush=True)
@@ -425,9 +432,9 @@ def _latest_profile(pattern):
 
 
 def bench_ngp(args, imgs, poses, rposes, K, rank, world, dev):
-    line = measure_ngp(args, imgs, poses, rposes, K, rank, world, dev, extra_bf16=(world == 1 and not args.no_extra_legs),
+    line = measure_ngp(args, imgs, poses, rposes, K, rank, world, dev, extra_bf16=(world == 1 and args.full and not args.no_extra_legs),
                        dump_dir=args.dump_outputs)
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline:
         line["cpu_baseline"] = cpu_baseline_ngp(args)
     if rank == 0:
         print(json.dumps(line), flush=True)

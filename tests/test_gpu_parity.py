@@ -883,14 +883,16 @@ def test_autograd_wrappers_match_explicit_backward():
 
 
 # ------------------------------------------------------------------------------ bench.py contract
-@pytest.mark.parametrize("extra", [[], ["--config", "ngp"], ["--n-importance", "0"]])
+@pytest.mark.parametrize("extra", [["--full"], ["--full", "--config", "ngp"], ["--full", "--n-importance", "0"], [], ["--config", "ngp"]])
 def test_bench_prints_one_contract_json_line(extra):
     """bench.py (small sizes, child process): exactly one JSON line with the driver's keys, a roofline object, finite
-    positive numbers; the cpu_baseline leg is exercised by the default run only (>= 10 s of CPU work)."""
+    positive numbers; the legs beside the headline come with --full only (the cpu_baseline leg, >= 10 s of CPU work, is
+    exercised by the full-size run only), and a plain run carries none of them."""
     import json, os, subprocess, sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    full = "--full" in extra
     cmd = [sys.executable, os.path.join(root, "bench.py"), "--steps", "2", "--warmup", "1", "--n-rand", "256",
-           "--render-rays", "2048", "--hw", "64", "--no-cpu-baseline", "--sustain-seconds", "1", "--fp32-steps", "2"] + extra
+           "--render-rays", "2048", "--hw", "64"] + (["--no-cpu-baseline", "--sustain-seconds", "1", "--fp32-steps", "2"] if full else []) + extra
     out = subprocess.run(cmd, capture_output=True, text=True, timeout=600, cwd=root)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [l for l in out.stdout.splitlines() if l.strip()]
@@ -908,8 +910,11 @@ def test_bench_prints_one_contract_json_line(extra):
         assert k in r, k
     assert r["bound"] in ("hbm", "mfma") and r["achieved"] > 0 and abs(r["frac"] - r["achieved"] / r["peak"]) < 1e-9
     assert abs(d["value"] - (256 + 2048) * 2 / (d["ms_per_step"] * 2e-3)) < 1e-6 * d["value"]
-    if "--config" not in extra:
-        # the legs the default N = 1 line carries beside the contract keys (round 3): the same step sustained, at the
+    if not full:
+        for leg in ("sustained", "lego_batch", "fp32", "bf16", "f32tol", "reference_precision_value", "frame", "ngp", "cpu_baseline"):
+            assert leg not in d, leg
+    elif "--config" not in extra:
+        # the legs the --full N = 1 line carries beside the contract keys (round 3): the same step sustained, at the
         # reference's arithmetic (fp32 models), at lego.txt's batch, and the configs[4] step
         for leg in ("sustained", "fp32", "lego_batch", "ngp"):
             assert leg in d and d[leg]["value"] > 0 and np.isfinite(d[leg]["value"]), leg
@@ -921,7 +926,7 @@ def test_bench_prints_one_contract_json_line(extra):
         assert not d["dtype"].startswith("f32") and d["operand_significand_bits"] == {"render": 22, "train": 16}
         assert d["ngp"]["dtype"].startswith("split16") and d["ngp"]["bf16"]["value"] > 0 and d["ngp"]["bf16"]["dtype"].startswith("bf16")
     if "--config" in extra:
-        assert d["config"]["precision"] == 22 and d["dtype"].startswith("split16") and d["bf16"]["value"] > 0
+        assert d["config"]["precision"] == 22 and d["dtype"].startswith("split16") and (not full or d["bf16"]["value"] > 0)
     assert d["rank_ms_per_step"] is None                                   # N = 1
 
 

@@ -147,7 +147,7 @@ def test_bench_and_entry_scripts_parse_without_a_gpu():
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--help"], capture_output=True, text=True, timeout=300)
     assert out.returncode == 0, out.stderr[-1000:]
-    for flag in ("--gpus", "--steps", "--warmup", "--config", "--n-importance"):
+    for flag in ("--gpus", "--steps", "--warmup", "--config", "--n-importance", "--full"):
         assert flag in out.stdout
     out = subprocess.run([sys.executable, "-c", "import __graft_entry__ as g; assert callable(g.build) and callable(g.smoke)"],
                          capture_output=True, text=True, timeout=300, cwd=root)

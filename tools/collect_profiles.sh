@@ -6,10 +6,10 @@ R=${1:-r05}
 O=$GRAFT_REPO_ROOT/gpurun_out/$R
 mkdir -p $O
 cd $GRAFT_REPO_ROOT
-python bench.py > $O/bench_n1.json.log 2> $O/bench_n1.err      # the default line: burst + sustained + fp32 + ngp legs + cpu_baseline
+python bench.py --full > $O/bench_n1.json.log 2> $O/bench_n1.err      # the full line: burst + sustained + fp32 + ngp legs + cpu_baseline
 python bench.py --steps 10 --warmup 3 --hw 400 --n-importance 0 --precision 16 --no-cpu-baseline --no-extra-legs > $O/bench_cfg1_400_coarse_only.json.log 2>> $O/bench_n1.err
 python bench.py --steps 10 --warmup 3 --n-rand 1024 --no-cpu-baseline --no-extra-legs > $O/bench_nrand1024.json.log 2>> $O/bench_n1.err
-python bench.py --steps 10 --warmup 3 --config ngp > $O/bench_configs4_ngp.json.log 2>> $O/bench_n1.err
+python bench.py --steps 10 --warmup 3 --config ngp --full > $O/bench_configs4_ngp.json.log 2>> $O/bench_n1.err
 python tools/bench_kernels.py > $O/hbm_kernels.csv 2>> $O/bench_n1.err
 python tools/probe_fp32.py > $O/fp32_mode.csv 2>> $O/bench_n1.err
 echo bench done
