@@ -408,6 +408,52 @@ int nerf_composite_packed_mse_backward(const float* raw, const int64_t* offsets,
                                        int white_bkgd, const float* target, float grad_scale, float* loss_out, float* rgb,
                                        float* d_raw, void* stream);
 
+/* ---------------------------------------------------------------- early ray termination (no reference counterpart)
+ * The round renderer of the march (inference only): a ray stops once its transmittance falls below min_transmittance = eps
+ * (0 <= eps < 1), and the steps behind that point are neither marched nor queried.  Additive: NERF_ABI_VERSION stays 3.
+ *   samples   a ray visits exactly the candidates of nerf_occ_march_count / _write ("ray march" above): the same depths (z_k uses
+ *             the absolute candidate index k), the same keep decisions, the same march_steps cap, in depth order.  A round resumes
+ *             at the ray's saved k and kept count.  With eps = 0 the (ray, depth) samples are those of the one-shot march, bit for bit.
+ *   fold      serial over a ray's samples in depth order, float32, one rounding per operation, in this order:
+ *               T = expf(-carry); if T < eps the ray terminates: this sample and every later one are skipped (NaN T does not);
+ *               x = expf(raw[3]) * step_world, alpha = 1 - expf(-x), w = alpha * T;
+ *               r += w raw[0], g += w raw[1], b += w raw[2], acc += w, depth += w z, carry += x, samples += 1.
+ *             At the end rgb += (1 - acc) with a white background.  A ray without samples gets the background, acc = depth = 0.
+ *             Because the fold is serial per ray, a ray's outputs depend on that ray and the field only: round sizes, chunking and
+ *             ray order change no bit.  Against the one-shot renderer (packed compositing above): |d rgb| <= T_stop max|c - bg|
+ *             < eps per channel, 0 <= acc_full - acc_eps < eps (up to float rounding), samples_eps <= samples_full.
+ *             sigma = +inf gives finite outputs (and terminates the ray when eps > 0); a NaN raw makes only its own ray NaN.
+ * State (caller memory, reused between calls): istate int32 [B, 4] = (next candidate k, kept count, samples folded, flags),
+ * fstate float [B, 6] = (carry, r, g, b, acc, depth), a list of live ray ids (int32, ascending, distinct), B < 2^31.  A call:
+ *   nerf_ert_init                  zero state, live = 0 .. B - 1, A = B.
+ *   per round, with m >= 1 slots per live ray:
+ *     nerf_ert_march_count         per live entry up to m further kept samples (none for a terminated ray); totals int64 [2] =
+ *                                  (K samples of the round, A' rays still live: those that took m and have candidates left).
+ *     (one read of totals to the host; K = 0 ends the call)
+ *     nerf_ert_march_write         same arguments and workspace: offsets int64 [A + 1] (entry i owns [offsets[i], offsets[i + 1]),
+ *                                  offsets[A] = K), rows_out [K, 11], z_out [K] (the layout of the march above), live_out [A']
+ *                                  (must not be live), and the resume point in istate.  No atomics: bit-reproducible.
+ *     query of the K rows           (nerf_ngp_query_fused_h, B = K, n = 1)
+ *     nerf_ert_fold                the fold over entry i's segment for ray live[i], raw [K, 4] (16-byte aligned), z [K].  A ray
+ *                                  whose next sample would terminate is flagged now (same outputs, no further march).
+ *   nerf_ert_finish                rgb [B, 3], and (each may be NULL) acc [B], depth [B], samples int32 [B].
+ * workspace: nerf_ert_march_workspace_bytes(B) bytes, kept from the count to the write of a round.  A live id outside [0, B)
+ * takes no sample and is not folded; offsets outside [0, K] or decreasing make that ray's outputs NaN.                      */
+#define NERF_ERT_TERMINATED 1
+int64_t nerf_ert_march_workspace_bytes(int64_t B);
+int nerf_ert_init(int64_t B, int32_t* istate, float* fstate, int32_t* live, void* stream);
+int nerf_ert_march_count(const float* rays, int64_t B, const float* jitter, float jitter_const, const uint32_t* bits, int log2_res,
+                         float pos_scale, float pos_offset, float step_world, int march_steps, const int32_t* live, int64_t A,
+                         const int32_t* istate, int max_new, void* workspace, int64_t* totals, void* stream);
+int nerf_ert_march_write(const float* rays, int64_t B, const float* jitter, float jitter_const, const uint32_t* bits, int log2_res,
+                         float pos_scale, float pos_offset, float step_world, int march_steps, const int32_t* live, int64_t A,
+                         int32_t* istate, int max_new, void* workspace, int64_t* offsets, int32_t* live_out, float* rows_out,
+                         float* z_out, void* stream);
+int nerf_ert_fold(const float* raw, const float* z, const int64_t* offsets, const int32_t* live, int64_t A, int64_t B, int64_t K,
+                  float step_world, float min_transmittance, int32_t* istate, float* fstate, void* stream);
+int nerf_ert_finish(const int32_t* istate, const float* fstate, int64_t B, int white_bkgd, float* rgb, float* acc, float* depth,
+                    int32_t* samples, void* stream);
+
 /* ---------------------------------------------------------------- fused renderer (a14 / a18)
  * replaces: rendering/render.py:164-241 render_rays_eval (coarse pass, importance sampling, sort, second pass)
  * as ONE call that enqueues the fixed kernel sequence on `stream`: nerf_sample_coarse -> nerf_query_fused ->

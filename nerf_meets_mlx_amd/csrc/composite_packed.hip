@@ -139,6 +139,79 @@ __global__ void __launch_bounds__(256) composite_packed_train_kernel(const float
   if (threadIdx.x == 0 && loss) atomicAdd(loss, (part[0] + part[1] + part[2] + part[3]) * inv);
 }
 
+// ---- round renderer with early ray termination (include/nerf_hip.h "early ray termination").  Per ray: istate int32 [4] = (next
+// candidate k, kept count, samples folded, flags), fstate float [6] = (carry, r, g, b, acc, depth).
+// init: 40 B of state and 4 B of live id written per ray, nothing read.
+__global__ void ert_init_kernel(int64_t B, int* __restrict__ istate, float* __restrict__ fstate, int* __restrict__ live) {
+  for (int64_t b = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; b < B; b += (int64_t)gridDim.x * blockDim.x) {
+#pragma unroll
+    for (int q = 0; q < 4; ++q) istate[4 * b + q] = 0;
+#pragma unroll
+    for (int q = 0; q < 6; ++q) fstate[6 * b + q] = 0.0f;
+    live[b] = (int)b;
+  }
+}
+
+// fold: one lane per live entry, serial over its segment in the header's operation order (so a ray's result does not depend on how
+// its samples were split into rounds).  Per entry 4 + 16 + 16 + 24 B read, 40 B written; per sample 20 B read.  The lanes of a wave
+// walk segments of different lengths: latency-bound, like the march.
+__global__ void ert_fold_kernel(const float* __restrict__ raw, const float* __restrict__ z, const int64_t* __restrict__ offsets,
+                                const int* __restrict__ live, int64_t A, int64_t B, int64_t K, float step, float eps,
+                                int* __restrict__ istate, float* __restrict__ fstate) {
+  for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < A; i += (int64_t)gridDim.x * blockDim.x) {
+    const int b = live[i];
+    if (b < 0 || b >= B) continue;
+    int flags = istate[4 * b + 3];
+    if (flags & NERF_ERT_TERMINATED) continue;
+    const int64_t s0 = offsets[i], s1 = offsets[i + 1];
+    float* fs = fstate + 6 * (int64_t)b;
+    float carry = fs[0], r = fs[1], g = fs[2], bl = fs[3], acc = fs[4], depth = fs[5];
+    int samples = istate[4 * b + 2];
+    if (!(s0 >= 0 && s0 <= s1 && s1 <= K)) {                     // bad offsets: the ray's outputs NaN, no access
+      carry = r = g = bl = acc = depth = __builtin_nanf("");
+      flags |= NERF_ERT_TERMINATED;
+    } else {
+      for (int64_t k = s0; k < s1; ++k) {
+        const float T = expf(-carry);
+        if (T < eps) {
+          flags |= NERF_ERT_TERMINATED;
+          break;
+        }
+        const float4 rv = *reinterpret_cast<const float4*>(raw + 4 * k);
+        const float x = expf(rv.w) * step;
+        const float alpha = 1.0f - expf(-x);
+        const float w = alpha * T;
+        r += w * rv.x; g += w * rv.y; bl += w * rv.z;
+        acc += w;
+        depth += w * z[k];
+        carry += x;
+        ++samples;
+      }
+      // the test of the next sample, made now: the march of the next round then skips the ray (the same outputs, fewer steps)
+      if (expf(-carry) < eps) flags |= NERF_ERT_TERMINATED;
+    }
+    fs[0] = carry; fs[1] = r; fs[2] = g; fs[3] = bl; fs[4] = acc; fs[5] = depth;
+    istate[4 * b + 2] = samples;
+    istate[4 * b + 3] = flags;
+  }
+}
+
+// finish: 40 B of state read, 24 B written per ray.
+__global__ void ert_finish_kernel(const int* __restrict__ istate, const float* __restrict__ fstate, int64_t B, int white,
+                                  float* __restrict__ rgb, float* __restrict__ acc, float* __restrict__ depth,
+                                  int* __restrict__ samples) {
+  for (int64_t b = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; b < B; b += (int64_t)gridDim.x * blockDim.x) {
+    const float* fs = fstate + 6 * b;
+    float r = fs[1], g = fs[2], bl = fs[3];
+    const float a = fs[4];
+    if (white) { r = r + (1.0f - a); g = g + (1.0f - a); bl = bl + (1.0f - a); }
+    rgb[3 * b] = r; rgb[3 * b + 1] = g; rgb[3 * b + 2] = bl;
+    if (acc) acc[b] = a;
+    if (depth) depth[b] = fs[5];
+    if (samples) samples[b] = istate[4 * b + 2];
+  }
+}
+
 bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
 }  // namespace
@@ -172,4 +245,35 @@ extern "C" int nerf_composite_packed_mse_backward(const float* raw, const int64_
   hipLaunchKernelGGL(composite_packed_train_kernel, g, b, 0, as_stream(stream), raw, offsets, B, K, step_world, white_bkgd, target,
                      grad_scale, loss_out, rgb, d_raw);
   return check_launch("nerf_composite_packed_mse_backward");
+}
+
+extern "C" int nerf_ert_init(int64_t B, int* istate, float* fstate, int* live, void* stream) {
+  NERF_REQUIRE(B >= 0 && B < (1ll << 31), NERF_E_SHAPE, "nerf_ert_init: need 0 <= B < 2^31");
+  if (B == 0) return NERF_OK;
+  NERF_REQUIRE(istate && fstate && live, NERF_E_NULL, "nerf_ert_init: NULL pointer");
+  hipLaunchKernelGGL(ert_init_kernel, dim3(grid_for(B, 256)), dim3(256), 0, as_stream(stream), B, istate, fstate, live);
+  return check_launch("nerf_ert_init");
+}
+
+extern "C" int nerf_ert_fold(const float* raw, const float* z, const int64_t* offsets, const int* live, int64_t A, int64_t B,
+                             int64_t K, float step_world, float min_transmittance, int* istate, float* fstate, void* stream) {
+  NERF_REQUIRE(B >= 0 && B < (1ll << 31) && A >= 0 && A <= B && K >= 0, NERF_E_SHAPE, "nerf_ert_fold: bad sizes");
+  NERF_REQUIRE(step_world > 0.0f, NERF_E_SHAPE, "nerf_ert_fold: step_world must be > 0");
+  NERF_REQUIRE(min_transmittance >= 0.0f && min_transmittance < 1.0f, NERF_E_SHAPE, "nerf_ert_fold: need 0 <= min_transmittance < 1");
+  if (A == 0) return NERF_OK;
+  NERF_REQUIRE(offsets && live && istate && fstate && (K == 0 || (raw && z)), NERF_E_NULL, "nerf_ert_fold: NULL pointer");
+  NERF_REQUIRE(K == 0 || aligned16(raw), NERF_E_SHAPE, "nerf_ert_fold: raw must be 16-byte aligned");
+  hipLaunchKernelGGL(ert_fold_kernel, dim3(grid_for(A, 256)), dim3(256), 0, as_stream(stream), raw, z, offsets, live, A, B, K,
+                     step_world, min_transmittance, istate, fstate);
+  return check_launch("nerf_ert_fold");
+}
+
+extern "C" int nerf_ert_finish(const int* istate, const float* fstate, int64_t B, int white_bkgd, float* rgb, float* acc,
+                               float* depth, int* samples, void* stream) {
+  NERF_REQUIRE(B >= 0 && B < (1ll << 31), NERF_E_SHAPE, "nerf_ert_finish: need 0 <= B < 2^31");
+  if (B == 0) return NERF_OK;
+  NERF_REQUIRE(istate && fstate && rgb, NERF_E_NULL, "nerf_ert_finish: NULL pointer");
+  hipLaunchKernelGGL(ert_finish_kernel, dim3(grid_for(B, 256)), dim3(256), 0, as_stream(stream), istate, fstate, B, white_bkgd, rgb,
+                     acc, depth, samples);
+  return check_launch("nerf_ert_finish");
 }

@@ -271,12 +271,21 @@ __device__ __forceinline__ MarchRay march_setup(const float* __restrict__ rr, fl
   return m;
 }
 
-// Visits the kept samples of one ray in depth order: fn(k_kept, z).  Returns the number kept (<= march_steps).
-template <class F>
+// Visits the kept samples of one ray in depth order: fn(i, z) for the i-th sample of this call.  The walk starts at candidate
+// k_start with kept_start samples already kept (0 and 0: the whole march), and stops after max_new samples, at the cap of
+// march_steps kept in all, or where the walk ends.  k_end = the candidate to resume at, or m.kmax when the ray has no candidate
+// left.  Returns the number of samples visited.  RESUME = false (the one-shot march: 0, 0, march_steps) compiles the resume
+// bookkeeping away, leaving k_end unset.
+template <bool RESUME, class F>
 __device__ __forceinline__ int march_ray(const float* __restrict__ rr, const MarchRay& m, const uint32_t* __restrict__ bits,
-                                         int log2R, float pos_scale, float pos_offset, int march_steps, F&& fn) {
-  int kept = 0;
-  for (int k0 = 0; k0 < m.kmax; k0 += MARCH_GROUP) {
+                                         int log2R, float pos_scale, float pos_offset, int march_steps, int k_start, int kept_start,
+                                         int max_new, int& k_end, F&& fn) {
+  int kept = kept_start;
+  if (RESUME) {
+    k_end = m.kmax;
+    if (kept >= march_steps) return 0;
+  }
+  for (int k0 = k_start; k0 < m.kmax; k0 += MARCH_GROUP) {
     float zs[MARCH_GROUP];
     int64_t cs[MARCH_GROUP];
     uint32_t ws[MARCH_GROUP];
@@ -289,14 +298,18 @@ __device__ __forceinline__ int march_ray(const float* __restrict__ rr, const Mar
     for (int g = 0; g < MARCH_GROUP; ++g) ws[g] = (bits && cs[g] >= 0) ? bits[cs[g] >> 5] : 0xFFFFFFFFu;
 #pragma unroll
     for (int g = 0; g < MARCH_GROUP; ++g) {
-      if (k0 + g >= m.kmax || !(zs[g] < m.t1)) return kept;
+      if (k0 + g >= m.kmax || !(zs[g] < m.t1)) return kept - kept_start;
       if (cs[g] >= 0 && ((ws[g] >> (cs[g] & 31)) & 1u)) {
-        fn(kept, zs[g]);
-        if (++kept == march_steps) return kept;
+        fn(kept - kept_start, zs[g]);
+        if (++kept == march_steps) return kept - kept_start;
+        if (RESUME && kept - kept_start == max_new) {
+          k_end = k0 + g + 1;
+          return max_new;
+        }
       }
     }
   }
-  return kept;
+  return kept - kept_start;
 }
 
 // ---- march, pass 1: per ray the number of kept samples (int32 to the workspace), per workgroup of 256 rays their sum (int64).
@@ -314,7 +327,8 @@ __global__ void __launch_bounds__(MARCH_BLOCK) occ_march_count_kernel(const floa
   if (b < B) {
     const float* rr = rays + b * NERF_RAY_STRIDE;
     const MarchRay m = march_setup(rr, jitter ? jitter[b] : jitter_const, pos_scale, pos_offset, step_world, march_steps);
-    n = march_ray(rr, m, bits, log2R, pos_scale, pos_offset, march_steps, [](int, float) {});
+    int k_end;
+    n = march_ray<false>(rr, m, bits, log2R, pos_scale, pos_offset, march_steps, 0, 0, march_steps, k_end, [](int, float) {});
     ray_counts[b] = n;
   }
   int t = n;
@@ -356,13 +370,113 @@ __global__ void __launch_bounds__(MARCH_BLOCK) occ_march_write_kernel(const floa
   if (n == 0) return;
   const float* rr = rays + b * NERF_RAY_STRIDE;
   const MarchRay m = march_setup(rr, jitter ? jitter[b] : jitter_const, pos_scale, pos_offset, step_world, march_steps);
-  march_ray(rr, m, bits, log2R, pos_scale, pos_offset, march_steps, [&](int k, float zv) {
+  int k_end;
+  march_ray<false>(rr, m, bits, log2R, pos_scale, pos_offset, march_steps, 0, 0, march_steps, k_end, [&](int k, float zv) {
     const int64_t o = base + k;
     z_out[o] = zv;
     float* dst = rows_out + o * NERF_RAY_STRIDE;
 #pragma unroll
     for (int q = 0; q < NERF_RAY_STRIDE; ++q) dst[q] = rr[q];
   });
+}
+
+// ---- resumed march of the round renderer (include/nerf_hip.h "early ray termination").  One lane per entry i of the live list;
+// the ray b = live[i] resumes at its saved candidate and kept count (istate[b] = k, kept, samples, flags) and takes up to max_new
+// further samples.  It stays live when it took max_new and has candidates left; a ray the fold has terminated takes none.
+// Per entry: 4 B of live id, 16 B of state, the row (32 B used) and jitter, one bitfield word per candidate; entry = 2 n + live.
+__device__ __forceinline__ int resume_ray(const float* __restrict__ rays, int64_t B, const float* __restrict__ jitter,
+                                          float jitter_const, const uint32_t* __restrict__ bits, int log2R, float pos_scale,
+                                          float pos_offset, float step_world, int march_steps, int b, const int* __restrict__ istate,
+                                          int max_new, bool& more, int& k_end, float* __restrict__ rows_out,
+                                          float* __restrict__ z_out, int64_t base) {
+  more = false;
+  k_end = 0;
+  if (b < 0 || b >= B || (istate[4 * b + 3] & NERF_ERT_TERMINATED)) return 0;
+  const float* rr = rays + (int64_t)b * NERF_RAY_STRIDE;
+  const MarchRay m = march_setup(rr, jitter ? jitter[b] : jitter_const, pos_scale, pos_offset, step_world, march_steps);
+  const int n = march_ray<true>(rr, m, bits, log2R, pos_scale, pos_offset, march_steps, istate[4 * b], istate[4 * b + 1], max_new, k_end,
+                          [&](int k, float zv) {
+                            if (!rows_out) return;
+                            const int64_t o = base + k;
+                            z_out[o] = zv;
+                            float* dst = rows_out + o * NERF_RAY_STRIDE;
+#pragma unroll
+                            for (int q = 0; q < NERF_RAY_STRIDE; ++q) dst[q] = rr[q];
+                          });
+  more = k_end < m.kmax;
+  return n;
+}
+
+__global__ void __launch_bounds__(MARCH_BLOCK) ert_march_count_kernel(const float* __restrict__ rays, int64_t B,
+                                                                      const float* __restrict__ jitter, float jitter_const,
+                                                                      const uint32_t* __restrict__ bits, int log2R, float pos_scale,
+                                                                      float pos_offset, float step_world, int march_steps,
+                                                                      const int* __restrict__ live, int64_t A,
+                                                                      const int* __restrict__ istate, int max_new,
+                                                                      int* __restrict__ entry, int64_t* __restrict__ blk, int64_t nblk) {
+  __shared__ int sh[2][MARCH_BLOCK / 64];
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  const int64_t i = (int64_t)blockIdx.x * MARCH_BLOCK + threadIdx.x;
+  int n = 0;
+  bool more = false;
+  if (i < A) {
+    int k_end;
+    n = resume_ray(rays, B, jitter, jitter_const, bits, log2R, pos_scale, pos_offset, step_world, march_steps, live[i], istate,
+                   max_new, more, k_end, nullptr, nullptr, 0);
+    entry[i] = 2 * n + (more ? 1 : 0);
+  }
+  int t = n, l = more ? 1 : 0;
+  for (int o = 32; o > 0; o >>= 1) {
+    t += __shfl_xor(t, o, WAVE);
+    l += __shfl_xor(l, o, WAVE);
+  }
+  if (lane == 0) { sh[0][w] = t; sh[1][w] = l; }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    int64_t s = 0, a = 0;
+    for (int k = 0; k < MARCH_BLOCK / 64; ++k) { s += sh[0][k]; a += sh[1][k]; }
+    blk[blockIdx.x] = s;
+    blk[nblk + blockIdx.x] = a;
+  }
+}
+
+// offsets[i] = the entry's sample offset, offsets[A] = K, the live rays in order to live_out, then the same walk again writing the
+// rows (44 B) and depths (4 B), and the ray's resume point (8 B of state).  Reads as the count, plus 4 B of entry per ray.
+__global__ void __launch_bounds__(MARCH_BLOCK) ert_march_write_kernel(const float* __restrict__ rays, int64_t B,
+                                                                      const float* __restrict__ jitter, float jitter_const,
+                                                                      const uint32_t* __restrict__ bits, int log2R, float pos_scale,
+                                                                      float pos_offset, float step_world, int march_steps,
+                                                                      const int* __restrict__ live, int64_t A, int* __restrict__ istate,
+                                                                      int max_new, const int* __restrict__ entry,
+                                                                      const int64_t* __restrict__ blk, int64_t nblk,
+                                                                      int64_t* __restrict__ offsets, int* __restrict__ live_out,
+                                                                      float* __restrict__ rows_out, float* __restrict__ z_out) {
+  __shared__ int sh[2][MARCH_BLOCK / 64];
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  const int64_t i = (int64_t)blockIdx.x * MARCH_BLOCK + threadIdx.x;
+  const int e = i < A ? entry[i] : 0;
+  const int n = e >> 1, l = e & 1;
+  int x = n, y = l;                                             // inclusive wave scans of the counts and the live flags
+  for (int o = 1; o < WAVE; o <<= 1) {
+    const int t = __shfl_up(x, o, WAVE), u = __shfl_up(y, o, WAVE);
+    if (lane >= o) { x += t; y += u; }
+  }
+  if (lane == 63) { sh[0][w] = x; sh[1][w] = y; }
+  __syncthreads();
+  int64_t base = blk[blockIdx.x] + (x - n), lbase = blk[nblk + blockIdx.x] + (y - l);
+  for (int k = 0; k < w; ++k) { base += sh[0][k]; lbase += sh[1][k]; }
+  if (i >= A) return;
+  offsets[i] = base;
+  if (i == A - 1) offsets[A] = base + n;
+  const int b = live[i];
+  if (l) live_out[lbase] = b;
+  if (n == 0) return;
+  bool more;
+  int k_end;
+  resume_ray(rays, B, jitter, jitter_const, bits, log2R, pos_scale, pos_offset, step_world, march_steps, b, istate, max_new, more,
+             k_end, rows_out, z_out, base);
+  istate[4 * b] = k_end;
+  istate[4 * b + 1] += n;
 }
 
 // ---- dst[idx[i], :] = src[i, :]: 8 + 4 C B read, 4 C B written per row (C = 4: one float4 each way).
@@ -547,4 +661,71 @@ extern "C" int nerf_scatter_rows(const float* src, const int64_t* idx, int64_t n
   hipLaunchKernelGGL(scatter_rows_kernel, dim3(grid_for(items, 256)), dim3(256), 0, as_stream(stream), src, idx, n,
                      channels, (int)vec, dst, n_dst);
   return check_launch("nerf_scatter_rows");
+}
+
+extern "C" int64_t nerf_ert_march_workspace_bytes(int64_t B) {
+  if (B < 0) return -1;
+  const int64_t nblk = (B + MARCH_BLOCK - 1) / MARCH_BLOCK;
+  return 2 * nblk * (int64_t)sizeof(int64_t) + ((B * (int64_t)sizeof(int) + 7) / 8) * 8;
+}
+
+static int ert_march_check(const char* who, const float* rays, int64_t B, int log2_res, float pos_scale, float step_world,
+                           int march_steps, const int* live, int64_t A, const int* istate, int max_new, void* workspace,
+                           int64_t* out) {
+  int rc = march_check(who, rays, B, log2_res, pos_scale, step_world, march_steps, workspace, out);
+  if (rc) return rc;
+  NERF_REQUIRE(B < (1ll << 31) && A >= 0 && A <= B, NERF_E_SHAPE, "%s: need 0 <= A <= B < 2^31", who);
+  NERF_REQUIRE(max_new >= 1, NERF_E_SHAPE, "%s: need max_new >= 1 (got %d)", who, max_new);
+  NERF_REQUIRE(A == 0 || (live && istate), NERF_E_NULL, "%s: NULL live / istate", who);
+  return NERF_OK;
+}
+
+extern "C" int nerf_ert_march_count(const float* rays, int64_t B, const float* jitter, float jitter_const, const uint32_t* bits,
+                                    int log2_res, float pos_scale, float pos_offset, float step_world, int march_steps,
+                                    const int* live, int64_t A, const int* istate, int max_new, void* workspace, int64_t* totals,
+                                    void* stream) {
+  int rc = ert_march_check("nerf_ert_march_count", rays, B, log2_res, pos_scale, step_world, march_steps, live, A, istate,
+                           max_new, workspace, totals);
+  if (rc) return rc;
+  if (A == 0) {
+    hipError_t e = hipMemsetAsync(totals, 0, 2 * sizeof(int64_t), as_stream(stream));
+    if (e != hipSuccess) return fail(NERF_E_HIP, "nerf_ert_march_count: %s", hipGetErrorString(e));
+    return NERF_OK;
+  }
+  const int64_t nblk = (A + MARCH_BLOCK - 1) / MARCH_BLOCK;
+  int64_t* blk = static_cast<int64_t*>(workspace);             // [2][nblk] for A <= B: the layout of the workspace of B
+  int* entry = reinterpret_cast<int*>(blk + 2 * ((B + MARCH_BLOCK - 1) / MARCH_BLOCK));
+  hipLaunchKernelGGL(ert_march_count_kernel, dim3((unsigned)nblk), dim3(MARCH_BLOCK), 0, as_stream(stream), rays, B, jitter,
+                     jitter_const, bits, log2_res, pos_scale, pos_offset, step_world, march_steps, live, A, istate, max_new, entry,
+                     blk, nblk);
+  rc = check_launch("nerf_ert_march_count (count)");
+  if (rc) return rc;
+  hipLaunchKernelGGL(occ_cull_scan_kernel, dim3(1), dim3(1024), 0, as_stream(stream), blk, nblk, totals);
+  rc = check_launch("nerf_ert_march_count (scan of the samples)");
+  if (rc) return rc;
+  hipLaunchKernelGGL(occ_cull_scan_kernel, dim3(1), dim3(1024), 0, as_stream(stream), blk + nblk, nblk, totals + 1);
+  return check_launch("nerf_ert_march_count (scan of the live rays)");
+}
+
+extern "C" int nerf_ert_march_write(const float* rays, int64_t B, const float* jitter, float jitter_const, const uint32_t* bits,
+                                    int log2_res, float pos_scale, float pos_offset, float step_world, int march_steps,
+                                    const int* live, int64_t A, int* istate, int max_new, void* workspace, int64_t* offsets,
+                                    int* live_out, float* rows_out, float* z_out, void* stream) {
+  int rc = ert_march_check("nerf_ert_march_write", rays, B, log2_res, pos_scale, step_world, march_steps, live, A, istate, max_new,
+                           workspace, offsets);
+  if (rc) return rc;
+  if (A == 0) {
+    hipError_t e = hipMemsetAsync(offsets, 0, sizeof(int64_t), as_stream(stream));
+    if (e != hipSuccess) return fail(NERF_E_HIP, "nerf_ert_march_write: %s", hipGetErrorString(e));
+    return NERF_OK;
+  }
+  NERF_REQUIRE(live_out && rows_out && z_out, NERF_E_NULL, "nerf_ert_march_write: NULL live_out / rows_out / z_out");
+  NERF_REQUIRE(live_out != live, NERF_E_SHAPE, "nerf_ert_march_write: live_out must not be live");
+  const int64_t nblk = (A + MARCH_BLOCK - 1) / MARCH_BLOCK;
+  const int64_t* blk = static_cast<const int64_t*>(workspace);
+  const int* entry = reinterpret_cast<const int*>(blk + 2 * ((B + MARCH_BLOCK - 1) / MARCH_BLOCK));
+  hipLaunchKernelGGL(ert_march_write_kernel, dim3((unsigned)nblk), dim3(MARCH_BLOCK), 0, as_stream(stream), rays, B, jitter,
+                     jitter_const, bits, log2_res, pos_scale, pos_offset, step_world, march_steps, live, A, istate, max_new, entry,
+                     blk, nblk, offsets, live_out, rows_out, z_out);
+  return check_launch("nerf_ert_march_write");
 }

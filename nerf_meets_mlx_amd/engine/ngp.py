@@ -253,6 +253,13 @@ class HashNeRF:
         return grads, e.grad
 
 
+def _cat(outs, aux: bool):
+    """torch.cat of the per-chunk outputs of render_rays (dicts of tensors when aux)."""
+    if not aux:
+        return torch.cat(outs, 0)
+    return {k: torch.cat([o[k] for o in outs], 0) for k in outs[0]}
+
+
 class NGPTrainer(Trainer):
     """Coarse-only training / rendering loop on a HashNeRF (one network, `n_depth_samples` stratified-grid samples per
     ray, no importance pass).  Rays shard across ranks; MLP and table gradients are sum-all-reduced before Adam."""
@@ -260,7 +267,8 @@ class NGPTrainer(Trainer):
     def __init__(self, images, poses, K, near: float = 2.0, far: float = 6.0, N_rand: int = 4096,
                  n_depth_samples: int = 64, lrate: float = 5e-4, lrate_decay: int = 500, white_bkgd: bool = True,
                  seed: int = 0, device="cuda", chunk: int = 1024 * 32, table_sync: str = "shard", precision: int = 22,
-                 occupancy_grid: bool = False, march_steps: Optional[int] = None, **hash_kw):
+                 occupancy_grid: bool = False, march_steps: Optional[int] = None, min_transmittance: Optional[float] = None,
+                 **hash_kw):
         """occupancy_grid: empty-space skipping (engine/occupancy.py): the grid is updated every UPDATE_EVERY iterations from the
         start; from iteration WARMUP on, training and rendering evaluate only the samples in occupied cells.  Off by default.
         march_steps (needs occupancy_grid=True and a scene box; 1 ... 1024; None: the n_depth_samples stratified grid): the
@@ -274,7 +282,13 @@ class NGPTrainer(Trainer):
                 raise ValueError("NGPTrainer: march_steps needs occupancy_grid=True (the march samples the grid)")
             if hash_kw.get("bound", 1.5) is None:
                 raise ValueError("NGPTrainer: march_steps needs a scene box (HashNeRF(bound=None) has none)")
+        if min_transmittance is not None:
+            from .occupancy import check_min_transmittance
+            min_transmittance = check_min_transmittance(min_transmittance)
+            if march_steps is None:
+                raise ValueError("NGPTrainer: min_transmittance needs march_steps (early termination is a mode of the march)")
         self.march_steps = march_steps
+        self.min_transmittance = min_transmittance
         super().__init__(images, poses, K, near=near, far=far, N_rand=N_rand, n_depth_samples=n_depth_samples,
                          N_importance=0, lrate=lrate, lrate_decay=lrate_decay, white_bkgd=white_bkgd, ref_quirks=True,
                          seed=seed, device=device, chunk=chunk, precision=precision)
@@ -421,23 +435,33 @@ class NGPTrainer(Trainer):
         loss, d_raw, _ = render.composite_packed_mse_backward(raw, offsets, B, self.grid.step_world, target, self.white_bkgd)
         return loss, d_raw
 
-    def render_rays(self, rays: torch.Tensor, u=None):
+    def render_rays(self, rays: torch.Tensor, u=None, aux: bool = False):
+        """rgb [B, 3] of rays [B, 11], `chunk` rays per call.  aux=True: {"rgb", "acc" [B], "depth" [B]} and, in march mode,
+        "samples" [B] int32 (the samples composited per ray)."""
         outs = []
         self._join_comm()
         if self.march_steps is not None:                     # march mode: jitter 0.5, the bitfield once the warm-up is over
             from .occupancy import WARMUP
+            use_bits = self.it >= WARMUP
             for s in range(0, rays.shape[0], self.chunk):
                 r = N.f32(rays[s:s + self.chunk])
-                offsets, rows, z, K = self.grid.march(r, 0.5, use_bits=self.it >= WARMUP)
+                if self.min_transmittance is not None:
+                    o = self.grid.render_ert(self._field, r, 0.5, self.min_transmittance, self.white_bkgd, use_bits=use_bits)
+                    outs.append(o if aux else o["rgb"])
+                    continue
+                offsets, rows, z, K = self.grid.march(r, 0.5, use_bits=use_bits)
                 raw = self._field.query_packed(rows, z)
-                outs.append(render.composite_packed(raw, z, offsets, r.shape[0], self.grid.step_world, self.white_bkgd)[0])
-            return torch.cat(outs, 0)
+                rgb, acc, depth = render.composite_packed(raw, z, offsets, r.shape[0], self.grid.step_world, self.white_bkgd)
+                outs.append({"rgb": rgb, "acc": acc, "depth": depth,
+                             "samples": (offsets[1:] - offsets[:-1]).to(torch.int32)} if aux else rgb)
+            return _cat(outs, aux)
         for s in range(0, rays.shape[0], self.chunk):
             r = rays[s:s + self.chunk]
             z = sampling.sample_coarse(r, self.n)
             raw = self._field.query(r, z, grid=self._grid_for_step())
-            outs.append(render.composite(raw, z, r, 0.0, self.white_bkgd, need_weights=False)[0])
-        return torch.cat(outs, 0)
+            rgb, _, acc, _, depth = render.composite(raw, z, r, 0.0, self.white_bkgd, need_weights=False)
+            outs.append({"rgb": rgb, "acc": acc, "depth": depth} if aux else rgb)
+        return _cat(outs, aux)
 
     def _grid_for_step(self, update: bool = False):
         """The occupancy grid to cull with at this iteration (None: every sample runs); update=True (the training step) first

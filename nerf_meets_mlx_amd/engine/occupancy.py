@@ -19,8 +19,13 @@ march"): the grid also samples.  `march()` walks each ray 
 step_world = sqrt(3) / S * 2 bound and keeps the steps in occupied cells (nerf_occ_march_count, one read of K, nerf_occ_march_write).
 The density of that field is trunc_exp(raw sigma), so the merge uses exp (nerf_occ_merge_ex) and the threshold cap is
 THRESHOLD / step_world.
+
+Early ray termination (`render_ert`, `NGPTrainer(..., min_transmittance=eps)`; include/nerf_hip.h "early ray termination",
+DESIGN.md section 13): rendering only.  Rays are marched in rounds of a few more samples each, queried, folded serially into a
+per-ray state, and dropped once their transmittance is below eps or their walk has ended.  One read of (K, live rays) per round.
 """
 import math
+import numbers
 import time
 from typing import Dict, Optional, Tuple
 
@@ -46,6 +51,16 @@ def check_march_steps(march_steps) -> int:
     if isinstance(march_steps, bool) or not isinstance(march_steps, int) or not 1 <= march_steps <= MAX_MARCH_STEPS:
         raise ValueError(f"march_steps must be an int in [1, {MAX_MARCH_STEPS}], got {march_steps!r}")
     return march_steps
+
+
+def check_min_transmittance(min_transmittance) -> Optional[float]:
+    """None, or min_transmittance as a float in [0, 1); ValueError otherwise (NaN included)."""
+    if min_transmittance is None:
+        return None
+    if isinstance(min_transmittance, bool) or not isinstance(min_transmittance, numbers.Real) \
+            or not 0.0 <= float(min_transmittance) < 1.0:
+        raise ValueError(f"min_transmittance must be None or a number in [0, 1), got {min_transmittance!r}")
+    return float(min_transmittance)
 
 
 def march_step_world(march_steps: int, bound: float) -> float:
@@ -84,6 +99,7 @@ class OccupancyGrid:
         self._pts = None                    # (rays [CHUNK, 11], z [CHUNK, 1]) of the update
         self._cull = {}                     # capacity buffers of the cull, grown on demand
         self.timing = None                  # tools/ngp_occupancy.py: list receiving (name, start event, end event)
+        self.last_ert = None                # render_ert: {"rounds", "marched"} of the last call
         self.reset()
 
     # ------------------------------------------------------------------ state
@@ -248,6 +264,82 @@ class OccupancyGrid:
             e1.record()
             self.timing.append(("march", e0, e1))
         return offsets, rows, z, K
+
+
+    # ------------------------------------------------------------------ early ray termination
+    def _ert_state(self, B: int):
+        """(istate [B, 4] int32, fstate [B, 6] float32, live [B] int32, live [B] int32): the round renderer's state buffers."""
+        n = max(1, B)
+        return (self._grow("ert_istate", 4 * n, torch.int32)[:4 * B].view(B, 4),
+                self._grow("ert_fstate", 6 * n, torch.float32)[:6 * B].view(B, 6),
+                self._grow("ert_live0", n, torch.int32)[:B], self._grow("ert_live1", n, torch.int32)[:B])
+
+    def _jitter(self, jitter, B):
+        if torch.is_tensor(jitter):
+            jit = N.f32(jitter).reshape(-1)
+            assert jit.numel() == B, "march: one jitter per ray"
+            return jit, 0.0
+        return None, float(jitter)
+
+    def march_resume(self, rays, jitter, istate, live, A: int, max_new: int, live_out, use_bits: bool = True):
+        """One round of the resumed march (`nerf_ert_march_count`, one read of (K, A') to the host, `nerf_ert_march_write`): each
+        of the A rays live[:A] takes up to max_new further kept samples from its saved (k, kept) = istate[b, 0:2], which is
+        advanced.  (offsets [A + 1], rows [K, 11], z [K], K, A'), the A' rays still live in live_out[:A'].  The outputs are views
+        of buffers the next round overwrites."""
+        rays = N.f32(rays)
+        B = rays.shape[0]
+        jit, jc = self._jitter(jitter, B)
+        ws = self._grow("ert_ws", max(1, N.lib().nerf_ert_march_workspace_bytes(B)), torch.uint8)
+        tot = self._grow("ert_totals", 2, torch.int64)
+        offsets = self._grow("ert_offsets", A + 1, torch.int64)
+        head = (N.ptr(rays) if B else None, B, N.ptr(jit) if jit is not None and B else None, jc,
+                N.ptr(self.bits) if use_bits else None, LOG2_RES, self.pos_scale, self.pos_offset, self.step_world, self.march_steps,
+                N.ptr(live) if A else None, A)
+        N.check(N.lib().nerf_ert_march_count(*head, N.ptr(istate) if A else None, int(max_new), N.ptr(ws), N.ptr(tot), N.stream()))
+        if self.timing is not None:
+            t0 = time.perf_counter()
+        K, A_next = tot.tolist()                             # the one host read of a round
+        if self.timing is not None:
+            self.timing.append(("sync_host", (time.perf_counter() - t0) * 1e3))
+        rows = self._grow("ert_rows", max(1, K) * 11, torch.float32)
+        zb = self._grow("ert_z", max(1, K), torch.float32)
+        if K:
+            N.check(N.lib().nerf_ert_march_write(*head, N.ptr(istate), int(max_new), N.ptr(ws), N.ptr(offsets), N.ptr(live_out),
+                                                 N.ptr(rows), N.ptr(zb), N.stream()))
+        return offsets, rows[:K * 11].view(K, 11), zb[:K], K, A_next
+
+    def render_ert(self, field, rays, jitter, min_transmittance: float, white_bkgd: bool = False, use_bits: bool = True,
+                   slots: int = 8) -> Dict[str, torch.Tensor]:
+        """Render rays [B, 11] through `field` (a HashNeRF) with early ray termination at T < min_transmittance (march mode only).
+        Round r gives each live ray m_r = min(march_steps, max(1, slots B // A)) slots, A the rays live before it (slots is a
+        tuning knob: by the fold's order no output depends on it).  {"rgb" [B, 3], "acc" [B], "depth" [B], "samples" [B] int32};
+        self.last_ert = {"rounds", "marched"} of the call (marched: samples queried, terminated rays' surplus included)."""
+        if self.march_steps is None:
+            raise ValueError("OccupancyGrid.render_ert: the grid was built without march_steps")
+        eps = check_min_transmittance(min_transmittance)
+        if eps is None:
+            raise ValueError("OccupancyGrid.render_ert: min_transmittance is required")
+        if int(slots) < 1:
+            raise ValueError(f"OccupancyGrid.render_ert: slots must be >= 1, got {slots!r}")
+        from ..rendering import render
+        rays = N.f32(rays)
+        B = rays.shape[0]
+        istate, fstate, la, lb = self._ert_state(B)
+        render.ert_init(istate, fstate, la, B)
+        A, rounds, total = B, 0, 0
+        while A > 0:
+            m = min(self.march_steps, max(1, int(slots) * B // A))
+            offsets, rows, z, K, A_next = self.march_resume(rays, jitter, istate, la, A, m, lb, use_bits=use_bits)
+            if K == 0:
+                break
+            raw = field.query_packed(rows, z)
+            render.ert_fold(raw, z, offsets, la, A, istate, fstate, self.step_world, eps)
+            A, la, lb = A_next, lb, la
+            rounds += 1
+            total += K
+        rgb, acc, depth, samples = render.ert_finish(istate, fstate, white_bkgd)
+        self.last_ert = {"rounds": rounds, "marched": total}
+        return {"rgb": rgb, "acc": acc, "depth": depth, "samples": samples}
 
 
 def scatter_rows(src: torch.Tensor, idx: torch.Tensor, dst: torch.Tensor):

@@ -89,6 +89,36 @@ def composite_packed_mse_backward(raw, offsets, B: int, step_world: float, targe
     return loss, d_raw, rgb
 
 
+def ert_init(istate, fstate, live, B: int):
+    """Zero the round renderer's state of B rays (istate int32 [B, 4], fstate float32 [B, 6]) and set live = 0 .. B - 1
+    (`nerf_ert_init`, include/nerf_hip.h "early ray termination")."""
+    N.check(N.lib().nerf_ert_init(B, N.ptr(istate), N.ptr(fstate), N.ptr(live), N.stream()))
+
+
+def ert_fold(raw, z, offsets, live, A: int, istate, fstate, step_world: float, min_transmittance: float):
+    """Fold one round's packed samples into the state (`nerf_ert_fold`): entry i < A owns raw [K, 4] / z [K] rows
+    [offsets[i], offsets[i + 1]) of ray live[i]; serial per ray, stopping where T = exp(-carry) < min_transmittance."""
+    raw = N.f32(raw).reshape(-1, 4)
+    z = N.f32(z).reshape(-1)
+    K = raw.shape[0]
+    B = istate.shape[0]
+    N.check(N.lib().nerf_ert_fold(N.ptr(raw) if K else None, N.ptr(z) if K else None, N.ptr(offsets), N.ptr(live), A, B, K,
+                                  float(step_world), float(min_transmittance), N.ptr(istate), N.ptr(fstate), N.stream()))
+
+
+def ert_finish(istate, fstate, white_bkgd=False):
+    """(rgb [B, 3], acc [B], depth [B], samples [B] int32) of the round renderer's state (`nerf_ert_finish`)."""
+    B = istate.shape[0]
+    dev = istate.device
+    rgb = torch.empty(B, 3, dtype=torch.float32, device=dev)
+    acc = torch.empty(B, dtype=torch.float32, device=dev)
+    depth = torch.empty(B, dtype=torch.float32, device=dev)
+    samples = torch.empty(B, dtype=torch.int32, device=dev)
+    N.check(N.lib().nerf_ert_finish(N.ptr(istate), N.ptr(fstate), B, int(bool(white_bkgd)), N.ptr(rgb), N.ptr(acc), N.ptr(depth),
+                                    N.ptr(samples), N.stream()))
+    return rgb, acc, depth, samples
+
+
 _WS = {}
 
 

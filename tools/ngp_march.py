@@ -5,11 +5,14 @@ N_rand 4096, seed 4, one 32 768-ray render chunk per step), in ONE process:
     python tools/ngp_march.py --out profiles/ngp_march.jsonl                  (GPU; a few minutes)
 
 Arms: "off" (64 stratified samples, no grid), "cull" (64 samples, grid cull) and "march<S>" (the march of
-section 12 with march_steps = S; default 1024 and 512).  Every arm is trained past the grid's warm-up, then the arms alternate
+section 12 with march_steps = S; default 1024 and 512), and "march<S>_ert" (the same march with early ray termination at
+min_transmittance --eps, section 13; trained exactly as "march<S>").  Every arm is trained past the grid's warm-up, then the arms alternate
 timed blocks of --block steps until --iters; each step is timed with device events (train step, render chunk).  Per arm: train
 ms / step, render ms / chunk, samples per ray in training and rendering, for march arms the device time of the march (count +
 scan + write) and the host time of the K read-back; after --iters the held-out PSNR on a fifth view, next to the PSNR of an
-all-white frame of that view.  One JSON line per arm and a summary line.
+all-white frame of that view.  Early-termination arms also report the ms per full held-out frame at the render chunk and at
+one whole-frame chunk, samples per ray, rounds and host-read ms per call, and the max |d| per pixel against the same trainer's
+one-shot render.  One JSON line per arm and a summary line.
 
     python tools/ngp_march.py --stats <rocprofv3 results .db>
 
@@ -31,6 +34,56 @@ def _ms(pairs):
     return float(np.mean([a.elapsed_time(b) for a, b in pairs])) if pairs else 0.0
 
 
+def _p10_p90(pairs):
+    v = [a.elapsed_time(b) for a, b in pairs]
+    return [float(np.percentile(v, 10)), float(np.percentile(v, 90))] if v else None
+
+
+def _frame_ms(tr, c2w, chunk, reps):
+    """Device ms of full-frame renders (mean, [min, max]) at `chunk` rays per call."""
+    old, tr.chunk = tr.chunk, chunk
+    tr.render_frame(c2w)                                      # warm: capacity buffers at this chunk size
+    v = []
+    for _ in range(reps):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        tr.render_frame(c2w)
+        e1.record()
+        torch.cuda.synchronize()
+        v.append(e0.elapsed_time(e1))
+    tr.chunk = old
+    return float(np.mean(v)), [min(v), max(v)]
+
+
+def _ert_extra(a, tr, rrays, c2w, npix):
+    """Early-termination arm: frame times (chunk and whole frame), against the same trainer's one-shot march (eps None) too,
+    samples per ray, rounds and host-read ms per call, max |d| per pixel of the held-out frame against the one-shot render."""
+    g, eps = tr.grid, tr.min_transmittance
+    out = {}
+    g.timing = []
+    o = tr.render_rays(rrays, aux=True)
+    torch.cuda.synchronize()
+    out["rounds_per_call"] = g.last_ert["rounds"]
+    out["host_read_ms_per_call"] = float(np.sum([t[1] for t in g.timing if t[0] == "sync_host"]))
+    out["samples_per_ray_render"] = float(o["samples"].double().mean())
+    out["marched_per_ray_render"] = g.last_ert["marched"] / float(rrays.shape[0])
+    g.timing = None
+    for tag, chunk in (("chunk", a.render_rays), ("whole_frame", npix)):
+        out[f"frame_ms_{tag}"], out[f"frame_ms_{tag}_min_max"] = _frame_ms(tr, c2w, chunk, a.frame_reps)
+        out["rounds_per_whole_frame"] = g.last_ert["rounds"]
+    img = tr.render_frame(c2w)
+    tr.min_transmittance = None
+    try:
+        full = tr.render_frame(c2w)
+        out["samples_per_ray_render_one_shot"] = float(tr.render_rays(rrays, aux=True)["samples"].double().mean())
+        for tag, chunk in (("chunk", a.render_rays), ("whole_frame", npix)):
+            out[f"one_shot_frame_ms_{tag}"], out[f"one_shot_frame_ms_{tag}_min_max"] = _frame_ms(tr, c2w, chunk, a.frame_reps)
+    finally:
+        tr.min_transmittance = eps
+    out["max_abs_diff_vs_one_shot"] = float((img - full).abs().max())
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--iters", type=int, default=2000)
@@ -40,6 +93,8 @@ def main():
     ap.add_argument("--render-rays", type=int, default=32768)
     ap.add_argument("--no-psnr", action="store_true")
     ap.add_argument("--arms", default="off,cull,march1024,march512")
+    ap.add_argument("--eps", type=float, default=1e-4, help="min_transmittance of the *_ert arms")
+    ap.add_argument("--frame-reps", type=int, default=5, help="timed full-frame renders per chunk size (ert arms)")
     ap.add_argument("--out", default=None, help="append the JSON lines to this file")
     ap.add_argument("--stats", default=None, help="summarise a rocprofv3 --kernel-trace results database instead of measuring")
     a = ap.parse_args()
@@ -57,9 +112,10 @@ def main():
     rrays = ray.gen_rays(H, W, K, rposes[40][:3, :4], 2.0, 6.0, torch.arange(a.render_rays, device=dev, dtype=torch.int64))
     arms = {}
     for name in a.arms.split(","):
-        steps = int(name[len("march"):]) if name.startswith("march") else None
+        ert = name.endswith("_ert")
+        steps = int(name[len("march"):len(name) - (4 if ert else 0)]) if name.startswith("march") else None
         tr = NGPTrainer(imgs[:4], poses[:4], K, N_rand=a.n_rand, n_depth_samples=64, seed=4, device=dev, chunk=a.render_rays,
-                        occupancy_grid=(name != "off"), march_steps=steps)
+                        occupancy_grid=(name != "off"), march_steps=steps, min_transmittance=a.eps if ert else None)
         arms[name] = {"tr": tr, "train": [], "render": [], "spr_train": [], "spr_render": []}
 
     def step(arm, timed):
@@ -104,6 +160,7 @@ def main():
         line = {"tool": "ngp_march", "arm": name, "march_steps": tr.march_steps, "hw": H, "n_rand": a.n_rand,
                 "render_rays": a.render_rays, "seed": 4, "iters": tr.it, "timed_steps": nsteps, "block": a.block,
                 "train_ms_per_step": _ms(arm["train"]), "render_ms_per_chunk": _ms(arm["render"]),
+                "render_ms_per_chunk_p10_p90": _p10_p90(arm["render"]), "min_transmittance": tr.min_transmittance,
                 "device": torch.cuda.get_device_name(dev)}
         g = tr.grid
         if g is None:
@@ -123,6 +180,8 @@ def main():
                          "samples_per_ray_train_min_max": [min(arm["spr_train"]), max(arm["spr_train"])],
                          "samples_per_ray_render": Kr / float(a.render_rays), "occupied_cells": g.occupied_fraction(),
                          "host_sync_ms_per_step": float(np.sum(syncs)) / nsteps})
+        if tr.min_transmittance is not None:
+            line.update(_ert_extra(a, tr, rrays, poses[4][:3, :4].numpy(), H * W))
         lines.append(line)
     if not a.no_psnr:
         gt = imgs[4]
@@ -157,7 +216,7 @@ def stats(a):
     import sqlite3
     db = sqlite3.connect(a.stats)
     for name, calls, avg_ns in db.execute("select name, count(*), avg(end - start) from kernels group by name"):
-        m = re.search(r"(occ_march_\w+|occ_cull_scan_kernel|occ_merge_exp_kernel|composite_packed_\w+|nerf_ngp\w*|ngp\w*fused\w*|"
+        m = re.search(r"(occ_march_\w+|ert_\w+|occ_cull_scan_kernel|occ_merge_exp_kernel|composite_packed_\w+|nerf_ngp\w*|ngp\w*fused\w*|"
                       r"hashgrid\w*|composite_train_kernel|occ_cull_\w+)", name)
         if m:
             print(json.dumps({"kernel": m.group(1), "calls": calls, "avg_us": round(avg_ns * 1e-3, 2)}))
