@@ -153,11 +153,13 @@ int nerf_hashgrid_backward_rays(const float* rays, const float* z, int64_t B, in
  * all-reduce of their slice of d_tables on another stream), and optionally DETERMINISTIC: fixed_point = 1 makes d_tables
  * an int64 [L,T,F] array of 2^-52 fixed-point accumulators added with integer atomics (associative: the result does not
  * depend on the order the memory side serves the requests; float atomics do).  nerf_adam_step_ex consumes either form.
- * Range of the fixed-point form: an addend with |v| > 256 saturates to +-1.5 x 2^60 units (+-384: outside the window below with
- * 128 to spare, so the ordinary addends of the same entry cannot bring the sum back inside), a NaN / Inf addend adds 2^61
- * units, and nerf_adam_step_ex reads every accumulator outside (-2^60, 2^60) units -- saturated, poisoned, or a per-entry sum
- * beyond +-256, also after a cross-rank sum -- as a NaN gradient: a diverged run surfaces as NaN parameters, as with float
- * atomics.  (Two saturated addends of opposite sign on one entry cancel, like two float gradients of +-1e9 would.) */
+ * Range of the fixed-point form: an addend with |v| > 256 saturates to +-1.5 x 2^60 units (+-384), a NaN / Inf addend adds
+ * 2^61 units, and nerf_adam_step_ex reads an accumulator as a NaN gradient exactly when it lies outside the open window
+ * (-2^60, 2^60) units (+-256).  The int64 accumulators wrap: an entry with k saturated addends of sign s, j NaN / Inf addends
+ * and an ordinary sum g (units of 2^-52, also summed over ranks) holds k s 1.5 2^60 + j 2^61 + g 2^52 mod 2^64 and reads FINITE
+ * whenever that lands inside the window -- e.g. k = 11, 21 or 0 (mod 32) with small g (+128 + g, -128 + g, g), j = 0 (mod 8),
+ * or g within 256 of a multiple of +-4096.  Otherwise a diverged run surfaces as NaN parameters, as with float atomics.
+ * (Two saturated addends of opposite sign on one entry cancel, like two float gradients of +-1e9 would.) */
 int nerf_hashgrid_backward_ex(const float* x, int64_t M, const float* d_out, int L, int log2_T, int F,
                               const int* resolutions_host, int level_lo, int level_hi, int fixed_point, void* d_tables,
                               void* stream);

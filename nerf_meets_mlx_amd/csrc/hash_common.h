@@ -35,15 +35,18 @@ struct ResTab { float res[32]; };
 // fixed-point unit of the deterministic table-gradient accumulators (int64): 2^-52
 #define NERF_HASH_FIX_SHIFT 52
 #define NERF_HASH_FIX_SCALE 4503599627370496.0
-// Representable range and failure behaviour (include/nerf_hip.h, nerf_hashgrid_backward_rays_ex): a finite addend with
-// |v| > 256 saturates to +-(2^60 + 2^59) units -- half a window width OUTSIDE the window, so that the ordinary addends of the same
-// entry (up to +-128 in sum; a coarse-level entry collects hundreds) cannot pull the sum back inside it (round 5 saturated to
-// +-2^60 exactly: -2^60 plus one small positive addend read as a finite -256) --, a NaN / Inf addend adds 2^61 units;
-// nerf_adam_step_ex turns every
-// accumulator outside (-2^60, 2^60) -- a saturated addend, a poisoned one, or a per-entry sum that large, also after the
-// cross-rank all-reduce -- back into a NaN gradient, so that a diverged run surfaces as NaN parameters exactly as it does
-// with float atomics instead of continuing on wrapped integers.  (k poisoned addends on one entry sum to k 2^61 mod 2^64,
-// which is inside the window only for k = 0 mod 8: a diverged batch poisons thousands of entries, 7 of 8 of them stay NaN.)
+// Range and failure behaviour (include/nerf_hip.h, nerf_hashgrid_backward_ex): an addend with |v| <= 256 is rounded to the
+// nearest unit (ties to even); a finite addend with |v| > 256 saturates to +-1.5 x 2^60 units (half a window width outside the
+// window below, so that one saturated addend plus ordinary ones of less than 128 in sum stays outside it); a NaN / Inf addend
+// adds 2^61 units.  nerf_adam_step_ex reads an accumulator a as a NaN gradient exactly when a is outside the OPEN window
+// (-2^60, 2^60) units, i.e. |gradient| >= 256.  The accumulators are int64 and wrap, so this is NOT a sticky poison flag: an
+// entry with k saturated addends of sign s, j NaN / Inf addends and an ordinary (rounded) sum g holds
+//     a = k s 1.5 2^60 + j 2^61 + g 2^52   (mod 2^64)
+// -- also after the cross-rank all-reduce, which adds the ranks' accumulators -- and reads as the finite gradient
+// a 2^-52 whenever that lands inside the window.  Examples: k = 11, 21 or 0 (mod 32) with |g| small (k = 11: +128 + g,
+// k = 21: -128 + g, k = 32: g); j = 0 (mod 8), e.g. a NaN upstream gradient at a lattice point, whose 8 corners collapse to ONE
+// entry (8 x 2^61 = 0 mod 2^64); an ordinary sum within 256 of a multiple of +-4096.  Every other case surfaces as NaN
+// parameters, as float atomics would.  (A sticky per-entry flag would close the gap: DESIGN.md, open items.)
 #define NERF_HASH_FIX_LIMIT 256.0f
 #define NERF_HASH_FIX_SATURATED ((1ll << 60) + (1ll << 59))
 __device__ __forceinline__ long long nerf_to_fixed(float v) {
