@@ -456,6 +456,43 @@ int nerf_ert_fold(const float* raw, const float* z, const int64_t* offsets, cons
 int nerf_ert_finish(const int32_t* istate, const float* fstate, int64_t B, int white_bkgd, float* rgb, float* acc, float* depth,
                     int32_t* samples, void* stream);
 
+/* ---------------------------------------------------------------- mesh extraction (no reference counterpart)
+ * Marching cubes over a density volume sampled from a trained field (Instant-NGP's mesh export).  Additive: NERF_ABI_VERSION
+ * stays 3.  Float32, one rounding per operation, in this order (tests/_mesh_ref.py reproduces every output):
+ *   lattice   box lo[3] < hi[3] (host floats, finite), resolution R (2 <= R <= NERF_MESH_MAX_RES), h_a = (hi_a - lo_a) / R
+ *             computed on the host.  Point (i, j, k), 0 <= i, j, k < R, has linear index i + R (j + R k) and position
+ *             p_a = lo_a + ((float)i_a + 0.5f) * h_a: cell centres, strictly inside the box.  vol: float32 [R, R, R] = vol[k, j, i].
+ *   density   (the caller; engine/mesh.py) sigma = act(raw[..., 3]) of the field's fused query on the rows of nerf_mesh_points
+ *             (o = p, the rest 0, z = 0), act = exp for the march mode's field, relu otherwise, NaN counting as 0: exactly
+ *             nerf_occ_merge_ex(slice, raw, n, decay = 0, act) on a zeroed slice.
+ *   inside    v > iso (iso finite): NaN and v == iso are outside.
+ *   cells     cell (i, j, k), all < R - 1, has corner c in [0, 8) at (i + (c & 1), j + ((c >> 1) & 1), k + (c >> 2)); its case is
+ *             sum inside(c) << c, its triangles the case's row of csrc/mc_table.h (generated by csrc/gen_mc_table.py from the face
+ *             rule stated there: neighbouring cells agree on every shared face, so the mesh is closed and consistently oriented
+ *             wherever the surface stays inside the box).  Winding: (b - a) x (c - a) points from inside to outside.
+ *   vertices  the edge from point q to q + e_a is owned by q; a crossing edge (one end inside) carries exactly one vertex, so the
+ *             mesh is welded by construction.  Order: by owner linear index, then axis x, y, z.  Position: p(q), and along a
+ *             t = (iso - v_q) / (v_{q+e_a} - v_q) (correctly rounded), t = 0.5 if t is NaN, else t clamped to [0, 1];
+ *             x_a = p_a(q) + t * h_a.  V <= 3 R^3 < 2^31: vertex ids are int32.
+ *   normals   g = the volume's gradient at the two ends, (v[+1] - v[-1]) / (2 h_a), one-sided (v[1] - v[0]) / h_a at the border,
+ *             interpolated as g0 + t (g1 - g0); |g| = sqrt((gx gx + gy gy) + gz gz); n = -(g / |g|), or 0 where |g| is 0 or not
+ *             finite (divisions and the square root correctly rounded).
+ *   faces     int32 [F, 3] vertex ids, by cell linear index, then table order.
+ * Calls: nerf_mesh_count writes totals int64 [2] = (V, F) (the caller reads them once and sizes the outputs); then, with the
+ * same volume, iso and workspace, nerf_mesh_write_vertices (verts [V, 3], normals [V, 3], and when color_rows != NULL the colour
+ * query rows [V, 11] = [x, -n, near = far = 0, viewdirs = -n]) and nerf_mesh_write_faces (faces [F, 3]).  V = 0 exactly when
+ * F = 0; then the write calls launch nothing.  Count -> block scan -> write, no atomics: bit-reproducible.
+ * workspace: nerf_mesh_workspace_bytes(R) bytes, kept from the count to the faces (the per-point vertex bases live there).
+ * Argument errors (R, box, non-finite iso, V / F out of range, NULL) return before any launch.                              */
+#define NERF_MESH_MAX_RES 512
+int64_t nerf_mesh_workspace_bytes(int res);
+int nerf_mesh_points(int res, const float* lo_host, const float* hi_host, int64_t p0, int64_t count, float* rays_out, float* z_out,
+                     void* stream);
+int nerf_mesh_count(const float* vol, int res, float iso, void* workspace, int64_t* totals, void* stream);
+int nerf_mesh_write_vertices(const float* vol, int res, float iso, const float* lo_host, const float* hi_host, void* workspace,
+                             int64_t V, float* verts, float* normals, float* color_rows, void* stream);
+int nerf_mesh_write_faces(const float* vol, int res, float iso, void* workspace, int64_t F, int32_t* faces, void* stream);
+
 /* ---------------------------------------------------------------- fused renderer (a14 / a18)
  * replaces: rendering/render.py:164-241 render_rays_eval (coarse pass, importance sampling, sort, second pass)
  * as ONE call that enqueues the fixed kernel sequence on `stream`: nerf_sample_coarse -> nerf_query_fused ->

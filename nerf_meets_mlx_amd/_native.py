@@ -82,6 +82,11 @@ SIGNATURES = {
     "nerf_ert_march_write": (_I, [_P, _I64, _P, _F, _P, _I, _F, _F, _F, _I, _P, _I64, _P, _I, _P, _P, _P, _P, _P, _P]),
     "nerf_ert_fold": (_I, [_P, _P, _P, _P, _I64, _I64, _I64, _F, _F, _P, _P, _P]),
     "nerf_ert_finish": (_I, [_P, _P, _I64, _I, _P, _P, _P, _P, _P]),
+    "nerf_mesh_workspace_bytes": (_I64, [_I]),
+    "nerf_mesh_points": (_I, [_I, C.POINTER(C.c_float), C.POINTER(C.c_float), _I64, _I64, _P, _P, _P]),
+    "nerf_mesh_count": (_I, [_P, _I, _F, _P, _P, _P]),
+    "nerf_mesh_write_vertices": (_I, [_P, _I, _F, C.POINTER(C.c_float), C.POINTER(C.c_float), _P, _I64, _P, _P, _P, _P]),
+    "nerf_mesh_write_faces": (_I, [_P, _I, _F, _P, _I64, _P, _P]),
 }
 
 

@@ -4,6 +4,7 @@
 // All of it is HBM- or launch-bound; each kernel's algorithmic bytes are in the comment above it.  No atomics anywhere: the
 // compaction order comes from block scans, the mean from a fixed reduction tree, so every output is bit-reproducible.
 #include "common.h"
+#include "scan.h"
 
 namespace nerf {
 namespace {
@@ -172,32 +173,7 @@ __global__ void __launch_bounds__(CULL_BLOCK) occ_cull_count_kernel(const float*
   }
 }
 
-// ---- cull, pass 2 (one workgroup): counts -> exclusive offsets in place, the total K to count_out.  8 + 8 B per 1024 samples.
-__global__ void __launch_bounds__(1024) occ_cull_scan_kernel(int64_t* __restrict__ offs, int64_t nblk, int64_t* __restrict__ count_out) {
-  __shared__ int64_t sh[1024 / 64];
-  __shared__ int64_t carry_sh;
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  int64_t carry = 0;
-  for (int64_t b0 = 0; b0 < nblk; b0 += 1024) {
-    const int64_t b = b0 + threadIdx.x;
-    const int64_t v = b < nblk ? offs[b] : 0;
-    int64_t x = v;                                               // inclusive wave scan
-    for (int o = 1; o < WAVE; o <<= 1) {
-      const int64_t t = __shfl_up(x, o, WAVE);
-      if (lane >= o) x += t;
-    }
-    if (lane == 63) sh[w] = x;
-    __syncthreads();
-    int64_t before = carry;
-    for (int k = 0; k < w; ++k) before += sh[k];
-    if (b < nblk) offs[b] = before + x - v;
-    if (threadIdx.x == 1023) carry_sh = before + x;
-    __syncthreads();
-    carry = carry_sh;
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) *count_out = carry;
-}
+// ---- cull, pass 2 (one workgroup): occ_cull_scan_kernel (scan.h).  8 + 8 B per 1024 samples.
 
 // ---- cull, pass 3: the same keep decisions again (same reads as pass 1), their ranks inside the workgroup from wave ballots in
 // sample order, and per kept sample: its index (8 B), its ray row (44 B) and depth (4 B) written at offset + rank.

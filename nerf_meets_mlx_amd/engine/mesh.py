@@ -1,0 +1,198 @@
+"""Mesh extraction from a trained field: marching cubes over its density volume (include/nerf_hip.h "mesh extraction", DESIGN.md
+section 14).  The reference has no such export; this is Instant-NGP's.
+
+  * `marching_cubes(volume, iso, lo, hi)` turns a float32 [R, R, R] device volume (vol[k, j, i] at the cell centres
+    lo + (i + 0.5) h of the box) into a welded, consistently oriented triangle mesh: nerf_mesh_count, one read of (V, F) to the
+    host, nerf_mesh_write_vertices, nerf_mesh_write_faces.
+  * `Trainer.density_volume` / `Trainer.extract_mesh` (engine/trainer.py) sample the field on that lattice with its fused query
+    (nerf_mesh_points, the query, nerf_occ_merge_ex with decay 0) and colour the vertices by a query along -normal.
+  * `write_ply` writes a binary little-endian PLY.
+"""
+import ctypes as C
+import math
+import numbers
+import os
+from typing import NamedTuple, Optional, Sequence
+
+import numpy as np
+import torch
+
+from .. import _native as N
+
+MAX_RES = 512                # NERF_MESH_MAX_RES
+CHUNK = 1 << 19              # lattice points (or vertices) per query, as OccupancyGrid.update
+RELU, EXP = 0, 1             # NERF_OCC_RELU / NERF_OCC_EXP
+
+
+class Mesh(NamedTuple):
+    verts: torch.Tensor                   # [V, 3] float32
+    faces: torch.Tensor                   # [F, 3] int32, counter-clockwise seen from outside
+    normals: torch.Tensor                 # [V, 3] float32, unit or 0
+    colors: Optional[torch.Tensor] = None  # [V, 3] float32 in [0, 1], or None
+
+
+def check_mesh_args(resolution, lo: Sequence[float], hi: Sequence[float], iso=0.0):
+    """(R, lo [3], hi [3], iso) as (int, float lists, float); ValueError for R outside [2, MAX_RES], a box with lo >= hi or a
+    non-finite corner, or a non-finite iso."""
+    if isinstance(resolution, bool) or not isinstance(resolution, numbers.Integral) or not 2 <= int(resolution) <= MAX_RES:
+        raise ValueError(f"mesh resolution must be an int in [2, {MAX_RES}], got {resolution!r}")
+    lo = [float(x) for x in lo]
+    hi = [float(x) for x in hi]
+    if len(lo) != 3 or len(hi) != 3:
+        raise ValueError(f"mesh box: lo and hi need 3 coordinates each, got {lo!r}, {hi!r}")
+    if not all(math.isfinite(a) and math.isfinite(b) and a < b for a, b in zip(lo, hi)):
+        raise ValueError(f"mesh box: need finite lo < hi on every axis, got lo={lo!r}, hi={hi!r}")
+    if isinstance(iso, bool) or not isinstance(iso, numbers.Real) or not math.isfinite(float(iso)):
+        raise ValueError(f"mesh iso level must be a finite number, got {iso!r}")
+    return int(resolution), lo, hi, float(iso)
+
+
+def _box(lo, hi):
+    return (C.c_float * 3)(*lo), (C.c_float * 3)(*hi)
+
+
+def lattice_rows(resolution: int, lo, hi, p0: int = 0, count: Optional[int] = None, device="cuda"):
+    """(rays [count, 11], z [count, 1]) of lattice points [p0, p0 + count): o = the point, the rest 0 (nerf_mesh_points)."""
+    R, lo, hi, _ = check_mesh_args(resolution, lo, hi)
+    if count is None:
+        count = R ** 3 - p0
+    rays = torch.empty(count, 11, dtype=torch.float32, device=device)
+    z = torch.empty(count, 1, dtype=torch.float32, device=device)
+    _rows_into(R, lo, hi, p0, count, rays, z)
+    return rays, z
+
+
+def _rows_into(R, lo, hi, p0, count, rays, z):
+    clo, chi = _box(lo, hi)
+    N.check(N.lib().nerf_mesh_points(R, clo, chi, p0, count, N.ptr(rays) if count else None, N.ptr(z) if count else None,
+                                     N.stream()))
+
+
+def density_volume(query, activation: int, resolution: int, lo, hi, device="cuda", chunk: int = CHUNK) -> torch.Tensor:
+    """float32 [R, R, R] = act(raw[..., 3]) of query(rays, z) -> raw [n, 1, 4] on the lattice, `chunk` points per query (the
+    volume does not depend on it); act: RELU or EXP, NaN counting as 0."""
+    R, lo, hi, _ = check_mesh_args(resolution, lo, hi)
+    if activation not in (RELU, EXP):
+        raise ValueError(f"density activation must be RELU (0) or EXP (1), got {activation!r}")
+    n3 = R ** 3
+    vol = torch.zeros(n3, dtype=torch.float32, device=device)
+    chunk = max(1, min(int(chunk), n3))
+    rays = torch.empty(chunk, 11, dtype=torch.float32, device=device)
+    z = torch.empty(chunk, 1, dtype=torch.float32, device=device)
+    for p0 in range(0, n3, chunk):
+        cnt = min(chunk, n3 - p0)
+        r, zz = rays[:cnt], z[:cnt]
+        _rows_into(R, lo, hi, p0, cnt, r, zz)
+        raw = N.f32(query(r, zz)).reshape(-1, 4)
+        assert raw.shape[0] == cnt
+        N.check(N.lib().nerf_occ_merge_ex(N.ptr(vol[p0:p0 + cnt]), N.ptr(raw), cnt, 0.0, activation, N.stream()))
+    return vol.view(R, R, R)
+
+
+def _marching_cubes(volume, iso, lo, hi, color_rows: bool):
+    if not torch.is_tensor(volume) or volume.dim() != 3 or volume.dtype != torch.float32 or not volume.is_contiguous() \
+            or not (volume.shape[0] == volume.shape[1] == volume.shape[2]):
+        raise ValueError("marching_cubes: volume must be a contiguous float32 [R, R, R] tensor")
+    R, lo, hi, iso = check_mesh_args(volume.shape[0], lo, hi, iso)
+    dev = volume.device
+    L = N.lib()
+    clo, chi = _box(lo, hi)
+    ws = torch.empty(L.nerf_mesh_workspace_bytes(R), dtype=torch.uint8, device=dev)
+    tot = torch.empty(2, dtype=torch.int64, device=dev)
+    N.check(L.nerf_mesh_count(N.ptr(volume), R, iso, N.ptr(ws), N.ptr(tot), N.stream()))
+    V, F = tot.tolist()                                       # the one host read
+    verts = torch.empty(V, 3, dtype=torch.float32, device=dev)
+    normals = torch.empty(V, 3, dtype=torch.float32, device=dev)
+    faces = torch.empty(F, 3, dtype=torch.int32, device=dev)
+    rows = torch.empty(V, 11, dtype=torch.float32, device=dev) if color_rows else None
+    if V or F:
+        N.check(L.nerf_mesh_write_vertices(N.ptr(volume), R, iso, clo, chi, N.ptr(ws), V, N.ptr(verts), N.ptr(normals),
+                                           N.ptr(rows) if rows is not None else None, N.stream()))
+        N.check(L.nerf_mesh_write_faces(N.ptr(volume), R, iso, N.ptr(ws), F, N.ptr(faces), N.stream()))
+    return Mesh(verts, faces, normals), rows
+
+
+def marching_cubes(volume: torch.Tensor, iso: float, lo, hi) -> Mesh:
+    """The mesh of {v > iso} of a contiguous float32 [R, R, R] device volume on the lattice of the box [lo, hi] (no colours)."""
+    return _marching_cubes(volume, iso, lo, hi, False)[0]
+
+
+def vertex_colors(query, rows: torch.Tensor, chunk: int = CHUNK) -> torch.Tensor:
+    """clamp(raw[..., :3], 0, 1) of query(rows, z = 0) -> raw [n, 1, 4] on the colour rows of nerf_mesh_write_vertices."""
+    V = rows.shape[0]
+    out = torch.empty(V, 3, dtype=torch.float32, device=rows.device)
+    if V == 0:
+        return out
+    z = torch.zeros(min(V, chunk), 1, dtype=torch.float32, device=rows.device)
+    for s in range(0, V, chunk):
+        e = min(V, s + chunk)
+        raw = query(rows[s:e], z[:e - s]).reshape(-1, 4)
+        out[s:e] = raw[:, :3].clamp(0.0, 1.0)
+    return out
+
+
+def extract(query, activation: int, resolution: int, threshold: float, lo, hi, colors: bool = True, device="cuda") -> Mesh:
+    """density_volume -> marching_cubes at `threshold` -> (optionally) vertex colours."""
+    check_mesh_args(resolution, lo, hi, threshold)
+    vol = density_volume(query, activation, resolution, lo, hi, device=device)
+    mesh, rows = _marching_cubes(vol, threshold, lo, hi, colors)
+    if not colors:
+        return mesh
+    return mesh._replace(colors=vertex_colors(query, rows))
+
+
+def write_ply(path: str, mesh: Mesh) -> str:
+    """Binary little-endian PLY: vertex x y z nx ny nz (float) [+ red green blue (uchar, round(255 c))], face
+    `list uchar int vertex_indices`.  Written under a temporary name, then renamed."""
+    v = mesh.verts.detach().cpu().numpy().astype("<f4")
+    n = mesh.normals.detach().cpu().numpy().astype("<f4")
+    f = mesh.faces.detach().cpu().numpy().astype("<i4")
+    fields = [("x", "<f4"), ("y", "<f4"), ("z", "<f4"), ("nx", "<f4"), ("ny", "<f4"), ("nz", "<f4")]
+    if mesh.colors is not None:
+        fields += [("red", "u1"), ("green", "u1"), ("blue", "u1")]
+    vert = np.empty(len(v), dtype=fields)
+    for k, name in enumerate("xyz"):
+        vert[name] = v[:, k]
+        vert["n" + name] = n[:, k]
+    if mesh.colors is not None:
+        c = np.clip(np.nan_to_num(mesh.colors.detach().cpu().numpy().astype(np.float64)), 0.0, 1.0)
+        rgb = np.round(255.0 * c).astype(np.uint8)
+        for k, name in enumerate(("red", "green", "blue")):
+            vert[name] = rgb[:, k]
+    face = np.empty(len(f), dtype=[("n", "u1"), ("i", "<i4", (3,))])
+    face["n"] = 3
+    face["i"] = f
+    head = ["ply", "format binary_little_endian 1.0", f"element vertex {len(v)}"]
+    head += [f"property {'float' if t == '<f4' else 'uchar'} {name}" for name, t in fields]
+    head += [f"element face {len(f)}", "property list uchar int vertex_indices", "end_header"]
+    tmp = path + ".tmp"
+    with open(tmp, "wb") as fh:
+        fh.write(("\n".join(head) + "\n").encode("ascii"))
+        fh.write(vert.tobytes())
+        fh.write(face.tobytes())
+    os.replace(tmp, path)
+    return path
+
+
+def read_ply(path: str) -> Mesh:
+    """The inverse of write_ply (CPU tensors); only the layout write_ply produces."""
+    with open(path, "rb") as fh:
+        data = fh.read()
+    end = data.index(b"end_header\n") + len(b"end_header\n")
+    head = data[:end].decode("ascii").splitlines()
+    if head[:2] != ["ply", "format binary_little_endian 1.0"]:
+        raise ValueError(f"{path}: not a binary little-endian PLY")
+    nv = int(head[2].split()[2])
+    props = [ln.split() for ln in head if ln.startswith("property ") and "list" not in ln]
+    fields = [(p[2], "<f4" if p[1] == "float" else "u1") for p in props]
+    nf = int(next(ln for ln in head if ln.startswith("element face")).split()[2])
+    vert = np.frombuffer(data, dtype=fields, count=nv, offset=end)
+    face = np.frombuffer(data, dtype=[("n", "u1"), ("i", "<i4", (3,))], count=nf, offset=end + vert.nbytes)
+    if end + vert.nbytes + face.nbytes != len(data) or not (face["n"] == 3).all():
+        raise ValueError(f"{path}: unexpected PLY layout")
+    verts = torch.from_numpy(np.stack([vert[k] for k in "xyz"], 1).copy())
+    normals = torch.from_numpy(np.stack([vert["n" + k] for k in "xyz"], 1).copy())
+    colors = None
+    if "red" in vert.dtype.names:
+        colors = torch.from_numpy(np.stack([vert[k] for k in ("red", "green", "blue")], 1).astype(np.float32) / 255.0)
+    return Mesh(verts, torch.from_numpy(face["i"].copy()), normals, colors)

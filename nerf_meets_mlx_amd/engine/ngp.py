@@ -336,6 +336,21 @@ class NGPTrainer(Trainer):
     def field(self, f):
         self._field = f
 
+    def _mesh_field(self):
+        """The hash-grid field through `field` (joins the comm stream); exp density in march mode, relu otherwise."""
+        from .mesh import EXP, RELU
+        f = self.field
+        return (lambda rays, z: f.query(rays, z)), (EXP if self.march_steps is not None else RELU)
+
+    def _mesh_box(self, aabb):
+        """aabb, or the field's scene box [-bound, bound]^3 by default."""
+        if aabb is not None:
+            return super()._mesh_box(aabb)
+        b = self._field.bound
+        if b is None:
+            raise ValueError("NGPTrainer mesh export: the field has no scene box (bound=None), pass aabb=(lo, hi)")
+        return [-float(b)] * 3, [float(b)] * 3
+
     def train_step(self, rays=None, target=None, u=None) -> Dict[str, torch.Tensor]:
         if rays is None:
             rays, target = self.sample_batch()

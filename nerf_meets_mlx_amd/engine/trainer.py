@@ -181,6 +181,40 @@ class Trainer:
         mse = torch.mean((img - gt.to(self.device)) ** 2)
         return float(10.0 * torch.log10(1.0 / mse))
 
+    # ---------------------------------------------------------------- mesh export
+    def _mesh_field(self):
+        """(query(rays, z) -> raw [n, 1, 4], density activation) of the field a mesh is extracted from: the fine network if there is
+        one, else the coarse, with relu (the reference's density)."""
+        from .mesh import RELU
+        model = self.fine if self.fine is not None else self.coarse
+        return (lambda rays, z: model.query(rays, z, ref_quirks=self.q)), RELU
+
+    def _mesh_box(self, aabb):
+        """(lo [3], hi [3]) of aabb = (lo, hi) or [[lo], [hi]]; this trainer's field has no box of its own, so one is required."""
+        if aabb is None:
+            raise ValueError("Trainer mesh export: the 8 x 256 field has no scene box, pass aabb=(lo, hi)")
+        lo, hi = aabb
+        return [float(x) for x in lo], [float(x) for x in hi]
+
+    def density_volume(self, resolution: int, aabb=None) -> torch.Tensor:
+        """float32 [R, R, R] density act(sigma) of the field on the lattice of aabb (vol[k, j, i] at the cell centres
+        lo + (i + 0.5) (hi - lo) / R; include/nerf_hip.h "mesh extraction").  Runs on this rank only (no collective)."""
+        from . import mesh
+        lo, hi = self._mesh_box(aabb)
+        query, act = self._mesh_field()
+        return mesh.density_volume(query, act, resolution, lo, hi, device=self.device)
+
+    def extract_mesh(self, resolution: int = 256, threshold: float = 2.5, aabb=None, colors: bool = True):
+        """engine.mesh.Mesh of {sigma > threshold}: marching cubes over density_volume(resolution, aabb), vertex colours (when
+        `colors`) from the field queried at each vertex looking along -normal, clamped to [0, 1].  2.5 is Instant-NGP's default
+        threshold; sigma's scale is the model's own (relu of the raw output for the 8 x 256 and the 64-sample hash-grid fields,
+        exp for the march mode's), so a threshold that suits one model need not suit another.  Runs on this rank only: no
+        collective, any rank may call it alone."""
+        from . import mesh
+        lo, hi = self._mesh_box(aabb)
+        query, act = self._mesh_field()
+        return mesh.extract(query, act, resolution, threshold, lo, hi, colors=colors, device=self.device)
+
     # ---------------------------------------------------------------- checkpoint (SURVEY 8f-3)
     def _checkpoint_buffers(self):
         """name -> object with `.params` (flat fp32 device buffer) and `.load_flat(t)`; the names are also the Adam keys."""

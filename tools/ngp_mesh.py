@@ -1,0 +1,249 @@
+#!/usr/bin/env python3
+"""Mesh extraction from the hash-grid field of BASELINE configs[4] (800 x 800 synthetic Lego, 4 training
+views, N_rand 4096, seed 4) trained in march mode (march_steps 512, 2000 iterations: the section-12 run), or from a checkpoint:
+
+    python tools/ngp_mesh.py --out profiles/ngp_mesh.jsonl [--save-ckpt /tmp/ngp.npz | --ckpt /tmp/ngp.npz]     (GPU)
+
+Per resolution R (default 128, 256, 512) over the field's box [-1.5, 1.5]^3, at threshold 2.5 (exp density): device ms of the
+density volume (lattice rows + fused query + merge) and of marching cubes (count, one host read, vertices with colour rows,
+faces) and of the colour query, each the mean of --reps event-timed runs; V and F; the geometry figure -- the fractions of
+vertices within h and 2 h (L-infinity) of the boundary of the union of synthetic._BOXES -- for this mesh and for the mesh of the
+teacher's own sigma volume at iso 25 (the ceiling a perfect field reaches on this lattice); at --ply-res the PLY is written,
+parsed back and checked (V, F, every directed edge at most once).
+
+    rocprofv3 --kernel-trace --output-format csv -d DIR -o mesh -- python tools/ngp_mesh.py --ckpt /tmp/ngp.npz --reps 1 --no-ply
+    python tools/ngp_mesh.py --stats DIR/.../mesh_kernel_trace.csv --from profiles/ngp_mesh.jsonl --out profiles/ngp_mesh_kernels.jsonl
+
+summarises such a trace: per mesh kernel and R the mean device time per launch, and its algorithmic bytes over that time
+against the MI355X's HBM bandwidth (8.0 TB/s spec, 6.29 TB/s measured float4 copy)."""
+import argparse
+import csv
+import json
+import os
+import sys
+import tempfile
+
+import numpy as np
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+HBM_SPEC, HBM_MEASURED = 8.0e12, 6.29e12
+BLOCK = 256
+
+
+def near_union_boundary(pts, boxes, d):
+    """bool [P]: the cube of half-size d around each point holds points inside and outside the union of the boxes
+    [(centre, half-size)] -- L-infinity distance to the union's boundary at most d (exact, on the boxes' own grid)."""
+    p = np.asarray(pts, np.float64)
+    lo = np.array([np.subtract(c, h) for c, h in boxes], np.float64)
+    hi = np.array([np.add(c, h) for c, h in boxes], np.float64)
+    xs = [np.unique(np.concatenate([lo[:, a], hi[:, a]])) for a in range(3)]
+    mids = [0.5 * (x[1:] + x[:-1]) for x in xs]
+    Mg = np.stack(np.meshgrid(*mids, indexing="ij"), -1)
+    occ = np.zeros(Mg.shape[:3], np.int64)
+    for l, u in zip(lo, hi):
+        occ |= ((Mg > l) & (Mg < u)).all(-1)
+    S = np.zeros(tuple(s + 1 for s in occ.shape), np.int64)            # 3-D prefix sums of the occupied cells
+    S[1:, 1:, 1:] = occ.cumsum(0).cumsum(1).cumsum(2)
+    c0, c1, beyond = [], [], np.zeros(len(p), bool)
+    for a in range(3):
+        x = xs[a]
+        a0 = np.clip(np.searchsorted(x, p[:, a] - d, side="right") - 1, 0, len(x) - 2)
+        a1 = np.clip(np.searchsorted(x, p[:, a] + d, side="left") - 1, 0, len(x) - 2)
+        beyond |= (p[:, a] - d < x[0]) | (p[:, a] + d > x[-1])
+        c0.append(a0)
+        c1.append(a1 + 1)
+    ok = (c1[0] > c0[0]) & (c1[1] > c0[1]) & (c1[2] > c0[2])
+    x0, y0, z0 = c0
+    x1, y1, z1 = c1
+    n_in = (S[x1, y1, z1] - S[x0, y1, z1] - S[x1, y0, z1] - S[x1, y1, z0] + S[x0, y0, z1] + S[x0, y1, z0] + S[x1, y0, z0]
+            - S[x0, y0, z0])
+    total = (x1 - x0) * (y1 - y0) * (z1 - z0)
+    has_in = ok & (n_in > 0)
+    has_out = beyond | ~ok | (n_in < total)
+    return has_in & has_out
+
+
+def _events():
+    return torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+
+
+def _geometry(verts, R, bound, boxes):
+    h = 2.0 * bound / R
+    v = verts.cpu().numpy()
+    if len(v) == 0:
+        return {"within_h": None, "within_2h": None}
+    return {"within_h": float(near_union_boundary(v, boxes, h).mean()), "within_2h": float(near_union_boundary(v, boxes, 2 * h).mean())}
+
+
+def _teacher_volume(R, lo, hi, dev):
+    from nerf_meets_mlx_amd.dataset import synthetic
+    from nerf_meets_mlx_amd.engine import mesh
+    vol = torch.empty(R ** 3, dtype=torch.float32, device=dev)
+    for p0 in range(0, R ** 3, mesh.CHUNK):
+        cnt = min(mesh.CHUNK, R ** 3 - p0)
+        rows, _ = mesh.lattice_rows(R, lo, hi, p0, cnt, device=dev)
+        vol[p0:p0 + cnt] = synthetic.teacher_field(rows[:, :3])[0]
+    return vol.view(R, R, R)
+
+
+def _ply_check(m, path):
+    from nerf_meets_mlx_amd.engine.mesh import read_ply, write_ply
+    write_ply(path, m)
+    back = read_ply(path)
+    V, F = back.verts.shape[0], back.faces.shape[0]
+    f = back.faces.numpy().astype(np.int64)
+    d = np.concatenate([f[:, [0, 1]], f[:, [1, 2]], f[:, [2, 0]]])
+    key = d[:, 0] * max(V, 1) + d[:, 1]
+    return {"ply_bytes": os.path.getsize(path), "ply_V": V, "ply_F": F,
+            "ply_matches": bool(V == m.verts.shape[0] and F == m.faces.shape[0]
+                                and torch.equal(back.verts, m.verts.cpu()) and torch.equal(back.faces, m.faces.cpu())),
+            "ply_directed_edges_unique": bool(len(np.unique(key)) == len(key))}
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--iters", type=int, default=2000)
+    ap.add_argument("--hw", type=int, default=800)
+    ap.add_argument("--n-rand", type=int, default=4096)
+    ap.add_argument("--march-steps", type=int, default=512)
+    ap.add_argument("--res", default="128,256,512")
+    ap.add_argument("--threshold", type=float, default=2.5)
+    ap.add_argument("--reps", type=int, default=3)
+    ap.add_argument("--ply-res", type=int, default=256)
+    ap.add_argument("--no-ply", action="store_true")
+    ap.add_argument("--ckpt", default=None, help="load this checkpoint instead of training")
+    ap.add_argument("--save-ckpt", default=None, help="save the trained state here")
+    ap.add_argument("--out", default=None, help="append the JSON lines to this file")
+    ap.add_argument("--stats", default=None, help="summarise a rocprofv3 --kernel-trace CSV of this tool instead of measuring")
+    ap.add_argument("--from", dest="from_", default=None, help="--stats: the measuring run's JSON lines (V and F per R)")
+    a = ap.parse_args()
+    if a.stats:
+        return stats(a)
+    from nerf_meets_mlx_amd.dataset import synthetic
+    from nerf_meets_mlx_amd.engine import mesh
+    from nerf_meets_mlx_amd.engine.ngp import NGPTrainer
+
+    dev = torch.device("cuda", 0)
+    torch.cuda.set_device(dev)
+    H = W = a.hw
+    if a.ckpt:
+        imgs, poses, K = torch.zeros(1, 8, 8, 3), synthetic.train_poses(1), synthetic.intrinsics(8, 8)[0]
+    else:
+        imgs, poses, _, _, K = synthetic.make_dataset(H, W, 5, seed=0, device=dev)
+        imgs, poses = imgs[:4], poses[:4]
+    tr = NGPTrainer(imgs, poses, K, N_rand=a.n_rand, n_depth_samples=64, seed=4, device=dev, occupancy_grid=True,
+                    march_steps=a.march_steps)
+    if a.ckpt:
+        tr.load(a.ckpt)
+    else:
+        for _ in range(a.iters):
+            tr.train_step()
+        if a.save_ckpt:
+            tr.save(a.save_ckpt)
+    torch.cuda.synchronize()
+    bound = float(tr.field.bound)
+    lo, hi = [-bound] * 3, [bound] * 3
+    boxes = [(c, h) for c, h, _ in synthetic._BOXES]
+    query, act = tr._mesh_field()
+    lines = []
+    for R in [int(r) for r in a.res.split(",")]:
+        rec = {"tool": "ngp_mesh", "R": R, "hw": a.hw, "iters": tr.it, "march_steps": a.march_steps, "seed": 4,
+               "threshold": a.threshold, "activation": "exp", "device": torch.cuda.get_device_name(dev)}
+        t_vol, t_mc, t_col = [], [], []
+        for _ in range(a.reps):
+            e = [torch.cuda.Event(enable_timing=True) for _ in range(4)]
+            e[0].record()
+            vol = mesh.density_volume(query, act, R, lo, hi, device=dev)
+            e[1].record()
+            m, rows = mesh._marching_cubes(vol, a.threshold, lo, hi, True)
+            e[2].record()
+            col = mesh.vertex_colors(query, rows)
+            e[3].record()
+            torch.cuda.synchronize()
+            t_vol.append(e[0].elapsed_time(e[1]))
+            t_mc.append(e[1].elapsed_time(e[2]))
+            t_col.append(e[2].elapsed_time(e[3]))
+        m = m._replace(colors=col)
+        rec.update({"V": int(m.verts.shape[0]), "F": int(m.faces.shape[0]), "density_volume_ms": float(np.mean(t_vol)),
+                    "marching_cubes_ms": float(np.mean(t_mc)), "colors_ms": float(np.mean(t_col)),
+                    "marching_cubes_ms_range": [min(t_mc), max(t_mc)], "density_volume_ms_range": [min(t_vol), max(t_vol)],
+                    "volume_MB": R ** 3 * 4 / 1e6})
+        rec["geometry"] = _geometry(m.verts, R, bound, boxes)
+        tv = _teacher_volume(R, lo, hi, dev)
+        tm = mesh.marching_cubes(tv, 25.0, lo, hi)
+        rec["teacher"] = {"V": int(tm.verts.shape[0]), "F": int(tm.faces.shape[0]), **_geometry(tm.verts, R, bound, boxes)}
+        del tv, tm
+        if not a.no_ply and R == a.ply_res:
+            with tempfile.TemporaryDirectory() as d:
+                rec.update(_ply_check(m, os.path.join(d, "mesh.ply")))
+        del vol, m, rows, col
+        torch.cuda.empty_cache()
+        print(json.dumps(rec), flush=True)
+        lines.append(rec)
+    if a.out:
+        with open(a.out, "a") as fh:
+            for r in lines:
+                fh.write(json.dumps(r) + "\n")
+
+
+def _bytes(kernel, R, V, F):
+    """Algorithmic HBM bytes of one launch (csrc/mesh.hip comments): the volume once, the outputs once."""
+    n3 = R ** 3
+    nblk = -(-n3 // BLOCK)
+    return {"mesh_count_kernel": 4 * n3 + 16 * nblk,
+            "mesh_vertices_kernel": 4 * n3 + 4 * n3 + 8 * nblk + (24 + 44) * V,
+            "mesh_faces_kernel": 4 * n3 + 4 * n3 + 8 * nblk + 12 * F,
+            "mesh_points_kernel": 48 * n3}.get(kernel)
+
+
+def stats(a):
+    """Per mesh kernel and lattice size: mean device time per launch from a rocprofv3 --kernel-trace CSV, bytes / time."""
+    import re
+    runs = {}
+    if a.from_:
+        with open(a.from_) as fh:
+            for ln in fh:
+                r = json.loads(ln)
+                runs[r["R"]] = r
+    with open(a.stats) as fh:
+        rows = list(csv.DictReader(fh))
+    col = {k.lower(): k for k in rows[0]} if rows else {}
+    name_k = col.get("kernel_name")
+    s_k, e_k = col.get("start_timestamp"), col.get("end_timestamp")
+    gx = col.get("grid_size_x", col.get("grid_size"))
+    groups = {}
+    for r in rows:
+        m = re.search(r"(mesh_\w+_kernel|occ_cull_scan_kernel|occ_merge_exp_kernel)", r[name_k])
+        if not m:
+            continue
+        k = m.group(1)
+        grid = int(r[gx])
+        if k == "mesh_points_kernel" or k == "occ_merge_exp_kernel" or k == "occ_cull_scan_kernel":
+            R = None                                                       # chunked / one workgroup: pooled per kernel
+        else:
+            R = next((R for R in runs if -(-R ** 3 // BLOCK) * BLOCK == grid), None)
+            if R is None:
+                R = round((grid) ** (1 / 3))
+        groups.setdefault((k, R), []).append((int(r[e_k]) - int(r[s_k])) * 1e-3)
+    out = []
+    for (k, R), us in sorted(groups.items(), key=lambda t: (t[0][0], t[0][1] or 0)):
+        rec = {"tool": "ngp_mesh --stats (rocprofv3 --kernel-trace)", "kernel": k, "R": R, "launches": len(us),
+               "avg_us": round(float(np.mean(us)), 2), "median_us": round(float(np.median(us)), 2)}
+        if R is not None and R in runs:
+            b = _bytes(k, R, runs[R]["V"], runs[R]["F"])
+            if b:
+                bw = b / (float(np.median(us)) * 1e-6)
+                rec.update({"bytes": b, "TBps": round(bw / 1e12, 3), "frac_hbm_spec": round(bw / HBM_SPEC, 3),
+                            "frac_hbm_measured": round(bw / HBM_MEASURED, 3)})
+        out.append(rec)
+        print(json.dumps(rec))
+    if a.out:
+        with open(a.out, "a") as fh:
+            for r in out:
+                fh.write(json.dumps(r) + "\n")
+
+
+if __name__ == "__main__":
+    main()
