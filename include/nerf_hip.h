@@ -107,8 +107,12 @@ int nerf_add_noise_z(const float* z_in, const float* t_rand, int64_t B, int n, f
 /* replaces: sampling/__init__.py:101-177 sample_from_inverse_cdf_torch (u passed in
  * instead of torch.rand) and the sort of entrypoints/__test_nerf.py:288 /
  * rendering/render.py:225.  weights: [B,n] (the reference's [B,n,1] squeezed).
- * Outputs (each may be NULL): z_new [B,N]; z_merged [B,n+N] ascending; cdf [B,n+1];
- * inds [B,N] int64 = searchsorted(cdf, u, side="right") -- bit-exact given (cdf,u).
+ * Outputs (each may be NULL): z_new [B,N]; z_merged [B,n+N]; cdf [B,n+1];
+ * inds [B,N] int64 = searchsorted(cdf, u, side="right") -- bit-exact given (cdf,u) for a monotone cdf (NaN or
+ * negative weights give a cdf that is not: inds is then what the binary search finds; a NaN u gives n + 1).
+ * z_merged is the exact multiset of the n coarse and the N new depths, ascending, equal depths coarse-first, NaN last
+ * -- for any coarse list (ascending or not, with ties, NaN or infinite depths) and for NaN new depths (an infinite
+ * first / last coarse depth makes the mid points infinite and their difference NaN).
  * Limits: 2 <= n <= 256, 1 <= N <= 512, n+N <= 768.                                   */
 int nerf_importance_sample(const float* z, const float* weights, const float* u, int64_t B, int n, int N, float eps,
                            float* z_new, float* z_merged, float* cdf, int64_t* inds, void* stream);
@@ -183,7 +187,8 @@ int nerf_composite_backward(const float* raw, const float* z, const float* rays,
                             const float* d_acc, const float* d_depth, float* d_raw, void* stream);
 
 /* replaces: ops/metric.py:12-14 MSE and its gradient: loss_out[0] += sum((pred-target)^2)
- * / count (caller zeroes it), d_pred = grad_scale * 2 (pred-target) / count.           */
+ * / count (caller zeroes it; the workgroups' terms are added atomically, so the last bits depend on their order),
+ * d_pred = grad_scale * 2 (pred-target) / count.  loss_out and d_pred may each be NULL; count > 0.       */
 int nerf_mse_loss_grad(const float* pred, const float* target, int64_t count, float grad_scale, float* loss_out,
                        float* d_pred, void* stream);
 

@@ -1,6 +1,6 @@
 // Depth sampling (a5-a7) and inverse-CDF importance sampling + merge (a15, a17 / K2, K8).
 // HBM-bound: one wavefront per ray, CDF / depths staged in LDS, per-lane binary search,
-// LDS rank-merge of the n sorted + N new depths.
+// LDS rank-merge of the n coarse + N new depths (the rule: the exact multiset, ascending, ties coarse-first, NaN last).
 #include "common.h"
 
 namespace nerf {
@@ -97,6 +97,7 @@ __global__ void __launch_bounds__(256) importance_kernel(const float* __restrict
     __builtin_amdgcn_wave_barrier();
     if (cdf_out) for (int i = lane; i <= n; i += WAVE) cdf_out[ray * (n + 1) + i] = s_cdf[i];
     // per-lane binary search: inds = #{i : cdf[i] <= u}  (searchsorted side="right")
+    bool new_nan = false;                   // a NaN new depth (inf - inf of two infinite mid points): the merge below must know
     for (int j = lane; j < N; j += WAVE) {
       const float uj = u[ray * N + j];
       const bool unan = uj != uj;                                  // torch.searchsorted orders NaN after everything: inds = n + 1
@@ -113,6 +114,7 @@ __global__ void __launch_bounds__(256) importance_kernel(const float* __restrict
       if (t != t) t = 0.0f;                                        // nan_to_num(.., 0)
       t = fminf(fmaxf(t, 0.0f), 1.0f);                             // (+-inf -> +-FLT_MAX -> clipped)
       const float zn = zf + t * (zt - zf);
+      new_nan = new_nan || (zn != zn);
       if (z_new) z_new[ray * N + j] = zn;
       if (inds_out) inds_out[ray * N + j] = inds;
       s_all[n + j] = zn;
@@ -123,8 +125,10 @@ __global__ void __launch_bounds__(256) importance_kernel(const float* __restrict
       const int tot = n + N;
       float* s_new = s_all + n;
       // is the coarse list ascending (it always is on the render path)?  Then: bitonic sort of the N new depths in
-      // LDS + two binary-search rank passes = O((n+N) log) instead of the O((n+N)^2) rank sort below.
-      bool asc = true;
+      // LDS + two binary-search rank passes = O((n+N) log) instead of the O((n+N)^2) rank sort below.  The network's
+      // comparison and the rank searches order numbers only: with a NaN among the new depths the ranks collide and slots
+      // of z_merged stay unwritten, so such a ray takes the rank sort (same vote, no extra ballot).
+      bool asc = !new_nan;
       for (int i = lane; i + 1 < n; i += WAVE) asc = asc && (s_all[i] <= s_all[i + 1]);
       if (__all(asc)) {
         for (int i = N + lane; i < P; i += WAVE) s_new[i] = __builtin_inff();          // pad to a power of two

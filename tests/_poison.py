@@ -114,3 +114,72 @@ def ngp_query_into(f, rays, z, pattern, train=False):
                                            N.ptr(f.table.shadow()), e.n_levels, e.log2_hashmap_size, e.n_features_per_level,
                                            e._res_c, 3, f.pos_scale, f.pos_offset, N.ptr(raw), N.ptr(acts), N.stream()))
     return raw
+
+
+# ---- the volume renderer (csrc/sampling.hip, csrc/composite.hip): same C ABI calls as sampling / rendering.render / ops.metric,
+# every requested output sentinel-filled first; an output not named in `want` is passed as NULL.  Loss words are accumulated
+# into by the kernels (the caller zeroes them), so they start at 0, not at the sentinel.
+def sample_coarse_into(rays, n, lindisp=False, perturb=0.0, t_rand=None):
+    B = rays.shape[0]
+    z = _out((B, n), rays.device)
+    N.check(N.lib().nerf_sample_coarse(N.ptr(rays), B, n, int(lindisp), float(perturb), N.ptr(t_rand), N.ptr(z), N.stream()))
+    return z
+
+
+def add_noise_z_into(z, t_rand, strength):
+    B, n = z.shape
+    out = _out((B, n), z.device)
+    N.check(N.lib().nerf_add_noise_z(N.ptr(z), N.ptr(t_rand), B, n, float(strength), N.ptr(out), N.stream()))
+    return out
+
+
+def importance_into(z, w, u, eps=1e-5, want=("z_new", "z_merged", "cdf", "inds")):
+    """dict of the requested outputs of `nerf_importance_sample` (inds: int64, sentinel words in both halves)."""
+    (B, n), Ns = z.shape, u.shape[1]
+    o = {"z_new": _out((B, Ns), z.device), "z_merged": _out((B, n + Ns), z.device), "cdf": _out((B, n + 1), z.device),
+         "inds": sentinel_(torch.empty(B, Ns, dtype=torch.int64, device=z.device))}
+    o = {k: v for k, v in o.items() if k in want}
+    N.check(N.lib().nerf_importance_sample(N.ptr(z), N.ptr(w), N.ptr(u), B, n, Ns, float(eps), N.ptr(o.get("z_new")),
+                                           N.ptr(o.get("z_merged")), N.ptr(o.get("cdf")), N.ptr(o.get("inds")), N.stream()))
+    return o
+
+
+FWD_OUTPUTS = ("rgb", "disp", "acc", "weights", "depth")
+
+
+def composite_forward_into(raw, z, rays, white=False, noise=None, raw_noise_std=0.0, want=FWD_OUTPUTS):
+    B, n = z.shape
+    o = {"rgb": _out((B, 3), z.device), "disp": _out((B,), z.device), "acc": _out((B,), z.device),
+         "weights": _out((B, n), z.device), "depth": _out((B,), z.device)}
+    o = {k: v for k, v in o.items() if k in want}
+    N.check(N.lib().nerf_composite_forward(N.ptr(raw), N.ptr(z), N.ptr(rays), B, n, float(raw_noise_std), N.ptr(noise),
+                                           int(white), N.ptr(o["rgb"]), N.ptr(o.get("disp")), N.ptr(o.get("acc")),
+                                           N.ptr(o.get("weights")), N.ptr(o.get("depth")), N.stream()))
+    return o
+
+
+def composite_backward_into(raw, z, rays, d_rgb, d_acc=None, d_depth=None, white=False, noise=None, raw_noise_std=0.0):
+    B, n = z.shape
+    d_raw = _out((B, n, 4), z.device)
+    N.check(N.lib().nerf_composite_backward(N.ptr(raw), N.ptr(z), N.ptr(rays), B, n, float(raw_noise_std), N.ptr(noise),
+                                            int(white), N.ptr(d_rgb), N.ptr(d_acc), N.ptr(d_depth), N.ptr(d_raw), N.stream()))
+    return d_raw
+
+
+def composite_mse_backward_into(raw, z, rays, target, white=False, grad_scale=1.0, want_rgb=True, want_loss=True):
+    """(loss [1] or None, rgb [B, 3] or None, d_raw [B, n, 4]) of `nerf_composite_mse_backward`."""
+    B, n = z.shape
+    d_raw = _out((B, n, 4), z.device)
+    rgb = _out((B, 3), z.device) if want_rgb else None
+    loss = torch.zeros(1, dtype=torch.float32, device=z.device) if want_loss else None
+    N.check(N.lib().nerf_composite_mse_backward(N.ptr(raw), N.ptr(z), N.ptr(rays), B, n, int(white), N.ptr(target),
+                                                float(grad_scale), N.ptr(loss), N.ptr(rgb), N.ptr(d_raw), N.stream()))
+    return loss, rgb, d_raw
+
+
+def mse_loss_grad_into(p, t, grad_scale=1.0, want_grad=True, want_loss=True):
+    """(loss [1] or None, d_pred or None) of `nerf_mse_loss_grad`."""
+    grad = _out(tuple(p.shape), p.device) if want_grad else None
+    loss = torch.zeros(1, dtype=torch.float32, device=p.device) if want_loss else None
+    N.check(N.lib().nerf_mse_loss_grad(N.ptr(p), N.ptr(t), p.numel(), float(grad_scale), N.ptr(loss), N.ptr(grad), N.stream()))
+    return loss, grad
