@@ -415,6 +415,48 @@ int nerf_composite_packed_mse_backward(const float* raw, const int64_t* offsets,
                                        int white_bkgd, const float* target, float grad_scale, float* loss_out, float* rgb,
                                        float* d_raw, void* stream);
 
+/* ---------------------------------------------------------------- distortion regulariser (no reference counterpart)
+ * The distortion loss of mip-NeRF 360 (Barron et al. 2022, eq. 15) on the packed samples of the march: it penalises ray weight
+ * that is spread out or split into separate clumps.  Additive: NERF_ABI_VERSION stays 3.  For ray b with samples k in
+ * [offsets[b], offsets[b + 1]) in depth order, weights w_k exactly as in "packed compositing" above, S = march_steps:
+ *   u_k   = (z_k - z_first) |d_b| / (S step_world): the position along the ray in units of the scene box's diagonal (S step_world =
+ *           sqrt(3) 2 bound), relative to the ray's first sample, so u in [0, 1] whatever near / far and the length of d are.
+ *           |d_b| is the march's norm, float(sqrt_double((d0 d0 + d1 d1) + d2 d2)) of rays[b, 3..5].
+ *   delta = 1 / S: the width of an interval (every march interval is step_world long).
+ *   L_b   = sum_i sum_j w_i w_j |u_i - u_j| + (delta / 3) sum_i w_i^2            (0 for a ray without samples)
+ *   dL_b/dw_k = 2 sum_j w_j |u_k - u_j| + (2 delta / 3) w_k
+ * The objective of a training step is MSE + dist_weight * mean over the B rays of L_b; rays without samples count with 0.
+ * Because the samples are sorted the double sum is two prefix sums.  With Wl_k = sum_{j<k} w_j, Ul_k = sum_{j<k} w_j u_j and the
+ * ray's totals W, U, in float32, one rounding per operation, in this order:
+ *   us = |d_b| / ((float)S * step_world), u_k = (z_k - z_first) * us
+ *   Wl_k, Ul_k: the sums over the 64-sample chunks before k's, added chunk total by chunk total in depth order, plus the
+ *           exclusive wave scan of w (of w * u) inside the chunk; W, U: the same chain after the last chunk
+ *   L_b   = 2 * sum_k w_k * (u_k * Wl_k - Ul_k) + c1 * sum_k w_k * w_k,  c1 = (1 / (float)S) / 3     (both sums: per lane over
+ *           the chunks, then a wave sum; every term of the first is >= 0 up to rounding)
+ *   inter_k = u_k * ((2 * Wl_k + w_k) - W) - ((2 * Ul_k + w_k * u_k) - U)        (= sum_j w_j |u_k - u_j|)
+ *   G_k  += coef * (2 * inter_k + (2 * c1) * w_k),  coef = grad_scale * dist_weight * (1 / (float)B)
+ * G_k is the per-sample adjoint of w_k in the training form of packed compositing; from there the term reaches d_raw[k, 3]
+ * through the same transmittance chain and trunc_exp backward.  d_raw[k, 0..2] do not see it.  Wave scans make this a
+ * tolerance-level contract against tests/_distortion_ref.py (as packed compositing is); run to run d_raw and dist are
+ * bit-reproducible (loss_out / dist_out are sums of float atomics).
+ * Edge cases: bad offsets (as above) -> the ray's outputs and dist NaN, no access; a NaN in a ray's raw or z -> that ray's
+ * d_raw and dist NaN and no other ray's; sigma = +inf -> finite dist and gradients; |d_b| zero or not finite -> dist = 0 and no
+ * extra gradient for that ray (the march gives such rays no samples).  rays: float32 [B, 11] (d in columns 3..5).
+ *   nerf_composite_packed_distortion          nerf_composite_packed_forward plus dist [B] = L_b (forward only; acc, depth may
+ *                                             be NULL).
+ *   nerf_composite_packed_mse_dist_backward   nerf_composite_packed_mse_backward plus the regulariser: loss_out keeps its meaning
+ *                                             (MSE only); dist_out (one float the caller zeroes; may be NULL) += mean_b L_b,
+ *                                             unweighted.  dist_weight: finite, >= 0.
+ * NERF_E_SHAPE for march_steps outside [1, NERF_MARCH_MAX_STEPS], step_world <= 0, a negative or non-finite dist_weight,
+ * unaligned raw / d_raw; NERF_E_NULL for NULL pointers; B = 0 returns NERF_OK.  All checked before any device work.        */
+int nerf_composite_packed_distortion(const float* raw, const float* z, const int64_t* offsets, const float* rays, int64_t B,
+                                     int64_t K, float step_world, int march_steps, int white_bkgd, float* rgb, float* acc,
+                                     float* depth, float* dist, void* stream);
+int nerf_composite_packed_mse_dist_backward(const float* raw, const float* z, const int64_t* offsets, const float* rays, int64_t B,
+                                            int64_t K, float step_world, int march_steps, int white_bkgd, const float* target,
+                                            float grad_scale, float dist_weight, float* loss_out, float* dist_out, float* rgb,
+                                            float* d_raw, void* stream);
+
 /* ---------------------------------------------------------------- early ray termination (no reference counterpart)
  * The round renderer of the march (inference only): a ray stops once its transmittance falls below min_transmittance = eps
  * (0 <= eps < 1), and the steps behind that point are neither marched nor queried.  Additive: NERF_ABI_VERSION stays 3.

@@ -76,6 +76,8 @@ SIGNATURES = {
     "nerf_occ_march_write": (_I, [_P, _I64, _P, _F, _P, _I, _F, _F, _F, _I, _P, _P, _P, _P, _P]),
     "nerf_composite_packed_forward": (_I, [_P, _P, _P, _I64, _I64, _F, _I, _P, _P, _P, _P]),
     "nerf_composite_packed_mse_backward": (_I, [_P, _P, _I64, _I64, _F, _I, _P, _F, _P, _P, _P, _P]),
+    "nerf_composite_packed_distortion": (_I, [_P, _P, _P, _P, _I64, _I64, _F, _I, _I, _P, _P, _P, _P, _P]),
+    "nerf_composite_packed_mse_dist_backward": (_I, [_P, _P, _P, _P, _I64, _I64, _F, _I, _I, _P, _F, _F, _P, _P, _P, _P, _P]),
     "nerf_ert_march_workspace_bytes": (_I64, [_I64]),
     "nerf_ert_init": (_I, [_I64, _P, _P, _P, _P]),
     "nerf_ert_march_count": (_I, [_P, _I64, _P, _F, _P, _I, _F, _F, _F, _I, _P, _I64, _P, _I, _P, _P, _P]),

@@ -139,6 +139,156 @@ __global__ void __launch_bounds__(256) composite_packed_train_kernel(const float
   if (threadIdx.x == 0 && loss) atomicAdd(loss, (part[0] + part[1] + part[2] + part[3]) * inv);
 }
 
+// ---- distortion regulariser (include/nerf_hip.h "distortion regulariser"): the two kernels above with L_b and its adjoint.  Kernels
+// of their own, so that the ones above keep their ISA.  Extra traffic: z (4 B per sample, read again by the reverse pass: L2 hits)
+// and the 12 B of d per ray.
+struct DistRay {
+  float z0, us;                         // depth of the ray's first sample; |d| / (S step_world)
+  bool on;                              // false: |d| zero or not finite, the ray has no distortion term
+};
+
+__device__ __forceinline__ DistRay dist_ray(const float* __restrict__ rays, const float* __restrict__ z, int64_t ray, int64_t s0,
+                                            int64_t s1, float diag) {
+  const float* rr = rays + ray * 11;
+  const float dn = (float)sqrt((double)((rr[3] * rr[3] + rr[4] * rr[4]) + rr[5] * rr[5]));      // the march's |d|
+  DistRay d;
+  d.on = dn > 0.0f && dn <= 3.4028234664e38f;
+  d.us = d.on ? dn / diag : 0.0f;
+  d.z0 = s0 < s1 ? z[s0] : 0.0f;
+  return d;
+}
+
+struct DistQ {
+  float u, Wl, Ul;                      // position of sample k, sum of w and of w u over the ray's samples before k
+};
+
+// the prefixes of sample k = c0 + lane; Wc / Uc = the sums over the chunks before this one, advanced to the next chunk's
+__device__ __forceinline__ DistQ dist_chunk(const float* __restrict__ z, int64_t c0, int64_t s1, int lane, const DistRay& d, float w,
+                                            float& Wc, float& Uc) {
+  DistQ o;
+  o.u = c0 + lane < s1 ? (z[c0 + lane] - d.z0) * d.us : 0.0f;
+  const float wi = wave_scan_incl(w, lane), ui = wave_scan_incl(w * o.u, lane);
+  const float wup = __shfl_up(wi, 1, WAVE), uup = __shfl_up(ui, 1, WAVE);
+  o.Wl = Wc + (lane == 0 ? 0.0f : wup);
+  o.Ul = Uc + (lane == 0 ? 0.0f : uup);
+  Wc += __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, wi), 63));
+  Uc += __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, ui), 63));
+  return o;
+}
+
+__global__ void __launch_bounds__(256) composite_packed_dist_fwd_kernel(const float* __restrict__ raw, const float* __restrict__ z,
+                                                                        const int64_t* __restrict__ offsets,
+                                                                        const float* __restrict__ rays, int64_t B, int64_t K,
+                                                                        float step, float diag, float c1, int white,
+                                                                        float* __restrict__ rgb, float* __restrict__ acc,
+                                                                        float* __restrict__ depth, float* __restrict__ dist) {
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+  for (int64_t ray = blockIdx.x * 4 + wv; ray < B; ray += (int64_t)gridDim.x * 4) {
+    int64_t s0, s1;
+    bool bad;
+    segment(offsets, ray, K, s0, s1, bad);
+    const DistRay dr = dist_ray(rays, z, ray, s0, s1, diag);
+    float carry = 0.0f, sr = 0.0f, sg = 0.0f, sb = 0.0f, sa = 0.0f, sd = 0.0f, Wc = 0.0f, Uc = 0.0f, pl = 0.0f, pq = 0.0f;
+    for (int64_t c0 = s0; c0 < s1; c0 += 64) {
+      float tot;
+      const PackedQ q = packed_chunk(raw, c0, s1, lane, step, carry, tot);
+      const float zk = c0 + lane < s1 ? z[c0 + lane] : 0.0f;
+      sr += q.w * q.r; sg += q.w * q.g; sb += q.w * q.b; sa += q.w; sd += q.w * zk;
+      carry += tot;
+      const DistQ e = dist_chunk(z, c0, s1, lane, dr, q.w, Wc, Uc);
+      pl += q.w * (e.u * e.Wl - e.Ul); pq += q.w * q.w;
+    }
+    sr = wave_sum(sr); sg = wave_sum(sg); sb = wave_sum(sb); sa = wave_sum(sa); sd = wave_sum(sd);
+    pl = wave_sum(pl); pq = wave_sum(pq);
+    if (lane == 0) {
+      float L = dr.on ? 2.0f * pl + c1 * pq : 0.0f;
+      if (white) { sr = sr + (1.0f - sa); sg = sg + (1.0f - sa); sb = sb + (1.0f - sa); }
+      if (bad) sr = sg = sb = sa = sd = L = __builtin_nanf("");
+      rgb[ray * 3 + 0] = sr; rgb[ray * 3 + 1] = sg; rgb[ray * 3 + 2] = sb;
+      if (acc) acc[ray] = sa;
+      if (depth) depth[ray] = sd;
+      dist[ray] = L;
+    }
+  }
+}
+
+// composite_packed_train_kernel with G_k += coef dL_b/dw_k, coef = grad_scale dist_weight / B.  The forward sweep also leaves the
+// chunk-entry sums of w and w u in lane c (next to the carried exponent) and ends with the ray's totals W, U; the reverse sweep
+// repeats each chunk's two scans (the same operations: the same bits) for Wl_k, Ul_k.
+//   dL_b/dw_k = 2 inter_k + (2 delta / 3) w_k,  inter_k = u_k ((2 Wl_k + w_k) - W) - ((2 Ul_k + w_k u_k) - U)
+__global__ void __launch_bounds__(256) composite_packed_dist_train_kernel(
+    const float* __restrict__ raw, const float* __restrict__ z, const int64_t* __restrict__ offsets, const float* __restrict__ rays,
+    int64_t B, int64_t K, float step, float diag, float c1, int white, const float* __restrict__ target, float grad_scale, float coef,
+    float* __restrict__ loss, float* __restrict__ dist_out, float* __restrict__ rgb_out, float* __restrict__ d_raw) {
+  __shared__ float part[4];
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+  const float inv = 1.0f / (float)(B * 3), invB = 1.0f / (float)B, c2 = 2.0f * c1;
+  float sq = 0.0f, sl = 0.0f;
+  for (int64_t ray = blockIdx.x * 4 + wv; ray < B; ray += (int64_t)gridDim.x * 4) {
+    int64_t s0, s1;
+    bool bad;
+    segment(offsets, ray, K, s0, s1, bad);
+    const DistRay dr = dist_ray(rays, z, ray, s0, s1, diag);
+    float carry = 0.0f, carries = 0.0f, wcs = 0.0f, ucs = 0.0f, sr = 0.0f, sg = 0.0f, sb = 0.0f, sa = 0.0f;
+    float Wc = 0.0f, Uc = 0.0f, pl = 0.0f, pq = 0.0f;
+    int nch = 0;
+    for (int64_t c0 = s0; c0 < s1; c0 += 64, ++nch) {
+      if (lane == nch) { carries = carry; wcs = Wc; ucs = Uc; }
+      float tot;
+      const PackedQ q = packed_chunk(raw, c0, s1, lane, step, carry, tot);
+      sr += q.w * q.r; sg += q.w * q.g; sb += q.w * q.b; sa += q.w;
+      carry += tot;
+      const DistQ e = dist_chunk(z, c0, s1, lane, dr, q.w, Wc, Uc);
+      pl += q.w * (e.u * e.Wl - e.Ul); pq += q.w * q.w;
+    }
+    sr = wave_sum(sr); sg = wave_sum(sg); sb = wave_sum(sb); sa = wave_sum(sa);
+    pl = wave_sum(pl); pq = wave_sum(pq);
+    if (white) { sr = sr + (1.0f - sa); sg = sg + (1.0f - sa); sb = sb + (1.0f - sa); }
+    if (bad) sr = sg = sb = __builtin_nanf("");
+    const float er = sr - target[ray * 3], eg = sg - target[ray * 3 + 1], eb = sb - target[ray * 3 + 2];
+    if (lane == 0) {
+      sq += er * er; sq += eg * eg; sq += eb * eb;
+      sl += bad ? __builtin_nanf("") : dr.on ? 2.0f * pl + c1 * pq : 0.0f;
+      if (rgb_out) { rgb_out[ray * 3] = sr; rgb_out[ray * 3 + 1] = sg; rgb_out[ray * 3 + 2] = sb; }
+    }
+    const float gr = grad_scale * 2.0f * er * inv, gg = grad_scale * 2.0f * eg * inv, gb = grad_scale * 2.0f * eb * inv;
+    const float gacc = 0.0f - (white ? (gr + gg + gb) : 0.0f);
+    const float W = Wc, U = Uc;
+    float suffix = 0.0f;                                         // sum of G w over the chunks after this one
+    for (int c = nch - 1; c >= 0; --c) {
+      const int64_t c0 = s0 + (int64_t)c * 64;
+      const float cin = __shfl(carries, c, WAVE);
+      float Wk = __shfl(wcs, c, WAVE), Uk = __shfl(ucs, c, WAVE);
+      float tot;
+      const PackedQ q = packed_chunk(raw, c0, s1, lane, step, cin, tot);
+      const DistQ e = dist_chunk(z, c0, s1, lane, dr, q.w, Wk, Uk);
+      const float inter = e.u * ((2.0f * e.Wl + q.w) - W) - ((2.0f * e.Ul + q.w * e.u) - U);
+      float G = gr * q.r + gg * q.g + gb * q.b + gacc;
+      if (dr.on) G = G + coef * (2.0f * inter + c2 * q.w);
+      const float gw = G * q.w;
+      const float rincl = wave_rscan_incl(gw, lane);
+      const float dn = __shfl_down(rincl, 1, WAVE);
+      const float after = suffix + (lane == 63 ? 0.0f : dn);   // sum over the samples k' > k of the ray
+      const int64_t k = c0 + lane;
+      if (k < s1) {
+        const float sig = raw[4 * k + 3];
+        const float dx = G * q.T * expf(-q.x) - after;
+        float4 o;
+        o.x = q.w * gr; o.y = q.w * gg; o.z = q.w * gb; o.w = dx * step * expf(fminf(sig, 15.0f));
+        *reinterpret_cast<float4*>(d_raw + 4 * k) = o;
+      }
+      suffix += __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, rincl), 0));
+    }
+  }
+  if (lane == 0) part[wv] = sq;
+  __syncthreads();
+  if (threadIdx.x == 0 && loss) atomicAdd(loss, (part[0] + part[1] + part[2] + part[3]) * inv);
+  __syncthreads();                                               // the same 16 B carry the second sum
+  if (lane == 0) part[wv] = sl;
+  __syncthreads();
+  if (threadIdx.x == 0 && dist_out) atomicAdd(dist_out, (part[0] + part[1] + part[2] + part[3]) * invB);
+}
+
 // ---- round renderer with early ray termination (include/nerf_hip.h "early ray termination").  Per ray: istate int32 [4] = (next
 // candidate k, kept count, samples folded, flags), fstate float [6] = (carry, r, g, b, acc, depth).
 // init: 40 B of state and 4 B of live id written per ray, nothing read.
@@ -245,6 +395,49 @@ extern "C" int nerf_composite_packed_mse_backward(const float* raw, const int64_
   hipLaunchKernelGGL(composite_packed_train_kernel, g, b, 0, as_stream(stream), raw, offsets, B, K, step_world, white_bkgd, target,
                      grad_scale, loss_out, rgb, d_raw);
   return check_launch("nerf_composite_packed_mse_backward");
+}
+
+// the checks the two distortion entries share, before any device work
+static int dist_args(const char* who, int64_t B, int64_t K, float step_world, int march_steps) {
+  NERF_REQUIRE(B >= 0 && K >= 0, NERF_E_SHAPE, "%s: bad sizes", who);
+  NERF_REQUIRE(step_world > 0.0f, NERF_E_SHAPE, "%s: step_world must be > 0", who);
+  NERF_REQUIRE(march_steps >= 1 && march_steps <= NERF_MARCH_MAX_STEPS, NERF_E_SHAPE, "%s: need 1 <= march_steps <= %d", who,
+               NERF_MARCH_MAX_STEPS);
+  return NERF_OK;
+}
+
+extern "C" int nerf_composite_packed_distortion(const float* raw, const float* z, const int64_t* offsets, const float* rays,
+                                                int64_t B, int64_t K, float step_world, int march_steps, int white_bkgd, float* rgb,
+                                                float* acc, float* depth, float* dist, void* stream) {
+  if (const int rc = dist_args("nerf_composite_packed_distortion", B, K, step_world, march_steps)) return rc;
+  if (B == 0) return NERF_OK;
+  NERF_REQUIRE(offsets && rays && rgb && dist && (K == 0 || (raw && z)), NERF_E_NULL, "nerf_composite_packed_distortion: NULL pointer");
+  NERF_REQUIRE(K == 0 || aligned16(raw), NERF_E_SHAPE, "nerf_composite_packed_distortion: raw must be 16-byte aligned");
+  const float S = (float)march_steps;
+  const dim3 g((unsigned)((B + 3) / 4 > 8192 ? 8192 : (B + 3) / 4)), b(256);
+  hipLaunchKernelGGL(composite_packed_dist_fwd_kernel, g, b, 0, as_stream(stream), raw, z, offsets, rays, B, K, step_world,
+                     S * step_world, (1.0f / S) / 3.0f, white_bkgd, rgb, acc, depth, dist);
+  return check_launch("nerf_composite_packed_distortion");
+}
+
+extern "C" int nerf_composite_packed_mse_dist_backward(const float* raw, const float* z, const int64_t* offsets, const float* rays,
+                                                       int64_t B, int64_t K, float step_world, int march_steps, int white_bkgd,
+                                                       const float* target, float grad_scale, float dist_weight, float* loss_out,
+                                                       float* dist_out, float* rgb, float* d_raw, void* stream) {
+  if (const int rc = dist_args("nerf_composite_packed_mse_dist_backward", B, K, step_world, march_steps)) return rc;
+  NERF_REQUIRE(dist_weight >= 0.0f && dist_weight <= 3.4028234664e38f, NERF_E_SHAPE,
+               "nerf_composite_packed_mse_dist_backward: dist_weight must be finite and >= 0");
+  if (B == 0) return NERF_OK;
+  NERF_REQUIRE(offsets && rays && target && (K == 0 || (raw && z && d_raw)), NERF_E_NULL,
+               "nerf_composite_packed_mse_dist_backward: NULL pointer");
+  NERF_REQUIRE(K == 0 || (aligned16(raw) && aligned16(d_raw)), NERF_E_SHAPE,
+               "nerf_composite_packed_mse_dist_backward: raw / d_raw must be 16-byte aligned");
+  const float S = (float)march_steps;
+  const dim3 g((unsigned)((B + 3) / 4 > 8192 ? 8192 : (B + 3) / 4)), b(256);
+  hipLaunchKernelGGL(composite_packed_dist_train_kernel, g, b, 0, as_stream(stream), raw, z, offsets, rays, B, K, step_world,
+                     S * step_world, (1.0f / S) / 3.0f, white_bkgd, target, grad_scale, grad_scale * dist_weight * (1.0f / (float)B),
+                     loss_out, dist_out, rgb, d_raw);
+  return check_launch("nerf_composite_packed_mse_dist_backward");
 }
 
 extern "C" int nerf_ert_init(int64_t B, int* istate, float* fstate, int* live, void* stream) {

@@ -268,7 +268,7 @@ class NGPTrainer(Trainer):
                  n_depth_samples: int = 64, lrate: float = 5e-4, lrate_decay: int = 500, white_bkgd: bool = True,
                  seed: int = 0, device="cuda", chunk: int = 1024 * 32, table_sync: str = "shard", precision: int = 22,
                  occupancy_grid: bool = False, march_steps: Optional[int] = None, min_transmittance: Optional[float] = None,
-                 **hash_kw):
+                 distortion_weight: Optional[float] = None, **hash_kw):
         """occupancy_grid: empty-space skipping (engine/occupancy.py): the grid is updated every UPDATE_EVERY iterations from the
         start; from iteration WARMUP on, training and rendering evaluate only the samples in occupied cells.  Off by default.
         march_steps (needs occupancy_grid=True and a scene box; 1 ... 1024; None: the n_depth_samples stratified grid): the
@@ -287,8 +287,14 @@ class NGPTrainer(Trainer):
             min_transmittance = check_min_transmittance(min_transmittance)
             if march_steps is None:
                 raise ValueError("NGPTrainer: min_transmittance needs march_steps (early termination is a mode of the march)")
+        if distortion_weight is not None:
+            from .occupancy import check_distortion_weight
+            distortion_weight = check_distortion_weight(distortion_weight)
+            if march_steps is None:
+                raise ValueError("NGPTrainer: distortion_weight needs march_steps (the regulariser acts on the march's packed samples)")
         self.march_steps = march_steps
         self.min_transmittance = min_transmittance
+        self.distortion_weight = distortion_weight
         super().__init__(images, poses, K, near=near, far=far, N_rand=N_rand, n_depth_samples=n_depth_samples,
                          N_importance=0, lrate=lrate, lrate_decay=lrate_decay, white_bkgd=white_bkgd, ref_quirks=True,
                          seed=seed, device=device, chunk=chunk, precision=precision)
@@ -357,7 +363,7 @@ class NGPTrainer(Trainer):
         self._opt.learning_rate = self.lrate * (0.1 ** (self.it / (self.lrate_decay * 1000)))
         if self.march_steps is not None:
             self._join_comm()
-            loss, d_raw = self._march_step_forward(rays, target)
+            loss, d_raw, dist = self._march_step_forward(rays, target)
         else:
             z = sampling.sample_coarse(rays, self.n)
             self._join_comm()                                # the previous step's table all-gathers (sharded updates)
@@ -434,11 +440,14 @@ class NGPTrainer(Trainer):
             self._opt.update(self._field.table, g_tab.view(-1), grad_scale=1.0 / self.world, zero_grads=True)    # reads g, writes 0
         self._field._grad_clean = True
         self.it += 1
+        if self.distortion_weight is not None:
+            return {"loss_coarse": loss, "loss_distortion": dist}
         return {"loss_coarse": loss}
 
     def _march_step_forward(self, rays, target):
         """March mode, training: grid update -> march (per-ray jitter from counter stream 4) -> fused query of the K packed
-        samples -> packed compositing + MSE backward.  (loss, d_raw [K, 4]); the last query(train=True) is the packed one."""
+        samples -> packed compositing + MSE backward, with the distortion regulariser when distortion_weight is set.
+        (loss, d_raw [K, 4], mean distortion or None); the last query(train=True) is the packed one."""
         from .occupancy import WARMUP
         self._grid_for_step(update=True)
         B = rays.shape[0]
@@ -447,12 +456,18 @@ class NGPTrainer(Trainer):
         offsets, rows, z, K = self.grid.march(rays, jitter, use_bits=self.it >= WARMUP)
         self.last_march = (B, K)
         raw = self._field.query_packed(rows, z, train=True)
+        if self.distortion_weight is not None:
+            loss, dist, d_raw, _ = render.composite_packed_mse_dist_backward(raw, z, offsets, rays, self.grid.step_world,
+                                                                             self.march_steps, target, self.distortion_weight,
+                                                                             self.white_bkgd)
+            return loss, d_raw, dist
         loss, d_raw, _ = render.composite_packed_mse_backward(raw, offsets, B, self.grid.step_world, target, self.white_bkgd)
-        return loss, d_raw
+        return loss, d_raw, None
 
     def render_rays(self, rays: torch.Tensor, u=None, aux: bool = False):
         """rgb [B, 3] of rays [B, 11], `chunk` rays per call.  aux=True: {"rgb", "acc" [B], "depth" [B]} and, in march mode,
-        "samples" [B] int32 (the samples composited per ray)."""
+        "samples" [B] int32 (the samples composited per ray); with distortion_weight set (and no early termination) also
+        "distortion" [B], every ray's distortion loss L_b."""
         outs = []
         self._join_comm()
         if self.march_steps is not None:                     # march mode: jitter 0.5, the bitfield once the warm-up is over
@@ -466,6 +481,12 @@ class NGPTrainer(Trainer):
                     continue
                 offsets, rows, z, K = self.grid.march(r, 0.5, use_bits=use_bits)
                 raw = self._field.query_packed(rows, z)
+                if aux and self.distortion_weight is not None:
+                    rgb, acc, depth, dist = render.composite_packed_distortion(raw, z, offsets, r, self.grid.step_world,
+                                                                               self.march_steps, self.white_bkgd)
+                    outs.append({"rgb": rgb, "acc": acc, "depth": depth, "samples": (offsets[1:] - offsets[:-1]).to(torch.int32),
+                                 "distortion": dist})
+                    continue
                 rgb, acc, depth = render.composite_packed(raw, z, offsets, r.shape[0], self.grid.step_world, self.white_bkgd)
                 outs.append({"rgb": rgb, "acc": acc, "depth": depth,
                              "samples": (offsets[1:] - offsets[:-1]).to(torch.int32)} if aux else rgb)
@@ -477,6 +498,23 @@ class NGPTrainer(Trainer):
             rgb, _, acc, _, depth = render.composite(raw, z, r, 0.0, self.white_bkgd, need_weights=False)
             outs.append({"rgb": rgb, "acc": acc, "depth": depth} if aux else rgb)
         return _cat(outs, aux)
+
+    def ray_distortion(self, rays: torch.Tensor) -> torch.Tensor:
+        """dist [B]: the distortion loss L_b of rays [B, 11] on the one-shot march renderer's samples
+        (jitter 0.5).  March mode only; works whether or not the trainer was built with a distortion_weight, so that a field
+        trained without the regulariser can be measured by the same yardstick."""
+        if self.march_steps is None:
+            raise ValueError("NGPTrainer.ray_distortion needs march_steps (the distortion loss is defined on the march's samples)")
+        from .occupancy import WARMUP
+        self._join_comm()
+        outs = []
+        for s in range(0, rays.shape[0], self.chunk):
+            r = N.f32(rays[s:s + self.chunk])
+            offsets, rows, z, K = self.grid.march(r, 0.5, use_bits=self.it >= WARMUP)
+            raw = self._field.query_packed(rows, z)
+            outs.append(render.composite_packed_distortion(raw, z, offsets, r, self.grid.step_world, self.march_steps,
+                                                           self.white_bkgd)[3])
+        return torch.cat(outs, 0) if outs else torch.empty(0, dtype=torch.float32, device=self.device)
 
     def _grid_for_step(self, update: bool = False):
         """The occupancy grid to cull with at this iteration (None: every sample runs); update=True (the training step) first

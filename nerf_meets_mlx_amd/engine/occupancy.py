@@ -63,6 +63,16 @@ def check_min_transmittance(min_transmittance) -> Optional[float]:
     return float(min_transmittance)
 
 
+def check_distortion_weight(distortion_weight) -> Optional[float]:
+    """None, or distortion_weight as a finite float > 0; ValueError otherwise (0, NaN and inf included)."""
+    if distortion_weight is None:
+        return None
+    if isinstance(distortion_weight, bool) or not isinstance(distortion_weight, numbers.Real) \
+            or not 0.0 < float(distortion_weight) < math.inf:
+        raise ValueError(f"distortion_weight must be None or a finite number > 0, got {distortion_weight!r}")
+    return float(distortion_weight)
+
+
 def march_step_world(march_steps: int, bound: float) -> float:
     """The march's world step sqrt(3) / march_steps * 2 bound, computed in double and rounded once to float32."""
     return float(torch.tensor(math.sqrt(3.0) / int(march_steps) * 2.0 * float(bound), dtype=torch.float32))

@@ -89,6 +89,45 @@ def composite_packed_mse_backward(raw, offsets, B: int, step_world: float, targe
     return loss, d_raw, rgb
 
 
+def composite_packed_distortion(raw, z, offsets, rays, step_world: float, march_steps: int, white_bkgd=False):
+    """(rgb [B, 3], acc [B], depth [B], dist [B]) of the packed rays [B, 11]: composite_packed plus the distortion loss L_b of
+    every ray (`nerf_composite_packed_distortion`, include/nerf_hip.h "distortion regulariser")."""
+    raw = N.f32(raw).reshape(-1, 4)
+    z = N.f32(z).reshape(-1)
+    rays = N.f32(rays)
+    B, K = rays.shape[0], raw.shape[0]
+    dev = offsets.device
+    rgb = torch.empty(B, 3, dtype=torch.float32, device=dev)
+    acc = torch.empty(B, dtype=torch.float32, device=dev)
+    depth = torch.empty(B, dtype=torch.float32, device=dev)
+    dist = torch.empty(B, dtype=torch.float32, device=dev)
+    N.check(N.lib().nerf_composite_packed_distortion(N.ptr(raw) if K else None, N.ptr(z) if K else None, N.ptr(offsets),
+                                                     N.ptr(rays), B, K, float(step_world), int(march_steps), int(bool(white_bkgd)),
+                                                     N.ptr(rgb), N.ptr(acc), N.ptr(depth), N.ptr(dist), N.stream()))
+    return rgb, acc, depth, dist
+
+
+def composite_packed_mse_dist_backward(raw, z, offsets, rays, step_world: float, march_steps: int, target, dist_weight: float,
+                                       white_bkgd=False, grad_scale: float = 1.0, need_rgb: bool = False):
+    """(loss [1], dist [1], d_raw [K, 4], rgb [B, 3] or None): composite_packed_mse_backward with the distortion regulariser
+    (`nerf_composite_packed_mse_dist_backward`).  d_raw is the gradient of MSE + dist_weight * mean_b L_b; loss is the MSE
+    alone and dist the unweighted mean_b L_b."""
+    raw = N.f32(raw).reshape(-1, 4)
+    z = N.f32(z).reshape(-1)
+    rays = N.f32(rays)
+    B, K = rays.shape[0], raw.shape[0]
+    dev = offsets.device
+    loss = torch.zeros(1, dtype=torch.float32, device=dev)
+    dist = torch.zeros(1, dtype=torch.float32, device=dev)
+    d_raw = torch.empty(K, 4, dtype=torch.float32, device=dev)
+    rgb = torch.empty(B, 3, dtype=torch.float32, device=dev) if need_rgb else None
+    N.check(N.lib().nerf_composite_packed_mse_dist_backward(
+        N.ptr(raw) if K else None, N.ptr(z) if K else None, N.ptr(offsets), N.ptr(rays), B, K, float(step_world), int(march_steps),
+        int(bool(white_bkgd)), N.ptr(N.f32(target)), float(grad_scale), float(dist_weight), N.ptr(loss), N.ptr(dist), N.ptr(rgb),
+        N.ptr(d_raw) if K else None, N.stream()))
+    return loss, dist, d_raw, rgb
+
+
 def ert_init(istate, fstate, live, B: int):
     """Zero the round renderer's state of B rays (istate int32 [B, 4], fstate float32 [B, 6]) and set live = 0 .. B - 1
     (`nerf_ert_init`, include/nerf_hip.h "early ray termination")."""

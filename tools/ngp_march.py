@@ -6,13 +6,15 @@ N_rand 4096, seed 4, one 32 768-ray render chunk per step), in ONE process:
 
 Arms: "off" (64 stratified samples, no grid), "cull" (64 samples, grid cull) and "march<S>" (the march of
 section 12 with march_steps = S; default 1024 and 512), and "march<S>_ert" (the same march with early ray termination at
-min_transmittance --eps, section 13; trained exactly as "march<S>").  Every arm is trained past the grid's warm-up, then the arms alternate
+min_transmittance --eps, section 13; trained exactly as "march<S>"), and "march<S>_dist" (the march trained with the distortion
+regulariser of section 15 at --dist-weight).  Every arm is trained past the grid's warm-up, then the arms alternate
 timed blocks of --block steps until --iters; each step is timed with device events (train step, render chunk).  Per arm: train
 ms / step, render ms / chunk, samples per ray in training and rendering, for march arms the device time of the march (count +
 scan + write) and the host time of the K read-back; after --iters the held-out PSNR on a fifth view, next to the PSNR of an
 all-white frame of that view.  Early-termination arms also report the ms per full held-out frame at the render chunk and at
 one whole-frame chunk, samples per ray, rounds and host-read ms per call, and the max |d| per pixel against the same trainer's
-one-shot render.  One JSON line per arm and a summary line.
+one-shot render.  One-shot march arms also report, over the held-out frame, the mean distortion loss L_b, the mean acc and the
+samples per ray without and with termination at --eps.  One JSON line per arm and a summary line.
 
     python tools/ngp_march.py --stats <rocprofv3 results .db>
 
@@ -21,6 +23,7 @@ prints the average time per launch of the march and packed-compositing kernels f
 import argparse
 import json
 import os
+import re
 import sys
 import time
 
@@ -84,6 +87,21 @@ def _ert_extra(a, tr, rrays, c2w, npix):
     return out
 
 
+def _heldout_extra(a, tr, frays):
+    """One-shot march arm, over the held-out frame's rays: mean distortion loss L_b (the forward entry, whether or not the arm
+    trained with it), mean acc, samples per ray of the one-shot render and of the round renderer at --eps."""
+    out = {"distortion_heldout_mean": float(tr.ray_distortion(frays).double().mean())}
+    o = tr.render_rays(frays, aux=True)
+    out["acc_heldout_mean"] = float(o["acc"].double().mean())
+    out["samples_per_ray_heldout"] = float(o["samples"].double().mean())
+    tr.min_transmittance = a.eps
+    try:
+        out["samples_per_ray_heldout_ert"] = float(tr.render_rays(frays, aux=True)["samples"].double().mean())
+    finally:
+        tr.min_transmittance = None
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--iters", type=int, default=2000)
@@ -94,6 +112,8 @@ def main():
     ap.add_argument("--no-psnr", action="store_true")
     ap.add_argument("--arms", default="off,cull,march1024,march512")
     ap.add_argument("--eps", type=float, default=1e-4, help="min_transmittance of the *_ert arms")
+    ap.add_argument("--dist-weight", type=float, default=1e-2,
+                    help="distortion_weight of the *_dist arms (mip-NeRF 360 publishes 0.01)")
     ap.add_argument("--frame-reps", type=int, default=5, help="timed full-frame renders per chunk size (ert arms)")
     ap.add_argument("--out", default=None, help="append the JSON lines to this file")
     ap.add_argument("--stats", default=None, help="summarise a rocprofv3 --kernel-trace results database instead of measuring")
@@ -112,10 +132,13 @@ def main():
     rrays = ray.gen_rays(H, W, K, rposes[40][:3, :4], 2.0, 6.0, torch.arange(a.render_rays, device=dev, dtype=torch.int64))
     arms = {}
     for name in a.arms.split(","):
-        ert = name.endswith("_ert")
-        steps = int(name[len("march"):len(name) - (4 if ert else 0)]) if name.startswith("march") else None
+        m = re.fullmatch(r"march(\d+)(_dist)?(_ert)?", name)
+        if m is None and name not in ("off", "cull"):
+            ap.error(f"unknown arm {name!r}")
+        steps, dist, ert = (int(m.group(1)), m.group(2) is not None, m.group(3) is not None) if m else (None, False, False)
         tr = NGPTrainer(imgs[:4], poses[:4], K, N_rand=a.n_rand, n_depth_samples=64, seed=4, device=dev, chunk=a.render_rays,
-                        occupancy_grid=(name != "off"), march_steps=steps, min_transmittance=a.eps if ert else None)
+                        occupancy_grid=(name != "off"), march_steps=steps, min_transmittance=a.eps if ert else None,
+                        distortion_weight=a.dist_weight if dist else None)
         arms[name] = {"tr": tr, "train": [], "render": [], "spr_train": [], "spr_render": []}
 
     def step(arm, timed):
@@ -161,6 +184,7 @@ def main():
                 "render_rays": a.render_rays, "seed": 4, "iters": tr.it, "timed_steps": nsteps, "block": a.block,
                 "train_ms_per_step": _ms(arm["train"]), "render_ms_per_chunk": _ms(arm["render"]),
                 "render_ms_per_chunk_p10_p90": _p10_p90(arm["render"]), "min_transmittance": tr.min_transmittance,
+                "distortion_weight": getattr(tr, "distortion_weight", None),
                 "device": torch.cuda.get_device_name(dev)}
         g = tr.grid
         if g is None:
@@ -182,6 +206,9 @@ def main():
                          "host_sync_ms_per_step": float(np.sum(syncs)) / nsteps})
         if tr.min_transmittance is not None:
             line.update(_ert_extra(a, tr, rrays, poses[4][:3, :4].numpy(), H * W))
+        elif tr.march_steps is not None:
+            line.update(_heldout_extra(a, tr, ray.gen_rays(H, W, K, poses[4][:3, :4].numpy(), 2.0, 6.0,
+                                                           torch.arange(H * W, device=dev, dtype=torch.int64))))
         lines.append(line)
     if not a.no_psnr:
         gt = imgs[4]
