@@ -83,6 +83,13 @@ int nerf_sample_batch(int64_t n, int H, int W, uint64_t seed, uint64_t offset, c
                       float near, float far, const float* image, float* rays, float* target, int64_t* pixel_idx,
                       void* stream);
 
+/* nerf_sample_batch for a straight RGBA image ("background colour" below): image [H*W, 4], target [n, 4] = image[pixel], both
+ * 16-byte aligned (NERF_E_SHAPE otherwise).  Pixels, rays and pixel_idx are those of nerf_sample_batch with the same arguments,
+ * bit for bit.  Additive: NERF_ABI_VERSION stays 3.                                                                            */
+int nerf_sample_batch_rgba(int64_t n, int H, int W, uint64_t seed, uint64_t offset, const double* K_host, const float* c2w_host,
+                           float near, float far, const float* image, float* rays, float* target, int64_t* pixel_idx,
+                           void* stream);
+
 /* out[i, :] = src[idx[i], :]   (target pixel gather, entrypoints/__test_nerf.py:236).
  * idx[i] outside [0, n_src) is never dereferenced: that output row is NaN.               */
 int nerf_gather_rows(const float* src, int64_t n_src, const int64_t* idx, int64_t n, int channels, float* out,
@@ -457,6 +464,44 @@ int nerf_composite_packed_mse_dist_backward(const float* raw, const float* z, co
                                             float grad_scale, float dist_weight, float* loss_out, float* dist_out, float* rgb,
                                             float* d_raw, void* stream);
 
+/* ---------------------------------------------------------------- background colour (no reference counterpart)
+ * Packed compositing over a background colour other than white or none, and its training form against straight (un-premultiplied)
+ * RGBA targets: Instant-NGP trains on the RGBA image over a random colour per ray, put behind the target and behind the rendered
+ * ray alike, so that only acc = alpha matches the target under every colour.  Additive: NERF_ABI_VERSION stays 3.
+ *   bg, bg_stride   device float32; colour of ray b = bg[b * bg_stride + 0..2].  bg_stride 0: one colour (3 floats) for all rays,
+ *                   3: bg [B, 3].  Any other stride is NERF_E_SHAPE.  The training entries take bg [B, 3] (stride 3).
+ * Everything up to the ray sums (sum w c per channel, acc, depth, the distortion loss) is "packed compositing" / "distortion
+ * regulariser" above: the same operations in the same order, the same bits.  Then, in float32, one rounding per operation:
+ *   forward    rgb_c = sum_c + (1.0f - acc) * bg_c                                                      (lane 0 of the ray's wave)
+ *   training   a = target_rgba[b, 3];  t_c = target_rgba[b, c] * a + bg_c * (1.0f - a)        (formed in the kernel: no composited
+ *              rgb_c as in the forward;  e_c = rgb_c - t_c;  loss_out += mean of e_c^2         target goes through memory)
+ *              g_c  = grad_scale * 2 * e_c * (1 / (float)(3 B))
+ *              gacc = 0.0f - ((g_r * bg_r + g_g * bg_g) + g_b * bg_b)                          (the one changed adjoint term)
+ *              G_k  = g_r r_k + g_g g_k + g_b b_k + gacc, and from there the suffix sums, the trunc_exp backward and the
+ *              distortion term added to G_k exactly as above.
+ *   finish     nerf_ert_finish with rgb_c = state_c + (1.0f - acc) * bg_c.
+ * Three identities follow (multiplying by 1.0f is exact; the library is built without FMA contraction):
+ *   bg = (1, 1, 1)  the forward entries give the bits of white_bkgd = 1; the training entries those of the white_bkgd = 1
+ *                   entries fed the same t.
+ *   a = 1           t_c = target_rgba[b, c] exactly (finite bg).
+ *   bg = (0, 0, 0)  with a finite acc the outputs equal those of white_bkgd = 0, except that a zero may change its sign.
+ * Edge cases as above (bad offsets -> that ray NaN, no access; sigma = +inf finite; B = 0 and K = 0 succeed; acc, depth, loss_out,
+ * dist_out, rgb of the training forms, samples may be NULL), and a NaN in a ray's bg or target makes that ray's outputs and
+ * d_raw NaN and no other ray's (loss_out, one sum over the batch, is NaN too).  No atomics beyond loss_out / dist_out.
+ * target_rgba must be 16-byte aligned like raw / d_raw (NERF_E_SHAPE).  All checks run before any device work.               */
+int nerf_composite_packed_forward_bg(const float* raw, const float* z, const int64_t* offsets, int64_t B, int64_t K, float step_world,
+                                     const float* bg, int bg_stride, float* rgb, float* acc, float* depth, void* stream);
+int nerf_composite_packed_distortion_bg(const float* raw, const float* z, const int64_t* offsets, const float* rays, int64_t B,
+                                        int64_t K, float step_world, int march_steps, const float* bg, int bg_stride, float* rgb,
+                                        float* acc, float* depth, float* dist, void* stream);
+int nerf_composite_packed_mse_backward_bg(const float* raw, const int64_t* offsets, int64_t B, int64_t K, float step_world,
+                                          const float* target_rgba, const float* bg, float grad_scale, float* loss_out, float* rgb,
+                                          float* d_raw, void* stream);
+int nerf_composite_packed_mse_dist_backward_bg(const float* raw, const float* z, const int64_t* offsets, const float* rays, int64_t B,
+                                               int64_t K, float step_world, int march_steps, const float* target_rgba,
+                                               const float* bg, float grad_scale, float dist_weight, float* loss_out,
+                                               float* dist_out, float* rgb, float* d_raw, void* stream);
+
 /* ---------------------------------------------------------------- early ray termination (no reference counterpart)
  * The round renderer of the march (inference only): a ray stops once its transmittance falls below min_transmittance = eps
  * (0 <= eps < 1), and the steps behind that point are neither marched nor queried.  Additive: NERF_ABI_VERSION stays 3.
@@ -502,6 +547,8 @@ int nerf_ert_fold(const float* raw, const float* z, const int64_t* offsets, cons
                   float step_world, float min_transmittance, int32_t* istate, float* fstate, void* stream);
 int nerf_ert_finish(const int32_t* istate, const float* fstate, int64_t B, int white_bkgd, float* rgb, float* acc, float* depth,
                     int32_t* samples, void* stream);
+int nerf_ert_finish_bg(const int32_t* istate, const float* fstate, int64_t B, const float* bg, int bg_stride, float* rgb, float* acc,
+                       float* depth, int32_t* samples, void* stream);    /* "background colour" above */
 
 /* ---------------------------------------------------------------- mesh extraction (no reference counterpart)
  * Marching cubes over a density volume sampled from a trained field (Instant-NGP's mesh export).  Additive: NERF_ABI_VERSION

@@ -19,6 +19,7 @@ SIGNATURES = {
     "nerf_pixel_permutation": (_I, [_P, _I64, _I64, _U64, _U64, _P]),
     "nerf_ray_gen": (_I, [_P, _I64, _I, _I, C.POINTER(C.c_double), C.POINTER(C.c_float), _F, _F, _P, _P, _P]),
     "nerf_sample_batch": (_I, [_I64, _I, _I, _U64, _U64, C.POINTER(C.c_double), C.POINTER(C.c_float), _F, _F, _P, _P, _P, _P, _P]),
+    "nerf_sample_batch_rgba": (_I, [_I64, _I, _I, _U64, _U64, C.POINTER(C.c_double), C.POINTER(C.c_float), _F, _F, _P, _P, _P, _P, _P]),
     "nerf_gather_rows": (_I, [_P, _I64, _P, _I64, _I, _P, _P]),
     "nerf_ndc_rays": (_I, [_P, _I64, _I, _I, _F, _F, _P]),
     "nerf_sample_coarse": (_I, [_P, _I64, _I, _I, _F, _P, _P, _P]),
@@ -78,12 +79,17 @@ SIGNATURES = {
     "nerf_composite_packed_mse_backward": (_I, [_P, _P, _I64, _I64, _F, _I, _P, _F, _P, _P, _P, _P]),
     "nerf_composite_packed_distortion": (_I, [_P, _P, _P, _P, _I64, _I64, _F, _I, _I, _P, _P, _P, _P, _P]),
     "nerf_composite_packed_mse_dist_backward": (_I, [_P, _P, _P, _P, _I64, _I64, _F, _I, _I, _P, _F, _F, _P, _P, _P, _P, _P]),
+    "nerf_composite_packed_forward_bg": (_I, [_P, _P, _P, _I64, _I64, _F, _P, _I, _P, _P, _P, _P]),
+    "nerf_composite_packed_distortion_bg": (_I, [_P, _P, _P, _P, _I64, _I64, _F, _I, _P, _I, _P, _P, _P, _P, _P]),
+    "nerf_composite_packed_mse_backward_bg": (_I, [_P, _P, _I64, _I64, _F, _P, _P, _F, _P, _P, _P, _P]),
+    "nerf_composite_packed_mse_dist_backward_bg": (_I, [_P, _P, _P, _P, _I64, _I64, _F, _I, _P, _P, _F, _F, _P, _P, _P, _P, _P]),
     "nerf_ert_march_workspace_bytes": (_I64, [_I64]),
     "nerf_ert_init": (_I, [_I64, _P, _P, _P, _P]),
     "nerf_ert_march_count": (_I, [_P, _I64, _P, _F, _P, _I, _F, _F, _F, _I, _P, _I64, _P, _I, _P, _P, _P]),
     "nerf_ert_march_write": (_I, [_P, _I64, _P, _F, _P, _I, _F, _F, _F, _I, _P, _I64, _P, _I, _P, _P, _P, _P, _P, _P]),
     "nerf_ert_fold": (_I, [_P, _P, _P, _P, _I64, _I64, _I64, _F, _F, _P, _P, _P]),
     "nerf_ert_finish": (_I, [_P, _P, _I64, _I, _P, _P, _P, _P, _P]),
+    "nerf_ert_finish_bg": (_I, [_P, _P, _I64, _P, _I, _P, _P, _P, _P, _P]),
     "nerf_mesh_workspace_bytes": (_I64, [_I]),
     "nerf_mesh_points": (_I, [_I, C.POINTER(C.c_float), C.POINTER(C.c_float), _I64, _I64, _P, _P, _P]),
     "nerf_mesh_count": (_I, [_P, _I, _F, _P, _P, _P]),

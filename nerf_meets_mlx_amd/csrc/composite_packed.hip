@@ -289,6 +289,141 @@ __global__ void __launch_bounds__(256) composite_packed_dist_train_kernel(
   if (threadIdx.x == 0 && dist_out) atomicAdd(dist_out, (part[0] + part[1] + part[2] + part[3]) * invB);
 }
 
+// ---- background colour (include/nerf_hip.h "background colour"): the four kernels above over a colour bg instead of white or
+// nothing, rgb = sum w c + (1 - acc) * bg.  Kernels of their own again, so that the ones above keep their ISA; DIST selects the form
+// with the distortion regulariser.  bg: one colour for all rays (stride 0) or one per ray (stride 3), read by every lane of the
+// ray's wave (one address: a broadcast).  Extra traffic per ray: 12 B of bg forward; training 16 + 12 B of target_rgba + bg
+// instead of 12 B of target.
+template <bool DIST>
+__global__ void __launch_bounds__(256) composite_packed_bg_fwd_kernel(const float* __restrict__ raw, const float* __restrict__ z,
+                                                                      const int64_t* __restrict__ offsets,
+                                                                      const float* __restrict__ rays, int64_t B, int64_t K,
+                                                                      float step, float diag, float c1, const float* __restrict__ bg,
+                                                                      int bg_stride, float* __restrict__ rgb, float* __restrict__ acc,
+                                                                      float* __restrict__ depth, float* __restrict__ dist) {
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+  for (int64_t ray = blockIdx.x * 4 + wv; ray < B; ray += (int64_t)gridDim.x * 4) {
+    int64_t s0, s1;
+    bool bad;
+    segment(offsets, ray, K, s0, s1, bad);
+    DistRay dr = {0.0f, 0.0f, false};
+    if constexpr (DIST) dr = dist_ray(rays, z, ray, s0, s1, diag);
+    float carry = 0.0f, sr = 0.0f, sg = 0.0f, sb = 0.0f, sa = 0.0f, sd = 0.0f, Wc = 0.0f, Uc = 0.0f, pl = 0.0f, pq = 0.0f;
+    for (int64_t c0 = s0; c0 < s1; c0 += 64) {
+      float tot;
+      const PackedQ q = packed_chunk(raw, c0, s1, lane, step, carry, tot);
+      const float zk = c0 + lane < s1 ? z[c0 + lane] : 0.0f;
+      sr += q.w * q.r; sg += q.w * q.g; sb += q.w * q.b; sa += q.w; sd += q.w * zk;
+      carry += tot;
+      if constexpr (DIST) {
+        const DistQ e = dist_chunk(z, c0, s1, lane, dr, q.w, Wc, Uc);
+        pl += q.w * (e.u * e.Wl - e.Ul); pq += q.w * q.w;
+      }
+    }
+    sr = wave_sum(sr); sg = wave_sum(sg); sb = wave_sum(sb); sa = wave_sum(sa); sd = wave_sum(sd);
+    if constexpr (DIST) { pl = wave_sum(pl); pq = wave_sum(pq); }
+    if (lane == 0) {
+      const float* c = bg + ray * bg_stride;
+      float L = dr.on ? 2.0f * pl + c1 * pq : 0.0f;
+      sr = sr + (1.0f - sa) * c[0]; sg = sg + (1.0f - sa) * c[1]; sb = sb + (1.0f - sa) * c[2];
+      if (bad) sr = sg = sb = sa = sd = L = __builtin_nanf("");
+      rgb[ray * 3 + 0] = sr; rgb[ray * 3 + 1] = sg; rgb[ray * 3 + 2] = sb;
+      if (acc) acc[ray] = sa;
+      if (depth) depth[ray] = sd;
+      if constexpr (DIST) dist[ray] = L;
+    }
+  }
+}
+
+// The training kernels above against a straight RGBA target over a per-ray background: the target t_c = rgba_c * a + bg_c * (1 - a)
+// is formed here (no composited target through HBM), the rendered ray gets (1 - acc) * bg_c, and acc's adjoint becomes
+//   gacc = -((gr * bg_r + gg * bg_g) + gb * bg_b)
+// Everything behind gacc (G_k, the suffix sums, the trunc_exp backward, the distortion term) is the code of the kernels above.
+template <bool DIST>
+__global__ void __launch_bounds__(256) composite_packed_bg_train_kernel(
+    const float* __restrict__ raw, const float* __restrict__ z, const int64_t* __restrict__ offsets, const float* __restrict__ rays,
+    int64_t B, int64_t K, float step, float diag, float c1, const float* __restrict__ target_rgba, const float* __restrict__ bg,
+    float grad_scale, float coef, float* __restrict__ loss, float* __restrict__ dist_out, float* __restrict__ rgb_out,
+    float* __restrict__ d_raw) {
+  __shared__ float part[4];
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+  const float inv = 1.0f / (float)(B * 3), invB = 1.0f / (float)B, c2 = 2.0f * c1;
+  float sq = 0.0f, sl = 0.0f;
+  for (int64_t ray = blockIdx.x * 4 + wv; ray < B; ray += (int64_t)gridDim.x * 4) {
+    int64_t s0, s1;
+    bool bad;
+    segment(offsets, ray, K, s0, s1, bad);
+    DistRay dr = {0.0f, 0.0f, false};
+    if constexpr (DIST) dr = dist_ray(rays, z, ray, s0, s1, diag);
+    float carry = 0.0f, carries = 0.0f, wcs = 0.0f, ucs = 0.0f, sr = 0.0f, sg = 0.0f, sb = 0.0f, sa = 0.0f;
+    float Wc = 0.0f, Uc = 0.0f, pl = 0.0f, pq = 0.0f;
+    int nch = 0;
+    for (int64_t c0 = s0; c0 < s1; c0 += 64, ++nch) {
+      if (lane == nch) { carries = carry; wcs = Wc; ucs = Uc; }
+      float tot;
+      const PackedQ q = packed_chunk(raw, c0, s1, lane, step, carry, tot);
+      sr += q.w * q.r; sg += q.w * q.g; sb += q.w * q.b; sa += q.w;
+      carry += tot;
+      if constexpr (DIST) {
+        const DistQ e = dist_chunk(z, c0, s1, lane, dr, q.w, Wc, Uc);
+        pl += q.w * (e.u * e.Wl - e.Ul); pq += q.w * q.w;
+      }
+    }
+    sr = wave_sum(sr); sg = wave_sum(sg); sb = wave_sum(sb); sa = wave_sum(sa);
+    if constexpr (DIST) { pl = wave_sum(pl); pq = wave_sum(pq); }
+    const float4 tv = *reinterpret_cast<const float4*>(target_rgba + ray * 4);
+    const float br = bg[ray * 3], bgn = bg[ray * 3 + 1], bb = bg[ray * 3 + 2];
+    const float tr = tv.x * tv.w + br * (1.0f - tv.w), tg = tv.y * tv.w + bgn * (1.0f - tv.w), tb = tv.z * tv.w + bb * (1.0f - tv.w);
+    sr = sr + (1.0f - sa) * br; sg = sg + (1.0f - sa) * bgn; sb = sb + (1.0f - sa) * bb;
+    if (bad) sr = sg = sb = __builtin_nanf("");
+    const float er = sr - tr, eg = sg - tg, eb = sb - tb;
+    if (lane == 0) {
+      sq += er * er; sq += eg * eg; sq += eb * eb;
+      if constexpr (DIST) sl += bad ? __builtin_nanf("") : dr.on ? 2.0f * pl + c1 * pq : 0.0f;
+      if (rgb_out) { rgb_out[ray * 3] = sr; rgb_out[ray * 3 + 1] = sg; rgb_out[ray * 3 + 2] = sb; }
+    }
+    const float gr = grad_scale * 2.0f * er * inv, gg = grad_scale * 2.0f * eg * inv, gb = grad_scale * 2.0f * eb * inv;
+    const float gacc = 0.0f - ((gr * br + gg * bgn) + gb * bb);
+    const float W = Wc, U = Uc;
+    float suffix = 0.0f;                                         // sum of G w over the chunks after this one
+    for (int c = nch - 1; c >= 0; --c) {
+      const int64_t c0 = s0 + (int64_t)c * 64;
+      const float cin = __shfl(carries, c, WAVE);
+      float tot;
+      const PackedQ q = packed_chunk(raw, c0, s1, lane, step, cin, tot);
+      float G = gr * q.r + gg * q.g + gb * q.b + gacc;
+      if constexpr (DIST) {
+        float Wk = __shfl(wcs, c, WAVE), Uk = __shfl(ucs, c, WAVE);
+        const DistQ e = dist_chunk(z, c0, s1, lane, dr, q.w, Wk, Uk);
+        const float inter = e.u * ((2.0f * e.Wl + q.w) - W) - ((2.0f * e.Ul + q.w * e.u) - U);
+        if (dr.on) G = G + coef * (2.0f * inter + c2 * q.w);
+      }
+      const float gw = G * q.w;
+      const float rincl = wave_rscan_incl(gw, lane);
+      const float dn = __shfl_down(rincl, 1, WAVE);
+      const float after = suffix + (lane == 63 ? 0.0f : dn);   // sum over the samples k' > k of the ray
+      const int64_t k = c0 + lane;
+      if (k < s1) {
+        const float sig = raw[4 * k + 3];
+        const float dx = G * q.T * expf(-q.x) - after;
+        float4 o;
+        o.x = q.w * gr; o.y = q.w * gg; o.z = q.w * gb; o.w = dx * step * expf(fminf(sig, 15.0f));
+        *reinterpret_cast<float4*>(d_raw + 4 * k) = o;
+      }
+      suffix += __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, rincl), 0));
+    }
+  }
+  if (lane == 0) part[wv] = sq;
+  __syncthreads();
+  if (threadIdx.x == 0 && loss) atomicAdd(loss, (part[0] + part[1] + part[2] + part[3]) * inv);
+  if constexpr (DIST) {
+    __syncthreads();                                             // the same 16 B carry the second sum
+    if (lane == 0) part[wv] = sl;
+    __syncthreads();
+    if (threadIdx.x == 0 && dist_out) atomicAdd(dist_out, (part[0] + part[1] + part[2] + part[3]) * invB);
+  }
+}
+
 // ---- round renderer with early ray termination (include/nerf_hip.h "early ray termination").  Per ray: istate int32 [4] = (next
 // candidate k, kept count, samples folded, flags), fstate float [6] = (carry, r, g, b, acc, depth).
 // init: 40 B of state and 4 B of live id written per ray, nothing read.
@@ -356,6 +491,21 @@ __global__ void ert_finish_kernel(const int* __restrict__ istate, const float* _
     const float a = fs[4];
     if (white) { r = r + (1.0f - a); g = g + (1.0f - a); bl = bl + (1.0f - a); }
     rgb[3 * b] = r; rgb[3 * b + 1] = g; rgb[3 * b + 2] = bl;
+    if (acc) acc[b] = a;
+    if (depth) depth[b] = fs[5];
+    if (samples) samples[b] = istate[4 * b + 2];
+  }
+}
+
+// finish over a background colour (bg as in the packed kernels above): 40 B of state and 12 B of bg read, 24 B written per ray.
+__global__ void ert_finish_bg_kernel(const int* __restrict__ istate, const float* __restrict__ fstate, int64_t B,
+                                     const float* __restrict__ bg, int bg_stride, float* __restrict__ rgb, float* __restrict__ acc,
+                                     float* __restrict__ depth, int* __restrict__ samples) {
+  for (int64_t b = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; b < B; b += (int64_t)gridDim.x * blockDim.x) {
+    const float* fs = fstate + 6 * b;
+    const float* c = bg + b * bg_stride;
+    const float a = fs[4];
+    rgb[3 * b] = fs[1] + (1.0f - a) * c[0]; rgb[3 * b + 1] = fs[2] + (1.0f - a) * c[1]; rgb[3 * b + 2] = fs[3] + (1.0f - a) * c[2];
     if (acc) acc[b] = a;
     if (depth) depth[b] = fs[5];
     if (samples) samples[b] = istate[4 * b + 2];
@@ -440,6 +590,80 @@ extern "C" int nerf_composite_packed_mse_dist_backward(const float* raw, const f
   return check_launch("nerf_composite_packed_mse_dist_backward");
 }
 
+// ---- background colour: the entries above over bg (stride 0: one colour, 3: one per ray)
+static int bg_args(const char* who, int64_t B, int64_t K, float step_world, int bg_stride) {
+  NERF_REQUIRE(B >= 0 && K >= 0, NERF_E_SHAPE, "%s: bad sizes", who);
+  NERF_REQUIRE(step_world > 0.0f, NERF_E_SHAPE, "%s: step_world must be > 0", who);
+  NERF_REQUIRE(bg_stride == 0 || bg_stride == 3, NERF_E_SHAPE, "%s: bg_stride must be 0 (one colour) or 3 (one per ray)", who);
+  return NERF_OK;
+}
+
+extern "C" int nerf_composite_packed_forward_bg(const float* raw, const float* z, const int64_t* offsets, int64_t B, int64_t K,
+                                                float step_world, const float* bg, int bg_stride, float* rgb, float* acc,
+                                                float* depth, void* stream) {
+  if (const int rc = bg_args("nerf_composite_packed_forward_bg", B, K, step_world, bg_stride)) return rc;
+  if (B == 0) return NERF_OK;
+  NERF_REQUIRE(offsets && bg && rgb && (K == 0 || (raw && z)), NERF_E_NULL, "nerf_composite_packed_forward_bg: NULL pointer");
+  NERF_REQUIRE(K == 0 || aligned16(raw), NERF_E_SHAPE, "nerf_composite_packed_forward_bg: raw must be 16-byte aligned");
+  const dim3 g((unsigned)((B + 3) / 4 > 8192 ? 8192 : (B + 3) / 4)), b(256);
+  hipLaunchKernelGGL(composite_packed_bg_fwd_kernel<false>, g, b, 0, as_stream(stream), raw, z, offsets, (const float*)nullptr, B, K,
+                     step_world, 0.0f, 0.0f, bg, bg_stride, rgb, acc, depth, (float*)nullptr);
+  return check_launch("nerf_composite_packed_forward_bg");
+}
+
+extern "C" int nerf_composite_packed_distortion_bg(const float* raw, const float* z, const int64_t* offsets, const float* rays,
+                                                   int64_t B, int64_t K, float step_world, int march_steps, const float* bg,
+                                                   int bg_stride, float* rgb, float* acc, float* depth, float* dist, void* stream) {
+  if (const int rc = dist_args("nerf_composite_packed_distortion_bg", B, K, step_world, march_steps)) return rc;
+  if (const int rc = bg_args("nerf_composite_packed_distortion_bg", B, K, step_world, bg_stride)) return rc;
+  if (B == 0) return NERF_OK;
+  NERF_REQUIRE(offsets && rays && bg && rgb && dist && (K == 0 || (raw && z)), NERF_E_NULL,
+               "nerf_composite_packed_distortion_bg: NULL pointer");
+  NERF_REQUIRE(K == 0 || aligned16(raw), NERF_E_SHAPE, "nerf_composite_packed_distortion_bg: raw must be 16-byte aligned");
+  const float S = (float)march_steps;
+  const dim3 g((unsigned)((B + 3) / 4 > 8192 ? 8192 : (B + 3) / 4)), b(256);
+  hipLaunchKernelGGL(composite_packed_bg_fwd_kernel<true>, g, b, 0, as_stream(stream), raw, z, offsets, rays, B, K, step_world,
+                     S * step_world, (1.0f / S) / 3.0f, bg, bg_stride, rgb, acc, depth, dist);
+  return check_launch("nerf_composite_packed_distortion_bg");
+}
+
+extern "C" int nerf_composite_packed_mse_backward_bg(const float* raw, const int64_t* offsets, int64_t B, int64_t K, float step_world,
+                                                     const float* target_rgba, const float* bg, float grad_scale, float* loss_out,
+                                                     float* rgb, float* d_raw, void* stream) {
+  if (const int rc = bg_args("nerf_composite_packed_mse_backward_bg", B, K, step_world, 3)) return rc;
+  if (B == 0) return NERF_OK;
+  NERF_REQUIRE(offsets && target_rgba && bg && (K == 0 || (raw && d_raw)), NERF_E_NULL,
+               "nerf_composite_packed_mse_backward_bg: NULL pointer");
+  NERF_REQUIRE(aligned16(target_rgba) && (K == 0 || (aligned16(raw) && aligned16(d_raw))), NERF_E_SHAPE,
+               "nerf_composite_packed_mse_backward_bg: target_rgba / raw / d_raw must be 16-byte aligned");
+  const dim3 g((unsigned)((B + 3) / 4 > 8192 ? 8192 : (B + 3) / 4)), b(256);
+  hipLaunchKernelGGL(composite_packed_bg_train_kernel<false>, g, b, 0, as_stream(stream), raw, (const float*)nullptr, offsets,
+                     (const float*)nullptr, B, K, step_world, 0.0f, 0.0f, target_rgba, bg, grad_scale, 0.0f, loss_out,
+                     (float*)nullptr, rgb, d_raw);
+  return check_launch("nerf_composite_packed_mse_backward_bg");
+}
+
+extern "C" int nerf_composite_packed_mse_dist_backward_bg(const float* raw, const float* z, const int64_t* offsets, const float* rays,
+                                                          int64_t B, int64_t K, float step_world, int march_steps,
+                                                          const float* target_rgba, const float* bg, float grad_scale,
+                                                          float dist_weight, float* loss_out, float* dist_out, float* rgb,
+                                                          float* d_raw, void* stream) {
+  if (const int rc = dist_args("nerf_composite_packed_mse_dist_backward_bg", B, K, step_world, march_steps)) return rc;
+  NERF_REQUIRE(dist_weight >= 0.0f && dist_weight <= 3.4028234664e38f, NERF_E_SHAPE,
+               "nerf_composite_packed_mse_dist_backward_bg: dist_weight must be finite and >= 0");
+  if (B == 0) return NERF_OK;
+  NERF_REQUIRE(offsets && rays && target_rgba && bg && (K == 0 || (raw && z && d_raw)), NERF_E_NULL,
+               "nerf_composite_packed_mse_dist_backward_bg: NULL pointer");
+  NERF_REQUIRE(aligned16(target_rgba) && (K == 0 || (aligned16(raw) && aligned16(d_raw))), NERF_E_SHAPE,
+               "nerf_composite_packed_mse_dist_backward_bg: target_rgba / raw / d_raw must be 16-byte aligned");
+  const float S = (float)march_steps;
+  const dim3 g((unsigned)((B + 3) / 4 > 8192 ? 8192 : (B + 3) / 4)), b(256);
+  hipLaunchKernelGGL(composite_packed_bg_train_kernel<true>, g, b, 0, as_stream(stream), raw, z, offsets, rays, B, K, step_world,
+                     S * step_world, (1.0f / S) / 3.0f, target_rgba, bg, grad_scale, grad_scale * dist_weight * (1.0f / (float)B),
+                     loss_out, dist_out, rgb, d_raw);
+  return check_launch("nerf_composite_packed_mse_dist_backward_bg");
+}
+
 extern "C" int nerf_ert_init(int64_t B, int* istate, float* fstate, int* live, void* stream) {
   NERF_REQUIRE(B >= 0 && B < (1ll << 31), NERF_E_SHAPE, "nerf_ert_init: need 0 <= B < 2^31");
   if (B == 0) return NERF_OK;
@@ -469,4 +693,15 @@ extern "C" int nerf_ert_finish(const int* istate, const float* fstate, int64_t B
   hipLaunchKernelGGL(ert_finish_kernel, dim3(grid_for(B, 256)), dim3(256), 0, as_stream(stream), istate, fstate, B, white_bkgd, rgb,
                      acc, depth, samples);
   return check_launch("nerf_ert_finish");
+}
+
+extern "C" int nerf_ert_finish_bg(const int* istate, const float* fstate, int64_t B, const float* bg, int bg_stride, float* rgb,
+                                  float* acc, float* depth, int* samples, void* stream) {
+  NERF_REQUIRE(B >= 0 && B < (1ll << 31), NERF_E_SHAPE, "nerf_ert_finish_bg: need 0 <= B < 2^31");
+  NERF_REQUIRE(bg_stride == 0 || bg_stride == 3, NERF_E_SHAPE, "nerf_ert_finish_bg: bg_stride must be 0 (one colour) or 3 (one per ray)");
+  if (B == 0) return NERF_OK;
+  NERF_REQUIRE(istate && fstate && bg && rgb, NERF_E_NULL, "nerf_ert_finish_bg: NULL pointer");
+  hipLaunchKernelGGL(ert_finish_bg_kernel, dim3(grid_for(B, 256)), dim3(256), 0, as_stream(stream), istate, fstate, B, bg, bg_stride,
+                     rgb, acc, depth, samples);
+  return check_launch("nerf_ert_finish_bg");
 }

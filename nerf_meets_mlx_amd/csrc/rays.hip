@@ -98,6 +98,19 @@ __global__ void sample_batch_kernel(int64_t n, uint64_t domain, uint64_t offset,
   }
 }
 
+// sample_batch_kernel for a straight RGBA image [H*W, 4]: the same permutation and rays, one 16-byte gather per pixel
+__global__ void sample_batch_rgba_kernel(int64_t n, uint64_t domain, uint64_t offset, PermKey key, int W, Cam cam, float near,
+                                         float far, const float4* __restrict__ image, float* __restrict__ rays,
+                                         float4* __restrict__ target, int64_t* __restrict__ idx_out) {
+  for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
+    uint64_t v = offset + (uint64_t)i;
+    do { v = feistel(v, key); } while (v >= domain);
+    write_ray(i, (int64_t)v, W, cam, near, far, rays, nullptr);
+    target[i] = image[v];
+    if (idx_out) idx_out[i] = (int64_t)v;
+  }
+}
+
 // An index outside [0, n_src) never reads: its output row is NaN (the launch is asynchronous, so it cannot fail)
 __global__ void gather_rows_kernel(const float* __restrict__ src, int64_t n_src, const int64_t* __restrict__ idx,
                                    int64_t n, int C, float* __restrict__ out) {
@@ -193,6 +206,23 @@ extern "C" int nerf_sample_batch(int64_t n, int H, int W, uint64_t seed, uint64_
   hipLaunchKernelGGL(sample_batch_kernel, dim3(grid_for(n, 256)), dim3(256), 0, as_stream(stream), n, domain, offset,
                      make_key(seed, domain), W, make_cam(K, c2w), near, far, image, rays, target, pixel_idx);
   return check_launch("nerf_sample_batch");
+}
+
+extern "C" int nerf_sample_batch_rgba(int64_t n, int H, int W, uint64_t seed, uint64_t offset, const double* K,
+                                      const float* c2w, float near, float far, const float* image, float* rays,
+                                      float* target, int64_t* pixel_idx, void* stream) {
+  NERF_REQUIRE(H > 0 && W > 0 && n >= 0, NERF_E_SHAPE, "nerf_sample_batch_rgba: bad H/W/n");
+  NERF_REQUIRE((int64_t)offset + n <= (int64_t)H * W, NERF_E_SHAPE,
+               "nerf_sample_batch_rgba: need offset+n <= H*W (n=%lld H*W=%lld)", (long long)n, (long long)H * W);
+  if (n == 0) return NERF_OK;
+  NERF_REQUIRE(K && c2w && image && rays && target, NERF_E_NULL, "nerf_sample_batch_rgba: NULL pointer");
+  NERF_REQUIRE(((reinterpret_cast<uintptr_t>(image) | reinterpret_cast<uintptr_t>(target)) & 15) == 0, NERF_E_SHAPE,
+               "nerf_sample_batch_rgba: image / target must be 16-byte aligned");
+  const uint64_t domain = (uint64_t)H * (uint64_t)W;
+  hipLaunchKernelGGL(sample_batch_rgba_kernel, dim3(grid_for(n, 256)), dim3(256), 0, as_stream(stream), n, domain, offset,
+                     make_key(seed, domain), W, make_cam(K, c2w), near, far, reinterpret_cast<const float4*>(image), rays,
+                     reinterpret_cast<float4*>(target), pixel_idx);
+  return check_launch("nerf_sample_batch_rgba");
 }
 
 extern "C" int nerf_gather_rows(const float* src, int64_t n_src, const int64_t* idx, int64_t n, int channels,

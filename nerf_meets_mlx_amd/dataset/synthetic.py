@@ -57,8 +57,10 @@ def render_poses() -> torch.Tensor:
 
 @torch.no_grad()
 def render_gt(H: int, W: int, c2w: torch.Tensor, near=2.0, far=6.0, n_samples=192, device="cpu", chunk=1 << 16,
-              dtype=torch.float32) -> torch.Tensor:
-    """[H,W,3] ground-truth image of the teacher field on a white background."""
+              dtype=torch.float32, rgba: bool = False) -> torch.Tensor:
+    """[H,W,3] ground-truth image of the teacher field on a white background; rgba=True: [H,W,4] straight (un-premultiplied)
+    RGBA, the layout of dataloader.load_blender_data: a = sum w, rgb = sum w c / a where a > 0, else 0, so that
+    rgb * a + (1 - a) is the white frame to float32 rounding."""
     K, _ = intrinsics(H, W)
     j, i = torch.meshgrid(torch.arange(H, dtype=torch.float64), torch.arange(W, dtype=torch.float64), indexing="ij")
     dirs = torch.stack([(i - K[0, 2]) / K[0, 0], -(j - K[1, 2]) / K[1, 1], -torch.ones_like(i)], -1).reshape(-1, 3)
@@ -66,7 +68,7 @@ def render_gt(H: int, W: int, c2w: torch.Tensor, near=2.0, far=6.0, n_samples=19
     d = (dirs @ R.T).to(dtype).to(device)
     o = c2w[:3, 3].to(dtype).to(device)
     t = torch.linspace(near, far, n_samples, dtype=dtype, device=device)
-    out = torch.empty(H * W, 3, dtype=dtype, device=device)
+    out = torch.empty(H * W, 4 if rgba else 3, dtype=dtype, device=device)
     for s in range(0, H * W, chunk):
         dd = d[s:s + chunk]
         pts = o + dd[:, None, :] * t[None, :, None]
@@ -75,13 +77,20 @@ def render_gt(H: int, W: int, c2w: torch.Tensor, near=2.0, far=6.0, n_samples=19
         alpha = 1.0 - torch.exp(-sigma * delta)
         T = torch.cumprod(torch.cat([torch.ones_like(alpha[:, :1]), 1.0 - alpha + 1e-10], -1), -1)[:, :-1]
         w = alpha * T
+        if rgba:
+            a = w.sum(1, keepdim=True)
+            c = (w[..., None] * rgb).sum(1)
+            out[s:s + chunk, :3] = torch.where(a > 0, c / a, torch.zeros_like(c))
+            out[s:s + chunk, 3:] = a
+            continue
         out[s:s + chunk] = (w[..., None] * rgb).sum(1) + (1.0 - w.sum(1, keepdim=True))
-    return out.reshape(H, W, 3)
+    return out.reshape(H, W, 4 if rgba else 3)
 
 
-def make_dataset(H: int, W: int, n_train: int, seed: int = 0, device="cpu"):
-    """(images [N,H,W,3] on `device`, poses [N,4,4] cpu, render_poses [160,4,4], [H,W,focal], K)."""
+def make_dataset(H: int, W: int, n_train: int, seed: int = 0, device="cpu", rgba: bool = False):
+    """(images [N,H,W,3] on `device`, poses [N,4,4] cpu, render_poses [160,4,4], [H,W,focal], K); rgba=True: images [N,H,W,4],
+    straight RGBA (render_gt)."""
     poses = train_poses(n_train, seed)
-    imgs = torch.stack([render_gt(H, W, p, device=device) for p in poses], 0)
+    imgs = torch.stack([render_gt(H, W, p, device=device, rgba=rgba) for p in poses], 0)
     K, f = intrinsics(H, W)
     return imgs, poses, render_poses(), [H, W, f], K

@@ -268,13 +268,17 @@ class NGPTrainer(Trainer):
                  n_depth_samples: int = 64, lrate: float = 5e-4, lrate_decay: int = 500, white_bkgd: bool = True,
                  seed: int = 0, device="cuda", chunk: int = 1024 * 32, table_sync: str = "shard", precision: int = 22,
                  occupancy_grid: bool = False, march_steps: Optional[int] = None, min_transmittance: Optional[float] = None,
-                 distortion_weight: Optional[float] = None, **hash_kw):
+                 distortion_weight: Optional[float] = None, random_background: bool = False, **hash_kw):
         """occupancy_grid: empty-space skipping (engine/occupancy.py): the grid is updated every UPDATE_EVERY iterations from the
         start; from iteration WARMUP on, training and rendering evaluate only the samples in occupied cells.  Off by default.
         march_steps (needs occupancy_grid=True and a scene box; 1 ... 1024; None: the n_depth_samples stratified grid): the
         occupancy-guided ray march of DESIGN.md section 12 replaces the fixed samples -- each ray is stepped at
         sqrt(3) / march_steps * 2 bound through the box, only the steps in occupied cells (every step inside the box before
-        WARMUP) are evaluated, and they are composited with sigma = trunc_exp(raw)."""
+        WARMUP) are evaluated, and they are composited with sigma = trunc_exp(raw).
+        random_background (needs march_steps and images [N, H, W, 4], straight RGBA in [0, 1] as load_blender_data returns them;
+        DESIGN.md section 16): every training ray gets a colour bg uniform in [0, 1)^3 (counter stream 5), the target is
+        rgb_gt a_gt + bg (1 - a_gt) and the rendered ray sum w c + (1 - acc) bg, so that opacity is supervised.  A constructor
+        setting like distortion_weight: not checkpointed.  Off by default."""
         if march_steps is not None:
             from .occupancy import check_march_steps
             check_march_steps(march_steps)
@@ -292,6 +296,17 @@ class NGPTrainer(Trainer):
             distortion_weight = check_distortion_weight(distortion_weight)
             if march_steps is None:
                 raise ValueError("NGPTrainer: distortion_weight needs march_steps (the regulariser acts on the march's packed samples)")
+        channels = None if images is None else int(images.shape[-1])
+        if random_background:
+            if march_steps is None:
+                raise ValueError("NGPTrainer: random_background needs march_steps (the background is a mode of the march's packed "
+                                 "compositing)")
+            if channels != 4:
+                raise ValueError(f"NGPTrainer: random_background needs RGBA images [N, H, W, 4], got {channels} channels")
+        elif channels == 4:
+            raise ValueError("NGPTrainer: images with 4 channels (RGBA) need random_background=True (and march_steps); fold them "
+                             "onto a background first otherwise, e.g. with dataset.dataloader.post_load_blender_data")
+        self.random_background = bool(random_background)
         self.march_steps = march_steps
         self.min_transmittance = min_transmittance
         self.distortion_weight = distortion_weight
@@ -308,6 +323,7 @@ class NGPTrainer(Trainer):
             self.grid = OccupancyGrid(self._field, near, far, n_depth_samples, seed=seed, device=self.device,
                                       march_steps=march_steps)
         self._march_gen = torch.Generator(device=self.device) if march_steps is not None else None
+        self._bg_gen = torch.Generator(device=self.device) if self.random_background else None
         # Adam WITH bias correction: without it the first steps are lr * sign(g), which turns bf16 noise in near-zero
         # table gradients into full-size steps and can drive sigma negative everywhere (a dead network under the
         # reference's un-activated sigma).  This loop is our wiring, so the choice is ours; lrate is
@@ -357,13 +373,17 @@ class NGPTrainer(Trainer):
             raise ValueError("NGPTrainer mesh export: the field has no scene box (bound=None), pass aabb=(lo, hi)")
         return [-float(b)] * 3, [float(b)] * 3
 
-    def train_step(self, rays=None, target=None, u=None) -> Dict[str, torch.Tensor]:
+    def train_step(self, rays=None, target=None, u=None, background=None) -> Dict[str, torch.Tensor]:
+        """background (random_background trainers only, with explicit rays and target [B, 4]): the colours bg [B, 3] behind the
+        rays instead of the ones drawn from counter stream 5."""
+        if background is not None and not self.random_background:
+            raise ValueError("NGPTrainer.train_step: background needs a trainer built with random_background=True")
         if rays is None:
             rays, target = self.sample_batch()
         self._opt.learning_rate = self.lrate * (0.1 ** (self.it / (self.lrate_decay * 1000)))
         if self.march_steps is not None:
             self._join_comm()
-            loss, d_raw, dist = self._march_step_forward(rays, target)
+            loss, d_raw, dist = self._march_step_forward(rays, target, background)
         else:
             z = sampling.sample_coarse(rays, self.n)
             self._join_comm()                                # the previous step's table all-gathers (sharded updates)
@@ -444,10 +464,11 @@ class NGPTrainer(Trainer):
             return {"loss_coarse": loss, "loss_distortion": dist}
         return {"loss_coarse": loss}
 
-    def _march_step_forward(self, rays, target):
+    def _march_step_forward(self, rays, target, background=None):
         """March mode, training: grid update -> march (per-ray jitter from counter stream 4) -> fused query of the K packed
-        samples -> packed compositing + MSE backward, with the distortion regulariser when distortion_weight is set.
-        (loss, d_raw [K, 4], mean distortion or None); the last query(train=True) is the packed one."""
+        samples -> packed compositing + MSE backward, with the distortion regulariser when distortion_weight is set and over a
+        random background per ray (counter stream 5, unless `background` [B, 3] is given) against the RGBA target when
+        random_background is.  (loss, d_raw [K, 4], mean distortion or None); the last query(train=True) is the packed one."""
         from .occupancy import WARMUP
         self._grid_for_step(update=True)
         B = rays.shape[0]
@@ -456,6 +477,17 @@ class NGPTrainer(Trainer):
         offsets, rows, z, K = self.grid.march(rays, jitter, use_bits=self.it >= WARMUP)
         self.last_march = (B, K)
         raw = self._field.query_packed(rows, z, train=True)
+        if self.random_background:
+            if background is None:
+                self._bg_gen.manual_seed(parallel.counter_seed(self.seed, self.rank, 5, self.it))
+                background = torch.rand(B, 3, dtype=torch.float32, device=self.device, generator=self._bg_gen)
+            if self.distortion_weight is not None:
+                loss, dist, d_raw, _ = render.composite_packed_mse_dist_backward_bg(raw, z, offsets, rays, self.grid.step_world,
+                                                                                    self.march_steps, target, background,
+                                                                                    self.distortion_weight)
+                return loss, d_raw, dist
+            loss, d_raw, _ = render.composite_packed_mse_backward_bg(raw, offsets, B, self.grid.step_world, target, background)
+            return loss, d_raw, None
         if self.distortion_weight is not None:
             loss, dist, d_raw, _ = render.composite_packed_mse_dist_backward(raw, z, offsets, rays, self.grid.step_world,
                                                                              self.march_steps, target, self.distortion_weight,
@@ -464,10 +496,24 @@ class NGPTrainer(Trainer):
         loss, d_raw, _ = render.composite_packed_mse_backward(raw, offsets, B, self.grid.step_world, target, self.white_bkgd)
         return loss, d_raw, None
 
-    def render_rays(self, rays: torch.Tensor, u=None, aux: bool = False):
+    def render_rays(self, rays: torch.Tensor, u=None, aux: bool = False, background=None):
         """rgb [B, 3] of rays [B, 11], `chunk` rays per call.  aux=True: {"rgb", "acc" [B], "depth" [B]} and, in march mode,
         "samples" [B] int32 (the samples composited per ray); with distortion_weight set (and no early termination) also
-        "distortion" [B], every ray's distortion loss L_b."""
+        "distortion" [B], every ray's distortion loss L_b.
+        background (march mode only; None: white_bkgd decides): 3 numbers, one colour behind all rays, or a tensor [B, 3], one per
+        ray.  (0, 0, 0) with aux=True gives premultiplied colour plus "acc": an RGBA frame."""
+        if background is not None:
+            if self.march_steps is None:
+                raise ValueError("NGPTrainer.render_rays: background needs march_steps (the 64-sample renderers composite onto "
+                                 "white or nothing: white_bkgd)")
+            per_ray = torch.is_tensor(background) and background.dim() == 2
+            if per_ray and tuple(background.shape) != (rays.shape[0], 3):
+                raise ValueError(f"NGPTrainer.render_rays: a per-ray background must be [B, 3] = [{rays.shape[0]}, 3], got "
+                                 f"{list(background.shape)}")
+            if not per_ray:
+                if torch.as_tensor(background).numel() != 3:
+                    raise ValueError(f"NGPTrainer.render_rays: background must be None, 3 numbers or a [B, 3] tensor, got {background!r}")
+                background = N.f32(torch.as_tensor(background, dtype=torch.float32).reshape(3), self.device)
         outs = []
         self._join_comm()
         if self.march_steps is not None:                     # march mode: jitter 0.5, the bitfield once the warm-up is over
@@ -475,19 +521,28 @@ class NGPTrainer(Trainer):
             use_bits = self.it >= WARMUP
             for s in range(0, rays.shape[0], self.chunk):
                 r = N.f32(rays[s:s + self.chunk])
+                bg = background if background is None or background.dim() == 1 else background[s:s + self.chunk]
                 if self.min_transmittance is not None:
-                    o = self.grid.render_ert(self._field, r, 0.5, self.min_transmittance, self.white_bkgd, use_bits=use_bits)
+                    o = self.grid.render_ert(self._field, r, 0.5, self.min_transmittance, self.white_bkgd, use_bits=use_bits,
+                                             background=bg)
                     outs.append(o if aux else o["rgb"])
                     continue
                 offsets, rows, z, K = self.grid.march(r, 0.5, use_bits=use_bits)
                 raw = self._field.query_packed(rows, z)
                 if aux and self.distortion_weight is not None:
-                    rgb, acc, depth, dist = render.composite_packed_distortion(raw, z, offsets, r, self.grid.step_world,
-                                                                               self.march_steps, self.white_bkgd)
+                    if bg is not None:
+                        rgb, acc, depth, dist = render.composite_packed_distortion_bg(raw, z, offsets, r, self.grid.step_world,
+                                                                                      self.march_steps, bg)
+                    else:
+                        rgb, acc, depth, dist = render.composite_packed_distortion(raw, z, offsets, r, self.grid.step_world,
+                                                                                   self.march_steps, self.white_bkgd)
                     outs.append({"rgb": rgb, "acc": acc, "depth": depth, "samples": (offsets[1:] - offsets[:-1]).to(torch.int32),
                                  "distortion": dist})
                     continue
-                rgb, acc, depth = render.composite_packed(raw, z, offsets, r.shape[0], self.grid.step_world, self.white_bkgd)
+                if bg is not None:
+                    rgb, acc, depth = render.composite_packed_bg(raw, z, offsets, r.shape[0], self.grid.step_world, bg)
+                else:
+                    rgb, acc, depth = render.composite_packed(raw, z, offsets, r.shape[0], self.grid.step_world, self.white_bkgd)
                 outs.append({"rgb": rgb, "acc": acc, "depth": depth,
                              "samples": (offsets[1:] - offsets[:-1]).to(torch.int32)} if aux else rgb)
             return _cat(outs, aux)

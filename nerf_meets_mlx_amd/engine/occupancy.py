@@ -319,11 +319,12 @@ class OccupancyGrid:
         return offsets, rows[:K * 11].view(K, 11), zb[:K], K, A_next
 
     def render_ert(self, field, rays, jitter, min_transmittance: float, white_bkgd: bool = False, use_bits: bool = True,
-                   slots: int = 8) -> Dict[str, torch.Tensor]:
+                   slots: int = 8, background=None) -> Dict[str, torch.Tensor]:
         """Render rays [B, 11] through `field` (a HashNeRF) with early ray termination at T < min_transmittance (march mode only).
         Round r gives each live ray m_r = min(march_steps, max(1, slots B // A)) slots, A the rays live before it (slots is a
         tuning knob: by the fold's order no output depends on it).  {"rgb" [B, 3], "acc" [B], "depth" [B], "samples" [B] int32};
-        self.last_ert = {"rounds", "marched"} of the call (marched: samples queried, terminated rays' surplus included)."""
+        self.last_ert = {"rounds", "marched"} of the call (marched: samples queried, terminated rays' surplus included).
+        background (None: white_bkgd decides): 3 numbers or a tensor [B, 3], the colour behind the rays (`nerf_ert_finish_bg`)."""
         if self.march_steps is None:
             raise ValueError("OccupancyGrid.render_ert: the grid was built without march_steps")
         eps = check_min_transmittance(min_transmittance)
@@ -347,7 +348,10 @@ class OccupancyGrid:
             A, la, lb = A_next, lb, la
             rounds += 1
             total += K
-        rgb, acc, depth, samples = render.ert_finish(istate, fstate, white_bkgd)
+        if background is not None:
+            rgb, acc, depth, samples = render.ert_finish_bg(istate, fstate, background)
+        else:
+            rgb, acc, depth, samples = render.ert_finish(istate, fstate, white_bkgd)
         self.last_ert = {"rounds": rounds, "marched": total}
         return {"rgb": rgb, "acc": acc, "depth": depth, "samples": samples}
 

@@ -39,7 +39,7 @@ class Trainer:
                  lrate_decay: int = 500, white_bkgd: bool = True, ref_quirks: bool = True, seed: int = 0,
                  device="cuda", chunk: int = 1024 * 32, precision: int = 22, overlap_comm: bool = True):
         self.device = torch.device(device)
-        self.images = images.to(self.device, torch.float32).contiguous()      # [N,H,W,3], white-composited
+        self.images = images.to(self.device, torch.float32).contiguous()      # [N,H,W,3], white-composited (or [N,H,W,4] RGBA)
         self.poses = poses.float().cpu()
         self.K = np.asarray(K, dtype=np.float64)
         self.H, self.W = int(images.shape[1]), int(images.shape[2])
@@ -120,14 +120,15 @@ class Trainer:
         return loss
 
     def sample_batch(self, pixel_idx: Optional[torch.Tensor] = None, img_i: Optional[int] = None):
-        """(rays [B,11], target [B,3]); by default one random image, N_rand distinct pixels."""
+        """(rays [B,11], target [B,3]); by default one random image, N_rand distinct pixels.  RGBA images give target [B,4]: the
+        same pixels and rays as the 3-channel call at the same (seed, rank, it), bit for bit."""
         if img_i is None:
             img_i = self.image_choice()
         if pixel_idx is None:                                                  # the usual case: one fused launch
             return ray.sample_batch(self.H, self.W, self.K, self.poses[img_i, :3, :4], self.near, self.far,
                                     self.images[img_i], self.N_rand, parallel.counter_seed(self.seed, self.rank, 3, self.it))
         rays = ray.gen_rays(self.H, self.W, self.K, self.poses[img_i, :3, :4], self.near, self.far, pixel_idx)
-        target = index.gather_rows(self.images[img_i].reshape(-1, 3), pixel_idx)
+        target = index.gather_rows(self.images[img_i].reshape(-1, self.images.shape[-1]), pixel_idx)
         return rays, target
 
     def train_step(self, rays=None, target=None, u=None) -> Dict[str, torch.Tensor]:
@@ -150,9 +151,13 @@ class Trainer:
         return out
 
     # ---------------------------------------------------------------- rendering
-    def render_rays(self, rays: torch.Tensor, u=None):
+    def render_rays(self, rays: torch.Tensor, u=None, background=None):
         """render_rays_eval on packed rays, chunked like batchify_rays (`chunk` rays per call of the fused
-        renderer `nerf_render_rays_fused`); returns rgb [B,3]."""
+        renderer `nerf_render_rays_fused`); returns rgb [B,3].  background: None only (a colour behind the rays is a mode of
+        NGPTrainer's march)."""
+        if background is not None:
+            raise ValueError("Trainer.render_rays: background is a mode of NGPTrainer's march; this renderer composites onto white "
+                             "or nothing (white_bkgd)")
         outs = []
         for s in range(0, rays.shape[0], self.chunk):
             r = rays[s:s + self.chunk]
@@ -163,21 +168,27 @@ class Trainer:
                                                  white_bkgd=self.white_bkgd, ref_quirks=self.q, with_coarse=False)["rgb_map"])
         return torch.cat(outs, 0)
 
-    def render_frame(self, c2w, shard: bool = True) -> Optional[torch.Tensor]:
+    def render_frame(self, c2w, shard: bool = True, background=None) -> Optional[torch.Tensor]:
         """Full frame [H,W,3]; with world_size > 1 each rank renders a contiguous slice of the
-        pixel list and rank 0 receives the image (others return None)."""
+        pixel list and rank 0 receives the image (others return None).  background: see render_rays (a [H W, 3] tensor is one
+        colour per pixel)."""
         lo, hi = parallel.shard_range(self.H * self.W, self.rank, self.world) if shard else (0, self.H * self.W)
         idx = torch.arange(lo, hi, device=self.device, dtype=torch.int64)
         rays = ray.gen_rays(self.H, self.W, self.K, np.asarray(c2w)[:3, :4], self.near, self.far, idx)
-        rgb = self.render_rays(rays)
+        if background is None:
+            rgb = self.render_rays(rays)
+        else:
+            per_pixel = torch.is_tensor(background) and background.dim() == 2 and background.shape[0] == self.H * self.W
+            rgb = self.render_rays(rays, background=background[lo:hi] if per_pixel else background)
         if shard and self.world > 1:
             rgb = parallel.gather_rows_to_rank0(rgb, self.H * self.W)
             if rgb is None:
                 return None
         return rgb.reshape(self.H, self.W, 3)
 
-    def psnr(self, c2w, gt: torch.Tensor) -> float:
-        img = self.render_frame(c2w, shard=False)
+    def psnr(self, c2w, gt: torch.Tensor, background=None) -> float:
+        """PSNR of the frame rendered over `background` (see render_rays) against gt [H,W,3], the truth over the same background."""
+        img = self.render_frame(c2w, shard=False, background=background)
         mse = torch.mean((img - gt.to(self.device)) ** 2)
         return float(10.0 * torch.log10(1.0 / mse))
 

@@ -38,14 +38,19 @@ def gen_rays(H: int, W: int, K, c2w, near: float, far: float, pixel_idx: Optiona
 def sample_batch(H: int, W: int, K, c2w, near: float, far: float, image: torch.Tensor, n: int, seed: int, offset: int = 0,
                  return_idx: bool = False):
     """One training batch in one launch (`nerf_sample_batch`): n distinct pixels of `image` [H,W,3] (the keyed permutation
-    of ops.index.pixel_permutation), their packed rays [n,11] and target colours [n,3] -- `__test_nerf.py:213-236, 60-82`."""
-    img = N.f32(image).reshape(-1, 3)
+    of ops.index.pixel_permutation), their packed rays [n,11] and target colours [n,3] -- `__test_nerf.py:213-236, 60-82`.
+    An [H,W,4] image (straight RGBA) gives target [n,4] through `nerf_sample_batch_rgba`: the same pixels and rays, bit for bit."""
+    ch = int(image.shape[-1])
+    if ch not in (3, 4):
+        raise ValueError(f"sample_batch: image must be [H, W, 3] or [H, W, 4] (straight RGBA), got {list(image.shape)}")
+    img = N.f32(image).reshape(-1, ch)
     rays = torch.empty(n, 11, dtype=torch.float32, device=img.device)
-    target = torch.empty(n, 3, dtype=torch.float32, device=img.device)
+    target = torch.empty(n, ch, dtype=torch.float32, device=img.device)
     idx = torch.empty(n, dtype=torch.int64, device=img.device) if return_idx else None
     Kc, cc = _host_cam(K, c2w)
-    N.check(N.lib().nerf_sample_batch(n, H, W, seed & ((1 << 64) - 1), offset, Kc, cc, float(near), float(far), N.ptr(img),
-                                      N.ptr(rays), N.ptr(target), N.ptr(idx), N.stream()))
+    fn = N.lib().nerf_sample_batch if ch == 3 else N.lib().nerf_sample_batch_rgba      # the same pixels and rays, a 4-float gather
+    N.check(fn(n, H, W, seed & ((1 << 64) - 1), offset, Kc, cc, float(near), float(far), N.ptr(img),
+               N.ptr(rays), N.ptr(target), N.ptr(idx), N.stream()))
     return (rays, target, idx) if return_idx else (rays, target)
 
 

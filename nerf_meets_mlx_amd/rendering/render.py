@@ -128,6 +128,101 @@ def composite_packed_mse_dist_backward(raw, z, offsets, rays, step_world: float,
     return loss, dist, d_raw, rgb
 
 
+def background_arg(background, B: int, device):
+    """(bg float32 device tensor, stride) for the *_bg entry points ("background colour" in include/nerf_hip.h): a 3-tuple (or a
+    tensor [3]) is one colour for all rays, stride 0 -- no [B, 3] buffer; a tensor [B, 3] is one colour per ray, stride 3."""
+    if torch.is_tensor(background) and background.dim() == 2:
+        if tuple(background.shape) != (B, 3):
+            raise ValueError(f"background: a per-ray background must be [B, 3] = [{B}, 3], got {list(background.shape)}")
+        return N.f32(background, device), 3
+    bg = torch.as_tensor(background, dtype=torch.float32).reshape(-1)
+    if bg.numel() != 3:
+        raise ValueError(f"background must be None, 3 numbers or a [B, 3] tensor, got {background!r}")
+    return N.f32(bg, device), 0
+
+
+def composite_packed_bg(raw, z, offsets, B: int, step_world: float, background):
+    """composite_packed over a background colour (`nerf_composite_packed_forward_bg`): rgb = sum w c + (1 - acc) * bg.
+    background: 3 numbers, or a tensor [B, 3] (one colour per ray)."""
+    raw = N.f32(raw).reshape(-1, 4)
+    z = N.f32(z).reshape(-1)
+    K = raw.shape[0]
+    dev = offsets.device
+    bg, stride = background_arg(background, B, dev)
+    rgb = torch.empty(B, 3, dtype=torch.float32, device=dev)
+    acc = torch.empty(B, dtype=torch.float32, device=dev)
+    depth = torch.empty(B, dtype=torch.float32, device=dev)
+    N.check(N.lib().nerf_composite_packed_forward_bg(N.ptr(raw) if K else None, N.ptr(z) if K else None, N.ptr(offsets), B, K,
+                                                     float(step_world), N.ptr(bg), stride, N.ptr(rgb), N.ptr(acc), N.ptr(depth),
+                                                     N.stream()))
+    return rgb, acc, depth
+
+
+def composite_packed_distortion_bg(raw, z, offsets, rays, step_world: float, march_steps: int, background):
+    """composite_packed_distortion over a background colour (`nerf_composite_packed_distortion_bg`)."""
+    raw = N.f32(raw).reshape(-1, 4)
+    z = N.f32(z).reshape(-1)
+    rays = N.f32(rays)
+    B, K = rays.shape[0], raw.shape[0]
+    dev = offsets.device
+    bg, stride = background_arg(background, B, dev)
+    rgb = torch.empty(B, 3, dtype=torch.float32, device=dev)
+    acc = torch.empty(B, dtype=torch.float32, device=dev)
+    depth = torch.empty(B, dtype=torch.float32, device=dev)
+    dist = torch.empty(B, dtype=torch.float32, device=dev)
+    N.check(N.lib().nerf_composite_packed_distortion_bg(N.ptr(raw) if K else None, N.ptr(z) if K else None, N.ptr(offsets),
+                                                        N.ptr(rays), B, K, float(step_world), int(march_steps), N.ptr(bg), stride,
+                                                        N.ptr(rgb), N.ptr(acc), N.ptr(depth), N.ptr(dist), N.stream()))
+    return rgb, acc, depth, dist
+
+
+def composite_packed_mse_backward_bg(raw, offsets, B: int, step_world: float, target_rgba, background, grad_scale: float = 1.0,
+                                     need_rgb: bool = False):
+    """(loss [1], d_raw [K, 4], rgb [B, 3] or None): composite_packed_mse_backward over a per-ray background [B, 3] against a
+    straight RGBA target [B, 4] (`nerf_composite_packed_mse_backward_bg`): the kernel renders rgb = sum w c + (1 - acc) * bg and
+    forms the target t = rgba[:3] * a + bg * (1 - a) itself."""
+    raw = N.f32(raw).reshape(-1, 4)
+    K = raw.shape[0]
+    dev = offsets.device
+    target_rgba, bg = _rgba_and_bg(target_rgba, background, B, dev)
+    loss = torch.zeros(1, dtype=torch.float32, device=dev)
+    d_raw = torch.empty(K, 4, dtype=torch.float32, device=dev)
+    rgb = torch.empty(B, 3, dtype=torch.float32, device=dev) if need_rgb else None
+    N.check(N.lib().nerf_composite_packed_mse_backward_bg(N.ptr(raw) if K else None, N.ptr(offsets), B, K, float(step_world),
+                                                          N.ptr(target_rgba), N.ptr(bg), float(grad_scale), N.ptr(loss),
+                                                          N.ptr(rgb), N.ptr(d_raw) if K else None, N.stream()))
+    return loss, d_raw, rgb
+
+
+def composite_packed_mse_dist_backward_bg(raw, z, offsets, rays, step_world: float, march_steps: int, target_rgba, background,
+                                          dist_weight: float, grad_scale: float = 1.0, need_rgb: bool = False):
+    """(loss [1], dist [1], d_raw [K, 4], rgb [B, 3] or None): composite_packed_mse_dist_backward over a per-ray background
+    [B, 3] against a straight RGBA target [B, 4] (`nerf_composite_packed_mse_dist_backward_bg`)."""
+    raw = N.f32(raw).reshape(-1, 4)
+    z = N.f32(z).reshape(-1)
+    rays = N.f32(rays)
+    B, K = rays.shape[0], raw.shape[0]
+    dev = offsets.device
+    target_rgba, bg = _rgba_and_bg(target_rgba, background, B, dev)
+    loss = torch.zeros(1, dtype=torch.float32, device=dev)
+    dist = torch.zeros(1, dtype=torch.float32, device=dev)
+    d_raw = torch.empty(K, 4, dtype=torch.float32, device=dev)
+    rgb = torch.empty(B, 3, dtype=torch.float32, device=dev) if need_rgb else None
+    N.check(N.lib().nerf_composite_packed_mse_dist_backward_bg(
+        N.ptr(raw) if K else None, N.ptr(z) if K else None, N.ptr(offsets), N.ptr(rays), B, K, float(step_world), int(march_steps),
+        N.ptr(target_rgba), N.ptr(bg), float(grad_scale), float(dist_weight), N.ptr(loss), N.ptr(dist), N.ptr(rgb),
+        N.ptr(d_raw) if K else None, N.stream()))
+    return loss, dist, d_raw, rgb
+
+
+def _rgba_and_bg(target_rgba, background, B: int, dev):
+    target_rgba, bg = N.f32(target_rgba, dev), N.f32(background, dev)
+    if tuple(target_rgba.shape) != (B, 4) or tuple(bg.shape) != (B, 3):
+        raise ValueError(f"the background training form needs target [B, 4] and background [B, 3] with B = {B}, got "
+                         f"{list(target_rgba.shape)} and {list(bg.shape)}")
+    return target_rgba, bg
+
+
 def ert_init(istate, fstate, live, B: int):
     """Zero the round renderer's state of B rays (istate int32 [B, 4], fstate float32 [B, 6]) and set live = 0 .. B - 1
     (`nerf_ert_init`, include/nerf_hip.h "early ray termination")."""
@@ -155,6 +250,20 @@ def ert_finish(istate, fstate, white_bkgd=False):
     samples = torch.empty(B, dtype=torch.int32, device=dev)
     N.check(N.lib().nerf_ert_finish(N.ptr(istate), N.ptr(fstate), B, int(bool(white_bkgd)), N.ptr(rgb), N.ptr(acc), N.ptr(depth),
                                     N.ptr(samples), N.stream()))
+    return rgb, acc, depth, samples
+
+
+def ert_finish_bg(istate, fstate, background):
+    """ert_finish over a background colour (`nerf_ert_finish_bg`): 3 numbers, or a tensor [B, 3]."""
+    B = istate.shape[0]
+    dev = istate.device
+    bg, stride = background_arg(background, B, dev)
+    rgb = torch.empty(B, 3, dtype=torch.float32, device=dev)
+    acc = torch.empty(B, dtype=torch.float32, device=dev)
+    depth = torch.empty(B, dtype=torch.float32, device=dev)
+    samples = torch.empty(B, dtype=torch.int32, device=dev)
+    N.check(N.lib().nerf_ert_finish_bg(N.ptr(istate), N.ptr(fstate), B, N.ptr(bg), stride, N.ptr(rgb), N.ptr(acc), N.ptr(depth),
+                                       N.ptr(samples), N.stream()))
     return rgb, acc, depth, samples
 
 

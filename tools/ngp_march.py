@@ -6,7 +6,8 @@ N_rand 4096, seed 4, one 32 768-ray render chunk per step), in ONE process:
 
 Arms: "off" (64 stratified samples, no grid), "cull" (64 samples, grid cull) and "march<S>" (the march of
 section 12 with march_steps = S; default 1024 and 512), and "march<S>_ert" (the same march with early ray termination at
-min_transmittance --eps, section 13; trained exactly as "march<S>"), and "march<S>_dist" (the march trained with the distortion
+min_transmittance --eps, section 13; trained exactly as "march<S>"), "march<S>_rbg" / "march<S>_dist_rbg" (the march trained on the
+RGBA frames over a random background per ray, section 16), and "march<S>_dist" (the march trained with the distortion
 regulariser of section 15 at --dist-weight).  Every arm is trained past the grid's warm-up, then the arms alternate
 timed blocks of --block steps until --iters; each step is timed with device events (train step, render chunk).  Per arm: train
 ms / step, render ms / chunk, samples per ray in training and rendering, for march arms the device time of the march (count +
@@ -130,15 +131,18 @@ def main():
     H = W = a.hw
     imgs, poses, rposes, hwf, K = synthetic.make_dataset(H, W, 5, seed=0, device=dev)
     rrays = ray.gen_rays(H, W, K, rposes[40][:3, :4], 2.0, 6.0, torch.arange(a.render_rays, device=dev, dtype=torch.int64))
-    arms = {}
+    arms, imgs_rgba = {}, None
     for name in a.arms.split(","):
-        m = re.fullmatch(r"march(\d+)(_dist)?(_ert)?", name)
+        m = re.fullmatch(r"march(\d+)(_dist)?(_rbg)?(_ert)?", name)
         if m is None and name not in ("off", "cull"):
             ap.error(f"unknown arm {name!r}")
-        steps, dist, ert = (int(m.group(1)), m.group(2) is not None, m.group(3) is not None) if m else (None, False, False)
-        tr = NGPTrainer(imgs[:4], poses[:4], K, N_rand=a.n_rand, n_depth_samples=64, seed=4, device=dev, chunk=a.render_rays,
-                        occupancy_grid=(name != "off"), march_steps=steps, min_transmittance=a.eps if ert else None,
-                        distortion_weight=a.dist_weight if dist else None)
+        steps, dist, rbg, ert = (int(m.group(1)), *(m.group(i) is not None for i in (2, 3, 4))) if m else (None, False, False, False)
+        if rbg and imgs_rgba is None:                       # the same frames as straight RGBA
+            imgs_rgba = synthetic.make_dataset(H, W, 5, seed=0, device=dev, rgba=True)[0]
+        tr = NGPTrainer((imgs_rgba if rbg else imgs)[:4], poses[:4], K, N_rand=a.n_rand, n_depth_samples=64, seed=4, device=dev,
+                        chunk=a.render_rays, occupancy_grid=(name != "off"), march_steps=steps,
+                        min_transmittance=a.eps if ert else None, distortion_weight=a.dist_weight if dist else None,
+                        random_background=rbg)
         arms[name] = {"tr": tr, "train": [], "render": [], "spr_train": [], "spr_render": []}
 
     def step(arm, timed):
@@ -185,6 +189,7 @@ def main():
                 "train_ms_per_step": _ms(arm["train"]), "render_ms_per_chunk": _ms(arm["render"]),
                 "render_ms_per_chunk_p10_p90": _p10_p90(arm["render"]), "min_transmittance": tr.min_transmittance,
                 "distortion_weight": getattr(tr, "distortion_weight", None),
+                "random_background": bool(getattr(tr, "random_background", False)),
                 "device": torch.cuda.get_device_name(dev)}
         g = tr.grid
         if g is None:
@@ -211,7 +216,7 @@ def main():
                                                            torch.arange(H * W, device=dev, dtype=torch.int64))))
         lines.append(line)
     if not a.no_psnr:
-        gt = imgs[4]
+        gt, gt_rgba = imgs[4], None
         white = float(-10.0 * torch.log10(((1.0 - gt.double()) ** 2).mean()))
         for name, line in zip(arms, lines):
             tr = arms[name]["tr"]
@@ -221,6 +226,14 @@ def main():
             if rgb is not None:
                 rgb = torch.as_tensor(rgb)
                 line["heldout_frame_white_fraction"] = float((rgb.reshape(-1, 3) > 0.999).all(-1).double().mean())
+            if tr.march_steps is not None:                  # over black against the teacher's RGBA frame, and opacity against its alpha
+                if gt_rgba is None:
+                    gt_rgba = synthetic.render_gt(H, W, poses[4], device=dev, rgba=True)
+                line["psnr_heldout_black"] = tr.psnr(poses[4][:3, :4].numpy(), gt_rgba[..., :3] * gt_rgba[..., 3:], background=(0.0, 0.0, 0.0))
+                acc = tr.render_rays(ray.gen_rays(H, W, K, poses[4][:3, :4].numpy(), 2.0, 6.0,
+                                                  torch.arange(H * W, device=dev, dtype=torch.int64)), aux=True)["acc"]
+                line["alpha_mae_heldout"] = float((acc - gt_rgba[..., 3].reshape(-1)).abs().double().mean())
+                line["teacher_alpha_mean"] = float(gt_rgba[..., 3].double().mean())
     summary = {"tool": "ngp_march", "summary": True, "wall_s_timed": wall}
     by = dict(zip(arms, lines))
     for ref in ("off", "cull"):
@@ -243,7 +256,7 @@ def stats(a):
     import sqlite3
     db = sqlite3.connect(a.stats)
     for name, calls, avg_ns in db.execute("select name, count(*), avg(end - start) from kernels group by name"):
-        m = re.search(r"(occ_march_\w+|ert_\w+|occ_cull_scan_kernel|occ_merge_exp_kernel|composite_packed_\w+|nerf_ngp\w*|ngp\w*fused\w*|"
+        m = re.search(r"(occ_march_\w+|ert_\w+|occ_cull_scan_kernel|occ_merge_exp_kernel|composite_packed_\w+(?:<\w+>)?|nerf_ngp\w*|ngp\w*fused\w*|"
                       r"hashgrid\w*|composite_train_kernel|occ_cull_\w+)", name)
         if m:
             print(json.dumps({"kernel": m.group(1), "calls": calls, "avg_us": round(avg_ns * 1e-3, 2)}))

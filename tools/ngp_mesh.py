@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """Mesh extraction from the hash-grid field of BASELINE configs[4] (800 x 800 synthetic Lego, 4 training
 views, N_rand 4096, seed 4) trained in march mode (march_steps 512, 2000 iterations: the section-12 run; --dist-weight W trains
-with the distortion regulariser of section 15), or from a checkpoint:
+with the distortion regulariser of section 15, --random-bg on the RGBA frames over a random background per ray, section 16), or
+from a checkpoint:
 
     python tools/ngp_mesh.py --out profiles/ngp_mesh.jsonl [--save-ckpt /tmp/ngp.npz | --ckpt /tmp/ngp.npz]     (GPU)
 
@@ -111,6 +112,8 @@ def main():
     ap.add_argument("--march-steps", type=int, default=512)
     ap.add_argument("--dist-weight", type=float, default=None,
                     help="train with the distortion regulariser at this weight (DESIGN.md section 15); default: without")
+    ap.add_argument("--random-bg", action="store_true",
+                    help="train on the RGBA frames over a random background per ray (DESIGN.md section 16); default: over white")
     ap.add_argument("--res", default="128,256,512")
     ap.add_argument("--threshold", type=float, default=2.5)
     ap.add_argument("--reps", type=int, default=3)
@@ -132,12 +135,12 @@ def main():
     torch.cuda.set_device(dev)
     H = W = a.hw
     if a.ckpt:
-        imgs, poses, K = torch.zeros(1, 8, 8, 3), synthetic.train_poses(1), synthetic.intrinsics(8, 8)[0]
+        imgs, poses, K = torch.zeros(1, 8, 8, 4 if a.random_bg else 3), synthetic.train_poses(1), synthetic.intrinsics(8, 8)[0]
     else:
-        imgs, poses, _, _, K = synthetic.make_dataset(H, W, 5, seed=0, device=dev)
+        imgs, poses, _, _, K = synthetic.make_dataset(H, W, 5, seed=0, device=dev, rgba=a.random_bg)
         imgs, poses = imgs[:4], poses[:4]
     tr = NGPTrainer(imgs, poses, K, N_rand=a.n_rand, n_depth_samples=64, seed=4, device=dev, occupancy_grid=True,
-                    march_steps=a.march_steps, distortion_weight=a.dist_weight)
+                    march_steps=a.march_steps, distortion_weight=a.dist_weight, random_background=a.random_bg)
     if a.ckpt:
         tr.load(a.ckpt)
     else:
@@ -153,7 +156,7 @@ def main():
     lines = []
     for R in [int(r) for r in a.res.split(",")]:
         rec = {"tool": "ngp_mesh", "R": R, "hw": a.hw, "iters": tr.it, "march_steps": a.march_steps, "seed": 4,
-               "distortion_weight": a.dist_weight,
+               "distortion_weight": a.dist_weight, "random_background": bool(a.random_bg),
                "threshold": a.threshold, "activation": "exp", "device": torch.cuda.get_device_name(dev)}
         t_vol, t_mc, t_col = [], [], []
         for _ in range(a.reps):
