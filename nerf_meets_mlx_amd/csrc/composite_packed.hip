@@ -47,101 +47,7 @@ __device__ __forceinline__ void segment(const int64_t* __restrict__ offsets, int
   if (bad) s0 = s1 = 0;
 }
 
-__global__ void __launch_bounds__(256) composite_packed_fwd_kernel(const float* __restrict__ raw, const float* __restrict__ z,
-                                                                   const int64_t* __restrict__ offsets, int64_t B, int64_t K,
-                                                                   float step, int white, float* __restrict__ rgb,
-                                                                   float* __restrict__ acc, float* __restrict__ depth) {
-  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-  for (int64_t ray = blockIdx.x * 4 + wv; ray < B; ray += (int64_t)gridDim.x * 4) {
-    int64_t s0, s1;
-    bool bad;
-    segment(offsets, ray, K, s0, s1, bad);
-    float carry = 0.0f, sr = 0.0f, sg = 0.0f, sb = 0.0f, sa = 0.0f, sd = 0.0f;
-    for (int64_t c0 = s0; c0 < s1; c0 += 64) {
-      float tot;
-      const PackedQ q = packed_chunk(raw, c0, s1, lane, step, carry, tot);
-      const float zk = c0 + lane < s1 ? z[c0 + lane] : 0.0f;
-      sr += q.w * q.r; sg += q.w * q.g; sb += q.w * q.b; sa += q.w; sd += q.w * zk;
-      carry += tot;
-    }
-    sr = wave_sum(sr); sg = wave_sum(sg); sb = wave_sum(sb); sa = wave_sum(sa); sd = wave_sum(sd);
-    if (lane == 0) {
-      if (white) { sr = sr + (1.0f - sa); sg = sg + (1.0f - sa); sb = sb + (1.0f - sa); }
-      if (bad) sr = sg = sb = sa = sd = __builtin_nanf("");
-      rgb[ray * 3 + 0] = sr; rgb[ray * 3 + 1] = sg; rgb[ray * 3 + 2] = sb;
-      if (acc) acc[ray] = sa;
-      if (depth) depth[ray] = sd;
-    }
-  }
-}
-
-// Forward (as above) -> rgb -> squared error against the target -> d loss / d raw of every sample of the ray.  The reverse pass
-// walks the chunks last to first with the suffix sum of G w carried exactly (no total-minus-prefix), and re-derives each chunk's
-// forward quantities from the exponent carried into it, which the forward pass left in lane c of `carries`.
-//   dL/dx_k = G_k T_k exp(-x_k) - sum_{k' > k} G_k' w_k',  G_k = gr r_k + gg g_k + gb b_k + gacc
-//   d_raw[k] = (w_k gr, w_k gg, w_k gb, dL/dx_k * step * exp(min(raw_k[3], 15)))      (trunc_exp backward)
-__global__ void __launch_bounds__(256) composite_packed_train_kernel(const float* __restrict__ raw, const int64_t* __restrict__ offsets,
-                                                                     int64_t B, int64_t K, float step, int white,
-                                                                     const float* __restrict__ target, float grad_scale,
-                                                                     float* __restrict__ loss, float* __restrict__ rgb_out,
-                                                                     float* __restrict__ d_raw) {
-  __shared__ float part[4];
-  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-  const float inv = 1.0f / (float)(B * 3);
-  float sq = 0.0f;
-  for (int64_t ray = blockIdx.x * 4 + wv; ray < B; ray += (int64_t)gridDim.x * 4) {
-    int64_t s0, s1;
-    bool bad;
-    segment(offsets, ray, K, s0, s1, bad);
-    float carry = 0.0f, carries = 0.0f, sr = 0.0f, sg = 0.0f, sb = 0.0f, sa = 0.0f;
-    int nch = 0;
-    for (int64_t c0 = s0; c0 < s1; c0 += 64, ++nch) {
-      if (lane == nch) carries = carry;
-      float tot;
-      const PackedQ q = packed_chunk(raw, c0, s1, lane, step, carry, tot);
-      sr += q.w * q.r; sg += q.w * q.g; sb += q.w * q.b; sa += q.w;
-      carry += tot;
-    }
-    sr = wave_sum(sr); sg = wave_sum(sg); sb = wave_sum(sb); sa = wave_sum(sa);
-    if (white) { sr = sr + (1.0f - sa); sg = sg + (1.0f - sa); sb = sb + (1.0f - sa); }
-    if (bad) sr = sg = sb = __builtin_nanf("");
-    const float er = sr - target[ray * 3], eg = sg - target[ray * 3 + 1], eb = sb - target[ray * 3 + 2];
-    if (lane == 0) {
-      sq += er * er; sq += eg * eg; sq += eb * eb;
-      if (rgb_out) { rgb_out[ray * 3] = sr; rgb_out[ray * 3 + 1] = sg; rgb_out[ray * 3 + 2] = sb; }
-    }
-    const float gr = grad_scale * 2.0f * er * inv, gg = grad_scale * 2.0f * eg * inv, gb = grad_scale * 2.0f * eb * inv;
-    const float gacc = 0.0f - (white ? (gr + gg + gb) : 0.0f);
-    float suffix = 0.0f;                                         // sum of G w over the chunks after this one
-    for (int c = nch - 1; c >= 0; --c) {
-      const int64_t c0 = s0 + (int64_t)c * 64;
-      const float cin = __shfl(carries, c, WAVE);
-      float tot;
-      const PackedQ q = packed_chunk(raw, c0, s1, lane, step, cin, tot);
-      const float G = gr * q.r + gg * q.g + gb * q.b + gacc;
-      const float gw = G * q.w;
-      const float rincl = wave_rscan_incl(gw, lane);
-      const float dn = __shfl_down(rincl, 1, WAVE);
-      const float after = suffix + (lane == 63 ? 0.0f : dn);   // sum over the samples k' > k of the ray
-      const int64_t k = c0 + lane;
-      if (k < s1) {
-        const float sig = raw[4 * k + 3];
-        const float dx = G * q.T * expf(-q.x) - after;
-        float4 o;
-        o.x = q.w * gr; o.y = q.w * gg; o.z = q.w * gb; o.w = dx * step * expf(fminf(sig, 15.0f));
-        *reinterpret_cast<float4*>(d_raw + 4 * k) = o;
-      }
-      suffix += __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, rincl), 0));
-    }
-  }
-  if (lane == 0) part[wv] = sq;
-  __syncthreads();
-  if (threadIdx.x == 0 && loss) atomicAdd(loss, (part[0] + part[1] + part[2] + part[3]) * inv);
-}
-
-// ---- distortion regulariser (include/nerf_hip.h "distortion regulariser"): the two kernels above with L_b and its adjoint.  Kernels
-// of their own, so that the ones above keep their ISA.  Extra traffic: z (4 B per sample, read again by the reverse pass: L2 hits)
-// and the 12 B of d per ray.
+// ---- the distortion regulariser's per-ray and per-chunk quantities (include/nerf_hip.h "distortion regulariser")
 struct DistRay {
   float z0, us;                         // depth of the ray's first sample; |d| / (S step_world)
   bool on;                              // false: |d| zero or not finite, the ray has no distortion term
@@ -176,131 +82,24 @@ __device__ __forceinline__ DistQ dist_chunk(const float* __restrict__ z, int64_t
   return o;
 }
 
-__global__ void __launch_bounds__(256) composite_packed_dist_fwd_kernel(const float* __restrict__ raw, const float* __restrict__ z,
-                                                                        const int64_t* __restrict__ offsets,
-                                                                        const float* __restrict__ rays, int64_t B, int64_t K,
-                                                                        float step, float diag, float c1, int white,
-                                                                        float* __restrict__ rgb, float* __restrict__ acc,
-                                                                        float* __restrict__ depth, float* __restrict__ dist) {
-  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-  for (int64_t ray = blockIdx.x * 4 + wv; ray < B; ray += (int64_t)gridDim.x * 4) {
-    int64_t s0, s1;
-    bool bad;
-    segment(offsets, ray, K, s0, s1, bad);
-    const DistRay dr = dist_ray(rays, z, ray, s0, s1, diag);
-    float carry = 0.0f, sr = 0.0f, sg = 0.0f, sb = 0.0f, sa = 0.0f, sd = 0.0f, Wc = 0.0f, Uc = 0.0f, pl = 0.0f, pq = 0.0f;
-    for (int64_t c0 = s0; c0 < s1; c0 += 64) {
-      float tot;
-      const PackedQ q = packed_chunk(raw, c0, s1, lane, step, carry, tot);
-      const float zk = c0 + lane < s1 ? z[c0 + lane] : 0.0f;
-      sr += q.w * q.r; sg += q.w * q.g; sb += q.w * q.b; sa += q.w; sd += q.w * zk;
-      carry += tot;
-      const DistQ e = dist_chunk(z, c0, s1, lane, dr, q.w, Wc, Uc);
-      pl += q.w * (e.u * e.Wl - e.Ul); pq += q.w * q.w;
-    }
-    sr = wave_sum(sr); sg = wave_sum(sg); sb = wave_sum(sb); sa = wave_sum(sa); sd = wave_sum(sd);
-    pl = wave_sum(pl); pq = wave_sum(pq);
-    if (lane == 0) {
-      float L = dr.on ? 2.0f * pl + c1 * pq : 0.0f;
-      if (white) { sr = sr + (1.0f - sa); sg = sg + (1.0f - sa); sb = sb + (1.0f - sa); }
-      if (bad) sr = sg = sb = sa = sd = L = __builtin_nanf("");
-      rgb[ray * 3 + 0] = sr; rgb[ray * 3 + 1] = sg; rgb[ray * 3 + 2] = sb;
-      if (acc) acc[ray] = sa;
-      if (depth) depth[ray] = sd;
-      dist[ray] = L;
-    }
-  }
-}
-
-// composite_packed_train_kernel with G_k += coef dL_b/dw_k, coef = grad_scale dist_weight / B.  The forward sweep also leaves the
-// chunk-entry sums of w and w u in lane c (next to the carried exponent) and ends with the ray's totals W, U; the reverse sweep
-// repeats each chunk's two scans (the same operations: the same bits) for Wl_k, Ul_k.
-//   dL_b/dw_k = 2 inter_k + (2 delta / 3) w_k,  inter_k = u_k ((2 Wl_k + w_k) - W) - ((2 Ul_k + w_k u_k) - U)
-__global__ void __launch_bounds__(256) composite_packed_dist_train_kernel(
-    const float* __restrict__ raw, const float* __restrict__ z, const int64_t* __restrict__ offsets, const float* __restrict__ rays,
-    int64_t B, int64_t K, float step, float diag, float c1, int white, const float* __restrict__ target, float grad_scale, float coef,
-    float* __restrict__ loss, float* __restrict__ dist_out, float* __restrict__ rgb_out, float* __restrict__ d_raw) {
-  __shared__ float part[4];
-  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-  const float inv = 1.0f / (float)(B * 3), invB = 1.0f / (float)B, c2 = 2.0f * c1;
-  float sq = 0.0f, sl = 0.0f;
-  for (int64_t ray = blockIdx.x * 4 + wv; ray < B; ray += (int64_t)gridDim.x * 4) {
-    int64_t s0, s1;
-    bool bad;
-    segment(offsets, ray, K, s0, s1, bad);
-    const DistRay dr = dist_ray(rays, z, ray, s0, s1, diag);
-    float carry = 0.0f, carries = 0.0f, wcs = 0.0f, ucs = 0.0f, sr = 0.0f, sg = 0.0f, sb = 0.0f, sa = 0.0f;
-    float Wc = 0.0f, Uc = 0.0f, pl = 0.0f, pq = 0.0f;
-    int nch = 0;
-    for (int64_t c0 = s0; c0 < s1; c0 += 64, ++nch) {
-      if (lane == nch) { carries = carry; wcs = Wc; ucs = Uc; }
-      float tot;
-      const PackedQ q = packed_chunk(raw, c0, s1, lane, step, carry, tot);
-      sr += q.w * q.r; sg += q.w * q.g; sb += q.w * q.b; sa += q.w;
-      carry += tot;
-      const DistQ e = dist_chunk(z, c0, s1, lane, dr, q.w, Wc, Uc);
-      pl += q.w * (e.u * e.Wl - e.Ul); pq += q.w * q.w;
-    }
-    sr = wave_sum(sr); sg = wave_sum(sg); sb = wave_sum(sb); sa = wave_sum(sa);
-    pl = wave_sum(pl); pq = wave_sum(pq);
-    if (white) { sr = sr + (1.0f - sa); sg = sg + (1.0f - sa); sb = sb + (1.0f - sa); }
-    if (bad) sr = sg = sb = __builtin_nanf("");
-    const float er = sr - target[ray * 3], eg = sg - target[ray * 3 + 1], eb = sb - target[ray * 3 + 2];
-    if (lane == 0) {
-      sq += er * er; sq += eg * eg; sq += eb * eb;
-      sl += bad ? __builtin_nanf("") : dr.on ? 2.0f * pl + c1 * pq : 0.0f;
-      if (rgb_out) { rgb_out[ray * 3] = sr; rgb_out[ray * 3 + 1] = sg; rgb_out[ray * 3 + 2] = sb; }
-    }
-    const float gr = grad_scale * 2.0f * er * inv, gg = grad_scale * 2.0f * eg * inv, gb = grad_scale * 2.0f * eb * inv;
-    const float gacc = 0.0f - (white ? (gr + gg + gb) : 0.0f);
-    const float W = Wc, U = Uc;
-    float suffix = 0.0f;                                         // sum of G w over the chunks after this one
-    for (int c = nch - 1; c >= 0; --c) {
-      const int64_t c0 = s0 + (int64_t)c * 64;
-      const float cin = __shfl(carries, c, WAVE);
-      float Wk = __shfl(wcs, c, WAVE), Uk = __shfl(ucs, c, WAVE);
-      float tot;
-      const PackedQ q = packed_chunk(raw, c0, s1, lane, step, cin, tot);
-      const DistQ e = dist_chunk(z, c0, s1, lane, dr, q.w, Wk, Uk);
-      const float inter = e.u * ((2.0f * e.Wl + q.w) - W) - ((2.0f * e.Ul + q.w * e.u) - U);
-      float G = gr * q.r + gg * q.g + gb * q.b + gacc;
-      if (dr.on) G = G + coef * (2.0f * inter + c2 * q.w);
-      const float gw = G * q.w;
-      const float rincl = wave_rscan_incl(gw, lane);
-      const float dn = __shfl_down(rincl, 1, WAVE);
-      const float after = suffix + (lane == 63 ? 0.0f : dn);   // sum over the samples k' > k of the ray
-      const int64_t k = c0 + lane;
-      if (k < s1) {
-        const float sig = raw[4 * k + 3];
-        const float dx = G * q.T * expf(-q.x) - after;
-        float4 o;
-        o.x = q.w * gr; o.y = q.w * gg; o.z = q.w * gb; o.w = dx * step * expf(fminf(sig, 15.0f));
-        *reinterpret_cast<float4*>(d_raw + 4 * k) = o;
-      }
-      suffix += __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, rincl), 0));
-    }
-  }
-  if (lane == 0) part[wv] = sq;
-  __syncthreads();
-  if (threadIdx.x == 0 && loss) atomicAdd(loss, (part[0] + part[1] + part[2] + part[3]) * inv);
-  __syncthreads();                                               // the same 16 B carry the second sum
-  if (lane == 0) part[wv] = sl;
-  __syncthreads();
-  if (threadIdx.x == 0 && dist_out) atomicAdd(dist_out, (part[0] + part[1] + part[2] + part[3]) * invB);
-}
-
-// ---- background colour (include/nerf_hip.h "background colour"): the four kernels above over a colour bg instead of white or
-// nothing, rgb = sum w c + (1 - acc) * bg.  Kernels of their own again, so that the ones above keep their ISA; DIST selects the form
-// with the distortion regulariser.  bg: one colour for all rays (stride 0) or one per ray (stride 3), read by every lane of the
-// ray's wave (one address: a broadcast).  Extra traffic per ray: 12 B of bg forward; training 16 + 12 B of target_rgba + bg
-// instead of 12 B of target.
-template <bool DIST>
-__global__ void __launch_bounds__(256) composite_packed_bg_fwd_kernel(const float* __restrict__ raw, const float* __restrict__ z,
-                                                                      const int64_t* __restrict__ offsets,
-                                                                      const float* __restrict__ rays, int64_t B, int64_t K,
-                                                                      float step, float diag, float c1, const float* __restrict__ bg,
-                                                                      int bg_stride, float* __restrict__ rgb, float* __restrict__ acc,
-                                                                      float* __restrict__ depth, float* __restrict__ dist) {
+// ---- One family, two switches.  The forward kernel and the training kernel below each exist in four instantiations over the
+// union of the modes' arguments (an instantiation ignores the ones of a switch that is off; the host passes NULL / 0 for them):
+//   DIST  the distortion regulariser: L_b of every ray, and in training its adjoint in G_k.  Extra traffic: z (4 B per sample,
+//         read again by the reverse pass: L2 hits) and the 12 B of d per ray.
+//   BG    a background colour instead of the run-time `white` flag (white or nothing): rgb = sum w c + (1 - acc) * bg.  Forward:
+//         bg is one colour for all rays (bg_stride 0) or one per ray (3), read by lane 0.  Training: bg [B, 3] and a straight RGBA
+//         target [B, 4] in place of an RGB one.  Extra traffic per ray: 12 B of bg forward; training 16 + 12 B of target + bg
+//         instead of 12 B of target.
+// With BG off `white` stays a run-time flag and adds (1 - acc) with no multiplication: a background of ones would give the same
+// bits but not the same code.
+template <bool DIST, bool BG>
+__global__ void __launch_bounds__(256) composite_packed_fwd_kernel(const float* __restrict__ raw, const float* __restrict__ z,
+                                                                   const int64_t* __restrict__ offsets,
+                                                                   const float* __restrict__ rays, int64_t B, int64_t K,
+                                                                   float step, float diag, float c1, int white,
+                                                                   const float* __restrict__ bg, int bg_stride,
+                                                                   float* __restrict__ rgb, float* __restrict__ acc,
+                                                                   float* __restrict__ depth, float* __restrict__ dist) {
   const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
   for (int64_t ray = blockIdx.x * 4 + wv; ray < B; ray += (int64_t)gridDim.x * 4) {
     int64_t s0, s1;
@@ -323,9 +122,13 @@ __global__ void __launch_bounds__(256) composite_packed_bg_fwd_kernel(const floa
     sr = wave_sum(sr); sg = wave_sum(sg); sb = wave_sum(sb); sa = wave_sum(sa); sd = wave_sum(sd);
     if constexpr (DIST) { pl = wave_sum(pl); pq = wave_sum(pq); }
     if (lane == 0) {
-      const float* c = bg + ray * bg_stride;
       float L = dr.on ? 2.0f * pl + c1 * pq : 0.0f;
-      sr = sr + (1.0f - sa) * c[0]; sg = sg + (1.0f - sa) * c[1]; sb = sb + (1.0f - sa) * c[2];
+      if constexpr (BG) {
+        const float* c = bg + ray * bg_stride;
+        sr = sr + (1.0f - sa) * c[0]; sg = sg + (1.0f - sa) * c[1]; sb = sb + (1.0f - sa) * c[2];
+      } else if (white) {
+        sr = sr + (1.0f - sa); sg = sg + (1.0f - sa); sb = sb + (1.0f - sa);
+      }
       if (bad) sr = sg = sb = sa = sd = L = __builtin_nanf("");
       rgb[ray * 3 + 0] = sr; rgb[ray * 3 + 1] = sg; rgb[ray * 3 + 2] = sb;
       if (acc) acc[ray] = sa;
@@ -335,16 +138,34 @@ __global__ void __launch_bounds__(256) composite_packed_bg_fwd_kernel(const floa
   }
 }
 
-// The training kernels above against a straight RGBA target over a per-ray background: the target t_c = rgba_c * a + bg_c * (1 - a)
-// is formed here (no composited target through HBM), the rendered ray gets (1 - acc) * bg_c, and acc's adjoint becomes
-//   gacc = -((gr * bg_r + gg * bg_g) + gb * bg_b)
-// Everything behind gacc (G_k, the suffix sums, the trunc_exp backward, the distortion term) is the code of the kernels above.
-template <bool DIST>
-__global__ void __launch_bounds__(256) composite_packed_bg_train_kernel(
+// one of the block's two loss sums: the waves' partial sums through the same 16 B of LDS, one atomic per block
+__device__ __forceinline__ void block_loss_add(float* part, int lane, int wv, float v, float scale, float* __restrict__ out) {
+  if (lane == 0) part[wv] = v;
+  __syncthreads();
+  if (threadIdx.x == 0 && out) atomicAdd(out, (part[0] + part[1] + part[2] + part[3]) * scale);
+}
+
+// Forward (as above) -> rgb -> squared error against the target -> d loss / d raw of every sample of the ray.  The reverse pass
+// walks the chunks last to first with the suffix sum of G w carried exactly (no total-minus-prefix), and re-derives each chunk's
+// forward quantities from the exponent carried into it, which the forward pass left in lane c of `carries`.
+//   dL/dx_k = G_k T_k exp(-x_k) - sum_{k' > k} G_k' w_k',  G_k = gr r_k + gg g_k + gb b_k + gacc
+//   d_raw[k] = (w_k gr, w_k gg, w_k gb, dL/dx_k * step * exp(min(raw_k[3], 15)))      (trunc_exp backward)
+// DIST: G_k += coef dL_b/dw_k, coef = grad_scale dist_weight / B.  The forward sweep also leaves the chunk-entry sums of w and w u
+// in lane c (next to the carried exponent) and ends with the ray's totals W, U; the reverse sweep repeats each chunk's two scans
+// (the same operations: the same bits) for Wl_k, Ul_k.
+//   dL_b/dw_k = 2 inter_k + (2 delta / 3) w_k,  inter_k = u_k ((2 Wl_k + w_k) - W) - ((2 Ul_k + w_k u_k) - U)
+// BG: `target` is RGBA and the target t_c = rgba_c * a + bg_c * (1 - a) is formed here (no composited target through HBM), the
+// rendered ray gets (1 - acc) * bg_c, and acc's adjoint becomes
+//   gacc = -((gr * bg_r + gg * bg_g) + gb * bg_b)                      (BG off: -(gr + gg + gb) with white, 0 without)
+// Two places follow the compiler rather than taste: `bg` is the last argument, and the reverse sweep spells
+// the regulariser's work out in two orders, because with either of them changed the <DIST, no BG> form gets another vector
+// instruction stream (other registers and another schedule) than the kernel it replaced.
+template <bool DIST, bool BG>
+__global__ void __launch_bounds__(256) composite_packed_train_kernel(
     const float* __restrict__ raw, const float* __restrict__ z, const int64_t* __restrict__ offsets, const float* __restrict__ rays,
-    int64_t B, int64_t K, float step, float diag, float c1, const float* __restrict__ target_rgba, const float* __restrict__ bg,
-    float grad_scale, float coef, float* __restrict__ loss, float* __restrict__ dist_out, float* __restrict__ rgb_out,
-    float* __restrict__ d_raw) {
+    int64_t B, int64_t K, float step, float diag, float c1, int white, const float* __restrict__ target, float grad_scale, float coef,
+    float* __restrict__ loss, float* __restrict__ dist_out, float* __restrict__ rgb_out, float* __restrict__ d_raw,
+    const float* __restrict__ bg) {
   __shared__ float part[4];
   const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
   const float inv = 1.0f / (float)(B * 3), invB = 1.0f / (float)B, c2 = 2.0f * c1;
@@ -371,10 +192,16 @@ __global__ void __launch_bounds__(256) composite_packed_bg_train_kernel(
     }
     sr = wave_sum(sr); sg = wave_sum(sg); sb = wave_sum(sb); sa = wave_sum(sa);
     if constexpr (DIST) { pl = wave_sum(pl); pq = wave_sum(pq); }
-    const float4 tv = *reinterpret_cast<const float4*>(target_rgba + ray * 4);
-    const float br = bg[ray * 3], bgn = bg[ray * 3 + 1], bb = bg[ray * 3 + 2];
-    const float tr = tv.x * tv.w + br * (1.0f - tv.w), tg = tv.y * tv.w + bgn * (1.0f - tv.w), tb = tv.z * tv.w + bb * (1.0f - tv.w);
-    sr = sr + (1.0f - sa) * br; sg = sg + (1.0f - sa) * bgn; sb = sb + (1.0f - sa) * bb;
+    float tr, tg, tb, br = 0.0f, bgn = 0.0f, bb = 0.0f;
+    if constexpr (BG) {
+      const float4 tv = *reinterpret_cast<const float4*>(target + ray * 4);
+      br = bg[ray * 3]; bgn = bg[ray * 3 + 1]; bb = bg[ray * 3 + 2];
+      tr = tv.x * tv.w + br * (1.0f - tv.w); tg = tv.y * tv.w + bgn * (1.0f - tv.w); tb = tv.z * tv.w + bb * (1.0f - tv.w);
+      sr = sr + (1.0f - sa) * br; sg = sg + (1.0f - sa) * bgn; sb = sb + (1.0f - sa) * bb;
+    } else {
+      tr = target[ray * 3]; tg = target[ray * 3 + 1]; tb = target[ray * 3 + 2];
+      if (white) { sr = sr + (1.0f - sa); sg = sg + (1.0f - sa); sb = sb + (1.0f - sa); }
+    }
     if (bad) sr = sg = sb = __builtin_nanf("");
     const float er = sr - tr, eg = sg - tg, eb = sb - tb;
     if (lane == 0) {
@@ -383,20 +210,30 @@ __global__ void __launch_bounds__(256) composite_packed_bg_train_kernel(
       if (rgb_out) { rgb_out[ray * 3] = sr; rgb_out[ray * 3 + 1] = sg; rgb_out[ray * 3 + 2] = sb; }
     }
     const float gr = grad_scale * 2.0f * er * inv, gg = grad_scale * 2.0f * eg * inv, gb = grad_scale * 2.0f * eb * inv;
-    const float gacc = 0.0f - ((gr * br + gg * bgn) + gb * bb);
+    const float gacc = 0.0f - (BG ? (gr * br + gg * bgn) + gb * bb : white ? (gr + gg + gb) : 0.0f);
     const float W = Wc, U = Uc;
     float suffix = 0.0f;                                         // sum of G w over the chunks after this one
     for (int c = nch - 1; c >= 0; --c) {
       const int64_t c0 = s0 + (int64_t)c * 64;
       const float cin = __shfl(carries, c, WAVE);
+      float Wk = 0.0f, Uk = 0.0f;
+      if constexpr (DIST && !BG) { Wk = __shfl(wcs, c, WAVE); Uk = __shfl(ucs, c, WAVE); }       // (the order: see above)
       float tot;
       const PackedQ q = packed_chunk(raw, c0, s1, lane, step, cin, tot);
-      float G = gr * q.r + gg * q.g + gb * q.b + gacc;
-      if constexpr (DIST) {
-        float Wk = __shfl(wcs, c, WAVE), Uk = __shfl(ucs, c, WAVE);
+      float G;
+      if constexpr (DIST && !BG) {
         const DistQ e = dist_chunk(z, c0, s1, lane, dr, q.w, Wk, Uk);
         const float inter = e.u * ((2.0f * e.Wl + q.w) - W) - ((2.0f * e.Ul + q.w * e.u) - U);
+        G = gr * q.r + gg * q.g + gb * q.b + gacc;
         if (dr.on) G = G + coef * (2.0f * inter + c2 * q.w);
+      } else {
+        G = gr * q.r + gg * q.g + gb * q.b + gacc;
+        if constexpr (DIST) {
+          Wk = __shfl(wcs, c, WAVE); Uk = __shfl(ucs, c, WAVE);
+          const DistQ e = dist_chunk(z, c0, s1, lane, dr, q.w, Wk, Uk);
+          const float inter = e.u * ((2.0f * e.Wl + q.w) - W) - ((2.0f * e.Ul + q.w * e.u) - U);
+          if (dr.on) G = G + coef * (2.0f * inter + c2 * q.w);
+        }
       }
       const float gw = G * q.w;
       const float rincl = wave_rscan_incl(gw, lane);
@@ -413,14 +250,10 @@ __global__ void __launch_bounds__(256) composite_packed_bg_train_kernel(
       suffix += __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, rincl), 0));
     }
   }
-  if (lane == 0) part[wv] = sq;
-  __syncthreads();
-  if (threadIdx.x == 0 && loss) atomicAdd(loss, (part[0] + part[1] + part[2] + part[3]) * inv);
+  block_loss_add(part, lane, wv, sq, inv, loss);
   if constexpr (DIST) {
     __syncthreads();                                             // the same 16 B carry the second sum
-    if (lane == 0) part[wv] = sl;
-    __syncthreads();
-    if (threadIdx.x == 0 && dist_out) atomicAdd(dist_out, (part[0] + part[1] + part[2] + part[3]) * invB);
+    block_loss_add(part, lane, wv, sl, invB, dist_out);
   }
 }
 
@@ -481,31 +314,23 @@ __global__ void ert_fold_kernel(const float* __restrict__ raw, const float* __re
   }
 }
 
-// finish: 40 B of state read, 24 B written per ray.
+// finish: 40 B of state read, 24 B written per ray.  BG: over a background colour (bg, bg_stride as in the packed forward kernel,
+// 12 B more read per ray) instead of the `white` flag.
+template <bool BG>
 __global__ void ert_finish_kernel(const int* __restrict__ istate, const float* __restrict__ fstate, int64_t B, int white,
-                                  float* __restrict__ rgb, float* __restrict__ acc, float* __restrict__ depth,
-                                  int* __restrict__ samples) {
+                                  const float* __restrict__ bg, int bg_stride, float* __restrict__ rgb, float* __restrict__ acc,
+                                  float* __restrict__ depth, int* __restrict__ samples) {
   for (int64_t b = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; b < B; b += (int64_t)gridDim.x * blockDim.x) {
     const float* fs = fstate + 6 * b;
-    float r = fs[1], g = fs[2], bl = fs[3];
     const float a = fs[4];
-    if (white) { r = r + (1.0f - a); g = g + (1.0f - a); bl = bl + (1.0f - a); }
-    rgb[3 * b] = r; rgb[3 * b + 1] = g; rgb[3 * b + 2] = bl;
-    if (acc) acc[b] = a;
-    if (depth) depth[b] = fs[5];
-    if (samples) samples[b] = istate[4 * b + 2];
-  }
-}
-
-// finish over a background colour (bg as in the packed kernels above): 40 B of state and 12 B of bg read, 24 B written per ray.
-__global__ void ert_finish_bg_kernel(const int* __restrict__ istate, const float* __restrict__ fstate, int64_t B,
-                                     const float* __restrict__ bg, int bg_stride, float* __restrict__ rgb, float* __restrict__ acc,
-                                     float* __restrict__ depth, int* __restrict__ samples) {
-  for (int64_t b = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; b < B; b += (int64_t)gridDim.x * blockDim.x) {
-    const float* fs = fstate + 6 * b;
-    const float* c = bg + b * bg_stride;
-    const float a = fs[4];
-    rgb[3 * b] = fs[1] + (1.0f - a) * c[0]; rgb[3 * b + 1] = fs[2] + (1.0f - a) * c[1]; rgb[3 * b + 2] = fs[3] + (1.0f - a) * c[2];
+    if constexpr (BG) {                       // (stores straight from the expressions: through r, g, bl the multiplications swap places)
+      const float* c = bg + b * bg_stride;
+      rgb[3 * b] = fs[1] + (1.0f - a) * c[0]; rgb[3 * b + 1] = fs[2] + (1.0f - a) * c[1]; rgb[3 * b + 2] = fs[3] + (1.0f - a) * c[2];
+    } else {
+      float r = fs[1], g = fs[2], bl = fs[3];
+      if (white) { r = r + (1.0f - a); g = g + (1.0f - a); bl = bl + (1.0f - a); }
+      rgb[3 * b] = r; rgb[3 * b + 1] = g; rgb[3 * b + 2] = bl;
+    }
     if (acc) acc[b] = a;
     if (depth) depth[b] = fs[5];
     if (samples) samples[b] = istate[4 * b + 2];
@@ -514,6 +339,74 @@ __global__ void ert_finish_bg_kernel(const int* __restrict__ istate, const float
 
 bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
+// ---- host side of the family.  Every entry reports its errors under its own name `who`, in one order: shapes (the sizes, the
+// step, then the switches' own settings) before the B == 0 early return, NULL pointers and alignment after it.
+template <bool DIST, bool BG>
+int packed_shapes(const char* who, int64_t B, int64_t K, float step_world, int march_steps, int bg_stride, float dist_weight) {
+  NERF_REQUIRE(B >= 0 && K >= 0, NERF_E_SHAPE, "%s: bad sizes", who);
+  NERF_REQUIRE(step_world > 0.0f, NERF_E_SHAPE, "%s: step_world must be > 0", who);
+  NERF_REQUIRE(!DIST || (march_steps >= 1 && march_steps <= NERF_MARCH_MAX_STEPS), NERF_E_SHAPE, "%s: need 1 <= march_steps <= %d",
+               who, NERF_MARCH_MAX_STEPS);
+  NERF_REQUIRE(!BG || bg_stride == 0 || bg_stride == 3, NERF_E_SHAPE, "%s: bg_stride must be 0 (one colour) or 3 (one per ray)", who);
+  NERF_REQUIRE(!DIST || (dist_weight >= 0.0f && dist_weight <= 3.4028234664e38f), NERF_E_SHAPE,
+               "%s: dist_weight must be finite and >= 0", who);
+  return NERF_OK;
+}
+
+// one wave per ray, four rays per block, at most 8192 blocks; both kernels begin with the same arguments, among them the
+// regulariser's two constants: the box's diagonal S step_world and delta / 3, delta = 1 / S (unused with DIST off, where the
+// entries pass march_steps 1)
+template <class... P, class... A>
+int packed_launch(const char* who, void (*kernel)(P...), void* stream, const float* raw, const float* z, const int64_t* offsets,
+                  const float* rays, int64_t B, int64_t K, float step_world, int march_steps, A... rest) {
+  const float S = (float)march_steps;
+  const dim3 g((unsigned)((B + 3) / 4 > 8192 ? 8192 : (B + 3) / 4)), b(256);
+  hipLaunchKernelGGL(kernel, g, b, 0, as_stream(stream), raw, z, offsets, rays, B, K, step_world, S * step_world, (1.0f / S) / 3.0f,
+                     rest...);
+  return check_launch(who);
+}
+
+template <bool DIST, bool BG>
+int packed_forward(const char* who, const float* raw, const float* z, const int64_t* offsets, const float* rays, int64_t B, int64_t K,
+                   float step_world, int march_steps, int white_bkgd, const float* bg, int bg_stride, float* rgb, float* acc,
+                   float* depth, float* dist, void* stream) {
+  if (const int rc = packed_shapes<DIST, BG>(who, B, K, step_world, march_steps, bg_stride, 0.0f)) return rc;
+  if (B == 0) return NERF_OK;
+  NERF_REQUIRE(offsets && rgb && (!DIST || (rays && dist)) && (!BG || bg) && (K == 0 || (raw && z)), NERF_E_NULL,
+               "%s: NULL pointer", who);
+  NERF_REQUIRE(K == 0 || aligned16(raw), NERF_E_SHAPE, "%s: raw must be 16-byte aligned", who);
+  return packed_launch(who, composite_packed_fwd_kernel<DIST, BG>, stream, raw, z, offsets, rays, B, K, step_world, march_steps,
+                       white_bkgd, bg, bg_stride, rgb, acc, depth, dist);
+}
+
+// target: RGB [B, 3], or with BG straight RGBA [B, 4] (one 16-byte load per ray) next to bg [B, 3]
+template <bool DIST, bool BG>
+int packed_train(const char* who, const float* raw, const float* z, const int64_t* offsets, const float* rays, int64_t B, int64_t K,
+                 float step_world, int march_steps, int white_bkgd, const float* target, const float* bg, float grad_scale,
+                 float dist_weight, float* loss_out, float* dist_out, float* rgb, float* d_raw, void* stream) {
+  if (const int rc = packed_shapes<DIST, BG>(who, B, K, step_world, march_steps, 3, dist_weight)) return rc;
+  if (B == 0) return NERF_OK;
+  NERF_REQUIRE(offsets && target && (!DIST || rays) && (!BG || bg) && (K == 0 || (raw && d_raw && (!DIST || z))), NERF_E_NULL,
+               "%s: NULL pointer", who);
+  NERF_REQUIRE((!BG || aligned16(target)) && (K == 0 || (aligned16(raw) && aligned16(d_raw))), NERF_E_SHAPE,
+               "%s: %sraw / d_raw must be 16-byte aligned", who, BG ? "target_rgba / " : "");
+  return packed_launch(who, composite_packed_train_kernel<DIST, BG>, stream, raw, z, offsets, rays, B, K, step_world, march_steps,
+                       white_bkgd, target, grad_scale, grad_scale * dist_weight * (1.0f / (float)B), loss_out, dist_out, rgb, d_raw,
+                       bg);
+}
+
+template <bool BG>
+int ert_finish(const char* who, const int* istate, const float* fstate, int64_t B, int white_bkgd, const float* bg, int bg_stride,
+               float* rgb, float* acc, float* depth, int* samples, void* stream) {
+  NERF_REQUIRE(B >= 0 && B < (1ll << 31), NERF_E_SHAPE, "%s: need 0 <= B < 2^31", who);
+  NERF_REQUIRE(!BG || bg_stride == 0 || bg_stride == 3, NERF_E_SHAPE, "%s: bg_stride must be 0 (one colour) or 3 (one per ray)", who);
+  if (B == 0) return NERF_OK;
+  NERF_REQUIRE(istate && fstate && rgb && (!BG || bg), NERF_E_NULL, "%s: NULL pointer", who);
+  hipLaunchKernelGGL(ert_finish_kernel<BG>, dim3(grid_for(B, 256)), dim3(256), 0, as_stream(stream), istate, fstate, B, white_bkgd, bg,
+                     bg_stride, rgb, acc, depth, samples);
+  return check_launch(who);
+}
+
 }  // namespace
 }  // namespace nerf
 
@@ -521,126 +414,51 @@ using namespace nerf;
 
 extern "C" int nerf_composite_packed_forward(const float* raw, const float* z, const int64_t* offsets, int64_t B, int64_t K,
                                              float step_world, int white_bkgd, float* rgb, float* acc, float* depth, void* stream) {
-  NERF_REQUIRE(B >= 0 && K >= 0, NERF_E_SHAPE, "nerf_composite_packed_forward: bad sizes");
-  NERF_REQUIRE(step_world > 0.0f, NERF_E_SHAPE, "nerf_composite_packed_forward: step_world must be > 0");
-  if (B == 0) return NERF_OK;
-  NERF_REQUIRE(offsets && rgb && (K == 0 || (raw && z)), NERF_E_NULL, "nerf_composite_packed_forward: NULL pointer");
-  NERF_REQUIRE(K == 0 || aligned16(raw), NERF_E_SHAPE, "nerf_composite_packed_forward: raw must be 16-byte aligned");
-  const dim3 g((unsigned)((B + 3) / 4 > 8192 ? 8192 : (B + 3) / 4)), b(256);
-  hipLaunchKernelGGL(composite_packed_fwd_kernel, g, b, 0, as_stream(stream), raw, z, offsets, B, K, step_world, white_bkgd, rgb,
-                     acc, depth);
-  return check_launch("nerf_composite_packed_forward");
-}
-
-extern "C" int nerf_composite_packed_mse_backward(const float* raw, const int64_t* offsets, int64_t B, int64_t K, float step_world,
-                                                  int white_bkgd, const float* target, float grad_scale, float* loss_out,
-                                                  float* rgb, float* d_raw, void* stream) {
-  NERF_REQUIRE(B >= 0 && K >= 0, NERF_E_SHAPE, "nerf_composite_packed_mse_backward: bad sizes");
-  NERF_REQUIRE(step_world > 0.0f, NERF_E_SHAPE, "nerf_composite_packed_mse_backward: step_world must be > 0");
-  if (B == 0) return NERF_OK;
-  NERF_REQUIRE(offsets && target && (K == 0 || (raw && d_raw)), NERF_E_NULL, "nerf_composite_packed_mse_backward: NULL pointer");
-  NERF_REQUIRE(K == 0 || (aligned16(raw) && aligned16(d_raw)), NERF_E_SHAPE,
-               "nerf_composite_packed_mse_backward: raw / d_raw must be 16-byte aligned");
-  const dim3 g((unsigned)((B + 3) / 4 > 8192 ? 8192 : (B + 3) / 4)), b(256);
-  hipLaunchKernelGGL(composite_packed_train_kernel, g, b, 0, as_stream(stream), raw, offsets, B, K, step_world, white_bkgd, target,
-                     grad_scale, loss_out, rgb, d_raw);
-  return check_launch("nerf_composite_packed_mse_backward");
-}
-
-// the checks the two distortion entries share, before any device work
-static int dist_args(const char* who, int64_t B, int64_t K, float step_world, int march_steps) {
-  NERF_REQUIRE(B >= 0 && K >= 0, NERF_E_SHAPE, "%s: bad sizes", who);
-  NERF_REQUIRE(step_world > 0.0f, NERF_E_SHAPE, "%s: step_world must be > 0", who);
-  NERF_REQUIRE(march_steps >= 1 && march_steps <= NERF_MARCH_MAX_STEPS, NERF_E_SHAPE, "%s: need 1 <= march_steps <= %d", who,
-               NERF_MARCH_MAX_STEPS);
-  return NERF_OK;
+  return packed_forward<false, false>("nerf_composite_packed_forward", raw, z, offsets, nullptr, B, K, step_world, 1, white_bkgd,
+                                      nullptr, 0, rgb, acc, depth, nullptr, stream);
 }
 
 extern "C" int nerf_composite_packed_distortion(const float* raw, const float* z, const int64_t* offsets, const float* rays,
                                                 int64_t B, int64_t K, float step_world, int march_steps, int white_bkgd, float* rgb,
                                                 float* acc, float* depth, float* dist, void* stream) {
-  if (const int rc = dist_args("nerf_composite_packed_distortion", B, K, step_world, march_steps)) return rc;
-  if (B == 0) return NERF_OK;
-  NERF_REQUIRE(offsets && rays && rgb && dist && (K == 0 || (raw && z)), NERF_E_NULL, "nerf_composite_packed_distortion: NULL pointer");
-  NERF_REQUIRE(K == 0 || aligned16(raw), NERF_E_SHAPE, "nerf_composite_packed_distortion: raw must be 16-byte aligned");
-  const float S = (float)march_steps;
-  const dim3 g((unsigned)((B + 3) / 4 > 8192 ? 8192 : (B + 3) / 4)), b(256);
-  hipLaunchKernelGGL(composite_packed_dist_fwd_kernel, g, b, 0, as_stream(stream), raw, z, offsets, rays, B, K, step_world,
-                     S * step_world, (1.0f / S) / 3.0f, white_bkgd, rgb, acc, depth, dist);
-  return check_launch("nerf_composite_packed_distortion");
+  return packed_forward<true, false>("nerf_composite_packed_distortion", raw, z, offsets, rays, B, K, step_world, march_steps,
+                                     white_bkgd, nullptr, 0, rgb, acc, depth, dist, stream);
+}
+
+extern "C" int nerf_composite_packed_forward_bg(const float* raw, const float* z, const int64_t* offsets, int64_t B, int64_t K,
+                                                float step_world, const float* bg, int bg_stride, float* rgb, float* acc,
+                                                float* depth, void* stream) {
+  return packed_forward<false, true>("nerf_composite_packed_forward_bg", raw, z, offsets, nullptr, B, K, step_world, 1, 0, bg,
+                                     bg_stride, rgb, acc, depth, nullptr, stream);
+}
+
+extern "C" int nerf_composite_packed_distortion_bg(const float* raw, const float* z, const int64_t* offsets, const float* rays,
+                                                   int64_t B, int64_t K, float step_world, int march_steps, const float* bg,
+                                                   int bg_stride, float* rgb, float* acc, float* depth, float* dist, void* stream) {
+  return packed_forward<true, true>("nerf_composite_packed_distortion_bg", raw, z, offsets, rays, B, K, step_world, march_steps, 0,
+                                    bg, bg_stride, rgb, acc, depth, dist, stream);
+}
+
+extern "C" int nerf_composite_packed_mse_backward(const float* raw, const int64_t* offsets, int64_t B, int64_t K, float step_world,
+                                                  int white_bkgd, const float* target, float grad_scale, float* loss_out,
+                                                  float* rgb, float* d_raw, void* stream) {
+  return packed_train<false, false>("nerf_composite_packed_mse_backward", raw, nullptr, offsets, nullptr, B, K, step_world, 1,
+                                    white_bkgd, target, nullptr, grad_scale, 0.0f, loss_out, nullptr, rgb, d_raw, stream);
 }
 
 extern "C" int nerf_composite_packed_mse_dist_backward(const float* raw, const float* z, const int64_t* offsets, const float* rays,
                                                        int64_t B, int64_t K, float step_world, int march_steps, int white_bkgd,
                                                        const float* target, float grad_scale, float dist_weight, float* loss_out,
                                                        float* dist_out, float* rgb, float* d_raw, void* stream) {
-  if (const int rc = dist_args("nerf_composite_packed_mse_dist_backward", B, K, step_world, march_steps)) return rc;
-  NERF_REQUIRE(dist_weight >= 0.0f && dist_weight <= 3.4028234664e38f, NERF_E_SHAPE,
-               "nerf_composite_packed_mse_dist_backward: dist_weight must be finite and >= 0");
-  if (B == 0) return NERF_OK;
-  NERF_REQUIRE(offsets && rays && target && (K == 0 || (raw && z && d_raw)), NERF_E_NULL,
-               "nerf_composite_packed_mse_dist_backward: NULL pointer");
-  NERF_REQUIRE(K == 0 || (aligned16(raw) && aligned16(d_raw)), NERF_E_SHAPE,
-               "nerf_composite_packed_mse_dist_backward: raw / d_raw must be 16-byte aligned");
-  const float S = (float)march_steps;
-  const dim3 g((unsigned)((B + 3) / 4 > 8192 ? 8192 : (B + 3) / 4)), b(256);
-  hipLaunchKernelGGL(composite_packed_dist_train_kernel, g, b, 0, as_stream(stream), raw, z, offsets, rays, B, K, step_world,
-                     S * step_world, (1.0f / S) / 3.0f, white_bkgd, target, grad_scale, grad_scale * dist_weight * (1.0f / (float)B),
-                     loss_out, dist_out, rgb, d_raw);
-  return check_launch("nerf_composite_packed_mse_dist_backward");
-}
-
-// ---- background colour: the entries above over bg (stride 0: one colour, 3: one per ray)
-static int bg_args(const char* who, int64_t B, int64_t K, float step_world, int bg_stride) {
-  NERF_REQUIRE(B >= 0 && K >= 0, NERF_E_SHAPE, "%s: bad sizes", who);
-  NERF_REQUIRE(step_world > 0.0f, NERF_E_SHAPE, "%s: step_world must be > 0", who);
-  NERF_REQUIRE(bg_stride == 0 || bg_stride == 3, NERF_E_SHAPE, "%s: bg_stride must be 0 (one colour) or 3 (one per ray)", who);
-  return NERF_OK;
-}
-
-extern "C" int nerf_composite_packed_forward_bg(const float* raw, const float* z, const int64_t* offsets, int64_t B, int64_t K,
-                                                float step_world, const float* bg, int bg_stride, float* rgb, float* acc,
-                                                float* depth, void* stream) {
-  if (const int rc = bg_args("nerf_composite_packed_forward_bg", B, K, step_world, bg_stride)) return rc;
-  if (B == 0) return NERF_OK;
-  NERF_REQUIRE(offsets && bg && rgb && (K == 0 || (raw && z)), NERF_E_NULL, "nerf_composite_packed_forward_bg: NULL pointer");
-  NERF_REQUIRE(K == 0 || aligned16(raw), NERF_E_SHAPE, "nerf_composite_packed_forward_bg: raw must be 16-byte aligned");
-  const dim3 g((unsigned)((B + 3) / 4 > 8192 ? 8192 : (B + 3) / 4)), b(256);
-  hipLaunchKernelGGL(composite_packed_bg_fwd_kernel<false>, g, b, 0, as_stream(stream), raw, z, offsets, (const float*)nullptr, B, K,
-                     step_world, 0.0f, 0.0f, bg, bg_stride, rgb, acc, depth, (float*)nullptr);
-  return check_launch("nerf_composite_packed_forward_bg");
-}
-
-extern "C" int nerf_composite_packed_distortion_bg(const float* raw, const float* z, const int64_t* offsets, const float* rays,
-                                                   int64_t B, int64_t K, float step_world, int march_steps, const float* bg,
-                                                   int bg_stride, float* rgb, float* acc, float* depth, float* dist, void* stream) {
-  if (const int rc = dist_args("nerf_composite_packed_distortion_bg", B, K, step_world, march_steps)) return rc;
-  if (const int rc = bg_args("nerf_composite_packed_distortion_bg", B, K, step_world, bg_stride)) return rc;
-  if (B == 0) return NERF_OK;
-  NERF_REQUIRE(offsets && rays && bg && rgb && dist && (K == 0 || (raw && z)), NERF_E_NULL,
-               "nerf_composite_packed_distortion_bg: NULL pointer");
-  NERF_REQUIRE(K == 0 || aligned16(raw), NERF_E_SHAPE, "nerf_composite_packed_distortion_bg: raw must be 16-byte aligned");
-  const float S = (float)march_steps;
-  const dim3 g((unsigned)((B + 3) / 4 > 8192 ? 8192 : (B + 3) / 4)), b(256);
-  hipLaunchKernelGGL(composite_packed_bg_fwd_kernel<true>, g, b, 0, as_stream(stream), raw, z, offsets, rays, B, K, step_world,
-                     S * step_world, (1.0f / S) / 3.0f, bg, bg_stride, rgb, acc, depth, dist);
-  return check_launch("nerf_composite_packed_distortion_bg");
+  return packed_train<true, false>("nerf_composite_packed_mse_dist_backward", raw, z, offsets, rays, B, K, step_world, march_steps,
+                                   white_bkgd, target, nullptr, grad_scale, dist_weight, loss_out, dist_out, rgb, d_raw, stream);
 }
 
 extern "C" int nerf_composite_packed_mse_backward_bg(const float* raw, const int64_t* offsets, int64_t B, int64_t K, float step_world,
                                                      const float* target_rgba, const float* bg, float grad_scale, float* loss_out,
                                                      float* rgb, float* d_raw, void* stream) {
-  if (const int rc = bg_args("nerf_composite_packed_mse_backward_bg", B, K, step_world, 3)) return rc;
-  if (B == 0) return NERF_OK;
-  NERF_REQUIRE(offsets && target_rgba && bg && (K == 0 || (raw && d_raw)), NERF_E_NULL,
-               "nerf_composite_packed_mse_backward_bg: NULL pointer");
-  NERF_REQUIRE(aligned16(target_rgba) && (K == 0 || (aligned16(raw) && aligned16(d_raw))), NERF_E_SHAPE,
-               "nerf_composite_packed_mse_backward_bg: target_rgba / raw / d_raw must be 16-byte aligned");
-  const dim3 g((unsigned)((B + 3) / 4 > 8192 ? 8192 : (B + 3) / 4)), b(256);
-  hipLaunchKernelGGL(composite_packed_bg_train_kernel<false>, g, b, 0, as_stream(stream), raw, (const float*)nullptr, offsets,
-                     (const float*)nullptr, B, K, step_world, 0.0f, 0.0f, target_rgba, bg, grad_scale, 0.0f, loss_out,
-                     (float*)nullptr, rgb, d_raw);
-  return check_launch("nerf_composite_packed_mse_backward_bg");
+  return packed_train<false, true>("nerf_composite_packed_mse_backward_bg", raw, nullptr, offsets, nullptr, B, K, step_world, 1, 0,
+                                   target_rgba, bg, grad_scale, 0.0f, loss_out, nullptr, rgb, d_raw, stream);
 }
 
 extern "C" int nerf_composite_packed_mse_dist_backward_bg(const float* raw, const float* z, const int64_t* offsets, const float* rays,
@@ -648,20 +466,8 @@ extern "C" int nerf_composite_packed_mse_dist_backward_bg(const float* raw, cons
                                                           const float* target_rgba, const float* bg, float grad_scale,
                                                           float dist_weight, float* loss_out, float* dist_out, float* rgb,
                                                           float* d_raw, void* stream) {
-  if (const int rc = dist_args("nerf_composite_packed_mse_dist_backward_bg", B, K, step_world, march_steps)) return rc;
-  NERF_REQUIRE(dist_weight >= 0.0f && dist_weight <= 3.4028234664e38f, NERF_E_SHAPE,
-               "nerf_composite_packed_mse_dist_backward_bg: dist_weight must be finite and >= 0");
-  if (B == 0) return NERF_OK;
-  NERF_REQUIRE(offsets && rays && target_rgba && bg && (K == 0 || (raw && z && d_raw)), NERF_E_NULL,
-               "nerf_composite_packed_mse_dist_backward_bg: NULL pointer");
-  NERF_REQUIRE(aligned16(target_rgba) && (K == 0 || (aligned16(raw) && aligned16(d_raw))), NERF_E_SHAPE,
-               "nerf_composite_packed_mse_dist_backward_bg: target_rgba / raw / d_raw must be 16-byte aligned");
-  const float S = (float)march_steps;
-  const dim3 g((unsigned)((B + 3) / 4 > 8192 ? 8192 : (B + 3) / 4)), b(256);
-  hipLaunchKernelGGL(composite_packed_bg_train_kernel<true>, g, b, 0, as_stream(stream), raw, z, offsets, rays, B, K, step_world,
-                     S * step_world, (1.0f / S) / 3.0f, target_rgba, bg, grad_scale, grad_scale * dist_weight * (1.0f / (float)B),
-                     loss_out, dist_out, rgb, d_raw);
-  return check_launch("nerf_composite_packed_mse_dist_backward_bg");
+  return packed_train<true, true>("nerf_composite_packed_mse_dist_backward_bg", raw, z, offsets, rays, B, K, step_world, march_steps,
+                                  0, target_rgba, bg, grad_scale, dist_weight, loss_out, dist_out, rgb, d_raw, stream);
 }
 
 extern "C" int nerf_ert_init(int64_t B, int* istate, float* fstate, int* live, void* stream) {
@@ -687,21 +493,10 @@ extern "C" int nerf_ert_fold(const float* raw, const float* z, const int64_t* of
 
 extern "C" int nerf_ert_finish(const int* istate, const float* fstate, int64_t B, int white_bkgd, float* rgb, float* acc,
                                float* depth, int* samples, void* stream) {
-  NERF_REQUIRE(B >= 0 && B < (1ll << 31), NERF_E_SHAPE, "nerf_ert_finish: need 0 <= B < 2^31");
-  if (B == 0) return NERF_OK;
-  NERF_REQUIRE(istate && fstate && rgb, NERF_E_NULL, "nerf_ert_finish: NULL pointer");
-  hipLaunchKernelGGL(ert_finish_kernel, dim3(grid_for(B, 256)), dim3(256), 0, as_stream(stream), istate, fstate, B, white_bkgd, rgb,
-                     acc, depth, samples);
-  return check_launch("nerf_ert_finish");
+  return ert_finish<false>("nerf_ert_finish", istate, fstate, B, white_bkgd, nullptr, 0, rgb, acc, depth, samples, stream);
 }
 
 extern "C" int nerf_ert_finish_bg(const int* istate, const float* fstate, int64_t B, const float* bg, int bg_stride, float* rgb,
                                   float* acc, float* depth, int* samples, void* stream) {
-  NERF_REQUIRE(B >= 0 && B < (1ll << 31), NERF_E_SHAPE, "nerf_ert_finish_bg: need 0 <= B < 2^31");
-  NERF_REQUIRE(bg_stride == 0 || bg_stride == 3, NERF_E_SHAPE, "nerf_ert_finish_bg: bg_stride must be 0 (one colour) or 3 (one per ray)");
-  if (B == 0) return NERF_OK;
-  NERF_REQUIRE(istate && fstate && bg && rgb, NERF_E_NULL, "nerf_ert_finish_bg: NULL pointer");
-  hipLaunchKernelGGL(ert_finish_bg_kernel, dim3(grid_for(B, 256)), dim3(256), 0, as_stream(stream), istate, fstate, B, bg, bg_stride,
-                     rgb, acc, depth, samples);
-  return check_launch("nerf_ert_finish_bg");
+  return ert_finish<true>("nerf_ert_finish_bg", istate, fstate, B, 0, bg, bg_stride, rgb, acc, depth, samples, stream);
 }

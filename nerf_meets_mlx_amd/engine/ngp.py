@@ -481,20 +481,11 @@ class NGPTrainer(Trainer):
             if background is None:
                 self._bg_gen.manual_seed(parallel.counter_seed(self.seed, self.rank, 5, self.it))
                 background = torch.rand(B, 3, dtype=torch.float32, device=self.device, generator=self._bg_gen)
-            if self.distortion_weight is not None:
-                loss, dist, d_raw, _ = render.composite_packed_mse_dist_backward_bg(raw, z, offsets, rays, self.grid.step_world,
-                                                                                    self.march_steps, target, background,
-                                                                                    self.distortion_weight)
-                return loss, d_raw, dist
-            loss, d_raw, _ = render.composite_packed_mse_backward_bg(raw, offsets, B, self.grid.step_world, target, background)
-            return loss, d_raw, None
-        if self.distortion_weight is not None:
-            loss, dist, d_raw, _ = render.composite_packed_mse_dist_backward(raw, z, offsets, rays, self.grid.step_world,
-                                                                             self.march_steps, target, self.distortion_weight,
-                                                                             self.white_bkgd)
-            return loss, d_raw, dist
-        loss, d_raw, _ = render.composite_packed_mse_backward(raw, offsets, B, self.grid.step_world, target, self.white_bkgd)
-        return loss, d_raw, None
+        dist_on = self.distortion_weight is not None
+        loss, dist, d_raw, _ = render.composite_packed_train(raw, z, offsets, rays, self.grid.step_world, target, self.white_bkgd,
+                                                             background, self.march_steps if dist_on else None,
+                                                             self.distortion_weight if dist_on else 0.0)
+        return loss, d_raw, dist
 
     def render_rays(self, rays: torch.Tensor, u=None, aux: bool = False, background=None):
         """rgb [B, 3] of rays [B, 11], `chunk` rays per call.  aux=True: {"rgb", "acc" [B], "depth" [B]} and, in march mode,
@@ -506,14 +497,7 @@ class NGPTrainer(Trainer):
             if self.march_steps is None:
                 raise ValueError("NGPTrainer.render_rays: background needs march_steps (the 64-sample renderers composite onto "
                                  "white or nothing: white_bkgd)")
-            per_ray = torch.is_tensor(background) and background.dim() == 2
-            if per_ray and tuple(background.shape) != (rays.shape[0], 3):
-                raise ValueError(f"NGPTrainer.render_rays: a per-ray background must be [B, 3] = [{rays.shape[0]}, 3], got "
-                                 f"{list(background.shape)}")
-            if not per_ray:
-                if torch.as_tensor(background).numel() != 3:
-                    raise ValueError(f"NGPTrainer.render_rays: background must be None, 3 numbers or a [B, 3] tensor, got {background!r}")
-                background = N.f32(torch.as_tensor(background, dtype=torch.float32).reshape(3), self.device)
+            background, bg_stride = render.background_arg(background, rays.shape[0], rays.device)
         outs = []
         self._join_comm()
         if self.march_steps is not None:                     # march mode: jitter 0.5, the bitfield once the warm-up is over
@@ -521,7 +505,7 @@ class NGPTrainer(Trainer):
             use_bits = self.it >= WARMUP
             for s in range(0, rays.shape[0], self.chunk):
                 r = N.f32(rays[s:s + self.chunk])
-                bg = background if background is None or background.dim() == 1 else background[s:s + self.chunk]
+                bg = background if background is None or bg_stride == 0 else background[s:s + self.chunk]
                 if self.min_transmittance is not None:
                     o = self.grid.render_ert(self._field, r, 0.5, self.min_transmittance, self.white_bkgd, use_bits=use_bits,
                                              background=bg)
@@ -529,22 +513,13 @@ class NGPTrainer(Trainer):
                     continue
                 offsets, rows, z, K = self.grid.march(r, 0.5, use_bits=use_bits)
                 raw = self._field.query_packed(rows, z)
-                if aux and self.distortion_weight is not None:
-                    if bg is not None:
-                        rgb, acc, depth, dist = render.composite_packed_distortion_bg(raw, z, offsets, r, self.grid.step_world,
-                                                                                      self.march_steps, bg)
-                    else:
-                        rgb, acc, depth, dist = render.composite_packed_distortion(raw, z, offsets, r, self.grid.step_world,
-                                                                                   self.march_steps, self.white_bkgd)
-                    outs.append({"rgb": rgb, "acc": acc, "depth": depth, "samples": (offsets[1:] - offsets[:-1]).to(torch.int32),
-                                 "distortion": dist})
-                    continue
-                if bg is not None:
-                    rgb, acc, depth = render.composite_packed_bg(raw, z, offsets, r.shape[0], self.grid.step_world, bg)
-                else:
-                    rgb, acc, depth = render.composite_packed(raw, z, offsets, r.shape[0], self.grid.step_world, self.white_bkgd)
-                outs.append({"rgb": rgb, "acc": acc, "depth": depth,
-                             "samples": (offsets[1:] - offsets[:-1]).to(torch.int32)} if aux else rgb)
+                with_dist = aux and self.distortion_weight is not None
+                rgb, acc, depth, dist = render.composite_packed_render(raw, z, offsets, r, self.grid.step_world, self.white_bkgd, bg,
+                                                                       self.march_steps if with_dist else None)
+                o = {"rgb": rgb, "acc": acc, "depth": depth, "samples": (offsets[1:] - offsets[:-1]).to(torch.int32)} if aux else rgb
+                if with_dist:
+                    o["distortion"] = dist
+                outs.append(o)
             return _cat(outs, aux)
         for s in range(0, rays.shape[0], self.chunk):
             r = rays[s:s + self.chunk]
@@ -567,8 +542,8 @@ class NGPTrainer(Trainer):
             r = N.f32(rays[s:s + self.chunk])
             offsets, rows, z, K = self.grid.march(r, 0.5, use_bits=self.it >= WARMUP)
             raw = self._field.query_packed(rows, z)
-            outs.append(render.composite_packed_distortion(raw, z, offsets, r, self.grid.step_world, self.march_steps,
-                                                           self.white_bkgd)[3])
+            outs.append(render.composite_packed_render(raw, z, offsets, r, self.grid.step_world, self.white_bkgd,
+                                                       dist_steps=self.march_steps)[3])
         return torch.cat(outs, 0) if outs else torch.empty(0, dtype=torch.float32, device=self.device)
 
     def _grid_for_step(self, update: bool = False):

@@ -348,10 +348,7 @@ class OccupancyGrid:
             A, la, lb = A_next, lb, la
             rounds += 1
             total += K
-        if background is not None:
-            rgb, acc, depth, samples = render.ert_finish_bg(istate, fstate, background)
-        else:
-            rgb, acc, depth, samples = render.ert_finish(istate, fstate, white_bkgd)
+        rgb, acc, depth, samples = render.ert_finish_over(istate, fstate, white_bkgd, background)
         self.last_ert = {"rounds": rounds, "marched": total}
         return {"rgb": rgb, "acc": acc, "depth": depth, "samples": samples}
 

@@ -57,74 +57,42 @@ def composite_mse_backward(raw, z_vals, rays, target, white_bkgd=False, grad_sca
     return loss, d_raw, rgb
 
 
-def composite_packed(raw, z, offsets, B: int, step_world: float, white_bkgd=False):
-    """(rgb [B, 3], acc [B], depth [B]) of packed rays (`nerf_composite_packed_forward`): ray b owns raw [K, 4] / z [K] rows
-    [offsets[b], offsets[b + 1]); sigma = trunc_exp(raw[..., 3]), every interval step_world (include/nerf_hip.h)."""
+def _packed_forward(raw, z, offsets, B: int, step_world: float, white_bkgd, bg, rays, march_steps):
+    """One launch of the packed forward family (csrc/composite_packed.hip): (rgb [B, 3], acc [B], depth [B], dist [B] or None).
+    bg: None (white_bkgd decides) or background_arg's (tensor, stride); march_steps not None: also the distortion loss of rays [B, 11]."""
     raw = N.f32(raw).reshape(-1, 4)
     z = N.f32(z).reshape(-1)
-    K = raw.shape[0]
-    dev = offsets.device
+    K, dev, dist_on = raw.shape[0], offsets.device, march_steps is not None
     rgb = torch.empty(B, 3, dtype=torch.float32, device=dev)
     acc = torch.empty(B, dtype=torch.float32, device=dev)
     depth = torch.empty(B, dtype=torch.float32, device=dev)
-    N.check(N.lib().nerf_composite_packed_forward(N.ptr(raw) if K else None, N.ptr(z) if K else None, N.ptr(offsets), B, K,
-                                                  float(step_world), int(bool(white_bkgd)), N.ptr(rgb), N.ptr(acc), N.ptr(depth),
-                                                  N.stream()))
-    return rgb, acc, depth
-
-
-def composite_packed_mse_backward(raw, offsets, B: int, step_world: float, target, white_bkgd=False, grad_scale: float = 1.0,
-                                  need_rgb: bool = False):
-    """(loss [1], d_raw [K, 4], rgb [B, 3] or None): the packed compositing + MSE + their gradient w.r.t. raw in one launch
-    (`nerf_composite_packed_mse_backward`, the conventions of composite_mse_backward)."""
-    raw = N.f32(raw).reshape(-1, 4)
-    K = raw.shape[0]
-    dev = offsets.device
-    loss = torch.zeros(1, dtype=torch.float32, device=dev)
-    d_raw = torch.empty(K, 4, dtype=torch.float32, device=dev)
-    rgb = torch.empty(B, 3, dtype=torch.float32, device=dev) if need_rgb else None
-    N.check(N.lib().nerf_composite_packed_mse_backward(N.ptr(raw) if K else None, N.ptr(offsets), B, K, float(step_world),
-                                                       int(bool(white_bkgd)), N.ptr(N.f32(target)), float(grad_scale), N.ptr(loss),
-                                                       N.ptr(rgb), N.ptr(d_raw) if K else None, N.stream()))
-    return loss, d_raw, rgb
-
-
-def composite_packed_distortion(raw, z, offsets, rays, step_world: float, march_steps: int, white_bkgd=False):
-    """(rgb [B, 3], acc [B], depth [B], dist [B]) of the packed rays [B, 11]: composite_packed plus the distortion loss L_b of
-    every ray (`nerf_composite_packed_distortion`, include/nerf_hip.h "distortion regulariser")."""
-    raw = N.f32(raw).reshape(-1, 4)
-    z = N.f32(z).reshape(-1)
-    rays = N.f32(rays)
-    B, K = rays.shape[0], raw.shape[0]
-    dev = offsets.device
-    rgb = torch.empty(B, 3, dtype=torch.float32, device=dev)
-    acc = torch.empty(B, dtype=torch.float32, device=dev)
-    depth = torch.empty(B, dtype=torch.float32, device=dev)
-    dist = torch.empty(B, dtype=torch.float32, device=dev)
-    N.check(N.lib().nerf_composite_packed_distortion(N.ptr(raw) if K else None, N.ptr(z) if K else None, N.ptr(offsets),
-                                                     N.ptr(rays), B, K, float(step_world), int(march_steps), int(bool(white_bkgd)),
-                                                     N.ptr(rgb), N.ptr(acc), N.ptr(depth), N.ptr(dist), N.stream()))
+    dist = torch.empty(B, dtype=torch.float32, device=dev) if dist_on else None
+    fn = getattr(N.lib(), "nerf_composite_packed_" + ("distortion" if dist_on else "forward") + ("_bg" if bg is not None else ""))
+    N.check(fn(N.ptr(raw) if K else None, N.ptr(z) if K else None, N.ptr(offsets), *([N.ptr(N.f32(rays))] if dist_on else []), B, K,
+               float(step_world), *([int(march_steps)] if dist_on else []),
+               *([int(bool(white_bkgd))] if bg is None else [N.ptr(bg[0]), bg[1]]), N.ptr(rgb), N.ptr(acc), N.ptr(depth),
+               *([N.ptr(dist)] if dist_on else []), N.stream()))
     return rgb, acc, depth, dist
 
 
-def composite_packed_mse_dist_backward(raw, z, offsets, rays, step_world: float, march_steps: int, target, dist_weight: float,
-                                       white_bkgd=False, grad_scale: float = 1.0, need_rgb: bool = False):
-    """(loss [1], dist [1], d_raw [K, 4], rgb [B, 3] or None): composite_packed_mse_backward with the distortion regulariser
-    (`nerf_composite_packed_mse_dist_backward`).  d_raw is the gradient of MSE + dist_weight * mean_b L_b; loss is the MSE
-    alone and dist the unweighted mean_b L_b."""
+def _packed_train(raw, z, offsets, B: int, step_world: float, target, white_bkgd, bg, rays, march_steps, dist_weight, grad_scale,
+                  need_rgb):
+    """One launch of the packed training family: (loss [1], dist [1] or None, d_raw [K, 4], rgb [B, 3] or None).  bg: None (target
+    RGB [B, 3], white_bkgd decides) or [B, 3] next to an RGBA target (both through _rgba_and_bg); march_steps not None: with the
+    distortion regulariser on rays [B, 11], weighted dist_weight."""
     raw = N.f32(raw).reshape(-1, 4)
-    z = N.f32(z).reshape(-1)
-    rays = N.f32(rays)
-    B, K = rays.shape[0], raw.shape[0]
-    dev = offsets.device
+    K, dev, dist_on = raw.shape[0], offsets.device, march_steps is not None
+    target = N.f32(target)
     loss = torch.zeros(1, dtype=torch.float32, device=dev)
-    dist = torch.zeros(1, dtype=torch.float32, device=dev)
+    dist = torch.zeros(1, dtype=torch.float32, device=dev) if dist_on else None
     d_raw = torch.empty(K, 4, dtype=torch.float32, device=dev)
     rgb = torch.empty(B, 3, dtype=torch.float32, device=dev) if need_rgb else None
-    N.check(N.lib().nerf_composite_packed_mse_dist_backward(
-        N.ptr(raw) if K else None, N.ptr(z) if K else None, N.ptr(offsets), N.ptr(rays), B, K, float(step_world), int(march_steps),
-        int(bool(white_bkgd)), N.ptr(N.f32(target)), float(grad_scale), float(dist_weight), N.ptr(loss), N.ptr(dist), N.ptr(rgb),
-        N.ptr(d_raw) if K else None, N.stream()))
+    fn = getattr(N.lib(), "nerf_composite_packed_mse_" + ("dist_" if dist_on else "") + "backward" + ("_bg" if bg is not None else ""))
+    lead = [N.ptr(N.f32(z).reshape(-1)) if K else None, N.ptr(offsets), N.ptr(N.f32(rays))] if dist_on else [N.ptr(offsets)]
+    N.check(fn(N.ptr(raw) if K else None, *lead, B, K, float(step_world), *([int(march_steps)] if dist_on else []),
+               *([int(bool(white_bkgd)), N.ptr(target)] if bg is None else [N.ptr(target), N.ptr(bg)]), float(grad_scale),
+               *([float(dist_weight)] if dist_on else []), N.ptr(loss), *([N.ptr(dist)] if dist_on else []), N.ptr(rgb),
+               N.ptr(d_raw) if K else None, N.stream()))
     return loss, dist, d_raw, rgb
 
 
@@ -141,86 +109,89 @@ def background_arg(background, B: int, device):
     return N.f32(bg, device), 0
 
 
-def composite_packed_bg(raw, z, offsets, B: int, step_world: float, background):
-    """composite_packed over a background colour (`nerf_composite_packed_forward_bg`): rgb = sum w c + (1 - acc) * bg.
-    background: 3 numbers, or a tensor [B, 3] (one colour per ray)."""
-    raw = N.f32(raw).reshape(-1, 4)
-    z = N.f32(z).reshape(-1)
-    K = raw.shape[0]
-    dev = offsets.device
-    bg, stride = background_arg(background, B, dev)
-    rgb = torch.empty(B, 3, dtype=torch.float32, device=dev)
-    acc = torch.empty(B, dtype=torch.float32, device=dev)
-    depth = torch.empty(B, dtype=torch.float32, device=dev)
-    N.check(N.lib().nerf_composite_packed_forward_bg(N.ptr(raw) if K else None, N.ptr(z) if K else None, N.ptr(offsets), B, K,
-                                                     float(step_world), N.ptr(bg), stride, N.ptr(rgb), N.ptr(acc), N.ptr(depth),
-                                                     N.stream()))
-    return rgb, acc, depth
-
-
-def composite_packed_distortion_bg(raw, z, offsets, rays, step_world: float, march_steps: int, background):
-    """composite_packed_distortion over a background colour (`nerf_composite_packed_distortion_bg`)."""
-    raw = N.f32(raw).reshape(-1, 4)
-    z = N.f32(z).reshape(-1)
-    rays = N.f32(rays)
-    B, K = rays.shape[0], raw.shape[0]
-    dev = offsets.device
-    bg, stride = background_arg(background, B, dev)
-    rgb = torch.empty(B, 3, dtype=torch.float32, device=dev)
-    acc = torch.empty(B, dtype=torch.float32, device=dev)
-    depth = torch.empty(B, dtype=torch.float32, device=dev)
-    dist = torch.empty(B, dtype=torch.float32, device=dev)
-    N.check(N.lib().nerf_composite_packed_distortion_bg(N.ptr(raw) if K else None, N.ptr(z) if K else None, N.ptr(offsets),
-                                                        N.ptr(rays), B, K, float(step_world), int(march_steps), N.ptr(bg), stride,
-                                                        N.ptr(rgb), N.ptr(acc), N.ptr(depth), N.ptr(dist), N.stream()))
-    return rgb, acc, depth, dist
-
-
-def composite_packed_mse_backward_bg(raw, offsets, B: int, step_world: float, target_rgba, background, grad_scale: float = 1.0,
-                                     need_rgb: bool = False):
-    """(loss [1], d_raw [K, 4], rgb [B, 3] or None): composite_packed_mse_backward over a per-ray background [B, 3] against a
-    straight RGBA target [B, 4] (`nerf_composite_packed_mse_backward_bg`): the kernel renders rgb = sum w c + (1 - acc) * bg and
-    forms the target t = rgba[:3] * a + bg * (1 - a) itself."""
-    raw = N.f32(raw).reshape(-1, 4)
-    K = raw.shape[0]
-    dev = offsets.device
-    target_rgba, bg = _rgba_and_bg(target_rgba, background, B, dev)
-    loss = torch.zeros(1, dtype=torch.float32, device=dev)
-    d_raw = torch.empty(K, 4, dtype=torch.float32, device=dev)
-    rgb = torch.empty(B, 3, dtype=torch.float32, device=dev) if need_rgb else None
-    N.check(N.lib().nerf_composite_packed_mse_backward_bg(N.ptr(raw) if K else None, N.ptr(offsets), B, K, float(step_world),
-                                                          N.ptr(target_rgba), N.ptr(bg), float(grad_scale), N.ptr(loss),
-                                                          N.ptr(rgb), N.ptr(d_raw) if K else None, N.stream()))
-    return loss, d_raw, rgb
-
-
-def composite_packed_mse_dist_backward_bg(raw, z, offsets, rays, step_world: float, march_steps: int, target_rgba, background,
-                                          dist_weight: float, grad_scale: float = 1.0, need_rgb: bool = False):
-    """(loss [1], dist [1], d_raw [K, 4], rgb [B, 3] or None): composite_packed_mse_dist_backward over a per-ray background
-    [B, 3] against a straight RGBA target [B, 4] (`nerf_composite_packed_mse_dist_backward_bg`)."""
-    raw = N.f32(raw).reshape(-1, 4)
-    z = N.f32(z).reshape(-1)
-    rays = N.f32(rays)
-    B, K = rays.shape[0], raw.shape[0]
-    dev = offsets.device
-    target_rgba, bg = _rgba_and_bg(target_rgba, background, B, dev)
-    loss = torch.zeros(1, dtype=torch.float32, device=dev)
-    dist = torch.zeros(1, dtype=torch.float32, device=dev)
-    d_raw = torch.empty(K, 4, dtype=torch.float32, device=dev)
-    rgb = torch.empty(B, 3, dtype=torch.float32, device=dev) if need_rgb else None
-    N.check(N.lib().nerf_composite_packed_mse_dist_backward_bg(
-        N.ptr(raw) if K else None, N.ptr(z) if K else None, N.ptr(offsets), N.ptr(rays), B, K, float(step_world), int(march_steps),
-        N.ptr(target_rgba), N.ptr(bg), float(grad_scale), float(dist_weight), N.ptr(loss), N.ptr(dist), N.ptr(rgb),
-        N.ptr(d_raw) if K else None, N.stream()))
-    return loss, dist, d_raw, rgb
-
-
 def _rgba_and_bg(target_rgba, background, B: int, dev):
     target_rgba, bg = N.f32(target_rgba, dev), N.f32(background, dev)
     if tuple(target_rgba.shape) != (B, 4) or tuple(bg.shape) != (B, 3):
         raise ValueError(f"the background training form needs target [B, 4] and background [B, 3] with B = {B}, got "
                          f"{list(target_rgba.shape)} and {list(bg.shape)}")
     return target_rgba, bg
+
+
+def composite_packed_render(raw, z, offsets, rays, step_world: float, white_bkgd=False, background=None, dist_steps=None):
+    """(rgb [B, 3], acc [B], depth [B], dist [B] or None) of the packed rays [B, 11], whatever the mode: ray b owns raw [K, 4] /
+    z [K] rows [offsets[b], offsets[b + 1]); sigma = trunc_exp(raw[..., 3]), every interval step_world (include/nerf_hip.h).
+    background (None: white_bkgd decides): 3 numbers or a tensor [B, 3], rgb = sum w c + (1 - acc) * bg.  dist_steps (the
+    march_steps of the grid; None: no dist): also every ray's distortion loss L_b."""
+    B = rays.shape[0]
+    bg = None if background is None else background_arg(background, B, offsets.device)
+    return _packed_forward(raw, z, offsets, B, step_world, white_bkgd, bg, rays, dist_steps)
+
+
+def composite_packed_train(raw, z, offsets, rays, step_world: float, target, white_bkgd=False, background=None, dist_steps=None,
+                           dist_weight: float = 0.0, grad_scale: float = 1.0, need_rgb: bool = False):
+    """(loss [1], dist [1] or None, d_raw [K, 4], rgb [B, 3] or None), whatever the mode: the packed compositing + MSE + their
+    gradient w.r.t. raw in one launch.  background [B, 3] (None: white_bkgd decides) makes target a straight RGBA [B, 4]: the kernel
+    renders over bg and forms t = rgba[:3] * a + bg * (1 - a) itself.  dist_steps (None: no regulariser): d_raw is the gradient of
+    MSE + dist_weight * mean_b L_b; loss stays the MSE alone and dist is the unweighted mean_b L_b."""
+    B = rays.shape[0]
+    bg = None
+    if background is not None:
+        target, bg = _rgba_and_bg(target, background, B, offsets.device)
+    return _packed_train(raw, z, offsets, B, step_world, target, white_bkgd, bg, rays, dist_steps, dist_weight, grad_scale, need_rgb)
+
+
+# ---- the modes by name (one C entry each): the call surface of the tests and tools
+def composite_packed(raw, z, offsets, B: int, step_world: float, white_bkgd=False):
+    """(rgb, acc, depth) (`nerf_composite_packed_forward`)."""
+    return _packed_forward(raw, z, offsets, B, step_world, white_bkgd, None, None, None)[:3]
+
+
+def composite_packed_mse_backward(raw, offsets, B: int, step_world: float, target, white_bkgd=False, grad_scale: float = 1.0,
+                                  need_rgb: bool = False):
+    """(loss, d_raw, rgb or None) (`nerf_composite_packed_mse_backward`, the conventions of composite_mse_backward)."""
+    loss, _, d_raw, rgb = _packed_train(raw, None, offsets, B, step_world, target, white_bkgd, None, None, None, None, grad_scale, need_rgb)
+    return loss, d_raw, rgb
+
+
+def composite_packed_distortion(raw, z, offsets, rays, step_world: float, march_steps: int, white_bkgd=False):
+    """(rgb, acc, depth, dist) (`nerf_composite_packed_distortion`, include/nerf_hip.h "distortion regulariser")."""
+    return _packed_forward(raw, z, offsets, rays.shape[0], step_world, white_bkgd, None, rays, march_steps)
+
+
+def composite_packed_mse_dist_backward(raw, z, offsets, rays, step_world: float, march_steps: int, target, dist_weight: float,
+                                       white_bkgd=False, grad_scale: float = 1.0, need_rgb: bool = False):
+    """(loss, dist, d_raw, rgb or None) (`nerf_composite_packed_mse_dist_backward`)."""
+    return _packed_train(raw, z, offsets, rays.shape[0], step_world, target, white_bkgd, None, rays, march_steps, dist_weight,
+                         grad_scale, need_rgb)
+
+
+def composite_packed_bg(raw, z, offsets, B: int, step_world: float, background):
+    """composite_packed over a background colour (`nerf_composite_packed_forward_bg`): 3 numbers, or a tensor [B, 3]."""
+    return _packed_forward(raw, z, offsets, B, step_world, False, background_arg(background, B, offsets.device), None, None)[:3]
+
+
+def composite_packed_distortion_bg(raw, z, offsets, rays, step_world: float, march_steps: int, background):
+    """composite_packed_distortion over a background colour (`nerf_composite_packed_distortion_bg`)."""
+    B = rays.shape[0]
+    return _packed_forward(raw, z, offsets, B, step_world, False, background_arg(background, B, offsets.device), rays, march_steps)
+
+
+def composite_packed_mse_backward_bg(raw, offsets, B: int, step_world: float, target_rgba, background, grad_scale: float = 1.0,
+                                     need_rgb: bool = False):
+    """composite_packed_mse_backward over a per-ray background [B, 3] against a straight RGBA target [B, 4]
+    (`nerf_composite_packed_mse_backward_bg`)."""
+    target_rgba, bg = _rgba_and_bg(target_rgba, background, B, offsets.device)
+    loss, _, d_raw, rgb = _packed_train(raw, None, offsets, B, step_world, target_rgba, False, bg, None, None, None, grad_scale, need_rgb)
+    return loss, d_raw, rgb
+
+
+def composite_packed_mse_dist_backward_bg(raw, z, offsets, rays, step_world: float, march_steps: int, target_rgba, background,
+                                          dist_weight: float, grad_scale: float = 1.0, need_rgb: bool = False):
+    """composite_packed_mse_dist_backward over a per-ray background [B, 3] against a straight RGBA target [B, 4]
+    (`nerf_composite_packed_mse_dist_backward_bg`)."""
+    target_rgba, bg = _rgba_and_bg(target_rgba, background, rays.shape[0], offsets.device)
+    return _packed_train(raw, z, offsets, rays.shape[0], step_world, target_rgba, False, bg, rays, march_steps, dist_weight, grad_scale,
+                         need_rgb)
 
 
 def ert_init(istate, fstate, live, B: int):
@@ -240,31 +211,30 @@ def ert_fold(raw, z, offsets, live, A: int, istate, fstate, step_world: float, m
                                   float(step_world), float(min_transmittance), N.ptr(istate), N.ptr(fstate), N.stream()))
 
 
-def ert_finish(istate, fstate, white_bkgd=False):
-    """(rgb [B, 3], acc [B], depth [B], samples [B] int32) of the round renderer's state (`nerf_ert_finish`)."""
-    B = istate.shape[0]
-    dev = istate.device
+def _ert_finish(istate, fstate, white_bkgd, bg):
+    B, dev = istate.shape[0], istate.device
     rgb = torch.empty(B, 3, dtype=torch.float32, device=dev)
     acc = torch.empty(B, dtype=torch.float32, device=dev)
     depth = torch.empty(B, dtype=torch.float32, device=dev)
     samples = torch.empty(B, dtype=torch.int32, device=dev)
-    N.check(N.lib().nerf_ert_finish(N.ptr(istate), N.ptr(fstate), B, int(bool(white_bkgd)), N.ptr(rgb), N.ptr(acc), N.ptr(depth),
-                                    N.ptr(samples), N.stream()))
+    fn, mode = (N.lib().nerf_ert_finish, [int(bool(white_bkgd))]) if bg is None else (N.lib().nerf_ert_finish_bg, [N.ptr(bg[0]), bg[1]])
+    N.check(fn(N.ptr(istate), N.ptr(fstate), B, *mode, N.ptr(rgb), N.ptr(acc), N.ptr(depth), N.ptr(samples), N.stream()))
     return rgb, acc, depth, samples
+
+
+def ert_finish(istate, fstate, white_bkgd=False):
+    """(rgb [B, 3], acc [B], depth [B], samples [B] int32) of the round renderer's state (`nerf_ert_finish`)."""
+    return _ert_finish(istate, fstate, white_bkgd, None)
 
 
 def ert_finish_bg(istate, fstate, background):
     """ert_finish over a background colour (`nerf_ert_finish_bg`): 3 numbers, or a tensor [B, 3]."""
-    B = istate.shape[0]
-    dev = istate.device
-    bg, stride = background_arg(background, B, dev)
-    rgb = torch.empty(B, 3, dtype=torch.float32, device=dev)
-    acc = torch.empty(B, dtype=torch.float32, device=dev)
-    depth = torch.empty(B, dtype=torch.float32, device=dev)
-    samples = torch.empty(B, dtype=torch.int32, device=dev)
-    N.check(N.lib().nerf_ert_finish_bg(N.ptr(istate), N.ptr(fstate), B, N.ptr(bg), stride, N.ptr(rgb), N.ptr(acc), N.ptr(depth),
-                                       N.ptr(samples), N.stream()))
-    return rgb, acc, depth, samples
+    return _ert_finish(istate, fstate, False, background_arg(background, istate.shape[0], istate.device))
+
+
+def ert_finish_over(istate, fstate, white_bkgd=False, background=None):
+    """ert_finish, over `background` (3 numbers or a tensor [B, 3]) when there is one and by white_bkgd otherwise."""
+    return ert_finish(istate, fstate, white_bkgd) if background is None else ert_finish_bg(istate, fstate, background)
 
 
 _WS = {}

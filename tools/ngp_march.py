@@ -256,7 +256,7 @@ def stats(a):
     import sqlite3
     db = sqlite3.connect(a.stats)
     for name, calls, avg_ns in db.execute("select name, count(*), avg(end - start) from kernels group by name"):
-        m = re.search(r"(occ_march_\w+|ert_\w+|occ_cull_scan_kernel|occ_merge_exp_kernel|composite_packed_\w+(?:<\w+>)?|nerf_ngp\w*|ngp\w*fused\w*|"
+        m = re.search(r"(occ_march_\w+|ert_\w+|occ_cull_scan_kernel|occ_merge_exp_kernel|composite_packed_\w+(?:<[\w, ]+>)?|nerf_ngp\w*|ngp\w*fused\w*|"
                       r"hashgrid\w*|composite_train_kernel|occ_cull_\w+)", name)
         if m:
             print(json.dumps({"kernel": m.group(1), "calls": calls, "avg_us": round(avg_ns * 1e-3, 2)}))
