@@ -587,6 +587,39 @@ int nerf_mesh_write_vertices(const float* vol, int res, float iso, const float* 
                              int64_t V, float* verts, float* normals, float* color_rows, void* stream);
 int nerf_mesh_write_faces(const float* vol, int res, float iso, void* workspace, int64_t F, int32_t* faces, void* stream);
 
+/* ---------------------------------------------------------------- connected components (no reference counterpart)
+ * The 6-connected components of {v > iso} of a mesh-extraction volume, and the filter that drops the small ones (the floaters of
+ * a trained field) before marching cubes.  Additive: NERF_ABI_VERSION stays 3.  vol: contiguous float32 [R, R, R] with the
+ * conventions of "mesh extraction": linear index p = i + R (j + R k), inside iff v > iso (NaN and v == iso are outside),
+ * 2 <= R <= NERF_MESH_MAX_RES, iso finite.  tests/_ccl_ref.py reproduces every output bit for bit.
+ *   labels    int32 [R^3]: -1 at an outside voxel; at an inside voxel the smallest linear index of its component.  Neighbours
+ *             are +-1 along one axis inside the lattice (no wrap from i = R - 1 to the next row's i = 0).  The rule defines the
+ *             output uniquely: any algorithm and any scheduling give the same bits.
+ *   sizes     int32 [R^3]: the component's voxel count at its root (labels[p] == p), 0 elsewhere (integer atomics: exact).
+ *   stats     int64 [3]: the number of components, the number of inside voxels, and the label of the largest component (the
+ *             most voxels, ties to the smaller label) or -1 when there is none.
+ *   filter    out[p] = dropped(p) ? iso : vol[p], float32 [R^3]; every kept or outside voxel (NaN included) is copied bit for
+ *             bit.  An inside voxel is dropped when its component has fewer than min_voxels voxels (min_voxels >= 0; 0 and 1
+ *             drop nothing) or, with largest_only != 0, when its component is not the largest one.  If the largest component
+ *             has fewer than min_voxels voxels nothing survives.  out may alias vol.  A dropped voxel is outside (iso > iso is
+ *             false) and leaves the central differences of the normals finite.
+ *   sub-mesh  No lattice edge joins a dropped voxel to a kept inside voxel (they would share a component).  Every crossing edge
+ *             of the filtered volume is therefore a crossing edge of the original with both end values unchanged: the vertices
+ *             of marching cubes on the filtered volume are, bit for bit and in the same order, the subsequence of the original's
+ *             vertices whose inside end is kept.  The case table's face rule keeps the two inside corners of a face diagonal
+ *             apart, so the mesh separates exactly the pieces 6-connectivity separates.  Normals are those of the filtered
+ *             volume: next to a dropped voxel they may differ from the original mesh's.
+ * Calls: nerf_ccl_label (three launches: runs along x inside a workgroup, unions across y / z with atomicMin on the parent array
+ * in the workspace -- the smaller root wins, so a root is its component's minimum --, flatten), nerf_ccl_sizes (four launches),
+ * nerf_ccl_filter (one).  The number of launches depends on R alone and nothing is read on the host; the filter reads sizes
+ * and stats from device memory.  workspace: nerf_ccl_workspace_bytes(R) bytes of unspecified content, used by nerf_ccl_label
+ * only.  Argument errors (R, non-finite iso, min_voxels < 0, NULL) return before any launch.                                  */
+int64_t nerf_ccl_workspace_bytes(int res);
+int nerf_ccl_label(const float* vol, int res, float iso, void* workspace, int32_t* labels, void* stream);
+int nerf_ccl_sizes(const int32_t* labels, int res, int32_t* sizes, int64_t* stats, void* stream);
+int nerf_ccl_filter(const float* vol, const int32_t* labels, const int32_t* sizes, const int64_t* stats, int res, float iso,
+                    int64_t min_voxels, int largest_only, float* out, void* stream);
+
 /* ---------------------------------------------------------------- fused renderer (a14 / a18)
  * replaces: rendering/render.py:164-241 render_rays_eval (coarse pass, importance sampling, sort, second pass)
  * as ONE call that enqueues the fixed kernel sequence on `stream`: nerf_sample_coarse -> nerf_query_fused ->

@@ -95,6 +95,10 @@ SIGNATURES = {
     "nerf_mesh_count": (_I, [_P, _I, _F, _P, _P, _P]),
     "nerf_mesh_write_vertices": (_I, [_P, _I, _F, C.POINTER(C.c_float), C.POINTER(C.c_float), _P, _I64, _P, _P, _P, _P]),
     "nerf_mesh_write_faces": (_I, [_P, _I, _F, _P, _I64, _P, _P]),
+    "nerf_ccl_workspace_bytes": (_I64, [_I]),
+    "nerf_ccl_label": (_I, [_P, _I, _F, _P, _P, _P]),
+    "nerf_ccl_sizes": (_I, [_P, _I, _P, _P, _P]),
+    "nerf_ccl_filter": (_I, [_P, _P, _P, _P, _I, _F, _I64, _I, _P, _P]),
 }
 
 

@@ -6,6 +6,10 @@ section 14).  The reference has no such export; this is Instant-NGP's.
     host, nerf_mesh_write_vertices, nerf_mesh_write_faces.
   * `Trainer.density_volume` / `Trainer.extract_mesh` (engine/trainer.py) sample the field on that lattice with its fused query
     (nerf_mesh_points, the query, nerf_occ_merge_ex with decay 0) and colour the vertices by a query along -normal.
+  * `connected_components(volume, iso)` labels the 6-connected components of {v > iso}; `filter_components` sets the small ones
+    (or all but the largest) to `iso`, which removes their pieces from the mesh and leaves the rest of it bit for bit
+    (include/nerf_hip.h "connected components").  `extract(..., min_component, largest_only)` runs it
+    between the density volume and marching cubes.
   * `write_ply` writes a binary little-endian PLY.
 """
 import ctypes as C
@@ -117,6 +121,63 @@ def marching_cubes(volume: torch.Tensor, iso: float, lo, hi) -> Mesh:
     return _marching_cubes(volume, iso, lo, hi, False)[0]
 
 
+class Components(NamedTuple):
+    labels: torch.Tensor                  # [R, R, R] int32: -1 outside, else the smallest linear index of the component
+    sizes: torch.Tensor                   # [R, R, R] int32: the component's voxel count at its root, 0 elsewhere
+    stats: torch.Tensor                   # [3] int64: components, inside voxels, the largest component's label or -1
+
+
+def check_component_args(min_component, largest_only, resolution: int):
+    """(min_component, largest_only) as (int, bool); ValueError for a min_component that is a bool, non-integral, negative or
+    above R^3, or a largest_only that is not a bool."""
+    if isinstance(min_component, bool) or not isinstance(min_component, numbers.Integral) \
+            or not 0 <= int(min_component) <= int(resolution) ** 3:
+        raise ValueError(f"min_component must be an int in [0, {int(resolution) ** 3}], got {min_component!r}")
+    if not isinstance(largest_only, bool):
+        raise ValueError(f"largest_only must be a bool, got {largest_only!r}")
+    return int(min_component), largest_only
+
+
+def _check_volume(who, volume, iso):
+    if not torch.is_tensor(volume) or volume.dim() != 3 or volume.dtype != torch.float32 or not volume.is_contiguous() \
+            or not (volume.shape[0] == volume.shape[1] == volume.shape[2]):
+        raise ValueError(f"{who}: volume must be a contiguous float32 [R, R, R] tensor")
+    R, _, _, iso = check_mesh_args(volume.shape[0], [0.0] * 3, [1.0] * 3, iso)
+    return R, iso
+
+
+def connected_components(volume: torch.Tensor, iso: float) -> Components:
+    """The 6-connected components of {v > iso} of a contiguous float32 [R, R, R] device volume (include/nerf_hip.h "connected
+    components"): nerf_ccl_label, nerf_ccl_sizes.  Device tensors; nothing is read on the host."""
+    R, iso = _check_volume("connected_components", volume, iso)
+    dev = volume.device
+    L = N.lib()
+    ws = torch.empty(L.nerf_ccl_workspace_bytes(R), dtype=torch.uint8, device=dev)
+    labels = torch.empty(R, R, R, dtype=torch.int32, device=dev)
+    sizes = torch.empty(R, R, R, dtype=torch.int32, device=dev)
+    stats = torch.empty(3, dtype=torch.int64, device=dev)
+    N.check(L.nerf_ccl_label(N.ptr(volume), R, iso, N.ptr(ws), N.ptr(labels), N.stream()))
+    N.check(L.nerf_ccl_sizes(N.ptr(labels), R, N.ptr(sizes), N.ptr(stats), N.stream()))
+    return Components(labels, sizes, stats)
+
+
+def filter_components(volume: torch.Tensor, iso: float, min_component: int = 0, largest_only: bool = False,
+                      components: Optional[Components] = None) -> torch.Tensor:
+    """A new volume in which every inside voxel of a component with fewer than `min_component` voxels -- and, with
+    `largest_only`, of every component but the largest -- holds `iso` (outside); everything else is copied bit for bit
+    (nerf_ccl_filter).  `components`: connected_components(volume, iso) when the caller has it already."""
+    R, iso = _check_volume("filter_components", volume, iso)
+    min_component, largest_only = check_component_args(min_component, largest_only, R)
+    c = components if components is not None else connected_components(volume, iso)
+    for t, dt, shape in ((c.labels, torch.int32, (R, R, R)), (c.sizes, torch.int32, (R, R, R)), (c.stats, torch.int64, (3,))):
+        if not torch.is_tensor(t) or t.dtype != dt or tuple(t.shape) != shape or not t.is_contiguous() or t.device != volume.device:
+            raise ValueError("filter_components: components do not belong to this volume")
+    out = torch.empty_like(volume)
+    N.check(N.lib().nerf_ccl_filter(N.ptr(volume), N.ptr(c.labels), N.ptr(c.sizes), N.ptr(c.stats), R, iso, min_component,
+                                    int(largest_only), N.ptr(out), N.stream()))
+    return out
+
+
 def vertex_colors(query, rows: torch.Tensor, chunk: int = CHUNK) -> torch.Tensor:
     """clamp(raw[..., :3], 0, 1) of query(rows, z = 0) -> raw [n, 1, 4] on the colour rows of nerf_mesh_write_vertices."""
     V = rows.shape[0]
@@ -131,10 +192,15 @@ def vertex_colors(query, rows: torch.Tensor, chunk: int = CHUNK) -> torch.Tensor
     return out
 
 
-def extract(query, activation: int, resolution: int, threshold: float, lo, hi, colors: bool = True, device="cuda") -> Mesh:
-    """density_volume -> marching_cubes at `threshold` -> (optionally) vertex colours."""
+def extract(query, activation: int, resolution: int, threshold: float, lo, hi, colors: bool = True, device="cuda",
+            min_component: int = 0, largest_only: bool = False) -> Mesh:
+    """density_volume -> (with min_component > 1 or largest_only: filter_components) -> marching_cubes at `threshold` ->
+    (optionally) vertex colours, queried on the filtered mesh's rows.  With the defaults the filter is not called."""
     check_mesh_args(resolution, lo, hi, threshold)
+    min_component, largest_only = check_component_args(min_component, largest_only, resolution)
     vol = density_volume(query, activation, resolution, lo, hi, device=device)
+    if min_component > 1 or largest_only:
+        vol = filter_components(vol, threshold, min_component, largest_only)
     mesh, rows = _marching_cubes(vol, threshold, lo, hi, colors)
     if not colors:
         return mesh

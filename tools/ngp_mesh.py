@@ -11,7 +11,10 @@ density volume (lattice rows + fused query + merge) and of marching cubes (count
 faces) and of the colour query, each the mean of --reps event-timed runs; V and F; the geometry figure -- the fractions of
 vertices within h and 2 h (L-infinity) of the boundary of the union of synthetic._BOXES -- for this mesh and for the mesh of the
 teacher's own sigma volume at iso 25 (the ceiling a perfect field reaches on this lattice); at --ply-res the PLY is written,
-parsed back and checked (V, F, every directed edge at most once).
+parsed back and checked (V, F, every directed edge at most once).  With --min-component N (repeatable) and / or --largest-only,
+one more line per value: the 6-connected components of {sigma > threshold} -- their number, the largest
+one's share of the inside voxels --, V, F and the geometry figures of the filtered mesh with the number of vertices farther than
+2 h from the boxes, and the device ms of the label, sizes and filter calls next to the density volume's and marching cubes'.
 
     rocprofv3 --kernel-trace --output-format csv -d DIR -o mesh -- python tools/ngp_mesh.py --ckpt /tmp/ngp.npz --reps 1 --no-ply
     python tools/ngp_mesh.py --stats DIR/.../mesh_kernel_trace.csv --from profiles/ngp_mesh.jsonl --out profiles/ngp_mesh_kernels.jsonl
@@ -75,8 +78,35 @@ def _geometry(verts, R, bound, boxes):
     h = 2.0 * bound / R
     v = verts.cpu().numpy()
     if len(v) == 0:
-        return {"within_h": None, "within_2h": None}
-    return {"within_h": float(near_union_boundary(v, boxes, h).mean()), "within_2h": float(near_union_boundary(v, boxes, 2 * h).mean())}
+        return {"within_h": None, "within_2h": None, "beyond_2h": 0}
+    near2 = near_union_boundary(v, boxes, 2 * h)
+    return {"within_h": float(near_union_boundary(v, boxes, h).mean()), "within_2h": float(near2.mean()),
+            "beyond_2h": int((~near2).sum())}
+
+
+def _components_timed(vol, iso, min_component, largest_only):
+    """engine.mesh.connected_components + filter_components as their three C calls, each between device events:
+    (Components, filtered volume, [label ms, sizes ms, filter ms])."""
+    from nerf_meets_mlx_amd import _native as N
+    from nerf_meets_mlx_amd.engine import mesh
+    L = N.lib()
+    R, dev = vol.shape[0], vol.device
+    ws = torch.empty(L.nerf_ccl_workspace_bytes(R), dtype=torch.uint8, device=dev)
+    labels = torch.empty(R, R, R, dtype=torch.int32, device=dev)
+    sizes = torch.empty(R, R, R, dtype=torch.int32, device=dev)
+    stats = torch.empty(3, dtype=torch.int64, device=dev)
+    out = torch.empty_like(vol)
+    e = [torch.cuda.Event(enable_timing=True) for _ in range(4)]
+    e[0].record()
+    N.check(L.nerf_ccl_label(N.ptr(vol), R, iso, N.ptr(ws), N.ptr(labels), N.stream()))
+    e[1].record()
+    N.check(L.nerf_ccl_sizes(N.ptr(labels), R, N.ptr(sizes), N.ptr(stats), N.stream()))
+    e[2].record()
+    N.check(L.nerf_ccl_filter(N.ptr(vol), N.ptr(labels), N.ptr(sizes), N.ptr(stats), R, iso, min_component, int(largest_only),
+                              N.ptr(out), N.stream()))
+    e[3].record()
+    torch.cuda.synchronize()
+    return mesh.Components(labels, sizes, stats), out, [e[k].elapsed_time(e[k + 1]) for k in range(3)]
 
 
 def _teacher_volume(R, lo, hi, dev):
@@ -119,6 +149,10 @@ def main():
     ap.add_argument("--reps", type=int, default=3)
     ap.add_argument("--ply-res", type=int, default=256)
     ap.add_argument("--no-ply", action="store_true")
+    ap.add_argument("--min-component", type=int, action="append", default=None,
+                    help="also mesh the volume without the components of fewer voxels (DESIGN.md section 17); repeatable: one "
+                         "JSON line per value")
+    ap.add_argument("--largest-only", action="store_true", help="the filtered arms keep the largest component only")
     ap.add_argument("--ckpt", default=None, help="load this checkpoint instead of training")
     ap.add_argument("--save-ckpt", default=None, help="save the trained state here")
     ap.add_argument("--out", default=None, help="append the JSON lines to this file")
@@ -189,6 +223,35 @@ def main():
         torch.cuda.empty_cache()
         print(json.dumps(rec), flush=True)
         lines.append(rec)
+        arms = a.min_component if a.min_component else ([0] if a.largest_only else [])
+        for m_min in arms:
+            vol = mesh.density_volume(query, act, R, lo, hi, device=dev)
+            t_ccl, t_fmc = [], []
+            for _ in range(a.reps):
+                comps, fvol, ms = _components_timed(vol, a.threshold, m_min, a.largest_only)
+                ev = _events()
+                ev[0].record()
+                fm = mesh.marching_cubes(fvol, a.threshold, lo, hi)
+                ev[1].record()
+                torch.cuda.synchronize()
+                t_ccl.append(ms)
+                t_fmc.append(ev[0].elapsed_time(ev[1]))
+            ncomp, inside, largest = comps.stats.tolist()
+            big = int(comps.sizes.reshape(-1)[largest]) if largest >= 0 else 0
+            t_ccl = np.mean(np.array(t_ccl), 0)
+            arm = {"tool": "ngp_mesh components", "R": R, "iters": tr.it, "march_steps": a.march_steps, "seed": 4,
+                   "distortion_weight": a.dist_weight, "random_background": bool(a.random_bg), "threshold": a.threshold,
+                   "min_component": m_min, "largest_only": bool(a.largest_only), "components": ncomp, "inside_voxels": inside,
+                   "largest_voxels": big, "largest_share": (big / inside if inside else None),
+                   "kept_voxels": int((fvol > a.threshold).sum()), "V": int(fm.verts.shape[0]), "F": int(fm.faces.shape[0]),
+                   "V_unfiltered": rec["V"], "geometry": _geometry(fm.verts, R, bound, boxes),
+                   "label_ms": float(t_ccl[0]), "sizes_ms": float(t_ccl[1]), "filter_ms": float(t_ccl[2]),
+                   "marching_cubes_ms": float(np.mean(t_fmc)), "density_volume_ms": rec["density_volume_ms"],
+                   "device": rec["device"]}
+            del vol, comps, fvol, fm
+            torch.cuda.empty_cache()
+            print(json.dumps(arm), flush=True)
+            lines.append(arm)
     if a.out:
         with open(a.out, "a") as fh:
             for r in lines:
@@ -202,7 +265,10 @@ def _bytes(kernel, R, V, F):
     return {"mesh_count_kernel": 4 * n3 + 16 * nblk,
             "mesh_vertices_kernel": 4 * n3 + 4 * n3 + 8 * nblk + (24 + 44) * V,
             "mesh_faces_kernel": 4 * n3 + 4 * n3 + 8 * nblk + 12 * F,
-            "mesh_points_kernel": 48 * n3}.get(kernel)
+            "mesh_points_kernel": 48 * n3,
+            # csrc/ccl.hip: the streaming bytes of each launch (the parent walks and the atomics come on top)
+            "ccl_init_kernel": 8 * n3, "ccl_union_kernel": 4 * n3, "ccl_flatten_kernel": 8 * n3, "ccl_zero_kernel": 4 * n3,
+            "ccl_count_kernel": 4 * n3, "ccl_roots_kernel": 8 * n3, "ccl_filter_kernel": 12 * n3}.get(kernel)
 
 
 def stats(a):
@@ -213,7 +279,8 @@ def stats(a):
         with open(a.from_) as fh:
             for ln in fh:
                 r = json.loads(ln)
-                runs[r["R"]] = r
+                if r.get("tool") == "ngp_mesh":
+                    runs[r["R"]] = r
     with open(a.stats) as fh:
         rows = list(csv.DictReader(fh))
     col = {k.lower(): k for k in rows[0]} if rows else {}
@@ -222,12 +289,12 @@ def stats(a):
     gx = col.get("grid_size_x", col.get("grid_size"))
     groups = {}
     for r in rows:
-        m = re.search(r"(mesh_\w+_kernel|occ_cull_scan_kernel|occ_merge_exp_kernel)", r[name_k])
+        m = re.search(r"(mesh_\w+_kernel|ccl_\w+_kernel|occ_cull_scan_kernel|occ_merge_exp_kernel)", r[name_k])
         if not m:
             continue
         k = m.group(1)
         grid = int(r[gx])
-        if k == "mesh_points_kernel" or k == "occ_merge_exp_kernel" or k == "occ_cull_scan_kernel":
+        if k in ("mesh_points_kernel", "occ_merge_exp_kernel", "occ_cull_scan_kernel", "ccl_finish_kernel"):
             R = None                                                       # chunked / one workgroup: pooled per kernel
         else:
             R = next((R for R in runs if -(-R ** 3 // BLOCK) * BLOCK == grid), None)
