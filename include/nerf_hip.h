@@ -620,6 +620,46 @@ int nerf_ccl_sizes(const int32_t* labels, int res, int32_t* sizes, int64_t* stat
 int nerf_ccl_filter(const float* vol, const int32_t* labels, const int32_t* sizes, const int64_t* stats, int res, float iso,
                     int64_t min_voxels, int largest_only, float* out, void* stream);
 
+/* ---------------------------------------------------------------- morphological opening (no reference counterpart)
+ * An erosion ahead of the connected-component filter, to cut the thin bridges that tie a floater to the surface, and the
+ * geodesic reconstruction that gives what the filter kept its skin back.  Additive: NERF_ABI_VERSION stays 3.  Volumes as in
+ * "connected components": contiguous float32 [R, R, R], p = i + R (j + R k), inside set M = {v > iso} (NaN and v == iso are
+ * outside), 2 <= R <= NERF_MESH_MAX_RES, iso finite; neighbours are +-1 along one axis inside the lattice (i = R - 1 and the next
+ * row's i = 0 are not neighbours).  radius r: 1 <= r <= NERF_MORPH_MAX_RADIUS; the structuring element is the 6-neighbour (L1)
+ * ball of radius r = r iterations of the 6-neighbour step.  tests/_morph_ref.py reproduces every output bit for bit.
+ *   erode        E_0 = M; E_{n+1}[p] = E_n[p] and all six neighbours are in E_n, a neighbour beyond the lattice counting as
+ *                outside (the box faces erode too); E = E_r.  core[p] = (p in M \ E) ? iso : vol[p]; every other voxel (NaN
+ *                included) is copied bit for bit.  core is again a volume of these conventions: nerf_ccl_* run on it unchanged.
+ *                core may alias vol.  stats2 = (|M|, |E|).
+ *   reconstruct  seeds K = {kept > iso} within M (a seed outside M is ignored); D_0 = K; D_{n+1} = (D_n united with the six
+ *                neighbours of D_n) within M: geodesic dilation, exactly r steps, not to convergence.  out[p] = (p in M \ D_r) ? iso : vol[p];
+ *                everything else is copied bit for bit.  out may alias vol or kept.  stats2 = (|K|, |D_r|).
+ *   stats2       int64 [2], exact integer reductions (integer atomics, in any order).
+ *   pipeline     (engine/mesh.py open_components) core = erode(vol); kept = nerf_ccl_filter(core) or core itself; out =
+ *                reconstruct(vol, kept).  min_voxels of the filter then counts CORE voxels.
+ * Properties (tests/test_morph_host.py checks each on the reference):
+ *   - E is the direct definition: p is in E exactly when every lattice point within L1 distance r of p is in M and none of
+ *     those points lies beyond the lattice.
+ *   - E (+) ball_r is a subset of D_r, D_r a subset of M (with K = E, or K any union of components of E): the reconstruction
+ *     gives back at least the classical opening, and keeps thin detail within r steps of a kept core.  It never crosses a gap:
+ *     two arms of M closer than r in L1 but farther apart inside M do not seed each other.
+ *   - With K = E, erode(out) has the core E again: the operation is idempotent.
+ *   - Sub-mesh, weaker than the filter's: a crossing edge of `out` whose outside end was outside in vol carries the original
+ *     mesh's vertex bit for bit, and these keep their order; an edge whose outside end is a dropped voxel (value iso exactly)
+ *     carries a new cut vertex on the dropped voxel (t = 1 counted from the kept end).
+ *   - A field thinner than 2 r + 1 voxels everywhere has an empty core: everything is dropped and the mesh is empty.  That is
+ *     the definition, not an error.
+ * Calls: pack (one wave's ballot of v > iso over 64 consecutive x is a mask word; rows are padded to whole 64-bit words, the dead
+ * bits 0), r steps on the bit masks (one lane per word; y / z neighbours are whole words, x neighbours a shift with a carry bit
+ * from the adjacent word of the same row), apply (one lane per voxel): r + 2 launches per call, decided by (R, r) alone; nothing
+ * is read on the host; every output bit has one writer.  workspace: nerf_morph_workspace_bytes(R) bytes of unspecified content
+ * (three masks), not kept between calls.  Argument errors (R, non-finite iso, radius, NULL) return before any launch.          */
+#define NERF_MORPH_MAX_RADIUS 16
+int64_t nerf_morph_workspace_bytes(int res);
+int nerf_morph_erode(const float* vol, int res, float iso, int radius, void* workspace, float* core, int64_t* stats2, void* stream);
+int nerf_morph_reconstruct(const float* vol, const float* kept, int res, float iso, int radius, void* workspace, float* out,
+                           int64_t* stats2, void* stream);
+
 /* ---------------------------------------------------------------- fused renderer (a14 / a18)
  * replaces: rendering/render.py:164-241 render_rays_eval (coarse pass, importance sampling, sort, second pass)
  * as ONE call that enqueues the fixed kernel sequence on `stream`: nerf_sample_coarse -> nerf_query_fused ->

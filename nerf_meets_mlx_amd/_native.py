@@ -99,6 +99,9 @@ SIGNATURES = {
     "nerf_ccl_label": (_I, [_P, _I, _F, _P, _P, _P]),
     "nerf_ccl_sizes": (_I, [_P, _I, _P, _P, _P]),
     "nerf_ccl_filter": (_I, [_P, _P, _P, _P, _I, _F, _I64, _I, _P, _P]),
+    "nerf_morph_workspace_bytes": (_I64, [_I]),
+    "nerf_morph_erode": (_I, [_P, _I, _F, _I, _P, _P, _P, _P]),
+    "nerf_morph_reconstruct": (_I, [_P, _P, _I, _F, _I, _P, _P, _P, _P]),
 }
 
 

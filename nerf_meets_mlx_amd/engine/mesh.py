@@ -10,6 +10,11 @@ section 14).  The reference has no such export; this is Instant-NGP's.
     (or all but the largest) to `iso`, which removes their pieces from the mesh and leaves the rest of it bit for bit
     (include/nerf_hip.h "connected components").  `extract(..., min_component, largest_only)` runs it
     between the density volume and marching cubes.
+  * `erode(volume, iso, radius)` takes `radius` 6-neighbour layers off {v > iso} (the box faces erode too), which cuts the thin
+    bridges that tie a floater to the surface; `reconstruct(volume, kept, iso, radius)` grows what was kept back inside
+    {v > iso} by exactly `radius` geodesic steps; `open_components` is erode -> filter_components on the core -> reconstruct
+    (include/nerf_hip.h "morphological opening").  `extract(..., opening_radius)` runs it in place of the
+    plain filter; `min_component` then counts core voxels.
   * `write_ply` writes a binary little-endian PLY.
 """
 import ctypes as C
@@ -24,6 +29,7 @@ import torch
 from .. import _native as N
 
 MAX_RES = 512                # NERF_MESH_MAX_RES
+MAX_OPENING_RADIUS = 16      # NERF_MORPH_MAX_RADIUS
 CHUNK = 1 << 19              # lattice points (or vertices) per query, as OccupancyGrid.update
 RELU, EXP = 0, 1             # NERF_OCC_RELU / NERF_OCC_EXP
 
@@ -178,6 +184,68 @@ def filter_components(volume: torch.Tensor, iso: float, min_component: int = 0, 
     return out
 
 
+def check_opening_args(opening_radius) -> int:
+    """opening_radius as an int; ValueError for a bool, a non-integral value or one outside [0, MAX_OPENING_RADIUS] (0: no
+    opening)."""
+    if isinstance(opening_radius, bool) or not isinstance(opening_radius, numbers.Integral) \
+            or not 0 <= int(opening_radius) <= MAX_OPENING_RADIUS:
+        raise ValueError(f"opening_radius must be an int in [0, {MAX_OPENING_RADIUS}], got {opening_radius!r}")
+    return int(opening_radius)
+
+
+def _check_radius(who, radius) -> int:
+    if check_opening_args(radius) < 1:
+        raise ValueError(f"{who}: radius must be an int in [1, {MAX_OPENING_RADIUS}], got {radius!r}")
+    return int(radius)
+
+
+def erode(volume: torch.Tensor, iso: float, radius: int):
+    """(core, stats): `radius` steps of 6-neighbour erosion of {v > iso}, a neighbour beyond the lattice counting as outside;
+    in the new volume `core` every inside voxel the erosion removed holds `iso`, everything else is copied bit for bit
+    (nerf_morph_erode).  stats: int64 [2] device tensor = (inside voxels, core voxels); nothing is read on the host."""
+    R, iso = _check_volume("erode", volume, iso)
+    radius = _check_radius("erode", radius)
+    L = N.lib()
+    ws = torch.empty(L.nerf_morph_workspace_bytes(R), dtype=torch.uint8, device=volume.device)
+    core = torch.empty_like(volume)
+    stats = torch.empty(2, dtype=torch.int64, device=volume.device)
+    N.check(L.nerf_morph_erode(N.ptr(volume), R, iso, radius, N.ptr(ws), N.ptr(core), N.ptr(stats), N.stream()))
+    return core, stats
+
+
+def reconstruct(volume: torch.Tensor, kept: torch.Tensor, iso: float, radius: int):
+    """(out, stats): the seeds {kept > iso} inside {volume > iso} grown by exactly `radius` 6-neighbour steps that never leave
+    {volume > iso} (geodesic dilation); in the new volume `out` every inside voxel of `volume` they did not reach holds `iso`,
+    everything else is copied bit for bit (nerf_morph_reconstruct).  `kept` must match `volume` in shape, dtype and device.
+    stats: int64 [2] device tensor = (seed voxels, voxels reached); nothing is read on the host."""
+    R, iso = _check_volume("reconstruct", volume, iso)
+    radius = _check_radius("reconstruct", radius)
+    if not torch.is_tensor(kept) or kept.shape != volume.shape or kept.dtype != volume.dtype or kept.device != volume.device \
+            or not kept.is_contiguous():
+        raise ValueError("reconstruct: kept must be a contiguous tensor of the volume's shape, dtype and device")
+    L = N.lib()
+    ws = torch.empty(L.nerf_morph_workspace_bytes(R), dtype=torch.uint8, device=volume.device)
+    out = torch.empty_like(volume)
+    stats = torch.empty(2, dtype=torch.int64, device=volume.device)
+    N.check(L.nerf_morph_reconstruct(N.ptr(volume), N.ptr(kept), R, iso, radius, N.ptr(ws), N.ptr(out), N.ptr(stats), N.stream()))
+    return out, stats
+
+
+def open_components(volume: torch.Tensor, iso: float, radius: int, min_component: int = 0,
+                    largest_only: bool = False) -> torch.Tensor:
+    """A new volume: core = erode(volume, iso, radius); kept = filter_components(core, iso, min_component, largest_only) when
+    min_component > 1 or largest_only, else the core itself (the plain opening by reconstruction); reconstruct(volume, kept, iso,
+    radius).  `min_component` counts CORE voxels: a piece thinner than 2 radius + 1 voxels everywhere has none and is dropped
+    whatever its size, and a field that thin everywhere yields an empty volume."""
+    R, iso = _check_volume("open_components", volume, iso)
+    radius = _check_radius("open_components", radius)
+    min_component, largest_only = check_component_args(min_component, largest_only, R)
+    kept, _ = erode(volume, iso, radius)
+    if min_component > 1 or largest_only:
+        kept = filter_components(kept, iso, min_component, largest_only)
+    return reconstruct(volume, kept, iso, radius)[0]
+
+
 def vertex_colors(query, rows: torch.Tensor, chunk: int = CHUNK) -> torch.Tensor:
     """clamp(raw[..., :3], 0, 1) of query(rows, z = 0) -> raw [n, 1, 4] on the colour rows of nerf_mesh_write_vertices."""
     V = rows.shape[0]
@@ -193,13 +261,17 @@ def vertex_colors(query, rows: torch.Tensor, chunk: int = CHUNK) -> torch.Tensor
 
 
 def extract(query, activation: int, resolution: int, threshold: float, lo, hi, colors: bool = True, device="cuda",
-            min_component: int = 0, largest_only: bool = False) -> Mesh:
-    """density_volume -> (with min_component > 1 or largest_only: filter_components) -> marching_cubes at `threshold` ->
-    (optionally) vertex colours, queried on the filtered mesh's rows.  With the defaults the filter is not called."""
+            min_component: int = 0, largest_only: bool = False, opening_radius: int = 0) -> Mesh:
+    """density_volume -> (with opening_radius > 0: open_components; else with min_component > 1 or largest_only:
+    filter_components) -> marching_cubes at `threshold` -> (optionally) vertex colours, queried on the filtered mesh's rows.
+    With opening_radius > 0 `min_component` counts core voxels (open_components).  With the defaults neither is called."""
     check_mesh_args(resolution, lo, hi, threshold)
     min_component, largest_only = check_component_args(min_component, largest_only, resolution)
+    opening_radius = check_opening_args(opening_radius)
     vol = density_volume(query, activation, resolution, lo, hi, device=device)
-    if min_component > 1 or largest_only:
+    if opening_radius > 0:
+        vol = open_components(vol, threshold, opening_radius, min_component, largest_only)
+    elif min_component > 1 or largest_only:
         vol = filter_components(vol, threshold, min_component, largest_only)
     mesh, rows = _marching_cubes(vol, threshold, lo, hi, colors)
     if not colors:

@@ -15,6 +15,10 @@ parsed back and checked (V, F, every directed edge at most once).  With --min-co
 one more line per value: the 6-connected components of {sigma > threshold} -- their number, the largest
 one's share of the inside voxels --, V, F and the geometry figures of the filtered mesh with the number of vertices farther than
 2 h from the boxes, and the device ms of the label, sizes and filter calls next to the density volume's and marching cubes'.
+With --opening-radius r (repeatable), one more line per filtered arm and r > 0: the opening of DESIGN.md section 18 (erode ->
+filter of the core -> reconstruct) -- its four stats (inside, core, seed and reconstructed voxels), the components of the core
+and the largest one's share, V, F, the geometry figures, and the device ms of the erode call, of the labelling of the core
+(label, sizes, filter) and of the reconstruct call.
 
     rocprofv3 --kernel-trace --output-format csv -d DIR -o mesh -- python tools/ngp_mesh.py --ckpt /tmp/ngp.npz --reps 1 --no-ply
     python tools/ngp_mesh.py --stats DIR/.../mesh_kernel_trace.csv --from profiles/ngp_mesh.jsonl --out profiles/ngp_mesh_kernels.jsonl
@@ -109,6 +113,41 @@ def _components_timed(vol, iso, min_component, largest_only):
     return mesh.Components(labels, sizes, stats), out, [e[k].elapsed_time(e[k + 1]) for k in range(3)]
 
 
+def _opening_timed(vol, iso, radius, min_component, largest_only):
+    """engine.mesh.open_components as its C calls, each between device events: (Components of the core, opened volume,
+    [erode, label, sizes, filter, reconstruct] ms, [|M|, |E|, |K|, |D_r|])."""
+    from nerf_meets_mlx_amd import _native as N
+    from nerf_meets_mlx_amd.engine import mesh
+    L = N.lib()
+    R, dev = vol.shape[0], vol.device
+    ws = torch.empty(L.nerf_morph_workspace_bytes(R), dtype=torch.uint8, device=dev)
+    ccl_ws = torch.empty(L.nerf_ccl_workspace_bytes(R), dtype=torch.uint8, device=dev)
+    core, kept, out = torch.empty_like(vol), torch.empty_like(vol), torch.empty_like(vol)
+    labels = torch.empty(R, R, R, dtype=torch.int32, device=dev)
+    sizes = torch.empty(R, R, R, dtype=torch.int32, device=dev)
+    stats = torch.empty(3, dtype=torch.int64, device=dev)
+    est, rst = (torch.empty(2, dtype=torch.int64, device=dev) for _ in range(2))
+    filt = min_component > 1 or largest_only
+    e = [torch.cuda.Event(enable_timing=True) for _ in range(6)]
+    e[0].record()
+    N.check(L.nerf_morph_erode(N.ptr(vol), R, iso, radius, N.ptr(ws), N.ptr(core), N.ptr(est), N.stream()))
+    e[1].record()
+    N.check(L.nerf_ccl_label(N.ptr(core), R, iso, N.ptr(ccl_ws), N.ptr(labels), N.stream()))
+    e[2].record()
+    N.check(L.nerf_ccl_sizes(N.ptr(labels), R, N.ptr(sizes), N.ptr(stats), N.stream()))
+    e[3].record()
+    if filt:
+        N.check(L.nerf_ccl_filter(N.ptr(core), N.ptr(labels), N.ptr(sizes), N.ptr(stats), R, iso, min_component, int(largest_only),
+                                  N.ptr(kept), N.stream()))
+    e[4].record()
+    N.check(L.nerf_morph_reconstruct(N.ptr(vol), N.ptr(kept if filt else core), R, iso, radius, N.ptr(ws), N.ptr(out), N.ptr(rst),
+                                     N.stream()))
+    e[5].record()
+    torch.cuda.synchronize()
+    return (mesh.Components(labels, sizes, stats), out, [e[k].elapsed_time(e[k + 1]) for k in range(5)],
+            est.tolist() + rst.tolist())
+
+
 def _teacher_volume(R, lo, hi, dev):
     from nerf_meets_mlx_amd.dataset import synthetic
     from nerf_meets_mlx_amd.engine import mesh
@@ -153,6 +192,9 @@ def main():
                     help="also mesh the volume without the components of fewer voxels (DESIGN.md section 17); repeatable: one "
                          "JSON line per value")
     ap.add_argument("--largest-only", action="store_true", help="the filtered arms keep the largest component only")
+    ap.add_argument("--opening-radius", type=int, action="append", default=None,
+                    help="also mesh each filtered arm after an opening of this radius (DESIGN.md section 18); repeatable: one "
+                         "JSON line per arm and radius > 0")
     ap.add_argument("--ckpt", default=None, help="load this checkpoint instead of training")
     ap.add_argument("--save-ckpt", default=None, help="save the trained state here")
     ap.add_argument("--out", default=None, help="append the JSON lines to this file")
@@ -248,10 +290,42 @@ def main():
                    "label_ms": float(t_ccl[0]), "sizes_ms": float(t_ccl[1]), "filter_ms": float(t_ccl[2]),
                    "marching_cubes_ms": float(np.mean(t_fmc)), "density_volume_ms": rec["density_volume_ms"],
                    "device": rec["device"]}
-            del vol, comps, fvol, fm
+            del comps, fvol, fm
             torch.cuda.empty_cache()
             print(json.dumps(arm), flush=True)
             lines.append(arm)
+            for r in [r for r in (a.opening_radius or []) if r > 0]:
+                t_open, t_omc = [], []
+                for _ in range(a.reps):
+                    comps, ovol, ms, st = _opening_timed(vol, a.threshold, r, m_min, a.largest_only)
+                    ev = _events()
+                    ev[0].record()
+                    om = mesh.marching_cubes(ovol, a.threshold, lo, hi)
+                    ev[1].record()
+                    torch.cuda.synchronize()
+                    t_open.append(ms)
+                    t_omc.append(ev[0].elapsed_time(ev[1]))
+                ncomp, core_vox, largest = comps.stats.tolist()
+                big = int(comps.sizes.reshape(-1)[largest]) if largest >= 0 else 0
+                t_open = np.mean(np.array(t_open), 0)
+                orec = {"tool": "ngp_mesh opening", "R": R, "iters": tr.it, "march_steps": a.march_steps, "seed": 4,
+                        "distortion_weight": a.dist_weight, "random_background": bool(a.random_bg), "threshold": a.threshold,
+                        "opening_radius": r, "min_component": m_min, "largest_only": bool(a.largest_only),
+                        "inside_voxels": st[0], "core_voxels": st[1], "seed_voxels": st[2], "reconstructed_voxels": st[3],
+                        "core_components": ncomp, "largest_core_voxels": big,
+                        "largest_core_share": (big / core_vox if core_vox else None),
+                        "V": int(om.verts.shape[0]), "F": int(om.faces.shape[0]), "V_unfiltered": rec["V"], "V_filtered": arm["V"],
+                        "geometry": _geometry(om.verts, R, bound, boxes),
+                        "erode_ms": float(t_open[0]), "label_core_ms": float(t_open[1]), "sizes_core_ms": float(t_open[2]),
+                        "filter_core_ms": float(t_open[3]), "reconstruct_ms": float(t_open[4]),
+                        "marching_cubes_ms": float(np.mean(t_omc)), "label_ms": arm["label_ms"], "sizes_ms": arm["sizes_ms"],
+                        "filter_ms": arm["filter_ms"], "density_volume_ms": rec["density_volume_ms"], "device": rec["device"]}
+                del comps, ovol, om
+                torch.cuda.empty_cache()
+                print(json.dumps(orec), flush=True)
+                lines.append(orec)
+            del vol
+            torch.cuda.empty_cache()
     if a.out:
         with open(a.out, "a") as fh:
             for r in lines:
@@ -268,7 +342,23 @@ def _bytes(kernel, R, V, F):
             "mesh_points_kernel": 48 * n3,
             # csrc/ccl.hip: the streaming bytes of each launch (the parent walks and the atomics come on top)
             "ccl_init_kernel": 8 * n3, "ccl_union_kernel": 4 * n3, "ccl_flatten_kernel": 8 * n3, "ccl_zero_kernel": 4 * n3,
-            "ccl_count_kernel": 4 * n3, "ccl_roots_kernel": 8 * n3, "ccl_filter_kernel": 12 * n3}.get(kernel)
+            "ccl_count_kernel": 4 * n3, "ccl_roots_kernel": 8 * n3, "ccl_filter_kernel": 12 * n3,
+            # csrc/morph.hip: the float passes (pack reads the volume, with seeds two; apply reads and writes it) and a mask step
+            # (one word read -- its six neighbours are cache hits --, M for a dilation, one written); a mask is n3 / 8 bytes at
+            # R % 64 == 0
+            "morph_pack_kernel": 4 * n3 + n3 // 8, "morph_pack_kernel<seeds>": 8 * n3 + n3 // 4,
+            "morph_apply_kernel": 8 * n3 + n3 // 4, "morph_step_kernel": n3 // 4,
+            "morph_step_kernel<dilate>": 3 * n3 // 8}.get(kernel)
+
+
+def _morph_grid(kernel, R):
+    """Work-items of a csrc/morph.hip launch at lattice size R."""
+    words = -(-R // 64) * R * R
+    if kernel.startswith("morph_pack"):
+        return -(-words // 4) * BLOCK
+    if kernel.startswith("morph_step"):
+        return min(-(-words // BLOCK), 1024) * BLOCK
+    return -(-R ** 3 // BLOCK) * BLOCK
 
 
 def stats(a):
@@ -289,11 +379,17 @@ def stats(a):
     gx = col.get("grid_size_x", col.get("grid_size"))
     groups = {}
     for r in rows:
-        m = re.search(r"(mesh_\w+_kernel|ccl_\w+_kernel|occ_cull_scan_kernel|occ_merge_exp_kernel)", r[name_k])
+        m = re.search(r"(mesh_\w+_kernel|ccl_\w+_kernel|morph_\w+_kernel|occ_cull_scan_kernel|occ_merge_exp_kernel)", r[name_k])
         if not m:
             continue
         k = m.group(1)
         grid = int(r[gx])
+        if k.startswith("morph_"):
+            if re.search(r"<true>|ILb1E", r[name_k]):
+                k += "<seeds>" if k == "morph_pack_kernel" else "<dilate>"
+            R = next((R for R in runs if _morph_grid(k, R) == grid), None)
+            groups.setdefault((k, R), []).append((int(r[e_k]) - int(r[s_k])) * 1e-3)
+            continue
         if k in ("mesh_points_kernel", "occ_merge_exp_kernel", "occ_cull_scan_kernel", "ccl_finish_kernel"):
             R = None                                                       # chunked / one workgroup: pooled per kernel
         else:
