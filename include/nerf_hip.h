@@ -178,6 +178,31 @@ int nerf_hashgrid_backward_rays_ex(const float* rays, const float* z, int64_t B,
                                    int log2_T, int F, const int* resolutions_host, float pos_scale, float pos_offset,
                                    int level_lo, int level_hi, int fixed_point, void* d_tables, void* stream);
 
+/* Level weights (coarse-to-fine training of the hash grid: FreeNeRF's frequency mask, Neuralangelo's progressive levels).
+ * The `_lw` entries take a per-level weight vector w[L]: float32, each finite and in [0, 1], a HOST array like
+ * resolutions_host; NULL means all ones and runs exactly the kernels of the entry without the suffix.  A value outside
+ * [0, 1] or a NaN is NERF_E_SHAPE.  Everything else is the argument list of the entry without the suffix.
+ *   forward         feature (l, f) = w[l] * interp_l,f: ONE float32 multiply after the interpolation above, before any
+ *                   rounding to bf16 / fp16 fragments.  w[l] == 0: level l's tables are NOT READ and its features are
+ *                   exactly +0, whatever the tables hold (NaN and Inf included).  w[l] == 1: bit-identical to the entry
+ *                   without the suffix.
+ *   table gradient  g = w[l] * d_out[., l, f] (one float32 multiply), then the addend formula above with g in place of
+ *                   d_out.  w[l] == 0: level l issues no atomics and its accumulators are not touched (the LDS
+ *                   write-combining path of the coarse levels included).
+ *   MLP input gradient: the d_x of nerf_mlp_backward_inputs is unchanged; the weight applies on the way into the tables. */
+int nerf_hashgrid_forward_lw(const float* x, int64_t M, const float* tables, int L, int log2_T, int F,
+                             const int* resolutions_host, const float* level_weights_host, float* out, void* stream);
+int nerf_ngp_encode_lw(const float* rays, const float* z, int64_t B, int n, const float* tables, int L, int log2_T,
+                       int F, const int* resolutions_host, const float* level_weights_host, int sh_degree,
+                       float pos_scale, float pos_offset, float* x_out, float* pts_out, void* stream);
+int nerf_hashgrid_backward_ex_lw(const float* x, int64_t M, const float* d_out, int L, int log2_T, int F,
+                                 const int* resolutions_host, const float* level_weights_host, int level_lo,
+                                 int level_hi, int fixed_point, void* d_tables, void* stream);
+int nerf_hashgrid_backward_rays_ex_lw(const float* rays, const float* z, int64_t B, int n, const float* d_out, int L,
+                                      int log2_T, int F, const int* resolutions_host, const float* level_weights_host,
+                                      float pos_scale, float pos_offset, int level_lo, int level_hi, int fixed_point,
+                                      void* d_tables, void* stream);
+
 /* ---------------------------------------------------------------- compositing (a13)
  * replaces: rendering/render.py:20-96 raw2outputs.  raw [B,n,4] = [rgb, sigma];
  * noise [B,n] (N(0,1), caller's RNG) may be NULL when raw_noise_std == 0.
@@ -330,6 +355,13 @@ int nerf_ngp_query_fused_h(const nerf_mlp_arch* arch, const void* packed, const 
                            int n, const float* tables, const void* tables_half, int L, int log2_T, int F,
                            const int* resolutions_host, int sh_degree, float pos_scale, float pos_offset, float* raw,
                            void* acts, void* stream);
+/* The same query with level weights ("Level weights" above): both fused kernels (bf16 with float32 or fp16-shadow gathers,
+ * split-bf16 at precision 22), both store modes, the ray-major inference tiling.  A lane's gathers of a level with
+ * w[l] == 0 are predicated off.  level_weights_host == NULL: nerf_ngp_query_fused_h.                                  */
+int nerf_ngp_query_fused_lw(const nerf_mlp_arch* arch, const void* packed, const float* rays, const float* z, int64_t B,
+                            int n, const float* tables, const void* tables_half, int L, int log2_T, int F,
+                            const int* resolutions_host, const float* level_weights_host, int sh_degree, float pos_scale,
+                            float pos_offset, float* raw, void* acts, void* stream);
 
 /* ---------------------------------------------------------------- occupancy grid (no reference counterpart)
  * Empty-space skipping for the hash-grid model: Instant-NGP's occupancy grid (Mueller et al. 2022, "Instant Neural Graphics

@@ -59,10 +59,12 @@ __global__ void sh_kernel(const float* __restrict__ d, int64_t M, int deg, float
 }
 
 // ---- multires hash grid  encoding/multi_hash.py:61-136 (intended semantics) ------------------
-template <int F, int LG>
+// LW: per-level weights (`_lw` entries): out = w[l] * interpolation; a level with w[l] == 0 is not gathered and gives +0.  The
+// level is uniform over the workgroup (blockIdx.y), so the skip is a scalar branch.  LW = false never reads `lw`.
+template <int F, int LG, bool LW>
 __global__ void __launch_bounds__(256) hashgrid_fwd_kernel(PointSrc ps, int64_t M, const float* __restrict__ tables,
                                                            int L, uint32_t T, ResTab rt, float* __restrict__ out,
-                                                           int64_t out_stride) {
+                                                           int64_t out_stride, LevelTab lw) {
   const int l0 = blockIdx.y * LG;
   const uint32_t mask = T - 1;
   for (int64_t m = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; m < M; m += (int64_t)gridDim.x * blockDim.x) {
@@ -73,11 +75,16 @@ __global__ void __launch_bounds__(256) hashgrid_fwd_kernel(PointSrc ps, int64_t 
     for (int li = 0; li < LG; ++li) {
       const int l = l0 + li;
       if (l >= L) break;
+      if (LW && lw.w[l] == 0.0f) {
+#pragma unroll
+        for (int f = 0; f < F; ++f) vals[li * F + f] = 0.0f;
+        continue;
+      }
       const Corners c = corners_of(px, py, pz, rt.res[l], mask);
       const float* tb = tables + (size_t)l * T * F;
       const FeatVec<F> fv = hash_level<F>(tb, c);
 #pragma unroll
-      for (int f = 0; f < F; ++f) vals[li * F + f] = fv.v[f];
+      for (int f = 0; f < F; ++f) vals[li * F + f] = LW ? lw.w[l] * fv.v[f] : fv.v[f];
     }
 #pragma unroll
     for (int i = 0; i < LG * F; ++i)
@@ -119,10 +126,11 @@ __global__ void __launch_bounds__(256) ngp_dir_rows_kernel(const float* __restri
 // is also the exactly rounded sum of the quantised addends (|addend| < 2^11, resolution 2^-52: finer than float32 for
 // every addend above 3e-9, and Adam's eps = 1e-8 hides what is below; out-of-range and non-finite addends: nerf_to_fixed,
 // hash_common.h).  nerf_adam_step_ex reads the accumulators.
-template <int F, int LG, bool FIXED>
+// LW (`_lw` entries): g = w[l] * d_out (one float32 multiply) in place of d_out; a level with w[l] == 0 issues no atomics.
+template <int F, int LG, bool FIXED, bool LW>
 __global__ void __launch_bounds__(256) hashgrid_bwd_kernel(PointSrc ps, int64_t M,
                                                            void* __restrict__ d_tables_v, const float* __restrict__ d_out,
-                                                           int L, uint32_t T, ResTab rt, int level_lo, int level_hi) {
+                                                           int L, uint32_t T, ResTab rt, int level_lo, int level_hi, LevelTab lw) {
   const int l0 = level_lo + blockIdx.y * LG;
   const uint32_t mask = T - 1;
   const int64_t total = M * (2 * F);
@@ -153,6 +161,7 @@ __global__ void __launch_bounds__(256) hashgrid_bwd_kernel(PointSrc ps, int64_t 
     for (int li = 0; li < LG; ++li) {
       const int l = l0 + li;
       if (l >= level_hi) break;
+      if (LW && lw.w[l] == 0.0f) continue;
       const float r = rt.res[l];
       // same roundings as corners_of (hash_common.h): xs = p * r, floor / ceil, offset = xs - floor
       const float xs = px * r, ys = py * r, zs = pz * r;
@@ -162,7 +171,7 @@ __global__ void __launch_bounds__(256) hashgrid_bwd_kernel(PointSrc ps, int64_t 
       const uint32_t yf = (uint32_t)(int32_t)fy * 2654435761u, yc = (uint32_t)(int32_t)ceilf(ys) * 2654435761u;
       const uint32_t zf = (uint32_t)(int32_t)fz * 805459861u, zc = (uint32_t)(int32_t)ceilf(zs) * 805459861u;
       const size_t tb = (size_t)l * T * F + f;
-      const float g = d_out[(m * L + l) * F + f];
+      const float g = LW ? lw.w[l] * d_out[(m * L + l) * F + f] : d_out[(m * L + l) * F + f];
       // products in the order of the per-corner form (g * wz * wy * wx), so every addend is bit-identical to it
       const float wx = dx ? ox : 1 - ox;
       add(tb + (size_t)((cx ^ yc ^ zc) & mask) * F, g * oz * oy * wx);
@@ -187,16 +196,17 @@ int g_hash_combine_max_res = 64;    // A/B knob (nerf_set_option "hash_combine_m
 constexpr int HC_CAP = 1024;                       // slots; at most 64 samples x 8 corners = 512 distinct keys per iteration
 constexpr int HC_PROBES = 32;
 constexpr uint32_t HC_EMPTY = 0xFFFFFFFFu;
-template <int F, bool FIXED>
+template <int F, bool FIXED, bool LW>
 __global__ void __launch_bounds__(256) hashgrid_bwd_combine_kernel(PointSrc ps, int64_t M, void* __restrict__ d_tables_v,
                                                                    const float* __restrict__ d_out, int L, uint32_t T,
-                                                                   ResTab rt, int level_lo) {
+                                                                   ResTab rt, int level_lo, LevelTab lw) {
   typedef typename std::conditional<FIXED, unsigned long long, float>::type AccT;
   __shared__ uint32_t keys[HC_CAP];
   __shared__ uint32_t list[HC_CAP];
   __shared__ AccT vals[HC_CAP * F];
   __shared__ uint32_t count[2];
   const int l = level_lo + blockIdx.y;
+  if (LW && lw.w[l] == 0.0f) return;               // the whole workgroup serves this level: nothing is added, LDS or global
   const uint32_t mask = T - 1;
   const float r = rt.res[l];
   float* d_tables = static_cast<float*>(d_tables_v);
@@ -225,7 +235,7 @@ __global__ void __launch_bounds__(256) hashgrid_bwd_combine_kernel(PointSrc ps, 
       const uint32_t cx = (uint32_t)(int32_t)(dx ? ceilf(xs) : fx);
       const uint32_t yf = (uint32_t)(int32_t)fy * 2654435761u, yc = (uint32_t)(int32_t)ceilf(ys) * 2654435761u;
       const uint32_t zf = (uint32_t)(int32_t)fz * 805459861u, zc = (uint32_t)(int32_t)ceilf(zs) * 805459861u;
-      const float g = d_out[(m * L + l) * F + f];
+      const float g = LW ? lw.w[l] * d_out[(m * L + l) * F + f] : d_out[(m * L + l) * F + f];
       const float wx = dx ? ox : 1 - ox;
       const uint32_t idx[4] = {(cx ^ yc ^ zc) & mask, (cx ^ yf ^ zc) & mask, (cx ^ yc ^ zf) & mask, (cx ^ yf ^ zf) & mask};
       const float val[4] = {g * oz * oy * wx, g * oz * (1 - oy) * wx, g * (1 - oz) * oy * wx, g * (1 - oz) * (1 - oy) * wx};
@@ -271,7 +281,7 @@ static int launch_hashgrid(const float* x, int64_t M, const float* tables, float
                            int log2_T, int F, const int* res, float* out, void* stream, const char* who,
                            const float* rays = nullptr, const float* z = nullptr, int n = 1, int64_t out_stride = 0,
                            float pos_scale = 1.0f, float pos_offset = 0.0f, int level_lo = 0, int level_hi = -1,
-                           bool fixed = false) {
+                           bool fixed = false, const float* lw_host = nullptr) {
   NERF_REQUIRE((x || (rays && z)) && res, NERF_E_NULL, "%s: NULL pointer", who);
   NERF_REQUIRE(L >= 1 && L <= 32 && log2_T >= 1 && log2_T <= 30, NERF_E_SHAPE, "%s: need 1<=L<=32, 1<=log2_T<=30", who);
   NERF_REQUIRE(F == 1 || F == 2 || F == 4 || F == 8, NERF_E_UNSUPPORTED, "%s: F must be 1, 2, 4 or 8", who);
@@ -283,6 +293,16 @@ static int launch_hashgrid(const float* x, int64_t M, const float* tables, float
   if (level_hi < 0) level_hi = L;
   NERF_REQUIRE(0 <= level_lo && level_lo <= level_hi && level_hi <= L, NERF_E_SHAPE, "%s: need 0 <= level_lo <= level_hi <= L", who);
   if (level_lo == level_hi) return NERF_OK;
+  // level weights (`_lw` entries; NULL = all ones = the kernels without them)
+  LevelTab lt;
+  const bool lw = lw_host != nullptr;
+  if (lw) NERF_REQUIRE(level_tab_fill(lt, lw_host, L), NERF_E_SHAPE, "%s: level weights must be finite and in [0, 1]", who);
+  else for (int l = 0; l < 32; ++l) lt.w[l] = 1.0f;
+  if (BWD && lw) {                                        // masked levels at either end of the range are not launched at all
+    while (level_hi > level_lo && lt.w[level_hi - 1] == 0.0f) --level_hi;
+    while (level_lo < level_hi && lt.w[level_lo] == 0.0f) ++level_lo;
+    if (level_lo == level_hi) return NERF_OK;
+  }
   if (BWD && (F == 2 || F == 4) && g_hash_combine_max_res > 0) {
     // leading levels of the range whose resolution is small enough for LDS write-combining to pay (see the kernel)
     int nc = 0;
@@ -291,10 +311,12 @@ static int launch_hashgrid(const float* x, int64_t M, const float* tables, float
       const dim3 gc(grid_for((M + 63) / 64, 1, 256 * 8), (unsigned)nc), bc(256);
       auto stc = as_stream(stream);
       const PointSrc psc{x, rays, z, n, pos_scale, pos_offset};
-#define HC(FF) do { if (fixed) hipLaunchKernelGGL((hashgrid_bwd_combine_kernel<FF, true>), gc, bc, 0, stc, psc, M, (void*)d_tables, d_out, L, T, rt, level_lo); \
-                    else hipLaunchKernelGGL((hashgrid_bwd_combine_kernel<FF, false>), gc, bc, 0, stc, psc, M, (void*)d_tables, d_out, L, T, rt, level_lo); } while (0)
+#define HC2(FF, FX, LWV) hipLaunchKernelGGL((hashgrid_bwd_combine_kernel<FF, FX, LWV>), gc, bc, 0, stc, psc, M, (void*)d_tables, d_out, L, T, rt, level_lo, lt)
+#define HC(FF) do { if (fixed) { if (lw) HC2(FF, true, true); else HC2(FF, true, false); } \
+                    else { if (lw) HC2(FF, false, true); else HC2(FF, false, false); } } while (0)
       if (F == 2) HC(2); else HC(4);
 #undef HC
+#undef HC2
       const int rc = check_launch(who);
       if (rc) return rc;
       level_lo += nc;
@@ -304,12 +326,17 @@ static int launch_hashgrid(const float* x, int64_t M, const float* tables, float
   const int nlev = BWD ? level_hi - level_lo : L;
   const dim3 g(grid_for(BWD ? M * F * 2 : M, 256, 256 * 32), (unsigned)((nlev + LG - 1) / LG)), b(256);
   auto st = as_stream(stream);
-#define HG(FF) do { if (BWD && fixed) hipLaunchKernelGGL((hashgrid_bwd_kernel<FF, LG, true>), g, b, 0, st, PointSrc{x, rays, z, n, pos_scale, pos_offset}, M, (void*)d_tables, d_out, L, T, rt, level_lo, level_hi); \
-                    else if (BWD) hipLaunchKernelGGL((hashgrid_bwd_kernel<FF, LG, false>), g, b, 0, st, PointSrc{x, rays, z, n, pos_scale, pos_offset}, M, (void*)d_tables, d_out, L, T, rt, level_lo, level_hi); \
-                    else hipLaunchKernelGGL((hashgrid_fwd_kernel<FF, LG>), g, b, 0, st, PointSrc{x, rays, z, n, pos_scale, pos_offset}, M, tables, L, T, rt, out, \
-                                            out_stride > 0 ? out_stride : (int64_t)L * FF); } while (0)
+  const PointSrc psd{x, rays, z, n, pos_scale, pos_offset};
+#define HB(FF, FX, LWV) hipLaunchKernelGGL((hashgrid_bwd_kernel<FF, LG, FX, LWV>), g, b, 0, st, psd, M, (void*)d_tables, d_out, L, T, rt, level_lo, level_hi, lt)
+#define HF(FF, LWV) hipLaunchKernelGGL((hashgrid_fwd_kernel<FF, LG, LWV>), g, b, 0, st, psd, M, tables, L, T, rt, out, \
+                                       out_stride > 0 ? out_stride : (int64_t)L * FF, lt)
+#define HG(FF) do { if (BWD && fixed) { if (lw) HB(FF, true, true); else HB(FF, true, false); } \
+                    else if (BWD) { if (lw) HB(FF, false, true); else HB(FF, false, false); } \
+                    else { if (lw) HF(FF, true); else HF(FF, false); } } while (0)
   switch (F) { case 1: HG(1); break; case 2: HG(2); break; case 4: HG(4); break; default: HG(8); }
 #undef HG
+#undef HF
+#undef HB
   return check_launch(who);
 }
 
@@ -410,4 +437,53 @@ extern "C" int nerf_hashgrid_backward_rays(const float* rays, const float* z, in
   NERF_REQUIRE(rays && z && d_out && d_tables, NERF_E_NULL, "nerf_hashgrid_backward_rays: NULL pointer");
   return launch_hashgrid<true>(nullptr, B * n, nullptr, d_tables, d_out, L, log2_T, F, resolutions_host, nullptr, stream,
                                "nerf_hashgrid_backward_rays", rays, z, n, 0, pos_scale, pos_offset);
+}
+
+// ---- the same entries with per-level weights (include/nerf_hip.h, "level weights"); level_weights_host == NULL: all ones ----
+extern "C" int nerf_hashgrid_forward_lw(const float* x, int64_t M, const float* tables, int L, int log2_T, int F,
+                                        const int* resolutions_host, const float* level_weights_host, float* out,
+                                        void* stream) {
+  NERF_REQUIRE(tables && out, NERF_E_NULL, "nerf_hashgrid_forward_lw: tables/out is NULL");
+  return launch_hashgrid<false>(x, M, tables, nullptr, nullptr, L, log2_T, F, resolutions_host, out, stream,
+                                "nerf_hashgrid_forward_lw", nullptr, nullptr, 1, 0, 1.0f, 0.0f, 0, -1, false, level_weights_host);
+}
+
+extern "C" int nerf_ngp_encode_lw(const float* rays, const float* z, int64_t B, int n, const float* tables, int L,
+                                  int log2_T, int F, const int* resolutions_host, const float* level_weights_host,
+                                  int sh_degree, float pos_scale, float pos_offset, float* x_out, float* pts_out,
+                                  void* stream) {
+  if (B <= 0 || n <= 0) return NERF_OK;
+  NERF_REQUIRE(rays && z && tables && x_out, NERF_E_NULL, "nerf_ngp_encode_lw: NULL pointer");
+  NERF_REQUIRE(sh_degree >= 0 && sh_degree <= 4, NERF_E_SHAPE, "nerf_ngp_encode_lw: sh_degree=%d must be in range [0, 4]", sh_degree);
+  const int64_t M = B * n;
+  const int64_t stride = (int64_t)L * F + (sh_degree + 1) * (sh_degree + 1);
+  const int rc = launch_hashgrid<false>(nullptr, M, tables, nullptr, nullptr, L, log2_T, F, resolutions_host, x_out, stream,
+                                        "nerf_ngp_encode_lw", rays, z, n, stride, pos_scale, pos_offset, 0, -1, false,
+                                        level_weights_host);
+  if (rc) return rc;
+  hipLaunchKernelGGL(ngp_dir_rows_kernel, dim3(grid_for(M, 256)), dim3(256), 0, as_stream(stream), rays, z, n, M, sh_degree,
+                     x_out, stride, L * F, pts_out, pos_scale, pos_offset);
+  return check_launch("nerf_ngp_encode_lw");
+}
+
+extern "C" int nerf_hashgrid_backward_ex_lw(const float* x, int64_t M, const float* d_out, int L, int log2_T, int F,
+                                            const int* resolutions_host, const float* level_weights_host, int level_lo,
+                                            int level_hi, int fixed_point, void* d_tables, void* stream) {
+  NERF_REQUIRE(d_out && d_tables, NERF_E_NULL, "nerf_hashgrid_backward_ex_lw: d_out/d_tables is NULL");
+  NERF_REQUIRE(fixed_point == 0 || fixed_point == 1, NERF_E_UNSUPPORTED, "nerf_hashgrid_backward_ex_lw: fixed_point must be 0 or 1");
+  return launch_hashgrid<true>(x, M, nullptr, static_cast<float*>(d_tables), d_out, L, log2_T, F, resolutions_host, nullptr,
+                               stream, "nerf_hashgrid_backward_ex_lw", nullptr, nullptr, 1, 0, 1.0f, 0.0f, level_lo, level_hi,
+                               fixed_point != 0, level_weights_host);
+}
+
+extern "C" int nerf_hashgrid_backward_rays_ex_lw(const float* rays, const float* z, int64_t B, int n, const float* d_out,
+                                                 int L, int log2_T, int F, const int* resolutions_host,
+                                                 const float* level_weights_host, float pos_scale, float pos_offset,
+                                                 int level_lo, int level_hi, int fixed_point, void* d_tables, void* stream) {
+  if (B <= 0 || n <= 0) return NERF_OK;
+  NERF_REQUIRE(rays && z && d_out && d_tables, NERF_E_NULL, "nerf_hashgrid_backward_rays_ex_lw: NULL pointer");
+  NERF_REQUIRE(fixed_point == 0 || fixed_point == 1, NERF_E_UNSUPPORTED, "nerf_hashgrid_backward_rays_ex_lw: fixed_point must be 0 or 1");
+  return launch_hashgrid<true>(nullptr, B * n, nullptr, static_cast<float*>(d_tables), d_out, L, log2_T, F, resolutions_host,
+                               nullptr, stream, "nerf_hashgrid_backward_rays_ex_lw", rays, z, n, 0, pos_scale, pos_offset,
+                               level_lo, level_hi, fixed_point != 0, level_weights_host);
 }

@@ -31,6 +31,18 @@ __device__ __forceinline__ void sh_eval(float x, float y, float z, int deg, floa
   }
 }
 struct ResTab { float res[32]; };
+// per-level weights of the `_lw` entries (include/nerf_hip.h, "level weights"): feature = w[l] * interpolation (one float32
+// multiply), table-gradient addends from g = w[l] * d_out; a level with w[l] == 0 is neither gathered from nor scattered into
+struct LevelTab { float w[32]; };
+// host side of every `_lw` entry: copies the caller's weights (finite, in [0, 1]) into the kernel argument
+static inline bool level_tab_fill(LevelTab& lt, const float* w_host, int L) {
+  for (int l = 0; l < 32; ++l) {
+    const float w = l < L ? w_host[l] : 0.0f;
+    if (!(w >= 0.0f && w <= 1.0f)) return false;          // NaN fails both comparisons
+    lt.w[l] = w + 0.0f;                                   // -0 counts as 0
+  }
+  return true;
+}
 
 // fixed-point unit of the deterministic table-gradient accumulators (int64): 2^-52
 #define NERF_HASH_FIX_SHIFT 52
@@ -161,6 +173,26 @@ __device__ __forceinline__ FeatVec<F> trilerp(const FeatVec<F> (&e)[8], const Co
     const float h4756 = h47 * oy + h56 * (1 - oy);
     r.v[f] = h0312 * oz + h4756 * (1 - oz);
   }
+  return r;
+}
+
+// the fused queries' weighted level (F = 2): w * interpolation under a per-lane predicate -- a lane's half selects its levels,
+// so w differs within a wave.  Lanes with w == 0 issue no load and return +0.  The select on the result is not redundant: the
+// offsets of a NaN / Inf position are NaN, so even all-zero entries interpolate to NaN there, and a masked level is +0 always.
+template <bool HALF>
+__device__ __forceinline__ FeatVec<2> hash_level_lw(const float* __restrict__ tb, const uint32_t* __restrict__ tbh, const Corners& c,
+                                                    float w) {
+  const bool on = w != 0.0f;
+  FeatVec<2> e[8];
+#pragma unroll
+  for (int k = 0; k < 8; ++k) { e[k].v[0] = 0.0f; e[k].v[1] = 0.0f; }
+  if (on) {
+#pragma unroll
+    for (int k = 0; k < 8; ++k) e[k] = HALF ? load_entry_h(tbh, c.i[k]) : load_entry<2>(tb, c.i[k]);
+  }
+  FeatVec<2> r = trilerp<2>(e, c);
+  r.v[0] = on ? w * r.v[0] : 0.0f;
+  r.v[1] = on ? w * r.v[1] : 0.0f;
   return r;
 }
 

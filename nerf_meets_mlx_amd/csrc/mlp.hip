@@ -1361,12 +1361,16 @@ struct SmallArgs {
   // the 32 lanes of a gather instruction fall into the same or adjacent cells at every level below N_l ~ 800 (13 of 16),
   // where 32 consecutive depths of one ray (0.021 apart) share cells only below N_l ~ 48.  Same values per sample.
   int ray_major; int64_t B;
+  // per-level weights of nerf_ngp_query_fused_lw, read by the LW kernels only (last member: the other kernels' argument
+  // offsets are what they were)
+  LevelTab lw;
 };
 
 // B fragments of one sample straight from the hash tables and the view direction: lane (r, h) owns channels
 // kperm(ks, h, j) of k-step ks = levels 8 ks + 4 (j >> 2) + 2 h + ((j & 3) >> 1), feature j & 1, i.e. the two lanes of
 // a sample split the 16 levels between them; SH degree 3 = 16 channels = one k-step.
-template <bool HALF>
+// LW: feature = w[l] * interpolation in float32, ahead of the bf16 rounding; w[l] == 0: no gather, feature +0.
+template <bool HALF, bool LW>
 __device__ __forceinline__ void ngp_row_frags(const SmallArgs& a, int64_t m, int h, bf16x8 (&xin)[1][2], bf16x8 (&din)[1][1]) {
   const float* rr = a.rays + (int64_t)((uint64_t)m / (unsigned)a.n) * NERF_RAY_STRIDE;
   const float zv = a.z[m];
@@ -1382,9 +1386,16 @@ __device__ __forceinline__ void ngp_row_frags(const SmallArgs& a, int64_t m, int
       for (int e = 0; e < 2; ++e) {
         const int l = 8 * ks + 4 * q + 2 * h + e;
         const Corners c = corners_of(px, py, pz, a.rt.res[l], mask);
-        const FeatVec<2> fv = HALF ? hash_level_h(a.tables_h + (size_t)l * a.T, c) : hash_level<2>(a.tables + (size_t)l * a.T * 2, c);
-        xin[0][ks][4 * q + 2 * e] = (__bf16)fv.v[0];
-        xin[0][ks][4 * q + 2 * e + 1] = (__bf16)fv.v[1];
+        if (LW) {
+          const float w = h ? a.lw.w[8 * ks + 4 * q + 2 + e] : a.lw.w[8 * ks + 4 * q + e];       // two scalars and a select
+          const FeatVec<2> fv = hash_level_lw<HALF>(a.tables + (size_t)l * a.T * 2, a.tables_h + (size_t)l * a.T, c, w);
+          xin[0][ks][4 * q + 2 * e] = (__bf16)fv.v[0];
+          xin[0][ks][4 * q + 2 * e + 1] = (__bf16)fv.v[1];
+        } else {
+          const FeatVec<2> fv = HALF ? hash_level_h(a.tables_h + (size_t)l * a.T, c) : hash_level<2>(a.tables + (size_t)l * a.T * 2, c);
+          xin[0][ks][4 * q + 2 * e] = (__bf16)fv.v[0];
+          xin[0][ks][4 * q + 2 * e + 1] = (__bf16)fv.v[1];
+        }
       }
   float sh[16];
   sh_eval(rr[8], rr[9], rr[10], 3, sh);
@@ -1392,7 +1403,7 @@ __device__ __forceinline__ void ngp_row_frags(const SmallArgs& a, int64_t m, int
   for (int j = 0; j < 8; ++j) din[0][0][j] = (__bf16)(h == 0 ? sh[8 * (j >> 2) + (j & 3)] : sh[8 * (j >> 2) + 4 + (j & 3)]);
 }
 
-template <bool STORE, bool FUSED>
+template <bool STORE, bool FUSED, bool LW = false>
 __global__ void __launch_bounds__(512) mlp_small_fwd_kernel(SmallArgs a) {
   constexpr int ST = 1;
   lds_load_stream(a.wf, a.bias);
@@ -1417,8 +1428,8 @@ __global__ void __launch_bounds__(512) mlp_small_fwd_kernel(SmallArgs a) {
     if (m >= a.M) m = a.M - 1;
     bf16x8 xin[ST][2], din[ST][1];
     if (FUSED) {
-      if (a.tables_h) ngp_row_frags<true>(a, m, h, xin, din);        // wave-uniform
-      else ngp_row_frags<false>(a, m, h, xin, din);
+      if (a.tables_h) ngp_row_frags<true, LW>(a, m, h, xin, din);        // wave-uniform
+      else ngp_row_frags<false, LW>(a, m, h, xin, din);
     } else {
       const float* row = a.x + m * LN::CIN;
       xin[0][0] = row_frag(row, 0, h, LN::CPOS); xin[0][1] = row_frag(row, 1, h, LN::CPOS);
@@ -1831,6 +1842,7 @@ static void small_args(SmallArgs& a, const void* packed) {
   a.astride = small_astride16(); a.zstride = small_zstride16();
   a.rays = nullptr; a.z = nullptr; a.n = 1; a.tables = nullptr; a.tables_h = nullptr; a.T = 0; a.pos_scale = 1.0f; a.pos_offset = 0.0f;
   a.ray_major = 0; a.B = 0;
+  for (int l = 0; l < 32; ++l) a.lw.w[l] = 1.0f;
 }
 
 extern "C" int nerf_mlp_forward_train(const nerf_mlp_arch* arch, const void* packed, const float* x, int64_t M,
@@ -2154,10 +2166,11 @@ static int mlp_backward_impl(const nerf_mlp_arch* arch, const void* packed, cons
   return launch_dw(d, nj, ntiles, L::P_TOTAL, acts, dz, astr, zstr, grads, s, split, s16::A_LO, s16::Z_LO);
 }
 
-extern "C" int nerf_ngp_query_fused_h(const nerf_mlp_arch* arch, const void* packed, const float* rays, const float* z,
-                                      int64_t B, int n, const float* tables, const void* tables_half, int L, int log2_T, int F,
-                                      const int* resolutions_host, int sh_degree, float pos_scale, float pos_offset,
-                                      float* raw, void* acts, void* stream) {
+// lw_host: the level weights of nerf_ngp_query_fused_lw; NULL = the kernels without them
+static int ngp_query_fused_impl(const nerf_mlp_arch* arch, const void* packed, const float* rays, const float* z,
+                                int64_t B, int n, const float* tables, const void* tables_half, int L, int log2_T, int F,
+                                const int* resolutions_host, const float* lw_host, int sh_degree, float pos_scale,
+                                float pos_offset, float* raw, void* acts, void* stream) {
   NERF_REQUIRE(arch_kind(arch) == 2, NERF_E_UNSUPPORTED, "nerf_ngp_query_fused: needs the (2x64, in 32+16) model");
   NERF_REQUIRE(L == 16 && F == 2 && sh_degree == 3, NERF_E_UNSUPPORTED,
                "nerf_ngp_query_fused: fused rows exist for 16 levels x 2 features + SH degree 3 (use nerf_ngp_encode + nerf_mlp_forward otherwise)");
@@ -2171,6 +2184,12 @@ extern "C" int nerf_ngp_query_fused_h(const nerf_mlp_arch* arch, const void* pac
     q.rays = rays; q.z = z; q.n = n; q.tables = tables; q.T = 1u << log2_T; q.pos_scale = pos_scale; q.pos_offset = pos_offset;
     for (int l = 0; l < 32; ++l) q.res[l] = l < L ? (float)resolutions_host[l] : 0.0f;
     q.B = B; q.ray_major = g_ngp_ray_major;
+    q.use_lw = lw_host != nullptr;
+    if (lw_host) {
+      LevelTab lt;
+      NERF_REQUIRE(level_tab_fill(lt, lw_host, L), NERF_E_SHAPE, "nerf_ngp_query_fused_lw: level weights must be finite and in [0, 1]");
+      for (int l = 0; l < 32; ++l) q.lw[l] = lt.w[l];
+    }
     return s16x::small_forward(static_cast<const char*>(packed) + LN::PACKED_BYTES, small_bias_of(packed), nullptr, M, raw, acts,
                                small_astride16(true), &q, as_stream(stream));
   }
@@ -2184,9 +2203,31 @@ extern "C" int nerf_ngp_query_fused_h(const nerf_mlp_arch* arch, const void* pac
   a.ray_major = (!acts && g_ngp_ray_major && B >= 32) ? 1 : 0;
   const int64_t nwg = ((a.ray_major ? ((B + 31) / 32) * (int64_t)n : (M + 31) / 32) + 7) / 8;
   const dim3 g((unsigned)(nwg < 2048 ? nwg : 2048)), b(512);
+  if (lw_host) {
+    NERF_REQUIRE(level_tab_fill(a.lw, lw_host, L), NERF_E_SHAPE, "nerf_ngp_query_fused_lw: level weights must be finite and in [0, 1]");
+    if (acts) hipLaunchKernelGGL((mlp_small_fwd_kernel<true, true, true>), g, b, LN::LDS_BYTES, as_stream(stream), a);
+    else hipLaunchKernelGGL((mlp_small_fwd_kernel<false, true, true>), g, b, LN::LDS_BYTES, as_stream(stream), a);
+    return check_launch("nerf_ngp_query_fused_lw");
+  }
   if (acts) hipLaunchKernelGGL((mlp_small_fwd_kernel<true, true>), g, b, LN::LDS_BYTES, as_stream(stream), a);
   else hipLaunchKernelGGL((mlp_small_fwd_kernel<false, true>), g, b, LN::LDS_BYTES, as_stream(stream), a);
   return check_launch("nerf_ngp_query_fused");
+}
+
+extern "C" int nerf_ngp_query_fused_h(const nerf_mlp_arch* arch, const void* packed, const float* rays, const float* z,
+                                      int64_t B, int n, const float* tables, const void* tables_half, int L, int log2_T, int F,
+                                      const int* resolutions_host, int sh_degree, float pos_scale, float pos_offset,
+                                      float* raw, void* acts, void* stream) {
+  return ngp_query_fused_impl(arch, packed, rays, z, B, n, tables, tables_half, L, log2_T, F, resolutions_host, nullptr, sh_degree,
+                              pos_scale, pos_offset, raw, acts, stream);
+}
+
+extern "C" int nerf_ngp_query_fused_lw(const nerf_mlp_arch* arch, const void* packed, const float* rays, const float* z,
+                                       int64_t B, int n, const float* tables, const void* tables_half, int L, int log2_T, int F,
+                                       const int* resolutions_host, const float* level_weights_host, int sh_degree,
+                                       float pos_scale, float pos_offset, float* raw, void* acts, void* stream) {
+  return ngp_query_fused_impl(arch, packed, rays, z, B, n, tables, tables_half, L, log2_T, F, resolutions_host, level_weights_host,
+                              sh_degree, pos_scale, pos_offset, raw, acts, stream);
 }
 
 extern "C" int nerf_ngp_query_fused(const nerf_mlp_arch* arch, const void* packed, const float* rays, const float* z,

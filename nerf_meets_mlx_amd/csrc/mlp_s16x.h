@@ -42,6 +42,7 @@ constexpr int64_t SM_PACKED_BYTES = (int64_t)(SM_F_FRAGS + SM_B_FRAGS) * 1024;
 struct SmallQuery {
   const float* rays; const float* z; int n; const float* tables; uint32_t T; float res[32]; float pos_scale, pos_offset;
   int ray_major; int64_t B;
+  int use_lw; float lw[32];     // nerf_ngp_query_fused_lw: per-level weights (validated by the caller); use_lw == 0: none
 };
 int small_pack(const float* params, void* packed, hipStream_t s);
 int small_forward(const void* packed, const float* bias_slots, const float* x, int64_t M, float* out, void* acts,

@@ -112,6 +112,18 @@ class HashNeRF:
         self._sel = None                    # culled training query: (kept sample indices [K], B, n); None: every sample ran
         self.fused = os.environ.get("NERF_NGP_FUSED", "1") != "0"      # rows inside the forward kernel (default) or through HBM
         self.timing = None                  # bench.py: list that receives (start, end) events around the table scatter
+        self._bwd_lw = None                 # level weights captured by the last query(train=True): backward() uses these
+
+    @property
+    def level_weights(self):
+        """Per-level weights of the hash encoding (a tuple of n_levels numbers in [0, 1]) or None, the default: every path then
+        calls exactly what it calls without the option.  features, features_unfused, query (fused, unfused, culled, packed) and
+        backward use them; backward uses the weights captured by the last query(train=True), not the current property."""
+        return self.enc.level_weights
+
+    @level_weights.setter
+    def level_weights(self, w):
+        self.enc.level_weights = w
 
     def features(self, rays: torch.Tensor, z: torch.Tensor, need_pts: bool = True):
         """x [B n, 48] = [MultiHashEncoding(o + z d) | SphericalHarmonicsEncoding(viewdirs)] in one call
@@ -120,6 +132,11 @@ class HashNeRF:
         e = self.enc
         x = torch.empty(B * n, 48, dtype=torch.float32, device=z.device)
         pts = torch.empty(B * n, 3, dtype=torch.float32, device=z.device) if need_pts else None
+        if e._lw_c is not None:
+            N.check(N.lib().nerf_ngp_encode_lw(N.ptr(N.f32(rays)), N.ptr(N.f32(z)), B, n, N.ptr(e.tables), e.n_levels,
+                                               e.log2_hashmap_size, e.n_features_per_level, e._res_c, e._lw_c, 3, self.pos_scale,
+                                               self.pos_offset, N.ptr(x), N.ptr(pts), N.stream()))
+            return pts, x
         N.check(N.lib().nerf_ngp_encode(N.ptr(N.f32(rays)), N.ptr(N.f32(z)), B, n, N.ptr(e.tables), e.n_levels,
                                         e.log2_hashmap_size, e.n_features_per_level, e._res_c, 3, self.pos_scale,
                                         self.pos_offset, N.ptr(x), N.ptr(pts), N.stream()))
@@ -152,6 +169,7 @@ class HashNeRF:
             return self._query_culled(rays, z, train, grid)
         if train:
             self._sel = None
+            self._bwd_lw = self.enc._lw_c
         if not fused:
             pts, x = self.features(rays, z, need_pts=train)
             self._pts, self._rz = (pts if train else None), None
@@ -163,6 +181,12 @@ class HashNeRF:
         if train:
             acts = m._begin_train_pass(B * n)
             self._pts, self._rz = None, (rays, z)
+        if e._lw_c is not None:
+            N.check(N.lib().nerf_ngp_query_fused_lw(C.byref(m.arch), N.ptr(m.packed()), N.ptr(rays), N.ptr(z), B, n,
+                                                    N.ptr(e.tables), N.ptr(self.table.shadow()), e.n_levels, e.log2_hashmap_size,
+                                                    e.n_features_per_level, e._res_c, e._lw_c, 3, self.pos_scale,
+                                                    self.pos_offset, N.ptr(raw), N.ptr(acts), N.stream()))
+            return raw
         N.check(N.lib().nerf_ngp_query_fused_h(C.byref(m.arch), N.ptr(m.packed()), N.ptr(rays), N.ptr(z), B, n,
                                                N.ptr(e.tables), N.ptr(self.table.shadow()), e.n_levels, e.log2_hashmap_size,
                                                e.n_features_per_level, e._res_c, 3, self.pos_scale, self.pos_offset,
@@ -184,6 +208,7 @@ class HashNeRF:
                 grid.timing.append(("scatter", e0, e1))
         elif train:
             self._rz, self._pts = None, None
+            self._bwd_lw = self.enc._lw_c
         if train:
             self._sel = (idx, B, n)
         return raw
@@ -198,6 +223,7 @@ class HashNeRF:
         if train:
             self._sel = (torch.empty(0, dtype=torch.int64, device=rows.device), 0, 1)
             self._rz, self._pts = None, None
+            self._bwd_lw = self.enc._lw_c
         return torch.empty(0, 1, 4, dtype=torch.float32, device=rows.device)
 
     def table_grad(self) -> torch.Tensor:
@@ -235,22 +261,63 @@ class HashNeRF:
                 if self.on_group_done is not None:
                     self.on_group_done(lo, hi)
         elif self._rz is None:                               # unfused rows: positions were kept by features()
-            e.backward(self._pts, d_x)
+            e.backward(self._pts, d_x, level_weights=self._bwd_lw)
             if self.on_group_done is not None:
                 self.on_group_done(0, e.n_levels)
         else:
             rays, z = self._rz
             for lo, hi in self.level_groups:
-                N.check(N.lib().nerf_hashgrid_backward_rays_ex(
-                    N.ptr(rays), N.ptr(z), z.shape[0], z.shape[1], N.ptr(d_x), e.n_levels, e.log2_hashmap_size,
-                    e.n_features_per_level, e._res_c, self.pos_scale, self.pos_offset, lo, hi, int(self.deterministic),
-                    N.ptr(e.grad), N.stream()))
+                if self._bwd_lw is not None:             # the weights of the forward pass this is the gradient of
+                    N.check(N.lib().nerf_hashgrid_backward_rays_ex_lw(
+                        N.ptr(rays), N.ptr(z), z.shape[0], z.shape[1], N.ptr(d_x), e.n_levels, e.log2_hashmap_size,
+                        e.n_features_per_level, e._res_c, self._bwd_lw, self.pos_scale, self.pos_offset, lo, hi,
+                        int(self.deterministic), N.ptr(e.grad), N.stream()))
+                else:
+                    N.check(N.lib().nerf_hashgrid_backward_rays_ex(
+                        N.ptr(rays), N.ptr(z), z.shape[0], z.shape[1], N.ptr(d_x), e.n_levels, e.log2_hashmap_size,
+                        e.n_features_per_level, e._res_c, self.pos_scale, self.pos_offset, lo, hi, int(self.deterministic),
+                        N.ptr(e.grad), N.stream()))
                 if self.on_group_done is not None:
                     self.on_group_done(lo, hi)
         if self.timing is not None:
             e1.record()
             self.timing.append((e0, e1))
         return grads, e.grad
+
+
+def check_level_anneal(level_anneal, n_levels: int):
+    """None or (start_levels, iters): integers with 1 <= start_levels <= n_levels and iters >= 1, else ValueError."""
+    if level_anneal is None:
+        return None
+    try:
+        start, iters = level_anneal
+    except (TypeError, ValueError):
+        raise ValueError(f"level_anneal must be None or (start_levels, iters), got {level_anneal!r}") from None
+    for name, v in (("start_levels", start), ("iters", iters)):
+        if isinstance(v, bool) or not isinstance(v, int):
+            raise ValueError(f"level_anneal: {name} must be an integer, got {v!r}")
+    if not 1 <= start <= n_levels:
+        raise ValueError(f"level_anneal: need 1 <= start_levels <= {n_levels}, got {start}")
+    if iters < 1:
+        raise ValueError(f"level_anneal: need iters >= 1, got {iters}")
+    return int(start), int(iters)
+
+
+def level_anneal_from_text(text: str):
+    """'START,ITERS' (the --level-anneal flag of the tools) -> (start_levels, iters); ValueError for anything else."""
+    try:
+        start, iters = (int(v) for v in text.split(","))
+    except (AttributeError, ValueError):
+        raise ValueError(f"level_anneal: need START,ITERS (two integers), got {text!r}") from None
+    return start, iters
+
+
+def level_anneal_weights(start_levels: int, iters: int, n_levels: int, it: int):
+    """w_l = min(1, max(0, alpha - l)), alpha = start_levels + (L - start_levels) min(1, it / iters), in double on the host,
+    rounded to float32 (returned as Python floats)."""
+    import numpy as np
+    alpha = float(start_levels) + float(n_levels - start_levels) * min(1.0, float(it) / float(iters))
+    return tuple(float(np.float32(min(1.0, max(0.0, alpha - l)))) for l in range(n_levels))
 
 
 def _cat(outs, aux: bool):
@@ -268,7 +335,7 @@ class NGPTrainer(Trainer):
                  n_depth_samples: int = 64, lrate: float = 5e-4, lrate_decay: int = 500, white_bkgd: bool = True,
                  seed: int = 0, device="cuda", chunk: int = 1024 * 32, table_sync: str = "shard", precision: int = 22,
                  occupancy_grid: bool = False, march_steps: Optional[int] = None, min_transmittance: Optional[float] = None,
-                 distortion_weight: Optional[float] = None, random_background: bool = False, **hash_kw):
+                 distortion_weight: Optional[float] = None, random_background: bool = False, level_anneal=None, **hash_kw):
         """occupancy_grid: empty-space skipping (engine/occupancy.py): the grid is updated every UPDATE_EVERY iterations from the
         start; from iteration WARMUP on, training and rendering evaluate only the samples in occupied cells.  Off by default.
         march_steps (needs occupancy_grid=True and a scene box; 1 ... 1024; None: the n_depth_samples stratified grid): the
@@ -278,7 +345,16 @@ class NGPTrainer(Trainer):
         random_background (needs march_steps and images [N, H, W, 4], straight RGBA in [0, 1] as load_blender_data returns them;
         DESIGN.md section 16): every training ray gets a colour bg uniform in [0, 1)^3 (counter stream 5), the target is
         rgb_gt a_gt + bg (1 - a_gt) and the rendered ray sum w c + (1 - acc) bg, so that opacity is supervised.  A constructor
-        setting like distortion_weight: not checkpointed.  Off by default."""
+        setting like distortion_weight: not checkpointed.  Off by default.
+        level_anneal = (start_levels, iters) (any mode, any precision): a coarse-to-fine schedule over the
+        hash levels.  At iteration `it` level l has the weight w_l = clamp(alpha - l, 0, 1) with alpha = start_levels +
+        (L - start_levels) min(1, it / iters) (`level_weights_at`): train_step sets the field's level_weights from self.it
+        before the forward pass, rendering uses the weights of the current `it`, and from it >= iters on the weights are None
+        again (the kernels without the option).  While it is set the trainer owns field.level_weights and overwrites a value
+        assigned by hand.  A constructor setting, not checkpointed: after load the weights follow from the restored `it`.  Off
+        by default."""
+        self._n_levels = int(hash_kw.get("n_levels", 16))
+        self.level_anneal = check_level_anneal(level_anneal, self._n_levels)
         if march_steps is not None:
             from .occupancy import check_march_steps
             check_march_steps(march_steps)
@@ -316,6 +392,7 @@ class NGPTrainer(Trainer):
         self.coarse = None                                   # the 8 x 256 network of the base class is not used
         self._field = HashNeRF(device=self.device, seed=seed, precision=precision, **hash_kw)
         self._field.mlp.name = "mlp"
+        self._apply_level_weights()
         self.grid = None
         self.last_march = None               # march mode: (rays, kept samples) of the last training march
         if occupancy_grid:
@@ -358,6 +435,21 @@ class NGPTrainer(Trainer):
     def field(self, f):
         self._field = f
 
+    def level_weights_at(self, it: int):
+        """The level weights at iteration `it`: None without level_anneal and from it >= iters on (every weight is exactly 1
+        then), else a tuple of n_levels float32-rounded numbers (`level_anneal_weights`)."""
+        if self.level_anneal is None or it >= self.level_anneal[1]:
+            return None
+        return level_anneal_weights(self.level_anneal[0], self.level_anneal[1], self._n_levels, it)
+
+    def _apply_level_weights(self):
+        """Sets the field's weights from self.it (identical on every rank: they depend on `it` only).  Called wherever `it`
+        changes -- the constructor, the end of train_step, load_state_dict -- so rendering, the distortion loss and mesh export
+        find the field current, and once more at the top of train_step, which DESIGN.md section 19 promises.  With level_anneal
+        set the trainer owns the field's level_weights: a value assigned to field.level_weights by hand is overwritten here."""
+        if self.level_anneal is not None:
+            self._field.level_weights = self.level_weights_at(self.it)
+
     def _mesh_field(self):
         """The hash-grid field through `field` (joins the comm stream); exp density in march mode, relu otherwise."""
         from .mesh import EXP, RELU
@@ -380,6 +472,7 @@ class NGPTrainer(Trainer):
             raise ValueError("NGPTrainer.train_step: background needs a trainer built with random_background=True")
         if rays is None:
             rays, target = self.sample_batch()
+        self._apply_level_weights()
         self._opt.learning_rate = self.lrate * (0.1 ** (self.it / (self.lrate_decay * 1000)))
         if self.march_steps is not None:
             self._join_comm()
@@ -460,6 +553,7 @@ class NGPTrainer(Trainer):
             self._opt.update(self._field.table, g_tab.view(-1), grad_scale=1.0 / self.world, zero_grads=True)    # reads g, writes 0
         self._field._grad_clean = True
         self.it += 1
+        self._apply_level_weights()                          # rendering sees the weights of the current iteration
         if self.distortion_weight is not None:
             return {"loss_coarse": loss, "loss_distortion": dist}
         return {"loss_coarse": loss}
@@ -588,6 +682,7 @@ class NGPTrainer(Trainer):
         self._join_comm()
         super().load_state_dict(sd, allow_legacy_rng=allow_legacy_rng)
         self._moments_synced = True
+        self._apply_level_weights()                     # not checkpointed: the weights follow from the restored `it`
         if self.grid is not None:
             self.grid.seed = int(self.seed)             # the update stream follows the adopted run's seed, like the ray streams
             occ = {k[len("occupancy/"):]: v for k, v in sd.get("extra", {}).items() if k.startswith("occupancy/")}

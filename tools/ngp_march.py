@@ -6,21 +6,24 @@ N_rand 4096, seed 4, one 32 768-ray render chunk per step), in ONE process:
 
 Arms: "off" (64 stratified samples, no grid), "cull" (64 samples, grid cull) and "march<S>" (the march of
 section 12 with march_steps = S; default 1024 and 512), and "march<S>_ert" (the same march with early ray termination at
-min_transmittance --eps, section 13; trained exactly as "march<S>"), "march<S>_rbg" / "march<S>_dist_rbg" (the march trained on the
-RGBA frames over a random background per ray, section 16), and "march<S>_dist" (the march trained with the distortion
-regulariser of section 15 at --dist-weight).  Every arm is trained past the grid's warm-up, then the arms alternate
-timed blocks of --block steps until --iters; each step is timed with device events (train step, render chunk).  Per arm: train
-ms / step, render ms / chunk, samples per ray in training and rendering, for march arms the device time of the march (count +
-scan + write) and the host time of the K read-back; after --iters the held-out PSNR on a fifth view, next to the PSNR of an
-all-white frame of that view.  Early-termination arms also report the ms per full held-out frame at the render chunk and at
-one whole-frame chunk, samples per ray, rounds and host-read ms per call, and the max |d| per pixel against the same trainer's
-one-shot render.  One-shot march arms also report, over the held-out frame, the mean distortion loss L_b, the mean acc and the
-samples per ray without and with termination at --eps.  One JSON line per arm and a summary line.
+min_transmittance --eps, section 13; trained exactly as "march<S>"), "march<S>_rbg" / "march<S>_dist_rbg" (the march trained on
+the RGBA frames over a random background per ray, section 16), and "march<S>_dist" (the march trained with the distortion
+regulariser of section 15 at --dist-weight); a "_c2f" behind the step count ("march<S>_c2f", "march<S>_c2f_dist_bg"; "_bg" is
+"_rbg") trains with the coarse-to-fine level schedule of section 19 at --level-anneal START,ITERS.  Every arm is trained past
+the grid's warm-up, then the arms alternate timed blocks of --block steps until --iters; each step is timed with device events
+(train step, render chunk).  Per arm: train ms / step, render ms / chunk, samples per ray in training and rendering (the train
+figures also over iterations 0 ... 255, the grid's warm-up, where the arms do not alternate, and over 1000 ... 1999, each as
+mean and median), for march arms the device time of the march (count + scan + write) and the host time of the K read-back; after
+--iters the held-out PSNR on a fifth view, next to the PSNR of an all-white frame of that view.  Early-termination arms also
+report the ms per full held-out frame at the render chunk and at one whole-frame chunk, samples per ray, rounds and host-read ms
+per call, and the max |d| per pixel against the same trainer's one-shot render.  One-shot march arms also report, over the
+held-out frame, the mean distortion loss L_b, the mean acc and the samples per ray without and with termination at --eps.  One
+JSON line per arm and a summary line.
 
     python tools/ngp_march.py --stats <rocprofv3 results .db>
 
-prints the average time per launch of the march and packed-compositing kernels from a `rocprofv3 --kernel-trace` run of this tool
-(e.g. with --iters 400 --no-psnr)."""
+prints the launches, the average time per launch and the total time of the march, packed-compositing, fused-query and table
+scatter kernels, per instantiation, from a `rocprofv3 --kernel-trace` run of this tool (e.g. with --iters 400 --no-psnr)."""
 import argparse
 import json
 import os
@@ -115,6 +118,8 @@ def main():
     ap.add_argument("--eps", type=float, default=1e-4, help="min_transmittance of the *_ert arms")
     ap.add_argument("--dist-weight", type=float, default=1e-2,
                     help="distortion_weight of the *_dist arms (mip-NeRF 360 publishes 0.01)")
+    ap.add_argument("--level-anneal", default="4,1000", metavar="START,ITERS",
+                    help="level_anneal of the *_c2f arms: coarse-to-fine schedule over the hash levels (DESIGN.md section 19)")
     ap.add_argument("--frame-reps", type=int, default=5, help="timed full-frame renders per chunk size (ert arms)")
     ap.add_argument("--out", default=None, help="append the JSON lines to this file")
     ap.add_argument("--stats", default=None, help="summarise a rocprofv3 --kernel-trace results database instead of measuring")
@@ -122,7 +127,7 @@ def main():
     if a.stats:
         return stats(a)
     from nerf_meets_mlx_amd.dataset import synthetic
-    from nerf_meets_mlx_amd.engine.ngp import NGPTrainer
+    from nerf_meets_mlx_amd.engine.ngp import NGPTrainer, level_anneal_from_text
     from nerf_meets_mlx_amd.engine.occupancy import UPDATE_EVERY, WARMUP
     from nerf_meets_mlx_amd.rendering import ray
 
@@ -131,19 +136,19 @@ def main():
     H = W = a.hw
     imgs, poses, rposes, hwf, K = synthetic.make_dataset(H, W, 5, seed=0, device=dev)
     rrays = ray.gen_rays(H, W, K, rposes[40][:3, :4], 2.0, 6.0, torch.arange(a.render_rays, device=dev, dtype=torch.int64))
-    arms, imgs_rgba = {}, None
+    arms, imgs_rgba, anneal = {}, None, level_anneal_from_text(a.level_anneal)
     for name in a.arms.split(","):
-        m = re.fullmatch(r"march(\d+)(_dist)?(_rbg)?(_ert)?", name)
+        m = re.fullmatch(r"march(\d+)(_c2f)?(_dist)?(_rbg|_bg)?(_ert)?", name)
         if m is None and name not in ("off", "cull"):
             ap.error(f"unknown arm {name!r}")
-        steps, dist, rbg, ert = (int(m.group(1)), *(m.group(i) is not None for i in (2, 3, 4))) if m else (None, False, False, False)
+        steps, c2f, dist, rbg, ert = (int(m.group(1)), *(m.group(i) is not None for i in (2, 3, 4, 5))) if m else (None, False, False, False, False)
         if rbg and imgs_rgba is None:                       # the same frames as straight RGBA
             imgs_rgba = synthetic.make_dataset(H, W, 5, seed=0, device=dev, rgba=True)[0]
         tr = NGPTrainer((imgs_rgba if rbg else imgs)[:4], poses[:4], K, N_rand=a.n_rand, n_depth_samples=64, seed=4, device=dev,
                         chunk=a.render_rays, occupancy_grid=(name != "off"), march_steps=steps,
                         min_transmittance=a.eps if ert else None, distortion_weight=a.dist_weight if dist else None,
-                        random_background=rbg)
-        arms[name] = {"tr": tr, "train": [], "render": [], "spr_train": [], "spr_render": []}
+                        random_background=rbg, level_anneal=anneal if c2f else None)
+        arms[name] = {"tr": tr, "train": [], "render": [], "spr_train": [], "spr_render": [], "by_it": []}
 
     def step(arm, timed):
         tr = arm["tr"]
@@ -151,6 +156,9 @@ def main():
         e[0].record()
         tr.train_step()
         e[1].record()
+        # every step, the warm-up included: (iteration, events, samples per ray) for the windows reported below
+        spr = tr.last_march[1] / float(a.n_rand) if tr.march_steps is not None else None
+        arm["by_it"].append((tr.it - 1, e[0], e[1], spr))
         if timed and tr.march_steps is not None:
             arm["spr_train"].append(tr.last_march[1] / float(a.n_rand))
         elif timed and tr.grid is not None:
@@ -190,7 +198,15 @@ def main():
                 "render_ms_per_chunk_p10_p90": _p10_p90(arm["render"]), "min_transmittance": tr.min_transmittance,
                 "distortion_weight": getattr(tr, "distortion_weight", None),
                 "random_background": bool(getattr(tr, "random_background", False)),
+                "level_anneal": getattr(tr, "level_anneal", None),
                 "device": torch.cuda.get_device_name(dev)}
+        for tag, lo, hi in (("first_256", 0, 256), ("1000_2000", 1000, 2000)):     # first_256 holds the set-up cost of step 0
+            win = [t for t in arm["by_it"] if lo <= t[0] < hi]
+            ms = [x.elapsed_time(y) for _, x, y, _ in win]
+            line[f"train_ms_per_step_{tag}"] = float(np.mean(ms)) if ms else None
+            line[f"train_ms_per_step_{tag}_median"] = float(np.median(ms)) if ms else None
+            spr = [t[3] for t in win if t[3] is not None]
+            line[f"samples_per_ray_train_{tag}"] = float(np.mean(spr)) if spr else None
         g = tr.grid
         if g is None:
             line.update({"samples_per_ray_train": 64.0, "samples_per_ray_render": 64.0})
@@ -251,15 +267,17 @@ def main():
 
 
 def stats(a):
-    """Average device time per launch of the march / packed-compositing kernels in a rocprofv3 --kernel-trace database."""
+    """Launches, average device time per launch and total time of the march / packed-compositing / fused-query / scatter
+    kernels, per instantiation (the full name tells LW = true from false), in a rocprofv3 --kernel-trace database."""
     import re
     import sqlite3
     db = sqlite3.connect(a.stats)
-    for name, calls, avg_ns in db.execute("select name, count(*), avg(end - start) from kernels group by name"):
+    for name, calls, avg_ns in db.execute("select name, count(*), avg(end - start) from kernels group by name order by name"):
         m = re.search(r"(occ_march_\w+|ert_\w+|occ_cull_scan_kernel|occ_merge_exp_kernel|composite_packed_\w+(?:<[\w, ]+>)?|nerf_ngp\w*|ngp\w*fused\w*|"
-                      r"hashgrid\w*|composite_train_kernel|occ_cull_\w+)", name)
+                      r"hashgrid\w*|composite_train_kernel|occ_cull_\w+|mlp_small_fwd_kernel|s16_small_fwd_kernel)", name)
         if m:
-            print(json.dumps({"kernel": m.group(1), "calls": calls, "avg_us": round(avg_ns * 1e-3, 2)}))
+            print(json.dumps({"kernel": m.group(1), "name": name, "calls": calls, "avg_us": round(avg_ns * 1e-3, 2),
+                              "total_ms": round(calls * avg_ns * 1e-6, 3)}))
 
 
 if __name__ == "__main__":

@@ -183,6 +183,8 @@ def main():
                     help="train with the distortion regulariser at this weight (DESIGN.md section 15); default: without")
     ap.add_argument("--random-bg", action="store_true",
                     help="train on the RGBA frames over a random background per ray (DESIGN.md section 16); default: over white")
+    ap.add_argument("--level-anneal", default=None, metavar="START,ITERS",
+                    help="train with NGPTrainer(level_anneal=(START, ITERS)): coarse-to-fine hash levels (DESIGN.md section 19)")
     ap.add_argument("--res", default="128,256,512")
     ap.add_argument("--threshold", type=float, default=2.5)
     ap.add_argument("--reps", type=int, default=3)
@@ -205,7 +207,7 @@ def main():
         return stats(a)
     from nerf_meets_mlx_amd.dataset import synthetic
     from nerf_meets_mlx_amd.engine import mesh
-    from nerf_meets_mlx_amd.engine.ngp import NGPTrainer
+    from nerf_meets_mlx_amd.engine.ngp import NGPTrainer, level_anneal_from_text
 
     dev = torch.device("cuda", 0)
     torch.cuda.set_device(dev)
@@ -216,7 +218,8 @@ def main():
         imgs, poses, _, _, K = synthetic.make_dataset(H, W, 5, seed=0, device=dev, rgba=a.random_bg)
         imgs, poses = imgs[:4], poses[:4]
     tr = NGPTrainer(imgs, poses, K, N_rand=a.n_rand, n_depth_samples=64, seed=4, device=dev, occupancy_grid=True,
-                    march_steps=a.march_steps, distortion_weight=a.dist_weight, random_background=a.random_bg)
+                    march_steps=a.march_steps, distortion_weight=a.dist_weight, random_background=a.random_bg,
+                    level_anneal=level_anneal_from_text(a.level_anneal) if a.level_anneal else None)
     if a.ckpt:
         tr.load(a.ckpt)
     else:
@@ -233,7 +236,7 @@ def main():
     for R in [int(r) for r in a.res.split(",")]:
         rec = {"tool": "ngp_mesh", "R": R, "hw": a.hw, "iters": tr.it, "march_steps": a.march_steps, "seed": 4,
                "distortion_weight": a.dist_weight, "random_background": bool(a.random_bg),
-               "threshold": a.threshold, "activation": "exp", "device": torch.cuda.get_device_name(dev)}
+               "level_anneal": tr.level_anneal, "threshold": a.threshold, "activation": "exp", "device": torch.cuda.get_device_name(dev)}
         t_vol, t_mc, t_col = [], [], []
         for _ in range(a.reps):
             e = [torch.cuda.Event(enable_timing=True) for _ in range(4)]
