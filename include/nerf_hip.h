@@ -181,7 +181,8 @@ int nerf_hashgrid_backward_rays_ex(const float* rays, const float* z, int64_t B,
 /* Level weights (coarse-to-fine training of the hash grid: FreeNeRF's frequency mask, Neuralangelo's progressive levels).
  * The `_lw` entries take a per-level weight vector w[L]: float32, each finite and in [0, 1], a HOST array like
  * resolutions_host; NULL means all ones and runs exactly the kernels of the entry without the suffix.  A value outside
- * [0, 1] or a NaN is NERF_E_SHAPE.  Everything else is the argument list of the entry without the suffix.
+ * [0, 1] or a NaN is NERF_E_SHAPE.  Everything else is the argument list of the entry without the suffix.  Each entry
+ * without the suffix IS its `_lw` entry called with NULL weights, under its own name in nerf_last_error().
  *   forward         feature (l, f) = w[l] * interp_l,f: ONE float32 multiply after the interpolation above, before any
  *                   rounding to bf16 / fp16 fragments.  w[l] == 0: level l's tables are NOT READ and its features are
  *                   exactly +0, whatever the tables hold (NaN and Inf included).  w[l] == 1: bit-identical to the entry

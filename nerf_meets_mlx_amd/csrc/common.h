@@ -5,6 +5,7 @@
 #include <stdio.h>
 #include <stdarg.h>
 #include <mutex>
+#include <type_traits>
 #include <utility>
 
 #include "../../include/nerf_hip.h"
@@ -40,6 +41,10 @@ static inline int grid_for(int64_t work_items, int block, int max_blocks = 256 *
   if (g > max_blocks) g = max_blocks;
   return (int)g;
 }
+
+// A runtime bool as a template argument: fn receives std::true_type / std::false_type, and a generic lambda names the
+// kernel instantiation with decltype(arg)::value.  Nested calls list every combination once, in one place.
+template <class Fn> static inline void with_bool(bool b, Fn&& fn) { if (b) fn(std::true_type{}); else fn(std::false_type{}); }
 
 // ---- wave64 scans / reductions.  float: DPP (v_add_f32 ... row_shr / row_shl / row_bcast: the data path of the
 // VALU, no LDS crossbar round trip per step as with ds_bpermute shuffles); double: shuffles (the one double scan,

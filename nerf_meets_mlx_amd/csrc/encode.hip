@@ -3,7 +3,6 @@
 // reference's `Encoding` classes and for parity tests, and are HBM/L2-gather bound.
 #include "common.h"
 #include "hash_common.h"
-#include <type_traits>
 
 namespace nerf {
 
@@ -162,22 +161,11 @@ __global__ void __launch_bounds__(256) hashgrid_bwd_kernel(PointSrc ps, int64_t 
       const int l = l0 + li;
       if (l >= level_hi) break;
       if (LW && lw.w[l] == 0.0f) continue;
-      const float r = rt.res[l];
-      // same roundings as corners_of (hash_common.h): xs = p * r, floor / ceil, offset = xs - floor
-      const float xs = px * r, ys = py * r, zs = pz * r;
-      const float fx = floorf(xs), fy = floorf(ys), fz = floorf(zs);
-      const float ox = xs - fx, oy = ys - fy, oz = zs - fz;
-      const uint32_t cx = (uint32_t)(int32_t)(dx ? ceilf(xs) : fx);
-      const uint32_t yf = (uint32_t)(int32_t)fy * 2654435761u, yc = (uint32_t)(int32_t)ceilf(ys) * 2654435761u;
-      const uint32_t zf = (uint32_t)(int32_t)fz * 805459861u, zc = (uint32_t)(int32_t)ceilf(zs) * 805459861u;
       const size_t tb = (size_t)l * T * F + f;
       const float g = LW ? lw.w[l] * d_out[(m * L + l) * F + f] : d_out[(m * L + l) * F + f];
-      // products in the order of the per-corner form (g * wz * wy * wx), so every addend is bit-identical to it
-      const float wx = dx ? ox : 1 - ox;
-      add(tb + (size_t)((cx ^ yc ^ zc) & mask) * F, g * oz * oy * wx);
-      add(tb + (size_t)((cx ^ yf ^ zc) & mask) * F, g * oz * (1 - oy) * wx);
-      add(tb + (size_t)((cx ^ yc ^ zf) & mask) * F, g * (1 - oz) * oy * wx);
-      add(tb + (size_t)((cx ^ yf ^ zf) & mask) * F, g * (1 - oz) * (1 - oy) * wx);
+      const PlaneAddends a = plane_addends(px, py, pz, rt.res[l], mask, dx, g);
+#pragma unroll
+      for (int c = 0; c < 4; ++c) add(tb + (size_t)a.idx[c] * F, a.val[c]);
     }
   }
 }
@@ -229,16 +217,10 @@ __global__ void __launch_bounds__(256) hashgrid_bwd_combine_kernel(PointSrc ps, 
       const int q = tid % (2 * F), f = q % F, dx = q / F;
       float px, py, pz;
       point_of(ps, m, px, py, pz);
-      const float xs = px * r, ys = py * r, zs = pz * r;
-      const float fx = floorf(xs), fy = floorf(ys), fz = floorf(zs);
-      const float ox = xs - fx, oy = ys - fy, oz = zs - fz;
-      const uint32_t cx = (uint32_t)(int32_t)(dx ? ceilf(xs) : fx);
-      const uint32_t yf = (uint32_t)(int32_t)fy * 2654435761u, yc = (uint32_t)(int32_t)ceilf(ys) * 2654435761u;
-      const uint32_t zf = (uint32_t)(int32_t)fz * 805459861u, zc = (uint32_t)(int32_t)ceilf(zs) * 805459861u;
       const float g = LW ? lw.w[l] * d_out[(m * L + l) * F + f] : d_out[(m * L + l) * F + f];
-      const float wx = dx ? ox : 1 - ox;
-      const uint32_t idx[4] = {(cx ^ yc ^ zc) & mask, (cx ^ yf ^ zc) & mask, (cx ^ yc ^ zf) & mask, (cx ^ yf ^ zf) & mask};
-      const float val[4] = {g * oz * oy * wx, g * oz * (1 - oy) * wx, g * (1 - oz) * oy * wx, g * (1 - oz) * (1 - oy) * wx};
+      const PlaneAddends pa = plane_addends(px, py, pz, r, mask, dx, g);
+      const uint32_t (&idx)[4] = pa.idx;
+      const float (&val)[4] = pa.val;
 #pragma unroll
       for (int c = 0; c < 4; ++c) {
         uint32_t slot = (idx[c] * 2654435761u) >> 22;              // top 10 bits: HC_CAP = 1024
@@ -276,68 +258,151 @@ __global__ void __launch_bounds__(256) hashgrid_bwd_combine_kernel(PointSrc ps, 
   }
 }
 
-template <bool BWD>
-static int launch_hashgrid(const float* x, int64_t M, const float* tables, float* d_tables, const float* d_out, int L,
-                           int log2_T, int F, const int* res, float* out, void* stream, const char* who,
-                           const float* rays = nullptr, const float* z = nullptr, int n = 1, int64_t out_stride = 0,
-                           float pos_scale = 1.0f, float pos_offset = 0.0f, int level_lo = 0, int level_hi = -1,
-                           bool fixed = false, const float* lw_host = nullptr) {
-  NERF_REQUIRE((x || (rays && z)) && res, NERF_E_NULL, "%s: NULL pointer", who);
-  NERF_REQUIRE(L >= 1 && L <= 32 && log2_T >= 1 && log2_T <= 30, NERF_E_SHAPE, "%s: need 1<=L<=32, 1<=log2_T<=30", who);
-  NERF_REQUIRE(F == 1 || F == 2 || F == 4 || F == 8, NERF_E_UNSUPPORTED, "%s: F must be 1, 2, 4 or 8", who);
-  if (M <= 0) return NERF_OK;
-  ResTab rt;
-  for (int l = 0; l < L; ++l) rt.res[l] = (float)res[l];
-  const uint32_t T = 1u << log2_T;
-  constexpr int LG = 4;                                   // levels per thread: LG x F contiguous floats per sample
-  if (level_hi < 0) level_hi = L;
-  NERF_REQUIRE(0 <= level_lo && level_lo <= level_hi && level_hi <= L, NERF_E_SHAPE, "%s: need 0 <= level_lo <= level_hi <= L", who);
-  if (level_lo == level_hi) return NERF_OK;
-  // level weights (`_lw` entries; NULL = all ones = the kernels without them)
-  LevelTab lt;
-  const bool lw = lw_host != nullptr;
-  if (lw) NERF_REQUIRE(level_tab_fill(lt, lw_host, L), NERF_E_SHAPE, "%s: level weights must be finite and in [0, 1]", who);
-  else for (int l = 0; l < 32; ++l) lt.w[l] = 1.0f;
-  if (BWD && lw) {                                        // masked levels at either end of the range are not launched at all
-    while (level_hi > level_lo && lt.w[level_hi - 1] == 0.0f) --level_hi;
-    while (level_lo < level_hi && lt.w[level_lo] == 0.0f) ++level_lo;
+// One hash-grid launch, filled by field name by the exported entries below.  Defaults: a point list, every level, float
+// atomics, no level weights, dense output rows.
+struct HashGridCall {
+  const char* who = nullptr;                               // the exported entry, for nerf_last_error()
+  PointSrc ps{nullptr, nullptr, nullptr, 1, 1.0f, 0.0f};   // sample positions: x [M,3], or rays / z / n / scale / offset (point_of)
+  int64_t M = 0;
+  int L = 0, log2_T = 0, F = 0;
+  const int* res = nullptr;                                // host: resolution of each level
+  const float* lw_host = nullptr;                          // host: level weights; NULL = all ones = the kernels without them
+  const float* tables = nullptr; float* out = nullptr;     // gather
+  int64_t out_stride = 0;                                  //   floats per output row; 0 = L F
+  const float* d_out = nullptr; void* d_tables = nullptr;  // scatter
+  int level_lo = 0, level_hi = -1;                         //   levels [lo, hi); hi < 0 = L
+  bool fixed = false;                                      //   d_tables holds int64 fixed-point accumulators
+};
+
+constexpr int HASH_LG = 4;                                // levels per thread: LG x F contiguous floats per sample
+
+// what the checks leave for the kernels; `empty`: a valid call with nothing to launch
+struct HashGridArgs { ResTab rt; LevelTab lt; uint32_t T; bool lw, empty; };
+
+// The argument checks of the gather and the scatter (level_hi < 0 becomes L).  Their order decides which error code wins when
+// several arguments are bad.
+static int hashgrid_check(HashGridCall& c, HashGridArgs& a) {
+  a.empty = true;
+  NERF_REQUIRE((c.ps.x || (c.ps.rays && c.ps.z)) && c.res, NERF_E_NULL, "%s: NULL pointer", c.who);
+  NERF_REQUIRE(c.L >= 1 && c.L <= 32 && c.log2_T >= 1 && c.log2_T <= 30, NERF_E_SHAPE, "%s: need 1<=L<=32, 1<=log2_T<=30", c.who);
+  NERF_REQUIRE(c.F == 1 || c.F == 2 || c.F == 4 || c.F == 8, NERF_E_UNSUPPORTED, "%s: F must be 1, 2, 4 or 8", c.who);
+  if (c.M <= 0) return NERF_OK;
+  for (int l = 0; l < c.L; ++l) a.rt.res[l] = (float)c.res[l];
+  a.T = 1u << c.log2_T;
+  if (c.level_hi < 0) c.level_hi = c.L;
+  NERF_REQUIRE(0 <= c.level_lo && c.level_lo <= c.level_hi && c.level_hi <= c.L, NERF_E_SHAPE,
+               "%s: need 0 <= level_lo <= level_hi <= L", c.who);
+  if (c.level_lo == c.level_hi) return NERF_OK;
+  a.lw = c.lw_host != nullptr;
+  if (a.lw) NERF_REQUIRE(level_tab_fill(a.lt, c.lw_host, c.L), NERF_E_SHAPE, "%s: level weights must be finite and in [0, 1]", c.who);
+  else for (int l = 0; l < 32; ++l) a.lt.w[l] = 1.0f;
+  a.empty = false;
+  return NERF_OK;
+}
+
+// a runtime feature count as a template argument, like with_bool (common.h): fn(std::integral_constant<int, F>) for the F in Fs
+template <int... Fs, class Fn> static void with_features(int F, Fn&& fn) {
+  (void)((F == Fs && (fn(std::integral_constant<int, Fs>{}), true)) || ...);
+}
+
+static int hashgrid_gather(HashGridCall c, void* stream) {
+  HashGridArgs a;
+  const int rc = hashgrid_check(c, a);
+  if (rc || a.empty) return rc;
+  const dim3 g(grid_for(c.M, 256, 256 * 32), (unsigned)((c.L + HASH_LG - 1) / HASH_LG)), b(256);
+  const int64_t out_stride = c.out_stride > 0 ? c.out_stride : (int64_t)c.L * c.F;
+  with_features<1, 2, 4, 8>(c.F, [&](auto f) { with_bool(a.lw, [&](auto lw) {
+    hipLaunchKernelGGL((hashgrid_fwd_kernel<decltype(f)::value, HASH_LG, decltype(lw)::value>), g, b, 0, as_stream(stream), c.ps,
+                       c.M, c.tables, c.L, a.T, a.rt, c.out, out_stride, a.lt);
+  }); });
+  return check_launch(c.who);
+}
+
+static int hashgrid_scatter(HashGridCall c, void* stream) {
+  HashGridArgs a;
+  const int rc = hashgrid_check(c, a);
+  if (rc || a.empty) return rc;
+  int level_lo = c.level_lo, level_hi = c.level_hi;
+  if (a.lw) {                                             // masked levels at either end of the range are not launched at all
+    while (level_hi > level_lo && a.lt.w[level_hi - 1] == 0.0f) --level_hi;
+    while (level_lo < level_hi && a.lt.w[level_lo] == 0.0f) ++level_lo;
     if (level_lo == level_hi) return NERF_OK;
   }
-  if (BWD && (F == 2 || F == 4) && g_hash_combine_max_res > 0) {
+  if ((c.F == 2 || c.F == 4) && g_hash_combine_max_res > 0) {
     // leading levels of the range whose resolution is small enough for LDS write-combining to pay (see the kernel)
     int nc = 0;
-    while (level_lo + nc < level_hi && res[level_lo + nc] <= g_hash_combine_max_res) ++nc;
+    while (level_lo + nc < level_hi && c.res[level_lo + nc] <= g_hash_combine_max_res) ++nc;
     if (nc > 0) {
-      const dim3 gc(grid_for((M + 63) / 64, 1, 256 * 8), (unsigned)nc), bc(256);
-      auto stc = as_stream(stream);
-      const PointSrc psc{x, rays, z, n, pos_scale, pos_offset};
-#define HC2(FF, FX, LWV) hipLaunchKernelGGL((hashgrid_bwd_combine_kernel<FF, FX, LWV>), gc, bc, 0, stc, psc, M, (void*)d_tables, d_out, L, T, rt, level_lo, lt)
-#define HC(FF) do { if (fixed) { if (lw) HC2(FF, true, true); else HC2(FF, true, false); } \
-                    else { if (lw) HC2(FF, false, true); else HC2(FF, false, false); } } while (0)
-      if (F == 2) HC(2); else HC(4);
-#undef HC
-#undef HC2
-      const int rc = check_launch(who);
-      if (rc) return rc;
+      const dim3 g(grid_for((c.M + 63) / 64, 1, 256 * 8), (unsigned)nc), b(256);
+      with_features<2, 4>(c.F, [&](auto f) { with_bool(c.fixed, [&](auto fixed) { with_bool(a.lw, [&](auto lw) {
+        hipLaunchKernelGGL((hashgrid_bwd_combine_kernel<decltype(f)::value, decltype(fixed)::value, decltype(lw)::value>), g, b, 0,
+                           as_stream(stream), c.ps, c.M, c.d_tables, c.d_out, c.L, a.T, a.rt, level_lo, a.lt);
+      }); }); });
+      const int rcc = check_launch(c.who);
+      if (rcc) return rcc;
       level_lo += nc;
       if (level_lo == level_hi) return NERF_OK;
     }
   }
-  const int nlev = BWD ? level_hi - level_lo : L;
-  const dim3 g(grid_for(BWD ? M * F * 2 : M, 256, 256 * 32), (unsigned)((nlev + LG - 1) / LG)), b(256);
-  auto st = as_stream(stream);
-  const PointSrc psd{x, rays, z, n, pos_scale, pos_offset};
-#define HB(FF, FX, LWV) hipLaunchKernelGGL((hashgrid_bwd_kernel<FF, LG, FX, LWV>), g, b, 0, st, psd, M, (void*)d_tables, d_out, L, T, rt, level_lo, level_hi, lt)
-#define HF(FF, LWV) hipLaunchKernelGGL((hashgrid_fwd_kernel<FF, LG, LWV>), g, b, 0, st, psd, M, tables, L, T, rt, out, \
-                                       out_stride > 0 ? out_stride : (int64_t)L * FF, lt)
-#define HG(FF) do { if (BWD && fixed) { if (lw) HB(FF, true, true); else HB(FF, true, false); } \
-                    else if (BWD) { if (lw) HB(FF, false, true); else HB(FF, false, false); } \
-                    else { if (lw) HF(FF, true); else HF(FF, false); } } while (0)
-  switch (F) { case 1: HG(1); break; case 2: HG(2); break; case 4: HG(4); break; default: HG(8); }
-#undef HG
-#undef HF
-#undef HB
+  const dim3 g(grid_for(c.M * c.F * 2, 256, 256 * 32), (unsigned)((level_hi - level_lo + HASH_LG - 1) / HASH_LG)), b(256);
+  with_features<1, 2, 4, 8>(c.F, [&](auto f) { with_bool(c.fixed, [&](auto fixed) { with_bool(a.lw, [&](auto lw) {
+    hipLaunchKernelGGL((hashgrid_bwd_kernel<decltype(f)::value, HASH_LG, decltype(fixed)::value, decltype(lw)::value>), g, b, 0,
+                       as_stream(stream), c.ps, c.M, c.d_tables, c.d_out, c.L, a.T, a.rt, level_lo, level_hi, a.lt);
+  }); }); });
+  return check_launch(c.who);
+}
+
+// ---- the bodies of the exported hash-grid entries.  A plain entry is its `_lw` entry with NULL weights (and, where it has no
+// level range or fixed_point argument, every level and float atomics); `who` keeps the called entry's name in the error text.
+static int hashgrid_forward_entry(const char* who, const float* x, int64_t M, const float* tables, int L, int log2_T, int F,
+                                  const int* res, const float* lw_host, float* out, void* stream) {
+  NERF_REQUIRE(tables && out, NERF_E_NULL, "%s: tables/out is NULL", who);
+  HashGridCall c;
+  c.who = who; c.ps.x = x; c.M = M; c.L = L; c.log2_T = log2_T; c.F = F; c.res = res; c.lw_host = lw_host;
+  c.tables = tables; c.out = out;
+  return hashgrid_gather(c, stream);
+}
+
+static int ngp_encode_entry(const char* who, const float* rays, const float* z, int64_t B, int n, const float* tables, int L,
+                            int log2_T, int F, const int* res, const float* lw_host, int sh_degree, float pos_scale,
+                            float pos_offset, float* x_out, float* pts_out, void* stream) {
+  if (B <= 0 || n <= 0) return NERF_OK;
+  NERF_REQUIRE(rays && z && tables && x_out, NERF_E_NULL, "%s: NULL pointer", who);
+  NERF_REQUIRE(sh_degree >= 0 && sh_degree <= 4, NERF_E_SHAPE, "%s: sh_degree=%d must be in range [0, 4]", who, sh_degree);
+  HashGridCall c;
+  c.who = who; c.ps.rays = rays; c.ps.z = z; c.ps.n = n; c.ps.scale = pos_scale; c.ps.offset = pos_offset;
+  c.M = B * n; c.L = L; c.log2_T = log2_T; c.F = F; c.res = res; c.lw_host = lw_host;
+  c.tables = tables; c.out = x_out; c.out_stride = (int64_t)L * F + (sh_degree + 1) * (sh_degree + 1);
+  const int rc = hashgrid_gather(c, stream);
+  if (rc) return rc;
+  hipLaunchKernelGGL(ngp_dir_rows_kernel, dim3(grid_for(c.M, 256)), dim3(256), 0, as_stream(stream), rays, z, n, c.M, sh_degree,
+                     x_out, c.out_stride, L * F, pts_out, pos_scale, pos_offset);
   return check_launch(who);
+}
+
+static int hashgrid_backward_entry(const char* who, const float* x, int64_t M, const float* d_out, int L, int log2_T, int F,
+                                   const int* res, const float* lw_host, int level_lo, int level_hi, int fixed_point,
+                                   void* d_tables, void* stream) {
+  NERF_REQUIRE(d_out && d_tables, NERF_E_NULL, "%s: d_out/d_tables is NULL", who);
+  NERF_REQUIRE(fixed_point == 0 || fixed_point == 1, NERF_E_UNSUPPORTED, "%s: fixed_point must be 0 or 1", who);
+  HashGridCall c;
+  c.who = who; c.ps.x = x; c.M = M; c.L = L; c.log2_T = log2_T; c.F = F; c.res = res; c.lw_host = lw_host;
+  c.d_out = d_out; c.d_tables = d_tables; c.level_lo = level_lo; c.level_hi = level_hi; c.fixed = fixed_point != 0;
+  return hashgrid_scatter(c, stream);
+}
+
+static int hashgrid_backward_rays_entry(const char* who, const float* rays, const float* z, int64_t B, int n, const float* d_out,
+                                        int L, int log2_T, int F, const int* res, const float* lw_host, float pos_scale,
+                                        float pos_offset, int level_lo, int level_hi, int fixed_point, void* d_tables,
+                                        void* stream) {
+  if (B <= 0 || n <= 0) return NERF_OK;
+  NERF_REQUIRE(rays && z && d_out && d_tables, NERF_E_NULL, "%s: NULL pointer", who);
+  NERF_REQUIRE(fixed_point == 0 || fixed_point == 1, NERF_E_UNSUPPORTED, "%s: fixed_point must be 0 or 1", who);
+  HashGridCall c;
+  c.who = who; c.ps.rays = rays; c.ps.z = z; c.ps.n = n; c.ps.scale = pos_scale; c.ps.offset = pos_offset;
+  c.M = B * n; c.L = L; c.log2_T = log2_T; c.F = F; c.res = res; c.lw_host = lw_host;
+  c.d_out = d_out; c.d_tables = d_tables; c.level_lo = level_lo; c.level_hi = level_hi; c.fixed = fixed_point != 0;
+  return hashgrid_scatter(c, stream);
 }
 
 }  // namespace nerf
@@ -380,110 +445,71 @@ extern "C" int nerf_sh_encode(const float* dirs, int64_t M, int degree, float* o
 
 extern "C" int nerf_hashgrid_forward(const float* x, int64_t M, const float* tables, int L, int log2_T, int F,
                                      const int* resolutions_host, float* out, void* stream) {
-  NERF_REQUIRE(tables && out, NERF_E_NULL, "nerf_hashgrid_forward: tables/out is NULL");
-  return launch_hashgrid<false>(x, M, tables, nullptr, nullptr, L, log2_T, F, resolutions_host, out, stream,
-                                "nerf_hashgrid_forward");
+  return hashgrid_forward_entry("nerf_hashgrid_forward", x, M, tables, L, log2_T, F, resolutions_host, nullptr, out, stream);
 }
 
 extern "C" int nerf_hashgrid_backward(const float* x, int64_t M, const float* d_out, int L, int log2_T, int F,
                                       const int* resolutions_host, float* d_tables, void* stream) {
-  NERF_REQUIRE(d_out && d_tables, NERF_E_NULL, "nerf_hashgrid_backward: d_out/d_tables is NULL");
-  return launch_hashgrid<true>(x, M, nullptr, d_tables, d_out, L, log2_T, F, resolutions_host, nullptr, stream,
-                               "nerf_hashgrid_backward");
+  return hashgrid_backward_entry("nerf_hashgrid_backward", x, M, d_out, L, log2_T, F, resolutions_host, nullptr, 0, -1, 0,
+                                 d_tables, stream);
 }
 
 extern "C" int nerf_ngp_encode(const float* rays, const float* z, int64_t B, int n, const float* tables, int L,
                                int log2_T, int F, const int* resolutions_host, int sh_degree, float pos_scale,
                                float pos_offset, float* x_out, float* pts_out, void* stream) {
-  if (B <= 0 || n <= 0) return NERF_OK;
-  NERF_REQUIRE(rays && z && tables && x_out, NERF_E_NULL, "nerf_ngp_encode: NULL pointer");
-  NERF_REQUIRE(sh_degree >= 0 && sh_degree <= 4, NERF_E_SHAPE, "nerf_ngp_encode: sh_degree=%d must be in range [0, 4]", sh_degree);
-  const int64_t M = B * n;
-  const int64_t stride = (int64_t)L * F + (sh_degree + 1) * (sh_degree + 1);
-  const int rc = launch_hashgrid<false>(nullptr, M, tables, nullptr, nullptr, L, log2_T, F, resolutions_host, x_out, stream,
-                                        "nerf_ngp_encode", rays, z, n, stride, pos_scale, pos_offset);
-  if (rc) return rc;
-  hipLaunchKernelGGL(ngp_dir_rows_kernel, dim3(grid_for(M, 256)), dim3(256), 0, as_stream(stream), rays, z, n, M, sh_degree,
-                     x_out, stride, L * F, pts_out, pos_scale, pos_offset);
-  return check_launch("nerf_ngp_encode");
+  return ngp_encode_entry("nerf_ngp_encode", rays, z, B, n, tables, L, log2_T, F, resolutions_host, nullptr, sh_degree, pos_scale,
+                          pos_offset, x_out, pts_out, stream);
 }
 
 extern "C" int nerf_hashgrid_backward_ex(const float* x, int64_t M, const float* d_out, int L, int log2_T, int F,
                                          const int* resolutions_host, int level_lo, int level_hi, int fixed_point,
                                          void* d_tables, void* stream) {
-  NERF_REQUIRE(d_out && d_tables, NERF_E_NULL, "nerf_hashgrid_backward_ex: d_out/d_tables is NULL");
-  NERF_REQUIRE(fixed_point == 0 || fixed_point == 1, NERF_E_UNSUPPORTED, "nerf_hashgrid_backward_ex: fixed_point must be 0 or 1");
-  return launch_hashgrid<true>(x, M, nullptr, static_cast<float*>(d_tables), d_out, L, log2_T, F, resolutions_host, nullptr,
-                               stream, "nerf_hashgrid_backward_ex", nullptr, nullptr, 1, 0, 1.0f, 0.0f, level_lo, level_hi,
-                               fixed_point != 0);
+  return hashgrid_backward_entry("nerf_hashgrid_backward_ex", x, M, d_out, L, log2_T, F, resolutions_host, nullptr, level_lo,
+                                 level_hi, fixed_point, d_tables, stream);
 }
 
 extern "C" int nerf_hashgrid_backward_rays_ex(const float* rays, const float* z, int64_t B, int n, const float* d_out, int L,
                                               int log2_T, int F, const int* resolutions_host, float pos_scale,
                                               float pos_offset, int level_lo, int level_hi, int fixed_point,
                                               void* d_tables, void* stream) {
-  if (B <= 0 || n <= 0) return NERF_OK;
-  NERF_REQUIRE(rays && z && d_out && d_tables, NERF_E_NULL, "nerf_hashgrid_backward_rays_ex: NULL pointer");
-  NERF_REQUIRE(fixed_point == 0 || fixed_point == 1, NERF_E_UNSUPPORTED, "nerf_hashgrid_backward_rays_ex: fixed_point must be 0 or 1");
-  return launch_hashgrid<true>(nullptr, B * n, nullptr, static_cast<float*>(d_tables), d_out, L, log2_T, F, resolutions_host,
-                               nullptr, stream, "nerf_hashgrid_backward_rays_ex", rays, z, n, 0, pos_scale, pos_offset,
-                               level_lo, level_hi, fixed_point != 0);
+  return hashgrid_backward_rays_entry("nerf_hashgrid_backward_rays_ex", rays, z, B, n, d_out, L, log2_T, F, resolutions_host,
+                                      nullptr, pos_scale, pos_offset, level_lo, level_hi, fixed_point, d_tables, stream);
 }
 
 extern "C" int nerf_hashgrid_backward_rays(const float* rays, const float* z, int64_t B, int n, const float* d_out, int L,
                                            int log2_T, int F, const int* resolutions_host, float pos_scale,
                                            float pos_offset, float* d_tables, void* stream) {
-  if (B <= 0 || n <= 0) return NERF_OK;
-  NERF_REQUIRE(rays && z && d_out && d_tables, NERF_E_NULL, "nerf_hashgrid_backward_rays: NULL pointer");
-  return launch_hashgrid<true>(nullptr, B * n, nullptr, d_tables, d_out, L, log2_T, F, resolutions_host, nullptr, stream,
-                               "nerf_hashgrid_backward_rays", rays, z, n, 0, pos_scale, pos_offset);
+  return hashgrid_backward_rays_entry("nerf_hashgrid_backward_rays", rays, z, B, n, d_out, L, log2_T, F, resolutions_host,
+                                      nullptr, pos_scale, pos_offset, 0, -1, 0, d_tables, stream);
 }
 
 // ---- the same entries with per-level weights (include/nerf_hip.h, "level weights"); level_weights_host == NULL: all ones ----
 extern "C" int nerf_hashgrid_forward_lw(const float* x, int64_t M, const float* tables, int L, int log2_T, int F,
                                         const int* resolutions_host, const float* level_weights_host, float* out,
                                         void* stream) {
-  NERF_REQUIRE(tables && out, NERF_E_NULL, "nerf_hashgrid_forward_lw: tables/out is NULL");
-  return launch_hashgrid<false>(x, M, tables, nullptr, nullptr, L, log2_T, F, resolutions_host, out, stream,
-                                "nerf_hashgrid_forward_lw", nullptr, nullptr, 1, 0, 1.0f, 0.0f, 0, -1, false, level_weights_host);
+  return hashgrid_forward_entry("nerf_hashgrid_forward_lw", x, M, tables, L, log2_T, F, resolutions_host, level_weights_host, out,
+                                stream);
 }
 
 extern "C" int nerf_ngp_encode_lw(const float* rays, const float* z, int64_t B, int n, const float* tables, int L,
                                   int log2_T, int F, const int* resolutions_host, const float* level_weights_host,
                                   int sh_degree, float pos_scale, float pos_offset, float* x_out, float* pts_out,
                                   void* stream) {
-  if (B <= 0 || n <= 0) return NERF_OK;
-  NERF_REQUIRE(rays && z && tables && x_out, NERF_E_NULL, "nerf_ngp_encode_lw: NULL pointer");
-  NERF_REQUIRE(sh_degree >= 0 && sh_degree <= 4, NERF_E_SHAPE, "nerf_ngp_encode_lw: sh_degree=%d must be in range [0, 4]", sh_degree);
-  const int64_t M = B * n;
-  const int64_t stride = (int64_t)L * F + (sh_degree + 1) * (sh_degree + 1);
-  const int rc = launch_hashgrid<false>(nullptr, M, tables, nullptr, nullptr, L, log2_T, F, resolutions_host, x_out, stream,
-                                        "nerf_ngp_encode_lw", rays, z, n, stride, pos_scale, pos_offset, 0, -1, false,
-                                        level_weights_host);
-  if (rc) return rc;
-  hipLaunchKernelGGL(ngp_dir_rows_kernel, dim3(grid_for(M, 256)), dim3(256), 0, as_stream(stream), rays, z, n, M, sh_degree,
-                     x_out, stride, L * F, pts_out, pos_scale, pos_offset);
-  return check_launch("nerf_ngp_encode_lw");
+  return ngp_encode_entry("nerf_ngp_encode_lw", rays, z, B, n, tables, L, log2_T, F, resolutions_host, level_weights_host,
+                          sh_degree, pos_scale, pos_offset, x_out, pts_out, stream);
 }
 
 extern "C" int nerf_hashgrid_backward_ex_lw(const float* x, int64_t M, const float* d_out, int L, int log2_T, int F,
                                             const int* resolutions_host, const float* level_weights_host, int level_lo,
                                             int level_hi, int fixed_point, void* d_tables, void* stream) {
-  NERF_REQUIRE(d_out && d_tables, NERF_E_NULL, "nerf_hashgrid_backward_ex_lw: d_out/d_tables is NULL");
-  NERF_REQUIRE(fixed_point == 0 || fixed_point == 1, NERF_E_UNSUPPORTED, "nerf_hashgrid_backward_ex_lw: fixed_point must be 0 or 1");
-  return launch_hashgrid<true>(x, M, nullptr, static_cast<float*>(d_tables), d_out, L, log2_T, F, resolutions_host, nullptr,
-                               stream, "nerf_hashgrid_backward_ex_lw", nullptr, nullptr, 1, 0, 1.0f, 0.0f, level_lo, level_hi,
-                               fixed_point != 0, level_weights_host);
+  return hashgrid_backward_entry("nerf_hashgrid_backward_ex_lw", x, M, d_out, L, log2_T, F, resolutions_host, level_weights_host,
+                                 level_lo, level_hi, fixed_point, d_tables, stream);
 }
 
 extern "C" int nerf_hashgrid_backward_rays_ex_lw(const float* rays, const float* z, int64_t B, int n, const float* d_out,
                                                  int L, int log2_T, int F, const int* resolutions_host,
                                                  const float* level_weights_host, float pos_scale, float pos_offset,
                                                  int level_lo, int level_hi, int fixed_point, void* d_tables, void* stream) {
-  if (B <= 0 || n <= 0) return NERF_OK;
-  NERF_REQUIRE(rays && z && d_out && d_tables, NERF_E_NULL, "nerf_hashgrid_backward_rays_ex_lw: NULL pointer");
-  NERF_REQUIRE(fixed_point == 0 || fixed_point == 1, NERF_E_UNSUPPORTED, "nerf_hashgrid_backward_rays_ex_lw: fixed_point must be 0 or 1");
-  return launch_hashgrid<true>(nullptr, B * n, nullptr, static_cast<float*>(d_tables), d_out, L, log2_T, F, resolutions_host,
-                               nullptr, stream, "nerf_hashgrid_backward_rays_ex_lw", rays, z, n, 0, pos_scale, pos_offset,
-                               level_lo, level_hi, fixed_point != 0, level_weights_host);
+  return hashgrid_backward_rays_entry("nerf_hashgrid_backward_rays_ex_lw", rays, z, B, n, d_out, L, log2_T, F, resolutions_host,
+                                      level_weights_host, pos_scale, pos_offset, level_lo, level_hi, fixed_point, d_tables, stream);
 }

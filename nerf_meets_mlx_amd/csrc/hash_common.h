@@ -125,6 +125,28 @@ __device__ __forceinline__ Corners corners_of(float px, float py, float pz, floa
   return c;
 }
 
+// The table-gradient scatter's share of corners_of: a lane serves ONE x plane of a sample's cell (dx = 0: x = floor,
+// dx = 1: x = ceil) and gets the four entries of that plane with the addends of its feature, g = (weighted) d_out.
+// The deterministic mode is bit-exact only while this rounds like corners_of and the forward interpolation: xs = p * r,
+// floor / ceil, offset = xs - floor, the hash3 multiplies, and each addend as the product g * wz * wy * wx in that order
+// (the per-corner form; -ffp-contract=off).  Pairing: 0 = (yc, zc), 1 = (yf, zc), 2 = (yc, zf), 3 = (yf, zf).
+struct PlaneAddends { uint32_t idx[4]; float val[4]; };
+__device__ __forceinline__ PlaneAddends plane_addends(float px, float py, float pz, float r, uint32_t mask, int dx, float g) {
+  const float xs = px * r, ys = py * r, zs = pz * r;
+  const float fx = floorf(xs), fy = floorf(ys), fz = floorf(zs);
+  const float ox = xs - fx, oy = ys - fy, oz = zs - fz;
+  const uint32_t cx = (uint32_t)(int32_t)(dx ? ceilf(xs) : fx);
+  const uint32_t yf = (uint32_t)(int32_t)fy * 2654435761u, yc = (uint32_t)(int32_t)ceilf(ys) * 2654435761u;
+  const uint32_t zf = (uint32_t)(int32_t)fz * 805459861u, zc = (uint32_t)(int32_t)ceilf(zs) * 805459861u;
+  const float wx = dx ? ox : 1 - ox;
+  PlaneAddends a;
+  a.idx[0] = (cx ^ yc ^ zc) & mask; a.val[0] = g * oz * oy * wx;
+  a.idx[1] = (cx ^ yf ^ zc) & mask; a.val[1] = g * oz * (1 - oy) * wx;
+  a.idx[2] = (cx ^ yc ^ zf) & mask; a.val[2] = g * (1 - oz) * oy * wx;
+  a.idx[3] = (cx ^ yf ^ zf) & mask; a.val[3] = g * (1 - oz) * (1 - oy) * wx;
+  return a;
+}
+
 // sample position: row m of x [M,3], or o + z d of ray m / n (rendering/render.py:142: one multiply, one add)
 struct PointSrc { const float* x; const float* rays; const float* z; int n; float scale, offset; };
 __device__ __forceinline__ void point_of(const PointSrc& ps, int64_t m, float& px, float& py, float& pz) {

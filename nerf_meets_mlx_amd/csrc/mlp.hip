@@ -2179,17 +2179,16 @@ static int ngp_query_fused_impl(const nerf_mlp_arch* arch, const void* packed, c
   NERF_REQUIRE(packed && rays && z && tables && resolutions_host && raw, NERF_E_NULL, "nerf_ngp_query_fused: NULL pointer");
   const int64_t M = B * n;
   NERF_REQUIRE(M < (1ll << 31), NERF_E_SHAPE, "nerf_ngp_query_fused: B*n must be < 2^31");
+  LevelTab lt;
+  if (lw_host)
+    NERF_REQUIRE(level_tab_fill(lt, lw_host, L), NERF_E_SHAPE, "nerf_ngp_query_fused_lw: level weights must be finite and in [0, 1]");
   if (arch_s16(arch)) {         // reference tolerance: float32 gathers from the master tables (the fp16 shadow is a reduced-precision
     s16x::SmallQuery q;         // image: not read in this mode), float32 interpolation, split-bf16 MLP (mlp_s16x.hip)
     q.rays = rays; q.z = z; q.n = n; q.tables = tables; q.T = 1u << log2_T; q.pos_scale = pos_scale; q.pos_offset = pos_offset;
     for (int l = 0; l < 32; ++l) q.res[l] = l < L ? (float)resolutions_host[l] : 0.0f;
     q.B = B; q.ray_major = g_ngp_ray_major;
     q.use_lw = lw_host != nullptr;
-    if (lw_host) {
-      LevelTab lt;
-      NERF_REQUIRE(level_tab_fill(lt, lw_host, L), NERF_E_SHAPE, "nerf_ngp_query_fused_lw: level weights must be finite and in [0, 1]");
-      for (int l = 0; l < 32; ++l) q.lw[l] = lt.w[l];
-    }
+    if (lw_host) for (int l = 0; l < 32; ++l) q.lw[l] = lt.w[l];
     return s16x::small_forward(static_cast<const char*>(packed) + LN::PACKED_BYTES, small_bias_of(packed), nullptr, M, raw, acts,
                                small_astride16(true), &q, as_stream(stream));
   }
@@ -2203,15 +2202,12 @@ static int ngp_query_fused_impl(const nerf_mlp_arch* arch, const void* packed, c
   a.ray_major = (!acts && g_ngp_ray_major && B >= 32) ? 1 : 0;
   const int64_t nwg = ((a.ray_major ? ((B + 31) / 32) * (int64_t)n : (M + 31) / 32) + 7) / 8;
   const dim3 g((unsigned)(nwg < 2048 ? nwg : 2048)), b(512);
-  if (lw_host) {
-    NERF_REQUIRE(level_tab_fill(a.lw, lw_host, L), NERF_E_SHAPE, "nerf_ngp_query_fused_lw: level weights must be finite and in [0, 1]");
-    if (acts) hipLaunchKernelGGL((mlp_small_fwd_kernel<true, true, true>), g, b, LN::LDS_BYTES, as_stream(stream), a);
-    else hipLaunchKernelGGL((mlp_small_fwd_kernel<false, true, true>), g, b, LN::LDS_BYTES, as_stream(stream), a);
-    return check_launch("nerf_ngp_query_fused_lw");
-  }
-  if (acts) hipLaunchKernelGGL((mlp_small_fwd_kernel<true, true>), g, b, LN::LDS_BYTES, as_stream(stream), a);
-  else hipLaunchKernelGGL((mlp_small_fwd_kernel<false, true>), g, b, LN::LDS_BYTES, as_stream(stream), a);
-  return check_launch("nerf_ngp_query_fused");
+  if (lw_host) a.lw = lt;
+  with_bool(acts != nullptr, [&](auto store) { with_bool(lw_host != nullptr, [&](auto lw) {
+    hipLaunchKernelGGL((mlp_small_fwd_kernel<decltype(store)::value, true, decltype(lw)::value>), g, b, LN::LDS_BYTES,
+                       as_stream(stream), a);
+  }); });
+  return check_launch(lw_host ? "nerf_ngp_query_fused_lw" : "nerf_ngp_query_fused");
 }
 
 extern "C" int nerf_ngp_query_fused_h(const nerf_mlp_arch* arch, const void* packed, const float* rays, const float* z,

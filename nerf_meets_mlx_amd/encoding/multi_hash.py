@@ -62,7 +62,8 @@ class MultiHashEncoding(Encoding):
 
     @property
     def level_weights(self):
-        """Per-level weights w[n_levels] in [0, 1] (a tuple) or None (the default: every call is the one without weights).
+        """Per-level weights w[n_levels] in [0, 1] (a tuple) or None (the default: the `_lw` entries get NULL and run the kernels without
+        weights).
         Forward: feature (l, f) = w[l] * interpolation, a level with w[l] == 0 is not read; backward: the table gradient of
         level l is that of w[l] * d_out, a level with w[l] == 0 is not touched (include/nerf_hip.h, "Level weights")."""
         return self._lw
@@ -78,14 +79,9 @@ class MultiHashEncoding(Encoding):
     def __call__(self, in_array: torch.Tensor):
         x = N.f32(in_array)
         out = torch.empty(x.shape[0], self.get_out_dim(), dtype=torch.float32, device=x.device)
-        if self._lw_c is not None:
-            N.check(N.lib().nerf_hashgrid_forward_lw(N.ptr(x), x.shape[0], N.ptr(self.tables), self.n_levels,
-                                                     self.log2_hashmap_size, self.n_features_per_level, self._res_c,
-                                                     self._lw_c, N.ptr(out), N.stream()))
-            return out
-        N.check(N.lib().nerf_hashgrid_forward(N.ptr(x), x.shape[0], N.ptr(self.tables), self.n_levels,
-                                              self.log2_hashmap_size, self.n_features_per_level, self._res_c,
-                                              N.ptr(out), N.stream()))
+        N.check(N.lib().nerf_hashgrid_forward_lw(N.ptr(x), x.shape[0], N.ptr(self.tables), self.n_levels,
+                                                 self.log2_hashmap_size, self.n_features_per_level, self._res_c,
+                                                 self._lw_c, N.ptr(out), N.stream()))       # _lw_c None: NULL, no weights
         return out
 
     def backward(self, in_array: torch.Tensor, d_out: torch.Tensor, level_weights=_CURRENT):
@@ -101,13 +97,7 @@ class MultiHashEncoding(Encoding):
             lw_c = level_weights
         else:
             lw_c = (C.c_float * self.n_levels)(*check_level_weights(level_weights, self.n_levels))
-        if lw_c is not None:
-            N.check(N.lib().nerf_hashgrid_backward_ex_lw(N.ptr(x), x.shape[0], N.ptr(g), self.n_levels, self.log2_hashmap_size,
-                                                         self.n_features_per_level, self._res_c,
-                                                         lw_c, 0, self.n_levels,
-                                                         int(self.grad.dtype == torch.int64), N.ptr(self.grad), N.stream()))
-            return self.grad
-        N.check(N.lib().nerf_hashgrid_backward_ex(N.ptr(x), x.shape[0], N.ptr(g), self.n_levels, self.log2_hashmap_size,
-                                                  self.n_features_per_level, self._res_c, 0, self.n_levels,
-                                                  int(self.grad.dtype == torch.int64), N.ptr(self.grad), N.stream()))
+        N.check(N.lib().nerf_hashgrid_backward_ex_lw(N.ptr(x), x.shape[0], N.ptr(g), self.n_levels, self.log2_hashmap_size,
+                                                     self.n_features_per_level, self._res_c, lw_c, 0, self.n_levels,
+                                                     int(self.grad.dtype == torch.int64), N.ptr(self.grad), N.stream()))
         return self.grad

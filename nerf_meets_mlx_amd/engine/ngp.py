@@ -117,8 +117,9 @@ class HashNeRF:
     @property
     def level_weights(self):
         """Per-level weights of the hash encoding (a tuple of n_levels numbers in [0, 1]) or None, the default: every path then
-        calls exactly what it calls without the option.  features, features_unfused, query (fused, unfused, culled, packed) and
-        backward use them; backward uses the weights captured by the last query(train=True), not the current property."""
+        passes NULL weights and runs the same kernels as without the option.  features, features_unfused, query (fused, unfused,
+        culled, packed) and backward use them; backward uses the weights captured by the last query(train=True), not the current
+        property."""
         return self.enc.level_weights
 
     @level_weights.setter
@@ -132,14 +133,9 @@ class HashNeRF:
         e = self.enc
         x = torch.empty(B * n, 48, dtype=torch.float32, device=z.device)
         pts = torch.empty(B * n, 3, dtype=torch.float32, device=z.device) if need_pts else None
-        if e._lw_c is not None:
-            N.check(N.lib().nerf_ngp_encode_lw(N.ptr(N.f32(rays)), N.ptr(N.f32(z)), B, n, N.ptr(e.tables), e.n_levels,
-                                               e.log2_hashmap_size, e.n_features_per_level, e._res_c, e._lw_c, 3, self.pos_scale,
-                                               self.pos_offset, N.ptr(x), N.ptr(pts), N.stream()))
-            return pts, x
-        N.check(N.lib().nerf_ngp_encode(N.ptr(N.f32(rays)), N.ptr(N.f32(z)), B, n, N.ptr(e.tables), e.n_levels,
-                                        e.log2_hashmap_size, e.n_features_per_level, e._res_c, 3, self.pos_scale,
-                                        self.pos_offset, N.ptr(x), N.ptr(pts), N.stream()))
+        N.check(N.lib().nerf_ngp_encode_lw(N.ptr(N.f32(rays)), N.ptr(N.f32(z)), B, n, N.ptr(e.tables), e.n_levels,
+                                           e.log2_hashmap_size, e.n_features_per_level, e._res_c, e._lw_c, 3, self.pos_scale,
+                                           self.pos_offset, N.ptr(x), N.ptr(pts), N.stream()))
         return pts, x
 
     def features_unfused(self, rays: torch.Tensor, z: torch.Tensor):
@@ -181,16 +177,10 @@ class HashNeRF:
         if train:
             acts = m._begin_train_pass(B * n)
             self._pts, self._rz = None, (rays, z)
-        if e._lw_c is not None:
-            N.check(N.lib().nerf_ngp_query_fused_lw(C.byref(m.arch), N.ptr(m.packed()), N.ptr(rays), N.ptr(z), B, n,
-                                                    N.ptr(e.tables), N.ptr(self.table.shadow()), e.n_levels, e.log2_hashmap_size,
-                                                    e.n_features_per_level, e._res_c, e._lw_c, 3, self.pos_scale,
-                                                    self.pos_offset, N.ptr(raw), N.ptr(acts), N.stream()))
-            return raw
-        N.check(N.lib().nerf_ngp_query_fused_h(C.byref(m.arch), N.ptr(m.packed()), N.ptr(rays), N.ptr(z), B, n,
-                                               N.ptr(e.tables), N.ptr(self.table.shadow()), e.n_levels, e.log2_hashmap_size,
-                                               e.n_features_per_level, e._res_c, 3, self.pos_scale, self.pos_offset,
-                                               N.ptr(raw), N.ptr(acts), N.stream()))
+        N.check(N.lib().nerf_ngp_query_fused_lw(C.byref(m.arch), N.ptr(m.packed()), N.ptr(rays), N.ptr(z), B, n,
+                                                N.ptr(e.tables), N.ptr(self.table.shadow()), e.n_levels, e.log2_hashmap_size,
+                                                e.n_features_per_level, e._res_c, e._lw_c, 3, self.pos_scale,
+                                                self.pos_offset, N.ptr(raw), N.ptr(acts), N.stream()))
         return raw
 
     def _query_culled(self, rays, z, train, grid):
@@ -267,16 +257,10 @@ class HashNeRF:
         else:
             rays, z = self._rz
             for lo, hi in self.level_groups:
-                if self._bwd_lw is not None:             # the weights of the forward pass this is the gradient of
-                    N.check(N.lib().nerf_hashgrid_backward_rays_ex_lw(
-                        N.ptr(rays), N.ptr(z), z.shape[0], z.shape[1], N.ptr(d_x), e.n_levels, e.log2_hashmap_size,
-                        e.n_features_per_level, e._res_c, self._bwd_lw, self.pos_scale, self.pos_offset, lo, hi,
-                        int(self.deterministic), N.ptr(e.grad), N.stream()))
-                else:
-                    N.check(N.lib().nerf_hashgrid_backward_rays_ex(
-                        N.ptr(rays), N.ptr(z), z.shape[0], z.shape[1], N.ptr(d_x), e.n_levels, e.log2_hashmap_size,
-                        e.n_features_per_level, e._res_c, self.pos_scale, self.pos_offset, lo, hi, int(self.deterministic),
-                        N.ptr(e.grad), N.stream()))
+                N.check(N.lib().nerf_hashgrid_backward_rays_ex_lw(       # the weights of the forward pass this is the gradient of
+                    N.ptr(rays), N.ptr(z), z.shape[0], z.shape[1], N.ptr(d_x), e.n_levels, e.log2_hashmap_size,
+                    e.n_features_per_level, e._res_c, self._bwd_lw, self.pos_scale, self.pos_offset, lo, hi,
+                    int(self.deterministic), N.ptr(e.grad), N.stream()))
                 if self.on_group_done is not None:
                     self.on_group_done(lo, hi)
         if self.timing is not None:

@@ -6,7 +6,9 @@ Every comparison is bit-exact.  The stand-alone encoders are held to the float32
 query is held to the EXISTING query on tables whose level l was multiplied by w[l] in {0, 0.25, 0.5, 1}: a power-of-two scale
 commutes with every rounding of the interpolation while nothing is subnormal (table magnitudes in [2^-8, 1]).  The weighted
 scatter is held to the existing entry fed d_out pre-multiplied per level column by w[l] in float32 -- the operation order the
-header states.  L = 16, F = 2, resolutions 16 ... 2048: the first five levels (N_l <= 64) take the LDS write-combining path."""
+header states.  L = 16, F = 2, resolutions 16 ... 2048: the first five levels (N_l <= 64) take the LDS write-combining path.
+Section 9 holds every entry without the suffix to its `_lw` entry called with NULL weights, results and error texts."""
+import contextlib
 import ctypes as C
 
 import numpy as np
@@ -17,7 +19,7 @@ from nerf_meets_mlx_amd import _native as N
 from oracle import nerf_oracle as O
 from tests import _hashgrid_ref as R
 from tests import _levels_ref as LR
-from tests._poison import bits_equal, sentinel_, unwritten
+from tests._poison import NAN_BYTES, bits_equal, layer_into, ngp_query_into, poison_, sentinel_, unwritten
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda"
@@ -427,3 +429,138 @@ def test_rendering_and_density_volume_see_the_weights(dataset):
     c = _trainer(dataset, None)                              # and the weights matter: all 16 levels give another volume
     c.field.enc.tables.copy_(big)
     assert not bits_equal(c.density_volume(16), va)
+
+
+# ----------------------------------------------------------------------- 9. a plain entry is its `_lw` entry with NULL weights
+# M = 300: one full 256-thread block plus a tail; for the write-combining kernel four full 64-sample chunks plus a tail.  With
+# hash_combine_max_res = 64 three levels go through LDS and three direct, and a group of 4 levels per thread straddles that line.
+PAIR_RES = [16, 30, 64, 65, 181, 2048]
+PAIR_L, PAIR_B, PAIR_N, PAIR_LOG2_T = 6, 100, 3, 12
+PAIR_M = PAIR_B * PAIR_N
+PAIR_PATHS = [(1, 0), (2, 0), (4, 0), (8, 0), (2, 64), (4, 64)]          # (F, hash_combine_max_res): 0 = every level direct
+
+
+@contextlib.contextmanager
+def _combine(max_res):
+    lib = N.lib()
+    old = lib.nerf_get_option(b"hash_combine_max_res")
+    N.check(lib.nerf_set_option(b"hash_combine_max_res", int(max_res)))
+    try:
+        yield
+    finally:
+        N.check(lib.nerf_set_option(b"hash_combine_max_res", old))
+
+
+@pytest.fixture(scope="module")
+def pair_points():
+    """(rays [B, 11], z [B, n], the same M = B n points as a list [M, 3]) on the device"""
+    rays, z = _rays(PAIR_B, PAIR_N, 77)
+    return _dev(rays), _dev(z), _dev(R.points(rays, z.reshape(-1), PAIR_N, SCALE, OFFSET))
+
+
+@pytest.mark.parametrize("Fp", [1, 2, 4, 8])
+def test_plain_encoders_equal_the_lw_entries_with_null(Fp, pair_points):
+    rays, z, p = pair_points
+    lib, s, res = N.lib(), N.stream(), (C.c_int * PAIR_L)(*PAIR_RES)
+    M, L, lt = PAIR_M, PAIR_L, PAIR_LOG2_T
+    tables = _dev(np.random.default_rng(Fp).standard_normal((L, 1 << lt, Fp)).astype(f32))
+    outs = []
+    for lw in (False, True):
+        out = sentinel_(torch.empty(M, L * Fp, dtype=torch.float32, device=DEV))
+        x = sentinel_(torch.empty(M, L * Fp + 16, dtype=torch.float32, device=DEV))
+        pts = sentinel_(torch.empty(M, 3, dtype=torch.float32, device=DEV))
+        if lw:
+            N.check(lib.nerf_hashgrid_forward_lw(N.ptr(p), M, N.ptr(tables), L, lt, Fp, res, None, N.ptr(out), s))
+            N.check(lib.nerf_ngp_encode_lw(N.ptr(rays), N.ptr(z), PAIR_B, PAIR_N, N.ptr(tables), L, lt, Fp, res, None, 3, SCALE,
+                                           OFFSET, N.ptr(x), N.ptr(pts), s))
+        else:
+            N.check(lib.nerf_hashgrid_forward(N.ptr(p), M, N.ptr(tables), L, lt, Fp, res, N.ptr(out), s))
+            N.check(lib.nerf_ngp_encode(N.ptr(rays), N.ptr(z), PAIR_B, PAIR_N, N.ptr(tables), L, lt, Fp, res, 3, SCALE, OFFSET,
+                                        N.ptr(x), N.ptr(pts), s))
+        outs.append((out, x, pts))
+    for a, b in zip(*outs):
+        assert unwritten(a) == 0 and unwritten(b) == 0 and bits_equal(a, b)
+    assert bits_equal(outs[0][0], outs[0][1][:, :L * Fp])
+
+
+@pytest.mark.parametrize("Fp,combine", PAIR_PATHS)
+def test_plain_scatters_equal_the_lw_entries_with_null(Fp, combine, pair_points):
+    """Fixed-point mode only: float atomics are not order-independent.  Random int64 in every accumulator; all bytes compared."""
+    rays, z, p = pair_points
+    lib, s, res = N.lib(), N.stream(), (C.c_int * PAIR_L)(*PAIR_RES)
+    M, L, lt = PAIR_M, PAIR_L, PAIR_LOG2_T
+    rng = np.random.default_rng(10 * Fp + combine)
+    d_out = _dev(rng.standard_normal((M, L * Fp)).astype(f32))
+    prefill = _dev(rng.integers(-(1 << 62), 1 << 62, (L, 1 << lt, Fp), dtype=np.int64))
+    pts, pts_lw, ray, ray_lw = (prefill.clone() for _ in range(4))
+    with _combine(combine):
+        N.check(lib.nerf_hashgrid_backward_ex(N.ptr(p), M, N.ptr(d_out), L, lt, Fp, res, 0, L, 1, N.ptr(pts), s))
+        N.check(lib.nerf_hashgrid_backward_ex_lw(N.ptr(p), M, N.ptr(d_out), L, lt, Fp, res, None, 0, L, 1, N.ptr(pts_lw), s))
+        N.check(lib.nerf_hashgrid_backward_rays_ex(N.ptr(rays), N.ptr(z), PAIR_B, PAIR_N, N.ptr(d_out), L, lt, Fp, res, SCALE,
+                                                   OFFSET, 0, L, 1, N.ptr(ray), s))
+        N.check(lib.nerf_hashgrid_backward_rays_ex_lw(N.ptr(rays), N.ptr(z), PAIR_B, PAIR_N, N.ptr(d_out), L, lt, Fp, res, None,
+                                                      SCALE, OFFSET, 0, L, 1, N.ptr(ray_lw), s))
+        torch.cuda.synchronize()
+    assert torch.equal(pts, pts_lw) and torch.equal(ray, ray_lw) and torch.equal(pts, ray)
+    assert all((pts[l] != prefill[l]).any() for l in range(L))           # every level was scattered into
+
+
+def _query_lw_null(f, rays, z, train):
+    """tests/_poison.py:ngp_query_into through `nerf_ngp_query_fused_lw` with NULL weights"""
+    B, n = z.shape
+    e, m = f.enc, f.mlp
+    raw = sentinel_(torch.empty(B, n, 4, dtype=torch.float32, device=z.device))
+    acts = poison_(m._begin_train_pass(B * n), NAN_BYTES) if train else None
+    N.check(N.lib().nerf_ngp_query_fused_lw(C.byref(m.arch), N.ptr(m.packed()), N.ptr(rays), N.ptr(z), B, n, N.ptr(e.tables),
+                                            N.ptr(f.table.shadow()), e.n_levels, e.log2_hashmap_size, e.n_features_per_level,
+                                            e._res_c, None, 3, f.pos_scale, f.pos_offset, N.ptr(raw), N.ptr(acts), N.stream()))
+    return raw
+
+
+@pytest.mark.parametrize("precision,half", MODES)
+@pytest.mark.parametrize("train", [False, True])
+def test_plain_fused_query_equals_the_lw_entry_with_null(precision, half, train):
+    f = _field(precision, half)
+    rays, z = (_dev(a) for a in _rays(40, 3, 120))
+    layers = (0, 1, 9) if train else ()                                  # the stored activations of the 2 x 64 model
+    want = ngp_query_into(f, rays, z, NAN_BYTES, train=train)            # nerf_ngp_query_fused_h
+    want_acts = [layer_into(f.mlp, "acts", l) for l in layers]
+    got = _query_lw_null(f, rays, z, train)
+    got_acts = [layer_into(f.mlp, "acts", l) for l in layers]
+    assert unwritten(want) == 0 and unwritten(got) == 0 and bits_equal(got, want)
+    for a, b in zip(got_acts, want_acts):
+        assert unwritten(a) == 0 and bits_equal(a, b)
+    assert bits_equal(f.query(rays, z, train=train, fused=True), want)   # HashNeRF.query with level_weights None: the same call
+
+
+def test_error_texts_name_the_entry_that_was_called():
+    """Codes and texts as the entries gave them before they shared their bodies."""
+    lib, s = N.lib(), N.stream()
+    res = (C.c_int * 4)(16, 16, 16, 16)
+    x = torch.zeros(8, 3, device=DEV)
+    t = torch.zeros(4, 16, 8, device=DEV)
+    out = torch.zeros(8, 64, device=DEV)
+    acc = torch.zeros(4, 16, 8, dtype=torch.int64, device=DEV)
+    rays, z = torch.zeros(2, 11, device=DEV), torch.zeros(2, 4, device=DEV)
+    X, T, O_, A, G, Rp, Z = (N.ptr(a) for a in (x, t, out, acc, out, rays, z))
+    E_UNSUP = -3
+    cases = [
+        (lambda: lib.nerf_hashgrid_forward(X, 8, T, 4, 4, 3, res, O_, s), b"nerf_hashgrid_forward: F must be 1, 2, 4 or 8"),
+        (lambda: lib.nerf_hashgrid_forward_lw(X, 8, T, 4, 4, 3, res, None, O_, s),
+         b"nerf_hashgrid_forward_lw: F must be 1, 2, 4 or 8"),
+        (lambda: lib.nerf_ngp_encode(Rp, Z, 2, 4, T, 4, 4, 3, res, 2, 1.0, 0.0, O_, None, s),
+         b"nerf_ngp_encode: F must be 1, 2, 4 or 8"),
+        (lambda: lib.nerf_ngp_encode_lw(Rp, Z, 2, 4, T, 4, 4, 3, res, None, 2, 1.0, 0.0, O_, None, s),
+         b"nerf_ngp_encode_lw: F must be 1, 2, 4 or 8"),
+        (lambda: lib.nerf_hashgrid_backward_ex(X, 8, G, 4, 4, 2, res, 0, 4, 2, A, s),
+         b"nerf_hashgrid_backward_ex: fixed_point must be 0 or 1"),
+        (lambda: lib.nerf_hashgrid_backward_ex_lw(X, 8, G, 4, 4, 2, res, None, 0, 4, 2, A, s),
+         b"nerf_hashgrid_backward_ex_lw: fixed_point must be 0 or 1"),
+        (lambda: lib.nerf_hashgrid_backward_rays_ex(Rp, Z, 2, 4, G, 4, 4, 2, res, 1.0, 0.0, 0, 4, 2, A, s),
+         b"nerf_hashgrid_backward_rays_ex: fixed_point must be 0 or 1"),
+        (lambda: lib.nerf_hashgrid_backward_rays_ex_lw(Rp, Z, 2, 4, G, 4, 4, 2, res, None, 1.0, 0.0, 0, 4, 2, A, s),
+         b"nerf_hashgrid_backward_rays_ex_lw: fixed_point must be 0 or 1"),
+    ]
+    for call, text in cases:
+        assert call() == E_UNSUP
+        assert lib.nerf_last_error() == text
