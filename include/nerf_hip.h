@@ -693,6 +693,48 @@ int nerf_morph_erode(const float* vol, int res, float iso, int radius, void* wor
 int nerf_morph_reconstruct(const float* vol, const float* kept, int res, float iso, int radius, void* workspace, float* out,
                            int64_t* stats2, void* stream);
 
+/* ---------------------------------------------------------------- TSDF fusion (no reference counterpart)
+ * Fuses rendered depth / opacity maps of posed pinhole cameras into a truncated signed distance volume on the lattice of "mesh
+ * extraction" (KinectFusion; nerfstudio's TSDF export), whose zero level set is the other mesh of a trained field: a voxel is
+ * inside only if the cameras agree a surface lies in front of it.  Additive: NERF_ABI_VERSION stays 3.  Lattice as above: box
+ * lo[3] < hi[3] (host floats, finite), 2 <= R <= NERF_MESH_MAX_RES, h_a = (hi_a - lo_a) / R on the host, point (i, j, k) has linear
+ * index p = i + R (j + R k) and position p_a = lo_a + ((float)i_a + 0.5f) * h_a.  Float32, one rounding per operation, in this
+ * order (divisions correctly rounded; tests/_tsdf_ref.py reproduces every output bit for bit):
+ *   state     D float32 [R^3], the running mean of the truncated distance in units of the truncation tau; Wt float32 [R^3], the
+ *             number of observations; flags uint8 [R^3], bit 0 = occluded in at least one view.  nerf_tsdf_reset zeroes all three.
+ *   view      nerf_tsdf_view, 16 floats: c2w [3, 4] row-major (r_ab = c2w[4 a + b], t_a = c2w[4 a + 3]; camera directions
+ *             [(col - cx) / fx, -(row - cy) / fy, -1] at integer pixel centres, as nerf_ray_gen), then fx, fy, cx, cy (the K doubles
+ *             cast once on the host); maps depth [H W] and acc [H W] as a renderer's aux outputs: depth = sum w z with z the
+ *             parameter of o + z d for the unnormalised d whose camera z is -1, so depth / acc is distance along the optical axis.
+ *   per voxel and view, with tau > 0, 0 < acc_min <= 1, far > 0, carve in {0, 1}:
+ *             q_a = p_a - t_a; x_c = (r00 q0 + r10 q1) + r20 q2, y_c with column 1, z_c with column 2; zc = 0.0f - z_c.
+ *             !(zc > 0): no observation (NaN included).  u = fx (x_c / zc) + cx; v = cy - fy (y_c / zc); fu = floorf(u + 0.5f),
+ *             fv = floorf(v + 0.5f); unless 0 <= fu < W and 0 <= fv < H (compared as floats: a non-finite or huge u, v fails here,
+ *             before any conversion): no observation.  i = (int)fu, j = (int)fv, a = acc[j W + i], s = depth[j W + i]; a or s NaN:
+ *             no observation.  a < acc_min: with carve and zc <= far the observation d = 1.0f (the ray hit nothing: empty all along
+ *             it), else none.  Otherwise e = s / a - zc; e < -tau: flags |= 1, no observation; e NaN: none; else
+ *             d = fminf(1.0f, e / tau).  On an observation: Wn = Wt + 1.0f; D = (D Wt + d) / Wn; Wt = Wn.
+ *   batch     nerf_tsdf_integrate folds n <= NERF_TSDF_MAX_VIEWS views (views_host: n structs on the host, passed by value as
+ *             kernel arguments; depth, acc: device [n, H W]) in order in ONE launch: one lane per voxel loads its state once, keeps
+ *             it in registers over the views and stores it once.  Bit-identical to n calls of one view in the same order.  n = 0
+ *             launches nothing.  No atomics, nothing read on the host, one writer per voxel: bit-reproducible.
+ *   finish    nerf_tsdf_volume: vol[p] = 0.0f - D[p] where Wt[p] >= (float)min_views (min_views >= 1); else +1.0f where flags bit 0
+ *             is set (seen only from behind a surface: inside -- without this every surface gets an inner twin at depth tau); else
+ *             -1.0f (never seen: outside).  vol is a volume of "mesh extraction" at iso = 0 (inside = D < 0): nerf_mesh_*, nerf_ccl_*
+ *             and nerf_morph_* run on it unchanged.
+ * Argument errors (R, box, n outside [0, 16], H, W outside [1, 2^24], non-positive or non-finite trunc / far, acc_min outside
+ * (0, 1], carve not 0 / 1, a non-finite camera number, min_views < 1, NULL) return before any launch.                          */
+#define NERF_TSDF_MAX_VIEWS 16
+typedef struct nerf_tsdf_view {
+  float c2w[12];
+  float fx, fy, cx, cy;
+} nerf_tsdf_view;
+int nerf_tsdf_reset(float* D, float* Wt, uint8_t* flags, int res, void* stream);
+int nerf_tsdf_integrate(float* D, float* Wt, uint8_t* flags, int res, const float* lo_host, const float* hi_host,
+                        const nerf_tsdf_view* views_host, int n, int H, int W, const float* depth, const float* acc, float trunc,
+                        float acc_min, float far, int carve, void* stream);
+int nerf_tsdf_volume(const float* D, const float* Wt, const uint8_t* flags, int res, int min_views, float* vol_out, void* stream);
+
 /* ---------------------------------------------------------------- fused renderer (a14 / a18)
  * replaces: rendering/render.py:164-241 render_rays_eval (coarse pass, importance sampling, sort, second pass)
  * as ONE call that enqueues the fixed kernel sequence on `stream`: nerf_sample_coarse -> nerf_query_fused ->

@@ -107,6 +107,10 @@ SIGNATURES = {
     "nerf_morph_workspace_bytes": (_I64, [_I]),
     "nerf_morph_erode": (_I, [_P, _I, _F, _I, _P, _P, _P, _P]),
     "nerf_morph_reconstruct": (_I, [_P, _P, _I, _F, _I, _P, _P, _P, _P]),
+    "nerf_tsdf_reset": (_I, [_P, _P, _P, _I, _P]),
+    "nerf_tsdf_integrate": (_I, [_P, _P, _P, _I, C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_float), _I, _I, _I, _P, _P,
+                                _F, _F, _F, _I, _P]),
+    "nerf_tsdf_volume": (_I, [_P, _P, _P, _I, _I, _P, _P]),
 }
 
 

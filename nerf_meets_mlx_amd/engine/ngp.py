@@ -19,6 +19,7 @@ import ctypes as C
 import os
 from typing import Dict, Optional
 
+import numpy as np
 import torch
 
 from .. import _native as N
@@ -26,7 +27,7 @@ from .. import parallel, sampling
 from ..encoding.multi_hash import MultiHashEncoding
 from ..encoding.spherical_harmonics import SphericalHarmonicsEncoding
 from ..models.NeRF import Adam, NeRF
-from ..rendering import render
+from ..rendering import ray, render
 from .trainer import Trainer
 
 
@@ -448,6 +449,52 @@ class NGPTrainer(Trainer):
         if b is None:
             raise ValueError("NGPTrainer mesh export: the field has no scene box (bound=None), pass aabb=(lo, hi)")
         return [-float(b)] * 3, [float(b)] * 3
+
+    def render_depth(self, c2w):
+        """(depth [H, W], acc [H, W]) of the full frame at pose c2w: the "depth" (sum w z, not normalised; depth / acc is distance
+        along the optical axis) and "acc" of render_rays(aux=True), in every hash-grid mode.  This rank only, no collective."""
+        c = np.asarray(c2w.detach().cpu().numpy() if torch.is_tensor(c2w) else c2w)[:3, :4]
+        idx = torch.arange(0, self.H * self.W, device=self.device, dtype=torch.int64)
+        rays = ray.gen_rays(self.H, self.W, self.K, c, self.near, self.far, idx)
+        o = self.render_rays(rays, aux=True)
+        return o["depth"].reshape(self.H, self.W), o["acc"].reshape(self.H, self.W)
+
+    def extract_mesh_tsdf(self, resolution: int = 256, aabb=None, poses=None, trunc=None, acc_min: float = 0.5, carve: bool = True,
+                          min_views: int = 1, colors: bool = True, min_component: int = 0, largest_only: bool = False,
+                          opening_radius: int = 0):
+        """engine.mesh.Mesh of the zero level set of a TSDF fused from this field's own depth renders (DESIGN.md section 21;
+        KinectFusion, nerfstudio's TSDF export): render_depth at every pose of `poses` ([n, 3 or 4, 4]; None: the training
+        poses), engine.mesh.TSDFVolume(resolution, box, trunc).integrate with far = the trainer's far, volume(min_views), the
+        component filter or the opening of extract_mesh at iso 0, marching cubes at 0, and vertex colours (when `colors`) from
+        the field queried at each vertex along -normal.  A voxel is inside only if the cameras agree a surface lies in front of
+        it; a ray with opacity below `acc_min` carves (with `carve`) every voxel along it.  trunc=None: 4 voxels
+        (TSDFVolume).  The order of `poses` is the fusion order and fixes the bits of the result: the running mean is a
+        float32 recurrence, so another order may differ in the last place.  Runs on this rank only, no collective."""
+        from . import mesh
+        lo, hi = self._mesh_box(aabb)
+        R = mesh.check_mesh_args(resolution, lo, hi, 0.0)[0]
+        mesh.check_component_args(min_component, largest_only, R)
+        mesh.check_opening_args(opening_radius)
+        mesh.check_tsdf_args(trunc, acc_min, self.far, carve, min_views, self.H, self.W)
+        poses = self.poses if poses is None else poses
+        views = mesh.tsdf_views(poses, self.K)
+        tsdf = mesh.TSDFVolume(R, lo, hi, trunc=trunc, device=self.device)
+        c2ws = views[:, :12].reshape(-1, 3, 4)
+        for s in range(0, len(c2ws), mesh.TSDF_MAX_VIEWS):
+            batch = c2ws[s:s + mesh.TSDF_MAX_VIEWS]
+            maps = [self.render_depth(c) for c in batch]
+            tsdf.integrate(torch.stack([m[0] for m in maps]), torch.stack([m[1] for m in maps]), batch, self.K, self.H, self.W,
+                           acc_min=acc_min, far=self.far, carve=carve)
+        vol = tsdf.volume(min_views)
+        del tsdf
+        if opening_radius > 0:
+            vol = mesh.open_components(vol, 0.0, opening_radius, min_component, largest_only)
+        elif min_component > 1 or largest_only:
+            vol = mesh.filter_components(vol, 0.0, min_component, largest_only)
+        m, rows = mesh._marching_cubes(vol, 0.0, lo, hi, colors)
+        if not colors:
+            return m
+        return m._replace(colors=mesh.vertex_colors(self._mesh_field()[0], rows))
 
     def train_step(self, rays=None, target=None, u=None, background=None) -> Dict[str, torch.Tensor]:
         """background (random_background trainers only, with explicit rays and target [B, 4]): the colours bg [B, 3] behind the

@@ -20,6 +20,11 @@ filter of the core -> reconstruct) -- its four stats (inside, core, seed and rec
 and the largest one's share, V, F, the geometry figures, and the device ms of the erode call, of the labelling of the core
 (label, sizes, filter) and of the reconstruct call.
 
+With --tsdf, one more line per R: the other export -- depth / opacity renders of the first --tsdf-views
+training poses (default: all), fused into a TSDF (engine.mesh.TSDFVolume, --tsdf-trunc, --tsdf-acc-min), meshed at 0 -- with V,
+F and the same geometry figures, the mean opacity of the rendered maps, and the device ms of the renders, the integrate
+launches, the finish and marching cubes.
+
     rocprofv3 --kernel-trace --output-format csv -d DIR -o mesh -- python tools/ngp_mesh.py --ckpt /tmp/ngp.npz --reps 1 --no-ply
     python tools/ngp_mesh.py --stats DIR/.../mesh_kernel_trace.csv --from profiles/ngp_mesh.jsonl --out profiles/ngp_mesh_kernels.jsonl
 
@@ -148,6 +153,41 @@ def _opening_timed(vol, iso, radius, min_component, largest_only):
             est.tolist() + rst.tolist())
 
 
+def _tsdf_arm(tr, mesh, R, lo, hi, a, rec, bound, boxes):
+    """The TSDF export of the same field as its stages, each between device events (the last of --reps runs is kept)."""
+    poses = tr.poses if a.tsdf_views is None else tr.poses[:a.tsdf_views]
+    t_ren, t_int, t_fin, t_mc = [], [], [], []
+    for _ in range(a.reps):
+        e = [torch.cuda.Event(enable_timing=True) for _ in range(5)]
+        tsdf = mesh.TSDFVolume(R, lo, hi, trunc=a.tsdf_trunc, device=tr.device)
+        e[0].record()
+        maps = [tr.render_depth(p) for p in poses]
+        depth, acc = torch.stack([m[0] for m in maps]), torch.stack([m[1] for m in maps])
+        e[1].record()
+        tsdf.integrate(depth, acc, poses, tr.K, tr.H, tr.W, acc_min=a.tsdf_acc_min, far=tr.far, carve=True)
+        e[2].record()
+        vol = tsdf.volume(1)
+        e[3].record()
+        m = mesh.marching_cubes(vol, 0.0, lo, hi)
+        e[4].record()
+        torch.cuda.synchronize()
+        for k, t in enumerate((t_ren, t_int, t_fin, t_mc)):
+            t.append(e[k].elapsed_time(e[k + 1]))
+    out = {"tool": "ngp_mesh tsdf", "R": R, "hw": a.hw, "iters": tr.it, "march_steps": a.march_steps, "seed": rec["seed"],
+           "distortion_weight": a.dist_weight, "random_background": bool(a.random_bg), "views": int(len(poses)),
+           "trunc": tsdf.trunc, "acc_min": a.tsdf_acc_min, "far": tr.far, "mean_acc": float(acc.mean()),
+           "pixels_above_acc_min": float((acc >= a.tsdf_acc_min).float().mean()),
+           "observed_voxels": int((tsdf.Wt > 0).sum()), "occluded_voxels": int((tsdf.flags & 1).sum()),
+           "inside_voxels": int((vol > 0).sum()), "V": int(m.verts.shape[0]), "F": int(m.faces.shape[0]),
+           "V_density": rec["V"], "geometry": _geometry(m.verts, R, bound, boxes), "geometry_density": rec["geometry"],
+           "render_ms": float(np.mean(t_ren)), "integrate_ms": float(np.mean(t_int)), "finish_ms": float(np.mean(t_fin)),
+           "marching_cubes_ms": float(np.mean(t_mc)), "integrate_launches": -(-len(poses) // mesh.TSDF_MAX_VIEWS),
+           "state_MB": R ** 3 * 9 / 1e6, "device": rec["device"]}
+    del tsdf, vol, m, maps, depth, acc
+    torch.cuda.empty_cache()
+    return out
+
+
 def _teacher_volume(R, lo, hi, dev):
     from nerf_meets_mlx_amd.dataset import synthetic
     from nerf_meets_mlx_amd.engine import mesh
@@ -197,6 +237,10 @@ def main():
     ap.add_argument("--opening-radius", type=int, action="append", default=None,
                     help="also mesh each filtered arm after an opening of this radius (DESIGN.md section 18); repeatable: one "
                          "JSON line per arm and radius > 0")
+    ap.add_argument("--tsdf", action="store_true", help="also mesh the TSDF fused from depth renders (DESIGN.md section 21)")
+    ap.add_argument("--tsdf-trunc", type=float, default=None, help="truncation in world units (default: 4 voxels)")
+    ap.add_argument("--tsdf-acc-min", type=float, default=0.5, help="a ray with less opacity carves instead of observing a surface")
+    ap.add_argument("--tsdf-views", type=int, default=None, help="fuse the first N training poses (default: all)")
     ap.add_argument("--ckpt", default=None, help="load this checkpoint instead of training")
     ap.add_argument("--save-ckpt", default=None, help="save the trained state here")
     ap.add_argument("--out", default=None, help="append the JSON lines to this file")
@@ -205,6 +249,8 @@ def main():
     a = ap.parse_args()
     if a.stats:
         return stats(a)
+    if a.tsdf_views is not None and a.tsdf_views < 1:
+        ap.error("--tsdf-views must be at least 1")
     from nerf_meets_mlx_amd.dataset import synthetic
     from nerf_meets_mlx_amd.engine import mesh
     from nerf_meets_mlx_amd.engine.ngp import NGPTrainer, level_anneal_from_text
@@ -214,6 +260,8 @@ def main():
     H = W = a.hw
     if a.ckpt:
         imgs, poses, K = torch.zeros(1, 8, 8, 4 if a.random_bg else 3), synthetic.train_poses(1), synthetic.intrinsics(8, 8)[0]
+        if a.tsdf:                                           # the depth renders need the training cameras at full size
+            imgs, poses, K = torch.zeros(1, H, W, imgs.shape[-1]), synthetic.train_poses(5)[:4], synthetic.intrinsics(H, W)[0]
     else:
         imgs, poses, _, _, K = synthetic.make_dataset(H, W, 5, seed=0, device=dev, rgba=a.random_bg)
         imgs, poses = imgs[:4], poses[:4]
@@ -268,6 +316,10 @@ def main():
         torch.cuda.empty_cache()
         print(json.dumps(rec), flush=True)
         lines.append(rec)
+        if a.tsdf:
+            trec = _tsdf_arm(tr, mesh, R, lo, hi, a, rec, bound, boxes)
+            print(json.dumps(trec), flush=True)
+            lines.append(trec)
         arms = a.min_component if a.min_component else ([0] if a.largest_only else [])
         for m_min in arms:
             vol = mesh.density_volume(query, act, R, lo, hi, device=dev)
@@ -351,7 +403,9 @@ def _bytes(kernel, R, V, F):
             # R % 64 == 0
             "morph_pack_kernel": 4 * n3 + n3 // 8, "morph_pack_kernel<seeds>": 8 * n3 + n3 // 4,
             "morph_apply_kernel": 8 * n3 + n3 // 4, "morph_step_kernel": n3 // 4,
-            "morph_step_kernel<dilate>": 3 * n3 // 8}.get(kernel)
+            "morph_step_kernel<dilate>": 3 * n3 // 8,
+            # csrc/tsdf.hip: the state read and written (the maps are L2-resident gathers); the finish reads it and writes the volume
+            "tsdf_integrate_kernel": 18 * n3, "tsdf_volume_kernel": 13 * n3, "tsdf_reset_kernel": 9 * n3}.get(kernel)
 
 
 def _morph_grid(kernel, R):
@@ -367,13 +421,15 @@ def _morph_grid(kernel, R):
 def stats(a):
     """Per mesh kernel and lattice size: mean device time per launch from a rocprofv3 --kernel-trace CSV, bytes / time."""
     import re
-    runs = {}
+    runs, tsdf_runs = {}, {}
     if a.from_:
         with open(a.from_) as fh:
             for ln in fh:
                 r = json.loads(ln)
                 if r.get("tool") == "ngp_mesh":
                     runs[r["R"]] = r
+                elif r.get("tool") == "ngp_mesh tsdf":
+                    tsdf_runs[r["R"]] = r
     with open(a.stats) as fh:
         rows = list(csv.DictReader(fh))
     col = {k.lower(): k for k in rows[0]} if rows else {}
@@ -382,7 +438,7 @@ def stats(a):
     gx = col.get("grid_size_x", col.get("grid_size"))
     groups = {}
     for r in rows:
-        m = re.search(r"(mesh_\w+_kernel|ccl_\w+_kernel|morph_\w+_kernel|occ_cull_scan_kernel|occ_merge_exp_kernel)", r[name_k])
+        m = re.search(r"(mesh_\w+_kernel|ccl_\w+_kernel|morph_\w+_kernel|tsdf_\w+_kernel|occ_cull_scan_kernel|occ_merge_exp_kernel)", r[name_k])
         if not m:
             continue
         k = m.group(1)
@@ -404,6 +460,8 @@ def stats(a):
     for (k, R), us in sorted(groups.items(), key=lambda t: (t[0][0], t[0][1] or 0)):
         rec = {"tool": "ngp_mesh --stats (rocprofv3 --kernel-trace)", "kernel": k, "R": R, "launches": len(us),
                "avg_us": round(float(np.mean(us)), 2), "median_us": round(float(np.median(us)), 2)}
+        if k == "tsdf_integrate_kernel" and R in tsdf_runs:
+            rec.update({"views": tsdf_runs[R]["views"], "hw": tsdf_runs[R]["hw"]})
         if R is not None and R in runs:
             b = _bytes(k, R, runs[R]["V"], runs[R]["F"])
             if b:
