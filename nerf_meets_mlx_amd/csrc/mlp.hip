@@ -28,13 +28,10 @@
 #include "mlp_arch2.h"
 #include "hash_common.h"
 #include "mlp_params.h"
-#include "mlp32.h"
-#include "mlp22.h"
-#include "mlp_s16.h"
-#include "mlp_s16x.h"
+#include "mlp_model.h"
+#include "dw_split.h"
+#include <limits.h>
 #include <string.h>
-#include <mutex>
-#include <unordered_map>
 
 
 namespace nerf {
@@ -1546,39 +1543,24 @@ static int g_dw_ring_cap = 8;  // "dw_ring_cap": most stages the 16-wave split-b
 static int g_dw_private = 4;   // "dw_private_tiles": split-bf16 dW jobs of at most this many output tiles run as sixteen wave-private pipelines (0 = off)
 static int g_dw16_variant = 1;  // "dw16_variant": bf16 weight gradients: 1 (default) = 256 x 256 jobs on mlp_dww.hip's kernel, tiny-job lists on mlp_s16.hip's, the rest on mlp_dw_kernel; 0 = every job on mlp_dw_kernel; 2 = as 1 without the tiny-job rule; 3 = as 1 with mlp_s16.hip's kernel for every narrow job
 static int g_dw_narrow_first = 1;   // "dw_narrow_first": order of the two weight-gradient launches (A/B knob; same gradients either way)
-static int g_dw_job_mask = 0;  // diagnostic: nonzero = run only these dW jobs (bit j)
-static int g_tile_pad16 = 0;     // extra 16-byte units between sample tiles of the fragment stores
-static inline int64_t astride16() { return (int64_t)L::A_SLOTS * 64 + g_tile_pad16; }
-static inline int64_t zstride16() { return (int64_t)L::Z_SLOTS * 64 + g_tile_pad16; }
+static int g_dw_job_mask = 0;  // diagnostic: nonzero = run only these dW jobs (bit j); view model only
+// (g_tile_pad16, "tile_pad16": mlp_model.h, beside the strides it enters)
 static int g_mlp_variant = 0;   // 0: auto, 1: ST=1 via L1, 2: ST=2 via L1, 3: LDS ring, 8 waves x 32 samples, 32x32x16 MFMA,
                                 // 4: ring, 16x16x32 MFMA, 8 waves x 32 samples (inference only), 5: same, 4 waves x 64 samples
 static int g_ring_wgs = 0;       // persistent workgroups of the ring kernels; 0 = one per CU of the current device
 static int g_ngp_ray_major = 1;   // A/B knob: fused configs[4] inference query walks (32 rays x 1 depth) tiles (1) or (1 ray x 32 depths) tiles (0)
 int g_pass_queue = 1;               // "pass_queue": 1 (default) the persistent ring kernels take their passes from a device-wide counter (mlp_ring.h), 0 = static split
 static int g_ring_split = 1;     // training ring kernels: 1 = one 8-wave workgroup per CU (128 KiB ring), 2 = two 4-wave workgroups (64 KiB rings)
-// precision of a model = nerf_mlp_arch.precision (ABI 3): 16 (or 0) bf16 MFMA operands with fp32 accumulate, 32 the fp32
-// reference-precision kernels of mlp32.hip.  Nothing process-wide: two models of different precision can be packed,
-// queried and trained side by side on any streams.
-// 22 = the reference-tolerance mode on the 16-bit matrix pipe: split-fp16 inference (mlp22.hip: float32-class accuracy at
-// 1/3 of the fp16 matrix rate) and split-bf16 training (mlp_s16.hip: training forward, dZ chain, dW at 1/3 of the bf16 rate);
-// such a model carries the bf16 image (its fp32 bias slots are shared), the split-fp16 and the split-bf16 streams.
-static inline int arch_prec(const nerf_mlp_arch* a) { return a->precision == 32 ? 32 : a->precision == 22 ? 22 : 16; }
-static inline bool arch_f32(const nerf_mlp_arch* a) { return a->precision == 32; }                          // trains on mlp32.hip
-static inline bool arch_s16(const nerf_mlp_arch* a) { return a->precision == 22; }                          // trains on mlp_s16.hip
-// CUs of the current device (256 on an MI355X in SPX mode), asked once: the persistent kernels and the dW split are
-// sized to it instead of to a constant
-// Per-device state: the CU count and the "dynamic LDS attribute set" flags belong to the CURRENT device (a process may
-// move between devices with hipSetDevice; hipFuncSetAttribute applies to the device that is current when it is called).
-constexpr int MAX_DEVICES = 64;
-static int cur_device() {
-  int d = 0;
-  if (hipGetDevice(&d) != hipSuccess || d < 0 || d >= MAX_DEVICES) d = 0;
-  return d;
-}
-// (DevOnce -- thread-safe per-device one-time set-up: common.h)
+
+// Per-device state.  The CU count (256 on an MI355X in SPX mode; the persistent kernels and the dW split are sized to it instead
+// of to a constant) is asked once per device, and the one-time opt-in of a kernel to dynamic LDS above 64 KiB goes through DevOnce
+// (common.h): both belong to the CURRENT device -- a process may move between devices with hipSetDevice, and
+// hipFuncSetAttribute applies to the device that is current when it is called.
 static int cu_count() {
+  constexpr int MAX_DEVICES = 64;
   static int n[MAX_DEVICES] = {};
-  const int dev = cur_device();
+  int dev = 0;
+  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= MAX_DEVICES) dev = 0;
   if (n[dev] == 0) {
     int v = 0;
     n[dev] = (hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && v > 0) ? v : 256;
@@ -1586,39 +1568,38 @@ static int cu_count() {
   return n[dev];
 }
 static inline int ring_wgs() { return g_ring_wgs > 0 ? g_ring_wgs : cu_count(); }
+// grid of a persistent kernel: one workgroup per super-tile, at most `wgs`
+static inline unsigned persistent_grid(int64_t nsuper, int64_t wgs = ring_wgs()) { return (unsigned)(nsuper < wgs ? nsuper : wgs); }
 
 template <class K>
 static void ensure_lds(K kernel, int bytes) {
   (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
 }
 
-// 0: the NeRF view model (63+27 -> 4), 1: the image-fitting model (40 -> out_ch), 2: the Instant-NGP-sized view
-// model (32+16 -> 4, 2 x 64), -1: no HIP kernel
-static int arch_kind(const nerf_mlp_arch* a) {
-  if (!a) return -1;
-  if (a->precision != 0 && a->precision != 16 && a->precision != 32 && a->precision != 22) return -1;
-  if (arch_f32(a) && !(a->n_layers == 8 && a->width == 256)) return -1;   // fp32 MFMA kernels: the 8 x 256 models (view head or image)
-  if (a->n_layers == 2 && a->width == 64 && a->skip_layer < 0 && a->use_viewdirs == 1 && a->in_pos == 32 && a->in_dir == 16) return 2;
-  if (a->n_layers != 8 || a->width != 256 || a->skip_layer != 4) return -1;
-  if (a->use_viewdirs == 1 && a->in_pos == 63 && a->in_dir == 27) return 0;
-  if (a->use_viewdirs == 0 && a->in_pos == 40 && a->out_ch >= 1 && a->out_ch <= 4) return 1;
-  return -1;
-}
-static bool arch_ok(const nerf_mlp_arch* a) { return arch_kind(a) == 0; }
-static inline int64_t img_astride16(bool split = false) { return (int64_t)(split ? s16x::IMG_A_SLOTS : LI::A_SLOTS) * 64 + g_tile_pad16; }
-static inline int64_t img_zstride16(bool split = false) { return (int64_t)(split ? s16x::IMG_Z_SLOTS : LI::Z_SLOTS) * 64 + g_tile_pad16; }
-static inline int64_t img_params(const nerf_mlp_arch* a) { return LI::P_WO + (int64_t)a->out_ch * 257; }
-static inline int64_t small_astride16(bool split = false) { return (int64_t)(split ? s16x::SM_A_SLOTS : LN::A_SLOTS) * 64 + g_tile_pad16; }
-static inline int64_t small_zstride16(bool split = false) { return (int64_t)(split ? s16x::SM_Z_SLOTS : LN::Z_SLOTS) * 64 + g_tile_pad16; }
-// bf16 images of the image-fitting / 2 x 64 models (a precision-22 model carries its split-bf16 pair streams behind them and
-// shares their fp32 bias slots)
-constexpr int64_t IMG_BF16_BYTES = (int64_t)(LI::F_TOTAL + LI::B_PADDED) * 1024 + LI::BI_TOTAL * 4;
-static inline const float* img_bias_of(const void* packed) {
-  return reinterpret_cast<const float*>(static_cast<const char*>(packed) + (size_t)(LI::F_TOTAL + LI::B_PADDED) * 1024);
-}
-static inline const float* small_bias_of(const void* packed) {
-  return reinterpret_cast<const float*>(static_cast<const char*>(packed) + (size_t)(LN::F_PADDED + LN::B_PADDED) * 1024);
-}
+// nerf_set_option / nerf_get_option: one row per key.  rule(v) clamps or normalises the value in place; false = refused with `refusal`.
+struct Option { const char* key; int* var; bool (*rule)(int& v); const char* refusal; };
+static bool opt_any(int&) { return true; }
+static bool opt_flag(int& v) { v = v ? 1 : 0; return true; }
+template <int LO, int HI> static bool opt_clamp(int& v) { v = v < LO ? LO : v > HI ? HI : v; return true; }
+static const Option OPTIONS[] = {
+    {"mlp_variant", &g_mlp_variant, opt_any, nullptr},
+    {"ring_split", &g_ring_split, [](int& v) { return v == 1 || v == 2; }, "nerf_set_option: ring_split must be 1 or 2"},
+    {"ring_workgroups", &g_ring_wgs, opt_clamp<0, INT_MAX>, nullptr},
+    {"tile_pad16", &g_tile_pad16, opt_clamp<0, INT_MAX>, nullptr},
+    {"dw_workgroups", &g_dw_wgs, opt_clamp<0, INT_MAX>, nullptr},
+    {"dw_unit_bias", &g_dw_bias, opt_clamp<-1, INT_MAX>, nullptr},        // -1 = automatic (a legitimate value: unknown keys are INT_MIN)
+    {"bwd_stage", &g_bwd_stage, opt_any, nullptr},
+    {"dw_job_mask", &g_dw_job_mask, opt_any, nullptr},
+    {"hash_combine_max_res", &g_hash_combine_max_res, opt_clamp<0, INT_MAX>, nullptr},
+    {"ngp_ray_major", &g_ngp_ray_major, opt_flag, nullptr},
+    {"dw22_variant", &s16::g_dw_variant, opt_flag, nullptr},
+    {"dw16_variant", &g_dw16_variant, opt_clamp<0, 3>, nullptr},
+    {"dw_private_tiles", &g_dw_private, opt_clamp<0, 4>, nullptr},
+    {"dw_ring_cap", &g_dw_ring_cap, opt_clamp<2, 16>, nullptr},
+    {"pass_queue", &g_pass_queue, opt_flag, nullptr},
+    {"dw_narrow_first", &g_dw_narrow_first, opt_flag, nullptr},
+    {"f22_tiles", &f22::g_tiles, [](int& v) { return v == 0 || v == 2 || v == 3; }, "nerf_set_option: f22_tiles must be 0 (automatic), 2 or 3"},
+};
 
 }  // namespace nerf
 
@@ -1626,31 +1607,12 @@ using namespace nerf;
 
 extern "C" int nerf_set_option(const char* key, int value) {
   NERF_REQUIRE(key, NERF_E_NULL, "nerf_set_option: key is NULL");
-  if (!strcmp(key, "mlp_variant")) { g_mlp_variant = value; return NERF_OK; }
-  if (!strcmp(key, "ring_split")) {
-    NERF_REQUIRE(value == 1 || value == 2, NERF_E_UNSUPPORTED, "nerf_set_option: ring_split must be 1 or 2");
-    g_ring_split = value;
-    return NERF_OK;
-  }
   NERF_REQUIRE(strcmp(key, "mlp_precision") != 0, NERF_E_UNSUPPORTED,
                "nerf_set_option: \"mlp_precision\" is gone (ABI 3): set nerf_mlp_arch.precision of the model instead");
-  if (!strcmp(key, "ring_workgroups")) { g_ring_wgs = value > 0 ? value : 0; return NERF_OK; }
-  if (!strcmp(key, "tile_pad16")) { g_tile_pad16 = value >= 0 ? value : 0; return NERF_OK; }
-  if (!strcmp(key, "dw_workgroups")) { g_dw_wgs = value > 0 ? value : 0; return NERF_OK; }
-  if (!strcmp(key, "dw_unit_bias")) { g_dw_bias = value >= 0 ? value : -1; return NERF_OK; }
-  if (!strcmp(key, "bwd_stage")) { g_bwd_stage = value; return NERF_OK; }
-  if (!strcmp(key, "dw_job_mask")) { g_dw_job_mask = value; return NERF_OK; }
-  if (!strcmp(key, "hash_combine_max_res")) { g_hash_combine_max_res = value > 0 ? value : 0; return NERF_OK; }
-  if (!strcmp(key, "ngp_ray_major")) { g_ngp_ray_major = value ? 1 : 0; return NERF_OK; }
-  if (!strcmp(key, "dw22_variant")) { s16::g_dw_variant = value == 0 ? 0 : 1; return NERF_OK; }
-  if (!strcmp(key, "dw16_variant")) { g_dw16_variant = value < 0 ? 0 : value > 3 ? 3 : value; return NERF_OK; }
-  if (!strcmp(key, "dw_private_tiles")) { g_dw_private = value < 0 ? 0 : value > 4 ? 4 : value; return NERF_OK; }
-  if (!strcmp(key, "dw_ring_cap")) { g_dw_ring_cap = value < 2 ? 2 : value > 16 ? 16 : value; return NERF_OK; }
-  if (!strcmp(key, "pass_queue")) { g_pass_queue = value ? 1 : 0; return NERF_OK; }
-  if (!strcmp(key, "dw_narrow_first")) { g_dw_narrow_first = value ? 1 : 0; return NERF_OK; }
-  if (!strcmp(key, "f22_tiles")) {
-    NERF_REQUIRE(value == 0 || value == 2 || value == 3, NERF_E_UNSUPPORTED, "nerf_set_option: f22_tiles must be 0 (automatic), 2 or 3");
-    f22::g_tiles = value;
+  for (const Option& o : OPTIONS) {
+    if (strcmp(key, o.key)) continue;
+    if (!o.rule(value)) return fail(NERF_E_UNSUPPORTED, "%s", o.refusal);
+    *o.var = value;
     return NERF_OK;
   }
   return fail(NERF_E_UNSUPPORTED, "nerf_set_option: unknown key '%s'", key);
@@ -1658,104 +1620,49 @@ extern "C" int nerf_set_option(const char* key, int value) {
 
 extern "C" int nerf_get_option(const char* key) {
   if (!key) return NERF_OPTION_UNKNOWN;
-  if (!strcmp(key, "mlp_variant")) return g_mlp_variant;
-  if (!strcmp(key, "ring_workgroups")) return g_ring_wgs;
-  if (!strcmp(key, "ring_split")) return g_ring_split;
-  if (!strcmp(key, "dw_workgroups")) return g_dw_wgs;
-  if (!strcmp(key, "hash_combine_max_res")) return g_hash_combine_max_res;
-  if (!strcmp(key, "ngp_ray_major")) return g_ngp_ray_major;
-  if (!strcmp(key, "dw22_variant")) return s16::g_dw_variant;
-  if (!strcmp(key, "dw16_variant")) return g_dw16_variant;
-  if (!strcmp(key, "tile_pad16")) return g_tile_pad16;
-  if (!strcmp(key, "dw_unit_bias")) return g_dw_bias;            // -1 = automatic (a legitimate value: unknown keys are INT_MIN)
-  if (!strcmp(key, "bwd_stage")) return g_bwd_stage;
-  if (!strcmp(key, "dw_job_mask")) return g_dw_job_mask;
-  if (!strcmp(key, "dw_private_tiles")) return g_dw_private;
-  if (!strcmp(key, "dw_ring_cap")) return g_dw_ring_cap;
-  if (!strcmp(key, "pass_queue")) return g_pass_queue;
-  if (!strcmp(key, "dw_narrow_first")) return g_dw_narrow_first;
-  if (!strcmp(key, "f22_tiles")) return f22::g_tiles;
+  for (const Option& o : OPTIONS)
+    if (!strcmp(key, o.key)) return *o.var;
   return NERF_OPTION_UNKNOWN;
 }
 
-extern "C" int64_t nerf_mlp_param_count(const nerf_mlp_arch* arch) {
-  const int k = arch_kind(arch);
-  return k == 0 ? L::P_TOTAL : k == 1 ? img_params(arch) : k == 2 ? LN::P_TOTAL : -1;
-}
-extern "C" int64_t nerf_mlp_packed_bytes(const nerf_mlp_arch* arch) {
-  const int k = arch_kind(arch);
-  // an fp32 (precision 32) 8 x 256 view model carries its fp32 streams behind the bf16 image
-  // ... and a precision-22 model its split-fp16 stream behind that
-  return k == 0 ? L::PACKED_BYTES + (arch_f32(arch) ? f32::PACKED_BYTES : 0) + (arch_s16(arch) ? f22::PACKED_BYTES + s16::PACKED_BYTES : 0)
-         : k == 1 ? IMG_BF16_BYTES + (arch_s16(arch) ? s16x::IMG_PACKED_BYTES : 0) + (arch_f32(arch) ? f32::PACKED_BYTES : 0)
-         : k == 2 ? LN::PACKED_BYTES + (arch_s16(arch) ? s16x::SM_PACKED_BYTES : 0) : -1;
-}
-static inline const void* packed32_of(const void* packed) { return static_cast<const char*>(packed) + L::PACKED_BYTES; }
-static inline const void* packed22_of(const void* packed) { return static_cast<const char*>(packed) + L::PACKED_BYTES; }
-static inline const void* packed_s16_of(const void* packed) { return static_cast<const char*>(packed) + L::PACKED_BYTES + f22::PACKED_BYTES; }
-static inline const float* bias_slots_of(const void* packed) {
-  return reinterpret_cast<const float*>(static_cast<const char*>(packed) + (size_t)(L::F_TOTAL + L::B_PADDED) * 1024);
-}
-static inline int64_t s16_astride16() { return (int64_t)s16::A_SLOTS * 64 + g_tile_pad16; }
-static inline int64_t s16_zstride16() { return (int64_t)s16::Z_SLOTS * 64 + g_tile_pad16; }
-static inline int64_t padded_tiles(int64_t M) { return (((M + 31) / 32) + 7) / 8 * 8; }
-extern "C" int64_t nerf_mlp_acts_bytes(const nerf_mlp_arch* arch, int64_t M) {
-  const int k = arch_kind(arch);
-  if (k < 0 || M < 0) return -1;
-  const bool sp = arch_s16(arch);
-  const int64_t b16 = padded_tiles(M) * (k == 0 ? astride16() : k == 1 ? img_astride16(sp) : small_astride16(sp)) * 16;
-  if (k == 0 && arch_s16(arch)) return padded_tiles(M) * s16_astride16() * 16;
-  return (k <= 1 && arch_f32(arch)) ? f32::acts_bytes(M) : b16;
-}
-extern "C" int64_t nerf_mlp_dz_bytes(const nerf_mlp_arch* arch, int64_t M) {
-  const int k = arch_kind(arch);
-  if (k < 0 || M < 0) return -1;
-  const bool sp = arch_s16(arch);
-  const int64_t b16 = padded_tiles(M) * (k == 0 ? zstride16() : k == 1 ? img_zstride16(sp) : small_zstride16(sp)) * 16
-                      + DW_PARTIAL_BYTES;                 // + the split-K partial tiles of the weight-gradient kernel
-  if (k == 0 && arch_s16(arch)) return padded_tiles(M) * s16_zstride16() * 16 + DW_PARTIAL_BYTES;
-  return (k <= 1 && arch_f32(arch)) ? f32::dz_bytes(M) : b16;
-}
+extern "C" int64_t nerf_mlp_param_count(const nerf_mlp_arch* arch) { return resolve(arch).params; }
+extern "C" int64_t nerf_mlp_packed_bytes(const nerf_mlp_arch* arch) { return resolve(arch).packed_bytes; }
+extern "C" int64_t nerf_mlp_acts_bytes(const nerf_mlp_arch* arch, int64_t M) { return resolve(arch).acts_bytes(M); }
+extern "C" int64_t nerf_mlp_dz_bytes(const nerf_mlp_arch* arch, int64_t M) { return resolve(arch).dz_bytes(M); }
 
 #define NERF_ARCH_MSG ": HIP kernels exist for (8x256, skip 4) with in=63+27 view head, or in=40 / no view head / out_ch<=4, and for (2x64, no skip) with in=32+16 view head"
-#define NERF_ARCH_CHECK(who) NERF_REQUIRE(arch_ok(arch), NERF_E_UNSUPPORTED, who NERF_ARCH_MSG)
-#define NERF_ARCH_CHECK_ANY(who) NERF_REQUIRE(arch_kind(arch) >= 0, NERF_E_UNSUPPORTED, who NERF_ARCH_MSG)
+// declares `m`, the description of `arch`, or returns NERF_E_UNSUPPORTED
+#define NERF_RESOLVE(who)        \
+  const Model m = resolve(arch); \
+  NERF_REQUIRE(m.ok, NERF_E_UNSUPPORTED, who NERF_ARCH_MSG)
 
 extern "C" int nerf_mlp_pack(const nerf_mlp_arch* arch, const float* params, void* packed, void* stream) {
-  NERF_ARCH_CHECK_ANY("nerf_mlp_pack");
+  NERF_RESOLVE("nerf_mlp_pack");
   NERF_REQUIRE(params && packed, NERF_E_NULL, "nerf_mlp_pack: params/packed is NULL");
-  char* base = static_cast<char*>(packed);
-  if (arch_kind(arch) == 2) {
+  auto s = as_stream(stream);
+  bf16x8* wf = m.stream<bf16x8>(packed, S_FWD);
+  bf16x8* wb = m.stream<bf16x8>(packed, S_BWD);
+  float* bias = m.stream<float>(packed, S_BIAS);
+  int rc;
+  if (m.shape == Shape::Small) {
     const int tot = (LN::F_PADDED + LN::B_PADDED) * 64 + LN::BI_TOTAL;
-    hipLaunchKernelGGL(pack_small_kernel, dim3((tot + 255) / 256), dim3(256), 0, as_stream(stream), params,
-                       reinterpret_cast<bf16x8*>(base), reinterpret_cast<bf16x8*>(base + (size_t)LN::F_PADDED * 1024),
-                       reinterpret_cast<float*>(base + (size_t)(LN::F_PADDED + LN::B_PADDED) * 1024));
-    int rcn = check_launch("nerf_mlp_pack (2x64 model)");
-    if (!rcn && arch_s16(arch)) rcn = s16x::small_pack(params, base + LN::PACKED_BYTES, as_stream(stream));
-    return rcn;
-  }
-  if (arch_kind(arch) == 1) {
-    bf16x8* wfi = reinterpret_cast<bf16x8*>(base);
-    bf16x8* wbi = reinterpret_cast<bf16x8*>(base + (size_t)LI::F_TOTAL * 1024);
-    float* bi = reinterpret_cast<float*>(base + (size_t)(LI::F_TOTAL + LI::B_PADDED) * 1024);
+    hipLaunchKernelGGL(pack_small_kernel, dim3((tot + 255) / 256), dim3(256), 0, s, params, wf, wb, bias);
+    rc = check_launch("nerf_mlp_pack (2x64 model)");
+    if (!rc && m.split()) rc = s16x::small_pack(params, m.stream<void>(packed, S_S16), s);
+  } else if (m.shape == Shape::Image) {
     const int tot = (LI::F_TOTAL + LI::B_PADDED) * 64 + LI::BI_TOTAL;
-    hipLaunchKernelGGL(pack_img_kernel, dim3((tot + 255) / 256), dim3(256), 0, as_stream(stream), params, wfi, wbi, bi,
-                       arch->out_ch);
-    int rci = check_launch("nerf_mlp_pack (image model)");
-    if (!rci && arch_s16(arch)) rci = s16x::img_pack(params, arch->out_ch, base + IMG_BF16_BYTES, as_stream(stream));
-    if (!rci && arch_f32(arch)) rci = f32::pack(params, base + IMG_BF16_BYTES, arch->out_ch, as_stream(stream));
-    return rci;
+    hipLaunchKernelGGL(pack_img_kernel, dim3((tot + 255) / 256), dim3(256), 0, s, params, wf, wb, bias, m.out_ch);
+    rc = check_launch("nerf_mlp_pack (image model)");
+    if (!rc && m.split()) rc = s16x::img_pack(params, m.out_ch, m.stream<void>(packed, S_S16), s);
+    if (!rc && m.prec == Prec::F32) rc = f32::pack(params, m.stream<void>(packed, S_F32), m.out_ch, s);
+  } else {
+    hipLaunchKernelGGL(pack_kernel, dim3(PACK_BLOCKS + PACK16_BLOCKS), dim3(256), 0, s, params, wf, wb, bias,
+                       m.stream<bf16x8>(packed, S_FWD16));
+    rc = check_launch("nerf_mlp_pack");
+    if (!rc && m.prec == Prec::F32) rc = f32::pack(params, m.stream<void>(packed, S_F32), 0, s);
+    if (!rc && m.split()) rc = f22::pack(params, m.stream<void>(packed, S_F22), s);
+    if (!rc && m.split()) rc = s16::pack(params, m.stream<void>(packed, S_S16), s);
   }
-  bf16x8* wf = reinterpret_cast<bf16x8*>(base);
-  bf16x8* wb = reinterpret_cast<bf16x8*>(base + (size_t)L::F_TOTAL * 1024);
-  float* bias = reinterpret_cast<float*>(base + (size_t)(L::F_TOTAL + L::B_PADDED) * 1024);
-  hipLaunchKernelGGL(pack_kernel, dim3(PACK_BLOCKS + PACK16_BLOCKS), dim3(256), 0, as_stream(stream), params, wf, wb, bias,
-                     reinterpret_cast<bf16x8*>(base + L::F16_OFFSET));
-  int rc = check_launch("nerf_mlp_pack");
-  if (rc) return rc;
-  if (arch_f32(arch)) rc = f32::pack(params, base + L::PACKED_BYTES, 0, as_stream(stream));
-  if (!rc && arch_s16(arch)) rc = f22::pack(params, base + L::PACKED_BYTES, as_stream(stream));
-  if (!rc && arch_s16(arch)) rc = s16::pack(params, base + L::PACKED_BYTES + f22::PACKED_BYTES, as_stream(stream));
   return rc;
 }
 
@@ -1765,14 +1672,13 @@ static void fill_freqs(PeFreq& fr, int mode) {
 }
 
 template <int MODE>
-static int launch_fwd(const void* packed, const float* x, const float* rays, const float* z, int64_t M, int n,
+static int launch_fwd(const Model& m, const void* packed, const float* x, const float* rays, const float* z, int64_t M, int n,
                       int freq_mode, float* out, void* acts, void* stream) {
   FwdArgs a;
   a.queue = nullptr;
-  const char* base = static_cast<const char*>(packed);
-  a.wf = reinterpret_cast<const bf16x8*>(base);
-  a.bias = reinterpret_cast<const float*>(base + (size_t)(L::F_TOTAL + L::B_PADDED) * 1024);
-  a.x = x; a.rays = rays; a.z = z; a.M = M; a.n = n; a.out = out; a.acts = acts; a.astride = astride16();
+  a.wf = m.stream<bf16x8>(packed, S_FWD);
+  a.bias = m.stream<float>(packed, S_BIAS);
+  a.x = x; a.rays = rays; a.z = z; a.M = M; a.n = n; a.out = out; a.acts = acts; a.astride = m.astride();
   fill_freqs(a.fr, freq_mode);
   const int64_t ntiles = (M + 31) / 32;
   auto s = as_stream(stream);
@@ -1780,13 +1686,12 @@ static int launch_fwd(const void* packed, const float* x, const float* rays, con
   // clock: +8 % back to back, +2.5 % inside bench.py's train+render step
   const int variant = (g_mlp_variant == 0) ? (MODE == 1 ? (acts ? 3 : 4) : 1) : g_mlp_variant;
   if ((variant == 4 || variant == 5) && MODE == 1 && !acts) {
-    const int64_t nsuper = (M + 255) / 256;
-    const dim3 g((unsigned)(nsuper < ring_wgs() ? nsuper : ring_wgs()));
+    const dim3 g(persistent_grid((M + 255) / 256));
     static DevOnce once16;
     once16.run([&] { ensure_lds(mlp_fwd_ring16_kernel<8, 2>, RING16_LDS_BYTES); ensure_lds(mlp_fwd_ring16_kernel<4, 4>, RING16_LDS_BYTES); });
     FwdArgs a16 = a;
     a16.queue = passq_slot();
-    a16.wf = reinterpret_cast<const bf16x8*>(base + L::F16_OFFSET);
+    a16.wf = m.stream<bf16x8>(packed, S_FWD16);
     if (variant == 4) hipLaunchKernelGGL((mlp_fwd_ring16_kernel<8, 2>), g, dim3(512), RING16_LDS_BYTES, s, a16);
     else hipLaunchKernelGGL((mlp_fwd_ring16_kernel<4, 4>), g, dim3(256), RING16_LDS_BYTES, s, a16);
     return check_launch("mlp forward (ring, 16x16x32)");
@@ -1794,16 +1699,14 @@ static int launch_fwd(const void* packed, const float* x, const float* rays, con
   if (variant >= 3 && MODE == 1) {
     a.queue = passq_slot();
     if (acts && g_ring_split == 2) {                      // two 4-wave workgroups per CU, each with its own 64 KiB ring
-      const int64_t nsuper = (ntiles + SPLIT_NW - 1) / SPLIT_NW;
-      const int64_t wgs = 2 * (int64_t)ring_wgs();
       static DevOnce once2;
       once2.run([&] { ensure_lds(mlp_fwd_ring_kernel<1, true, SPLIT_NW, SPLIT_CHUNK>, SPLIT_LDS_BYTES); });
-      hipLaunchKernelGGL((mlp_fwd_ring_kernel<1, true, SPLIT_NW, SPLIT_CHUNK>), dim3((unsigned)(nsuper < wgs ? nsuper : wgs)),
-                         dim3(64 * SPLIT_NW), SPLIT_LDS_BYTES, s, a);
+      hipLaunchKernelGGL((mlp_fwd_ring_kernel<1, true, SPLIT_NW, SPLIT_CHUNK>),
+                         dim3(persistent_grid((ntiles + SPLIT_NW - 1) / SPLIT_NW, 2 * (int64_t)ring_wgs())), dim3(64 * SPLIT_NW),
+                         SPLIT_LDS_BYTES, s, a);
       return check_launch("mlp forward (ring, 2 workgroups per CU)");
     }
-    const int64_t nsuper = (ntiles + 7) / 8;
-    const dim3 g((unsigned)(nsuper < ring_wgs() ? nsuper : ring_wgs())), b(512);
+    const dim3 g(persistent_grid((ntiles + 7) / 8)), b(512);
     static DevOnce once;
     once.run([&] { ensure_lds(mlp_fwd_ring_kernel<1, true>, RING_LDS_BYTES); ensure_lds(mlp_fwd_ring_kernel<1, false>, RING_LDS_BYTES); });
     if (acts) hipLaunchKernelGGL((mlp_fwd_ring_kernel<1, true>), g, b, RING_LDS_BYTES, s, a);
@@ -1824,72 +1727,79 @@ static int launch_fwd(const void* packed, const float* x, const float* rays, con
   return check_launch("mlp forward");
 }
 
-static void img_args(ImgArgs& a, const nerf_mlp_arch* arch, const void* packed) {
-  const char* base = static_cast<const char*>(packed);
-  a.wf = reinterpret_cast<const bf16x8*>(base);
-  a.wb = reinterpret_cast<const bf16x8*>(base + (size_t)LI::F_TOTAL * 1024);
-  a.bias = reinterpret_cast<const float*>(base + (size_t)(LI::F_TOTAL + LI::B_PADDED) * 1024);
-  a.out_ch = arch->out_ch; a.astride = img_astride16(); a.zstride = img_zstride16();
+static void img_args(ImgArgs& a, const Model& m, const void* packed) {
+  a.wf = m.stream<bf16x8>(packed, S_FWD);
+  a.wb = m.stream<bf16x8>(packed, S_BWD);
+  a.bias = m.stream<float>(packed, S_BIAS);
+  a.out_ch = m.out_ch; a.astride = m.astride(); a.zstride = m.zstride();
   a.x = nullptr; a.d_out = nullptr; a.out = nullptr; a.acts = nullptr; a.dz = nullptr; a.M = 0;
 }
 
-static void small_args(SmallArgs& a, const void* packed) {
-  const char* base = static_cast<const char*>(packed);
-  a.wf = reinterpret_cast<const bf16x8*>(base);
-  a.wb = reinterpret_cast<const bf16x8*>(base + (size_t)LN::F_PADDED * 1024);
-  a.bias = reinterpret_cast<const float*>(base + (size_t)(LN::F_PADDED + LN::B_PADDED) * 1024);
+static void small_args(SmallArgs& a, const Model& m, const void* packed) {
+  a.wf = m.stream<bf16x8>(packed, S_FWD);
+  a.wb = m.stream<bf16x8>(packed, S_BWD);
+  a.bias = m.stream<float>(packed, S_BIAS);
   a.x = nullptr; a.d_raw = nullptr; a.out = nullptr; a.d_x = nullptr; a.acts = nullptr; a.dz = nullptr; a.M = 0;
-  a.astride = small_astride16(); a.zstride = small_zstride16();
+  a.astride = m.astride(); a.zstride = m.zstride();
   a.rays = nullptr; a.z = nullptr; a.n = 1; a.tables = nullptr; a.tables_h = nullptr; a.T = 0; a.pos_scale = 1.0f; a.pos_offset = 0.0f;
   a.ray_major = 0; a.B = 0;
   for (int l = 0; l < 32; ++l) a.lw.w[l] = 1.0f;
 }
 
+// (defined behind nerf_mlp_forward_train: the kernel templates keep the order of first use they always had in the code object)
+static int view_forward(const Model& m, const void* packed, const float* x, const float* rays, const float* z, int64_t M, int n,
+                        int freq_mode, float* out, void* acts, void* stream);
+
 extern "C" int nerf_mlp_forward_train(const nerf_mlp_arch* arch, const void* packed, const float* x, int64_t M,
                                       float* out, void* acts, void* stream) {
-  NERF_ARCH_CHECK_ANY("nerf_mlp_forward");
+  NERF_RESOLVE("nerf_mlp_forward");
   if (M <= 0) return NERF_OK;
   NERF_REQUIRE(packed && x && out, NERF_E_NULL, "nerf_mlp_forward: NULL pointer");
-  if (arch_kind(arch) == 2) {
+  auto s = as_stream(stream);
+  if (m.shape == Shape::Small) {
+    if (m.split())                             // split bf16: float32-class products (mlp_s16x.hip)
+      return s16x::small_forward(m.stream<void>(packed, S_S16), m.stream<float>(packed, S_BIAS), x, M, out, acts, m.astride(),
+                                 nullptr, s);
     SmallArgs a;
-    small_args(a, packed);
-    if (arch_s16(arch))                        // split bf16: float32-class products (mlp_s16x.hip)
-      return s16x::small_forward(static_cast<const char*>(packed) + LN::PACKED_BYTES, small_bias_of(packed), x, M, out, acts,
-                                 small_astride16(true), nullptr, as_stream(stream));
+    small_args(a, m, packed);
     a.x = x; a.out = out; a.acts = acts; a.M = M;
     const int64_t nwg = ((M + 31) / 32 + 7) / 8;
     const dim3 g((unsigned)(nwg < 2048 ? nwg : 2048)), b(512);
-    if (acts) hipLaunchKernelGGL((mlp_small_fwd_kernel<true, false>), g, b, LN::LDS_BYTES, as_stream(stream), a);
-    else hipLaunchKernelGGL((mlp_small_fwd_kernel<false, false>), g, b, LN::LDS_BYTES, as_stream(stream), a);
+    if (acts) hipLaunchKernelGGL((mlp_small_fwd_kernel<true, false>), g, b, LN::LDS_BYTES, s, a);
+    else hipLaunchKernelGGL((mlp_small_fwd_kernel<false, false>), g, b, LN::LDS_BYTES, s, a);
     return check_launch("mlp forward (2x64 model)");
   }
-  if (arch_kind(arch) == 1) {
-    if (arch_f32(arch))                        // float32 operands on the fp32 MFMA (mlp32.hip)
-      return f32::forward(static_cast<const char*>(packed) + IMG_BF16_BYTES, x, nullptr, nullptr, M, 1, 0, out, acts, arch->out_ch,
-                          as_stream(stream));
-    if (arch_s16(arch))
-      return s16x::img_forward(static_cast<const char*>(packed) + IMG_BF16_BYTES, img_bias_of(packed), x, M, arch->out_ch, out, acts,
-                               img_astride16(true), ring_wgs(), as_stream(stream));
+  if (m.shape == Shape::Image) {
+    if (m.prec == Prec::F32)                   // float32 operands on the fp32 MFMA (mlp32.hip)
+      return f32::forward(m.stream<void>(packed, S_F32), x, nullptr, nullptr, M, 1, 0, out, acts, m.out_ch, s);
+    if (m.split())
+      return s16x::img_forward(m.stream<void>(packed, S_S16), m.stream<float>(packed, S_BIAS), x, M, m.out_ch, out, acts,
+                               m.astride(), ring_wgs(), s);
     ImgArgs a;
-    img_args(a, arch, packed);
+    img_args(a, m, packed);
     a.x = x; a.out = out; a.acts = acts; a.M = M;
-    const int64_t nsuper = ((M + 31) / 32 + 7) / 8;
     static DevOnce once;
     once.run([&] { ensure_lds(mlp_img_fwd_ring_kernel<true>, RING_LDS_BYTES); ensure_lds(mlp_img_fwd_ring_kernel<false>, RING_LDS_BYTES); });
-    const dim3 g((unsigned)(nsuper < ring_wgs() ? nsuper : ring_wgs())), b(512);
-    if (acts) hipLaunchKernelGGL(mlp_img_fwd_ring_kernel<true>, g, b, RING_LDS_BYTES, as_stream(stream), a);
-    else hipLaunchKernelGGL(mlp_img_fwd_ring_kernel<false>, g, b, RING_LDS_BYTES, as_stream(stream), a);
+    const dim3 g(persistent_grid(((M + 31) / 32 + 7) / 8)), b(512);
+    if (acts) hipLaunchKernelGGL(mlp_img_fwd_ring_kernel<true>, g, b, RING_LDS_BYTES, s, a);
+    else hipLaunchKernelGGL(mlp_img_fwd_ring_kernel<false>, g, b, RING_LDS_BYTES, s, a);
     return check_launch("mlp forward (image model)");
   }
-  if (arch_s16(arch) && !acts)                 // inference: split fp16 on the 16-bit matrix pipe
-    return f22::forward(packed22_of(packed), x, nullptr, nullptr, M, 1, 0, out, ring_wgs(), as_stream(stream));
-  if (arch_s16(arch))                          // training forward: split bf16, hi + lo fragment blocks kept
-    return s16::forward(packed_s16_of(packed), bias_slots_of(packed), x, nullptr, nullptr, M, 1, 0, out, acts, s16_astride16(),
-                        ring_wgs(), as_stream(stream));
-  if (arch_f32(arch)) {
-    return f32::forward(packed32_of(packed), x, nullptr, nullptr, M, 1, 0, out, acts, 0, as_stream(stream));
-  }
-  return launch_fwd<0>(packed, x, nullptr, nullptr, M, 1, 0, out, acts, stream);
+  return view_forward(m, packed, x, nullptr, nullptr, M, 1, 0, out, acts, stream);
+}
+
+// the view model's forward in its precision; x != nullptr: embedded rows [M,90], else rays + depths (encodings in the kernel)
+static int view_forward(const Model& m, const void* packed, const float* x, const float* rays, const float* z, int64_t M, int n,
+                        int freq_mode, float* out, void* acts, void* stream) {
+  auto s = as_stream(stream);
+  if (m.split() && !acts)                      // inference: split fp16 on the 16-bit matrix pipe
+    return f22::forward(m.stream<void>(packed, S_F22), x, rays, z, M, n, freq_mode, out, ring_wgs(), s);
+  if (m.split())                               // training forward: split bf16, hi + lo fragment blocks kept
+    return s16::forward(m.stream<void>(packed, S_S16), m.stream<float>(packed, S_BIAS), x, rays, z, M, n, freq_mode, out, acts,
+                        m.astride(), ring_wgs(), s);
+  if (m.prec == Prec::F32) return f32::forward(m.stream<void>(packed, S_F32), x, rays, z, M, n, freq_mode, out, acts, 0, s);
+  return x ? launch_fwd<0>(m, packed, x, rays, z, M, n, freq_mode, out, acts, stream)
+           : launch_fwd<1>(m, packed, x, rays, z, M, n, freq_mode, out, acts, stream);
 }
 
 extern "C" int nerf_mlp_forward(const nerf_mlp_arch* arch, const void* packed, const float* x, int64_t M, float* out,
@@ -1899,82 +1809,36 @@ extern "C" int nerf_mlp_forward(const nerf_mlp_arch* arch, const void* packed, c
 
 extern "C" int nerf_query_fused(const nerf_mlp_arch* arch, const void* packed, const float* rays, const float* z,
                                 int64_t B, int n, int freq_mode, float* raw, void* acts, void* stream) {
-  NERF_ARCH_CHECK("nerf_query_fused");
+  const Model m = resolve(arch);
+  NERF_REQUIRE(m.ok && m.shape == Shape::View, NERF_E_UNSUPPORTED, "nerf_query_fused" NERF_ARCH_MSG);
   NERF_REQUIRE(n >= 1, NERF_E_SHAPE, "nerf_query_fused: n must be >= 1");
   if (B <= 0) return NERF_OK;
   NERF_REQUIRE(packed && rays && z && raw, NERF_E_NULL, "nerf_query_fused: NULL pointer");
   NERF_REQUIRE(freq_mode == 0 || freq_mode == 1, NERF_E_UNSUPPORTED, "nerf_query_fused: freq_mode must be 0 or 1");
   NERF_REQUIRE(B * (int64_t)n < (1ll << 31), NERF_E_SHAPE, "nerf_query_fused: B*n must be < 2^31 samples per call");
-  if (arch_s16(arch) && !acts)
-    return f22::forward(packed22_of(packed), nullptr, rays, z, B * n, n, freq_mode, raw, ring_wgs(), as_stream(stream));
-  if (arch_s16(arch))
-    return s16::forward(packed_s16_of(packed), bias_slots_of(packed), nullptr, rays, z, B * n, n, freq_mode, raw, acts,
-                        s16_astride16(), ring_wgs(), as_stream(stream));
-  if (arch_f32(arch)) {
-    return f32::forward(packed32_of(packed), nullptr, rays, z, B * n, n, freq_mode, raw, acts, 0, as_stream(stream));
-  }
-  return launch_fwd<1>(packed, nullptr, rays, z, B * n, n, freq_mode, raw, acts, stream);
+  return view_forward(m, packed, nullptr, rays, z, B * n, n, freq_mode, raw, acts, stream);
 }
 
 // one dW launch + its reduce over a job list.  kind 0: bf16, 16 waves (mlp_dw_kernel); 1: split bf16, 16 waves (s16_dw_kernel);
 // 2 / 3: split bf16 / bf16, 256 x 256 jobs only, one wave per SIMD (mlp_dww_kernel).  slot_base: first partial-tile slot of this
 // launch (the two launches of one backward pass use disjoint slots).
-static int launch_dw_part(DwArgs& d, int nj, int64_t ntiles, int64_t nparams, const void* acts, void* dz, int64_t astride,
-                          int64_t zstride, float* grads, hipStream_t s, int kind, int a_lo, int z_lo, int slot_base, int max_wgs) {
-  const bool split_bf16 = kind == 1 || kind == 2;
-  // A job's cost per sample tile = its bytes (nf + kf KiB) + a fixed part (barrier, waits, the 4 DMA issues per wave,
-  // transposed reads, MFMAs) worth about 128 KiB of streaming: single-job timings fit t = a (nf + kf + c0) with c0 = 24
-  // at a full grid, but under load the sweep over c0 keeps improving up to ~128 and is flat beyond (tools/sweep_dw.py).  Split the sample range of every job in proportion.
-  // Split-bf16 kernels (round 6): since the 256 x 256 jobs run in a launch of their own (all equal: the bias is moot there), the bias only
-  // balances the six narrow jobs among themselves, and their times alone fit t = 9.0 (nf + kf) + 0 ... 14: 32 gave the two tiny jobs
-  // (dir0 | dirPE, rgb) 36 workgroups each instead of 26-28 and the launch waited for dir0 | feature; 2 is worth -1.8 % of the
-  // training step (tools/ab_train_step.py dw_unit_bias -1 2: 10.66 -> 10.46 ms; 0 / 1 / 3 within noise of it, 8: -0.8 %).
-  int64_t units[DW_MAX_JOBS], total_units = 0;
-  for (int j = 0; j < nj; ++j) {
-    units[j] = d.jobs[j].nf + d.jobs[j].kf + (g_dw_bias >= 0 ? g_dw_bias : split_bf16 ? 2 : 128);
-    total_units += units[j];
-  }
-  // One workgroup per CU and launch (256), shares by largest remainder so that they sum to exactly 256: every
-  // workgroup starts at once and, with the cost model above, ends at about the same time -- one prologue and one atomic
-  // flush per CU instead of 6-16.  (tools/sweep_dw.py: 1.54 ms against 1.70 for the 192-sample pass, 0.52 against 0.66
-  // for the 64-sample pass; with the old byte-only cost model 256 workgroups took 3.1 ms because the small jobs'
-  // workgroups ran twice as long as the others.)  "dw_workgroups" overrides the total.
+static int launch_dw_part(const Model& m, DwArgs& d, int nj, int64_t ntiles, const void* acts, void* dz, float* grads,
+                          hipStream_t s, int kind, int slot_base, int max_wgs) {
+  static_assert(DW_SPLIT_MAX_JOBS == DW_MAX_JOBS, "dw_split.h sizes its arrays for DwArgs::jobs");
+  DwCost cost[DW_MAX_JOBS];
+  for (int j = 0; j < nj; ++j) cost[j] = DwCost{d.jobs[j].nf, d.jobs[j].kf};
+  // the cost model and the largest-remainder split: dw_split.h.  "dw_workgroups" overrides the total.
   int target_wgs = g_dw_wgs > 0 ? g_dw_wgs : cu_count();
   if (target_wgs > max_wgs) target_wgs = max_wgs;               // one partial-tile slot per workgroup
-  const int64_t max_splits = (ntiles + 3) / 4;                  // >= 4 sample tiles per workgroup
-  int nw = 0;
-  double frac[DW_MAX_JOBS];
-  for (int j = 0; j < DW_MAX_JOBS; ++j) d.splits[j] = 0;
-  for (int j = 0; j < nj; ++j) {
-    const double share = (double)units[j] * target_wgs / (double)total_units;
-    int64_t sp = (int64_t)share;
-    frac[j] = share - (double)sp;
-    if (sp < 1) { sp = 1; frac[j] = 0.0; }
-    if (sp > max_splits) { sp = max_splits; frac[j] = 0.0; }
-    d.splits[j] = (int)sp;
-    nw += (int)sp;
-  }
-  while (nw < target_wgs) {                                     // hand out the remainder, largest fraction first
-    int best = -1;
-    for (int j = 0; j < nj; ++j)
-      if (d.splits[j] < max_splits && (best < 0 || frac[j] > frac[best])) best = j;
-    if (best < 0 || frac[best] <= 0.0) break;
-    d.splits[best] += 1; frac[best] = 0.0; nw += 1;
-  }
-  while (nw > target_wgs) {                                     // (minimum-of-one bumps) take back from the largest
-    int big = 0;
-    for (int j = 1; j < nj; ++j) if (d.splits[j] > d.splits[big]) big = j;
-    if (d.splits[big] <= 1) break;
-    d.splits[big] -= 1; nw -= 1;
-  }
+  const int nw = dw_split(cost, nj, g_dw_bias >= 0 ? g_dw_bias : m.split() ? 2 : 128, target_wgs, (ntiles + 3) / 4, d.splits);
   NERF_REQUIRE(slot_base + nw <= DW_MAX_WGS, NERF_E_SHAPE, "nerf_mlp_backward: dw_workgroups must be <= %d", DW_MAX_WGS);
   bool all_tiny = true;
   for (int j = 0; j < nj; ++j) all_tiny = all_tiny && ((d.jobs[j].nf + 1) / 2) * ((d.jobs[j].kf + 1) / 2) <= 4;
-  d.ntiles = (int)ntiles; d.astride = astride; d.zstride = zstride;
+  d.ntiles = (int)ntiles; d.astride = m.astride(); d.zstride = m.zstride();
   d.acts = acts; d.dz = dz; d.grads = grads;
-  d.a_lo = a_lo; d.z_lo = z_lo; d.ring_cap = g_dw_ring_cap; d.private_max_tiles = g_dw_private;
+  d.a_lo = m.info->a_lo; d.z_lo = m.info->z_lo; d.ring_cap = g_dw_ring_cap; d.private_max_tiles = g_dw_private;
   // the partial-tile slots live behind the dZ fragment blocks in the caller's dz workspace (nerf_mlp_dz_bytes counts them)
-  d.partial = reinterpret_cast<float*>(static_cast<char*>(dz) + padded_tiles(ntiles * 32) * zstride * 16) + (size_t)slot_base * DW_SLOT_FLOATS;
+  d.partial = m.dw_partial(dz, ntiles) + (size_t)slot_base * DW_SLOT_FLOATS;
   int rc;
   if (kind >= 2) {             // 16 x 16-fragment jobs, one wave per SIMD (mlp_dww.hip); same slots and reduce
     rc = launch_dw_wide_kernel(d, nw, kind == 2, s);
@@ -1987,7 +1851,7 @@ static int launch_dw_part(DwArgs& d, int nj, int64_t ntiles, int64_t nparams, co
     rc = s16::launch_dw_kernel(d, nw, false, s);
   } else {
     static DevOnce lds_attr_set;
-    lds_attr_set.run([&] { (void)hipFuncSetAttribute(reinterpret_cast<const void*>(mlp_dw_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, DW_LDS_BYTES); });
+    lds_attr_set.run([&] { ensure_lds(mlp_dw_kernel, DW_LDS_BYTES); });
     hipLaunchKernelGGL(mlp_dw_kernel, dim3(nw), dim3(64 * DW_WAVES), DW_LDS_BYTES, s, d);
     rc = check_launch("mlp dW");
   }
@@ -1996,17 +1860,17 @@ static int launch_dw_part(DwArgs& d, int nj, int64_t ntiles, int64_t nparams, co
   return check_launch("mlp dW reduce");
 }
 
-// split the (dZ, H) jobs over workgroups and launch the dW kernel(s); grads[0..nparams) is overwritten
-static int launch_dw(DwArgs& d, int nj, int64_t ntiles, int64_t nparams, const void* acts, void* dz, int64_t astride,
-                     int64_t zstride, float* grads, hipStream_t s, bool split_bf16 = false, int a_lo = 0, int z_lo = 0) {
+// split the (dZ, H) jobs over workgroups and launch the dW kernel(s); grads[0..m.params) is overwritten
+static int launch_dw(const Model& m, DwArgs& d, int nj, int64_t ntiles, const void* acts, void* dz, float* grads, hipStream_t s) {
   if (g_dw_job_mask) {          // diagnostic subset of jobs: the parameters of the jobs left out read as zero
-    hipError_t e = hipMemsetAsync(grads, 0, sizeof(float) * nparams, s);
+    hipError_t e = hipMemsetAsync(grads, 0, sizeof(float) * m.params, s);
     if (e != hipSuccess) return fail(NERF_E_HIP, "nerf_mlp_backward: memset: %s", hipGetErrorString(e));
   }
   // "dw22_variant" / "dw16_variant" 1 (default): the 256 x 256 jobs on the one-wave-per-SIMD kernel, the others on the 16-wave kernel;
   // two launches, each with its own static split over all CUs and its own half of the partial-tile slots.  0: one 16-wave launch.
+  const bool split_bf16 = m.split();
   if ((split_bf16 ? s16::g_dw_variant : g_dw16_variant) == 0)
-    return launch_dw_part(d, nj, ntiles, nparams, acts, dz, astride, zstride, grads, s, split_bf16 ? 1 : 0, a_lo, z_lo, 0, DW_MAX_WGS);
+    return launch_dw_part(m, d, nj, ntiles, acts, dz, grads, s, split_bf16 ? 1 : 0, 0, DW_MAX_WGS);
   DwArgs wide = d, rest = d;
   int nwide = 0, nrest = 0;
   for (int j = 0; j < nj; ++j) {
@@ -2017,123 +1881,45 @@ static int launch_dw(DwArgs& d, int nj, int64_t ntiles, int64_t nparams, const v
   for (int turn = 0; turn < 2; ++turn) {        // "dw_narrow_first" 1: the load-bound narrow jobs before the MFMA-bound 256 x 256 jobs
     const bool do_wide = (turn == 0) != (g_dw_narrow_first != 0);
     if (do_wide && nwide) {
-      const int rc = launch_dw_part(wide, nwide, ntiles, nparams, acts, dz, astride, zstride, grads, s, split_bf16 ? 2 : 3, a_lo, z_lo, half, half);
+      const int rc = launch_dw_part(m, wide, nwide, ntiles, acts, dz, grads, s, split_bf16 ? 2 : 3, half, half);
       if (rc) return rc;
     }
     if (!do_wide && nrest) {
-      const int rc = launch_dw_part(rest, nrest, ntiles, nparams, acts, dz, astride, zstride, grads, s, split_bf16 ? 1 : 0, a_lo, z_lo, 0, half);
+      const int rc = launch_dw_part(m, rest, nrest, ntiles, acts, dz, grads, s, split_bf16 ? 1 : 0, 0, half);
       if (rc) return rc;
     }
   }
   return NERF_OK;
 }
 
-static int mlp_backward_impl(const nerf_mlp_arch* arch, const void* packed, const void* acts, const float* d_raw,
-                             int64_t M, void* dz, float* grads, float* d_x, void* stream) {
-  NERF_ARCH_CHECK_ANY("nerf_mlp_backward");
-  NERF_REQUIRE(!d_x || arch_kind(arch) == 2, NERF_E_UNSUPPORTED,
-               "nerf_mlp_backward_inputs: input gradients exist for the (2x64) model only (the 8x256 models take fixed encodings)");
-  NERF_REQUIRE(packed && acts && d_raw && dz && grads, NERF_E_NULL, "nerf_mlp_backward: NULL pointer");
-  NERF_REQUIRE(M > 0, NERF_E_SHAPE, "nerf_mlp_backward: M must be > 0");
-  auto s = as_stream(stream);
+// the dZ chain of the view model (bf16 or split bf16)
+static int view_backward_chain(const Model& m, const void* packed, const void* acts, const float* d_raw, int64_t M, void* dz,
+                               hipStream_t s) {
   const int64_t ntiles = (M + 31) / 32;
-  if (arch_kind(arch) == 2) {
-    const bool sp = arch_s16(arch);
-    int rcs;
-    if (sp) {
-      rcs = s16x::small_backward_chain(static_cast<const char*>(packed) + LN::PACKED_BYTES, acts, d_raw, M, dz, d_x,
-                                       small_astride16(true), small_zstride16(true), s);
-    } else {
-      SmallArgs a;
-      small_args(a, packed);
-      a.d_raw = d_raw; a.acts = const_cast<void*>(acts); a.dz = dz; a.M = M; a.d_x = d_x;
-      const int64_t nwg = (ntiles + 7) / 8;
-      hipLaunchKernelGGL(mlp_small_bwd_kernel, dim3((unsigned)(nwg < 2048 ? nwg : 2048)), dim3(512), LN::LDS_BYTES, s, a);
-      rcs = check_launch("mlp backward chain (2x64 model)");
+  if (m.split()) {
+    if (g_bwd_stage != 2) {
+      const int rcs = s16::backward_chain(m.stream<void>(packed, S_S16), acts, d_raw, M, dz, m.astride(), m.zstride(), ring_wgs(), s);
+      if (rcs) return rcs;
     }
-    if (rcs) return rcs;
-    DwArgs ds;
-    int njs = 0;
-    auto jobs = [&](int dz_slot, int nf, int act_slot, int kf, int w_off, int ldw, int col0, int nv, int kv, int b_off) {
-      ds.jobs[njs++] = DwJob{dz_slot, nf, act_slot, kf, w_off, ldw, col0, nv, kv, b_off};
-    };
-    jobs(LN::Z_L0, 4, LN::A_X, 2, LN::P_W0, 32, 0, 64, 32, LN::P_B0);          // pos0
-    jobs(LN::Z_L1, 4, LN::A_H0, 4, LN::P_W1, 64, 0, 64, 64, LN::P_B1);         // pos1
-    jobs(LN::Z_F, 4, LN::A_H1, 4, LN::P_WF, 64, 0, 64, 64, LN::P_BF);          // feature
-    jobs(LN::Z_A, 1, LN::A_H1, 4, LN::P_WA, 64, 0, 1, 64, LN::P_BA);           // alpha
-    jobs(LN::Z_D, 2, LN::A_FEAT, 4, LN::P_WD, 80, 0, 32, 64, LN::P_BD);        // dir0 | feature
-    jobs(LN::Z_D, 2, LN::A_DX, 1, LN::P_WD, 80, 64, 32, 16, -1);               // dir0 | direction features
-    jobs(LN::Z_RGB, 1, LN::A_HD, 2, LN::P_WR, 32, 0, 3, 32, LN::P_BR);         // rgb
-    return launch_dw(ds, njs, ntiles, LN::P_TOTAL, acts, dz, small_astride16(sp), small_zstride16(sp), grads, s, sp, s16x::SM_A_LO,
-                     s16x::SM_Z_LO);
+    return check_launch("mlp backward chain");
   }
-  if (arch_kind(arch) == 1) {
-    if (arch_f32(arch))
-      return f32::backward(static_cast<const char*>(packed) + IMG_BF16_BYTES, acts, d_raw, M, dz, grads, arch->out_ch, s);
-    const bool sp = arch_s16(arch);
-    int rci;
-    if (sp) {
-      rci = s16x::img_backward_chain(static_cast<const char*>(packed) + IMG_BF16_BYTES, acts, d_raw, M, arch->out_ch, dz,
-                                     img_astride16(true), img_zstride16(true), ring_wgs(), s);
-    } else {
-      ImgArgs a;
-      img_args(a, arch, packed);
-      a.d_out = d_raw; a.acts = const_cast<void*>(acts); a.dz = dz; a.M = M;
-      const int64_t nsuper = (ntiles + 7) / 8;
-      static DevOnce once_i;
-      once_i.run([&] { ensure_lds(mlp_img_bwd_ring_kernel, RING_LDS_BYTES); });
-      hipLaunchKernelGGL(mlp_img_bwd_ring_kernel, dim3((unsigned)(nsuper < ring_wgs() ? nsuper : ring_wgs())), dim3(512),
-                         RING_LDS_BYTES, s, a);
-      rci = check_launch("mlp backward chain (image model)");
-    }
-    if (rci) return rci;
-    DwArgs di;
-    int nji = 0;
-    auto jobi = [&](int dz_slot, int nf, int act_slot, int kf, int w_off, int ldw, int col0, int nv, int kv, int b_off) {
-      di.jobs[nji++] = DwJob{dz_slot, nf, act_slot, kf, w_off, ldw, col0, nv, kv, b_off};
-    };
-    jobi(LI::Z_L0, 16, LI::A_X, 3, LI::P_W0, 40, 0, 256, 40, LI::P_B0);                                    // pos0
-    for (int l = 1; l <= 4; ++l)
-      jobi(LI::Z_L0 + 16 * l, 16, LI::A_H0 + 16 * (l - 1), 16, LI::pw(l), 256, 0, 256, 256, LI::pb(l));    // pos1..4
-    jobi(LI::Z_L0 + 80, 16, LI::A_H0 + 64, 16, LI::P_W5, 296, 40, 256, 256, LI::P_B5);                     // pos5 | H4
-    jobi(LI::Z_L0 + 80, 16, LI::A_X, 3, LI::P_W5, 296, 0, 256, 40, -1);                                    // pos5 | x
-    jobi(LI::Z_L0 + 96, 16, LI::A_H0 + 80, 16, LI::P_W6, 256, 0, 256, 256, LI::P_B6);                      // pos6
-    jobi(LI::Z_L0 + 112, 16, LI::A_H0 + 96, 16, LI::P_W7, 256, 0, 256, 256, LI::P_B7);                     // pos7
-    jobi(LI::Z_OUT, 1, LI::A_H0 + 112, 16, LI::P_WO, 256, 0, arch->out_ch, 256, LI::P_WO + arch->out_ch * 256);   // output
-    return launch_dw(di, nji, ntiles, img_params(arch), acts, dz, img_astride16(sp), img_zstride16(sp), grads, s, sp, s16x::IMG_A_LO,
-                     s16x::IMG_Z_LO);
-  }
-  if (arch_f32(arch)) {
-    return f32::backward(packed32_of(packed), acts, d_raw, M, dz, grads, 0, s);
-  }
-  const bool split = arch_s16(arch);
-  const int64_t astr = split ? s16_astride16() : astride16(), zstr = split ? s16_zstride16() : zstride16();
-  if (split && g_bwd_stage != 2) {
-    int rcs = s16::backward_chain(packed_s16_of(packed), acts, d_raw, M, dz, astr, zstr, ring_wgs(), s);
-    if (rcs) return rcs;
-  }
-  // ---- 1. dZ chain
   BwdArgs b;
   b.queue = nullptr;
-  b.wb = reinterpret_cast<const bf16x8*>(static_cast<const char*>(packed) + (size_t)L::F_TOTAL * 1024);
-  b.acts = acts; b.d_raw = d_raw; b.M = M; b.dz = dz; b.astride = astride16(); b.zstride = zstride16();
+  b.wb = m.stream<bf16x8>(packed, S_BWD);
+  b.acts = acts; b.d_raw = d_raw; b.M = M; b.dz = dz; b.astride = m.astride(); b.zstride = m.zstride();
   const int variant = g_mlp_variant == 0 ? 3 : g_mlp_variant;
-  if (split) {
-  } else if (variant >= 3) {
+  if (variant >= 3) {
     b.queue = passq_slot();
     if (g_bwd_stage != 2 && g_ring_split == 2) {
-      const int64_t nsuper = (ntiles + SPLIT_NW - 1) / SPLIT_NW;
-      const int64_t wgs = 2 * (int64_t)ring_wgs();
       static DevOnce once2;
       once2.run([&] { ensure_lds(mlp_bwd_ring_kernel<SPLIT_NW, SPLIT_CHUNK>, SPLIT_LDS_BYTES); });
-      hipLaunchKernelGGL((mlp_bwd_ring_kernel<SPLIT_NW, SPLIT_CHUNK>), dim3((unsigned)(nsuper < wgs ? nsuper : wgs)),
-                         dim3(64 * SPLIT_NW), SPLIT_LDS_BYTES, s, b);
+      hipLaunchKernelGGL((mlp_bwd_ring_kernel<SPLIT_NW, SPLIT_CHUNK>),
+                         dim3(persistent_grid((ntiles + SPLIT_NW - 1) / SPLIT_NW, 2 * (int64_t)ring_wgs())), dim3(64 * SPLIT_NW),
+                         SPLIT_LDS_BYTES, s, b);
     } else if (g_bwd_stage != 2) {
-      const int64_t nsuper = (ntiles + 7) / 8;
       static DevOnce once;
       once.run([&] { ensure_lds(mlp_bwd_ring_kernel<>, RING_LDS_BYTES); });
-      hipLaunchKernelGGL(mlp_bwd_ring_kernel<>, dim3((unsigned)(nsuper < ring_wgs() ? nsuper : ring_wgs())), dim3(512),
-                         RING_LDS_BYTES, s, b);
+      hipLaunchKernelGGL(mlp_bwd_ring_kernel<>, dim3(persistent_grid((ntiles + 7) / 8)), dim3(512), RING_LDS_BYTES, s, b);
     }
   } else {
     const int st = variant == 2 ? 2 : 1;
@@ -2141,29 +1927,54 @@ static int mlp_backward_impl(const nerf_mlp_arch* arch, const void* packed, cons
     if (st == 1) hipLaunchKernelGGL((mlp_bwd_kernel<1>), dim3((unsigned)blocks), dim3(256), 0, s, b);
     else hipLaunchKernelGGL((mlp_bwd_kernel<2>), dim3((unsigned)blocks), dim3(256), 0, s, b);
   }
-  int rc = check_launch("mlp backward chain");
+  return check_launch("mlp backward chain");
+}
+
+static int mlp_backward_impl(const nerf_mlp_arch* arch, const void* packed, const void* acts, const float* d_raw,
+                             int64_t M, void* dz, float* grads, float* d_x, void* stream) {
+  NERF_RESOLVE("nerf_mlp_backward");
+  NERF_REQUIRE(!d_x || m.shape == Shape::Small, NERF_E_UNSUPPORTED,
+               "nerf_mlp_backward_inputs: input gradients exist for the (2x64) model only (the 8x256 models take fixed encodings)");
+  NERF_REQUIRE(packed && acts && d_raw && dz && grads, NERF_E_NULL, "nerf_mlp_backward: NULL pointer");
+  NERF_REQUIRE(M > 0, NERF_E_SHAPE, "nerf_mlp_backward: M must be > 0");
+  auto s = as_stream(stream);
+  const int64_t ntiles = (M + 31) / 32;
+  if (m.prec == Prec::F32)                     // mlp32.hip: chain and dW in its own store format
+    return f32::backward(m.stream<void>(packed, S_F32), acts, d_raw, M, dz, grads, m.shape == Shape::Image ? m.out_ch : 0, s);
+  // ---- 1. dZ chain
+  int rc;
+  if (m.shape == Shape::Small) {
+    if (m.split()) {
+      rc = s16x::small_backward_chain(m.stream<void>(packed, S_S16), acts, d_raw, M, dz, d_x, m.astride(), m.zstride(), s);
+    } else {
+      SmallArgs a;
+      small_args(a, m, packed);
+      a.d_raw = d_raw; a.acts = const_cast<void*>(acts); a.dz = dz; a.M = M; a.d_x = d_x;
+      const int64_t nwg = (ntiles + 7) / 8;
+      hipLaunchKernelGGL(mlp_small_bwd_kernel, dim3((unsigned)(nwg < 2048 ? nwg : 2048)), dim3(512), LN::LDS_BYTES, s, a);
+      rc = check_launch("mlp backward chain (2x64 model)");
+    }
+  } else if (m.shape == Shape::Image) {
+    if (m.split()) {
+      rc = s16x::img_backward_chain(m.stream<void>(packed, S_S16), acts, d_raw, M, m.out_ch, dz, m.astride(), m.zstride(), ring_wgs(), s);
+    } else {
+      ImgArgs a;
+      img_args(a, m, packed);
+      a.d_out = d_raw; a.acts = const_cast<void*>(acts); a.dz = dz; a.M = M;
+      static DevOnce once_i;
+      once_i.run([&] { ensure_lds(mlp_img_bwd_ring_kernel, RING_LDS_BYTES); });
+      hipLaunchKernelGGL(mlp_img_bwd_ring_kernel, dim3(persistent_grid((ntiles + 7) / 8)), dim3(512), RING_LDS_BYTES, s, a);
+      rc = check_launch("mlp backward chain (image model)");
+    }
+  } else {
+    rc = view_backward_chain(m, packed, acts, d_raw, M, dz, s);
+    if (!rc && g_bwd_stage == 1) return NERF_OK;
+  }
   if (rc) return rc;
-  if (g_bwd_stage == 1) return NERF_OK;
   // ---- 2. dW / db
   DwArgs d;
-  int nj = 0, jseq = 0;
-  auto job = [&](int dz_slot, int nf, int act_slot, int kf, int w_off, int ldw, int col0, int nv, int kv, int b_off) {
-    if (g_dw_job_mask && !((g_dw_job_mask >> jseq++) & 1)) return;
-    d.jobs[nj++] = DwJob{dz_slot, nf, act_slot, kf, w_off, ldw, col0, nv, kv, b_off};
-  };
-  job(L::Z_L0, 16, L::A_PE, 4, L::P_W0, 63, 0, 256, 63, L::P_B0);                                  // pos0
-  for (int l = 1; l <= 4; ++l)
-    job(L::Z_L0 + 16 * l, 16, L::A_H0 + 16 * (l - 1), 16, L::pw(l), 256, 0, 256, 256, L::pb(l));   // pos1..4
-  job(L::Z_L0 + 80, 16, L::A_H0 + 64, 16, L::P_W5, 319, 63, 256, 256, L::P_B5);                    // pos5 | H4
-  job(L::Z_L0 + 80, 16, L::A_PE, 4, L::P_W5, 319, 0, 256, 63, -1);                                 // pos5 | PE
-  job(L::Z_L0 + 96, 16, L::A_H0 + 80, 16, L::P_W6, 256, 0, 256, 256, L::P_B6);                     // pos6
-  job(L::Z_L0 + 112, 16, L::A_H0 + 96, 16, L::P_W7, 256, 0, 256, 256, L::P_B7);                    // pos7
-  job(L::Z_F, 16, L::A_H0 + 112, 16, L::P_WF, 256, 0, 256, 256, L::P_BF);                          // feature
-  job(L::Z_A, 1, L::A_H0 + 112, 16, L::P_WA, 256, 0, 1, 256, L::P_BA);                             // alpha
-  job(L::Z_D, 8, L::A_FEAT, 16, L::P_WD, 283, 0, 128, 256, L::P_BD);                               // dir0 | feature
-  job(L::Z_D, 8, L::A_DPE, 2, L::P_WD, 283, 256, 128, 27, -1);                                     // dir0 | dirPE
-  job(L::Z_RGB, 1, L::A_HD, 8, L::P_WR, 128, 0, 3, 128, L::P_BR);                                  // rgb
-  return launch_dw(d, nj, ntiles, L::P_TOTAL, acts, dz, astr, zstr, grads, s, split, s16::A_LO, s16::Z_LO);
+  const int nj = m.dw_jobs(d.jobs, m.shape == Shape::View ? g_dw_job_mask : 0);
+  return launch_dw(m, d, nj, ntiles, acts, dz, grads, s);
 }
 
 // lw_host: the level weights of nerf_ngp_query_fused_lw; NULL = the kernels without them
@@ -2171,7 +1982,8 @@ static int ngp_query_fused_impl(const nerf_mlp_arch* arch, const void* packed, c
                                 int64_t B, int n, const float* tables, const void* tables_half, int L, int log2_T, int F,
                                 const int* resolutions_host, const float* lw_host, int sh_degree, float pos_scale,
                                 float pos_offset, float* raw, void* acts, void* stream) {
-  NERF_REQUIRE(arch_kind(arch) == 2, NERF_E_UNSUPPORTED, "nerf_ngp_query_fused: needs the (2x64, in 32+16) model");
+  const Model m = resolve(arch);
+  NERF_REQUIRE(m.ok && m.shape == Shape::Small, NERF_E_UNSUPPORTED, "nerf_ngp_query_fused: needs the (2x64, in 32+16) model");
   NERF_REQUIRE(L == 16 && F == 2 && sh_degree == 3, NERF_E_UNSUPPORTED,
                "nerf_ngp_query_fused: fused rows exist for 16 levels x 2 features + SH degree 3 (use nerf_ngp_encode + nerf_mlp_forward otherwise)");
   NERF_REQUIRE(log2_T >= 1 && log2_T <= 30, NERF_E_SHAPE, "nerf_ngp_query_fused: need 1<=log2_T<=30");
@@ -2182,18 +1994,18 @@ static int ngp_query_fused_impl(const nerf_mlp_arch* arch, const void* packed, c
   LevelTab lt;
   if (lw_host)
     NERF_REQUIRE(level_tab_fill(lt, lw_host, L), NERF_E_SHAPE, "nerf_ngp_query_fused_lw: level weights must be finite and in [0, 1]");
-  if (arch_s16(arch)) {         // reference tolerance: float32 gathers from the master tables (the fp16 shadow is a reduced-precision
+  if (m.split()) {              // reference tolerance: float32 gathers from the master tables (the fp16 shadow is a reduced-precision
     s16x::SmallQuery q;         // image: not read in this mode), float32 interpolation, split-bf16 MLP (mlp_s16x.hip)
     q.rays = rays; q.z = z; q.n = n; q.tables = tables; q.T = 1u << log2_T; q.pos_scale = pos_scale; q.pos_offset = pos_offset;
     for (int l = 0; l < 32; ++l) q.res[l] = l < L ? (float)resolutions_host[l] : 0.0f;
     q.B = B; q.ray_major = g_ngp_ray_major;
     q.use_lw = lw_host != nullptr;
     if (lw_host) for (int l = 0; l < 32; ++l) q.lw[l] = lt.w[l];
-    return s16x::small_forward(static_cast<const char*>(packed) + LN::PACKED_BYTES, small_bias_of(packed), nullptr, M, raw, acts,
-                               small_astride16(true), &q, as_stream(stream));
+    return s16x::small_forward(m.stream<void>(packed, S_S16), m.stream<float>(packed, S_BIAS), nullptr, M, raw, acts, m.astride(), &q,
+                               as_stream(stream));
   }
   SmallArgs a;
-  small_args(a, packed);
+  small_args(a, m, packed);
   a.out = raw; a.acts = acts; a.M = M; a.rays = rays; a.z = z; a.n = n; a.tables = tables; a.T = 1u << log2_T;
   a.tables_h = static_cast<const uint32_t*>(tables_half);
   a.pos_scale = pos_scale; a.pos_offset = pos_offset;
@@ -2264,74 +2076,30 @@ __global__ void __launch_bounds__(256) decode_frags_kernel(const void* base, int
     }
   }
 }
-// (slot, fragments) of `layer` in the activation (kind 0) or dZ (kind 1) store of an architecture (arch_kind 0 / 1 / 2)
-static bool debug_slot(int ak, int kind, int layer, int* slot, int* nfrag) {
-  if (layer < 0 || layer > 11 || (kind != 0 && kind != 1)) return false;
-  if (ak == 1) {                       // image model: pos0..7; 8 = output gradient; 10 = input rows (48 = 40 + pad)
-    if (layer < 8) { *slot = (kind == 0 ? LI::A_H0 : LI::Z_L0) + 16 * layer; *nfrag = 16; return true; }
-    if (kind == 0 && layer == 10) { *slot = LI::A_X; *nfrag = 3; return true; }
-    if (kind == 1 && layer == 8) { *slot = LI::Z_OUT; *nfrag = 1; return true; }
-    return false;
-  }
-  if (ak == 2) {                       // 2 x 64 model: pos0, pos1; 8 = feature; 9 = dir0; 10 / 11 = inputs (acts) or d alpha / d rgb (dz)
-    if (kind == 0) {
-      if (layer == 0) { *slot = LN::A_H0; *nfrag = 4; } else if (layer == 1) { *slot = LN::A_H1; *nfrag = 4; }
-      else if (layer == 8) { *slot = LN::A_FEAT; *nfrag = 4; } else if (layer == 9) { *slot = LN::A_HD; *nfrag = 2; }
-      else if (layer == 10) { *slot = LN::A_X; *nfrag = 2; } else if (layer == 11) { *slot = LN::A_DX; *nfrag = 1; }
-      else return false;
-      return true;
-    }
-    if (layer == 0) { *slot = LN::Z_L0; *nfrag = 4; } else if (layer == 1) { *slot = LN::Z_L1; *nfrag = 4; }
-    else if (layer == 8) { *slot = LN::Z_F; *nfrag = 4; } else if (layer == 9) { *slot = LN::Z_D; *nfrag = 2; }
-    else if (layer == 10) { *slot = LN::Z_A; *nfrag = 1; } else if (layer == 11) { *slot = LN::Z_RGB; *nfrag = 1; }
-    else return false;
-    return true;
-  }
-  if (kind == 0) {
-    if (layer < 8) { *slot = L::A_H0 + 16 * layer; *nfrag = 16; }
-    else if (layer == 8) { *slot = L::A_FEAT; *nfrag = 16; }
-    else if (layer == 9) { *slot = L::A_HD; *nfrag = 8; }
-    else if (layer == 10) { *slot = L::A_PE; *nfrag = 4; }
-    else { *slot = L::A_DPE; *nfrag = 2; }
-    return true;
-  }
-  if (layer < 8) { *slot = L::Z_L0 + 16 * layer; *nfrag = 16; }
-  else if (layer == 8) { *slot = L::Z_F; *nfrag = 16; }
-  else if (layer == 9) { *slot = L::Z_D; *nfrag = 8; }
-  else if (layer == 10) { *slot = L::Z_A; *nfrag = 1; }
-  else { *slot = L::Z_RGB; *nfrag = 1; }
-  return true;
-}
 }  // namespace nerf
 
 extern "C" int nerf_mlp_debug_width(const nerf_mlp_arch* arch, int kind, int layer) {
-  int slot = 0, nfrag = 0;
-  const int ak = arch_kind(arch);
-  if (ak < 0) return -1;
-  if (arch_f32(arch)) return f32::debug_width(kind, layer);
-  if (!debug_slot(ak, kind, layer, &slot, &nfrag)) return -1;
-  return 16 * nfrag;
+  const Model m = resolve(arch);
+  if (!m.ok) return -1;
+  if (m.prec == Prec::F32) return f32::debug_width(kind, layer);
+  const DebugSlot ds = m.debug_slot(kind, layer);
+  return ds.nfrag ? 16 * ds.nfrag : -1;
 }
 
 extern "C" int nerf_mlp_debug_read(const nerf_mlp_arch* arch, const void* store, int kind, int layer, int64_t M,
                                    float* out, void* stream) {
-  NERF_ARCH_CHECK_ANY("nerf_mlp_debug_read");
-  if (arch_f32(arch)) {
+  NERF_RESOLVE("nerf_mlp_debug_read");
+  if (m.prec == Prec::F32) {
     NERF_REQUIRE(store && out, NERF_E_NULL, "nerf_mlp_debug_read: NULL pointer");
     return M <= 0 ? NERF_OK : f32::debug_read(store, kind, layer, M, out, as_stream(stream));
   }
-  int slot = 0, nfrag = 0;
-  const int ak = arch_kind(arch);
-  NERF_REQUIRE(debug_slot(ak, kind, layer, &slot, &nfrag), NERF_E_SHAPE, "nerf_mlp_debug_read: no such (kind, layer) in this architecture's stores");
+  const DebugSlot ds = m.debug_slot(kind, layer);
+  NERF_REQUIRE(ds.nfrag, NERF_E_SHAPE, "nerf_mlp_debug_read: no such (kind, layer) in this architecture's stores");
   NERF_REQUIRE(store && out, NERF_E_NULL, "nerf_mlp_debug_read: NULL pointer");
   if (M <= 0) return NERF_OK;
-  const bool sp = arch_s16(arch);
-  const int64_t stride = ak == 0 ? (sp ? (kind == 0 ? s16_astride16() : s16_zstride16()) : (kind == 0 ? astride16() : zstride16()))
-                         : ak == 1 ? (kind == 0 ? img_astride16(sp) : img_zstride16(sp)) : (kind == 0 ? small_astride16(sp) : small_zstride16(sp));
-  const int lo_off = !sp ? 0 : ak == 0 ? (kind == 0 ? s16::A_LO : s16::Z_LO) : ak == 1 ? (kind == 0 ? s16x::IMG_A_LO : s16x::IMG_Z_LO)
-                                                                                     : (kind == 0 ? s16x::SM_A_LO : s16x::SM_Z_LO);
-  hipLaunchKernelGGL(decode_frags_kernel, dim3(grid_for(M * nfrag * 2, 256)), dim3(256), 0, as_stream(stream), store, stride, slot, nfrag,
-                     M, out, lo_off);
+  const int lo_off = !m.split() ? 0 : kind == 0 ? m.info->a_lo : m.info->z_lo;       // split-bf16 stores: value = hi block + lo block
+  hipLaunchKernelGGL(decode_frags_kernel, dim3(grid_for(M * ds.nfrag * 2, 256)), dim3(256), 0, as_stream(stream), store,
+                     kind == 0 ? m.astride() : m.zstride(), ds.slot, ds.nfrag, M, out, lo_off);
   return check_launch("nerf_mlp_debug_read");
 }
 

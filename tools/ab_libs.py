@@ -1,7 +1,14 @@
-"""A/B of two BUILDS of the library (tools/ab_one.sh) on one box: the render chunk of the bench (coarse 32768 x 64 + fine 32768 x 192
-samples through the precision-22 inference forward) in alternating child processes, outputs compared bit for bit.
-    python tools/ab_libs.py tools/diag/libnerf_A.so tools/diag/libnerf_B.so [--rounds 3]      ("default" = the shipped library)"""
-import argparse, hashlib, json, os, subprocess, sys
+"""A/B of two BUILDS of the library (tools/ab_one.sh) on one box, in alternating fresh child processes ("default" = the shipped library).
+    python tools/ab_libs.py tools/diag/libnerf_A.so tools/diag/libnerf_B.so [--rounds 3]
+        the render chunk of the bench (coarse 32768 x 64 + fine 32768 x 192 samples through the precision-22 inference forward):
+        times, outputs compared bit for bit
+    python tools/ab_libs.py --models tools/diag/libnerf_A.so default
+        every MLP model (view / image / 2x64 in each of their precisions) through pack, training forward and backward at M = 65 and
+        8193, plus the fused view-model and hash-grid queries at B = 64, n = 3 and 64, on seeded inputs: sha256 of the output, the
+        packed buffer, the activation store, the dZ store (without the split-K partial slots), the gradients and d_x.  Exit 1 unless
+        every digest is the same in every library.
+Every child runs under a time limit, and after a child that failed or ran out of time no further child is started."""
+import argparse, json, os, subprocess, sys
 CHILD = r'''
 import sys, json, hashlib, torch
 sys.path.insert(0, ".")
@@ -26,17 +33,102 @@ for n in (64, 192):
     res[f"sha_{n}"] = hashlib.sha256(out.cpu().numpy().tobytes()).hexdigest()[:16]
 print(json.dumps(res))
 '''
-ap = argparse.ArgumentParser(); ap.add_argument("libs", nargs="+"); ap.add_argument("--rounds", type=int, default=3); ap.add_argument("--precision", type=int, default=22)
+CHILD_MODELS = r'''
+import sys, json, hashlib, ctypes as C, torch
+sys.path.insert(0, ".")
+from nerf_meets_mlx_amd import _native as N
+from oracle import nerf_oracle as O
+lib, dev, res = N.lib(), "cuda", {}
+sha = lambda t: hashlib.sha256(t.contiguous().cpu().numpy().tobytes()).hexdigest()[:16]
+zeros = lambda n, dt=torch.uint8: torch.zeros(n, dtype=dt, device=dev)
+rnd = lambda g, *shape: torch.randn(*shape, generator=g)
+MODELS = {"view": (8, 256, 63, 27, 4, 1, 4), "image": (8, 256, 40, 0, 4, 0, 3), "small": (2, 64, 32, 16, -1, 1, 4)}
+def packed_model(shape, prec, g):
+    arch = N.MlpArch(*MODELS[shape], prec); a = C.byref(arch)
+    params = (rnd(g, lib.nerf_mlp_param_count(a)) * 0.05).to(dev)
+    packed = zeros(lib.nerf_mlp_packed_bytes(a))
+    N.check(lib.nerf_mlp_pack(a, N.ptr(params), N.ptr(packed), N.stream()))
+    return arch, a, params, packed
+def rays_z(g, B, n):
+    o = torch.nn.functional.normalize(rnd(g, B, 3), dim=-1) * 4.0
+    return O.pack_rays(o, -o / 4.0 + 0.25 * rnd(g, B, 3), 2.0, 6.0).to(dev), (torch.sort(torch.rand(B, n, generator=g), -1).values * 4 + 2).to(dev)
+for shape, prec in [(s, p) for s in MODELS for p in (16, 32, 22) if (s, p) != ("small", 32)]:
+    for M in (65, 8193):
+        g = torch.Generator().manual_seed(1000 * prec + M)
+        arch, a, params, packed = packed_model(shape, prec, g)
+        cin, cout = arch.in_pos + arch.in_dir, arch.out_ch
+        x, d_out = (rnd(g, M, cin) * 0.5).to(dev), rnd(g, M, cout).to(dev)
+        acts, dz = zeros(lib.nerf_mlp_acts_bytes(a, M)), zeros(lib.nerf_mlp_dz_bytes(a, M))
+        out, grads, d_x = zeros(M * cout, torch.float32), zeros(params.numel(), torch.float32), zeros(M * arch.in_pos, torch.float32)
+        N.check(lib.nerf_mlp_forward_train(a, N.ptr(packed), N.ptr(x), M, N.ptr(out), N.ptr(acts), N.stream()))
+        if shape == "small":
+            N.check(lib.nerf_mlp_backward_inputs(a, N.ptr(packed), N.ptr(acts), N.ptr(d_out), M, N.ptr(dz), N.ptr(grads), N.ptr(d_x), N.stream()))
+        else:
+            N.check(lib.nerf_mlp_backward(a, N.ptr(packed), N.ptr(acts), N.ptr(d_out), M, N.ptr(dz), N.ptr(grads), N.stream()))
+        torch.cuda.synchronize()
+        assert bool(torch.isfinite(out).all()) and bool(torch.isfinite(grads).all()) and float(grads.abs().max()) > 0, (shape, prec, M)
+        partial = 2048 * (4096 + 64) * 4 if prec == 32 else 512 * (64 * 1024 + 256) * 4      # split-K partial slots behind the dZ blocks
+        res[f"{shape}{prec} M={M}"] = {"out": sha(out), "packed": sha(packed), "acts": sha(acts), "dz": sha(dz[:dz.numel() - partial]),
+                                       "grads": sha(grads), "d_x": sha(d_x) if shape == "small" else "-"}
+for n in (3, 64):
+    B = 64
+    for prec in (16, 32, 22):                      # nerf_query_fused: inference (no stores) and training forward
+        g = torch.Generator().manual_seed(7 * prec + n)
+        arch, a, params, packed = packed_model("view", prec, g)
+        rays, z = rays_z(g, B, n)
+        for train in (False, True):
+            acts, raw = zeros(lib.nerf_mlp_acts_bytes(a, B * n)), zeros(B * n * 4, torch.float32)
+            N.check(lib.nerf_query_fused(a, N.ptr(packed), N.ptr(rays), N.ptr(z), B, n, 0, N.ptr(raw), N.ptr(acts) if train else None, N.stream()))
+            torch.cuda.synchronize()
+            res[f"query view{prec} n={n} {'train' if train else 'infer'}"] = {"out": sha(raw), "acts": sha(acts)}
+    for prec in (16, 22):                          # nerf_ngp_query_fused / _lw on float32 tables
+        g = torch.Generator().manual_seed(11 * prec + n)
+        arch, a, params, packed = packed_model("small", prec, g)
+        rays, z = rays_z(g, B, n)
+        tables = (rnd(g, 16 * (1 << 14) * 2) * 0.1).to(dev)
+        reso = (C.c_int * 16)(*[int(16 * (2048 / 16) ** (l / 15)) for l in range(16)])
+        lw = (C.c_float * 16)(*[1.0] * 12 + [0.75, 0.5, 0.25, 0.0])
+        for train in (False, True):
+            for weighted in (False, True):
+                acts, raw = zeros(lib.nerf_mlp_acts_bytes(a, B * n)), zeros(B * n * 4, torch.float32)
+                tail = (3, 1.0 / 12.0, 0.5, N.ptr(raw), N.ptr(acts) if train else None, N.stream())
+                if weighted:
+                    N.check(lib.nerf_ngp_query_fused_lw(a, N.ptr(packed), N.ptr(rays), N.ptr(z), B, n, N.ptr(tables), None, 16, 14, 2, reso, lw, *tail))
+                else:
+                    N.check(lib.nerf_ngp_query_fused(a, N.ptr(packed), N.ptr(rays), N.ptr(z), B, n, N.ptr(tables), 16, 14, 2, reso, *tail))
+                torch.cuda.synchronize()
+                assert bool(torch.isfinite(raw).all()), (prec, n)
+                res[f"query small{prec} n={n} {'train' if train else 'infer'}{' lw' if weighted else ''}"] = {"out": sha(raw), "acts": sha(acts)}
+print(json.dumps(res))
+'''
+ap = argparse.ArgumentParser(); ap.add_argument("libs", nargs="+"); ap.add_argument("--rounds", type=int, default=None); ap.add_argument("--precision", type=int, default=22)
+ap.add_argument("--models", action="store_true", help="digests of every MLP model instead of the render-chunk timing")
+ap.add_argument("--timeout", type=float, default=300.0, help="seconds per child process")
 a = ap.parse_args()
+rounds = a.rounds if a.rounds is not None else (1 if a.models else 3)
 acc = {l: [] for l in a.libs}
-for r in range(a.rounds):
+for r in range(rounds):
     for l in a.libs:
         env = dict(os.environ)
         if l != "default": env["NERF_HIP_LIB"] = os.path.abspath(l)
-        out = subprocess.run([sys.executable, "-c", CHILD, str(a.precision)], capture_output=True, text=True, env=env)
+        else: env.pop("NERF_HIP_LIB", None)
+        cmd = [sys.executable, "-c", CHILD_MODELS] if a.models else [sys.executable, "-c", CHILD, str(a.precision)]
+        try:
+            out = subprocess.run(cmd, capture_output=True, text=True, env=env, timeout=a.timeout)
+        except subprocess.TimeoutExpired:
+            sys.exit(f"{l}: child ran past {a.timeout:.0f} s and was killed; no further child is started")
         line = [x for x in out.stdout.splitlines() if x.startswith("{")]
-        if not line: print(l, "FAILED", out.stderr[-500:]); continue
+        if out.returncode != 0 or not line:
+            sys.exit(f"{l}: child FAILED (exit {out.returncode}); no further child is started\n{out.stderr[-2000:]}")
         acc[l].append(json.loads(line[-1]))
+if a.models:
+    ref, bad = acc[a.libs[0]][0], 0
+    for case, digests in ref.items():
+        same = all(run.get(case) == digests for l in a.libs for run in acc[l])
+        bad += not same
+        print(f"{case}: " + " ".join(f"{k}={v}" for k, v in digests.items()) + ("   same in every library" if same else "   MISMATCH: " + json.dumps({l: acc[l][0].get(case) for l in a.libs})))
+    print(f"{len(ref)} cases x {len(a.libs)} libraries x {rounds} round(s): {bad} mismatching")
+    sys.exit(1 if bad else 0)
 for l in a.libs:
     rs = acc[l]
     print(f"{l}: coarse " + " ".join(f"{x['ms_64']:.3f}" for x in rs) + " ms | fine " + " ".join(f"{x['ms_192']:.3f}" for x in rs) + f" ms | sha {rs[0]['sha_64']} {rs[0]['sha_192']}")
