@@ -52,21 +52,6 @@ __device__ __forceinline__ int crossing_mask(uint32_t ins, int R, int i, int j, 
 
 __device__ __forceinline__ bool is_cell(int R, int i, int j, int k) { return i < R - 1 && j < R - 1 && k < R - 1; }
 
-// exclusive prefix of n over the workgroup's lanes in point order (wave scan, then the waves in order), plus `base`
-__device__ __forceinline__ int64_t block_offset(int n, int64_t base, int* sh) {
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  int x = n;
-  for (int o = 1; o < WAVE; o <<= 1) {
-    const int t = __shfl_up(x, o, WAVE);
-    if (lane >= o) x += t;
-  }
-  if (lane == 63) sh[w] = x;
-  __syncthreads();
-  int64_t b = base + (x - n);
-  for (int k = 0; k < w; ++k) b += sh[k];
-  return b;
-}
-
 // the volume's gradient at lattice point (c[0], c[1], c[2]) = linear l: central differences, one-sided at the border
 __device__ __forceinline__ void gradient_at(const float* __restrict__ vol, int R, const int* c, int l, const Box& bx, float* g) {
 #pragma unroll
@@ -97,8 +82,6 @@ __global__ void mesh_points_kernel(int R, Box bx, int64_t p0, int64_t count, flo
 // of (blk[nblk + b]).  4 B of volume per point from HBM (the 7 neighbours are L1 / L2 hits), 16 B written per workgroup.
 __global__ void __launch_bounds__(MESH_BLOCK) mesh_count_kernel(const float* __restrict__ vol, int R, float iso,
                                                                int64_t* __restrict__ blk, int64_t nblk) {
-  __shared__ int sh[2][MESH_BLOCK / 64];
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
   const int64_t n3 = (int64_t)R * R * R;
   const int64_t lg = (int64_t)blockIdx.x * MESH_BLOCK + threadIdx.x;
   int nv = 0, nt = 0;
@@ -108,17 +91,11 @@ __global__ void __launch_bounds__(MESH_BLOCK) mesh_count_kernel(const float* __r
     nv = __popc(crossing_mask(ins, R, i, j, k));
     if (is_cell(R, i, j, k)) nt = c_mc_table[ins][0];
   }
-  for (int o = 32; o > 0; o >>= 1) {
-    nv += __shfl_xor(nv, o, WAVE);
-    nt += __shfl_xor(nt, o, WAVE);
-  }
-  if (lane == 0) { sh[0][w] = nv; sh[1][w] = nt; }
-  __syncthreads();
+  int64_t t[2];
+  block_sum<MESH_BLOCK>({nv, nt}, t);
   if (threadIdx.x == 0) {
-    int64_t a = 0, b = 0;
-    for (int q = 0; q < MESH_BLOCK / 64; ++q) { a += sh[0][q]; b += sh[1][q]; }
-    blk[blockIdx.x] = a;
-    blk[nblk + blockIdx.x] = b;
+    blk[blockIdx.x] = t[0];
+    blk[nblk + blockIdx.x] = t[1];
   }
 }
 
@@ -129,7 +106,6 @@ __global__ void __launch_bounds__(MESH_BLOCK) mesh_vertices_kernel(const float* 
                                                                   const int64_t* __restrict__ blk, int64_t V, int* __restrict__ vbase,
                                                                   float* __restrict__ verts, float* __restrict__ normals,
                                                                   float* __restrict__ rows) {
-  __shared__ int sh[MESH_BLOCK / 64];
   const int64_t n3 = (int64_t)R * R * R;
   const int64_t lg = (int64_t)blockIdx.x * MESH_BLOCK + threadIdx.x;
   int m = 0, l = 0, c[3] = {0, 0, 0};
@@ -138,7 +114,7 @@ __global__ void __launch_bounds__(MESH_BLOCK) mesh_vertices_kernel(const float* 
     c[0] = l % R; c[1] = (l / R) % R; c[2] = l / (R * R);
     m = crossing_mask(corner_bits(vol, R, c[0], c[1], c[2], l, iso), R, c[0], c[1], c[2]);
   }
-  int64_t id = block_offset(__popc(m), blk[blockIdx.x], sh);
+  int64_t id = block_offset<MESH_BLOCK>(__popc(m), blk[blockIdx.x]);
   if (lg >= n3) return;
   vbase[l] = (int)id;
   if (!m) return;
@@ -204,7 +180,6 @@ __device__ __forceinline__ int edge_vertex(const float* __restrict__ vol, const 
 __global__ void __launch_bounds__(MESH_BLOCK) mesh_faces_kernel(const float* __restrict__ vol, int R, float iso,
                                                                const int64_t* __restrict__ blk_f, const int* __restrict__ vbase,
                                                                int64_t F, int* __restrict__ faces) {
-  __shared__ int sh[MESH_BLOCK / 64];
   const int64_t n3 = (int64_t)R * R * R;
   const int64_t lg = (int64_t)blockIdx.x * MESH_BLOCK + threadIdx.x;
   int nt = 0, i = 0, j = 0, k = 0;
@@ -217,7 +192,7 @@ __global__ void __launch_bounds__(MESH_BLOCK) mesh_faces_kernel(const float* __r
       nt = c_mc_table[ins][0];
     }
   }
-  const int64_t f0 = block_offset(nt, blk_f[blockIdx.x], sh);
+  const int64_t f0 = block_offset<MESH_BLOCK>(nt, blk_f[blockIdx.x]);
   for (int t = 0; t < nt && f0 + t < F; ++t) {
 #pragma unroll
     for (int v = 0; v < 3; ++v)
@@ -243,7 +218,11 @@ int box_of(const char* who, int R, const float* lo, const float* hi, Box* bx) {
   return NERF_OK;
 }
 
-int64_t mesh_blocks(int R) { return ((int64_t)R * R * R + MESH_BLOCK - 1) / MESH_BLOCK; }
+// blk[2][nblk] (vertices, faces), then every lattice point's vertex base
+PairWs mesh_ws(void* ws, int R) {
+  const int64_t n3 = (int64_t)R * R * R;
+  return pair_ws(ws, 2, (n3 + MESH_BLOCK - 1) / MESH_BLOCK, n3 * (int64_t)sizeof(int));
+}
 
 }  // namespace
 }  // namespace nerf
@@ -251,8 +230,7 @@ int64_t mesh_blocks(int R) { return ((int64_t)R * R * R + MESH_BLOCK - 1) / MESH
 using namespace nerf;
 
 extern "C" int64_t nerf_mesh_workspace_bytes(int res) {
-  if (res < 2 || res > NERF_MESH_MAX_RES) return -1;
-  return 2 * mesh_blocks(res) * (int64_t)sizeof(int64_t) + (int64_t)res * res * res * (int64_t)sizeof(int);
+  return res < 2 || res > NERF_MESH_MAX_RES ? -1 : mesh_ws(nullptr, res).bytes;
 }
 
 extern "C" int nerf_mesh_points(int res, const float* lo, const float* hi, int64_t p0, int64_t count, float* rays_out,
@@ -276,15 +254,14 @@ extern "C" int nerf_mesh_count(const float* vol, int res, float iso, void* works
   int rc = mesh_check("nerf_mesh_count", res, iso);
   if (rc) return rc;
   NERF_REQUIRE(vol && workspace && totals, NERF_E_NULL, "nerf_mesh_count: NULL pointer");
-  const int64_t nblk = mesh_blocks(res);
-  int64_t* blk = static_cast<int64_t*>(workspace);
-  hipLaunchKernelGGL(mesh_count_kernel, dim3((unsigned)nblk), dim3(MESH_BLOCK), 0, as_stream(stream), vol, res, iso, blk, nblk);
+  const PairWs w = mesh_ws(workspace, res);
+  hipLaunchKernelGGL(mesh_count_kernel, dim3((unsigned)w.nblk), dim3(MESH_BLOCK), 0, as_stream(stream), vol, res, iso, w.blk, w.nblk);
   rc = check_launch("nerf_mesh_count (count)");
   if (rc) return rc;
-  hipLaunchKernelGGL(occ_cull_scan_kernel, dim3(1), dim3(1024), 0, as_stream(stream), blk, nblk, totals);
+  hipLaunchKernelGGL(occ_cull_scan_kernel, dim3(1), dim3(1024), 0, as_stream(stream), w.blk, w.nblk, totals);
   rc = check_launch("nerf_mesh_count (scan of the vertices)");
   if (rc) return rc;
-  hipLaunchKernelGGL(occ_cull_scan_kernel, dim3(1), dim3(1024), 0, as_stream(stream), blk + nblk, nblk, totals + 1);
+  hipLaunchKernelGGL(occ_cull_scan_kernel, dim3(1), dim3(1024), 0, as_stream(stream), w.blk + w.nblk, w.nblk, totals + 1);
   return check_launch("nerf_mesh_count (scan of the faces)");
 }
 
@@ -298,11 +275,9 @@ extern "C" int nerf_mesh_write_vertices(const float* vol, int res, float iso, co
   NERF_REQUIRE(V >= 0 && V <= 3ll * res * res * res, NERF_E_SHAPE, "nerf_mesh_write_vertices: bad V %lld", (long long)V);
   if (V == 0) return NERF_OK;
   NERF_REQUIRE(vol && workspace && verts && normals, NERF_E_NULL, "nerf_mesh_write_vertices: NULL pointer");
-  const int64_t nblk = mesh_blocks(res);
-  const int64_t* blk = static_cast<const int64_t*>(workspace);
-  int* vbase = reinterpret_cast<int*>(static_cast<int64_t*>(workspace) + 2 * nblk);
-  hipLaunchKernelGGL(mesh_vertices_kernel, dim3((unsigned)nblk), dim3(MESH_BLOCK), 0, as_stream(stream), vol, res, iso, bx, blk,
-                     V, vbase, verts, normals, color_rows);
+  const PairWs w = mesh_ws(workspace, res);
+  hipLaunchKernelGGL(mesh_vertices_kernel, dim3((unsigned)w.nblk), dim3(MESH_BLOCK), 0, as_stream(stream), vol, res, iso, bx,
+                     (const int64_t*)w.blk, V, w.items, verts, normals, color_rows);
   return check_launch("nerf_mesh_write_vertices");
 }
 
@@ -314,10 +289,8 @@ extern "C" int nerf_mesh_write_faces(const float* vol, int res, float iso, void*
                (long long)F);
   if (F == 0) return NERF_OK;
   NERF_REQUIRE(vol && workspace && faces, NERF_E_NULL, "nerf_mesh_write_faces: NULL pointer");
-  const int64_t nblk = mesh_blocks(res);
-  const int64_t* blk = static_cast<const int64_t*>(workspace);
-  const int* vbase = reinterpret_cast<const int*>(blk + 2 * nblk);
-  hipLaunchKernelGGL(mesh_faces_kernel, dim3((unsigned)nblk), dim3(MESH_BLOCK), 0, as_stream(stream), vol, res, iso, blk + nblk,
-                     vbase, F, faces);
+  const PairWs w = mesh_ws(workspace, res);
+  hipLaunchKernelGGL(mesh_faces_kernel, dim3((unsigned)w.nblk), dim3(MESH_BLOCK), 0, as_stream(stream), vol, res, iso,
+                     (const int64_t*)(w.blk + w.nblk), (const int*)w.items, F, faces);
   return check_launch("nerf_mesh_write_faces");
 }

@@ -9,6 +9,8 @@
 #include <cmath>
 
 #include "common.h"
+#define NERF_SCAN_HELPERS_ONLY                      // block_sum alone: this unit launches no scan and carves no pair workspace
+#include "scan.h"
 
 namespace nerf {
 namespace {
@@ -55,11 +57,10 @@ __global__ void __launch_bounds__(MORPH_BLOCK) morph_pack_kernel(const float* vo
 template <bool DILATE>
 __global__ void __launch_bounds__(MORPH_BLOCK) morph_step_kernel(const u64* __restrict__ src, const u64* __restrict__ m_mask, int R,
                                                                 u64* __restrict__ dst, u64* count_src, u64* count_dst) {
-  __shared__ unsigned sh[2][MORPH_BLOCK / 64];
   const int W = morph_row_words(R);
   const int n_words = W * R * R;                     // <= 8 * 512 * 512
   const int sy = W, sz = W * R;
-  unsigned n_src = 0, n_dst = 0;                     // <= 64 * n_words < 2^31
+  int n_src = 0, n_dst = 0;                          // <= 64 * n_words < 2^31
   for (int w = blockIdx.x * MORPH_BLOCK + threadIdx.x; w < n_words; w += gridDim.x * MORPH_BLOCK) {
     const int wx = w % W, row = w / W;
     const int j = row % R, k = row / R;
@@ -72,28 +73,15 @@ __global__ void __launch_bounds__(MORPH_BLOCK) morph_step_kernel(const u64* __re
     const u64 zp = k < R - 1 ? src[w + sz] : 0ull;
     const u64 d = DILATE ? (c | xm | xp | ym | yp | zm | zp) & m_mask[w] : c & xm & xp & ym & yp & zm & zp;
     dst[w] = d;
-    n_src += (unsigned)__popcll(c);
-    n_dst += (unsigned)__popcll(d);
+    n_src += __popcll(c);
+    n_dst += __popcll(d);
   }
   if (!count_src && !count_dst) return;
-  for (int o = 32; o > 0; o >>= 1) {
-    n_src += __shfl_xor(n_src, o, WAVE);
-    n_dst += __shfl_xor(n_dst, o, WAVE);
-  }
-  if ((threadIdx.x & 63) == 0) {
-    sh[0][threadIdx.x >> 6] = n_src;
-    sh[1][threadIdx.x >> 6] = n_dst;
-  }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    u64 a = 0ull, b = 0ull;
-    for (int q = 0; q < MORPH_BLOCK / 64; ++q) {
-      a += sh[0][q];
-      b += sh[1][q];
-    }
-    if (count_src && a) atomicAdd(count_src, a);
-    if (count_dst && b) atomicAdd(count_dst, b);
-  }
+  int64_t t[2];
+  block_sum<MORPH_BLOCK>({n_src, n_dst}, t);
+  if (threadIdx.x != 0) return;
+  if (count_src && t[0]) atomicAdd(count_src, (u64)t[0]);
+  if (count_dst && t[1]) atomicAdd(count_dst, (u64)t[1]);
 }
 
 // ---- apply: 4 B read, 4 B written per voxel (the two mask words of a wave's voxels are broadcast cache hits).  A voxel of M that

@@ -43,6 +43,14 @@ __device__ __forceinline__ bool occupied(const uint32_t* __restrict__ bits, int6
   return c >= 0 && ((bits[c >> 5] >> (c & 31)) & 1u);
 }
 
+// a kept sample: its depth (4 B) and its ray's row (44 B) at o
+__device__ __forceinline__ void store_sample(float* rows_out, float* z_out, int64_t o, const float* rr, float zv) {
+  z_out[o] = zv;
+  float* dst = rows_out + o * NERF_RAY_STRIDE;
+#pragma unroll
+  for (int q = 0; q < NERF_RAY_STRIDE; ++q) dst[q] = rr[q];
+}
+
 // ---- jittered points: 44 + 4 B written per cell, nothing read.  Row = [p, d = 0, near = far = 0, viewdirs = 0], z = 0, so that
 // nerf_ngp_query_fused_h evaluates the field at o + 0 * 0 = p exactly (n = 1).  d = 0 is harmless there: the kernel neither
 // normalises d nor the view direction (sh_eval is a polynomial: SH of 0 is the constant band), near / far are not read, and sigma
@@ -153,8 +161,6 @@ __global__ void __launch_bounds__(CULL_BLOCK) occ_cull_count_kernel(const float*
                                                                     int64_t M, int n, const uint32_t* __restrict__ bits, int log2R,
                                                                     float pos_scale, float pos_offset, int64_t* __restrict__ counts,
                                                                     float* __restrict__ raw_fill) {
-  __shared__ int sh[CULL_BLOCK / 64];
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
   int kept = 0;
   for (int k = 0; k < CULL_ROUNDS; ++k) {
     const int64_t s = (int64_t)blockIdx.x * CULL_SPAN + k * CULL_BLOCK + threadIdx.x;
@@ -163,14 +169,8 @@ __global__ void __launch_bounds__(CULL_BLOCK) occ_cull_count_kernel(const float*
     kept += keep;
     if (!keep && raw_fill) reinterpret_cast<float4*>(raw_fill)[s] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
   }
-  for (int o = 32; o > 0; o >>= 1) kept += __shfl_xor(kept, o, WAVE);
-  if (lane == 0) sh[w] = kept;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    int64_t t = 0;
-    for (int k = 0; k < CULL_BLOCK / 64; ++k) t += sh[k];
-    counts[blockIdx.x] = t;
-  }
+  const int64_t t = block_sum<CULL_BLOCK>(kept);
+  if (threadIdx.x == 0) counts[blockIdx.x] = t;
 }
 
 // ---- cull, pass 2 (one workgroup): occ_cull_scan_kernel (scan.h).  8 + 8 B per 1024 samples.
@@ -200,10 +200,7 @@ __global__ void __launch_bounds__(CULL_BLOCK) occ_cull_compact_kernel(const floa
     if (keep) {
       const int64_t o = before + __popcll(m & ((1ull << lane) - 1ull));
       idx_out[o] = s;
-      z_out[o] = zv;
-      float* dst = rays_out + o * NERF_RAY_STRIDE;
-#pragma unroll
-      for (int q = 0; q < NERF_RAY_STRIDE; ++q) dst[q] = rr[q];
+      store_sample(rays_out, z_out, o, rr, zv);
     }
     base += round_total;
     __syncthreads();                                            // sh is rewritten by the next round
@@ -218,48 +215,68 @@ __global__ void __launch_bounds__(CULL_BLOCK) occ_cull_compact_kernel(const floa
 constexpr int MARCH_BLOCK = 256;                    // rays per march workgroup
 constexpr int MARCH_GROUP = 8;
 
+// what a march is: the rays, their jitter (per ray, or one constant), the bitfield (NULL: every cell counts as occupied) and the
+// step.  Filled by march_args on the host, passed by value to the four march kernels.
+struct MarchArgs {
+  const float* rays;
+  int64_t B;
+  const float* jitter;
+  float jitter_const;
+  const uint32_t* bits;
+  int log2R;
+  float pos_scale, pos_offset, step_world;
+  int march_steps;
+  __device__ __forceinline__ float jitter_of(int64_t b) const { return jitter ? jitter[b] : jitter_const; }
+  __device__ __forceinline__ const float* row(int64_t b) const { return rays + b * NERF_RAY_STRIDE; }
+};
+
 struct MarchRay {
+  // the ray's row, in registers: the kernels' pointers arrive inside MarchArgs, so without __restrict__, and a row read through
+  // memory would be read again behind every store of a kept sample (and keep those stores from merging)
+  float r[NERF_RAY_STRIDE];
   float t0, t1, dt, j;
   int kmax;                                         // 0: no sample (axis-parallel, NaN / inf, missed box)
 };
 
-__device__ __forceinline__ MarchRay march_setup(const float* __restrict__ rr, float jitter, float pos_scale, float pos_offset,
-                                                float step_world, int march_steps) {
+__device__ __forceinline__ MarchRay march_setup(const MarchArgs& a, int64_t b) {
+  const float jitter = a.jitter_of(b);
   MarchRay m;
+#pragma unroll
+  for (int q = 0; q < NERF_RAY_STRIDE; ++q) m.r[q] = a.row(b)[q];
+  const float* rr = m.r;
   m.t0 = rr[6]; m.t1 = rr[7]; m.j = jitter; m.kmax = 0; m.dt = 0.0f;
   bool ok = isfinite(m.t0) && isfinite(m.t1) && isfinite(jitter);
 #pragma unroll
-  for (int a = 0; a < 6; ++a) ok = ok && isfinite(rr[a]);
+  for (int x = 0; x < 6; ++x) ok = ok && isfinite(rr[x]);
   ok = ok && rr[3] != 0.0f && rr[4] != 0.0f && rr[5] != 0.0f;
   if (!ok) return m;
-  const float lo = (0.0f - pos_offset) / pos_scale, hi = (1.0f - pos_offset) / pos_scale;      // the box, world units
+  const float lo = (0.0f - a.pos_offset) / a.pos_scale, hi = (1.0f - a.pos_offset) / a.pos_scale;      // the box, world units
 #pragma unroll
-  for (int a = 0; a < 3; ++a) {
-    const float ta = (lo - rr[a]) / rr[3 + a], tb = (hi - rr[a]) / rr[3 + a];
+  for (int x = 0; x < 3; ++x) {
+    const float ta = (lo - rr[x]) / rr[3 + x], tb = (hi - rr[x]) / rr[3 + x];
     m.t0 = fmaxf(m.t0, fminf(ta, tb));
     m.t1 = fminf(m.t1, fmaxf(ta, tb));
   }
   // |d| through a double square root rounded once to float: the correctly rounded float square root, which the float
   // instruction sequence is not in every case
   const float dn = (float)sqrt((double)((rr[3] * rr[3] + rr[4] * rr[4]) + rr[5] * rr[5]));
-  m.dt = step_world / dn;
-  if (m.t0 < m.t1 && m.dt > 0.0f) m.kmax = 2 * march_steps;
+  m.dt = a.step_world / dn;
+  if (m.t0 < m.t1 && m.dt > 0.0f) m.kmax = 2 * a.march_steps;
   return m;
 }
 
-// Visits the kept samples of one ray in depth order: fn(i, z) for the i-th sample of this call.  The walk starts at candidate
+// Visits the kept samples of one ray in depth order: fn(i, z, row) for the i-th sample of this call.  The walk starts at candidate
 // k_start with kept_start samples already kept (0 and 0: the whole march), and stops after max_new samples, at the cap of
 // march_steps kept in all, or where the walk ends.  k_end = the candidate to resume at, or m.kmax when the ray has no candidate
 // left.  Returns the number of samples visited.  RESUME = false (the one-shot march: 0, 0, march_steps) compiles the resume
 // bookkeeping away, leaving k_end unset.
 template <bool RESUME, class F>
-__device__ __forceinline__ int march_ray(const float* __restrict__ rr, const MarchRay& m, const uint32_t* __restrict__ bits,
-                                         int log2R, float pos_scale, float pos_offset, int march_steps, int k_start, int kept_start,
-                                         int max_new, int& k_end, F&& fn) {
+__device__ __forceinline__ int march_ray(const MarchArgs& a, const MarchRay& m, int k_start, int kept_start, int max_new, int& k_end,
+                                         F&& fn) {
   int kept = kept_start;
   if (RESUME) {
     k_end = m.kmax;
-    if (kept >= march_steps) return 0;
+    if (kept >= a.march_steps) return 0;
   }
   for (int k0 = k_start; k0 < m.kmax; k0 += MARCH_GROUP) {
     float zs[MARCH_GROUP];
@@ -268,16 +285,16 @@ __device__ __forceinline__ int march_ray(const float* __restrict__ rr, const Mar
 #pragma unroll
     for (int g = 0; g < MARCH_GROUP; ++g) {
       zs[g] = m.t0 + ((float)(k0 + g) + m.j) * m.dt;
-      cs[g] = cell_of(rr, zs[g], pos_scale, pos_offset, log2R);
+      cs[g] = cell_of(m.r, zs[g], a.pos_scale, a.pos_offset, a.log2R);
     }
 #pragma unroll
-    for (int g = 0; g < MARCH_GROUP; ++g) ws[g] = (bits && cs[g] >= 0) ? bits[cs[g] >> 5] : 0xFFFFFFFFu;
+    for (int g = 0; g < MARCH_GROUP; ++g) ws[g] = (a.bits && cs[g] >= 0) ? a.bits[cs[g] >> 5] : 0xFFFFFFFFu;
 #pragma unroll
     for (int g = 0; g < MARCH_GROUP; ++g) {
       if (k0 + g >= m.kmax || !(zs[g] < m.t1)) return kept - kept_start;
       if (cs[g] >= 0 && ((ws[g] >> (cs[g] & 31)) & 1u)) {
-        fn(kept - kept_start, zs[g]);
-        if (++kept == march_steps) return kept - kept_start;
+        fn(kept - kept_start, zs[g], m.r);
+        if (++kept == a.march_steps) return kept - kept_start;
         if (RESUME && kept - kept_start == max_new) {
           k_end = k0 + g + 1;
           return max_new;
@@ -288,169 +305,100 @@ __device__ __forceinline__ int march_ray(const float* __restrict__ rr, const Mar
   return kept - kept_start;
 }
 
+// the one-shot march of ray b: every kept sample to fn, their number back
+template <class F>
+__device__ __forceinline__ int march_whole(const MarchArgs& a, int64_t b, F&& fn) {
+  int k_end;
+  return march_ray<false>(a, march_setup(a, b), 0, 0, a.march_steps, k_end, fn);
+}
+
 // ---- march, pass 1: per ray the number of kept samples (int32 to the workspace), per workgroup of 256 rays their sum (int64).
 // Per ray: 44 B of row read (the 32 B of o, d, near, far used), 4 B of jitter, one bitfield word per candidate (the 256 KiB field of
 // a 128^3 grid: L2 hits, not HBM); 4 B written.
-__global__ void __launch_bounds__(MARCH_BLOCK) occ_march_count_kernel(const float* __restrict__ rays, int64_t B,
-                                                                      const float* __restrict__ jitter, float jitter_const,
-                                                                      const uint32_t* __restrict__ bits, int log2R, float pos_scale,
-                                                                      float pos_offset, float step_world, int march_steps,
-                                                                      int* __restrict__ ray_counts, int64_t* __restrict__ blk) {
-  __shared__ int sh[MARCH_BLOCK / 64];
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+__global__ void __launch_bounds__(MARCH_BLOCK) occ_march_count_kernel(MarchArgs a, int* __restrict__ ray_counts,
+                                                                      int64_t* __restrict__ blk) {
   const int64_t b = (int64_t)blockIdx.x * MARCH_BLOCK + threadIdx.x;
   int n = 0;
-  if (b < B) {
-    const float* rr = rays + b * NERF_RAY_STRIDE;
-    const MarchRay m = march_setup(rr, jitter ? jitter[b] : jitter_const, pos_scale, pos_offset, step_world, march_steps);
-    int k_end;
-    n = march_ray<false>(rr, m, bits, log2R, pos_scale, pos_offset, march_steps, 0, 0, march_steps, k_end, [](int, float) {});
-    ray_counts[b] = n;
-  }
-  int t = n;
-  for (int o = 32; o > 0; o >>= 1) t += __shfl_xor(t, o, WAVE);
-  if (lane == 0) sh[w] = t;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    int64_t s = 0;
-    for (int k = 0; k < MARCH_BLOCK / 64; ++k) s += sh[k];
-    blk[blockIdx.x] = s;
-  }
+  if (b < a.B) ray_counts[b] = n = march_whole(a, b, [](int, float, const float*) {});
+  const int64_t s = block_sum<MARCH_BLOCK>(n);
+  if (threadIdx.x == 0) blk[blockIdx.x] = s;
 }
 
 // ---- march, pass 3 (pass 2 is occ_cull_scan_kernel over the workgroup sums): the ray's offset = its workgroup's offset + the
 // exclusive scan of the counts inside the workgroup (8 B written), then the same march again, and per kept sample its ray row
 // (44 B) and depth (4 B) written at offset + rank.  Reads as pass 1, plus 4 B of count per ray and 8 B per workgroup.
-__global__ void __launch_bounds__(MARCH_BLOCK) occ_march_write_kernel(const float* __restrict__ rays, int64_t B,
-                                                                      const float* __restrict__ jitter, float jitter_const,
-                                                                      const uint32_t* __restrict__ bits, int log2R, float pos_scale,
-                                                                      float pos_offset, float step_world, int march_steps,
-                                                                      const int* __restrict__ ray_counts,
+__global__ void __launch_bounds__(MARCH_BLOCK) occ_march_write_kernel(MarchArgs a, const int* __restrict__ ray_counts,
                                                                       const int64_t* __restrict__ blk, int64_t* __restrict__ offsets,
                                                                       float* __restrict__ rows_out, float* __restrict__ z_out) {
-  __shared__ int sh[MARCH_BLOCK / 64];
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
   const int64_t b = (int64_t)blockIdx.x * MARCH_BLOCK + threadIdx.x;
-  const int n = b < B ? ray_counts[b] : 0;
-  int x = n;                                                    // inclusive wave scan of the counts
-  for (int o = 1; o < WAVE; o <<= 1) {
-    const int t = __shfl_up(x, o, WAVE);
-    if (lane >= o) x += t;
-  }
-  if (lane == 63) sh[w] = x;
-  __syncthreads();
-  int64_t base = blk[blockIdx.x] + (x - n);
-  for (int k = 0; k < w; ++k) base += sh[k];
-  if (b >= B) return;
+  const int n = b < a.B ? ray_counts[b] : 0;
+  const int64_t base = block_offset<MARCH_BLOCK>(n, blk[blockIdx.x]);
+  if (b >= a.B) return;
   offsets[b] = base;
   if (n == 0) return;
-  const float* rr = rays + b * NERF_RAY_STRIDE;
-  const MarchRay m = march_setup(rr, jitter ? jitter[b] : jitter_const, pos_scale, pos_offset, step_world, march_steps);
-  int k_end;
-  march_ray<false>(rr, m, bits, log2R, pos_scale, pos_offset, march_steps, 0, 0, march_steps, k_end, [&](int k, float zv) {
-    const int64_t o = base + k;
-    z_out[o] = zv;
-    float* dst = rows_out + o * NERF_RAY_STRIDE;
-#pragma unroll
-    for (int q = 0; q < NERF_RAY_STRIDE; ++q) dst[q] = rr[q];
-  });
+  march_whole(a, b, [&](int k, float zv, const float* rr) { store_sample(rows_out, z_out, base + k, rr, zv); });
 }
 
 // ---- resumed march of the round renderer (include/nerf_hip.h "early ray termination").  One lane per entry i of the live list;
 // the ray b = live[i] resumes at its saved candidate and kept count (istate[b] = k, kept, samples, flags) and takes up to max_new
-// further samples.  It stays live when it took max_new and has candidates left; a ray the fold has terminated takes none.
-// Per entry: 4 B of live id, 16 B of state, the row (32 B used) and jitter, one bitfield word per candidate; entry = 2 n + live.
-__device__ __forceinline__ int resume_ray(const float* __restrict__ rays, int64_t B, const float* __restrict__ jitter,
-                                          float jitter_const, const uint32_t* __restrict__ bits, int log2R, float pos_scale,
-                                          float pos_offset, float step_world, int march_steps, int b, const int* __restrict__ istate,
-                                          int max_new, bool& more, int& k_end, float* __restrict__ rows_out,
-                                          float* __restrict__ z_out, int64_t base) {
+// further samples, each to fn.  It stays live when it took max_new and has candidates left; a ray the fold has terminated takes
+// none.  Per entry: 4 B of live id, 16 B of state, the row (32 B used) and jitter, one bitfield word per candidate;
+// entry = 2 n + live.
+template <class F>
+__device__ __forceinline__ int resume_ray(const MarchArgs& a, int b, const int* __restrict__ istate, int max_new, bool& more,
+                                          int& k_end, F&& fn) {
   more = false;
   k_end = 0;
-  if (b < 0 || b >= B || (istate[4 * b + 3] & NERF_ERT_TERMINATED)) return 0;
-  const float* rr = rays + (int64_t)b * NERF_RAY_STRIDE;
-  const MarchRay m = march_setup(rr, jitter ? jitter[b] : jitter_const, pos_scale, pos_offset, step_world, march_steps);
-  const int n = march_ray<true>(rr, m, bits, log2R, pos_scale, pos_offset, march_steps, istate[4 * b], istate[4 * b + 1], max_new, k_end,
-                          [&](int k, float zv) {
-                            if (!rows_out) return;
-                            const int64_t o = base + k;
-                            z_out[o] = zv;
-                            float* dst = rows_out + o * NERF_RAY_STRIDE;
-#pragma unroll
-                            for (int q = 0; q < NERF_RAY_STRIDE; ++q) dst[q] = rr[q];
-                          });
+  if (b < 0 || b >= a.B || (istate[4 * b + 3] & NERF_ERT_TERMINATED)) return 0;
+  const MarchRay m = march_setup(a, b);
+  const int n = march_ray<true>(a, m, istate[4 * b], istate[4 * b + 1], max_new, k_end, fn);
   more = k_end < m.kmax;
   return n;
 }
 
-__global__ void __launch_bounds__(MARCH_BLOCK) ert_march_count_kernel(const float* __restrict__ rays, int64_t B,
-                                                                      const float* __restrict__ jitter, float jitter_const,
-                                                                      const uint32_t* __restrict__ bits, int log2R, float pos_scale,
-                                                                      float pos_offset, float step_world, int march_steps,
-                                                                      const int* __restrict__ live, int64_t A,
+__global__ void __launch_bounds__(MARCH_BLOCK) ert_march_count_kernel(MarchArgs a, const int* __restrict__ live, int64_t A,
                                                                       const int* __restrict__ istate, int max_new,
                                                                       int* __restrict__ entry, int64_t* __restrict__ blk, int64_t nblk) {
-  __shared__ int sh[2][MARCH_BLOCK / 64];
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
   const int64_t i = (int64_t)blockIdx.x * MARCH_BLOCK + threadIdx.x;
   int n = 0;
   bool more = false;
   if (i < A) {
     int k_end;
-    n = resume_ray(rays, B, jitter, jitter_const, bits, log2R, pos_scale, pos_offset, step_world, march_steps, live[i], istate,
-                   max_new, more, k_end, nullptr, nullptr, 0);
+    n = resume_ray(a, live[i], istate, max_new, more, k_end, [](int, float, const float*) {});
     entry[i] = 2 * n + (more ? 1 : 0);
   }
-  int t = n, l = more ? 1 : 0;
-  for (int o = 32; o > 0; o >>= 1) {
-    t += __shfl_xor(t, o, WAVE);
-    l += __shfl_xor(l, o, WAVE);
-  }
-  if (lane == 0) { sh[0][w] = t; sh[1][w] = l; }
-  __syncthreads();
+  int64_t t[2];
+  block_sum<MARCH_BLOCK>({n, more ? 1 : 0}, t);
   if (threadIdx.x == 0) {
-    int64_t s = 0, a = 0;
-    for (int k = 0; k < MARCH_BLOCK / 64; ++k) { s += sh[0][k]; a += sh[1][k]; }
-    blk[blockIdx.x] = s;
-    blk[nblk + blockIdx.x] = a;
+    blk[blockIdx.x] = t[0];
+    blk[nblk + blockIdx.x] = t[1];
   }
 }
 
 // offsets[i] = the entry's sample offset, offsets[A] = K, the live rays in order to live_out, then the same walk again writing the
 // rows (44 B) and depths (4 B), and the ray's resume point (8 B of state).  Reads as the count, plus 4 B of entry per ray.
-__global__ void __launch_bounds__(MARCH_BLOCK) ert_march_write_kernel(const float* __restrict__ rays, int64_t B,
-                                                                      const float* __restrict__ jitter, float jitter_const,
-                                                                      const uint32_t* __restrict__ bits, int log2R, float pos_scale,
-                                                                      float pos_offset, float step_world, int march_steps,
-                                                                      const int* __restrict__ live, int64_t A, int* __restrict__ istate,
-                                                                      int max_new, const int* __restrict__ entry,
-                                                                      const int64_t* __restrict__ blk, int64_t nblk,
-                                                                      int64_t* __restrict__ offsets, int* __restrict__ live_out,
-                                                                      float* __restrict__ rows_out, float* __restrict__ z_out) {
-  __shared__ int sh[2][MARCH_BLOCK / 64];
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+__global__ void __launch_bounds__(MARCH_BLOCK) ert_march_write_kernel(MarchArgs a, const int* __restrict__ live, int64_t A,
+                                                                      int* __restrict__ istate, int max_new,
+                                                                      const int* __restrict__ entry, const int64_t* __restrict__ blk,
+                                                                      int64_t nblk, int64_t* __restrict__ offsets,
+                                                                      int* __restrict__ live_out, float* __restrict__ rows_out,
+                                                                      float* __restrict__ z_out) {
   const int64_t i = (int64_t)blockIdx.x * MARCH_BLOCK + threadIdx.x;
   const int e = i < A ? entry[i] : 0;
   const int n = e >> 1, l = e & 1;
-  int x = n, y = l;                                             // inclusive wave scans of the counts and the live flags
-  for (int o = 1; o < WAVE; o <<= 1) {
-    const int t = __shfl_up(x, o, WAVE), u = __shfl_up(y, o, WAVE);
-    if (lane >= o) { x += t; y += u; }
-  }
-  if (lane == 63) { sh[0][w] = x; sh[1][w] = y; }
-  __syncthreads();
-  int64_t base = blk[blockIdx.x] + (x - n), lbase = blk[nblk + blockIdx.x] + (y - l);
-  for (int k = 0; k < w; ++k) { base += sh[0][k]; lbase += sh[1][k]; }
+  int64_t off[2] = {blk[blockIdx.x], blk[nblk + blockIdx.x]};   // of the entry's samples, of its place in live_out
+  block_offset<MARCH_BLOCK>({n, l}, off);
   if (i >= A) return;
+  const int64_t base = off[0];
   offsets[i] = base;
   if (i == A - 1) offsets[A] = base + n;
   const int b = live[i];
-  if (l) live_out[lbase] = b;
+  if (l) live_out[off[1]] = b;
   if (n == 0) return;
   bool more;
   int k_end;
-  resume_ray(rays, B, jitter, jitter_const, bits, log2R, pos_scale, pos_offset, step_world, march_steps, b, istate, max_new, more,
-             k_end, rows_out, z_out, base);
+  resume_ray(a, b, istate, max_new, more, k_end,
+             [&](int k, float zv, const float* rr) { store_sample(rows_out, z_out, base + k, rr, zv); });
   istate[4 * b] = k_end;
   istate[4 * b + 1] += n;
 }
@@ -476,6 +424,47 @@ __global__ void scatter_rows_kernel(const float* __restrict__ src, const int64_t
 
 bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
+int occ_res_check(const char* who, int log2_res) {
+  NERF_REQUIRE(log2_res >= 2 && log2_res <= 10, NERF_E_SHAPE, "%s: need 2 <= log2_res <= 10", who);
+  return NERF_OK;
+}
+
+int64_t march_blocks(int64_t n) { return (n + MARCH_BLOCK - 1) / MARCH_BLOCK; }
+int64_t ray_ints(int64_t B) { return ((B * (int64_t)sizeof(int) + 7) / 8) * 8; }
+
+// the workspaces of the two march pairs: blk[nblk], then one count per ray; and blk[2][nblk], then one entry per live ray.  The
+// entries lie where the workspace of B rays puts them, whatever A <= B is; the two rows of blk are those of the launch (A).
+PairWs march_ws(void* ws, int64_t B) { return pair_ws(ws, 1, march_blocks(B), ray_ints(B)); }
+PairWs ert_ws(void* ws, int64_t B, int64_t A) {
+  PairWs w = pair_ws(ws, 2, march_blocks(B), ray_ints(B));
+  w.nblk = march_blocks(A);
+  return w;
+}
+
+// The checks every march entry starts with, in this order (which fault wins is part of the behaviour), then the description the
+// kernels take.  `offsets`: the entry's first output, whatever it calls it.
+int march_args(const char* who, const float* rays, int64_t B, const float* jitter, float jitter_const, const uint32_t* bits,
+               int log2_res, float pos_scale, float pos_offset, float step_world, int march_steps, void* workspace,
+               int64_t* offsets, MarchArgs* a) {
+  if (int rc = occ_res_check(who, log2_res)) return rc;
+  NERF_REQUIRE(B >= 0 && B < (1ll << 40), NERF_E_SHAPE, "%s: bad B", who);
+  NERF_REQUIRE(march_steps >= 1 && march_steps <= NERF_MARCH_MAX_STEPS, NERF_E_SHAPE, "%s: need 1 <= march_steps <= %d (got %d)",
+               who, NERF_MARCH_MAX_STEPS, march_steps);
+  NERF_REQUIRE(pos_scale != 0.0f && step_world > 0.0f, NERF_E_SHAPE, "%s: need pos_scale != 0 and step_world > 0", who);
+  NERF_REQUIRE(offsets, NERF_E_NULL, "%s: NULL offsets", who);
+  NERF_REQUIRE(B == 0 || (rays && workspace), NERF_E_NULL, "%s: NULL pointer", who);
+  *a = MarchArgs{rays, B, jitter, jitter_const, bits, log2_res, pos_scale, pos_offset, step_world, march_steps};
+  return NERF_OK;
+}
+
+// the early-termination entries' checks on top
+int ert_march_check(const char* who, const MarchArgs& a, const int* live, int64_t A, const int* istate, int max_new) {
+  NERF_REQUIRE(a.B < (1ll << 31) && A >= 0 && A <= a.B, NERF_E_SHAPE, "%s: need 0 <= A <= B < 2^31", who);
+  NERF_REQUIRE(max_new >= 1, NERF_E_SHAPE, "%s: need max_new >= 1 (got %d)", who, max_new);
+  NERF_REQUIRE(A == 0 || (live && istate), NERF_E_NULL, "%s: NULL live / istate", who);
+  return NERF_OK;
+}
+
 }  // namespace
 }  // namespace nerf
 
@@ -495,7 +484,7 @@ extern "C" int64_t nerf_occ_cull_workspace_bytes(int64_t B, int n) {
 
 extern "C" int nerf_occ_points(int log2_res, int64_t cell0, int64_t count, uint64_t seed, uint64_t update, float pos_scale,
                                float pos_offset, float* rays_out, float* z_out, void* stream) {
-  NERF_REQUIRE(log2_res >= 2 && log2_res <= 10, NERF_E_SHAPE, "nerf_occ_points: need 2 <= log2_res <= 10");
+  if (int rc = occ_res_check("nerf_occ_points", log2_res)) return rc;
   const int64_t ncells = 1ll << (3 * log2_res);
   NERF_REQUIRE(cell0 >= 0 && count >= 0 && cell0 + count <= ncells, NERF_E_SHAPE,
                "nerf_occ_points: cells [%lld, %lld) outside the grid of %lld", (long long)cell0, (long long)(cell0 + count),
@@ -530,7 +519,7 @@ extern "C" int nerf_occ_merge_ex(float* density, const float* raw, int64_t count
 
 extern "C" int nerf_occ_finalize(const float* density, int log2_res, float thr_cap, void* workspace, float* thr_out,
                                  uint32_t* bits, void* stream) {
-  NERF_REQUIRE(log2_res >= 2 && log2_res <= 10, NERF_E_SHAPE, "nerf_occ_finalize: need 2 <= log2_res <= 10");
+  if (int rc = occ_res_check("nerf_occ_finalize", log2_res)) return rc;
   NERF_REQUIRE(density && workspace && bits, NERF_E_NULL, "nerf_occ_finalize: NULL pointer");
   const int64_t ncells = 1ll << (3 * log2_res);
   const int64_t nparts = (ncells + SUM_SPAN - 1) / SUM_SPAN;
@@ -546,15 +535,11 @@ extern "C" int nerf_occ_finalize(const float* density, int log2_res, float thr_c
 extern "C" int nerf_occ_cull(const float* rays, const float* z, int64_t B, int n, const uint32_t* bits, int log2_res,
                              float pos_scale, float pos_offset, void* workspace, int64_t* idx_out, int64_t* count_out,
                              float* rays_out, float* z_out, float* raw_fill, void* stream) {
-  NERF_REQUIRE(log2_res >= 2 && log2_res <= 10, NERF_E_SHAPE, "nerf_occ_cull: need 2 <= log2_res <= 10");
+  if (int rc = occ_res_check("nerf_occ_cull", log2_res)) return rc;
   NERF_REQUIRE(B >= 0 && n >= 0, NERF_E_SHAPE, "nerf_occ_cull: bad sizes");
   NERF_REQUIRE(count_out, NERF_E_NULL, "nerf_occ_cull: NULL count_out");
   const int64_t M = B * (int64_t)n;
-  if (M == 0) {
-    hipError_t e = hipMemsetAsync(count_out, 0, sizeof(int64_t), as_stream(stream));
-    if (e != hipSuccess) return fail(NERF_E_HIP, "nerf_occ_cull: %s", hipGetErrorString(e));
-    return NERF_OK;
-  }
+  if (M == 0) return zero_i64("nerf_occ_cull", count_out, 1, stream);
   NERF_REQUIRE(rays && z && bits && workspace && idx_out && rays_out && z_out, NERF_E_NULL, "nerf_occ_cull: NULL pointer");
   NERF_REQUIRE(!raw_fill || aligned16(raw_fill), NERF_E_SHAPE, "nerf_occ_cull: raw_fill must be 16-byte aligned");
   const int64_t nblk = (M + CULL_SPAN - 1) / CULL_SPAN;
@@ -572,58 +557,36 @@ extern "C" int nerf_occ_cull(const float* rays, const float* z, int64_t B, int n
   return check_launch("nerf_occ_cull (compact)");
 }
 
-extern "C" int64_t nerf_occ_march_workspace_bytes(int64_t B) {
-  if (B < 0) return -1;
-  const int64_t nblk = (B + MARCH_BLOCK - 1) / MARCH_BLOCK;
-  return nblk * (int64_t)sizeof(int64_t) + ((B * (int64_t)sizeof(int) + 7) / 8) * 8;
-}
-
-static int march_check(const char* who, const float* rays, int64_t B, int log2_res, float pos_scale, float step_world,
-                       int march_steps, void* workspace, int64_t* offsets) {
-  NERF_REQUIRE(log2_res >= 2 && log2_res <= 10, NERF_E_SHAPE, "%s: need 2 <= log2_res <= 10", who);
-  NERF_REQUIRE(B >= 0 && B < (1ll << 40), NERF_E_SHAPE, "%s: bad B", who);
-  NERF_REQUIRE(march_steps >= 1 && march_steps <= NERF_MARCH_MAX_STEPS, NERF_E_SHAPE, "%s: need 1 <= march_steps <= %d (got %d)",
-               who, NERF_MARCH_MAX_STEPS, march_steps);
-  NERF_REQUIRE(pos_scale != 0.0f && step_world > 0.0f, NERF_E_SHAPE, "%s: need pos_scale != 0 and step_world > 0", who);
-  NERF_REQUIRE(offsets, NERF_E_NULL, "%s: NULL offsets", who);
-  NERF_REQUIRE(B == 0 || (rays && workspace), NERF_E_NULL, "%s: NULL pointer", who);
-  return NERF_OK;
-}
+extern "C" int64_t nerf_occ_march_workspace_bytes(int64_t B) { return B < 0 ? -1 : march_ws(nullptr, B).bytes; }
 
 extern "C" int nerf_occ_march_count(const float* rays, int64_t B, const float* jitter, float jitter_const, const uint32_t* bits,
                                     int log2_res, float pos_scale, float pos_offset, float step_world, int march_steps,
                                     void* workspace, int64_t* offsets, void* stream) {
-  int rc = march_check("nerf_occ_march_count", rays, B, log2_res, pos_scale, step_world, march_steps, workspace, offsets);
+  MarchArgs a;
+  int rc = march_args("nerf_occ_march_count", rays, B, jitter, jitter_const, bits, log2_res, pos_scale, pos_offset, step_world,
+                      march_steps, workspace, offsets, &a);
   if (rc) return rc;
-  if (B == 0) {
-    hipError_t e = hipMemsetAsync(offsets, 0, sizeof(int64_t), as_stream(stream));
-    if (e != hipSuccess) return fail(NERF_E_HIP, "nerf_occ_march_count: %s", hipGetErrorString(e));
-    return NERF_OK;
-  }
-  const int64_t nblk = (B + MARCH_BLOCK - 1) / MARCH_BLOCK;
-  int64_t* blk = static_cast<int64_t*>(workspace);
-  int* counts = reinterpret_cast<int*>(blk + nblk);
-  hipLaunchKernelGGL(occ_march_count_kernel, dim3((unsigned)nblk), dim3(MARCH_BLOCK), 0, as_stream(stream), rays, B, jitter,
-                     jitter_const, bits, log2_res, pos_scale, pos_offset, step_world, march_steps, counts, blk);
+  if (B == 0) return zero_i64("nerf_occ_march_count", offsets, 1, stream);
+  const PairWs w = march_ws(workspace, B);
+  hipLaunchKernelGGL(occ_march_count_kernel, dim3((unsigned)w.nblk), dim3(MARCH_BLOCK), 0, as_stream(stream), a, w.items, w.blk);
   rc = check_launch("nerf_occ_march_count (count)");
   if (rc) return rc;
-  hipLaunchKernelGGL(occ_cull_scan_kernel, dim3(1), dim3(1024), 0, as_stream(stream), blk, nblk, offsets + B);
+  hipLaunchKernelGGL(occ_cull_scan_kernel, dim3(1), dim3(1024), 0, as_stream(stream), w.blk, w.nblk, offsets + B);
   return check_launch("nerf_occ_march_count (scan)");
 }
 
 extern "C" int nerf_occ_march_write(const float* rays, int64_t B, const float* jitter, float jitter_const, const uint32_t* bits,
                                     int log2_res, float pos_scale, float pos_offset, float step_world, int march_steps,
                                     void* workspace, int64_t* offsets, float* rows_out, float* z_out, void* stream) {
-  int rc = march_check("nerf_occ_march_write", rays, B, log2_res, pos_scale, step_world, march_steps, workspace, offsets);
+  MarchArgs a;
+  int rc = march_args("nerf_occ_march_write", rays, B, jitter, jitter_const, bits, log2_res, pos_scale, pos_offset, step_world,
+                      march_steps, workspace, offsets, &a);
   if (rc) return rc;
   if (B == 0) return NERF_OK;
   NERF_REQUIRE(rows_out && z_out, NERF_E_NULL, "nerf_occ_march_write: NULL rows_out / z_out");
-  const int64_t nblk = (B + MARCH_BLOCK - 1) / MARCH_BLOCK;
-  const int64_t* blk = static_cast<const int64_t*>(workspace);
-  const int* counts = reinterpret_cast<const int*>(blk + nblk);
-  hipLaunchKernelGGL(occ_march_write_kernel, dim3((unsigned)nblk), dim3(MARCH_BLOCK), 0, as_stream(stream), rays, B, jitter,
-                     jitter_const, bits, log2_res, pos_scale, pos_offset, step_world, march_steps, counts, blk, offsets, rows_out,
-                     z_out);
+  const PairWs w = march_ws(workspace, B);
+  hipLaunchKernelGGL(occ_march_write_kernel, dim3((unsigned)w.nblk), dim3(MARCH_BLOCK), 0, as_stream(stream), a,
+                     (const int*)w.items, (const int64_t*)w.blk, offsets, rows_out, z_out);
   return check_launch("nerf_occ_march_write");
 }
 
@@ -639,47 +602,27 @@ extern "C" int nerf_scatter_rows(const float* src, const int64_t* idx, int64_t n
   return check_launch("nerf_scatter_rows");
 }
 
-extern "C" int64_t nerf_ert_march_workspace_bytes(int64_t B) {
-  if (B < 0) return -1;
-  const int64_t nblk = (B + MARCH_BLOCK - 1) / MARCH_BLOCK;
-  return 2 * nblk * (int64_t)sizeof(int64_t) + ((B * (int64_t)sizeof(int) + 7) / 8) * 8;
-}
-
-static int ert_march_check(const char* who, const float* rays, int64_t B, int log2_res, float pos_scale, float step_world,
-                           int march_steps, const int* live, int64_t A, const int* istate, int max_new, void* workspace,
-                           int64_t* out) {
-  int rc = march_check(who, rays, B, log2_res, pos_scale, step_world, march_steps, workspace, out);
-  if (rc) return rc;
-  NERF_REQUIRE(B < (1ll << 31) && A >= 0 && A <= B, NERF_E_SHAPE, "%s: need 0 <= A <= B < 2^31", who);
-  NERF_REQUIRE(max_new >= 1, NERF_E_SHAPE, "%s: need max_new >= 1 (got %d)", who, max_new);
-  NERF_REQUIRE(A == 0 || (live && istate), NERF_E_NULL, "%s: NULL live / istate", who);
-  return NERF_OK;
-}
+extern "C" int64_t nerf_ert_march_workspace_bytes(int64_t B) { return B < 0 ? -1 : ert_ws(nullptr, B, B).bytes; }
 
 extern "C" int nerf_ert_march_count(const float* rays, int64_t B, const float* jitter, float jitter_const, const uint32_t* bits,
                                     int log2_res, float pos_scale, float pos_offset, float step_world, int march_steps,
                                     const int* live, int64_t A, const int* istate, int max_new, void* workspace, int64_t* totals,
                                     void* stream) {
-  int rc = ert_march_check("nerf_ert_march_count", rays, B, log2_res, pos_scale, step_world, march_steps, live, A, istate,
-                           max_new, workspace, totals);
+  MarchArgs a;
+  int rc = march_args("nerf_ert_march_count", rays, B, jitter, jitter_const, bits, log2_res, pos_scale, pos_offset, step_world,
+                      march_steps, workspace, totals, &a);
+  if (!rc) rc = ert_march_check("nerf_ert_march_count", a, live, A, istate, max_new);
   if (rc) return rc;
-  if (A == 0) {
-    hipError_t e = hipMemsetAsync(totals, 0, 2 * sizeof(int64_t), as_stream(stream));
-    if (e != hipSuccess) return fail(NERF_E_HIP, "nerf_ert_march_count: %s", hipGetErrorString(e));
-    return NERF_OK;
-  }
-  const int64_t nblk = (A + MARCH_BLOCK - 1) / MARCH_BLOCK;
-  int64_t* blk = static_cast<int64_t*>(workspace);             // [2][nblk] for A <= B: the layout of the workspace of B
-  int* entry = reinterpret_cast<int*>(blk + 2 * ((B + MARCH_BLOCK - 1) / MARCH_BLOCK));
-  hipLaunchKernelGGL(ert_march_count_kernel, dim3((unsigned)nblk), dim3(MARCH_BLOCK), 0, as_stream(stream), rays, B, jitter,
-                     jitter_const, bits, log2_res, pos_scale, pos_offset, step_world, march_steps, live, A, istate, max_new, entry,
-                     blk, nblk);
+  if (A == 0) return zero_i64("nerf_ert_march_count", totals, 2, stream);
+  const PairWs w = ert_ws(workspace, B, A);
+  hipLaunchKernelGGL(ert_march_count_kernel, dim3((unsigned)w.nblk), dim3(MARCH_BLOCK), 0, as_stream(stream), a, live, A, istate,
+                     max_new, w.items, w.blk, w.nblk);
   rc = check_launch("nerf_ert_march_count (count)");
   if (rc) return rc;
-  hipLaunchKernelGGL(occ_cull_scan_kernel, dim3(1), dim3(1024), 0, as_stream(stream), blk, nblk, totals);
+  hipLaunchKernelGGL(occ_cull_scan_kernel, dim3(1), dim3(1024), 0, as_stream(stream), w.blk, w.nblk, totals);
   rc = check_launch("nerf_ert_march_count (scan of the samples)");
   if (rc) return rc;
-  hipLaunchKernelGGL(occ_cull_scan_kernel, dim3(1), dim3(1024), 0, as_stream(stream), blk + nblk, nblk, totals + 1);
+  hipLaunchKernelGGL(occ_cull_scan_kernel, dim3(1), dim3(1024), 0, as_stream(stream), w.blk + w.nblk, w.nblk, totals + 1);
   return check_launch("nerf_ert_march_count (scan of the live rays)");
 }
 
@@ -687,21 +630,16 @@ extern "C" int nerf_ert_march_write(const float* rays, int64_t B, const float* j
                                     int log2_res, float pos_scale, float pos_offset, float step_world, int march_steps,
                                     const int* live, int64_t A, int* istate, int max_new, void* workspace, int64_t* offsets,
                                     int* live_out, float* rows_out, float* z_out, void* stream) {
-  int rc = ert_march_check("nerf_ert_march_write", rays, B, log2_res, pos_scale, step_world, march_steps, live, A, istate, max_new,
-                           workspace, offsets);
+  MarchArgs a;
+  int rc = march_args("nerf_ert_march_write", rays, B, jitter, jitter_const, bits, log2_res, pos_scale, pos_offset, step_world,
+                      march_steps, workspace, offsets, &a);
+  if (!rc) rc = ert_march_check("nerf_ert_march_write", a, live, A, istate, max_new);
   if (rc) return rc;
-  if (A == 0) {
-    hipError_t e = hipMemsetAsync(offsets, 0, sizeof(int64_t), as_stream(stream));
-    if (e != hipSuccess) return fail(NERF_E_HIP, "nerf_ert_march_write: %s", hipGetErrorString(e));
-    return NERF_OK;
-  }
+  if (A == 0) return zero_i64("nerf_ert_march_write", offsets, 1, stream);
   NERF_REQUIRE(live_out && rows_out && z_out, NERF_E_NULL, "nerf_ert_march_write: NULL live_out / rows_out / z_out");
   NERF_REQUIRE(live_out != live, NERF_E_SHAPE, "nerf_ert_march_write: live_out must not be live");
-  const int64_t nblk = (A + MARCH_BLOCK - 1) / MARCH_BLOCK;
-  const int64_t* blk = static_cast<const int64_t*>(workspace);
-  const int* entry = reinterpret_cast<const int*>(blk + 2 * ((B + MARCH_BLOCK - 1) / MARCH_BLOCK));
-  hipLaunchKernelGGL(ert_march_write_kernel, dim3((unsigned)nblk), dim3(MARCH_BLOCK), 0, as_stream(stream), rays, B, jitter,
-                     jitter_const, bits, log2_res, pos_scale, pos_offset, step_world, march_steps, live, A, istate, max_new, entry,
-                     blk, nblk, offsets, live_out, rows_out, z_out);
+  const PairWs w = ert_ws(workspace, B, A);
+  hipLaunchKernelGGL(ert_march_write_kernel, dim3((unsigned)w.nblk), dim3(MARCH_BLOCK), 0, as_stream(stream), a, live, A, istate,
+                     max_new, (const int*)w.items, (const int64_t*)w.blk, w.nblk, offsets, live_out, rows_out, z_out);
   return check_launch("nerf_ert_march_write");
 }

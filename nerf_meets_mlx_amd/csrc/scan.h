@@ -1,11 +1,83 @@
-// The block scan shared by the compactions of occupancy.hip (cull, march, early termination) and mesh.hip (marching cubes):
-// one workgroup turns per-workgroup counts into exclusive offsets in place, in a fixed order (no atomics).
+// The three passes shared by the compactions of occupancy.hip (cull, march, early termination), mesh.hip (marching cubes) and
+// morph.hip (the steps' statistics): count per workgroup (block_sum), scan of the workgroup sums by one workgroup
+// (occ_cull_scan_kernel), rank inside the workgroup (block_offset).  Fixed order, no atomics; and the host's layout of the
+// workspace a count / write pair shares.
 #pragma once
 #include "common.h"
 
 namespace nerf {
 namespace {
 
+// Both helpers below contain a __syncthreads(): EVERY lane of the workgroup must reach them, lanes past the end of the data
+// included (with v = 0), and none may have returned before.  BLOCK = the workgroup's threads; N counters are carried at once.
+
+// total[c] = the sum of v[c] over the workgroup in thread 0 (0 in every other): wave butterfly, lane 0 to LDS, thread 0 adds the waves.
+template <int BLOCK, int N>
+__device__ __forceinline__ void block_sum(const int (&v)[N], int64_t (&total)[N]) {
+  __shared__ int sh[N][BLOCK / WAVE];
+  int t[N];
+#pragma unroll
+  for (int c = 0; c < N; ++c) t[c] = v[c];
+  for (int o = 32; o > 0; o >>= 1) {
+#pragma unroll
+    for (int c = 0; c < N; ++c) t[c] += __shfl_xor(t[c], o, WAVE);
+  }
+  if ((threadIdx.x & 63) == 0) {
+#pragma unroll
+    for (int c = 0; c < N; ++c) sh[c][threadIdx.x >> 6] = t[c];
+  }
+  __syncthreads();
+#pragma unroll
+  for (int c = 0; c < N; ++c) {
+    total[c] = 0;
+    if (threadIdx.x != 0) continue;
+    for (int k = 0; k < BLOCK / WAVE; ++k) total[c] += sh[c][k];
+  }
+}
+
+// off[c] += the exclusive prefix of v[c] over the workgroup's lanes in thread order (off[c] comes in as the workgroup's base):
+// inclusive wave scan, last lane to LDS, the waves below added in order.
+template <int BLOCK, int N>
+__device__ __forceinline__ void block_offset(const int (&v)[N], int64_t (&off)[N]) {
+  __shared__ int sh[N][BLOCK / WAVE];
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  int x[N];
+#pragma unroll
+  for (int c = 0; c < N; ++c) x[c] = v[c];
+  for (int o = 1; o < WAVE; o <<= 1) {
+#pragma unroll
+    for (int c = 0; c < N; ++c) {
+      const int t = __shfl_up(x[c], o, WAVE);
+      if (lane >= o) x[c] += t;
+    }
+  }
+  if (lane == 63) {
+#pragma unroll
+    for (int c = 0; c < N; ++c) sh[c][w] = x[c];
+  }
+  __syncthreads();
+#pragma unroll
+  for (int c = 0; c < N; ++c) {
+    off[c] += x[c] - v[c];
+    for (int k = 0; k < w; ++k) off[c] += sh[c][k];
+  }
+}
+
+// the one-counter forms
+template <int BLOCK>
+__device__ __forceinline__ int64_t block_sum(int v) {
+  int64_t t[1];
+  block_sum<BLOCK>({v}, t);
+  return t[0];
+}
+template <int BLOCK>
+__device__ __forceinline__ int64_t block_offset(int v, int64_t base) {
+  int64_t o[1] = {base};
+  block_offset<BLOCK>({v}, o);
+  return o[0];
+}
+
+#ifndef NERF_SCAN_HELPERS_ONLY                       // (a kernel defined here is emitted by every unit that includes it)
 // counts -> exclusive offsets in place, the total to count_out.  8 + 8 B per count.
 __global__ void __launch_bounds__(1024) occ_cull_scan_kernel(int64_t* __restrict__ offs, int64_t nblk, int64_t* __restrict__ count_out) {
   __shared__ int64_t sh[1024 / 64];
@@ -32,6 +104,27 @@ __global__ void __launch_bounds__(1024) occ_cull_scan_kernel(int64_t* __restrict
   }
   if (threadIdx.x == 0) *count_out = carry;
 }
+
+// The workspace of a count / write pair: `rows` x nblk workgroup sums (int64, scanned in place), then item_bytes of one int per
+// item.  The count entry, the write entries and the *_workspace_bytes function of a pair all take their pointers and sizes here.
+struct PairWs {
+  int64_t nblk;
+  int64_t* blk;                                     // [rows][nblk]
+  int* items;
+  int64_t bytes;
+};
+inline PairWs pair_ws(void* ws, int rows, int64_t nblk, int64_t item_bytes) {
+  const int64_t head = rows * nblk * (int64_t)sizeof(int64_t);
+  return {nblk, static_cast<int64_t*>(ws), reinterpret_cast<int*>(reinterpret_cast<uintptr_t>(ws) + (uintptr_t)head), head + item_bytes};
+}
+
+// "nothing to do": n int64 zeros on the stream, or HIP's text
+inline int zero_i64(const char* who, int64_t* p, int n, void* stream) {
+  const hipError_t e = hipMemsetAsync(p, 0, n * sizeof(int64_t), as_stream(stream));
+  return e == hipSuccess ? NERF_OK : fail(NERF_E_HIP, "%s: %s", who, hipGetErrorString(e));
+}
+
+#endif
 
 }  // namespace
 }  // namespace nerf
