@@ -27,11 +27,13 @@ static inline hipStream_t as_stream(void* s) { return reinterpret_cast<hipStream
 // before / after the call let it launch in between).
 struct DevOnce {
   std::once_flag flag[64];
-  template <class F> void run(F&& f) {
+  static int device() {
     int d = 0;
     if (hipGetDevice(&d) != hipSuccess || d < 0 || d >= 64) d = 0;
-    std::call_once(flag[d], std::forward<F>(f));
+    return d;
   }
+  template <class F> void run(int d, F&& f) { std::call_once(flag[d], std::forward<F>(f)); }     // d: device()
+  template <class F> void run(F&& f) { run(device(), std::forward<F>(f)); }
 };
 
 // grid sizing for HBM-bound kernels: enough workgroups to fill 256 CUs, grid-stride the rest
@@ -43,8 +45,8 @@ static inline int grid_for(int64_t work_items, int block, int max_blocks = 256 *
 }
 
 // A runtime bool as a template argument: fn receives std::true_type / std::false_type, and a generic lambda names the
-// kernel instantiation with decltype(arg)::value.  Nested calls list every combination once, in one place.
-template <class Fn> static inline void with_bool(bool b, Fn&& fn) { if (b) fn(std::true_type{}); else fn(std::false_type{}); }
+// kernel instantiation with decltype(arg)::value.  Nested calls list every combination once, in one place.  Returns what fn returns.
+template <class Fn> static inline auto with_bool(bool b, Fn&& fn) { if (b) return fn(std::true_type{}); else return fn(std::false_type{}); }
 
 // ---- wave64 scans / reductions.  float: DPP (v_add_f32 ... row_shr / row_shl / row_bcast: the data path of the
 // VALU, no LDS crossbar round trip per step as with ds_bpermute shuffles); double: shuffles (the one double scan,

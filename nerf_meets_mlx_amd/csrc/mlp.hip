@@ -1553,8 +1553,8 @@ int g_pass_queue = 1;               // "pass_queue": 1 (default) the persistent 
 static int g_ring_split = 1;     // training ring kernels: 1 = one 8-wave workgroup per CU (128 KiB ring), 2 = two 4-wave workgroups (64 KiB rings)
 
 // Per-device state.  The CU count (256 on an MI355X in SPX mode; the persistent kernels and the dW split are sized to it instead
-// of to a constant) is asked once per device, and the one-time opt-in of a kernel to dynamic LDS above 64 KiB goes through DevOnce
-// (common.h): both belong to the CURRENT device -- a process may move between devices with hipSetDevice, and
+// of to a constant) is asked once per device, and the one-time opt-in of a kernel to dynamic LDS above 64 KiB happens inside
+// launch<> (launch.h): both belong to the CURRENT device -- a process may move between devices with hipSetDevice, and
 // hipFuncSetAttribute applies to the device that is current when it is called.
 static int cu_count() {
   constexpr int MAX_DEVICES = 64;
@@ -1568,13 +1568,8 @@ static int cu_count() {
   return n[dev];
 }
 static inline int ring_wgs() { return g_ring_wgs > 0 ? g_ring_wgs : cu_count(); }
-// grid of a persistent kernel: one workgroup per super-tile, at most `wgs`
-static inline unsigned persistent_grid(int64_t nsuper, int64_t wgs = ring_wgs()) { return (unsigned)(nsuper < wgs ? nsuper : wgs); }
-
-template <class K>
-static void ensure_lds(K kernel, int bytes) {
-  (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
-}
+// grid of the 8-wave ring kernels: one workgroup per super-tile of 8 tiles, at most one per CU
+static inline unsigned ring_grid(int64_t ntiles) { return persistent_grid((ntiles + 7) / 8, ring_wgs()); }
 
 // nerf_set_option / nerf_get_option: one row per key.  rule(v) clamps or normalises the value in place; false = refused with `refusal`.
 struct Option { const char* key; int* var; bool (*rule)(int& v); const char* refusal; };
@@ -1646,29 +1641,21 @@ extern "C" int nerf_mlp_pack(const nerf_mlp_arch* arch, const float* params, voi
   int rc;
   if (m.shape == Shape::Small) {
     const int tot = (LN::F_PADDED + LN::B_PADDED) * 64 + LN::BI_TOTAL;
-    hipLaunchKernelGGL(pack_small_kernel, dim3((tot + 255) / 256), dim3(256), 0, s, params, wf, wb, bias);
-    rc = check_launch("nerf_mlp_pack (2x64 model)");
+    rc = launch<pack_small_kernel>("nerf_mlp_pack (2x64 model)", dim3((tot + 255) / 256), dim3(256), 0, s, params, wf, wb, bias);
     if (!rc && m.split()) rc = s16x::small_pack(params, m.stream<void>(packed, S_S16), s);
   } else if (m.shape == Shape::Image) {
     const int tot = (LI::F_TOTAL + LI::B_PADDED) * 64 + LI::BI_TOTAL;
-    hipLaunchKernelGGL(pack_img_kernel, dim3((tot + 255) / 256), dim3(256), 0, s, params, wf, wb, bias, m.out_ch);
-    rc = check_launch("nerf_mlp_pack (image model)");
+    rc = launch<pack_img_kernel>("nerf_mlp_pack (image model)", dim3((tot + 255) / 256), dim3(256), 0, s, params, wf, wb, bias, m.out_ch);
     if (!rc && m.split()) rc = s16x::img_pack(params, m.out_ch, m.stream<void>(packed, S_S16), s);
     if (!rc && m.prec == Prec::F32) rc = f32::pack(params, m.stream<void>(packed, S_F32), m.out_ch, s);
   } else {
-    hipLaunchKernelGGL(pack_kernel, dim3(PACK_BLOCKS + PACK16_BLOCKS), dim3(256), 0, s, params, wf, wb, bias,
-                       m.stream<bf16x8>(packed, S_FWD16));
-    rc = check_launch("nerf_mlp_pack");
+    rc = launch<pack_kernel>("nerf_mlp_pack", dim3(PACK_BLOCKS + PACK16_BLOCKS), dim3(256), 0, s, params, wf, wb, bias,
+                             m.stream<bf16x8>(packed, S_FWD16));
     if (!rc && m.prec == Prec::F32) rc = f32::pack(params, m.stream<void>(packed, S_F32), 0, s);
     if (!rc && m.split()) rc = f22::pack(params, m.stream<void>(packed, S_F22), s);
     if (!rc && m.split()) rc = s16::pack(params, m.stream<void>(packed, S_S16), s);
   }
   return rc;
-}
-
-static void fill_freqs(PeFreq& fr, int mode) {
-  for (int k = 0; k < 10; ++k) fr.pos[k] = mode == 0 ? (float)(k * k) : (float)(1 << k);
-  for (int k = 0; k < 4; ++k) fr.dir[k] = mode == 0 ? (float)(k * k) : (float)(1 << k);
 }
 
 template <int MODE>
@@ -1679,52 +1666,41 @@ static int launch_fwd(const Model& m, const void* packed, const float* x, const 
   a.wf = m.stream<bf16x8>(packed, S_FWD);
   a.bias = m.stream<float>(packed, S_BIAS);
   a.x = x; a.rays = rays; a.z = z; a.M = M; a.n = n; a.out = out; a.acts = acts; a.astride = m.astride();
-  fill_freqs(a.fr, freq_mode);
+  fill_freqs(a.fr.pos, a.fr.dir, freq_mode);
   const int64_t ntiles = (M + 31) / 32;
   auto s = as_stream(stream);
   // auto: fused query -> LDS ring; the render path (no activations kept) on the 16x16x32 shape, which holds a higher
   // clock: +8 % back to back, +2.5 % inside bench.py's train+render step
   const int variant = (g_mlp_variant == 0) ? (MODE == 1 ? (acts ? 3 : 4) : 1) : g_mlp_variant;
   if ((variant == 4 || variant == 5) && MODE == 1 && !acts) {
-    const dim3 g(persistent_grid((M + 255) / 256));
-    static DevOnce once16;
-    once16.run([&] { ensure_lds(mlp_fwd_ring16_kernel<8, 2>, RING16_LDS_BYTES); ensure_lds(mlp_fwd_ring16_kernel<4, 4>, RING16_LDS_BYTES); });
+    const dim3 g(persistent_grid((M + 255) / 256, ring_wgs()));
     FwdArgs a16 = a;
     a16.queue = passq_slot();
     a16.wf = m.stream<bf16x8>(packed, S_FWD16);
-    if (variant == 4) hipLaunchKernelGGL((mlp_fwd_ring16_kernel<8, 2>), g, dim3(512), RING16_LDS_BYTES, s, a16);
-    else hipLaunchKernelGGL((mlp_fwd_ring16_kernel<4, 4>), g, dim3(256), RING16_LDS_BYTES, s, a16);
-    return check_launch("mlp forward (ring, 16x16x32)");
+    const char* what = "mlp forward (ring, 16x16x32)";
+    if (variant == 4) return launch<mlp_fwd_ring16_kernel<8, 2>, mlp_fwd_ring16_kernel<4, 4>>(what, g, dim3(512), RING16_LDS_BYTES, s, a16);
+    return launch<mlp_fwd_ring16_kernel<4, 4>, mlp_fwd_ring16_kernel<8, 2>>(what, g, dim3(256), RING16_LDS_BYTES, s, a16);
   }
   if (variant >= 3 && MODE == 1) {
     a.queue = passq_slot();
     if (acts && g_ring_split == 2) {                      // two 4-wave workgroups per CU, each with its own 64 KiB ring
-      static DevOnce once2;
-      once2.run([&] { ensure_lds(mlp_fwd_ring_kernel<1, true, SPLIT_NW, SPLIT_CHUNK>, SPLIT_LDS_BYTES); });
-      hipLaunchKernelGGL((mlp_fwd_ring_kernel<1, true, SPLIT_NW, SPLIT_CHUNK>),
-                         dim3(persistent_grid((ntiles + SPLIT_NW - 1) / SPLIT_NW, 2 * (int64_t)ring_wgs())), dim3(64 * SPLIT_NW),
-                         SPLIT_LDS_BYTES, s, a);
-      return check_launch("mlp forward (ring, 2 workgroups per CU)");
+      return launch<mlp_fwd_ring_kernel<1, true, SPLIT_NW, SPLIT_CHUNK>>(
+          "mlp forward (ring, 2 workgroups per CU)", dim3(persistent_grid((ntiles + SPLIT_NW - 1) / SPLIT_NW, 2 * (int64_t)ring_wgs())),
+          dim3(64 * SPLIT_NW), SPLIT_LDS_BYTES, s, a);
     }
-    const dim3 g(persistent_grid((ntiles + 7) / 8)), b(512);
-    static DevOnce once;
-    once.run([&] { ensure_lds(mlp_fwd_ring_kernel<1, true>, RING_LDS_BYTES); ensure_lds(mlp_fwd_ring_kernel<1, false>, RING_LDS_BYTES); });
-    if (acts) hipLaunchKernelGGL((mlp_fwd_ring_kernel<1, true>), g, b, RING_LDS_BYTES, s, a);
-    else hipLaunchKernelGGL((mlp_fwd_ring_kernel<1, false>), g, b, RING_LDS_BYTES, s, a);
-    return check_launch("mlp forward (ring)");
+    return with_bool(acts != nullptr, [&](auto store) {
+      constexpr bool ST = decltype(store)::value;
+      return launch<mlp_fwd_ring_kernel<1, ST>, mlp_fwd_ring_kernel<1, !ST>>("mlp forward (ring)", dim3(ring_grid(ntiles)), dim3(512),
+                                                                              RING_LDS_BYTES, s, a);
+    });
   }
   const int st = variant == 2 ? 2 : 1;
   const int64_t blocks = (ntiles + 4 * st - 1) / (4 * st);
   NERF_REQUIRE(blocks < (1ll << 31), NERF_E_SHAPE, "mlp forward: M too large");
-  const dim3 g((unsigned)blocks), b(256);
-  if (st == 1) {
-    if (acts) hipLaunchKernelGGL((mlp_fwd_kernel<1, MODE, true>), g, b, 0, s, a);
-    else hipLaunchKernelGGL((mlp_fwd_kernel<1, MODE, false>), g, b, 0, s, a);
-  } else {
-    if (acts) hipLaunchKernelGGL((mlp_fwd_kernel<2, MODE, true>), g, b, 0, s, a);
-    else hipLaunchKernelGGL((mlp_fwd_kernel<2, MODE, false>), g, b, 0, s, a);
-  }
-  return check_launch("mlp forward");
+  return with_bool(st == 1, [&](auto one) { return with_bool(acts != nullptr, [&](auto store) {
+    return launch<mlp_fwd_kernel<decltype(one)::value ? 1 : 2, MODE, decltype(store)::value>>("mlp forward", dim3((unsigned)blocks), dim3(256),
+                                                                                                0, s, a);
+  }); });
 }
 
 static void img_args(ImgArgs& a, const Model& m, const void* packed) {
@@ -1763,11 +1739,10 @@ extern "C" int nerf_mlp_forward_train(const nerf_mlp_arch* arch, const void* pac
     SmallArgs a;
     small_args(a, m, packed);
     a.x = x; a.out = out; a.acts = acts; a.M = M;
-    const int64_t nwg = ((M + 31) / 32 + 7) / 8;
-    const dim3 g((unsigned)(nwg < 2048 ? nwg : 2048)), b(512);
-    if (acts) hipLaunchKernelGGL((mlp_small_fwd_kernel<true, false>), g, b, LN::LDS_BYTES, s, a);
-    else hipLaunchKernelGGL((mlp_small_fwd_kernel<false, false>), g, b, LN::LDS_BYTES, s, a);
-    return check_launch("mlp forward (2x64 model)");
+    return with_bool(acts != nullptr, [&](auto store) {
+      return launch<mlp_small_fwd_kernel<decltype(store)::value, false>>("mlp forward (2x64 model)", dim3(small_grid((M + 31) / 32)), dim3(512),
+                                                                         LN::LDS_BYTES, s, a);
+    });
   }
   if (m.shape == Shape::Image) {
     if (m.prec == Prec::F32)                   // float32 operands on the fp32 MFMA (mlp32.hip)
@@ -1778,12 +1753,11 @@ extern "C" int nerf_mlp_forward_train(const nerf_mlp_arch* arch, const void* pac
     ImgArgs a;
     img_args(a, m, packed);
     a.x = x; a.out = out; a.acts = acts; a.M = M;
-    static DevOnce once;
-    once.run([&] { ensure_lds(mlp_img_fwd_ring_kernel<true>, RING_LDS_BYTES); ensure_lds(mlp_img_fwd_ring_kernel<false>, RING_LDS_BYTES); });
-    const dim3 g(persistent_grid(((M + 31) / 32 + 7) / 8)), b(512);
-    if (acts) hipLaunchKernelGGL(mlp_img_fwd_ring_kernel<true>, g, b, RING_LDS_BYTES, s, a);
-    else hipLaunchKernelGGL(mlp_img_fwd_ring_kernel<false>, g, b, RING_LDS_BYTES, s, a);
-    return check_launch("mlp forward (image model)");
+    return with_bool(acts != nullptr, [&](auto store) {
+      constexpr bool ST = decltype(store)::value;
+      return launch<mlp_img_fwd_ring_kernel<ST>, mlp_img_fwd_ring_kernel<!ST>>("mlp forward (image model)", dim3(ring_grid((M + 31) / 32)),
+                                                                               dim3(512), RING_LDS_BYTES, s, a);
+    });
   }
   return view_forward(m, packed, x, nullptr, nullptr, M, 1, 0, out, acts, stream);
 }
@@ -1850,14 +1824,10 @@ static int launch_dw_part(const Model& m, DwArgs& d, int nj, int64_t ntiles, con
     // mlp_dw_kernel below (4.45 against 4.43 ms per training step), which keeps them ("dw16_variant" 3 forces this kernel).
     rc = s16::launch_dw_kernel(d, nw, false, s);
   } else {
-    static DevOnce lds_attr_set;
-    lds_attr_set.run([&] { ensure_lds(mlp_dw_kernel, DW_LDS_BYTES); });
-    hipLaunchKernelGGL(mlp_dw_kernel, dim3(nw), dim3(64 * DW_WAVES), DW_LDS_BYTES, s, d);
-    rc = check_launch("mlp dW");
+    rc = launch<mlp_dw_kernel>("mlp dW", dim3(nw), dim3(64 * DW_WAVES), DW_LDS_BYTES, s, d);
   }
   if (rc) return rc;
-  hipLaunchKernelGGL(mlp_dw_reduce_kernel, dim3(257, nj), dim3(256), 0, s, d);        // 256 x 256 weights + 256 biases: one element per thread
-  return check_launch("mlp dW reduce");
+  return launch<mlp_dw_reduce_kernel>("mlp dW reduce", dim3(257, nj), dim3(256), 0, s, d);        // 256 x 256 weights + 256 biases: one element per thread
 }
 
 // split the (dZ, H) jobs over workgroups and launch the dW kernel(s); grads[0..m.params) is overwritten
@@ -1908,26 +1878,20 @@ static int view_backward_chain(const Model& m, const void* packed, const void* a
   b.wb = m.stream<bf16x8>(packed, S_BWD);
   b.acts = acts; b.d_raw = d_raw; b.M = M; b.dz = dz; b.astride = m.astride(); b.zstride = m.zstride();
   const int variant = g_mlp_variant == 0 ? 3 : g_mlp_variant;
+  const char* what = "mlp backward chain";
   if (variant >= 3) {
     b.queue = passq_slot();
-    if (g_bwd_stage != 2 && g_ring_split == 2) {
-      static DevOnce once2;
-      once2.run([&] { ensure_lds(mlp_bwd_ring_kernel<SPLIT_NW, SPLIT_CHUNK>, SPLIT_LDS_BYTES); });
-      hipLaunchKernelGGL((mlp_bwd_ring_kernel<SPLIT_NW, SPLIT_CHUNK>),
-                         dim3(persistent_grid((ntiles + SPLIT_NW - 1) / SPLIT_NW, 2 * (int64_t)ring_wgs())), dim3(64 * SPLIT_NW),
-                         SPLIT_LDS_BYTES, s, b);
-    } else if (g_bwd_stage != 2) {
-      static DevOnce once;
-      once.run([&] { ensure_lds(mlp_bwd_ring_kernel<>, RING_LDS_BYTES); });
-      hipLaunchKernelGGL(mlp_bwd_ring_kernel<>, dim3(persistent_grid((ntiles + 7) / 8)), dim3(512), RING_LDS_BYTES, s, b);
-    }
-  } else {
-    const int st = variant == 2 ? 2 : 1;
-    const int64_t blocks = (ntiles + 4 * st - 1) / (4 * st);
-    if (st == 1) hipLaunchKernelGGL((mlp_bwd_kernel<1>), dim3((unsigned)blocks), dim3(256), 0, s, b);
-    else hipLaunchKernelGGL((mlp_bwd_kernel<2>), dim3((unsigned)blocks), dim3(256), 0, s, b);
+    if (g_bwd_stage == 2) return check_launch(what);
+    if (g_ring_split == 2)
+      return launch<mlp_bwd_ring_kernel<SPLIT_NW, SPLIT_CHUNK>>(
+          what, dim3(persistent_grid((ntiles + SPLIT_NW - 1) / SPLIT_NW, 2 * (int64_t)ring_wgs())), dim3(64 * SPLIT_NW), SPLIT_LDS_BYTES, s, b);
+    return launch<mlp_bwd_ring_kernel<>>(what, dim3(ring_grid(ntiles)), dim3(512), RING_LDS_BYTES, s, b);
   }
-  return check_launch("mlp backward chain");
+  const int st = variant == 2 ? 2 : 1;
+  const int64_t blocks = (ntiles + 4 * st - 1) / (4 * st);
+  return with_bool(st == 1, [&](auto one) {
+    return launch<mlp_bwd_kernel<decltype(one)::value ? 1 : 2>>(what, dim3((unsigned)blocks), dim3(256), 0, s, b);
+  });
 }
 
 static int mlp_backward_impl(const nerf_mlp_arch* arch, const void* packed, const void* acts, const float* d_raw,
@@ -1950,9 +1914,7 @@ static int mlp_backward_impl(const nerf_mlp_arch* arch, const void* packed, cons
       SmallArgs a;
       small_args(a, m, packed);
       a.d_raw = d_raw; a.acts = const_cast<void*>(acts); a.dz = dz; a.M = M; a.d_x = d_x;
-      const int64_t nwg = (ntiles + 7) / 8;
-      hipLaunchKernelGGL(mlp_small_bwd_kernel, dim3((unsigned)(nwg < 2048 ? nwg : 2048)), dim3(512), LN::LDS_BYTES, s, a);
-      rc = check_launch("mlp backward chain (2x64 model)");
+      rc = launch<mlp_small_bwd_kernel>("mlp backward chain (2x64 model)", dim3(small_grid(ntiles)), dim3(512), LN::LDS_BYTES, s, a);
     }
   } else if (m.shape == Shape::Image) {
     if (m.split()) {
@@ -1961,10 +1923,7 @@ static int mlp_backward_impl(const nerf_mlp_arch* arch, const void* packed, cons
       ImgArgs a;
       img_args(a, m, packed);
       a.d_out = d_raw; a.acts = const_cast<void*>(acts); a.dz = dz; a.M = M;
-      static DevOnce once_i;
-      once_i.run([&] { ensure_lds(mlp_img_bwd_ring_kernel, RING_LDS_BYTES); });
-      hipLaunchKernelGGL(mlp_img_bwd_ring_kernel, dim3(persistent_grid((ntiles + 7) / 8)), dim3(512), RING_LDS_BYTES, s, a);
-      rc = check_launch("mlp backward chain (image model)");
+      rc = launch<mlp_img_bwd_ring_kernel>("mlp backward chain (image model)", dim3(ring_grid(ntiles)), dim3(512), RING_LDS_BYTES, s, a);
     }
   } else {
     rc = view_backward_chain(m, packed, acts, d_raw, M, dz, s);
@@ -2012,14 +1971,12 @@ static int ngp_query_fused_impl(const nerf_mlp_arch* arch, const void* packed, c
   for (int l = 0; l < 32; ++l) a.rt.res[l] = l < L ? (float)resolutions_host[l] : 0.0f;
   a.B = B;
   a.ray_major = (!acts && g_ngp_ray_major && B >= 32) ? 1 : 0;
-  const int64_t nwg = ((a.ray_major ? ((B + 31) / 32) * (int64_t)n : (M + 31) / 32) + 7) / 8;
-  const dim3 g((unsigned)(nwg < 2048 ? nwg : 2048)), b(512);
+  const dim3 g(small_grid(a.ray_major ? ((B + 31) / 32) * (int64_t)n : (M + 31) / 32));
   if (lw_host) a.lw = lt;
-  with_bool(acts != nullptr, [&](auto store) { with_bool(lw_host != nullptr, [&](auto lw) {
-    hipLaunchKernelGGL((mlp_small_fwd_kernel<decltype(store)::value, true, decltype(lw)::value>), g, b, LN::LDS_BYTES,
-                       as_stream(stream), a);
+  return with_bool(acts != nullptr, [&](auto store) { return with_bool(lw_host != nullptr, [&](auto lw) {
+    return launch<mlp_small_fwd_kernel<decltype(store)::value, true, decltype(lw)::value>>(
+        lw_host ? "nerf_ngp_query_fused_lw" : "nerf_ngp_query_fused", g, dim3(512), LN::LDS_BYTES, as_stream(stream), a);
   }); });
-  return check_launch(lw_host ? "nerf_ngp_query_fused_lw" : "nerf_ngp_query_fused");
 }
 
 extern "C" int nerf_ngp_query_fused_h(const nerf_mlp_arch* arch, const void* packed, const float* rays, const float* z,
@@ -2098,9 +2055,8 @@ extern "C" int nerf_mlp_debug_read(const nerf_mlp_arch* arch, const void* store,
   NERF_REQUIRE(store && out, NERF_E_NULL, "nerf_mlp_debug_read: NULL pointer");
   if (M <= 0) return NERF_OK;
   const int lo_off = !m.split() ? 0 : kind == 0 ? m.info->a_lo : m.info->z_lo;       // split-bf16 stores: value = hi block + lo block
-  hipLaunchKernelGGL(decode_frags_kernel, dim3(grid_for(M * ds.nfrag * 2, 256)), dim3(256), 0, as_stream(stream), store,
-                     kind == 0 ? m.astride() : m.zstride(), ds.slot, ds.nfrag, M, out, lo_off);
-  return check_launch("nerf_mlp_debug_read");
+  return launch<decode_frags_kernel>("nerf_mlp_debug_read", dim3(grid_for(M * ds.nfrag * 2, 256)), dim3(256), 0, as_stream(stream), store,
+                                     kind == 0 ? m.astride() : m.zstride(), ds.slot, ds.nfrag, M, out, lo_off);
 }
 
 NERF_STAMP2_EXPORT(nerf_debug_stamps2_ring16)

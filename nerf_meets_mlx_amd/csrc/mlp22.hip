@@ -500,9 +500,8 @@ __global__ void __launch_bounds__(64 * NW22) mlp22_fwd_kernel(FwdArgs a) {
 // ------------------------------------------------------------------------------------------
 int pack(const float* params, void* packed22, hipStream_t s) {
   char* base = static_cast<char*>(packed22);
-  hipLaunchKernelGGL(pack22_kernel, dim3((PACK_THREADS + 255) / 256), dim3(256), 0, s, params,
-                     reinterpret_cast<u32x4*>(base), reinterpret_cast<float*>(base + (size_t)F_PADDED * 1024));
-  return check_launch("nerf_mlp_pack (split-fp16 image)");
+  return launch<pack22_kernel>("nerf_mlp_pack (split-fp16 image)", dim3((PACK_THREADS + 255) / 256), dim3(256), 0, s, params,
+                               reinterpret_cast<u32x4*>(base), reinterpret_cast<float*>(base + (size_t)F_PADDED * 1024));
 }
 
 // nerf_set_option("f22_tiles"): 16-sample tiles per wave of the rays + depths launch: 2 (32 samples) | 3 (48 samples) | 0 (default) = 3
@@ -518,29 +517,21 @@ int forward(const void* packed22, const float* x, const float* rays, const float
   a.wf = reinterpret_cast<const bf16x8*>(base);
   a.bias = reinterpret_cast<const float*>(base + (size_t)F_PADDED * 1024);
   a.x = x; a.rays = rays; a.z = z; a.M = M; a.n = n; a.out = out; a.acts = nullptr; a.astride = 0;
-  for (int k = 0; k < 10; ++k) a.fr.pos[k] = freq_mode == 0 ? (float)(k * k) : (float)(1 << k);
-  for (int k = 0; k < 4; ++k) a.fr.dir[k] = freq_mode == 0 ? (float)(k * k) : (float)(1 << k);
+  fill_freqs(a.fr.pos, a.fr.dir, freq_mode);
   int tiles = g_tiles;
   if (tiles == 0) {
     const int64_t w = persistent_wgs > 0 ? persistent_wgs : 1;
     const int64_t p2 = (((M + 31) / 32 + NW22 - 1) / NW22 + w - 1) / w, p3 = (((M + 47) / 48 + NW22 - 1) / NW22 + w - 1) / w;     // passes of the busiest workgroup
     tiles = 100 * p2 < 141 * p3 ? 2 : 3;
   }
-  const int mode = x ? 0 : (tiles == 3 ? 2 : 1);
-  const int ns = mode == 2 ? 3 : 2;
-  const int64_t nsuper = ((M + 16 * ns - 1) / (16 * ns) + NW22 - 1) / NW22;
-  const dim3 g((unsigned)(nsuper < persistent_wgs ? nsuper : persistent_wgs)), b(64 * NW22);
-  // dynamic LDS above 64 KiB is an opt-in per kernel AND per device
-  static DevOnce once[3];
-  once[mode].run([&] {
-    const void* k = mode == 0 ? reinterpret_cast<const void*>(mlp22_fwd_kernel<0>) : mode == 1 ? reinterpret_cast<const void*>(mlp22_fwd_kernel<1>)
-                                                                                                : reinterpret_cast<const void*>(mlp22_fwd_kernel<1, 3>);
-    (void)hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, RING_LDS_BYTES + park_bytes<3>());
+  // form 0: embedded rows; 1: rays + depths, 32 samples per wave; 2: rays + depths, 48 samples per wave
+  return with_index<3>(x ? 0 : (tiles == 3 ? 2 : 1), [&](auto form) {
+    constexpr int MODE = decltype(form)::value == 0 ? 0 : 1, NS = decltype(form)::value == 2 ? 3 : 2;
+    const int64_t nsuper = ((M + 16 * NS - 1) / (16 * NS) + NW22 - 1) / NW22;
+    // every form is opted in to the largest form's LDS
+    return launch<mlp22_fwd_kernel<MODE, NS>>("mlp forward (split fp16)", dim3(persistent_grid(nsuper, persistent_wgs)), dim3(64 * NW22),
+                                             Lds(RING_LDS_BYTES + park_bytes<NS>(), RING_LDS_BYTES + park_bytes<3>()), s, a);
   });
-  if (mode == 0) hipLaunchKernelGGL(mlp22_fwd_kernel<0>, g, b, RING_LDS_BYTES, s, a);
-  else if (mode == 1) hipLaunchKernelGGL(mlp22_fwd_kernel<1>, g, b, RING_LDS_BYTES, s, a);
-  else hipLaunchKernelGGL((mlp22_fwd_kernel<1, 3>), g, b, RING_LDS_BYTES + park_bytes<3>(), s, a);
-  return check_launch("mlp forward (split fp16)");
 }
 
 }  // namespace f22

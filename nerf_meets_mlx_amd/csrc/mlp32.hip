@@ -849,25 +849,10 @@ static bool debug_slot(int kind, int layer, int* row0, int* width) {
 constexpr int SLAB_BYTES = 4 * 256 * 32 * 4;        // 128 KiB: one 32 KiB slab per wave
 constexpr int FWD_LDS_BYTES = SLAB_BYTES + BIAS_FLOATS * 4, BWD_LDS_BYTES = SLAB_BYTES + 1024 * 4;
 
-// opt in to more than 64 KiB of dynamic LDS, once per (kernel, device).  Keyed by the kernel's ADDRESS: the two forward
-// instantiations have the same function type, so a per-type flag (the first version) served only whichever ran first.
-template <class K>
-static void want_lds(K kernel, int bytes = SLAB_BYTES) {
-  static const void* seen[8][64] = {};
-  const void* fn = reinterpret_cast<const void*>(kernel);
-  int d = 0;
-  if (hipGetDevice(&d) != hipSuccess || d < 0 || d >= 64) d = 0;
-  for (int i = 0; i < 8; ++i) {
-    if (seen[i][d] == fn) return;
-    if (seen[i][d] == nullptr) { seen[i][d] = fn; break; }
-  }
-  (void)hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
-}
-
 int pack(const float* params, void* packed32, int img_out_ch, hipStream_t s) {
   const int total = (F_FRAGS + B_FRAGS) * 64 + TAIL_FLOATS;
-  hipLaunchKernelGGL(pack32_kernel, dim3((total + 255) / 256), dim3(256), 0, s, params, static_cast<float*>(packed32), img_out_ch);
-  return check_launch("nerf_mlp_pack (fp32 streams)");
+  return launch<pack32_kernel>("nerf_mlp_pack (fp32 streams)", dim3((total + 255) / 256), dim3(256), 0, s, params, static_cast<float*>(packed32),
+                               img_out_ch);
 }
 
 static const float* tail_of(const void* packed32) {
@@ -881,27 +866,14 @@ int forward(const void* packed32, const float* x, const float* rays, const float
   a.wf = static_cast<const float4*>(packed32);
   a.tail = tail_of(packed32);
   a.x = x; a.rays = rays; a.z = z; a.M = M; a.n = n; a.out = out; a.acts = static_cast<float*>(acts);
-  for (int k = 0; k < 10; ++k) a.fpos[k] = freq_mode == 0 ? (float)(k * k) : (float)(1 << k);
-  for (int k = 0; k < 4; ++k) a.fdir[k] = freq_mode == 0 ? (float)(k * k) : (float)(1 << k);
+  fill_freqs(a.fpos, a.fdir, freq_mode);
   const int64_t blocks = (tiles_of(M) + 3) / 4;
   NERF_REQUIRE(blocks < (1ll << 31), NERF_E_SHAPE, "mlp forward (fp32): M too large");
-  if (img_out_ch > 0) {
+  if (img_out_ch > 0)
     NERF_REQUIRE(x && img_out_ch <= 4, NERF_E_SHAPE, "mlp forward (fp32, image model): needs embedded rows and out_ch <= 4");
-    if (acts) {
-      want_lds((mlp32_fwd_kernel<true, true>), FWD_LDS_BYTES);
-      hipLaunchKernelGGL((mlp32_fwd_kernel<true, true>), dim3((unsigned)blocks), dim3(256), FWD_LDS_BYTES, s, a);
-    } else {
-      want_lds((mlp32_fwd_kernel<false, true>), FWD_LDS_BYTES);
-      hipLaunchKernelGGL((mlp32_fwd_kernel<false, true>), dim3((unsigned)blocks), dim3(256), FWD_LDS_BYTES, s, a);
-    }
-  } else if (acts) {
-    want_lds((mlp32_fwd_kernel<true, false>), FWD_LDS_BYTES);
-    hipLaunchKernelGGL((mlp32_fwd_kernel<true, false>), dim3((unsigned)blocks), dim3(256), FWD_LDS_BYTES, s, a);
-  } else {
-    want_lds((mlp32_fwd_kernel<false, false>), FWD_LDS_BYTES);
-    hipLaunchKernelGGL((mlp32_fwd_kernel<false, false>), dim3((unsigned)blocks), dim3(256), FWD_LDS_BYTES, s, a);
-  }
-  return check_launch("mlp forward (fp32)");
+  return with_bool(img_out_ch > 0, [&](auto img) { return with_bool(acts != nullptr, [&](auto store) {
+    return launch<mlp32_fwd_kernel<decltype(store)::value, decltype(img)::value>>("mlp forward (fp32)", dim3((unsigned)blocks), dim3(256), FWD_LDS_BYTES, s, a);
+  }); });
 }
 
 int backward(const void* packed32, const void* acts, const float* d_raw, int64_t M, void* dz, float* grads, int img_out_ch,
@@ -914,14 +886,9 @@ int backward(const void* packed32, const void* acts, const float* d_raw, int64_t
   b.acts = static_cast<const float*>(acts); b.d_raw = d_raw; b.M = M; b.dz = static_cast<float*>(dz);
   const int64_t ntiles = tiles_of(M), blocks = (ntiles + 3) / 4;
   NERF_REQUIRE(blocks < (1ll << 31), NERF_E_SHAPE, "mlp backward (fp32): M too large");
-  if (img) {
-    want_lds(mlp32_bwd_kernel<true>, BWD_LDS_BYTES);
-    hipLaunchKernelGGL(mlp32_bwd_kernel<true>, dim3((unsigned)blocks), dim3(256), BWD_LDS_BYTES, s, b);
-  } else {
-    want_lds(mlp32_bwd_kernel<false>, BWD_LDS_BYTES);
-    hipLaunchKernelGGL(mlp32_bwd_kernel<false>, dim3((unsigned)blocks), dim3(256), BWD_LDS_BYTES, s, b);
-  }
-  int rc = check_launch("mlp backward chain (fp32)");
+  int rc = with_bool(img, [&](auto im) {
+    return launch<mlp32_bwd_kernel<decltype(im)::value>>("mlp backward chain (fp32)", dim3((unsigned)blocks), dim3(256), BWD_LDS_BYTES, s, b);
+  });
   if (rc) return rc;
   DwArgs32 d;
   int nj = 0;
@@ -964,11 +931,9 @@ int backward(const void* packed32, const void* acts, const float* d_raw, int64_t
   d.njobs = nj; d.splits = splits; d.ntiles = (int)ntiles;
   d.acts = b.acts; d.dz = b.dz; d.grads = grads;
   d.part = reinterpret_cast<float*>(static_cast<char*>(dz) + ntiles * Z_ROWS * 128);     // dz_bytes() counts the slots
-  hipLaunchKernelGGL(mlp32_dw_kernel, dim3((d.unit0[nj] + 3) / 4), dim3(256), 0, s, d);
-  rc = check_launch("mlp dW (fp32)");
+  rc = launch<mlp32_dw_kernel>("mlp dW (fp32)", dim3((d.unit0[nj] + 3) / 4), dim3(256), 0, s, d);
   if (rc) return rc;
-  hipLaunchKernelGGL(mlp32_dw_reduce_kernel, dim3(d.blk0[nj], 8), dim3(256), 0, s, d);       // every parameter is written: no memset
-  return check_launch("mlp dW reduce (fp32)");
+  return launch<mlp32_dw_reduce_kernel>("mlp dW reduce (fp32)", dim3(d.blk0[nj], 8), dim3(256), 0, s, d);       // every parameter is written: no memset
 }
 
 int debug_width(int kind, int layer) {
@@ -978,9 +943,8 @@ int debug_width(int kind, int layer) {
 int debug_read(const void* store, int kind, int layer, int64_t M, float* out, hipStream_t s) {
   int row0 = 0, width = 0;
   NERF_REQUIRE(debug_slot(kind, layer, &row0, &width), NERF_E_SHAPE, "nerf_mlp_debug_read: kind must be 0/1 and layer 0..11");
-  hipLaunchKernelGGL(decode32_kernel, dim3(grid_for(M * width, 256)), dim3(256), 0, s, static_cast<const float*>(store),
-                     kind == 0 ? A_ROWS : Z_ROWS, row0, width, M, out);
-  return check_launch("nerf_mlp_debug_read (fp32)");
+  return launch<decode32_kernel>("nerf_mlp_debug_read (fp32)", dim3(grid_for(M * width, 256)), dim3(256), 0, s, static_cast<const float*>(store),
+                                 kind == 0 ? A_ROWS : Z_ROWS, row0, width, M, out);
 }
 
 }  // namespace f32

@@ -2,6 +2,7 @@
 // LDS-DMA helpers, the LDS weight ring (RingW) and the argument block of the forward kernels.
 #pragma once
 #include "common.h"
+#include "launch.h"
 #include <atomic>
 
 #ifndef NERF_SPREAD_DMA
@@ -28,6 +29,11 @@ typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 struct PeFreq { float pos[10]; float dir[4]; };
+// host: the encoding frequencies of freq_mode 0 (k * k) / 1 (2^k)
+static inline void fill_freqs(float* pos, float* dir, int mode) {
+  for (int k = 0; k < 10; ++k) pos[k] = mode == 0 ? (float)(k * k) : (float)(1 << k);
+  for (int k = 0; k < 4; ++k) dir[k] = mode == 0 ? (float)(k * k) : (float)(1 << k);
+}
 
 // ------------------------------------------------------------------------------------------
 // weight sources: where a wave gets the 1 KiB A-operand fragment `f` of the packed stream from
@@ -355,9 +361,8 @@ static inline unsigned* passq_slot() {
   static unsigned* base[64] = {};
   static DevOnce once;
   static std::atomic<unsigned> next{0};
-  int d = 0;
-  if (hipGetDevice(&d) != hipSuccess || d < 0 || d >= 64) d = 0;
-  once.run([&] { void* p = nullptr; if (hipGetSymbolAddress(&p, HIP_SYMBOL(g_passq)) == hipSuccess) base[d] = static_cast<unsigned*>(p); });
+  const int d = DevOnce::device();
+  once.run(d, [&] { void* p = nullptr; if (hipGetSymbolAddress(&p, HIP_SYMBOL(g_passq)) == hipSuccess) base[d] = static_cast<unsigned*>(p); });
   return base[d] ? base[d] + 4 * (next.fetch_add(1u) % PASSQ_SLOTS) : nullptr;
 }
 

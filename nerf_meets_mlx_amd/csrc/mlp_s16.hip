@@ -702,9 +702,8 @@ __global__ void __launch_bounds__(64 * DW_WAVES) s16_dw_kernel(DwArgs a) {
 
 int pack(const float* params, void* packed_s16, hipStream_t s) {
   char* base = static_cast<char*>(packed_s16);
-  hipLaunchKernelGGL(pack_s16_kernel, dim3((PACK_PAIRS * 64 + 255) / 256), dim3(256), 0, s, params,
-                     reinterpret_cast<bf16x8*>(base), reinterpret_cast<bf16x8*>(base + (size_t)F_FRAGS * 1024));
-  return check_launch("nerf_mlp_pack (split-bf16 image)");
+  return launch<pack_s16_kernel>("nerf_mlp_pack (split-bf16 image)", dim3((PACK_PAIRS * 64 + 255) / 256), dim3(256), 0, s, params,
+                                 reinterpret_cast<bf16x8*>(base), reinterpret_cast<bf16x8*>(base + (size_t)F_FRAGS * 1024));
 }
 
 int forward(const void* packed_s16, const float* bias_slots, const float* x, const float* rays, const float* z, int64_t M,
@@ -714,18 +713,12 @@ int forward(const void* packed_s16, const float* bias_slots, const float* x, con
   a.wf = reinterpret_cast<const bf16x8*>(packed_s16);
   a.bias = bias_slots;
   a.x = x; a.rays = rays; a.z = z; a.M = M; a.n = n; a.out = out; a.acts = acts; a.astride = astride16;
-  for (int k = 0; k < 10; ++k) a.fr.pos[k] = freq_mode == 0 ? (float)(k * k) : (float)(1 << k);
-  for (int k = 0; k < 4; ++k) a.fr.dir[k] = freq_mode == 0 ? (float)(k * k) : (float)(1 << k);
+  fill_freqs(a.fr.pos, a.fr.dir, freq_mode);
   const int64_t nsuper = ((M + 31) / 32 + NW - 1) / NW;
-  const dim3 g((unsigned)(nsuper < persistent_wgs ? nsuper : persistent_wgs)), b(64 * NW);
-  // dynamic LDS above 64 KiB is an opt-in per kernel AND per device
-  static DevOnce once[2];
-  const int mode = x ? 0 : 1;
-  once[mode].run([&] { const void* k = mode == 0 ? reinterpret_cast<const void*>(s16_fwd_kernel<0>) : reinterpret_cast<const void*>(s16_fwd_kernel<1>);
-    (void)hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, FwdRing::LDS_BYTES); });
-  if (mode == 0) hipLaunchKernelGGL(s16_fwd_kernel<0>, g, b, FwdRing::LDS_BYTES, s, a);
-  else hipLaunchKernelGGL(s16_fwd_kernel<1>, g, b, FwdRing::LDS_BYTES, s, a);
-  return check_launch("mlp training forward (split bf16)");
+  return with_bool(x != nullptr, [&](auto rows) {          // MODE 0: embedded rows, 1: rays + depths
+    return launch<s16_fwd_kernel<decltype(rows)::value ? 0 : 1>>("mlp training forward (split bf16)", dim3(persistent_grid(nsuper, persistent_wgs)),
+                                                                  dim3(64 * NW), FwdRing::LDS_BYTES, s, a);
+  });
 }
 
 int backward_chain(const void* packed_s16, const void* acts, const float* d_raw, int64_t M, void* dz, int64_t astride16,
@@ -735,22 +728,17 @@ int backward_chain(const void* packed_s16, const void* acts, const float* d_raw,
   b.wb = reinterpret_cast<const bf16x8*>(static_cast<const char*>(packed_s16) + (size_t)F_FRAGS * 1024);
   b.acts = acts; b.d_raw = d_raw; b.M = M; b.dz = dz; b.astride = astride16; b.zstride = zstride16;
   const int64_t nsuper = ((M + 31) / 32 + NW - 1) / NW;
-  static DevOnce once;
-  once.run([&] { (void)hipFuncSetAttribute(reinterpret_cast<const void*>(s16_bwd_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, BwdRing::LDS_BYTES); });
-  hipLaunchKernelGGL(s16_bwd_kernel, dim3((unsigned)(nsuper < persistent_wgs ? nsuper : persistent_wgs)), dim3(64 * NW),
-                     BwdRing::LDS_BYTES, s, b);
-  return check_launch("mlp backward chain (split bf16)");
+  return launch<s16_bwd_kernel>("mlp backward chain (split bf16)", dim3(persistent_grid(nsuper, persistent_wgs)), dim3(64 * NW),
+                                BwdRing::LDS_BYTES, s, b);
 }
 
 int g_dw_variant = 1;          // nerf_set_option("dw22_variant"): 1 (default) 256 x 256 jobs on mlp_dww.hip's kernel, the others here; 0 every job here
 
 int launch_dw_kernel(const DwArgs& d, int workgroups, bool split_bf16, hipStream_t s) {
-  static DevOnce once[2];
-  once[split_bf16].run([&] { (void)hipFuncSetAttribute(split_bf16 ? reinterpret_cast<const void*>(s16_dw_kernel<true>) : reinterpret_cast<const void*>(s16_dw_kernel<false>),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, DW_LDS_BYTES); });
-  if (split_bf16) hipLaunchKernelGGL(s16_dw_kernel<true>, dim3(workgroups), dim3(64 * DW_WAVES), DW_LDS_BYTES, s, d);
-  else hipLaunchKernelGGL(s16_dw_kernel<false>, dim3(workgroups), dim3(64 * DW_WAVES), DW_LDS_BYTES, s, d);
-  return check_launch(split_bf16 ? "mlp dW (split bf16)" : "mlp dW (bf16)");
+  return with_bool(split_bf16, [&](auto split) {
+    return launch<s16_dw_kernel<decltype(split)::value>>(split_bf16 ? "mlp dW (split bf16)" : "mlp dW (bf16)", dim3(workgroups), dim3(64 * DW_WAVES),
+                                                         DW_LDS_BYTES, s, d);
+  });
 }
 
 }  // namespace s16

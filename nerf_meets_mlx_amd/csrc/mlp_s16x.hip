@@ -297,9 +297,8 @@ __global__ void __launch_bounds__(512) s16_small_bwd_kernel(SmallArgs a) {
 // ==========================================================================================
 int img_pack(const float* params, int out_ch, void* packed, hipStream_t s) {
   char* base = static_cast<char*>(packed);
-  hipLaunchKernelGGL(pack_s16_img_kernel, dim3((IMG_PACK_PAIRS * 64 + 255) / 256), dim3(256), 0, s, params,
-                     reinterpret_cast<bf16x8*>(base), reinterpret_cast<bf16x8*>(base + (size_t)IMG_F_FRAGS * 1024), out_ch);
-  return check_launch("nerf_mlp_pack (image model, split-bf16 image)");
+  return launch<pack_s16_img_kernel>("nerf_mlp_pack (image model, split-bf16 image)", dim3((IMG_PACK_PAIRS * 64 + 255) / 256), dim3(256), 0, s,
+                                     params, reinterpret_cast<bf16x8*>(base), reinterpret_cast<bf16x8*>(base + (size_t)IMG_F_FRAGS * 1024), out_ch);
 }
 
 static void img_fill(ImgArgs& a, const void* packed, const float* bias_slots, int out_ch, int64_t astride16, int64_t zstride16) {
@@ -316,14 +315,11 @@ int img_forward(const void* packed, const float* bias_slots, const float* x, int
   img_fill(a, packed, bias_slots, out_ch, astride16, 0);
   a.x = x; a.out = out; a.acts = acts; a.M = M;
   const int64_t nsuper = ((M + 31) / 32 + NW - 1) / NW;
-  const dim3 g((unsigned)(nsuper < persistent_wgs ? nsuper : persistent_wgs)), b(64 * NW);
-  static DevOnce once;
-  once.run([&] { // dynamic LDS above 64 KiB is an opt-in per kernel AND per device
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(s16_img_fwd_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize, ImgFwdRing::LDS_BYTES);
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(s16_img_fwd_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize, ImgFwdRing::LDS_BYTES); });
-  if (acts) hipLaunchKernelGGL(s16_img_fwd_kernel<true>, g, b, ImgFwdRing::LDS_BYTES, s, a);
-  else hipLaunchKernelGGL(s16_img_fwd_kernel<false>, g, b, ImgFwdRing::LDS_BYTES, s, a);
-  return check_launch("mlp forward (image model, split bf16)");
+  return with_bool(acts != nullptr, [&](auto store) {
+    constexpr bool ST = decltype(store)::value;
+    return launch<s16_img_fwd_kernel<ST>, s16_img_fwd_kernel<!ST>>("mlp forward (image model, split bf16)", dim3(persistent_grid(nsuper, persistent_wgs)),
+                                                                   dim3(64 * NW), ImgFwdRing::LDS_BYTES, s, a);
+  });
 }
 
 int img_backward_chain(const void* packed, const void* acts, const float* d_out, int64_t M, int out_ch, void* dz,
@@ -332,18 +328,14 @@ int img_backward_chain(const void* packed, const void* acts, const float* d_out,
   img_fill(a, packed, nullptr, out_ch, astride16, zstride16);
   a.d_out = d_out; a.acts = const_cast<void*>(acts); a.dz = dz; a.M = M;
   const int64_t nsuper = ((M + 31) / 32 + NW - 1) / NW;
-  static DevOnce once;
-  once.run([&] { (void)hipFuncSetAttribute(reinterpret_cast<const void*>(s16_img_bwd_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, ImgBwdRing::LDS_BYTES); });
-  hipLaunchKernelGGL(s16_img_bwd_kernel, dim3((unsigned)(nsuper < persistent_wgs ? nsuper : persistent_wgs)), dim3(64 * NW),
-                     ImgBwdRing::LDS_BYTES, s, a);
-  return check_launch("mlp backward chain (image model, split bf16)");
+  return launch<s16_img_bwd_kernel>("mlp backward chain (image model, split bf16)", dim3(persistent_grid(nsuper, persistent_wgs)), dim3(64 * NW),
+                                    ImgBwdRing::LDS_BYTES, s, a);
 }
 
 int small_pack(const float* params, void* packed, hipStream_t s) {
   char* base = static_cast<char*>(packed);
-  hipLaunchKernelGGL(pack_s16_small_kernel, dim3(((LN::F_PADDED + LN::B_PADDED) * 64 + 255) / 256), dim3(256), 0, s, params,
-                     reinterpret_cast<bf16x8*>(base), reinterpret_cast<bf16x8*>(base + (size_t)SM_F_FRAGS * 1024));
-  return check_launch("nerf_mlp_pack (2x64 model, split-bf16 image)");
+  return launch<pack_s16_small_kernel>("nerf_mlp_pack (2x64 model, split-bf16 image)", dim3(((LN::F_PADDED + LN::B_PADDED) * 64 + 255) / 256), dim3(256),
+                                       0, s, params, reinterpret_cast<bf16x8*>(base), reinterpret_cast<bf16x8*>(base + (size_t)SM_F_FRAGS * 1024));
 }
 
 static void small_fill(SmallArgs& a, const void* packed, const float* bias_slots, int64_t astride16, int64_t zstride16) {
@@ -356,11 +348,6 @@ static void small_fill(SmallArgs& a, const void* packed, const float* bias_slots
   a.rays = nullptr; a.z = nullptr; a.n = 1; a.tables = nullptr; a.T = 0; a.pos_scale = 1.0f; a.pos_offset = 0.0f;
   a.ray_major = 0; a.B = 0;
   for (int l = 0; l < 32; ++l) { a.rt.res[l] = 0.0f; a.lw.w[l] = 1.0f; }
-}
-
-template <class K>
-static void want_lds(K kernel, DevOnce& once) {
-  once.run([&] { (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, SM_LDS_BYTES); });
 }
 
 int small_forward(const void* packed, const float* bias_slots, const float* x, int64_t M, float* out, void* acts,
@@ -376,19 +363,15 @@ int small_forward(const void* packed, const float* bias_slots, const float* x, i
     a.ray_major = (!acts && q->ray_major && q->B >= 32) ? 1 : 0;
     if (a.ray_major) ntiles = ((q->B + 31) / 32) * (int64_t)q->n;
   }
-  const int64_t nwg = (ntiles + 7) / 8;
-  const dim3 g((unsigned)(nwg < 2048 ? nwg : 2048)), b(512);
-  static DevOnce once[4];
+  const dim3 g(small_grid(ntiles));
   const bool fused = a.rays != nullptr;
   if (fused && q->use_lw) {                  // nerf_ngp_query_fused_lw: the level-weight kernels
     for (int l = 0; l < 32; ++l) a.lw.w[l] = q->lw[l];
     return small_forward_lw(a, g, s);          // mlp_s16x_lw.hip
   }
-  if (acts && fused) { want_lds(s16_small_fwd_kernel<true, true>, once[0]); hipLaunchKernelGGL((s16_small_fwd_kernel<true, true>), g, b, SM_LDS_BYTES, s, a); }
-  else if (acts) { want_lds(s16_small_fwd_kernel<true, false>, once[1]); hipLaunchKernelGGL((s16_small_fwd_kernel<true, false>), g, b, SM_LDS_BYTES, s, a); }
-  else if (fused) { want_lds(s16_small_fwd_kernel<false, true>, once[2]); hipLaunchKernelGGL((s16_small_fwd_kernel<false, true>), g, b, SM_LDS_BYTES, s, a); }
-  else { want_lds(s16_small_fwd_kernel<false, false>, once[3]); hipLaunchKernelGGL((s16_small_fwd_kernel<false, false>), g, b, SM_LDS_BYTES, s, a); }
-  return check_launch("mlp forward (2x64 model, split bf16)");
+  return with_bool(acts != nullptr, [&](auto store) { return with_bool(fused, [&](auto fu) {
+    return launch<s16_small_fwd_kernel<decltype(store)::value, decltype(fu)::value>>("mlp forward (2x64 model, split bf16)", g, dim3(512), SM_LDS_BYTES, s, a);
+  }); });
 }
 
 int small_backward_chain(const void* packed, const void* acts, const float* d_raw, int64_t M, void* dz, float* d_x,
@@ -396,11 +379,7 @@ int small_backward_chain(const void* packed, const void* acts, const float* d_ra
   SmallArgs a;
   small_fill(a, packed, nullptr, astride16, zstride16);
   a.d_raw = d_raw; a.acts = const_cast<void*>(acts); a.dz = dz; a.M = M; a.d_x = d_x;
-  const int64_t nwg = ((M + 31) / 32 + 7) / 8;
-  static DevOnce once;
-  want_lds(s16_small_bwd_kernel, once);
-  hipLaunchKernelGGL(s16_small_bwd_kernel, dim3((unsigned)(nwg < 2048 ? nwg : 2048)), dim3(512), SM_LDS_BYTES, s, a);
-  return check_launch("mlp backward chain (2x64 model, split bf16)");
+  return launch<s16_small_bwd_kernel>("mlp backward chain (2x64 model, split bf16)", dim3(small_grid((M + 31) / 32)), dim3(512), SM_LDS_BYTES, s, a);
 }
 
 }  // namespace s16x

@@ -7,13 +7,10 @@ namespace nerf {
 namespace s16x {
 
 int small_forward_lw(const SmallArgs& a, dim3 grid, hipStream_t s) {
-  static DevOnce once[2];
-  auto want = [](auto kernel, DevOnce& o) {
-    o.run([&] { (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, SM_LDS_BYTES); });
-  };
-  if (a.acts) { want(s16_small_fwd_kernel<true, true, true>, once[0]); hipLaunchKernelGGL((s16_small_fwd_kernel<true, true, true>), grid, dim3(512), SM_LDS_BYTES, s, a); }
-  else { want(s16_small_fwd_kernel<false, true, true>, once[1]); hipLaunchKernelGGL((s16_small_fwd_kernel<false, true, true>), grid, dim3(512), SM_LDS_BYTES, s, a); }
-  return check_launch("mlp forward (2x64 model, split bf16, level weights)");
+  return with_bool(a.acts != nullptr, [&](auto store) {
+    return launch<s16_small_fwd_kernel<decltype(store)::value, true, true>>("mlp forward (2x64 model, split bf16, level weights)", grid, dim3(512),
+                                                                            SM_LDS_BYTES, s, a);
+  });
 }
 
 }  // namespace s16x
