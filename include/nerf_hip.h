@@ -795,6 +795,14 @@ int nerf_comm_destroy(void* comm);
  *   "dw_unit_bias"    (see above) automatic = 128 for the bf16 kernels, 2 for the split-bf16 kernels (round 6: was 32)
  *   "dw_narrow_first" order of the two weight-gradient launches: 1 (default) the narrow jobs before the 256 x 256 jobs | 0 after.
  *                     Same gradients either way.
+ *   "dw_factor"       weight gradients of the 8 x 256 view model at precision 22: 1 (default) the jobs `feature`, `alpha` and
+ *                     `dir0 | feature` run as ONE job (d alpha and dZ_D against H7: G = dZ_D H7^T, db_D) followed by a small post step
+ *                     that forms dW_F = W_D[:, :256]^T G, db_F = W_D[:, :256]^T db_D and dW_D[:, :256] = G W_F^T + db_D b_F^T from the
+ *                     packed split-bf16 weights in float64 (feature has no activation, so this is exact algebra): H7 is read once
+ *                     instead of three times, dZ_F and the stored feature not at all | 0 the three jobs.  G and db_D live in a
+ *                     partial-tile slot that is idle at that moment: no workspace size changes.  Other models and precisions, a
+ *                     non-zero "dw_job_mask" and "dw22_variant" 0 (one launch over all slots) keep the three jobs whatever this says.
+ *                     The affected tensors are summed in a different order (~1e-6 rel-L2); each setting is bit-reproducible.
  * nerf_get_option returns the current value of EVERY key nerf_set_option accepts (a get / set pair restores a setting;
  * "dw_unit_bias" reads -1 while it is automatic), or NERF_OPTION_UNKNOWN for an unknown key.                        */
 #define NERF_OPTION_UNKNOWN (-2147483647 - 1)

@@ -1110,9 +1110,18 @@ __global__ void __launch_bounds__(256) mlp_dw_reduce_kernel(DwArgs a) {
       const int n = t / jb.k_valid, k = t - n * jb.k_valid;
       src = base + (8 * (n >> 5) + (k >> 5)) * 1024 + (n & 31) * 32 + (k & 31);
       dst = a.grads + jb.w_off + (int64_t)n * jb.ldw + jb.col0 + k;
+      if (jb.aux_row0 > 0) {                   // (DwJob) rows that are no gradient: to aux, or nowhere
+        if (n >= jb.aux_row0) dst = a.aux + (n - jb.aux_row0) * jb.k_valid + k;
+        else if (n >= jb.n_grad) continue;
+      }
     } else {
-      src = base + 64 * 1024 + (t - nw);
-      dst = a.grads + jb.b_off + (t - nw);
+      const int n = t - nw;
+      src = base + 64 * 1024 + n;
+      dst = a.grads + jb.b_off + n;
+      if (jb.aux_row0 > 0) {
+        if (n >= jb.aux_row0) dst = a.aux + (jb.n_valid - jb.aux_row0) * jb.k_valid + (n - jb.aux_row0);
+        else if (n >= jb.n_grad) continue;
+      }
     }
     float sum = 0.0f;
     int sidx = 0;
@@ -1543,6 +1552,7 @@ static int g_dw_ring_cap = 8;  // "dw_ring_cap": most stages the 16-wave split-b
 static int g_dw_private = 4;   // "dw_private_tiles": split-bf16 dW jobs of at most this many output tiles run as sixteen wave-private pipelines (0 = off)
 static int g_dw16_variant = 1;  // "dw16_variant": bf16 weight gradients: 1 (default) = 256 x 256 jobs on mlp_dww.hip's kernel, tiny-job lists on mlp_s16.hip's, the rest on mlp_dw_kernel; 0 = every job on mlp_dw_kernel; 2 = as 1 without the tiny-job rule; 3 = as 1 with mlp_s16.hip's kernel for every narrow job
 static int g_dw_narrow_first = 1;   // "dw_narrow_first": order of the two weight-gradient launches (A/B knob; same gradients either way)
+static int g_dw_factor = 1;    // "dw_factor": view model at precision 22: 1 = feature / alpha / dir0 | feature as one shared job + post step (mlp_model.h), 0 = three jobs
 static int g_dw_job_mask = 0;  // diagnostic: nonzero = run only these dW jobs (bit j); view model only
 // (g_tile_pad16, "tile_pad16": mlp_model.h, beside the strides it enters)
 static int g_mlp_variant = 0;   // 0: auto, 1: ST=1 via L1, 2: ST=2 via L1, 3: LDS ring, 8 waves x 32 samples, 32x32x16 MFMA,
@@ -1593,6 +1603,7 @@ static const Option OPTIONS[] = {
     {"dw_ring_cap", &g_dw_ring_cap, opt_clamp<2, 16>, nullptr},
     {"pass_queue", &g_pass_queue, opt_flag, nullptr},
     {"dw_narrow_first", &g_dw_narrow_first, opt_flag, nullptr},
+    {"dw_factor", &g_dw_factor, opt_flag, nullptr},
     {"f22_tiles", &f22::g_tiles, [](int& v) { return v == 0 || v == 2 || v == 3; }, "nerf_set_option: f22_tiles must be 0 (automatic), 2 or 3"},
 };
 
@@ -1797,10 +1808,14 @@ extern "C" int nerf_query_fused(const nerf_mlp_arch* arch, const void* packed, c
 // 2 / 3: split bf16 / bf16, 256 x 256 jobs only, one wave per SIMD (mlp_dww_kernel).  slot_base: first partial-tile slot of this
 // launch (the two launches of one backward pass use disjoint slots).
 static int launch_dw_part(const Model& m, DwArgs& d, int nj, int64_t ntiles, const void* acts, void* dz, float* grads,
-                          hipStream_t s, int kind, int slot_base, int max_wgs) {
+                          hipStream_t s, int kind, int slot_base, int max_wgs, int aux_slot = -1) {
   static_assert(DW_SPLIT_MAX_JOBS == DW_MAX_JOBS, "dw_split.h sizes its arrays for DwArgs::jobs");
   DwCost cost[DW_MAX_JOBS];
-  for (int j = 0; j < nj; ++j) cost[j] = DwCost{d.jobs[j].nf, d.jobs[j].kf};
+  // The shared job of the factored view model (aux_row0 > 0) multiplies 5 x 8 output tiles for its 25 KiB per half tile, twice the
+  // tiles per byte of the other narrow jobs, and the 16-wave kernel runs a stage's reads and MFMAs one after the other: it is costed
+  // 12 units above its bytes (training step, blocks of 12 steps, three each: +0 10.13 | +6 10.03 | +12 9.99 | +18 10.03 | +24 10.07 ms).
+  constexpr int SHARED_JOB_EXTRA_UNITS = 12;
+  for (int j = 0; j < nj; ++j) cost[j] = DwCost{d.jobs[j].nf, d.jobs[j].kf + (d.jobs[j].aux_row0 > 0 ? SHARED_JOB_EXTRA_UNITS : 0)};
   // the cost model and the largest-remainder split: dw_split.h.  "dw_workgroups" overrides the total.
   int target_wgs = g_dw_wgs > 0 ? g_dw_wgs : cu_count();
   if (target_wgs > max_wgs) target_wgs = max_wgs;               // one partial-tile slot per workgroup
@@ -1813,6 +1828,7 @@ static int launch_dw_part(const Model& m, DwArgs& d, int nj, int64_t ntiles, con
   d.a_lo = m.info->a_lo; d.z_lo = m.info->z_lo; d.ring_cap = g_dw_ring_cap; d.private_max_tiles = g_dw_private;
   // the partial-tile slots live behind the dZ fragment blocks in the caller's dz workspace (nerf_mlp_dz_bytes counts them)
   d.partial = m.dw_partial(dz, ntiles) + (size_t)slot_base * DW_SLOT_FLOATS;
+  d.aux = aux_slot >= 0 ? m.dw_partial(dz, ntiles) + (size_t)aux_slot * DW_SLOT_FLOATS : nullptr;
   int rc;
   if (kind >= 2) {             // 16 x 16-fragment jobs, one wave per SIMD (mlp_dww.hip); same slots and reduce
     rc = launch_dw_wide_kernel(d, nw, kind == 2, s);
@@ -1830,8 +1846,14 @@ static int launch_dw_part(const Model& m, DwArgs& d, int nj, int64_t ntiles, con
   return launch<mlp_dw_reduce_kernel>("mlp dW reduce", dim3(257, nj), dim3(256), 0, s, d);        // 256 x 256 weights + 256 biases: one element per thread
 }
 
-// split the (dZ, H) jobs over workgroups and launch the dW kernel(s); grads[0..m.params) is overwritten
-static int launch_dw(const Model& m, DwArgs& d, int nj, int64_t ntiles, const void* acts, void* dz, float* grads, hipStream_t s) {
+// split the (dZ, H) jobs over workgroups and launch the dW kernel(s); grads[0..m.params) is overwritten.
+// factored: d.jobs is the view model's factored list (mlp_model.h).  Its shared job is a narrow one; the reduce of the narrow launch
+// leaves G and db_D in the FIRST partial-tile slot of the wide launch's half, which is idle then in either order of the two launches
+// (not yet written, or already reduced: the stream serialises them), and the post step runs directly behind that reduce, in front of
+// whatever the wide launch does next.  No byte of workspace is added.  The one-launch form ("dw22_variant" 0) may use all slots, so
+// the caller keeps the legacy table there.
+static int launch_dw(const Model& m, const void* packed, DwArgs& d, int nj, int64_t ntiles, const void* acts, void* dz, float* grads,
+                     hipStream_t s, bool factored) {
   if (g_dw_job_mask) {          // diagnostic subset of jobs: the parameters of the jobs left out read as zero
     hipError_t e = hipMemsetAsync(grads, 0, sizeof(float) * m.params, s);
     if (e != hipSuccess) return fail(NERF_E_HIP, "nerf_mlp_backward: memset: %s", hipGetErrorString(e));
@@ -1855,7 +1877,9 @@ static int launch_dw(const Model& m, DwArgs& d, int nj, int64_t ntiles, const vo
       if (rc) return rc;
     }
     if (!do_wide && nrest) {
-      const int rc = launch_dw_part(m, rest, nrest, ntiles, acts, dz, grads, s, split_bf16 ? 1 : 0, 0, half);
+      int rc = launch_dw_part(m, rest, nrest, ntiles, acts, dz, grads, s, split_bf16 ? 1 : 0, 0, half, factored ? half : -1);
+      if (!rc && factored)
+        rc = launch_dw_factor_post(m.stream<void>(packed, S_S16), m.stream<float>(packed, S_BIAS), rest.aux, grads, s);
       if (rc) return rc;
     }
   }
@@ -1932,8 +1956,10 @@ static int mlp_backward_impl(const nerf_mlp_arch* arch, const void* packed, cons
   if (rc) return rc;
   // ---- 2. dW / db
   DwArgs d;
-  const int nj = m.dw_jobs(d.jobs, m.shape == Shape::View ? g_dw_job_mask : 0);
-  return launch_dw(m, d, nj, ntiles, acts, dz, grads, s);
+  const int mask = m.shape == Shape::View ? g_dw_job_mask : 0;
+  const bool factored = g_dw_factor && m.can_factor() && !mask && s16::g_dw_variant != 0;      // (launch_dw: two launches only)
+  const int nj = m.dw_jobs(d.jobs, mask, factored);
+  return launch_dw(m, packed, d, nj, ntiles, acts, dz, grads, s, factored);
 }
 
 // lw_host: the level weights of nerf_ngp_query_fused_lw; NULL = the kernels without them

@@ -16,68 +16,15 @@ __host__ __device__ constexpr Chan chan_of(int c, int limit) {
 // ------------------------------------------------------------------------------------------
 // weight packing sources: which master parameter sits in element j of lane (r, h) of fragment f of the 32x32x16 streams
 // ------------------------------------------------------------------------------------------
+// (the index arithmetic itself: fwd_index / bwd_index in mlp_index.h, shared with the host)
 __device__ inline float fwd_src(const float* __restrict__ p, int f, int r, int h, int j) {
-  int nt, ks;
-  if (f < L::F_L1) {                                   // pos0: K space 64 (63 + pad)
-    nt = f / 4; ks = f % 4;
-    const int kk = kperm(ks, h, j);
-    return kk < 63 ? p[L::P_W0 + (32 * nt + r) * 63 + kk] : 0.0f;
-  }
-  if (f < L::F_L5) {                                   // pos1..pos4
-    const int l = 1 + (f - L::F_L1) / 128, g = (f - L::F_L1) % 128;
-    nt = g / 16; ks = g % 16;
-    return p[L::pw(l) + (32 * nt + r) * 256 + kperm(ks, h, j)];
-  }
-  if (f < L::F_L6) {                                   // pos5: [PE(64), H4(256)] vs W5[256][319]
-    const int g = f - L::F_L5;
-    nt = g / 20; ks = g % 20;
-    const int kk = kperm(ks, h, j), n = 32 * nt + r;
-    if (kk < 64) return kk < 63 ? p[L::P_W5 + n * 319 + kk] : 0.0f;
-    return p[L::P_W5 + n * 319 + 63 + (kk - 64)];
-  }
-  if (f < L::F_FA) {                                   // pos6, pos7
-    const int l = 6 + (f - L::F_L6) / 128, g = (f - L::F_L6) % 128;
-    nt = g / 16; ks = g % 16;
-    return p[L::pw(l) + (32 * nt + r) * 256 + kperm(ks, h, j)];
-  }
-  if (f < L::F_DIR) {                                  // feature (8 tiles) + alpha (tile 8, row 0)
-    const int g = f - L::F_FA;
-    nt = g / 16; ks = g % 16;
-    const int kk = kperm(ks, h, j);
-    if (nt < 8) return p[L::P_WF + (32 * nt + r) * 256 + kk];
-    return r == 0 ? p[L::P_WA + kk] : 0.0f;
-  }
-  if (f < L::F_RGB) {                                  // dir0: [feature(256), dirPE(27+5 pad)] vs WD[128][283]
-    const int g = f - L::F_DIR;
-    nt = g / 18; ks = g % 18;
-    const int kk = kperm(ks, h, j), n = 32 * nt + r;
-    if (kk < 256) return p[L::P_WD + n * 283 + kk];
-    return (kk - 256) < 27 ? p[L::P_WD + n * 283 + kk] : 0.0f;
-  }
-  ks = f - L::F_RGB;                                   // rgb: rows 0..2 of one tile, K = 128
-  return r < 3 ? p[L::P_WR + r * 128 + kperm(ks, h, j)] : 0.0f;
+  const int i = fwd_index(f, r, h, j);
+  return i >= 0 ? p[i] : 0.0f;
 }
-
 // transposed stream: A rows = INPUT feature (32 kt + r), k index = OUTPUT feature nn
 __device__ inline float bwd_src(const float* __restrict__ p, int f, int r, int h, int j) {
-  if (f < L::B_DIR) {                                  // rgb^T: 4 tiles of H_d, one k-step (rows 0..2)
-    const int nn = kperm(0, h, j);
-    return nn < 3 ? p[L::P_WR + nn * 128 + 32 * f + r] : 0.0f;
-  }
-  if (f < L::B_FA) {                                   // dir0^T, feature columns only: 8 tiles x 8 k-steps
-    const int g = f - L::B_DIR, kt = g / 8, ns = g % 8;
-    return p[L::P_WD + kperm(ns, h, j) * 283 + 32 * kt + r];
-  }
-  if (f < L::B_L7) {                                   // [feature; alpha]^T: 8 tiles x 17 k-steps
-    const int g = f - L::B_FA, kt = g / 17, ns = g % 17;
-    const int nn = kperm(ns, h, j);
-    if (ns < 16) return p[L::P_WF + nn * 256 + 32 * kt + r];
-    return nn == 256 ? p[L::P_WA + 32 * kt + r] : 0.0f;
-  }
-  const int g = f - L::B_L7, li = g / 128, q = g % 128, kt = q / 16, ns = q % 16;   // pos7, 6, 5, 4, 3, 2, 1
-  const int l = 7 - li, nn = kperm(ns, h, j), row = 32 * kt + r;
-  if (l == 5) return p[L::P_W5 + nn * 319 + 63 + row];
-  return p[L::pw(l) + nn * 256 + row];
+  const int i = bwd_index(f, r, h, j);
+  return i >= 0 ? p[i] : 0.0f;
 }
 
 // fragment block address: tile T, slot s, lane (r,h) at byte 32 r + 16 h.  Written as (uniform 64-bit tile base) +
@@ -237,6 +184,10 @@ struct DwJob {
   int w_off, ldw, col0;   // grads[w_off + n*ldw + col0 + k]
   int n_valid, k_valid;
   int b_off;              // bias gradient offset or -1 (only the job with col0 == 0 of a layer owns it)
+  // aux_row0 > 0: a job whose result is only in part a gradient (the shared job of the factored view model, mlp_model.h).  Rows
+  // [0, n_grad) go to grads as above; rows [aux_row0, n_valid) go to DwArgs::aux, row n at aux[(n - aux_row0) * k_valid + k], its
+  // bias sum at aux[(n_valid - aux_row0) * k_valid + (n - aux_row0)]; the rows between the two ranges are written nowhere.
+  int n_grad, aux_row0;
 };
 constexpr int DW_MAX_JOBS = 16;
 struct DwArgs {
@@ -251,6 +202,7 @@ struct DwArgs {
   int ring_cap;           // s16_dw_kernel: most stages its LDS ring may hold (<= 16)
   int private_max_tiles;  // s16_dw_kernel: jobs of at most this many output tiles (<= 4) run as sixteen independent wave pipelines; 0 = none
   int a_lo, z_lo;         // split-bf16 stores (mlp_s16.hip's dW kernel): slot distance from a hi block to its lo block in acts / dz
+  float* aux;             // mlp_dw_reduce_kernel: where the non-gradient rows of a job with aux_row0 > 0 go (else unused)
 };
 // One slot per dW workgroup: up to 8 x 8 output tiles of 32 x 32 floats (tile (nt, kt) at (8 nt + kt) * 1024, row-major
 // inside the tile) + 8 x 32 bias partial sums.  The workgroups of a job write their partial dW here with plain
@@ -260,6 +212,13 @@ struct DwArgs {
 constexpr int DW_SLOT_FLOATS = 64 * 1024 + 256;
 constexpr int DW_MAX_WGS = 512;
 constexpr int64_t DW_PARTIAL_BYTES = (int64_t)DW_MAX_WGS * DW_SLOT_FLOATS * 4;
+// Factored weight gradients of the view model's feature and dir0 layers ("dw_factor", mlp_model.h): the reduce of the shared job
+// leaves G[128][256] = dZ_D H7^T and db_D[128] in one partial-tile slot of the launch that is idle, the post step (mlp_dwf.hip)
+// turns them into dW_F, db_F and columns 0..255 of dW_D.
+constexpr int DWF_G = 0, DWF_DB = 128 * 256, DWF_FLOATS = DWF_DB + 128;
+static_assert(DWF_FLOATS <= DW_SLOT_FLOATS, "the factored job's result fits one partial-tile slot");
+// packed_s16: the split-bf16 image of the model (forward stream first); bias_slots: its fp32 bias slots
+int launch_dw_factor_post(const void* packed_s16, const float* bias_slots, const float* aux, float* grads, hipStream_t s);
 // dW of jobs of 16 x 16 fragments only, one wave per SIMD (mlp_dww.hip); split_bf16: hi + lo blocks (precision 22), else bf16 blocks
 int launch_dw_wide_kernel(const DwArgs& d, int workgroups, bool split_bf16, hipStream_t s);
 

@@ -1,0 +1,111 @@
+// Which master parameter sits where in the 32x32x16 weight fragment streams of the 8 x 256 view model, and back.  Pure integer
+// arithmetic without a HIP dependency, shared by host and device: nerf_mlp_pack fills the streams through fwd_index / bwd_index
+// (mlp_frag.h: fwd_src / bwd_src), the post step of the factored weight gradients (mlp_dwf.hip) finds W_F and W_D in the packed
+// split-bf16 image through fwd_elem, and a CPU test walks both directions against each other (tests/frag_index_check.cpp).
+#pragma once
+#if !defined(__HIPCC__) && !defined(__host__)
+#define __host__
+#define __device__
+#endif
+#include "mlp_params.h"
+
+namespace nerf {
+
+namespace L {
+// forward weight stream, 1 KiB fragments in consumption order
+constexpr int F_L0 = 0, F_L1 = 32, F_L5 = 544, F_L6 = 704, F_L7 = 832, F_FA = 960, F_DIR = 1104, F_RGB = 1176;
+constexpr int F_TOTAL = 1184;
+// backward (transposed) weight stream
+constexpr int B_RGB = 0, B_DIR = 4, B_FA = 68, B_L7 = 204, B_L6 = 332, B_L5 = 460, B_L4 = 588;
+constexpr int B_TOTAL = 1100, B_PADDED = 1120;    // padded with zero fragments to whole 32-fragment ring chunks
+}  // namespace L
+
+// element j of lane half h in k-step ks  <->  feature index
+__host__ __device__ constexpr int kperm(int ks, int h, int j) { return 16 * ks + 8 * (j >> 2) + 4 * h + (j & 3); }
+// ... and back: feature index kk = kperm(kperm_ks(kk), kperm_h(kk), kperm_j(kk))
+__host__ __device__ constexpr int kperm_ks(int kk) { return kk >> 4; }
+__host__ __device__ constexpr int kperm_h(int kk) { return (kk >> 2) & 1; }
+__host__ __device__ constexpr int kperm_j(int kk) { return 4 * ((kk >> 3) & 1) + (kk & 3); }
+
+// ------------------------------------------------------------------------------------------
+// weight packing sources: offset of the master parameter that sits in element j of lane (r, h) of fragment f; -1 = zero padding
+// ------------------------------------------------------------------------------------------
+__host__ __device__ constexpr int fwd_index(int f, int r, int h, int j) {
+  if (f < L::F_L1) {                                   // pos0: K space 64 (63 + pad)
+    const int nt = f / 4, ks = f % 4;
+    const int kk = kperm(ks, h, j);
+    return kk < 63 ? L::P_W0 + (32 * nt + r) * 63 + kk : -1;
+  }
+  if (f < L::F_L5) {                                   // pos1..pos4
+    const int l = 1 + (f - L::F_L1) / 128, g = (f - L::F_L1) % 128;
+    const int nt = g / 16, ks = g % 16;
+    return L::pw(l) + (32 * nt + r) * 256 + kperm(ks, h, j);
+  }
+  if (f < L::F_L6) {                                   // pos5: [PE(64), H4(256)] vs W5[256][319]
+    const int g = f - L::F_L5;
+    const int nt = g / 20, ks = g % 20;
+    const int kk = kperm(ks, h, j), n = 32 * nt + r;
+    if (kk < 64) return kk < 63 ? L::P_W5 + n * 319 + kk : -1;
+    return L::P_W5 + n * 319 + 63 + (kk - 64);
+  }
+  if (f < L::F_FA) {                                   // pos6, pos7
+    const int l = 6 + (f - L::F_L6) / 128, g = (f - L::F_L6) % 128;
+    const int nt = g / 16, ks = g % 16;
+    return L::pw(l) + (32 * nt + r) * 256 + kperm(ks, h, j);
+  }
+  if (f < L::F_DIR) {                                  // feature (8 tiles) + alpha (tile 8, row 0)
+    const int g = f - L::F_FA;
+    const int nt = g / 16, ks = g % 16;
+    const int kk = kperm(ks, h, j);
+    if (nt < 8) return L::P_WF + (32 * nt + r) * 256 + kk;
+    return r == 0 ? L::P_WA + kk : -1;
+  }
+  if (f < L::F_RGB) {                                  // dir0: [feature(256), dirPE(27+5 pad)] vs WD[128][283]
+    const int g = f - L::F_DIR;
+    const int nt = g / 18, ks = g % 18;
+    const int kk = kperm(ks, h, j), n = 32 * nt + r;
+    if (kk < 256) return L::P_WD + n * 283 + kk;
+    return (kk - 256) < 27 ? L::P_WD + n * 283 + kk : -1;
+  }
+  const int ks = f - L::F_RGB;                         // rgb: rows 0..2 of one tile, K = 128
+  return r < 3 ? L::P_WR + r * 128 + kperm(ks, h, j) : -1;
+}
+
+// transposed stream: A rows = INPUT feature (32 kt + r), k index = OUTPUT feature nn
+__host__ __device__ constexpr int bwd_index(int f, int r, int h, int j) {
+  if (f < L::B_DIR) {                                  // rgb^T: 4 tiles of H_d, one k-step (rows 0..2)
+    const int nn = kperm(0, h, j);
+    return nn < 3 ? L::P_WR + nn * 128 + 32 * f + r : -1;
+  }
+  if (f < L::B_FA) {                                   // dir0^T, feature columns only: 8 tiles x 8 k-steps
+    const int g = f - L::B_DIR, kt = g / 8, ns = g % 8;
+    return L::P_WD + kperm(ns, h, j) * 283 + 32 * kt + r;
+  }
+  if (f < L::B_L7) {                                   // [feature; alpha]^T: 8 tiles x 17 k-steps
+    const int g = f - L::B_FA, kt = g / 17, ns = g % 17;
+    const int nn = kperm(ns, h, j);
+    if (ns < 16) return L::P_WF + nn * 256 + 32 * kt + r;
+    return nn == 256 ? L::P_WA + 32 * kt + r : -1;
+  }
+  const int g = f - L::B_L7, li = g / 128, q = g % 128, kt = q / 16, ns = q % 16;   // pos7, 6, 5, 4, 3, 2, 1
+  const int l = 7 - li, nn = kperm(ns, h, j), row = 32 * kt + r;
+  if (l == 5) return L::P_W5 + nn * 319 + 63 + row;
+  return L::pw(l) + nn * 256 + row;
+}
+
+// ------------------------------------------------------------------------------------------
+// ... and back, for the two matrices the factored weight gradients read out of the forward stream
+// ------------------------------------------------------------------------------------------
+struct FragElem { int f, r, h, j; };                   // fragment, lane (r, h), element
+// W_F[row][col] (feature layer, 256 x 256): fwd_index(fwd_elem_feature(row, col)) == P_WF + row * 256 + col
+__host__ __device__ constexpr FragElem fwd_elem_feature(int row, int col) {
+  return FragElem{L::F_FA + 16 * (row >> 5) + kperm_ks(col), row & 31, kperm_h(col), kperm_j(col)};
+}
+// W_D[row][col], col < 256 (dir0 layer, feature columns): fwd_index(fwd_elem_dir0(row, col)) == P_WD + row * 283 + col
+__host__ __device__ constexpr FragElem fwd_elem_dir0(int row, int col) {
+  return FragElem{L::F_DIR + 18 * (row >> 5) + kperm_ks(col), row & 31, kperm_h(col), kperm_j(col)};
+}
+// bf16 element index of a fragment element in a weight stream of 1 KiB fragments: lane 32 h + r holds eight elements of 2 bytes
+__host__ __device__ constexpr int frag_elem_offset(const FragElem& e) { return (e.f * 64 + 32 * e.h + e.r) * 8 + e.j; }
+
+}  // namespace nerf

@@ -3,6 +3,7 @@
 #pragma once
 #include "mlp_ring.h"
 #include "mlp_params.h"
+#include "mlp_index.h"
 
 namespace nerf {
 
@@ -12,12 +13,7 @@ namespace nerf {
 namespace L {
 // float32 parameter offsets P_*: mlp_params.h (shared with the fp32 reference-precision kernels of mlp32.hip)
 
-// forward weight stream, 1 KiB fragments in consumption order
-constexpr int F_L0 = 0, F_L1 = 32, F_L5 = 544, F_L6 = 704, F_L7 = 832, F_FA = 960, F_DIR = 1104, F_RGB = 1176;
-constexpr int F_TOTAL = 1184;
-// backward (transposed) weight stream
-constexpr int B_RGB = 0, B_DIR = 4, B_FA = 68, B_L7 = 204, B_L6 = 332, B_L5 = 460, B_L4 = 588;
-constexpr int B_TOTAL = 1100, B_PADDED = 1120;    // padded with zero fragments to whole 32-fragment ring chunks
+// forward / backward weight streams F_*, B_* (1 KiB fragments in consumption order): mlp_index.h
 // fp32 bias slots
 constexpr int BI_FEAT = 2048, BI_ALPHA = 2304, BI_DIR = 2336, BI_RGB = 2464, BI_TOTAL = 2496;
 constexpr int F16_TOTAL = 1172, F16_PADDED = 1184;   // forward stream of the 16x16x32 variant (inference only)
@@ -35,8 +31,7 @@ constexpr int Z_L0 = 0;                            // dZ_l at 16 l, l = 0..7
 constexpr int Z_F = 128, Z_A = 144, Z_D = 145, Z_RGB = 153, Z_SLOTS = 154;
 }  // namespace L
 
-// element j of lane half h in k-step ks  <->  feature index
-__host__ __device__ constexpr int kperm(int ks, int h, int j) { return 16 * ks + 8 * (j >> 2) + 4 * h + (j & 3); }
+// kperm (element j of lane half h in k-step ks <-> feature index): mlp_index.h
 
 namespace L16 {
 constexpr int F_L0 = 0, F_L1 = 32, F_L5 = 544, F_L6 = 704, F_L7 = 832, F_FA = 960, F_DIR = 1096, F_RGB = 1168;

@@ -45,6 +45,18 @@ constexpr DwJob VIEW_JOBS[] = {
     {L::Z_D, 8, L::A_DPE, 2, L::P_WD, 283, 256, 128, 27, -1},                          // dir0 | dirPE
     {L::Z_RGB, 1, L::A_HD, 8, L::P_WR, 128, 0, 3, 128, L::P_BR},                       // rgb
 };
+// The same gradients with the feature and dir0 layers factored ("dw_factor", precision 22).  feature = W_F h7 + b_F has no
+// activation (models/NeRF.py:231), so with  G = dZ_D H7^T (128 x 256)  and  db_D = row sums of dZ_D
+//     dW_F = W_D[:, :256]^T G,   db_F = W_D[:, :256]^T db_D,   dW_D[:, :256] = G W_F^T + db_D b_F^T
+// and the jobs `feature`, `alpha` and `dir0 | feature` (73 operand fragments per sample tile, H7 read three times) become ONE job
+// over the nine adjacent dZ fragments Z_A, Z_D .. Z_D + 7 and H7 (25 fragments): row 0 of its result is d alpha, rows 16 .. 143
+// are G (DwJob::aux_row0), which the post step of mlp_dwf.hip multiplies with the packed weights once per call.
+static_assert(L::Z_D == L::Z_A + 1, "d alpha and dZ_D are adjacent dZ fragments");
+constexpr DwJob VIEW_JOBS_FACTORED[] = {
+    VIEW_JOBS[0], VIEW_JOBS[1], VIEW_JOBS[2], VIEW_JOBS[3], VIEW_JOBS[4], VIEW_JOBS[5], VIEW_JOBS[6], VIEW_JOBS[7], VIEW_JOBS[8],
+    {L::Z_A, 9, L::A_H0 + 112, 16, L::P_WA, 256, 0, 16 + 128, 256, L::P_BA, 1, 16},    // alpha | G, db_D (shared)
+    VIEW_JOBS[12], VIEW_JOBS[13],                                                      // dir0 | dirPE, rgb
+};
 constexpr DwJob IMG_JOBS[] = {
     {LI::Z_L0, 16, LI::A_X, 3, LI::P_W0, 40, 0, 256, 40, LI::P_B0},                    // pos0
     img_pos(1), img_pos(2), img_pos(3), img_pos(4),                                    // pos1..4
@@ -117,9 +129,16 @@ struct Model {
     return !ok || M < 0 ? -1 : prec == Prec::F32 ? f32::dz_bytes(M) : padded_tiles(M) * zstride() * 16 + DW_PARTIAL_BYTES;
   }
   float* dw_partial(void* dz, int64_t ntiles) const { return reinterpret_cast<float*>(static_cast<char*>(dz) + padded_tiles(ntiles * 32) * zstride() * 16); }
-  // copies the weight-gradient jobs whose bit is set in `mask` (0: all) to dst, returns their number
-  int dw_jobs(DwJob* dst, int mask) const {
+  // copies the weight-gradient jobs whose bit is set in `mask` (0: all) to dst, returns their number.  factored: the view model's
+  // precision-22 list with the shared job (VIEW_JOBS_FACTORED; the caller runs the post step behind its reduce).  A mask names
+  // jobs of the legacy table, so it keeps that table.
+  bool can_factor() const { return shape == Shape::View && prec == Prec::Split; }
+  int dw_jobs(DwJob* dst, int mask, bool factored = false) const {
     int nj = 0;
+    if (factored && can_factor() && !mask) {
+      for (const DwJob& j : VIEW_JOBS_FACTORED) dst[nj++] = j;
+      return nj;
+    }
     for (int j = 0; j < info->njobs; ++j) {
       if (mask && !((mask >> j) & 1)) continue;
       dst[nj] = info->jobs[j];

@@ -42,4 +42,4 @@ for r in range(a.rounds):
         res[v].append(block(a.steps))
 for v in a.values:
     t = [x[0] for x in res[v]]; rn = [x[1] for x in res[v]]
-    print(f"{a.key} = {v}: train {np.mean(t):.3f} ms/step ({4096 / np.mean(t) / 1e3:.4f} M rays/s; blocks " + " ".join(f"{x:.3f}" for x in t) + f") | render {np.mean(rn):.3f} ms", flush=True)
+    print(f"{a.key} = {v}: train {np.mean(t):.3f} ms/step ({4096 / np.mean(t) / 1e3:.4f} M rays/s; blocks " + " ".join(f"{x:.3f}" for x in t) + f") | render {np.mean(rn):.3f} ms (blocks " + " ".join(f"{x:.3f}" for x in rn) + ")", flush=True)
