@@ -34,7 +34,14 @@
 #define NERF_F22_MIXSUB 1     // lo part of the activation split: v - hi as one v_fma_mix_f32 (see split2); 0: v_cvt_f32_f16 + v_sub_f32
 #endif
 #ifndef NERF_F22_RG3
-#define NERF_F22_RG3 4        // LDS weight fragments fetched per software-pipeline group in the 48-sample kernel (2: 16 registers less, no spill, 1.3 % slower)
+#define NERF_F22_RG3 4        // LDS weight fragments fetched per software-pipeline group in the 48-sample kernel (2: 16 registers less, no spill; 1.3 % slower in time, 6 % in cycles)
+#endif
+// input fragments of pos5 that the 48-sample kernel keeps in the LDS for the length of that layer (layer22, PARK_LDS).  Unfolded stream: 1.
+// Folded stream: 2 -- pos5 is the same layer in both, but with the shorter tail behind it hipcc's register allocation of it no longer
+// closes with one: an output fragment goes to scratch for the length of the layer, i.e. a reload (s_waitcnt vmcnt(0): a drain of the
+// weight ring) in the middle of every pass, which the build's scratch gate (Makefile, SCRATCH_OK_mlp22) refuses.
+#ifndef NERF_F22_PARK
+#define NERF_F22_PARK (NERF_F22_FOLD ? 2 : 1)
 #endif
 #ifndef NERF_F22_IGLP
 #define NERF_F22_IGLP 0       // __builtin_amdgcn_iglp_opt strategy of the layer body; -1: none
@@ -50,8 +57,15 @@ typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 
 constexpr float LO_SCALE = 2048.0f, LO_INV = 1.0f / 2048.0f;
 constexpr float F16_MIN_NORMAL = 6.103515625e-05f;          // 2^-14
-constexpr int CHUNKS = F_PADDED / RING_CHUNK;               // 74
-static_assert(CHUNKS * RING_CHUNK == F_PADDED && F_FRAGS % 4 == 0 && F_PAIRS == L::F16_TOTAL, "f22 stream layout");
+// the trunk is the bf16 16x16x32 stream's (fwd_src16); the ring walks CHUNKS chunks per pass, the last one partly: a chunk count
+// other than ceil(F_FRAGS / chunk) would start a workgroup's second pass on shifted weights
+static_assert(F_CHUNK == RING_CHUNK && CHUNKS == (F_FRAGS + RING_CHUNK - 1) / RING_CHUNK && CHUNKS * RING_CHUNK <= F_PADDED, "f22 ring chunks");
+static_assert(P_L0 == L16::F_L0 && P_L1 == L16::F_L1 && P_L5 == L16::F_L5 && P_L6 == L16::F_L6 && P_L7 == L16::F_L7 && P_HEADS == L16::F_FA, "f22 trunk");
+#if NERF_F22_FOLD
+static_assert(F_PAIRS == L::F16_TOTAL - 128 && CHUNKS == 66 && F_FRAGS % RING_CHUNK == (2 * L::F16_TOTAL) % RING_CHUNK, "f22 folded stream");
+#else
+static_assert(F_PAIRS == L::F16_TOTAL && P_ALPHA == L16::F_FA + 128 && P_DIR == L16::F_DIR && P_RGB == L16::F_RGB && CHUNKS == 74, "f22 stream layout");
+#endif
 
 // two float32 values -> packed fp16 pair of their leading 11 bits, packed fp16 pair of the (scaled) remainders.
 // v - hi is exact in float32 (hi is v rounded to 11 bits), so hi + lo / 2^11 == v up to the rounding of lo: 2^-22 |v|.
@@ -81,13 +95,37 @@ __global__ void __launch_bounds__(256) pack22_kernel(const float* __restrict__ p
     const int fp = t >> 6, lane = t & 63;
     u32x4 hi = {0u, 0u, 0u, 0u}, lo = {0u, 0u, 0u, 0u};
     if (fp < F_PAIRS) {
+#if NERF_F22_FOLD
+      // the 64 pairs of W' = W_D[:, :256] W_F: this lane's eight elements (one row n, columns kperm16(ks, g, 0..7) = two runs of four) as
+      // float64 sums over the 256 features in index order, rounded ONCE to float32 -- the products of two float32 numbers are exact in
+      // float64 -- and then split like every other weight.  A non-finite W_F / W_D entry makes its column / row of W' NaN (IEEE).
+      float fold[8] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
+      if (fp >= P_DIR && fp < P_RGB && (fp - P_DIR) % 9 < 8) {
+        const float* __restrict__ wd = p + L::P_WD + (16 * ((fp - P_DIR) / 9) + (lane & 15)) * 283;
+        const float* __restrict__ wfk = p + L::P_WF + kperm16((fp - P_DIR) % 9, lane >> 4, 0);
+        double acc[8] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+#pragma unroll 4
+        for (int f = 0; f < 256; ++f) {
+          const double a = (double)wd[f];
+#pragma unroll
+          for (int e = 0; e < 8; ++e) acc[e] = __builtin_fma(a, (double)wfk[f * 256 + 16 * (e >> 2) + (e & 3)], acc[e]);
+        }
+#pragma unroll
+        for (int e = 0; e < 8; ++e) fold[e] = (float)acc[e];
+      }
+#endif
 #pragma unroll
       for (int j = 0; j < 8; j += 2) {
         float w[2];
         _Float16 wh[2], wl[2];
 #pragma unroll
         for (int e = 0; e < 2; ++e) {
+#if NERF_F22_FOLD
+          const Src src = stream_src(fp, lane & 15, lane >> 4, j + e);
+          w[e] = src.p >= 0 ? p[src.p] : src.p == SRC_FOLD ? fold[j + e] : 0.0f;
+#else
           w[e] = fwd_src16(p, fp, lane & 15, lane >> 4, j + e);
+#endif
           // weights below the fp16 normal range go to the lo part whole (hi = 0): nothing rests on fp16 denormals
           wh[e] = __builtin_fabsf(w[e]) < F16_MIN_NORMAL ? (_Float16)0.0f : (_Float16)w[e];
           wl[e] = (_Float16)((w[e] - (float)wh[e]) * LO_SCALE);
@@ -103,9 +141,20 @@ __global__ void __launch_bounds__(256) pack22_kernel(const float* __restrict__ p
     const int s = t - (F_PADDED / 2) * 64;                  // bias slots: numbering of the bf16 image (mlp.hip pack_part)
     float v = 0.0f;
     if (s < 2048) v = p[L::pb(s >> 8) + (s & 255)];
+#if NERF_F22_FOLD
+    else if (s < L::BI_ALPHA) v = 0.0f;                       // (the feature layer's slots: no layer reads them)
+    else if (s < L::BI_DIR) v = (s == L::BI_ALPHA) ? p[L::P_BA] : 0.0f;
+    else if (s < L::BI_RGB) {                                 // b' = W_D[:, :256] b_F + b_D: float64 sum in index order, b_D last, rounded once
+      const float* __restrict__ wd = p + L::P_WD + (s - L::BI_DIR) * 283;
+      double acc = 0.0;
+      for (int f = 0; f < 256; ++f) acc = __builtin_fma((double)wd[f], (double)p[L::P_BF + f], acc);
+      v = (float)(acc + (double)p[L::P_BD + (s - L::BI_DIR)]);
+    }
+#else
     else if (s < L::BI_ALPHA) v = p[L::P_BF + (s - L::BI_FEAT)];
     else if (s < L::BI_DIR) v = (s == L::BI_ALPHA) ? p[L::P_BA] : 0.0f;
     else if (s < L::BI_RGB) v = p[L::P_BD + (s - L::BI_DIR)];
+#endif
     else v = (s - L::BI_RGB) < 3 ? p[L::P_BR + (s - L::BI_RGB)] : 0.0f;
     bias[s] = v;
   }
@@ -207,14 +256,20 @@ __device__ __forceinline__ f32x4 mfma16(const u32x4& a, const u32x4& b, const f3
 // PARK_LDS != 0 (pos5 of the 48-sample form, the one layer whose inputs + outputs + accumulators + weight groups exceed the 512
 // registers by one fragment): the LAST input fragment (lo part of k-step KS - 1, sample tile NS - 1) lives in the LDS for the length of
 // the layer -- written once at its head, read back behind the weight fragments of every n-tile (16 ds_read_b128 of 2 400 per pass).
+// PARK_LDS 2: the same fragment of sample tile NS - 2 as well, as four dwords in slots that hold nothing live during this layer: the
+// positions of sample tiles 0 and 1 parked by tiles22 (park2_addr = its park address; slots 0, 1, 2, 6), which were read back just before
+// the layer (the skip input's encodings) and are written again at the head of the next pass -- no LDS beyond the 160 KiB the form fills.
 // Left to hipcc the same fragment goes to scratch, and a scratch reload is a compiler-counted VMEM load: s_waitcnt vmcnt(0), a drain
 // of the weight ring in the middle of a pass.  park_addr: LDS byte address of this lane's 16 bytes.
-template <int NS, int KS, int NT, bool RELU, class WS, bool PARK_LDS = false>
+template <int NS, int KS, int NT, bool RELU, class WS, int PARK_LDS = 0>
 __device__ __forceinline__ void layer22(WS& ws, int pbase, int bias_slot, const u32x4 (&ih)[NS][KS], const u32x4 (&il)[NS][KS],
-                                        u32x4 (&oh)[NS][NT / 2], u32x4 (&ol)[NS][NT / 2], int lane, unsigned park_addr = 0u) {
+                                        u32x4 (&oh)[NS][NT / 2], u32x4 (&ol)[NS][NT / 2], int lane, unsigned park_addr = 0u, unsigned park2_addr = 0u) {
   const int g = lane >> 4;
   f32x4 pm[NS], pc[NS];
   if (PARK_LDS) asm volatile("ds_write_b128 %0, %1" :: "v"(park_addr), "v"(il[NS - 1][KS - 1]) : "memory");
+  if (PARK_LDS >= 2)
+    asm volatile("ds_write_b32 %0, %1\n\tds_write_b32 %0, %2 offset:1024\n\tds_write_b32 %0, %3 offset:2048\n\tds_write_b32 %0, %4 offset:6144"
+                 :: "v"(park2_addr), "v"(il[NS - 2][KS - 1][0]), "v"(il[NS - 2][KS - 1][1]), "v"(il[NS - 2][KS - 1][2]), "v"(il[NS - 2][KS - 1][3]) : "memory");
 #if NERF_F22_IGLP >= 0
   // LLVM's MFMA-interleaving scheduling strategy for this region (the layer is one basic block): the static gap model goes from 0.770
   // to 0.792 busy (tools/isa_gap_stats.py), measured 15.6-16.1 against 16.1-16.3 ms per fine pass in alternating runs (round 5).
@@ -279,6 +334,11 @@ __device__ __forceinline__ void layer22(WS& ws, int pbase, int bias_slot, const 
           if (PARK_LDS && t == NS - 1 && ks == KS - 1) {
             u32x4 b;
             asm volatile("ds_read_b128 %0, %1\n\ts_waitcnt lgkmcnt(0)" : "=v"(b) : "v"(park_addr) : "memory");
+            c[t] = mfma16(ah, b, c[t]);
+          } else if (PARK_LDS >= 2 && t == NS - 2 && ks == KS - 1) {
+            u32x4 b;
+            asm volatile("ds_read_b32 %0, %4\n\tds_read_b32 %1, %4 offset:1024\n\tds_read_b32 %2, %4 offset:2048\n\tds_read_b32 %3, %4 offset:6144\n\ts_waitcnt lgkmcnt(0)"
+                         : "=&v"(b[0]), "=&v"(b[1]), "=&v"(b[2]), "=&v"(b[3]) : "v"(park2_addr) : "memory");
             c[t] = mfma16(ah, b, c[t]);
           } else {
             c[t] = mfma16(ah, il[t][ks], c[t]);
@@ -428,21 +488,27 @@ __device__ __forceinline__ void tiles22(const FwdArgs& a, WS& ws, int64_t wtile0
 #pragma unroll
       for (int k = 0; k < 8; ++k) { cth[s][2 + k] = hah[s][k]; ctl[s][2 + k] = hal[s][k]; }
     }
-    layer22<NS, 10, 16, true, WS, (NS > 2)>(ws, L16::F_L5, 1280, cth, ctl, hbh, hbl, lane,
-                                            ws.lds0 + PARK_OFF + 6 * NS * 64 * NW22 * 4 + 16u * (unsigned)(ws.wv * 64 + lane));
+    layer22<NS, 10, 16, true, WS, (NS > 2 ? NERF_F22_PARK : 0)>(ws, L16::F_L5, 1280, cth, ctl, hbh, hbl, lane,
+                                            ws.lds0 + PARK_OFF + 6 * NS * 64 * NW22 * 4 + 16u * (unsigned)(ws.wv * 64 + lane), park);
   }
   layer22<NS, 8, 16, true>(ws, L16::F_L6, 1536, hbh, hbl, hah, hal, lane);
   layer22<NS, 8, 16, true>(ws, L16::F_L7, 1792, hah, hal, hbh, hbl, lane);
-  layer22<NS, 8, 16, false>(ws, L16::F_FA, L::BI_FEAT, hbh, hbl, hah, hal, lane);       // feature: no activation (:231)
+#if NERF_F22_FOLD
+  // the feature layer (no activation, :231) is folded into dir0's weights and bias when the image is packed (mlp22.h): dir0' reads h7
+  u32x4 (&fth)[NS][8] = hbh, (&ftl)[NS][8] = hbl;
+#else
+  layer22<NS, 8, 16, false>(ws, P_FEAT, L::BI_FEAT, hbh, hbl, hah, hal, lane);          // feature: no activation (:231)
+  u32x4 (&fth)[NS][8] = hah, (&ftl)[NS][8] = hal;
+#endif
   f32x4 alpha[NS];
-  head22<NS, 8>(ws, L16::F_FA + 128, L::BI_ALPHA, hbh, hbl, alpha, lane);               // alpha = Linear(256, 1)(h) (:230)
+  head22<NS, 8>(ws, P_ALPHA, L::BI_ALPHA, hbh, hbl, alpha, lane);                       // alpha = Linear(256, 1)(h) (:230)
   u32x4 hdh[NS][4], hdl[NS][4];
-  {                                                           // relu(Linear(283, 128)([feature, input_dir]))  (:232-236)
+  {                                                           // relu(Linear(283, 128)([feature, input_dir]))  (:232-236); folded: [h7, input_dir]
     u32x4 cth[NS][9], ctl[NS][9];
 #pragma unroll
     for (int s = 0; s < NS; ++s) {
 #pragma unroll
-      for (int k = 0; k < 8; ++k) { cth[s][k] = hah[s][k]; ctl[s][k] = hal[s][k]; }
+      for (int k = 0; k < 8; ++k) { cth[s][k] = fth[s][k]; ctl[s][k] = ftl[s][k]; }
       if (RECOMP) {
         float dd[3];
         park_get_s<3>(s, park, dd);
@@ -450,10 +516,10 @@ __device__ __forceinline__ void tiles22(const FwdArgs& a, WS& ws, int64_t wtile0
       }
       cth[s][8] = dph[s][0]; ctl[s][8] = dpl[s][0];
     }
-    layer22<NS, 9, 8, true>(ws, L16::F_DIR, L::BI_DIR, cth, ctl, hdh, hdl, lane);
+    layer22<NS, 9, 8, true>(ws, P_DIR, L::BI_DIR, cth, ctl, hdh, hdl, lane);
   }
   f32x4 rgb[NS];
-  head22<NS, 4>(ws, L16::F_RGB, L::BI_RGB, hdh, hdl, rgb, lane);
+  head22<NS, 4>(ws, P_RGB, L::BI_RGB, hdh, hdl, rgb, lane);
 #pragma unroll
   for (int s = 0; s < NS; ++s) {
     const int64_t m = wtile0 * (16 * NS) + 16 * s + c;

@@ -27,6 +27,25 @@ __host__ __device__ constexpr int kperm_ks(int kk) { return kk >> 4; }
 __host__ __device__ constexpr int kperm_h(int kk) { return (kk >> 2) & 1; }
 __host__ __device__ constexpr int kperm_j(int kk) { return 4 * ((kk >> 3) & 1) + (kk & 3); }
 
+// the 16x16x32 forward streams (bf16 render kernel of mlp.hip, split-fp16 forward of mlp22.hip): element j of lane group g in k-step ks
+__host__ __device__ constexpr int kperm16(int ks, int g, int j) { return 32 * ks + 16 * (j >> 2) + 4 * g + (j & 3); }
+// Which embedding channel sits in element j of lane group g in the encoding k-steps.  The order is ours to choose
+// (the packed weights follow it), so it is chosen to make the per-element (sin | cos, x | y | z) pattern the same in
+// all four lane groups -- only the frequency differs, three per-lane registers -- instead of a table lookup and four
+// selects per element.  Position (63 channels, 2 k-steps = slots 8 ks + j): slots 0-11 = bands 2g, 2g+1 as
+// (sin xyz, cos xyz); slots 12-14 = band 8 + (g>>1), sin for even g / cos for odd g, xyz; slot 15 = identity
+// channel g (zero pad for g = 3).  Direction (27 channels, 1 k-step): j 0-5 = band g, j 6 = identity g, j 7 = pad.
+__host__ __device__ constexpr int pos_chan16(int ks, int g, int j) {
+  const int sl = 8 * ks + j;
+  if (sl < 12) return 3 + 6 * (2 * g + sl / 6) + (sl % 6);
+  if (sl < 15) return 3 + 6 * (8 + (g >> 1)) + 3 * (g & 1) + (sl - 12);
+  return g < 3 ? g : -1;
+}
+__host__ __device__ constexpr int dir_chan16(int g, int j) {
+  if (j < 6) return 3 + 6 * g + j;
+  return (j == 6 && g < 3) ? g : -1;
+}
+
 // ------------------------------------------------------------------------------------------
 // weight packing sources: offset of the master parameter that sits in element j of lane (r, h) of fragment f; -1 = zero padding
 // ------------------------------------------------------------------------------------------

@@ -37,23 +37,7 @@ namespace L16 {
 constexpr int F_L0 = 0, F_L1 = 32, F_L5 = 544, F_L6 = 704, F_L7 = 832, F_FA = 960, F_DIR = 1096, F_RGB = 1168;
 constexpr int CHUNKS = L::F16_PADDED / RING_CHUNK;     // 37
 }
-__host__ __device__ constexpr int kperm16(int ks, int g, int j) { return 32 * ks + 16 * (j >> 2) + 4 * g + (j & 3); }
-// Which embedding channel sits in element j of lane group g in the encoding k-steps.  The order is ours to choose
-// (the packed weights follow it), so it is chosen to make the per-element (sin | cos, x | y | z) pattern the same in
-// all four lane groups -- only the frequency differs, three per-lane registers -- instead of a table lookup and four
-// selects per element.  Position (63 channels, 2 k-steps = slots 8 ks + j): slots 0-11 = bands 2g, 2g+1 as
-// (sin xyz, cos xyz); slots 12-14 = band 8 + (g>>1), sin for even g / cos for odd g, xyz; slot 15 = identity
-// channel g (zero pad for g = 3).  Direction (27 channels, 1 k-step): j 0-5 = band g, j 6 = identity g, j 7 = pad.
-__host__ __device__ constexpr int pos_chan16(int ks, int g, int j) {
-  const int sl = 8 * ks + j;
-  if (sl < 12) return 3 + 6 * (2 * g + sl / 6) + (sl % 6);
-  if (sl < 15) return 3 + 6 * (8 + (g >> 1)) + 3 * (g & 1) + (sl - 12);
-  return g < 3 ? g : -1;
-}
-__host__ __device__ constexpr int dir_chan16(int g, int j) {
-  if (j < 6) return 3 + 6 * g + j;
-  return (j == 6 && g < 3) ? g : -1;
-}
+// kperm16 / pos_chan16 / dir_chan16 (element <-> feature / embedding channel of the 16x16x32 k-steps): mlp_index.h
 
 __device__ inline float fwd_src16(const float* __restrict__ p, int f, int i, int g, int j) {
   if (f < L16::F_L1) {

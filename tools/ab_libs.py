@@ -1,16 +1,18 @@
 """A/B of two BUILDS of the library (tools/ab_one.sh) on one box, in alternating fresh child processes ("default" = the shipped library).
     python tools/ab_libs.py tools/diag/libnerf_A.so tools/diag/libnerf_B.so [--rounds 3]
         the render chunk of the bench (coarse 32768 x 64 + fine 32768 x 192 samples through the precision-22 inference forward):
-        times, outputs compared bit for bit
+        times, outputs compared bit for bit -- per channel group: the alpha channel (bit equality) and the three colour channels
+        (max-abs difference) against the first library.  --fold-differs: the builds differ in NERF_F22_FOLD (csrc/mlp22.h), which
+        moves the colours by rounding and nothing else: then only an alpha difference is a bit-identity failure (exit 1)
     python tools/ab_libs.py --models tools/diag/libnerf_A.so default
         every MLP model (view / image / 2x64 in each of their precisions) through pack, training forward and backward at M = 65 and
         8193, plus the fused view-model and hash-grid queries at B = 64, n = 3 and 64, on seeded inputs: sha256 of the output, the
         packed buffer, the activation store, the dZ store (without the split-K partial slots), the gradients and d_x.  Exit 1 unless
         every digest is the same in every library.
 Every child runs under a time limit, and after a child that failed or ran out of time no further child is started."""
-import argparse, json, os, subprocess, sys
+import argparse, json, os, subprocess, sys, tempfile
 CHILD = r'''
-import sys, json, hashlib, torch
+import sys, json, hashlib, numpy, torch
 sys.path.insert(0, ".")
 from nerf_meets_mlx_amd.models.NeRF import NeRF
 from oracle import nerf_oracle as O
@@ -31,6 +33,7 @@ for n in (64, 192):
     e1.record(); torch.cuda.synchronize()
     res[f"ms_{n}"] = e0.elapsed_time(e1) / 12
     res[f"sha_{n}"] = hashlib.sha256(out.cpu().numpy().tobytes()).hexdigest()[:16]
+    if len(sys.argv) > 2: numpy.save(f"{sys.argv[2]}_{n}.npy", out.cpu().numpy())
 print(json.dumps(res))
 '''
 CHILD_MODELS = r'''
@@ -104,15 +107,17 @@ print(json.dumps(res))
 ap = argparse.ArgumentParser(); ap.add_argument("libs", nargs="+"); ap.add_argument("--rounds", type=int, default=None); ap.add_argument("--precision", type=int, default=22)
 ap.add_argument("--models", action="store_true", help="digests of every MLP model instead of the render-chunk timing")
 ap.add_argument("--timeout", type=float, default=300.0, help="seconds per child process")
+ap.add_argument("--fold-differs", action="store_true", help="the builds differ in NERF_F22_FOLD: colour differences are reported, not failed")
 a = ap.parse_args()
 rounds = a.rounds if a.rounds is not None else (1 if a.models else 3)
 acc = {l: [] for l in a.libs}
+tmp = None if a.models else tempfile.mkdtemp(prefix="ab_libs_")
 for r in range(rounds):
-    for l in a.libs:
+    for i, l in enumerate(a.libs):
         env = dict(os.environ)
         if l != "default": env["NERF_HIP_LIB"] = os.path.abspath(l)
         else: env.pop("NERF_HIP_LIB", None)
-        cmd = [sys.executable, "-c", CHILD_MODELS] if a.models else [sys.executable, "-c", CHILD, str(a.precision)]
+        cmd = [sys.executable, "-c", CHILD_MODELS] if a.models else [sys.executable, "-c", CHILD, str(a.precision)] + ([os.path.join(tmp, f"lib{i}")] if r == 0 else [])
         try:
             out = subprocess.run(cmd, capture_output=True, text=True, env=env, timeout=a.timeout)
         except subprocess.TimeoutExpired:
@@ -132,3 +137,20 @@ if a.models:
 for l in a.libs:
     rs = acc[l]
     print(f"{l}: coarse " + " ".join(f"{x['ms_64']:.3f}" for x in rs) + " ms | fine " + " ".join(f"{x['ms_192']:.3f}" for x in rs) + f" ms | sha {rs[0]['sha_64']} {rs[0]['sha_192']}")
+# outputs of the first round, per channel group, against the first library
+import numpy as np
+bad = 0
+for i, l in enumerate(a.libs[1:], 1):
+    for n in (64, 192):
+        x, y = np.load(os.path.join(tmp, f"lib0_{n}.npy")), np.load(os.path.join(tmp, f"lib{i}_{n}.npy"))
+        alpha_same = bool(np.array_equal(x[..., 3].view(np.int32), y[..., 3].view(np.int32)))
+        colour_same = bool(np.array_equal(x[..., :3].view(np.int32), y[..., :3].view(np.int32)))
+        d = float(np.nanmax(np.abs(x[..., :3].astype(np.float64) - y[..., :3])))
+        fail = (not alpha_same) or (not colour_same and not a.fold_differs)
+        bad += fail
+        print(f"{l} against {a.libs[0]}, n = {n}: alpha " + ("bit-identical" if alpha_same else "DIFFERS") + "; colours "
+              + ("bit-identical" if colour_same else f"differ, max abs {d:.3e} (output scale {float(np.nanmax(np.abs(x))):.3e})")
+              + ("   BIT-IDENTITY FAILURE" if fail else ""))
+for f in os.listdir(tmp): os.remove(os.path.join(tmp, f))
+os.rmdir(tmp)
+sys.exit(1 if bad else 0)
