@@ -75,43 +75,7 @@ __device__ __forceinline__ void pack_part(int tid, const float* __restrict__ p, 
 // ------------------------------------------------------------------------------------------
 
 
-// models/embedding.py:30-71 channel order [x, sin(f0 x), cos(f0 x), ...]; cos(a) = sin(a + 1/4 rev)
-template <int C0, int LIMIT, int NB>
-__device__ __forceinline__ float pe_value(const float (&x)[3], const float (&fr)[NB], int h) {
-  constexpr Chan a = chan_of(C0, LIMIT), b = chan_of(C0 + 4, LIMIT);
-  const float xa = x[a.dim], xb = x[b.dim];
-  const float xv = h ? xb : xa;
-  const float fv = h ? fr[b.band] : fr[a.band];
-  const float ph = h ? (b.kind == 2 ? 0.25f : 0.0f) : (a.kind == 2 ? 0.25f : 0.0f);
-  const float arg = xv * fv;                                    // x * freq in fp32, as the reference
-  const float t = __builtin_amdgcn_fractf(arg * 0.15915494309189535f + ph);
-  const float s = __builtin_amdgcn_sinf(t);                     // sin(2 pi t)
-  const float va = a.kind == 0 ? xa : (a.kind == 3 ? 0.0f : s);
-  const float vb = b.kind == 0 ? xb : (b.kind == 3 ? 0.0f : s);
-  return h ? vb : va;
-}
-
-template <int KS, int LIMIT, int NB, int... J>
-__device__ __forceinline__ bf16x8 pe_frag_impl(const float (&x)[3], const float (&fr)[NB], int h) {
-  bf16x8 v;
-  ((v[J] = (__bf16)pe_value<16 * KS + 8 * (J >> 2) + (J & 3), LIMIT, NB>(x, fr, h)), ...);
-  return v;
-}
-template <int KS, int LIMIT, int NB>
-__device__ __forceinline__ bf16x8 pe_frag(const float (&x)[3], const float (&fr)[NB], int h) {
-  return pe_frag_impl<KS, LIMIT, NB, 0, 1, 2, 3, 4, 5, 6, 7>(x, fr, h);
-}
-
-// fragment of an already-embedded row x[m][base + c], c < limit else 0   (NeRF.forward(x) entry)
-__device__ __forceinline__ bf16x8 row_frag(const float* __restrict__ row, int ks, int h, int limit) {
-  bf16x8 v;
-#pragma unroll
-  for (int j = 0; j < 8; ++j) {
-    const int c = kperm(ks, h, j);
-    v[j] = (__bf16)(c < limit ? row[c] : 0.0f);
-  }
-  return v;
-}
+// channel order, evaluators, encoders, row readers, sample loader: mlp_input.h (here: SinRevFract; CvtBf16 in the 32x32x16 chains, PackBf16 in the 16x16x32 render kernel)
 
 // weight sources (GlobalW: L1, RingW: LDS ring fed by LDS-DMA), FwdArgs, PeFreq: mlp_ring.h
 // ------------------------------------------------------------------------------------------
@@ -173,29 +137,24 @@ __device__ __forceinline__ void fwd_tiles(const FwdArgs& a, WS& ws, int64_t tile
 #pragma unroll
   for (int t = 0; t < ST; ++t) {
     int64_t tile = tile0 + t; if (tile >= ntiles) tile = ntiles - 1;
-    int64_t m = tile * 32 + r; if (m >= a.M) m = a.M - 1;
+    const int64_t m = clamp_sample(tile * 32 + r, a.M);
     if (MODE == 0) {
       const float* row = a.x + m * 90;
 #pragma unroll
-      for (int ks = 0; ks < 4; ++ks) pe[t][ks] = row_frag(row, ks, h, 63);
+      for (int ks = 0; ks < 4; ++ks) row_pairs<CvtBf16>(row, ks, h, 63, pe[t][ks]);
 #pragma unroll
-      for (int ks = 0; ks < 2; ++ks) dpe[t][ks] = row_frag(row + 63, ks, h, 27);
+      for (int ks = 0; ks < 2; ++ks) row_pairs<CvtBf16>(row + 63, ks, h, 27, dpe[t][ks]);
     } else {
-      const int64_t ray = (int64_t)((unsigned)m / (unsigned)a.n);     // M < 2^31 (checked on the host): 32-bit divide
-      const float* rr = a.rays + ray * NERF_RAY_STRIDE;
-      const float zv = a.z[m];
-      float p[3], d[3];
-#pragma unroll
-      for (int c = 0; c < 3; ++c) { p[c] = rr[c] + zv * rr[3 + c]; d[c] = rr[8 + c]; }   // render.py:142
+      const Sample sm = load_sample(a.rays, a.z, m, a.n);
 #if NERF_ABLATE == 3          // timing-only build 3: no positional-encoding arithmetic
-      for (int q = 0; q < 4; ++q) for (int j = 0; j < 8; ++j) pe[t][q][j] = (__bf16)p[j % 3];
-      for (int q = 0; q < 2; ++q) for (int j = 0; j < 8; ++j) dpe[t][q][j] = (__bf16)d[j % 3];
+      for (int q = 0; q < 4; ++q) for (int j = 0; j < 8; ++j) pe[t][q][j] = (__bf16)sm.p[j % 3];
+      for (int q = 0; q < 2; ++q) for (int j = 0; j < 8; ++j) dpe[t][q][j] = (__bf16)sm.d[j % 3];
       if (false)
 #endif
       {
-      pe[t][0] = pe_frag<0, 63, 10>(p, a.fr.pos, h); pe[t][1] = pe_frag<1, 63, 10>(p, a.fr.pos, h);
-      pe[t][2] = pe_frag<2, 63, 10>(p, a.fr.pos, h); pe[t][3] = pe_frag<3, 63, 10>(p, a.fr.pos, h);
-      dpe[t][0] = pe_frag<0, 27, 4>(d, a.fr.dir, h); dpe[t][1] = pe_frag<1, 27, 4>(d, a.fr.dir, h);
+      encode_pairs<SinRevFract, CvtBf16, 0, 63, 10>(sm.p, a.fr.pos, h, pe[t][0]); encode_pairs<SinRevFract, CvtBf16, 1, 63, 10>(sm.p, a.fr.pos, h, pe[t][1]);
+      encode_pairs<SinRevFract, CvtBf16, 2, 63, 10>(sm.p, a.fr.pos, h, pe[t][2]); encode_pairs<SinRevFract, CvtBf16, 3, 63, 10>(sm.p, a.fr.pos, h, pe[t][3]);
+      encode_pairs<SinRevFract, CvtBf16, 0, 27, 4>(sm.d, a.fr.dir, h, dpe[t][0]); encode_pairs<SinRevFract, CvtBf16, 1, 27, 4>(sm.d, a.fr.dir, h, dpe[t][1]);
       }
     }
   }
@@ -421,61 +380,13 @@ __global__ void __launch_bounds__(256) pack_kernel(const float* __restrict__ p, 
 }
 
 constexpr int RING16_LDS_BYTES = RING_LDS_BYTES;
-// per-lane frequencies of the channel order above (pass-invariant; recomputed per pass, cheaper than keeping them)
-struct Pe16 {
-  float fa, fb, fc, phc;      // position: bands 2g, 2g+1, 8 + (g>>1); phase of the third (0 sin, 1/4 rev cos)
-  float fd;                   // direction: band g
-  int g;
-};
-__device__ __forceinline__ Pe16 pe16_setup(const PeFreq& fr, int g) {
-  Pe16 q;
-  q.fa = g == 0 ? fr.pos[0] : g == 1 ? fr.pos[2] : g == 2 ? fr.pos[4] : fr.pos[6];
-  q.fb = g == 0 ? fr.pos[1] : g == 1 ? fr.pos[3] : g == 2 ? fr.pos[5] : fr.pos[7];
-  q.fc = g < 2 ? fr.pos[8] : fr.pos[9];
-  q.phc = (g & 1) ? 0.25f : 0.0f;
-  q.fd = g == 0 ? fr.dir[0] : g == 1 ? fr.dir[1] : g == 2 ? fr.dir[2] : fr.dir[3];
-  q.g = g;
-  return q;
-}
-// sin(x f + phase [rev] 2 pi): x f is the reference's fp32 product; v_sin_f32 takes revolutions
-__device__ __forceinline__ float sin_rev(float x, float f, float ph) {
-  return __builtin_amdgcn_sinf(__builtin_amdgcn_fractf((x * f) * 0.15915494309189535f + ph));
-}
-__device__ __forceinline__ void pe16_pos(const Pe16& q, const float (&x)[3], bf16x8& k0, bf16x8& k1) {
-  float v[16];
-#pragma unroll
-  for (int sl = 0; sl < 12; ++sl) v[sl] = sin_rev(x[sl % 3], sl < 6 ? q.fa : q.fb, (sl % 6) >= 3 ? 0.25f : 0.0f);
-#pragma unroll
-  for (int d = 0; d < 3; ++d) v[12 + d] = sin_rev(x[d], q.fc, q.phc);
-  v[15] = q.g == 0 ? x[0] : q.g == 1 ? x[1] : q.g == 2 ? x[2] : 0.0f;
-#pragma unroll
-  for (int j = 0; j < 8; j += 2) {
-    const bf16x2 a = pack2(v[j], v[j + 1]), b = pack2(v[8 + j], v[8 + j + 1]);
-    k0[j] = a[0]; k0[j + 1] = a[1]; k1[j] = b[0]; k1[j + 1] = b[1];
-  }
-}
-__device__ __forceinline__ bf16x8 pe16_dir(const Pe16& q, const float (&x)[3]) {
-  float v[8];
-#pragma unroll
-  for (int j = 0; j < 6; ++j) v[j] = sin_rev(x[j % 3], q.fd, j >= 3 ? 0.25f : 0.0f);
-  v[6] = q.g == 0 ? x[0] : q.g == 1 ? x[1] : q.g == 2 ? x[2] : 0.0f;
-  v[7] = 0.0f;
-  bf16x8 k;
-#pragma unroll
-  for (int j = 0; j < 8; j += 2) { const bf16x2 a = pack2(v[j], v[j + 1]); k[j] = a[0]; k[j + 1] = a[1]; }
-  return k;
-}
-
 #ifndef NERF_BF16_IGLP
 #define NERF_BF16_IGLP 0      // __builtin_amdgcn_iglp_opt strategy of the bf16 render layers (as in mlp22.hip: 4.79 -> 4.71 ms per fine pass); -1: none
 #endif
-struct NoHook { __device__ __forceinline__ void operator()(int) const {} };
 // out[s][nt>>1] (elements 4 (nt&1) + i) = act( W[16-row tile nt] . in[s] + bias ), s = 0..NS-1 sample tiles of 16.
-// hook(nt * KS + ks) runs behind the MFMAs of k-step (nt, ks): a place to put independent VALU work (the NEXT pass's
-// positional encoding) in the shadow of the matrix pipe; the slot index is a constant at every call site after unrolling.
-template <int NS, int KS, int NT, bool RELU, class WS, class HOOK = NoHook>
+template <int NS, int KS, int NT, bool RELU, class WS>
 __device__ __forceinline__ void layer_fwd16(WS& ws, int fbase, int bias_slot, const bf16x8 (&in)[NS][KS],
-                                            bf16x8 (&out)[NS][NT / 2], int lane, const HOOK& hook = HOOK()) {
+                                            bf16x8 (&out)[NS][NT / 2], int lane) {
   const int g = lane >> 4;
   f32x4 prev[NS];
 #if NERF_BF16_IGLP >= 0
@@ -509,7 +420,6 @@ __device__ __forceinline__ void layer_fwd16(WS& ws, int fbase, int bias_slot, co
       if (nt > 0 && ks == KS / 2) finish(nt - 1, prev);      // previous tile's epilogue, half a tile of MFMAs later
 #pragma unroll
       for (int s = 0; s < NS; ++s) acc[s] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, in[s][ks], acc[s], 0, 0, 0);
-      hook(nt * KS + ks);
     }
 #pragma unroll
     for (int s = 0; s < NS; ++s) prev[s] = acc[s];
@@ -517,112 +427,31 @@ __device__ __forceinline__ void layer_fwd16(WS& ws, int fbase, int bias_slot, co
   finish(NT - 1, prev);
 }
 
-// 1 = compute the NEXT pass's encodings pair by pair behind the MFMAs of pos6 (ray loads) / pos7 (arithmetic) instead of
-// at the top of the pass, where the arithmetic of all 8 lock-stepped waves leaves the matrix pipe idle (4.3 % of the
-// pass's cycles by ablation).  Measured round 2 (profiles/r02_pe_hoist_ab.log, parity tests green with it): 8 waves x 32
-// samples 4.66 ms with and without, 4 waves x 64 samples 4.92 vs 4.82 ms (worse) -- the kernel is power-limited, the
-// cycles saved come back as a lower clock, and the hoist costs 28 VGPRs.  Kept as a negative result, off.
-#ifndef NERF_PE_HOIST
-#define NERF_PE_HOIST 0
-#endif
-#if NERF_ABLATE == 3          // the encoding-free timing build computes its placeholder at the top of the pass
-#undef NERF_PE_HOIST
-#define NERF_PE_HOIST 0
-#endif
-// The encodings of one wave's NS x 16 samples, and the raw ray data they are made from
-template <int NS> struct PeRegs { bf16x8 pe[NS][2], dpe[NS][1]; };
-template <int NS> struct PeRaw { float o[NS][3], d[NS][3], v[NS][3], z[NS]; };
-template <int NS>
-__device__ __forceinline__ void pe16_load(const FwdArgs& a, int64_t wtile, int c, PeRaw<NS>& r) {
-#pragma unroll
-  for (int s = 0; s < NS; ++s) {
-    int64_t m = wtile * (16 * NS) + 16 * s + c; if (m >= a.M) m = a.M - 1;
-    const int64_t ray = (int64_t)((unsigned)m / (unsigned)a.n);
-    const float* rr = a.rays + ray * NERF_RAY_STRIDE;
-    r.z[s] = a.z[m];
-#pragma unroll
-    for (int k = 0; k < 3; ++k) { r.o[s][k] = rr[k]; r.d[s][k] = rr[3 + k]; r.v[s][k] = rr[8 + k]; }
-  }
-}
-// pair j of one sample: j 0..7 = position slots (2 j, 2 j + 1) -> pe[j >> 2] elements 2 (j & 3), +1; j 8..11 = direction
-template <int NS>
-__device__ __forceinline__ void pe16_pair(const Pe16& q, const float (&p)[3], const float (&d)[3], int j, PeRegs<NS>& out, int s) {
-  auto slot = [&](int sl) -> float {              // position slot sl of this lane group (see pos_chan16)
-    if (sl < 12) return sin_rev(p[sl % 3], sl < 6 ? q.fa : q.fb, (sl % 6) >= 3 ? 0.25f : 0.0f);
-    if (sl < 15) return sin_rev(p[sl - 12], q.fc, q.phc);
-    return q.g == 0 ? p[0] : q.g == 1 ? p[1] : q.g == 2 ? p[2] : 0.0f;
-  };
-  auto dslot = [&](int sl) -> float {             // direction slot (see dir_chan16)
-    if (sl < 6) return sin_rev(d[sl % 3], q.fd, sl >= 3 ? 0.25f : 0.0f);
-    if (sl == 6) return q.g == 0 ? d[0] : q.g == 1 ? d[1] : q.g == 2 ? d[2] : 0.0f;
-    return 0.0f;
-  };
-  if (j < 8) {
-    const bf16x2 pr = pack2(slot(2 * j), slot(2 * j + 1));
-    out.pe[s][j >> 2][2 * (j & 3)] = pr[0]; out.pe[s][j >> 2][2 * (j & 3) + 1] = pr[1];
-  } else {
-    const bf16x2 pr = pack2(dslot(2 * (j - 8)), dslot(2 * (j - 8) + 1));
-    out.dpe[s][0][2 * (j - 8)] = pr[0]; out.dpe[s][0][2 * (j - 8) + 1] = pr[1];
-  }
-}
-template <int NS>
-__device__ __forceinline__ void pe16_all(const FwdArgs& a, const Pe16& pq, int64_t wtile, int c, PeRegs<NS>& out) {
-  PeRaw<NS> r;
-  pe16_load<NS>(a, wtile, c, r);
-#pragma unroll
-  for (int s = 0; s < NS; ++s) {
-    float p[3];
-#pragma unroll
-    for (int k = 0; k < 3; ++k) p[k] = r.o[s][k] + r.z[s] * r.d[s][k];          // render.py:142
-#if NERF_ABLATE == 3          // timing-only build 3: no positional-encoding arithmetic
-    bf16x8 cst;
-    for (int j = 0; j < 8; ++j) cst[j] = (__bf16)(p[0] + r.v[s][0]);
-    out.pe[s][0] = cst; out.pe[s][1] = cst; out.dpe[s][0] = cst;
-#else
-#pragma unroll
-    for (int j = 0; j < 12; ++j) pe16_pair<NS>(pq, p, r.v[s], j, out, s);
-#endif
-  }
-}
-
-// one wave: NS x 16 samples starting at sample wtile * 16 NS.  `cur` holds this tile's encodings on entry and the NEXT
-// tile's (wtile_next) on return: they are produced pair by pair behind the MFMAs of pos6 (ray loads) and pos7
-// (arithmetic) -- the position fragments are dead after pos5, so they are overwritten in place; only the direction
-// fragment needs a second copy until the view layer has read it.  Done at the top of a pass, the encoding arithmetic of
-// all 8 waves (in lockstep behind the ring barrier) left the matrix pipe idle for 4.3 % of the pass.
+// one wave: NS x 16 samples starting at sample wtile0 * 16 NS, encoded at the head of the pass (the pass queue is asked before the
+// input loads).  Computing the NEXT pass's encodings behind the MFMAs of pos6 / pos7 instead was measured and gained nothing
+// (DESIGN_HISTORY.md, profiles/r02_pe_hoist_ab.log).
 template <int NS, class WS>
-__device__ __forceinline__ void fwd_tiles16(const FwdArgs& a, WS& ws, int64_t wtile0, int64_t wtile_next, int64_t nwtiles,
-                                            int lane, PeRegs<NS>& cur) {
+__device__ __forceinline__ void fwd_tiles16(const FwdArgs& a, WS& ws, int64_t wtile0, int64_t nwtiles, int lane, PassQueue& pq) {
   const int c = lane & 15, g = lane >> 4;
-  const Pe16 pq = pe16_setup(a.fr, g);
-  bf16x8 (&pe)[NS][2] = cur.pe;
-  bf16x8 (&dpe)[NS][1] = cur.dpe;
-  PeRaw<NS> raw;
-  PeRegs<NS> nxt;                 // only nxt.dpe is used (position fragments are written into cur.pe in place)
-  float pn[NS][3];
-  const int64_t wt_n = wtile_next < nwtiles ? wtile_next : nwtiles - 1;
-  auto hook_load = [&](int slot) {
-    if (NERF_PE_HOIST && slot == 0) pe16_load<NS>(a, wt_n, c, raw);
-  };
-  auto hook_math = [&](int slot) {
-    if (!NERF_PE_HOIST) return;
-    if (slot == 0) {
+  bf16x8 pe[NS][2], dpe[NS][1];
+  pq.ask(ws.wv, lane);                                  // before this pass's input loads
+  {
+    const GroupFreq q = group_freqs(a.fr, g);
+    const int64_t wt = wtile0 < nwtiles ? wtile0 : nwtiles - 1;
 #pragma unroll
-      for (int s = 0; s < NS; ++s)
-#pragma unroll
-        for (int k = 0; k < 3; ++k) pn[s][k] = raw.o[s][k] + raw.z[s] * raw.d[s][k];
+    for (int s = 0; s < NS; ++s) {
+      const Sample sm = load_sample(a.rays, a.z, clamp_sample(wt * (16 * NS) + 16 * s + c, a.M), a.n);
+#if NERF_ABLATE == 3          // timing-only build 3: no positional-encoding arithmetic
+      bf16x8 cst;
+      for (int j = 0; j < 8; ++j) cst[j] = (__bf16)(sm.p[0] + sm.d[0]);
+      pe[s][0] = cst; pe[s][1] = cst; dpe[s][0] = cst;
+#else
+      encode_group<SinRevFract, PackBf16, false>(q, sm.p, pe[s]);
+      encode_group<SinRevFract, PackBf16, true>(q, sm.d, dpe[s]);
+#endif
     }
-    // 12 NS pairs over the remaining slots of the layer (128 k-steps): one pair every 4th slot (NS <= 2) / 2nd slot
-    constexpr int EVERY = NS <= 2 ? 4 : 2;
-    if (slot >= 4 && (slot % EVERY) == 0) {
-      const int idx = (slot - 4) / EVERY;
-      if (idx < 12 * NS) {
-        const int s = idx / 12, j = idx % 12;
-        if (j < 8) pe16_pair<NS>(pq, pn[s], raw.v[s], j, cur, s);      // in place: pos5 was the last reader
-        else pe16_pair<NS>(pq, pn[s], raw.v[s], j, nxt, s);
-      }
-    }
-  };
+  }
+  pq.publish(ws.wv);
   int bad[NS];                      // non-finite inputs of this lane's samples (mlp_frag.h: nonfinite_flags), used at the output store
 #pragma unroll
   for (int s = 0; s < NS; ++s)
@@ -646,8 +475,8 @@ __device__ __forceinline__ void fwd_tiles16(const FwdArgs& a, WS& ws, int64_t wt
     }
     layer_fwd16<NS, 10, 16, true>(ws, L16::F_L5, 1280, cat, hb, lane);
   }
-  layer_fwd16<NS, 8, 16, true>(ws, L16::F_L6, 1536, hb, ha, lane, hook_load);
-  layer_fwd16<NS, 8, 16, true>(ws, L16::F_L7, 1792, ha, hb, lane, hook_math);
+  layer_fwd16<NS, 8, 16, true>(ws, L16::F_L6, 1536, hb, ha, lane);
+  layer_fwd16<NS, 8, 16, true>(ws, L16::F_L7, 1792, ha, hb, lane);
   layer_fwd16<NS, 8, 16, false>(ws, L16::F_FA, L::BI_FEAT, hb, ha, lane);
   float alpha[NS];
   {
@@ -697,10 +526,6 @@ __device__ __forceinline__ void fwd_tiles16(const FwdArgs& a, WS& ws, int64_t wt
       }
     }
   }
-  if (NERF_PE_HOIST) {
-#pragma unroll
-    for (int s = 0; s < NS; ++s) cur.dpe[s][0] = nxt.dpe[s][0];
-  }
 }
 
 // NW waves x NS sample tiles of 16 = 256 samples per workgroup pass either way: <8, 2> two waves per SIMD at 256
@@ -721,24 +546,13 @@ __global__ void __launch_bounds__(64 * NW) mlp_fwd_ring16_kernel(FwdArgs a) {
   __syncthreads();
   NERF_STAMP_BEGIN();
   NERF_STAMP2_LOOP();
-  PeRegs<NS> cur;
-  if (NERF_PE_HOIST) {
-    const int64_t first = (int64_t)blockIdx.x * NW + wv;
-    pe16_all<NS>(a, pe16_setup(a.fr, lane >> 4), first < nwtiles ? first : nwtiles - 1, lane & 15, cur);
-  }
   PassQueue pq;                                         // dynamic pass queue (mlp_ring.h); a.queue == nullptr: static split
-  pq.init(NERF_PE_HOIST ? nullptr : a.queue, ws.lds0 + RING_BIAS_OFF);      // (the hoisted-encoding build needs the next pass a pass early)
+  pq.init(a.queue, ws.lds0 + RING_BIAS_OFF);
   for (int64_t sp = blockIdx.x; sp < nsuper;) {
     int ln = lane;
     asm volatile("" : "+v"(ln));
     ws.new_pass();
-    if (!NERF_PE_HOIST) {
-      const int64_t wt = sp * NW + wv;
-      pq.ask(wv, ln);                                   // before this pass's input loads
-      pe16_all<NS>(a, pe16_setup(a.fr, ln >> 4), wt < nwtiles ? wt : nwtiles - 1, ln & 15, cur);
-      pq.publish(wv);
-    }
-    fwd_tiles16<NS>(a, ws, sp * NW + wv, (sp + gridDim.x) * NW + wv, nwtiles, ln, cur);
+    fwd_tiles16<NS>(a, ws, sp * NW + wv, nwtiles, ln, pq);
     NERF_STAMP_PASS();
     NERF_STAMP2_PASS();
     sp = pq.next(sp);
@@ -1182,7 +996,7 @@ __device__ __forceinline__ void fwd_tiles_img(const ImgArgs& a, WS& ws, int64_t 
   int64_t m = tile * 32 + r; if (m >= a.M) m = a.M - 1;
   bf16x8 xin[ST][3];
 #pragma unroll
-  for (int ks = 0; ks < 3; ++ks) xin[0][ks] = row_frag(a.x + m * LI::CIN, ks, h, LI::CIN);
+  for (int ks = 0; ks < 3; ++ks) row_pairs<CvtBf16>(a.x + m * LI::CIN, ks, h, LI::CIN, xin[0][ks]);
   int bad = nonfinite_flags<32>(nonfinite_bits(xin[0][0]) | nonfinite_bits(xin[0][1]) | nonfinite_bits(xin[0][2]), 0u);
   asm volatile("" : "+v"(bad));               // at the head of the pass (see fwd_tiles)
   if (STORE) { store_frags<3>(a.acts, tile0, a.astride, LI::A_X, xin[0], r, h); ws.note_stores(3); }
@@ -1438,8 +1252,8 @@ __global__ void __launch_bounds__(512) mlp_small_fwd_kernel(SmallArgs a) {
       else ngp_row_frags<false, LW>(a, m, h, xin, din);
     } else {
       const float* row = a.x + m * LN::CIN;
-      xin[0][0] = row_frag(row, 0, h, LN::CPOS); xin[0][1] = row_frag(row, 1, h, LN::CPOS);
-      din[0][0] = row_frag(row + LN::CPOS, 0, h, LN::CDIR);
+      row_pairs<CvtBf16>(row, 0, h, LN::CPOS, xin[0][0]); row_pairs<CvtBf16>(row, 1, h, LN::CPOS, xin[0][1]);
+      row_pairs<CvtBf16>(row + LN::CPOS, 0, h, LN::CDIR, din[0][0]);
     }
     int bad = nonfinite_flags<32>(nonfinite_bits(xin[0][0]) | nonfinite_bits(xin[0][1]), nonfinite_bits(din[0][0]));
     asm volatile("" : "+v"(bad));         // at the head of the tile (see fwd_tiles)

@@ -17,12 +17,6 @@
 #include "mlp_layout.h"
 #include "mlp22.h"
 
-// 1: OCML sinf / cosf for the positional encodings; 0: two-fma Cody-Waite reduction + v_sin_f32 (tools/f16_probe.hip
-// measures both against sin() in double on the encodings' argument range)
-#ifndef NERF_F22_SINF
-#define NERF_F22_SINF 0
-#endif
-
 // A/B switches of the layer epilogue (see layer22)
 #ifndef NERF_F22_PIN
 #define NERF_F22_PIN 1
@@ -160,35 +154,7 @@ __global__ void __launch_bounds__(256) pack22_kernel(const float* __restrict__ p
   }
 }
 
-// ------------------------------------------------------------------------------------------
-// positional encodings (models/embedding.py:30-71), float32-accurate, straight into (hi, lo) B fragments
-// ------------------------------------------------------------------------------------------
-// sin(x f + 2 pi ph), ph in {0, 1/4} (cos).  x f is the reference's float32 product.
-__device__ __forceinline__ float sin_acc(float x, float f, float ph) {
-  const float a = x * f;
-#if NERF_F22_SINF
-  return ph != 0.0f ? cosf(a) : sinf(a);
-#else
-  // a - k 2 pi with 2 pi = HI + LO in two fused steps (|k| <= 80: exact products), then v_sin_f32 on revolutions in [-3/4, 3/4]
-  const float k = __builtin_rintf(a * 0.15915494309189535f);
-  float r = __builtin_fmaf(-k, 6.2831854820251465f, a);
-  r = __builtin_fmaf(-k, -1.7484556000744487e-07f, r);
-  return __builtin_amdgcn_sinf(__builtin_fmaf(r, 0.15915494309189535f, ph));
-#endif
-}
-
-struct Pe22 { float fa, fb, fc, phc, fd; int g; };          // per-lane-group frequencies of the channel order (pos_chan16)
-__device__ __forceinline__ Pe22 pe22_setup(const PeFreq& fr, int g) {
-  Pe22 q;
-  q.fa = g == 0 ? fr.pos[0] : g == 1 ? fr.pos[2] : g == 2 ? fr.pos[4] : fr.pos[6];
-  q.fb = g == 0 ? fr.pos[1] : g == 1 ? fr.pos[3] : g == 2 ? fr.pos[5] : fr.pos[7];
-  q.fc = g < 2 ? fr.pos[8] : fr.pos[9];
-  q.phc = (g & 1) ? 0.25f : 0.0f;
-  q.fd = g == 0 ? fr.dir[0] : g == 1 ? fr.dir[1] : g == 2 ? fr.dir[2] : fr.dir[3];
-  q.g = g;
-  return q;
-}
-
+// positional encodings, float32-accurate, straight into (hi, lo) B fragments: mlp_input.h (here: SinCodyWaite, SplitF16)
 template <int COUNT>
 __device__ __forceinline__ void split_slots(const float (&v)[COUNT], u32x4* hi, u32x4* lo) {
 #pragma unroll
@@ -197,47 +163,10 @@ __device__ __forceinline__ void split_slots(const float (&v)[COUNT], u32x4* hi, 
     hi[j >> 3][(j & 7) >> 1] = q.hi; lo[j >> 3][(j & 7) >> 1] = q.lo;
   }
 }
-
-// MODE 1: from a position p and a view direction d
-__device__ __forceinline__ void pe22_pos(const Pe22& q, const float (&p)[3], u32x4 (&peh)[2], u32x4 (&pel)[2]) {
-  float v[16];
-#pragma unroll
-  for (int sl = 0; sl < 12; ++sl) v[sl] = sin_acc(p[sl % 3], sl < 6 ? q.fa : q.fb, (sl % 6) >= 3 ? 0.25f : 0.0f);
-#pragma unroll
-  for (int k = 0; k < 3; ++k) v[12 + k] = sin_acc(p[k], q.fc, q.phc);
-  v[15] = q.g == 0 ? p[0] : q.g == 1 ? p[1] : q.g == 2 ? p[2] : 0.0f;
-  split_slots<16>(v, peh, pel);
-}
-__device__ __forceinline__ void pe22_dir(const Pe22& q, const float (&d)[3], u32x4 (&dph)[1], u32x4 (&dpl)[1]) {
-  float w[8];
-#pragma unroll
-  for (int j = 0; j < 6; ++j) w[j] = sin_acc(d[j % 3], q.fd, j >= 3 ? 0.25f : 0.0f);
-  w[6] = q.g == 0 ? d[0] : q.g == 1 ? d[1] : q.g == 2 ? d[2] : 0.0f;
-  w[7] = 0.0f;
-  split_slots<8>(w, dph, dpl);
-}
-__device__ __forceinline__ void pe22_encode(const Pe22& q, const float (&p)[3], const float (&d)[3], u32x4 (&peh)[2],
-                                            u32x4 (&pel)[2], u32x4 (&dph)[1], u32x4 (&dpl)[1]) {
-  pe22_pos(q, p, peh, pel);
-  pe22_dir(q, d, dph, dpl);
-}
-// MODE 0: from an already-embedded row x[90] = [embed(pos) 63 | embed(dir) 27]   (NeRF.forward(x) entry)
-__device__ __forceinline__ void pe22_row(const float* __restrict__ row, int g, u32x4 (&peh)[2], u32x4 (&pel)[2],
-                                         u32x4 (&dph)[1], u32x4 (&dpl)[1]) {
-  float v[16], w[8];
-#pragma unroll
-  for (int sl = 0; sl < 16; ++sl) {
-    const int ch = pos_chan16(sl >> 3, g, sl & 7);
-    v[sl] = ch >= 0 ? row[ch] : 0.0f;
-  }
-#pragma unroll
-  for (int j = 0; j < 8; ++j) {
-    const int ch = dir_chan16(g, j);
-    w[j] = ch >= 0 ? row[63 + ch] : 0.0f;
-  }
-  split_slots<16>(v, peh, pel);
-  split_slots<8>(w, dph, dpl);
-}
+// packer of the input stage: eight floats -> a (hi, lo) pair of fp16 B fragments
+struct SplitF16 {
+  static __device__ __forceinline__ void pack(const float (&v)[8], u32x4& hi, u32x4& lo) { split_slots<8>(v, &hi, &lo); }
+};
 
 // ------------------------------------------------------------------------------------------
 // one linear layer on register-resident (hi, lo) activations
@@ -438,33 +367,26 @@ __device__ __forceinline__ void tiles22(const FwdArgs& a, WS& ws, int64_t wtile0
   u32x4 peh[NS][2], pel[NS][2], dph[NS][1], dpl[NS][1];
   const unsigned park = ws.lds0 + PARK_OFF + 4u * (unsigned)(ws.wv * 64 + lane);      // + 1024 k: value k of this lane
   pq.ask(ws.wv, lane);                    // the workgroup's next pass: asked for before this pass's input loads (mlp_ring.h)
-  const Pe22 q = pe22_setup(a.fr, g);
+  const GroupFreq q = group_freqs(a.fr, g);
   {
     const int64_t wt = wtile0 < nwtiles ? wtile0 : nwtiles - 1;
 #pragma unroll
     for (int s = 0; s < NS; ++s) {
-      int64_t m = wt * (16 * NS) + 16 * s + c; if (m >= a.M) m = a.M - 1;
+      const int64_t m = clamp_sample(wt * (16 * NS) + 16 * s + c, a.M);
       if (MODE == 0) {
-        pe22_row(a.x + m * 90, g, peh[s], pel[s], dph[s], dpl[s]);
+        row_group<SplitF16, false>(a.x + m * 90, g, peh[s], pel[s]);
+        row_group<SplitF16, true>(a.x + m * 90 + 63, g, dph[s], dpl[s]);
       } else {
-        const int64_t ray = (int64_t)((unsigned)m / (unsigned)a.n);            // M < 2^31 (checked on the host)
-        const float* rr = a.rays + ray * NERF_RAY_STRIDE;
-        float p[3], d[3];
 #if NERF_ABLATE == 3          // timing-only build 3: no input loads at the head of a pass (positions from the lane id)
-        (void)rr;
+        Sample sm;
 #pragma unroll
-        for (int k = 0; k < 3; ++k) { p[k] = 0.001f * (float)(m & 1023) + (float)k; d[k] = 0.5f; }
+        for (int k = 0; k < 3; ++k) { sm.p[k] = 0.001f * (float)(m & 1023) + (float)k; sm.d[k] = 0.5f; }
 #else
-        const float zv = a.z[m];
-#pragma unroll
-        for (int k = 0; k < 3; ++k) { p[k] = rr[k] + zv * rr[3 + k]; d[k] = rr[8 + k]; }   // render.py:142
+        const Sample sm = load_sample(a.rays, a.z, m, a.n);
 #endif
-        if (RECOMP) {
-          park_put_s(s, park, p, d);
-          pe22_pos(q, p, peh[s], pel[s]);
-        } else {
-          pe22_encode(q, p, d, peh[s], pel[s], dph[s], dpl[s]);
-        }
+        if (RECOMP) park_put_s(s, park, sm.p, sm.d);
+        encode_group<SinCodyWaite, SplitF16, false>(q, sm.p, peh[s], pel[s]);
+        if (!RECOMP) encode_group<SinCodyWaite, SplitF16, true>(q, sm.d, dph[s], dpl[s]);
       }
     }
   }
@@ -482,7 +404,7 @@ __device__ __forceinline__ void tiles22(const FwdArgs& a, WS& ws, int64_t wtile0
       if (RECOMP) {                                                             // re-evaluated HERE, not kept from the head of the pass
         float pp[3];
         park_get_s<0>(s, park, pp);
-        pe22_pos(q, pp, peh[s], pel[s]);
+        encode_group<SinCodyWaite, SplitF16, false>(q, pp, peh[s], pel[s]);
       }
       cth[s][0] = peh[s][0]; cth[s][1] = peh[s][1]; ctl[s][0] = pel[s][0]; ctl[s][1] = pel[s][1];
 #pragma unroll
@@ -512,7 +434,7 @@ __device__ __forceinline__ void tiles22(const FwdArgs& a, WS& ws, int64_t wtile0
       if (RECOMP) {
         float dd[3];
         park_get_s<3>(s, park, dd);
-        pe22_dir(q, dd, dph[s], dpl[s]);
+        encode_group<SinCodyWaite, SplitF16, true>(q, dd, dph[s], dpl[s]);
       }
       cth[s][8] = dph[s][0]; ctl[s][8] = dpl[s][0];
     }

@@ -318,39 +318,14 @@ struct FwdArgs32 {
   int out_ch;            // image model: columns of `out` (1..4)
 };
 
-// channel c of the embedding [x, sin(f0 x), cos(f0 x), ...] (models/embedding.py:30-71), c >= limit -> 0
-struct Chan { int kind, dim, band; };   // kind: 0 identity, 1 sin, 2 cos, 3 zero pad
-__host__ __device__ constexpr Chan chan_of(int c, int limit) {
-  if (c < 3) return Chan{0, c, 0};
-  if (c >= limit) return Chan{3, 0, 0};
-  return Chan{((c - 3) % 6) >= 3 ? 2 : 1, (c - 3) % 3, (c - 3) / 6};
-}
-// register i of a lane holds channel C0 (lane half 0) or C0 + 4 (lane half 1): both descriptions are compile-time, only
-// the select is per lane, so the frequency table is never indexed dynamically (no scratch)
-template <int C0, int LIMIT, int NB>
-__device__ __forceinline__ float embed_pair(const float (&v)[3], const float (&fr)[NB], int h) {
-  constexpr Chan a = chan_of(C0, LIMIT), b = chan_of(C0 + 4, LIMIT);
-  const float xa = v[a.dim], xb = v[b.dim];
-  const float arg = h ? xb * fr[b.band] : xa * fr[a.band];        // x * freq as one float32 product, like the reference
-  float sv = 0.0f, cv = 0.0f;
-  constexpr bool need_s = a.kind == 1 || b.kind == 1, need_c = a.kind == 2 || b.kind == 2;
-  if (need_s && need_c) sincosf(arg, &sv, &cv);                    // one argument reduction for the two lane halves
-  else if (need_s) sv = sinf(arg);
-  else if (need_c) cv = cosf(arg);
-  const float va = a.kind == 0 ? xa : a.kind == 1 ? sv : a.kind == 2 ? cv : 0.0f;
-  const float vb = b.kind == 0 ? xb : b.kind == 1 ? sv : b.kind == 2 ? cv : 0.0f;
-  return h ? vb : va;
-}
-template <int KT, int LIMIT, int NB, int... I>
-__device__ __forceinline__ f32x16 embed_tile_impl(const float (&v)[3], const float (&fr)[NB], int h) {
-  f32x16 r;
-  ((r[I] = embed_pair<32 * KT + prow(I), LIMIT, NB>(v, fr, h)), ...);
-  return r;
-}
-template <int KT, int LIMIT, int NB>
-__device__ __forceinline__ f32x16 embed_tile(const float (&v)[3], const float (&fr)[NB], int h) {
-  return embed_tile_impl<KT, LIMIT, NB, 0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11, 12, 13, 14, 15>(v, fr, h);
-}
+// packer of the input stage (mlp_input.h; here: SinOcml): a 32-channel tile is two k-steps of the pair layout, eight floats each
+struct PlainF32 {
+  static __device__ __forceinline__ void pack(const float (&v)[8], f32x16& tile, int half) {
+#pragma unroll
+    for (int j = 0; j < 8; ++j) tile[8 * half + j] = v[j];
+  }
+};
+static_assert(prow(11) == kperm(1, 0, 3) && prow(4) + 4 == kperm(0, 1, 4), "register i of a tile = element i & 7 of k-step i >> 3");
 
 template <bool STORE, bool IMG>
 __global__ void __launch_bounds__(256) mlp32_fwd_kernel(FwdArgs32 a) {
@@ -366,14 +341,14 @@ __global__ void __launch_bounds__(256) mlp32_fwd_kernel(FwdArgs32 a) {
   if (tile >= ntiles) return;
   float* slab = slab_smem + wv * (256 * 32);
   const float4* wl = a.wf + lane * 4;
-  int64_t m = tile * 32 + col; if (m >= a.M) m = a.M - 1;
+  const int64_t m = clamp_sample(tile * 32 + col, a.M);
   f32x16 pe[2], dpe[1];
   if (IMG) {                                                           // embedded rows [M,40] only (no fused encoding)
     const float* row = a.x + m * LI::CIN;
 #pragma unroll
     for (int kt = 0; kt < 2; ++kt)
 #pragma unroll
-      for (int i = 0; i < 16; ++i) { const int c = 32 * kt + prow(i) + 4 * h; pe[kt][i] = c < LI::CIN ? row[c] : 0.0f; }
+      for (int half = 0; half < 2; ++half) row_pairs<PlainF32>(row, 2 * kt + half, h, LI::CIN, pe[kt], half);
 #pragma unroll
     for (int i = 0; i < 16; ++i) dpe[0][i] = 0.0f;
     // the row loads are complete before the first store below is issued: hipcc otherwise interleaves them and counts the
@@ -382,20 +357,14 @@ __global__ void __launch_bounds__(256) mlp32_fwd_kernel(FwdArgs32 a) {
   } else if (a.x) {
     const float* row = a.x + m * 90;
 #pragma unroll
-    for (int kt = 0; kt < 2; ++kt)
+    for (int ks = 0; ks < 4; ++ks) row_pairs<PlainF32>(row, ks, h, 63, pe[ks >> 1], ks & 1);
 #pragma unroll
-      for (int i = 0; i < 16; ++i) { const int c = 32 * kt + prow(i) + 4 * h; pe[kt][i] = c < 63 ? row[c] : 0.0f; }
-#pragma unroll
-    for (int i = 0; i < 16; ++i) { const int c = prow(i) + 4 * h; dpe[0][i] = c < 27 ? row[63 + c] : 0.0f; }
+    for (int ks = 0; ks < 2; ++ks) row_pairs<PlainF32>(row + 63, ks, h, 27, dpe[0], ks);
   } else {
-    const float* rr = a.rays + (m / a.n) * NERF_RAY_STRIDE;
-    const float zv = a.z[m];
-    float p[3], d[3];
-#pragma unroll
-    for (int c = 0; c < 3; ++c) { p[c] = rr[c] + zv * rr[3 + c]; d[c] = rr[8 + c]; }       // render.py:142
-    pe[0] = embed_tile<0, 63, 10>(p, a.fpos, h);
-    pe[1] = embed_tile<1, 63, 10>(p, a.fpos, h);
-    dpe[0] = embed_tile<0, 27, 4>(d, a.fdir, h);
+    const Sample sm = load_sample(a.rays, a.z, m, a.n);
+    encode_pairs<SinOcml, PlainF32, 0, 63, 10>(sm.p, a.fpos, h, pe[0], 0); encode_pairs<SinOcml, PlainF32, 1, 63, 10>(sm.p, a.fpos, h, pe[0], 1);
+    encode_pairs<SinOcml, PlainF32, 2, 63, 10>(sm.p, a.fpos, h, pe[1], 0); encode_pairs<SinOcml, PlainF32, 3, 63, 10>(sm.p, a.fpos, h, pe[1], 1);
+    encode_pairs<SinOcml, PlainF32, 0, 27, 4>(sm.d, a.fdir, h, dpe[0], 0); encode_pairs<SinOcml, PlainF32, 1, 27, 4>(sm.d, a.fdir, h, dpe[0], 1);
   }
   // rows `row0` ... of this tile in the activation store (training only): each layer is stored by the NEXT one
   auto rows_of = [&](int row0) -> float* { return STORE ? store_row(a.acts, tile, A_ROWS, row0, 0) : nullptr; };

@@ -6,13 +6,6 @@
 
 namespace nerf {
 
-struct Chan { int kind, dim, band; };   // kind: 0 identity, 1 sin, 2 cos, 3 zero pad
-__host__ __device__ constexpr Chan chan_of(int c, int limit) {
-  if (c < 3) return Chan{0, c, 0};
-  if (c >= limit) return Chan{3, 0, 0};
-  return Chan{((c - 3) % 6) >= 3 ? 2 : 1, (c - 3) % 3, (c - 3) / 6};
-}
-
 // ------------------------------------------------------------------------------------------
 // weight packing sources: which master parameter sits in element j of lane (r, h) of fragment f of the 32x32x16 streams
 // ------------------------------------------------------------------------------------------
@@ -93,6 +86,20 @@ __device__ __forceinline__ bf16x2 pack2(float a, float b) {       // one v_cvt_p
   const f32x2 v = {a, b};
   return __builtin_convertvector(v, bf16x2);
 }
+// packer of the input stage (mlp_input.h): eight floats -> one bf16 B fragment
+struct PackBf16 {
+  static __device__ __forceinline__ void pack(const float (&v)[8], bf16x8& o) {
+#pragma unroll
+    for (int j = 0; j < 8; j += 2) { const bf16x2 a = pack2(v[j], v[j + 1]); o[j] = a[0]; o[j + 1] = a[1]; }
+  }
+};
+// ... element by element, as the 32x32x16 chains convert their inputs (hipcc pairs the conversions itself, in another order)
+struct CvtBf16 {
+  static __device__ __forceinline__ void pack(const float (&v)[8], bf16x8& o) {
+#pragma unroll
+    for (int j = 0; j < 8; ++j) o[j] = (__bf16)v[j];
+  }
+};
 __device__ __forceinline__ bf16x2 relu_pack(float a, float b) {
   s16x2 q = __builtin_bit_cast(s16x2, pack2(a, b));
   const s16x2 zero = {0, 0};

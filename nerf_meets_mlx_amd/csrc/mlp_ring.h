@@ -3,6 +3,7 @@
 #pragma once
 #include "common.h"
 #include "launch.h"
+#include "mlp_input.h"
 #include <atomic>
 
 #ifndef NERF_SPREAD_DMA
@@ -28,12 +29,7 @@ typedef short s16x4 __attribute__((ext_vector_type(4)));
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
-struct PeFreq { float pos[10]; float dir[4]; };
-// host: the encoding frequencies of freq_mode 0 (k * k) / 1 (2^k)
-static inline void fill_freqs(float* pos, float* dir, int mode) {
-  for (int k = 0; k < 10; ++k) pos[k] = mode == 0 ? (float)(k * k) : (float)(1 << k);
-  for (int k = 0; k < 4; ++k) dir[k] = mode == 0 ? (float)(k * k) : (float)(1 << k);
-}
+// PeFreq, fill_freqs (the encoding frequencies in FwdArgs): mlp_input.h
 
 // ------------------------------------------------------------------------------------------
 // weight sources: where a wave gets the 1 KiB A-operand fragment `f` of the packed stream from

@@ -62,42 +62,7 @@ __global__ void __launch_bounds__(256) pack_s16_kernel(const float* __restrict__
   dst[(2 * f + 1) * 64 + lane] = lo[0];
 }
 
-// ------------------------------------------------------------------------------------------
-// positional encodings (models/embedding.py:30-71), float32-accurate, straight into (hi, lo) B fragments
-// ------------------------------------------------------------------------------------------
-// sin(x f + 2 pi ph), ph in {0, 1/4} (cos).  x f is the reference's float32 product; a - k 2 pi with 2 pi = HI + LO in two
-// fused steps (|k| <= 82: exact products), then v_sin_f32 on revolutions in [-3/4, 3/4]  (same evaluation as mlp22.hip)
-__device__ __forceinline__ float sin_acc(float x, float f, float ph) {
-  const float a = x * f;
-  const float k = __builtin_rintf(a * 0.15915494309189535f);
-  float r = __builtin_fmaf(-k, 6.2831854820251465f, a);
-  r = __builtin_fmaf(-k, -1.7484556000744487e-07f, r);
-  return __builtin_amdgcn_sinf(__builtin_fmaf(r, 0.15915494309189535f, ph));
-}
-// channel order [x, sin(f0 x), cos(f0 x), ...]: element j of lane half h in k-step KS is channel kperm(KS, h, j)
-template <int C0, int LIMIT, int NB>
-__device__ __forceinline__ float pe_value_acc(const float (&x)[3], const float (&fr)[NB], int h) {
-  constexpr Chan a = chan_of(C0, LIMIT), b = chan_of(C0 + 4, LIMIT);
-  const float xa = x[a.dim], xb = x[b.dim];
-  const float xv = h ? xb : xa;
-  const float fv = h ? fr[b.band] : fr[a.band];
-  const float ph = h ? (b.kind == 2 ? 0.25f : 0.0f) : (a.kind == 2 ? 0.25f : 0.0f);
-  const float s = sin_acc(xv, fv, ph);
-  const float va = a.kind == 0 ? xa : (a.kind == 3 ? 0.0f : s);
-  const float vb = b.kind == 0 ? xb : (b.kind == 3 ? 0.0f : s);
-  return h ? vb : va;
-}
-template <int KS, int LIMIT, int NB, int... J>
-__device__ __forceinline__ void pe_frag_impl(const float (&x)[3], const float (&fr)[NB], int h, bf16x8& hi, bf16x8& lo) {
-  float v[8];
-  ((v[J] = pe_value_acc<16 * KS + 8 * (J >> 2) + (J & 3), LIMIT, NB>(x, fr, h)), ...);
-  split_slots<8>(v, &hi, &lo);
-}
-template <int KS, int LIMIT, int NB>
-__device__ __forceinline__ void pe_frag(const float (&x)[3], const float (&fr)[NB], int h, bf16x8& hi, bf16x8& lo) {
-  pe_frag_impl<KS, LIMIT, NB, 0, 1, 2, 3, 4, 5, 6, 7>(x, fr, h, hi, lo);
-}
-
+// positional encodings, float32-accurate, straight into (hi, lo) B fragments: mlp_input.h (here: SinCodyWaite, SplitBf16)
 
 // All 12 layers for the wave's 32 samples (sample tile `tile0`).  Waves past the end compute on clamped inputs, store into
 // the padding tiles of the workspace and write no output, so every wave runs the same instruction stream (the ring needs it).
@@ -109,23 +74,18 @@ __device__ __forceinline__ void fwd_tiles(const FwdArgs& a, WS& ws, int64_t tile
   pq.ask(ws.wv, lane);                    // dynamic pass queue (mlp_ring.h): before this pass's input loads
   {
     const int64_t tile = tile0 < ntiles ? tile0 : ntiles - 1;
-    int64_t m = tile * 32 + r; if (m >= a.M) m = a.M - 1;
+    const int64_t m = clamp_sample(tile * 32 + r, a.M);
     if (MODE == 0) {
       const float* row = a.x + m * 90;
 #pragma unroll
-      for (int ks = 0; ks < 4; ++ks) row_frag(row, ks, h, 63, peh[ks], pel[ks]);
+      for (int ks = 0; ks < 4; ++ks) row_pairs<SplitBf16>(row, ks, h, 63, peh[ks], pel[ks]);
 #pragma unroll
-      for (int ks = 0; ks < 2; ++ks) row_frag(row + 63, ks, h, 27, dph[ks], dpl[ks]);
+      for (int ks = 0; ks < 2; ++ks) row_pairs<SplitBf16>(row + 63, ks, h, 27, dph[ks], dpl[ks]);
     } else {
-      const int64_t ray = (int64_t)((unsigned)m / (unsigned)a.n);     // M < 2^31 (checked on the host): 32-bit divide
-      const float* rr = a.rays + ray * NERF_RAY_STRIDE;
-      const float zv = a.z[m];
-      float p[3], d[3];
-#pragma unroll
-      for (int c = 0; c < 3; ++c) { p[c] = rr[c] + zv * rr[3 + c]; d[c] = rr[8 + c]; }   // render.py:142
-      pe_frag<0, 63, 10>(p, a.fr.pos, h, peh[0], pel[0]); pe_frag<1, 63, 10>(p, a.fr.pos, h, peh[1], pel[1]);
-      pe_frag<2, 63, 10>(p, a.fr.pos, h, peh[2], pel[2]); pe_frag<3, 63, 10>(p, a.fr.pos, h, peh[3], pel[3]);
-      pe_frag<0, 27, 4>(d, a.fr.dir, h, dph[0], dpl[0]); pe_frag<1, 27, 4>(d, a.fr.dir, h, dph[1], dpl[1]);
+      const Sample sm = load_sample(a.rays, a.z, m, a.n);
+      encode_pairs<SinCodyWaite, SplitBf16, 0, 63, 10>(sm.p, a.fr.pos, h, peh[0], pel[0]); encode_pairs<SinCodyWaite, SplitBf16, 1, 63, 10>(sm.p, a.fr.pos, h, peh[1], pel[1]);
+      encode_pairs<SinCodyWaite, SplitBf16, 2, 63, 10>(sm.p, a.fr.pos, h, peh[2], pel[2]); encode_pairs<SinCodyWaite, SplitBf16, 3, 63, 10>(sm.p, a.fr.pos, h, peh[3], pel[3]);
+      encode_pairs<SinCodyWaite, SplitBf16, 0, 27, 4>(sm.d, a.fr.dir, h, dph[0], dpl[0]); encode_pairs<SinCodyWaite, SplitBf16, 1, 27, 4>(sm.d, a.fr.dir, h, dph[1], dpl[1]);
     }
   }
   pq.publish(ws.wv);

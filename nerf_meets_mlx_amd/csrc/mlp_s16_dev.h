@@ -34,16 +34,10 @@ __device__ __forceinline__ f32x16 mfma32(const bf16x8& a, const bf16x8& b, const
   return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, 0, 0, 0);
 }
 
-// fragment of an already-embedded row x[m][base + c], c < limit else 0   (NeRF.forward(x) entry)
-__device__ __forceinline__ void row_frag(const float* __restrict__ row, int ks, int h, int limit, bf16x8& hi, bf16x8& lo) {
-  float v[8];
-#pragma unroll
-  for (int j = 0; j < 8; ++j) {
-    const int c = kperm(ks, h, j);
-    v[j] = c < limit ? row[c] : 0.0f;
-  }
-  split_slots<8>(v, &hi, &lo);
-}
+// packer of the input stage (mlp_input.h): eight floats -> a (hi, lo) pair of bf16 B fragments
+struct SplitBf16 {
+  static __device__ __forceinline__ void pack(const float (&v)[8], bf16x8& hi, bf16x8& lo) { split_slots<8>(v, &hi, &lo); }
+};
 
 // ------------------------------------------------------------------------------------------
 // one linear layer on register-resident (hi, lo) activations

@@ -84,7 +84,7 @@ __device__ __forceinline__ void img_fwd_tiles(const ImgArgs& a, WS& ws, int64_t 
     int64_t m = tile * 32 + r; if (m >= a.M) m = a.M - 1;
     const float* row = a.x + m * LI::CIN;
 #pragma unroll
-    for (int ks = 0; ks < 3; ++ks) s16::row_frag(row, ks, h, LI::CIN, xh[ks], xl[ks]);
+    for (int ks = 0; ks < 3; ++ks) row_pairs<s16::SplitBf16>(row, ks, h, LI::CIN, xh[ks], xl[ks]);
   }
   if (STORE) {
     store_frags<3>(a.acts, tile0, a.astride, LI::A_X, xh, r, h);

@@ -125,8 +125,8 @@ __global__ void __launch_bounds__(512) s16_small_fwd_kernel(SmallArgs a) {
       ngp_row_pairs<LW>(a, m, h, xh, xl, dh, dl);
     } else {
       const float* row = a.x + m * LN::CIN;
-      s16::row_frag(row, 0, h, LN::CPOS, xh[0], xl[0]); s16::row_frag(row, 1, h, LN::CPOS, xh[1], xl[1]);
-      s16::row_frag(row + LN::CPOS, 0, h, LN::CDIR, dh[0], dl[0]);
+      row_pairs<s16::SplitBf16>(row, 0, h, LN::CPOS, xh[0], xl[0]); row_pairs<s16::SplitBf16>(row, 1, h, LN::CPOS, xh[1], xl[1]);
+      row_pairs<s16::SplitBf16>(row + LN::CPOS, 0, h, LN::CDIR, dh[0], dl[0]);
     }
 #define SINK(slot0) make_sink<STORE>(a.acts, tile0, a.astride, slot0, SM_A_LO, r, h)
 #define MASK_STORE(layer) do { if (STORE) *reinterpret_cast<u32x4*>(frag_ptr(a.acts, tile0, a.astride, SM_A_MASK + (layer), r, h)) = mk; } while (0)

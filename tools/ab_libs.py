@@ -6,9 +6,10 @@
         moves the colours by rounding and nothing else: then only an alpha difference is a bit-identity failure (exit 1)
     python tools/ab_libs.py --models tools/diag/libnerf_A.so default
         every MLP model (view / image / 2x64 in each of their precisions) through pack, training forward and backward at M = 65 and
-        8193, plus the fused view-model and hash-grid queries at B = 64, n = 3 and 64, on seeded inputs: sha256 of the output, the
-        packed buffer, the activation store, the dZ store (without the split-K partial slots), the gradients and d_x.  Exit 1 unless
-        every digest is the same in every library.
+        8193 (the embedded-row entry; the view model's rows also through the inference forward), plus the fused view-model query at
+        freq_mode 0 and 1 and the hash-grid queries at B = 64, n = 3 and 64, on seeded inputs: sha256 of the output, the packed
+        buffer, the activation store (it holds the stored encodings), the dZ store (without the split-K partial slots), the
+        gradients and d_x.  Exit 1 unless every digest is the same in every library.
 Every child runs under a time limit, and after a child that failed or ran out of time no further child is started."""
 import argparse, json, os, subprocess, sys, tempfile
 CHILD = r'''
@@ -73,17 +74,22 @@ for shape, prec in [(s, p) for s in MODELS for p in (16, 32, 22) if (s, p) != ("
         partial = 2048 * (4096 + 64) * 4 if prec == 32 else 512 * (64 * 1024 + 256) * 4      # split-K partial slots behind the dZ blocks
         res[f"{shape}{prec} M={M}"] = {"out": sha(out), "packed": sha(packed), "acts": sha(acts), "dz": sha(dz[:dz.numel() - partial]),
                                        "grads": sha(grads), "d_x": sha(d_x) if shape == "small" else "-"}
+        if shape == "view":                        # NeRF.forward(x) without stores: the inference kernels' embedded-row entry
+            out_inf = zeros(M * cout, torch.float32)
+            N.check(lib.nerf_mlp_forward(a, N.ptr(packed), N.ptr(x), M, N.ptr(out_inf), N.stream()))
+            torch.cuda.synchronize()
+            res[f"rows view{prec} M={M} infer"] = {"out": sha(out_inf)}
 for n in (3, 64):
     B = 64
     for prec in (16, 32, 22):                      # nerf_query_fused: inference (no stores) and training forward
         g = torch.Generator().manual_seed(7 * prec + n)
         arch, a, params, packed = packed_model("view", prec, g)
         rays, z = rays_z(g, B, n)
-        for train in (False, True):
+        for train, freq_mode in [(t, fm) for t in (False, True) for fm in (0, 1)]:
             acts, raw = zeros(lib.nerf_mlp_acts_bytes(a, B * n)), zeros(B * n * 4, torch.float32)
-            N.check(lib.nerf_query_fused(a, N.ptr(packed), N.ptr(rays), N.ptr(z), B, n, 0, N.ptr(raw), N.ptr(acts) if train else None, N.stream()))
+            N.check(lib.nerf_query_fused(a, N.ptr(packed), N.ptr(rays), N.ptr(z), B, n, freq_mode, N.ptr(raw), N.ptr(acts) if train else None, N.stream()))
             torch.cuda.synchronize()
-            res[f"query view{prec} n={n} {'train' if train else 'infer'}"] = {"out": sha(raw), "acts": sha(acts)}
+            res[f"query view{prec} n={n} freq_mode={freq_mode} {'train' if train else 'infer'}"] = {"out": sha(raw), "acts": sha(acts)}
     for prec in (16, 22):                          # nerf_ngp_query_fused / _lw on float32 tables
         g = torch.Generator().manual_seed(11 * prec + n)
         arch, a, params, packed = packed_model("small", prec, g)
