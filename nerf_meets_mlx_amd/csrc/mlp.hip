@@ -26,6 +26,8 @@
 #include "mlp_layout.h"
 #include "mlp_frag.h"
 #include "mlp_arch2.h"
+#include "mlp_input2.h"
+#include "mlp_pack.h"
 #include "hash_common.h"
 #include "mlp_params.h"
 #include "mlp_model.h"
@@ -44,31 +46,7 @@ extern int g_hash_combine_max_res;        // encode.hip
 // ------------------------------------------------------------------------------------------
 // weight packing: fp32 master parameters -> bf16 MFMA fragments (+ fp32 bias slots)
 // ------------------------------------------------------------------------------------------
-// fwd_src / bwd_src (fragment element -> master parameter): mlp_frag.h
-
-constexpr int PACK_THREADS = (L::F_TOTAL + L::B_PADDED) * 64 + L::BI_TOTAL;      // one thread per 16-byte lane slot / bias
-__device__ __forceinline__ void pack_part(int tid, const float* __restrict__ p, bf16x8* __restrict__ wf,
-                                          bf16x8* __restrict__ wb, float* __restrict__ bias) {
-  const int nf = L::F_TOTAL * 64, nb = L::B_PADDED * 64;
-  if (tid < nf + nb) {
-    const bool fw = tid < nf;
-    const int t = fw ? tid : tid - nf;
-    const int f = t >> 6, lane = t & 63, r = lane & 31, h = lane >> 5;
-    bf16x8 v;
-#pragma unroll
-    for (int j = 0; j < 8; ++j) v[j] = (__bf16)(fw ? fwd_src(p, f, r, h, j) : (f < L::B_TOTAL ? bwd_src(p, f, r, h, j) : 0.0f));
-    (fw ? wf : wb)[t] = v;
-  } else if (tid < nf + nb + L::BI_TOTAL) {
-    const int s = tid - nf - nb;
-    float v = 0.0f;
-    if (s < 2048) v = p[L::pb(s >> 8) + (s & 255)];
-    else if (s < L::BI_ALPHA) v = p[L::P_BF + (s - L::BI_FEAT)];
-    else if (s < L::BI_DIR) v = (s == L::BI_ALPHA) ? p[L::P_BA] : 0.0f;
-    else if (s < L::BI_RGB) v = p[L::P_BD + (s - L::BI_DIR)];
-    else v = (s - L::BI_RGB) < 3 ? p[L::P_BR + (s - L::BI_RGB)] : 0.0f;
-    bias[s] = v;
-  }
-}
+// the index maps: mlp_index.h (ViewPack); the routine: mlp_pack.h
 
 // ------------------------------------------------------------------------------------------
 // positional encoding straight into B-operand fragments
@@ -362,12 +340,12 @@ __global__ void __launch_bounds__(64 * NW, 2) mlp_fwd_ring_kernel(FwdArgs a) {
 // the whole bf16 image in ONE launch (was two: at N_rand = 1024 the ~30 five-microsecond launches of an iteration are a tenth
 // of it): blocks [0, PACK_BLOCKS) build the 32x32x16 forward / backward streams and the bias slots, the rest the 16x16x32
 // forward stream of the render kernels
-constexpr int PACK_BLOCKS = (PACK_THREADS + 255) / 256, PACK16_BLOCKS = L::F16_PADDED * 64 / 256;
+constexpr int PACK_BLOCKS = pack_blocks<ViewPack, true>(), PACK16_BLOCKS = L::F16_PADDED * 64 / 256;
 __global__ void __launch_bounds__(256) pack_kernel(const float* __restrict__ p, bf16x8* __restrict__ wf,
                                                    bf16x8* __restrict__ wb, float* __restrict__ bias,
                                                    bf16x8* __restrict__ w16) {
   if (blockIdx.x < PACK_BLOCKS) {
-    pack_part(blockIdx.x * 256 + threadIdx.x, p, wf, wb, bias);
+    pack_streams<ViewPack, CvtBf16, true>(blockIdx.x * 256 + threadIdx.x, p, wf, wb, bias, 0);
     return;
   }
   const int t = (blockIdx.x - PACK_BLOCKS) * 256 + threadIdx.x;
@@ -959,34 +937,8 @@ __global__ void __launch_bounds__(256) mlp_dw_reduce_kernel(DwArgs a) {
 // (models/NeRF.py:182-197,241).  Same register-resident transposed scheme, same ring, same dW kernel.
 // ==========================================================================================
 
-__global__ void __launch_bounds__(256) pack_img_kernel(const float* __restrict__ p, bf16x8* __restrict__ wf,
-                                                       bf16x8* __restrict__ wb, float* __restrict__ bias, int out_ch) {
-  const int tid = blockIdx.x * 256 + threadIdx.x;
-  const int nf = LI::F_TOTAL * 64, nb = LI::B_PADDED * 64;
-  if (tid < nf + nb) {
-    const bool fw = tid < nf;
-    const int t = fw ? tid : tid - nf;
-    const int f = t >> 6, lane = t & 63, r = lane & 31, h = lane >> 5;
-    bf16x8 v;
-#pragma unroll
-    for (int j = 0; j < 8; ++j)
-      v[j] = (__bf16)(fw ? fwd_src_img(p, f, r, h, j, out_ch) : (f < LI::B_TOTAL ? bwd_src_img(p, f, r, h, j, out_ch) : 0.0f));
-    (fw ? wf : wb)[t] = v;
-  } else if (tid < nf + nb + LI::BI_TOTAL) {
-    const int s = tid - nf - nb;
-    bias[s] = s < 2048 ? p[LI::pb(s >> 8) + (s & 255)] : ((s - LI::BI_OUT) < out_ch ? p[LI::P_WO + out_ch * 256 + (s - LI::BI_OUT)] : 0.0f);
-  }
-}
-
-struct ImgArgs {
-  const bf16x8* wf; const bf16x8* wb; const float* bias;
-  const float* x;        // [M,40] embedded rows
-  const float* d_out;    // [M,out_ch]
-  int64_t M; int out_ch;
-  float* out;            // [M,out_ch]
-  void* acts; void* dz;
-  int64_t astride, zstride;
-};
+// index maps and pack description (ImgPack): mlp_arch2.h; ImgArgs: mlp_input2.h
+static_assert(LI::F_CHUNKS * RING_CHUNK == LI::F_TOTAL && LI::B_CHUNKS * RING_CHUNK == LI::B_PADDED, "whole ring chunks");
 
 template <bool STORE, class WS>
 __device__ __forceinline__ void fwd_tiles_img(const ImgArgs& a, WS& ws, int64_t tile0, int64_t ntiles, int lane) {
@@ -1127,29 +1079,7 @@ __global__ void __launch_bounds__(512, 2) mlp_img_bwd_ring_kernel(ImgArgs a) {
 // its 8 waves then run independently over sample tiles.  Same register-resident chain, same fragment-block stores,
 // same dW kernel (7 jobs); the chain additionally returns dL/d(input features) for the hash-grid backward.
 // ==========================================================================================
-__global__ void __launch_bounds__(256) pack_small_kernel(const float* __restrict__ p, bf16x8* __restrict__ wf,
-                                                         bf16x8* __restrict__ wb, float* __restrict__ bias) {
-  const int tid = blockIdx.x * 256 + threadIdx.x;
-  const int nf = LN::F_PADDED * 64, nb = LN::B_PADDED * 64;
-  if (tid < nf + nb) {
-    const bool fw = tid < nf;
-    const int t = fw ? tid : tid - nf, f = t >> 6, lane = t & 63, r = lane & 31, h = lane >> 5;
-    bf16x8 v;
-#pragma unroll
-    for (int j = 0; j < 8; ++j) v[j] = (__bf16)(fw ? fwd_src_small(p, f, r, h, j) : bwd_src_small(p, f, r, h, j));
-    (fw ? wf : wb)[t] = v;
-  } else if (tid < nf + nb + LN::BI_TOTAL) {
-    const int s = tid - nf - nb;
-    float v = 0.0f;
-    if (s < LN::BI_L1) v = p[LN::P_B0 + s];
-    else if (s < LN::BI_FEAT) v = p[LN::P_B1 + (s - LN::BI_L1)];
-    else if (s < LN::BI_ALPHA) v = p[LN::P_BF + (s - LN::BI_FEAT)];
-    else if (s < LN::BI_DIR) v = (s == LN::BI_ALPHA) ? p[LN::P_BA] : 0.0f;
-    else if (s < LN::BI_RGB) v = p[LN::P_BD + (s - LN::BI_DIR)];
-    else v = (s - LN::BI_RGB) < 3 ? p[LN::P_BR + (s - LN::BI_RGB)] : 0.0f;
-    bias[s] = v;
-  }
-}
+// index maps and pack description (SmallPack): mlp_arch2.h
 
 // weight source (3): the whole stream resident in LDS (copied once per workgroup)
 struct LdsW {
@@ -1164,64 +1094,7 @@ __device__ __forceinline__ void lds_load_stream(const bf16x8* __restrict__ w, co
   __syncthreads();
 }
 
-struct SmallArgs {
-  const bf16x8* wf; const bf16x8* wb; const float* bias;
-  const float* x;        // [M,48]: 32 position features | 16 direction features
-  const float* d_raw;    // [M,4]
-  int64_t M;
-  float* out;            // [M,4] raw
-  float* d_x;            // [M,32] dL/d(position features) or nullptr
-  void* acts; void* dz;
-  int64_t astride, zstride;
-  // fused configs[4] query: rows are computed in the kernel from rays / depths / hash tables (16 levels x 2 features)
-  const float* rays; const float* z; int n; const float* tables; uint32_t T; ResTab rt; float pos_scale, pos_offset;
-  const uint32_t* tables_h;   // fp16 shadow image of the tables (one 4-byte pair per entry) or nullptr: gathered instead of `tables`
-  // ray_major (inference of the fused query only): a 32-sample tile = ONE depth index of 32 ADJACENT RAYS instead of 32
-  // consecutive depths of one ray.  Neighbouring pixels' samples at the same depth are 0.0012 apart in the unit cube, so
-  // the 32 lanes of a gather instruction fall into the same or adjacent cells at every level below N_l ~ 800 (13 of 16),
-  // where 32 consecutive depths of one ray (0.021 apart) share cells only below N_l ~ 48.  Same values per sample.
-  int ray_major; int64_t B;
-  // per-level weights of nerf_ngp_query_fused_lw, read by the LW kernels only (last member: the other kernels' argument
-  // offsets are what they were)
-  LevelTab lw;
-};
-
-// B fragments of one sample straight from the hash tables and the view direction: lane (r, h) owns channels
-// kperm(ks, h, j) of k-step ks = levels 8 ks + 4 (j >> 2) + 2 h + ((j & 3) >> 1), feature j & 1, i.e. the two lanes of
-// a sample split the 16 levels between them; SH degree 3 = 16 channels = one k-step.
-// LW: feature = w[l] * interpolation in float32, ahead of the bf16 rounding; w[l] == 0: no gather, feature +0.
-template <bool HALF, bool LW>
-__device__ __forceinline__ void ngp_row_frags(const SmallArgs& a, int64_t m, int h, bf16x8 (&xin)[1][2], bf16x8 (&din)[1][1]) {
-  const float* rr = a.rays + (int64_t)((uint64_t)m / (unsigned)a.n) * NERF_RAY_STRIDE;
-  const float zv = a.z[m];
-  // render.py:142, then the scene box -> unit cube map (same two roundings as hash_common.h:point_of)
-  const float px = (rr[0] + zv * rr[3]) * a.pos_scale + a.pos_offset, py = (rr[1] + zv * rr[4]) * a.pos_scale + a.pos_offset;
-  const float pz = (rr[2] + zv * rr[5]) * a.pos_scale + a.pos_offset;
-  const uint32_t mask = a.T - 1;
-#pragma unroll
-  for (int ks = 0; ks < 2; ++ks)
-#pragma unroll
-    for (int q = 0; q < 2; ++q)
-#pragma unroll
-      for (int e = 0; e < 2; ++e) {
-        const int l = 8 * ks + 4 * q + 2 * h + e;
-        const Corners c = corners_of(px, py, pz, a.rt.res[l], mask);
-        if (LW) {
-          const float w = h ? a.lw.w[8 * ks + 4 * q + 2 + e] : a.lw.w[8 * ks + 4 * q + e];       // two scalars and a select
-          const FeatVec<2> fv = hash_level_lw<HALF>(a.tables + (size_t)l * a.T * 2, a.tables_h + (size_t)l * a.T, c, w);
-          xin[0][ks][4 * q + 2 * e] = (__bf16)fv.v[0];
-          xin[0][ks][4 * q + 2 * e + 1] = (__bf16)fv.v[1];
-        } else {
-          const FeatVec<2> fv = HALF ? hash_level_h(a.tables_h + (size_t)l * a.T, c) : hash_level<2>(a.tables + (size_t)l * a.T * 2, c);
-          xin[0][ks][4 * q + 2 * e] = (__bf16)fv.v[0];
-          xin[0][ks][4 * q + 2 * e + 1] = (__bf16)fv.v[1];
-        }
-      }
-  float sh[16];
-  sh_eval(rr[8], rr[9], rr[10], 3, sh);
-#pragma unroll
-  for (int j = 0; j < 8; ++j) din[0][0][j] = (__bf16)(h == 0 ? sh[8 * (j >> 2) + (j & 3)] : sh[8 * (j >> 2) + 4 + (j & 3)]);
-}
+// SmallArgs, the tile map and the fused row stage (ngp_row: B fragments straight from the hash tables): mlp_input2.h
 
 template <bool STORE, bool FUSED, bool LW = false>
 __global__ void __launch_bounds__(512) mlp_small_fwd_kernel(SmallArgs a) {
@@ -1235,26 +1108,18 @@ __global__ void __launch_bounds__(512) mlp_small_fwd_kernel(SmallArgs a) {
     int lane = lane0;
     asm volatile("" : "+v"(lane));        // fragment addresses are per-tile values: the 31 LDS reads are not hoisted (spills)
     const int r = lane & 31, h = lane >> 5;
-    int64_t m = tile0 * 32 + r;
-    bool valid = m < a.M;
-    if (rmaj) {                            // tile = (block of 32 rays, depth index): sample m = ray * n + depth
-      const int64_t rb = tile0 / a.n;
-      const int depth = (int)(tile0 - rb * a.n);
-      int64_t ray = rb * 32 + r;
-      valid = ray < a.B;
-      if (!valid) ray = a.B - 1;
-      m = ray * a.n + depth;
-    }
-    if (m >= a.M) m = a.M - 1;
-    bf16x8 xin[ST][2], din[ST][1];
+    const TileSample ts = small_tile_sample(a, tile0, r, rmaj);
+    const int64_t m = ts.m;
+    const bool valid = ts.valid;
+    bf16x8 in[3];                          // position k-steps 0, 1 | direction
     if (FUSED) {
-      if (a.tables_h) ngp_row_frags<true, LW>(a, m, h, xin, din);        // wave-uniform
-      else ngp_row_frags<false, LW>(a, m, h, xin, din);
+      if (a.tables_h) ngp_row<true, LW, CvtBf16>(a, m, h, in);        // wave-uniform
+      else ngp_row<false, LW, CvtBf16>(a, m, h, in);
     } else {
-      const float* row = a.x + m * LN::CIN;
-      row_pairs<CvtBf16>(row, 0, h, LN::CPOS, xin[0][0]); row_pairs<CvtBf16>(row, 1, h, LN::CPOS, xin[0][1]);
-      row_pairs<CvtBf16>(row + LN::CPOS, 0, h, LN::CDIR, din[0][0]);
+      small_row<CvtBf16>(a.x + m * LN::CIN, h, in);
     }
+    bf16x8 xin[ST][2], din[ST][1];
+    xin[0][0] = in[0]; xin[0][1] = in[1]; din[0][0] = in[2];
     int bad = nonfinite_flags<32>(nonfinite_bits(xin[0][0]) | nonfinite_bits(xin[0][1]), nonfinite_bits(din[0][0]));
     asm volatile("" : "+v"(bad));         // at the head of the tile (see fwd_tiles)
 #define SINK(slot0) FragSink<STORE>{a.acts, tile0, a.astride, slot0, r, h}
@@ -1465,12 +1330,12 @@ extern "C" int nerf_mlp_pack(const nerf_mlp_arch* arch, const float* params, voi
   float* bias = m.stream<float>(packed, S_BIAS);
   int rc;
   if (m.shape == Shape::Small) {
-    const int tot = (LN::F_PADDED + LN::B_PADDED) * 64 + LN::BI_TOTAL;
-    rc = launch<pack_small_kernel>("nerf_mlp_pack (2x64 model)", dim3((tot + 255) / 256), dim3(256), 0, s, params, wf, wb, bias);
+    rc = launch<pack_streams_kernel<SmallPack, CvtBf16, true>>("nerf_mlp_pack (2x64 model)", dim3(pack_blocks<SmallPack, true>()), dim3(256), 0, s,
+                                                               params, wf, wb, bias, 0);
     if (!rc && m.split()) rc = s16x::small_pack(params, m.stream<void>(packed, S_S16), s);
   } else if (m.shape == Shape::Image) {
-    const int tot = (LI::F_TOTAL + LI::B_PADDED) * 64 + LI::BI_TOTAL;
-    rc = launch<pack_img_kernel>("nerf_mlp_pack (image model)", dim3((tot + 255) / 256), dim3(256), 0, s, params, wf, wb, bias, m.out_ch);
+    rc = launch<pack_streams_kernel<ImgPack, CvtBf16, true>>("nerf_mlp_pack (image model)", dim3(pack_blocks<ImgPack, true>()), dim3(256), 0, s,
+                                                             params, wf, wb, bias, m.out_ch);
     if (!rc && m.split()) rc = s16x::img_pack(params, m.out_ch, m.stream<void>(packed, S_S16), s);
     if (!rc && m.prec == Prec::F32) rc = f32::pack(params, m.stream<void>(packed, S_F32), m.out_ch, s);
   } else {
@@ -1528,24 +1393,7 @@ static int launch_fwd(const Model& m, const void* packed, const float* x, const 
   }); });
 }
 
-static void img_args(ImgArgs& a, const Model& m, const void* packed) {
-  a.wf = m.stream<bf16x8>(packed, S_FWD);
-  a.wb = m.stream<bf16x8>(packed, S_BWD);
-  a.bias = m.stream<float>(packed, S_BIAS);
-  a.out_ch = m.out_ch; a.astride = m.astride(); a.zstride = m.zstride();
-  a.x = nullptr; a.d_out = nullptr; a.out = nullptr; a.acts = nullptr; a.dz = nullptr; a.M = 0;
-}
-
-static void small_args(SmallArgs& a, const Model& m, const void* packed) {
-  a.wf = m.stream<bf16x8>(packed, S_FWD);
-  a.wb = m.stream<bf16x8>(packed, S_BWD);
-  a.bias = m.stream<float>(packed, S_BIAS);
-  a.x = nullptr; a.d_raw = nullptr; a.out = nullptr; a.d_x = nullptr; a.acts = nullptr; a.dz = nullptr; a.M = 0;
-  a.astride = m.astride(); a.zstride = m.zstride();
-  a.rays = nullptr; a.z = nullptr; a.n = 1; a.tables = nullptr; a.tables_h = nullptr; a.T = 0; a.pos_scale = 1.0f; a.pos_offset = 0.0f;
-  a.ray_major = 0; a.B = 0;
-  for (int l = 0; l < 32; ++l) a.lw.w[l] = 1.0f;
-}
+// img_args / small_args (kernel arguments of the image / 2 x 64 model from its description): mlp_model.h
 
 // (defined behind nerf_mlp_forward_train: the kernel templates keep the order of first use they always had in the code object)
 static int view_forward(const Model& m, const void* packed, const float* x, const float* rays, const float* z, int64_t M, int n,
@@ -1558,12 +1406,10 @@ extern "C" int nerf_mlp_forward_train(const nerf_mlp_arch* arch, const void* pac
   NERF_REQUIRE(packed && x && out, NERF_E_NULL, "nerf_mlp_forward: NULL pointer");
   auto s = as_stream(stream);
   if (m.shape == Shape::Small) {
-    if (m.split())                             // split bf16: float32-class products (mlp_s16x.hip)
-      return s16x::small_forward(m.stream<void>(packed, S_S16), m.stream<float>(packed, S_BIAS), x, M, out, acts, m.astride(),
-                                 nullptr, s);
     SmallArgs a;
     small_args(a, m, packed);
     a.x = x; a.out = out; a.acts = acts; a.M = M;
+    if (m.split()) return s16x::small_forward(a, false, dim3(small_grid(small_tiles(a))), s);      // split bf16: float32-class products (mlp_s16x.hip)
     return with_bool(acts != nullptr, [&](auto store) {
       return launch<mlp_small_fwd_kernel<decltype(store)::value, false>>("mlp forward (2x64 model)", dim3(small_grid((M + 31) / 32)), dim3(512),
                                                                          LN::LDS_BYTES, s, a);
@@ -1572,12 +1418,10 @@ extern "C" int nerf_mlp_forward_train(const nerf_mlp_arch* arch, const void* pac
   if (m.shape == Shape::Image) {
     if (m.prec == Prec::F32)                   // float32 operands on the fp32 MFMA (mlp32.hip)
       return f32::forward(m.stream<void>(packed, S_F32), x, nullptr, nullptr, M, 1, 0, out, acts, m.out_ch, s);
-    if (m.split())
-      return s16x::img_forward(m.stream<void>(packed, S_S16), m.stream<float>(packed, S_BIAS), x, M, m.out_ch, out, acts,
-                               m.astride(), ring_wgs(), s);
     ImgArgs a;
     img_args(a, m, packed);
     a.x = x; a.out = out; a.acts = acts; a.M = M;
+    if (m.split()) return s16x::img_forward(a, ring_wgs(), s);
     return with_bool(acts != nullptr, [&](auto store) {
       constexpr bool ST = decltype(store)::value;
       return launch<mlp_img_fwd_ring_kernel<ST>, mlp_img_fwd_ring_kernel<!ST>>("mlp forward (image model)", dim3(ring_grid((M + 31) / 32)),
@@ -1746,23 +1590,17 @@ static int mlp_backward_impl(const nerf_mlp_arch* arch, const void* packed, cons
   // ---- 1. dZ chain
   int rc;
   if (m.shape == Shape::Small) {
-    if (m.split()) {
-      rc = s16x::small_backward_chain(m.stream<void>(packed, S_S16), acts, d_raw, M, dz, d_x, m.astride(), m.zstride(), s);
-    } else {
-      SmallArgs a;
-      small_args(a, m, packed);
-      a.d_raw = d_raw; a.acts = const_cast<void*>(acts); a.dz = dz; a.M = M; a.d_x = d_x;
-      rc = launch<mlp_small_bwd_kernel>("mlp backward chain (2x64 model)", dim3(small_grid(ntiles)), dim3(512), LN::LDS_BYTES, s, a);
-    }
+    SmallArgs a;
+    small_args(a, m, packed);
+    a.d_raw = d_raw; a.acts = const_cast<void*>(acts); a.dz = dz; a.M = M; a.d_x = d_x;
+    if (m.split()) rc = s16x::small_backward_chain(a, s);
+    else rc = launch<mlp_small_bwd_kernel>("mlp backward chain (2x64 model)", dim3(small_grid(ntiles)), dim3(512), LN::LDS_BYTES, s, a);
   } else if (m.shape == Shape::Image) {
-    if (m.split()) {
-      rc = s16x::img_backward_chain(m.stream<void>(packed, S_S16), acts, d_raw, M, m.out_ch, dz, m.astride(), m.zstride(), ring_wgs(), s);
-    } else {
-      ImgArgs a;
-      img_args(a, m, packed);
-      a.d_out = d_raw; a.acts = const_cast<void*>(acts); a.dz = dz; a.M = M;
-      rc = launch<mlp_img_bwd_ring_kernel>("mlp backward chain (image model)", dim3(ring_grid(ntiles)), dim3(512), RING_LDS_BYTES, s, a);
-    }
+    ImgArgs a;
+    img_args(a, m, packed);
+    a.d_out = d_raw; a.acts = const_cast<void*>(acts); a.dz = dz; a.M = M;
+    if (m.split()) rc = s16x::img_backward_chain(a, ring_wgs(), s);
+    else rc = launch<mlp_img_bwd_ring_kernel>("mlp backward chain (image model)", dim3(ring_grid(ntiles)), dim3(512), RING_LDS_BYTES, s, a);
   } else {
     rc = view_backward_chain(m, packed, acts, d_raw, M, dz, s);
     if (!rc && g_bwd_stage == 1) return NERF_OK;
@@ -1793,26 +1631,19 @@ static int ngp_query_fused_impl(const nerf_mlp_arch* arch, const void* packed, c
   LevelTab lt;
   if (lw_host)
     NERF_REQUIRE(level_tab_fill(lt, lw_host, L), NERF_E_SHAPE, "nerf_ngp_query_fused_lw: level weights must be finite and in [0, 1]");
-  if (m.split()) {              // reference tolerance: float32 gathers from the master tables (the fp16 shadow is a reduced-precision
-    s16x::SmallQuery q;         // image: not read in this mode), float32 interpolation, split-bf16 MLP (mlp_s16x.hip)
-    q.rays = rays; q.z = z; q.n = n; q.tables = tables; q.T = 1u << log2_T; q.pos_scale = pos_scale; q.pos_offset = pos_offset;
-    for (int l = 0; l < 32; ++l) q.res[l] = l < L ? (float)resolutions_host[l] : 0.0f;
-    q.B = B; q.ray_major = g_ngp_ray_major;
-    q.use_lw = lw_host != nullptr;
-    if (lw_host) for (int l = 0; l < 32; ++l) q.lw[l] = lt.w[l];
-    return s16x::small_forward(m.stream<void>(packed, S_S16), m.stream<float>(packed, S_BIAS), nullptr, M, raw, acts, m.astride(), &q,
-                               as_stream(stream));
-  }
   SmallArgs a;
   small_args(a, m, packed);
   a.out = raw; a.acts = acts; a.M = M; a.rays = rays; a.z = z; a.n = n; a.tables = tables; a.T = 1u << log2_T;
-  a.tables_h = static_cast<const uint32_t*>(tables_half);
   a.pos_scale = pos_scale; a.pos_offset = pos_offset;
-  for (int l = 0; l < 32; ++l) a.rt.res[l] = l < L ? (float)resolutions_host[l] : 0.0f;
-  a.B = B;
-  a.ray_major = (!acts && g_ngp_ray_major && B >= 32) ? 1 : 0;
-  const dim3 g(small_grid(a.ray_major ? ((B + 31) / 32) * (int64_t)n : (M + 31) / 32));
+  for (int l = 0; l < L; ++l) a.rt.res[l] = (float)resolutions_host[l];
   if (lw_host) a.lw = lt;
+  a.B = B;
+  a.ray_major = small_ray_major(acts != nullptr, g_ngp_ray_major, B);
+  const dim3 g(small_grid(small_tiles(a)));
+  // precision 22 is the reference's tolerance: float32 gathers from the master tables (the fp16 shadow is a reduced-precision
+  // image: not read in this mode), float32 interpolation, split-bf16 MLP (mlp_s16x.hip)
+  if (m.split()) return s16x::small_forward(a, lw_host != nullptr, g, as_stream(stream));
+  a.tables_h = static_cast<const uint32_t*>(tables_half);
   return with_bool(acts != nullptr, [&](auto store) { return with_bool(lw_host != nullptr, [&](auto lw) {
     return launch<mlp_small_fwd_kernel<decltype(store)::value, true, decltype(lw)::value>>(
         lw_host ? "nerf_ngp_query_fused_lw" : "nerf_ngp_query_fused", g, dim3(512), LN::LDS_BYTES, as_stream(stream), a);

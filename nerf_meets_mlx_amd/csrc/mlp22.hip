@@ -132,7 +132,7 @@ __global__ void __launch_bounds__(256) pack22_kernel(const float* __restrict__ p
     wf[(2 * fp) * 64 + lane] = hi;
     wf[(2 * fp + 1) * 64 + lane] = lo;
   } else if (t < PACK_THREADS) {
-    const int s = t - (F_PADDED / 2) * 64;                  // bias slots: numbering of the bf16 image (mlp.hip pack_part)
+    const int s = t - (F_PADDED / 2) * 64;                  // bias slots: numbering of the bf16 image (mlp_index.h: bias_index)
     float v = 0.0f;
     if (s < 2048) v = p[L::pb(s >> 8) + (s & 255)];
 #if NERF_F22_FOLD

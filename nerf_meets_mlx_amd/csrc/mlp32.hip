@@ -24,6 +24,7 @@
 //    revolution-sine of the bf16 path.
 #include "common.h"
 #include "mlp_params.h"
+#include "mlp_layout.h"
 #include "mlp_arch2.h"
 #include "mlp32.h"
 #include <type_traits>

@@ -23,7 +23,7 @@ constexpr int DWF_BLOCKS_F = 256 / DWF_ROWS, DWF_BLOCKS_D = 128 / DWF_ROWS;
 
 __device__ __forceinline__ double pair_value(const __bf16* __restrict__ wf, const FragElem& e) {      // hi + lo of one stream element
   FragElem hi = e, lo = e;
-  hi.f = 2 * e.f; lo.f = 2 * e.f + 1;                      // (hi, lo) fragment pairs in stream order (mlp_s16.hip: pack_s16_kernel)
+  hi.f = 2 * e.f; lo.f = 2 * e.f + 1;                      // (hi, lo) fragment pairs in stream order (mlp_pack.h: SplitBf16)
   return (double)(float)wf[frag_elem_offset(hi)] + (double)(float)wf[frag_elem_offset(lo)];
 }
 

@@ -6,19 +6,7 @@
 
 namespace nerf {
 
-// ------------------------------------------------------------------------------------------
-// weight packing sources: which master parameter sits in element j of lane (r, h) of fragment f of the 32x32x16 streams
-// ------------------------------------------------------------------------------------------
-// (the index arithmetic itself: fwd_index / bwd_index in mlp_index.h, shared with the host)
-__device__ inline float fwd_src(const float* __restrict__ p, int f, int r, int h, int j) {
-  const int i = fwd_index(f, r, h, j);
-  return i >= 0 ? p[i] : 0.0f;
-}
-// transposed stream: A rows = INPUT feature (32 kt + r), k index = OUTPUT feature nn
-__device__ inline float bwd_src(const float* __restrict__ p, int f, int r, int h, int j) {
-  const int i = bwd_index(f, r, h, j);
-  return i >= 0 ? p[i] : 0.0f;
-}
+// weight packing (which master parameter sits in element j of lane (r, h) of fragment f): mlp_index.h, mlp_arch2.h; mlp_pack.h
 
 // fragment block address: tile T, slot s, lane (r,h) at byte 32 r + 16 h.  Written as (uniform 64-bit tile base) +
 // (constant slot offset) + (32-bit lane offset) so that hipcc keeps the base in SGPRs.
@@ -95,6 +83,7 @@ struct PackBf16 {
 };
 // ... element by element, as the 32x32x16 chains convert their inputs (hipcc pairs the conversions itself, in another order)
 struct CvtBf16 {
+  static constexpr int FRAGS = 1;          // fragments per eight values (mlp_pack.h)
   static __device__ __forceinline__ void pack(const float (&v)[8], bf16x8& o) {
 #pragma unroll
     for (int j = 0; j < 8; ++j) o[j] = (__bf16)v[j];

@@ -1,6 +1,6 @@
 // Which master parameter sits where in the 32x32x16 weight fragment streams of the 8 x 256 view model, and back.  Pure integer
 // arithmetic without a HIP dependency, shared by host and device: nerf_mlp_pack fills the streams through fwd_index / bwd_index
-// (mlp_frag.h: fwd_src / bwd_src), the post step of the factored weight gradients (mlp_dwf.hip) finds W_F and W_D in the packed
+// (mlp_pack.h, by way of ViewPack below), the post step of the factored weight gradients (mlp_dwf.hip) finds W_F and W_D in the packed
 // split-bf16 image through fwd_elem, and a CPU test walks both directions against each other (tests/frag_index_check.cpp).
 #pragma once
 #if !defined(__HIPCC__) && !defined(__host__)
@@ -18,6 +18,8 @@ constexpr int F_TOTAL = 1184;
 // backward (transposed) weight stream
 constexpr int B_RGB = 0, B_DIR = 4, B_FA = 68, B_L7 = 204, B_L6 = 332, B_L5 = 460, B_L4 = 588;
 constexpr int B_TOTAL = 1100, B_PADDED = 1120;    // padded with zero fragments to whole 32-fragment ring chunks
+// fp32 bias slots: pos l at 256 l, then feature, alpha (one row of a 32-row tile), dir0, rgb (three rows)
+constexpr int BI_FEAT = 2048, BI_ALPHA = 2304, BI_DIR = 2336, BI_RGB = 2464, BI_TOTAL = 2496;
 }  // namespace L
 
 // element j of lane half h in k-step ks  <->  feature index
@@ -110,6 +112,29 @@ __host__ __device__ constexpr int bwd_index(int f, int r, int h, int j) {
   const int l = 7 - li, nn = kperm(ns, h, j), row = 32 * kt + r;
   if (l == 5) return L::P_W5 + nn * 319 + 63 + row;
   return L::pw(l) + nn * 256 + row;
+}
+
+// bias slot s -> offset of the master parameter, -1 = zero padding
+__host__ __device__ constexpr int bias_index(int s) {
+  if (s < L::BI_FEAT) return L::pb(s >> 8) + (s & 255);
+  if (s < L::BI_ALPHA) return L::P_BF + (s - L::BI_FEAT);
+  if (s < L::BI_DIR) return s == L::BI_ALPHA ? L::P_BA : -1;
+  if (s < L::BI_RGB) return L::P_BD + (s - L::BI_DIR);
+  return (s - L::BI_RGB) < 3 ? L::P_BR + (s - L::BI_RGB) : -1;
+}
+// What the pack routine (mlp_pack.h) needs to know of a model: fragment counts of its two streams, used and padded, its bias
+// slots, and the three maps.  (out_ch: the image model's; unused here)
+struct ViewPack {
+  static constexpr int F_TOTAL = L::F_TOTAL, F_PADDED = L::F_TOTAL, B_TOTAL = L::B_TOTAL, B_PADDED = L::B_PADDED, BI_TOTAL = L::BI_TOTAL;
+  static __host__ __device__ constexpr int fwd(int f, int r, int h, int j, int) { return fwd_index(f, r, h, j); }
+  static __host__ __device__ constexpr int bwd(int f, int r, int h, int j, int) { return bwd_index(f, r, h, j); }
+  static __host__ __device__ constexpr int bias(int s, int) { return bias_index(s); }
+};
+// element j of lane (r, h) of fragment f of S's padded forward (fw) or transposed stream: fragments behind the last used one are zero
+template <class S>
+__host__ __device__ constexpr int pack_index(bool fw, int f, int r, int h, int j, int out_ch) {
+  if (f >= (fw ? S::F_TOTAL : S::B_TOTAL)) return -1;
+  return fw ? S::fwd(f, r, h, j, out_ch) : S::bwd(f, r, h, j, out_ch);
 }
 
 // ------------------------------------------------------------------------------------------

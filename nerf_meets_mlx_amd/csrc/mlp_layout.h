@@ -14,8 +14,7 @@ namespace L {
 // float32 parameter offsets P_*: mlp_params.h (shared with the fp32 reference-precision kernels of mlp32.hip)
 
 // forward / backward weight streams F_*, B_* (1 KiB fragments in consumption order): mlp_index.h
-// fp32 bias slots
-constexpr int BI_FEAT = 2048, BI_ALPHA = 2304, BI_DIR = 2336, BI_RGB = 2464, BI_TOTAL = 2496;
+// fp32 bias slots BI_*: mlp_index.h
 constexpr int F16_TOTAL = 1172, F16_PADDED = 1184;   // forward stream of the 16x16x32 variant (inference only)
 constexpr int64_t F16_OFFSET = (int64_t)(F_TOTAL + B_PADDED) * 1024 + BI_TOTAL * 4;    // appended after the bias slots
 constexpr int64_t PACKED_BYTES = F16_OFFSET + (int64_t)F16_PADDED * 1024;

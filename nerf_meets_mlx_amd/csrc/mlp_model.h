@@ -2,9 +2,10 @@
 // points of mlp.hip need to know about it -- parameter count, byte offset of every stream in the packed buffer, fragment slots
 // per sample tile of the training stores, weight-gradient jobs, and the (slot, fragments) of each layer for the test hook.
 // A new model or precision is described HERE; the entry points hold no layout arithmetic of their own.  (Host only: no kernel
-// reads any of this; the kernels take the layouts from mlp_layout.h / mlp_arch2.h and the per-precision headers.)
+// reads any of this; the kernels take the layouts from mlp_layout.h / mlp_arch2.h and the per-precision headers.)  The kernel
+// arguments of the image and 2 x 64 models (mlp_input2.h) are filled here too, from the description: img_args / small_args.
 #pragma once
-#include "mlp_arch2.h"
+#include "mlp_input2.h"
 #include "mlp_frag.h"
 #include "mlp32.h"
 #include "mlp22.h"
@@ -183,6 +184,28 @@ inline Model resolve(const nerf_mlp_arch* a) {
   m.packed_bytes = end;
   m.ok = true;
   return m;
+}
+
+// Kernel arguments of the image / 2 x 64 model in the model's precision: the bf16 streams, or the (hi, lo) pair streams of a
+// precision-22 model (forward stream first), the shared fp32 bias slots, the tile strides; everything per call unset.
+template <class A>
+inline void weight_args(A& a, const Model& m, const void* packed, int split_f_frags) {
+  a.wf = m.stream<bf16x8>(packed, m.split() ? S_S16 : S_FWD);
+  a.wb = m.split() ? a.wf + (size_t)split_f_frags * 64 : m.stream<bf16x8>(packed, S_BWD);
+  a.bias = m.stream<float>(packed, S_BIAS);
+  a.astride = m.astride(); a.zstride = m.zstride();
+  a.x = nullptr; a.out = nullptr; a.acts = nullptr; a.dz = nullptr; a.M = 0;
+}
+inline void img_args(ImgArgs& a, const Model& m, const void* packed) {
+  weight_args(a, m, packed, s16x::IMG_F_FRAGS);
+  a.out_ch = m.out_ch; a.d_out = nullptr;
+}
+inline void small_args(SmallArgs& a, const Model& m, const void* packed) {
+  weight_args(a, m, packed, s16x::SM_F_FRAGS);
+  a.d_raw = nullptr; a.d_x = nullptr;
+  a.rays = nullptr; a.z = nullptr; a.n = 1; a.tables = nullptr; a.tables_h = nullptr; a.T = 0; a.pos_scale = 1.0f; a.pos_offset = 0.0f;
+  a.ray_major = 0; a.B = 0;
+  for (int l = 0; l < 32; ++l) { a.rt.res[l] = 0.0f; a.lw.w[l] = 1.0f; }
 }
 
 }  // namespace nerf

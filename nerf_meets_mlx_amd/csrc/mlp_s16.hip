@@ -17,6 +17,7 @@
 // 256 activation registers.  dW: 16 waves per workgroup as in mlp.hip, LDS stages of 16 samples (half a tile) so that four
 // stages of hi + lo operands fit the CU's 160 KiB.
 #include "mlp_s16_dev.h"
+#include "mlp_pack.h"
 #include "mlp_s16.h"
 
 // 1: the training forward re-reads its own stored encodings before pos5 / dir0 (48 registers less to carry through pos1..4; a
@@ -42,25 +43,11 @@ typedef RingW<B_CHUNKS, B_FRAGS, 4, NW, RING_CHUNK, RING_STAGES, true> BwdRing;
 
 
 // ------------------------------------------------------------------------------------------
-// packing: fp32 master parameters -> (hi, lo) bf16 fragment pairs in the 32x32x16 stream orders of mlp_frag.h
+// packing: fp32 master parameters -> (hi, lo) bf16 fragment pairs in the 32x32x16 stream orders of mlp_index.h (mlp_pack.h)
 // ------------------------------------------------------------------------------------------
-constexpr int PACK_PAIRS = L::F_TOTAL + B_PADDED / 2;    // 1184 forward + 1104 transposed (4 of them zero padding)
-__global__ void __launch_bounds__(256) pack_s16_kernel(const float* __restrict__ p, bf16x8* __restrict__ wf,
-                                                       bf16x8* __restrict__ wb) {
-  const int t = blockIdx.x * 256 + threadIdx.x;
-  if (t >= PACK_PAIRS * 64) return;
-  const int fp = t >> 6, lane = t & 63, r = lane & 31, h = lane >> 5;
-  const bool fw = fp < L::F_TOTAL;
-  const int f = fw ? fp : fp - L::F_TOTAL;
-  float v[8];
-#pragma unroll
-  for (int j = 0; j < 8; ++j) v[j] = fw ? fwd_src(p, f, r, h, j) : (f < L::B_TOTAL ? bwd_src(p, f, r, h, j) : 0.0f);
-  bf16x8 hi[1], lo[1];
-  split_slots<8>(v, hi, lo);
-  bf16x8* dst = fw ? wf : wb;
-  dst[(2 * f) * 64 + lane] = hi[0];
-  dst[(2 * f + 1) * 64 + lane] = lo[0];
-}
+// the transposed pair stream ends 1104 pairs in (4 of them zero padding), not at the bf16 stream's 1120
+struct ViewPairPack : ViewPack { static constexpr int B_PADDED = s16::B_PADDED / 2; };
+static_assert(ViewPairPack::B_PADDED >= L::B_TOTAL, "the padded stream holds every transposed fragment");
 
 // positional encodings, float32-accurate, straight into (hi, lo) B fragments: mlp_input.h (here: SinCodyWaite, SplitBf16)
 
@@ -661,9 +648,9 @@ __global__ void __launch_bounds__(64 * DW_WAVES) s16_dw_kernel(DwArgs a) {
 // ------------------------------------------------------------------------------------------
 
 int pack(const float* params, void* packed_s16, hipStream_t s) {
-  char* base = static_cast<char*>(packed_s16);
-  return launch<pack_s16_kernel>("nerf_mlp_pack (split-bf16 image)", dim3((PACK_PAIRS * 64 + 255) / 256), dim3(256), 0, s, params,
-                                 reinterpret_cast<bf16x8*>(base), reinterpret_cast<bf16x8*>(base + (size_t)F_FRAGS * 1024));
+  bf16x8* wf = static_cast<bf16x8*>(packed_s16);
+  return launch<pack_streams_kernel<ViewPairPack, SplitBf16, false>>("nerf_mlp_pack (split-bf16 image)", dim3(pack_blocks<ViewPairPack, false>()),
+                                                                     dim3(256), 0, s, params, wf, wf + (size_t)F_FRAGS * 64, nullptr, 0);
 }
 
 int forward(const void* packed_s16, const float* bias_slots, const float* x, const float* rays, const float* z, int64_t M,

@@ -36,6 +36,7 @@ __device__ __forceinline__ f32x16 mfma32(const bf16x8& a, const bf16x8& b, const
 
 // packer of the input stage (mlp_input.h): eight floats -> a (hi, lo) pair of bf16 B fragments
 struct SplitBf16 {
+  static constexpr int FRAGS = 2;
   static __device__ __forceinline__ void pack(const float (&v)[8], bf16x8& hi, bf16x8& lo) { split_slots<8>(v, &hi, &lo); }
 };
 

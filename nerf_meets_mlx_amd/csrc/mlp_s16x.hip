@@ -15,13 +15,25 @@
 // workgroup; in the fused query the hash features are gathered from the float32 master tables and interpolated in float32
 // (encoding/multi_hash.py:112-131) and enter the first layer as (hi, lo) pairs -- nothing is rounded to 8 bits anywhere.
 #include "mlp_s16_dev.h"
-#include "mlp_arch2.h"
-#include "hash_common.h"
+#include "mlp_input2.h"
+#include "mlp_pack.h"
 #include "mlp_s16x.h"
-#include "mlp_s16x_small.h"
 
 namespace nerf {
 namespace s16x {
+
+using s16::HL; using s16::split2; using s16::split_slots; using s16::mfma32; using s16::PairSink; using s16::NoPairSink; using s16::SplitBf16;
+
+template <bool STORE> struct SinkOf { typedef NoPairSink type; };
+template <> struct SinkOf<true> { typedef PairSink type; };
+template <bool STORE>
+__device__ __forceinline__ typename SinkOf<STORE>::type make_sink(void* base, int64_t tile, int64_t stride16, int slot0, int lo_off, int r, int h);
+template <>
+__device__ __forceinline__ PairSink make_sink<true>(void* base, int64_t tile, int64_t stride16, int slot0, int lo_off, int r, int h) {
+  return PairSink{base, tile, stride16, slot0, lo_off, r, h};
+}
+template <>
+__device__ __forceinline__ NoPairSink make_sink<false>(void*, int64_t, int64_t, int, int, int, int) { return NoPairSink{}; }
 
 static_assert(IMG_A_LO == LI::A_MASK && IMG_A_MASK == 2 * LI::A_MASK && IMG_A_SLOTS == IMG_A_MASK + 8, "image activation slots");
 static_assert(IMG_Z_LO == LI::Z_SLOTS && IMG_Z_SLOTS == 2 * LI::Z_SLOTS, "image dZ slots");
@@ -45,33 +57,7 @@ static_assert(IMG_F_CHUNKS * RING_CHUNK == IMG_F_FRAGS && IMG_B_CHUNKS * RING_CH
 typedef RingW<IMG_F_CHUNKS, IMG_F_FRAGS, NERF_S16X_GROUP, NW, RING_CHUNK, RING_STAGES, true> ImgFwdRing;
 typedef RingW<IMG_B_CHUNKS, IMG_B_FRAGS, 4, NW, RING_CHUNK, RING_STAGES, true> ImgBwdRing;
 
-constexpr int IMG_PACK_PAIRS = LI::F_TOTAL + LI::B_PADDED;
-__global__ void __launch_bounds__(256) pack_s16_img_kernel(const float* __restrict__ p, bf16x8* __restrict__ wf,
-                                                           bf16x8* __restrict__ wb, int out_ch) {
-  const int t = blockIdx.x * 256 + threadIdx.x;
-  if (t >= IMG_PACK_PAIRS * 64) return;
-  const int fp = t >> 6, lane = t & 63, r = lane & 31, h = lane >> 5;
-  const bool fw = fp < LI::F_TOTAL;
-  const int f = fw ? fp : fp - LI::F_TOTAL;
-  float v[8];
-#pragma unroll
-  for (int j = 0; j < 8; ++j) v[j] = fw ? fwd_src_img(p, f, r, h, j, out_ch) : (f < LI::B_TOTAL ? bwd_src_img(p, f, r, h, j, out_ch) : 0.0f);
-  bf16x8 hi[1], lo[1];
-  split_slots<8>(v, hi, lo);
-  bf16x8* dst = fw ? wf : wb;
-  dst[(2 * f) * 64 + lane] = hi[0];
-  dst[(2 * f + 1) * 64 + lane] = lo[0];
-}
-
-struct ImgArgs {
-  const bf16x8* wf; const bf16x8* wb; const float* bias;
-  const float* x;        // [M,40] embedded rows
-  const float* d_out;    // [M,out_ch]
-  int64_t M; int out_ch;
-  float* out;            // [M,out_ch]
-  void* acts; void* dz;
-  int64_t astride, zstride;
-};
+// index maps and pack description (ImgPack): mlp_arch2.h; ImgArgs: mlp_input2.h
 
 // All 9 layers for the wave's 32 samples.  Waves past the end compute on clamped inputs, store into the padding tiles of the
 // workspace and write no output, so every wave runs the same instruction stream (the ring needs it).
@@ -84,7 +70,7 @@ __device__ __forceinline__ void img_fwd_tiles(const ImgArgs& a, WS& ws, int64_t 
     int64_t m = tile * 32 + r; if (m >= a.M) m = a.M - 1;
     const float* row = a.x + m * LI::CIN;
 #pragma unroll
-    for (int ks = 0; ks < 3; ++ks) row_pairs<s16::SplitBf16>(row, ks, h, LI::CIN, xh[ks], xl[ks]);
+    for (int ks = 0; ks < 3; ++ks) row_pairs<SplitBf16>(row, ks, h, LI::CIN, xh[ks], xl[ks]);
   }
   if (STORE) {
     store_frags<3>(a.acts, tile0, a.astride, LI::A_X, xh, r, h);
@@ -216,21 +202,77 @@ __global__ void __launch_bounds__(64 * NW) s16_img_bwd_kernel(ImgArgs a) {
 // ==========================================================================================
 // 2 x 64 model
 // ==========================================================================================
-__global__ void __launch_bounds__(256) pack_s16_small_kernel(const float* __restrict__ p, bf16x8* __restrict__ wf,
-                                                             bf16x8* __restrict__ wb) {
-  const int t = blockIdx.x * 256 + threadIdx.x;
-  if (t >= (LN::F_PADDED + LN::B_PADDED) * 64) return;
-  const int fp = t >> 6, lane = t & 63, r = lane & 31, h = lane >> 5;
-  const bool fw = fp < LN::F_PADDED;
-  const int f = fw ? fp : fp - LN::F_PADDED;
-  float v[8];
+// index maps and pack description (SmallPack): mlp_arch2.h; SmallArgs, tile map, fused row stage: mlp_input2.h
+constexpr int SM_STREAM_BYTES = 64 * 1024;               // 64 fragments of 1 KiB: (hi, lo) pairs of one direction's stream
+constexpr int SM_LDS_BYTES = SM_STREAM_BYTES + LN::BI_TOTAL * 4;
+// weight source: the whole pair stream resident in LDS (copied once per workgroup); biases behind it
+struct LdsPairW {
+  __device__ __forceinline__ bf16x8 frag(int f, int lane) { return *reinterpret_cast<const bf16x8*>(ring_smem + f * 1024 + lane * 16); }
+  __device__ __forceinline__ void note_stores(int) {}
+  __device__ __forceinline__ float4 bias4(int slot) { return *reinterpret_cast<const float4*>(ring_smem + SM_STREAM_BYTES + slot * 4); }
+};
+__device__ __forceinline__ void lds_load_pairs(const bf16x8* __restrict__ w, const float* __restrict__ bias) {
+  for (int i = threadIdx.x; i < 64 * 64; i += blockDim.x) *reinterpret_cast<bf16x8*>(ring_smem + i * 16) = w[i];
+  if (bias)
+    for (int i = threadIdx.x; i < LN::BI_TOTAL; i += blockDim.x) *reinterpret_cast<float*>(ring_smem + SM_STREAM_BYTES + 4 * i) = bias[i];
+  __syncthreads();
+}
+
+
+template <bool STORE, bool FUSED, bool LW = false>
+__global__ void __launch_bounds__(512) s16_small_fwd_kernel(SmallArgs a) {
+  lds_load_pairs(a.wf, a.bias);
+  const int lane0 = threadIdx.x & 63, wv = threadIdx.x >> 6;
+  const bool rmaj = FUSED && !STORE && a.ray_major;
+  const int64_t ntiles = rmaj ? ((a.B + 31) >> 5) * a.n : (a.M + 31) >> 5;
+  LdsPairW ws;
+  for (int64_t tile0 = (int64_t)blockIdx.x * 8 + wv; tile0 < ntiles; tile0 += (int64_t)gridDim.x * 8) {
+    int lane = lane0;
+    asm volatile("" : "+v"(lane));        // fragment addresses are per-tile values: the LDS reads are not hoisted (spills)
+    const int r = lane & 31, h = lane >> 5;
+    const TileSample ts = small_tile_sample(a, tile0, r, rmaj);
+    const int64_t m = ts.m;
+    const bool valid = ts.valid;
+    bf16x8 inh[3], inl[3];                 // position k-steps 0, 1 | direction
+    if (FUSED) ngp_row<false, LW, SplitBf16>(a, m, h, inh, inl);       // the float32 master tables (mlp_input2.h: tables_h)
+    else small_row<SplitBf16>(a.x + m * LN::CIN, h, inh, inl);
+    bf16x8 xh[2], xl[2], dh[1], dl[1];
+    xh[0] = inh[0]; xh[1] = inh[1]; dh[0] = inh[2];
+    xl[0] = inl[0]; xl[1] = inl[1]; dl[0] = inl[2];
+#define SINK(slot0) make_sink<STORE>(a.acts, tile0, a.astride, slot0, SM_A_LO, r, h)
+#define MASK_STORE(layer) do { if (STORE) *reinterpret_cast<u32x4*>(frag_ptr(a.acts, tile0, a.astride, SM_A_MASK + (layer), r, h)) = mk; } while (0)
+    if (STORE) {
+      store_frags<2>(a.acts, tile0, a.astride, LN::A_X, xh, r, h); store_frags<2>(a.acts, tile0, a.astride, SM_A_LO + LN::A_X, xl, r, h);
+      store_frags<1>(a.acts, tile0, a.astride, LN::A_DX, dh, r, h); store_frags<1>(a.acts, tile0, a.astride, SM_A_LO + LN::A_DX, dl, r, h);
+    }
+    u32x4 mk;
+    bf16x8 h0h[4], h0l[4], h1h[4], h1l[4], fth[4], ftl[4];
+    mk = u32x4{0u, 0u, 0u, 0u};
+    s16::layer_fwd<2, 2, true, STORE>(ws, LN::F_L0, LN::BI_L0, xh, xl, h0h, h0l, mk, lane, SINK(LN::A_H0));
+    MASK_STORE(0);
+    mk = u32x4{0u, 0u, 0u, 0u};
+    s16::layer_fwd<4, 2, true, STORE>(ws, LN::F_L1, LN::BI_L1, h0h, h0l, h1h, h1l, mk, lane, SINK(LN::A_H1));
+    MASK_STORE(1);
+    s16::layer_fwd<4, 2, false, false>(ws, LN::F_FA, LN::BI_FEAT, h1h, h1l, fth, ftl, mk, lane, SINK(LN::A_FEAT));     // feature: no activation
+    const float alpha = s16::head<4>(ws, LN::F_FA + 8, LN::BI_ALPHA, h1h, h1l, lane)[0];
+    bf16x8 hdh[2], hdl[2];
+    {
+      bf16x8 cth[5], ctl[5];
 #pragma unroll
-  for (int j = 0; j < 8; ++j) v[j] = fw ? fwd_src_small(p, f, r, h, j) : bwd_src_small(p, f, r, h, j);
-  bf16x8 hi[1], lo[1];
-  split_slots<8>(v, hi, lo);
-  bf16x8* dst = fw ? wf : wb;
-  dst[(2 * f) * 64 + lane] = hi[0];
-  dst[(2 * f + 1) * 64 + lane] = lo[0];
+      for (int k = 0; k < 4; ++k) { cth[k] = fth[k]; ctl[k] = ftl[k]; }
+      cth[4] = dh[0]; ctl[4] = dl[0];
+      mk = u32x4{0u, 0u, 0u, 0u};
+      s16::layer_fwd<5, 1, true, STORE>(ws, LN::F_DIR, LN::BI_DIR, cth, ctl, hdh, hdl, mk, lane, SINK(LN::A_HD));
+      MASK_STORE(2);
+    }
+    const f32x16 rgb = s16::head<2>(ws, LN::F_RGB, LN::BI_RGB, hdh, hdl, lane);
+    if (h == 0 && valid) {
+      float4 o; o.x = rgb[0]; o.y = rgb[1]; o.z = rgb[2]; o.w = alpha;
+      *reinterpret_cast<float4*>(a.out + m * 4) = o;
+    }
+#undef SINK
+#undef MASK_STORE
+  }
 }
 
 __global__ void __launch_bounds__(512) s16_small_bwd_kernel(SmallArgs a) {
@@ -296,90 +338,46 @@ __global__ void __launch_bounds__(512) s16_small_bwd_kernel(SmallArgs a) {
 // host side
 // ==========================================================================================
 int img_pack(const float* params, int out_ch, void* packed, hipStream_t s) {
-  char* base = static_cast<char*>(packed);
-  return launch<pack_s16_img_kernel>("nerf_mlp_pack (image model, split-bf16 image)", dim3((IMG_PACK_PAIRS * 64 + 255) / 256), dim3(256), 0, s,
-                                     params, reinterpret_cast<bf16x8*>(base), reinterpret_cast<bf16x8*>(base + (size_t)IMG_F_FRAGS * 1024), out_ch);
+  bf16x8* wf = static_cast<bf16x8*>(packed);
+  return launch<pack_streams_kernel<ImgPack, SplitBf16, false>>("nerf_mlp_pack (image model, split-bf16 image)", dim3(pack_blocks<ImgPack, false>()),
+                                                                dim3(256), 0, s, params, wf, wf + (size_t)IMG_F_FRAGS * 64, nullptr, out_ch);
 }
 
-static void img_fill(ImgArgs& a, const void* packed, const float* bias_slots, int out_ch, int64_t astride16, int64_t zstride16) {
-  const char* base = static_cast<const char*>(packed);
-  a.wf = reinterpret_cast<const bf16x8*>(base);
-  a.wb = reinterpret_cast<const bf16x8*>(base + (size_t)IMG_F_FRAGS * 1024);
-  a.bias = bias_slots; a.out_ch = out_ch; a.astride = astride16; a.zstride = zstride16;
-  a.x = nullptr; a.d_out = nullptr; a.out = nullptr; a.acts = nullptr; a.dz = nullptr; a.M = 0;
-}
-
-int img_forward(const void* packed, const float* bias_slots, const float* x, int64_t M, int out_ch, float* out, void* acts,
-                int64_t astride16, int persistent_wgs, hipStream_t s) {
-  ImgArgs a;
-  img_fill(a, packed, bias_slots, out_ch, astride16, 0);
-  a.x = x; a.out = out; a.acts = acts; a.M = M;
-  const int64_t nsuper = ((M + 31) / 32 + NW - 1) / NW;
-  return with_bool(acts != nullptr, [&](auto store) {
+int img_forward(const ImgArgs& a, int persistent_wgs, hipStream_t s) {
+  const int64_t nsuper = ((a.M + 31) / 32 + NW - 1) / NW;
+  return with_bool(a.acts != nullptr, [&](auto store) {
     constexpr bool ST = decltype(store)::value;
     return launch<s16_img_fwd_kernel<ST>, s16_img_fwd_kernel<!ST>>("mlp forward (image model, split bf16)", dim3(persistent_grid(nsuper, persistent_wgs)),
                                                                    dim3(64 * NW), ImgFwdRing::LDS_BYTES, s, a);
   });
 }
 
-int img_backward_chain(const void* packed, const void* acts, const float* d_out, int64_t M, int out_ch, void* dz,
-                       int64_t astride16, int64_t zstride16, int persistent_wgs, hipStream_t s) {
-  ImgArgs a;
-  img_fill(a, packed, nullptr, out_ch, astride16, zstride16);
-  a.d_out = d_out; a.acts = const_cast<void*>(acts); a.dz = dz; a.M = M;
-  const int64_t nsuper = ((M + 31) / 32 + NW - 1) / NW;
+int img_backward_chain(const ImgArgs& a, int persistent_wgs, hipStream_t s) {
+  const int64_t nsuper = ((a.M + 31) / 32 + NW - 1) / NW;
   return launch<s16_img_bwd_kernel>("mlp backward chain (image model, split bf16)", dim3(persistent_grid(nsuper, persistent_wgs)), dim3(64 * NW),
                                     ImgBwdRing::LDS_BYTES, s, a);
 }
 
 int small_pack(const float* params, void* packed, hipStream_t s) {
-  char* base = static_cast<char*>(packed);
-  return launch<pack_s16_small_kernel>("nerf_mlp_pack (2x64 model, split-bf16 image)", dim3(((LN::F_PADDED + LN::B_PADDED) * 64 + 255) / 256), dim3(256),
-                                       0, s, params, reinterpret_cast<bf16x8*>(base), reinterpret_cast<bf16x8*>(base + (size_t)SM_F_FRAGS * 1024));
+  bf16x8* wf = static_cast<bf16x8*>(packed);
+  return launch<pack_streams_kernel<SmallPack, SplitBf16, false>>("nerf_mlp_pack (2x64 model, split-bf16 image)", dim3(pack_blocks<SmallPack, false>()),
+                                                                  dim3(256), 0, s, params, wf, wf + (size_t)SM_F_FRAGS * 64, nullptr, 0);
 }
 
-static void small_fill(SmallArgs& a, const void* packed, const float* bias_slots, int64_t astride16, int64_t zstride16) {
-  const char* base = static_cast<const char*>(packed);
-  a.wf = reinterpret_cast<const bf16x8*>(base);
-  a.wb = reinterpret_cast<const bf16x8*>(base + (size_t)SM_F_FRAGS * 1024);
-  a.bias = bias_slots;
-  a.x = nullptr; a.d_raw = nullptr; a.out = nullptr; a.d_x = nullptr; a.acts = nullptr; a.dz = nullptr; a.M = 0;
-  a.astride = astride16; a.zstride = zstride16;
-  a.rays = nullptr; a.z = nullptr; a.n = 1; a.tables = nullptr; a.T = 0; a.pos_scale = 1.0f; a.pos_offset = 0.0f;
-  a.ray_major = 0; a.B = 0;
-  for (int l = 0; l < 32; ++l) { a.rt.res[l] = 0.0f; a.lw.w[l] = 1.0f; }
-}
-
-int small_forward(const void* packed, const float* bias_slots, const float* x, int64_t M, float* out, void* acts,
-                  int64_t astride16, const SmallQuery* q, hipStream_t s) {
-  SmallArgs a;
-  small_fill(a, packed, bias_slots, astride16, 0);
-  a.x = x; a.out = out; a.acts = acts; a.M = M;
-  int64_t ntiles = (M + 31) / 32;
-  if (q && q->rays) {
-    a.rays = q->rays; a.z = q->z; a.n = q->n; a.tables = q->tables; a.T = q->T; a.pos_scale = q->pos_scale; a.pos_offset = q->pos_offset;
-    for (int l = 0; l < 32; ++l) a.rt.res[l] = q->res[l];
-    a.B = q->B;
-    a.ray_major = (!acts && q->ray_major && q->B >= 32) ? 1 : 0;
-    if (a.ray_major) ntiles = ((q->B + 31) / 32) * (int64_t)q->n;
-  }
-  const dim3 g(small_grid(ntiles));
+int small_forward(const SmallArgs& a, bool lw, dim3 grid, hipStream_t s) {
   const bool fused = a.rays != nullptr;
-  if (fused && q->use_lw) {                  // nerf_ngp_query_fused_lw: the level-weight kernels
-    for (int l = 0; l < 32; ++l) a.lw.w[l] = q->lw[l];
-    return small_forward_lw(a, g, s);          // mlp_s16x_lw.hip
-  }
-  return with_bool(acts != nullptr, [&](auto store) { return with_bool(fused, [&](auto fu) {
-    return launch<s16_small_fwd_kernel<decltype(store)::value, decltype(fu)::value>>("mlp forward (2x64 model, split bf16)", g, dim3(512), SM_LDS_BYTES, s, a);
+  if (fused && lw)                           // nerf_ngp_query_fused_lw: the level-weight kernels
+    return with_bool(a.acts != nullptr, [&](auto store) {
+      return launch<s16_small_fwd_kernel<decltype(store)::value, true, true>>("mlp forward (2x64 model, split bf16, level weights)", grid, dim3(512),
+                                                                              SM_LDS_BYTES, s, a);
+    });
+  return with_bool(a.acts != nullptr, [&](auto store) { return with_bool(fused, [&](auto fu) {
+    return launch<s16_small_fwd_kernel<decltype(store)::value, decltype(fu)::value>>("mlp forward (2x64 model, split bf16)", grid, dim3(512), SM_LDS_BYTES, s, a);
   }); });
 }
 
-int small_backward_chain(const void* packed, const void* acts, const float* d_raw, int64_t M, void* dz, float* d_x,
-                         int64_t astride16, int64_t zstride16, hipStream_t s) {
-  SmallArgs a;
-  small_fill(a, packed, nullptr, astride16, zstride16);
-  a.d_raw = d_raw; a.acts = const_cast<void*>(acts); a.dz = dz; a.M = M; a.d_x = d_x;
-  return launch<s16_small_bwd_kernel>("mlp backward chain (2x64 model, split bf16)", dim3(small_grid((M + 31) / 32)), dim3(512), SM_LDS_BYTES, s, a);
+int small_backward_chain(const SmallArgs& a, hipStream_t s) {
+  return launch<s16_small_bwd_kernel>("mlp backward chain (2x64 model, split bf16)", dim3(small_grid((a.M + 31) / 32)), dim3(512), SM_LDS_BYTES, s, a);
 }
 
 }  // namespace s16x

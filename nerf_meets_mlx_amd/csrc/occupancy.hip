@@ -29,7 +29,7 @@ __device__ __forceinline__ int cell_1d(float u, float R) {
 }
 
 // the sample's cell index ix + R (iy + R iz), or -1 outside the box; the position is computed with exactly the roundings of the
-// hash-grid kernels (hash_common.h point_of, mlp.hip ngp_row_frags): (o + z d) * pos_scale + pos_offset, one rounding per op
+// hash-grid kernels (hash_common.h point_of, mlp_input2.h ngp_row): (o + z d) * pos_scale + pos_offset, one rounding per op
 __device__ __forceinline__ int64_t cell_of(const float* __restrict__ rr, float zv, float pos_scale, float pos_offset, int log2R) {
   const float R = (float)(1 << log2R);
   const int ix = cell_1d((rr[0] + zv * rr[3]) * pos_scale + pos_offset, R);

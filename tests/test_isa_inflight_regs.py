@@ -103,7 +103,7 @@ def test_shipped_split_kernels_passed_the_build_time_scans():
     # none between the head and the end of a pass, where a scratch reload would drain the weight ring), nowhere else
     edge = {"mlp22_fwd_kernelILi1ELi3E": 6}
     for name, kernels, ring in (("mlp22_m0_scan.txt", 4, 3), ("mlp_s16_m0_scan.txt", 6, 5), ("mlp_dww_m0_scan.txt", 2, 2),
-                                ("mlp_s16x_m0_scan.txt", 10, 3)):
+                                ("mlp_s16x_m0_scan.txt", 12, 3)):
         path = os.path.join(build, name)
         assert os.path.exists(path), f"{name} missing: the Makefile rule of the split kernels did not run"
         rows = [ln for ln in open(path) if "LDS-DMA M0 writes" in ln]

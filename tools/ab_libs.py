@@ -7,7 +7,8 @@
     python tools/ab_libs.py --models tools/diag/libnerf_A.so default
         every MLP model (view / image / 2x64 in each of their precisions) through pack, training forward and backward at M = 65 and
         8193 (the embedded-row entry; the view model's rows also through the inference forward), plus the fused view-model query at
-        freq_mode 0 and 1 and the hash-grid queries at B = 64, n = 3 and 64, on seeded inputs: sha256 of the output, the packed
+        freq_mode 0 and 1 and the hash-grid queries (plain, with level weights, with an fp16 shadow of the tables) at B = 64 and 33,
+        n = 3 and 64, "ngp_ray_major" 1 and 0, on seeded inputs: sha256 of the output, the packed
         buffer, the activation store (it holds the stored encodings), the dZ store (without the split-K partial slots), the
         gradients and d_x.  Exit 1 unless every digest is the same in every library.
 Every child runs under a time limit, and after a child that failed or ran out of time no further child is started."""
@@ -90,24 +91,29 @@ for n in (3, 64):
             N.check(lib.nerf_query_fused(a, N.ptr(packed), N.ptr(rays), N.ptr(z), B, n, freq_mode, N.ptr(raw), N.ptr(acts) if train else None, N.stream()))
             torch.cuda.synchronize()
             res[f"query view{prec} n={n} freq_mode={freq_mode} {'train' if train else 'infer'}"] = {"out": sha(raw), "acts": sha(acts)}
-    for prec in (16, 22):                          # nerf_ngp_query_fused / _lw on float32 tables
-        g = torch.Generator().manual_seed(11 * prec + n)
+    for prec, Bq, ray_major in [(p, b, r) for p in (16, 22) for b in (64, 33) for r in (1, 0)]:      # nerf_ngp_query_fused / _lw / _h
+        g = torch.Generator().manual_seed(11 * prec + n + (0 if Bq == 64 else Bq))
         arch, a, params, packed = packed_model("small", prec, g)
-        rays, z = rays_z(g, B, n)
+        rays, z = rays_z(g, Bq, n)
         tables = (rnd(g, 16 * (1 << 14) * 2) * 0.1).to(dev)
+        shadow = tables.half()                     # the fp16 image: one 4-byte pair per entry (precision 22 ignores it)
         reso = (C.c_int * 16)(*[int(16 * (2048 / 16) ** (l / 15)) for l in range(16)])
         lw = (C.c_float * 16)(*[1.0] * 12 + [0.75, 0.5, 0.25, 0.0])
+        N.check(lib.nerf_set_option(b"ngp_ray_major", ray_major))
         for train in (False, True):
-            for weighted in (False, True):
-                acts, raw = zeros(lib.nerf_mlp_acts_bytes(a, B * n)), zeros(B * n * 4, torch.float32)
+            for entry in ("", " lw", " h"):
+                acts, raw = zeros(lib.nerf_mlp_acts_bytes(a, Bq * n)), zeros(Bq * n * 4, torch.float32)
                 tail = (3, 1.0 / 12.0, 0.5, N.ptr(raw), N.ptr(acts) if train else None, N.stream())
-                if weighted:
-                    N.check(lib.nerf_ngp_query_fused_lw(a, N.ptr(packed), N.ptr(rays), N.ptr(z), B, n, N.ptr(tables), None, 16, 14, 2, reso, lw, *tail))
+                if entry == " lw":
+                    N.check(lib.nerf_ngp_query_fused_lw(a, N.ptr(packed), N.ptr(rays), N.ptr(z), Bq, n, N.ptr(tables), None, 16, 14, 2, reso, lw, *tail))
+                elif entry == " h":
+                    N.check(lib.nerf_ngp_query_fused_h(a, N.ptr(packed), N.ptr(rays), N.ptr(z), Bq, n, N.ptr(tables), N.ptr(shadow), 16, 14, 2, reso, *tail))
                 else:
-                    N.check(lib.nerf_ngp_query_fused(a, N.ptr(packed), N.ptr(rays), N.ptr(z), B, n, N.ptr(tables), 16, 14, 2, reso, *tail))
+                    N.check(lib.nerf_ngp_query_fused(a, N.ptr(packed), N.ptr(rays), N.ptr(z), Bq, n, N.ptr(tables), 16, 14, 2, reso, *tail))
                 torch.cuda.synchronize()
                 assert bool(torch.isfinite(raw).all()), (prec, n)
-                res[f"query small{prec} n={n} {'train' if train else 'infer'}{' lw' if weighted else ''}"] = {"out": sha(raw), "acts": sha(acts)}
+                res[f"query small{prec} B={Bq} n={n} ray_major={ray_major} {'train' if train else 'infer'}{entry}"] = {"out": sha(raw), "acts": sha(acts)}
+        N.check(lib.nerf_set_option(b"ngp_ray_major", 1))
 print(json.dumps(res))
 '''
 ap = argparse.ArgumentParser(); ap.add_argument("libs", nargs="+"); ap.add_argument("--rounds", type=int, default=None); ap.add_argument("--precision", type=int, default=22)
