@@ -735,6 +735,74 @@ int nerf_tsdf_integrate(float* D, float* Wt, uint8_t* flags, int res, const floa
                         float acc_min, float far, int carve, void* stream);
 int nerf_tsdf_volume(const float* D, const float* Wt, const uint8_t* flags, int res, int min_views, float* vol_out, void* stream);
 
+/* ---------------------------------------------------------------- mesh simplification (no reference counterpart)
+ * Vertex clustering (Rossignac-Borrel) with quadric placement (Lindstrom's out-of-core simplification): the decimation step
+ * behind marching cubes.  Additive: NERF_ABI_VERSION stays 3.  All arithmetic is IEEE double, one rounding per operation, in
+ * exactly the order and grouping written here, unless it says int64; tests/_simplify_ref.py reproduces every output bit for bit.
+ *   input     verts [V, 3] float32, faces [F, 3] int32, normals [V, 3] float32, colors [V, 3] float32 or NULL; box lo[3] < hi[3]
+ *             (host floats, finite); grid G, 2 <= G <= NERF_MESH_MAX_RES; 0 <= V, F <= 2^24; min(V, G^3) <= 2^21 (the bound on
+ *             the cluster count that is known without a host read: cluster ids must fit the 21-bit fields of the face key).
+ *             Outside these ranges: NERF_E_SHAPE; NULL: NERF_E_NULL.  V = 0 or F = 0: the empty mesh, nothing is launched.
+ *   cells     ext_a = (double)hi_a - (double)lo_a; c_a = ext_a / G; inv_a = G / ext_a; t_a = ((double)v_a - lo_a) * inv_a;
+ *             q_a = min(max(floor(t_a), 0), G - 1); key = (q_z G + q_y) G + q_x.  A vertex is invalid when some t_a is not
+ *             finite (a non-finite coordinate always is): it joins no cluster, and every face that uses it is dropped.  A face
+ *             with an index outside [0, V) is dropped too, and nothing is read through that index.
+ *   clusters  the occupied cells, numbered in ascending key order; K of them.
+ *   sums      exact int64, independent of the arrival order.  fix(x, L, s) = (int64)rint(min(max(x, -L), L) * s), 0 for a NaN x
+ *             (rint: to nearest, ties to even).  Local coordinates of a point with lattice coordinates t in the cluster of cell
+ *             q: u_a = t_a - (q_a + 0.5).  Per cluster, over its vertices: n = the count; S_a = sum fix(u_a, 64, 2^32) (the clamp
+ *             only touches vertices 64 cells outside the box); N_a = sum fix(normal_a, 256, 2^30), a non-finite component
+ *             counting as 0; with colours C_a = sum rint(min(max(color_a, 0), 1) * 2^30), NaN counting as 0.
+ *   quadrics  for every face with three valid corners (also one that turns out degenerate or annihilated), once for every
+ *             distinct cluster among its corners, in that cluster's local coordinates u0, u1, u2 of the three corners:
+ *             e1 = u1 - u0, e2 = u2 - u0, n = (e1y e2z - e1z e2y, e1z e2x - e1x e2z, e1x e2y - e1y e2x),
+ *             d = -((nx u0x + ny u0y) + nz u0z); the nine sums Q = (Axx, Axy, Axz, Ayy, Ayz, Azz, bx, by, bz) receive
+ *             fix(x, 64, 2^32) for x = nx nx, nx ny, nx nz, ny ny, ny nz, nz nz, nx d, ny d, nz d: area^2-weighted.  The clamp
+ *             and the limit on F keep every sum inside int64.
+ *   placement ubar_a = S_a / 2^32 / n.  A.. and b. below are the sums / 2^32.  With NERF_SIMPLIFY_MEAN, or when
+ *             tr = (Axx + Ayy) + Azz <= 0: x = ubar.  Otherwise mu = (tr / 3) * 2^-10, and (A + mu I) x = mu ubar - b by Cramer's
+ *             rule: a00 = Axx + mu, a01 = Axy, a02 = Axz, a11 = Ayy + mu, a12 = Ayz, a22 = Azz + mu; r_a = mu ubar_a - b_a;
+ *             c00 = a11 a22 - a12 a12, c01 = a02 a12 - a01 a22, c02 = a01 a12 - a02 a11, c11 = a00 a22 - a02 a02,
+ *             c12 = a01 a02 - a00 a12, c22 = a00 a11 - a01 a01; det = (a00 c00 + a01 c01) + a02 c02;
+ *             x0 = ((c00 r0 + c01 r1) + c02 r2) / det, x1 = ((c01 r0 + c11 r1) + c12 r2) / det,
+ *             x2 = ((c02 r0 + c12 r1) + c22 r2) / det.  x is taken when all three are finite and |x_a| <= 0.5, else x = ubar.
+ *             The mu term pulls towards the mean: it decides the position along a flat face or a straight edge, where A alone is
+ *             singular.  Vertex: (float)(lo_a + ((q_a + 0.5) + x_a) * c_a).
+ *   normals   s_a = N_a / 2^30, len = sqrt((sx sx + sy sy) + sz sz); (float)(s_a / len) when len > 0, else 0.
+ *   colours   (float)(C_a / 2^30 / n).
+ *   faces     every corner becomes its cluster; a face with two equal corners is dropped.  Among the remaining faces on one
+ *             vertex set, p with one orientation and m with the other, the first min(p, m) of each orientation in input order are
+ *             dropped: opposite faces annihilate, a one-voxel-thick sheet vanishes.  Survivors keep their corner order and their
+ *             input order.
+ *   compact   clusters that no surviving face uses are dropped, the others keep ascending key order, faces are renumbered: no
+ *             isolated vertex; if every directed edge of the input occurs as often as its reverse, so does every one of the output.
+ * Calls, with the same (V, faces, F, box, G) and workspace throughout:
+ *   nerf_simplify_cluster  keys, occupancy bit mask over G^3 with per-word prefix counts, ranks, the sums (64-bit integer
+ *                          atomics), and per face tri_keys int64 [F]: (lo << 42) | (mid << 21) | hi of its sorted cluster triple,
+ *                          INT64_MAX for a dropped face.  Its orientation stays in the workspace.
+ *   (the caller)           a STABLE ascending sort of tri_keys: sorted_keys [F] and perm int64 [F], sorted_keys[i] = tri_keys[perm[i]].
+ *   nerf_simplify_count    survivors inside the sorted runs in constant work per face (one scan carries the run heads and one
+ *                          orientation's prefix; a run of any length costs its length), used clusters, both compactions'
+ *                          counts.  totals int64 [3] = (V', F', K): the one host read.
+ *   nerf_simplify_write    verts_out [V', 3], normals_out [V', 3], colors_out [V', 3] (NULL without input colours), color_rows
+ *                          [V', 11] or NULL (the rows of nerf_mesh_write_vertices: [x, -n, 0, 0, -n]), faces_out [F', 3].  Nothing
+ *                          is written past V_out vertices or F_out faces.
+ * No float atomics, every output element has one writer: bit-reproducible, and independent of the order of the input's vertices
+ * and faces up to the order of the output faces.  workspace: nerf_simplify_workspace_bytes(V, F, G) bytes (-1 for arguments out
+ * of range), kept from the cluster call to the write call; its content on entry is unspecified.  All argument checks run before
+ * any device work.
+ * Not done: no edge-collapse decimation to a target face count, no texture atlas, no guarantee of manifoldness after clustering. */
+#define NERF_SIMPLIFY_MEAN 0
+#define NERF_SIMPLIFY_QUADRIC 1
+int64_t nerf_simplify_workspace_bytes(int64_t V, int64_t F, int grid);
+int nerf_simplify_cluster(const float* verts, const float* normals, const float* colors, int64_t V, const int32_t* faces, int64_t F,
+                          const float* lo_host, const float* hi_host, int grid, void* workspace, int64_t* tri_keys, void* stream);
+int nerf_simplify_count(const int64_t* sorted_keys, const int64_t* perm, int64_t V, const int32_t* faces, int64_t F, int grid,
+                        void* workspace, int64_t* totals, void* stream);
+int nerf_simplify_write(int64_t V, const int32_t* faces, int64_t F, const float* lo_host, const float* hi_host, int grid,
+                        int placement, void* workspace, int64_t V_out, int64_t F_out, float* verts_out, float* normals_out,
+                        float* colors_out, float* color_rows, int32_t* faces_out, void* stream);
+
 /* ---------------------------------------------------------------- fused renderer (a14 / a18)
  * replaces: rendering/render.py:164-241 render_rays_eval (coarse pass, importance sampling, sort, second pass)
  * as ONE call that enqueues the fixed kernel sequence on `stream`: nerf_sample_coarse -> nerf_query_fused ->

@@ -111,6 +111,11 @@ SIGNATURES = {
     "nerf_tsdf_integrate": (_I, [_P, _P, _P, _I, C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_float), _I, _I, _I, _P, _P,
                                 _F, _F, _F, _I, _P]),
     "nerf_tsdf_volume": (_I, [_P, _P, _P, _I, _I, _P, _P]),
+    "nerf_simplify_workspace_bytes": (_I64, [_I64, _I64, _I]),
+    "nerf_simplify_cluster": (_I, [_P, _P, _P, _I64, _P, _I64, C.POINTER(C.c_float), C.POINTER(C.c_float), _I, _P, _P, _P]),
+    "nerf_simplify_count": (_I, [_P, _P, _I64, _P, _I64, _I, _P, _P, _P]),
+    "nerf_simplify_write": (_I, [_I64, _P, _I64, C.POINTER(C.c_float), C.POINTER(C.c_float), _I, _I, _P, _I64, _I64, _P, _P, _P, _P,
+                                _P, _P]),
 }
 
 

@@ -18,6 +18,10 @@ section 14).  The reference has no such export; this is Instant-NGP's.
   * `TSDFVolume(resolution, lo, hi, trunc)` fuses rendered depth / opacity maps of posed cameras into a truncated signed distance
     volume on the same lattice (nerf_tsdf_integrate, 16 views per launch); `.volume()` is a volume for everything above at
     iso = 0 (include/nerf_hip.h "TSDF fusion").  `NGPTrainer.extract_mesh_tsdf` renders, fuses and meshes.
+  * `simplify(mesh, grid, lo, hi, placement)` decimates a mesh by vertex clustering on a `grid`^3 lattice of the box, one vertex
+    per occupied cell placed by the cell's quadric (box corners and edges survive) or at the mean; opposite faces that land on
+    the same three cells annihilate, so one-voxel-thick sheets vanish (include/nerf_hip.h "mesh simplification", DESIGN.md
+    section 27).  `extract(..., simplify_grid, simplify_placement)` runs it between marching cubes and the colour query.
   * `write_ply` writes a binary little-endian PLY.
 """
 import ctypes as C
@@ -36,6 +40,9 @@ MAX_OPENING_RADIUS = 16      # NERF_MORPH_MAX_RADIUS
 TSDF_MAX_VIEWS = 16          # NERF_TSDF_MAX_VIEWS
 CHUNK = 1 << 19              # lattice points (or vertices) per query, as OccupancyGrid.update
 RELU, EXP = 0, 1             # NERF_OCC_RELU / NERF_OCC_EXP
+PLACEMENTS = {"mean": 0, "quadric": 1}   # NERF_SIMPLIFY_MEAN / NERF_SIMPLIFY_QUADRIC
+SIMPLIFY_MAX_ITEMS = 1 << 24  # vertices, faces
+SIMPLIFY_MAX_CLUSTERS = 1 << 21
 
 
 class Mesh(NamedTuple):
@@ -370,20 +377,110 @@ def vertex_colors(query, rows: torch.Tensor, chunk: int = CHUNK) -> torch.Tensor
     return out
 
 
+def check_simplify_grid(grid) -> int:
+    """simplify_grid as an int; ValueError for a bool, a non-integral value or one outside {0} + [2, MAX_RES] (0: no
+    simplification)."""
+    if isinstance(grid, bool) or not isinstance(grid, numbers.Integral) or not (int(grid) == 0 or 2 <= int(grid) <= MAX_RES):
+        raise ValueError(f"simplify_grid must be 0 or an int in [2, {MAX_RES}], got {grid!r}")
+    return int(grid)
+
+
+def check_simplify_args(mesh, grid, lo: Sequence[float], hi: Sequence[float], placement="quadric"):
+    """(grid, lo [3], hi [3], placement code) as (int, float lists, int); ValueError for a grid that is not an int in
+    [2, MAX_RES], a placement other than "mean" / "quadric", a box with lo >= hi or a non-finite corner, or a mesh whose tensors
+    are not contiguous verts float32 [V, 3], faces int32 [F, 3], normals float32 [V, 3] and colors None or float32 [V, 3] on one
+    device, with V, F <= 2^24 and min(V, grid^3) <= 2^21."""
+    if check_simplify_grid(grid) < 2:
+        raise ValueError(f"simplify grid must be an int in [2, {MAX_RES}], got {grid!r}")
+    grid, lo, hi, _ = check_mesh_args(int(grid), lo, hi)
+    if not isinstance(placement, str) or placement not in PLACEMENTS:
+        raise ValueError(f"simplify placement must be one of {sorted(PLACEMENTS)}, got {placement!r}")
+    if not isinstance(mesh, Mesh):
+        raise ValueError(f"simplify: need an engine.mesh.Mesh, got {type(mesh).__name__}")
+
+    def ok(t, dtype, rows=None):
+        return torch.is_tensor(t) and t.dtype == dtype and t.dim() == 2 and t.shape[1] == 3 and t.is_contiguous() \
+            and (rows is None or t.shape[0] == rows) and t.device == mesh.verts.device
+    if not ok(mesh.verts, torch.float32):
+        raise ValueError("simplify: verts must be a contiguous float32 [V, 3] tensor")
+    V = mesh.verts.shape[0]
+    if not ok(mesh.faces, torch.int32):
+        raise ValueError("simplify: faces must be a contiguous int32 [F, 3] tensor on the vertices' device")
+    if not ok(mesh.normals, torch.float32, V):
+        raise ValueError("simplify: normals must be a contiguous float32 [V, 3] tensor on the vertices' device")
+    if mesh.colors is not None and not ok(mesh.colors, torch.float32, V):
+        raise ValueError("simplify: colors must be None or a contiguous float32 [V, 3] tensor on the vertices' device")
+    F = mesh.faces.shape[0]
+    if V > SIMPLIFY_MAX_ITEMS or F > SIMPLIFY_MAX_ITEMS:
+        raise ValueError(f"simplify: at most 2^24 vertices and faces, got {V} and {F}")
+    if min(V, grid ** 3) > SIMPLIFY_MAX_CLUSTERS:
+        raise ValueError(f"simplify: min(V, grid^3) = {min(V, grid ** 3)} possible clusters exceed 2^21; use a coarser grid")
+    return grid, lo, hi, PLACEMENTS[placement]
+
+
+def _simplify(mesh: Mesh, grid, lo, hi, placement, color_rows: bool):
+    G, lo, hi, code = check_simplify_args(mesh, grid, lo, hi, placement)
+    dev = mesh.verts.device
+    V, F = mesh.verts.shape[0], mesh.faces.shape[0]
+    L = N.lib()
+    clo, chi = _box(lo, hi)
+    ws = torch.empty(L.nerf_simplify_workspace_bytes(V, F, G), dtype=torch.uint8, device=dev)
+    keys = torch.empty(F, dtype=torch.int64, device=dev)
+    tot = torch.empty(3, dtype=torch.int64, device=dev)
+    N.check(L.nerf_simplify_cluster(N.ptr(mesh.verts), N.ptr(mesh.normals), N.ptr(mesh.colors), V, N.ptr(mesh.faces), F, clo, chi,
+                                    G, N.ptr(ws), N.ptr(keys), N.stream()))
+    skeys, perm = torch.sort(keys, stable=True)               # plumbing between two of our launches: groups faces by vertex set
+    N.check(L.nerf_simplify_count(N.ptr(skeys), N.ptr(perm), V, N.ptr(mesh.faces), F, G, N.ptr(ws), N.ptr(tot), N.stream()))
+    V2, F2, _ = tot.tolist()                                  # the one host read
+    verts = torch.empty(V2, 3, dtype=torch.float32, device=dev)
+    normals = torch.empty(V2, 3, dtype=torch.float32, device=dev)
+    colors = torch.empty(V2, 3, dtype=torch.float32, device=dev) if mesh.colors is not None else None
+    rows = torch.empty(V2, 11, dtype=torch.float32, device=dev) if color_rows else None
+    faces = torch.empty(F2, 3, dtype=torch.int32, device=dev)
+    if V2 or F2:
+        N.check(L.nerf_simplify_write(V, N.ptr(mesh.faces), F, clo, chi, G, code, N.ptr(ws), V2, F2, N.ptr(verts), N.ptr(normals),
+                                      N.ptr(colors), N.ptr(rows), N.ptr(faces), N.stream()))
+    return Mesh(verts, faces, normals, colors), rows
+
+
+def simplify(mesh: Mesh, grid: int, lo, hi, placement: str = "quadric") -> Mesh:
+    """The mesh clustered on the `grid`^3 cells of the box [lo, hi]: one vertex per occupied cell that a surviving face uses, at
+    the minimiser of the cell's area^2-weighted plane quadric pulled slightly towards the mean ("quadric") or at the mean of the
+    cell's vertices ("mean"); normals are the normalised sums, colours (when the input has them, else None) the means.  Faces
+    with two corners in one cell go, and faces of opposite orientation on the same three cells cancel in pairs
+    (nerf_simplify_cluster, a stable torch.sort of the face keys, nerf_simplify_count, one read of (V', F') to the host,
+    nerf_simplify_write).  Bit-reproducible and independent of the order of the input's vertices and faces."""
+    return _simplify(mesh, grid, lo, hi, placement, False)[0]
+
+
 def extract(query, activation: int, resolution: int, threshold: float, lo, hi, colors: bool = True, device="cuda",
-            min_component: int = 0, largest_only: bool = False, opening_radius: int = 0) -> Mesh:
+            min_component: int = 0, largest_only: bool = False, opening_radius: int = 0, simplify_grid: int = 0,
+            simplify_placement: str = "quadric") -> Mesh:
     """density_volume -> (with opening_radius > 0: open_components; else with min_component > 1 or largest_only:
-    filter_components) -> marching_cubes at `threshold` -> (optionally) vertex colours, queried on the filtered mesh's rows.
-    With opening_radius > 0 `min_component` counts core voxels (open_components).  With the defaults neither is called."""
+    filter_components) -> marching_cubes at `threshold` -> (with simplify_grid > 0: simplify on that grid of the box) ->
+    (optionally) vertex colours, queried on the final mesh's rows: the field is asked once per vertex that is kept.
+    With opening_radius > 0 `min_component` counts core voxels (open_components).  With the defaults none of them is called."""
     check_mesh_args(resolution, lo, hi, threshold)
     min_component, largest_only = check_component_args(min_component, largest_only, resolution)
     opening_radius = check_opening_args(opening_radius)
+    simplify_grid = check_simplify_grid(simplify_grid)
+    if simplify_placement not in PLACEMENTS:
+        raise ValueError(f"simplify placement must be one of {sorted(PLACEMENTS)}, got {simplify_placement!r}")
     vol = density_volume(query, activation, resolution, lo, hi, device=device)
     if opening_radius > 0:
         vol = open_components(vol, threshold, opening_radius, min_component, largest_only)
     elif min_component > 1 or largest_only:
         vol = filter_components(vol, threshold, min_component, largest_only)
-    mesh, rows = _marching_cubes(vol, threshold, lo, hi, colors)
+    return mesh_volume(query, vol, threshold, lo, hi, colors, simplify_grid, simplify_placement)
+
+
+def mesh_volume(query, vol, iso, lo, hi, colors: bool, simplify_grid: int = 0, simplify_placement: str = "quadric") -> Mesh:
+    """marching_cubes of `vol` at `iso` -> (with simplify_grid > 0: simplify) -> (with `colors`) vertex_colors of `query` on the
+    final mesh's rows [x, -n, 0, 0, -n].  With simplify_grid 0 the calls are those of marching cubes and the colour query alone."""
+    if simplify_grid > 0:
+        mesh, rows = _simplify(_marching_cubes(vol, iso, lo, hi, False)[0], simplify_grid, lo, hi, simplify_placement, colors)
+    else:
+        mesh, rows = _marching_cubes(vol, iso, lo, hi, colors)
     if not colors:
         return mesh
     return mesh._replace(colors=vertex_colors(query, rows))

@@ -25,6 +25,12 @@ training poses (default: all), fused into a TSDF (engine.mesh.TSDFVolume, --tsdf
 F and the same geometry figures, the mean opacity of the rendered maps, and the device ms of the renders, the integrate
 launches, the finish and marching cubes.
 
+With --simplify G (repeatable), one more line per G and meshed volume (the density mesh, the TSDF mesh, every filtered and opened
+arm): the mesh clustered on the G^3 cells of the box with quadric and with mean placement -- V, F -> V', F',
+the clusters, the device ms of the simplifier alone (cluster, the sort, count with the host read, write) and the sort's share of
+it, and the geometry figures of the simplified vertices (the share within h of a box face, the count beyond 2 h; h is the
+marching-cubes lattice's) beside the input mesh's.
+
     rocprofv3 --kernel-trace --output-format csv -d DIR -o mesh -- python tools/ngp_mesh.py --ckpt /tmp/ngp.npz --reps 1 --no-ply
     python tools/ngp_mesh.py --stats DIR/.../mesh_kernel_trace.csv --from profiles/ngp_mesh.jsonl --out profiles/ngp_mesh_kernels.jsonl
 
@@ -153,6 +159,71 @@ def _opening_timed(vol, iso, radius, min_component, largest_only):
             est.tolist() + rst.tolist())
 
 
+def _simplify_timed(m, G, lo, hi, placement):
+    """engine.mesh.simplify as its calls, each between device events: (Mesh, clusters, [cluster, sort, count + the host read,
+    write] ms)."""
+    import ctypes as C
+    from nerf_meets_mlx_amd import _native as N
+    from nerf_meets_mlx_amd.engine import mesh
+    L = N.lib()
+    G, lo, hi, code = mesh.check_simplify_args(m, G, lo, hi, placement)
+    dev = m.verts.device
+    V, F = m.verts.shape[0], m.faces.shape[0]
+    clo, chi = (C.c_float * 3)(*lo), (C.c_float * 3)(*hi)
+    ws = torch.empty(L.nerf_simplify_workspace_bytes(V, F, G), dtype=torch.uint8, device=dev)
+    keys = torch.empty(F, dtype=torch.int64, device=dev)
+    tot = torch.empty(3, dtype=torch.int64, device=dev)
+    e = [torch.cuda.Event(enable_timing=True) for _ in range(5)]
+    e[0].record()
+    N.check(L.nerf_simplify_cluster(N.ptr(m.verts), N.ptr(m.normals), N.ptr(m.colors), V, N.ptr(m.faces), F, clo, chi, G, N.ptr(ws),
+                                    N.ptr(keys), N.stream()))
+    e[1].record()
+    skeys, perm = torch.sort(keys, stable=True)
+    e[2].record()
+    N.check(L.nerf_simplify_count(N.ptr(skeys), N.ptr(perm), V, N.ptr(m.faces), F, G, N.ptr(ws), N.ptr(tot), N.stream()))
+    V2, F2, K = tot.tolist()
+    e[3].record()
+    verts = torch.empty(V2, 3, dtype=torch.float32, device=dev)
+    normals = torch.empty(V2, 3, dtype=torch.float32, device=dev)
+    colors = torch.empty(V2, 3, dtype=torch.float32, device=dev) if m.colors is not None else None
+    faces = torch.empty(F2, 3, dtype=torch.int32, device=dev)
+    if V2 or F2:
+        N.check(L.nerf_simplify_write(V, N.ptr(m.faces), F, clo, chi, G, code, N.ptr(ws), V2, F2, N.ptr(verts), N.ptr(normals),
+                                      N.ptr(colors), None, N.ptr(faces), N.stream()))
+    e[4].record()
+    torch.cuda.synchronize()
+    return mesh.Mesh(verts, faces, normals, colors), K, [e[k].elapsed_time(e[k + 1]) for k in range(4)]
+
+
+def _simplify_arms(m, source, R, lo, hi, a, rec, bound, boxes, extra=None):
+    """One JSON line per --simplify G for the mesh `m` of the volume `source`."""
+    out = []
+    if m.verts.shape[0] == 0 or m.faces.shape[0] == 0:
+        return out
+    geo_in = _geometry(m.verts, R, bound, boxes)
+    for G in a.simplify or []:
+        arm = {"tool": "ngp_mesh simplify", "source": source, "R": R, "grid": G, "iters": rec["iters"], "seed": rec["seed"],
+               "V": int(m.verts.shape[0]), "F": int(m.faces.shape[0]), "geometry_in": geo_in,
+               "marching_cubes_ms": rec.get("marching_cubes_ms"), "device": rec["device"], **(extra or {})}
+        for placement in ("quadric", "mean"):
+            ts = []
+            _simplify_timed(m, G, lo, hi, placement)                      # warm: the sort's first call allocates
+            for _ in range(a.reps):
+                sm, K, ms = _simplify_timed(m, G, lo, hi, placement)
+                ts.append(ms)
+            t = np.mean(np.array(ts), 0)
+            arm[placement] = {"V_out": int(sm.verts.shape[0]), "F_out": int(sm.faces.shape[0]), "clusters": K,
+                              "simplify_ms": float(t.sum()), "cluster_ms": float(t[0]), "sort_ms": float(t[1]),
+                              "count_ms": float(t[2]), "write_ms": float(t[3]), "sort_share": float(t[1] / t.sum()),
+                              "simplify_ms_range": [float(np.sum(x)) for x in (min(ts, key=sum), max(ts, key=sum))],
+                              "geometry": _geometry(sm.verts, R, bound, boxes)}
+            del sm
+        print(json.dumps(arm), flush=True)
+        out.append(arm)
+    torch.cuda.empty_cache()
+    return out
+
+
 def _tsdf_arm(tr, mesh, R, lo, hi, a, rec, bound, boxes):
     """The TSDF export of the same field as its stages, each between device events (the last of --reps runs is kept)."""
     poses = tr.poses if a.tsdf_views is None else tr.poses[:a.tsdf_views]
@@ -183,9 +254,9 @@ def _tsdf_arm(tr, mesh, R, lo, hi, a, rec, bound, boxes):
            "render_ms": float(np.mean(t_ren)), "integrate_ms": float(np.mean(t_int)), "finish_ms": float(np.mean(t_fin)),
            "marching_cubes_ms": float(np.mean(t_mc)), "integrate_launches": -(-len(poses) // mesh.TSDF_MAX_VIEWS),
            "state_MB": R ** 3 * 9 / 1e6, "device": rec["device"]}
-    del tsdf, vol, m, maps, depth, acc
+    del tsdf, vol, maps, depth, acc
     torch.cuda.empty_cache()
-    return out
+    return out, m
 
 
 def _teacher_volume(R, lo, hi, dev):
@@ -241,6 +312,9 @@ def main():
     ap.add_argument("--tsdf-trunc", type=float, default=None, help="truncation in world units (default: 4 voxels)")
     ap.add_argument("--tsdf-acc-min", type=float, default=0.5, help="a ray with less opacity carves instead of observing a surface")
     ap.add_argument("--tsdf-views", type=int, default=None, help="fuse the first N training poses (default: all)")
+    ap.add_argument("--simplify", type=int, action="append", default=None,
+                    help="also cluster every mesh on a grid of this size (DESIGN.md section 27); repeatable: one JSON line per "
+                         "grid and meshed volume")
     ap.add_argument("--ckpt", default=None, help="load this checkpoint instead of training")
     ap.add_argument("--save-ckpt", default=None, help="save the trained state here")
     ap.add_argument("--out", default=None, help="append the JSON lines to this file")
@@ -312,14 +386,17 @@ def main():
         if not a.no_ply and R == a.ply_res:
             with tempfile.TemporaryDirectory() as d:
                 rec.update(_ply_check(m, os.path.join(d, "mesh.ply")))
-        del vol, m, rows, col
-        torch.cuda.empty_cache()
         print(json.dumps(rec), flush=True)
         lines.append(rec)
+        lines += _simplify_arms(m._replace(colors=None), "density", R, lo, hi, a, rec, bound, boxes)
+        del vol, m, rows, col
+        torch.cuda.empty_cache()
         if a.tsdf:
-            trec = _tsdf_arm(tr, mesh, R, lo, hi, a, rec, bound, boxes)
+            trec, tm = _tsdf_arm(tr, mesh, R, lo, hi, a, rec, bound, boxes)
             print(json.dumps(trec), flush=True)
             lines.append(trec)
+            lines += _simplify_arms(tm, "tsdf", R, lo, hi, a, {**rec, "marching_cubes_ms": trec["marching_cubes_ms"]}, bound, boxes)
+            del tm
         arms = a.min_component if a.min_component else ([0] if a.largest_only else [])
         for m_min in arms:
             vol = mesh.density_volume(query, act, R, lo, hi, device=dev)
@@ -345,10 +422,12 @@ def main():
                    "label_ms": float(t_ccl[0]), "sizes_ms": float(t_ccl[1]), "filter_ms": float(t_ccl[2]),
                    "marching_cubes_ms": float(np.mean(t_fmc)), "density_volume_ms": rec["density_volume_ms"],
                    "device": rec["device"]}
-            del comps, fvol, fm
-            torch.cuda.empty_cache()
             print(json.dumps(arm), flush=True)
             lines.append(arm)
+            lines += _simplify_arms(fm, "components", R, lo, hi, a, {**rec, "marching_cubes_ms": arm["marching_cubes_ms"]}, bound,
+                                    boxes, {"min_component": m_min, "largest_only": bool(a.largest_only)})
+            del comps, fvol, fm
+            torch.cuda.empty_cache()
             for r in [r for r in (a.opening_radius or []) if r > 0]:
                 t_open, t_omc = [], []
                 for _ in range(a.reps):
@@ -375,10 +454,12 @@ def main():
                         "filter_core_ms": float(t_open[3]), "reconstruct_ms": float(t_open[4]),
                         "marching_cubes_ms": float(np.mean(t_omc)), "label_ms": arm["label_ms"], "sizes_ms": arm["sizes_ms"],
                         "filter_ms": arm["filter_ms"], "density_volume_ms": rec["density_volume_ms"], "device": rec["device"]}
-                del comps, ovol, om
-                torch.cuda.empty_cache()
                 print(json.dumps(orec), flush=True)
                 lines.append(orec)
+                lines += _simplify_arms(om, "opening", R, lo, hi, a, {**rec, "marching_cubes_ms": orec["marching_cubes_ms"]}, bound,
+                                        boxes, {"opening_radius": r, "min_component": m_min, "largest_only": bool(a.largest_only)})
+                del comps, ovol, om
+                torch.cuda.empty_cache()
             del vol
             torch.cuda.empty_cache()
     if a.out:
@@ -438,7 +519,7 @@ def stats(a):
     gx = col.get("grid_size_x", col.get("grid_size"))
     groups = {}
     for r in rows:
-        m = re.search(r"(mesh_\w+_kernel|ccl_\w+_kernel|morph_\w+_kernel|tsdf_\w+_kernel|occ_cull_scan_kernel|occ_merge_exp_kernel)", r[name_k])
+        m = re.search(r"(mesh_\w+_kernel|ccl_\w+_kernel|morph_\w+_kernel|tsdf_\w+_kernel|simp_\w+_kernel|occ_cull_scan_kernel|occ_merge_exp_kernel)", r[name_k])
         if not m:
             continue
         k = m.group(1)
@@ -449,7 +530,9 @@ def stats(a):
             R = next((R for R in runs if _morph_grid(k, R) == grid), None)
             groups.setdefault((k, R), []).append((int(r[e_k]) - int(r[s_k])) * 1e-3)
             continue
-        if k in ("mesh_points_kernel", "occ_merge_exp_kernel", "occ_cull_scan_kernel", "ccl_finish_kernel"):
+        if k.startswith("simp_"):                      # sized by the mesh: one lane per vertex or face of the run at R; else pooled
+            R = next((R for R, run in runs.items() if grid in (-(-run["V"] // BLOCK) * BLOCK, -(-run["F"] // BLOCK) * BLOCK)), None)
+        elif k in ("mesh_points_kernel", "occ_merge_exp_kernel", "occ_cull_scan_kernel", "ccl_finish_kernel"):
             R = None                                                       # chunked / one workgroup: pooled per kernel
         else:
             R = next((R for R in runs if -(-R ** 3 // BLOCK) * BLOCK == grid), None)
