@@ -4,15 +4,11 @@
 // array), so a component's root is its smallest linear index whatever the scheduling: every output is bit-reproducible.  The
 // launch sequence depends on R alone and nothing is read on the host.  Every loop that follows parents or retries a union
 // strictly lowers an index per iteration (parent[x] <= x throughout), so none can spin.  All HBM- or atomic-bound; bytes per
-// voxel above each kernel.
-#include <cmath>
-
-#include "common.h"
+// voxel above each kernel.  Indexing, checks and the voxels of a workgroup: lattice.h.
+#include "lattice.h"
 
 namespace nerf {
 namespace {
-
-constexpr int CCL_BLOCK = 256;                      // voxels per workgroup, x fastest (as mesh.hip)
 
 __device__ __forceinline__ int ld_parent(const int* parent, int x) {
   return __hip_atomic_load(parent + x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -51,12 +47,11 @@ __device__ __forceinline__ void unite(int* parent, int a, int b) {
 // ---- init: 4 B of volume read, 4 B of parent written per voxel.  An inside voxel's parent is the first voxel of its run along x
 // inside the workgroup (runs end at the row's end: i = R - 1 and the next row's i = 0 are adjacent in memory, not neighbours);
 // an outside voxel's is -1.  Run starts by a max-scan over the workgroup's lanes.
-__global__ void __launch_bounds__(CCL_BLOCK) ccl_init_kernel(const float* __restrict__ vol, int R, float iso, int* __restrict__ parent) {
-  __shared__ int sh_in[CCL_BLOCK];
-  __shared__ int sh_w[CCL_BLOCK / 64];
+__global__ void __launch_bounds__(LATTICE_BLOCK) ccl_init_kernel(const float* __restrict__ vol, int R, float iso, int* __restrict__ parent) {
+  __shared__ int sh_in[LATTICE_BLOCK];
+  __shared__ int sh_w[LATTICE_BLOCK / 64];
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-  const int64_t n3 = (int64_t)R * R * R;
-  const int64_t lg = (int64_t)blockIdx.x * CCL_BLOCK + tid;
+  const int64_t n3 = lattice_n3(R), lg = lattice_lane();
   const int l = (int)lg;
   const bool inside = lg < n3 && vol[lg < n3 ? l : 0] > iso;
   sh_in[tid] = inside ? 1 : 0;
@@ -78,19 +73,19 @@ __global__ void __launch_bounds__(CCL_BLOCK) ccl_init_kernel(const float* __rest
 // q = p - R is implied when p - 1 and q - 1 are inside too: p ~ p - 1 and q ~ q - 1 along x, and p - 1 joins q - 1 itself (or
 // hands it down the same way); along z likewise, through the x or the y neighbours.  On a solid region only its first
 // row / column issues atomics.
-__global__ void __launch_bounds__(CCL_BLOCK) ccl_union_kernel(const float* __restrict__ vol, int R, float iso, int* parent) {
-  const int64_t n3 = (int64_t)R * R * R;
-  const int64_t lg = (int64_t)blockIdx.x * CCL_BLOCK + threadIdx.x;
+__global__ void __launch_bounds__(LATTICE_BLOCK) ccl_union_kernel(const float* __restrict__ vol, int R, float iso, int* parent) {
+  const int64_t n3 = lattice_n3(R), lg = lattice_lane();
   if (lg >= n3) return;
   const int l = (int)lg;
   if (!(vol[l] > iso)) return;
-  const int i = l % R, j = (l / R) % R, k = l / (R * R);
-  const int sy = R, sz = R * R;
-  const bool xm = i > 0 && vol[l - 1] > iso;
+  int c[3];
+  lattice_coords(l, R, c);
+  const int sy = axis_stride(1, R), sz = axis_stride(2, R);
+  const bool xm = c[0] > 0 && vol[l - 1] > iso;
   if (xm && threadIdx.x == 0) unite(parent, l, l - 1);
-  const bool ym = j > 0 && vol[l - sy] > iso;
+  const bool ym = c[1] > 0 && vol[l - sy] > iso;
   if (ym && !(xm && vol[l - sy - 1] > iso)) unite(parent, l, l - sy);
-  if (k > 0 && vol[l - sz] > iso) {
+  if (c[2] > 0 && vol[l - sz] > iso) {
     const bool by_x = xm && vol[l - sz - 1] > iso;
     const bool by_y = ym && vol[l - sz - sy] > iso;
     if (!by_x && !by_y) unite(parent, l, l - sz);
@@ -98,9 +93,8 @@ __global__ void __launch_bounds__(CCL_BLOCK) ccl_union_kernel(const float* __res
 }
 
 // ---- flatten: 4 B of parent read (plus the walk to the root, cache hits), 4 B of label written per voxel
-__global__ void __launch_bounds__(CCL_BLOCK) ccl_flatten_kernel(const int* __restrict__ parent, int R, int* __restrict__ labels) {
-  const int64_t n3 = (int64_t)R * R * R;
-  const int64_t lg = (int64_t)blockIdx.x * CCL_BLOCK + threadIdx.x;
+__global__ void __launch_bounds__(LATTICE_BLOCK) ccl_flatten_kernel(const int* __restrict__ parent, int R, int* __restrict__ labels) {
+  const int64_t n3 = lattice_n3(R), lg = lattice_lane();
   if (lg >= n3) return;
   int x = parent[lg];
   if (x >= 0) {
@@ -114,19 +108,17 @@ __global__ void __launch_bounds__(CCL_BLOCK) ccl_flatten_kernel(const int* __res
 }
 
 // ---- sizes, 1 of 4: 4 B written per voxel; stats = 0
-__global__ void __launch_bounds__(CCL_BLOCK) ccl_zero_kernel(int R, int* __restrict__ sizes, unsigned long long* __restrict__ stats) {
-  const int64_t n3 = (int64_t)R * R * R;
-  const int64_t lg = (int64_t)blockIdx.x * CCL_BLOCK + threadIdx.x;
+__global__ void __launch_bounds__(LATTICE_BLOCK) ccl_zero_kernel(int R, int* __restrict__ sizes, unsigned long long* __restrict__ stats) {
+  const int64_t n3 = lattice_n3(R), lg = lattice_lane();
   if (lg < n3) sizes[lg] = 0;
   if (lg < 3) stats[lg] = 0ull;
 }
 
 // ---- sizes, 2 of 4: 4 B of label read per voxel; one integer atomic add per run of equal labels inside a wave (the run's
 // length, from the ballot of the run heads), so a solid row costs one atomic per 64 voxels
-__global__ void __launch_bounds__(CCL_BLOCK) ccl_count_kernel(const int* __restrict__ labels, int R, int* __restrict__ sizes) {
+__global__ void __launch_bounds__(LATTICE_BLOCK) ccl_count_kernel(const int* __restrict__ labels, int R, int* __restrict__ sizes) {
   const int lane = threadIdx.x & 63;
-  const int64_t n3 = (int64_t)R * R * R;
-  const int64_t lg = (int64_t)blockIdx.x * CCL_BLOCK + threadIdx.x;
+  const int64_t n3 = lattice_n3(R), lg = lattice_lane();
   const int lab = lg < n3 ? labels[lg] : -1;
   const int prev = __shfl_up(lab, 1, WAVE);
   const bool head = lane == 0 || prev != lab;
@@ -140,11 +132,10 @@ __global__ void __launch_bounds__(CCL_BLOCK) ccl_count_kernel(const int* __restr
 
 // ---- sizes, 3 of 4: 8 B read per voxel; per wave the roots, their voxels and the largest component's key
 // (size << 32 | 0xFFFFFFFF - label: the most voxels, ties to the smaller label), then three 64-bit integer atomics per wave
-__global__ void __launch_bounds__(CCL_BLOCK) ccl_roots_kernel(const int* __restrict__ labels, const int* __restrict__ sizes, int R,
+__global__ void __launch_bounds__(LATTICE_BLOCK) ccl_roots_kernel(const int* __restrict__ labels, const int* __restrict__ sizes, int R,
                                                              unsigned long long* __restrict__ stats) {
   const int lane = threadIdx.x & 63;
-  const int64_t n3 = (int64_t)R * R * R;
-  const int64_t lg = (int64_t)blockIdx.x * CCL_BLOCK + threadIdx.x;
+  const int64_t n3 = lattice_n3(R), lg = lattice_lane();
   const bool root = lg < n3 && (int64_t)labels[lg < n3 ? lg : 0] == lg;
   const unsigned sz = root ? (unsigned)sizes[lg] : 0u;
   unsigned long long key = root ? ((unsigned long long)sz << 32) | (0xFFFFFFFFull - (unsigned long long)lg) : 0ull;
@@ -173,11 +164,10 @@ __global__ void ccl_finish_kernel(int64_t* __restrict__ stats) {
 
 // ---- filter: 4 + 4 B read (+ 4 B of size per inside voxel, cache hits on a large component), 4 B written per voxel.  Values
 // move as bits (NaN payloads survive); out may be vol (each lane reads its voxel before it writes it).
-__global__ void __launch_bounds__(CCL_BLOCK) ccl_filter_kernel(const uint32_t* vol, const int* __restrict__ labels,
+__global__ void __launch_bounds__(LATTICE_BLOCK) ccl_filter_kernel(const uint32_t* vol, const int* __restrict__ labels,
                                                               const int* __restrict__ sizes, const int64_t* __restrict__ stats, int R,
                                                               uint32_t iso_bits, int64_t min_voxels, int largest_only, uint32_t* out) {
-  const int64_t n3 = (int64_t)R * R * R;
-  const int64_t lg = (int64_t)blockIdx.x * CCL_BLOCK + threadIdx.x;
+  const int64_t n3 = lattice_n3(R), lg = lattice_lane();
   if (lg >= n3) return;
   uint32_t v = vol[lg];
   const int lab = labels[lg];
@@ -189,71 +179,50 @@ __global__ void __launch_bounds__(CCL_BLOCK) ccl_filter_kernel(const uint32_t* v
   out[lg] = v;
 }
 
-int ccl_res_check(const char* who, int R) {
-  NERF_REQUIRE(R >= 2 && R <= NERF_MESH_MAX_RES, NERF_E_SHAPE, "%s: need 2 <= res <= %d (got %d)", who, NERF_MESH_MAX_RES, R);
-  return NERF_OK;
-}
-
-unsigned ccl_blocks(int R) { return (unsigned)(((int64_t)R * R * R + CCL_BLOCK - 1) / CCL_BLOCK); }
-
 }  // namespace
 }  // namespace nerf
 
 using namespace nerf;
 
 extern "C" int64_t nerf_ccl_workspace_bytes(int res) {
-  if (res < 2 || res > NERF_MESH_MAX_RES) return -1;
-  return (int64_t)res * res * res * (int64_t)sizeof(int32_t);
+  return lattice_res_ok(res) ? lattice_n3(res) * (int64_t)sizeof(int32_t) : -1;
 }
 
 extern "C" int nerf_ccl_label(const float* vol, int res, float iso, void* workspace, int32_t* labels, void* stream) {
-  int rc = ccl_res_check("nerf_ccl_label", res);
+  const int rc = lattice_check("nerf_ccl_label", res, iso);
   if (rc) return rc;
-  NERF_REQUIRE(std::isfinite(iso), NERF_E_SHAPE, "nerf_ccl_label: iso must be finite");
   NERF_REQUIRE(vol && workspace && labels, NERF_E_NULL, "nerf_ccl_label: NULL pointer");
   int* parent = static_cast<int*>(workspace);
-  const dim3 grid(ccl_blocks(res)), block(CCL_BLOCK);
-  hipLaunchKernelGGL(ccl_init_kernel, grid, block, 0, as_stream(stream), vol, res, iso, parent);
-  rc = check_launch("nerf_ccl_label (init)");
-  if (rc) return rc;
-  hipLaunchKernelGGL(ccl_union_kernel, grid, block, 0, as_stream(stream), vol, res, iso, parent);
-  rc = check_launch("nerf_ccl_label (union)");
-  if (rc) return rc;
-  hipLaunchKernelGGL(ccl_flatten_kernel, grid, block, 0, as_stream(stream), parent, res, labels);
-  return check_launch("nerf_ccl_label (flatten)");
+  const unsigned grid = lattice_blocks(res);
+  hipStream_t st = as_stream(stream);
+  NERF_LAUNCH("nerf_ccl_label (init)", ccl_init_kernel, grid, LATTICE_BLOCK, st, vol, res, iso, parent);
+  NERF_LAUNCH("nerf_ccl_label (union)", ccl_union_kernel, grid, LATTICE_BLOCK, st, vol, res, iso, parent);
+  NERF_LAUNCH("nerf_ccl_label (flatten)", ccl_flatten_kernel, grid, LATTICE_BLOCK, st, parent, res, labels);
+  return NERF_OK;
 }
 
 extern "C" int nerf_ccl_sizes(const int32_t* labels, int res, int32_t* sizes, int64_t* stats, void* stream) {
-  int rc = ccl_res_check("nerf_ccl_sizes", res);
+  const int rc = lattice_res_check("nerf_ccl_sizes", res);
   if (rc) return rc;
   NERF_REQUIRE(labels && sizes && stats, NERF_E_NULL, "nerf_ccl_sizes: NULL pointer");
   unsigned long long* ustats = reinterpret_cast<unsigned long long*>(stats);
-  const dim3 grid(ccl_blocks(res)), block(CCL_BLOCK);
-  hipLaunchKernelGGL(ccl_zero_kernel, grid, block, 0, as_stream(stream), res, sizes, ustats);
-  rc = check_launch("nerf_ccl_sizes (zero)");
-  if (rc) return rc;
-  hipLaunchKernelGGL(ccl_count_kernel, grid, block, 0, as_stream(stream), labels, res, sizes);
-  rc = check_launch("nerf_ccl_sizes (count)");
-  if (rc) return rc;
-  hipLaunchKernelGGL(ccl_roots_kernel, grid, block, 0, as_stream(stream), labels, sizes, res, ustats);
-  rc = check_launch("nerf_ccl_sizes (roots)");
-  if (rc) return rc;
-  hipLaunchKernelGGL(ccl_finish_kernel, dim3(1), dim3(64), 0, as_stream(stream), stats);
-  return check_launch("nerf_ccl_sizes (finish)");
+  const unsigned grid = lattice_blocks(res);
+  hipStream_t st = as_stream(stream);
+  NERF_LAUNCH("nerf_ccl_sizes (zero)", ccl_zero_kernel, grid, LATTICE_BLOCK, st, res, sizes, ustats);
+  NERF_LAUNCH("nerf_ccl_sizes (count)", ccl_count_kernel, grid, LATTICE_BLOCK, st, labels, res, sizes);
+  NERF_LAUNCH("nerf_ccl_sizes (roots)", ccl_roots_kernel, grid, LATTICE_BLOCK, st, labels, sizes, res, ustats);
+  NERF_LAUNCH("nerf_ccl_sizes (finish)", ccl_finish_kernel, 1, 64, st, stats);
+  return NERF_OK;
 }
 
 extern "C" int nerf_ccl_filter(const float* vol, const int32_t* labels, const int32_t* sizes, const int64_t* stats, int res, float iso,
                                int64_t min_voxels, int largest_only, float* out, void* stream) {
-  int rc = ccl_res_check("nerf_ccl_filter", res);
+  const int rc = lattice_check("nerf_ccl_filter", res, iso);
   if (rc) return rc;
-  NERF_REQUIRE(std::isfinite(iso), NERF_E_SHAPE, "nerf_ccl_filter: iso must be finite");
   NERF_REQUIRE(min_voxels >= 0, NERF_E_SHAPE, "nerf_ccl_filter: min_voxels must be >= 0 (got %lld)", (long long)min_voxels);
   NERF_REQUIRE(vol && labels && sizes && stats && out, NERF_E_NULL, "nerf_ccl_filter: NULL pointer");
-  uint32_t iso_bits;
-  static_assert(sizeof(iso_bits) == sizeof(iso), "float32");
-  __builtin_memcpy(&iso_bits, &iso, sizeof(iso_bits));
-  hipLaunchKernelGGL(ccl_filter_kernel, dim3(ccl_blocks(res)), dim3(CCL_BLOCK), 0, as_stream(stream),
-                     reinterpret_cast<const uint32_t*>(vol), labels, sizes, stats, res, iso_bits, min_voxels, largest_only,
+  hipLaunchKernelGGL(ccl_filter_kernel, dim3(lattice_blocks(res)), dim3(LATTICE_BLOCK), 0, as_stream(stream),
+                     reinterpret_cast<const uint32_t*>(vol), labels, sizes, stats, res, float_bits(iso), min_voxels, largest_only,
                      reinterpret_cast<uint32_t*>(out));
   return check_launch("nerf_ccl_filter");
 }

@@ -106,3 +106,11 @@ __device__ __forceinline__ float wave_rscan_incl(float v, int lane) {
   do {                                \
     if (!(cond)) return nerf::fail(code, __VA_ARGS__); \
   } while (0)
+
+// Launches `kernel` with `blocks` workgroups of `threads` on hipStream_t `st`; a failed launch returns its code from the calling entry.
+#define NERF_LAUNCH(what, kernel, blocks, threads, st, ...)                                        \
+  do {                                                                                             \
+    hipLaunchKernelGGL(kernel, dim3((unsigned)(blocks)), dim3(threads), 0, st, __VA_ARGS__);       \
+    const int rc_ = nerf::check_launch(what);                                                      \
+    if (rc_) return rc_;                                                                           \
+  } while (0)

@@ -3,30 +3,16 @@
 // point.  Semantics in include/nerf_hip.h "mesh extraction"; tests/_mesh_ref.py reproduces every output.  No reference
 // counterpart.  Count -> block scan -> write, like the cull and the march of occupancy.hip: no atomics, every output is
 // bit-reproducible and independent of the launch configuration.  All HBM- or launch-bound; bytes per point above each kernel.
-#include <cmath>
-
-#include "common.h"
+#include "lattice.h"
 #include "mc_table.h"
 #include "scan.h"
 
 namespace nerf {
 namespace {
 
-constexpr int MESH_BLOCK = 256;                     // lattice points per workgroup, x fastest
-
 __constant__ uint8_t c_mc_table[256][NERF_MC_ROW] = NERF_MC_TABLE_INIT;
 __constant__ int8_t c_edge_corner[12] = NERF_MC_EDGE_CORNER_INIT;
 __constant__ int8_t c_edge_axis[12] = NERF_MC_EDGE_AXIS_INIT;
-
-struct Box {
-  float lo[3], h[3];
-};
-
-// correctly rounded float32 division / square root: the double result rounded once (exact enough for one float rounding)
-__device__ __forceinline__ float div_rn(float a, float b) { return (float)((double)a / (double)b); }
-__device__ __forceinline__ float sqrt_rn(float a) { return (float)sqrt((double)a); }
-
-__device__ __forceinline__ int axis_stride(int a, int R) { return a == 0 ? 1 : (a == 1 ? R : R * R); }
 
 // bit c: corner c of the cell at (i, j, k) is inside (v > iso; NaN is outside).  Corners past the lattice read as outside and
 // are never used: the crossing mask and the case below only look at corners that exist.
@@ -53,7 +39,7 @@ __device__ __forceinline__ int crossing_mask(uint32_t ins, int R, int i, int j, 
 __device__ __forceinline__ bool is_cell(int R, int i, int j, int k) { return i < R - 1 && j < R - 1 && k < R - 1; }
 
 // the volume's gradient at lattice point (c[0], c[1], c[2]) = linear l: central differences, one-sided at the border
-__device__ __forceinline__ void gradient_at(const float* __restrict__ vol, int R, const int* c, int l, const Box& bx, float* g) {
+__device__ __forceinline__ void gradient_at(const float* __restrict__ vol, int R, const int* c, int l, const Lattice& bx, float* g) {
 #pragma unroll
   for (int b = 0; b < 3; ++b) {
     const int s = axis_stride(b, R);
@@ -64,14 +50,13 @@ __device__ __forceinline__ void gradient_at(const float* __restrict__ vol, int R
 }
 
 // ---- lattice rows: 44 + 4 B written per point, nothing read.  Row = [p, d = 0, near = far = 0, viewdirs = 0], z = 0: the rows
-// of nerf_occ_points, at the cell centres p_a = lo_a + ((float)i_a + 0.5f) h_a.
-__global__ void mesh_points_kernel(int R, Box bx, int64_t p0, int64_t count, float* __restrict__ rays, float* __restrict__ z) {
+// of nerf_occ_points, at the cell centres (lattice_centre).
+__global__ void mesh_points_kernel(Lattice bx, int64_t p0, int64_t count, float* __restrict__ rays, float* __restrict__ z) {
   for (int64_t t = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; t < count; t += (int64_t)gridDim.x * blockDim.x) {
-    const int64_t l = p0 + t;
-    const int c[3] = {(int)(l % R), (int)((l / R) % R), (int)(l / ((int64_t)R * R))};
+    int c[3];
+    lattice_coords((int)(p0 + t), bx.R, c);
     float* r = rays + t * NERF_RAY_STRIDE;
-#pragma unroll
-    for (int a = 0; a < 3; ++a) r[a] = bx.lo[a] + ((float)c[a] + 0.5f) * bx.h[a];
+    lattice_centre(bx, c, r);
 #pragma unroll
     for (int q = 3; q < NERF_RAY_STRIDE; ++q) r[q] = 0.0f;
     z[t] = 0.0f;
@@ -80,19 +65,19 @@ __global__ void mesh_points_kernel(int R, Box bx, int64_t p0, int64_t count, flo
 
 // ---- count: per workgroup of 256 points the crossing owned edges (blk[b]) and the triangles of the cells they are the origins
 // of (blk[nblk + b]).  4 B of volume per point from HBM (the 7 neighbours are L1 / L2 hits), 16 B written per workgroup.
-__global__ void __launch_bounds__(MESH_BLOCK) mesh_count_kernel(const float* __restrict__ vol, int R, float iso,
+__global__ void __launch_bounds__(LATTICE_BLOCK) mesh_count_kernel(const float* __restrict__ vol, int R, float iso,
                                                                int64_t* __restrict__ blk, int64_t nblk) {
-  const int64_t n3 = (int64_t)R * R * R;
-  const int64_t lg = (int64_t)blockIdx.x * MESH_BLOCK + threadIdx.x;
+  const int64_t lg = lattice_lane();
   int nv = 0, nt = 0;
-  if (lg < n3) {
-    const int l = (int)lg, i = l % R, j = (l / R) % R, k = l / (R * R);
-    const uint32_t ins = corner_bits(vol, R, i, j, k, l, iso);
-    nv = __popc(crossing_mask(ins, R, i, j, k));
-    if (is_cell(R, i, j, k)) nt = c_mc_table[ins][0];
+  if (lg < lattice_n3(R)) {
+    int c[3];
+    lattice_coords((int)lg, R, c);
+    const uint32_t ins = corner_bits(vol, R, c[0], c[1], c[2], (int)lg, iso);
+    nv = __popc(crossing_mask(ins, R, c[0], c[1], c[2]));
+    if (is_cell(R, c[0], c[1], c[2])) nt = c_mc_table[ins][0];
   }
   int64_t t[2];
-  block_sum<MESH_BLOCK>({nv, nt}, t);
+  block_sum<LATTICE_BLOCK>({nv, nt}, t);
   if (threadIdx.x == 0) {
     blk[blockIdx.x] = t[0];
     blk[nblk + blockIdx.x] = t[1];
@@ -102,23 +87,24 @@ __global__ void __launch_bounds__(MESH_BLOCK) mesh_count_kernel(const float* __r
 // ---- vertices: the same decisions, ranked inside the workgroup; per point its vertex base (4 B) to the workspace, per vertex
 // its position and normal (24 B) and, when asked, the colour query row [x, -n, 0, 0, -n] (44 B).  Reads: the volume as the count
 // does, plus the 6-neighbourhoods of an edge's two ends for the normal (cache hits), 8 B per workgroup.
-__global__ void __launch_bounds__(MESH_BLOCK) mesh_vertices_kernel(const float* __restrict__ vol, int R, float iso, Box bx,
+__global__ void __launch_bounds__(LATTICE_BLOCK) mesh_vertices_kernel(const float* __restrict__ vol, float iso, Lattice bx,
                                                                   const int64_t* __restrict__ blk, int64_t V, int* __restrict__ vbase,
                                                                   float* __restrict__ verts, float* __restrict__ normals,
                                                                   float* __restrict__ rows) {
-  const int64_t n3 = (int64_t)R * R * R;
-  const int64_t lg = (int64_t)blockIdx.x * MESH_BLOCK + threadIdx.x;
+  const int R = bx.R;
+  const int64_t n3 = lattice_n3(R), lg = lattice_lane();
   int m = 0, l = 0, c[3] = {0, 0, 0};
   if (lg < n3) {
     l = (int)lg;
-    c[0] = l % R; c[1] = (l / R) % R; c[2] = l / (R * R);
+    lattice_coords(l, R, c);
     m = crossing_mask(corner_bits(vol, R, c[0], c[1], c[2], l, iso), R, c[0], c[1], c[2]);
   }
-  int64_t id = block_offset<MESH_BLOCK>(__popc(m), blk[blockIdx.x]);
+  int64_t id = block_offset<LATTICE_BLOCK>(__popc(m), blk[blockIdx.x]);
   if (lg >= n3) return;
   vbase[l] = (int)id;
   if (!m) return;
-  float g0[3];
+  float g0[3], p0[3];
+  lattice_centre(bx, c, p0);                             // once, ahead of the axis loop: inside it the kernel takes 4 more VGPRs
   gradient_at(vol, R, c, l, bx, g0);
   const float v0 = vol[l];
   for (int a = 0; a < 3; ++a) {
@@ -127,9 +113,7 @@ __global__ void __launch_bounds__(MESH_BLOCK) mesh_vertices_kernel(const float* 
     const int s = axis_stride(a, R);
     float t = div_rn(iso - v0, vol[l + s] - v0);
     t = (t != t) ? 0.5f : fminf(fmaxf(t, 0.0f), 1.0f);
-    float x[3];
-#pragma unroll
-    for (int b = 0; b < 3; ++b) x[b] = bx.lo[b] + ((float)c[b] + 0.5f) * bx.h[b];
+    float x[3] = {p0[0], p0[1], p0[2]};
     x[a] = x[a] + t * bx.h[a];
     int c1[3] = {c[0], c[1], c[2]};
     c1[a] += 1;
@@ -148,12 +132,7 @@ __global__ void __launch_bounds__(MESH_BLOCK) mesh_vertices_kernel(const float* 
       verts[3 * id + b] = x[b];
       normals[3 * id + b] = n[b];
     }
-    if (rows) {
-      float* r = rows + id * NERF_RAY_STRIDE;
-#pragma unroll
-      for (int b = 0; b < 3; ++b) { r[b] = x[b]; r[3 + b] = -n[b]; r[8 + b] = -n[b]; }
-      r[6] = 0.0f; r[7] = 0.0f;
-    }
+    if (rows) write_color_row(rows, id, x, n);
     ++id;
   }
 }
@@ -177,51 +156,30 @@ __device__ __forceinline__ int edge_vertex(const float* __restrict__ vol, const 
 
 // ---- faces: per cell its case again, ranked inside the workgroup; per triangle 12 B written.  Reads: the volume as the count,
 // plus for the cells on the surface the bases of the owners of their crossing edges (4 B each) and a few volume neighbours.
-__global__ void __launch_bounds__(MESH_BLOCK) mesh_faces_kernel(const float* __restrict__ vol, int R, float iso,
+__global__ void __launch_bounds__(LATTICE_BLOCK) mesh_faces_kernel(const float* __restrict__ vol, int R, float iso,
                                                                const int64_t* __restrict__ blk_f, const int* __restrict__ vbase,
                                                                int64_t F, int* __restrict__ faces) {
-  const int64_t n3 = (int64_t)R * R * R;
-  const int64_t lg = (int64_t)blockIdx.x * MESH_BLOCK + threadIdx.x;
-  int nt = 0, i = 0, j = 0, k = 0;
+  const int64_t lg = lattice_lane();
+  int nt = 0, c[3] = {0, 0, 0};
   uint32_t ins = 0;
-  if (lg < n3) {
-    const int l = (int)lg;
-    i = l % R; j = (l / R) % R; k = l / (R * R);
-    if (is_cell(R, i, j, k)) {
-      ins = corner_bits(vol, R, i, j, k, l, iso);
+  if (lg < lattice_n3(R)) {
+    lattice_coords((int)lg, R, c);
+    if (is_cell(R, c[0], c[1], c[2])) {
+      ins = corner_bits(vol, R, c[0], c[1], c[2], (int)lg, iso);
       nt = c_mc_table[ins][0];
     }
   }
-  const int64_t f0 = block_offset<MESH_BLOCK>(nt, blk_f[blockIdx.x]);
+  const int64_t f0 = block_offset<LATTICE_BLOCK>(nt, blk_f[blockIdx.x]);
   for (int t = 0; t < nt && f0 + t < F; ++t) {
 #pragma unroll
     for (int v = 0; v < 3; ++v)
-      faces[3 * (f0 + t) + v] = edge_vertex(vol, vbase, R, iso, ins, i, j, k, c_mc_table[ins][1 + 3 * t + v]);
+      faces[3 * (f0 + t) + v] = edge_vertex(vol, vbase, R, iso, ins, c[0], c[1], c[2], c_mc_table[ins][1 + 3 * t + v]);
   }
-}
-
-int mesh_check(const char* who, int R, float iso) {
-  NERF_REQUIRE(R >= 2 && R <= NERF_MESH_MAX_RES, NERF_E_SHAPE, "%s: need 2 <= res <= %d (got %d)", who, NERF_MESH_MAX_RES, R);
-  NERF_REQUIRE(std::isfinite(iso), NERF_E_SHAPE, "%s: iso must be finite", who);
-  return NERF_OK;
-}
-
-int box_of(const char* who, int R, const float* lo, const float* hi, Box* bx) {
-  NERF_REQUIRE(lo && hi, NERF_E_NULL, "%s: NULL lo / hi", who);
-  for (int a = 0; a < 3; ++a) {
-    NERF_REQUIRE(std::isfinite(lo[a]) && std::isfinite(hi[a]) && lo[a] < hi[a], NERF_E_SHAPE,
-                 "%s: need finite lo[%d] < hi[%d] (got %g, %g)", who, a, a, (double)lo[a], (double)hi[a]);
-    bx->lo[a] = lo[a];
-    bx->h[a] = (hi[a] - lo[a]) / (float)R;                 // float32, two roundings
-    NERF_REQUIRE(bx->h[a] > 0.0f && std::isfinite(bx->h[a]), NERF_E_SHAPE, "%s: box too small or too large on axis %d", who, a);
-  }
-  return NERF_OK;
 }
 
 // blk[2][nblk] (vertices, faces), then every lattice point's vertex base
 PairWs mesh_ws(void* ws, int R) {
-  const int64_t n3 = (int64_t)R * R * R;
-  return pair_ws(ws, 2, (n3 + MESH_BLOCK - 1) / MESH_BLOCK, n3 * (int64_t)sizeof(int));
+  return pair_ws(ws, 2, lattice_blocks(R), lattice_n3(R) * (int64_t)sizeof(int));
 }
 
 }  // namespace
@@ -230,67 +188,64 @@ PairWs mesh_ws(void* ws, int R) {
 using namespace nerf;
 
 extern "C" int64_t nerf_mesh_workspace_bytes(int res) {
-  return res < 2 || res > NERF_MESH_MAX_RES ? -1 : mesh_ws(nullptr, res).bytes;
+  return !lattice_res_ok(res) ? -1 : mesh_ws(nullptr, res).bytes;
 }
 
 extern "C" int nerf_mesh_points(int res, const float* lo, const float* hi, int64_t p0, int64_t count, float* rays_out,
                                 float* z_out, void* stream) {
-  NERF_REQUIRE(res >= 2 && res <= NERF_MESH_MAX_RES, NERF_E_SHAPE, "nerf_mesh_points: need 2 <= res <= %d (got %d)",
-               NERF_MESH_MAX_RES, res);
-  Box bx;
-  int rc = box_of("nerf_mesh_points", res, lo, hi, &bx);
+  int rc = lattice_res_check("nerf_mesh_points", res);
   if (rc) return rc;
-  const int64_t n3 = (int64_t)res * res * res;
+  Lattice bx;
+  rc = lattice_box("nerf_mesh_points", res, lo, hi, &bx);
+  if (rc) return rc;
+  const int64_t n3 = lattice_n3(res);
   NERF_REQUIRE(p0 >= 0 && count >= 0 && p0 + count <= n3, NERF_E_SHAPE, "nerf_mesh_points: points [%lld, %lld) outside the %lld",
                (long long)p0, (long long)(p0 + count), (long long)n3);
   if (count == 0) return NERF_OK;
   NERF_REQUIRE(rays_out && z_out, NERF_E_NULL, "nerf_mesh_points: NULL pointer");
-  hipLaunchKernelGGL(mesh_points_kernel, dim3(grid_for(count, 256)), dim3(256), 0, as_stream(stream), res, bx, p0, count, rays_out,
+  hipLaunchKernelGGL(mesh_points_kernel, dim3(grid_for(count, 256)), dim3(256), 0, as_stream(stream), bx, p0, count, rays_out,
                      z_out);
   return check_launch("nerf_mesh_points");
 }
 
 extern "C" int nerf_mesh_count(const float* vol, int res, float iso, void* workspace, int64_t* totals, void* stream) {
-  int rc = mesh_check("nerf_mesh_count", res, iso);
+  int rc = lattice_check("nerf_mesh_count", res, iso);
   if (rc) return rc;
   NERF_REQUIRE(vol && workspace && totals, NERF_E_NULL, "nerf_mesh_count: NULL pointer");
   const PairWs w = mesh_ws(workspace, res);
-  hipLaunchKernelGGL(mesh_count_kernel, dim3((unsigned)w.nblk), dim3(MESH_BLOCK), 0, as_stream(stream), vol, res, iso, w.blk, w.nblk);
-  rc = check_launch("nerf_mesh_count (count)");
+  hipStream_t st = as_stream(stream);
+  NERF_LAUNCH("nerf_mesh_count (count)", mesh_count_kernel, w.nblk, LATTICE_BLOCK, st, vol, res, iso, w.blk, w.nblk);
+  rc = scan_launch("nerf_mesh_count (scan of the vertices)", w.blk, w.nblk, totals, st);
   if (rc) return rc;
-  hipLaunchKernelGGL(occ_cull_scan_kernel, dim3(1), dim3(1024), 0, as_stream(stream), w.blk, w.nblk, totals);
-  rc = check_launch("nerf_mesh_count (scan of the vertices)");
-  if (rc) return rc;
-  hipLaunchKernelGGL(occ_cull_scan_kernel, dim3(1), dim3(1024), 0, as_stream(stream), w.blk + w.nblk, w.nblk, totals + 1);
-  return check_launch("nerf_mesh_count (scan of the faces)");
+  return scan_launch("nerf_mesh_count (scan of the faces)", w.blk + w.nblk, w.nblk, totals + 1, st);
 }
 
 extern "C" int nerf_mesh_write_vertices(const float* vol, int res, float iso, const float* lo, const float* hi, void* workspace,
                                         int64_t V, float* verts, float* normals, float* color_rows, void* stream) {
-  int rc = mesh_check("nerf_mesh_write_vertices", res, iso);
+  int rc = lattice_check("nerf_mesh_write_vertices", res, iso);
   if (rc) return rc;
-  Box bx;
-  rc = box_of("nerf_mesh_write_vertices", res, lo, hi, &bx);
+  Lattice bx;
+  rc = lattice_box("nerf_mesh_write_vertices", res, lo, hi, &bx);
   if (rc) return rc;
   NERF_REQUIRE(V >= 0 && V <= 3ll * res * res * res, NERF_E_SHAPE, "nerf_mesh_write_vertices: bad V %lld", (long long)V);
   if (V == 0) return NERF_OK;
   NERF_REQUIRE(vol && workspace && verts && normals, NERF_E_NULL, "nerf_mesh_write_vertices: NULL pointer");
   const PairWs w = mesh_ws(workspace, res);
-  hipLaunchKernelGGL(mesh_vertices_kernel, dim3((unsigned)w.nblk), dim3(MESH_BLOCK), 0, as_stream(stream), vol, res, iso, bx,
+  hipLaunchKernelGGL(mesh_vertices_kernel, dim3((unsigned)w.nblk), dim3(LATTICE_BLOCK), 0, as_stream(stream), vol, iso, bx,
                      (const int64_t*)w.blk, V, w.items, verts, normals, color_rows);
   return check_launch("nerf_mesh_write_vertices");
 }
 
 extern "C" int nerf_mesh_write_faces(const float* vol, int res, float iso, void* workspace, int64_t F, int32_t* faces,
                                      void* stream) {
-  int rc = mesh_check("nerf_mesh_write_faces", res, iso);
+  int rc = lattice_check("nerf_mesh_write_faces", res, iso);
   if (rc) return rc;
   NERF_REQUIRE(F >= 0 && F <= (int64_t)NERF_MC_MAX_TRIS * res * res * res, NERF_E_SHAPE, "nerf_mesh_write_faces: bad F %lld",
                (long long)F);
   if (F == 0) return NERF_OK;
   NERF_REQUIRE(vol && workspace && faces, NERF_E_NULL, "nerf_mesh_write_faces: NULL pointer");
   const PairWs w = mesh_ws(workspace, res);
-  hipLaunchKernelGGL(mesh_faces_kernel, dim3((unsigned)w.nblk), dim3(MESH_BLOCK), 0, as_stream(stream), vol, res, iso,
+  hipLaunchKernelGGL(mesh_faces_kernel, dim3((unsigned)w.nblk), dim3(LATTICE_BLOCK), 0, as_stream(stream), vol, res, iso,
                      (const int64_t*)(w.blk + w.nblk), (const int*)w.items, F, faces);
   return check_launch("nerf_mesh_write_faces");
 }

@@ -6,16 +6,14 @@
 // x neighbour a shift with one carry bit from the adjacent word of the same row (none across a row end).  A mask of R = 512 is
 // 16 MiB against the volume's 512 MiB, so a step costs 1 / 32 of a float pass.  Launches: pack, r steps, apply -- (R, r) alone
 // decide them, nothing is read on the host, and every output bit has one writer: bit-reproducible.
-#include <cmath>
-
-#include "common.h"
+#include "lattice.h"
 #define NERF_SCAN_HELPERS_ONLY                      // block_sum alone: this unit launches no scan and carves no pair workspace
 #include "scan.h"
 
 namespace nerf {
 namespace {
 
-constexpr int MORPH_BLOCK = 256;                    // voxels (pack, apply) or words (step) per workgroup, x fastest
+constexpr int MORPH_BLOCK = LATTICE_BLOCK;         // voxels (pack, apply: lattice.h) or words (step) per workgroup, x fastest
 constexpr int MORPH_STEP_MAX_BLOCKS = 1024;         // the steps stride over the words: at most 2 x 1024 atomics on the stats
 
 typedef unsigned long long u64;
@@ -87,12 +85,11 @@ __global__ void __launch_bounds__(MORPH_BLOCK) morph_step_kernel(const u64* __re
 // ---- apply: 4 B read, 4 B written per voxel (the two mask words of a wave's voxels are broadcast cache hits).  A voxel of M that
 // is not in `keep` becomes iso; every other value moves as bits (NaN payloads survive).  out may be vol: each lane reads its voxel
 // before it writes it.
-__global__ void __launch_bounds__(MORPH_BLOCK) morph_apply_kernel(const uint32_t* vol, const u64* __restrict__ m_mask,
+__global__ void __launch_bounds__(LATTICE_BLOCK) morph_apply_kernel(const uint32_t* vol, const u64* __restrict__ m_mask,
                                                                  const u64* __restrict__ keep, int R, uint32_t iso_bits,
                                                                  uint32_t* out) {
-  const int64_t n3 = (int64_t)R * R * R;
-  const int64_t lg = (int64_t)blockIdx.x * MORPH_BLOCK + threadIdx.x;
-  if (lg >= n3) return;
+  const int64_t lg = lattice_lane();
+  if (lg >= lattice_n3(R)) return;
   const int W = morph_row_words(R);
   const int i = (int)(lg % R);
   const int64_t w = (lg / R) * W + (i >> 6);
@@ -103,8 +100,8 @@ __global__ void __launch_bounds__(MORPH_BLOCK) morph_apply_kernel(const uint32_t
 }
 
 int morph_check(const char* who, int R, float iso, int radius) {
-  NERF_REQUIRE(R >= 2 && R <= NERF_MESH_MAX_RES, NERF_E_SHAPE, "%s: need 2 <= res <= %d (got %d)", who, NERF_MESH_MAX_RES, R);
-  NERF_REQUIRE(std::isfinite(iso), NERF_E_SHAPE, "%s: iso must be finite", who);
+  const int rc = lattice_check(who, R, iso);
+  if (rc) return rc;
   NERF_REQUIRE(radius >= 1 && radius <= NERF_MORPH_MAX_RADIUS, NERF_E_SHAPE, "%s: need 1 <= radius <= %d (got %d)", who,
                NERF_MORPH_MAX_RADIUS, radius);
   return NERF_OK;
@@ -112,26 +109,17 @@ int morph_check(const char* who, int R, float iso, int radius) {
 
 int64_t morph_words(int R) { return (int64_t)morph_row_words(R) * R * R; }
 
-uint32_t float_bits(float x) {
-  uint32_t b;
-  static_assert(sizeof(b) == sizeof(x), "float32");
-  __builtin_memcpy(&b, &x, sizeof(b));
-  return b;
-}
-
 // the r steps from buf[a] to buf[a ^ 1] and back (buf[0], buf[1]: the ping-pong pair; the first step reads `first`); the first
 // step counts its source into stats[0], the last its result into stats[1].  Returns the buffer that holds the result.
 template <bool DILATE>
 int morph_steps(const char* who, const u64* first, const u64* m_mask, u64* const buf[2], int into, int R, int radius, u64* stats,
                 hipStream_t st, const u64** result) {
-  const dim3 grid(grid_for(morph_words(R), MORPH_BLOCK, MORPH_STEP_MAX_BLOCKS)), block(MORPH_BLOCK);
+  const int grid = grid_for(morph_words(R), MORPH_BLOCK, MORPH_STEP_MAX_BLOCKS);
   const u64* src = first;
   for (int n = 0; n < radius; ++n) {
     u64* dst = buf[into];
-    hipLaunchKernelGGL(morph_step_kernel<DILATE>, grid, block, 0, st, src, m_mask, R, dst, n == 0 ? stats + 0 : (u64*)nullptr,
-                       n == radius - 1 ? stats + 1 : (u64*)nullptr);
-    const int rc = check_launch(who);
-    if (rc) return rc;
+    NERF_LAUNCH(who, morph_step_kernel<DILATE>, grid, MORPH_BLOCK, st, src, m_mask, R, dst, n == 0 ? stats + 0 : (u64*)nullptr,
+                n == radius - 1 ? stats + 1 : (u64*)nullptr);
     src = dst;
     into ^= 1;
   }
@@ -139,7 +127,6 @@ int morph_steps(const char* who, const u64* first, const u64* m_mask, u64* const
   return NERF_OK;
 }
 
-unsigned morph_voxel_blocks(int R) { return (unsigned)(((int64_t)R * R * R + MORPH_BLOCK - 1) / MORPH_BLOCK); }
 unsigned morph_pack_blocks(int R) { return (unsigned)((morph_words(R) + MORPH_BLOCK / 64 - 1) / (MORPH_BLOCK / 64)); }
 
 }  // namespace
@@ -149,8 +136,7 @@ using namespace nerf;
 
 // three masks: M and the ping-pong pair
 extern "C" int64_t nerf_morph_workspace_bytes(int res) {
-  if (res < 2 || res > NERF_MESH_MAX_RES) return -1;
-  return 3 * morph_words(res) * (int64_t)sizeof(u64);
+  return lattice_res_ok(res) ? 3 * morph_words(res) * (int64_t)sizeof(u64) : -1;
 }
 
 extern "C" int nerf_morph_erode(const float* vol, int res, float iso, int radius, void* workspace, float* core, int64_t* stats2,
@@ -163,14 +149,12 @@ extern "C" int nerf_morph_erode(const float* vol, int res, float iso, int radius
   u64* const buf[2] = {m_mask + nw, m_mask + 2 * nw};
   u64* stats = reinterpret_cast<u64*>(stats2);
   hipStream_t st = as_stream(stream);
-  hipLaunchKernelGGL(morph_pack_kernel<false>, dim3(morph_pack_blocks(res)), dim3(MORPH_BLOCK), 0, st, vol, (const float*)nullptr,
-                     res, iso, m_mask, (u64*)nullptr, stats);
-  rc = check_launch("nerf_morph_erode (pack)");
-  if (rc) return rc;
+  NERF_LAUNCH("nerf_morph_erode (pack)", morph_pack_kernel<false>, morph_pack_blocks(res), MORPH_BLOCK, st, vol,
+              (const float*)nullptr, res, iso, m_mask, (u64*)nullptr, stats);
   const u64* eroded = nullptr;
   rc = morph_steps<false>("nerf_morph_erode (step)", m_mask, m_mask, buf, 0, res, radius, stats, st, &eroded);
   if (rc) return rc;
-  hipLaunchKernelGGL(morph_apply_kernel, dim3(morph_voxel_blocks(res)), dim3(MORPH_BLOCK), 0, st,
+  hipLaunchKernelGGL(morph_apply_kernel, dim3(lattice_blocks(res)), dim3(LATTICE_BLOCK), 0, st,
                      reinterpret_cast<const uint32_t*>(vol), m_mask, eroded, res, float_bits(iso), reinterpret_cast<uint32_t*>(core));
   return check_launch("nerf_morph_erode (apply)");
 }
@@ -185,14 +169,12 @@ extern "C" int nerf_morph_reconstruct(const float* vol, const float* kept, int r
   u64* const buf[2] = {m_mask + nw, m_mask + 2 * nw};
   u64* stats = reinterpret_cast<u64*>(stats2);
   hipStream_t st = as_stream(stream);
-  hipLaunchKernelGGL(morph_pack_kernel<true>, dim3(morph_pack_blocks(res)), dim3(MORPH_BLOCK), 0, st, vol, kept, res, iso, m_mask,
-                     buf[0], stats);
-  rc = check_launch("nerf_morph_reconstruct (pack)");
-  if (rc) return rc;
+  NERF_LAUNCH("nerf_morph_reconstruct (pack)", morph_pack_kernel<true>, morph_pack_blocks(res), MORPH_BLOCK, st, vol, kept, res, iso,
+              m_mask, buf[0], stats);
   const u64* grown = nullptr;
   rc = morph_steps<true>("nerf_morph_reconstruct (step)", buf[0], m_mask, buf, 1, res, radius, stats, st, &grown);
   if (rc) return rc;
-  hipLaunchKernelGGL(morph_apply_kernel, dim3(morph_voxel_blocks(res)), dim3(MORPH_BLOCK), 0, st,
+  hipLaunchKernelGGL(morph_apply_kernel, dim3(lattice_blocks(res)), dim3(LATTICE_BLOCK), 0, st,
                      reinterpret_cast<const uint32_t*>(vol), m_mask, grown, res, float_bits(iso), reinterpret_cast<uint32_t*>(out));
   return check_launch("nerf_morph_reconstruct (apply)");
 }

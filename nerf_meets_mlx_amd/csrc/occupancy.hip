@@ -549,8 +549,7 @@ extern "C" int nerf_occ_cull(const float* rays, const float* z, int64_t B, int n
                      log2_res, pos_scale, pos_offset, offs, raw_fill);
   int rc = check_launch("nerf_occ_cull (count)");
   if (rc) return rc;
-  hipLaunchKernelGGL(occ_cull_scan_kernel, dim3(1), dim3(1024), 0, as_stream(stream), offs, nblk, count_out);
-  rc = check_launch("nerf_occ_cull (scan)");
+  rc = scan_launch("nerf_occ_cull (scan)", offs, nblk, count_out, as_stream(stream));
   if (rc) return rc;
   hipLaunchKernelGGL(occ_cull_compact_kernel, dim3((unsigned)nblk), dim3(CULL_BLOCK), 0, as_stream(stream), rays, z, M, n, bits,
                      log2_res, pos_scale, pos_offset, offs, idx_out, rays_out, z_out);
@@ -571,8 +570,7 @@ extern "C" int nerf_occ_march_count(const float* rays, int64_t B, const float* j
   hipLaunchKernelGGL(occ_march_count_kernel, dim3((unsigned)w.nblk), dim3(MARCH_BLOCK), 0, as_stream(stream), a, w.items, w.blk);
   rc = check_launch("nerf_occ_march_count (count)");
   if (rc) return rc;
-  hipLaunchKernelGGL(occ_cull_scan_kernel, dim3(1), dim3(1024), 0, as_stream(stream), w.blk, w.nblk, offsets + B);
-  return check_launch("nerf_occ_march_count (scan)");
+  return scan_launch("nerf_occ_march_count (scan)", w.blk, w.nblk, offsets + B, as_stream(stream));
 }
 
 extern "C" int nerf_occ_march_write(const float* rays, int64_t B, const float* jitter, float jitter_const, const uint32_t* bits,
@@ -619,11 +617,9 @@ extern "C" int nerf_ert_march_count(const float* rays, int64_t B, const float* j
                      max_new, w.items, w.blk, w.nblk);
   rc = check_launch("nerf_ert_march_count (count)");
   if (rc) return rc;
-  hipLaunchKernelGGL(occ_cull_scan_kernel, dim3(1), dim3(1024), 0, as_stream(stream), w.blk, w.nblk, totals);
-  rc = check_launch("nerf_ert_march_count (scan of the samples)");
+  rc = scan_launch("nerf_ert_march_count (scan of the samples)", w.blk, w.nblk, totals, as_stream(stream));
   if (rc) return rc;
-  hipLaunchKernelGGL(occ_cull_scan_kernel, dim3(1), dim3(1024), 0, as_stream(stream), w.blk + w.nblk, w.nblk, totals + 1);
-  return check_launch("nerf_ert_march_count (scan of the live rays)");
+  return scan_launch("nerf_ert_march_count (scan of the live rays)", w.blk + w.nblk, w.nblk, totals + 1, as_stream(stream));
 }
 
 extern "C" int nerf_ert_march_write(const float* rays, int64_t B, const float* jitter, float jitter_const, const uint32_t* bits,

@@ -1,7 +1,7 @@
 // The three passes shared by the compactions of occupancy.hip (cull, march, early termination), mesh.hip (marching cubes) and
 // morph.hip (the steps' statistics): count per workgroup (block_sum), scan of the workgroup sums by one workgroup
-// (occ_cull_scan_kernel), rank inside the workgroup (block_offset).  Fixed order, no atomics; and the host's layout of the
-// workspace a count / write pair shares.
+// (occ_cull_scan_kernel, launched by scan_launch), rank inside the workgroup (block_offset).  Fixed order, no atomics; and the
+// host's layout of the workspace a count / write pair shares.
 #pragma once
 #include "common.h"
 
@@ -103,6 +103,10 @@ __global__ void __launch_bounds__(1024) occ_cull_scan_kernel(int64_t* __restrict
     __syncthreads();
   }
   if (threadIdx.x == 0) *count_out = carry;
+}
+inline int scan_launch(const char* what, int64_t* blk, int64_t nblk, int64_t* total, hipStream_t st) {
+  hipLaunchKernelGGL(occ_cull_scan_kernel, dim3(1), dim3(1024), 0, st, blk, nblk, total);
+  return check_launch(what);
 }
 
 // The workspace of a count / write pair: `rows` x nblk workgroup sums (int64, scanned in place), then item_bytes of one int per

@@ -9,9 +9,7 @@
 //            position from the run's two ends (linear in F whatever the run lengths), used clusters, both compactions' counts.
 //   write    the placement solve of the used clusters and the renumbered surviving faces, ranked inside the workgroup.
 // All HBM- or launch-bound.
-#include <cmath>
-
-#include "common.h"
+#include "lattice.h"
 #include "scan.h"
 
 namespace nerf {
@@ -418,12 +416,7 @@ __global__ void __launch_bounds__(SIMP_BLOCK) simp_solve_kernel(const int64_t* _
     normals[3 * id + a] = no[a];
     if (colors) colors[3 * id + a] = (float)((double)A[7 + a] / 1073741824.0 / n);
   }
-  if (rows) {
-    float* r = rows + id * NERF_RAY_STRIDE;
-#pragma unroll
-    for (int a = 0; a < 3; ++a) { r[a] = xo[a]; r[3 + a] = -no[a]; r[8 + a] = -no[a]; }
-    r[6] = 0.0f; r[7] = 0.0f;
-  }
+  if (rows) write_color_row(rows, id, xo, no);
 }
 
 // ---- faces out: 4 + 12 B read per face, 12 B written per survivor, renumbered, in input order
@@ -439,17 +432,25 @@ __global__ void __launch_bounds__(SIMP_BLOCK) simp_faces_write_kernel(const int*
   for (int c = 0; c < 3; ++c) out[3 * id + c] = newid[vcid[faces[3 * f + c]]];
 }
 
-int simp_check(const char* who, int64_t V, int64_t F, const float* lo, const float* hi, int G, SBox* bx) {
-  NERF_REQUIRE(G >= 2 && G <= NERF_MESH_MAX_RES, NERF_E_SHAPE, "%s: need 2 <= grid <= %d (got %d)", who, NERF_MESH_MAX_RES, G);
+// the grid and the item counts: all that nerf_simplify_count takes
+int simp_size_check(const char* who, int64_t V, int64_t F, int G) {
+  const int rc = lattice_res_check(who, G, "grid");
+  if (rc) return rc;
   NERF_REQUIRE(V >= 0 && V <= SIMP_MAX_ITEMS && F >= 0 && F <= SIMP_MAX_ITEMS, NERF_E_SHAPE,
                "%s: need 0 <= V, F <= 2^24 (got %lld, %lld)", who, (long long)V, (long long)F);
+  return NERF_OK;
+}
+
+int simp_check(const char* who, int64_t V, int64_t F, const float* lo, const float* hi, int G, SBox* bx) {
+  int rc = simp_size_check(who, V, F, G);
+  if (rc) return rc;
   NERF_REQUIRE(lo && hi, NERF_E_NULL, "%s: NULL lo / hi", who);
-  const int64_t cells = (int64_t)G * G * G;
+  const int64_t cells = lattice_n3(G);
   NERF_REQUIRE((V < cells ? V : cells) <= (1ll << SIMP_KEY_BITS), NERF_E_SHAPE,
                "%s: min(V, grid^3) = %lld clusters do not fit %d bits", who, (long long)(V < cells ? V : cells), SIMP_KEY_BITS);
+  rc = box_check(who, lo, hi);
+  if (rc) return rc;
   for (int a = 0; a < 3; ++a) {
-    NERF_REQUIRE(std::isfinite(lo[a]) && std::isfinite(hi[a]) && lo[a] < hi[a], NERF_E_SHAPE,
-                 "%s: need finite lo[%d] < hi[%d] (got %g, %g)", who, a, a, (double)lo[a], (double)hi[a]);
     const double ext = (double)hi[a] - (double)lo[a];
     bx->lo[a] = (double)lo[a];
     bx->inv[a] = (double)G / ext;
@@ -459,17 +460,7 @@ int simp_check(const char* who, int64_t V, int64_t F, const float* lo, const flo
   return NERF_OK;
 }
 
-#define SIMP_LAUNCH(what, kernel, blocks, ...)                                                          \
-  do {                                                                                                  \
-    hipLaunchKernelGGL(kernel, dim3((unsigned)(blocks)), dim3(SIMP_BLOCK), 0, st, __VA_ARGS__);         \
-    const int rc_ = check_launch(what);                                                                 \
-    if (rc_) return rc_;                                                                                \
-  } while (0)
-
-int simp_scan(const char* what, int64_t* blk, int64_t nblk, int64_t* total, hipStream_t st) {
-  hipLaunchKernelGGL(occ_cull_scan_kernel, dim3(1), dim3(1024), 0, st, blk, nblk, total);
-  return check_launch(what);
-}
+#define SIMP_LAUNCH(what, kernel, blocks, ...) NERF_LAUNCH(what, kernel, blocks, SIMP_BLOCK, st, __VA_ARGS__)
 
 }  // namespace
 }  // namespace nerf
@@ -477,7 +468,7 @@ int simp_scan(const char* what, int64_t* blk, int64_t nblk, int64_t* total, hipS
 using namespace nerf;
 
 extern "C" int64_t nerf_simplify_workspace_bytes(int64_t V, int64_t F, int grid) {
-  if (grid < 2 || grid > NERF_MESH_MAX_RES || V < 0 || V > SIMP_MAX_ITEMS || F < 0 || F > SIMP_MAX_ITEMS) return -1;
+  if (!lattice_res_ok(grid) || V < 0 || V > SIMP_MAX_ITEMS || F < 0 || F > SIMP_MAX_ITEMS) return -1;
   return simp_ws(nullptr, V, F, grid).bytes;
 }
 
@@ -495,7 +486,7 @@ extern "C" int nerf_simplify_cluster(const float* verts, const float* normals, c
   if (e != hipSuccess) return fail(NERF_E_HIP, "nerf_simplify_cluster: %s", hipGetErrorString(e));
   SIMP_LAUNCH("nerf_simplify_cluster (keys)", simp_keys_kernel, blocks_of(V), verts, (int)V, bx, w.mask, w.vcid);
   SIMP_LAUNCH("nerf_simplify_cluster (word counts)", simp_words_count_kernel, w.nblk_w, (const u64*)w.mask, w.W, w.blk_w);
-  rc = simp_scan("nerf_simplify_cluster (scan of the words)", w.blk_w, w.nblk_w, w.cnt, st);
+  rc = scan_launch("nerf_simplify_cluster (scan of the words)", w.blk_w, w.nblk_w, w.cnt, st);
   if (rc) return rc;
   SIMP_LAUNCH("nerf_simplify_cluster (word prefixes)", simp_words_write_kernel, w.nblk_w, (const u64*)w.mask, w.W,
               (const int64_t*)w.blk_w, w.wpre);
@@ -510,10 +501,8 @@ extern "C" int nerf_simplify_cluster(const float* verts, const float* normals, c
 
 extern "C" int nerf_simplify_count(const int64_t* sorted_keys, const int64_t* perm, int64_t V, const int32_t* faces, int64_t F,
                                    int grid, void* workspace, int64_t* totals, void* stream) {
-  NERF_REQUIRE(grid >= 2 && grid <= NERF_MESH_MAX_RES, NERF_E_SHAPE, "nerf_simplify_count: need 2 <= grid <= %d (got %d)",
-               NERF_MESH_MAX_RES, grid);
-  NERF_REQUIRE(V >= 0 && V <= SIMP_MAX_ITEMS && F >= 0 && F <= SIMP_MAX_ITEMS, NERF_E_SHAPE,
-               "nerf_simplify_count: need 0 <= V, F <= 2^24 (got %lld, %lld)", (long long)V, (long long)F);
+  int rc = simp_size_check("nerf_simplify_count", V, F, grid);
+  if (rc) return rc;
   NERF_REQUIRE(totals, NERF_E_NULL, "nerf_simplify_count: NULL totals");
   if (V == 0 || F == 0) return zero_i64("nerf_simplify_count", totals, 3, stream);
   NERF_REQUIRE(sorted_keys && perm && faces && workspace, NERF_E_NULL, "nerf_simplify_count: NULL pointer");
@@ -522,9 +511,9 @@ extern "C" int nerf_simplify_count(const int64_t* sorted_keys, const int64_t* pe
   const int n = (int)F;
   const uint8_t* par = w.par;
   SIMP_LAUNCH("nerf_simplify_count (runs)", simp_runs_count_kernel, w.nblk_f, sorted_keys, perm, par, n, w.blk_s, w.nblk_f);
-  int rc = simp_scan("nerf_simplify_count (scan of the run heads)", w.blk_s, w.nblk_f, w.cnt + 1, st);
+  rc = scan_launch("nerf_simplify_count (scan of the run heads)", w.blk_s, w.nblk_f, w.cnt + 1, st);
   if (rc) return rc;
-  rc = simp_scan("nerf_simplify_count (scan of the odd faces)", w.blk_s + w.nblk_f, w.nblk_f, w.cnt + 2, st);
+  rc = scan_launch("nerf_simplify_count (scan of the odd faces)", w.blk_s + w.nblk_f, w.nblk_f, w.cnt + 2, st);
   if (rc) return rc;
   SIMP_LAUNCH("nerf_simplify_count (run ranks)", simp_runs_write_kernel, w.nblk_f, sorted_keys, perm, par, n,
               (const int64_t*)w.blk_s, w.nblk_f, (const int64_t*)w.cnt, w.rid, w.heads, w.odd);
@@ -532,11 +521,11 @@ extern "C" int nerf_simplify_count(const int64_t* sorted_keys, const int64_t* pe
               (const int*)w.rid, (const int*)w.heads, (const int*)w.odd, (const int*)w.vcid, (int)V, w.keep, w.used);
   SIMP_LAUNCH("nerf_simplify_count (used clusters)", simp_flags_count_kernel, w.nblk_c, (const int*)w.used, (const int64_t*)w.cnt,
               (int64_t)0, w.blk_c);
-  rc = simp_scan("nerf_simplify_count (scan of the clusters)", w.blk_c, w.nblk_c, totals, st);
+  rc = scan_launch("nerf_simplify_count (scan of the clusters)", w.blk_c, w.nblk_c, totals, st);
   if (rc) return rc;
   SIMP_LAUNCH("nerf_simplify_count (kept faces)", simp_flags_count_kernel, w.nblk_f, (const int*)w.keep, (const int64_t*)nullptr, F,
               w.blk_f);
-  rc = simp_scan("nerf_simplify_count (scan of the faces)", w.blk_f, w.nblk_f, totals + 1, st);
+  rc = scan_launch("nerf_simplify_count (scan of the faces)", w.blk_f, w.nblk_f, totals + 1, st);
   if (rc) return rc;
   const hipError_t e = hipMemcpyAsync(totals + 2, w.cnt, sizeof(int64_t), hipMemcpyDeviceToDevice, st);
   return e == hipSuccess ? NERF_OK : fail(NERF_E_HIP, "nerf_simplify_count: %s", hipGetErrorString(e));

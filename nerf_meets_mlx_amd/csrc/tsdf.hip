@@ -1,35 +1,24 @@
 // TSDF fusion of rendered depth / opacity maps into a truncated signed distance volume on the mesh-extraction lattice
 // (KinectFusion; nerfstudio's TSDF export).  Semantics in include/nerf_hip.h "TSDF fusion"; tests/_tsdf_ref.py reproduces every
-// output bit for bit.  No reference counterpart.  One lane per voxel, x fastest: a lane loads its D, Wt and flags once, folds up to
-// NERF_TSDF_MAX_VIEWS views into them in registers, in order, and stores once -- 18 B of state per voxel cross HBM per launch and
-// not per view; the maps (4 B per pixel each) are gathered, and at 16 views of 800 x 800 those gathers, not the state, are most
-// of the launch time.  The view parameters are kernel arguments (scalar loads, uniform over the launch).
-// Every voxel has one writer and the views are folded in call order: bit-reproducible, and
-// identical to one launch per view.
-#include <cmath>
-
-#include "common.h"
+// output bit for bit.  No reference counterpart.  The lattice, its box and its cell centres are lattice.h's.  One lane per voxel: a
+// lane loads its D, Wt and flags once, folds up to NERF_TSDF_MAX_VIEWS views into them in registers, in order, and stores once --
+// 18 B of state per voxel cross HBM per launch and not per view; the maps (4 B per pixel each) are gathered, and at 16 views of
+// 800 x 800 those gathers, not the state, are most of the launch time.  The view parameters are kernel
+// arguments (scalar loads, uniform over the launch).  Every voxel has one writer and the views are folded in call order:
+// bit-reproducible, and identical to one launch per view.
+#include "lattice.h"
 
 namespace nerf {
 namespace {
-
-constexpr int TSDF_BLOCK = 256;
-
-struct TsdfBox {
-  float lo[3], h[3];
-};
 
 struct TsdfViews {
   nerf_tsdf_view v[NERF_TSDF_MAX_VIEWS];
 };
 static_assert(sizeof(nerf_tsdf_view) == 16 * sizeof(float), "16 floats per view");
 
-// correctly rounded float32 division (as csrc/mesh.hip)
-__device__ __forceinline__ float div_rn(float a, float b) { return (float)((double)a / (double)b); }
-
-__global__ void __launch_bounds__(TSDF_BLOCK) tsdf_reset_kernel(float* __restrict__ D, float* __restrict__ Wt,
+__global__ void __launch_bounds__(LATTICE_BLOCK) tsdf_reset_kernel(float* __restrict__ D, float* __restrict__ Wt,
                                                                uint8_t* __restrict__ flags, int64_t n3) {
-  const int64_t p = (int64_t)blockIdx.x * TSDF_BLOCK + threadIdx.x;
+  const int64_t p = lattice_lane();
   if (p >= n3) return;
   D[p] = 0.0f;
   Wt[p] = 0.0f;
@@ -37,19 +26,17 @@ __global__ void __launch_bounds__(TSDF_BLOCK) tsdf_reset_kernel(float* __restric
 }
 
 // ---- integrate: 4 + 4 + 1 B read and written per voxel and launch; per view and voxel at most two gathered map reads.
-__global__ void __launch_bounds__(TSDF_BLOCK) tsdf_integrate_kernel(float* __restrict__ D, float* __restrict__ Wt,
-                                                                   uint8_t* __restrict__ flags, int R, TsdfBox bx, TsdfViews views,
+__global__ void __launch_bounds__(LATTICE_BLOCK) tsdf_integrate_kernel(float* __restrict__ D, float* __restrict__ Wt,
+                                                                   uint8_t* __restrict__ flags, Lattice bx, TsdfViews views,
                                                                    int n, int H, int W, const float* __restrict__ depth,
                                                                    const float* __restrict__ acc, float tau, float acc_min,
                                                                    float far, int carve) {
-  const int64_t n3 = (int64_t)R * R * R;
-  const int64_t lg = (int64_t)blockIdx.x * TSDF_BLOCK + threadIdx.x;
-  if (lg >= n3) return;
-  const int l = (int)lg;
-  const int c[3] = {l % R, (l / R) % R, l / (R * R)};
+  const int64_t lg = lattice_lane();
+  if (lg >= lattice_n3(bx.R)) return;
+  int c[3];
+  lattice_coords((int)lg, bx.R, c);
   float p[3];
-#pragma unroll
-  for (int a = 0; a < 3; ++a) p[a] = bx.lo[a] + ((float)c[a] + 0.5f) * bx.h[a];
+  lattice_centre(bx, c, p);                                                // bit for bit the points of marching cubes
   float d_mean = D[lg], wt = Wt[lg];
   const uint8_t f_in = flags[lg];
   uint8_t f = f_in;
@@ -94,10 +81,10 @@ __global__ void __launch_bounds__(TSDF_BLOCK) tsdf_integrate_kernel(float* __res
 }
 
 // ---- finish: 9 B read, 4 B written per voxel.
-__global__ void __launch_bounds__(TSDF_BLOCK) tsdf_volume_kernel(const float* __restrict__ D, const float* __restrict__ Wt,
+__global__ void __launch_bounds__(LATTICE_BLOCK) tsdf_volume_kernel(const float* __restrict__ D, const float* __restrict__ Wt,
                                                                 const uint8_t* __restrict__ flags, int64_t n3, float min_views,
                                                                 float* __restrict__ vol) {
-  const int64_t p = (int64_t)blockIdx.x * TSDF_BLOCK + threadIdx.x;
+  const int64_t p = lattice_lane();
   if (p >= n3) return;
   float v;
   if (Wt[p] >= min_views) v = 0.0f - D[p];
@@ -105,24 +92,17 @@ __global__ void __launch_bounds__(TSDF_BLOCK) tsdf_volume_kernel(const float* __
   vol[p] = v;
 }
 
-int tsdf_res_check(const char* who, int R) {
-  NERF_REQUIRE(R >= 2 && R <= NERF_MESH_MAX_RES, NERF_E_SHAPE, "%s: need 2 <= res <= %d (got %d)", who, NERF_MESH_MAX_RES, R);
-  return NERF_OK;
-}
-
-unsigned tsdf_blocks(int R) { return (unsigned)(((int64_t)R * R * R + TSDF_BLOCK - 1) / TSDF_BLOCK); }
-
 }  // namespace
 }  // namespace nerf
 
 using namespace nerf;
 
 extern "C" int nerf_tsdf_reset(float* D, float* Wt, uint8_t* flags, int res, void* stream) {
-  int rc = tsdf_res_check("nerf_tsdf_reset", res);
+  int rc = lattice_res_check("nerf_tsdf_reset", res);
   if (rc) return rc;
   NERF_REQUIRE(D && Wt && flags, NERF_E_NULL, "nerf_tsdf_reset: NULL pointer");
-  hipLaunchKernelGGL(tsdf_reset_kernel, dim3(tsdf_blocks(res)), dim3(TSDF_BLOCK), 0, as_stream(stream), D, Wt, flags,
-                     (int64_t)res * res * res);
+  hipLaunchKernelGGL(tsdf_reset_kernel, dim3(lattice_blocks(res)), dim3(LATTICE_BLOCK), 0, as_stream(stream), D, Wt, flags,
+                     lattice_n3(res));
   return check_launch("nerf_tsdf_reset");
 }
 
@@ -130,17 +110,11 @@ extern "C" int nerf_tsdf_integrate(float* D, float* Wt, uint8_t* flags, int res,
                                    const nerf_tsdf_view* views_host, int n, int H, int W, const float* depth, const float* acc,
                                    float trunc, float acc_min, float far, int carve, void* stream) {
   const char* who = "nerf_tsdf_integrate";
-  int rc = tsdf_res_check(who, res);
+  int rc = lattice_res_check(who, res);
   if (rc) return rc;
-  NERF_REQUIRE(lo && hi, NERF_E_NULL, "%s: NULL lo / hi", who);
-  TsdfBox bx;
-  for (int a = 0; a < 3; ++a) {
-    NERF_REQUIRE(std::isfinite(lo[a]) && std::isfinite(hi[a]) && lo[a] < hi[a], NERF_E_SHAPE,
-                 "%s: need finite lo[%d] < hi[%d] (got %g, %g)", who, a, a, (double)lo[a], (double)hi[a]);
-    bx.lo[a] = lo[a];
-    bx.h[a] = (hi[a] - lo[a]) / (float)res;                  // float32, two roundings (as nerf_mesh_points)
-    NERF_REQUIRE(bx.h[a] > 0.0f && std::isfinite(bx.h[a]), NERF_E_SHAPE, "%s: box too small or too large on axis %d", who, a);
-  }
+  Lattice bx;
+  rc = lattice_box(who, res, lo, hi, &bx);
+  if (rc) return rc;
   NERF_REQUIRE(n >= 0 && n <= NERF_TSDF_MAX_VIEWS, NERF_E_SHAPE, "%s: need 0 <= n <= %d views (got %d)", who, NERF_TSDF_MAX_VIEWS, n);
   // (float)H and (float)W are exact up to 2^24, and n H W then stays far inside int64
   NERF_REQUIRE(H > 0 && W > 0 && H <= (1 << 24) && W <= (1 << 24), NERF_E_SHAPE, "%s: need 1 <= H, W <= 2^24 (got %d x %d)", who, H, W);
@@ -158,18 +132,18 @@ extern "C" int nerf_tsdf_integrate(float* D, float* Wt, uint8_t* flags, int res,
     const float* x = views.v[s].c2w;                         // the 12 pose numbers, then fx, fy, cx, cy
     for (int q = 0; q < 16; ++q) NERF_REQUIRE(std::isfinite(x[q]), NERF_E_SHAPE, "%s: view %d: non-finite camera number %d", who, s, q);
   }
-  hipLaunchKernelGGL(tsdf_integrate_kernel, dim3(tsdf_blocks(res)), dim3(TSDF_BLOCK), 0, as_stream(stream), D, Wt, flags, res, bx,
+  hipLaunchKernelGGL(tsdf_integrate_kernel, dim3(lattice_blocks(res)), dim3(LATTICE_BLOCK), 0, as_stream(stream), D, Wt, flags, bx,
                      views, n, H, W, depth, acc, trunc, acc_min, far, carve);
   return check_launch(who);
 }
 
 extern "C" int nerf_tsdf_volume(const float* D, const float* Wt, const uint8_t* flags, int res, int min_views, float* vol_out,
                                 void* stream) {
-  int rc = tsdf_res_check("nerf_tsdf_volume", res);
+  int rc = lattice_res_check("nerf_tsdf_volume", res);
   if (rc) return rc;
   NERF_REQUIRE(min_views >= 1, NERF_E_SHAPE, "nerf_tsdf_volume: need min_views >= 1 (got %d)", min_views);
   NERF_REQUIRE(D && Wt && flags && vol_out, NERF_E_NULL, "nerf_tsdf_volume: NULL pointer");
-  hipLaunchKernelGGL(tsdf_volume_kernel, dim3(tsdf_blocks(res)), dim3(TSDF_BLOCK), 0, as_stream(stream), D, Wt, flags,
-                     (int64_t)res * res * res, (float)min_views, vol_out);
+  hipLaunchKernelGGL(tsdf_volume_kernel, dim3(lattice_blocks(res)), dim3(LATTICE_BLOCK), 0, as_stream(stream), D, Wt, flags,
+                     lattice_n3(res), (float)min_views, vol_out);
   return check_launch("nerf_tsdf_volume");
 }

@@ -110,11 +110,23 @@ def density_volume(query, activation: int, resolution: int, lo, hi, device="cuda
     return vol.view(R, R, R)
 
 
-def _marching_cubes(volume, iso, lo, hi, color_rows: bool):
+def _check_volume(who, volume, iso, lo=(0.0,) * 3, hi=(1.0,) * 3):
     if not torch.is_tensor(volume) or volume.dim() != 3 or volume.dtype != torch.float32 or not volume.is_contiguous() \
             or not (volume.shape[0] == volume.shape[1] == volume.shape[2]):
-        raise ValueError("marching_cubes: volume must be a contiguous float32 [R, R, R] tensor")
-    R, lo, hi, iso = check_mesh_args(volume.shape[0], lo, hi, iso)
+        raise ValueError(f"{who}: volume must be a contiguous float32 [R, R, R] tensor")
+    return check_mesh_args(volume.shape[0], lo, hi, iso)
+
+
+def _mark(mark, stage):
+    """The stage hook of connected_components, filter_components, erode, reconstruct, _open_components and _simplify:
+    mark(stage) just ahead of the stage's first C call (tools/ngp_mesh.py records a device event there).  None: nothing is
+    called."""
+    if mark is not None:
+        mark(stage)
+
+
+def _marching_cubes(volume, iso, lo, hi, color_rows: bool):
+    R, lo, hi, iso = _check_volume("marching_cubes", volume, iso, lo, hi)
     dev = volume.device
     L = N.lib()
     clo, chi = _box(lo, hi)
@@ -155,41 +167,38 @@ def check_component_args(min_component, largest_only, resolution: int):
     return int(min_component), largest_only
 
 
-def _check_volume(who, volume, iso):
-    if not torch.is_tensor(volume) or volume.dim() != 3 or volume.dtype != torch.float32 or not volume.is_contiguous() \
-            or not (volume.shape[0] == volume.shape[1] == volume.shape[2]):
-        raise ValueError(f"{who}: volume must be a contiguous float32 [R, R, R] tensor")
-    R, _, _, iso = check_mesh_args(volume.shape[0], [0.0] * 3, [1.0] * 3, iso)
-    return R, iso
-
-
-def connected_components(volume: torch.Tensor, iso: float) -> Components:
+def connected_components(volume: torch.Tensor, iso: float, mark=None) -> Components:
     """The 6-connected components of {v > iso} of a contiguous float32 [R, R, R] device volume (include/nerf_hip.h "connected
-    components"): nerf_ccl_label, nerf_ccl_sizes.  Device tensors; nothing is read on the host."""
-    R, iso = _check_volume("connected_components", volume, iso)
+    components"): nerf_ccl_label, nerf_ccl_sizes.  Device tensors; nothing is read on the host.  mark: _mark's hook ("label",
+    "sizes")."""
+    R, _, _, iso = _check_volume("connected_components", volume, iso)
     dev = volume.device
     L = N.lib()
     ws = torch.empty(L.nerf_ccl_workspace_bytes(R), dtype=torch.uint8, device=dev)
     labels = torch.empty(R, R, R, dtype=torch.int32, device=dev)
     sizes = torch.empty(R, R, R, dtype=torch.int32, device=dev)
     stats = torch.empty(3, dtype=torch.int64, device=dev)
+    _mark(mark, "label")
     N.check(L.nerf_ccl_label(N.ptr(volume), R, iso, N.ptr(ws), N.ptr(labels), N.stream()))
+    _mark(mark, "sizes")
     N.check(L.nerf_ccl_sizes(N.ptr(labels), R, N.ptr(sizes), N.ptr(stats), N.stream()))
     return Components(labels, sizes, stats)
 
 
 def filter_components(volume: torch.Tensor, iso: float, min_component: int = 0, largest_only: bool = False,
-                      components: Optional[Components] = None) -> torch.Tensor:
+                      components: Optional[Components] = None, mark=None) -> torch.Tensor:
     """A new volume in which every inside voxel of a component with fewer than `min_component` voxels -- and, with
     `largest_only`, of every component but the largest -- holds `iso` (outside); everything else is copied bit for bit
-    (nerf_ccl_filter).  `components`: connected_components(volume, iso) when the caller has it already."""
-    R, iso = _check_volume("filter_components", volume, iso)
+    (nerf_ccl_filter).  `components`: connected_components(volume, iso) when the caller has it already.  mark: _mark's hook
+    ("label" and "sizes" when the components are computed here, then "filter")."""
+    R, _, _, iso = _check_volume("filter_components", volume, iso)
     min_component, largest_only = check_component_args(min_component, largest_only, R)
-    c = components if components is not None else connected_components(volume, iso)
+    c = components if components is not None else connected_components(volume, iso, mark)
     for t, dt, shape in ((c.labels, torch.int32, (R, R, R)), (c.sizes, torch.int32, (R, R, R)), (c.stats, torch.int64, (3,))):
         if not torch.is_tensor(t) or t.dtype != dt or tuple(t.shape) != shape or not t.is_contiguous() or t.device != volume.device:
             raise ValueError("filter_components: components do not belong to this volume")
     out = torch.empty_like(volume)
+    _mark(mark, "filter")
     N.check(N.lib().nerf_ccl_filter(N.ptr(volume), N.ptr(c.labels), N.ptr(c.sizes), N.ptr(c.stats), R, iso, min_component,
                                     int(largest_only), N.ptr(out), N.stream()))
     return out
@@ -210,26 +219,29 @@ def _check_radius(who, radius) -> int:
     return int(radius)
 
 
-def erode(volume: torch.Tensor, iso: float, radius: int):
+def erode(volume: torch.Tensor, iso: float, radius: int, mark=None):
     """(core, stats): `radius` steps of 6-neighbour erosion of {v > iso}, a neighbour beyond the lattice counting as outside;
     in the new volume `core` every inside voxel the erosion removed holds `iso`, everything else is copied bit for bit
-    (nerf_morph_erode).  stats: int64 [2] device tensor = (inside voxels, core voxels); nothing is read on the host."""
-    R, iso = _check_volume("erode", volume, iso)
+    (nerf_morph_erode).  stats: int64 [2] device tensor = (inside voxels, core voxels); nothing is read on the host.
+    mark: _mark's hook ("erode")."""
+    R, _, _, iso = _check_volume("erode", volume, iso)
     radius = _check_radius("erode", radius)
     L = N.lib()
     ws = torch.empty(L.nerf_morph_workspace_bytes(R), dtype=torch.uint8, device=volume.device)
     core = torch.empty_like(volume)
     stats = torch.empty(2, dtype=torch.int64, device=volume.device)
+    _mark(mark, "erode")
     N.check(L.nerf_morph_erode(N.ptr(volume), R, iso, radius, N.ptr(ws), N.ptr(core), N.ptr(stats), N.stream()))
     return core, stats
 
 
-def reconstruct(volume: torch.Tensor, kept: torch.Tensor, iso: float, radius: int):
+def reconstruct(volume: torch.Tensor, kept: torch.Tensor, iso: float, radius: int, mark=None):
     """(out, stats): the seeds {kept > iso} inside {volume > iso} grown by exactly `radius` 6-neighbour steps that never leave
     {volume > iso} (geodesic dilation); in the new volume `out` every inside voxel of `volume` they did not reach holds `iso`,
     everything else is copied bit for bit (nerf_morph_reconstruct).  `kept` must match `volume` in shape, dtype and device.
-    stats: int64 [2] device tensor = (seed voxels, voxels reached); nothing is read on the host."""
-    R, iso = _check_volume("reconstruct", volume, iso)
+    stats: int64 [2] device tensor = (seed voxels, voxels reached); nothing is read on the host.
+    mark: _mark's hook ("reconstruct")."""
+    R, _, _, iso = _check_volume("reconstruct", volume, iso)
     radius = _check_radius("reconstruct", radius)
     if not torch.is_tensor(kept) or kept.shape != volume.shape or kept.dtype != volume.dtype or kept.device != volume.device \
             or not kept.is_contiguous():
@@ -238,6 +250,7 @@ def reconstruct(volume: torch.Tensor, kept: torch.Tensor, iso: float, radius: in
     ws = torch.empty(L.nerf_morph_workspace_bytes(R), dtype=torch.uint8, device=volume.device)
     out = torch.empty_like(volume)
     stats = torch.empty(2, dtype=torch.int64, device=volume.device)
+    _mark(mark, "reconstruct")
     N.check(L.nerf_morph_reconstruct(N.ptr(volume), N.ptr(kept), R, iso, radius, N.ptr(ws), N.ptr(out), N.ptr(stats), N.stream()))
     return out, stats
 
@@ -248,13 +261,23 @@ def open_components(volume: torch.Tensor, iso: float, radius: int, min_component
     min_component > 1 or largest_only, else the core itself (the plain opening by reconstruction); reconstruct(volume, kept, iso,
     radius).  `min_component` counts CORE voxels: a piece thinner than 2 radius + 1 voxels everywhere has none and is dropped
     whatever its size, and a field that thin everywhere yields an empty volume."""
-    R, iso = _check_volume("open_components", volume, iso)
+    return _open_components(volume, iso, radius, min_component, largest_only)[0]
+
+
+def _open_components(volume, iso, radius, min_component=0, largest_only=False, mark=None):
+    """open_components with what it computes on the way: (opened volume, core, the core's Components or None when no filter ran,
+    erode stats, reconstruct stats).  mark: _mark's hook ("erode", then "label", "sizes", "filter" when the filter runs,
+    "reconstruct")."""
+    R, _, _, iso = _check_volume("open_components", volume, iso)
     radius = _check_radius("open_components", radius)
     min_component, largest_only = check_component_args(min_component, largest_only, R)
-    kept, _ = erode(volume, iso, radius)
+    core, est = erode(volume, iso, radius, mark)
+    kept, comps = core, None
     if min_component > 1 or largest_only:
-        kept = filter_components(kept, iso, min_component, largest_only)
-    return reconstruct(volume, kept, iso, radius)[0]
+        comps = connected_components(core, iso, mark)
+        kept = filter_components(core, iso, min_component, largest_only, comps, mark)
+    out, rst = reconstruct(volume, kept, iso, radius, mark)
+    return out, core, comps, est, rst
 
 
 def check_tsdf_args(trunc=None, acc_min=0.5, far=1.0, carve=True, min_views=1, H=1, W=1):
@@ -418,7 +441,9 @@ def check_simplify_args(mesh, grid, lo: Sequence[float], hi: Sequence[float], pl
     return grid, lo, hi, PLACEMENTS[placement]
 
 
-def _simplify(mesh: Mesh, grid, lo, hi, placement, color_rows: bool):
+def _simplify(mesh: Mesh, grid, lo, hi, placement, color_rows: bool, mark=None):
+    """(Mesh, colour rows or None, clusters before the unused ones go).  mark: _mark's hook ("cluster", "sort", "count" -- it
+    ends behind the host read --, "write")."""
     G, lo, hi, code = check_simplify_args(mesh, grid, lo, hi, placement)
     dev = mesh.verts.device
     V, F = mesh.verts.shape[0], mesh.faces.shape[0]
@@ -427,11 +452,15 @@ def _simplify(mesh: Mesh, grid, lo, hi, placement, color_rows: bool):
     ws = torch.empty(L.nerf_simplify_workspace_bytes(V, F, G), dtype=torch.uint8, device=dev)
     keys = torch.empty(F, dtype=torch.int64, device=dev)
     tot = torch.empty(3, dtype=torch.int64, device=dev)
+    _mark(mark, "cluster")
     N.check(L.nerf_simplify_cluster(N.ptr(mesh.verts), N.ptr(mesh.normals), N.ptr(mesh.colors), V, N.ptr(mesh.faces), F, clo, chi,
                                     G, N.ptr(ws), N.ptr(keys), N.stream()))
+    _mark(mark, "sort")
     skeys, perm = torch.sort(keys, stable=True)               # plumbing between two of our launches: groups faces by vertex set
+    _mark(mark, "count")
     N.check(L.nerf_simplify_count(N.ptr(skeys), N.ptr(perm), V, N.ptr(mesh.faces), F, G, N.ptr(ws), N.ptr(tot), N.stream()))
-    V2, F2, _ = tot.tolist()                                  # the one host read
+    V2, F2, K = tot.tolist()                                  # the one host read
+    _mark(mark, "write")
     verts = torch.empty(V2, 3, dtype=torch.float32, device=dev)
     normals = torch.empty(V2, 3, dtype=torch.float32, device=dev)
     colors = torch.empty(V2, 3, dtype=torch.float32, device=dev) if mesh.colors is not None else None
@@ -440,7 +469,7 @@ def _simplify(mesh: Mesh, grid, lo, hi, placement, color_rows: bool):
     if V2 or F2:
         N.check(L.nerf_simplify_write(V, N.ptr(mesh.faces), F, clo, chi, G, code, N.ptr(ws), V2, F2, N.ptr(verts), N.ptr(normals),
                                       N.ptr(colors), N.ptr(rows), N.ptr(faces), N.stream()))
-    return Mesh(verts, faces, normals, colors), rows
+    return Mesh(verts, faces, normals, colors), rows, K
 
 
 def simplify(mesh: Mesh, grid: int, lo, hi, placement: str = "quadric") -> Mesh:
@@ -478,7 +507,7 @@ def mesh_volume(query, vol, iso, lo, hi, colors: bool, simplify_grid: int = 0, s
     """marching_cubes of `vol` at `iso` -> (with simplify_grid > 0: simplify) -> (with `colors`) vertex_colors of `query` on the
     final mesh's rows [x, -n, 0, 0, -n].  With simplify_grid 0 the calls are those of marching cubes and the colour query alone."""
     if simplify_grid > 0:
-        mesh, rows = _simplify(_marching_cubes(vol, iso, lo, hi, False)[0], simplify_grid, lo, hi, simplify_placement, colors)
+        mesh, rows = _simplify(_marching_cubes(vol, iso, lo, hi, False)[0], simplify_grid, lo, hi, simplify_placement, colors)[:2]
     else:
         mesh, rows = _marching_cubes(vol, iso, lo, hi, colors)
     if not colors:

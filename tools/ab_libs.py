@@ -11,6 +11,10 @@
         n = 3 and 64, "ngp_ray_major" 1 and 0, on seeded inputs: sha256 of the output, the packed
         buffer, the activation store (it holds the stored encodings), the dZ store (without the split-K partial slots), the
         gradients and d_x.  Exit 1 unless every digest is the same in every library.
+    python tools/ab_libs.py --volumes tools/diag/libnerf_A.so default
+        every volume entry (lattice points, marching cubes, components and both filters, erode / reconstruct at radius 1 and 2, TSDF
+        fusion of 3 synthetic views with carve on and off, the simplifier at grid 8 with both placements) at R = 17 and 65 on a smooth,
+        a noise and a NaN / +-inf volume, iso 0.25, over a non-cubic box: sha256 of every output.  Exit 1 unless all are the same.
 Every child runs under a time limit, and after a child that failed or ran out of time no further child is started."""
 import argparse, json, os, subprocess, sys, tempfile
 CHILD = r'''
@@ -116,20 +120,73 @@ for n in (3, 64):
         N.check(lib.nerf_set_option(b"ngp_ray_major", 1))
 print(json.dumps(res))
 '''
+CHILD_VOLUMES = r'''
+import sys, json, hashlib, numpy as np, torch
+sys.path.insert(0, ".")
+from nerf_meets_mlx_amd.engine import mesh
+dev, res, iso, lo, hi = "cuda", {}, 0.25, [-1.5, -0.7, 0.1], [1.5, 2.3, 0.35]
+sha = lambda t: hashlib.sha256(t.contiguous().cpu().numpy().tobytes()).hexdigest()[:16]
+def volumes(R, g):
+    x = torch.linspace(-1, 1, R)
+    k, j, i = torch.meshgrid(x, x, x, indexing="ij")
+    noise = torch.rand(R, R, R, generator=g)
+    odd = noise.clone().reshape(-1)
+    at = torch.randperm(R ** 3, generator=g)[:3 * (R ** 3 // 50)].reshape(3, -1)
+    odd[at[0]], odd[at[1]], odd[at[2]] = float("nan"), float("inf"), float("-inf")
+    return {"smooth": 0.9 - (i * i + 0.6 * j * j + k * k) + 0.2 * torch.sin(7 * i) * torch.cos(5 * j + 3 * k), "noise": noise,
+            "nan_inf": odd.reshape(R, R, R)}
+for R in (17, 65):
+    g = torch.Generator().manual_seed(100 + R)
+    rays, z = mesh.lattice_rows(R, lo, hi, device=dev)
+    res[f"R={R} points"] = {"rays": sha(rays), "z": sha(z)}
+    for name, v in volumes(R, g).items():
+        v, tag = v.to(dev).contiguous(), f"R={R} {name}"
+        m, rows = mesh._marching_cubes(v, iso, lo, hi, True)
+        res[f"{tag} marching cubes"] = {"verts": sha(m.verts), "normals": sha(m.normals), "rows": sha(rows), "faces": sha(m.faces),
+                                        "V": m.verts.shape[0], "F": m.faces.shape[0]}
+        c = mesh.connected_components(v, iso)
+        res[f"{tag} components"] = {"labels": sha(c.labels), "sizes": sha(c.sizes), "stats": sha(c.stats),
+                                    "min5": sha(mesh.filter_components(v, iso, 5, False, c)),
+                                    "largest": sha(mesh.filter_components(v, iso, 0, True, c))}
+        for r in (1, 2):
+            core, est = mesh.erode(v, iso, r)
+            out, rst = mesh.reconstruct(v, core, iso, r)
+            res[f"{tag} opening r={r}"] = {"core": sha(core), "erode_stats": sha(est), "out": sha(out), "reconstruct_stats": sha(rst)}
+        if m.verts.shape[0] and m.faces.shape[0]:
+            for placement in ("quadric", "mean"):
+                s, srows, K = mesh._simplify(m, 8, lo, hi, placement, True)
+                res[f"{tag} simplify {placement}"] = {"verts": sha(s.verts), "normals": sha(s.normals), "rows": sha(srows),
+                                                      "faces": sha(s.faces), "K": K}
+    H = W = 32
+    c2w = torch.tensor([[[1, 0, 0, 0], [0, 1, 0, 0.8], [0, 0, 1, 4]], [[1, 0, 0, 0.5], [0, 1, 0, 0.3], [0, 0, 1, 3]],
+                        [[-1, 0, 0, 0], [0, 1, 0, 0.8], [0, 0, -1, -3]]], dtype=torch.float64)
+    K = torch.tensor([[20.0, 0, 16], [0, 20.0, 16], [0, 0, 1]], dtype=torch.float64)
+    acc = torch.rand(3, H, W, generator=g)
+    depth = acc * (2.5 + 2.0 * torch.rand(3, H, W, generator=g))
+    depth[0, 3, 4], acc[1, 5, 6] = float("nan"), float("nan")
+    for carve in (True, False):
+        t = mesh.TSDFVolume(R, lo, hi, device=dev).integrate(depth.to(dev), acc.to(dev), c2w, K, H, W, far=6.0, carve=carve)
+        res[f"R={R} tsdf carve={carve}"] = {"D": sha(t.D), "Wt": sha(t.Wt), "flags": sha(t.flags), "volume": sha(t.volume(1)),
+                                            "observed": int((t.Wt > 0).sum())}
+torch.cuda.synchronize()
+print(json.dumps(res))
+'''
 ap = argparse.ArgumentParser(); ap.add_argument("libs", nargs="+"); ap.add_argument("--rounds", type=int, default=None); ap.add_argument("--precision", type=int, default=22)
 ap.add_argument("--models", action="store_true", help="digests of every MLP model instead of the render-chunk timing")
+ap.add_argument("--volumes", action="store_true", help="digests of every volume entry (mesh, components, opening, TSDF, simplifier)")
 ap.add_argument("--timeout", type=float, default=300.0, help="seconds per child process")
 ap.add_argument("--fold-differs", action="store_true", help="the builds differ in NERF_F22_FOLD: colour differences are reported, not failed")
 a = ap.parse_args()
-rounds = a.rounds if a.rounds is not None else (1 if a.models else 3)
+digests_of = CHILD_MODELS if a.models else CHILD_VOLUMES if a.volumes else None
+rounds = a.rounds if a.rounds is not None else (1 if digests_of else 3)
 acc = {l: [] for l in a.libs}
-tmp = None if a.models else tempfile.mkdtemp(prefix="ab_libs_")
+tmp = None if digests_of else tempfile.mkdtemp(prefix="ab_libs_")
 for r in range(rounds):
     for i, l in enumerate(a.libs):
         env = dict(os.environ)
         if l != "default": env["NERF_HIP_LIB"] = os.path.abspath(l)
         else: env.pop("NERF_HIP_LIB", None)
-        cmd = [sys.executable, "-c", CHILD_MODELS] if a.models else [sys.executable, "-c", CHILD, str(a.precision)] + ([os.path.join(tmp, f"lib{i}")] if r == 0 else [])
+        cmd = [sys.executable, "-c", digests_of] if digests_of else [sys.executable, "-c", CHILD, str(a.precision)] + ([os.path.join(tmp, f"lib{i}")] if r == 0 else [])
         try:
             out = subprocess.run(cmd, capture_output=True, text=True, env=env, timeout=a.timeout)
         except subprocess.TimeoutExpired:
@@ -138,7 +195,7 @@ for r in range(rounds):
         if out.returncode != 0 or not line:
             sys.exit(f"{l}: child FAILED (exit {out.returncode}); no further child is started\n{out.stderr[-2000:]}")
         acc[l].append(json.loads(line[-1]))
-if a.models:
+if digests_of:
     ref, bad = acc[a.libs[0]][0], 0
     for case, digests in ref.items():
         same = all(run.get(case) == digests for l in a.libs for run in acc[l])

@@ -99,100 +99,57 @@ def _geometry(verts, R, bound, boxes):
             "beyond_2h": int((~near2).sum())}
 
 
+class _Stages:
+    """The `mark` hook of engine.mesh: a device event ahead of each stage's first C call, so what is timed is the engine's own
+    call sequence.  ms(): {stage: device ms up to the next mark}; the caller closes the last stage with mark("end")."""
+
+    def __init__(self):
+        self.names, self.events = [], []
+
+    def __call__(self, name):
+        self.names.append(name)
+        self.events.append(torch.cuda.Event(enable_timing=True))
+        self.events[-1].record()
+
+    def ms(self):
+        torch.cuda.synchronize()
+        return {n: e0.elapsed_time(e1) for n, e0, e1 in zip(self.names, self.events, self.events[1:])}
+
+
 def _components_timed(vol, iso, min_component, largest_only):
-    """engine.mesh.connected_components + filter_components as their three C calls, each between device events:
-    (Components, filtered volume, [label ms, sizes ms, filter ms])."""
-    from nerf_meets_mlx_amd import _native as N
+    """engine.mesh.connected_components + filter_components: (Components, filtered volume, [label ms, sizes ms, filter ms])."""
     from nerf_meets_mlx_amd.engine import mesh
-    L = N.lib()
-    R, dev = vol.shape[0], vol.device
-    ws = torch.empty(L.nerf_ccl_workspace_bytes(R), dtype=torch.uint8, device=dev)
-    labels = torch.empty(R, R, R, dtype=torch.int32, device=dev)
-    sizes = torch.empty(R, R, R, dtype=torch.int32, device=dev)
-    stats = torch.empty(3, dtype=torch.int64, device=dev)
-    out = torch.empty_like(vol)
-    e = [torch.cuda.Event(enable_timing=True) for _ in range(4)]
-    e[0].record()
-    N.check(L.nerf_ccl_label(N.ptr(vol), R, iso, N.ptr(ws), N.ptr(labels), N.stream()))
-    e[1].record()
-    N.check(L.nerf_ccl_sizes(N.ptr(labels), R, N.ptr(sizes), N.ptr(stats), N.stream()))
-    e[2].record()
-    N.check(L.nerf_ccl_filter(N.ptr(vol), N.ptr(labels), N.ptr(sizes), N.ptr(stats), R, iso, min_component, int(largest_only),
-                              N.ptr(out), N.stream()))
-    e[3].record()
-    torch.cuda.synchronize()
-    return mesh.Components(labels, sizes, stats), out, [e[k].elapsed_time(e[k + 1]) for k in range(3)]
+    st = _Stages()
+    comps = mesh.connected_components(vol, iso, st)
+    out = mesh.filter_components(vol, iso, min_component, largest_only, comps, st)
+    st("end")
+    t = st.ms()
+    return comps, out, [t["label"], t["sizes"], t["filter"]]
 
 
 def _opening_timed(vol, iso, radius, min_component, largest_only):
-    """engine.mesh.open_components as its C calls, each between device events: (Components of the core, opened volume,
-    [erode, label, sizes, filter, reconstruct] ms, [|M|, |E|, |K|, |D_r|])."""
-    from nerf_meets_mlx_amd import _native as N
+    """engine.mesh.open_components: (Components of the core, opened volume, [erode, label, sizes, filter, reconstruct] ms, [|M|,
+    |E|, |K|, |D_r|]).  Without a filter the engine does not label the core: it is labelled here, behind the opening, for the
+    core's statistics, and timed as label / sizes all the same (filter: 0)."""
     from nerf_meets_mlx_amd.engine import mesh
-    L = N.lib()
-    R, dev = vol.shape[0], vol.device
-    ws = torch.empty(L.nerf_morph_workspace_bytes(R), dtype=torch.uint8, device=dev)
-    ccl_ws = torch.empty(L.nerf_ccl_workspace_bytes(R), dtype=torch.uint8, device=dev)
-    core, kept, out = torch.empty_like(vol), torch.empty_like(vol), torch.empty_like(vol)
-    labels = torch.empty(R, R, R, dtype=torch.int32, device=dev)
-    sizes = torch.empty(R, R, R, dtype=torch.int32, device=dev)
-    stats = torch.empty(3, dtype=torch.int64, device=dev)
-    est, rst = (torch.empty(2, dtype=torch.int64, device=dev) for _ in range(2))
-    filt = min_component > 1 or largest_only
-    e = [torch.cuda.Event(enable_timing=True) for _ in range(6)]
-    e[0].record()
-    N.check(L.nerf_morph_erode(N.ptr(vol), R, iso, radius, N.ptr(ws), N.ptr(core), N.ptr(est), N.stream()))
-    e[1].record()
-    N.check(L.nerf_ccl_label(N.ptr(core), R, iso, N.ptr(ccl_ws), N.ptr(labels), N.stream()))
-    e[2].record()
-    N.check(L.nerf_ccl_sizes(N.ptr(labels), R, N.ptr(sizes), N.ptr(stats), N.stream()))
-    e[3].record()
-    if filt:
-        N.check(L.nerf_ccl_filter(N.ptr(core), N.ptr(labels), N.ptr(sizes), N.ptr(stats), R, iso, min_component, int(largest_only),
-                                  N.ptr(kept), N.stream()))
-    e[4].record()
-    N.check(L.nerf_morph_reconstruct(N.ptr(vol), N.ptr(kept if filt else core), R, iso, radius, N.ptr(ws), N.ptr(out), N.ptr(rst),
-                                     N.stream()))
-    e[5].record()
-    torch.cuda.synchronize()
-    return (mesh.Components(labels, sizes, stats), out, [e[k].elapsed_time(e[k + 1]) for k in range(5)],
-            est.tolist() + rst.tolist())
+    st = _Stages()
+    out, core, comps, est, rst = mesh._open_components(vol, iso, radius, min_component, largest_only, st)
+    st("end")
+    if comps is None:
+        comps = mesh.connected_components(core, iso, st)
+        st("end")
+    t = st.ms()
+    return (comps, out, [t["erode"], t["label"], t["sizes"], t.get("filter", 0.0), t["reconstruct"]], est.tolist() + rst.tolist())
 
 
 def _simplify_timed(m, G, lo, hi, placement):
-    """engine.mesh.simplify as its calls, each between device events: (Mesh, clusters, [cluster, sort, count + the host read,
-    write] ms)."""
-    import ctypes as C
-    from nerf_meets_mlx_amd import _native as N
+    """engine.mesh.simplify: (Mesh, clusters, [cluster, sort, count + the host read, write] ms)."""
     from nerf_meets_mlx_amd.engine import mesh
-    L = N.lib()
-    G, lo, hi, code = mesh.check_simplify_args(m, G, lo, hi, placement)
-    dev = m.verts.device
-    V, F = m.verts.shape[0], m.faces.shape[0]
-    clo, chi = (C.c_float * 3)(*lo), (C.c_float * 3)(*hi)
-    ws = torch.empty(L.nerf_simplify_workspace_bytes(V, F, G), dtype=torch.uint8, device=dev)
-    keys = torch.empty(F, dtype=torch.int64, device=dev)
-    tot = torch.empty(3, dtype=torch.int64, device=dev)
-    e = [torch.cuda.Event(enable_timing=True) for _ in range(5)]
-    e[0].record()
-    N.check(L.nerf_simplify_cluster(N.ptr(m.verts), N.ptr(m.normals), N.ptr(m.colors), V, N.ptr(m.faces), F, clo, chi, G, N.ptr(ws),
-                                    N.ptr(keys), N.stream()))
-    e[1].record()
-    skeys, perm = torch.sort(keys, stable=True)
-    e[2].record()
-    N.check(L.nerf_simplify_count(N.ptr(skeys), N.ptr(perm), V, N.ptr(m.faces), F, G, N.ptr(ws), N.ptr(tot), N.stream()))
-    V2, F2, K = tot.tolist()
-    e[3].record()
-    verts = torch.empty(V2, 3, dtype=torch.float32, device=dev)
-    normals = torch.empty(V2, 3, dtype=torch.float32, device=dev)
-    colors = torch.empty(V2, 3, dtype=torch.float32, device=dev) if m.colors is not None else None
-    faces = torch.empty(F2, 3, dtype=torch.int32, device=dev)
-    if V2 or F2:
-        N.check(L.nerf_simplify_write(V, N.ptr(m.faces), F, clo, chi, G, code, N.ptr(ws), V2, F2, N.ptr(verts), N.ptr(normals),
-                                      N.ptr(colors), None, N.ptr(faces), N.stream()))
-    e[4].record()
-    torch.cuda.synchronize()
-    return mesh.Mesh(verts, faces, normals, colors), K, [e[k].elapsed_time(e[k + 1]) for k in range(4)]
+    st = _Stages()
+    sm, _, K = mesh._simplify(m, G, lo, hi, placement, False, st)
+    st("end")
+    t = st.ms()
+    return sm, K, [t["cluster"], t["sort"], t["count"], t["write"]]
 
 
 def _simplify_arms(m, source, R, lo, hi, a, rec, bound, boxes, extra=None):
