@@ -43,10 +43,18 @@ static inline int grid_for(int64_t work_items, int block, int max_blocks = 256 *
   if (g > max_blocks) g = max_blocks;
   return (int)g;
 }
+// the kernels with one wave per ray: four rays per 256-thread workgroup, at most max_blocks workgroups striding over the rest
+static inline int wave_per_ray_grid(int64_t B, int max_blocks = 8192) { return grid_for(B, 4, max_blocks); }
 
 // A runtime bool as a template argument: fn receives std::true_type / std::false_type, and a generic lambda names the
 // kernel instantiation with decltype(arg)::value.  Nested calls list every combination once, in one place.  Returns what fn returns.
 template <class Fn> static inline auto with_bool(bool b, Fn&& fn) { if (b) return fn(std::true_type{}); else return fn(std::false_type{}); }
+// A runtime int as a template argument: fn receives std::integral_constant<int, V> for the first V of the list with v <= V
+// (the last one if there is none).  Returns what fn returns.
+template <int V, int... Vs, class Fn> static inline auto with_int_up_to(int v, Fn&& fn) {
+  if constexpr (sizeof...(Vs) > 0) { if (v > V) return with_int_up_to<Vs...>(v, std::forward<Fn>(fn)); }
+  return fn(std::integral_constant<int, V>{});
+}
 
 // ---- wave64 scans / reductions.  float: DPP (v_add_f32 ... row_shr / row_shl / row_bcast: the data path of the
 // VALU, no LDS crossbar round trip per step as with ds_bpermute shuffles); double: shuffles (the one double scan,
@@ -98,6 +106,14 @@ __device__ __forceinline__ float wave_rscan_incl(float v, int lane) {
   const int row = lane >> 4;
   const float above = row == 0 ? (t1 + (t2 + t3)) : row == 1 ? (t2 + t3) : row == 2 ? t3 : 0.0f;
   return v + above;
+}
+
+// one loss sum of a 256-thread workgroup: the four waves' partial sums (lane 0 of wave wv holds v) through 16 B of LDS, one
+// atomic per block
+__device__ __forceinline__ void block_loss_add(float* part, int lane, int wv, float v, float scale, float* __restrict__ out) {
+  if (lane == 0) part[wv] = v;
+  __syncthreads();
+  if (threadIdx.x == 0 && out) atomicAdd(out, (part[0] + part[1] + part[2] + part[3]) * scale);
 }
 
 }  // namespace nerf

@@ -48,6 +48,31 @@ __device__ __forceinline__ void composite_lane(const float* __restrict__ raw, co
   }
 }
 
+__device__ __forceinline__ float ray_dnorm(const float* rays, int64_t ray) {      // |d|
+  const float* rr = rays + ray * NERF_RAY_STRIDE;
+  return sqrtf(rr[3] * rr[3] + rr[4] * rr[4] + rr[5] * rr[5]);
+}
+
+// the ray's sums over its samples, in every lane: colour (with the white background added), acc, and with DEPTH the depth
+struct RaySums { float r, g, b, a, d; };
+template <bool DEPTH, int CH>
+__device__ __forceinline__ RaySums composite_sums(const RayQ (&q)[CH], int white) {
+  float sr = 0, sg = 0, sb = 0, sd = 0, sa = 0;
+#pragma unroll
+  for (int c = 0; c < CH; ++c) {
+    sr += q[c].w * q[c].r; sg += q[c].w * q[c].g; sb += q[c].w * q[c].b;
+    if (DEPTH) sd += q[c].w * q[c].z;
+    sa += q[c].w;
+  }
+  sr = wave_sum(sr); sg = wave_sum(sg); sb = wave_sum(sb); sa = wave_sum(sa);
+  if (DEPTH) sd = wave_sum(sd);
+  if (white) { sr = sr + (1.0f - sa); sg = sg + (1.0f - sa); sb = sb + (1.0f - sa); }             // render.py:91-92
+  return {sr, sg, sb, sa, sd};
+}
+
+// (The ray's adjoint stays written out in the backward and in the training kernel: folded into one function, the training
+// kernel's instances with CH >= 2 returned NaNs of the other sign on rays whose d_raw is NaN throughout -- DESIGN.md section 29.)
+
 template <int CH>
 __global__ void __launch_bounds__(256) composite_fwd_kernel(const float* __restrict__ raw, const float* __restrict__ z,
                                                             const float* __restrict__ rays, int64_t B, int n,
@@ -57,29 +82,25 @@ __global__ void __launch_bounds__(256) composite_fwd_kernel(const float* __restr
                                                             float* __restrict__ weights, float* __restrict__ depth) {
   const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
   for (int64_t ray = blockIdx.x * 4 + wv; ray < B; ray += (int64_t)gridDim.x * 4) {
-    const float* rr = rays + ray * NERF_RAY_STRIDE;
-    const float dnorm = sqrtf(rr[3] * rr[3] + rr[4] * rr[4] + rr[5] * rr[5]);
     RayQ q[CH];
-    composite_lane<CH>(raw + ray * n * 4, z + ray * n, noise ? noise + ray * n : nullptr, raw_noise_std, dnorm, n,
-                       lane, q);
-    float sr = 0, sg = 0, sb = 0, sd = 0, sa = 0;
+    composite_lane<CH>(raw + ray * n * 4, z + ray * n, noise ? noise + ray * n : nullptr, raw_noise_std,
+                       ray_dnorm(rays, ray), n, lane, q);
+    if (weights) {
 #pragma unroll
-    for (int c = 0; c < CH; ++c) {
-      sr += q[c].w * q[c].r; sg += q[c].w * q[c].g; sb += q[c].w * q[c].b;
-      sd += q[c].w * q[c].z; sa += q[c].w;
-      const int k = lane * CH + c;
-      if (weights && k < n) weights[ray * n + k] = q[c].w;
+      for (int c = 0; c < CH; ++c) {
+        const int k = lane * CH + c;
+        if (k < n) weights[ray * n + k] = q[c].w;
+      }
     }
-    sr = wave_sum(sr); sg = wave_sum(sg); sb = wave_sum(sb); sd = wave_sum(sd); sa = wave_sum(sa);
+    const RaySums s = composite_sums<true>(q, white);
     if (lane == 0) {
-      if (white) { sr = sr + (1.0f - sa); sg = sg + (1.0f - sa); sb = sb + (1.0f - sa); }   // render.py:91-92
-      rgb[ray * 3 + 0] = sr; rgb[ray * 3 + 1] = sg; rgb[ray * 3 + 2] = sb;
+      rgb[ray * 3 + 0] = s.r; rgb[ray * 3 + 1] = s.g; rgb[ray * 3 + 2] = s.b;
       if (disp) {                                     // render.py:85-88; maximum() propagates NaN: acc == 0 -> NaN (Q11)
-        const float q = sd / sa;
+        const float q = s.d / s.a;
         disp[ray] = 1.0f / ((q != q) ? q : fmaxf(1e-10f, q));
       }
-      if (acc) acc[ray] = sa;
-      if (depth) depth[ray] = sd;
+      if (acc) acc[ray] = s.a;
+      if (depth) depth[ray] = s.d;
     }
   }
 }
@@ -94,11 +115,9 @@ __global__ void __launch_bounds__(256) composite_bwd_kernel(const float* __restr
                                                             float* __restrict__ d_raw) {
   const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
   for (int64_t ray = blockIdx.x * 4 + wv; ray < B; ray += (int64_t)gridDim.x * 4) {
-    const float* rr = rays + ray * NERF_RAY_STRIDE;
-    const float dnorm = sqrtf(rr[3] * rr[3] + rr[4] * rr[4] + rr[5] * rr[5]);
     RayQ q[CH];
-    composite_lane<CH>(raw + ray * n * 4, z + ray * n, noise ? noise + ray * n : nullptr, raw_noise_std, dnorm, n,
-                       lane, q);
+    composite_lane<CH>(raw + ray * n * 4, z + ray * n, noise ? noise + ray * n : nullptr, raw_noise_std,
+                       ray_dnorm(rays, ray), n, lane, q);
     const float gr = d_rgb[ray * 3], gg = d_rgb[ray * 3 + 1], gb = d_rgb[ray * 3 + 2];
     // d rgb / d acc = -1 per channel under the white background; acc = sum w
     const float gacc = (d_acc ? d_acc[ray] : 0.0f) - (white ? (gr + gg + gb) : 0.0f);
@@ -144,19 +163,13 @@ __global__ void __launch_bounds__(256) composite_train_kernel(const float* __res
   const float inv = 1.0f / (float)(B * 3);
   float sq = 0.0f;
   for (int64_t ray = blockIdx.x * 4 + wv; ray < B; ray += (int64_t)gridDim.x * 4) {
-    const float* rr = rays + ray * NERF_RAY_STRIDE;
-    const float dnorm = sqrtf(rr[3] * rr[3] + rr[4] * rr[4] + rr[5] * rr[5]);
     RayQ q[CH];
-    composite_lane<CH>(raw + ray * n * 4, z + ray * n, nullptr, 0.0f, dnorm, n, lane, q);
-    float sr = 0, sg = 0, sb = 0, sa = 0;
-#pragma unroll
-    for (int c = 0; c < CH; ++c) { sr += q[c].w * q[c].r; sg += q[c].w * q[c].g; sb += q[c].w * q[c].b; sa += q[c].w; }
-    sr = wave_sum(sr); sg = wave_sum(sg); sb = wave_sum(sb); sa = wave_sum(sa);
-    if (white) { sr = sr + (1.0f - sa); sg = sg + (1.0f - sa); sb = sb + (1.0f - sa); }          // render.py:91-92
-    const float er = sr - target[ray * 3], eg = sg - target[ray * 3 + 1], eb = sb - target[ray * 3 + 2];
+    composite_lane<CH>(raw + ray * n * 4, z + ray * n, nullptr, 0.0f, ray_dnorm(rays, ray), n, lane, q);
+    const RaySums s = composite_sums<false>(q, white);
+    const float er = s.r - target[ray * 3], eg = s.g - target[ray * 3 + 1], eb = s.b - target[ray * 3 + 2];
     if (lane == 0) {
       sq += er * er; sq += eg * eg; sq += eb * eb;
-      if (rgb_out) { rgb_out[ray * 3] = sr; rgb_out[ray * 3 + 1] = sg; rgb_out[ray * 3 + 2] = sb; }
+      if (rgb_out) { rgb_out[ray * 3] = s.r; rgb_out[ray * 3 + 1] = s.g; rgb_out[ray * 3 + 2] = s.b; }
     }
     const float gr = grad_scale * 2.0f * er * inv, gg = grad_scale * 2.0f * eg * inv, gb = grad_scale * 2.0f * eb * inv;
     const float gacc = 0.0f - (white ? (gr + gg + gb) : 0.0f);
@@ -164,7 +177,7 @@ __global__ void __launch_bounds__(256) composite_train_kernel(const float* __res
     float run = 0.0f;
 #pragma unroll
     for (int c = CH - 1; c >= 0; --c) {
-      G[c] = gr * q[c].r + gg * q[c].g + gb * q[c].b + gacc + 0.0f * q[c].z;
+      G[c] = gr * q[c].r + gg * q[c].g + gb * q[c].b + gacc + 0.0f * q[c].z;      // 0 * z: an infinite z gives NaN, as staged
       gw[c] = run;
       run += G[c] * q[c].w;
     }
@@ -182,9 +195,7 @@ __global__ void __launch_bounds__(256) composite_train_kernel(const float* __res
       *reinterpret_cast<float4*>(d_raw + (ray * n + k) * 4) = o;
     }
   }
-  if (lane == 0) part[wv] = sq;
-  __syncthreads();
-  if (threadIdx.x == 0 && loss) atomicAdd(loss, (part[0] + part[1] + part[2] + part[3]) * inv);
+  block_loss_add(part, lane, wv, sq, inv, loss);
 }
 
 __global__ void __launch_bounds__(256) mse_kernel(const float* __restrict__ p, const float* __restrict__ t,
@@ -198,74 +209,62 @@ __global__ void __launch_bounds__(256) mse_kernel(const float* __restrict__ p, c
     s += d * d;
     if (d_pred) d_pred[i] = grad_scale * 2.0f * d * inv;
   }
-  s = wave_sum(s);
-  if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = s;
-  __syncthreads();
-  if (threadIdx.x == 0 && loss) atomicAdd(loss, (part[0] + part[1] + part[2] + part[3]) * inv);
+  block_loss_add(part, threadIdx.x & 63, threadIdx.x >> 6, wave_sum(s), inv, loss);
+}
+
+// The host side the three per-ray entries share: the check of n, nothing to do without rays, then `body` (the entry's NULL
+// checks and its launch) with CH = ceil(n / 64) rounded up to an instantiated chunk count, and the grid.
+template <class Body>
+static int composite_entry(const char* who, int64_t B, int n, Body&& body) {
+  NERF_REQUIRE(n >= 1 && n <= 1024, NERF_E_SHAPE, "%s: need 1 <= n <= 1024 (n=%d)", who, n);
+  if (B <= 0) return NERF_OK;
+  return with_int_up_to<1, 2, 3, 4, 8, 16>((n + 63) / 64, [&](auto ch) -> int { return body(ch, wave_per_ray_grid(B)); });
 }
 
 }  // namespace nerf
 
 using namespace nerf;
 
-#define DISPATCH_CH(n, CALL)                                  \
-  do {                                                        \
-    const int ch_ = ((n) + 63) / 64;                          \
-    if (ch_ <= 1) { CALL(1); } else if (ch_ == 2) { CALL(2); } else if (ch_ == 3) { CALL(3); } \
-    else if (ch_ == 4) { CALL(4); } else if (ch_ <= 8) { CALL(8); } else { CALL(16); }       \
-  } while (0)
-
 extern "C" int nerf_composite_forward(const float* raw, const float* z, const float* rays, int64_t B, int n,
                                       float raw_noise_std, const float* noise, int white_bkgd, float* rgb, float* disp,
                                       float* acc, float* weights, float* depth, void* stream) {
-  NERF_REQUIRE(n >= 1 && n <= 1024, NERF_E_SHAPE, "nerf_composite_forward: need 1 <= n <= 1024 (n=%d)", n);
-  if (B <= 0) return NERF_OK;
-  NERF_REQUIRE(raw && z && rays && rgb, NERF_E_NULL, "nerf_composite_forward: raw/z/rays/rgb is NULL");
-  NERF_REQUIRE(raw_noise_std <= 0.0f || noise, NERF_E_NULL, "nerf_composite_forward: raw_noise_std > 0 needs noise");
-  if (B <= 0) return NERF_OK;
-  const dim3 g((unsigned)((B + 3) / 4 > 8192 ? 8192 : (B + 3) / 4)), b(256);
-  auto st = as_stream(stream);
-#define CALL(C) hipLaunchKernelGGL(composite_fwd_kernel<C>, g, b, 0, st, raw, z, rays, B, n, raw_noise_std, noise, white_bkgd, rgb, disp, acc, weights, depth)
-  DISPATCH_CH(n, CALL);
-#undef CALL
-  return check_launch("nerf_composite_forward");
+  return composite_entry("nerf_composite_forward", B, n, [&](auto ch, int grid) -> int {
+    NERF_REQUIRE(raw && z && rays && rgb, NERF_E_NULL, "nerf_composite_forward: raw/z/rays/rgb is NULL");
+    NERF_REQUIRE(raw_noise_std <= 0.0f || noise, NERF_E_NULL, "nerf_composite_forward: raw_noise_std > 0 needs noise");
+    NERF_LAUNCH("nerf_composite_forward", composite_fwd_kernel<decltype(ch)::value>, grid, 256, as_stream(stream), raw, z, rays, B,
+                n, raw_noise_std, noise, white_bkgd, rgb, disp, acc, weights, depth);
+    return NERF_OK;
+  });
 }
 
 extern "C" int nerf_composite_backward(const float* raw, const float* z, const float* rays, int64_t B, int n,
                                        float raw_noise_std, const float* noise, int white_bkgd, const float* d_rgb,
                                        const float* d_acc, const float* d_depth, float* d_raw, void* stream) {
-  NERF_REQUIRE(n >= 1 && n <= 1024, NERF_E_SHAPE, "nerf_composite_backward: need 1 <= n <= 1024 (n=%d)", n);
-  if (B <= 0) return NERF_OK;
-  NERF_REQUIRE(raw && z && rays && d_rgb && d_raw, NERF_E_NULL, "nerf_composite_backward: NULL pointer");
-  NERF_REQUIRE(raw_noise_std <= 0.0f || noise, NERF_E_NULL, "nerf_composite_backward: raw_noise_std > 0 needs noise");
-  if (B <= 0) return NERF_OK;
-  const dim3 g((unsigned)((B + 3) / 4 > 8192 ? 8192 : (B + 3) / 4)), b(256);
-  auto st = as_stream(stream);
-#define CALL(C) hipLaunchKernelGGL(composite_bwd_kernel<C>, g, b, 0, st, raw, z, rays, B, n, raw_noise_std, noise, white_bkgd, d_rgb, d_acc, d_depth, d_raw)
-  DISPATCH_CH(n, CALL);
-#undef CALL
-  return check_launch("nerf_composite_backward");
+  return composite_entry("nerf_composite_backward", B, n, [&](auto ch, int grid) -> int {
+    NERF_REQUIRE(raw && z && rays && d_rgb && d_raw, NERF_E_NULL, "nerf_composite_backward: NULL pointer");
+    NERF_REQUIRE(raw_noise_std <= 0.0f || noise, NERF_E_NULL, "nerf_composite_backward: raw_noise_std > 0 needs noise");
+    NERF_LAUNCH("nerf_composite_backward", composite_bwd_kernel<decltype(ch)::value>, grid, 256, as_stream(stream), raw, z, rays, B,
+                n, raw_noise_std, noise, white_bkgd, d_rgb, d_acc, d_depth, d_raw);
+    return NERF_OK;
+  });
 }
 
 extern "C" int nerf_composite_mse_backward(const float* raw, const float* z, const float* rays, int64_t B, int n,
                                           int white_bkgd, const float* target, float grad_scale, float* loss_out,
                                           float* rgb, float* d_raw, void* stream) {
-  NERF_REQUIRE(n >= 1 && n <= 1024, NERF_E_SHAPE, "nerf_composite_mse_backward: need 1 <= n <= 1024 (n=%d)", n);
-  if (B <= 0) return NERF_OK;
-  NERF_REQUIRE(raw && z && rays && target && d_raw, NERF_E_NULL, "nerf_composite_mse_backward: NULL pointer");
-  const dim3 g((unsigned)((B + 3) / 4 > 8192 ? 8192 : (B + 3) / 4)), b(256);
-  auto st = as_stream(stream);
-#define CALL(C) hipLaunchKernelGGL(composite_train_kernel<C>, g, b, 0, st, raw, z, rays, B, n, white_bkgd, target, grad_scale, loss_out, rgb, d_raw)
-  DISPATCH_CH(n, CALL);
-#undef CALL
-  return check_launch("nerf_composite_mse_backward");
+  return composite_entry("nerf_composite_mse_backward", B, n, [&](auto ch, int grid) -> int {
+    NERF_REQUIRE(raw && z && rays && target && d_raw, NERF_E_NULL, "nerf_composite_mse_backward: NULL pointer");
+    NERF_LAUNCH("nerf_composite_mse_backward", composite_train_kernel<decltype(ch)::value>, grid, 256, as_stream(stream), raw, z,
+                rays, B, n, white_bkgd, target, grad_scale, loss_out, rgb, d_raw);
+    return NERF_OK;
+  });
 }
 
 extern "C" int nerf_mse_loss_grad(const float* pred, const float* target, int64_t count, float grad_scale,
                                   float* loss_out, float* d_pred, void* stream) {
   NERF_REQUIRE(pred && target, NERF_E_NULL, "nerf_mse_loss_grad: pred/target is NULL");
   NERF_REQUIRE(count > 0, NERF_E_SHAPE, "nerf_mse_loss_grad: count must be > 0");
-  hipLaunchKernelGGL(mse_kernel, dim3(grid_for(count, 256, 64)), dim3(256), 0, as_stream(stream), pred, target, count,
-                     grad_scale, loss_out, d_pred);
-  return check_launch("nerf_mse_loss_grad");
+  NERF_LAUNCH("nerf_mse_loss_grad", mse_kernel, grid_for(count, 256, 64), 256, as_stream(stream), pred, target, count, grad_scale,
+              loss_out, d_pred);
+  return NERF_OK;
 }

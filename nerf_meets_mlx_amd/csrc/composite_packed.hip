@@ -138,13 +138,6 @@ __global__ void __launch_bounds__(256) composite_packed_fwd_kernel(const float* 
   }
 }
 
-// one of the block's two loss sums: the waves' partial sums through the same 16 B of LDS, one atomic per block
-__device__ __forceinline__ void block_loss_add(float* part, int lane, int wv, float v, float scale, float* __restrict__ out) {
-  if (lane == 0) part[wv] = v;
-  __syncthreads();
-  if (threadIdx.x == 0 && out) atomicAdd(out, (part[0] + part[1] + part[2] + part[3]) * scale);
-}
-
 // Forward (as above) -> rgb -> squared error against the target -> d loss / d raw of every sample of the ray.  The reverse pass
 // walks the chunks last to first with the suffix sum of G w carried exactly (no total-minus-prefix), and re-derives each chunk's
 // forward quantities from the exponent carried into it, which the forward pass left in lane c of `carries`.
@@ -360,7 +353,7 @@ template <class... P, class... A>
 int packed_launch(const char* who, void (*kernel)(P...), void* stream, const float* raw, const float* z, const int64_t* offsets,
                   const float* rays, int64_t B, int64_t K, float step_world, int march_steps, A... rest) {
   const float S = (float)march_steps;
-  const dim3 g((unsigned)((B + 3) / 4 > 8192 ? 8192 : (B + 3) / 4)), b(256);
+  const dim3 g((unsigned)wave_per_ray_grid(B)), b(256);
   hipLaunchKernelGGL(kernel, g, b, 0, as_stream(stream), raw, z, offsets, rays, B, K, step_world, S * step_world, (1.0f / S) / 3.0f,
                      rest...);
   return check_launch(who);

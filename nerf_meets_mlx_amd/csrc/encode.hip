@@ -375,9 +375,9 @@ static int ngp_encode_entry(const char* who, const float* rays, const float* z, 
   c.tables = tables; c.out = x_out; c.out_stride = (int64_t)L * F + (sh_degree + 1) * (sh_degree + 1);
   const int rc = hashgrid_gather(c, stream);
   if (rc) return rc;
-  hipLaunchKernelGGL(ngp_dir_rows_kernel, dim3(grid_for(c.M, 256)), dim3(256), 0, as_stream(stream), rays, z, n, c.M, sh_degree,
-                     x_out, c.out_stride, L * F, pts_out, pos_scale, pos_offset);
-  return check_launch(who);
+  NERF_LAUNCH(who, ngp_dir_rows_kernel, grid_for(c.M, 256), 256, as_stream(stream), rays, z, n, c.M, sh_degree, x_out, c.out_stride,
+              L * F, pts_out, pos_scale, pos_offset);
+  return NERF_OK;
 }
 
 static int hashgrid_backward_entry(const char* who, const float* x, int64_t M, const float* d_out, int L, int log2_T, int F,
@@ -415,10 +415,9 @@ extern "C" int nerf_encode_freq(const float* x, int64_t M, int D, int n_freqs, i
   NERF_REQUIRE(x && out, NERF_E_NULL, "nerf_encode_freq: x/out is NULL");
   NERF_REQUIRE(D >= 1 && D <= 8 && n_freqs >= 0 && n_freqs <= 16, NERF_E_SHAPE, "nerf_encode_freq: bad D/n_freqs");
   NERF_REQUIRE(freq_mode == 0 || freq_mode == 1, NERF_E_UNSUPPORTED, "nerf_encode_freq: freq_mode must be 0 or 1");
-  if (M <= 0) return NERF_OK;
-  hipLaunchKernelGGL(encode_freq_kernel, dim3(grid_for(M * D * (1 + 2 * n_freqs), 256)), dim3(256), 0,
-                     as_stream(stream), x, M, D, n_freqs, freq_mode, out);
-  return check_launch("nerf_encode_freq");
+  NERF_LAUNCH("nerf_encode_freq", encode_freq_kernel, grid_for(M * D * (1 + 2 * n_freqs), 256), 256, as_stream(stream), x, M, D,
+              n_freqs, freq_mode, out);
+  return NERF_OK;
 }
 
 extern "C" int nerf_encode_sinusoidal(const float* x, int64_t M, int D, int n_freqs, const float* freqs_host,
@@ -426,21 +425,20 @@ extern "C" int nerf_encode_sinusoidal(const float* x, int64_t M, int D, int n_fr
   if (M <= 0) return NERF_OK;
   NERF_REQUIRE(x && out && freqs_host, NERF_E_NULL, "nerf_encode_sinusoidal: NULL pointer");
   NERF_REQUIRE(D >= 1 && n_freqs >= 1 && n_freqs <= 32, NERF_E_SHAPE, "nerf_encode_sinusoidal: need 1<=n_freqs<=32");
-  if (M <= 0) return NERF_OK;
   FreqTab ft;
   for (int k = 0; k < 32; ++k) ft.f[k] = k < n_freqs ? freqs_host[k] : 0.0f;
   const int C = 2 * D * n_freqs + (include_input ? D : 0);
-  hipLaunchKernelGGL(encode_sinusoidal_kernel, dim3(grid_for(M * C, 256)), dim3(256), 0, as_stream(stream), x, M, D,
-                     n_freqs, ft, include_input, out);
-  return check_launch("nerf_encode_sinusoidal");
+  NERF_LAUNCH("nerf_encode_sinusoidal", encode_sinusoidal_kernel, grid_for(M * C, 256), 256, as_stream(stream), x, M, D, n_freqs,
+              ft, include_input, out);
+  return NERF_OK;
 }
 
 extern "C" int nerf_sh_encode(const float* dirs, int64_t M, int degree, float* out, void* stream) {
   NERF_REQUIRE(degree >= 0 && degree <= 4, NERF_E_SHAPE, "nerf_sh_encode: n_degrees=%d must be in range [0, 4]", degree);
   if (M <= 0) return NERF_OK;
   NERF_REQUIRE(dirs && out, NERF_E_NULL, "nerf_sh_encode: NULL pointer");
-  hipLaunchKernelGGL(sh_kernel, dim3(grid_for(M, 256)), dim3(256), 0, as_stream(stream), dirs, M, degree, out);
-  return check_launch("nerf_sh_encode");
+  NERF_LAUNCH("nerf_sh_encode", sh_kernel, grid_for(M, 256), 256, as_stream(stream), dirs, M, degree, out);
+  return NERF_OK;
 }
 
 extern "C" int nerf_hashgrid_forward(const float* x, int64_t M, const float* tables, int L, int log2_T, int F,

@@ -1,9 +1,18 @@
 // Depth sampling (a5-a7) and inverse-CDF importance sampling + merge (a15, a17 / K2, K8).
 // HBM-bound: one wavefront per ray, CDF / depths staged in LDS, per-lane binary search,
 // LDS rank-merge of the n coarse + N new depths (the rule: the exact multiset, ascending, ties coarse-first, NaN last).
-#include "common.h"
+#include "launch.h"
 
 namespace nerf {
+
+// stratified jitter of depth v (sampling/__init__.py:10-31): sample k of n moves to lo + (hi - lo) * (t * s), lo / hi the mid
+// points towards its neighbours `below` / `above` (lower = [z_first, mids], upper = [mids, z_last]).  The first sample has no
+// `below` and the last no `above`: the callers pass v there (it is not used) and touch no neighbour that does not exist.
+__device__ __forceinline__ float jitter_z(float v, int k, int n, float below, float above, float t, float s) {
+  const float lo = (k == 0) ? v : 0.5f * (below + v);
+  const float hi = (k == n - 1) ? v : 0.5f * (v + above);
+  return lo + (hi - lo) * (t * s);
+}
 
 __global__ void sample_coarse_kernel(const float* __restrict__ rays, int64_t B, int n, int lindisp, float perturb,
                                      const float* __restrict__ t_rand, float step, float* __restrict__ z) {
@@ -17,11 +26,7 @@ __global__ void sample_coarse_kernel(const float* __restrict__ rays, int64_t B, 
       return 1.0f / (1.0f / (near * (1.0f - tv)) + 1.0f / (far * tv));  // linear_disparity.py:15-17 (literal)
     };
     float v = zk(k);
-    if (perturb > 0.0f) {                                         // sampling/__init__.py:17-29
-      const float lo = (k == 0) ? v : 0.5f * (zk(k - 1) + v);
-      const float hi = (k == n - 1) ? v : 0.5f * (v + zk(k + 1));
-      v = lo + (hi - lo) * (t_rand[t] * perturb);
-    }
+    if (perturb > 0.0f) v = jitter_z(v, k, n, k == 0 ? v : zk(k - 1), k == n - 1 ? v : zk(k + 1), t_rand[t], perturb);
     z[t] = v;
   }
 }
@@ -33,9 +38,7 @@ __global__ void add_noise_z_kernel(const float* __restrict__ z_in, const float* 
   for (int64_t t = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; t < total; t += (int64_t)gridDim.x * blockDim.x) {
     const int k = (int)(t % n);
     const float v = z_in[t];
-    const float lo = (k == 0) ? v : 0.5f * (z_in[t - 1] + v);               // lower = [z_first, mids]
-    const float hi = (k == n - 1) ? v : 0.5f * (v + z_in[t + 1]);           // upper = [mids, z_last]
-    z_out[t] = lo + (hi - lo) * (t_rand[t] * strength);
+    z_out[t] = jitter_z(v, k, n, k == 0 ? v : z_in[t - 1], k == n - 1 ? v : z_in[t + 1], t_rand[t], strength);
   }
 }
 
@@ -189,11 +192,10 @@ extern "C" int nerf_sample_coarse(const float* rays, int64_t B, int n, int lindi
   if (B == 0) return NERF_OK;
   NERF_REQUIRE(rays && z, NERF_E_NULL, "nerf_sample_coarse: rays/z is NULL");
   NERF_REQUIRE(perturb <= 0.0f || t_rand, NERF_E_NULL, "nerf_sample_coarse: perturb > 0 needs t_rand");
-  if (B == 0) return NERF_OK;
   const float step = (float)((1.0 - 0.0) / (double)(n - 1));
-  hipLaunchKernelGGL(sample_coarse_kernel, dim3(grid_for(B * n, 256)), dim3(256), 0, as_stream(stream), rays, B, n,
-                     lindisp, perturb, t_rand, step, z);
-  return check_launch("nerf_sample_coarse");
+  NERF_LAUNCH("nerf_sample_coarse", sample_coarse_kernel, grid_for(B * n, 256), 256, as_stream(stream), rays, B, n, lindisp,
+              perturb, t_rand, step, z);
+  return NERF_OK;
 }
 
 extern "C" int nerf_add_noise_z(const float* z_in, const float* t_rand, int64_t B, int n, float strength, float* z_out,
@@ -202,9 +204,9 @@ extern "C" int nerf_add_noise_z(const float* z_in, const float* t_rand, int64_t 
   if (B == 0) return NERF_OK;
   NERF_REQUIRE(z_in && t_rand && z_out, NERF_E_NULL, "nerf_add_noise_z: NULL pointer");
   NERF_REQUIRE(z_in != z_out, NERF_E_SHAPE, "nerf_add_noise_z: in-place use is not supported (neighbours are read)");
-  hipLaunchKernelGGL(add_noise_z_kernel, dim3(grid_for(B * n, 256)), dim3(256), 0, as_stream(stream), z_in, t_rand, B, n,
-                     strength, z_out);
-  return check_launch("nerf_add_noise_z");
+  NERF_LAUNCH("nerf_add_noise_z", add_noise_z_kernel, grid_for(B * n, 256), 256, as_stream(stream), z_in, t_rand, B, n, strength,
+              z_out);
+  return NERF_OK;
 }
 
 extern "C" int nerf_importance_sample(const float* z, const float* weights, const float* u, int64_t B, int n, int N,
@@ -217,12 +219,10 @@ extern "C" int nerf_importance_sample(const float* z, const float* weights, cons
   int P = 2;
   while (P < N) P <<= 1;                                  // bitonic sort width of the new depths
   const int per_wave = (n + 1) * 2 + ((n + P + 3) & ~3);
-  const size_t lds = (size_t)per_wave * 4 * sizeof(float);
-  const int grid = (int)((B + 3) / 4 > 256 * 8 ? 256 * 8 : (B + 3) / 4);
-  const int ch = (n + 63) / 64;
-  auto st = as_stream(stream);
-#define LAUNCH(C) hipLaunchKernelGGL(importance_kernel<C>, dim3(grid), dim3(256), lds, st, z, weights, u, B, n, N, P, eps, z_new, z_merged, cdf, inds)
-  if (ch == 1) LAUNCH(1); else if (ch == 2) LAUNCH(2); else if (ch == 3) LAUNCH(3); else LAUNCH(4);
-#undef LAUNCH
-  return check_launch("nerf_importance_sample");
+  const int lds = per_wave * 4 * (int)sizeof(float);       // at most 20.5 KB; dynamic, so launch() (launch.h), not NERF_LAUNCH
+  return with_int_up_to<1, 2, 3, 4>((n + 63) / 64, [&](auto ch) {
+    return launch<importance_kernel<decltype(ch)::value>>("nerf_importance_sample", dim3(wave_per_ray_grid(B, 256 * 8)), dim3(256),
+                                                          lds, as_stream(stream), z, weights, u, B, n, N, P, eps, z_new, z_merged,
+                                                          cdf, inds);
+  });
 }

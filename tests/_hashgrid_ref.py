@@ -10,7 +10,7 @@ Everything is numpy float32 with ONE rounding per operation, in the operation or
   addends    g * w_z * w_y * w_x, left to right                                                   (encode.hip: hashgrid_bwd_kernel)
   to_fixed   2^-52 fixed point, saturation / poison codes                                         (hash_common.h: nerf_to_fixed)
   scatter    the exact int64 sum per entry (mod 2^64), or the float64 sum with sum |a| and the addend count
-  adam_ex    nerf_adam_step(_ex / _shadow)                                                        (adam.hip: adam_ex_kernel)
+  adam_ex    nerf_adam_step(_ex / _shadow)                                                        (adam.hip: adam_kernel)
 """
 import ctypes
 import ctypes.util
@@ -175,14 +175,14 @@ def bias_factors(b1, b2, bias_correction, step):
 
 
 def fixed_grad(a, gscale):
-    """float32 gradient of int64 accumulators (adam_ex_kernel): float32(float64(a) 2^-52) * gscale, NaN outside (-2^60, 2^60)."""
+    """float32 gradient of int64 accumulators (adam_kernel): float32(float64(a) 2^-52) * gscale, NaN outside (-2^60, 2^60)."""
     a = np.asarray(a, dtype=np.int64)
     g = (a.astype(np.float64) * 2.0 ** -FIX_SHIFT).astype(f32) * f32(gscale)
     return np.where((a <= -(1 << 60)) | (a >= (1 << 60)), f32(np.nan), g).astype(f32)
 
 
 def adam_ex(p, g, m, v, lr, b1, b2, eps, c1, c2, gscale, fixed=False):
-    """(p, m, v) after one step of adam_ex_kernel / adam_kernel; g float32 (scaled by gscale here) or int64 accumulators."""
+    """(p, m, v) after one step of adam_kernel; g float32 (scaled by gscale here) or int64 accumulators."""
     p, m, v = (np.asarray(t, dtype=f32) for t in (p, m, v))
     lr, b1, b2, eps, c1, c2 = (f32(t) for t in (lr, b1, b2, eps, c1, c2))
     gi = fixed_grad(g, gscale) if fixed else np.asarray(g, dtype=f32) * f32(gscale)

@@ -4,7 +4,7 @@ csrc/composite.hip are the product).
 Everything is numpy float32 with ONE rounding per operation, in the operation order of the kernels (the library is built with
 -ffp-contract=off, `/` and sqrtf are correctly rounded, f32 subnormals are kept):
   lanes      a ray is one wave of 64 lanes; lane l holds the CH consecutive samples k = l CH + c.  CH = ceil(n / 64) in the
-             importance sampler, and the next of {1, 2, 3, 4, 8, 16} in the compositing kernels (DISPATCH_CH)
+             importance sampler, and the next of {1, 2, 3, 4, 8, 16} in the compositing kernels (with_int_up_to)
   prefixes   a lane-serial running sum inside the lane, then the wave scan; the exclusive value is `inclusive - own`, as written
   wave scans `wave_scan_incl`, `wave_rscan_incl`, `wave_sum` of csrc/common.h step by step: lanes without a source add +0.0f
   float64    the importance sampler's weight sum (xor butterfly) and CDF (lane-serial + Hillis-Steele scan) are float64 and

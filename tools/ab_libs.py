@@ -15,6 +15,16 @@
         every volume entry (lattice points, marching cubes, components and both filters, erode / reconstruct at radius 1 and 2, TSDF
         fusion of 3 synthetic views with carve on and off, the simplifier at grid 8 with both placements) at R = 17 and 65 on a smooth,
         a noise and a NaN / +-inf volume, iso 0.25, over a non-cubic box: sha256 of every output.  Exit 1 unless all are the same.
+    python tools/ab_libs.py --rays tools/diag/libnerf_A.so default
+        every entry of rays.hip, sampling.hip, composite.hip, adam.hip and the closed-form encoders on seeded inputs, at the
+        smallest shapes that reach every template instance, partial block and grid-stride loop (compositing n = 1 ... 1024 for the
+        chunk counts 1, 2, 3, 4, 8, 16 and B = 32 773; importance sampling at every chunk count, both merge paths; Adam in every
+        (fixed, zero, shadow) form at 1 and 524 293 parameters with a poisoned accumulator; densities with +-inf and NaN, a z row
+        ending in +inf; optional outputs NULL and given): sha256 of every output, sentinel-filled first.  The loss of
+        nerf_composite_mse_backward / nerf_mse_loss_grad is one atomicAdd per workgroup, so its bits depend on the order of the
+        workgroups: digested only where there is one (B <= 4, count <= 256).  Exit 1 unless all digests are the same.  A float
+        output is printed as bits/values, the second digest taken with every NaN replaced by 0: where only that one is the same
+        in every library, the mismatch is reported as one of NaN sign / payload bits (it still counts).
 Every child runs under a time limit, and after a child that failed or ran out of time no further child is started."""
 import argparse, json, os, subprocess, sys, tempfile
 CHILD = r'''
@@ -171,13 +181,153 @@ for R in (17, 65):
 torch.cuda.synchronize()
 print(json.dumps(res))
 '''
+CHILD_RAYS = r'''
+import sys, json, hashlib, itertools, ctypes as C, torch
+sys.path.insert(0, ".")
+from nerf_meets_mlx_amd import _native as N
+lib, dev, res, P, S = N.lib(), "cuda", {}, N.ptr, N.stream
+sha = lambda t: hashlib.sha256(t.contiguous().cpu().numpy().tobytes()).hexdigest()[:16]
+new = lambda *shape, dt=torch.float32: torch.full(shape, -7.25 if dt.is_floating_point else -7, dtype=dt, device=dev)    # unwritten slots show
+inf, nan = float("inf"), float("nan")
+def put(case, **tensors):     # "bits/values": sha256 of the bytes, and of the bytes with every NaN replaced by 0 (for the report of a mismatch)
+    torch.cuda.synchronize()
+    res[case] = {k: sha(t) + ("/" + sha(torch.where(torch.isnan(t), torch.zeros_like(t), t)) if t.is_floating_point() else "")
+                 for k, t in tensors.items() if t is not None}
+def make_rays(g, B):
+    o, d = torch.randn(B, 3, generator=g), torch.randn(B, 3, generator=g)
+    return torch.cat([o, d, torch.full((B, 1), 2.0), torch.full((B, 1), 6.0), torch.nn.functional.normalize(d, dim=-1)], 1).to(dev).contiguous()
+# ---- compositing: chunk counts 1, 1, 1, 2, 3, 4, 8, 16 at B = 5; 8192 workgroups and one more pass at B = 32773
+for B, n in [(5, n) for n in (1, 2, 64, 65, 129, 200, 300, 1024)] + [(32773, 64), (4, 64), (3, 300)]:
+    g = torch.Generator().manual_seed(31 * n + B)
+    rays = make_rays(g, B)
+    raw = torch.randn(B, n, 4, generator=g); raw[..., 3] *= 3.0
+    z = torch.sort(torch.rand(B, n, generator=g) * 4 + 2, -1).values
+    raw[0, 0, 3], raw[1, n // 2, 3], raw[2, -1, 3] = -5.0, 1e30, inf
+    if B > 4: raw[3, 0, 3], raw[4, n // 3, 3] = -inf, nan
+    z[1, -1] = inf
+    raw, z, noise = raw.to(dev), z.to(dev), torch.randn(B, n, generator=g).to(dev)
+    d_rgb, d_acc, d_depth, target = (torch.randn(B, c, generator=g).to(dev) for c in (3, 1, 1, 3))
+    for white, std, full in itertools.product((0, 1), (0.0, 0.5), (False, True)):
+        tag = f"B={B} n={n} white={white} noise={std} optional={'given' if full else 'NULL'}"
+        rgb, opt = new(B, 3), [new(B), new(B), new(B, n), new(B)] if full else [None] * 4
+        N.check(lib.nerf_composite_forward(P(raw), P(z), P(rays), B, n, std, P(noise) if std else None, white, P(rgb), *map(P, opt), S()))
+        put("composite_forward " + tag, rgb=rgb, disp=opt[0], acc=opt[1], weights=opt[2], depth=opt[3])
+        d_raw = new(B, n, 4)
+        N.check(lib.nerf_composite_backward(P(raw), P(z), P(rays), B, n, std, P(noise) if std else None, white, P(d_rgb),
+                                            P(d_acc) if full else None, P(d_depth) if full else None, P(d_raw), S()))
+        put("composite_backward " + tag, d_raw=d_raw)
+        if not std:
+            loss, rgb = (torch.zeros(1, device=dev), new(B, 3)) if full else (None, None)
+            d_raw = new(B, n, 4)
+            N.check(lib.nerf_composite_mse_backward(P(raw), P(z), P(rays), B, n, white, P(target), 0.75, P(loss), P(rgb), P(d_raw), S()))
+            put("composite_mse_backward " + tag, d_raw=d_raw, rgb=rgb, loss=loss if B <= 4 else None)      # one atomic per block: see the docstring
+for count in (1, 255, 256, 100003):
+    g = torch.Generator().manual_seed(count)
+    p, t = torch.randn(count, generator=g).to(dev), torch.randn(count, generator=g).to(dev)
+    for full in (False, True):
+        loss, d_pred = (torch.zeros(1, device=dev), new(count)) if full else (None, None)
+        N.check(lib.nerf_mse_loss_grad(P(p), P(t), count, 0.75, P(loss), P(d_pred), S()))
+        put(f"mse_loss_grad count={count} optional={'given' if full else 'NULL'}", d_pred=d_pred, loss=loss if count <= 256 else None)
+# ---- importance sampling: every chunk count, both merge paths (row 1 is not ascending), a NaN u, a ray without weight
+for B, n, Nn in [(9, 2, 1), (9, 64, 128), (9, 65, 3), (9, 130, 200), (9, 256, 512), (8197, 64, 128)]:
+    g = torch.Generator().manual_seed(1000 * n + Nn + B)
+    z = torch.sort(torch.rand(B, n, generator=g) * 4 + 2, -1).values
+    z[1] = z[1].flip(0)
+    w, u = torch.rand(B, n, generator=g), torch.rand(B, Nn, generator=g)
+    w[3], u[2, 0], u[4] = 0.0, nan, torch.linspace(0, 1, Nn)
+    z, w, u = z.to(dev), w.to(dev), u.to(dev)
+    for full in (False, True):
+        z_new, cdf, inds = (new(B, Nn), new(B, n + 1), new(B, Nn, dt=torch.int64)) if full else (None, None, None)
+        z_merged = new(B, n + Nn)
+        N.check(lib.nerf_importance_sample(P(z), P(w), P(u), B, n, Nn, 1e-5, P(z_new), P(z_merged), P(cdf), P(inds), S()))
+        put(f"importance_sample B={B} n={n} N={Nn} optional={'given' if full else 'NULL'}", z_merged=z_merged, z_new=z_new, cdf=cdf, inds=inds)
+# ---- depth sampling
+for B, n in [(7, 2), (7, 64), (8200, 64)]:
+    g = torch.Generator().manual_seed(77 * n + B)
+    rays, t_rand = make_rays(g, B), torch.rand(B, n, generator=g).to(dev)
+    for lindisp, perturb in itertools.product((0, 1), (0.0, 1.0)):
+        z = new(B, n)
+        N.check(lib.nerf_sample_coarse(P(rays), B, n, lindisp, perturb, P(t_rand) if perturb else None, P(z), S()))
+        put(f"sample_coarse B={B} n={n} lindisp={lindisp} perturb={perturb}", z=z)
+        if not perturb:
+            z_out = new(B, n)
+            N.check(lib.nerf_add_noise_z(P(z), P(t_rand), B, n, 0.5, P(z_out), S()))
+            put(f"add_noise_z B={B} n={n} lindisp={lindisp}", z=z_out)
+# ---- pixels, rays, batches
+K = (C.c_double * 9)(555.5, 0, 400.0, 0, 554.25, 399.5, 0, 0, 1)
+c2w = (C.c_float * 16)(0.6, -0.48, 0.64, 2.5, 0.8, 0.36, -0.48, -1.9, 0.0, 0.8, 0.6, 2.4, 0, 0, 0, 1)
+for H, W, n, offset in [(5, 7, 35, 0), (800, 800, 1000, 123457)]:
+    g = torch.Generator().manual_seed(H)
+    idx = new(n, dt=torch.int64)
+    N.check(lib.nerf_pixel_permutation(P(idx), n, H * W, 0xFEDCBA9876543210, offset, S()))
+    put(f"pixel_permutation {H}x{W} n={n} offset={offset}", idx=idx)
+    for use_idx, use_coords in itertools.product((False, True), (False, True)):
+        if not use_idx and n != H * W: continue
+        rays, coords = new(n, 11), new(n, 2, dt=torch.int64) if use_coords else None
+        N.check(lib.nerf_ray_gen(P(idx) if use_idx else None, n, H, W, K, c2w, 2.0, 6.0, P(rays), P(coords), S()))
+        put(f"ray_gen {H}x{W} n={n} idx={use_idx} coords={use_coords}", rays=rays, coords=coords)
+    for ch, fn in ((3, lib.nerf_sample_batch), (4, lib.nerf_sample_batch_rgba)):
+        image = torch.rand(H * W, ch, generator=g).to(dev)
+        for use_idx in (False, True):
+            rays, target, pix = new(n, 11), new(n, ch), new(n, dt=torch.int64) if use_idx else None
+            N.check(fn(n, H, W, 0xFEDCBA9876543210, offset, K, c2w, 2.0, 6.0, P(image), P(rays), P(target), P(pix), S()))
+            put(f"sample_batch channels={ch} {H}x{W} n={n} offset={offset} pixel_idx={use_idx}", rays=rays, target=target, pixel_idx=pix)
+g = torch.Generator().manual_seed(5)
+for ch in (3, 4):
+    src, idx = torch.rand(1000, ch, generator=g).to(dev), torch.randint(0, 1000, (300,), generator=g)
+    idx[5], idx[17] = -1, 1000
+    out, idx = new(300, ch), idx.to(dev)
+    N.check(lib.nerf_gather_rows(P(src), 1000, P(idx), 300, ch, P(out), S()))
+    put(f"gather_rows channels={ch}", out=out)
+rays = make_rays(g, 1000)
+N.check(lib.nerf_ndc_rays(P(rays), 1000, 378, 504, 407.5, 1.0, S()))
+put("ndc_rays 1000", rays=rays)
+# ---- Adam: one thread and 2048 workgroups plus five elements; a poisoned accumulator in the fixed-point gradients
+for count in (1, 524293):
+    g = torch.Generator().manual_seed(count)
+    p0, m0, v0 = torch.randn(count, generator=g).to(dev), (0.1 * torch.randn(count, generator=g)).to(dev), (0.01 * torch.rand(count, generator=g)).to(dev)
+    gf = torch.randn(count, generator=g)
+    gx = (gf.double() * 0.01 * 2.0 ** 52).long()
+    gx[count // 2] = 1 << 61
+    for bias, step in ((1, 1), (1, 7), (0, 0)):
+        hyper = (count, 1e-3, 0.9, 0.999, 1e-8, bias, step, 0.5)
+        p, m, v, gr = p0.clone(), m0.clone(), v0.clone(), gf.to(dev)
+        N.check(lib.nerf_adam_step(P(p), P(gr), P(m), P(v), *hyper, S()))
+        put(f"adam_step count={count} bias={bias} step={step}", p=p, m=m, v=v, grads=gr)
+        for fixed, zero, shadow in itertools.product((0, 1), (0, 1), (None, False, True)):     # shadow None: through nerf_adam_step_ex
+            p, m, v, gr, ph = p0.clone(), m0.clone(), v0.clone(), (gx if fixed else gf).to(dev), new(count, dt=torch.float16) if shadow else None
+            if shadow is None: N.check(lib.nerf_adam_step_ex(P(p), P(gr), P(m), P(v), *hyper, fixed, zero, S()))
+            else: N.check(lib.nerf_adam_step_shadow(P(p), P(gr), P(m), P(v), *hyper, fixed, zero, P(ph), S()))
+            put(f"adam_step_{'ex' if shadow is None else 'shadow'} count={count} bias={bias} step={step} fixed={fixed} zero={zero} shadow={bool(shadow)}",
+                p=p, m=m, v=v, grads=gr, shadow=ph)
+# ---- closed-form encoders
+freqs = (C.c_float * 4)(1.0, 2.5, 6.25, 15.625)
+for M in (3, 70001):
+    g = torch.Generator().manual_seed(M)
+    x = torch.randn(M, 3, generator=g).to(dev)
+    dirs = torch.nn.functional.normalize(x, dim=-1).contiguous()
+    for mode in (0, 1):
+        out = new(M, 63)
+        N.check(lib.nerf_encode_freq(P(x), M, 3, 10, mode, P(out), S()))
+        put(f"encode_freq M={M} freq_mode={mode}", out=out)
+    for inc in (0, 1):
+        out = new(M, 24 + 3 * inc)
+        N.check(lib.nerf_encode_sinusoidal(P(x), M, 3, 4, freqs, inc, P(out), S()))
+        put(f"encode_sinusoidal M={M} include_input={inc}", out=out)
+    for deg in range(5):
+        out = new(M, (deg + 1) ** 2)
+        N.check(lib.nerf_sh_encode(P(dirs), M, deg, P(out), S()))
+        put(f"sh_encode M={M} degree={deg}", out=out)
+print(json.dumps(res))
+'''
 ap = argparse.ArgumentParser(); ap.add_argument("libs", nargs="+"); ap.add_argument("--rounds", type=int, default=None); ap.add_argument("--precision", type=int, default=22)
 ap.add_argument("--models", action="store_true", help="digests of every MLP model instead of the render-chunk timing")
 ap.add_argument("--volumes", action="store_true", help="digests of every volume entry (mesh, components, opening, TSDF, simplifier)")
+ap.add_argument("--rays", action="store_true", help="digests of the ray, sampling, compositing, Adam and closed-form encoder entries")
 ap.add_argument("--timeout", type=float, default=300.0, help="seconds per child process")
 ap.add_argument("--fold-differs", action="store_true", help="the builds differ in NERF_F22_FOLD: colour differences are reported, not failed")
 a = ap.parse_args()
-digests_of = CHILD_MODELS if a.models else CHILD_VOLUMES if a.volumes else None
+digests_of = CHILD_MODELS if a.models else CHILD_VOLUMES if a.volumes else CHILD_RAYS if a.rays else None
 rounds = a.rounds if a.rounds is not None else (1 if digests_of else 3)
 acc = {l: [] for l in a.libs}
 tmp = None if digests_of else tempfile.mkdtemp(prefix="ab_libs_")
@@ -200,7 +350,10 @@ if digests_of:
     for case, digests in ref.items():
         same = all(run.get(case) == digests for l in a.libs for run in acc[l])
         bad += not same
-        print(f"{case}: " + " ".join(f"{k}={v}" for k, v in digests.items()) + ("   same in every library" if same else "   MISMATCH: " + json.dumps({l: acc[l][0].get(case) for l in a.libs})))
+        values = lambda d: {k: v.split("/")[-1] for k, v in (d or {}).items()}        # --rays: the digests with NaNs zeroed
+        nan_only = not same and all("/" in v for v in digests.values()) and all(values(run.get(case)) == values(digests) for l in a.libs for run in acc[l])
+        print(f"{case}: " + " ".join(f"{k}={v}" for k, v in digests.items()) + ("   same in every library" if same else
+              "   MISMATCH" + (" (only in the sign / payload bits of NaNs)" if nan_only else "") + ": " + json.dumps({l: acc[l][0].get(case) for l in a.libs})))
     print(f"{len(ref)} cases x {len(a.libs)} libraries x {rounds} round(s): {bad} mismatching")
     sys.exit(1 if bad else 0)
 for l in a.libs:

@@ -53,6 +53,12 @@ report("composite fwd n=192 (rgb only)", f"{B2} rays", B2 * (192 * 20 + 44 + 12)
 d_rgb = torch.randn(B2, 3, device=dev)
 report("composite bwd n=192", f"{B2} rays", B2 * (192 * 20 + 44 + 12 + 192 * 16),
        lambda: render.composite_backward(raw192, zf2, rays2, d_rgb, True))
+target = torch.rand(B, 3, device=dev)
+report("composite_mse_backward n=64 (loss, d_raw)", f"{B} rays", B * (64 * 20 + 44 + 12 + 64 * 16),
+       lambda: render.composite_mse_backward(raw64, z64, rays, target, True))
+image = imgs[0]
+report("sample_batch N_rand=4096 (launch-bound)", "4096 rays", 4096 * (12 + 44 + 12),
+       lambda: ray.sample_batch(H, W, K, c2w, 2.0, 6.0, image, 4096, 7, 1000))
 m = NeRF(channel_input=63, channel_input_views=27, is_use_view_directions=True, device=dev, seed=0)
 opt = Adam(5e-4, shared_state=True)
 m.grads.normal_()
