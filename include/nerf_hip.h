@@ -803,6 +803,63 @@ int nerf_simplify_write(int64_t V, const int32_t* faces, int64_t F, const float*
                         int placement, void* workspace, int64_t V_out, int64_t F_out, float* verts_out, float* normals_out,
                         float* colors_out, float* color_rows, int32_t* faces_out, void* stream);
 
+/* ---------------------------------------------------------------- mesh smoothing (no reference counterpart)
+ * Taubin's lambda|mu filter ("A signal processing approach to fair surface design", 1995): an umbrella-Laplacian half-step with
+ * lambda > 0, then one with mu < 0; it takes the voxel-scale noise off a marching-cubes mesh without the shrinkage of plain
+ * Laplacian smoothing.  The step between marching cubes and the simplifier.  Additive: NERF_ABI_VERSION stays 3.  All arithmetic
+ * is IEEE double, one rounding per operation, in exactly the order and grouping written here, unless it says int64;
+ * tests/_smooth_ref.py reproduces every output bit for bit.
+ *   input     verts [V, 3] float32, faces [F, 3] int32; box lo[3] < hi[3] (host floats, finite); 0 <= V, F <= 2^24.
+ *             ext_a = (double)hi_a - (double)lo_a, ctr_a = ((double)lo_a + (double)hi_a) * 0.5.
+ *   ignored   a face with an index outside [0, V) or with two equal corners is ignored entirely: nothing is read through a bad
+ *             index, and dropping such a face from the input changes no output bit.
+ *   rows      every remaining face (a, b, c) adds one entry to the row of each corner, the other two corners in face order: row a
+ *             receives (b, c), row b (c, a), row c (a, b).  The weight of a neighbour in the umbrella is so the number of faces
+ *             on the shared edge (2 on a closed manifold, 1 along a boundary), and an entry keeps the face's orientation.
+ *   sums      exact int64, independent of the arrival order.  fix(x, L, s) = (int64)rint(min(max(x, -L), L) * s), 0 for a NaN x
+ *             (rint: to nearest, ties to even), as in the simplifier.
+ *   half-step with factor k (a float32 argument, used as (double)k), float32 positions in, float32 positions out.  A position is
+ *             finite when its three coordinates are.  For vertex a with a finite position v: over the entries of its row, for
+ *             each of the entry's two neighbours whose position w is finite, S_x += fix(u_x, 4, 2^32) with
+ *             u_x = ((double)w_x - ctr_x) / ext_x per axis x, and n counts the positions added.  One unit is 2^-32 of the extent;
+ *             a row of 2^24 entries adds 2^25 positions of at most 2^34 units each, below 2^63; the clamp only touches
+ *             neighbours 3.5 extents outside the box.  mean_x = ctr_x + (S_x / 2^32 / n) * ext_x;
+ *             out_x = (float)((double)v_x + k * (mean_x - (double)v_x)).  A vertex with n = 0, or whose own position is not
+ *             finite, is copied bit for bit.
+ *   run       `iterations` pairs: a half-step with lambda, then one with mu.  mu = 0 is plain Laplacian smoothing: the second
+ *             half-step is not launched.  0 < lambda <= 1; mu = 0 or -2 <= mu < 0; 1 <= iterations <= 1024; NaN is refused.
+ *             verts_in is never written; verts_in and verts_out must not overlap.
+ *   normals   for vertex a with a finite position v, over the entries (b, c) of its row whose two positions are finite:
+ *             d1_x = ((double)v_b,x - (double)v_x) / ext_x, d2_x = ((double)v_c,x - (double)v_x) / ext_x, the cross product in box
+ *             units c = (d1y d2z - d1z d2y, d1z d2x - d1x d2z, d1x d2y - d1y d2x), N_x += fix(c_x, 16, 2^34).  Back in world
+ *             units (a cross product scales by the other two extents) s_x = (N_x / 2^34) * (ext_y * ext_z),
+ *             s_y = (N_y / 2^34) * (ext_z * ext_x), s_z = (N_z / 2^34) * (ext_x * ext_y): the sum of the face normals
+ *             (v_b - v_a) x (v_c - v_a), weighted by area.  2^24 entries of at most 16 * 2^34 units stay below 2^63; a face
+ *             spanning one cell of an R = 512 lattice has c = 2^-18, 2^16 units; the clamp only touches faces with an edge
+ *             longer than 2.8 extents.  len = sqrt((sx sx + sy sy) + sz sz); (float)(s_x / len) when len > 0, else 0 (an
+ *             unreferenced or non-finite vertex).  color_rows [V, 11] or NULL: the rows [x, -n, 0, 0, -n] of
+ *             nerf_mesh_write_vertices.
+ * Calls, with the same V and workspace throughout:
+ *   nerf_smooth_build      entries per vertex (integer atomics), their exclusive scan, the entries through per-row cursors.  The
+ *                          order inside a row depends on the arrival order; no result does.  No sort, no host read.
+ *   nerf_smooth_run        2 * iterations half-steps (iterations with mu = 0), one lane per vertex, alternating between verts_out
+ *                          and one workspace buffer so that the last one writes verts_out.
+ *   nerf_smooth_normals    normals_out [V, 3] (and color_rows) of `verts` over the rows of the build.
+ * Faces are not touched: the connectivity, orientation and closedness of the input are those of the output.  No float atomics,
+ * every output element has one writer: bit-reproducible, independent of the order of the faces, equivariant under a renumbering
+ * of the vertices.  workspace: nerf_smooth_workspace_bytes(V, F) bytes (-1 for arguments out of range), kept from the build on;
+ * its content on entry is unspecified.  Out of range: NERF_E_SHAPE; NULL: NERF_E_NULL; all argument checks run before any device
+ * work.  V = 0: nothing is launched.  F = 0: the build zeroes the row offsets with one memset and launches nothing; run and
+ * normals, which are not told F, then copy V rows and write V zero normals.
+ * Not done: no cotangent weights, no feature-preserving (bilateral) smoothing, no pinning of the vertices on the box faces, no
+ * smoothing of the density volume before marching cubes, no change to the simplifier's arithmetic.                                */
+int64_t nerf_smooth_workspace_bytes(int64_t V, int64_t F);
+int nerf_smooth_build(int64_t V, const int32_t* faces, int64_t F, void* workspace, void* stream);
+int nerf_smooth_run(const float* verts_in, int64_t V, const float* lo_host, const float* hi_host, int iterations, float lambda,
+                    float mu, void* workspace, float* verts_out, void* stream);
+int nerf_smooth_normals(const float* verts, int64_t V, const float* lo_host, const float* hi_host, void* workspace,
+                        float* normals_out, float* color_rows, void* stream);
+
 /* ---------------------------------------------------------------- fused renderer (a14 / a18)
  * replaces: rendering/render.py:164-241 render_rays_eval (coarse pass, importance sampling, sort, second pass)
  * as ONE call that enqueues the fixed kernel sequence on `stream`: nerf_sample_coarse -> nerf_query_fused ->

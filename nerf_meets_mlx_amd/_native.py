@@ -116,6 +116,10 @@ SIGNATURES = {
     "nerf_simplify_count": (_I, [_P, _P, _I64, _P, _I64, _I, _P, _P, _P]),
     "nerf_simplify_write": (_I, [_I64, _P, _I64, C.POINTER(C.c_float), C.POINTER(C.c_float), _I, _I, _P, _I64, _I64, _P, _P, _P, _P,
                                 _P, _P]),
+    "nerf_smooth_workspace_bytes": (_I64, [_I64, _I64]),
+    "nerf_smooth_build": (_I, [_I64, _P, _I64, _P, _P]),
+    "nerf_smooth_run": (_I, [_P, _I64, C.POINTER(C.c_float), C.POINTER(C.c_float), _I, _F, _F, _P, _P, _P]),
+    "nerf_smooth_normals": (_I, [_P, _I64, C.POINTER(C.c_float), C.POINTER(C.c_float), _P, _P, _P, _P]),
 }
 
 

@@ -22,6 +22,10 @@ section 14).  The reference has no such export; this is Instant-NGP's.
     per occupied cell placed by the cell's quadric (box corners and edges survive) or at the mean; opposite faces that land on
     the same three cells annihilate, so one-voxel-thick sheets vanish (include/nerf_hip.h "mesh simplification", DESIGN.md
     section 27).  `extract(..., simplify_grid, simplify_placement)` runs it between marching cubes and the colour query.
+  * `smooth(mesh, iterations, lo, hi, lam, mu)` moves the vertices by `iterations` pairs of Taubin's lambda|mu umbrella steps
+    (mu = 0: plain Laplacian) and recomputes the normals from the faces; the faces and the colours are the input's
+    (include/nerf_hip.h "mesh smoothing").  `extract(..., smooth_iterations, smooth_lambda, smooth_mu)`
+    runs it between marching cubes and the simplifier.
   * `write_ply` writes a binary little-endian PLY.
 """
 import ctypes as C
@@ -43,6 +47,7 @@ RELU, EXP = 0, 1             # NERF_OCC_RELU / NERF_OCC_EXP
 PLACEMENTS = {"mean": 0, "quadric": 1}   # NERF_SIMPLIFY_MEAN / NERF_SIMPLIFY_QUADRIC
 SIMPLIFY_MAX_ITEMS = 1 << 24  # vertices, faces
 SIMPLIFY_MAX_CLUSTERS = 1 << 21
+SMOOTH_MAX_ITERATIONS = 1024
 
 
 class Mesh(NamedTuple):
@@ -118,7 +123,7 @@ def _check_volume(who, volume, iso, lo=(0.0,) * 3, hi=(1.0,) * 3):
 
 
 def _mark(mark, stage):
-    """The stage hook of connected_components, filter_components, erode, reconstruct, _open_components and _simplify:
+    """The stage hook of connected_components, filter_components, erode, reconstruct, _open_components, _simplify and _smooth:
     mark(stage) just ahead of the stage's first C call (tools/ngp_mesh.py records a device event there).  None: nothing is
     called."""
     if mark is not None:
@@ -482,32 +487,125 @@ def simplify(mesh: Mesh, grid: int, lo, hi, placement: str = "quadric") -> Mesh:
     return _simplify(mesh, grid, lo, hi, placement, False)[0]
 
 
+def check_smooth_params(iterations, lam=0.5, mu=-0.53):
+    """(iterations, lam, mu) as (int, float, float), lam and mu rounded to float32 as the library receives them; ValueError for
+    an iterations that is a bool, non-integral or outside [0, SMOOTH_MAX_ITERATIONS] (0: no smoothing), a lam outside (0, 1], a
+    mu that is neither 0 nor in [-2, 0), or either being a bool, not a real number or NaN."""
+    if isinstance(iterations, bool) or not isinstance(iterations, numbers.Integral) \
+            or not 0 <= int(iterations) <= SMOOTH_MAX_ITERATIONS:
+        raise ValueError(f"smooth iterations must be an int in [0, {SMOOTH_MAX_ITERATIONS}], got {iterations!r}")
+    out = []
+    for name, x in (("lambda", lam), ("mu", mu)):
+        if isinstance(x, bool) or not isinstance(x, numbers.Real) or math.isnan(float(x)):
+            raise ValueError(f"smooth {name} must be a number, got {x!r}")
+        with np.errstate(over="ignore"):
+            out.append(float(np.float32(float(x))))
+    lam, mu = out
+    if not 0.0 < lam <= 1.0:
+        raise ValueError(f"smooth lambda must be in (0, 1] as a float32, got {lam!r}")
+    if not (mu == 0.0 or -2.0 <= mu < 0.0):
+        raise ValueError(f"smooth mu must be 0 (plain Laplacian) or in [-2, 0), got {mu!r}")
+    return int(iterations), lam, mu
+
+
+def check_smooth_args(mesh, iterations, lo: Sequence[float], hi: Sequence[float], lam=0.5, mu=-0.53):
+    """(iterations, lo [3], hi [3], lam, mu) as (int, float lists, floats); ValueError for an iterations that is not an int in
+    [1, SMOOTH_MAX_ITERATIONS], a lam outside (0, 1], a mu that is neither 0 nor in [-2, 0) (bools, non-numbers and NaN are
+    refused), a box with lo >= hi or a non-finite corner, or a mesh whose tensors are not contiguous verts float32 [V, 3], faces
+    int32 [F, 3], normals float32 [V, 3] and colors None or float32 [V, 3] on one device, with V, F <= 2^24."""
+    iterations, lam, mu = check_smooth_params(iterations, lam, mu)
+    if iterations < 1:
+        raise ValueError(f"smooth iterations must be an int in [1, {SMOOTH_MAX_ITERATIONS}], got {iterations!r}")
+    _, lo, hi, _ = check_mesh_args(2, lo, hi)
+    if not isinstance(mesh, Mesh):
+        raise ValueError(f"smooth: need an engine.mesh.Mesh, got {type(mesh).__name__}")
+
+    def ok(t, dtype, rows=None):
+        return torch.is_tensor(t) and t.dtype == dtype and t.dim() == 2 and t.shape[1] == 3 and t.is_contiguous() \
+            and (rows is None or t.shape[0] == rows) and t.device == mesh.verts.device
+    if not ok(mesh.verts, torch.float32):
+        raise ValueError("smooth: verts must be a contiguous float32 [V, 3] tensor")
+    V = mesh.verts.shape[0]
+    if not ok(mesh.faces, torch.int32):
+        raise ValueError("smooth: faces must be a contiguous int32 [F, 3] tensor on the vertices' device")
+    if not ok(mesh.normals, torch.float32, V):
+        raise ValueError("smooth: normals must be a contiguous float32 [V, 3] tensor on the vertices' device")
+    if mesh.colors is not None and not ok(mesh.colors, torch.float32, V):
+        raise ValueError("smooth: colors must be None or a contiguous float32 [V, 3] tensor on the vertices' device")
+    if V > SIMPLIFY_MAX_ITEMS or mesh.faces.shape[0] > SIMPLIFY_MAX_ITEMS:
+        raise ValueError(f"smooth: at most 2^24 vertices and faces, got {V} and {mesh.faces.shape[0]}")
+    return iterations, lo, hi, lam, mu
+
+
+def _smooth(mesh: Mesh, iterations, lo, hi, lam, mu, color_rows: bool, mark=None):
+    """(Mesh, colour rows or None).  mark: _mark's hook ("build", "run", "normals")."""
+    iterations, lo, hi, lam, mu = check_smooth_args(mesh, iterations, lo, hi, lam, mu)
+    dev = mesh.verts.device
+    V, F = mesh.verts.shape[0], mesh.faces.shape[0]
+    L = N.lib()
+    clo, chi = _box(lo, hi)
+    verts = torch.empty(V, 3, dtype=torch.float32, device=dev)
+    normals = torch.empty(V, 3, dtype=torch.float32, device=dev)
+    rows = torch.empty(V, 11, dtype=torch.float32, device=dev) if color_rows else None
+    if V:
+        ws = torch.empty(L.nerf_smooth_workspace_bytes(V, F), dtype=torch.uint8, device=dev)
+        _mark(mark, "build")
+        N.check(L.nerf_smooth_build(V, N.ptr(mesh.faces), F, N.ptr(ws), N.stream()))
+        _mark(mark, "run")
+        N.check(L.nerf_smooth_run(N.ptr(mesh.verts), V, clo, chi, iterations, lam, mu, N.ptr(ws), N.ptr(verts), N.stream()))
+        _mark(mark, "normals")
+        N.check(L.nerf_smooth_normals(N.ptr(verts), V, clo, chi, N.ptr(ws), N.ptr(normals), N.ptr(rows), N.stream()))
+    return Mesh(verts, mesh.faces, normals, mesh.colors), rows
+
+
+def smooth(mesh: Mesh, iterations: int, lo, hi, lam: float = 0.5, mu: float = -0.53) -> Mesh:
+    """The mesh after `iterations` pairs of Taubin's lambda|mu filter: an umbrella-Laplacian half-step with factor `lam`, then
+    one with `mu` (< -lam keeps the volume; mu = 0 is plain Laplacian smoothing and launches no second half-step).  A
+    neighbour weighs as many times as faces share the edge; the box [lo, hi] only fixes the fixed-point scale of the exact
+    sums.  Same `faces` tensor, new `verts`, new `normals` (area-weighted from the faces), `colors` carried over: vertices
+    keep their identity (nerf_smooth_build, nerf_smooth_run, nerf_smooth_normals; no host read).  Bit-reproducible and
+    independent of the order of the faces."""
+    return _smooth(mesh, iterations, lo, hi, lam, mu, False)[0]
+
+
 def extract(query, activation: int, resolution: int, threshold: float, lo, hi, colors: bool = True, device="cuda",
             min_component: int = 0, largest_only: bool = False, opening_radius: int = 0, simplify_grid: int = 0,
-            simplify_placement: str = "quadric") -> Mesh:
+            simplify_placement: str = "quadric", smooth_iterations: int = 0, smooth_lambda: float = 0.5,
+            smooth_mu: float = -0.53) -> Mesh:
     """density_volume -> (with opening_radius > 0: open_components; else with min_component > 1 or largest_only:
-    filter_components) -> marching_cubes at `threshold` -> (with simplify_grid > 0: simplify on that grid of the box) ->
-    (optionally) vertex colours, queried on the final mesh's rows: the field is asked once per vertex that is kept.
-    With opening_radius > 0 `min_component` counts core voxels (open_components).  With the defaults none of them is called."""
+    filter_components) -> marching_cubes at `threshold` -> (with smooth_iterations > 0: smooth) -> (with simplify_grid > 0:
+    simplify on that grid of the box) -> (optionally) vertex colours, queried on the final mesh's rows: the field is asked once
+    per vertex that is kept.  With opening_radius > 0 `min_component` counts core voxels (open_components).  With the defaults
+    none of them is called."""
     check_mesh_args(resolution, lo, hi, threshold)
     min_component, largest_only = check_component_args(min_component, largest_only, resolution)
     opening_radius = check_opening_args(opening_radius)
     simplify_grid = check_simplify_grid(simplify_grid)
     if simplify_placement not in PLACEMENTS:
         raise ValueError(f"simplify placement must be one of {sorted(PLACEMENTS)}, got {simplify_placement!r}")
+    check_smooth_params(smooth_iterations, smooth_lambda, smooth_mu)
     vol = density_volume(query, activation, resolution, lo, hi, device=device)
     if opening_radius > 0:
         vol = open_components(vol, threshold, opening_radius, min_component, largest_only)
     elif min_component > 1 or largest_only:
         vol = filter_components(vol, threshold, min_component, largest_only)
-    return mesh_volume(query, vol, threshold, lo, hi, colors, simplify_grid, simplify_placement)
+    return mesh_volume(query, vol, threshold, lo, hi, colors, simplify_grid, simplify_placement, smooth_iterations, smooth_lambda,
+                       smooth_mu)
 
 
-def mesh_volume(query, vol, iso, lo, hi, colors: bool, simplify_grid: int = 0, simplify_placement: str = "quadric") -> Mesh:
-    """marching_cubes of `vol` at `iso` -> (with simplify_grid > 0: simplify) -> (with `colors`) vertex_colors of `query` on the
-    final mesh's rows [x, -n, 0, 0, -n].  With simplify_grid 0 the calls are those of marching cubes and the colour query alone."""
-    if simplify_grid > 0:
-        mesh, rows = _simplify(_marching_cubes(vol, iso, lo, hi, False)[0], simplify_grid, lo, hi, simplify_placement, colors)[:2]
+def mesh_volume(query, vol, iso, lo, hi, colors: bool, simplify_grid: int = 0, simplify_placement: str = "quadric",
+                smooth_iterations: int = 0, smooth_lambda: float = 0.5, smooth_mu: float = -0.53) -> Mesh:
+    """marching_cubes of `vol` at `iso` -> (with smooth_iterations > 0: smooth) -> (with simplify_grid > 0: simplify) -> (with
+    `colors`) vertex_colors of `query` on the final mesh's rows [x, -n, 0, 0, -n]: the simplifier's, else the smoother's, else
+    marching cubes'.  With smooth_iterations 0 and simplify_grid 0 the calls are those of marching cubes and the colour query
+    alone."""
+    smooth_iterations = check_smooth_params(smooth_iterations, smooth_lambda, smooth_mu)[0]
+    if smooth_iterations > 0 or simplify_grid > 0:
+        mesh, rows = _marching_cubes(vol, iso, lo, hi, False)[0], None
+        if smooth_iterations > 0:
+            mesh, rows = _smooth(mesh, smooth_iterations, lo, hi, smooth_lambda, smooth_mu, colors and simplify_grid == 0)
+        if simplify_grid > 0:
+            mesh, rows = _simplify(mesh, simplify_grid, lo, hi, simplify_placement, colors)[:2]
     else:
         mesh, rows = _marching_cubes(vol, iso, lo, hi, colors)
     if not colors:

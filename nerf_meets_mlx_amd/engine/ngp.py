@@ -461,7 +461,8 @@ class NGPTrainer(Trainer):
 
     def extract_mesh_tsdf(self, resolution: int = 256, aabb=None, poses=None, trunc=None, acc_min: float = 0.5, carve: bool = True,
                           min_views: int = 1, colors: bool = True, min_component: int = 0, largest_only: bool = False,
-                          opening_radius: int = 0, simplify_grid: int = 0, simplify_placement: str = "quadric"):
+                          opening_radius: int = 0, simplify_grid: int = 0, simplify_placement: str = "quadric",
+                          smooth_iterations: int = 0, smooth_lambda: float = 0.5, smooth_mu: float = -0.53):
         """engine.mesh.Mesh of the zero level set of a TSDF fused from this field's own depth renders (DESIGN.md section 21;
         KinectFusion, nerfstudio's TSDF export): render_depth at every pose of `poses` ([n, 3 or 4, 4]; None: the training
         poses), engine.mesh.TSDFVolume(resolution, box, trunc).integrate with far = the trainer's far, volume(min_views), the
@@ -470,7 +471,8 @@ class NGPTrainer(Trainer):
         it; a ray with opacity below `acc_min` carves (with `carve`) every voxel along it.  trunc=None: 4 voxels
         (TSDFVolume).  The order of `poses` is the fusion order and fixes the bits of the result: the running mean is a
         float32 recurrence, so another order may differ in the last place.  `simplify_grid` / `simplify_placement` as in
-        extract_mesh: the mesh is clustered before it is coloured.  Runs on this rank only, no collective."""
+        extract_mesh: the mesh is clustered before it is coloured; `smooth_iterations` / `smooth_lambda` / `smooth_mu` as in
+        extract_mesh: the mesh is smoothed before it is clustered.  Runs on this rank only, no collective."""
         from . import mesh
         lo, hi = self._mesh_box(aabb)
         R = mesh.check_mesh_args(resolution, lo, hi, 0.0)[0]
@@ -480,6 +482,7 @@ class NGPTrainer(Trainer):
         simplify_grid = mesh.check_simplify_grid(simplify_grid)
         if simplify_placement not in mesh.PLACEMENTS:
             raise ValueError(f"simplify placement must be one of {sorted(mesh.PLACEMENTS)}, got {simplify_placement!r}")
+        mesh.check_smooth_params(smooth_iterations, smooth_lambda, smooth_mu)
         poses = self.poses if poses is None else poses
         views = mesh.tsdf_views(poses, self.K)
         tsdf = mesh.TSDFVolume(R, lo, hi, trunc=trunc, device=self.device)
@@ -496,7 +499,8 @@ class NGPTrainer(Trainer):
         elif min_component > 1 or largest_only:
             vol = mesh.filter_components(vol, 0.0, min_component, largest_only)
         query = self._mesh_field()[0] if colors else None          # (reading the field joins the comm stream: only when it is asked)
-        return mesh.mesh_volume(query, vol, 0.0, lo, hi, colors, simplify_grid, simplify_placement)
+        return mesh.mesh_volume(query, vol, 0.0, lo, hi, colors, simplify_grid, simplify_placement, smooth_iterations, smooth_lambda,
+                                smooth_mu)
 
     def train_step(self, rays=None, target=None, u=None, background=None) -> Dict[str, torch.Tensor]:
         """background (random_background trainers only, with explicit rays and target [B, 4]): the colours bg [B, 3] behind the

@@ -217,7 +217,8 @@ class Trainer:
 
     def extract_mesh(self, resolution: int = 256, threshold: float = 2.5, aabb=None, colors: bool = True,
                      min_component: int = 0, largest_only: bool = False, opening_radius: int = 0, simplify_grid: int = 0,
-                     simplify_placement: str = "quadric"):
+                     simplify_placement: str = "quadric", smooth_iterations: int = 0, smooth_lambda: float = 0.5,
+                     smooth_mu: float = -0.53):
         """engine.mesh.Mesh of {sigma > threshold}: marching cubes over density_volume(resolution, aabb), vertex colours (when
         `colors`) from the field queried at each vertex looking along -normal, clamped to [0, 1].  2.5 is Instant-NGP's default
         threshold; sigma's scale is the model's own (relu of the raw output for the 8 x 256 and the 64-sample hash-grid fields,
@@ -229,16 +230,20 @@ class Trainer:
         section 18): floaters that hang on the surface by bridges thinner than 2 r + 1 voxels go too, and so does everything
         else that thin.  `simplify_grid` G > 0 clusters the mesh on the G^3 cells of the box before it is coloured
         (engine.mesh.simplify; `simplify_placement` "quadric" or "mean"): the colours are then queried at the
-        simplified mesh's vertices.  Runs on this rank only: no collective, any rank may call it alone."""
+        simplified mesh's vertices.  `smooth_iterations` n > 0 first runs n pairs of Taubin's lambda|mu filter on the marching-cubes
+        mesh (engine.mesh.smooth; `smooth_lambda`, `smooth_mu`, mu = 0 for plain Laplacian): the voxel-scale
+        roughness of the field goes, the faces stay.  Runs on this rank only: no collective, any rank may call it alone."""
         from . import mesh
         lo, hi = self._mesh_box(aabb)
         mesh.check_component_args(min_component, largest_only, mesh.check_mesh_args(resolution, lo, hi, threshold)[0])
         mesh.check_opening_args(opening_radius)
         mesh.check_simplify_grid(simplify_grid)
+        mesh.check_smooth_params(smooth_iterations, smooth_lambda, smooth_mu)
         query, act = self._mesh_field()
         return mesh.extract(query, act, resolution, threshold, lo, hi, colors=colors, device=self.device,
                             min_component=min_component, largest_only=largest_only, opening_radius=opening_radius,
-                            simplify_grid=simplify_grid, simplify_placement=simplify_placement)
+                            simplify_grid=simplify_grid, simplify_placement=simplify_placement,
+                            smooth_iterations=smooth_iterations, smooth_lambda=smooth_lambda, smooth_mu=smooth_mu)
 
     # ---------------------------------------------------------------- checkpoint (SURVEY 8f-3)
     def _checkpoint_buffers(self):

@@ -31,6 +31,11 @@ the clusters, the device ms of the simplifier alone (cluster, the sort, count wi
 it, and the geometry figures of the simplified vertices (the share within h of a box face, the count beyond 2 h; h is the
 marching-cubes lattice's) beside the input mesh's.
 
+With --smooth N (repeatable), one more line per N and R for the density mesh: N pairs of Taubin's lambda|mu filter (DESIGN.md
+section 30; --smooth-lambda, --smooth-mu, mu 0 for plain Laplacian) -- the device ms of the build, of the half-steps (and of one),
+of the normals, V and F, the geometry figures, the enclosed volume and the roughness (the mean distance of a vertex from the mean
+of its neighbours) before and after; and with --simplify the simplifier's lines for the smoothed mesh (source "density smooth N").
+
     rocprofv3 --kernel-trace --output-format csv -d DIR -o mesh -- python tools/ngp_mesh.py --ckpt /tmp/ngp.npz --reps 1 --no-ply
     python tools/ngp_mesh.py --stats DIR/.../mesh_kernel_trace.csv --from profiles/ngp_mesh.jsonl --out profiles/ngp_mesh_kernels.jsonl
 
@@ -181,6 +186,68 @@ def _simplify_arms(m, source, R, lo, hi, a, rec, bound, boxes, extra=None):
     return out
 
 
+def _enclosed_volume(verts, faces):
+    """sum of a . (b x c) / 6 in float64 (tests/_mesh_ref.enclosed_volume)."""
+    v, f = verts.double(), faces.long()
+    a, b, c = v[f[:, 0]], v[f[:, 1]], v[f[:, 2]]
+    return float((a * torch.linalg.cross(b, c)).sum() / 6.0)
+
+
+def _roughness(verts, faces):
+    """The mean distance of a referenced vertex from the mean of its neighbours, one count per face on the shared edge."""
+    v, f = verts.double(), faces.long()
+    S = torch.zeros_like(v)
+    n = torch.zeros(v.shape[0], dtype=torch.float64, device=v.device)
+    for r, o in ((0, (1, 2)), (1, (2, 0)), (2, (0, 1))):
+        for k in o:
+            S.index_add_(0, f[:, r], v[f[:, k]])
+            n.index_add_(0, f[:, r], torch.ones(f.shape[0], dtype=torch.float64, device=v.device))
+    use = n > 0
+    return float((S[use] / n[use, None] - v[use]).norm(dim=1).mean())
+
+
+def _smooth_timed(m, iterations, lo, hi, lam, mu):
+    """engine.mesh.smooth: (Mesh, [build, run, normals] ms)."""
+    from nerf_meets_mlx_amd.engine import mesh
+    st = _Stages()
+    sm, _ = mesh._smooth(m, iterations, lo, hi, lam, mu, False, st)
+    st("end")
+    t = st.ms()
+    return sm, [t["build"], t["run"], t["normals"]]
+
+
+def _smooth_arms(m, source, R, lo, hi, a, rec, bound, boxes):
+    """One JSON line per --smooth N for the mesh `m` of the volume `source`, then the simplifier's lines for the smoothed mesh."""
+    out = []
+    if m.verts.shape[0] == 0 or m.faces.shape[0] == 0:
+        return out
+    before = {"geometry": _geometry(m.verts, R, bound, boxes), "enclosed_volume": _enclosed_volume(m.verts, m.faces),
+              "roughness": _roughness(m.verts, m.faces)}
+    for n_it in a.smooth or []:
+        _smooth_timed(m, n_it, lo, hi, a.smooth_lambda, a.smooth_mu)          # warm
+        ts = []
+        for _ in range(a.reps):
+            sm, ms = _smooth_timed(m, n_it, lo, hi, a.smooth_lambda, a.smooth_mu)
+            ts.append(ms)
+        t = np.mean(np.array(ts), 0)
+        steps = n_it * (1 if a.smooth_mu == 0 else 2)
+        arm = {"tool": "ngp_mesh smooth", "source": source, "R": R, "iterations": n_it, "lambda": a.smooth_lambda, "mu": a.smooth_mu,
+               "iters": rec["iters"], "seed": rec["seed"], "V": int(m.verts.shape[0]), "F": int(m.faces.shape[0]),
+               "half_steps": steps, "smooth_ms": float(t.sum()), "build_ms": float(t[0]), "run_ms": float(t[1]),
+               "half_step_us": float(1e3 * t[1] / steps), "normals_ms": float(t[2]),
+               "smooth_ms_range": [float(np.sum(x)) for x in (min(ts, key=sum), max(ts, key=sum))],
+               "marching_cubes_ms": rec.get("marching_cubes_ms"), "before": before,
+               "after": {"geometry": _geometry(sm.verts, R, bound, boxes), "enclosed_volume": _enclosed_volume(sm.verts, sm.faces),
+                         "roughness": _roughness(sm.verts, sm.faces)}, "device": rec["device"]}
+        print(json.dumps(arm), flush=True)
+        out.append(arm)
+        out += _simplify_arms(sm, f"{source} smooth {n_it}", R, lo, hi, a, rec, bound, boxes,
+                              {"smooth_iterations": n_it, "smooth_lambda": a.smooth_lambda, "smooth_mu": a.smooth_mu})
+        del sm
+    torch.cuda.empty_cache()
+    return out
+
+
 def _tsdf_arm(tr, mesh, R, lo, hi, a, rec, bound, boxes):
     """The TSDF export of the same field as its stages, each between device events (the last of --reps runs is kept)."""
     poses = tr.poses if a.tsdf_views is None else tr.poses[:a.tsdf_views]
@@ -241,7 +308,7 @@ def _ply_check(m, path):
             "ply_directed_edges_unique": bool(len(np.unique(key)) == len(key))}
 
 
-def main():
+def parser():
     ap = argparse.ArgumentParser()
     ap.add_argument("--iters", type=int, default=2000)
     ap.add_argument("--hw", type=int, default=800)
@@ -272,11 +339,21 @@ def main():
     ap.add_argument("--simplify", type=int, action="append", default=None,
                     help="also cluster every mesh on a grid of this size (DESIGN.md section 27); repeatable: one JSON line per "
                          "grid and meshed volume")
+    ap.add_argument("--smooth", type=int, action="append", default=None,
+                    help="also smooth the density mesh by this many Taubin pairs (DESIGN.md section 30); repeatable: one JSON "
+                         "line per value and R, and with --simplify the simplifier's lines for the smoothed mesh")
+    ap.add_argument("--smooth-lambda", type=float, default=0.5)
+    ap.add_argument("--smooth-mu", type=float, default=-0.53, help="0: plain Laplacian smoothing")
     ap.add_argument("--ckpt", default=None, help="load this checkpoint instead of training")
     ap.add_argument("--save-ckpt", default=None, help="save the trained state here")
     ap.add_argument("--out", default=None, help="append the JSON lines to this file")
     ap.add_argument("--stats", default=None, help="summarise a rocprofv3 --kernel-trace CSV of this tool instead of measuring")
     ap.add_argument("--from", dest="from_", default=None, help="--stats: the measuring run's JSON lines (V and F per R)")
+    return ap
+
+
+def main():
+    ap = parser()
     a = ap.parse_args()
     if a.stats:
         return stats(a)
@@ -346,6 +423,7 @@ def main():
         print(json.dumps(rec), flush=True)
         lines.append(rec)
         lines += _simplify_arms(m._replace(colors=None), "density", R, lo, hi, a, rec, bound, boxes)
+        lines += _smooth_arms(m._replace(colors=None), "density", R, lo, hi, a, rec, bound, boxes)
         del vol, m, rows, col
         torch.cuda.empty_cache()
         if a.tsdf:
@@ -476,7 +554,7 @@ def stats(a):
     gx = col.get("grid_size_x", col.get("grid_size"))
     groups = {}
     for r in rows:
-        m = re.search(r"(mesh_\w+_kernel|ccl_\w+_kernel|morph_\w+_kernel|tsdf_\w+_kernel|simp_\w+_kernel|occ_cull_scan_kernel|occ_merge_exp_kernel)", r[name_k])
+        m = re.search(r"(mesh_\w+_kernel|ccl_\w+_kernel|morph_\w+_kernel|tsdf_\w+_kernel|simp_\w+_kernel|smooth_\w+_kernel|occ_cull_scan_kernel|occ_merge_exp_kernel)", r[name_k])
         if not m:
             continue
         k = m.group(1)
@@ -487,7 +565,7 @@ def stats(a):
             R = next((R for R in runs if _morph_grid(k, R) == grid), None)
             groups.setdefault((k, R), []).append((int(r[e_k]) - int(r[s_k])) * 1e-3)
             continue
-        if k.startswith("simp_"):                      # sized by the mesh: one lane per vertex or face of the run at R; else pooled
+        if k.startswith(("simp_", "smooth_")):         # sized by the mesh: one lane per vertex or face of the run at R; else pooled
             R = next((R for R, run in runs.items() if grid in (-(-run["V"] // BLOCK) * BLOCK, -(-run["F"] // BLOCK) * BLOCK)), None)
         elif k in ("mesh_points_kernel", "occ_merge_exp_kernel", "occ_cull_scan_kernel", "ccl_finish_kernel"):
             R = None                                                       # chunked / one workgroup: pooled per kernel
