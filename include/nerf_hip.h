@@ -279,7 +279,7 @@ typedef struct nerf_mlp_arch {
                      * activations (nerf_mlp_forward, nerf_query_fused / nerf_render_rays_fused with acts == NULL) run the
                      * split-fp16 kernel of csrc/mlp22.hip: every float32 operand x = hi + lo 2^-11 as two fp16 numbers
                      * (22 significand bits), a product = hi hi + 2^-11 (hi lo + lo hi) on v_mfma_f32_16x16x32_f16 with
-                     * fp32 accumulate, float32-accurate encodings; operands must stay inside the fp16 range
+                     * fp32 accumulate, encodings within 6e-7 of the float64 sine; operands must stay inside the fp16 range
                      * (|activation| < 65504: an overflow becomes inf / NaN in the output, never a silent wrong value).
                      * Everything that keeps activations (training forward with acts != NULL, nerf_mlp_backward) runs the
                      * split-bf16 kernels of csrc/mlp_s16.hip: x = hi + lo as two bf16 numbers (16 significand bits at

@@ -154,7 +154,7 @@ __global__ void __launch_bounds__(256) pack22_kernel(const float* __restrict__ p
   }
 }
 
-// positional encodings, float32-accurate, straight into (hi, lo) B fragments: mlp_input.h (here: SinCodyWaite, SplitF16)
+// positional encodings (within 6e-7 of the float64 sine before the split), straight into (hi, lo) B fragments: mlp_input.h (here: SinCodyWaite, SplitF16)
 template <int COUNT>
 __device__ __forceinline__ void split_slots(const float (&v)[COUNT], u32x4* hi, u32x4* lo) {
 #pragma unroll

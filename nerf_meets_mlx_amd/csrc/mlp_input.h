@@ -214,11 +214,15 @@ struct SinRevFract : ByPhase<SinRevFract> {
     return __builtin_amdgcn_sinf(__builtin_amdgcn_fractf((x * f) * INV_2PI + ph));
   }
 };
-// split-bf16 training and split-fp16 render (float32-accurate): Cody-Waite, a - k 2 pi with 2 pi = HI + LO in two fused steps,
-// then v_sin_f32 on revolutions in [-3/4, 3/4].  k = rint(a / 2 pi) grows with the argument a = x f: |k| <= 82 for |x| <= 1 at the
-// top frequency f = 2^9 (freq_mode 1; 81 in mode 0), and |k| <= 489 at |x| = 6, the far end of the scenes' depth range, where
-// k HI has more bits than a float32 holds.  The steps are fused multiply-adds, so no product is rounded, whatever k; each step
-// rounds its sum, a remainder of at most pi in size, once; |k LO| <= 8.6e-5 at |k| = 489.
+// split-bf16 training and split-fp16 render: Cody-Waite, a - k 2 pi with 2 pi = HI + LO in two fused steps, then v_sin_f32 on
+// revolutions in [-3/4, 3/4].  k = rint(a / 2 pi) grows with the argument a = x f: |k| <= 81 for |x| <= 1 at the top frequency
+// f = 2^9 (freq_mode 1; 13 in mode 0, whose top frequency is 81), and |k| <= 489 at |x| = 6, the far end of the scenes' depth
+// range (77 in mode 0), where k HI has more bits than a float32 holds.  The steps are fused multiply-adds, so no product is
+// rounded, whatever k; each step rounds its sum, a remainder of at most pi in size, once; |k LO| <= 8.6e-5 at |k| = 489.
+// Accuracy against the float64 sine of the float32 argument, before the packer: the reduction errs by at most 5.6e-7 (two half
+// ulps of a remainder, half an ulp of the revolutions, INV_2PI's rounding; 4.0e-7 seen out to |x| = 64) and v_sin_f32 adds
+// 9.3e-8 (measured) -- "float32 tolerance", about five times the error of a float32 sinf, not its last bit
+// (tests/test_encoding_host.py, tests/test_gpu_encodings.py).
 struct SinCodyWaite : ByPhase<SinCodyWaite> {
   static __device__ __forceinline__ float sin_ph(float x, float f, float ph) {
     const float a = x * f;

@@ -49,7 +49,7 @@ typedef RingW<B_CHUNKS, B_FRAGS, 4, NW, RING_CHUNK, RING_STAGES, true> BwdRing;
 struct ViewPairPack : ViewPack { static constexpr int B_PADDED = s16::B_PADDED / 2; };
 static_assert(ViewPairPack::B_PADDED >= L::B_TOTAL, "the padded stream holds every transposed fragment");
 
-// positional encodings, float32-accurate, straight into (hi, lo) B fragments: mlp_input.h (here: SinCodyWaite, SplitBf16)
+// positional encodings (within 6e-7 of the float64 sine before the split), straight into (hi, lo) B fragments: mlp_input.h (here: SinCodyWaite, SplitBf16)
 
 // All 12 layers for the wave's 32 samples (sample tile `tile0`).  Waves past the end compute on clamped inputs, store into
 // the padding tiles of the workspace and write no output, so every wave runs the same instruction stream (the ring needs it).
