@@ -860,6 +860,64 @@ int nerf_smooth_run(const float* verts_in, int64_t V, const float* lo_host, cons
 int nerf_smooth_normals(const float* verts, int64_t V, const float* lo_host, const float* hi_host, void* workspace,
                         float* normals_out, float* color_rows, void* stream);
 
+/* ---------------------------------------------------------------- texture atlas (no reference counterpart)
+ * A texture for a finished mesh, baked by one field query per texel: a simplified mesh then carries the field's appearance at
+ * a resolution of its own, not one colour per surviving vertex.  A separate step behind the export pipeline; it changes no
+ * mesh.  Additive: NERF_ABI_VERSION stays 3.  All arithmetic is IEEE float32, one rounding per operation (no contraction), in
+ * exactly the order and grouping written here; a / b and sqrt are correctly rounded; pos(x) = x > 0 ? x : 0 and
+ * unit(x) = min(pos(x), 1) send NaN to 0.  tests/_texture_ref.py reproduces every output bit for bit.
+ *   input     verts, normals [V, 3] float32, faces [F, 3] int32, 0 <= V, F <= 2^24; texels T, an int in [2, 64].
+ *   layout    every face gets a right triangle of T texels a leg; two faces share a square cell of side S = T + 2.
+ *             cells = ceil(F / 2); C = the smallest integer >= 1 with C C >= cells; W = C S, H = max(1, ceil(cells / C)) S; both
+ *             at most NERF_TEXTURE_MAX_SIDE, else NERF_E_SHAPE with a text that names the largest T that fits.  Atlas texel
+ *             (X, Y), Y the image row and row 0 the top one, raster index p = X + W Y (int64), lies in cell
+ *             c = (Y / S) C + X / S at (i, j) = (X mod S, Y mod S).  It belongs to face 2c if i + j <= S - 1; otherwise to face
+ *             2c + 1, and (i, j) becomes (S - 1 - i, S - 1 - j).  A texel whose face is >= F is unused.
+ *   corners   face (a, b, c) has a at the centre of its local texel (0, 0), b at (T - 1, 0), c at (0, T - 1).  Local texel (i, j)
+ *             has the barycentrics wb = (float)i / (float)(T - 1), wc = (float)j / (float)(T - 1), wa = (1 - wb) - wc.  wa is not
+ *             clamped: the texels beyond the hypotenuse (the gutter) lie in the face's plane at extrapolated positions, so a
+ *             bilinear lookup of a field that is affine in position reproduces it up to the 8-bit quantisation.  Every texel
+ *             with a non-zero weight in a bilinear lookup inside a face's UV triangle belongs to that face, up to rounding
+ *             on the hypotenuse: the float32 products of `sample` can put a point of it one ulp outside, and the diagonal
+ *             texel of the cell's other face then gets a weight of order 1e-14.
+ *   bad face  a face with an index outside [0, V) gets zero rows and black texels; nothing is read through the index, and
+ *             nothing is read on the host to find such faces.
+ *   row       position x = (wa A + wb B) + wc C per axis; direction m = (pos(wa) nA + pos(wb) nB) + pos(wc) nC from the vertex
+ *             normals, len = sqrt((mx mx + my my) + mz mz), n = m / len when 0 < len < inf, else 0.  The row is
+ *             [x, -n, 0, 0, -n], the colour query row of nerf_mesh_write_vertices; the row of an unused texel or of a bad face
+ *             is eleven +0.
+ *   colour    byte = (uint8)rint(255 unit(c)) for the first three of the four floats the query returned for the texel; 0 for
+ *             an unused texel or a bad face whatever raw holds.
+ *   uv        the corner at atlas texel (X, Y): u = ((float)X + 0.5f) / (float)W, v = 1.0f - ((float)Y + 0.5f) / (float)H
+ *             (OBJ's convention: v goes up).
+ *   sample    (face, wb, wc): wb = unit(wb); wc = min(pos(wc), 1 - wb).  A face outside [0, F) gives rgb 0 and a zero row.  Local
+ *             texel coordinates x = wb (float)(T - 1), y = wc (float)(T - 1); i0 = (int)floor(x) clamped to [0, S - 2], j0
+ *             likewise, fx = x - (float)i0, fy = y - (float)j0; with gx = 1 - fx, gy = 1 - fy the weights are w00 = gx gy,
+ *             w10 = fx gy, w01 = gx fy, w11 = fx fy (the first index along i), c = (float)byte / 255.0f, and per channel
+ *             rgb = ((w00 c00 + w10 c10) + w01 c01) + w11 c11.  The optional row is that of `row` at (wb, wc).
+ * Calls:
+ *   nerf_texture_layout    host only: out = {W, H, C, S}.  Needs no device.
+ *   nerf_texture_rows      rows [count, 11] of the texels [p0, p0 + count) of the atlas in raster order, one lane per texel.
+ *   nerf_texture_store     image [H, W, 3] uint8 for the same texels from raw [count, 4] (16-byte aligned), one lane per texel;
+ *                          the bytes of other texels are not touched, so the image does not depend on how the atlas is cut
+ *                          into chunks.
+ *   nerf_texture_uv        uv [F, 3, 2], one lane per face.
+ *   nerf_texture_sample    rgb [n, 3] and, when `rows` is not NULL, rows [n, 11] of n < 2^31 samples sample_face [n] int32,
+ *                          bary [n, 2] = (wb, wc); verts, normals and faces are read for the rows only.
+ * No atomics, no workspace, no host read; every output element has one writer: bit-reproducible.  Out of range: NERF_E_SHAPE;
+ * NULL: NERF_E_NULL; all argument checks run before any device work.  count = 0, n = 0, F = 0 (uv): nothing is launched.
+ * Not done: no mipmaps (the atlas is safe for bilinear filtering at level 0 only), no chart packing by area (every face gets the
+ * same texels whatever its size), no seam handling across face edges beyond the shared field.                                    */
+#define NERF_TEXTURE_MAX_SIDE 16384
+int nerf_texture_layout(int64_t F, int texels, int64_t* out_host);
+int nerf_texture_rows(const float* verts, const float* normals, int64_t V, const int32_t* faces, int64_t F, int texels, int64_t p0,
+                      int64_t count, float* rows, void* stream);
+int nerf_texture_store(const float* raw, int64_t V, const int32_t* faces, int64_t F, int texels, int64_t p0, int64_t count,
+                       uint8_t* image, void* stream);
+int nerf_texture_uv(int64_t F, int texels, float* uv, void* stream);
+int nerf_texture_sample(const uint8_t* image, const float* verts, const float* normals, int64_t V, const int32_t* faces, int64_t F,
+                        int texels, const int32_t* sample_face, const float* bary, int64_t n, float* rgb, float* rows, void* stream);
+
 /* ---------------------------------------------------------------- fused renderer (a14 / a18)
  * replaces: rendering/render.py:164-241 render_rays_eval (coarse pass, importance sampling, sort, second pass)
  * as ONE call that enqueues the fixed kernel sequence on `stream`: nerf_sample_coarse -> nerf_query_fused ->

@@ -120,6 +120,11 @@ SIGNATURES = {
     "nerf_smooth_build": (_I, [_I64, _P, _I64, _P, _P]),
     "nerf_smooth_run": (_I, [_P, _I64, C.POINTER(C.c_float), C.POINTER(C.c_float), _I, _F, _F, _P, _P, _P]),
     "nerf_smooth_normals": (_I, [_P, _I64, C.POINTER(C.c_float), C.POINTER(C.c_float), _P, _P, _P, _P]),
+    "nerf_texture_layout": (_I, [_I64, _I, C.POINTER(C.c_int64)]),
+    "nerf_texture_rows": (_I, [_P, _P, _I64, _P, _I64, _I, _I64, _I64, _P, _P]),
+    "nerf_texture_store": (_I, [_P, _I64, _P, _I64, _I, _I64, _I64, _P, _P]),
+    "nerf_texture_uv": (_I, [_I64, _I, _P, _P]),
+    "nerf_texture_sample": (_I, [_P, _P, _P, _I64, _P, _I64, _I, _P, _P, _I64, _P, _P, _P]),
 }
 
 

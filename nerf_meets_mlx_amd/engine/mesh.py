@@ -26,12 +26,19 @@ section 14).  The reference has no such export; this is Instant-NGP's.
     (mu = 0: plain Laplacian) and recomputes the normals from the faces; the faces and the colours are the input's
     (include/nerf_hip.h "mesh smoothing").  `extract(..., smooth_iterations, smooth_lambda, smooth_mu)`
     runs it between marching cubes and the simplifier.
-  * `write_ply` writes a binary little-endian PLY.
+  * `bake_texture(query, mesh, texels)` bakes a texture atlas for a finished mesh, one field query per texel: a right triangle
+    of `texels` texels a leg per face, two faces to a cell, gutters extrapolated so that bilinear lookups do not bleed
+    (include/nerf_hip.h "texture atlas"); `sample_texture` looks it up at surface samples.  A separate
+    step behind `extract`: the pipeline's keywords are what they were.
+  * `write_ply` writes a binary little-endian PLY; `write_obj` an OBJ with its .mtl and the atlas as a .png, which a PLY cannot
+    carry.
 """
 import ctypes as C
 import math
 import numbers
 import os
+import struct
+import zlib
 from typing import NamedTuple, Optional, Sequence
 
 import numpy as np
@@ -48,6 +55,8 @@ PLACEMENTS = {"mean": 0, "quadric": 1}   # NERF_SIMPLIFY_MEAN / NERF_SIMPLIFY_QU
 SIMPLIFY_MAX_ITEMS = 1 << 24  # vertices, faces
 SIMPLIFY_MAX_CLUSTERS = 1 << 21
 SMOOTH_MAX_ITERATIONS = 1024
+TEXTURE_MAX_TEXELS = 64      # texels per triangle leg
+TEXTURE_MAX_SIDE = 16384     # NERF_TEXTURE_MAX_SIDE
 
 
 class Mesh(NamedTuple):
@@ -413,6 +422,31 @@ def check_simplify_grid(grid) -> int:
     return int(grid)
 
 
+def _check_mesh_tensors(who, mesh):
+    """(V, F) of a Mesh whose tensors are contiguous verts float32 [V, 3], faces int32 [F, 3], normals float32 [V, 3] and colors
+    None or float32 [V, 3] on one device, with V, F <= 2^24; ValueError otherwise (check_simplify_args, check_smooth_args,
+    check_texture_args)."""
+    if not isinstance(mesh, Mesh):
+        raise ValueError(f"{who}: need an engine.mesh.Mesh, got {type(mesh).__name__}")
+
+    def ok(t, dtype, rows=None):
+        return torch.is_tensor(t) and t.dtype == dtype and t.dim() == 2 and t.shape[1] == 3 and t.is_contiguous() \
+            and (rows is None or t.shape[0] == rows) and t.device == mesh.verts.device
+    if not ok(mesh.verts, torch.float32):
+        raise ValueError(f"{who}: verts must be a contiguous float32 [V, 3] tensor")
+    V = mesh.verts.shape[0]
+    if not ok(mesh.faces, torch.int32):
+        raise ValueError(f"{who}: faces must be a contiguous int32 [F, 3] tensor on the vertices' device")
+    if not ok(mesh.normals, torch.float32, V):
+        raise ValueError(f"{who}: normals must be a contiguous float32 [V, 3] tensor on the vertices' device")
+    if mesh.colors is not None and not ok(mesh.colors, torch.float32, V):
+        raise ValueError(f"{who}: colors must be None or a contiguous float32 [V, 3] tensor on the vertices' device")
+    F = mesh.faces.shape[0]
+    if V > SIMPLIFY_MAX_ITEMS or F > SIMPLIFY_MAX_ITEMS:
+        raise ValueError(f"{who}: at most 2^24 vertices and faces, got {V} and {F}")
+    return V, F
+
+
 def check_simplify_args(mesh, grid, lo: Sequence[float], hi: Sequence[float], placement="quadric"):
     """(grid, lo [3], hi [3], placement code) as (int, float lists, int); ValueError for a grid that is not an int in
     [2, MAX_RES], a placement other than "mean" / "quadric", a box with lo >= hi or a non-finite corner, or a mesh whose tensors
@@ -423,24 +457,7 @@ def check_simplify_args(mesh, grid, lo: Sequence[float], hi: Sequence[float], pl
     grid, lo, hi, _ = check_mesh_args(int(grid), lo, hi)
     if not isinstance(placement, str) or placement not in PLACEMENTS:
         raise ValueError(f"simplify placement must be one of {sorted(PLACEMENTS)}, got {placement!r}")
-    if not isinstance(mesh, Mesh):
-        raise ValueError(f"simplify: need an engine.mesh.Mesh, got {type(mesh).__name__}")
-
-    def ok(t, dtype, rows=None):
-        return torch.is_tensor(t) and t.dtype == dtype and t.dim() == 2 and t.shape[1] == 3 and t.is_contiguous() \
-            and (rows is None or t.shape[0] == rows) and t.device == mesh.verts.device
-    if not ok(mesh.verts, torch.float32):
-        raise ValueError("simplify: verts must be a contiguous float32 [V, 3] tensor")
-    V = mesh.verts.shape[0]
-    if not ok(mesh.faces, torch.int32):
-        raise ValueError("simplify: faces must be a contiguous int32 [F, 3] tensor on the vertices' device")
-    if not ok(mesh.normals, torch.float32, V):
-        raise ValueError("simplify: normals must be a contiguous float32 [V, 3] tensor on the vertices' device")
-    if mesh.colors is not None and not ok(mesh.colors, torch.float32, V):
-        raise ValueError("simplify: colors must be None or a contiguous float32 [V, 3] tensor on the vertices' device")
-    F = mesh.faces.shape[0]
-    if V > SIMPLIFY_MAX_ITEMS or F > SIMPLIFY_MAX_ITEMS:
-        raise ValueError(f"simplify: at most 2^24 vertices and faces, got {V} and {F}")
+    V, F = _check_mesh_tensors("simplify", mesh)
     if min(V, grid ** 3) > SIMPLIFY_MAX_CLUSTERS:
         raise ValueError(f"simplify: min(V, grid^3) = {min(V, grid ** 3)} possible clusters exceed 2^21; use a coarser grid")
     return grid, lo, hi, PLACEMENTS[placement]
@@ -517,23 +534,7 @@ def check_smooth_args(mesh, iterations, lo: Sequence[float], hi: Sequence[float]
     if iterations < 1:
         raise ValueError(f"smooth iterations must be an int in [1, {SMOOTH_MAX_ITERATIONS}], got {iterations!r}")
     _, lo, hi, _ = check_mesh_args(2, lo, hi)
-    if not isinstance(mesh, Mesh):
-        raise ValueError(f"smooth: need an engine.mesh.Mesh, got {type(mesh).__name__}")
-
-    def ok(t, dtype, rows=None):
-        return torch.is_tensor(t) and t.dtype == dtype and t.dim() == 2 and t.shape[1] == 3 and t.is_contiguous() \
-            and (rows is None or t.shape[0] == rows) and t.device == mesh.verts.device
-    if not ok(mesh.verts, torch.float32):
-        raise ValueError("smooth: verts must be a contiguous float32 [V, 3] tensor")
-    V = mesh.verts.shape[0]
-    if not ok(mesh.faces, torch.int32):
-        raise ValueError("smooth: faces must be a contiguous int32 [F, 3] tensor on the vertices' device")
-    if not ok(mesh.normals, torch.float32, V):
-        raise ValueError("smooth: normals must be a contiguous float32 [V, 3] tensor on the vertices' device")
-    if mesh.colors is not None and not ok(mesh.colors, torch.float32, V):
-        raise ValueError("smooth: colors must be None or a contiguous float32 [V, 3] tensor on the vertices' device")
-    if V > SIMPLIFY_MAX_ITEMS or mesh.faces.shape[0] > SIMPLIFY_MAX_ITEMS:
-        raise ValueError(f"smooth: at most 2^24 vertices and faces, got {V} and {mesh.faces.shape[0]}")
+    _check_mesh_tensors("smooth", mesh)
     return iterations, lo, hi, lam, mu
 
 
@@ -668,3 +669,199 @@ def read_ply(path: str) -> Mesh:
     if "red" in vert.dtype.names:
         colors = torch.from_numpy(np.stack([vert[k] for k in ("red", "green", "blue")], 1).astype(np.float32) / 255.0)
     return Mesh(verts, torch.from_numpy(face["i"].copy()), normals, colors)
+
+
+class Texture(NamedTuple):
+    image: torch.Tensor                   # [H, W, 3] uint8, row 0 on top
+    uv: torch.Tensor                      # [F, 3, 2] float32, (u, v) per corner, v upwards
+    texels: int                           # T: texels per triangle leg
+
+
+def texture_layout(F: int, texels: int):
+    """(W, H, C, S) of the atlas of F faces at `texels` texels per triangle leg (nerf_texture_layout; no device needed):
+    S = texels + 2 the cell side, C cells per row.  ValueError for F outside [0, 2^24], texels outside [2, TEXTURE_MAX_TEXELS] or
+    an atlas side above TEXTURE_MAX_SIDE (the text names the largest texels that fits)."""
+    out = (C.c_int64 * 4)()
+    N.check(N.lib().nerf_texture_layout(int(F), int(texels), out))
+    return tuple(int(x) for x in out)
+
+
+def check_texture_args(mesh, texels=8):
+    """(texels, (W, H, C, S)) as (int, ints); ValueError for a texels that is a bool, non-integral or outside
+    [2, TEXTURE_MAX_TEXELS], an atlas wider or higher than TEXTURE_MAX_SIDE, or a mesh that check_smooth_args would refuse."""
+    if isinstance(texels, bool) or not isinstance(texels, numbers.Integral) or not 2 <= int(texels) <= TEXTURE_MAX_TEXELS:
+        raise ValueError(f"texture texels must be an int in [2, {TEXTURE_MAX_TEXELS}], got {texels!r}")
+    _, F = _check_mesh_tensors("texture", mesh)
+    return int(texels), texture_layout(F, int(texels))
+
+
+def bake_texture(query, mesh: Mesh, texels: int = 8, chunk: int = CHUNK, mark=None) -> Texture:
+    """The texture atlas of `mesh` (include/nerf_hip.h "texture atlas"): every face gets a right triangle
+    of `texels` texels a leg, two faces to a square cell, and every texel the colour clamp(raw[..., :3], 0, 1) of
+    query(rows, z = 0) -> raw [n, 1, 4] at its point of the face looking along minus the interpolated normal, as the vertex
+    colour query does at the vertices.  `chunk` texels per query (nerf_texture_rows, the query, nerf_texture_store; the image
+    does not depend on it), then nerf_texture_uv once; no host read.  F = 0: a black cell, no query.  The mesh is not changed.
+    mark: _mark's hook ("rows", "query", "store" per chunk, then "uv")."""
+    T, (W, H, _, _) = check_texture_args(mesh, texels)
+    dev, V, F = mesh.verts.device, mesh.verts.shape[0], mesh.faces.shape[0]
+    uv = torch.empty(F, 3, 2, dtype=torch.float32, device=dev)
+    if F == 0:
+        return Texture(torch.zeros(H, W, 3, dtype=torch.uint8, device=dev), uv, T)
+    L = N.lib()
+    image = torch.empty(H, W, 3, dtype=torch.uint8, device=dev)
+    P = W * H
+    chunk = max(1, min(int(chunk), P))
+    rows = torch.empty(chunk, 11, dtype=torch.float32, device=dev)
+    z = torch.zeros(chunk, 1, dtype=torch.float32, device=dev)
+    for p0 in range(0, P, chunk):
+        cnt = min(chunk, P - p0)
+        r = rows[:cnt]
+        _mark(mark, "rows")
+        N.check(L.nerf_texture_rows(N.ptr(mesh.verts), N.ptr(mesh.normals), V, N.ptr(mesh.faces), F, T, p0, cnt, N.ptr(r), N.stream()))
+        _mark(mark, "query")
+        raw = N.f32(query(r, z[:cnt]))
+        if raw.numel() != 4 * cnt:
+            raise ValueError(f"bake_texture: the query must return raw [{cnt}, 1, 4], got shape {tuple(raw.shape)}")
+        raw = raw.reshape(-1, 4)
+        if raw.data_ptr() % 16:
+            raw = raw.clone()
+        _mark(mark, "store")
+        N.check(L.nerf_texture_store(N.ptr(raw), V, N.ptr(mesh.faces), F, T, p0, cnt, N.ptr(image), N.stream()))
+    _mark(mark, "uv")
+    N.check(L.nerf_texture_uv(F, T, N.ptr(uv), N.stream()))
+    return Texture(image, uv, T)
+
+
+def _check_texture(who, texture, mesh):
+    """(texels, layout) of a Texture that belongs to `mesh`: an image of the layout's size and one uv triple per face, on the
+    mesh's device."""
+    if not isinstance(texture, Texture):
+        raise ValueError(f"{who}: need an engine.mesh.Texture, got {type(texture).__name__}")
+    T, lay = check_texture_args(mesh, texture.texels)
+    F, dev = mesh.faces.shape[0], mesh.verts.device
+    im, uv = texture.image, texture.uv
+    if not torch.is_tensor(im) or im.dtype != torch.uint8 or tuple(im.shape) != (lay[1], lay[0], 3) or not im.is_contiguous() \
+            or im.device != dev:
+        raise ValueError(f"{who}: image must be a contiguous uint8 [{lay[1]}, {lay[0]}, 3] tensor on the vertices' device")
+    if not torch.is_tensor(uv) or uv.dtype != torch.float32 or tuple(uv.shape) != (F, 3, 2) or not uv.is_contiguous() \
+            or uv.device != dev:
+        raise ValueError(f"{who}: uv must be a contiguous float32 [{F}, 3, 2] tensor on the vertices' device")
+    return T, lay
+
+
+def sample_texture(texture: Texture, mesh: Mesh, face: torch.Tensor, bary: torch.Tensor, rows: bool = False):
+    """rgb float32 [n, 3]: the bilinear lookup of the atlas at the surface samples (face [n] int32, bary [n, 2] float32 =
+    the weights (wb, wc) of the face's second and third corner, clamped into the triangle); a face outside [0, F) reads black.
+    With `rows` also the query rows [n, 11] of the very points, as bake_texture asks them (nerf_texture_sample)."""
+    T, _ = _check_texture("sample_texture", texture, mesh)
+    dev = mesh.verts.device
+    if not torch.is_tensor(face) or face.dtype != torch.int32 or face.dim() != 1 or not face.is_contiguous() or face.device != dev:
+        raise ValueError("sample_texture: face must be a contiguous int32 [n] tensor on the vertices' device")
+    n = face.shape[0]
+    if not torch.is_tensor(bary) or bary.dtype != torch.float32 or tuple(bary.shape) != (n, 2) or not bary.is_contiguous() \
+            or bary.device != dev:
+        raise ValueError(f"sample_texture: bary must be a contiguous float32 [{n}, 2] tensor on the vertices' device")
+    rgb = torch.empty(n, 3, dtype=torch.float32, device=dev)
+    out = torch.empty(n, 11, dtype=torch.float32, device=dev) if rows else None
+    if n:
+        N.check(N.lib().nerf_texture_sample(N.ptr(texture.image), N.ptr(mesh.verts), N.ptr(mesh.normals), mesh.verts.shape[0],
+                                            N.ptr(mesh.faces), mesh.faces.shape[0], T, N.ptr(face), N.ptr(bary), n, N.ptr(rgb),
+                                            N.ptr(out), N.stream()))
+    return (rgb, out) if rows else rgb
+
+
+def _replace_file(path: str, data: bytes):
+    tmp = path + ".tmp"
+    with open(tmp, "wb") as fh:
+        fh.write(data)
+    os.replace(tmp, path)
+
+
+def _png_chunk(kind: bytes, data: bytes) -> bytes:
+    return struct.pack(">I", len(data)) + kind + data + struct.pack(">I", zlib.crc32(kind + data))
+
+
+_PNG_MAGIC = b"\x89PNG\r\n\x1a\n"
+
+
+def png_bytes(image: np.ndarray) -> bytes:
+    """An 8-bit RGB PNG of a uint8 [H, W, 3] array, every row with filter type 0 (zlib and struct alone)."""
+    H, W, _ = image.shape
+    lines = np.zeros((H, 1 + 3 * W), np.uint8)
+    lines[:, 1:] = image.reshape(H, 3 * W)
+    return _PNG_MAGIC + _png_chunk(b"IHDR", struct.pack(">IIBBBBB", W, H, 8, 2, 0, 0, 0)) \
+        + _png_chunk(b"IDAT", zlib.compress(lines.tobytes(), 6)) + _png_chunk(b"IEND", b"")
+
+
+def png_array(data: bytes) -> np.ndarray:
+    """The inverse of png_bytes: uint8 [H, W, 3]; ValueError for anything but 8-bit RGB with filter type 0 throughout."""
+    if data[:8] != _PNG_MAGIC:
+        raise ValueError("not a PNG")
+    pos, head, idat = 8, None, b""
+    while pos < len(data):
+        n, kind = struct.unpack(">I4s", data[pos:pos + 8])
+        body = data[pos + 8:pos + 8 + n]
+        if struct.unpack(">I", data[pos + 8 + n:pos + 12 + n])[0] != zlib.crc32(kind + body):
+            raise ValueError("PNG: bad chunk checksum")
+        if kind == b"IHDR":
+            head = struct.unpack(">IIBBBBB", body)
+        elif kind == b"IDAT":
+            idat += body
+        pos += 12 + n
+    if head is None or head[2:] != (8, 2, 0, 0, 0):
+        raise ValueError("PNG: only 8-bit RGB without interlace")
+    W, H = head[:2]
+    lines = np.frombuffer(zlib.decompress(idat), np.uint8).reshape(H, 1 + 3 * W)
+    if lines[:, 0].any():
+        raise ValueError("PNG: only filter type 0")
+    return lines[:, 1:].reshape(H, W, 3).copy()
+
+
+def write_obj(path: str, mesh: Mesh, texture: Texture) -> str:
+    """Wavefront OBJ with its material and texture: `path` (v, vn, one vt per face corner, `f a/t/a b/t/b c/t/c`, 1-based; floats
+    with nine significant digits, which float32 survives), beside it the same name with the suffix .mtl (one material whose
+    map_Kd names the image) and with .png (8-bit RGB, png_bytes).  Vertex colours are not written.  Each file is written under
+    a temporary name, then renamed."""
+    _check_texture("write_obj", texture, mesh)
+    stem = os.path.splitext(path)[0]
+    v = mesh.verts.detach().cpu().numpy().astype(np.float64)
+    n = mesh.normals.detach().cpu().numpy().astype(np.float64)
+    f = mesh.faces.detach().cpu().numpy().astype(np.int64) + 1
+    uv = texture.uv.detach().cpu().numpy().astype(np.float64).reshape(-1, 2)
+    out = [f"# texels {texture.texels}", f"mtllib {os.path.basename(stem)}.mtl", "usemtl atlas"]
+    out += ["v %.9g %.9g %.9g" % tuple(r) for r in v]
+    out += ["vn %.9g %.9g %.9g" % tuple(r) for r in n]
+    out += ["vt %.9g %.9g" % tuple(r) for r in uv]
+    out += ["f %d/%d/%d %d/%d/%d %d/%d/%d" % (a, 3 * k + 1, a, b, 3 * k + 2, b, c, 3 * k + 3, c) for k, (a, b, c) in enumerate(f)]
+    _replace_file(stem + ".png", png_bytes(texture.image.detach().cpu().numpy()))
+    _replace_file(stem + ".mtl", f"newmtl atlas\nKd 1 1 1\nmap_Kd {os.path.basename(stem)}.png\n".encode("ascii"))
+    _replace_file(path, ("\n".join(out) + "\n").encode("ascii"))
+    return path
+
+
+def read_obj(path: str):
+    """The inverse of write_obj: (Mesh without colours, Texture) as CPU tensors; only the layout write_obj produces."""
+    with open(path) as fh:
+        lines = [ln.split() for ln in fh]
+    if not lines or lines[0][:2] != ["#", "texels"]:
+        raise ValueError(f"{path}: not an OBJ of write_obj")
+    T = int(lines[0][2])
+    by = {k: [w[1:] for w in lines if w and w[0] == k] for k in ("v", "vn", "vt", "f", "mtllib")}
+    verts = torch.tensor(np.array(by["v"], np.float64).reshape(-1, 3), dtype=torch.float32)
+    normals = torch.tensor(np.array(by["vn"], np.float64).reshape(-1, 3), dtype=torch.float32)
+    uv = torch.tensor(np.array(by["vt"], np.float64).reshape(-1, 3, 2), dtype=torch.float32)
+    corners = np.array([[c.split("/") for c in w] for w in by["f"]], np.int64).reshape(-1, 3, 3)
+    F = len(corners)
+    if len(by["mtllib"]) != 1 or uv.shape[0] != F or normals.shape != verts.shape \
+            or not np.array_equal(corners[:, :, 1].reshape(-1), np.arange(1, 3 * F + 1)) \
+            or not np.array_equal(corners[:, :, 0], corners[:, :, 2]):
+        raise ValueError(f"{path}: unexpected OBJ layout")
+    here = os.path.dirname(path)
+    with open(os.path.join(here, by["mtllib"][0][0])) as fh:
+        maps = [ln.split()[1] for ln in fh if ln.startswith("map_Kd ")]
+    if len(maps) != 1:
+        raise ValueError(f"{path}: the material needs one map_Kd")
+    with open(os.path.join(here, maps[0]), "rb") as fh:
+        image = torch.from_numpy(png_array(fh.read()))
+    faces = torch.from_numpy((corners[:, :, 0] - 1).astype(np.int32))
+    return Mesh(verts, faces, normals), Texture(image, uv, T)

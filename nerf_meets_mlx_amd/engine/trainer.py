@@ -245,6 +245,14 @@ class Trainer:
                             simplify_grid=simplify_grid, simplify_placement=simplify_placement,
                             smooth_iterations=smooth_iterations, smooth_lambda=smooth_lambda, smooth_mu=smooth_mu)
 
+    def texture_mesh(self, mesh, texels: int = 8):
+        """engine.mesh.Texture of a finished engine.mesh.Mesh (extract_mesh's, simplified or not): an atlas with a right triangle
+        of `texels` texels a leg per face, every texel the field's colour at its point of the face looking along minus the
+        interpolated normal (engine.mesh.bake_texture); engine.mesh.write_obj writes both.  Runs on this
+        rank only: no collective."""
+        from .mesh import bake_texture
+        return bake_texture(self._mesh_field()[0], mesh, texels)
+
     # ---------------------------------------------------------------- checkpoint (SURVEY 8f-3)
     def _checkpoint_buffers(self):
         """name -> object with `.params` (flat fp32 device buffer) and `.load_flat(t)`; the names are also the Adam keys."""

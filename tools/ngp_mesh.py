@@ -36,6 +36,12 @@ section 30; --smooth-lambda, --smooth-mu, mu 0 for plain Laplacian) -- the devic
 of the normals, V and F, the geometry figures, the enclosed volume and the roughness (the mean distance of a vertex from the mean
 of its neighbours) before and after; and with --simplify the simplifier's lines for the smoothed mesh (source "density smooth N").
 
+With --texture T (repeatable), one more line per T for the density mesh at --ply-res and for each --simplify arm of it (quadric
+placement): the texture atlas of DESIGN.md section 31 -- W x H and the share of used texels, the device ms of the rows, query,
+store and uv stages (summed over the chunks) beside the vertex colour query of the same mesh, the OBJ / MTL / PNG written next to
+the PLY and read back, and the fidelity of 2^20 area-weighted random surface samples, each queried directly from the field
+through the sampler's rows: RMS error and PSNR of the texture lookup and of the barycentric interpolation of the vertex colours.
+
     rocprofv3 --kernel-trace --output-format csv -d DIR -o mesh -- python tools/ngp_mesh.py --ckpt /tmp/ngp.npz --reps 1 --no-ply
     python tools/ngp_mesh.py --stats DIR/.../mesh_kernel_trace.csv --from profiles/ngp_mesh.jsonl --out profiles/ngp_mesh_kernels.jsonl
 
@@ -119,6 +125,14 @@ class _Stages:
     def ms(self):
         torch.cuda.synchronize()
         return {n: e0.elapsed_time(e1) for n, e0, e1 in zip(self.names, self.events, self.events[1:])}
+
+    def total_ms(self):
+        """ms() with the times of a stage that is marked more than once (bake_texture: once per chunk) added up."""
+        torch.cuda.synchronize()
+        out = {}
+        for n, e0, e1 in zip(self.names, self.events, self.events[1:]):
+            out[n] = out.get(n, 0.0) + e0.elapsed_time(e1)
+        return out
 
 
 def _components_timed(vol, iso, min_component, largest_only):
@@ -248,6 +262,81 @@ def _smooth_arms(m, source, R, lo, hi, a, rec, bound, boxes):
     return out
 
 
+def _psnr(err):
+    mse = float((err.double() ** 2).mean())
+    return {"rms": mse ** 0.5, "psnr_db": (10.0 * np.log10(1.0 / mse) if mse > 0 else None)}
+
+
+def _texture_fidelity(query, m, tex, n=1 << 20, seed=0):
+    """RMS error and PSNR against the field, queried at n area-weighted random surface points through the sampler's own rows, of
+    the bilinear texture lookup and of the barycentric interpolation of the vertex colours m.colors."""
+    from nerf_meets_mlx_amd.engine import mesh
+    g = torch.Generator(device=m.verts.device).manual_seed(seed)
+    f = m.faces.long()
+    a, b, c = m.verts[f[:, 0]].double(), m.verts[f[:, 1]].double(), m.verts[f[:, 2]].double()
+    area = torch.linalg.cross(b - a, c - a).norm(dim=1)
+    face = torch.multinomial(area / area.sum(), n, replacement=True, generator=g)
+    r = torch.rand(n, 2, device=m.verts.device, generator=g)
+    fold = r.sum(1) > 1.0                                             # uniform over the triangle: mirror the upper half of the square
+    r = torch.where(fold[:, None], 1.0 - r, r).float().contiguous()
+    rgb, rows = mesh.sample_texture(tex, m, face.int().contiguous(), r, rows=True)
+    truth = mesh.vertex_colors(query, rows)
+    wb, wc = r[:, :1], r[:, 1:]
+    col = m.colors
+    lerp = ((1.0 - wb) - wc) * col[f[face, 0]] + wb * col[f[face, 1]] + wc * col[f[face, 2]]
+    return {"samples": n, "texture": _psnr(rgb - truth), "vertex_colors": _psnr(lerp - truth)}
+
+
+def _texture_arms(query, m, source, R, a, rec, out_dir):
+    """One JSON line per --texture T for the coloured mesh `m`."""
+    from nerf_meets_mlx_amd.engine import mesh
+    out = []
+    if m.faces.shape[0] == 0:
+        return out
+    V, F = int(m.verts.shape[0]), int(m.faces.shape[0])
+    rows = torch.zeros(V, 11, dtype=torch.float32, device=m.verts.device)
+    rows[:, 0:3], rows[:, 3:6], rows[:, 8:11] = m.verts, -m.normals, -m.normals
+    t_col = []
+    for _ in range(a.reps + 1):                                           # (the first run warms)
+        ev = _events()
+        ev[0].record()
+        mesh.vertex_colors(query, rows)
+        ev[1].record()
+        torch.cuda.synchronize()
+        t_col.append(ev[0].elapsed_time(ev[1]))
+    for T in a.texture or []:
+        W, H, C, S = mesh.texture_layout(F, T)
+        mesh.bake_texture(query, m, T)                                    # warm
+        ts = []
+        for _ in range(a.reps):
+            st = _Stages()
+            tex = mesh.bake_texture(query, m, T, mark=st)
+            st("end")
+            t = st.total_ms()
+            ts.append([t["rows"], t["query"], t["store"], t["uv"]])
+        t = np.mean(np.array(ts), 0)
+        used = (F + 1) // 2 * (S * (S + 1) // 2) + F // 2 * (S * (S - 1) // 2)      # even faces own the cell's diagonal
+        arm = {"tool": "ngp_mesh texture", "source": source, "R": R, "texels": T, "iters": rec["iters"], "seed": rec["seed"],
+               "V": V, "F": F, "W": W, "H": H, "cells_per_row": C, "image_MB": W * H * 3 / 1e6, "used_texels": used / (W * H),
+               "chunks": -(-W * H // mesh.CHUNK), "bake_ms": float(t.sum()), "rows_ms": float(t[0]), "query_ms": float(t[1]),
+               "store_ms": float(t[2]), "uv_ms": float(t[3]),
+               "bake_ms_range": [float(np.sum(x)) for x in (min(ts, key=sum), max(ts, key=sum))],
+               "vertex_colors_ms": float(np.mean(t_col[1:])), "fidelity": _texture_fidelity(query, m, tex),
+               "device": rec["device"]}
+        if not a.no_ply:
+            path = os.path.join(out_dir, f"mesh_{source.replace(' ', '_')}_R{R}_T{T}.obj")
+            mesh.write_obj(path, m, tex)
+            bm, bt = mesh.read_obj(path)
+            arm.update({"obj_bytes": os.path.getsize(path), "png_bytes": os.path.getsize(path[:-4] + ".png"),
+                        "obj_matches": bool(torch.equal(bm.verts, m.verts.cpu()) and torch.equal(bm.faces, m.faces.cpu())
+                                            and torch.equal(bt.image, tex.image.cpu()) and torch.equal(bt.uv, tex.uv.cpu()))})
+        print(json.dumps(arm), flush=True)
+        out.append(arm)
+        del tex
+    torch.cuda.empty_cache()
+    return out
+
+
 def _tsdf_arm(tr, mesh, R, lo, hi, a, rec, bound, boxes):
     """The TSDF export of the same field as its stages, each between device events (the last of --reps runs is kept)."""
     poses = tr.poses if a.tsdf_views is None else tr.poses[:a.tsdf_views]
@@ -342,6 +431,9 @@ def parser():
     ap.add_argument("--smooth", type=int, action="append", default=None,
                     help="also smooth the density mesh by this many Taubin pairs (DESIGN.md section 30); repeatable: one JSON "
                          "line per value and R, and with --simplify the simplifier's lines for the smoothed mesh")
+    ap.add_argument("--texture", type=int, action="append", default=None, metavar="T",
+                    help="also bake a texture atlas with T texels per triangle leg for the density mesh at --ply-res and each "
+                         "--simplify arm of it (DESIGN.md section 31); repeatable: one JSON line per value and mesh")
     ap.add_argument("--smooth-lambda", type=float, default=0.5)
     ap.add_argument("--smooth-mu", type=float, default=-0.53, help="0: plain Laplacian smoothing")
     ap.add_argument("--ckpt", default=None, help="load this checkpoint instead of training")
@@ -422,6 +514,14 @@ def main():
                 rec.update(_ply_check(m, os.path.join(d, "mesh.ply")))
         print(json.dumps(rec), flush=True)
         lines.append(rec)
+        if a.texture and R == a.ply_res:
+            with tempfile.TemporaryDirectory() as d:
+                lines += _texture_arms(query, m, "density", R, a, rec, d)
+                for G in a.simplify or []:
+                    sm, srows, _ = mesh._simplify(m._replace(colors=None), G, lo, hi, "quadric", True)
+                    sm = sm._replace(colors=mesh.vertex_colors(query, srows))
+                    lines += _texture_arms(query, sm, f"density simplify {G}", R, a, rec, d)
+                    del sm, srows
         lines += _simplify_arms(m._replace(colors=None), "density", R, lo, hi, a, rec, bound, boxes)
         lines += _smooth_arms(m._replace(colors=None), "density", R, lo, hi, a, rec, bound, boxes)
         del vol, m, rows, col
@@ -524,6 +624,12 @@ def _bytes(kernel, R, V, F):
             "tsdf_integrate_kernel": 18 * n3, "tsdf_volume_kernel": 13 * n3, "tsdf_reset_kernel": 9 * n3}.get(kernel)
 
 
+def _texture_bytes(kernel, items):
+    """Algorithmic HBM bytes of one csrc/texture.hip launch over `items` atlas texels (rows, store), faces (uv) or samples with
+    rows (sample): what is written, and what is streamed in; the gathered corners and texels are cache hits."""
+    return {"tex_rows_kernel": 44, "tex_store_kernel": 16 + 3, "tex_uv_kernel": 24, "tex_sample_kernel": 12 + 12 + 44}[kernel] * items
+
+
 def _morph_grid(kernel, R):
     """Work-items of a csrc/morph.hip launch at lattice size R."""
     words = -(-R // 64) * R * R
@@ -552,9 +658,9 @@ def stats(a):
     name_k = col.get("kernel_name")
     s_k, e_k = col.get("start_timestamp"), col.get("end_timestamp")
     gx = col.get("grid_size_x", col.get("grid_size"))
-    groups = {}
+    groups, tex_items = {}, {}
     for r in rows:
-        m = re.search(r"(mesh_\w+_kernel|ccl_\w+_kernel|morph_\w+_kernel|tsdf_\w+_kernel|simp_\w+_kernel|smooth_\w+_kernel|occ_cull_scan_kernel|occ_merge_exp_kernel)", r[name_k])
+        m = re.search(r"(mesh_\w+_kernel|ccl_\w+_kernel|morph_\w+_kernel|tsdf_\w+_kernel|simp_\w+_kernel|smooth_\w+_kernel|tex_\w+_kernel|occ_cull_scan_kernel|occ_merge_exp_kernel)", r[name_k])
         if not m:
             continue
         k = m.group(1)
@@ -565,9 +671,11 @@ def stats(a):
             R = next((R for R in runs if _morph_grid(k, R) == grid), None)
             groups.setdefault((k, R), []).append((int(r[e_k]) - int(r[s_k])) * 1e-3)
             continue
+        if k.startswith("tex_"):                       # chunked: pooled per kernel; one lane per texel, face or sample
+            tex_items.setdefault(k, []).append(grid)
         if k.startswith(("simp_", "smooth_")):         # sized by the mesh: one lane per vertex or face of the run at R; else pooled
             R = next((R for R, run in runs.items() if grid in (-(-run["V"] // BLOCK) * BLOCK, -(-run["F"] // BLOCK) * BLOCK)), None)
-        elif k in ("mesh_points_kernel", "occ_merge_exp_kernel", "occ_cull_scan_kernel", "ccl_finish_kernel"):
+        elif k.startswith("tex_") or k in ("mesh_points_kernel", "occ_merge_exp_kernel", "occ_cull_scan_kernel", "ccl_finish_kernel"):
             R = None                                                       # chunked / one workgroup: pooled per kernel
         else:
             R = next((R for R in runs if -(-R ** 3 // BLOCK) * BLOCK == grid), None)
@@ -580,12 +688,16 @@ def stats(a):
                "avg_us": round(float(np.mean(us)), 2), "median_us": round(float(np.median(us)), 2)}
         if k == "tsdf_integrate_kernel" and R in tsdf_runs:
             rec.update({"views": tsdf_runs[R]["views"], "hw": tsdf_runs[R]["hw"]})
-        if R is not None and R in runs:
+        b = None
+        if k in tex_items:
+            rec["items"] = int(np.median(tex_items[k]))
+            b = _texture_bytes(k, rec["items"])
+        elif R is not None and R in runs:
             b = _bytes(k, R, runs[R]["V"], runs[R]["F"])
-            if b:
-                bw = b / (float(np.median(us)) * 1e-6)
-                rec.update({"bytes": b, "TBps": round(bw / 1e12, 3), "frac_hbm_spec": round(bw / HBM_SPEC, 3),
-                            "frac_hbm_measured": round(bw / HBM_MEASURED, 3)})
+        if b:
+            bw = b / (float(np.median(us)) * 1e-6)
+            rec.update({"bytes": b, "TBps": round(bw / 1e12, 3), "frac_hbm_spec": round(bw / HBM_SPEC, 3),
+                        "frac_hbm_measured": round(bw / HBM_MEASURED, 3)})
         out.append(rec)
         print(json.dumps(rec))
     if a.out:
