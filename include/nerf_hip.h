@@ -918,6 +918,75 @@ int nerf_texture_uv(int64_t F, int texels, float* uv, void* stream);
 int nerf_texture_sample(const uint8_t* image, const float* verts, const float* normals, int64_t V, const int32_t* faces, int64_t F,
                         int texels, const int32_t* sample_face, const float* bary, int64_t n, float* rgb, float* rows, void* stream);
 
+/* ---------------------------------------------------------------- mesh rendering (no reference counterpart)
+ * A visibility-buffer rasteriser: what a posed pinhole camera sees of a finished mesh, so that an exported mesh can be compared
+ * in image space with the held-out frame and with the field's own render.  Additive: NERF_ABI_VERSION stays 3.  Float steps are
+ * IEEE float32, one rounding per operation (no contraction), in exactly the order and grouping written here, a / b correctly
+ * rounded; integer steps are exact.  csrc/raster.h states the rule in code; tests/_raster_ref.py reproduces every output bit for
+ * bit.
+ *   input     verts [V, 3] float32, faces [F, 3] int32, 0 <= V, F <= 2^24; image 1 <= H, W <= 16384; near finite and > 0; the
+ *             camera a nerf_tsdf_view on the host (16 finite floats: c2w [3, 4] row-major, fx, fy, cx, cy).
+ *   camera    per vertex p, as nerf_tsdf_integrate and nerf_ray_gen: q_a = p_a - t_a; x_c = (r00 q0 + r10 q1) + r20 q2, y_c with
+ *             column 1, z_w with column 2; zc = 0.0f - z_w; u = fx (x_c / zc) + cx; v = cy - fy (y_c / zc).  Pixel (px, py), py
+ *             the image row, has its centre at (u, v) = (px, py): the ray nerf_ray_gen shoots.  Depth is zc, the distance along
+ *             the optical axis (what depth / acc of a renderer's aux maps means).
+ *   snap      X = (int)rintf(u * 256.0f), Y = (int)rintf(v * 256.0f): screen coordinates in 1 / 256 pixel.
+ *   dropped   a face is dropped and counted, never clipped: an index outside [0, V) or a non-finite vertex coordinate ("other";
+ *             nothing is read through a bad index); else a vertex with !(near <= zc < inf), or with !(|u| <= 2^20) or
+ *             !(|v| <= 2^20), the guard band, compared as floats before the cast ("depth or guard band"); else D = 0, or D > 0
+ *             with cull_backfaces ("other"), where D = (Xb - Xa)(Yc - Ya) - (Yb - Ya)(Xc - Xa) in int64.  v grows downwards, so
+ *             a face that is counter-clockwise seen from the camera, a front face of "mesh extraction", has D < 0.  The guard
+ *             band keeps |X|, |Y| <= 2^28: a coordinate difference is below 2^30, a product of two below 2^59, D and every edge
+ *             function below 2^60.
+ *   coverage  s = sign(D), S = s D > 0.  E(U, V; P) = (Vx - Ux)(Py - Uy) - (Vy - Uy)(Px - Ux) at P = (256 px, 256 py);
+ *             Ea = s E(B, C; P), Eb = s E(C, A; P), Ec = s E(A, B; P); Ea + Eb + Ec = S exactly.  Pixel (px, py) is covered iff
+ *             Ea >= 0, Eb >= 0 and Ec >= 0 (inclusive).  E(U, V; P) = -E(V, U; P) exactly, so a pixel centre on an edge shared
+ *             by two faces belongs to both and a closed surface has no cracks; the key decides between them.
+ *   pixel     per covered pixel and face: qa = (float)Ea / za, qb = (float)Eb / zb, qc = (float)Ec / zc (int64 -> float32
+ *             rounds to nearest even); Q = (qa + qb) + qc; wb = qb / Q; wc = qc / Q; z = (float)S / Q.  Perspective-correct:
+ *             1 / z is the screen-space interpolation of 1 / zc.
+ *   key       ((uint64)bits(z) << 32) | (uint32)(face_base + face index), one 64-bit atomicMin per covered pixel on keys
+ *             uint64 [H W], pixel index px + W py.  A cleared pixel holds all ones.  z > 0, so its bits order like its value; of
+ *             equal depths the lower face id wins.  A minimum does not depend on the order of its operands: the buffer is
+ *             bit-reproducible and independent of face order, launch shape, small_max and of how a mesh is cut into draws.
+ *             No float atomics.
+ *   stats     uint64 [4]: faces drawn (not dropped, whether or not they cover a pixel), faces dropped for depth or guard band,
+ *             faces dropped for another reason, key updates attempted = covered (pixel, face) pairs.
+ *   resolve   per pixel: empty (key all ones): face -1, bary (0, 0), depth 0, acc 0.  Otherwise the winner's setup and `pixel`
+ *             again, which gives the bits of the draw: face int32 = the id, bary float32 (wb, wc), the pair nerf_texture_sample
+ *             takes, depth = z, acc = 1.  depth and acc are a renderer's aux maps of an opaque surface (depth / acc = zc):
+ *             nerf_tsdf_integrate takes them unchanged.  An id outside [0, F) or a winner the setup refuses reads as empty.
+ *   shade     per pixel with face >= 0: rgb_in's pixel if rgb_in is given (what the caller looked up, e.g. nerf_texture_sample
+ *             at (face, bary)); else with wa = (1 - wb) - wc per channel (wa ca + wb cb) + wc cc of the vertex colours [V, 3]
+ *             (a face outside [0, F) or with an index outside [0, V): the background).  face < 0: the background, one colour
+ *             [3] or, with per_pixel, [H W, 3] (device memory).
+ * Calls:
+ *   nerf_raster_clear      keys to all ones and stats to 0, one lane per pixel.
+ *   nerf_raster_draw       faces [F, 3] with ids face_base + f (0 <= face_base <= 2^24 - F) into keys; adds to stats.  It does
+ *                          not clear: several meshes or chunks of faces share a buffer.  One lane per face does the setup and
+ *                          the bounding box of the snapped corners clipped to the image, the pixels with X_min <= 256 px <= X_max
+ *                          and Y_min <= 256 py <= Y_max inside [0, W) x [0, H).  A face whose box has at most small_max
+ *                          pixels (0 <= small_max <= 2^30) is walked by its own lane; the others one after another by the
+ *                          whole wave.  0: every face by the wave; 2^30: every face by its lane.  The keys and the stats do
+ *                          not depend on it.  NERF_RASTER_SMALL_MAX is the measured default.  F = 0 launches nothing.
+ *   nerf_raster_resolve    face [H W] int32, bary [H W, 2], depth [H W], acc [H W] from keys; faces is the whole array the ids
+ *                          index.
+ *   nerf_raster_shade      rgb [H W, 3]; exactly one of colors and rgb_in is not NULL.
+ * Out of range: NERF_E_SHAPE; NULL: NERF_E_NULL; all argument checks run before any device work; nothing is read on the host.
+ * Not done: no near-plane clipping (a face with a vertex in front of `near` is dropped: the project's cameras stand outside
+ * the scene box), no antialiasing or supersampling (one sample at the pixel centre, like one ray per pixel), no mipmapped
+ * texture lookups, no tile binning for screen-filling faces, no transparency.                                                   */
+#define NERF_RASTER_SMALL_MAX 16
+int nerf_raster_clear(uint64_t* keys, int H, int W, uint64_t* stats, void* stream);
+int nerf_raster_draw(const float* verts, int64_t V, const int32_t* faces, int64_t F, int64_t face_base,
+                     const nerf_tsdf_view* view_host, int H, int W, float near, int cull_backfaces, int small_max, uint64_t* keys,
+                     uint64_t* stats, void* stream);
+int nerf_raster_resolve(const uint64_t* keys, const float* verts, int64_t V, const int32_t* faces, int64_t F,
+                        const nerf_tsdf_view* view_host, int H, int W, float near, int32_t* face, float* bary, float* depth,
+                        float* acc, void* stream);
+int nerf_raster_shade(const int32_t* face, const float* bary, const int32_t* faces, int64_t V, int64_t F, const float* colors,
+                      const float* rgb_in, const float* background, int per_pixel, int H, int W, float* rgb, void* stream);
+
 /* ---------------------------------------------------------------- fused renderer (a14 / a18)
  * replaces: rendering/render.py:164-241 render_rays_eval (coarse pass, importance sampling, sort, second pass)
  * as ONE call that enqueues the fixed kernel sequence on `stream`: nerf_sample_coarse -> nerf_query_fused ->

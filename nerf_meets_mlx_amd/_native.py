@@ -125,6 +125,10 @@ SIGNATURES = {
     "nerf_texture_store": (_I, [_P, _I64, _P, _I64, _I, _I64, _I64, _P, _P]),
     "nerf_texture_uv": (_I, [_I64, _I, _P, _P]),
     "nerf_texture_sample": (_I, [_P, _P, _P, _I64, _P, _I64, _I, _P, _P, _I64, _P, _P, _P]),
+    "nerf_raster_clear": (_I, [_P, _I, _I, _P, _P]),
+    "nerf_raster_draw": (_I, [_P, _I64, _P, _I64, _I64, C.POINTER(C.c_float), _I, _I, _F, _I, _I, _P, _P, _P]),
+    "nerf_raster_resolve": (_I, [_P, _P, _I64, _P, _I64, C.POINTER(C.c_float), _I, _I, _F, _P, _P, _P, _P, _P]),
+    "nerf_raster_shade": (_I, [_P, _P, _P, _I64, _I64, _P, _P, _P, _I, _I, _I, _P, _P]),
 }
 
 

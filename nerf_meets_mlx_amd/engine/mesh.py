@@ -30,6 +30,10 @@ section 14).  The reference has no such export; this is Instant-NGP's.
     of `texels` texels a leg per face, two faces to a cell, gutters extrapolated so that bilinear lookups do not bleed
     (include/nerf_hip.h "texture atlas"); `sample_texture` looks it up at surface samples.  A separate
     step behind `extract`: the pipeline's keywords are what they were.
+  * `rasterize(mesh, c2w, K, H, W)` finds the face every pixel centre of a posed pinhole camera sees, its barycentrics and its
+    depth, by exact integer coverage and one 64-bit atomicMin per covered pixel; `render_mesh` shades that with the vertex
+    colours or through `sample_texture` into a `MeshFrame` (include/nerf_hip.h "mesh rendering"), so a
+    mesh can be compared with the held-out frame and with the field's render in image space (`Trainer.mesh_psnr`).
   * `write_ply` writes a binary little-endian PLY; `write_obj` an OBJ with its .mtl and the atlas as a .png, which a PLY cannot
     carry.
 """
@@ -57,6 +61,9 @@ SIMPLIFY_MAX_CLUSTERS = 1 << 21
 SMOOTH_MAX_ITERATIONS = 1024
 TEXTURE_MAX_TEXELS = 64      # texels per triangle leg
 TEXTURE_MAX_SIDE = 16384     # NERF_TEXTURE_MAX_SIDE
+RASTER_MAX_SIDE = 16384      # image height and width of the mesh renderer
+RASTER_SMALL_MAX = 16        # NERF_RASTER_SMALL_MAX
+RASTER_NEAR = 0.01           # the mesh renderer's default near plane
 
 
 class Mesh(NamedTuple):
@@ -768,6 +775,114 @@ def sample_texture(texture: Texture, mesh: Mesh, face: torch.Tensor, bary: torch
                                             N.ptr(mesh.faces), mesh.faces.shape[0], T, N.ptr(face), N.ptr(bary), n, N.ptr(rgb),
                                             N.ptr(out), N.stream()))
     return (rgb, out) if rows else rgb
+
+
+class MeshFrame(NamedTuple):
+    rgb: torch.Tensor                     # [H, W, 3] float32
+    depth: torch.Tensor                   # [H, W] float32: distance along the optical axis, 0 where empty
+    acc: torch.Tensor                     # [H, W] float32: 1 where a face is seen, else 0
+    face: torch.Tensor                    # [H, W] int32: the face seen, -1 where empty
+    bary: torch.Tensor                    # [H, W, 2] float32: (wb, wc) on that face, as sample_texture takes them
+
+
+def check_raster_args(H=1, W=1, near=RASTER_NEAR, cull_backfaces=False, small_max=RASTER_SMALL_MAX):
+    """(H, W, near, cull_backfaces, small_max) as (int, int, float, bool, int); ValueError for an H or W that is not an int in
+    [1, RASTER_MAX_SIDE], a near that is not a finite number > 0 (as a float32), a cull_backfaces that is not a bool or a
+    small_max that is not an int in [0, 2^30]."""
+    for name, x in (("H", H), ("W", W)):
+        if isinstance(x, bool) or not isinstance(x, numbers.Integral) or not 1 <= int(x) <= RASTER_MAX_SIDE:
+            raise ValueError(f"raster {name} must be an int in [1, {RASTER_MAX_SIDE}], got {x!r}")
+    if isinstance(near, bool) or not isinstance(near, numbers.Real) or not math.isfinite(float(near)) \
+            or not 0.0 < float(np.float32(near)) < math.inf:
+        raise ValueError(f"raster near must be a finite number > 0, got {near!r}")
+    if not isinstance(cull_backfaces, bool):
+        raise ValueError(f"raster cull_backfaces must be a bool, got {cull_backfaces!r}")
+    if isinstance(small_max, bool) or not isinstance(small_max, numbers.Integral) or not 0 <= int(small_max) <= 1 << 30:
+        raise ValueError(f"raster small_max must be an int in [0, 2^30], got {small_max!r}")
+    return int(H), int(W), float(near), cull_backfaces, int(small_max)
+
+
+def _raster_view(c2w, K):
+    views = tsdf_views(c2w, K)
+    if views.shape[0] != 1:
+        raise ValueError(f"raster: need one camera, got a stack of {views.shape[0]}")
+    return np.ascontiguousarray(views[0]).ctypes.data_as(C.POINTER(C.c_float)), views
+
+
+def rasterize(mesh: Mesh, c2w, K, H: int, W: int, near: float = RASTER_NEAR, cull_backfaces: bool = False, mark=None,
+              small_max: int = RASTER_SMALL_MAX):
+    """(face [H, W] int32, bary [H, W, 2], depth [H, W], acc [H, W] float32, stats [4] int64) of `mesh` seen by the pinhole
+    camera (c2w [3, 4] or [4, 4], K [3, 3], as tsdf_views takes them) whose pixel centres are the rays of gen_rays
+    (include/nerf_hip.h "mesh rendering"): the nearest face at every pixel centre, the weights of its
+    second and third corner there, the distance along the optical axis, and 1 where a face is seen.  depth and acc go into
+    TSDFVolume.integrate unchanged.  Faces with a vertex in front of `near` are dropped, not clipped.  stats (on the device):
+    faces drawn, dropped for depth or guard band, dropped otherwise, key updates.  small_max: the largest bounding box, in
+    pixels, that one lane walks; the result does not depend on it.  nerf_raster_clear, _draw, _resolve; no host read.  F = 0:
+    nothing is launched.  mark: _mark's hook ("clear", "draw", "resolve")."""
+    _check_mesh_tensors("rasterize", mesh)
+    H, W, near, cull, small_max = check_raster_args(H, W, near, cull_backfaces, small_max)
+    view, _keep = _raster_view(c2w, K)
+    dev, V, F = mesh.verts.device, mesh.verts.shape[0], mesh.faces.shape[0]
+    stats = torch.zeros(4, dtype=torch.int64, device=dev)
+    if F == 0:
+        return (torch.full((H, W), -1, dtype=torch.int32, device=dev), torch.zeros(H, W, 2, dtype=torch.float32, device=dev),
+                torch.zeros(H, W, dtype=torch.float32, device=dev), torch.zeros(H, W, dtype=torch.float32, device=dev), stats)
+    L = N.lib()
+    keys = torch.empty(H * W, dtype=torch.int64, device=dev)
+    face = torch.empty(H, W, dtype=torch.int32, device=dev)
+    bary = torch.empty(H, W, 2, dtype=torch.float32, device=dev)
+    depth = torch.empty(H, W, dtype=torch.float32, device=dev)
+    acc = torch.empty(H, W, dtype=torch.float32, device=dev)
+    _mark(mark, "clear")
+    N.check(L.nerf_raster_clear(N.ptr(keys), H, W, N.ptr(stats), N.stream()))
+    _mark(mark, "draw")
+    N.check(L.nerf_raster_draw(N.ptr(mesh.verts), V, N.ptr(mesh.faces), F, 0, view, H, W, near, int(cull), small_max, N.ptr(keys),
+                               N.ptr(stats), N.stream()))
+    _mark(mark, "resolve")
+    N.check(L.nerf_raster_resolve(N.ptr(keys), N.ptr(mesh.verts), V, N.ptr(mesh.faces), F, view, H, W, near, N.ptr(face), N.ptr(bary),
+                                  N.ptr(depth), N.ptr(acc), N.stream()))
+    return face, bary, depth, acc, stats
+
+
+def _raster_background(background, H, W, dev):
+    """(tensor, per_pixel): None is white; one colour [3]; or one per pixel, [H W, 3] or [H, W, 3], as render_frame takes it."""
+    if background is None:
+        return torch.ones(3, dtype=torch.float32, device=dev), 0
+    bg = N.f32(background, dev)
+    if bg.numel() == 3:
+        return bg.reshape(3), 0
+    if bg.numel() == 3 * H * W and bg.shape[-1] == 3:
+        return bg.reshape(H * W, 3), 1
+    raise ValueError(f"render_mesh: background must be None, one colour [3] or [{H * W}, 3], got shape {tuple(bg.shape)}")
+
+
+def render_mesh(mesh: Mesh, c2w, K, H: int, W: int, texture: Optional[Texture] = None, background=None, near: float = RASTER_NEAR,
+                cull_backfaces: bool = False, mark=None, small_max: int = RASTER_SMALL_MAX) -> MeshFrame:
+    """The picture of `mesh` from the camera of `rasterize`: with `texture` every covered pixel looks the atlas up at its
+    (face, bary) through sample_texture; without one it takes the barycentric sum of mesh.colors (ValueError if there are none).
+    Empty pixels take `background`: None is white, else one colour or one per pixel as Trainer.render_frame.  One sample at the
+    pixel centre; no antialiasing.  mark: rasterize's stages, then "texture" (with one) and "shade"."""
+    _check_mesh_tensors("render_mesh", mesh)
+    H, W, near, cull_backfaces, small_max = check_raster_args(H, W, near, cull_backfaces, small_max)
+    if texture is not None:
+        _check_texture("render_mesh", texture, mesh)
+    elif mesh.colors is None:
+        raise ValueError("render_mesh: a mesh without colors needs a texture")
+    dev, V, F = mesh.verts.device, mesh.verts.shape[0], mesh.faces.shape[0]
+    bg, per_pixel = _raster_background(background, H, W, dev)
+    face, bary, depth, acc, _ = rasterize(mesh, c2w, K, H, W, near, cull_backfaces, mark, small_max)
+    if F == 0:
+        rgb = (bg.reshape(H, W, 3) if per_pixel else bg.expand(H, W, 3)).clone()
+        return MeshFrame(rgb, depth, acc, face, bary)
+    looked_up = None
+    if texture is not None:
+        _mark(mark, "texture")
+        looked_up = sample_texture(texture, mesh, face.reshape(-1), bary.reshape(-1, 2))
+    rgb = torch.empty(H, W, 3, dtype=torch.float32, device=dev)
+    _mark(mark, "shade")
+    N.check(N.lib().nerf_raster_shade(N.ptr(face), N.ptr(bary), N.ptr(mesh.faces), V, F, None if texture is not None else N.ptr(mesh.colors),
+                                      N.ptr(looked_up), N.ptr(bg), per_pixel, H, W, N.ptr(rgb), N.stream()))
+    return MeshFrame(rgb, depth, acc, face, bary)
 
 
 def _replace_file(path: str, data: bytes):

@@ -253,6 +253,20 @@ class Trainer:
         from .mesh import bake_texture
         return bake_texture(self._mesh_field()[0], mesh, texels)
 
+    def render_mesh(self, mesh, c2w, texture=None, background=None):
+        """engine.mesh.MeshFrame of a finished mesh from pose c2w with this trainer's H, W, K and near: the pixels are the rays
+        of render_frame, shaded with `texture` or the mesh's vertex colours over `background` (None: white; one colour; or one
+        per pixel as render_frame takes it) (engine.mesh.render_mesh).  Runs on this rank only: no
+        collective."""
+        from .mesh import render_mesh
+        return render_mesh(mesh, c2w, self.K, self.H, self.W, texture=texture, background=background, near=float(self.near))
+
+    def mesh_psnr(self, mesh, c2w, gt: torch.Tensor, texture=None, background=None) -> float:
+        """PSNR of render_mesh's picture against gt [H, W, 3], computed as `psnr` computes the field's.  This rank only."""
+        img = self.render_mesh(mesh, c2w, texture=texture, background=background).rgb
+        mse = torch.mean((img - gt.to(self.device)) ** 2)
+        return float(10.0 * torch.log10(1.0 / mse))
+
     # ---------------------------------------------------------------- checkpoint (SURVEY 8f-3)
     def _checkpoint_buffers(self):
         """name -> object with `.params` (flat fp32 device buffer) and `.load_flat(t)`; the names are also the Adam keys."""

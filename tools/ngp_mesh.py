@@ -42,6 +42,14 @@ store and uv stages (summed over the chunks) beside the vertex colour query of t
 the PLY and read back, and the fidelity of 2^20 area-weighted random surface samples, each queried directly from the field
 through the sampler's rows: RMS error and PSNR of the texture lookup and of the barycentric interpolation of the vertex colours.
 
+With --render, one more line per mesh the tool builds at --ply-res (the density mesh and each --simplify arm of it, quadric
+placement) and per shading (the vertex colours and each --texture T): the picture of DESIGN.md section 32 from the held-out pose
+(the fifth of the dataset's poses; the field trains on the first four) -- its PSNR against the held-out frame and against the
+field's own render_frame beside the field's PSNR, the device ms of the clear, draw, resolve, texture-lookup and shade stages at
+the stage hook beside the field's render_frame, the stats block (faces drawn, dropped, key updates) with the key updates per
+covered pixel, the draw's ms for every --small-max (repeatable; every value must give the same picture), and a PNG of the
+picture under --render-dir.
+
     rocprofv3 --kernel-trace --output-format csv -d DIR -o mesh -- python tools/ngp_mesh.py --ckpt /tmp/ngp.npz --reps 1 --no-ply
     python tools/ngp_mesh.py --stats DIR/.../mesh_kernel_trace.csv --from profiles/ngp_mesh.jsonl --out profiles/ngp_mesh_kernels.jsonl
 
@@ -337,6 +345,90 @@ def _texture_arms(query, m, source, R, a, rec, out_dir):
     return out
 
 
+def _render_timed(mesh, m, view, tex, small_max, log):
+    """engine.mesh.render_mesh of `m` from view = (c2w, K, H, W, near): (MeshFrame, {stage: ms}); every draw launch is logged."""
+    st = _Stages()
+    c2w, K, H, W, near = view
+    log.append(small_max)
+    fr = mesh.render_mesh(m, c2w, K, H, W, texture=tex, near=near, mark=st, small_max=small_max)
+    st("end")
+    return fr, st.ms()
+
+
+def _render_arms(tr, query, m, source, R, a, rec, heldout, out_dir):
+    """One JSON line per shading (vertex colours, each --texture T) of the coloured mesh `m` seen from the held-out pose."""
+    from nerf_meets_mlx_amd.engine import mesh
+    out = []
+    if m.faces.shape[0] == 0:
+        return out
+    pose, gt, field_rgb, field_ms = heldout
+    view = (pose, tr.K, tr.H, tr.W, float(tr.near))
+    field_psnr = _psnr(field_rgb - gt)["psnr_db"]
+    stages = ("clear", "draw", "resolve", "texture", "shade")
+    for T in [None] + list(a.texture or []):
+        tex = mesh.bake_texture(query, m, T) if T else None
+        log = []
+        _render_timed(mesh, m, view, tex, mesh.RASTER_SMALL_MAX, log)                # warm
+        ts = []
+        for _ in range(a.reps):
+            fr, t = _render_timed(mesh, m, view, tex, mesh.RASTER_SMALL_MAX, log)
+            ts.append([t.get(k, 0.0) for k in stages])
+        mean = np.mean(np.array(ts), 0)
+        log.append(mesh.RASTER_SMALL_MAX)
+        stats = mesh.rasterize(m, pose, tr.K, tr.H, tr.W, near=float(tr.near))[4].tolist()
+        covered = int((fr.face >= 0).sum())
+        arm = {"tool": "ngp_mesh render", "source": source, "R": R, "texels": T, "hw": tr.H, "iters": rec["iters"], "seed": rec["seed"],
+               "V": int(m.verts.shape[0]), "F": int(m.faces.shape[0]), "near": float(tr.near),
+               "psnr_vs_heldout_db": _psnr(fr.rgb - gt)["psnr_db"], "psnr_vs_field_db": _psnr(fr.rgb - field_rgb)["psnr_db"],
+               "field_psnr_db": field_psnr, "field_render_frame_ms": field_ms,
+               **{f"{k}_ms": float(x) for k, x in zip(stages, mean)},
+               **{f"{k}_ms_range": [float(min(r[i] for r in ts)), float(max(r[i] for r in ts))] for i, k in enumerate(stages)},
+               "render_ms": float(mean.sum()), "faces_drawn": stats[0], "faces_dropped_depth_or_guard": stats[1],
+               "faces_dropped_other": stats[2], "key_updates": stats[3], "covered_pixels": covered,
+               "key_updates_per_covered_pixel": (stats[3] / covered if covered else None), "small_max": mesh.RASTER_SMALL_MAX,
+               "device": rec["device"]}
+        if T is None and a.small_max:                                     # the draw alone depends on it; swept once per mesh
+            sweep = {}
+            for sm in a.small_max:
+                _render_timed(mesh, m, view, None, sm, log)
+                td, same = [], True
+                for _ in range(a.reps):
+                    f2, t = _render_timed(mesh, m, view, None, sm, log)
+                    td.append(t["draw"])
+                    same = same and bool(torch.equal(f2.face, fr.face) and torch.equal(f2.depth, fr.depth)
+                                         and torch.equal(f2.rgb, fr.rgb))
+                sweep[str(sm)] = {"draw_ms": float(np.mean(td)), "draw_ms_range": [min(td), max(td)], "same_picture": same}
+            arm["small_max_sweep"] = sweep
+        arm["draw_launch_small_max"] = log
+        name = f"render_{source.replace(' ', '_')}_R{R}_{'T%d' % T if T else 'colors'}.png"
+        img = (fr.rgb.clamp(0.0, 1.0) * 255.0).round().to(torch.uint8).cpu().numpy()
+        data = mesh.png_bytes(img)
+        arm["png_bytes"] = len(data)
+        if out_dir:
+            os.makedirs(out_dir, exist_ok=True)
+            with open(os.path.join(out_dir, name), "wb") as fh:
+                fh.write(data)
+            arm["png"] = name
+        print(json.dumps(arm), flush=True)
+        out.append(arm)
+        del tex, fr
+    torch.cuda.empty_cache()
+    return out
+
+
+def _heldout(tr, pose, gt, reps):
+    """(pose, gt [H, W, 3], the field's render_frame, its device ms: the mean of `reps` runs behind a warm-up)."""
+    ts = []
+    for _ in range(reps + 1):
+        ev = _events()
+        ev[0].record()
+        rgb = tr.render_frame(pose, shard=False)
+        ev[1].record()
+        torch.cuda.synchronize()
+        ts.append(ev[0].elapsed_time(ev[1]))
+    return pose, gt, rgb, float(np.mean(ts[1:]))
+
+
 def _tsdf_arm(tr, mesh, R, lo, hi, a, rec, bound, boxes):
     """The TSDF export of the same field as its stages, each between device events (the last of --reps runs is kept)."""
     poses = tr.poses if a.tsdf_views is None else tr.poses[:a.tsdf_views]
@@ -434,6 +526,12 @@ def parser():
     ap.add_argument("--texture", type=int, action="append", default=None, metavar="T",
                     help="also bake a texture atlas with T texels per triangle leg for the density mesh at --ply-res and each "
                          "--simplify arm of it (DESIGN.md section 31); repeatable: one JSON line per value and mesh")
+    ap.add_argument("--render", action="store_true",
+                    help="also render the density mesh at --ply-res and each --simplify arm of it from the held-out pose, with "
+                         "vertex colours and with each --texture T (DESIGN.md section 32): PSNR, stage times, stats, a PNG")
+    ap.add_argument("--small-max", type=int, action="append", default=None, metavar="N",
+                    help="--render: also time the draw with this small_max (repeatable); the picture must not change")
+    ap.add_argument("--render-dir", default=None, help="--render: write the PNGs here (default: not written)")
     ap.add_argument("--smooth-lambda", type=float, default=0.5)
     ap.add_argument("--smooth-mu", type=float, default=-0.53, help="0: plain Laplacian smoothing")
     ap.add_argument("--ckpt", default=None, help="load this checkpoint instead of training")
@@ -460,11 +558,16 @@ def main():
     H = W = a.hw
     if a.ckpt:
         imgs, poses, K = torch.zeros(1, 8, 8, 4 if a.random_bg else 3), synthetic.train_poses(1), synthetic.intrinsics(8, 8)[0]
-        if a.tsdf:                                           # the depth renders need the training cameras at full size
+        if a.tsdf or a.render:                               # the depth renders and the pictures need the cameras at full size
             imgs, poses, K = torch.zeros(1, H, W, imgs.shape[-1]), synthetic.train_poses(5)[:4], synthetic.intrinsics(H, W)[0]
+        if a.render:
+            held_pose, held_gt = synthetic.train_poses(5)[4], synthetic.render_gt(H, W, synthetic.train_poses(5)[4], device=dev)
     else:
         imgs, poses, _, _, K = synthetic.make_dataset(H, W, 5, seed=0, device=dev, rgba=a.random_bg)
+        held_pose, held_gt = poses[4], imgs[4]
         imgs, poses = imgs[:4], poses[:4]
+    if a.render and a.random_bg:                             # straight RGBA over the renderer's white
+        held_gt = held_gt[..., :3] * held_gt[..., 3:] + (1.0 - held_gt[..., 3:])
     tr = NGPTrainer(imgs, poses, K, N_rand=a.n_rand, n_depth_samples=64, seed=4, device=dev, occupancy_grid=True,
                     march_steps=a.march_steps, distortion_weight=a.dist_weight, random_background=a.random_bg,
                     level_anneal=level_anneal_from_text(a.level_anneal) if a.level_anneal else None)
@@ -522,6 +625,14 @@ def main():
                     sm = sm._replace(colors=mesh.vertex_colors(query, srows))
                     lines += _texture_arms(query, sm, f"density simplify {G}", R, a, rec, d)
                     del sm, srows
+        if a.render and R == a.ply_res:
+            heldout = _heldout(tr, held_pose, held_gt[..., :3].to(dev).float(), a.reps)
+            lines += _render_arms(tr, query, m, "density", R, a, rec, heldout, a.render_dir)
+            for G in a.simplify or []:
+                sm, srows, _ = mesh._simplify(m._replace(colors=None), G, lo, hi, "quadric", True)
+                sm = sm._replace(colors=mesh.vertex_colors(query, srows))
+                lines += _render_arms(tr, query, sm, f"density simplify {G}", R, a, rec, heldout, a.render_dir)
+                del sm, srows
         lines += _simplify_arms(m._replace(colors=None), "density", R, lo, hi, a, rec, bound, boxes)
         lines += _smooth_arms(m._replace(colors=None), "density", R, lo, hi, a, rec, bound, boxes)
         del vol, m, rows, col
@@ -630,6 +741,12 @@ def _texture_bytes(kernel, items):
     return {"tex_rows_kernel": 44, "tex_store_kernel": 16 + 3, "tex_uv_kernel": 24, "tex_sample_kernel": 12 + 12 + 44}[kernel] * items
 
 
+def _raster_bytes(kernel, items):
+    """Algorithmic HBM bytes of one csrc/raster.hip launch over `items` pixels (clear, resolve, shade) or faces (draw): what is
+    streamed in and written; the gathered vertices, keys and colours are cache hits or depend on the picture."""
+    return {"raster_clear_kernel": 8, "raster_draw_kernel": 12, "raster_resolve_kernel": 8 + 20, "raster_shade_kernel": 12 + 12}[kernel] * items
+
+
 def _morph_grid(kernel, R):
     """Work-items of a csrc/morph.hip launch at lattice size R."""
     words = -(-R // 64) * R * R
@@ -643,7 +760,7 @@ def _morph_grid(kernel, R):
 def stats(a):
     """Per mesh kernel and lattice size: mean device time per launch from a rocprofv3 --kernel-trace CSV, bytes / time."""
     import re
-    runs, tsdf_runs = {}, {}
+    runs, tsdf_runs, renders = {}, {}, []
     if a.from_:
         with open(a.from_) as fh:
             for ln in fh:
@@ -652,15 +769,22 @@ def stats(a):
                     runs[r["R"]] = r
                 elif r.get("tool") == "ngp_mesh tsdf":
                     tsdf_runs[r["R"]] = r
+                elif r.get("tool") == "ngp_mesh render":
+                    renders.append(r)
     with open(a.stats) as fh:
         rows = list(csv.DictReader(fh))
     col = {k.lower(): k for k in rows[0]} if rows else {}
     name_k = col.get("kernel_name")
     s_k, e_k = col.get("start_timestamp"), col.get("end_timestamp")
     gx = col.get("grid_size_x", col.get("grid_size"))
-    groups, tex_items = {}, {}
+    groups, tex_items, raster_items = {}, {}, {}
+    # the draws of one mesh in launch order: the render lines of that mesh list the small_max of every draw launch they made
+    draw_sm = {}
+    for r in renders:
+        draw_sm.setdefault(-(-r["F"] // BLOCK) * BLOCK, []).extend((r["F"], sm) for sm in r.get("draw_launch_small_max", []))
+    draw_seen = {}
     for r in rows:
-        m = re.search(r"(mesh_\w+_kernel|ccl_\w+_kernel|morph_\w+_kernel|tsdf_\w+_kernel|simp_\w+_kernel|smooth_\w+_kernel|tex_\w+_kernel|occ_cull_scan_kernel|occ_merge_exp_kernel)", r[name_k])
+        m = re.search(r"(mesh_\w+_kernel|ccl_\w+_kernel|morph_\w+_kernel|tsdf_\w+_kernel|simp_\w+_kernel|smooth_\w+_kernel|tex_\w+_kernel|raster_\w+_kernel|occ_cull_scan_kernel|occ_merge_exp_kernel)", r[name_k])
         if not m:
             continue
         k = m.group(1)
@@ -670,6 +794,17 @@ def stats(a):
                 k += "<seeds>" if k == "morph_pack_kernel" else "<dilate>"
             R = next((R for R in runs if _morph_grid(k, R) == grid), None)
             groups.setdefault((k, R), []).append((int(r[e_k]) - int(r[s_k])) * 1e-3)
+            continue
+        if k.startswith("raster_"):                    # one lane per pixel or face; the draws apart by mesh and small_max
+            tag = None
+            if k == "raster_draw_kernel" and grid in draw_sm:
+                i = draw_seen.get(grid, 0)
+                draw_seen[grid] = i + 1
+                if i < len(draw_sm[grid]):
+                    tag = "F=%d small_max=%d" % draw_sm[grid][i]
+            k = k if tag is None else f"{k} {tag}"
+            raster_items.setdefault(k, []).append(grid)
+            groups.setdefault((k, None), []).append((int(r[e_k]) - int(r[s_k])) * 1e-3)
             continue
         if k.startswith("tex_"):                       # chunked: pooled per kernel; one lane per texel, face or sample
             tex_items.setdefault(k, []).append(grid)
@@ -692,6 +827,9 @@ def stats(a):
         if k in tex_items:
             rec["items"] = int(np.median(tex_items[k]))
             b = _texture_bytes(k, rec["items"])
+        elif k in raster_items:
+            rec["items"] = int(np.median(raster_items[k]))
+            b = _raster_bytes(k.split()[0], rec["items"])
         elif R is not None and R in runs:
             b = _bytes(k, R, runs[R]["V"], runs[R]["F"])
         if b:
