@@ -1000,6 +1000,57 @@ int nerf_render_rays_fused(const nerf_mlp_arch* arch, const void* packed_coarse,
                            void* workspace, float* rgb, float* disp, float* acc, float* rgb_coarse, float* disp_coarse,
                            float* acc_coarse, float* z_vals, float* weights, void* stream);
 
+/* ---------------------------------------------------------------- view-projected texture (no reference counterpart)
+ * The atlas of "texture atlas" coloured from posed images, as photogrammetry pipelines bake a texture: every texel is projected
+ * into every view, the observation is kept only where the mesh's own depth map of that view ("mesh rendering") says the texel is
+ * visible, and the observations are blended.  The texels then hold what cameras saw along their rays, not what the field answers
+ * along minus the normal.  Additive: NERF_ABI_VERSION stays 3.  All float steps are IEEE float32, one rounding per operation (no
+ * contraction), in exactly the order and grouping written here; a / b and sqrt are correctly rounded.  csrc/project.h states the
+ * rule in code; tests/_project_ref.py reproduces every output bit for bit.
+ *   input     the mesh, texels T and the atlas of "texture atlas"; n <= NERF_PROJECT_MAX_VIEWS views, each a nerf_tsdf_view on the
+ *             host (16 finite floats), an image [H, W, 3] float32 and a depth / acc map pair [H W] float32 of the same camera, as
+ *             nerf_raster_resolve or a renderer's aux maps give them, stacked: images [n, H, W, 3], depth and acc [n, H W];
+ *             1 <= H, W <= 16384; near finite and > 0; depth_tol finite and >= 0; cos_min and acc_min in (0, 1].
+ *   texel     texel p of the atlas has the position x and the unit normal n of nerf_texture_rows: row[0:3] = x, row[3:6] = -n,
+ *             the unclamped extrapolation beyond the hypotenuse and the zero normal included.  A texel of no face, or of a face
+ *             with an index outside [0, V), makes no observation and its state is not touched.
+ *   camera    q_a = x_a - t_a; x_c = (r00 q0 + r10 q1) + r20 q2, y_c with column 1, z_w with column 2; zc = 0.0f - z_w;
+ *             !(zc >= near): no observation (NaN included).  u = fx (x_c / zc) + cx; v = cy - fy (y_c / zc).
+ *   facing    e_a = t_a - x_a; L = sqrt((e0 e0 + e1 e1) + e2 e2); cosv = ((n0 e0 + n1 e1) + n2 e2) / L; !(cosv >= cos_min): no
+ *             observation.  The weight of the observation is w = cosv.
+ *   visible   fu = floorf(u + 0.5f), fv = floorf(v + 0.5f); unless 0 <= fu < W and 0 <= fv < H, compared as floats: no
+ *             observation.  a = acc[fv W + fu], s = depth[fv W + fu]; a or s NaN, or a < acc_min: no observation.
+ *             ez = s / a - zc; !(ez >= 0.0f - depth_tol): no observation, the texel lies behind what the view sees.
+ *   colour    a bilinear lookup of the image at (u, v), pixel centres at the integers: x0 = floorf(u), y0 = floorf(v); unless
+ *             0 <= x0, x0 + 1 <= W - 1, 0 <= y0 and y0 + 1 <= H - 1, compared as floats: no observation.  fx = u - x0, fy = v - y0,
+ *             gx = 1 - fx, gy = 1 - fy; w00 = gx gy, w10 = fx gy, w01 = gx fy, w11 = fx fy (the first index along x, cij the pixel
+ *             (x0 + i, y0 + j)); per channel c = ((w00 c00 + w10 c10) + w01 c01) + w11 c11.  A NaN channel: no observation.
+ *   state     float32 [W_atlas H_atlas, 4] = (S_c [3], S_w) per texel, 16-byte aligned, zeroed by the caller before the first
+ *             view.  NERF_PROJECT_BLEND: S_c = S_c + w c per channel and S_w = S_w + w, in view order.  NERF_PROJECT_BEST: if
+ *             w > S_w then S = (c, w); strict, so of equal weights the earlier view stays.
+ *   finish    where S_w > 0: c = S_c / S_w (blend) or S_c (best), byte = (uint8)rint(255 unit(c)) as nerf_texture_store; seen = 1.
+ *             Elsewhere (NaN included): the byte of `fallback` [H_atlas, W_atlas, 3] uint8 at the texel, 0 without one; seen = 0.
+ * Calls:
+ *   nerf_project_accumulate  folds views 0 .. n - 1 in order into the state of the texels [p0, p0 + count) of the atlas, one lane
+ *                            per texel: the state is loaded once, kept in registers over the views and stored once, which is
+ *                            bit-identical to n calls with one view each.  n = 0 or count = 0: nothing is launched.
+ *   nerf_project_finish      image [H_atlas, W_atlas, 3] uint8 and seen [H_atlas, W_atlas] uint8 of the same texels; other texels
+ *                            are not touched, so neither depends on how the atlas is cut into chunks.
+ * The UVs are nerf_texture_uv's.  No atomics, no workspace, no host read; every output element has one writer: bit-reproducible.
+ * Out of range: NERF_E_SHAPE; NULL: NERF_E_NULL; all argument checks run before any device work.
+ * Not done: no RGBA inputs with alpha-weighted observations, no mipmaps or footprint-sized filtering of the images (one bilinear
+ * lookup whatever the texel's size on the screen), no seam levelling between views, no exposure or colour correction between views,
+ * no near-plane clipping (the depth maps are the rasteriser's), no inpainting of unseen texels beyond the fallback.             */
+#define NERF_PROJECT_MAX_VIEWS 16
+#define NERF_PROJECT_BLEND 0
+#define NERF_PROJECT_BEST 1
+int nerf_project_accumulate(const float* verts, const float* normals, int64_t V, const int32_t* faces, int64_t F, int texels,
+                            int64_t p0, int64_t count, const nerf_tsdf_view* views_host, int n, int H, int W, const float* images,
+                            const float* depth, const float* acc, float near, float depth_tol, float cos_min, float acc_min, int mode,
+                            float* state, void* stream);
+int nerf_project_finish(const float* state, int64_t F, int texels, int64_t p0, int64_t count, int mode, const uint8_t* fallback,
+                        uint8_t* image, uint8_t* seen, void* stream);
+
 /* ---------------------------------------------------------------- gradient all-reduce (no reference
  * counterpart: the reference is single-device).  RCCL over xGMI, one in-place float32 sum of the flat gradient
  * buffer per network step.  id: 128 host bytes from nerf_comm_unique_id on rank 0, distributed by the caller.

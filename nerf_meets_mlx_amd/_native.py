@@ -129,6 +129,9 @@ SIGNATURES = {
     "nerf_raster_draw": (_I, [_P, _I64, _P, _I64, _I64, C.POINTER(C.c_float), _I, _I, _F, _I, _I, _P, _P, _P]),
     "nerf_raster_resolve": (_I, [_P, _P, _I64, _P, _I64, C.POINTER(C.c_float), _I, _I, _F, _P, _P, _P, _P, _P]),
     "nerf_raster_shade": (_I, [_P, _P, _P, _I64, _I64, _P, _P, _P, _I, _I, _I, _P, _P]),
+    "nerf_project_accumulate": (_I, [_P, _P, _I64, _P, _I64, _I, _I64, _I64, C.POINTER(C.c_float), _I, _I, _I, _P, _P, _P, _F, _F, _F, _F,
+                                    _I, _P, _P]),
+    "nerf_project_finish": (_I, [_P, _I64, _I, _I64, _I64, _I, _P, _P, _P, _P]),
 }
 
 

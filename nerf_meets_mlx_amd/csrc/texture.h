@@ -8,7 +8,8 @@
 //   lookup   bilinear, corner (i0, j0) = the floors clamped to [0, S - 2], fractions (fx, fy) = x - i0, y - j0;
 //            ((w00 c00 + w10 c10) + w01 c01) + w11 c11 with w00 = (1 - fx)(1 - fy), w10 = fx (1 - fy), w01 = (1 - fx) fy,
 //            w11 = fx fy and c = (float)byte / 255.0f, every operation rounded to float32 on its own
-// The layout helpers compile for host and device; the host checks use nerf::fail through NERF_REQUIRE.
+// The layout helpers compile for host and device; the host checks use nerf::fail through NERF_REQUIRE.  The device part below them
+// (a texel's face, barycentrics, position and normal) is shared by texture.hip and project.hip, which therefore see the same texel.
 #pragma once
 #include "lattice.h"
 
@@ -49,6 +50,19 @@ inline int tex_layout(const char* who, int64_t F, int T, TexLayout* lay) {
   return NERF_OK;
 }
 
+// the mesh arguments of rows, store and sample, and the chunk [p0, p0 + count) of the atlas that rows, store and project.hip walk
+inline int tex_mesh_check(const char* who, int64_t V, int64_t F, int T, TexLayout* lay) {
+  NERF_REQUIRE(V >= 0 && V <= TEX_MAX_FACES, NERF_E_SHAPE, "%s: need 0 <= V <= 2^24 (got %lld)", who, (long long)V);
+  return tex_layout(who, F, T, lay);
+}
+inline int tex_chunk_check(const char* who, const TexLayout& lay, int64_t p0, int64_t count) {
+  const int64_t P = (int64_t)lay.W * lay.H;
+  NERF_REQUIRE(p0 >= 0 && count >= 0 && p0 <= P && count <= P - p0, NERF_E_SHAPE,
+               "%s: the chunk [%lld, %lld + %lld) leaves the atlas of %lld texels", who, (long long)p0, (long long)p0, (long long)count,
+               (long long)P);
+  return NERF_OK;
+}
+
 // the face of atlas texel (X, Y) and its local texel (i, j), mirrored for the odd face; a face >= F is unused
 __host__ __device__ __forceinline__ int tex_owner(const TexLayout& l, int X, int Y, int* i, int* j) {
   const int c = (Y / l.S) * l.C + X / l.S;
@@ -67,6 +81,54 @@ __host__ __device__ __forceinline__ void tex_place(const TexLayout& l, int f, in
   *X = (c % l.C) * l.S + i;
   *Y = (c / l.C) * l.S + j;
 }
+
+#if defined(__HIPCC__)
+__device__ __forceinline__ float tex_pos(float x) { return x > 0.0f ? x : 0.0f; }                 // NaN -> 0
+__device__ __forceinline__ float tex_unit(float x) { x = tex_pos(x); return x < 1.0f ? x : 1.0f; }
+
+// the corners of face f; false for an unused face (f outside [0, F)) or one with an index outside [0, V): nothing is read through it
+__device__ __forceinline__ bool tex_face(const int* __restrict__ faces, int f, int F, int V, int* g) {
+  if (f < 0 || f >= F) return false;
+  bool ok = true;
+#pragma unroll
+  for (int c = 0; c < 3; ++c) {
+    g[c] = faces[3 * (int64_t)f + c];
+    ok = ok && g[c] >= 0 && g[c] < V;
+  }
+  return ok;
+}
+
+// position x and unit normal n (0 where the interpolated normal has no direction) of the point with barycentrics (wb, wc) of the
+// face with corners g: the texel of the rows kernel, the sample of the sampler and the texel the projective bake observes
+__device__ __forceinline__ void tex_point(const float* __restrict__ verts, const float* __restrict__ normals, const int* g, float wb,
+                                          float wc, float* x, float* n) {
+  const float wa = (1.0f - wb) - wc;
+  const float pa = tex_pos(wa), pb = tex_pos(wb), pc = tex_pos(wc);
+  float m[3];
+#pragma unroll
+  for (int a = 0; a < 3; ++a) {
+    x[a] = (wa * verts[3 * g[0] + a] + wb * verts[3 * g[1] + a]) + wc * verts[3 * g[2] + a];
+    m[a] = (pa * normals[3 * g[0] + a] + pb * normals[3 * g[1] + a]) + pc * normals[3 * g[2] + a];
+  }
+  const float len = sqrt_rn((m[0] * m[0] + m[1] * m[1]) + m[2] * m[2]);
+  const bool ok = len > 0.0f && len <= 3.402823466e+38f;
+#pragma unroll
+  for (int a = 0; a < 3; ++a) n[a] = ok ? div_rn(m[a], len) : 0.0f;
+}
+
+// texel p of the atlas: its face's corners g and its barycentrics; false for a texel of no face or of a face with a bad index
+__device__ __forceinline__ bool tex_texel(const TexLayout& lay, const int* __restrict__ faces, int V, int64_t p, int* g, float* wb,
+                                          float* wc) {
+  const int Y = (int)(p / lay.W), X = (int)(p - (int64_t)Y * lay.W);
+  int i, j;
+  const int f = tex_owner(lay, X, Y, &i, &j);
+  if (!tex_face(faces, f, lay.F, V, g)) return false;
+  const float d = (float)(lay.T - 1);
+  *wb = div_rn((float)i, d);
+  *wc = div_rn((float)j, d);
+  return true;
+}
+#endif
 
 }  // namespace
 }  // namespace nerf

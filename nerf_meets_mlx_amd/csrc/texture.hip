@@ -14,36 +14,11 @@
 namespace nerf {
 namespace {
 
-__device__ __forceinline__ float tex_pos(float x) { return x > 0.0f ? x : 0.0f; }                 // NaN -> 0
-__device__ __forceinline__ float tex_unit(float x) { x = tex_pos(x); return x < 1.0f ? x : 1.0f; }
-
-// the corners of face f; false for an unused face (f outside [0, F)) or one with an index outside [0, V): nothing is read through it
-__device__ __forceinline__ bool tex_face(const int* __restrict__ faces, int f, int F, int V, int* g) {
-  if (f < 0 || f >= F) return false;
-  bool ok = true;
-#pragma unroll
-  for (int c = 0; c < 3; ++c) {
-    g[c] = faces[3 * (int64_t)f + c];
-    ok = ok && g[c] >= 0 && g[c] < V;
-  }
-  return ok;
-}
-
 // row `id` of `rows` (LDS or global): the point with barycentrics (wb, wc) of the face with corners g, looking along -normal
 __device__ __forceinline__ void tex_write_row(float* rows, int id, const float* __restrict__ verts, const float* __restrict__ normals,
                                               const int* g, float wb, float wc) {
-  const float wa = (1.0f - wb) - wc;
-  const float pa = tex_pos(wa), pb = tex_pos(wb), pc = tex_pos(wc);
-  float x[3], m[3], n[3];
-#pragma unroll
-  for (int a = 0; a < 3; ++a) {
-    x[a] = (wa * verts[3 * g[0] + a] + wb * verts[3 * g[1] + a]) + wc * verts[3 * g[2] + a];
-    m[a] = (pa * normals[3 * g[0] + a] + pb * normals[3 * g[1] + a]) + pc * normals[3 * g[2] + a];
-  }
-  const float len = sqrt_rn((m[0] * m[0] + m[1] * m[1]) + m[2] * m[2]);
-  const bool ok = len > 0.0f && len <= 3.402823466e+38f;
-#pragma unroll
-  for (int a = 0; a < 3; ++a) n[a] = ok ? div_rn(m[a], len) : 0.0f;
+  float x[3], n[3];
+  tex_point(verts, normals, g, wb, wc, x, n);
   write_color_row(rows, id, x, n);
 }
 
@@ -67,15 +42,10 @@ __global__ void __launch_bounds__(TEX_BLOCK) tex_rows_kernel(const float* __rest
   const int64_t first = (int64_t)blockIdx.x * TEX_BLOCK, q = first + threadIdx.x;
   if (q < count) {
     const int64_t p = p0 + q;
-    const int Y = (int)(p / lay.W), X = (int)(p - (int64_t)Y * lay.W);
-    int i, j, g[3];
-    const int f = tex_owner(lay, X, Y, &i, &j);
-    if (tex_face(faces, f, lay.F, V, g)) {
-      const float d = (float)(lay.T - 1);
-      tex_write_row(stage, threadIdx.x, verts, normals, g, div_rn((float)i, d), div_rn((float)j, d));
-    } else {
-      tex_zero_row(stage, threadIdx.x);
-    }
+    int g[3];
+    float wb, wc;
+    if (tex_texel(lay, faces, V, p, g, &wb, &wc)) tex_write_row(stage, threadIdx.x, verts, normals, g, wb, wc);
+    else tex_zero_row(stage, threadIdx.x);
   }
   const int64_t left = count - first;
   tex_flush_rows(stage, rows, first, (int)(left < TEX_BLOCK ? left : TEX_BLOCK));
@@ -165,19 +135,6 @@ __global__ void __launch_bounds__(TEX_BLOCK) tex_sample_kernel(const uint8_t* __
 }
 
 inline unsigned tex_blocks(int64_t n) { return (unsigned)((n + TEX_BLOCK - 1) / TEX_BLOCK); }
-
-// the mesh arguments of rows, store and sample
-int tex_mesh_check(const char* who, int64_t V, int64_t F, int T, TexLayout* lay) {
-  NERF_REQUIRE(V >= 0 && V <= TEX_MAX_FACES, NERF_E_SHAPE, "%s: need 0 <= V <= 2^24 (got %lld)", who, (long long)V);
-  return tex_layout(who, F, T, lay);
-}
-int tex_chunk_check(const char* who, const TexLayout& lay, int64_t p0, int64_t count) {
-  const int64_t P = (int64_t)lay.W * lay.H;
-  NERF_REQUIRE(p0 >= 0 && count >= 0 && p0 <= P && count <= P - p0, NERF_E_SHAPE,
-               "%s: the chunk [%lld, %lld + %lld) leaves the atlas of %lld texels", who, (long long)p0, (long long)p0, (long long)count,
-               (long long)P);
-  return NERF_OK;
-}
 
 #define TEX_LAUNCH(what, kernel, blocks, ...) NERF_LAUNCH(what, kernel, blocks, TEX_BLOCK, st, __VA_ARGS__)
 

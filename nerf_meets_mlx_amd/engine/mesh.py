@@ -34,6 +34,9 @@ section 14).  The reference has no such export; this is Instant-NGP's.
     depth, by exact integer coverage and one 64-bit atomicMin per covered pixel; `render_mesh` shades that with the vertex
     colours or through `sample_texture` into a `MeshFrame` (include/nerf_hip.h "mesh rendering"), so a
     mesh can be compared with the held-out frame and with the field's render in image space (`Trainer.mesh_psnr`).
+  * `project_texture(mesh, images, c2w, K, texels, depth_tol)` colours the same atlas from posed pictures: every texel takes what
+    the views saw of it where the mesh's own depth map of the view says it is visible, blended by the cosine or from the best
+    view, and a fallback texture elsewhere (include/nerf_hip.h "view-projected texture").
   * `write_ply` writes a binary little-endian PLY; `write_obj` an OBJ with its .mtl and the atlas as a .png, which a PLY cannot
     carry.
 """
@@ -64,6 +67,10 @@ TEXTURE_MAX_SIDE = 16384     # NERF_TEXTURE_MAX_SIDE
 RASTER_MAX_SIDE = 16384      # image height and width of the mesh renderer
 RASTER_SMALL_MAX = 16        # NERF_RASTER_SMALL_MAX
 RASTER_NEAR = 0.01           # the mesh renderer's default near plane
+PROJECT_MAX_VIEWS = 16       # NERF_PROJECT_MAX_VIEWS: views per launch of the projective bake
+PROJECT_MODES = {"blend": 0, "best": 1}   # NERF_PROJECT_BLEND / NERF_PROJECT_BEST
+PROJECT_COS_MIN = 0.05       # the projective bake's default grazing limit: the best of the sweep of DESIGN.md section 33
+PROJECT_DEPTH_TOL_CELLS = 4.0  # Trainer.project_texture's default depth_tol in spacings of a 256^3 lattice on its scene box (section 33)
 
 
 class Mesh(NamedTuple):
@@ -883,6 +890,105 @@ def render_mesh(mesh: Mesh, c2w, K, H: int, W: int, texture: Optional[Texture] =
     N.check(N.lib().nerf_raster_shade(N.ptr(face), N.ptr(bary), N.ptr(mesh.faces), V, F, None if texture is not None else N.ptr(mesh.colors),
                                       N.ptr(looked_up), N.ptr(bg), per_pixel, H, W, N.ptr(rgb), N.stream()))
     return MeshFrame(rgb, depth, acc, face, bary)
+
+
+def check_project_args(depth_tol, mode="blend", near=RASTER_NEAR, cos_min=PROJECT_COS_MIN, acc_min=0.5, chunk=CHUNK):
+    """(depth_tol, mode number, near, cos_min, acc_min, chunk) as (float, int, float, float, float, int); ValueError for a
+    depth_tol that is not a finite number >= 0 (there is no scale-free default: it is a length of the scene; Trainer.project_texture
+    derives one from its scene box), a mode that is not "blend" or "best", a near that check_raster_args refuses, a cos_min or
+    acc_min outside (0, 1], or a chunk that is not an int >= 1."""
+    def real(x):
+        return not isinstance(x, bool) and isinstance(x, numbers.Real) and math.isfinite(float(x))
+    if not (real(depth_tol) and 0.0 <= float(depth_tol) <= float(np.finfo(np.float32).max)):
+        raise ValueError(f"project depth_tol must be a finite number >= 0 in the scene's units, got {depth_tol!r}")
+    if not isinstance(mode, str) or mode not in PROJECT_MODES:
+        raise ValueError(f"project mode must be one of {sorted(PROJECT_MODES)}, got {mode!r}")
+    near = check_raster_args(near=near)[2]
+    for name, x in (("cos_min", cos_min), ("acc_min", acc_min)):
+        if not (real(x) and 0.0 < float(np.float32(x)) <= 1.0):
+            raise ValueError(f"project {name} must be a number in (0, 1], got {x!r}")
+    if isinstance(chunk, bool) or not isinstance(chunk, numbers.Integral) or int(chunk) < 1:
+        raise ValueError(f"project chunk must be an int >= 1, got {chunk!r}")
+    return float(depth_tol), PROJECT_MODES[mode], near, float(cos_min), float(acc_min), int(chunk)
+
+
+def project_texture(mesh: Mesh, images: torch.Tensor, c2w, K, texels: int = 8, depth_tol=None, mode: str = "blend",
+                    fallback: Optional[Texture] = None, depth: Optional[torch.Tensor] = None, acc: Optional[torch.Tensor] = None,
+                    near: float = RASTER_NEAR, cos_min: float = PROJECT_COS_MIN, acc_min: float = 0.5, chunk: int = CHUNK, mark=None):
+    """(Texture, seen uint8 [H_atlas, W_atlas]): the atlas of bake_texture coloured from posed images (include/nerf_hip.h
+    "view-projected texture").  images [n, H, W, 3] float32 on the mesh's device, c2w a stack of n poses and
+    K as tsdf_views takes them.  Every texel is projected into every view; the view's bilinear colour there counts, with the
+    weight cos(normal, direction to the camera) >= cos_min, only where the view's depth map, read at the nearest pixel, puts the
+    surface no more than depth_tol (a length of the scene; required) in front of the texel.  mode "blend": the weighted mean over
+    the views; "best": the view with the largest weight, the earlier one of equal weights.  depth, acc [n, H, W]: the maps of
+    the views (a renderer's aux maps, depth not normalised); without them every view is rasterised (`rasterize` at `near`).  A
+    texel no view sees takes the byte of `fallback`, a Texture of this mesh at these texels (bake_texture's, say), or 0; seen is
+    1 where a view saw it.  PROJECT_MAX_VIEWS views per launch and `chunk` texels per launch; neither changes a bit.  F = 0 or
+    n = 0: no projection kernel is launched.  No host read.  mark: _mark's hook ("rasterize" per view, "accumulate" per launch,
+    then "finish" and "uv")."""
+    T, (Wa, Ha, _, _) = check_texture_args(mesh, texels)
+    tol, mode_id, near, cos_min, acc_min, chunk = check_project_args(depth_tol, mode, near, cos_min, acc_min, chunk)
+    dev, V, F = mesh.verts.device, mesh.verts.shape[0], mesh.faces.shape[0]
+    if not torch.is_tensor(images) or images.dtype != torch.float32 or images.dim() != 4 or images.shape[-1] != 3 \
+            or not images.is_contiguous() or images.device != dev:
+        raise ValueError("project_texture: images must be a contiguous float32 [n, H, W, 3] tensor on the vertices' device"
+                         + (" (RGBA frames are not supported)" if torch.is_tensor(images) and images.dim() == 4 and images.shape[-1] == 4 else ""))
+    n = images.shape[0]
+    H, W = check_raster_args(int(images.shape[1]) if n else 1, int(images.shape[2]) if n else 1)[:2]
+    views = tsdf_views(c2w, K) if n else np.zeros((0, 16), np.float32)
+    if views.shape[0] != n:
+        raise ValueError(f"project_texture: {n} images need {n} poses, got {views.shape[0]}")
+    if (depth is None) != (acc is None):
+        raise ValueError("project_texture: pass both depth and acc, or neither")
+    for name, t in (("depth", depth), ("acc", acc)):
+        if t is not None and (not torch.is_tensor(t) or t.dtype != torch.float32 or t.numel() != n * H * W or not t.is_contiguous()
+                              or t.device != dev):
+            raise ValueError(f"project_texture: {name} must be a contiguous float32 tensor of {n} x {H} x {W} elements on the vertices' device")
+    fb = None
+    if fallback is not None:
+        if _check_texture("project_texture", fallback, mesh)[0] != T:
+            raise ValueError(f"project_texture: the fallback has texels = {fallback.texels}, not {T}")
+        fb = fallback.image
+    uv = torch.empty(F, 3, 2, dtype=torch.float32, device=dev)
+    if F == 0 or n == 0:                                                   # nothing is seen: the fallback, or black
+        image = torch.zeros(Ha, Wa, 3, dtype=torch.uint8, device=dev) if fb is None else fb.clone()
+        seen = torch.zeros(Ha, Wa, dtype=torch.uint8, device=dev)
+    else:
+        image = torch.empty(Ha, Wa, 3, dtype=torch.uint8, device=dev)
+        seen = torch.empty(Ha, Wa, dtype=torch.uint8, device=dev)
+    if F == 0:
+        return Texture(image, uv, T), seen
+    L = N.lib()
+    P = Wa * Ha
+    chunk = min(chunk, P)
+    if n:
+        state = torch.zeros(P, 4, dtype=torch.float32, device=dev)
+        for s in range(0, n, PROJECT_MAX_VIEWS):
+            m = min(PROJECT_MAX_VIEWS, n - s)
+            if depth is None:
+                both = []
+                for k in range(s, s + m):
+                    _mark(mark, "rasterize")
+                    both.append(rasterize(mesh, views[k, :12].reshape(3, 4), _k_of(views[k]), H, W, near)[2:4])
+                d, a = torch.stack([b[0] for b in both]), torch.stack([b[1] for b in both])
+            else:
+                d, a = depth.reshape(n, H * W)[s:s + m], acc.reshape(n, H * W)[s:s + m]
+            v = np.ascontiguousarray(views[s:s + m])
+            _mark(mark, "accumulate")
+            for p0 in range(0, P, chunk):
+                N.check(L.nerf_project_accumulate(N.ptr(mesh.verts), N.ptr(mesh.normals), V, N.ptr(mesh.faces), F, T, p0, min(chunk, P - p0),
+                                                  v.ctypes.data_as(C.POINTER(C.c_float)), m, H, W, N.ptr(images[s:s + m]), N.ptr(d), N.ptr(a),
+                                                  near, tol, cos_min, acc_min, mode_id, N.ptr(state), N.stream()))
+        _mark(mark, "finish")
+        N.check(L.nerf_project_finish(N.ptr(state), F, T, 0, P, mode_id, N.ptr(fb), N.ptr(image), N.ptr(seen), N.stream()))
+    _mark(mark, "uv")
+    N.check(L.nerf_texture_uv(F, T, N.ptr(uv), N.stream()))
+    return Texture(image, uv, T), seen
+
+
+def _k_of(view):
+    """K [3, 3] of a nerf_tsdf_view row: its float32 fx, fy, cx, cy are exact as doubles, so tsdf_views gives the row back."""
+    return np.array([[view[12], 0.0, view[14]], [0.0, view[13], view[15]], [0.0, 0.0, 1.0]], np.float64)
 
 
 def _replace_file(path: str, data: bytes):

@@ -253,6 +253,43 @@ class Trainer:
         from .mesh import bake_texture
         return bake_texture(self._mesh_field()[0], mesh, texels)
 
+    def project_texture(self, mesh, texels: int = 8, views=None, source: str = "images", mode: str = "blend", fallback: bool = True,
+                        depth_tol=None):
+        """(engine.mesh.Texture, seen) of a finished engine.mesh.Mesh coloured from posed pictures: every texel takes what the
+        training cameras saw of it where the mesh's own depth map says it is visible from there (engine.mesh.project_texture,
+        DESIGN.md section 33), not what the field answers along minus the normal.  `views`: indices into the training poses, None
+        for all.  `source` "images": the training frames (RGB; a trainer that holds RGBA frames has no colours to project, use
+        "field"); "field": render_frame at those poses.  `fallback`: texels no view sees take texture_mesh(mesh, texels)'s colour,
+        else black.  `depth_tol` None: PROJECT_DEPTH_TOL_CELLS lattice spacings of a 256^3 lattice on the trainer's scene box, the
+        best of the sweep of DESIGN.md section 33; a trainer without a scene box needs a number.  Runs on this rank only: no
+        collective."""
+        from . import mesh as M
+        if source not in ("images", "field"):
+            raise ValueError(f"project_texture: source must be 'images' or 'field', got {source!r}")
+        n_all = int(self.poses.shape[0])
+        idx = list(range(n_all)) if views is None else [int(v) for v in views]
+        if any(not 0 <= v < n_all for v in idx):
+            raise ValueError(f"project_texture: views must be indices into the {n_all} training poses, got {views!r}")
+        if source == "images" and self.images.shape[-1] != 3:
+            raise ValueError("project_texture: this trainer holds RGBA frames, which have no colour behind their transparent pixels; "
+                             "use source=\"field\"")
+        if depth_tol is None:
+            try:
+                lo, hi = self._mesh_box(None)
+            except ValueError:
+                raise ValueError("project_texture: this trainer has no scene box to derive depth_tol from, pass depth_tol (a length "
+                                 "of the scene, about two voxels of the lattice the mesh came from)") from None
+            depth_tol = M.PROJECT_DEPTH_TOL_CELLS * max(h - l for l, h in zip(lo, hi)) / 256.0
+        poses = self.poses[idx, :3, :4] if idx else self.poses[:0, :3, :4]
+        if source == "images":
+            images = self.images[idx].contiguous() if idx else self.images[:0]
+        else:
+            frames = [self.render_frame(self.poses[v], shard=False).reshape(self.H, self.W, 3) for v in idx]
+            images = torch.stack(frames).contiguous() if frames else torch.zeros(0, self.H, self.W, 3, device=self.device)
+        fb = self.texture_mesh(mesh, texels) if fallback else None
+        return M.project_texture(mesh, images, poses, self.K, texels=texels, depth_tol=depth_tol, mode=mode, fallback=fb,
+                                 near=float(self.near))
+
     def render_mesh(self, mesh, c2w, texture=None, background=None):
         """engine.mesh.MeshFrame of a finished mesh from pose c2w with this trainer's H, W, K and near: the pixels are the rays
         of render_frame, shaded with `texture` or the mesh's vertex colours over `background` (None: white; one colour; or one

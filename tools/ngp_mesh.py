@@ -50,12 +50,21 @@ the stage hook beside the field's render_frame, the stats block (faces drawn, dr
 covered pixel, the draw's ms for every --small-max (repeatable; every value must give the same picture), and a PNG of the
 picture under --render-dir.
 
+With --project, for the same meshes at 8 texels a leg, the projective bake of DESIGN.md section 33: the PSNR of the picture from
+the held-out pose with the vertex colours, with the -normal texture and with the atlas coloured from the four training frames,
+from the field's own pictures at their poses and from the field's pictures on a ring of --project-ring poses, in both modes, with
+the share of texels seen and the device ms of the rasterize, accumulate and finish stages; the depth_tol sweep {h/2, h, 2h, 4h}
+and the cos_min sweep {0.05, 0.1, 0.3}; and the accumulate stage of sixteen views as one launch per chunk against one launch
+per view.  The last line of a mesh lists the views and texels of every accumulate launch in order, by which --stats --from tells
+the launches of a kernel trace apart.
+
     rocprofv3 --kernel-trace --output-format csv -d DIR -o mesh -- python tools/ngp_mesh.py --ckpt /tmp/ngp.npz --reps 1 --no-ply
     python tools/ngp_mesh.py --stats DIR/.../mesh_kernel_trace.csv --from profiles/ngp_mesh.jsonl --out profiles/ngp_mesh_kernels.jsonl
 
 summarises such a trace: per mesh kernel and R the mean device time per launch, and its algorithmic bytes over that time
 against the MI355X's HBM bandwidth (8.0 TB/s spec, 6.29 TB/s measured float4 copy)."""
 import argparse
+import ctypes as C
 import csv
 import json
 import os
@@ -416,6 +425,127 @@ def _render_arms(tr, query, m, source, R, a, rec, heldout, out_dir):
     return out
 
 
+def _project_arms(tr, query, m, source, R, a, rec, heldout, h, train):
+    """The projective bake of DESIGN.md section 33 on the coloured mesh `m` at T = 8: one JSON line per baseline (vertex colours,
+    the -normal texture) and per arm (pictures x mode, the depth_tol and cos_min sweeps, the launch shapes), each with the PSNR of
+    the picture from the held-out pose.  h: the lattice spacing; train = (images [n, H, W, 3], poses [n, 4, 4])."""
+    from nerf_meets_mlx_amd.dataset import synthetic
+    from nerf_meets_mlx_amd.engine import mesh
+    out = []
+    F = int(m.faces.shape[0])
+    if F == 0:
+        return out
+    T = 8
+    pose, gt, field_rgb, _ = heldout
+    near = float(tr.near)
+    W_a, H_a, _, S = mesh.texture_layout(F, T)
+    used = (F + 1) // 2 * (S * (S + 1) // 2) + F // 2 * (S * (S - 1) // 2)
+    base = {"tool": "ngp_mesh project", "source": source, "R": R, "texels": T, "hw": tr.H, "iters": rec["iters"], "seed": rec["seed"],
+            "V": int(m.verts.shape[0]), "F": F, "atlas": [W_a, H_a], "used_texels": used, "h": h, "device": rec["device"]}
+
+    def picture(tex):
+        rgb = mesh.render_mesh(m, pose, tr.K, tr.H, tr.W, texture=tex, near=near).rgb
+        return {"psnr_vs_heldout_db": _psnr(rgb - gt)["psnr_db"], "psnr_vs_field_db": _psnr(rgb - field_rgb)["psnr_db"]}
+
+    def emit(arm):
+        arm = {**base, **arm}
+        print(json.dumps(arm), flush=True)
+        out.append(arm)
+
+    ts = []
+    for _ in range(a.reps + 1):                                           # (the first run warms)
+        st = _Stages()
+        fallback = mesh.bake_texture(query, m, T, mark=st)
+        st("end")
+        ts.append(st.total_ms())
+    bake = {f"bake_{k}_ms": float(np.mean([t[k] for t in ts[1:]])) for k in ("rows", "query", "store", "uv")}
+    emit({"arm": "vertex colours", **picture(None)})
+    emit({"arm": "-normal texture", **picture(fallback), **bake})
+    ring = synthetic.render_poses()[::max(1, 160 // a.project_ring)][:a.project_ring]
+    frames = lambda poses: torch.stack([tr.render_frame(p, shard=False).reshape(tr.H, tr.W, 3) for p in poses]).contiguous()
+    pictures = {"images": (train[0], train[1]), "field": (frames(train[1]), train[1]), f"field ring {len(ring)}": (frames(ring), ring)}
+
+    log = []                                                              # (views, texels) of every accumulate launch, in order
+    P = W_a * H_a
+
+    def project(images, poses, mark=None, **kw):
+        for s in range(0, int(images.shape[0]), mesh.PROJECT_MAX_VIEWS):
+            log.extend((min(mesh.PROJECT_MAX_VIEWS, int(images.shape[0]) - s), min(mesh.CHUNK, P - p0)) for p0 in range(0, P, mesh.CHUNK))
+        return mesh.project_texture(m, images, poses, tr.K, mark=mark, **kw)
+
+    def arm(name, mode, k_tol, cos_min, timed=False):
+        images, poses = pictures[name]
+        kw = dict(texels=T, depth_tol=k_tol * h, mode=mode, fallback=fallback, near=near, cos_min=cos_min)
+        tex, seen = project(images, poses[:, :3, :4], **kw)
+        line = {"arm": "project", "pictures": name, "views": int(images.shape[0]), "mode": mode, "depth_tol_h": k_tol, "cos_min": cos_min,
+                "seen_share": float(seen.sum()) / used, **picture(tex)}
+        if timed:
+            ts = []
+            for _ in range(a.reps):
+                st = _Stages()
+                project(images, poses[:, :3, :4], mark=st, **kw)
+                st("end")
+                ts.append(st.total_ms())
+            line.update({f"{k}_ms": float(np.mean([t[k] for t in ts])) for k in ("rasterize", "accumulate", "finish", "uv")})
+            line.update({f"{k}_ms_range": [min(t[k] for t in ts), max(t[k] for t in ts)] for k in ("rasterize", "accumulate", "finish")})
+        emit(line)
+
+    for name in pictures:
+        for mode in ("blend", "best"):
+            arm(name, mode, mesh.PROJECT_DEPTH_TOL_CELLS, mesh.PROJECT_COS_MIN, timed=True)
+    for name in ("images", f"field ring {len(ring)}"):
+        for k_tol in (0.5, 1.0, 2.0, 4.0):
+            arm(name, "blend", k_tol, mesh.PROJECT_COS_MIN)
+        for cos_min in (0.05, 0.1, 0.3):
+            arm(name, "blend", mesh.PROJECT_DEPTH_TOL_CELLS, cos_min)
+    # the accumulate stage alone on the ring's views, the maps made once: all views folded by one launch per chunk, against one
+    # launch per view over the whole atlas, through the C entries as engine.mesh.project_texture calls them
+    from nerf_meets_mlx_amd import _native as N
+    images, poses = pictures[f"field ring {len(ring)}"]
+    n = min(int(images.shape[0]), mesh.PROJECT_MAX_VIEWS)
+    images, poses = images[:n].contiguous(), poses[:n, :3, :4]
+    maps = [mesh.rasterize(m, p, tr.K, tr.H, tr.W, near)[2:4] for p in poses]
+    depth, acc = torch.stack([x[0] for x in maps]), torch.stack([x[1] for x in maps])
+    views = mesh.tsdf_views(poses, tr.K)
+    tol, cos_min = mesh.PROJECT_DEPTH_TOL_CELLS * h, mesh.PROJECT_COS_MIN
+    state = torch.empty(P, 4, dtype=torch.float32, device=m.verts.device)
+    image = torch.empty(H_a, W_a, 3, dtype=torch.uint8, device=m.verts.device)
+    seen = torch.empty(H_a, W_a, dtype=torch.uint8, device=m.verts.device)
+    L = N.lib()
+    for mode in ("blend", "best"):
+        t_one, t_each, same = [], [], True
+        for rep in range(a.reps + 1):
+            st = _Stages()
+            tex, _ = project(images, poses, mark=st, texels=T, depth_tol=tol, mode=mode, near=near, cos_min=cos_min, depth=depth, acc=acc)
+            st("end")
+            t_one.append(st.total_ms()["accumulate"])
+            state.zero_()
+            ev = _events()
+            ev[0].record()
+            for k in range(n):
+                log.append((1, P))
+                N.check(L.nerf_project_accumulate(N.ptr(m.verts), N.ptr(m.normals), int(m.verts.shape[0]), N.ptr(m.faces), F, T, 0, P,
+                                                  np.ascontiguousarray(views[k]).ctypes.data_as(C.POINTER(C.c_float)), 1, tr.H, tr.W,
+                                                  N.ptr(images[k]), N.ptr(depth[k]), N.ptr(acc[k]), near, tol, cos_min, 0.5,
+                                                  mesh.PROJECT_MODES[mode], N.ptr(state), N.stream()))
+            ev[1].record()
+            torch.cuda.synchronize()
+            t_each.append(ev[0].elapsed_time(ev[1]))
+            N.check(L.nerf_project_finish(N.ptr(state), F, T, 0, P, mesh.PROJECT_MODES[mode], None, N.ptr(image), N.ptr(seen), N.stream()))
+            same = same and bool(torch.equal(image, tex.image))
+        gathered = n * used * 56
+        emit({"arm": "launch shape", "pictures": f"field ring {len(ring)}", "views": n, "mode": mode, "chunks": -(-P // mesh.CHUNK),
+              "one_launch_per_chunk_ms": float(np.mean(t_one[1:])), "one_launch_per_chunk_ms_range": [min(t_one[1:]), max(t_one[1:])],
+              "one_launch_per_view_ms": float(np.mean(t_each[1:])), "one_launch_per_view_ms_range": [min(t_each[1:]), max(t_each[1:])],
+              "same_image": same, "gathered_bytes_upper_bound": gathered,
+              "gathered_TBps_upper_bound": gathered / (float(np.mean(t_one[1:])) * 1e-3) / 1e12})
+    out[-1]["accumulate_launches"] = log
+    print(json.dumps({"tool": "ngp_mesh project", "source": source, "arm": "launch log", "launches": len(log)}), flush=True)
+    del fallback, pictures
+    torch.cuda.empty_cache()
+    return out
+
+
 def _heldout(tr, pose, gt, reps):
     """(pose, gt [H, W, 3], the field's render_frame, its device ms: the mean of `reps` runs behind a warm-up)."""
     ts = []
@@ -532,6 +662,12 @@ def parser():
     ap.add_argument("--small-max", type=int, action="append", default=None, metavar="N",
                     help="--render: also time the draw with this small_max (repeatable); the picture must not change")
     ap.add_argument("--render-dir", default=None, help="--render: write the PNGs here (default: not written)")
+    ap.add_argument("--project", action="store_true",
+                    help="also colour the atlas (8 texels a leg) of the density mesh at --ply-res and of each --simplify arm of it from "
+                         "posed pictures and render it from the held-out pose (DESIGN.md section 33): PSNR beside the vertex colours "
+                         "and the -normal texture, the share of texels seen, stage times, the depth_tol and cos_min sweeps")
+    ap.add_argument("--project-ring", type=int, default=16, metavar="N",
+                    help="--project: the denser ring of N poses the field is also rendered from")
     ap.add_argument("--smooth-lambda", type=float, default=0.5)
     ap.add_argument("--smooth-mu", type=float, default=-0.53, help="0: plain Laplacian smoothing")
     ap.add_argument("--ckpt", default=None, help="load this checkpoint instead of training")
@@ -558,15 +694,17 @@ def main():
     H = W = a.hw
     if a.ckpt:
         imgs, poses, K = torch.zeros(1, 8, 8, 4 if a.random_bg else 3), synthetic.train_poses(1), synthetic.intrinsics(8, 8)[0]
-        if a.tsdf or a.render:                               # the depth renders and the pictures need the cameras at full size
+        if a.tsdf or a.render or a.project:                  # the depth renders and the pictures need the cameras at full size
             imgs, poses, K = torch.zeros(1, H, W, imgs.shape[-1]), synthetic.train_poses(5)[:4], synthetic.intrinsics(H, W)[0]
-        if a.render:
+        if a.project:                                        # and the projective bake the training pictures themselves
+            imgs = torch.stack([synthetic.render_gt(H, W, p, device=dev, rgba=a.random_bg) for p in poses], 0)
+        if a.render or a.project:
             held_pose, held_gt = synthetic.train_poses(5)[4], synthetic.render_gt(H, W, synthetic.train_poses(5)[4], device=dev)
     else:
         imgs, poses, _, _, K = synthetic.make_dataset(H, W, 5, seed=0, device=dev, rgba=a.random_bg)
         held_pose, held_gt = poses[4], imgs[4]
         imgs, poses = imgs[:4], poses[:4]
-    if a.render and a.random_bg:                             # straight RGBA over the renderer's white
+    if (a.render or a.project) and a.random_bg:              # straight RGBA over the renderer's white
         held_gt = held_gt[..., :3] * held_gt[..., 3:] + (1.0 - held_gt[..., 3:])
     tr = NGPTrainer(imgs, poses, K, N_rand=a.n_rand, n_depth_samples=64, seed=4, device=dev, occupancy_grid=True,
                     march_steps=a.march_steps, distortion_weight=a.dist_weight, random_background=a.random_bg,
@@ -632,6 +770,17 @@ def main():
                 sm, srows, _ = mesh._simplify(m._replace(colors=None), G, lo, hi, "quadric", True)
                 sm = sm._replace(colors=mesh.vertex_colors(query, srows))
                 lines += _render_arms(tr, query, sm, f"density simplify {G}", R, a, rec, heldout, a.render_dir)
+                del sm, srows
+        if a.project and R == a.ply_res:
+            if a.random_bg:
+                raise SystemExit("--project needs RGB training pictures (not --random-bg)")
+            heldout = _heldout(tr, held_pose, held_gt[..., :3].to(dev).float(), a.reps)
+            train = (tr.images, tr.poses)
+            lines += _project_arms(tr, query, m, "density", R, a, rec, heldout, 2.0 * bound / R, train)
+            for G in a.simplify or []:
+                sm, srows, _ = mesh._simplify(m._replace(colors=None), G, lo, hi, "quadric", True)
+                sm = sm._replace(colors=mesh.vertex_colors(query, srows))
+                lines += _project_arms(tr, query, sm, f"density simplify {G}", R, a, rec, heldout, 2.0 * bound / R, train)
                 del sm, srows
         lines += _simplify_arms(m._replace(colors=None), "density", R, lo, hi, a, rec, bound, boxes)
         lines += _smooth_arms(m._replace(colors=None), "density", R, lo, hi, a, rec, bound, boxes)
@@ -747,6 +896,13 @@ def _raster_bytes(kernel, items):
     return {"raster_clear_kernel": 8, "raster_draw_kernel": 12, "raster_resolve_kernel": 8 + 20, "raster_shade_kernel": 12 + 12}[kernel] * items
 
 
+def _project_bytes(kernel, items, views):
+    """Algorithmic bytes of one csrc/project.hip launch over `items` atlas texels: accumulate reads and writes 16 B of state and, per
+    view that observes the texel, gathers two map values and four corners of three floats (all `views` here: an upper bound);
+    finish reads the state and writes three bytes and the seen flag (the fallback's three on top where there is one)."""
+    return {"project_accumulate_kernel": 32 + views * (8 + 48), "project_finish_kernel": 16 + 4}[kernel] * items
+
+
 def _morph_grid(kernel, R):
     """Work-items of a csrc/morph.hip launch at lattice size R."""
     words = -(-R // 64) * R * R
@@ -760,7 +916,7 @@ def _morph_grid(kernel, R):
 def stats(a):
     """Per mesh kernel and lattice size: mean device time per launch from a rocprofv3 --kernel-trace CSV, bytes / time."""
     import re
-    runs, tsdf_runs, renders = {}, {}, []
+    runs, tsdf_runs, renders, accumulate_log = {}, {}, [], []
     if a.from_:
         with open(a.from_) as fh:
             for ln in fh:
@@ -771,20 +927,23 @@ def stats(a):
                     tsdf_runs[r["R"]] = r
                 elif r.get("tool") == "ngp_mesh render":
                     renders.append(r)
+                elif r.get("tool") == "ngp_mesh project":
+                    accumulate_log.extend(tuple(x) for x in r.get("accumulate_launches", []))
     with open(a.stats) as fh:
         rows = list(csv.DictReader(fh))
     col = {k.lower(): k for k in rows[0]} if rows else {}
     name_k = col.get("kernel_name")
     s_k, e_k = col.get("start_timestamp"), col.get("end_timestamp")
     gx = col.get("grid_size_x", col.get("grid_size"))
-    groups, tex_items, raster_items = {}, {}, {}
+    groups, tex_items, raster_items, project_items = {}, {}, {}, {}
     # the draws of one mesh in launch order: the render lines of that mesh list the small_max of every draw launch they made
     draw_sm = {}
     for r in renders:
         draw_sm.setdefault(-(-r["F"] // BLOCK) * BLOCK, []).extend((r["F"], sm) for sm in r.get("draw_launch_small_max", []))
     draw_seen = {}
+    project_seen = 0
     for r in rows:
-        m = re.search(r"(mesh_\w+_kernel|ccl_\w+_kernel|morph_\w+_kernel|tsdf_\w+_kernel|simp_\w+_kernel|smooth_\w+_kernel|tex_\w+_kernel|raster_\w+_kernel|occ_cull_scan_kernel|occ_merge_exp_kernel)", r[name_k])
+        m = re.search(r"(mesh_\w+_kernel|ccl_\w+_kernel|morph_\w+_kernel|tsdf_\w+_kernel|simp_\w+_kernel|smooth_\w+_kernel|tex_\w+_kernel|raster_\w+_kernel|project_\w+_kernel|occ_cull_scan_kernel|occ_merge_exp_kernel)", r[name_k])
         if not m:
             continue
         k = m.group(1)
@@ -808,6 +967,15 @@ def stats(a):
             continue
         if k.startswith("tex_"):                       # chunked: pooled per kernel; one lane per texel, face or sample
             tex_items.setdefault(k, []).append(grid)
+        if k.startswith("project_"):                   # one lane per texel; pooled per kernel, or apart by the run's launch log
+            if k == "project_accumulate_kernel" and accumulate_log:
+                i = project_seen
+                project_seen += 1
+                if i < len(accumulate_log) and -(-accumulate_log[i][1] // BLOCK) * BLOCK == grid:
+                    k = "%s views=%d texels=%d" % (k, *accumulate_log[i])
+            project_items.setdefault(k, []).append(grid)
+            groups.setdefault((k, None), []).append((int(r[e_k]) - int(r[s_k])) * 1e-3)
+            continue
         if k.startswith(("simp_", "smooth_")):         # sized by the mesh: one lane per vertex or face of the run at R; else pooled
             R = next((R for R, run in runs.items() if grid in (-(-run["V"] // BLOCK) * BLOCK, -(-run["F"] // BLOCK) * BLOCK)), None)
         elif k.startswith("tex_") or k in ("mesh_points_kernel", "occ_merge_exp_kernel", "occ_cull_scan_kernel", "ccl_finish_kernel"):
@@ -827,6 +995,9 @@ def stats(a):
         if k in tex_items:
             rec["items"] = int(np.median(tex_items[k]))
             b = _texture_bytes(k, rec["items"])
+        elif k in project_items:                       # (accumulate's gathers depend on the views: the tool's own lines have them)
+            rec["items"] = int(np.median(project_items[k]))
+            b = _project_bytes(k, rec["items"], 0) if k == "project_finish_kernel" else None
         elif k in raster_items:
             rec["items"] = int(np.median(raster_items[k]))
             b = _raster_bytes(k.split()[0], rec["items"])
