@@ -906,8 +906,9 @@ int nerf_smooth_normals(const float* verts, int64_t V, const float* lo_host, con
  *                          bary [n, 2] = (wb, wc); verts, normals and faces are read for the rows only.
  * No atomics, no workspace, no host read; every output element has one writer: bit-reproducible.  Out of range: NERF_E_SHAPE;
  * NULL: NERF_E_NULL; all argument checks run before any device work.  count = 0, n = 0, F = 0 (uv): nothing is launched.
- * Not done: no mipmaps (the atlas is safe for bilinear filtering at level 0 only), no chart packing by area (every face gets the
- * same texels whatever its size), no seam handling across face edges beyond the shared field.                                    */
+ * Not done: no mipmaps in this section (one atlas is safe for bilinear filtering at level 0 only; "texture mip pyramid" builds
+ * the coarser levels), no chart packing by area (every face gets the same texels whatever its size), no seam handling across
+ * face edges beyond the shared field.                                                                                            */
 #define NERF_TEXTURE_MAX_SIDE 16384
 int nerf_texture_layout(int64_t F, int texels, int64_t* out_host);
 int nerf_texture_rows(const float* verts, const float* normals, int64_t V, const int32_t* faces, int64_t F, int texels, int64_t p0,
@@ -975,7 +976,8 @@ int nerf_texture_sample(const uint8_t* image, const float* verts, const float* n
  * Out of range: NERF_E_SHAPE; NULL: NERF_E_NULL; all argument checks run before any device work; nothing is read on the host.
  * Not done: no near-plane clipping (a face with a vertex in front of `near` is dropped: the project's cameras stand outside
  * the scene box), no antialiasing or supersampling (one sample at the pixel centre, like one ray per pixel), no mipmapped
- * texture lookups, no tile binning for screen-filling faces, no transparency.                                                   */
+ * texture lookups in these calls (nerf_mip_sample of "texture mip pyramid" has them), no tile binning for screen-filling
+ * faces, no transparency.                                                                                                        */
 #define NERF_RASTER_SMALL_MAX 16
 int nerf_raster_clear(uint64_t* keys, int H, int W, uint64_t* stats, void* stream);
 int nerf_raster_draw(const float* verts, int64_t V, const int32_t* faces, int64_t F, int64_t face_base,
@@ -1050,6 +1052,62 @@ int nerf_project_accumulate(const float* verts, const float* normals, int64_t V,
                             float* state, void* stream);
 int nerf_project_finish(const float* state, int64_t F, int texels, int64_t p0, int64_t count, int mode, const uint8_t* fallback,
                         uint8_t* image, uint8_t* seen, void* stream);
+
+/* ---------------------------------------------------------------- texture mip pyramid (no reference counterpart)
+ * Coarser levels for the atlas of "texture atlas", a level of detail per face from its footprint on the screen, and a trilinear
+ * lookup through both: a face that covers one pixel is read from the level whose texels are about a pixel wide, not point-sampled
+ * from level 0.  The filter is per face, because neighbouring cells of the atlas belong to unrelated faces.  Additive:
+ * NERF_ABI_VERSION stays 3.  All float steps are IEEE float32, one rounding per operation (no contraction), in exactly the order
+ * and grouping written here; a / b and sqrt are correctly rounded.  csrc/mip.h states the rule in code; tests/_mip_ref.py
+ * reproduces every output bit for bit.
+ *   levels    T_0 = T; T_{l+1} = (T_l + 1) / 2 in integers while T_l > 2: 8 -> 8, 4, 2; 9 -> 9, 5, 3, 2; 64 -> 64, 32, 16, 8, 4, 2;
+ *             2 -> 2.  At most NERF_MIP_MAX_LEVELS.  Level l is a complete atlas of the same F faces: the layout of "texture
+ *             atlas" at T_l texels, the UVs of nerf_texture_uv(F, T_l); nerf_texture_sample takes any level unchanged.
+ *   reduce    level l (fine: T, S = T + 2) -> level l + 1 (coarse: T', S'), one lane per coarse atlas texel: its face f and local
+ *             texel (i, j) by the coarse layout; a texel whose face is >= F is black.  Only the fine image is read, never the mesh.
+ *             In-triangle texels, i + j <= T' - 1: x = (float)(i (T - 1)) / (float)(T' - 1), y likewise from j;
+ *             r = (float)(T - 1) / (float)(T' - 1), d = 0.25f r; c = lookup(x, y), the bilinear lookup of `sample` in "texture
+ *             atlas" at the local texel coordinates (x, y) of face f.  Four antipodal tap pairs (x, y) +- o with the offsets
+ *             o = (d, 0), (0, d), (d, d), (d, -d).  A pair counts only if both of its taps (ax, ay) lie in the closed triangle
+ *             ax >= 0, ay >= 0, ax + ay <= (float)(T - 1), the sum taken in float32; it then contributes p = lookup(a) + lookup(b),
+ *             any other pair p = c + c.  Per channel value = ((p0 + p1) + (p2 + p3)) 0.125f and byte = (uint8)rint(255 unit(value))
+ *             as nerf_texture_store.  The centroid of the taps is the texel's own point and every lookup interpolates inside the
+ *             face: a constant is kept exactly, an affine field up to rounding, and no read leaves the face's texels.
+ *             Gutter texels, the diagonals i + j = T' and then T' + 1, by planar extrapolation of the coarse bytes in integers:
+ *             g(i, j) = v(i - 1, j) + v(i, j - 1) - v(i - 1, j - 1) for i, j >= 1; g(i, 0) = 2 v(i - 1, 0) - v(i - 2, 0);
+ *             g(0, j) = 2 v(0, j - 1) - v(0, j - 2); clamped to [0, 255]; the second diagonal uses the clamped first.  (Taps that
+ *             extrapolate past the hypotenuse instead compound the 8-bit noise from level to level and are not used.)
+ *   lod       per face: the snapped face of "mesh rendering" without culling; a dropped face has lod 0.  S = |D| in int64;
+ *             g = scale (sqrt((float)S) / 256.0f), the leg in pixels of the right isosceles triangle with the face's screen area;
+ *             level l puts T_l - 1 texel steps on it.  lod = 0 with one level or g >= T_0 - 1; lod = L - 1 if g <= T_{L-1} - 1; else
+ *             with the l for which T_{l+1} - 1 <= g < T_l - 1: lod = (float)l + ((float)(T_l - 1) - g) / (float)(T_l - T_{l+1}).
+ *             Linear in g, no logarithm; isotropic and constant over a face.
+ *   sample    lod' = lod clamped to [0, L - 1], NaN -> 0; l = (int)floor(lod'), t = lod' - (float)l; (wb, wc) clamped as `sample`
+ *             of "texture atlas"; c_l = lookup on level l at (wb (float)(T_l - 1), wc (float)(T_l - 1)); rgb = c_l when t == 0, else
+ *             ((1.0f - t) c_l) + (t c_{l+1}) per channel.  A face outside [0, F) reads black.
+ * Calls:
+ *   nerf_mip_levels    host only: out = {L, T_0, ..., T_{L-1}, 0 ...}, int32 [1 + NERF_MIP_MAX_LEVELS].  Needs no device.
+ *   nerf_mip_reduce    the texels [p0, p0 + count) of the coarse atlas (T' = (texels_fine + 1) / 2) in raster order from the fine
+ *                      image; other texels are not touched, a gutter lane recomputes the in-triangle bytes it needs: the image
+ *                      depends on neither the chunk nor the launch shape.  texels_fine in [3, 64].
+ *   nerf_mip_lod       lod [F] float32 for the camera (a nerf_tsdf_view on the host, 16 finite floats), near finite and > 0, scale
+ *                      finite and > 0, over a pyramid of `texels` at level 0.  One lane per face.  F = 0 launches nothing.
+ *   nerf_mip_sample    rgb [n, 3] of n < 2^31 samples face [n] int32, bary [n, 2]; images is a HOST array of the L device
+ *                      pointers of the levels of a pyramid over `texels`, handed to the kernel by value; lod is [F] and read at
+ *                      the sample's face with per_face = 1, else [n].  n = 0 launches nothing.
+ * No atomics, no workspace, no host read; every output element has one writer: bit-reproducible.  Out of range (F or V outside
+ * [0, 2^24], texels outside [2, 64], a chunk that leaves the atlas, a scale or near that is not finite and > 0, a non-finite
+ * camera): NERF_E_SHAPE; NULL: NERF_E_NULL; all argument checks run before any device work.
+ * Not done: no anisotropic or per-pixel footprints (one isotropic lod per face), no filtering of the source pictures in
+ * nerf_project_accumulate, no chart packing by area, no seam levelling, no push-pull inpainting of unseen texels over the
+ * pyramid, no supersampled coverage, no pyramid inside the OBJ (write_obj writes level 0).                                       */
+#define NERF_MIP_MAX_LEVELS 6
+int nerf_mip_levels(int texels, int32_t* out_host);
+int nerf_mip_reduce(const uint8_t* fine, int64_t F, int texels_fine, uint8_t* coarse, int64_t p0, int64_t count, void* stream);
+int nerf_mip_lod(const float* verts, int64_t V, const int32_t* faces, int64_t F, const nerf_tsdf_view* view_host, float near,
+                 int texels, float scale, float* lod, void* stream);
+int nerf_mip_sample(const uint8_t* const* images_host, int64_t F, int texels, const int32_t* face, const float* bary,
+                    const float* lod, int per_face, int64_t n, float* rgb, void* stream);
 
 /* ---------------------------------------------------------------- gradient all-reduce (no reference
  * counterpart: the reference is single-device).  RCCL over xGMI, one in-place float32 sum of the flat gradient

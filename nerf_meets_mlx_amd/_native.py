@@ -132,6 +132,10 @@ SIGNATURES = {
     "nerf_project_accumulate": (_I, [_P, _P, _I64, _P, _I64, _I, _I64, _I64, C.POINTER(C.c_float), _I, _I, _I, _P, _P, _P, _F, _F, _F, _F,
                                     _I, _P, _P]),
     "nerf_project_finish": (_I, [_P, _I64, _I, _I64, _I64, _I, _P, _P, _P, _P]),
+    "nerf_mip_levels": (_I, [_I, C.POINTER(C.c_int32)]),
+    "nerf_mip_reduce": (_I, [_P, _I64, _I, _P, _I64, _I64, _P]),
+    "nerf_mip_lod": (_I, [_P, _I64, _P, _I64, C.POINTER(C.c_float), _F, _I, _F, _P, _P]),
+    "nerf_mip_sample": (_I, [C.POINTER(C.c_void_p), _I64, _I, _P, _P, _P, _I, _I64, _P, _P]),
 }
 
 

@@ -9,7 +9,8 @@
 //            ((w00 c00 + w10 c10) + w01 c01) + w11 c11 with w00 = (1 - fx)(1 - fy), w10 = fx (1 - fy), w01 = (1 - fx) fy,
 //            w11 = fx fy and c = (float)byte / 255.0f, every operation rounded to float32 on its own
 // The layout helpers compile for host and device; the host checks use nerf::fail through NERF_REQUIRE.  The device part below them
-// (a texel's face, barycentrics, position and normal) is shared by texture.hip and project.hip, which therefore see the same texel.
+// (a texel's face, barycentrics, position and normal) is shared by texture.hip and project.hip, which therefore see the same texel;
+// the bilinear lookup is shared by texture.hip and mip.hip, which therefore read the same colour.
 #pragma once
 #include "lattice.h"
 
@@ -127,6 +128,29 @@ __device__ __forceinline__ bool tex_texel(const TexLayout& lay, const int* __res
   *wb = div_rn((float)i, d);
   *wc = div_rn((float)j, d);
   return true;
+}
+
+// the bilinear `lookup` of the header at the local texel coordinates (x, y) of face f (inside [0, F)): rgb into out[3].  The one
+// copy: tex_sample_kernel calls it at (wb (T - 1), wc (T - 1)), mip.hip at its taps and on every level of a pyramid.
+__device__ __forceinline__ void tex_lookup(const uint8_t* __restrict__ image, const TexLayout& lay, int f, float x, float y, float* out) {
+  const int i0 = min(max((int)floorf(x), 0), lay.S - 2), j0 = min(max((int)floorf(y), 0), lay.S - 2);
+  const float fx = x - (float)i0, fy = y - (float)j0;
+  const float gx = 1.0f - fx, gy = 1.0f - fy;
+  const float w[4] = {gx * gy, fx * gy, gx * fy, fx * fy};
+  const uint8_t* t[4];
+#pragma unroll
+  for (int k = 0; k < 4; ++k) {
+    int X, Y;
+    tex_place(lay, f, i0 + (k & 1), j0 + (k >> 1), &X, &Y);
+    t[k] = image + 3 * ((int64_t)Y * lay.W + X);
+  }
+#pragma unroll
+  for (int ch = 0; ch < 3; ++ch) {
+    float c[4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) c[k] = div_rn((float)t[k][ch], 255.0f);
+    out[ch] = ((w[0] * c[0] + w[1] * c[1]) + w[2] * c[2]) + w[3] * c[3];
+  }
 }
 #endif
 

@@ -7,8 +7,8 @@
 //   store    one lane per texel: one 16-byte load of raw, three byte stores.  Packing four texels a lane into one 12-byte store
 //            measured slower and is not shipped.
 //   uv       one lane per face, 24 bytes.
-//   sample   one lane per surface sample: a bilinear lookup in the face's own texels, and optionally the query row of the very
-//            point, by the device function of the rows kernel.
+//   sample   one lane per surface sample: a bilinear lookup in the face's own texels (tex_lookup of texture.h, which mip.hip
+//            shares), and optionally the query row of the very point, by the device function of the rows kernel.
 #include "texture.h"
 
 namespace nerf {
@@ -100,25 +100,8 @@ __global__ void __launch_bounds__(TEX_BLOCK) tex_sample_kernel(const uint8_t* __
     wc = wc < hi ? wc : hi;
     float out[3] = {0.0f, 0.0f, 0.0f};
     if (f >= 0 && f < lay.F) {
-      const float d = (float)(lay.T - 1), x = wb * d, y = wc * d;
-      const int i0 = min(max((int)floorf(x), 0), lay.S - 2), j0 = min(max((int)floorf(y), 0), lay.S - 2);
-      const float fx = x - (float)i0, fy = y - (float)j0;
-      const float gx = 1.0f - fx, gy = 1.0f - fy;
-      const float w[4] = {gx * gy, fx * gy, gx * fy, fx * fy};
-      const uint8_t* t[4];
-#pragma unroll
-      for (int k = 0; k < 4; ++k) {
-        int X, Y;
-        tex_place(lay, f, i0 + (k & 1), j0 + (k >> 1), &X, &Y);
-        t[k] = image + 3 * ((int64_t)Y * lay.W + X);
-      }
-#pragma unroll
-      for (int ch = 0; ch < 3; ++ch) {
-        float c[4];
-#pragma unroll
-        for (int k = 0; k < 4; ++k) c[k] = div_rn((float)t[k][ch], 255.0f);
-        out[ch] = ((w[0] * c[0] + w[1] * c[1]) + w[2] * c[2]) + w[3] * c[3];
-      }
+      const float d = (float)(lay.T - 1);
+      tex_lookup(image, lay, f, wb * d, wc * d, out);
     }
 #pragma unroll
     for (int ch = 0; ch < 3; ++ch) rgb[3 * s + ch] = out[ch];

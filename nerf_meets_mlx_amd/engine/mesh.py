@@ -37,6 +37,10 @@ section 14).  The reference has no such export; this is Instant-NGP's.
   * `project_texture(mesh, images, c2w, K, texels, depth_tol)` colours the same atlas from posed pictures: every texel takes what
     the views saw of it where the mesh's own depth map of the view says it is visible, blended by the cosine or from the best
     view, and a fallback texture elsewhere (include/nerf_hip.h "view-projected texture").
+  * `build_mipmaps(texture, mesh)` reduces an atlas face by face into a `TexturePyramid` of complete textures, `face_lod` gives
+    every face a level of detail from its footprint on a camera's screen, and `sample_texture_mip` / `render_mesh_mip` look the
+    pyramid up trilinearly, so a face that covers one pixel is not point-sampled from 45 texels (include/nerf_hip.h "texture mip
+    pyramid").
   * `write_ply` writes a binary little-endian PLY; `write_obj` an OBJ with its .mtl and the atlas as a .png, which a PLY cannot
     carry.
 """
@@ -67,6 +71,7 @@ TEXTURE_MAX_SIDE = 16384     # NERF_TEXTURE_MAX_SIDE
 RASTER_MAX_SIDE = 16384      # image height and width of the mesh renderer
 RASTER_SMALL_MAX = 16        # NERF_RASTER_SMALL_MAX
 RASTER_NEAR = 0.01           # the mesh renderer's default near plane
+MIP_MAX_LEVELS = 6           # NERF_MIP_MAX_LEVELS: levels of a texture pyramid
 PROJECT_MAX_VIEWS = 16       # NERF_PROJECT_MAX_VIEWS: views per launch of the projective bake
 PROJECT_MODES = {"blend": 0, "best": 1}   # NERF_PROJECT_BLEND / NERF_PROJECT_BEST
 PROJECT_COS_MIN = 0.05       # the projective bake's default grazing limit: the best of the sweep of DESIGN.md section 33
@@ -889,6 +894,148 @@ def render_mesh(mesh: Mesh, c2w, K, H: int, W: int, texture: Optional[Texture] =
     _mark(mark, "shade")
     N.check(N.lib().nerf_raster_shade(N.ptr(face), N.ptr(bary), N.ptr(mesh.faces), V, F, None if texture is not None else N.ptr(mesh.colors),
                                       N.ptr(looked_up), N.ptr(bg), per_pixel, H, W, N.ptr(rgb), N.stream()))
+    return MeshFrame(rgb, depth, acc, face, bary)
+
+
+class TexturePyramid(NamedTuple):
+    levels: tuple                         # of Texture: levels[0] the atlas itself, levels[l] at mip_levels(texels)[l] texels a leg
+
+
+def mip_levels(texels: int) -> tuple:
+    """(T_0, ..., T_{L-1}): the texels per triangle leg of the levels of a pyramid over an atlas of `texels` (nerf_mip_levels; no
+    device needed): T_{l+1} = (T_l + 1) // 2 while T_l > 2, at most MIP_MAX_LEVELS.  ValueError for texels outside
+    [2, TEXTURE_MAX_TEXELS]."""
+    if isinstance(texels, bool) or not isinstance(texels, numbers.Integral):
+        raise ValueError(f"mip texels must be an int in [2, {TEXTURE_MAX_TEXELS}], got {texels!r}")
+    out = (C.c_int32 * (1 + MIP_MAX_LEVELS))()
+    N.check(N.lib().nerf_mip_levels(int(texels), out))
+    return tuple(int(x) for x in out[1:1 + out[0]])
+
+
+def build_mipmaps(texture: Texture, mesh: Mesh, chunk: int = CHUNK, mark=None) -> TexturePyramid:
+    """The mip pyramid of `texture` (bake_texture's or project_texture's) of `mesh` (include/nerf_hip.h "texture mip pyramid",
+    DESIGN.md section 34): level l + 1 is reduced from level l face by face, nine bilinear taps inside the face's own triangle per
+    texel and gutters extrapolated from the coarse bytes, so every level is a complete Texture that sample_texture, render_mesh
+    and write_obj take unchanged.  levels[0] is `texture` itself.  `chunk` coarse texels per launch of nerf_mip_reduce (the images
+    do not depend on it), then nerf_texture_uv once per level; no host read.  F = 0: black cells, nothing is launched.  mark:
+    _mark's hook ("reduce" and "uv" once per level, in that order)."""
+    T, _ = _check_texture("build_mipmaps", texture, mesh)
+    dev, F = mesh.verts.device, mesh.faces.shape[0]
+    L = N.lib()
+    levels = [texture]
+    for Tl in mip_levels(T)[1:]:
+        W, H, _, _ = texture_layout(F, Tl)
+        uv = torch.empty(F, 3, 2, dtype=torch.float32, device=dev)
+        if F == 0:
+            levels.append(Texture(torch.zeros(H, W, 3, dtype=torch.uint8, device=dev), uv, Tl))
+            continue
+        fine = levels[-1]
+        image = torch.empty(H, W, 3, dtype=torch.uint8, device=dev)
+        P = W * H
+        step = max(1, min(int(chunk), P))
+        _mark(mark, "reduce")
+        for p0 in range(0, P, step):
+            N.check(L.nerf_mip_reduce(N.ptr(fine.image), F, fine.texels, N.ptr(image), p0, min(step, P - p0), N.stream()))
+        _mark(mark, "uv")
+        N.check(L.nerf_texture_uv(F, Tl, N.ptr(uv), N.stream()))
+        levels.append(Texture(image, uv, Tl))
+    return TexturePyramid(tuple(levels))
+
+
+def _check_pyramid(who, pyramid, mesh):
+    """The texels of level 0 of a TexturePyramid that belongs to `mesh`: every level a Texture of the mesh (_check_texture) and
+    their texels the chain mip_levels(levels[0].texels)."""
+    if not isinstance(pyramid, TexturePyramid) or not isinstance(pyramid.levels, tuple) or not pyramid.levels:
+        raise ValueError(f"{who}: need an engine.mesh.TexturePyramid with at least one level, got {type(pyramid).__name__}")
+    for level in pyramid.levels:
+        _check_texture(who, level, mesh)
+    chain = mip_levels(pyramid.levels[0].texels)
+    if tuple(level.texels for level in pyramid.levels) != chain:
+        raise ValueError(f"{who}: the levels must have {chain} texels a leg, got {tuple(level.texels for level in pyramid.levels)}")
+    return chain[0]
+
+
+def check_lod_scale(scale) -> float:
+    """`scale` as a float; ValueError unless it is a finite number > 0 (as a float32)."""
+    ok = not isinstance(scale, bool) and isinstance(scale, numbers.Real) and math.isfinite(float(scale))
+    if ok:
+        with np.errstate(over="ignore"):
+            ok = 0.0 < float(np.float32(scale)) < math.inf
+    if not ok:
+        raise ValueError(f"mip lod scale must be a finite number > 0, got {scale!r}")
+    return float(scale)
+
+
+def face_lod(mesh: Mesh, c2w, K, near: float = RASTER_NEAR, texels: int = 8, scale: float = 1.0) -> torch.Tensor:
+    """float32 [F]: the level of detail of every face of `mesh` in a pyramid over `texels` texels a leg, seen by the camera of
+    `rasterize` (nerf_mip_lod): with g = scale * the leg in pixels of the right isosceles triangle that has the area of the
+    rasteriser's snapped face, 0 where g >= texels - 1 (a texel of level 0 per pixel or fewer), rising linearly in g from level
+    to level, L - 1 at the last one; 0 for a face the rasteriser drops.  scale > 1 sharpens, < 1 blurs.  No host read; F = 0:
+    nothing is launched."""
+    _check_mesh_tensors("face_lod", mesh)
+    _, _, near, _, _ = check_raster_args(1, 1, near)
+    mip_levels(texels)
+    scale = check_lod_scale(scale)
+    view, _keep = _raster_view(c2w, K)
+    dev, V, F = mesh.verts.device, mesh.verts.shape[0], mesh.faces.shape[0]
+    lod = torch.empty(F, dtype=torch.float32, device=dev)
+    if F:
+        N.check(N.lib().nerf_mip_lod(N.ptr(mesh.verts), V, N.ptr(mesh.faces), F, view, near, int(texels), scale, N.ptr(lod), N.stream()))
+    return lod
+
+
+def sample_texture_mip(pyramid: TexturePyramid, mesh: Mesh, face: torch.Tensor, bary: torch.Tensor, lod: torch.Tensor,
+                       per_face: bool = False) -> torch.Tensor:
+    """rgb float32 [n, 3]: the trilinear lookup of the pyramid at the surface samples (face, bary) of sample_texture and the level
+    of detail `lod`, float32 [n], or with per_face [F] and read at the sample's face (face_lod's).  lod is clamped to [0, L - 1]
+    (NaN reads level 0); an integral lod is exactly sample_texture on that level; a face outside [0, F) reads black
+    (nerf_mip_sample)."""
+    T = _check_pyramid("sample_texture_mip", pyramid, mesh)
+    dev, F = mesh.verts.device, mesh.faces.shape[0]
+    if not isinstance(per_face, bool):
+        raise ValueError(f"sample_texture_mip: per_face must be a bool, got {per_face!r}")
+    if not torch.is_tensor(face) or face.dtype != torch.int32 or face.dim() != 1 or not face.is_contiguous() or face.device != dev:
+        raise ValueError("sample_texture_mip: face must be a contiguous int32 [n] tensor on the vertices' device")
+    n = face.shape[0]
+    if not torch.is_tensor(bary) or bary.dtype != torch.float32 or tuple(bary.shape) != (n, 2) or not bary.is_contiguous() \
+            or bary.device != dev:
+        raise ValueError(f"sample_texture_mip: bary must be a contiguous float32 [{n}, 2] tensor on the vertices' device")
+    m = F if per_face else n
+    if not torch.is_tensor(lod) or lod.dtype != torch.float32 or tuple(lod.shape) != (m,) or not lod.is_contiguous() or lod.device != dev:
+        raise ValueError(f"sample_texture_mip: lod must be a contiguous float32 [{m}] tensor on the vertices' device")
+    rgb = torch.empty(n, 3, dtype=torch.float32, device=dev)
+    if n and F == 0:
+        rgb.zero_()
+    elif n:
+        images = (C.c_void_p * len(pyramid.levels))(*[level.image.data_ptr() for level in pyramid.levels])
+        N.check(N.lib().nerf_mip_sample(images, F, T, N.ptr(face), N.ptr(bary), N.ptr(lod), int(per_face), n, N.ptr(rgb), N.stream()))
+    return rgb
+
+
+def render_mesh_mip(mesh: Mesh, c2w, K, H: int, W: int, pyramid: TexturePyramid, background=None, near: float = RASTER_NEAR,
+                    cull_backfaces: bool = False, mark=None, small_max: int = RASTER_SMALL_MAX, lod_scale: float = 1.0) -> MeshFrame:
+    """render_mesh through a mip pyramid: rasterize, face_lod(scale=lod_scale) for the same camera, the
+    trilinear lookup of sample_texture_mip at every pixel's (face, bary) with its face's level of detail, nerf_raster_shade.
+    face, bary, depth and acc are render_mesh's; where every lod is 0 so is rgb.  mark: rasterize's stages, then "lod",
+    "texture" and "shade"."""
+    _check_mesh_tensors("render_mesh_mip", mesh)
+    H, W, near, cull_backfaces, small_max = check_raster_args(H, W, near, cull_backfaces, small_max)
+    T = _check_pyramid("render_mesh_mip", pyramid, mesh)
+    lod_scale = check_lod_scale(lod_scale)
+    dev, V, F = mesh.verts.device, mesh.verts.shape[0], mesh.faces.shape[0]
+    bg, per_pixel = _raster_background(background, H, W, dev)
+    face, bary, depth, acc, _ = rasterize(mesh, c2w, K, H, W, near, cull_backfaces, mark, small_max)
+    if F == 0:
+        rgb = (bg.reshape(H, W, 3) if per_pixel else bg.expand(H, W, 3)).clone()
+        return MeshFrame(rgb, depth, acc, face, bary)
+    _mark(mark, "lod")
+    lod = face_lod(mesh, c2w, K, near, T, lod_scale)
+    _mark(mark, "texture")
+    looked_up = sample_texture_mip(pyramid, mesh, face.reshape(-1), bary.reshape(-1, 2), lod, per_face=True)
+    rgb = torch.empty(H, W, 3, dtype=torch.float32, device=dev)
+    _mark(mark, "shade")
+    N.check(N.lib().nerf_raster_shade(N.ptr(face), N.ptr(bary), N.ptr(mesh.faces), V, F, None, N.ptr(looked_up), N.ptr(bg), per_pixel,
+                                      H, W, N.ptr(rgb), N.stream()))
     return MeshFrame(rgb, depth, acc, face, bary)
 
 

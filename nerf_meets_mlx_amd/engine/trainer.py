@@ -304,6 +304,25 @@ class Trainer:
         mse = torch.mean((img - gt.to(self.device)) ** 2)
         return float(10.0 * torch.log10(1.0 / mse))
 
+    def mip_texture(self, mesh, texture):
+        """engine.mesh.TexturePyramid over `texture` (texture_mesh's or project_texture's) of `mesh`: the atlas itself as level 0
+        and its per-face reductions below it (engine.mesh.build_mipmaps).  This rank only."""
+        from .mesh import build_mipmaps
+        return build_mipmaps(texture, mesh)
+
+    def render_mesh_mip(self, mesh, c2w, pyramid, background=None, lod_scale: float = 1.0):
+        """render_mesh through a TexturePyramid: every face is looked up trilinearly at the level of detail of its footprint on
+        this trainer's H x W screen (engine.mesh.render_mesh_mip).  This rank only."""
+        from .mesh import render_mesh_mip
+        return render_mesh_mip(mesh, c2w, self.K, self.H, self.W, pyramid, background=background, near=float(self.near),
+                               lod_scale=lod_scale)
+
+    def mesh_psnr_mip(self, mesh, c2w, gt: torch.Tensor, pyramid, background=None, lod_scale: float = 1.0) -> float:
+        """mesh_psnr of render_mesh_mip's picture.  This rank only."""
+        img = self.render_mesh_mip(mesh, c2w, pyramid, background=background, lod_scale=lod_scale).rgb
+        mse = torch.mean((img - gt.to(self.device)) ** 2)
+        return float(10.0 * torch.log10(1.0 / mse))
+
     # ---------------------------------------------------------------- checkpoint (SURVEY 8f-3)
     def _checkpoint_buffers(self):
         """name -> object with `.params` (flat fp32 device buffer) and `.load_flat(t)`; the names are also the Adam keys."""

@@ -58,6 +58,12 @@ and the cos_min sweep {0.05, 0.1, 0.3}; and the accumulate stage of sixteen view
 per view.  The last line of a mesh lists the views and texels of every accumulate launch in order, by which --stats --from tells
 the launches of a kernel trace apart.
 
+With --mip (beside --render and --texture T or --project), for the same meshes, the mip pyramid of DESIGN.md section 34 over the
+-normal texture of each --texture T and, with --project, over the atlas coloured from the training frames (8 texels, blend): the
+device ms of bake_texture beside the pyramid's reduce and uv per level, the pyramid's bytes beside level 0's, the stage ms of the
+level-0 render and of the mip render (its lod and lookup stages among them), the PSNR of both pictures from the held-out pose,
+and the histogram of floor(lod) over the faces the picture sees.  Without --mip nothing changes.
+
     rocprofv3 --kernel-trace --output-format csv -d DIR -o mesh -- python tools/ngp_mesh.py --ckpt /tmp/ngp.npz --reps 1 --no-ply
     python tools/ngp_mesh.py --stats DIR/.../mesh_kernel_trace.csv --from profiles/ngp_mesh.jsonl --out profiles/ngp_mesh_kernels.jsonl
 
@@ -546,6 +552,79 @@ def _project_arms(tr, query, m, source, R, a, rec, heldout, h, train):
     return out
 
 
+def _mip_arms(tr, query, m, source, R, a, rec, heldout, h, train):
+    """The mip pyramid of DESIGN.md section 34 on the coloured mesh `m`: one JSON line per atlas (the -normal texture of each
+    --texture T, and with --project the atlas coloured from the training pictures at T = 8), each with the device ms of
+    bake_texture beside the pyramid's reduce per level and uv, the bytes of the pyramid beside level 0's, the device ms of the
+    level-0 render and of the mip render by stage (lod and lookup among them), the PSNR of both pictures from the held-out pose and
+    the histogram of floor(lod) over the faces the picture sees."""
+    from nerf_meets_mlx_amd.engine import mesh
+    out = []
+    F = int(m.faces.shape[0])
+    if F == 0:
+        return out
+    pose, gt, field_rgb, _ = heldout
+    near = float(tr.near)
+    atlases = [("-normal texture", T) for T in (a.texture or [])]
+    if a.project:
+        atlases.append(("project images blend", 8))
+    for name, T in atlases:
+        ts = []
+        for _ in range(a.reps + 1):                                       # (the first run warms)
+            st = _Stages()
+            tex = mesh.bake_texture(query, m, T, mark=st)
+            st("end")
+            ts.append(sum(st.total_ms().values()))
+        line = {"tool": "ngp_mesh mip", "source": source, "R": R, "atlas": name, "texels": T, "hw": tr.H, "iters": rec["iters"],
+                "seed": rec["seed"], "V": int(m.verts.shape[0]), "F": F, "device": rec["device"], "bake_texture_ms": float(np.mean(ts[1:]))}
+        if name != "-normal texture":
+            tex, _ = mesh.project_texture(m, train[0], train[1][:, :3, :4], tr.K, texels=T, depth_tol=mesh.PROJECT_DEPTH_TOL_CELLS * h,
+                                          mode="blend", fallback=tex, near=near)
+        levels = mesh.mip_levels(T)
+        ts = []
+        for _ in range(a.reps + 1):
+            st = _Stages()
+            pyr = mesh.build_mipmaps(tex, m, mark=st)
+            st("end")
+            torch.cuda.synchronize()                                      # ("reduce" and "uv" come once per level: in order)
+            ts.append([st.events[i].elapsed_time(st.events[i + 1]) for i in range(len(st.names) - 1)])
+        mean = np.mean(np.array(ts[1:]), 0) if len(levels) > 1 else np.zeros(0)
+        line.update({"levels": list(levels), "reduce_ms": [float(x) for x in mean[0::2]], "uv_ms": [float(x) for x in mean[1::2]],
+                     "pyramid_ms": float(mean.sum()), "level0_bytes": int(tex.image.numel()),
+                     "pyramid_bytes": int(sum(t.image.numel() for t in pyr.levels)),
+                     "coarse_texels": [int(t.image.numel() // 3) for t in pyr.levels[1:]]})
+        stages0 = ("clear", "draw", "resolve", "texture", "shade")
+        stages1 = ("clear", "draw", "resolve", "lod", "texture", "shade")
+        t0, t1 = [], []
+        for _ in range(a.reps + 1):
+            st = _Stages()
+            plain = mesh.render_mesh(m, pose, tr.K, tr.H, tr.W, texture=tex, near=near, mark=st)
+            st("end")
+            t0.append(st.ms())
+            st = _Stages()
+            fr = mesh.render_mesh_mip(m, pose, tr.K, tr.H, tr.W, pyr, near=near, mark=st)
+            st("end")
+            t1.append(st.ms())
+        line.update({f"level0_{k}_ms": float(np.mean([t[k] for t in t0[1:]])) for k in stages0})
+        line.update({f"mip_{k}_ms": float(np.mean([t[k] for t in t1[1:]])) for k in stages1})
+        line["level0_render_ms"] = float(sum(line[f"level0_{k}_ms"] for k in stages0))
+        line["mip_render_ms"] = float(sum(line[f"mip_{k}_ms"] for k in stages1))
+        lod = mesh.face_lod(m, pose, tr.K, near, T)
+        seen = torch.unique(fr.face[fr.face >= 0]).long()
+        hist = torch.bincount(torch.floor(lod[seen]).long(), minlength=len(levels)).tolist()
+        line.update({"seen_faces": int(seen.numel()), "covered_pixels": int((fr.face >= 0).sum()), "floor_lod_histogram": hist,
+                     "mean_lod": float(lod[seen].mean()) if seen.numel() else None,
+                     "level0_psnr_vs_heldout_db": _psnr(plain.rgb - gt)["psnr_db"], "mip_psnr_vs_heldout_db": _psnr(fr.rgb - gt)["psnr_db"],
+                     "level0_psnr_vs_field_db": _psnr(plain.rgb - field_rgb)["psnr_db"],
+                     "mip_psnr_vs_field_db": _psnr(fr.rgb - field_rgb)["psnr_db"],
+                     "same_visibility": bool(torch.equal(fr.face, plain.face) and torch.equal(fr.depth, plain.depth))})
+        print(json.dumps(line), flush=True)
+        out.append(line)
+        del tex, pyr, fr, plain
+    torch.cuda.empty_cache()
+    return out
+
+
 def _heldout(tr, pose, gt, reps):
     """(pose, gt [H, W, 3], the field's render_frame, its device ms: the mean of `reps` runs behind a warm-up)."""
     ts = []
@@ -668,6 +747,10 @@ def parser():
                          "and the -normal texture, the share of texels seen, stage times, the depth_tol and cos_min sweeps")
     ap.add_argument("--project-ring", type=int, default=16, metavar="N",
                     help="--project: the denser ring of N poses the field is also rendered from")
+    ap.add_argument("--mip", action="store_true",
+                    help="with --render and --texture T or --project: also build the mip pyramid of each atlas of the density mesh at "
+                         "--ply-res and of each --simplify arm of it and render it trilinearly from the held-out pose (DESIGN.md "
+                         "section 34): stage times, bytes, the histogram of floor(lod), PSNR with and without the pyramid")
     ap.add_argument("--smooth-lambda", type=float, default=0.5)
     ap.add_argument("--smooth-mu", type=float, default=-0.53, help="0: plain Laplacian smoothing")
     ap.add_argument("--ckpt", default=None, help="load this checkpoint instead of training")
@@ -685,6 +768,10 @@ def main():
         return stats(a)
     if a.tsdf_views is not None and a.tsdf_views < 1:
         ap.error("--tsdf-views must be at least 1")
+    if a.mip and not (a.render and (a.texture or a.project)):
+        ap.error("--mip needs --render and --texture T or --project")
+    if a.mip and a.project and a.random_bg:
+        ap.error("--mip with --project needs RGB training pictures (not --random-bg)")
     from nerf_meets_mlx_amd.dataset import synthetic
     from nerf_meets_mlx_amd.engine import mesh
     from nerf_meets_mlx_amd.engine.ngp import NGPTrainer, level_anneal_from_text
@@ -781,6 +868,15 @@ def main():
                 sm, srows, _ = mesh._simplify(m._replace(colors=None), G, lo, hi, "quadric", True)
                 sm = sm._replace(colors=mesh.vertex_colors(query, srows))
                 lines += _project_arms(tr, query, sm, f"density simplify {G}", R, a, rec, heldout, 2.0 * bound / R, train)
+                del sm, srows
+        if a.mip and R == a.ply_res:
+            heldout = _heldout(tr, held_pose, held_gt[..., :3].to(dev).float(), a.reps)
+            train = (tr.images, tr.poses)
+            lines += _mip_arms(tr, query, m, "density", R, a, rec, heldout, 2.0 * bound / R, train)
+            for G in a.simplify or []:
+                sm, srows, _ = mesh._simplify(m._replace(colors=None), G, lo, hi, "quadric", True)
+                sm = sm._replace(colors=mesh.vertex_colors(query, srows))
+                lines += _mip_arms(tr, query, sm, f"density simplify {G}", R, a, rec, heldout, 2.0 * bound / R, train)
                 del sm, srows
         lines += _simplify_arms(m._replace(colors=None), "density", R, lo, hi, a, rec, bound, boxes)
         lines += _smooth_arms(m._replace(colors=None), "density", R, lo, hi, a, rec, bound, boxes)
@@ -903,6 +999,14 @@ def _project_bytes(kernel, items, views):
     return {"project_accumulate_kernel": 32 + views * (8 + 48), "project_finish_kernel": 16 + 4}[kernel] * items
 
 
+def _mip_bytes(kernel, items):
+    """Algorithmic bytes of one csrc/mip.hip launch over `items` coarse atlas texels (reduce), faces (lod) or samples (sample):
+    reduce gathers nine bilinear lookups of four texels of three bytes (an in-triangle texel with every pair counted; cache hits,
+    the footprints overlap) and writes three bytes; lod reads 12 B of indices and 36 B of vertices and writes 4 B; sample reads
+    face, bary and a lod (16 B), gathers two lookups (24 B) and writes 12 B."""
+    return {"mip_reduce_kernel": 9 * 12 + 3, "mip_lod_kernel": 12 + 36 + 4, "mip_sample_kernel": 16 + 24 + 12}[kernel] * items
+
+
 def _morph_grid(kernel, R):
     """Work-items of a csrc/morph.hip launch at lattice size R."""
     words = -(-R // 64) * R * R
@@ -935,7 +1039,7 @@ def stats(a):
     name_k = col.get("kernel_name")
     s_k, e_k = col.get("start_timestamp"), col.get("end_timestamp")
     gx = col.get("grid_size_x", col.get("grid_size"))
-    groups, tex_items, raster_items, project_items = {}, {}, {}, {}
+    groups, tex_items, raster_items, project_items, mip_items = {}, {}, {}, {}, {}
     # the draws of one mesh in launch order: the render lines of that mesh list the small_max of every draw launch they made
     draw_sm = {}
     for r in renders:
@@ -943,7 +1047,7 @@ def stats(a):
     draw_seen = {}
     project_seen = 0
     for r in rows:
-        m = re.search(r"(mesh_\w+_kernel|ccl_\w+_kernel|morph_\w+_kernel|tsdf_\w+_kernel|simp_\w+_kernel|smooth_\w+_kernel|tex_\w+_kernel|raster_\w+_kernel|project_\w+_kernel|occ_cull_scan_kernel|occ_merge_exp_kernel)", r[name_k])
+        m = re.search(r"(mesh_\w+_kernel|ccl_\w+_kernel|morph_\w+_kernel|tsdf_\w+_kernel|simp_\w+_kernel|smooth_\w+_kernel|tex_\w+_kernel|raster_\w+_kernel|project_\w+_kernel|mip_\w+_kernel|occ_cull_scan_kernel|occ_merge_exp_kernel)", r[name_k])
         if not m:
             continue
         k = m.group(1)
@@ -976,6 +1080,10 @@ def stats(a):
             project_items.setdefault(k, []).append(grid)
             groups.setdefault((k, None), []).append((int(r[e_k]) - int(r[s_k])) * 1e-3)
             continue
+        if k.startswith("mip_"):                       # one lane per coarse texel, face or sample; pooled per kernel
+            mip_items.setdefault(k, []).append(grid)
+            groups.setdefault((k, None), []).append((int(r[e_k]) - int(r[s_k])) * 1e-3)
+            continue
         if k.startswith(("simp_", "smooth_")):         # sized by the mesh: one lane per vertex or face of the run at R; else pooled
             R = next((R for R, run in runs.items() if grid in (-(-run["V"] // BLOCK) * BLOCK, -(-run["F"] // BLOCK) * BLOCK)), None)
         elif k.startswith("tex_") or k in ("mesh_points_kernel", "occ_merge_exp_kernel", "occ_cull_scan_kernel", "ccl_finish_kernel"):
@@ -998,6 +1106,10 @@ def stats(a):
         elif k in project_items:                       # (accumulate's gathers depend on the views: the tool's own lines have them)
             rec["items"] = int(np.median(project_items[k]))
             b = _project_bytes(k, rec["items"], 0) if k == "project_finish_kernel" else None
+        elif k in mip_items:
+            rec["items"] = int(np.median(mip_items[k]))
+            b = _mip_bytes(k, rec["items"])
+            rec["bytes_per_item"] = _mip_bytes(k, 1)
         elif k in raster_items:
             rec["items"] = int(np.median(raster_items[k]))
             b = _raster_bytes(k.split()[0], rec["items"])
