@@ -693,6 +693,23 @@ int nerf_morph_erode(const float* vol, int res, float iso, int radius, void* wor
 int nerf_morph_reconstruct(const float* vol, const float* kept, int res, float iso, int radius, void* workspace, float* out,
                            int64_t* stats2, void* stream);
 
+/* ---------------------------------------------------------------- pinhole camera (no reference counterpart)
+ * The one camera of "TSDF fusion", "mesh rendering", "view-projected texture" and "texture mip pyramid": they must agree bit for
+ * bit (the bake tests a texel against the depth map the rasteriser drew, fusion integrates that depth, the level of detail calls the
+ * rasteriser's setup).  csrc/camera.h states it in code; tests/_camera_ref.py is its numpy reference.  IEEE float32, one rounding
+ * per operation (no contraction), in exactly the order and grouping written here; a / b correctly rounded.
+ *   view      nerf_tsdf_view (below), 16 finite floats on the host: c2w [3, 4] row-major (r_ab = c2w[4 a + b], t_a = c2w[4 a + 3];
+ *             camera directions [(col - cx) / fx, -(row - cy) / fy, -1] at integer pixel centres, as nerf_ray_gen), then fx, fy, cx,
+ *             cy (the K doubles cast once on the host).  A non-finite number is NERF_E_SHAPE.
+ *   point     a world point p: q_a = p_a - t_a; x_c = (r00 q0 + r10 q1) + r20 q2, y_c with column 1, z_w with column 2;
+ *             zc = 0.0f - z_w, the distance along the optical axis (what depth / acc of a renderer's aux maps means).
+ *   pixel     u = fx (x_c / zc) + cx; v = cy - fy (y_c / zc).  Pixel (px, py), py the image row, has its centre at (u, v) =
+ *             (px, py): the ray nerf_ray_gen shoots.  Each user says whether it tests zc before or after the division.
+ *   nearest   the pixel of an [H, W] map nearest to (u, v): fu = floorf(u + 0.5f), fv = floorf(v + 0.5f); outside unless
+ *             0 <= fu < W and 0 <= fv < H, compared as floats (a non-finite or huge u, v fails here, before any conversion);
+ *             inside, i = (int)fu, j = (int)fv and the map is read at j W + i.
+ *   batch     an entry that takes n views takes n structs on the host and hands at most 16 to a launch by value.                 */
+
 /* ---------------------------------------------------------------- TSDF fusion (no reference counterpart)
  * Fuses rendered depth / opacity maps of posed pinhole cameras into a truncated signed distance volume on the lattice of "mesh
  * extraction" (KinectFusion; nerfstudio's TSDF export), whose zero level set is the other mesh of a trained field: a voxel is
@@ -702,16 +719,11 @@ int nerf_morph_reconstruct(const float* vol, const float* kept, int res, float i
  * order (divisions correctly rounded; tests/_tsdf_ref.py reproduces every output bit for bit):
  *   state     D float32 [R^3], the running mean of the truncated distance in units of the truncation tau; Wt float32 [R^3], the
  *             number of observations; flags uint8 [R^3], bit 0 = occluded in at least one view.  nerf_tsdf_reset zeroes all three.
- *   view      nerf_tsdf_view, 16 floats: c2w [3, 4] row-major (r_ab = c2w[4 a + b], t_a = c2w[4 a + 3]; camera directions
- *             [(col - cx) / fx, -(row - cy) / fy, -1] at integer pixel centres, as nerf_ray_gen), then fx, fy, cx, cy (the K doubles
- *             cast once on the host); maps depth [H W] and acc [H W] as a renderer's aux outputs: depth = sum w z with z the
+ *   view      a nerf_tsdf_view of "pinhole camera"; maps depth [H W] and acc [H W] as a renderer's aux outputs: depth = sum w z with z the
  *             parameter of o + z d for the unnormalised d whose camera z is -1, so depth / acc is distance along the optical axis.
  *   per voxel and view, with tau > 0, 0 < acc_min <= 1, far > 0, carve in {0, 1}:
- *             q_a = p_a - t_a; x_c = (r00 q0 + r10 q1) + r20 q2, y_c with column 1, z_c with column 2; zc = 0.0f - z_c.
- *             !(zc > 0): no observation (NaN included).  u = fx (x_c / zc) + cx; v = cy - fy (y_c / zc); fu = floorf(u + 0.5f),
- *             fv = floorf(v + 0.5f); unless 0 <= fu < W and 0 <= fv < H (compared as floats: a non-finite or huge u, v fails here,
- *             before any conversion): no observation.  i = (int)fu, j = (int)fv, a = acc[j W + i], s = depth[j W + i]; a or s NaN:
- *             no observation.  a < acc_min: with carve and zc <= far the observation d = 1.0f (the ray hit nothing: empty all along
+ *             zc of the camera's `point`; !(zc > 0): no observation (NaN included).  (u, v) of its `pixel` and (i, j) of its
+ *             `nearest`; outside the map: no observation.  a = acc[j W + i], s = depth[j W + i]; a or s NaN: no observation.  a < acc_min: with carve and zc <= far the observation d = 1.0f (the ray hit nothing: empty all along
  *             it), else none.  Otherwise e = s / a - zc; e < -tau: flags |= 1, no observation; e NaN: none; else
  *             d = fminf(1.0f, e / tau).  On an observation: Wn = Wt + 1.0f; D = (D Wt + d) / Wn; Wt = Wn.
  *   batch     nerf_tsdf_integrate folds n <= NERF_TSDF_MAX_VIEWS views (views_host: n structs on the host, passed by value as
@@ -926,11 +938,8 @@ int nerf_texture_sample(const uint8_t* image, const float* verts, const float* n
  * rounded; integer steps are exact.  csrc/raster.h states the rule in code; tests/_raster_ref.py reproduces every output bit for
  * bit.
  *   input     verts [V, 3] float32, faces [F, 3] int32, 0 <= V, F <= 2^24; image 1 <= H, W <= 16384; near finite and > 0; the
- *             camera a nerf_tsdf_view on the host (16 finite floats: c2w [3, 4] row-major, fx, fy, cx, cy).
- *   camera    per vertex p, as nerf_tsdf_integrate and nerf_ray_gen: q_a = p_a - t_a; x_c = (r00 q0 + r10 q1) + r20 q2, y_c with
- *             column 1, z_w with column 2; zc = 0.0f - z_w; u = fx (x_c / zc) + cx; v = cy - fy (y_c / zc).  Pixel (px, py), py
- *             the image row, has its centre at (u, v) = (px, py): the ray nerf_ray_gen shoots.  Depth is zc, the distance along
- *             the optical axis (what depth / acc of a renderer's aux maps means).
+ *             camera a nerf_tsdf_view on the host.
+ *   camera    per vertex p, `point` and then `pixel` of "pinhole camera" (the tests below follow the division).  Depth is zc.
  *   snap      X = (int)rintf(u * 256.0f), Y = (int)rintf(v * 256.0f): screen coordinates in 1 / 256 pixel.
  *   dropped   a face is dropped and counted, never clipped: an index outside [0, V) or a non-finite vertex coordinate ("other";
  *             nothing is read through a bad index); else a vertex with !(near <= zc < inf), or with !(|u| <= 2^20) or
@@ -1010,18 +1019,18 @@ int nerf_render_rays_fused(const nerf_mlp_arch* arch, const void* packed_coarse,
  * contraction), in exactly the order and grouping written here; a / b and sqrt are correctly rounded.  csrc/project.h states the
  * rule in code; tests/_project_ref.py reproduces every output bit for bit.
  *   input     the mesh, texels T and the atlas of "texture atlas"; n <= NERF_PROJECT_MAX_VIEWS views, each a nerf_tsdf_view on the
- *             host (16 finite floats), an image [H, W, 3] float32 and a depth / acc map pair [H W] float32 of the same camera, as
+ *             host, an image [H, W, 3] float32 and a depth / acc map pair [H W] float32 of the same camera, as
  *             nerf_raster_resolve or a renderer's aux maps give them, stacked: images [n, H, W, 3], depth and acc [n, H W];
  *             1 <= H, W <= 16384; near finite and > 0; depth_tol finite and >= 0; cos_min and acc_min in (0, 1].
  *   texel     texel p of the atlas has the position x and the unit normal n of nerf_texture_rows: row[0:3] = x, row[3:6] = -n,
  *             the unclamped extrapolation beyond the hypotenuse and the zero normal included.  A texel of no face, or of a face
  *             with an index outside [0, V), makes no observation and its state is not touched.
- *   camera    q_a = x_a - t_a; x_c = (r00 q0 + r10 q1) + r20 q2, y_c with column 1, z_w with column 2; zc = 0.0f - z_w;
- *             !(zc >= near): no observation (NaN included).  u = fx (x_c / zc) + cx; v = cy - fy (y_c / zc).
+ *   camera    `point` of "pinhole camera" at x (zc = 0.0f - z_w); !(zc >= near): no observation (NaN included).  Then (u, v) of
+ *             its `pixel`.
  *   facing    e_a = t_a - x_a; L = sqrt((e0 e0 + e1 e1) + e2 e2); cosv = ((n0 e0 + n1 e1) + n2 e2) / L; !(cosv >= cos_min): no
  *             observation.  The weight of the observation is w = cosv.
- *   visible   fu = floorf(u + 0.5f), fv = floorf(v + 0.5f); unless 0 <= fu < W and 0 <= fv < H, compared as floats: no
- *             observation.  a = acc[fv W + fu], s = depth[fv W + fu]; a or s NaN, or a < acc_min: no observation.
+ *   visible   (i, j) of the camera's `nearest` (floorf(u + 0.5f), floorf(v + 0.5f)); outside the maps: no observation.
+ *             a = acc[j W + i], s = depth[j W + i]; a or s NaN, or a < acc_min: no observation.
  *             ez = s / a - zc; !(ez >= 0.0f - depth_tol): no observation, the texel lies behind what the view sees.
  *   colour    a bilinear lookup of the image at (u, v), pixel centres at the integers: x0 = floorf(u), y0 = floorf(v); unless
  *             0 <= x0, x0 + 1 <= W - 1, 0 <= y0 and y0 + 1 <= H - 1, compared as floats: no observation.  fx = u - x0, fy = v - y0,
@@ -1090,7 +1099,7 @@ int nerf_project_finish(const float* state, int64_t F, int texels, int64_t p0, i
  *   nerf_mip_reduce    the texels [p0, p0 + count) of the coarse atlas (T' = (texels_fine + 1) / 2) in raster order from the fine
  *                      image; other texels are not touched, a gutter lane recomputes the in-triangle bytes it needs: the image
  *                      depends on neither the chunk nor the launch shape.  texels_fine in [3, 64].
- *   nerf_mip_lod       lod [F] float32 for the camera (a nerf_tsdf_view on the host, 16 finite floats), near finite and > 0, scale
+ *   nerf_mip_lod       lod [F] float32 for the camera (a nerf_tsdf_view on the host, "pinhole camera"), near finite and > 0, scale
  *                      finite and > 0, over a pyramid of `texels` at level 0.  One lane per face.  F = 0 launches nothing.
  *   nerf_mip_sample    rgb [n, 3] of n < 2^31 samples face [n] int32, bary [n, 2]; images is a HOST array of the L device
  *                      pointers of the levels of a pyramid over `texels`, handed to the kernel by value; lod is [F] and read at

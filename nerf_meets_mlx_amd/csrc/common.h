@@ -116,6 +116,8 @@ __device__ __forceinline__ void block_loss_add(float* part, int lane, int wv, fl
   if (threadIdx.x == 0 && out) atomicAdd(out, (part[0] + part[1] + part[2] + part[3]) * scale);
 }
 
+// the workgroups of a flat launch (NERF_LAUNCH below): one lane per item, `block` lanes a workgroup
+static inline unsigned blocks(int64_t n, int block) { return (unsigned)((n + block - 1) / block); }
 }  // namespace nerf
 
 #define NERF_REQUIRE(cond, code, ...) \

@@ -8,6 +8,9 @@
 // The index helpers compile without HIP (tests/lattice_check.cpp runs them under a host compiler, which supplies nerf::fail and
 // NERF_REQUIRE itself).  Not here, on purpose: simplify.hip's double-precision SBox (another lattice, of G^3 cells), morph.hip's
 // word geometry (it counts 64-voxel words) and ccl.hip's union-find.
+// Below the lattice, the triangle mesh as the surface kernels take it (texture.hip, raster.hip, project.hip, mip.hip; smooth.hip for
+// the corners): verts float32 [V, 3], faces int32 [F, 3], 0 <= V, F <= MESH_MAX_ITEMS, nothing read through an index outside [0, V).
+// Not simplify.hip's checks (one message for V and F) or its fetch, which tests only >= 0.
 #pragma once
 #include <cmath>
 #include <stdint.h>
@@ -72,13 +75,25 @@ inline int lattice_box(const char* who, int R, const float* lo, const float* hi,
   return NERF_OK;
 }
 
+constexpr int64_t MESH_MAX_ITEMS = 1 << 24;                    // vertices, faces
+inline int mesh_check(const char* who, int64_t V, int64_t F) {             // (an entry without vertices passes V = 0)
+  NERF_REQUIRE(V >= 0 && V <= MESH_MAX_ITEMS, NERF_E_SHAPE, "%s: need 0 <= V <= 2^24 (got %lld)", who, (long long)V);
+  NERF_REQUIRE(F >= 0 && F <= MESH_MAX_ITEMS, NERF_E_SHAPE, "%s: need 0 <= F <= 2^24 (got %lld)", who, (long long)F);
+  return NERF_OK;
+}
+// the corners g of the face whose three indices start at idx; false when one lies outside [0, V)
+__host__ __device__ __forceinline__ bool mesh_corners(const int* __restrict__ idx, int V, int* g) {
+  g[0] = idx[0], g[1] = idx[1], g[2] = idx[2];
+  return g[0] >= 0 && g[0] < V && g[1] >= 0 && g[1] < V && g[2] >= 0 && g[2] < V;
+}
+
+// correctly rounded float32 division / square root: the double result rounded once (exact enough for one float rounding)
+__host__ __device__ __forceinline__ float div_rn(float a, float b) { return (float)((double)a / (double)b); }
+__host__ __device__ __forceinline__ float sqrt_rn(float a) { return (float)sqrt((double)a); }
+
 #if defined(__HIPCC__)
 // this lane's voxel; at or past lattice_n3(R) in the last workgroup's tail
 __device__ __forceinline__ int64_t lattice_lane() { return (int64_t)blockIdx.x * LATTICE_BLOCK + threadIdx.x; }
-
-// correctly rounded float32 division / square root: the double result rounded once (exact enough for one float rounding)
-__device__ __forceinline__ float div_rn(float a, float b) { return (float)((double)a / (double)b); }
-__device__ __forceinline__ float sqrt_rn(float a) { return (float)sqrt((double)a); }
 
 // the colour query row [x, -n, 0, 0, -n] of vertex `id`
 __device__ __forceinline__ void write_color_row(float* __restrict__ rows, int64_t id, const float* x, const float* n) {

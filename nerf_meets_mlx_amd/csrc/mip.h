@@ -77,20 +77,17 @@ inline int mip_reduce_check(const char* who, const uint8_t* fine, int64_t F, int
   return NERF_OK;
 }
 
-// every argument of nerf_mip_lod; fills the chain and the view
+// every argument of nerf_mip_lod; fills the chain
 inline int mip_lod_check(const char* who, const float* verts, int64_t V, const int32_t* faces, int64_t F, const nerf_tsdf_view* view_host,
-                         float near, int T, float scale, const float* lod, MipChain* chain, nerf_tsdf_view* view, bool* work) {
+                         float near, int T, float scale, const float* lod, MipChain* chain, bool* work) {
   *work = false;
-  NERF_REQUIRE(V >= 0 && V <= RASTER_MAX_ITEMS, NERF_E_SHAPE, "%s: need 0 <= V <= 2^24 (got %lld)", who, (long long)V);
-  NERF_REQUIRE(F >= 0 && F <= RASTER_MAX_ITEMS, NERF_E_SHAPE, "%s: need 0 <= F <= 2^24 (got %lld)", who, (long long)F);
-  const int rc = mip_texels_check(who, T);
+  int rc = mesh_check(who, V, F);
+  if (!rc) rc = mip_texels_check(who, T);
+  if (!rc) rc = camera_near_check(who, near);
   if (rc) return rc;
-  NERF_REQUIRE(std::isfinite(near) && near > 0.0f, NERF_E_SHAPE, "%s: near must be finite and > 0 (got %g)", who, (double)near);
   NERF_REQUIRE(std::isfinite(scale) && scale > 0.0f, NERF_E_SHAPE, "%s: scale must be finite and > 0 (got %g)", who, (double)scale);
-  NERF_REQUIRE(view_host, NERF_E_NULL, "%s: NULL view", who);
-  const float* x = reinterpret_cast<const float*>(view_host);
-  for (int q = 0; q < 16; ++q) NERF_REQUIRE(std::isfinite(x[q]), NERF_E_SHAPE, "%s: non-finite camera number %d", who, q);
-  *view = *view_host;
+  rc = camera_view_check(who, view_host);
+  if (rc) return rc;
   chain->L = mip_chain(T, chain->T);
   NERF_REQUIRE((lod && faces) || F == 0, NERF_E_NULL, "%s: NULL pointer", who);
   NERF_REQUIRE(verts || V == 0, NERF_E_NULL, "%s: NULL verts", who);

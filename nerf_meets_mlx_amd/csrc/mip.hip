@@ -29,13 +29,13 @@ __global__ void __launch_bounds__(MIP_BLOCK) mip_reduce_kernel(const uint8_t* __
 }
 
 __global__ void __launch_bounds__(MIP_BLOCK) mip_lod_kernel(const float* __restrict__ verts, int V, const int* __restrict__ faces, int F,
-                                                           RasterView view, float near, MipChain chain, float scale,
+                                                           nerf_tsdf_view view, float near, MipChain chain, float scale,
                                                            float* __restrict__ lod) {
   const int f = blockIdx.x * MIP_BLOCK + threadIdx.x;
   if (f >= F) return;
   RasterFace rf;
   float out = 0.0f;
-  if (raster_setup(verts, V, faces + 3 * (int64_t)f, view.v, near, 0, &rf) == RASTER_OK) {
+  if (raster_setup(verts, V, faces + 3 * (int64_t)f, view, near, 0, &rf) == RASTER_OK) {
     const int64_t D = raster_edge(rf.X[0], rf.Y[0], rf.X[1], rf.Y[1], rf.X[2], rf.Y[2]);
     out = mip_lod(chain, D < 0 ? -D : D, scale);
   }
@@ -81,10 +81,6 @@ __global__ void __launch_bounds__(MIP_BLOCK) mip_sample_kernel(MipLevels lv, con
   for (int ch = 0; ch < 3; ++ch) rgb[3 * s + ch] = out[ch];
 }
 
-inline unsigned mip_blocks(int64_t n) { return (unsigned)((n + MIP_BLOCK - 1) / MIP_BLOCK); }
-
-#define MIP_LAUNCH(what, kernel, blocks, ...) NERF_LAUNCH(what, kernel, blocks, MIP_BLOCK, st, __VA_ARGS__)
-
 }  // namespace
 }  // namespace nerf
 
@@ -106,20 +102,18 @@ extern "C" int nerf_mip_reduce(const uint8_t* fine, int64_t F, int texels_fine, 
   bool work;
   const int rc = mip_reduce_check("nerf_mip_reduce", fine, F, texels_fine, coarse, p0, count, &lf, &lc, &work);
   if (rc || !work) return rc;
-  hipStream_t st = as_stream(stream);
-  MIP_LAUNCH("nerf_mip_reduce", mip_reduce_kernel, mip_blocks(count), fine, lf, lc, p0, count, coarse);
+  NERF_LAUNCH("nerf_mip_reduce", mip_reduce_kernel, blocks(count, MIP_BLOCK), MIP_BLOCK, as_stream(stream), fine, lf, lc, p0, count, coarse);
   return NERF_OK;
 }
 
 extern "C" int nerf_mip_lod(const float* verts, int64_t V, const int32_t* faces, int64_t F, const nerf_tsdf_view* view_host, float near,
                             int texels, float scale, float* lod, void* stream) {
   MipChain chain;
-  RasterView view;
   bool work;
-  const int rc = mip_lod_check("nerf_mip_lod", verts, V, faces, F, view_host, near, texels, scale, lod, &chain, &view.v, &work);
+  const int rc = mip_lod_check("nerf_mip_lod", verts, V, faces, F, view_host, near, texels, scale, lod, &chain, &work);
   if (rc || !work) return rc;
-  hipStream_t st = as_stream(stream);
-  MIP_LAUNCH("nerf_mip_lod", mip_lod_kernel, mip_blocks(F), verts, (int)V, faces, (int)F, view, near, chain, scale, lod);
+  NERF_LAUNCH("nerf_mip_lod", mip_lod_kernel, blocks(F, MIP_BLOCK), MIP_BLOCK, as_stream(stream), verts, (int)V, faces, (int)F, *view_host, near,
+              chain, scale, lod);
   return NERF_OK;
 }
 
@@ -129,7 +123,6 @@ extern "C" int nerf_mip_sample(const uint8_t* const* images_host, int64_t F, int
   bool work;
   const int rc = mip_sample_check("nerf_mip_sample", images_host, F, texels, face, bary, lod, per_face, n, rgb, &lv, &work);
   if (rc || !work) return rc;
-  hipStream_t st = as_stream(stream);
-  MIP_LAUNCH("nerf_mip_sample", mip_sample_kernel, mip_blocks(n), lv, face, bary, lod, per_face, n, rgb);
+  NERF_LAUNCH("nerf_mip_sample", mip_sample_kernel, blocks(n, MIP_BLOCK), MIP_BLOCK, as_stream(stream), lv, face, bary, lod, per_face, n, rgb);
   return NERF_OK;
 }

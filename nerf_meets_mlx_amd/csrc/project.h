@@ -1,29 +1,23 @@
 // The projective texture bake (project.hip), the one statement in code of include/nerf_hip.h "view-projected texture": what one
 // posed image says about one texel of the atlas of texture.h.
 //   texel    position x and unit normal n of tex_point at the texel's barycentrics (texture.h: the texel of nerf_texture_rows)
-//   camera   nerf_tsdf_view, as raster.h: q = x - t; (xc, yc, zw) = R^T q with the sums associated as in tsdf_integrate_kernel;
-//            zc = 0 - zw; !(zc >= near): none.  u = fx (xc / zc) + cx, v = cy - fy (yc / zc)
+//   camera   camera.h: camera_point; !(zc >= near): none; after the facing test camera_pixel
 //   facing   e = t - x; L = sqrt((e0 e0 + e1 e1) + e2 e2); cosv = ((n0 e0 + n1 e1) + n2 e2) / L; !(cosv >= cos_min): none; w = cosv
-//   visible  fu = floorf(u + 0.5f), fv likewise; unless 0 <= fu < W and 0 <= fv < H (floats): none.  a = acc[fv W + fu],
-//            s = depth[fv W + fu]; a or s NaN, or a < acc_min: none.  ez = s / a - zc; !(ez >= 0 - depth_tol): none
+//   visible  camera.h: camera_nearest, the pixel the rasteriser drew; outside: none.  a = acc[pix], s = depth[pix]; a or s NaN, or
+//            a < acc_min: none.  ez = s / a - zc; !(ez >= 0 - depth_tol): none
 //   colour   x0 = floorf(u), y0 = floorf(v); unless 0 <= x0, x0 + 1 <= W - 1, 0 <= y0, y0 + 1 <= H - 1 (floats): none.
 //            fx = u - x0, fy = v - y0, gx = 1 - fx, gy = 1 - fy; w00 = gx gy, w10 = fx gy, w01 = gx fy, w11 = fx fy (the first index
 //            along x); c = ((w00 c00 + w10 c10) + w01 c01) + w11 c11 per channel; a NaN channel: none
 //   fold     blend: S_c = S_c + w c, S_w = S_w + w.  best: if w > S_w then S = (c, w)
 // The argument checks compile without HIP (tests/project_check.cpp runs them under a host compiler with sanitizers).
 #pragma once
+#include "camera.h"
 #include "texture.h"
 
 namespace nerf {
 namespace {
 
 constexpr int PROJECT_BLOCK = 256;
-constexpr int PROJECT_MAX_SIDE = 16384;
-
-struct ProjectViews {
-  nerf_tsdf_view v[NERF_PROJECT_MAX_VIEWS];
-};
-static_assert(sizeof(nerf_tsdf_view) == 16 * sizeof(float), "16 floats per view");
 
 // what every view of a launch shares
 struct ProjectRule {
@@ -42,28 +36,23 @@ inline int project_accumulate_check(const char* who, const float* verts, const f
                                     int T, int64_t p0, int64_t count, const nerf_tsdf_view* views_host, int n, int H, int W,
                                     const float* images, const float* depth, const float* acc, float near, float depth_tol,
                                     float cos_min, float acc_min, int mode, const float* state, TexLayout* lay, ProjectRule* rule,
-                                    ProjectViews* views, bool* work) {
+                                    CameraViews* views, bool* work) {
   *work = false;
   int rc = tex_mesh_check(who, V, F, T, lay);
   if (!rc) rc = tex_chunk_check(who, *lay, p0, count);
   if (!rc) rc = project_mode_check(who, mode);
   if (rc) return rc;
   NERF_REQUIRE(n >= 0 && n <= NERF_PROJECT_MAX_VIEWS, NERF_E_SHAPE, "%s: need 0 <= n <= %d views (got %d)", who, NERF_PROJECT_MAX_VIEWS, n);
-  NERF_REQUIRE(H >= 1 && W >= 1 && H <= PROJECT_MAX_SIDE && W <= PROJECT_MAX_SIDE, NERF_E_SHAPE, "%s: need 1 <= H, W <= %d (got %d x %d)",
-               who, PROJECT_MAX_SIDE, H, W);
-  NERF_REQUIRE(std::isfinite(near) && near > 0.0f, NERF_E_SHAPE, "%s: near must be finite and > 0 (got %g)", who, (double)near);
+  rc = camera_image_check(who, H, W, CAMERA_MAX_SIDE);
+  if (!rc) rc = camera_near_check(who, near);
+  if (rc) return rc;
   NERF_REQUIRE(std::isfinite(depth_tol) && depth_tol >= 0.0f, NERF_E_SHAPE, "%s: depth_tol must be finite and >= 0 (got %g)", who,
                (double)depth_tol);
   NERF_REQUIRE(cos_min > 0.0f && cos_min <= 1.0f, NERF_E_SHAPE, "%s: need 0 < cos_min <= 1 (got %g)", who, (double)cos_min);
   NERF_REQUIRE(acc_min > 0.0f && acc_min <= 1.0f, NERF_E_SHAPE, "%s: need 0 < acc_min <= 1 (got %g)", who, (double)acc_min);
   NERF_REQUIRE(n == 0 || views_host, NERF_E_NULL, "%s: NULL views", who);
-  for (int s = 0; s < NERF_PROJECT_MAX_VIEWS; ++s) {
-    if (n == 0) break;
-    views->v[s] = views_host[s < n ? s : 0];
-    if (s >= n) continue;
-    const float* x = views->v[s].c2w;                        // the 12 pose numbers, then fx, fy, cx, cy
-    for (int q = 0; q < 16; ++q) NERF_REQUIRE(std::isfinite(x[q]), NERF_E_SHAPE, "%s: view %d: non-finite camera number %d", who, s, q);
-  }
+  rc = camera_views_check(who, views_host, n, views);
+  if (rc) return rc;
   *rule = ProjectRule{H, W, mode, near, 0.0f - depth_tol, cos_min, acc_min};
   if (n == 0 || count == 0) return NERF_OK;
   NERF_REQUIRE(images && depth && acc && state && (faces || F == 0) && ((verts && normals) || V == 0), NERF_E_NULL, "%s: NULL pointer", who);
@@ -93,11 +82,9 @@ inline int project_finish_check(const char* who, const float* state, int64_t F, 
 __device__ __forceinline__ bool project_observe(const nerf_tsdf_view& vw, const ProjectRule& r, const float* __restrict__ image,
                                                 const float* __restrict__ depth, const float* __restrict__ acc, const float* x,
                                                 const float* n, float* w, float* c) {
-  const float q0 = x[0] - vw.c2w[3], q1 = x[1] - vw.c2w[7], q2 = x[2] - vw.c2w[11];
-  const float xc = (vw.c2w[0] * q0 + vw.c2w[4] * q1) + vw.c2w[8] * q2;
-  const float yc = (vw.c2w[1] * q0 + vw.c2w[5] * q1) + vw.c2w[9] * q2;
-  const float zw = (vw.c2w[2] * q0 + vw.c2w[6] * q1) + vw.c2w[10] * q2;
-  const float zc = 0.0f - zw;
+  float cam[3], u, v;
+  camera_point(vw, x, cam);
+  const float zc = cam[2];
   if (!(zc >= r.near)) return false;                                       // in front of the near plane, behind the camera, or NaN
   const float e0 = vw.c2w[3] - x[0], e1 = vw.c2w[7] - x[1], e2 = vw.c2w[11] - x[2];
   const float dot = (n[0] * e0 + n[1] * e1) + n[2] * e2;
@@ -109,12 +96,10 @@ __device__ __forceinline__ bool project_observe(const nerf_tsdf_view& vw, const 
   const float L = sqrt_rn((e0 * e0 + e1 * e1) + e2 * e2);
   const float cosv = div_rn(dot, L);
   if (!(cosv >= r.cos_min)) return false;                                  // facing away, grazing, no normal, or NaN
-  const float u = vw.fx * div_rn(xc, zc) + vw.cx;
-  const float v = vw.cy - vw.fy * div_rn(yc, zc);
+  camera_pixel(vw, cam, &u, &v);
+  int64_t pix;
+  if (!camera_nearest(u, v, r.H, r.W, &pix)) return false;                 // outside the image, or not finite
   const float fW = (float)r.W, fH = (float)r.H;
-  const float fu = floorf(u + 0.5f), fv = floorf(v + 0.5f);
-  if (!(fu >= 0.0f && fu < fW && fv >= 0.0f && fv < fH)) return false;     // outside the image, or not finite: before the cast
-  const int64_t pix = (int64_t)(int)fv * r.W + (int)fu;
   const float a = acc[pix], s = depth[pix];
   if (a != a || s != s || a < r.acc_min) return false;
   const float ez = div_rn(s, a) - zc;

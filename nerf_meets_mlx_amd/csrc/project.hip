@@ -17,7 +17,7 @@ namespace {
 // texel that passes the camera and facing tests 8 B of maps and 48 B of image gathered
 __global__ void __launch_bounds__(PROJECT_BLOCK) project_accumulate_kernel(const float* __restrict__ verts, const float* __restrict__ normals,
                                                                           int V, const int* __restrict__ faces, TexLayout lay, int64_t p0,
-                                                                          int64_t count, ProjectViews views, int n, ProjectRule rule,
+                                                                          int64_t count, CameraViews views, int n, ProjectRule rule,
                                                                           const float* __restrict__ images, const float* __restrict__ depth,
                                                                           const float* __restrict__ acc, float4* __restrict__ state) {
   const int64_t q = (int64_t)blockIdx.x * PROJECT_BLOCK + threadIdx.x;
@@ -67,8 +67,6 @@ __global__ void __launch_bounds__(PROJECT_BLOCK) project_finish_kernel(const flo
   seen[p] = got ? 1 : 0;
 }
 
-inline unsigned project_blocks(int64_t n) { return (unsigned)((n + PROJECT_BLOCK - 1) / PROJECT_BLOCK); }
-
 }  // namespace
 }  // namespace nerf
 
@@ -81,14 +79,13 @@ extern "C" int nerf_project_accumulate(const float* verts, const float* normals,
   const char* who = "nerf_project_accumulate";
   TexLayout lay;
   ProjectRule rule;
-  ProjectViews views;
+  CameraViews views;
   bool work;
   const int rc = project_accumulate_check(who, verts, normals, V, faces, F, texels, p0, count, views_host, n, H, W, images, depth, acc,
                                           near, depth_tol, cos_min, acc_min, mode, state, &lay, &rule, &views, &work);
   if (rc || !work) return rc;
-  hipStream_t st = as_stream(stream);
-  NERF_LAUNCH(who, project_accumulate_kernel, project_blocks(count), PROJECT_BLOCK, st, verts, normals, (int)V, faces, lay, p0, count, views,
-              n, rule, images, depth, acc, reinterpret_cast<float4*>(state));
+  NERF_LAUNCH(who, project_accumulate_kernel, blocks(count, PROJECT_BLOCK), PROJECT_BLOCK, as_stream(stream), verts, normals, (int)V, faces, lay, p0,
+              count, views, n, rule, images, depth, acc, reinterpret_cast<float4*>(state));
   return NERF_OK;
 }
 
@@ -99,8 +96,7 @@ extern "C" int nerf_project_finish(const float* state, int64_t F, int texels, in
   bool work;
   const int rc = project_finish_check(who, state, F, texels, p0, count, mode, image, seen, &lay, &work);
   if (rc || !work) return rc;
-  hipStream_t st = as_stream(stream);
-  NERF_LAUNCH(who, project_finish_kernel, project_blocks(count), PROJECT_BLOCK, st, reinterpret_cast<const float4*>(state), p0, count, mode,
-              fallback, image, seen);
+  NERF_LAUNCH(who, project_finish_kernel, blocks(count, PROJECT_BLOCK), PROJECT_BLOCK, as_stream(stream), reinterpret_cast<const float4*>(state), p0,
+              count, mode, fallback, image, seen);
   return NERF_OK;
 }

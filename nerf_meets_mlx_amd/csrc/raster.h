@@ -1,6 +1,5 @@
 // The visibility-buffer rasteriser of a triangle mesh (raster.hip), the one statement in code of include/nerf_hip.h "mesh rendering":
-//   camera   nerf_tsdf_view: q = p - t; (xc, yc, zw) = R^T q with the sums associated as in tsdf_integrate_kernel; zc = 0 - zw;
-//            u = fx (xc / zc) + cx, v = cy - fy (yc / zc); pixel (px, py) has its centre at (u, v) = (px, py); depth is zc
+//   camera   camera.h: camera_point, then camera_pixel, on every vertex; the tests follow the division; depth is zc
 //   snap     X = (int)rintf(u * 256), Y = (int)rintf(v * 256): screen coordinates in 1 / 256 pixel
 //   guard    |u|, |v| <= 2^20 pixels, tested on the floats before the cast, so |X|, |Y| <= 2^28: a difference of two coordinates is
 //            below 2^30 (an int), a product of two differences below 2^59 and a difference of two products below 2^60 (an int64)
@@ -14,14 +13,12 @@
 //   key      ((uint64)float_bits(z) << 32) | (uint32)face, minimised; all ones = empty
 // Everything below is device code shared by the draw and the resolve, which therefore compute the same bits.
 #pragma once
-#include "lattice.h"
+#include "camera.h"
 
 namespace nerf {
 namespace {
 
 constexpr int RASTER_BLOCK = 256;
-constexpr int RASTER_MAX_SIDE = 16384;
-constexpr int64_t RASTER_MAX_ITEMS = 1 << 24;                  // vertices, faces
 constexpr int RASTER_MAX_SMALL = 1 << 30;
 constexpr int RASTER_SNAP = 256;                               // sub-pixel steps
 constexpr float RASTER_GUARD = 1048576.0f;                     // 2^20 pixels
@@ -29,10 +26,6 @@ constexpr unsigned long long RASTER_EMPTY = ~0ull;
 constexpr int RASTER_OK = 0, RASTER_DROP_DEPTH = 1, RASTER_DROP_OTHER = 2;
 
 #if defined(__HIPCC__)
-struct RasterView {
-  nerf_tsdf_view v;
-};
-
 // a face on the screen: snapped corners, camera depths, orientation
 struct RasterFace {
   int X[3], Y[3];
@@ -48,28 +41,18 @@ __device__ __forceinline__ int64_t raster_edge(int Ux, int Uy, int Vx, int Vy, i
 __device__ __forceinline__ int raster_setup(const float* __restrict__ verts, int V, const int* __restrict__ idx, const nerf_tsdf_view& vw,
                                             float near, int cull, RasterFace* out) {
   int g[3];
-  bool ok = true;
-#pragma unroll
-  for (int c = 0; c < 3; ++c) {
-    g[c] = idx[c];
-    ok = ok && g[c] >= 0 && g[c] < V;
-  }
-  if (!ok) return RASTER_DROP_OTHER;
+  if (!mesh_corners(idx, V, g)) return RASTER_DROP_OTHER;
   float u[3], v[3];
   bool finite = true, seen = true;
 #pragma unroll
   for (int c = 0; c < 3; ++c) {
-    const float p0 = verts[3 * g[c]], p1 = verts[3 * g[c] + 1], p2 = verts[3 * g[c] + 2];
-    finite = finite && fabsf(p0) <= 3.402823466e+38f && fabsf(p1) <= 3.402823466e+38f && fabsf(p2) <= 3.402823466e+38f;
-    const float q0 = p0 - vw.c2w[3], q1 = p1 - vw.c2w[7], q2 = p2 - vw.c2w[11];
-    const float xc = (vw.c2w[0] * q0 + vw.c2w[4] * q1) + vw.c2w[8] * q2;
-    const float yc = (vw.c2w[1] * q0 + vw.c2w[5] * q1) + vw.c2w[9] * q2;
-    const float zw = (vw.c2w[2] * q0 + vw.c2w[6] * q1) + vw.c2w[10] * q2;
-    const float zc = 0.0f - zw;
-    out->z[c] = zc;
-    u[c] = vw.fx * div_rn(xc, zc) + vw.cx;
-    v[c] = vw.cy - vw.fy * div_rn(yc, zc);
-    seen = seen && zc >= near && zc <= 3.402823466e+38f;
+    const float p[3] = {verts[3 * g[c]], verts[3 * g[c] + 1], verts[3 * g[c] + 2]};
+    finite = finite && fabsf(p[0]) <= 3.402823466e+38f && fabsf(p[1]) <= 3.402823466e+38f && fabsf(p[2]) <= 3.402823466e+38f;
+    float cam[3];
+    camera_point(vw, p, cam);
+    out->z[c] = cam[2];
+    camera_pixel(vw, cam, &u[c], &v[c]);
+    seen = seen && cam[2] >= near && cam[2] <= 3.402823466e+38f;
   }
   if (!finite) return RASTER_DROP_OTHER;
   if (!seen) return RASTER_DROP_DEPTH;

@@ -41,7 +41,7 @@ __global__ void __launch_bounds__(RASTER_BLOCK) raster_clear_kernel(unsigned lon
 
 // ---- draw: per face 12 B of indices and 36 B of vertices gathered; per covered pixel one 8-byte atomic without a return
 __global__ void __launch_bounds__(RASTER_BLOCK) raster_draw_kernel(const float* __restrict__ verts, int V, const int* __restrict__ faces,
-                                                                  int F, int face_base, RasterView view, int H, int W, float near,
+                                                                  int F, int face_base, nerf_tsdf_view view, int H, int W, float near,
                                                                   int cull, int small_max, unsigned long long* keys,
                                                                   unsigned long long* __restrict__ stats) {
   const int f = blockIdx.x * RASTER_BLOCK + threadIdx.x;
@@ -49,7 +49,7 @@ __global__ void __launch_bounds__(RASTER_BLOCK) raster_draw_kernel(const float* 
   RasterFace rf = {};
   int why = -1, x0 = 0, x1 = -1, y0 = 0, y1 = -1;
   if (f < F) {
-    why = raster_setup(verts, V, faces + 3 * (int64_t)f, view.v, near, cull, &rf);
+    why = raster_setup(verts, V, faces + 3 * (int64_t)f, view, near, cull, &rf);
     if (why == RASTER_OK) {
       const int xmin = min(rf.X[0], min(rf.X[1], rf.X[2])), xmax = max(rf.X[0], max(rf.X[1], rf.X[2]));
       const int ymin = min(rf.Y[0], min(rf.Y[1], rf.Y[2])), ymax = max(rf.Y[0], max(rf.Y[1], rf.Y[2]));
@@ -112,7 +112,7 @@ __global__ void __launch_bounds__(RASTER_BLOCK) raster_draw_kernel(const float* 
 // ---- resolve: 8 B read per pixel, the winner's 48 B gathered, 20 B written
 __global__ void __launch_bounds__(RASTER_BLOCK) raster_resolve_kernel(const unsigned long long* __restrict__ keys,
                                                                      const float* __restrict__ verts, int V,
-                                                                     const int* __restrict__ faces, int F, RasterView view, int H, int W,
+                                                                     const int* __restrict__ faces, int F, nerf_tsdf_view view, int H, int W,
                                                                      float near, int* __restrict__ face, float* __restrict__ bary,
                                                                      float* __restrict__ depth, float* __restrict__ acc) {
   const int64_t p = (int64_t)blockIdx.x * RASTER_BLOCK + threadIdx.x;
@@ -122,7 +122,7 @@ __global__ void __launch_bounds__(RASTER_BLOCK) raster_resolve_kernel(const unsi
   int out_face = -1;
   float wb = 0.0f, wc = 0.0f, z = 0.0f, a = 0.0f;
   RasterFace rf;
-  if (key != RASTER_EMPTY && id < (unsigned)F && raster_setup(verts, V, faces + 3 * (int64_t)id, view.v, near, 0, &rf) == RASTER_OK) {
+  if (key != RASTER_EMPTY && id < (unsigned)F && raster_setup(verts, V, faces + 3 * (int64_t)id, view, near, 0, &rf) == RASTER_OK) {
     const int py = (int)(p / W), px = (int)(p - (int64_t)py * W);
     float b, c, d;
     if (raster_pixel(rf, px, py, &b, &c, &d)) {
@@ -152,12 +152,12 @@ __global__ void __launch_bounds__(RASTER_BLOCK) raster_shade_kernel(const int* _
 #pragma unroll
       for (int ch = 0; ch < 3; ++ch) out[ch] = rgb_in[3 * p + ch];
     } else if (f < F) {
-      const int ga = faces[3 * (int64_t)f], gb = faces[3 * (int64_t)f + 1], gc = faces[3 * (int64_t)f + 2];
-      if (ga >= 0 && ga < V && gb >= 0 && gb < V && gc >= 0 && gc < V) {
+      int g[3];
+      if (mesh_corners(faces + 3 * (int64_t)f, V, g)) {
         const float wb = bary[2 * p], wc = bary[2 * p + 1];
         const float wa = (1.0f - wb) - wc;
 #pragma unroll
-        for (int ch = 0; ch < 3; ++ch) out[ch] = (wa * colors[3 * ga + ch] + wb * colors[3 * gb + ch]) + wc * colors[3 * gc + ch];
+        for (int ch = 0; ch < 3; ++ch) out[ch] = (wa * colors[3 * g[0] + ch] + wb * colors[3 * g[1] + ch]) + wc * colors[3 * g[2] + ch];
       }
     }
   }
@@ -165,42 +165,18 @@ __global__ void __launch_bounds__(RASTER_BLOCK) raster_shade_kernel(const int* _
   for (int ch = 0; ch < 3; ++ch) rgb[3 * p + ch] = out[ch];
 }
 
-inline unsigned raster_blocks(int64_t n) { return (unsigned)((n + RASTER_BLOCK - 1) / RASTER_BLOCK); }
-
-int raster_image_check(const char* who, int H, int W) {
-  NERF_REQUIRE(H >= 1 && W >= 1 && H <= RASTER_MAX_SIDE && W <= RASTER_MAX_SIDE, NERF_E_SHAPE, "%s: need 1 <= H, W <= %d (got %d x %d)", who,
-               RASTER_MAX_SIDE, H, W);
-  return NERF_OK;
-}
-int raster_mesh_check(const char* who, int64_t V, int64_t F) {
-  NERF_REQUIRE(V >= 0 && V <= RASTER_MAX_ITEMS, NERF_E_SHAPE, "%s: need 0 <= V <= 2^24 (got %lld)", who, (long long)V);
-  NERF_REQUIRE(F >= 0 && F <= RASTER_MAX_ITEMS, NERF_E_SHAPE, "%s: need 0 <= F <= 2^24 (got %lld)", who, (long long)F);
-  return NERF_OK;
-}
-int raster_view_check(const char* who, const nerf_tsdf_view* view, float near, RasterView* out) {
-  NERF_REQUIRE(std::isfinite(near) && near > 0.0f, NERF_E_SHAPE, "%s: near must be finite and > 0 (got %g)", who, (double)near);
-  NERF_REQUIRE(view, NERF_E_NULL, "%s: NULL view", who);
-  const float* x = reinterpret_cast<const float*>(view);
-  for (int q = 0; q < 16; ++q) NERF_REQUIRE(std::isfinite(x[q]), NERF_E_SHAPE, "%s: non-finite camera number %d", who, q);
-  out->v = *view;
-  return NERF_OK;
-}
-
-#define RASTER_LAUNCH(what, kernel, blocks, ...) NERF_LAUNCH(what, kernel, blocks, RASTER_BLOCK, st, __VA_ARGS__)
-
 }  // namespace
 }  // namespace nerf
 
 using namespace nerf;
 
 extern "C" int nerf_raster_clear(uint64_t* keys, int H, int W, uint64_t* stats, void* stream) {
-  const int rc = raster_image_check("nerf_raster_clear", H, W);
+  const int rc = camera_image_check("nerf_raster_clear", H, W, CAMERA_MAX_SIDE);
   if (rc) return rc;
   NERF_REQUIRE(keys && stats, NERF_E_NULL, "nerf_raster_clear: NULL pointer");
-  hipStream_t st = as_stream(stream);
   const int64_t n = (int64_t)H * W;
-  RASTER_LAUNCH("nerf_raster_clear", raster_clear_kernel, raster_blocks(n), reinterpret_cast<unsigned long long*>(keys), n,
-                reinterpret_cast<unsigned long long*>(stats));
+  NERF_LAUNCH("nerf_raster_clear", raster_clear_kernel, blocks(n, RASTER_BLOCK), RASTER_BLOCK, as_stream(stream),
+              reinterpret_cast<unsigned long long*>(keys), n, reinterpret_cast<unsigned long long*>(stats));
   return NERF_OK;
 }
 
@@ -208,21 +184,21 @@ extern "C" int nerf_raster_draw(const float* verts, int64_t V, const int32_t* fa
                                 const nerf_tsdf_view* view_host, int H, int W, float near, int cull_backfaces, int small_max,
                                 uint64_t* keys, uint64_t* stats, void* stream) {
   const char* who = "nerf_raster_draw";
-  RasterView view;
-  int rc = raster_image_check(who, H, W);
-  if (!rc) rc = raster_mesh_check(who, V, F);
+  int rc = camera_image_check(who, H, W, CAMERA_MAX_SIDE);
+  if (!rc) rc = mesh_check(who, V, F);
   if (rc) return rc;
-  NERF_REQUIRE(face_base >= 0 && face_base <= RASTER_MAX_ITEMS - F, NERF_E_SHAPE, "%s: need 0 <= face_base <= 2^24 - F (got %lld)", who,
+  NERF_REQUIRE(face_base >= 0 && face_base <= MESH_MAX_ITEMS - F, NERF_E_SHAPE, "%s: need 0 <= face_base <= 2^24 - F (got %lld)", who,
                (long long)face_base);
   NERF_REQUIRE(cull_backfaces == 0 || cull_backfaces == 1, NERF_E_SHAPE, "%s: cull_backfaces must be 0 or 1 (got %d)", who, cull_backfaces);
   NERF_REQUIRE(small_max >= 0 && small_max <= RASTER_MAX_SMALL, NERF_E_SHAPE, "%s: need 0 <= small_max <= 2^30 (got %d)", who, small_max);
-  rc = raster_view_check(who, view_host, near, &view);
+  rc = camera_near_check(who, near);
+  if (!rc) rc = camera_view_check(who, view_host);
   if (rc) return rc;
   NERF_REQUIRE(keys && stats && (faces || F == 0) && (verts || V == 0), NERF_E_NULL, "%s: NULL pointer", who);
   if (F == 0) return NERF_OK;
-  hipStream_t st = as_stream(stream);
-  RASTER_LAUNCH(who, raster_draw_kernel, raster_blocks(F), verts, (int)V, faces, (int)F, (int)face_base, view, H, W, near, cull_backfaces,
-                small_max, reinterpret_cast<unsigned long long*>(keys), reinterpret_cast<unsigned long long*>(stats));
+  NERF_LAUNCH(who, raster_draw_kernel, blocks(F, RASTER_BLOCK), RASTER_BLOCK, as_stream(stream), verts, (int)V, faces, (int)F, (int)face_base,
+              *view_host, H, W, near, cull_backfaces, small_max, reinterpret_cast<unsigned long long*>(keys),
+              reinterpret_cast<unsigned long long*>(stats));
   return NERF_OK;
 }
 
@@ -230,29 +206,28 @@ extern "C" int nerf_raster_resolve(const uint64_t* keys, const float* verts, int
                                    const nerf_tsdf_view* view_host, int H, int W, float near, int32_t* face, float* bary, float* depth,
                                    float* acc, void* stream) {
   const char* who = "nerf_raster_resolve";
-  RasterView view;
-  int rc = raster_image_check(who, H, W);
-  if (!rc) rc = raster_mesh_check(who, V, F);
-  if (!rc) rc = raster_view_check(who, view_host, near, &view);
+  int rc = camera_image_check(who, H, W, CAMERA_MAX_SIDE);
+  if (!rc) rc = mesh_check(who, V, F);
+  if (!rc) rc = camera_near_check(who, near);
+  if (!rc) rc = camera_view_check(who, view_host);
   if (rc) return rc;
   NERF_REQUIRE(keys && face && bary && depth && acc && (faces || F == 0) && (verts || V == 0), NERF_E_NULL, "%s: NULL pointer", who);
-  hipStream_t st = as_stream(stream);
-  RASTER_LAUNCH(who, raster_resolve_kernel, raster_blocks((int64_t)H * W), reinterpret_cast<const unsigned long long*>(keys), verts, (int)V,
-                faces, (int)F, view, H, W, near, face, bary, depth, acc);
+  NERF_LAUNCH(who, raster_resolve_kernel, blocks((int64_t)H * W, RASTER_BLOCK), RASTER_BLOCK, as_stream(stream),
+              reinterpret_cast<const unsigned long long*>(keys), verts, (int)V, faces, (int)F, *view_host, H, W, near, face, bary, depth, acc);
   return NERF_OK;
 }
 
 extern "C" int nerf_raster_shade(const int32_t* face, const float* bary, const int32_t* faces, int64_t V, int64_t F, const float* colors,
                                  const float* rgb_in, const float* background, int per_pixel, int H, int W, float* rgb, void* stream) {
   const char* who = "nerf_raster_shade";
-  int rc = raster_image_check(who, H, W);
-  if (!rc) rc = raster_mesh_check(who, V, F);
+  int rc = camera_image_check(who, H, W, CAMERA_MAX_SIDE);
+  if (!rc) rc = mesh_check(who, V, F);
   if (rc) return rc;
   NERF_REQUIRE(per_pixel == 0 || per_pixel == 1, NERF_E_SHAPE, "%s: per_pixel must be 0 or 1 (got %d)", who, per_pixel);
   NERF_REQUIRE((colors != nullptr) != (rgb_in != nullptr), NERF_E_NULL, "%s: need exactly one of colors and rgb_in", who);
   NERF_REQUIRE(face && background && rgb && (rgb_in || (bary && (faces || F == 0))), NERF_E_NULL, "%s: NULL pointer", who);
-  hipStream_t st = as_stream(stream);
   const int64_t n = (int64_t)H * W;
-  RASTER_LAUNCH(who, raster_shade_kernel, raster_blocks(n), face, bary, faces, (int)V, (int)F, colors, rgb_in, background, per_pixel, n, rgb);
+  NERF_LAUNCH(who, raster_shade_kernel, blocks(n, RASTER_BLOCK), RASTER_BLOCK, as_stream(stream), face, bary, faces, (int)V, (int)F, colors,
+              rgb_in, background, per_pixel, n, rgb);
   return NERF_OK;
 }

@@ -46,13 +46,7 @@ __device__ __forceinline__ bool smooth_load(const float* __restrict__ verts, int
 
 // the corners of face f; false for an ignored face (an index outside [0, V) or two equal corners)
 __device__ __forceinline__ bool smooth_face(const int* __restrict__ faces, int f, int V, int* g) {
-  bool ok = true;
-#pragma unroll
-  for (int c = 0; c < 3; ++c) {
-    g[c] = faces[3 * f + c];
-    ok = ok && g[c] >= 0 && g[c] < V;
-  }
-  return ok && g[0] != g[1] && g[1] != g[2] && g[0] != g[2];
+  return mesh_corners(faces + 3 * f, V, g) && g[0] != g[1] && g[1] != g[2] && g[0] != g[2];
 }
 
 // ---- entries per vertex: 12 B read and three integer atomics per face.  cnt comes in zeroed.

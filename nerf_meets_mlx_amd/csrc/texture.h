@@ -19,7 +19,6 @@ namespace {
 
 constexpr int TEX_BLOCK = 256;
 constexpr int TEX_MIN_TEXELS = 2, TEX_MAX_TEXELS = 64;
-constexpr int64_t TEX_MAX_FACES = 1 << 24;
 
 struct TexLayout {
   int W, H, C, S, T;
@@ -36,7 +35,8 @@ inline int tex_cells_per_row(int64_t cells) {
 
 // W, H, C, S of F faces at T texels per leg; NERF_E_SHAPE with the largest T that fits when a side exceeds NERF_TEXTURE_MAX_SIDE
 inline int tex_layout(const char* who, int64_t F, int T, TexLayout* lay) {
-  NERF_REQUIRE(F >= 0 && F <= TEX_MAX_FACES, NERF_E_SHAPE, "%s: need 0 <= F <= 2^24 (got %lld)", who, (long long)F);
+  const int rc = mesh_check(who, 0, F);
+  if (rc) return rc;
   NERF_REQUIRE(T >= TEX_MIN_TEXELS && T <= TEX_MAX_TEXELS, NERF_E_SHAPE, "%s: need %d <= texels <= %d (got %d)", who, TEX_MIN_TEXELS,
                TEX_MAX_TEXELS, T);
   const int64_t cells = (F + 1) / 2;
@@ -53,8 +53,8 @@ inline int tex_layout(const char* who, int64_t F, int T, TexLayout* lay) {
 
 // the mesh arguments of rows, store and sample, and the chunk [p0, p0 + count) of the atlas that rows, store and project.hip walk
 inline int tex_mesh_check(const char* who, int64_t V, int64_t F, int T, TexLayout* lay) {
-  NERF_REQUIRE(V >= 0 && V <= TEX_MAX_FACES, NERF_E_SHAPE, "%s: need 0 <= V <= 2^24 (got %lld)", who, (long long)V);
-  return tex_layout(who, F, T, lay);
+  const int rc = mesh_check(who, V, F);
+  return rc ? rc : tex_layout(who, F, T, lay);
 }
 inline int tex_chunk_check(const char* who, const TexLayout& lay, int64_t p0, int64_t count) {
   const int64_t P = (int64_t)lay.W * lay.H;
@@ -89,14 +89,7 @@ __device__ __forceinline__ float tex_unit(float x) { x = tex_pos(x); return x < 
 
 // the corners of face f; false for an unused face (f outside [0, F)) or one with an index outside [0, V): nothing is read through it
 __device__ __forceinline__ bool tex_face(const int* __restrict__ faces, int f, int F, int V, int* g) {
-  if (f < 0 || f >= F) return false;
-  bool ok = true;
-#pragma unroll
-  for (int c = 0; c < 3; ++c) {
-    g[c] = faces[3 * (int64_t)f + c];
-    ok = ok && g[c] >= 0 && g[c] < V;
-  }
-  return ok;
+  return f >= 0 && f < F && mesh_corners(faces + 3 * (int64_t)f, V, g);
 }
 
 // position x and unit normal n (0 where the interpolated normal has no direction) of the point with barycentrics (wb, wc) of the

@@ -117,10 +117,6 @@ __global__ void __launch_bounds__(TEX_BLOCK) tex_sample_kernel(const uint8_t* __
   }
 }
 
-inline unsigned tex_blocks(int64_t n) { return (unsigned)((n + TEX_BLOCK - 1) / TEX_BLOCK); }
-
-#define TEX_LAUNCH(what, kernel, blocks, ...) NERF_LAUNCH(what, kernel, blocks, TEX_BLOCK, st, __VA_ARGS__)
-
 }  // namespace
 }  // namespace nerf
 
@@ -143,8 +139,8 @@ extern "C" int nerf_texture_rows(const float* verts, const float* normals, int64
   if (rc) return rc;
   if (count == 0) return NERF_OK;
   NERF_REQUIRE(rows && (faces || F == 0) && ((verts && normals) || V == 0), NERF_E_NULL, "nerf_texture_rows: NULL pointer");
-  hipStream_t st = as_stream(stream);
-  TEX_LAUNCH("nerf_texture_rows", tex_rows_kernel, tex_blocks(count), verts, normals, (int)V, faces, lay, p0, count, rows);
+  NERF_LAUNCH("nerf_texture_rows", tex_rows_kernel, blocks(count, TEX_BLOCK), TEX_BLOCK, as_stream(stream), verts, normals, (int)V, faces, lay,
+              p0, count, rows);
   return NERF_OK;
 }
 
@@ -157,9 +153,8 @@ extern "C" int nerf_texture_store(const float* raw, int64_t V, const int32_t* fa
   if (count == 0) return NERF_OK;
   NERF_REQUIRE(raw && image && (faces || F == 0), NERF_E_NULL, "nerf_texture_store: NULL pointer");
   NERF_REQUIRE(((uintptr_t)raw & 15) == 0, NERF_E_SHAPE, "nerf_texture_store: raw must be 16-byte aligned");
-  hipStream_t st = as_stream(stream);
-  TEX_LAUNCH("nerf_texture_store", tex_store_kernel, tex_blocks(count), reinterpret_cast<const float4*>(raw), (int)V, faces, lay, p0,
-             count, image);
+  NERF_LAUNCH("nerf_texture_store", tex_store_kernel, blocks(count, TEX_BLOCK), TEX_BLOCK, as_stream(stream), reinterpret_cast<const float4*>(raw),
+              (int)V, faces, lay, p0, count, image);
   return NERF_OK;
 }
 
@@ -169,8 +164,7 @@ extern "C" int nerf_texture_uv(int64_t F, int texels, float* uv, void* stream) {
   if (rc) return rc;
   if (F == 0) return NERF_OK;
   NERF_REQUIRE(uv, NERF_E_NULL, "nerf_texture_uv: NULL uv");
-  hipStream_t st = as_stream(stream);
-  TEX_LAUNCH("nerf_texture_uv", tex_uv_kernel, tex_blocks(F), lay, uv);
+  NERF_LAUNCH("nerf_texture_uv", tex_uv_kernel, blocks(F, TEX_BLOCK), TEX_BLOCK, as_stream(stream), lay, uv);
   return NERF_OK;
 }
 
@@ -185,8 +179,7 @@ extern "C" int nerf_texture_sample(const uint8_t* image, const float* verts, con
   NERF_REQUIRE(image && sample_face && bary && rgb, NERF_E_NULL, "nerf_texture_sample: NULL pointer");
   NERF_REQUIRE(!rows || ((faces || F == 0) && ((verts && normals) || V == 0)), NERF_E_NULL,
                "nerf_texture_sample: rows need verts, normals and faces");
-  hipStream_t st = as_stream(stream);
-  TEX_LAUNCH("nerf_texture_sample", tex_sample_kernel, tex_blocks(n), image, verts, normals, (int)V, faces, lay, sample_face, bary, n,
-             rgb, rows);
+  NERF_LAUNCH("nerf_texture_sample", tex_sample_kernel, blocks(n, TEX_BLOCK), TEX_BLOCK, as_stream(stream), image, verts, normals, (int)V, faces,
+              lay, sample_face, bary, n, rgb, rows);
   return NERF_OK;
 }

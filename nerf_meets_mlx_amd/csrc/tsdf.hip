@@ -1,20 +1,15 @@
 // TSDF fusion of rendered depth / opacity maps into a truncated signed distance volume on the mesh-extraction lattice
 // (KinectFusion; nerfstudio's TSDF export).  Semantics in include/nerf_hip.h "TSDF fusion"; tests/_tsdf_ref.py reproduces every
-// output bit for bit.  No reference counterpart.  The lattice, its box and its cell centres are lattice.h's.  One lane per voxel: a
-// lane loads its D, Wt and flags once, folds up to NERF_TSDF_MAX_VIEWS views into them in registers, in order, and stores once --
-// 18 B of state per voxel cross HBM per launch and not per view; the maps (4 B per pixel each) are gathered, and at 16 views of
-// 800 x 800 those gathers, not the state, are most of the launch time.  The view parameters are kernel
-// arguments (scalar loads, uniform over the launch).  Every voxel has one writer and the views are folded in call order:
-// bit-reproducible, and identical to one launch per view.
-#include "lattice.h"
+// output bit for bit.  No reference counterpart.  The lattice, its box and its cell centres are lattice.h's, the camera and the
+// nearest pixel of a map camera.h's.  One lane per voxel: a lane loads its D, Wt and flags once, folds up to NERF_TSDF_MAX_VIEWS
+// views into them in registers, in order, and stores once -- 18 B of state per voxel cross HBM per launch and not per view; the
+// maps (4 B per pixel each) are gathered, and at 16 views of 800 x 800 those gathers, not the state, are most of the launch time
+// (DESIGN.md section 21).  The view parameters are kernel arguments (scalar loads, uniform over the launch).  Every voxel has one
+// writer and the views are folded in call order: bit-reproducible, and identical to one launch per view.
+#include "camera.h"
 
 namespace nerf {
 namespace {
-
-struct TsdfViews {
-  nerf_tsdf_view v[NERF_TSDF_MAX_VIEWS];
-};
-static_assert(sizeof(nerf_tsdf_view) == 16 * sizeof(float), "16 floats per view");
 
 __global__ void __launch_bounds__(LATTICE_BLOCK) tsdf_reset_kernel(float* __restrict__ D, float* __restrict__ Wt,
                                                                uint8_t* __restrict__ flags, int64_t n3) {
@@ -27,7 +22,7 @@ __global__ void __launch_bounds__(LATTICE_BLOCK) tsdf_reset_kernel(float* __rest
 
 // ---- integrate: 4 + 4 + 1 B read and written per voxel and launch; per view and voxel at most two gathered map reads.
 __global__ void __launch_bounds__(LATTICE_BLOCK) tsdf_integrate_kernel(float* __restrict__ D, float* __restrict__ Wt,
-                                                                   uint8_t* __restrict__ flags, Lattice bx, TsdfViews views,
+                                                                   uint8_t* __restrict__ flags, Lattice bx, CameraViews views,
                                                                    int n, int H, int W, const float* __restrict__ depth,
                                                                    const float* __restrict__ acc, float tau, float acc_min,
                                                                    float far, int carve) {
@@ -41,21 +36,16 @@ __global__ void __launch_bounds__(LATTICE_BLOCK) tsdf_integrate_kernel(float* __
   const uint8_t f_in = flags[lg];
   uint8_t f = f_in;
   const float neg_tau = 0.0f - tau;
-  const float fW = (float)W, fH = (float)H;
   const int64_t HW = (int64_t)H * W;
   for (int s = 0; s < n; ++s) {
-    const nerf_tsdf_view& vw = views.v[s];
-    const float q0 = p[0] - vw.c2w[3], q1 = p[1] - vw.c2w[7], q2 = p[2] - vw.c2w[11];
-    const float xc = (vw.c2w[0] * q0 + vw.c2w[4] * q1) + vw.c2w[8] * q2;
-    const float yc = (vw.c2w[1] * q0 + vw.c2w[5] * q1) + vw.c2w[9] * q2;
-    const float zw = (vw.c2w[2] * q0 + vw.c2w[6] * q1) + vw.c2w[10] * q2;
-    const float zc = 0.0f - zw;
+    float cam[3], u, v;
+    camera_point(views.v[s], p, cam);
+    const float zc = cam[2];
     if (!(zc > 0.0f)) continue;                                            // behind the camera, or NaN
-    const float u = vw.fx * div_rn(xc, zc) + vw.cx;
-    const float v = vw.cy - vw.fy * div_rn(yc, zc);
-    const float fu = floorf(u + 0.5f), fv = floorf(v + 0.5f);
-    if (!(fu >= 0.0f && fu < fW && fv >= 0.0f && fv < fH)) continue;       // outside the image, or not finite: before the cast
-    const int64_t pix = s * HW + ((int64_t)(int)fv * W + (int)fu);
+    camera_pixel(views.v[s], cam, &u, &v);
+    int64_t pix;
+    if (!camera_nearest(u, v, H, W, &pix)) continue;                       // outside the image, or not finite
+    pix += s * HW;
     const float a = acc[pix], sd = depth[pix];
     if (a != a || sd != sd) continue;
     float d;
@@ -125,13 +115,9 @@ extern "C" int nerf_tsdf_integrate(float* D, float* Wt, uint8_t* flags, int res,
   NERF_REQUIRE(D && Wt && flags, NERF_E_NULL, "%s: NULL state pointer", who);
   if (n == 0) return NERF_OK;
   NERF_REQUIRE(views_host && depth && acc, NERF_E_NULL, "%s: NULL views / depth / acc", who);
-  TsdfViews views;
-  for (int s = 0; s < NERF_TSDF_MAX_VIEWS; ++s) {
-    views.v[s] = views_host[s < n ? s : 0];
-    if (s >= n) continue;
-    const float* x = views.v[s].c2w;                         // the 12 pose numbers, then fx, fy, cx, cy
-    for (int q = 0; q < 16; ++q) NERF_REQUIRE(std::isfinite(x[q]), NERF_E_SHAPE, "%s: view %d: non-finite camera number %d", who, s, q);
-  }
+  CameraViews views;
+  rc = camera_views_check(who, views_host, n, &views);
+  if (rc) return rc;
   hipLaunchKernelGGL(tsdf_integrate_kernel, dim3(lattice_blocks(res)), dim3(LATTICE_BLOCK), 0, as_stream(stream), D, Wt, flags, bx,
                      views, n, H, W, depth, acc, trunc, acc_min, far, carve);
   return check_launch(who);

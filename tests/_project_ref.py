@@ -1,9 +1,10 @@
 """numpy reference of include/nerf_hip.h "view-projected texture" (a helper module, not a test): the texels are those of
-tests/_texture_ref.py, the camera that of tests/_raster_ref.py, every float step a float32 array operation in the header's order
+tests/_texture_ref.py, the camera that of tests/_camera_ref.py, every float step a float32 array operation in the header's order
 (numpy rounds each on its own; its division and square root are correctly rounded).  Same state, image and seen as
 csrc/project.hip, bit for bit."""
 import numpy as np
 
+from tests import _camera_ref as C
 from tests import _raster_ref as R
 from tests import _texture_ref as TX
 
@@ -36,16 +37,14 @@ def observe(view, image, depth, acc, x, n, near, depth_tol, cos_min, acc_min):
     t = np.asarray(view, F32)[[3, 7, 11]]
     fW, fH = F32(W), F32(H)
     with np.errstate(all="ignore"):
-        u, v, zc = R.project(x, view)
+        u, v, zc = C.project(x, view)
         got = zc >= F32(near)
         e = t[None, :] - x
         L = np.sqrt((e[:, 0] * e[:, 0] + e[:, 1] * e[:, 1]) + e[:, 2] * e[:, 2])
         cosv = ((n[:, 0] * e[:, 0] + n[:, 1] * e[:, 1]) + n[:, 2] * e[:, 2]) / L
         got &= cosv >= F32(cos_min)
-        fu, fv = np.floor(u + F32(0.5)), np.floor(v + F32(0.5))
-        inside = (fu >= 0) & (fu < fW) & (fv >= 0) & (fv < fH)
+        inside, pix = C.nearest(u, v, H, W)
         got &= inside
-        pix = np.where(inside, fv, 0).astype(np.int64) * W + np.where(inside, fu, 0).astype(np.int64)
         a, s = acc[pix], depth[pix]
         got &= ~(np.isnan(a) | np.isnan(s) | (a < F32(acc_min)))
         ez = s / a - zc

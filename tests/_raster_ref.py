@@ -3,6 +3,9 @@ steps, one rounding per operation in the header's order; int64 for the snapped c
 minimum by np.minimum.at.  Same outputs and the same stats as csrc/raster.hip, bit for bit."""
 import numpy as np
 
+from tests import _camera_ref as C
+from tests._camera_ref import intrinsics, project, view_of  # noqa: F401  (the camera; the names the tests use)
+
 F32 = np.float32
 EMPTY = np.uint64(0xFFFFFFFFFFFFFFFF)
 SNAP = 256
@@ -11,44 +14,9 @@ OK, DROP_DEPTH, DROP_OTHER = 0, 1, 2
 SMALL_MAX = 16                                                          # NERF_RASTER_SMALL_MAX
 
 
-def view_of(c2w, K):
-    """float32 [16]: c2w [3, 4] row-major, then fx, fy, cx, cy (nerf_tsdf_view; engine.mesh.tsdf_views)."""
-    v = np.empty(16, F32)
-    v[:12] = np.asarray(c2w, np.float64)[:3, :4].reshape(12)
-    K = np.asarray(K, np.float64)
-    v[12:] = [K[0, 0], K[1, 1], K[0, 2], K[1, 2]]
-    return v
-
-
 def look_at(eye, target, up=(0.0, 1.0, 0.0)):
-    """c2w [3, 4] float64 of a camera at `eye` looking at `target` along its -z, x to the right, y up."""
-    eye, target = np.asarray(eye, np.float64), np.asarray(target, np.float64)
-    z = eye - target
-    z /= np.linalg.norm(z)
-    x = np.cross(np.asarray(up, np.float64), z)
-    x /= np.linalg.norm(x)
-    y = np.cross(z, x)
-    return np.concatenate([np.stack([x, y, z], 1), eye[:, None]], 1)
-
-
-def intrinsics(H, W, fov=0.9):
-    f = 0.5 * W / np.tan(0.5 * fov)
-    return np.array([[f, 0.0, 0.5 * W], [0.0, f, 0.5 * H], [0.0, 0.0, 1.0]])
-
-
-def project(p, view):
-    """(u, v, zc) float32 of points p [n, 3] float32."""
-    p = np.asarray(p, F32).reshape(-1, 3)
-    c = np.asarray(view, F32)
-    with np.errstate(all="ignore"):
-        q0, q1, q2 = p[:, 0] - c[3], p[:, 1] - c[7], p[:, 2] - c[11]
-        xc = (c[0] * q0 + c[4] * q1) + c[8] * q2
-        yc = (c[1] * q0 + c[5] * q1) + c[9] * q2
-        zw = (c[2] * q0 + c[6] * q1) + c[10] * q2
-        zc = F32(0.0) - zw
-        u = c[12] * (xc / zc) + c[14]
-        v = c[15] - c[13] * (yc / zc)
-    return u.astype(F32), v.astype(F32), zc.astype(F32)
+    """_camera_ref.look_at with y up by default, for which its fallback for a vertical view changes nothing."""
+    return C.look_at(eye, target, up)
 
 
 def area2(X, Y):

@@ -1,10 +1,11 @@
 """numpy float32 emulation of include/nerf_hip.h "TSDF fusion" (csrc/tsdf.hip): every intermediate is an np.float32 array, one
 rounding per operation, in the header's order (numpy's float32 +, -, *, / are IEEE, correctly rounded), a plain loop over the
-views.  Also the analytic depth / opacity maps of a sphere for a pinhole camera of the project's convention (camera directions
+views; the camera is tests/_camera_ref.py's.  Also the analytic depth / opacity maps of a sphere for a pinhole camera of the project's convention (camera directions
 [(col - cx) / fx, -(row - cy) / fy, -1], c2w [3, 4])."""
 import numpy as np
 
 from tests import _mesh_ref as M
+from tests._camera_ref import intrinsics, look_at, nearest, project, view_of as view_floats  # noqa: F401  (the tests' names)
 
 _F = np.float32
 MAX_VIEWS = 16
@@ -25,13 +26,6 @@ class State:
         return s
 
 
-def view_floats(c2w, K):
-    """The 16 floats of a view: c2w [3, 4] row-major as float32, then fx, fy, cx, cy cast once from the K doubles."""
-    c = np.asarray(c2w, np.float64)[:3, :4].astype(_F).reshape(12)
-    K = np.asarray(K, np.float64)
-    return np.concatenate([c, np.array([K[0, 0], K[1, 1], K[0, 2], K[1, 2]], np.float64).astype(_F)]).astype(_F)
-
-
 def classify_view(R, lo, hi, view, H, W, depth, acc, tau, acc_min, far, carve):
     """The per-voxel rule of one view as masks over the R^3 voxels, each voxel in exactly one of
     behind (!(zc > 0)), outside (off the image or not finite), nan_acc, nan_depth (acc fine, depth NaN), low_skipped (acc < acc_min,
@@ -39,26 +33,15 @@ def classify_view(R, lo, hi, view, H, W, depth, acc, tau, acc_min, far, carve):
     plus "d" (float32, valid where empty | surface), "zero_pixel" (acc == 0 and depth == 0 under the voxel) and "zc"."""
     with np.errstate(all="ignore"):
         p = M.lattice_points(R, lo, hi)                                    # [R^3, 3] float32
-        view = np.asarray(view, _F)
-        r = view[:12].reshape(3, 4)
-        fx, fy, cx, cy = view[12:16]
         tau, acc_min, far = _F(tau), _F(acc_min), _F(far)
         depth = np.asarray(depth, _F).reshape(-1)
         acc = np.asarray(acc, _F).reshape(-1)
         assert depth.size == H * W and acc.size == H * W
-        q = [(p[:, a] - r[a, 3]).astype(_F) for a in range(3)]
-        cam = [((r[0, b] * q[0] + r[1, b] * q[1]).astype(_F) + r[2, b] * q[2]).astype(_F) for b in range(3)]
-        zc = (_F(0.0) - cam[2]).astype(_F)
+        u, v, zc = project(p, view)
         front = zc > 0
-        u = (fx * (cam[0] / zc).astype(_F) + cx).astype(_F)
-        v = (cy - (fy * (cam[1] / zc).astype(_F)).astype(_F)).astype(_F)
-        fu = np.floor((u + _F(0.5)).astype(_F)).astype(_F)
-        fv = np.floor((v + _F(0.5)).astype(_F)).astype(_F)
-        inside = front & (fu >= 0) & (fu < _F(W)) & (fv >= 0) & (fv < _F(H))   # NaN and +-inf fail
-        i = np.where(inside, fu, 0).astype(np.int64)
-        j = np.where(inside, fv, 0).astype(np.int64)
-        a = acc[j * W + i]
-        s = depth[j * W + i]
+        in_map, pix = nearest(u, v, H, W)                                  # NaN and +-inf fail
+        inside = front & in_map
+        a, s = acc[pix], depth[pix]
         nan_acc = inside & np.isnan(a)
         nan_depth = inside & ~np.isnan(a) & np.isnan(s)
         ok = inside & ~np.isnan(a) & ~np.isnan(s)
@@ -116,24 +99,6 @@ def default_trunc(R, lo, hi):
 
 
 # ------------------------------------------------------------------------------------------------ analytic fixtures
-def look_at(eye, target=(0.0, 0.0, 0.0), up=(0.0, 0.0, 1.0)):
-    """c2w [3, 4] float64 of a camera at `eye` looking at `target` (it looks along its -z; +y is up in the image)."""
-    eye, target, up = (np.asarray(x, np.float64) for x in (eye, target, up))
-    zax = eye - target
-    zax /= np.linalg.norm(zax)
-    if abs(np.dot(zax, up)) > 0.99:
-        up = np.array([0.0, 1.0, 0.0])
-    xax = np.cross(up, zax)
-    xax /= np.linalg.norm(xax)
-    yax = np.cross(zax, xax)
-    return np.concatenate([np.stack([xax, yax, zax], 1), eye[:, None]], 1)
-
-
-def intrinsics(H, W, fov=0.9):
-    f = 0.5 * W / np.tan(0.5 * fov)
-    return np.array([[f, 0.0, 0.5 * W], [0.0, f, 0.5 * H], [0.0, 0.0, 1.0]])
-
-
 def sphere_maps(c2w, K, H, W, radius, centre=(0.0, 0.0, 0.0)):
     """(depth [H W], acc [H W]) float32 of an opaque sphere: acc = 1 and depth = the ray parameter z of the first hit of
     o + z d, d = R [(col - cx) / fx, -(row - cy) / fy, -1] (distance along the optical axis); both 0 where the ray misses."""

@@ -51,7 +51,7 @@ static void run(const char* name, const Acc& a) {
   }
   TexLayout lay;
   ProjectRule rule;
-  ProjectViews out;
+  CameraViews out;
   memset(&out, 0, sizeof(out));
   bool work = true;
   const int rc = project_accumulate_check("t", a.verts, a.normals, a.V, a.faces, a.F, a.T, a.p0, a.count,
