@@ -33,13 +33,15 @@ __device__ __forceinline__ void write_ray(int64_t i, int64_t p, int W, const Cam
   for (int a = 0; a < 3; ++a)
     d[a] = dx * (double)cam.r[3 * a + 0] + dy * (double)cam.r[3 * a + 1] + dz * (double)cam.r[3 * a + 2];
   const float fx_ = (float)d[0], fy_ = (float)d[1], fz_ = (float)d[2];
-  // viewdirs = d / |d| on the float32 d (entrypoints/__test_nerf.py:62-64 works on the f32 array)
-  const float inv = 1.0f / sqrtf(fx_ * fx_ + fy_ * fy_ + fz_ * fz_);
+  // viewdirs = d / |d| on the float32 d (entrypoints/__test_nerf.py:62-64 works on the f32 array), normalised in float64 and
+  // rounded once: within 1 ulp of the exact unit vector (float32 arithmetic here erred by up to 2.6 ulp)
+  const double x = fx_, y = fy_, z = fz_;
+  const double inv = 1.0 / sqrt(x * x + y * y + z * z);
   float* o = rays + i * NERF_RAY_STRIDE;
   o[0] = cam.t[0]; o[1] = cam.t[1]; o[2] = cam.t[2];
   o[3] = fx_; o[4] = fy_; o[5] = fz_;
   o[6] = near; o[7] = far;
-  o[8] = fx_ * inv; o[9] = fy_ * inv; o[10] = fz_ * inv;
+  o[8] = (float)(x * inv); o[9] = (float)(y * inv); o[10] = (float)(z * inv);
   if (coords) { coords[2 * i] = row; coords[2 * i + 1] = col; }
 }
 

@@ -3,7 +3,11 @@ CPU oracle on identical seeded inputs, and against the reference-run golden fixt
 
 Tolerances (stated per test):
   * integer / index outputs: bit-exact.
-  * float32 kernels (rays, sampling, compositing, encoders, Adam): a few ulp, written as atol/rtol.
+  * float32 kernels (rays, sampling, compositing, encoders, Adam): a few ulp, written as atol/rtol IN THIS FILE.  The same units are
+    held bit for bit to float32 host mirrors elsewhere: ray generation, the fused batch, the NDC warp and the row gather in
+    tests/test_gpu_rays.py; depth sampling, the importance sampler and the MSE gradient in tests/test_gpu_render.py (compositing
+    within a derived expf bound); the hash grid in tests/test_gpu_hashgrid.py; SSIM on its float64 sums within a derived
+    summation bound in tests/test_gpu_ssim.py.
   * the MLP at the DEFAULT precision (22: the reference's float32 tolerance, split 16-bit MFMA operands) vs the pure float32
     oracle: rel-to-max 1e-4 on network outputs, 1e-3-class bars on rendered / trained quantities (stated per test).
   * the MLP at precision=16 (bf16 MFMA operands: the DECLARED reduced-precision mode, opt-in; the `mlp_variant` kernels of
