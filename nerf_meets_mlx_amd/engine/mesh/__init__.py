@@ -1,0 +1,22 @@
+"""Mesh extraction from a trained field, and what is done with the mesh (include/nerf_hip.h "mesh extraction" and the sections
+behind it, DESIGN.md section 14 onwards; the map of this package is DESIGN.md section 36).  The reference has no such export; this
+is Instant-NGP's.  One module per stage, and every name of theirs is a name of this package:
+
+  _checks (the three argument tests) <- _base (Mesh, the lattice arguments, the stage hook) <- surface (simplify, smooth) <- volume
+  (density volume, marching cubes, components, opening, extract / mesh_volume); _base <- tsdf (TSDFVolume, tsdf_views); _base <-
+  texture (atlas bake and lookup, mip pyramid) <- raster (rasterize, face_lod, render_mesh, render_mesh_mip) <- project
+  (project_texture); texture <- files (PLY, OBJ, PNG)."""
+from ._base import CHUNK, MAX_RES, SIMPLIFY_MAX_ITEMS, Mesh, _box, _check_mesh_tensors, _mark, check_mesh_args
+from .files import _PNG_MAGIC, _png_chunk, _replace_file, png_array, png_bytes, read_obj, read_ply, write_obj, write_ply
+from .project import PROJECT_COS_MIN, PROJECT_DEPTH_TOL_CELLS, PROJECT_MAX_VIEWS, PROJECT_MODES, check_project_args, project_texture
+from .raster import (RASTER_MAX_SIDE, RASTER_NEAR, RASTER_SMALL_MAX, MeshFrame, _raster_background, _raster_view, check_lod_scale,
+                     check_raster_args, face_lod, rasterize, render_mesh, render_mesh_mip)
+from .surface import (PLACEMENTS, SIMPLIFY_MAX_CLUSTERS, SMOOTH_MAX_ITERATIONS, _simplify, _smooth, check_simplify_args,
+                      check_simplify_grid, check_smooth_args, check_smooth_params, check_surface_options, simplify, smooth)
+from .texture import (MIP_MAX_LEVELS, TEXTURE_MAX_SIDE, TEXTURE_MAX_TEXELS, Texture, TexturePyramid, _check_pyramid, _check_texture,
+                      bake_texture, build_mipmaps, check_texture_args, mip_levels, sample_texture, sample_texture_mip, texture_layout)
+from .tsdf import TSDF_MAX_VIEWS, TSDFVolume, _k_of, check_tsdf_args, tsdf_views
+from .volume import (EXP, MAX_OPENING_RADIUS, RELU, Components, _check_radius, _check_volume, _marching_cubes, _open_components,
+                     _rows_into, check_component_args, check_opening_args, check_volume_options, connected_components, density_volume,
+                     erode, extract, filter_components, filter_volume, lattice_rows, marching_cubes, mesh_volume, open_components,
+                     reconstruct, vertex_colors)

@@ -476,13 +476,9 @@ class NGPTrainer(Trainer):
         from . import mesh
         lo, hi = self._mesh_box(aabb)
         R = mesh.check_mesh_args(resolution, lo, hi, 0.0)[0]
-        mesh.check_component_args(min_component, largest_only, R)
-        mesh.check_opening_args(opening_radius)
+        volume_options = mesh.check_volume_options(min_component, largest_only, opening_radius, R)
         mesh.check_tsdf_args(trunc, acc_min, self.far, carve, min_views, self.H, self.W)
-        simplify_grid = mesh.check_simplify_grid(simplify_grid)
-        if simplify_placement not in mesh.PLACEMENTS:
-            raise ValueError(f"simplify placement must be one of {sorted(mesh.PLACEMENTS)}, got {simplify_placement!r}")
-        mesh.check_smooth_params(smooth_iterations, smooth_lambda, smooth_mu)
+        surface_options = mesh.check_surface_options(simplify_grid, simplify_placement, smooth_iterations, smooth_lambda, smooth_mu)
         poses = self.poses if poses is None else poses
         views = mesh.tsdf_views(poses, self.K)
         tsdf = mesh.TSDFVolume(R, lo, hi, trunc=trunc, device=self.device)
@@ -494,13 +490,9 @@ class NGPTrainer(Trainer):
                            acc_min=acc_min, far=self.far, carve=carve)
         vol = tsdf.volume(min_views)
         del tsdf
-        if opening_radius > 0:
-            vol = mesh.open_components(vol, 0.0, opening_radius, min_component, largest_only)
-        elif min_component > 1 or largest_only:
-            vol = mesh.filter_components(vol, 0.0, min_component, largest_only)
+        vol = mesh.filter_volume(vol, 0.0, *volume_options)
         query = self._mesh_field()[0] if colors else None          # (reading the field joins the comm stream: only when it is asked)
-        return mesh.mesh_volume(query, vol, 0.0, lo, hi, colors, simplify_grid, simplify_placement, smooth_iterations, smooth_lambda,
-                                smooth_mu)
+        return mesh.mesh_volume(query, vol, 0.0, lo, hi, colors, *surface_options)
 
     def train_step(self, rays=None, target=None, u=None, background=None) -> Dict[str, torch.Tensor]:
         """background (random_background trainers only, with explicit rays and target [B, 4]): the colours bg [B, 3] behind the

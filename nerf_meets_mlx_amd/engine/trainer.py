@@ -235,10 +235,8 @@ class Trainer:
         roughness of the field goes, the faces stay.  Runs on this rank only: no collective, any rank may call it alone."""
         from . import mesh
         lo, hi = self._mesh_box(aabb)
-        mesh.check_component_args(min_component, largest_only, mesh.check_mesh_args(resolution, lo, hi, threshold)[0])
-        mesh.check_opening_args(opening_radius)
-        mesh.check_simplify_grid(simplify_grid)
-        mesh.check_smooth_params(smooth_iterations, smooth_lambda, smooth_mu)
+        mesh.check_volume_options(min_component, largest_only, opening_radius, mesh.check_mesh_args(resolution, lo, hi, threshold)[0])
+        mesh.check_surface_options(simplify_grid, simplify_placement, smooth_iterations, smooth_lambda, smooth_mu)
         query, act = self._mesh_field()
         return mesh.extract(query, act, resolution, threshold, lo, hi, colors=colors, device=self.device,
                             min_component=min_component, largest_only=largest_only, opening_radius=opening_radius,

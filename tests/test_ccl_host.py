@@ -1,6 +1,6 @@
 """Connected components, host side (no GPU): the reference tests/_ccl_ref.py against first principles (a breadth-first search
 written out here) on small volumes, the sub-mesh property of include/nerf_hip.h "connected components" through the marching
-cubes of tests/_mesh_ref.py, the argument checks of engine/mesh.py and of the C entry points, and the exported symbols."""
+cubes of tests/_mesh_ref.py, the argument checks of engine/mesh/volume.py and of the C entry points, and the exported symbols."""
 import ctypes as C
 import os
 import re

@@ -1,4 +1,4 @@
-"""Connected components on the GPU (csrc/ccl.hip, engine/mesh.py connected_components / filter_components, extract_mesh's
+"""Connected components on the GPU (csrc/ccl.hip, engine/mesh/volume.py connected_components / filter_components, extract_mesh's
 min_component / largest_only) against the reference of tests/_ccl_ref.py: labels, sizes, stats and filtered volumes bit for bit,
 into sentinel outputs with one spare element and a poisoned workspace, at lattice sizes that are no multiple of a wave or a
 workgroup, on the volumes a labelling kernel goes wrong on; reproducibility; the filter through marching cubes; a march-mode

@@ -1,4 +1,4 @@
-"""Mesh extraction on the GPU (csrc/mesh.hip, engine/mesh.py, Trainer.density_volume / extract_mesh) against the numpy reference
+"""Mesh extraction on the GPU (csrc/mesh.hip, engine/mesh, Trainer.density_volume / extract_mesh) against the numpy reference
 of tests/_mesh_ref.py: vertices and faces bit for bit (normals within 1e-6) at lattice sizes that are no multiple of a workgroup,
 with iso values present in the volume, NaN / +-inf corners and constant volumes, into poisoned buffers; reproducibility; the
 density volume against the fields' query of torch-built lattice rows; the vertex colours; a march-mode trainer's mesh through

@@ -1,4 +1,4 @@
-"""The texture mip pyramid on the GPU (csrc/mip.hip, engine/mesh.py build_mipmaps / face_lod / sample_texture_mip / render_mesh_mip,
+"""The texture mip pyramid on the GPU (csrc/mip.hip, engine/mesh build_mipmaps / face_lod / sample_texture_mip / render_mesh_mip,
 Trainer.mip_texture / render_mesh_mip / mesh_psnr_mip) against the numpy reference of tests/_mip_ref.py: bytes and float bits
 compared as integers -- no tolerance, the rule is exact -- into poisoned or sentinel-filled outputs."""
 import ctypes as C

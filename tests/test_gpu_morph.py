@@ -1,4 +1,4 @@
-"""Morphological opening on the GPU (csrc/morph.hip, engine/mesh.py erode / reconstruct / open_components, extract_mesh's
+"""Morphological opening on the GPU (csrc/morph.hip, engine/mesh/volume.py erode / reconstruct / open_components, extract_mesh's
 opening_radius) against the reference of tests/_morph_ref.py: eroded and reconstructed volumes and their stats bit for bit, into
 sentinel outputs with one spare element and a poisoned workspace, at lattice sizes around the 64-voxel mask word (word tails,
 exactly one word, one word + 1), at radii up to the largest (r >= R / 2: an empty core, everything dropped), on the volumes a

@@ -1,4 +1,4 @@
-"""The projective texture bake on the GPU (csrc/project.hip, engine/mesh.py project_texture, Trainer.project_texture) against the
+"""The projective texture bake on the GPU (csrc/project.hip, engine/mesh/project.py project_texture, Trainer.project_texture) against the
 numpy reference of tests/_project_ref.py: state, image and seen compared as integers -- no tolerance, the rule is exact -- into
 sentinel-filled outputs with a spare row; chunks, repeats and the split of the views over launches change no bit; NaN maps and
 images, bad faces, texels outside the image or behind the near plane, the smallest images, no faces and no views; and end to end

@@ -1,4 +1,4 @@
-"""The mesh rasteriser on the GPU (csrc/raster.hip, engine/mesh.py rasterize / render_mesh, Trainer.render_mesh / mesh_psnr)
+"""The mesh rasteriser on the GPU (csrc/raster.hip, engine/mesh/raster.py rasterize / render_mesh, Trainer.render_mesh / mesh_psnr)
 against the numpy reference of tests/_raster_ref.py: keys, face, barycentrics, depth, acc, stats and the vertex-colour picture
 compared as integers -- no tolerance, the rule is exact -- into sentinel-filled outputs with a spare row, the key buffer poisoned
 before the clear; every small_max gives the same bits; face order and chunked draws change nothing; dropped faces are counted;

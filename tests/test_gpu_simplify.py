@@ -1,4 +1,4 @@
-"""Mesh simplification on the GPU (csrc/simplify.hip, engine/mesh.py simplify, Trainer.extract_mesh / NGPTrainer.extract_mesh_tsdf
+"""Mesh simplification on the GPU (csrc/simplify.hip, engine/mesh/surface.py simplify, Trainer.extract_mesh / NGPTrainer.extract_mesh_tsdf
 with simplify_grid) against the numpy reference of tests/_simplify_ref.py: vertex, normal and colour bits compared as integers and
 faces exactly -- no tolerance anywhere, the rule is exact -- into sentinel-filled outputs with a poisoned workspace;
 reproducibility under a permutation of the input; empty meshes and total collapse; long runs of faces on one vertex set; the C

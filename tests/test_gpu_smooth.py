@@ -1,4 +1,4 @@
-"""Mesh smoothing on the GPU (csrc/smooth.hip, engine/mesh.py smooth, mesh_volume / Trainer.extract_mesh with smooth_iterations)
+"""Mesh smoothing on the GPU (csrc/smooth.hip, engine/mesh smooth, mesh_volume / Trainer.extract_mesh with smooth_iterations)
 against the numpy reference of tests/_smooth_ref.py: vertex, normal and colour-row bits compared as integers -- no tolerance
 anywhere, the rule is exact -- into sentinel-filled outputs with a poisoned workspace; both parities of the ping-pong with and
 without the mu half-step; rows longer than a wave and than a workgroup; ignored faces, a NaN vertex, an unreferenced vertex;

@@ -1,4 +1,4 @@
-"""The texture atlas on the GPU (csrc/texture.hip, engine/mesh.py bake_texture / sample_texture, Trainer.texture_mesh) against
+"""The texture atlas on the GPU (csrc/texture.hip, engine/mesh/texture.py bake_texture / sample_texture, Trainer.texture_mesh) against
 the numpy reference of tests/_texture_ref.py: row, image, UV and sampler bits compared as integers -- no tolerance, the rule is
 exact -- into sentinel-filled outputs; chunked stores into a poisoned image; bad faces and zero normals; and the
 functional property the layout exists for: a bilinear lookup never reads another face's texels."""

@@ -1,4 +1,4 @@
-"""TSDF fusion on the GPU (csrc/tsdf.hip, engine/mesh.py TSDFVolume, NGPTrainer.render_depth / extract_mesh_tsdf) against the
+"""TSDF fusion on the GPU (csrc/tsdf.hip, engine/mesh/tsdf.py TSDFVolume, NGPTrainer.render_depth / extract_mesh_tsdf) against the
 float32 emulation of tests/_tsdf_ref.py: D, Wt and flags bit for bit (compared as integers) on maps that reach every branch of
 the per-voxel rule, batched against single-view calls, the finish rule into a poisoned output, the empty volume, the 6-view
 sphere through marching cubes, and a march-mode trainer's fused mesh."""

@@ -1,6 +1,6 @@
 """Mesh extraction, host side (no GPU): the generated case table (csrc/gen_mc_table.py -> csrc/mc_table.h) against the rule it
 states, meshes of the numpy reference tests/_mesh_ref.py on analytic volumes (closed, oriented, topology, enclosed volume), the
-synthetic scene's teacher density, the argument checks of engine/mesh.py and of the C entry points, and the PLY writer."""
+synthetic scene's teacher density, the argument checks of engine/mesh and of the C entry points, and the PLY writer."""
 import ctypes as C
 import itertools
 import math

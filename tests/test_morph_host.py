@@ -1,7 +1,7 @@
 """Morphological opening, host side (no GPU): the properties include/nerf_hip.h "morphological opening" states, checked on the
 reference tests/_morph_ref.py at R <= 17 (the erosion against the direct ball definition, the reconstruction between the
 classical opening and M, idempotence, the dumbbell's numbers, the C-channel, the weaker sub-mesh property through the marching
-cubes of tests/_mesh_ref.py), the argument checks of engine/mesh.py and of the C entry points, and the exported symbols."""
+cubes of tests/_mesh_ref.py), the argument checks of engine/mesh/volume.py and of the C entry points, and the exported symbols."""
 import ctypes as C
 import os
 import re

@@ -1,4 +1,4 @@
-"""TSDF fusion, host side (no GPU): the argument checks of engine/mesh.py, and on the reference tests/_tsdf_ref.py the
+"""TSDF fusion, host side (no GPU): the argument checks of engine/mesh/tsdf.py, and on the reference tests/_tsdf_ref.py the
 properties include/nerf_hip.h "TSDF fusion" relies on -- the fused sphere's zero crossing sits at the true radius, the depth
 convention (depth / acc is distance along the optical axis) against the synthetic teacher, the three branches of the finish
 rule, and that the +1 behind a surface leaves no inner shell; the exported symbols."""
