@@ -30,8 +30,8 @@ def march_keep(rays: torch.Tensor, jitter, occ, log2_res: int, pos_scale: float,
     live = torch.cumprod((z < t1[:, None]).to(torch.int32), 1).bool() & ok[:, None]
     c = O.cell_index(O.unit_coords(rays, torch.where(live, z, torch.zeros_like(z)), pos_scale, pos_offset), log2_res)
     keep = live & (c >= 0)
-    if occ is not None:
-        keep = keep & occ[c.clamp(min=0)]
+    if occ is not None:                                      # bool [R^3], or the packed words
+        keep = keep & O.occupied(occ, c)
     keep = keep & (torch.cumsum(keep.to(torch.int64), 1) <= march_steps)
     return keep, z
 

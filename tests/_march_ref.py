@@ -42,8 +42,8 @@ def interval(rays: torch.Tensor, pos_scale: float, pos_offset: float, step: floa
 
 
 def march(rays: torch.Tensor, jitter, occ, log2_res: int, pos_scale: float, pos_offset: float, step: float, march_steps: int):
-    """(offsets [B + 1] int64, rows [K, 11], z [K], K).  jitter: float or float32 [B]; occ: bool [R^3], or None (every cell
-    of the box counts as occupied, the warm-up)."""
+    """(offsets [B + 1] int64, rows [K, 11], z [K], K).  jitter: float or float32 [B]; occ: bool [R^3] or the packed words
+    (tests/_occupancy_ref.py occupied_words), or None (every cell of the box counts as occupied, the warm-up)."""
     rays = rays.float()
     B = rays.shape[0]
     j = jitter.float() if torch.is_tensor(jitter) else torch.full((B,), float(jitter), dtype=torch.float32, device=rays.device)
@@ -55,7 +55,7 @@ def march(rays: torch.Tensor, jitter, occ, log2_res: int, pos_scale: float, pos_
     c = O.cell_index(O.unit_coords(rays, torch.where(live, z, torch.zeros_like(z)), pos_scale, pos_offset), log2_res)
     keep = live & (c >= 0)
     if occ is not None:
-        keep = keep & occ[c.clamp(min=0)]
+        keep = keep & O.occupied(occ, c)
     keep = keep & (torch.cumsum(keep.to(torch.int64), 1) <= march_steps)
     counts = keep.sum(1)
     offsets = torch.zeros(B + 1, dtype=torch.int64, device=rays.device)
