@@ -872,6 +872,92 @@ int nerf_smooth_run(const float* verts_in, int64_t V, const float* lo_host, cons
 int nerf_smooth_normals(const float* verts, int64_t V, const float* lo_host, const float* hi_host, void* workspace,
                         float* normals_out, float* color_rows, void* stream);
 
+/* ---------------------------------------------------------------- mesh distance (no reference counterpart)
+ * How far one mesh is from another: points drawn on a surface in proportion to area, and for each point the closest point of
+ * another mesh (the Metro measurement of Cignoni, Rocchini and Scopigno, 1998).  It changes no mesh.  Additive: NERF_ABI_VERSION
+ * stays 3.  All arithmetic is IEEE float32, one rounding per operation (no contraction), in exactly the order and grouping written
+ * here, unless it says double or int64; a / b and sqrt are correctly rounded; dot(x, y) = (x0 y0 + x1 y1) + x2 y2.
+ * tests/_distance_ref.py reproduces every output bit for bit.
+ *   input     verts [V, 3] float32, faces [F, 3] int32, 0 <= V, F <= 2^24; box lo[3] < hi[3] (host floats, finite);
+ *             ext_a = (double)hi_a - (double)lo_a.
+ *   valid     a face (a, b, c) is valid unless it has an index outside [0, V), a corner with a non-finite coordinate, or a cross
+ *             product n = e1 x e2 = (e1y e2z - e1z e2y, e1z e2x - e1x e2z, e1x e2y - e1y e2x), e1 = b - a, e2 = c - a, whose three
+ *             components are exactly zero.  Nothing is read through a bad index; an invalid face is never drawn and never the
+ *             closest one, and dropping it from the input changes no output bit but the face numbers.
+ *   weight    d = sqrt((nx nx + ny ny) + nz nz), the float32 doubled area.  U = max_a(ext_a)^2 (double), x = (double)d / U, x = 16
+ *             unless x < 16 (an area that overflowed to inf or NaN takes the cap), w = max(1, (int64)rint(x * 2^34)) for a valid
+ *             face (rint: to nearest, ties to even) and 0 for any other.  One unit is 2^-35 of the area of the box's largest
+ *             face; 2^24 faces of at most 2^38 units stay below 2^63; a face spanning one cell of an R = 512 lattice has 2^16
+ *             units.  cdf_f = w_0 + ... + w_f (int64, exact: no summation order enters), total = cdf_{F-1}.
+ *   draws     for sample i of seed s, with mix64 the splitmix64 finaliser (z ^= z >> 30, z *= 0xBF58476D1CE4E5B9, z ^= z >> 27,
+ *             z *= 0x94D049BB133111EB, z ^= z >> 31), all in uint64: key = mix64(s ^ mix64(i + 0x632BE59BD9B4E019)),
+ *             r_j = mix64(key + (j + 1) 0x9E3779B97F4A7C15) for j = 0, 1, 2.  target = the high 64 bits of r_0 * total, in
+ *             [0, total); the face is the first f with cdf_f > target (binary search), so P(f) = w_f / total up to 2^-64 total.
+ *             A = r_1 >> 40, B = r_2 >> 40 (24 bits each); when A + B > 2^24 (the point lies beyond the diagonal) A = 2^24 - A,
+ *             B = 2^24 - B; u1 = A 2^-24, u2 = B 2^-24 (exact), so u1, u2 >= 0 and u1 + u2 <= 1 without a square root.
+ *             point_x = (a_x + u1 (b_x - a_x)) + u2 (c_x - a_x) per axis.
+ *   distance  of point p to a valid face (a, b, c), C. Ericson, "Real-Time Collision Detection" 5.1.5: ab = b - a, ac = c - a,
+ *             ap = p - a, bp = p - b, cp = p - c; d1 = dot(ab, ap), d2 = dot(ac, ap), d3 = dot(ab, bp), d4 = dot(ac, bp),
+ *             d5 = dot(ab, cp), d6 = dot(ac, cp); vc = d1 d4 - d3 d2, vb = d5 d2 - d1 d6, va = d3 d6 - d5 d4.  The closest point q
+ *             is taken by the first test that holds:
+ *               d1 <= 0 and d2 <= 0                          q = a
+ *               d3 >= 0 and d4 <= d3                         q = b
+ *               vc <= 0 and d1 >= 0 and d3 <= 0              v = d1 / (d1 - d3), q = a + v ab
+ *               d6 >= 0 and d5 <= d6                         q = c
+ *               vb <= 0 and d2 >= 0 and d6 <= 0              w = d2 / (d2 - d6), q = a + w ac
+ *               va <= 0 and d4 - d3 >= 0 and d5 - d6 >= 0    w = (d4 - d3) / ((d4 - d3) + (d5 - d6)), q = b + w (c - b)
+ *               otherwise                                    s = (va + vb) + vc, v = vb / s, w = vc / s, q = (a + v ab) + w ac
+ *             (a comparison with a NaN is false), and D(p, f) = dot(p - q, p - q).
+ *   result    over the valid faces whose D is not NaN, the smallest 64-bit key (bits of D) 2^32 + f: dist2 = the smallest D, face =
+ *             the lowest index that attains it.  No such face: dist2 = +inf, face = -1.  A point with a non-finite coordinate:
+ *             dist2 = NaN (0x7FC00000), face = -1.  The result is that of a scan over every face, for points inside the box and
+ *             outside; the grid below only decides which faces are looked at.
+ *   grid      G^3 cells over the box, 1 <= G <= 256; cell of a coordinate x on axis a: t = ((double)x - lo_a) * (G / ext_a),
+ *             0 unless t > 0, G - 1 when t >= G, else (int)t.  A valid face is entered into every cell of the product of its three
+ *             cell ranges [cell(min), cell(max)]: its bounding box clamped onto the grid.  G = 1 is the scan over every valid face.
+ *   query     one lane per point: the shells of cells at Chebyshev radius r = 0, 1, ... around the cell of the point (clamped like
+ *             any coordinate).  After a shell, m is the distance (double) from the point projected onto the box to the nearest
+ *             plane of the block of visited cells that still has cells behind it; every face not yet seen is at least m away.  A
+ *             float32 distance differs from the true one: the computed closest point lies within 64 * 2^-24 * S of the triangle,
+ *             S the largest |coordinate| among the point, the valid faces' corners and the box, and the squared norm has a
+ *             relative error below 2^-21.  The walk stops when m > slack = 2^-18 S and (m - slack)^2 (1 - 2^-20) is strictly
+ *             greater than the best dist2, or when every cell has been visited.
+ * Calls:
+ *   nerf_surface_cdf       cdf [F] int64: weights, their workgroup sums, one scan, the inclusive sums in place.  No atomics.
+ *                          workspace: nerf_surface_cdf_workspace_bytes(F) bytes (-1 out of range).  F = 0: nothing is launched.
+ *   nerf_surface_sample    points [n, 3], face [n] of samples 0 .. n - 1 of `seed`; `total` is cdf[F - 1], read once by the caller
+ *                          (the sampler's one host read, as the simplifier's).  One lane per sample, no atomics, no host read.
+ *                          n = 0: nothing is launched.  total <= 0 or F = 0 with n > 0: NERF_E_SHAPE, "the mesh has no area".
+ *   nerf_meshdist_count    entries per cell (one integer atomic per cell and face), the largest |coordinate| of a valid face
+ *                          (integer atomic max on the bits), the exclusive scan of the cells; total_out [1] int64 (device): the
+ *                          number of entries, which exceeds F when faces are large or the grid is fine.  The caller reads it once
+ *                          and sizes `entries`; above 2^30 the build refuses ("use a coarser grid"), nothing is truncated.
+ *   nerf_meshdist_build    entries [E] int32, E = that total: the face indices through per-cell cursors.  The order inside a cell
+ *                          depends on the arrival order; no result does.  No sort.
+ *   nerf_meshdist_query    dist2 [n], face [n] of a chunk of points [n, 3] against the index; the same mesh, box, grid, workspace
+ *                          and entries as the build.  No host read, no atomics; the index is only read, so one build serves any
+ *                          number of chunks.  n = 0: nothing is launched.
+ * workspace (count, build, query): nerf_meshdist_workspace_bytes(F, grid) bytes (-1 for arguments out of range), kept from the
+ * count on; its content on entry is unspecified.  No float atomics, one writer per output element: bit-reproducible and
+ * independent of the order of the faces (face numbers aside).  Out of range (V, F outside [0, 2^24], grid outside [1, 256], n
+ * outside [0, 2^30], lo >= hi or a non-finite corner): NERF_E_SHAPE; NULL: NERF_E_NULL; all argument checks run before any
+ * device work.
+ * Not done: no BVH (a grid walk grows with the cube of the distance to the nearest face), no signed distance, no
+ * point-cloud-to-point-cloud entry, no closest point returned (the face and the distance are), no per-face normals.             */
+int64_t nerf_surface_cdf_workspace_bytes(int64_t F);
+int nerf_surface_cdf(const float* verts, int64_t V, const int32_t* faces, int64_t F, const float* lo_host, const float* hi_host,
+                     void* workspace, int64_t* cdf, void* stream);
+int nerf_surface_sample(const float* verts, int64_t V, const int32_t* faces, int64_t F, const int64_t* cdf, int64_t total, int64_t n,
+                        uint64_t seed, float* points, int32_t* face, void* stream);
+int64_t nerf_meshdist_workspace_bytes(int64_t F, int grid);
+int nerf_meshdist_count(const float* verts, int64_t V, const int32_t* faces, int64_t F, const float* lo_host, const float* hi_host,
+                        int grid, void* workspace, int64_t* total_out, void* stream);
+int nerf_meshdist_build(const float* verts, int64_t V, const int32_t* faces, int64_t F, const float* lo_host, const float* hi_host,
+                        int grid, void* workspace, int32_t* entries, int64_t E, void* stream);
+int nerf_meshdist_query(const float* points, int64_t n, const float* verts, int64_t V, const int32_t* faces, int64_t F,
+                        const float* lo_host, const float* hi_host, int grid, const void* workspace, const int32_t* entries,
+                        int64_t E, float* dist2, int32_t* face, void* stream);
+
 /* ---------------------------------------------------------------- texture atlas (no reference counterpart)
  * A texture for a finished mesh, baked by one field query per texel: a simplified mesh then carries the field's appearance at
  * a resolution of its own, not one colour per surviving vertex.  A separate step behind the export pipeline; it changes no

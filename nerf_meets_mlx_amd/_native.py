@@ -136,6 +136,14 @@ SIGNATURES = {
     "nerf_mip_reduce": (_I, [_P, _I64, _I, _P, _I64, _I64, _P]),
     "nerf_mip_lod": (_I, [_P, _I64, _P, _I64, C.POINTER(C.c_float), _F, _I, _F, _P, _P]),
     "nerf_mip_sample": (_I, [C.POINTER(C.c_void_p), _I64, _I, _P, _P, _P, _I, _I64, _P, _P]),
+    "nerf_surface_cdf_workspace_bytes": (_I64, [_I64]),
+    "nerf_surface_cdf": (_I, [_P, _I64, _P, _I64, C.POINTER(C.c_float), C.POINTER(C.c_float), _P, _P, _P]),
+    "nerf_surface_sample": (_I, [_P, _I64, _P, _I64, _P, _I64, _I64, _U64, _P, _P, _P]),
+    "nerf_meshdist_workspace_bytes": (_I64, [_I64, _I]),
+    "nerf_meshdist_count": (_I, [_P, _I64, _P, _I64, C.POINTER(C.c_float), C.POINTER(C.c_float), _I, _P, _P, _P]),
+    "nerf_meshdist_build": (_I, [_P, _I64, _P, _I64, C.POINTER(C.c_float), C.POINTER(C.c_float), _I, _P, _P, _I64, _P]),
+    "nerf_meshdist_query": (_I, [_P, _I64, _P, _I64, _P, _I64, C.POINTER(C.c_float), C.POINTER(C.c_float), _I, _P, _P, _I64, _P, _P,
+                                _P]),
 }
 
 

@@ -1,0 +1,520 @@
+// Mesh-to-mesh distance: area-weighted surface sampling and closest-point queries against a uniform grid of faces.  Semantics in
+// include/nerf_hip.h "mesh distance"; tests/_distance_ref.py reproduces every output bit for bit.  No reference counterpart.
+//   cdf      one lane per face: the float32 doubled area as an integer weight -> int64 inclusive scan (count -> block scan -> write,
+//            scan.h's single-workgroup pass between).  Exact, so independent of the summation order.
+//   sample   one lane per sample: three counter-based draws, a binary search in the CDF, the point on the face.  No atomics.
+//   count    one lane per face: one integer atomic per cell its clamped bounding box overlaps, and the largest |coordinate| of a
+//            valid face (integer atomic max on the float's bits) -> exclusive scan of the cells.
+//   fill     the face index through per-cell cursors.  The arrival order inside a cell is free: the query's minimum is a 64-bit
+//            key (distance bits, face), which no order changes.
+//   query    one lane per point: shells of cells by Chebyshev radius around the point's (clamped) cell until the bound says stop.
+// Register use and what was measured: DESIGN.md section 37.
+#include "lattice.h"
+#include "scan.h"
+
+namespace nerf {
+namespace {
+
+constexpr int DIST_BLOCK = 256;
+constexpr int DIST_MAX_GRID = 256;                                 // G^3 <= 2^24 cells
+constexpr int64_t DIST_MAX_ENTRIES = 1ll << 30;                    // offsets are ints
+constexpr int64_t DIST_MAX_SAMPLES = 1ll << 30;
+constexpr double DIST_W_LIM = 16.0, DIST_W_SCALE = 17179869184.0;  // weight = max(1, rint(min(d / U, 16) 2^34))
+constexpr uint64_t DIST_NONE = 0x7F800000FFFFFFFFull;              // (+inf, face -1)
+
+struct DistBox {
+  double lo[3], h[3], inv[3];                                      // h = ext / G, inv = G / ext
+  double unit;                                                     // U = the largest extent squared
+  float box_abs;                                                   // the largest |corner coordinate|
+  int G;
+};
+
+__host__ __device__ __forceinline__ uint64_t dist_mix64(uint64_t z) {      // splitmix64 finaliser, as occupancy.hip
+  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+  z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+  return z ^ (z >> 31);
+}
+
+__device__ __forceinline__ float dot3(const float* x, const float* y) { return (x[0] * y[0] + x[1] * y[1]) + x[2] * y[2]; }
+
+struct Tri {
+  float a[3], b[3], c[3];
+};
+
+// the corners of face f and its float32 doubled area; false for an invalid face (an index outside [0, V), a non-finite corner or
+// a cross product that is exactly zero)
+__device__ __forceinline__ bool dist_face(const float* __restrict__ verts, const int* __restrict__ faces, int f, int V, Tri& t,
+                                          float* dbl_area) {
+  int g[3];
+  if (!mesh_corners(faces + 3 * f, V, g)) return false;
+  bool ok = true;
+#pragma unroll
+  for (int k = 0; k < 3; ++k) {
+    t.a[k] = verts[3 * g[0] + k];
+    t.b[k] = verts[3 * g[1] + k];
+    t.c[k] = verts[3 * g[2] + k];
+    ok = ok && isfinite(t.a[k]) && isfinite(t.b[k]) && isfinite(t.c[k]);
+  }
+  if (!ok) return false;
+  float e1[3], e2[3];
+#pragma unroll
+  for (int k = 0; k < 3; ++k) {
+    e1[k] = t.b[k] - t.a[k];
+    e2[k] = t.c[k] - t.a[k];
+  }
+  const float cx = e1[1] * e2[2] - e1[2] * e2[1], cy = e1[2] * e2[0] - e1[0] * e2[2], cz = e1[0] * e2[1] - e1[1] * e2[0];
+  if (cx == 0.0f && cy == 0.0f && cz == 0.0f) return false;
+  *dbl_area = sqrt_rn((cx * cx + cy * cy) + cz * cz);
+  return true;
+}
+
+// the integer weight of a valid face with doubled area d: at least 1; an overflowed (inf, NaN) area takes the cap
+__device__ __forceinline__ int64_t dist_weight(float d, double unit) {
+  double x = (double)d / unit;
+  if (!(x < DIST_W_LIM)) x = DIST_W_LIM;
+  const int64_t w = (int64_t)rint(x * DIST_W_SCALE);
+  return w > 1 ? w : 1;
+}
+
+// the corners of a valid face (every index in range): no checks
+__device__ __forceinline__ void dist_load(const float* __restrict__ verts, const int* __restrict__ faces, int f, Tri& t) {
+  const int g0 = faces[3 * f], g1 = faces[3 * f + 1], g2 = faces[3 * f + 2];
+#pragma unroll
+  for (int k = 0; k < 3; ++k) {
+    t.a[k] = verts[3 * g0 + k];
+    t.b[k] = verts[3 * g1 + k];
+    t.c[k] = verts[3 * g2 + k];
+  }
+}
+
+// Squared distance from p to the triangle: Ericson, "Real-Time Collision Detection" 5.1.5, the region tests in his order; float32,
+// every operation rounded separately, the divisions correctly rounded.  The closest point is always a + v ab + w ac with v, w in
+// [0, 1] as computed, so it lies within rounding of the triangle whatever region the rounded tests choose.
+__device__ __forceinline__ float point_triangle_d2(const float* p, const Tri& t) {
+  float ab[3], ac[3], ap[3], bp[3], cp[3], q[3];
+#pragma unroll
+  for (int k = 0; k < 3; ++k) {
+    ab[k] = t.b[k] - t.a[k];
+    ac[k] = t.c[k] - t.a[k];
+    ap[k] = p[k] - t.a[k];
+    bp[k] = p[k] - t.b[k];
+    cp[k] = p[k] - t.c[k];
+  }
+  const float d1 = dot3(ab, ap), d2 = dot3(ac, ap), d3 = dot3(ab, bp), d4 = dot3(ac, bp), d5 = dot3(ab, cp), d6 = dot3(ac, cp);
+  const float vc = d1 * d4 - d3 * d2, vb = d5 * d2 - d1 * d6, va = d3 * d6 - d5 * d4;
+  const float e43 = d4 - d3, e56 = d5 - d6;
+  if (d1 <= 0.0f && d2 <= 0.0f) {                                   // vertex a
+#pragma unroll
+    for (int k = 0; k < 3; ++k) q[k] = t.a[k];
+  } else if (d3 >= 0.0f && d4 <= d3) {                              // vertex b
+#pragma unroll
+    for (int k = 0; k < 3; ++k) q[k] = t.b[k];
+  } else if (vc <= 0.0f && d1 >= 0.0f && d3 <= 0.0f) {              // edge ab
+    const float v = div_rn(d1, d1 - d3);
+#pragma unroll
+    for (int k = 0; k < 3; ++k) q[k] = t.a[k] + v * ab[k];
+  } else if (d6 >= 0.0f && d5 <= d6) {                              // vertex c
+#pragma unroll
+    for (int k = 0; k < 3; ++k) q[k] = t.c[k];
+  } else if (vb <= 0.0f && d2 >= 0.0f && d6 <= 0.0f) {              // edge ac
+    const float w = div_rn(d2, d2 - d6);
+#pragma unroll
+    for (int k = 0; k < 3; ++k) q[k] = t.a[k] + w * ac[k];
+  } else if (va <= 0.0f && e43 >= 0.0f && e56 >= 0.0f) {            // edge bc
+    const float w = div_rn(e43, e43 + e56);
+#pragma unroll
+    for (int k = 0; k < 3; ++k) q[k] = t.b[k] + w * (t.c[k] - t.b[k]);
+  } else {                                                          // interior
+    const float s = (va + vb) + vc;
+    const float v = div_rn(vb, s), w = div_rn(vc, s);
+#pragma unroll
+    for (int k = 0; k < 3; ++k) q[k] = (t.a[k] + v * ab[k]) + w * ac[k];
+  }
+  const float d[3] = {p[0] - q[0], p[1] - q[1], p[2] - q[2]};
+  return dot3(d, d);
+}
+
+// the cell of coordinate x on axis a, clamped onto the grid (x finite)
+__device__ __forceinline__ int dist_cell(const DistBox& bx, int a, float x) {
+  const double t = ((double)x - bx.lo[a]) * bx.inv[a];
+  if (!(t > 0.0)) return 0;
+  if (t >= (double)bx.G) return bx.G - 1;
+  return (int)t;
+}
+
+// ---- int64 forms of scan.h's block_sum / block_offset (a weight does not fit an int); every lane of the workgroup must call them
+__device__ __forceinline__ int64_t dist_block_sum(int64_t v) {
+  __shared__ int64_t sh[DIST_BLOCK / WAVE];
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, WAVE);
+  if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
+  __syncthreads();
+  int64_t t = 0;
+  if (threadIdx.x == 0)
+    for (int k = 0; k < DIST_BLOCK / WAVE; ++k) t += sh[k];
+  return t;
+}
+__device__ __forceinline__ int64_t dist_block_inclusive(int64_t v, int64_t base) {
+  __shared__ int64_t sh[DIST_BLOCK / WAVE];
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  int64_t x = v;
+  for (int o = 1; o < WAVE; o <<= 1) {
+    const int64_t t = __shfl_up(x, o, WAVE);
+    if (lane >= o) x += t;
+  }
+  if (lane == 63) sh[w] = x;
+  __syncthreads();
+  for (int k = 0; k < w; ++k) base += sh[k];
+  return base + x;
+}
+
+// ---- weights: 12 B of indices and 36 B of corners read per face, 8 B written; the workgroup's sum to blk
+__global__ void __launch_bounds__(DIST_BLOCK) dist_weight_kernel(const float* __restrict__ verts, int V, const int* __restrict__ faces,
+                                                                int F, double unit, int64_t* __restrict__ cdf,
+                                                                int64_t* __restrict__ blk) {
+  const int f = blockIdx.x * DIST_BLOCK + threadIdx.x;
+  int64_t w = 0;
+  if (f < F) {
+    Tri t;
+    float d;
+    if (dist_face(verts, faces, f, V, t, &d)) w = dist_weight(d, unit);
+    cdf[f] = w;
+  }
+  const int64_t s = dist_block_sum(w);
+  if (threadIdx.x == 0) blk[blockIdx.x] = s;
+}
+// ---- weights -> inclusive CDF in place (every lane reads and writes its own element only)
+__global__ void __launch_bounds__(DIST_BLOCK) dist_cdf_kernel(int64_t* __restrict__ cdf, int F, const int64_t* __restrict__ blk) {
+  const int f = blockIdx.x * DIST_BLOCK + threadIdx.x;
+  const int64_t c = dist_block_inclusive(f < F ? cdf[f] : 0, blk[blockIdx.x]);
+  if (f < F) cdf[f] = c;
+}
+
+// ---- samples: one lane each; log2(F) gathered CDF words, 12 + 36 B of the face, 16 B written
+__global__ void __launch_bounds__(DIST_BLOCK) dist_sample_kernel(const float* __restrict__ verts, int V, const int* __restrict__ faces, int F,
+                                                                const int64_t* __restrict__ cdf, uint64_t total, int64_t n,
+                                                                uint64_t seed, float* __restrict__ points, int* __restrict__ face) {
+  const int64_t i = (int64_t)blockIdx.x * DIST_BLOCK + threadIdx.x;
+  if (i >= n) return;
+  const uint64_t key = dist_mix64(seed ^ dist_mix64((uint64_t)i + 0x632BE59BD9B4E019ull));
+  const uint64_t r0 = dist_mix64(key + 1 * 0x9E3779B97F4A7C15ull), r1 = dist_mix64(key + 2 * 0x9E3779B97F4A7C15ull),
+                 r2 = dist_mix64(key + 3 * 0x9E3779B97F4A7C15ull);
+  const int64_t target = (int64_t)__umul64hi(r0, total);           // [0, total)
+  int lo = 0, hi = F - 1;                                           // the first face whose inclusive CDF exceeds the target
+  while (lo < hi) {
+    const int mid = lo + ((hi - lo) >> 1);
+    if (cdf[mid] > target) hi = mid; else lo = mid + 1;
+  }
+  Tri t;
+  float d;
+  if (!dist_face(verts, faces, lo, V, t, &d)) {                     // only with a cdf or total that are not this mesh's
+#pragma unroll
+    for (int k = 0; k < 3; ++k) points[3 * i + k] = __uint_as_float(0x7FC00000u);
+    face[i] = -1;
+    return;
+  }
+  int a =(int)(r1 >> 40), b = (int)(r2 >> 40);                     // 24 bits each
+  if (a + b > (1 << 24)) {                                          // u1 + u2 > 1: reflected across the diagonal
+    a = (1 << 24) - a;
+    b = (1 << 24) - b;
+  }
+  const float u1 = (float)a * 0x1p-24f, u2 = (float)b * 0x1p-24f;
+#pragma unroll
+  for (int k = 0; k < 3; ++k) points[3 * i + k] = (t.a[k] + u1 * (t.b[k] - t.a[k])) + u2 * (t.c[k] - t.a[k]);
+  face[i] = lo;
+}
+
+// the cells [c0, c1] per axis that the clamped bounding box of a valid face overlaps
+__device__ __forceinline__ void dist_span(const DistBox& bx, const Tri& t, int* c0, int* c1) {
+#pragma unroll
+  for (int a = 0; a < 3; ++a) {
+    c0[a] = dist_cell(bx, a, fminf(fminf(t.a[a], t.b[a]), t.c[a]));
+    c1[a] = dist_cell(bx, a, fmaxf(fmaxf(t.a[a], t.b[a]), t.c[a]));
+  }
+}
+
+// ---- entries per cell, and the largest |coordinate| of a valid face.  cnt and scale come in zeroed.
+__global__ void __launch_bounds__(DIST_BLOCK) dist_count_kernel(const float* __restrict__ verts, int V, const int* __restrict__ faces,
+                                                               int F, DistBox bx, int* __restrict__ cnt, uint32_t* __restrict__ scale) {
+  const int f = blockIdx.x * DIST_BLOCK + threadIdx.x;
+  Tri t;
+  float d;
+  if (f >= F || !dist_face(verts, faces, f, V, t, &d)) return;
+  float m = 0.0f;
+#pragma unroll
+  for (int a = 0; a < 3; ++a) m = fmaxf(m, fmaxf(fmaxf(fabsf(t.a[a]), fabsf(t.b[a])), fabsf(t.c[a])));
+  atomicMax(scale, __float_as_uint(m));                             // non-negative floats order as their bits
+  int c0[3], c1[3];
+  dist_span(bx, t, c0, c1);
+  for (int z = c0[2]; z <= c1[2]; ++z)
+    for (int y = c0[1]; y <= c1[1]; ++y)
+      for (int x = c0[0]; x <= c1[0]; ++x) atomicAdd(&cnt[x + bx.G * (y + bx.G * z)], 1);
+}
+
+// ---- cell offsets, as smooth.hip's rows
+__global__ void __launch_bounds__(DIST_BLOCK) dist_cells_count_kernel(const int* __restrict__ cnt, int C, int64_t* __restrict__ blk) {
+  const int c = blockIdx.x * DIST_BLOCK + threadIdx.x;
+  const int64_t t = block_sum<DIST_BLOCK>(c < C ? cnt[c] : 0);
+  if (threadIdx.x == 0) blk[blockIdx.x] = t;
+}
+__global__ void __launch_bounds__(DIST_BLOCK) dist_cells_write_kernel(int* __restrict__ cur, int C, const int64_t* __restrict__ blk,
+                                                                     const int64_t* __restrict__ total, int* __restrict__ off,
+                                                                     int64_t* __restrict__ total_out) {
+  const int c = blockIdx.x * DIST_BLOCK + threadIdx.x;
+  const int64_t o = block_offset<DIST_BLOCK>(c < C ? cur[c] : 0, blk[blockIdx.x]);
+  const int64_t tot = total[0];
+  // a total beyond the cap is refused by the caller before anything reads the offsets: they are clamped, not wrapped
+  if (c == 0) {
+    off[C] = (int)(tot < DIST_MAX_ENTRIES ? tot : DIST_MAX_ENTRIES);
+    total_out[0] = tot;
+  }
+  if (c >= C) return;
+  const int oc = (int)(o < DIST_MAX_ENTRIES ? o : DIST_MAX_ENTRIES);
+  off[c] = oc;
+  cur[c] = oc;
+}
+
+// ---- entries: one cursor atomic and one 4-byte store per overlapped cell; nothing is written at or past E
+__global__ void __launch_bounds__(DIST_BLOCK) dist_fill_kernel(const float* __restrict__ verts, int V, const int* __restrict__ faces, int F,
+                                                              DistBox bx, int* __restrict__ cur, int* __restrict__ ent, int64_t E) {
+  const int f = blockIdx.x * DIST_BLOCK + threadIdx.x;
+  Tri t;
+  float d;
+  if (f >= F || !dist_face(verts, faces, f, V, t, &d)) return;
+  int c0[3], c1[3];
+  dist_span(bx, t, c0, c1);
+  for (int z = c0[2]; z <= c1[2]; ++z)
+    for (int y = c0[1]; y <= c1[1]; ++y)
+      for (int x = c0[0]; x <= c1[0]; ++x) {
+        const int slot = atomicAdd(&cur[x + bx.G * (y + bx.G * z)], 1);
+        if (slot >= 0 && slot < E) ent[slot] = f;
+      }
+}
+
+// ---- the query: 12 B read and 8 B written per point, and per candidate 12 B of indices and 36 B of corners gathered
+__global__ void __launch_bounds__(DIST_BLOCK) dist_query_kernel(const float* __restrict__ points, int64_t n, const float* __restrict__ verts,
+                                                               const int* __restrict__ faces, DistBox bx, const int* __restrict__ off,
+                                                               const int* __restrict__ ent, int64_t E,
+                                                               const uint32_t* __restrict__ scale, float* __restrict__ dist2,
+                                                               int* __restrict__ face) {
+  const int64_t i = (int64_t)blockIdx.x * DIST_BLOCK + threadIdx.x;
+  if (i >= n) return;
+  const float p[3] = {points[3 * i], points[3 * i + 1], points[3 * i + 2]};
+  if (!(isfinite(p[0]) && isfinite(p[1]) && isfinite(p[2]))) {
+    dist2[i] = __uint_as_float(0x7FC00000u);
+    face[i] = -1;
+    return;
+  }
+  const int G = bx.G;
+  int c[3];
+  double q[3];                                                       // the point projected onto the box
+#pragma unroll
+  for (int a = 0; a < 3; ++a) {
+    c[a] = dist_cell(bx, a, p[a]);
+    q[a] = fmin(fmax((double)p[a], bx.lo[a]), bx.lo[a] + bx.h[a] * (double)G);
+  }
+  // The float32 distance of a face is that of a point within `slack` of the triangle (point_triangle_d2), taken with a relative
+  // error below 2^-21: ten float32 operations on operands of at most 4 S each lead to the closest point and to the difference,
+  // S the largest |coordinate| of the point, the valid faces and the box.  64 * 2^-24 S covers them and the double roundings of
+  // the cell planes.
+  const float S = fmaxf(fmaxf(fmaxf(fabsf(p[0]), fabsf(p[1])), fabsf(p[2])), fmaxf(__uint_as_float(scale[0]), bx.box_abs));
+  const double slack = (double)S * 0x1p-18;
+  uint64_t best = DIST_NONE;
+  for (int r = 0;; ++r) {
+    const int z0 = max(c[2] - r, 0), z1 = min(c[2] + r, G - 1), y0 = max(c[1] - r, 0), y1 = min(c[1] + r, G - 1);
+    const int x0 = max(c[0] - r, 0), x1 = min(c[0] + r, G - 1);
+    for (int z = z0; z <= z1; ++z)
+      for (int y = y0; y <= y1; ++y) {
+        const bool whole = z == c[2] - r || z == c[2] + r || y == c[1] - r || y == c[1] + r;
+        // a row on the shell's y or z faces is scanned whole; any other row only at its two ends x = cx - r, cx + r
+        const int step = whole ? 1 : 2 * r;
+        for (int x = whole ? x0 : c[0] - r; x <= (whole ? x1 : c[0] + r); x += step) {
+          if (x < 0 || x >= G) continue;
+          const int cell = x + G * (y + G * z);
+          int e1 = off[cell + 1];
+          if (e1 > E) e1 = (int)E;
+          for (int e = off[cell]; e < e1; ++e) {
+            const int f = ent[e];
+            Tri t;
+            dist_load(verts, faces, f, t);
+            const float d = point_triangle_d2(p, t);
+            if (d != d) continue;
+            const uint64_t key = ((uint64_t)__float_as_uint(d) << 32) | (uint32_t)f;
+            best = key < best ? key : best;
+          }
+        }
+      }
+    // The cells not yet visited lie beyond the six planes of the block [c - r, c + r]; m is the distance from q to the nearest of
+    // those planes that has cells behind it.
+    //  * Per-axis clamping of a face's bounding box only moves it nearer to a point inside the box, and a face is entered into
+    //    every cell its clamped bounding box overlaps: for every point x of a face not yet seen, the projection of x onto the box
+    //    lies in one of the face's cells, all of them unvisited, so |q - proj(x)| >= m.
+    //  * Projection onto the box is non-expansive: |p - x| >= |q - proj(x)| >= m, for p inside the box (q = p) and outside.
+    // So every unseen face has a true distance of at least m and a float32 distance of at least (m - slack)^2 (1 - 2^-20).  Stop
+    // only when that is strictly greater than the best: on equality a lower face index may still tie.
+    double m = INFINITY;
+#pragma unroll
+    for (int a = 0; a < 3; ++a) {
+      if (c[a] - r > 0) m = fmin(m, q[a] - (bx.lo[a] + bx.h[a] * (double)(c[a] - r)));
+      if (c[a] + r + 1 < G) m = fmin(m, (bx.lo[a] + bx.h[a] * (double)(c[a] + r + 1)) - q[a]);
+    }
+    if (m == INFINITY) break;                                        // every cell has been visited
+    const double s = m - slack;
+    if (s > 0.0 && (s * s) * (1.0 - 0x1p-20) > (double)__uint_as_float((uint32_t)(best >> 32))) break;
+  }
+  dist2[i] = __uint_as_float((uint32_t)(best >> 32));
+  face[i] = (int)(uint32_t)(best & 0xFFFFFFFFull);
+}
+
+// ---- host side
+struct DistWs {
+  int64_t cells, nblk;
+  int64_t* blk;                                      // [nblk] entries per workgroup of cells, scanned in place
+  int64_t* total;                                    // [1]
+  uint32_t* scale;                                   // [2] the bits of the largest |coordinate| of a valid face (8 B with padding)
+  int32_t* off;                                      // [cells + 1]
+  int32_t* cur;                                      // [cells]
+  int64_t bytes;
+};
+inline bool dist_grid_ok(int G) { return G >= 1 && G <= DIST_MAX_GRID; }
+inline DistWs dist_ws(void* ws, int G) {
+  DistWs w;
+  w.cells = (int64_t)G * G * G;
+  w.nblk = (w.cells + DIST_BLOCK - 1) / DIST_BLOCK;
+  uintptr_t p = reinterpret_cast<uintptr_t>(ws);
+  const uintptr_t p0 = p;
+  auto take = [&p](int64_t bytes) {
+    const uintptr_t at = p;
+    p += (uintptr_t)((bytes + 7) & ~(int64_t)7);
+    return at;
+  };
+  w.blk = reinterpret_cast<int64_t*>(take(w.nblk * 8));
+  w.total = reinterpret_cast<int64_t*>(take(8));
+  w.scale = reinterpret_cast<uint32_t*>(take(8));
+  w.off = reinterpret_cast<int32_t*>(take((w.cells + 1) * 4));
+  w.cur = reinterpret_cast<int32_t*>(take(w.cells * 4));
+  w.bytes = (int64_t)(p - p0);
+  return w;
+}
+
+int dist_box(const char* who, int64_t V, int64_t F, const float* lo, const float* hi, int G, DistBox* bx) {
+  int rc = mesh_check(who, V, F);
+  if (rc) return rc;
+  NERF_REQUIRE(dist_grid_ok(G), NERF_E_SHAPE, "%s: need 1 <= grid <= %d (got %d)", who, DIST_MAX_GRID, G);
+  rc = box_check(who, lo, hi);
+  if (rc) return rc;
+  double emax = 0.0;
+  float babs = 0.0f;
+  for (int a = 0; a < 3; ++a) {
+    const double ext = (double)hi[a] - (double)lo[a];
+    bx->lo[a] = (double)lo[a];
+    bx->h[a] = ext / (double)G;
+    bx->inv[a] = (double)G / ext;
+    emax = ext > emax ? ext : emax;
+    babs = std::fmax(babs, std::fmax(std::fabs(lo[a]), std::fabs(hi[a])));
+  }
+  bx->unit = emax * emax;
+  bx->box_abs = babs;
+  bx->G = G;
+  return NERF_OK;
+}
+
+#define DIST_LAUNCH(what, kernel, blocks, ...) NERF_LAUNCH(what, kernel, blocks, DIST_BLOCK, st, __VA_ARGS__)
+
+}  // namespace
+}  // namespace nerf
+
+using namespace nerf;
+
+extern "C" int64_t nerf_surface_cdf_workspace_bytes(int64_t F) {
+  return F >= 0 && F <= MESH_MAX_ITEMS ? (blocks(F, DIST_BLOCK) + 1) * (int64_t)sizeof(int64_t) : -1;
+}
+
+extern "C" int nerf_surface_cdf(const float* verts, int64_t V, const int32_t* faces, int64_t F, const float* lo, const float* hi,
+                                void* workspace, int64_t* cdf, void* stream) {
+  DistBox bx;
+  const int rc = dist_box("nerf_surface_cdf", V, F, lo, hi, 1, &bx);
+  if (rc) return rc;
+  if (F == 0) return NERF_OK;
+  NERF_REQUIRE(faces && workspace && cdf && (verts || V == 0), NERF_E_NULL, "nerf_surface_cdf: NULL pointer");
+  hipStream_t st = as_stream(stream);
+  const int64_t nblk = blocks(F, DIST_BLOCK);
+  int64_t* blk = static_cast<int64_t*>(workspace);
+  DIST_LAUNCH("nerf_surface_cdf (weights)", dist_weight_kernel, nblk, verts, (int)V, faces, (int)F, bx.unit, cdf, blk);
+  const int rs = scan_launch("nerf_surface_cdf (scan)", blk, nblk, blk + nblk, st);
+  if (rs) return rs;
+  DIST_LAUNCH("nerf_surface_cdf (write)", dist_cdf_kernel, nblk, cdf, (int)F, (const int64_t*)blk);
+  return NERF_OK;
+}
+
+extern "C" int nerf_surface_sample(const float* verts, int64_t V, const int32_t* faces, int64_t F, const int64_t* cdf, int64_t total,
+                                   int64_t n, uint64_t seed, float* points, int32_t* face, void* stream) {
+  const int rc = mesh_check("nerf_surface_sample", V, F);
+  if (rc) return rc;
+  NERF_REQUIRE(n >= 0 && n <= DIST_MAX_SAMPLES, NERF_E_SHAPE, "nerf_surface_sample: need 0 <= n <= 2^30 (got %lld)", (long long)n);
+  if (n == 0) return NERF_OK;
+  NERF_REQUIRE(total > 0 && F > 0, NERF_E_SHAPE, "nerf_surface_sample: the mesh has no area (total weight %lld over %lld faces)",
+               (long long)total, (long long)F);
+  NERF_REQUIRE(verts && faces && cdf && points && face, NERF_E_NULL, "nerf_surface_sample: NULL pointer");
+  hipStream_t st = as_stream(stream);
+  DIST_LAUNCH("nerf_surface_sample", dist_sample_kernel, blocks(n, DIST_BLOCK), verts, (int)V, faces, (int)F, cdf, (uint64_t)total, n, seed, points,
+              face);
+  return NERF_OK;
+}
+
+extern "C" int64_t nerf_meshdist_workspace_bytes(int64_t F, int grid) {
+  return F >= 0 && F <= MESH_MAX_ITEMS && dist_grid_ok(grid) ? dist_ws(nullptr, grid).bytes : -1;
+}
+
+extern "C" int nerf_meshdist_count(const float* verts, int64_t V, const int32_t* faces, int64_t F, const float* lo, const float* hi,
+                                   int grid, void* workspace, int64_t* total_out, void* stream) {
+  DistBox bx;
+  const int rc = dist_box("nerf_meshdist_count", V, F, lo, hi, grid, &bx);
+  if (rc) return rc;
+  NERF_REQUIRE(workspace && total_out && (faces || F == 0) && (verts || V == 0), NERF_E_NULL, "nerf_meshdist_count: NULL pointer");
+  const DistWs w = dist_ws(workspace, grid);
+  hipStream_t st = as_stream(stream);
+  hipError_t e = hipMemsetAsync(w.cur, 0, w.cells * sizeof(int32_t), st);
+  if (e == hipSuccess) e = hipMemsetAsync(w.scale, 0, 8, st);
+  if (e != hipSuccess) return fail(NERF_E_HIP, "nerf_meshdist_count: %s", hipGetErrorString(e));
+  if (F > 0)
+    DIST_LAUNCH("nerf_meshdist_count (count)", dist_count_kernel, blocks(F, DIST_BLOCK), verts, (int)V, faces, (int)F, bx, w.cur, w.scale);
+  DIST_LAUNCH("nerf_meshdist_count (cell counts)", dist_cells_count_kernel, w.nblk, (const int*)w.cur, (int)w.cells, w.blk);
+  const int rs = scan_launch("nerf_meshdist_count (scan of the cells)", w.blk, w.nblk, w.total, st);
+  if (rs) return rs;
+  DIST_LAUNCH("nerf_meshdist_count (cell offsets)", dist_cells_write_kernel, w.nblk, w.cur, (int)w.cells, (const int64_t*)w.blk,
+              (const int64_t*)w.total, w.off, total_out);
+  return NERF_OK;
+}
+
+extern "C" int nerf_meshdist_build(const float* verts, int64_t V, const int32_t* faces, int64_t F, const float* lo, const float* hi,
+                                   int grid, void* workspace, int32_t* entries, int64_t E, void* stream) {
+  DistBox bx;
+  const int rc = dist_box("nerf_meshdist_build", V, F, lo, hi, grid, &bx);
+  if (rc) return rc;
+  NERF_REQUIRE(E >= 0, NERF_E_SHAPE, "nerf_meshdist_build: need entries >= 0 (got %lld)", (long long)E);
+  NERF_REQUIRE(E <= DIST_MAX_ENTRIES, NERF_E_SHAPE, "nerf_meshdist_build: %lld entries exceed 2^30; use a coarser grid", (long long)E);
+  if (E == 0 || F == 0) return NERF_OK;
+  NERF_REQUIRE(verts && faces && workspace && entries, NERF_E_NULL, "nerf_meshdist_build: NULL pointer");
+  const DistWs w = dist_ws(workspace, grid);
+  hipStream_t st = as_stream(stream);
+  DIST_LAUNCH("nerf_meshdist_build (fill)", dist_fill_kernel, blocks(F, DIST_BLOCK), verts, (int)V, faces, (int)F, bx, w.cur, entries, E);
+  return NERF_OK;
+}
+
+extern "C" int nerf_meshdist_query(const float* points, int64_t n, const float* verts, int64_t V, const int32_t* faces, int64_t F,
+                                   const float* lo, const float* hi, int grid, const void* workspace, const int32_t* entries, int64_t E,
+                                   float* dist2, int32_t* face, void* stream) {
+  DistBox bx;
+  const int rc = dist_box("nerf_meshdist_query", V, F, lo, hi, grid, &bx);
+  if (rc) return rc;
+  NERF_REQUIRE(n >= 0 && n <= DIST_MAX_SAMPLES, NERF_E_SHAPE, "nerf_meshdist_query: need 0 <= n <= 2^30 (got %lld)", (long long)n);
+  NERF_REQUIRE(E >= 0 && E <= DIST_MAX_ENTRIES, NERF_E_SHAPE, "nerf_meshdist_query: need 0 <= entries <= 2^30 (got %lld)", (long long)E);
+  if (n == 0) return NERF_OK;
+  NERF_REQUIRE(points && workspace && dist2 && face && (E == 0 || (verts && faces && entries)), NERF_E_NULL,
+               "nerf_meshdist_query: NULL pointer");
+  const DistWs w = dist_ws(const_cast<void*>(workspace), grid);
+  hipStream_t st = as_stream(stream);
+  DIST_LAUNCH("nerf_meshdist_query", dist_query_kernel, blocks(n, DIST_BLOCK), points, n, verts, faces, bx, (const int*)w.off, entries, E,
+              (const uint32_t*)w.scale, dist2, face);
+  return NERF_OK;
+}

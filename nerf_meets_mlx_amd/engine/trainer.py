@@ -243,6 +243,15 @@ class Trainer:
                             simplify_grid=simplify_grid, simplify_placement=simplify_placement,
                             smooth_iterations=smooth_iterations, smooth_lambda=smooth_lambda, smooth_mu=smooth_mu)
 
+    def mesh_distance(self, mesh, other, n: int = 1 << 20, tau=None, seed: int = 0, aabb=None):
+        """engine.mesh.MeshDistance between two engine.mesh.Mesh on the box of the export (`aabb` as in extract_mesh): `n`
+        area-weighted samples on each, every sample taken to the other surface; mean, RMS and Hausdorff distance per direction and
+        symmetric, and with `tau` precision (`mesh` within tau of `other`), recall and F-score (engine.mesh.mesh_distance,
+        DESIGN.md section 37).  Runs on this rank only: no collective."""
+        from . import mesh as M
+        lo, hi = self._mesh_box(aabb)
+        return M.mesh_distance(mesh, other, n, lo, hi, seed=seed, tau=tau)
+
     def texture_mesh(self, mesh, texels: int = 8):
         """engine.mesh.Texture of a finished engine.mesh.Mesh (extract_mesh's, simplified or not): an atlas with a right triangle
         of `texels` texels a leg per face, every texel the field's colour at its point of the face looking along minus the

@@ -673,6 +673,90 @@ def _tsdf_arm(tr, mesh, R, lo, hi, a, rec, bound, boxes):
     return out, m
 
 
+def _distance_pair(mesh, x, y, n, lo, hi, h, reps):
+    """engine.mesh.mesh_distance(x, y) with tau = h: the figures in units of h and the stages' device ms (host reads included)."""
+    ts = []
+    for _ in range(reps + 1):                                            # the first run warms the allocator
+        st = _Stages()
+        r = mesh.mesh_distance(x, y, n, lo, hi, seed=0, tau=h, mark=st)
+        st("end")
+        ts.append(st.total_ms())
+    t = {k: float(np.mean([q[k] for q in ts[1:]])) for k in ts[0]}
+    units = lambda s: {"mean_h": s.mean / h, "rms_h": s.rms / h, "hausdorff_h": s.max / h}
+    return {"V": [int(x.verts.shape[0]), int(y.verts.shape[0])], "F": [int(x.faces.shape[0]), int(y.faces.shape[0])], "n": n,
+            "a_to_b": units(r.a_to_b), "b_to_a": units(r.b_to_a), "symmetric": units(r.symmetric), "tau_h": 1.0,
+            "precision": r.precision, "recall": r.recall, "fscore": r.fscore, "stage_ms": t, "total_ms": float(sum(t.values()))}
+
+
+def _distance_timing(mesh, pts_of, target, n, lo, hi, reps, brute_points=4096):
+    """Build and query ms of MeshIndex(target) for n samples of `pts_of` at the default grid and two neighbours, unsorted and
+    cell-sorted, and the grid = 1 scan on `brute_points` of them (extrapolated to n in the open)."""
+    pts, _ = mesh.sample_surface(pts_of, n, lo, hi, 0)
+    G0 = mesh.default_distance_grid(int(target.faces.shape[0]))
+    out = {"n": n, "F": int(target.faces.shape[0]), "default_grid": G0, "grids": {}}
+    ref = None
+    for G in sorted({max(1, (2 * G0) // 3), G0, min(mesh.DISTANCE_MAX_GRID, (3 * G0) // 2)}):
+        rows = []
+        for _ in range(reps + 1):
+            st = _Stages()
+            idx = mesh.MeshIndex(target, lo, hi, G, st)
+            d_u, f_u = idx.query(pts, False, st)
+            st("between")
+            d_s, f_s = idx.query(pts, True, st)
+            st("end")
+            t = st.ms()
+            rows.append([t["count"], t["build"], t["query"], 0.0])
+            names = st.names
+            k = names.index("between")
+            rows[-1][3] = float(sum(st.events[j].elapsed_time(st.events[j + 1]) for j in range(k + 1, len(names) - 1)))
+            rows[-1][2] = float(st.events[names.index("query")].elapsed_time(st.events[k]))
+        same = bool(torch.equal(d_u.view(torch.int32), d_s.view(torch.int32)) and torch.equal(f_u, f_s))
+        if ref is not None:
+            same = same and bool(torch.equal(d_u.view(torch.int32), ref[0].view(torch.int32)) and torch.equal(f_u, ref[1]))
+        ref = (d_u, f_u)
+        t = np.mean(np.array(rows[1:]), 0)
+        out["grids"][G] = {"entries": idx.entries, "count_ms": float(t[0]), "fill_ms": float(t[1]), "query_ms": float(t[2]),
+                           "sorted_query_ms": float(t[3]), "same_bits": same}
+        del idx
+    sub = pts[:brute_points].contiguous()
+    st = _Stages()
+    idx = mesh.MeshIndex(target, lo, hi, 1, st)
+    d_b, f_b = idx.query(sub, False, st)
+    st("end")
+    t = st.ms()
+    out["grid_1"] = {"points": int(sub.shape[0]), "query_ms": t["query"], "extrapolated_to_n_ms": t["query"] * n / max(1, sub.shape[0]),
+                     "same_bits": bool(torch.equal(d_b.view(torch.int32), ref[0][:brute_points].view(torch.int32))
+                                       and torch.equal(f_b, ref[1][:brute_points]))}
+    return out
+
+
+def _distance_arms(mesh, m, tsdf_mesh, teacher, R, lo, hi, a, rec, bound):
+    """JSON lines of --distance: every surface stage against its input (the marching-cubes mesh `m`), the TSDF mesh against it,
+    and each of them against the marching-cubes mesh of the teacher's volume at the same R."""
+    h = 2.0 * bound / R
+    n = a.distance_n
+    arms = [(f"simplify {G}", mesh.simplify(m, G, lo, hi)) for G in (64, 128) if G < R]
+    its = (a.smooth or [10])[0]
+    arms.append((f"smooth {its}", mesh.smooth(m, its, lo, hi, a.smooth_lambda, a.smooth_mu)))
+    if tsdf_mesh is not None:
+        arms.append(("tsdf", tsdf_mesh))
+    out = []
+    base = {"tool": "ngp_mesh distance", "R": R, "iters": rec["iters"], "seed": rec["seed"], "h": h, "device": rec["device"]}
+
+    def line(r):
+        print(json.dumps(r), flush=True)
+        out.append(r)
+
+    line({**base, "a": arms[0][0], "b": "marching cubes", "timing": _distance_timing(mesh, arms[0][1], m, n, lo, hi, a.reps)})
+    for name, x in arms:
+        if x.faces.shape[0]:
+            line({**base, "a": name, "b": "marching cubes", **_distance_pair(mesh, x, m, n, lo, hi, h, a.reps)})
+    for name, x in [("marching cubes", m)] + arms:
+        if x.faces.shape[0] and teacher.faces.shape[0]:
+            line({**base, "a": name, "b": "teacher", **_distance_pair(mesh, x, teacher, n, lo, hi, h, a.reps)})
+    return out
+
+
 def _teacher_volume(R, lo, hi, dev):
     from nerf_meets_mlx_amd.dataset import synthetic
     from nerf_meets_mlx_amd.engine import mesh
@@ -751,6 +835,11 @@ def parser():
                     help="with --render and --texture T or --project: also build the mip pyramid of each atlas of the density mesh at "
                          "--ply-res and of each --simplify arm of it and render it trilinearly from the held-out pose (DESIGN.md "
                          "section 34): stage times, bytes, the histogram of floor(lod), PSNR with and without the pyramid")
+    ap.add_argument("--distance", action="store_true",
+                    help="at --ply-res: surface-to-surface distance (DESIGN.md section 37) of the simplified (G = 64, 128), smoothed "
+                         "(the first --smooth N, default 10) and, with --tsdf, TSDF meshes against the marching-cubes mesh, and of "
+                         "all of them against the teacher's marching-cubes surface; index build and query times")
+    ap.add_argument("--distance-n", type=int, default=1 << 20, metavar="N", help="--distance: samples a side")
     ap.add_argument("--smooth-lambda", type=float, default=0.5)
     ap.add_argument("--smooth-mu", type=float, default=-0.53, help="0: plain Laplacian smoothing")
     ap.add_argument("--ckpt", default=None, help="load this checkpoint instead of training")
@@ -880,14 +969,21 @@ def main():
                 del sm, srows
         lines += _simplify_arms(m._replace(colors=None), "density", R, lo, hi, a, rec, bound, boxes)
         lines += _smooth_arms(m._replace(colors=None), "density", R, lo, hi, a, rec, bound, boxes)
+        dist_m = m._replace(colors=None) if a.distance and R == a.ply_res else None
         del vol, m, rows, col
         torch.cuda.empty_cache()
+        tm = None
         if a.tsdf:
             trec, tm = _tsdf_arm(tr, mesh, R, lo, hi, a, rec, bound, boxes)
             print(json.dumps(trec), flush=True)
             lines.append(trec)
             lines += _simplify_arms(tm, "tsdf", R, lo, hi, a, {**rec, "marching_cubes_ms": trec["marching_cubes_ms"]}, bound, boxes)
-            del tm
+        if dist_m is not None and dist_m.faces.shape[0]:
+            teacher = mesh.marching_cubes(_teacher_volume(R, lo, hi, dev), 25.0, lo, hi)
+            lines += _distance_arms(mesh, dist_m, tm, teacher, R, lo, hi, a, rec, bound)
+            del teacher
+        del tm, dist_m
+        torch.cuda.empty_cache()
         arms = a.min_component if a.min_component else ([0] if a.largest_only else [])
         for m_min in arms:
             vol = mesh.density_volume(query, act, R, lo, hi, device=dev)
