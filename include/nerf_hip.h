@@ -958,6 +958,62 @@ int nerf_meshdist_query(const float* points, int64_t n, const float* verts, int6
                         const float* lo_host, const float* hi_host, int grid, const void* workspace, const int32_t* entries,
                         int64_t E, float* dist2, int32_t* face, void* stream);
 
+/* ---------------------------------------------------------------- mesh BVH (no reference counterpart)
+ * A second index for the queries of "mesh distance": a bounding-volume hierarchy over the faces, whose cost follows the surface
+ * near the query and not the empty space between (the grid walks (2 r + 1)^3 cells to reach a face r cells away), and the closest
+ * point of a given face.  dist2 and face are those of "mesh distance", result: the bits of the scan over every face; validity, the
+ * distance D(p, f) and the key (bits of D) 2^32 + f are the ones written there.  Additive: NERF_ABI_VERSION stays 3.
+ * tests/_bvh_ref.py reproduces every output bit for bit.
+ *   keys      for a valid face, m_a = ((double)min_a + (double)max_a) * 0.5 per axis, min and max over its three float32 corners;
+ *             cell c_a = ((m_a - lo_a) / ext_a) * 4096 in double, 0 unless it is > 0, 4095 when it is >= 4096, else truncated; the
+ *             code is the 36-bit interleave (bit 3 i + a of the code = bit i of c_a: x lowest), an invalid face has code 2^36;
+ *             key_f = code 2^24 + f (int64).  Keys are unique, so sorting them leaves nothing to the sort's stability.
+ *   tree      the caller sorts the keys ascending.  A leaf holds LEAF = 4 consecutive sorted faces: nL = ceil(F / 4) leaves, P the
+ *             smallest power of two >= max(nL, 1).  A complete binary tree in heap order: the root is node 1, the children of i
+ *             are 2 i and 2 i + 1, the leaves are P .. 2 P - 1 (leaf P + j holds the sorted faces 4 j .. 4 j + 3), node 0 is unused.
+ *             A node is six floats, the exact min and max of the float32 corner coordinates of the valid faces below it; a node
+ *             with none is (+inf, -inf).  order [F]: the face of each sorted key, -1 for an invalid one.  The depth is at most 22.
+ *   query     one lane per point, a stackless depth-first walk: the lane keeps the node index and one 32-bit trail word with a
+ *             bit per level at which the far sibling is still pending.  At an internal node the child whose box is nearer is
+ *             entered first (the left one on a tie); going up, the lane pops to the lowest set bit k, the pending sibling is
+ *             (node >> k) ^ 1, and it is tested again, for the best distance may have improved.  A leaf takes D(p, f) of each of
+ *             its valid faces into the smallest key.  Neither the order of the walk nor the tree enters the result.
+ *   rule      m is the distance (double) from the point to a node's box; S the largest |coordinate| among the point, the root box
+ *             and the box [lo, hi]; slack = 2^-18 S.  A node is skipped only if it is empty, or if m > slack and
+ *             (m - slack)^2 (1 - 2^-20) is strictly greater than the best dist2.  Every point of a face lies in the boxes of all
+ *             its ancestors, so m bounds the true distance from below; the slack and the factor cover the float32 error of the
+ *             computed distance as in "mesh distance", query.  On equality a node is entered: a lower face index may still tie.
+ *   closest   for point i and face f = face[i]: the q of "mesh distance", distance, as computed, so that dot(p - q, p - q) is dist2
+ *             bit for bit when f is the face the query answered; three NaN (0x7FC00000) for f = -1, f outside [0, F) or an invalid
+ *             face.
+ * Calls:
+ *   nerf_bvh_keys          keys [F] int64.  One lane per face, no atomics.  F = 0: nothing is launched.
+ *   nerf_bvh_build         sorted_keys [F] int64 (the keys sorted ascending; every face named by a key is tested again, so keys
+ *                          that are not this mesh's cannot lead a read out of range) -> the nodes and the order in the workspace:
+ *                          one launch for the leaves, one per level upward, the levels of at most 256 nodes in one launch of one
+ *                          workgroup; 2 + max(0, log2 P - 9) launches, at most 15, a function of F alone.  No atomics, no host
+ *                          read, no workgroup waits for another.  F = 0: an empty root is written.
+ *   nerf_bvh_query         dist2 [n], face [n] of a chunk of points [n, 3]; the same mesh and workspace as the build, and the box
+ *                          (it enters S only).  No host read, no atomics, no LDS; the workspace is only read, so one build serves
+ *                          any number of chunks.  n = 0: nothing is launched.
+ *   nerf_closest_points    closest [n, 3] of points [n, 3] and face [n] int32.  Needs no index.  n = 0: nothing is launched.
+ * workspace (build, query): nerf_bvh_workspace_bytes(F) bytes (-1 for an F out of range), starting on a multiple of 16 bytes:
+ * the nodes [2 P][6] float32, then the order [F] int32, each region padded to 16 bytes.  Its content on entry is unspecified.  One
+ * writer per output element: bit-reproducible; under a renumbering of the faces dist2 is unchanged and face follows the renumbering.
+ * Out of range (V, F outside [0, 2^24], n outside [0, 2^30], lo >= hi or a non-finite corner, a misaligned workspace):
+ * NERF_E_SHAPE; NULL: NERF_E_NULL; all argument checks run before any device work.
+ * Not done: no surface-area-heuristic or Karras (longest-common-prefix) splits -- the tree is the implicit median split of the
+ * Morton order; no signed distance; no ray casting.                                                                               */
+int64_t nerf_bvh_workspace_bytes(int64_t F);
+int nerf_bvh_keys(const float* verts, int64_t V, const int32_t* faces, int64_t F, const float* lo_host, const float* hi_host,
+                  int64_t* keys, void* stream);
+int nerf_bvh_build(const float* verts, int64_t V, const int32_t* faces, int64_t F, const int64_t* sorted_keys, void* workspace,
+                   void* stream);
+int nerf_bvh_query(const float* points, int64_t n, const float* verts, int64_t V, const int32_t* faces, int64_t F,
+                   const float* lo_host, const float* hi_host, const void* workspace, float* dist2, int32_t* face, void* stream);
+int nerf_closest_points(const float* points, int64_t n, const float* verts, int64_t V, const int32_t* faces, int64_t F,
+                        const int32_t* face, float* closest, void* stream);
+
 /* ---------------------------------------------------------------- texture atlas (no reference counterpart)
  * A texture for a finished mesh, baked by one field query per texel: a simplified mesh then carries the field's appearance at
  * a resolution of its own, not one colour per surviving vertex.  A separate step behind the export pipeline; it changes no

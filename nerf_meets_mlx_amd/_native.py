@@ -144,6 +144,11 @@ SIGNATURES = {
     "nerf_meshdist_build": (_I, [_P, _I64, _P, _I64, C.POINTER(C.c_float), C.POINTER(C.c_float), _I, _P, _P, _I64, _P]),
     "nerf_meshdist_query": (_I, [_P, _I64, _P, _I64, _P, _I64, C.POINTER(C.c_float), C.POINTER(C.c_float), _I, _P, _P, _I64, _P, _P,
                                 _P]),
+    "nerf_bvh_workspace_bytes": (_I64, [_I64]),
+    "nerf_bvh_keys": (_I, [_P, _I64, _P, _I64, C.POINTER(C.c_float), C.POINTER(C.c_float), _P, _P]),
+    "nerf_bvh_build": (_I, [_P, _I64, _P, _I64, _P, _P, _P]),
+    "nerf_bvh_query": (_I, [_P, _I64, _P, _I64, _P, _I64, C.POINTER(C.c_float), C.POINTER(C.c_float), _P, _P, _P, _P]),
+    "nerf_closest_points": (_I, [_P, _I64, _P, _I64, _P, _I64, _P, _P, _P]),
 }
 
 

@@ -5,10 +5,13 @@ is Instant-NGP's.  One module per stage, and every name of theirs is a name of t
   _checks (the three argument tests) <- _base (Mesh, the lattice arguments, the stage hook) <- surface (simplify, smooth) <- volume
   (density volume, marching cubes, components, opening, extract / mesh_volume); _base <- tsdf (TSDFVolume, tsdf_views); _base <-
   texture (atlas bake and lookup, mip pyramid) <- raster (rasterize, face_lod, render_mesh, render_mesh_mip) <- project
-  (project_texture); texture <- files (PLY, OBJ, PNG); _base <- distance (sample_surface, MeshIndex, mesh_distance)."""
+  (project_texture); texture <- files (PLY, OBJ, PNG); _base <- distance (sample_surface, MeshIndex, mesh_distance).
+  distance also holds the second index, MeshBVH (a bounding-volume hierarchy with the grid's answers bit for bit), and
+  closest_points."""
 from ._base import CHUNK, MAX_RES, SIMPLIFY_MAX_ITEMS, Mesh, _box, _check_mesh_tensors, _mark, check_mesh_args
-from .distance import (DISTANCE_MAX_ENTRIES, DISTANCE_MAX_GRID, DISTANCE_MAX_SAMPLES, DistanceStats, MeshDistance, MeshIndex,
-                       check_distance_args, default_distance_grid, mesh_distance, point_mesh_distance, sample_surface)
+from .distance import (DISTANCE_INDEXES, DISTANCE_MAX_ENTRIES, DISTANCE_MAX_GRID, DISTANCE_MAX_SAMPLES, DistanceStats, MeshBVH,
+                       MeshDistance, MeshIndex, check_distance_args, check_distance_index, closest_points, default_distance_grid,
+                       mesh_distance, point_mesh_distance, sample_surface)
 from .files import _PNG_MAGIC, _png_chunk, _replace_file, png_array, png_bytes, read_obj, read_ply, write_obj, write_ply
 from .project import PROJECT_COS_MIN, PROJECT_DEPTH_TOL_CELLS, PROJECT_MAX_VIEWS, PROJECT_MODES, check_project_args, project_texture
 from .raster import (RASTER_MAX_SIDE, RASTER_NEAR, RASTER_SMALL_MAX, MeshFrame, _raster_background, _raster_view, check_lod_scale,

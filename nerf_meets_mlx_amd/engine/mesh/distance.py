@@ -6,6 +6,10 @@ mesh.
   * `MeshIndex(mesh, lo, hi, grid)` enters the faces into a `grid`^3 lattice of the box once; `.query(points)` answers, per point,
     the squared distance to the closest face and that face, bit for bit what a scan over every face answers (`grid=1` is that
     scan).  `point_mesh_distance` is the one-shot form.
+  * `MeshBVH(mesh, lo, hi)` is the second index with the same answers, bit for bit: a bounding-volume hierarchy over the
+    Morton-sorted faces (include/nerf_hip.h "mesh BVH"), whose cost does not grow with the empty space
+    between a point and the surface.  `index="bvh"` selects it in `point_mesh_distance` and `mesh_distance`; "grid" is the default.
+  * `closest_points(mesh, points, face)` is the closest point of the given face per point: the q behind the query's dist2.
   * `mesh_distance(a, b, n, lo, hi, seed, tau)` samples both meshes, queries each set against the other mesh and reduces: mean,
     RMS and Hausdorff distance per direction and symmetric, and with `tau` precision, recall and F-score.
   * `check_distance_args` is the one check of their arguments."""
@@ -21,6 +25,7 @@ from ._checks import need_int, need_real, need_tensor
 DISTANCE_MAX_GRID = 256
 DISTANCE_MAX_SAMPLES = 1 << 30
 DISTANCE_MAX_ENTRIES = 1 << 30
+DISTANCE_INDEXES = ("grid", "bvh")
 DISTANCE_SORTED_QUERY = True      # query in cell-sorted order (measured 2.4 - 3.2 times faster on 2^20 samples: DESIGN.md section 37)
 
 
@@ -145,9 +150,125 @@ class MeshIndex:
         return dist2, face
 
 
-def point_mesh_distance(points: torch.Tensor, mesh: Mesh, lo, hi, grid=None):
-    """MeshIndex(mesh, lo, hi, grid).query(points)."""
-    return MeshIndex(mesh, lo, hi, grid).query(points)
+BVH_SORTED_QUERY = True           # query in Morton order of the points (measured 1.4 - 1.9 times faster: DESIGN.md section 38)
+BVH_LEAF = 4
+BVH_CELLS = 4096
+
+
+def _morton_codes(points, lo, hi):
+    """int64 [n]: the 36-bit Morton code of each point's cell on the 4096^3 lattice of the box (clamped; NaN as 0), x lowest:
+    torch plumbing, no result depends on it."""
+    tlo = torch.tensor(lo, dtype=torch.float64, device=points.device)
+    ext = torch.tensor(hi, dtype=torch.float64, device=points.device) - tlo
+    c = ((torch.nan_to_num(points.double(), nan=0.0, posinf=0.0, neginf=0.0) - tlo) / ext * BVH_CELLS).floor().clamp_(0, BVH_CELLS - 1).long()
+    c = (c | (c << 16)) & 0x00000000FF0000FF
+    c = (c | (c << 8)) & 0x000000F00F00F00F
+    c = (c | (c << 4)) & 0x00000030C30C30C3
+    c = (c | (c << 2)) & 0x0000009249249249
+    return c[:, 0] | (c[:, 1] << 1) | (c[:, 2] << 2)
+
+
+class MeshBVH:
+    """The faces of `mesh` in a bounding-volume hierarchy: Morton keys of the faces' bounding-box midpoints on the 4096^3 lattice
+    of the box [lo, hi] (nerf_bvh_keys), one torch.sort (the keys are unique), then leaves of four sorted faces under a complete
+    binary tree of exact float32 boxes (nerf_bvh_build: no host read).  Faces may stick out of the box and points may lie outside
+    it; the box only shapes the tree, never an answer.  The index keeps the mesh's tensors; they must not change while it is in
+    use.  mark: _mark's hook ("keys", "sort_keys", "build")."""
+
+    def __init__(self, mesh: Mesh, lo, hi, mark=None):
+        _, lo, hi, _, _, _ = check_distance_args(mesh, 0, lo, hi)
+        self.mesh, self.lo, self.hi = mesh, lo, hi
+        self.V, self.F = mesh.verts.shape[0], mesh.faces.shape[0]
+        self.leaves = -(-self.F // BVH_LEAF)
+        self.P = 1 << max(self.leaves - 1, 0).bit_length()
+        dev = mesh.verts.device
+        L = N.lib()
+        self._box = _box(lo, hi)
+        self._ws = torch.empty(L.nerf_bvh_workspace_bytes(self.F), dtype=torch.uint8, device=dev)
+        keys = torch.empty(self.F, dtype=torch.int64, device=dev)
+        _mark(mark, "keys")
+        N.check(L.nerf_bvh_keys(N.ptr(mesh.verts), self.V, N.ptr(mesh.faces), self.F, *self._box, N.ptr(keys), N.stream()))
+        _mark(mark, "sort_keys")
+        keys = torch.sort(keys).values
+        _mark(mark, "build")
+        N.check(L.nerf_bvh_build(N.ptr(mesh.verts), self.V, N.ptr(mesh.faces), self.F, N.ptr(keys), N.ptr(self._ws), N.stream()))
+
+    @property
+    def nodes(self):
+        """float32 [2 P, 6]: node i as (min x y z, max x y z) in heap order; node 0 is unused.  A view: do not write."""
+        return self._ws[:2 * self.P * 24].view(torch.float32).view(2 * self.P, 6)
+
+    @property
+    def order(self):
+        """int32 [F]: the face of each sorted key, -1 for an invalid face.  A view: do not write."""
+        at = (2 * self.P * 24 + 15) // 16 * 16
+        return self._ws[at:at + 4 * self.F].view(torch.int32)
+
+    def query(self, points: torch.Tensor, sort: Optional[bool] = None, mark=None):
+        """(dist2 float32 [n], face int32 [n]) of points [n, 3]: MeshIndex.query's contract and its bits (nerf_bvh_query: no host
+        read, any number of calls per index).  `sort`: query the points in the order of their own 36-bit Morton codes and scatter
+        the answers back, the same bits (None: BVH_SORTED_QUERY).  mark: _mark's hook ("sort", "query", "scatter")."""
+        n = points.shape[0] if torch.is_tensor(points) and points.dim() == 2 else 0
+        check_distance_args(self.mesh, n, self.lo, self.hi, points=points)
+        dev = points.device
+        dist2 = torch.empty(n, dtype=torch.float32, device=dev)
+        face = torch.empty(n, dtype=torch.int32, device=dev)
+        if n == 0:
+            return dist2, face
+        sort = BVH_SORTED_QUERY if sort is None else bool(sort)
+        order = None
+        if sort:
+            _mark(mark, "sort")
+            order = torch.sort(_morton_codes(points, self.lo, self.hi)).indices
+            points = points[order].contiguous()
+        m = self.mesh
+        _mark(mark, "query")
+        N.check(N.lib().nerf_bvh_query(N.ptr(points), n, N.ptr(m.verts), self.V, N.ptr(m.faces), self.F, *self._box, N.ptr(self._ws),
+                                       N.ptr(dist2), N.ptr(face), N.stream()))
+        if order is not None:
+            _mark(mark, "scatter")
+            d, f = torch.empty_like(dist2), torch.empty_like(face)
+            d[order], f[order] = dist2, face
+            dist2, face = d, f
+        return dist2, face
+
+
+def check_distance_index(index) -> str:
+    """`index` as given; ValueError unless it is "grid" or "bvh"."""
+    if not isinstance(index, str) or index not in DISTANCE_INDEXES:
+        raise ValueError(f"distance index must be one of {DISTANCE_INDEXES}, got {index!r}")
+    return index
+
+
+def _index(mesh, lo, hi, grid, index):
+    if index == "bvh":
+        if grid is not None:
+            raise ValueError(f"distance grid must be None with index='bvh', got {grid!r}")
+        return MeshBVH(mesh, lo, hi)
+    return MeshIndex(mesh, lo, hi, grid)
+
+
+def point_mesh_distance(points: torch.Tensor, mesh: Mesh, lo, hi, grid=None, index="grid"):
+    """MeshIndex(mesh, lo, hi, grid).query(points), or with index="bvh" MeshBVH(mesh, lo, hi).query(points): the same bits."""
+    return _index(mesh, lo, hi, grid, check_distance_index(index)).query(points)
+
+
+def closest_points(mesh: Mesh, points: torch.Tensor, face: torch.Tensor):
+    """float32 [n, 3]: for points [n, 3] and face int32 [n] (a query's answer), the closest point of that face as the query
+    computed it, so that dot(p - q, p - q) in float32 is the query's dist2 bit for bit; NaN for a face of -1, out of range or
+    invalid (nerf_closest_points: one lane per point, no index needed)."""
+    _check_mesh_tensors("distance", mesh)
+    dev = mesh.verts.device
+    n = points.shape[0] if torch.is_tensor(points) and points.dim() == 2 else 0
+    need_tensor(points, "distance: points", torch.float32, (n, 3), dev, "[n, 3]")
+    need_tensor(face, "distance: face", torch.int32, (n,), dev, "[n]")
+    if n > DISTANCE_MAX_SAMPLES:
+        raise ValueError(f"distance: at most 2^30 points, got {n}")
+    out = torch.empty(n, 3, dtype=torch.float32, device=dev)
+    if n:
+        N.check(N.lib().nerf_closest_points(N.ptr(points), n, N.ptr(mesh.verts), mesh.verts.shape[0], N.ptr(mesh.faces),
+                                            mesh.faces.shape[0], N.ptr(face), N.ptr(out), N.stream()))
+    return out
 
 
 class DistanceStats(NamedTuple):
@@ -176,13 +297,15 @@ def _stats(d2: torch.Tensor) -> DistanceStats:
     return DistanceStats(float(d2.sqrt().mean()), float(d2.mean().sqrt()), float(d2.max().sqrt()))
 
 
-def mesh_distance(a: Mesh, b: Mesh, n: int, lo, hi, seed: int = 0, tau=None, grid=None, mark=None) -> MeshDistance:
+def mesh_distance(a: Mesh, b: Mesh, n: int, lo, hi, seed: int = 0, tau=None, grid=None, mark=None, index="grid") -> MeshDistance:
     """The distance between two meshes from n >= 1 area-weighted samples a side (the samples of `seed` on each): every sample of
     a is taken to the surface of b and the reverse; mean, RMS and largest distance per direction, and symmetric (the mean over
     both sets, the Hausdorff distance).  With `tau`, precision = the share of a's samples within tau of b, recall = the share of
     b's within tau of a, and their F-score, a being the reconstruction and b the truth.  Roots and reductions are torch float64 on
-    the kernels' float32 squared distances, which the result carries.  mark: _mark's hook ("sample_a", "index_b", "query_ab",
-    "sample_b", "index_a", "query_ba", "reduce")."""
+    the kernels' float32 squared distances, which the result carries.  `index`: "grid" (MeshIndex) or "bvh" (MeshBVH, the
+    better choice when the meshes lie cells apart: DESIGN.md section 38); every field is the same.  mark: _mark's hook
+    ("sample_a", "index_b", "query_ab", "sample_b", "index_a", "query_ba", "reduce")."""
+    index = check_distance_index(index)
     n, lo, hi, grid, seed, tau = check_distance_args(a, n, lo, hi, grid=grid, seed=seed, tau=tau)
     check_distance_args(b, n, lo, hi)
     if n < 1:
@@ -190,13 +313,13 @@ def mesh_distance(a: Mesh, b: Mesh, n: int, lo, hi, seed: int = 0, tau=None, gri
     _mark(mark, "sample_a")
     pa, _ = sample_surface(a, n, lo, hi, seed)
     _mark(mark, "index_b")
-    ib = MeshIndex(b, lo, hi, grid)
+    ib = _index(b, lo, hi, grid, index)
     _mark(mark, "query_ab")
     d_ab, f_ab = ib.query(pa)
     _mark(mark, "sample_b")
     pb, _ = sample_surface(b, n, lo, hi, seed)
     _mark(mark, "index_a")
-    ia = MeshIndex(a, lo, hi, grid)
+    ia = _index(a, lo, hi, grid, index)
     _mark(mark, "query_ba")
     d_ba, f_ba = ia.query(pb)
     _mark(mark, "reduce")

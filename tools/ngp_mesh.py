@@ -673,12 +673,12 @@ def _tsdf_arm(tr, mesh, R, lo, hi, a, rec, bound, boxes):
     return out, m
 
 
-def _distance_pair(mesh, x, y, n, lo, hi, h, reps):
+def _distance_pair(mesh, x, y, n, lo, hi, h, reps, index="grid"):
     """engine.mesh.mesh_distance(x, y) with tau = h: the figures in units of h and the stages' device ms (host reads included)."""
     ts = []
     for _ in range(reps + 1):                                            # the first run warms the allocator
         st = _Stages()
-        r = mesh.mesh_distance(x, y, n, lo, hi, seed=0, tau=h, mark=st)
+        r = mesh.mesh_distance(x, y, n, lo, hi, seed=0, tau=h, mark=st, index=index)
         st("end")
         ts.append(st.total_ms())
     t = {k: float(np.mean([q[k] for q in ts[1:]])) for k in ts[0]}
@@ -741,7 +741,8 @@ def _distance_arms(mesh, m, tsdf_mesh, teacher, R, lo, hi, a, rec, bound):
     if tsdf_mesh is not None:
         arms.append(("tsdf", tsdf_mesh))
     out = []
-    base = {"tool": "ngp_mesh distance", "R": R, "iters": rec["iters"], "seed": rec["seed"], "h": h, "device": rec["device"]}
+    base = {"tool": "ngp_mesh distance", "R": R, "iters": rec["iters"], "seed": rec["seed"], "h": h, "device": rec["device"],
+            "index": a.distance_index}
 
     def line(r):
         print(json.dumps(r), flush=True)
@@ -750,10 +751,10 @@ def _distance_arms(mesh, m, tsdf_mesh, teacher, R, lo, hi, a, rec, bound):
     line({**base, "a": arms[0][0], "b": "marching cubes", "timing": _distance_timing(mesh, arms[0][1], m, n, lo, hi, a.reps)})
     for name, x in arms:
         if x.faces.shape[0]:
-            line({**base, "a": name, "b": "marching cubes", **_distance_pair(mesh, x, m, n, lo, hi, h, a.reps)})
+            line({**base, "a": name, "b": "marching cubes", **_distance_pair(mesh, x, m, n, lo, hi, h, a.reps, a.distance_index)})
     for name, x in [("marching cubes", m)] + arms:
         if x.faces.shape[0] and teacher.faces.shape[0]:
-            line({**base, "a": name, "b": "teacher", **_distance_pair(mesh, x, teacher, n, lo, hi, h, a.reps)})
+            line({**base, "a": name, "b": "teacher", **_distance_pair(mesh, x, teacher, n, lo, hi, h, a.reps, a.distance_index)})
     return out
 
 
@@ -840,6 +841,9 @@ def parser():
                          "(the first --smooth N, default 10) and, with --tsdf, TSDF meshes against the marching-cubes mesh, and of "
                          "all of them against the teacher's marching-cubes surface; index build and query times")
     ap.add_argument("--distance-n", type=int, default=1 << 20, metavar="N", help="--distance: samples a side")
+    ap.add_argument("--distance-index", choices=("grid", "bvh"), default="grid",
+                    help="--distance: the face index of the pairs, the uniform grid or the bounding-volume hierarchy (DESIGN.md "
+                         "section 38); the figures are the same bit for bit, the stage times are not")
     ap.add_argument("--smooth-lambda", type=float, default=0.5)
     ap.add_argument("--smooth-mu", type=float, default=-0.53, help="0: plain Laplacian smoothing")
     ap.add_argument("--ckpt", default=None, help="load this checkpoint instead of training")
