@@ -1315,6 +1315,15 @@ int nerf_comm_destroy(void* comm);
  *                     partial-tile slot that is idle at that moment: no workspace size changes.  Other models and precisions, a
  *                     non-zero "dw_job_mask" and "dw22_variant" 0 (one launch over all slots) keep the three jobs whatever this says.
  *                     The affected tensors are summed in a different order (~1e-6 rel-L2); each setting is bit-reproducible.
+ *   "train_fold"      split-bf16 TRAINING image and kernels of the 8 x 256 view model at precision 22: 0 (default) the unfolded form |
+ *                     1 the feature layer folded into dir0 (W' = W_D[:, :256] W_F, b' = W_D[:, :256] b_F + b_D, each element the float64
+ *                     sum in index order rounded once to float32, computed by nerf_mlp_pack): the training forward neither computes
+ *                     nor stores `feature`, the chain neither computes nor stores dZ_F (nerf_mlp_debug_read of layer 8 then reads
+ *                     whatever the workspace held), and the post step of "dw_factor" takes W_F, W_D[:, :256] and b_F from fp32 copies
+ *                     inside the image.  The packed image keeps its size but holds ONE form: nerf_mlp_pack, the training forward and
+ *                     nerf_mlp_backward of a model must run under the same setting (models/NeRF.py sets it around its own calls).
+ *                     Takes effect only where the factored job list runs ("dw_factor" 1, "dw22_variant" 1, no "dw_job_mask");
+ *                     ignored otherwise and by every other model and precision.  sigma is bit-identical to the unfolded form.
  * nerf_get_option returns the current value of EVERY key nerf_set_option accepts (a get / set pair restores a setting;
  * "dw_unit_bias" reads -1 while it is automatic), or NERF_OPTION_UNKNOWN for an unknown key.                        */
 #define NERF_OPTION_UNKNOWN (-2147483647 - 1)

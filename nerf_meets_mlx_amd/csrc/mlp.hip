@@ -1232,6 +1232,7 @@ static int g_dw_private = 4;   // "dw_private_tiles": split-bf16 dW jobs of at m
 static int g_dw16_variant = 1;  // "dw16_variant": bf16 weight gradients: 1 (default) = 256 x 256 jobs on mlp_dww.hip's kernel, tiny-job lists on mlp_s16.hip's, the rest on mlp_dw_kernel; 0 = every job on mlp_dw_kernel; 2 = as 1 without the tiny-job rule; 3 = as 1 with mlp_s16.hip's kernel for every narrow job
 static int g_dw_narrow_first = 1;   // "dw_narrow_first": order of the two weight-gradient launches (A/B knob; same gradients either way)
 static int g_dw_factor = 1;    // "dw_factor": view model at precision 22: 1 = feature / alpha / dir0 | feature as one shared job + post step (mlp_model.h), 0 = three jobs
+static int g_train_fold = 0;   // "train_fold": view model at precision 22 with the factored job list: 1 = the folded split-bf16 training image and kernels (mlp_s16.h), 0 (default) = unfolded
 static int g_dw_job_mask = 0;  // diagnostic: nonzero = run only these dW jobs (bit j); view model only
 // (g_tile_pad16, "tile_pad16": mlp_model.h, beside the strides it enters)
 static int g_mlp_variant = 0;   // 0: auto, 1: ST=1 via L1, 2: ST=2 via L1, 3: LDS ring, 8 waves x 32 samples, 32x32x16 MFMA,
@@ -1256,6 +1257,12 @@ static int cu_count() {
   }
   return n[dev];
 }
+// The weight gradients of the view model at precision 22 run the factored job list (mlp_model.h: VIEW_JOBS_FACTORED) ...
+static inline bool dw_factored(const Model& m) { return g_dw_factor && m.can_factor() && !g_dw_job_mask && s16::g_dw_variant != 0; }   // (launch_dw: two launches only)
+// ... and only then may its split-bf16 training image be the folded one ("train_fold"): pack, training forward, chain and post step
+// all ask here, so the caller sets the option around the calls of one model and a folded image never meets an unfolded kernel.
+// Without the factored list the option is ignored.
+static inline bool train_folded(const Model& m) { return g_train_fold && dw_factored(m); }
 static inline int ring_wgs() { return g_ring_wgs > 0 ? g_ring_wgs : cu_count(); }
 // grid of the 8-wave ring kernels: one workgroup per super-tile of 8 tiles, at most one per CU
 static inline unsigned ring_grid(int64_t ntiles) { return persistent_grid((ntiles + 7) / 8, ring_wgs()); }
@@ -1283,6 +1290,7 @@ static const Option OPTIONS[] = {
     {"pass_queue", &g_pass_queue, opt_flag, nullptr},
     {"dw_narrow_first", &g_dw_narrow_first, opt_flag, nullptr},
     {"dw_factor", &g_dw_factor, opt_flag, nullptr},
+    {"train_fold", &g_train_fold, opt_flag, nullptr},
     {"f22_tiles", &f22::g_tiles, [](int& v) { return v == 0 || v == 2 || v == 3; }, "nerf_set_option: f22_tiles must be 0 (automatic), 2 or 3"},
 };
 
@@ -1343,7 +1351,7 @@ extern "C" int nerf_mlp_pack(const nerf_mlp_arch* arch, const float* params, voi
                              m.stream<bf16x8>(packed, S_FWD16));
     if (!rc && m.prec == Prec::F32) rc = f32::pack(params, m.stream<void>(packed, S_F32), 0, s);
     if (!rc && m.split()) rc = f22::pack(params, m.stream<void>(packed, S_F22), s);
-    if (!rc && m.split()) rc = s16::pack(params, m.stream<void>(packed, S_S16), s);
+    if (!rc && m.split()) rc = s16::pack(params, m.stream<void>(packed, S_S16), train_folded(m), s);
   }
   return rc;
 }
@@ -1439,7 +1447,7 @@ static int view_forward(const Model& m, const void* packed, const float* x, cons
     return f22::forward(m.stream<void>(packed, S_F22), x, rays, z, M, n, freq_mode, out, ring_wgs(), s);
   if (m.split())                               // training forward: split bf16, hi + lo fragment blocks kept
     return s16::forward(m.stream<void>(packed, S_S16), m.stream<float>(packed, S_BIAS), x, rays, z, M, n, freq_mode, out, acts,
-                        m.astride(), ring_wgs(), s);
+                        m.astride(), ring_wgs(), train_folded(m), s);
   if (m.prec == Prec::F32) return f32::forward(m.stream<void>(packed, S_F32), x, rays, z, M, n, freq_mode, out, acts, 0, s);
   return x ? launch_fwd<0>(m, packed, x, rays, z, M, n, freq_mode, out, acts, stream)
            : launch_fwd<1>(m, packed, x, rays, z, M, n, freq_mode, out, acts, stream);
@@ -1537,7 +1545,7 @@ static int launch_dw(const Model& m, const void* packed, DwArgs& d, int nj, int6
     if (!do_wide && nrest) {
       int rc = launch_dw_part(m, rest, nrest, ntiles, acts, dz, grads, s, split_bf16 ? 1 : 0, 0, half, factored ? half : -1);
       if (!rc && factored)
-        rc = launch_dw_factor_post(m.stream<void>(packed, S_S16), m.stream<float>(packed, S_BIAS), rest.aux, grads, s);
+        rc = launch_dw_factor_post(m.stream<void>(packed, S_S16), m.stream<float>(packed, S_BIAS), rest.aux, grads, train_folded(m), s);
       if (rc) return rc;
     }
   }
@@ -1550,7 +1558,7 @@ static int view_backward_chain(const Model& m, const void* packed, const void* a
   const int64_t ntiles = (M + 31) / 32;
   if (m.split()) {
     if (g_bwd_stage != 2) {
-      const int rcs = s16::backward_chain(m.stream<void>(packed, S_S16), acts, d_raw, M, dz, m.astride(), m.zstride(), ring_wgs(), s);
+      const int rcs = s16::backward_chain(m.stream<void>(packed, S_S16), acts, d_raw, M, dz, m.astride(), m.zstride(), ring_wgs(), train_folded(m), s);
       if (rcs) return rcs;
     }
     return check_launch("mlp backward chain");
@@ -1609,7 +1617,7 @@ static int mlp_backward_impl(const nerf_mlp_arch* arch, const void* packed, cons
   // ---- 2. dW / db
   DwArgs d;
   const int mask = m.shape == Shape::View ? g_dw_job_mask : 0;
-  const bool factored = g_dw_factor && m.can_factor() && !mask && s16::g_dw_variant != 0;      // (launch_dw: two launches only)
+  const bool factored = dw_factored(m);
   const int nj = m.dw_jobs(d.jobs, mask, factored);
   return launch_dw(m, packed, d, nj, ntiles, acts, dz, grads, s, factored);
 }

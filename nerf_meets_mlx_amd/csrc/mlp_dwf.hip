@@ -12,6 +12,11 @@
 // (K = 128 or 256) runs in float64 in a fixed order and is rounded once: bit-reproducible, and the rounding of the post step is
 // far below that of G itself.  db_D is dir0's bias gradient as it is.  Columns 256 .. 282 of dW_D (row stride 283) belong to the
 // job dir0 | dirPE and are not touched.
+//
+// FOLD (a folded image, "train_fold": mlp_s16.h): the forward and the chain multiply with W' = W_D[:, :256] W_F, so G is exactly
+// dL/dW' and the three results above are the product rule.  W_F and W_D[:, :256] are no longer streamed; the post step reads their
+// fp32 masters from the copies the pack left in the image (mlp_index.h: LF::C_WFT -- W_F transposed --, LF::C_WD1, LF::C_BF).  Same
+// formulas, float64 sums in index order, one rounding.
 #include "common.h"
 #include "launch.h"
 #include "mlp_frag.h"
@@ -27,6 +32,7 @@ __device__ __forceinline__ double pair_value(const __bf16* __restrict__ wf, cons
   return (double)(float)wf[frag_elem_offset(hi)] + (double)(float)wf[frag_elem_offset(lo)];
 }
 
+template <bool FOLD>
 __global__ void __launch_bounds__(256) mlp_dw_factor_post_kernel(const __bf16* __restrict__ wf, const float* __restrict__ bias,
                                                                  const float* __restrict__ aux, float* __restrict__ grads) {
   __shared__ double sh[256 * DWF_ROWS];                    // [K index][row of this workgroup]
@@ -34,6 +40,7 @@ __global__ void __launch_bounds__(256) mlp_dw_factor_post_kernel(const __bf16* _
   const int t = threadIdx.x;
   const float* G = aux + DWF_G;
   const float* dbD = aux + DWF_DB;
+  const float* cp = reinterpret_cast<const float*>(wf);    // FOLD: the image's fp32 copies
   double acc[DWF_ROWS];
 #pragma unroll
   for (int q = 0; q < DWF_ROWS; ++q) acc[q] = 0.0;
@@ -42,7 +49,7 @@ __global__ void __launch_bounds__(256) mlp_dw_factor_post_kernel(const __bf16* _
     const int k0 = DWF_ROWS * blockIdx.x;
     for (int e = t; e < 128 * DWF_ROWS; e += 256) {        // sh[j][q] = W_D[j][k0 + q]
       const int j = e / DWF_ROWS, q = e % DWF_ROWS;
-      sh[e] = pair_value(wf, fwd_elem_dir0(j, k0 + q));
+      sh[e] = FOLD ? (double)cp[LF::C_WD1 + j * 256 + k0 + q] : pair_value(wf, fwd_elem_dir0(j, k0 + q));
     }
     if (t < 128) sdb[t] = (double)dbD[t];
     __syncthreads();
@@ -66,6 +73,13 @@ __global__ void __launch_bounds__(256) mlp_dw_factor_post_kernel(const __bf16* _
       sh[i * DWF_ROWS + q] = (double)G[(j0 + q) * 256 + i];
     }
     __syncthreads();
+    if constexpr (FOLD) {
+      for (int i = 0; i < 256; ++i) {
+        const double w = (double)cp[LF::C_WFT + i * 256 + t];      // W_F[t][i]
+#pragma unroll
+        for (int q = 0; q < DWF_ROWS; ++q) acc[q] = __builtin_fma(w, sh[i * DWF_ROWS + q], acc[q]);
+      }
+    } else
     for (int ks = 0; ks < 16; ++ks) {
       for (int h = 0; h < 2; ++h) {
         // the eight elements of lane (t & 31, h) of k-step ks: W_F[t][kperm(ks, h, 0 .. 7)], 16 contiguous bytes per part
@@ -83,16 +97,18 @@ __global__ void __launch_bounds__(256) mlp_dw_factor_post_kernel(const __bf16* _
         }
       }
     }
-    const double bf = (double)bias[L::BI_FEAT + t];
+    const double bf = (double)(FOLD ? cp[LF::C_BF + t] : bias[L::BI_FEAT + t]);
 #pragma unroll
     for (int q = 0; q < DWF_ROWS; ++q) grads[L::P_WD + (j0 + q) * 283 + t] = (float)__builtin_fma(bf, (double)dbD[j0 + q], acc[q]);
     if (t < DWF_ROWS) grads[L::P_BD + j0 + t] = dbD[j0 + t];      // db_D itself: the shared job's bias sums are dir0's bias gradient
   }
 }
 
-int launch_dw_factor_post(const void* packed_s16, const float* bias_slots, const float* aux, float* grads, hipStream_t s) {
-  return launch<mlp_dw_factor_post_kernel>("mlp dW post step (factored feature / dir0)", dim3(DWF_BLOCKS_F + DWF_BLOCKS_D), dim3(256), 0, s,
-                                           static_cast<const __bf16*>(packed_s16), bias_slots, aux, grads);
+int launch_dw_factor_post(const void* packed_s16, const float* bias_slots, const float* aux, float* grads, bool fold, hipStream_t s) {
+  return with_bool(fold, [&](auto fd) {
+    return launch<mlp_dw_factor_post_kernel<decltype(fd)::value>>("mlp dW post step (factored feature / dir0)", dim3(DWF_BLOCKS_F + DWF_BLOCKS_D),
+                                                                  dim3(256), 0, s, static_cast<const __bf16*>(packed_s16), bias_slots, aux, grads);
+  });
 }
 
 }  // namespace nerf

@@ -213,8 +213,9 @@ constexpr int64_t DW_PARTIAL_BYTES = (int64_t)DW_MAX_WGS * DW_SLOT_FLOATS * 4;
 // turns them into dW_F, db_F and columns 0..255 of dW_D.
 constexpr int DWF_G = 0, DWF_DB = 128 * 256, DWF_FLOATS = DWF_DB + 128;
 static_assert(DWF_FLOATS <= DW_SLOT_FLOATS, "the factored job's result fits one partial-tile slot");
-// packed_s16: the split-bf16 image of the model (forward stream first); bias_slots: its fp32 bias slots
-int launch_dw_factor_post(const void* packed_s16, const float* bias_slots, const float* aux, float* grads, hipStream_t s);
+// packed_s16: the split-bf16 image of the model (forward stream first); bias_slots: its fp32 bias slots; fold: a folded image
+// (mlp_s16.h): W_F, W_D[:, :256] and b_F come from its fp32 copies
+int launch_dw_factor_post(const void* packed_s16, const float* bias_slots, const float* aux, float* grads, bool fold, hipStream_t s);
 // dW of jobs of 16 x 16 fragments only, one wave per SIMD (mlp_dww.hip); split_bf16: hi + lo blocks (precision 22), else bf16 blocks
 int launch_dw_wide_kernel(const DwArgs& d, int workgroups, bool split_bf16, hipStream_t s);
 

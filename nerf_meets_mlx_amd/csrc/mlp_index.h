@@ -114,6 +114,59 @@ __host__ __device__ constexpr int bwd_index(int f, int r, int h, int j) {
   return L::pw(l) + nn * 256 + row;
 }
 
+// ------------------------------------------------------------------------------------------
+// The folded form of the split-bf16 training image ("train_fold", mlp_s16.hip).  feature = W_F h7 + b_F has no activation
+// (models/NeRF.py:231), so dir0 reads h7 through  W' = W_D[:, :256] W_F  (128 x 256) with bias  b' = W_D[:, :256] b_F + b_D:
+//   forward stream     trunk (unchanged) | alpha head 16 | dir0' = [W' | W_D[:, 256:]] 4 x 18 | rgb 8        = 1056 pairs
+//   transposed stream  rgb^T 4 | [W'^T | W_A^T] 8 x 9 (input [dZ_D | d alpha]) | trunk (unchanged)           =  972 pairs
+// Each stream is 128 pairs (256 KiB) shorter than the unfolded one; the image keeps its size, and the freed bytes hold the fp32
+// masters the post step of the factored weight gradients needs (mlp_dwf.hip): LF::C_* below.  A source is a master parameter
+// offset (>= 0), zero padding (-1) or element (n, k) of W' (fold_wp(n, k) <= -2), which nerf_mlp_pack computes.
+// ------------------------------------------------------------------------------------------
+namespace LF {
+constexpr int F_A = L::F_FA, F_DIR = F_A + 16, F_RGB = F_DIR + 72, F_TOTAL = F_RGB + 8;         // 960, 976, 1048, 1056
+constexpr int B_RGB = 0, B_DA = 4, B_L7 = B_DA + 72, B_TOTAL = B_L7 + 7 * 128;                  // 0, 4, 76, 972
+constexpr int B_PADDED = 976;                          // pairs: 1952 fragments = 61 whole ring chunks
+constexpr int B_SHIFT = L::B_L7 - B_L7;                // trunk fragment of the unfolded stream = folded + B_SHIFT
+// fp32 copies in the bytes the shorter streams free, as float offsets from the start of the split-bf16 image (unfolded pair streams:
+// 2 x L::F_TOTAL fragments forward, 2 x 1104 transposed; a fragment is 256 floats).  Behind the forward stream: W_F TRANSPOSED
+// ([i][k] = W_F[k][i], 256 x 256: the post step reads it along k).  Behind the transposed stream: W_D[:, :256] (128 x 256, row-major),
+// b_F (256), b' (128), zeros.
+constexpr int C_WFT = 2 * F_TOTAL * 256, C_WFT_END = C_WFT + 256 * 256;
+constexpr int C_WD1 = (2 * L::F_TOTAL + 2 * B_PADDED) * 256, C_BF = C_WD1 + 128 * 256, C_BP = C_BF + 256, C_USED = C_BP + 128;
+constexpr int C_END = (2 * L::F_TOTAL + 2 * 1104) * 256;                                        // end of the image
+static_assert(C_WFT_END == 2 * L::F_TOTAL * 256, "W_F^T fills the forward stream's freed fragments exactly");
+static_assert(C_USED <= C_END, "the copies fit the transposed stream's freed fragments");
+}  // namespace LF
+__host__ __device__ constexpr int fold_wp(int n, int k) { return -2 - (n * 256 + k); }
+__host__ __device__ constexpr bool is_fold_wp(int src) { return src <= -2; }
+__host__ __device__ constexpr int fold_wp_n(int src) { return (-2 - src) >> 8; }
+__host__ __device__ constexpr int fold_wp_k(int src) { return (-2 - src) & 255; }
+
+__host__ __device__ constexpr int fwd_index_fold(int f, int r, int h, int j) {
+  if (f < LF::F_A) return fwd_index(f, r, h, j);       // trunk
+  if (f < LF::F_DIR) return r == 0 ? L::P_WA + kperm(f - LF::F_A, h, j) : -1;                   // alpha: row 0 of one tile, K = 256
+  if (f < LF::F_RGB) {                                 // dir0': [h7(256), dirPE(27+5 pad)] vs [W' | WD[:, 256:]]
+    const int g = f - LF::F_DIR;
+    const int nt = g / 18, ks = g % 18;
+    const int kk = kperm(ks, h, j), n = 32 * nt + r;
+    if (kk < 256) return fold_wp(n, kk);
+    return (kk - 256) < 27 ? L::P_WD + n * 283 + kk : -1;
+  }
+  const int ks = f - LF::F_RGB;                        // rgb
+  return r < 3 ? L::P_WR + r * 128 + kperm(ks, h, j) : -1;
+}
+__host__ __device__ constexpr int bwd_index_fold(int f, int r, int h, int j) {
+  if (f < LF::B_DA) return bwd_index(f, r, h, j);      // rgb^T
+  if (f < LF::B_L7) {                                  // [W'; alpha]^T: 8 tiles of h7 x 9 k-steps (dZ_D 0..127, d alpha 128)
+    const int g = f - LF::B_DA, kt = g / 9, ns = g % 9;
+    const int nn = kperm(ns, h, j), row = 32 * kt + r;
+    if (ns < 8) return fold_wp(nn, row);
+    return nn == 128 ? L::P_WA + row : -1;
+  }
+  return bwd_index(f + LF::B_SHIFT, r, h, j);          // pos7 .. pos1
+}
+
 // bias slot s -> offset of the master parameter, -1 = zero padding
 __host__ __device__ constexpr int bias_index(int s) {
   if (s < L::BI_FEAT) return L::pb(s >> 8) + (s & 255);
@@ -148,6 +201,13 @@ __host__ __device__ constexpr FragElem fwd_elem_feature(int row, int col) {
 // W_D[row][col], col < 256 (dir0 layer, feature columns): fwd_index(fwd_elem_dir0(row, col)) == P_WD + row * 283 + col
 __host__ __device__ constexpr FragElem fwd_elem_dir0(int row, int col) {
   return FragElem{L::F_DIR + 18 * (row >> 5) + kperm_ks(col), row & 31, kperm_h(col), kperm_j(col)};
+}
+// W'[n][k] in the folded streams: fwd_index_fold(fold_elem_fwd(n, k)) == bwd_index_fold(fold_elem_bwd(n, k)) == fold_wp(n, k)
+__host__ __device__ constexpr FragElem fold_elem_fwd(int n, int k) {
+  return FragElem{LF::F_DIR + 18 * (n >> 5) + kperm_ks(k), n & 31, kperm_h(k), kperm_j(k)};
+}
+__host__ __device__ constexpr FragElem fold_elem_bwd(int n, int k) {
+  return FragElem{LF::B_DA + 9 * (k >> 5) + kperm_ks(n), k & 31, kperm_h(n), kperm_j(n)};
 }
 // bf16 element index of a fragment element in a weight stream of 1 KiB fragments: lane 32 h + r holds eight elements of 2 bytes
 __host__ __device__ constexpr int frag_elem_offset(const FragElem& e) { return (e.f * 64 + 32 * e.h + e.r) * 8 + e.j; }

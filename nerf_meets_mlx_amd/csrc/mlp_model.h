@@ -53,6 +53,10 @@ constexpr DwJob VIEW_JOBS[] = {
 // over the nine adjacent dZ fragments Z_A, Z_D .. Z_D + 7 and H7 (25 fragments): row 0 of its result is d alpha, rows 16 .. 143
 // are G (DwJob::aux_row0), which the post step of mlp_dwf.hip multiplies with the packed weights once per call.
 static_assert(L::Z_D == L::Z_A + 1, "d alpha and dZ_D are adjacent dZ fragments");
+// A FOLDED split-bf16 training image ("train_fold": mlp_s16.h; streams and fp32 copies: mlp_index.h, namespace LF) multiplies with
+// W' = W_D[:, :256] W_F in the forward and the chain, so G is exactly dL/dW' there; it ALWAYS runs this list -- the post step then reads
+// the fp32 masters from the image's copies --, and its stores have no feature / dZ_F blocks (slots L::A_FEAT, L::Z_F stay unwritten; the
+// slot numbering and the strides are unchanged).  mlp.hip: train_folded().
 constexpr DwJob VIEW_JOBS_FACTORED[] = {
     VIEW_JOBS[0], VIEW_JOBS[1], VIEW_JOBS[2], VIEW_JOBS[3], VIEW_JOBS[4], VIEW_JOBS[5], VIEW_JOBS[6], VIEW_JOBS[7], VIEW_JOBS[8],
     {L::Z_A, 9, L::A_H0 + 112, 16, L::P_WA, 256, 0, 16 + 128, 256, L::P_BA, 1, 16},    // alpha | G, db_D (shared)

@@ -25,12 +25,25 @@ constexpr int Z_LO = 154, Z_SLOTS = 308;
 constexpr int F_FRAGS = 2368, B_FRAGS = 2200, B_PADDED = 2208;
 constexpr int64_t PACKED_BYTES = (int64_t)(F_FRAGS + B_PADDED) * 1024;
 
-int pack(const float* params, void* packed_s16, hipStream_t s);
+// The FOLDED form of the same image ("train_fold"; stream description: mlp_index.h, namespace LF): the feature layer is folded into
+// dir0, W' = W_D[:, :256] W_F and b' = W_D[:, :256] b_F + b_D computed by pack() -- each element the float64 sum in index order
+// from the fp32 masters, rounded once to float32 (b_D added last), then split like every other weight.  Each stream is 128 pairs
+// shorter (66 and 61 ring chunks); the image keeps PACKED_BYTES, the freed bytes hold fp32 copies of W_F (transposed), W_D[:, :256],
+// b_F and b' and are otherwise zero.  A folded image is read by the folded kernels only: the caller passes the same `fold` to
+// pack, forward, backward_chain and the post step of the factored weight gradients.  The forward then neither computes nor stores
+// `feature` (slots L::A_FEAT) and the chain neither computes nor stores dZ_F (slots L::Z_F).
+int pack(const float* params, void* packed_s16, bool fold, hipStream_t s);
 // x != nullptr: embedded rows [M,90]; else rays [B,11] + z [B,n] with the encodings evaluated in the kernel.  acts != nullptr.
 int forward(const void* packed_s16, const float* bias_slots, const float* x, const float* rays, const float* z, int64_t M,
-            int n, int freq_mode, float* out, void* acts, int64_t astride16, int persistent_wgs, hipStream_t s);
+            int n, int freq_mode, float* out, void* acts, int64_t astride16, int persistent_wgs, bool fold, hipStream_t s);
 int backward_chain(const void* packed_s16, const void* acts, const float* d_raw, int64_t M, void* dz, int64_t astride16,
-                   int64_t zstride16, int persistent_wgs, hipStream_t s);
+                   int64_t zstride16, int persistent_wgs, bool fold, hipStream_t s);
+// the folded form's unit (mlp_s16f.hip), reached through the three entry points above with fold = true
+int pack_folded(const float* params, void* packed_s16, hipStream_t s);
+int forward_folded(const void* packed_s16, const float* bias_slots, const float* x, const float* rays, const float* z, int64_t M,
+                   int n, int freq_mode, float* out, void* acts, int64_t astride16, int persistent_wgs, hipStream_t s);
+int backward_chain_folded(const void* packed_s16, const void* acts, const float* d_raw, int64_t M, void* dz, int64_t astride16,
+                          int64_t zstride16, int persistent_wgs, hipStream_t s);
 // the weight-gradient kernel proper (job table, split and partial slots prepared by mlp.hip's launch_dw)
 int launch_dw_kernel(const DwArgs& d, int workgroups, bool split_bf16, hipStream_t s);     // split_bf16: hi + lo blocks; else the bf16 stores
 extern int g_dw_variant;      // A/B knob ("dw22_variant"): 1 = 256 x 256 jobs on the one-wave-per-SIMD kernel (mlp_dww.hip), the others on the 16-wave kernel (default); 0 = every job on the 16-wave kernel

@@ -13,34 +13,18 @@
 // fragment-block stores, ReLU sign-bit words, split-K dW over fragment blocks with the sample axis as the MFMA K axis) with
 // every stream doubled: (hi, lo) weight fragment pairs, hi and lo fragment blocks in the stores.
 //
+// The device code of the forward and the chain is mlp_s16_view.h, shared with mlp_s16f.hip, which instantiates the FOLDED form of the
+// same kernels ("train_fold": mlp_s16.h); this unit holds the unfolded instantiations, the unfolded pack, the weight-gradient kernel
+// and the host entry points of both forms.
+//
 // Forward / chain: one wave = 32 samples, ONE wave per SIMD (4 waves per workgroup): input and output layer, hi and lo, are
 // 256 activation registers.  dW: 16 waves per workgroup as in mlp.hip, LDS stages of 16 samples (half a tile) so that four
 // stages of hi + lo operands fit the CU's 160 KiB.
-#include "mlp_s16_dev.h"
+#include "mlp_s16_view.h"
 #include "mlp_pack.h"
-#include "mlp_s16.h"
-
-// 1: the training forward re-reads its own stored encodings before pos5 / dir0 (48 registers less to carry through pos1..4; a
-// compiler-counted global load, i.e. a vmcnt(0) that drains the ring's DMAs and the pending stores); 0: keeps them (the 512-register
-// file of a one-wave-per-SIMD kernel has the room: they live in AGPRs)
-#ifndef NERF_S16_RELOAD_PE
-#define NERF_S16_RELOAD_PE 0
-#endif
 
 namespace nerf {
 namespace s16 {
-
-constexpr int F_CHUNKS = F_FRAGS / RING_CHUNK;          // 74
-constexpr int B_CHUNKS = B_PADDED / RING_CHUNK;         // 69
-static_assert(F_CHUNKS * RING_CHUNK == F_FRAGS && B_CHUNKS * RING_CHUNK == B_PADDED, "whole ring chunks");
-static_assert(F_FRAGS == 2 * L::F_TOTAL && B_FRAGS == 2 * L::B_TOTAL, "pair streams");
-static_assert(A_LO == L::A_MASK && A_MASK == 2 * L::A_MASK && A_SLOTS == A_MASK + 9, "activation slots");
-static_assert(Z_LO == L::Z_SLOTS && Z_SLOTS == 2 * L::Z_SLOTS, "dZ slots");
-constexpr int NW = 4;                                    // waves per workgroup of the forward / chain kernels
-
-typedef RingW<F_CHUNKS, F_FRAGS, 4, NW, RING_CHUNK, RING_STAGES, true> FwdRing;      // DMA runs of four (mlp_ring.h)
-typedef RingW<B_CHUNKS, B_FRAGS, 4, NW, RING_CHUNK, RING_STAGES, true> BwdRing;
-
 
 // ------------------------------------------------------------------------------------------
 // packing: fp32 master parameters -> (hi, lo) bf16 fragment pairs in the 32x32x16 stream orders of mlp_index.h (mlp_pack.h)
@@ -48,219 +32,6 @@ typedef RingW<B_CHUNKS, B_FRAGS, 4, NW, RING_CHUNK, RING_STAGES, true> BwdRing;
 // the transposed pair stream ends 1104 pairs in (4 of them zero padding), not at the bf16 stream's 1120
 struct ViewPairPack : ViewPack { static constexpr int B_PADDED = s16::B_PADDED / 2; };
 static_assert(ViewPairPack::B_PADDED >= L::B_TOTAL, "the padded stream holds every transposed fragment");
-
-// positional encodings (within 6e-7 of the float64 sine before the split), straight into (hi, lo) B fragments: mlp_input.h (here: SinCodyWaite, SplitBf16)
-
-// All 12 layers for the wave's 32 samples (sample tile `tile0`).  Waves past the end compute on clamped inputs, store into
-// the padding tiles of the workspace and write no output, so every wave runs the same instruction stream (the ring needs it).
-// MODE 0: embedded rows;  MODE 1: rays + z with fused positional encodings
-template <int MODE, class WS>
-__device__ __forceinline__ void fwd_tiles(const FwdArgs& a, WS& ws, int64_t tile0, int64_t ntiles, int lane, PassQueue& pq) {
-  const int r = lane & 31, h = lane >> 5;
-  bf16x8 peh[4], pel[4], dph[2], dpl[2];
-  pq.ask(ws.wv, lane);                    // dynamic pass queue (mlp_ring.h): before this pass's input loads
-  {
-    const int64_t tile = tile0 < ntiles ? tile0 : ntiles - 1;
-    const int64_t m = clamp_sample(tile * 32 + r, a.M);
-    if (MODE == 0) {
-      const float* row = a.x + m * 90;
-#pragma unroll
-      for (int ks = 0; ks < 4; ++ks) row_pairs<SplitBf16>(row, ks, h, 63, peh[ks], pel[ks]);
-#pragma unroll
-      for (int ks = 0; ks < 2; ++ks) row_pairs<SplitBf16>(row + 63, ks, h, 27, dph[ks], dpl[ks]);
-    } else {
-      const Sample sm = load_sample(a.rays, a.z, m, a.n);
-      encode_pairs<SinCodyWaite, SplitBf16, 0, 63, 10>(sm.p, a.fr.pos, h, peh[0], pel[0]); encode_pairs<SinCodyWaite, SplitBf16, 1, 63, 10>(sm.p, a.fr.pos, h, peh[1], pel[1]);
-      encode_pairs<SinCodyWaite, SplitBf16, 2, 63, 10>(sm.p, a.fr.pos, h, peh[2], pel[2]); encode_pairs<SinCodyWaite, SplitBf16, 3, 63, 10>(sm.p, a.fr.pos, h, peh[3], pel[3]);
-      encode_pairs<SinCodyWaite, SplitBf16, 0, 27, 4>(sm.d, a.fr.dir, h, dph[0], dpl[0]); encode_pairs<SinCodyWaite, SplitBf16, 1, 27, 4>(sm.d, a.fr.dir, h, dph[1], dpl[1]);
-    }
-  }
-  pq.publish(ws.wv);
-  store_frags<4>(a.acts, tile0, a.astride, L::A_PE, peh, r, h); store_frags<4>(a.acts, tile0, a.astride, A_LO + L::A_PE, pel, r, h);
-  store_frags<2>(a.acts, tile0, a.astride, L::A_DPE, dph, r, h); store_frags<2>(a.acts, tile0, a.astride, A_LO + L::A_DPE, dpl, r, h);
-
-  bf16x8 hah[16], hal[16], hbh[16], hbl[16];
-  u32x4 mk;
-#define SINK(slot0) PairSink{a.acts, tile0, a.astride, slot0, A_LO, r, h}
-#define MASK_BEGIN() mk = u32x4{0u, 0u, 0u, 0u}
-#define MASK_STORE(layer) *reinterpret_cast<u32x4*>(frag_ptr(a.acts, tile0, a.astride, A_MASK + (layer), r, h)) = mk
-  MASK_BEGIN();
-  layer_fwd<4, 8, true, true>(ws, L::F_L0, 0, peh, pel, hah, hal, mk, lane, SINK(L::A_H0));
-  MASK_STORE(0);
-  MASK_BEGIN();
-  layer_fwd<16, 8, true, true>(ws, L::F_L1 + 0 * 128, 256, hah, hal, hbh, hbl, mk, lane, SINK(L::A_H0 + 16));
-  MASK_STORE(1);
-  MASK_BEGIN();
-  layer_fwd<16, 8, true, true>(ws, L::F_L1 + 1 * 128, 512, hbh, hbl, hah, hal, mk, lane, SINK(L::A_H0 + 32));
-  MASK_STORE(2);
-  MASK_BEGIN();
-  layer_fwd<16, 8, true, true>(ws, L::F_L1 + 2 * 128, 768, hah, hal, hbh, hbl, mk, lane, SINK(L::A_H0 + 48));
-  MASK_STORE(3);
-  MASK_BEGIN();
-  layer_fwd<16, 8, true, true>(ws, L::F_L1 + 3 * 128, 1024, hbh, hbl, hah, hal, mk, lane, SINK(L::A_H0 + 64));
-  MASK_STORE(4);
-  {                                                           // pos5 on concat[input_pos, h]  (models/NeRF.py:224-225)
-    bf16x8 cth[20], ctl[20];
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-#if NERF_S16_RELOAD_PE                                        // register relief: the encoding was just stored
-      cth[k] = *frag_ptr(a.acts, tile0, a.astride, L::A_PE + k, r, h);
-      ctl[k] = *frag_ptr(a.acts, tile0, a.astride, A_LO + L::A_PE + k, r, h);
-#else
-      cth[k] = peh[k]; ctl[k] = pel[k];
-#endif
-    }
-#pragma unroll
-    for (int k = 0; k < 16; ++k) { cth[4 + k] = hah[k]; ctl[4 + k] = hal[k]; }
-    MASK_BEGIN();
-    layer_fwd<20, 8, true, true>(ws, L::F_L5, 1280, cth, ctl, hbh, hbl, mk, lane, SINK(L::A_H0 + 80));
-    MASK_STORE(5);
-  }
-  MASK_BEGIN();
-  layer_fwd<16, 8, true, true>(ws, L::F_L6, 1536, hbh, hbl, hah, hal, mk, lane, SINK(L::A_H0 + 96));
-  MASK_STORE(6);
-  MASK_BEGIN();
-  layer_fwd<16, 8, true, true>(ws, L::F_L7, 1792, hah, hal, hbh, hbl, mk, lane, SINK(L::A_H0 + 112));
-  MASK_STORE(7);
-  // feature (no activation) and alpha (row 0 of a ninth tile)   models/NeRF.py:229-231
-  layer_fwd<16, 8, false, false>(ws, L::F_FA, L::BI_FEAT, hbh, hbl, hah, hal, mk, lane, SINK(L::A_FEAT));
-  const float alpha = head<16>(ws, L::F_FA + 128, L::BI_ALPHA, hbh, hbl, lane)[0];
-  // view branch: relu(Linear([feature, input_dir]))  then rgb   models/NeRF.py:232-238
-  bf16x8 hdh[8], hdl[8];
-  {
-    bf16x8 cth[18], ctl[18];
-#pragma unroll
-    for (int k = 0; k < 16; ++k) { cth[k] = hah[k]; ctl[k] = hal[k]; }
-#pragma unroll
-    for (int k = 0; k < 2; ++k) {
-#if NERF_S16_RELOAD_PE
-      cth[16 + k] = *frag_ptr(a.acts, tile0, a.astride, L::A_DPE + k, r, h);
-      ctl[16 + k] = *frag_ptr(a.acts, tile0, a.astride, A_LO + L::A_DPE + k, r, h);
-#else
-      cth[16 + k] = dph[k]; ctl[16 + k] = dpl[k];
-#endif
-    }
-    MASK_BEGIN();
-    layer_fwd<18, 4, true, true>(ws, L::F_DIR, L::BI_DIR, cth, ctl, hdh, hdl, mk, lane, SINK(L::A_HD));
-    MASK_STORE(8);
-  }
-  const f32x16 rgb = head<8>(ws, L::F_RGB, L::BI_RGB, hdh, hdl, lane);
-  const int64_t m = tile0 * 32 + r;
-  if (h == 0 && tile0 < ntiles && m < a.M) {
-    float4 o; o.x = rgb[0]; o.y = rgb[1]; o.z = rgb[2]; o.w = alpha;     // [rgb, alpha] raw (:239)
-    *reinterpret_cast<float4*>(a.out + m * 4) = o;
-  }
-#undef SINK
-#undef MASK_BEGIN
-#undef MASK_STORE
-}
-
-template <int MODE>
-__global__ void __launch_bounds__(64 * NW) s16_fwd_kernel(FwdArgs a) {
-  const int lane = threadIdx.x & 63;
-  const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  const int64_t ntiles = (a.M + 31) >> 5, nsuper = (ntiles + NW - 1) / NW;
-  FwdRing ws;
-  ws.wsrc = reinterpret_cast<const char*>(a.wf);
-  ws.lane16 = 16 * lane;
-  ws.lds0 = __builtin_amdgcn_readfirstlane(lds_addr_of(ring_smem));
-  ws.wv = wv;
-  ws.start(lane);
-  ring_load_bias(a.bias, L::BI_TOTAL, FwdRing::BIAS_OFF);
-  __syncthreads();
-  PassQueue pq;                           // dynamic pass queue (mlp_ring.h); a.queue == nullptr: static split
-  pq.init(a.queue, ws.lds0 + FwdRing::BIAS_OFF);
-  for (int64_t sp = blockIdx.x; sp < nsuper;) {
-    int ln = lane;
-    asm volatile("" : "+v"(ln));          // lane-derived values are recomputed per pass, not hoisted and spilled
-    ws.new_pass();
-    fwd_tiles<MODE>(a, ws, sp * NW + wv, ntiles, ln, pq);
-    sp = pq.next(sp);
-  }
-  ws.drain();                             // the ring always runs 3 chunks ahead
-  pq.leave();
-}
-
-
-struct BwdArgs {
-  unsigned* queue;       // dynamic pass queue slot of this launch, or nullptr (static split): mlp_ring.h
-  const bf16x8* wb;
-  const void* acts;
-  const float* d_raw;    // [M,4]
-  int64_t M;
-  void* dz;
-  int64_t astride, zstride;
-};
-
-template <class WS>
-__device__ __forceinline__ void bwd_tiles(const BwdArgs& a, WS& ws, int64_t tile0, int64_t ntiles, int lane, PassQueue& pq) {
-  const int r = lane & 31, h = lane >> 5;
-  const bool live = tile0 < ntiles;
-  pq.ask(ws.wv, lane);                    // dynamic pass queue (mlp_ring.h): before this pass's input loads
-  const int64_t tile = live ? tile0 : ntiles - 1;
-  bf16x8 zrh[1], zrl[1], zah[1], zal[1];
-  {
-    const int64_t m = tile * 32 + r;
-    float4 g = make_float4(0.f, 0.f, 0.f, 0.f);
-    if (live && m < a.M && h == 0) g = *reinterpret_cast<const float4*>(a.d_raw + m * 4);
-    float vr[8] = {g.x, g.y, g.z, 0.f, 0.f, 0.f, 0.f, 0.f}, va[8] = {g.w, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-    split_slots<8>(vr, zrh, zrl);                         // rows 0..2 (h == 0)
-    split_slots<8>(va, zah, zal);                         // row 0
-  }
-  pq.publish(ws.wv);
-  // every ReLU mask of the pass is fetched here, so the chain itself issues no loads the compiler must wait for
-  u32x4 mk[9];
-#pragma unroll
-  for (int l = 0; l < 9; ++l)
-    mk[l] = *reinterpret_cast<const u32x4*>(frag_ptr(const_cast<void*>(a.acts), tile, a.astride, A_MASK + l, r, h));
-#define ZSINK(slot0) PairSink{a.dz, tile0, a.zstride, slot0, Z_LO, r, h}
-  ZSINK(L::Z_RGB).put(0, zrh[0], zrl[0]);
-  ZSINK(L::Z_A).put(0, zah[0], zal[0]);
-  bf16x8 zdh[8], zdl[8];
-  layer_bwd<1, 4, true>(ws, L::B_RGB, zrh, zrl, zdh, zdl, mk[8], lane, ZSINK(L::Z_D));
-  bf16x8 zxh[16], zxl[16], zyh[16], zyl[16];
-  layer_bwd<8, 8, false>(ws, L::B_DIR, zdh, zdl, zxh, zxl, mk[8], lane, ZSINK(L::Z_F));          // d feature
-  {
-    bf16x8 cth[17], ctl[17];
-#pragma unroll
-    for (int k = 0; k < 16; ++k) { cth[k] = zxh[k]; ctl[k] = zxl[k]; }
-    cth[16] = zah[0]; ctl[16] = zal[0];
-    layer_bwd<17, 8, true>(ws, L::B_FA, cth, ctl, zyh, zyl, mk[7], lane, ZSINK(L::Z_L0 + 112));   // dZ7
-  }
-  layer_bwd<16, 8, true>(ws, L::B_L7, zyh, zyl, zxh, zxl, mk[6], lane, ZSINK(L::Z_L0 + 96));     // dZ6
-  layer_bwd<16, 8, true>(ws, L::B_L6, zxh, zxl, zyh, zyl, mk[5], lane, ZSINK(L::Z_L0 + 80));     // dZ5
-  layer_bwd<16, 8, true>(ws, L::B_L5, zyh, zyl, zxh, zxl, mk[4], lane, ZSINK(L::Z_L0 + 64));     // dZ4
-  layer_bwd<16, 8, true>(ws, L::B_L4 + 0 * 128, zxh, zxl, zyh, zyl, mk[3], lane, ZSINK(L::Z_L0 + 48));   // dZ3
-  layer_bwd<16, 8, true>(ws, L::B_L4 + 1 * 128, zyh, zyl, zxh, zxl, mk[2], lane, ZSINK(L::Z_L0 + 32));   // dZ2
-  layer_bwd<16, 8, true>(ws, L::B_L4 + 2 * 128, zxh, zxl, zyh, zyl, mk[1], lane, ZSINK(L::Z_L0 + 16));   // dZ1
-  layer_bwd<16, 8, true>(ws, L::B_L4 + 3 * 128, zyh, zyl, zxh, zxl, mk[0], lane, ZSINK(L::Z_L0 + 0));    // dZ0
-#undef ZSINK
-}
-
-__global__ void __launch_bounds__(64 * NW) s16_bwd_kernel(BwdArgs a) {
-  const int lane = threadIdx.x & 63;
-  const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  const int64_t ntiles = (a.M + 31) >> 5, nsuper = (ntiles + NW - 1) / NW;
-  BwdRing ws;
-  ws.wsrc = reinterpret_cast<const char*>(a.wb);
-  ws.lane16 = 16 * lane;
-  ws.lds0 = __builtin_amdgcn_readfirstlane(lds_addr_of(ring_smem));
-  ws.wv = wv;
-  ws.start(lane);
-  PassQueue pq;                           // dynamic pass queue (mlp_ring.h); a.queue == nullptr: static split
-  pq.init(a.queue, ws.lds0 + BwdRing::BIAS_OFF);
-  for (int64_t sp = blockIdx.x; sp < nsuper;) {
-    int ln = lane;
-    asm volatile("" : "+v"(ln));
-    ws.new_pass();
-    bwd_tiles(a, ws, sp * NW + wv, ntiles, ln, pq);
-    // the pass ends inside the last chunk (2200 is not a multiple of 32): the next pass starts at a chunk boundary again
-    // because fragment indices restart at 0
-    sp = pq.next(sp);
-  }
-  ws.drain();
-  pq.leave();
-}
 
 // ------------------------------------------------------------------------------------------
 // dW: split-K GEMMs  dW[n][k] = sum_m dZ[n][m] H[k][m]  over hi / lo fragment blocks, samples = MFMA K
@@ -647,14 +418,17 @@ __global__ void __launch_bounds__(64 * DW_WAVES) s16_dw_kernel(DwArgs a) {
 // host side
 // ------------------------------------------------------------------------------------------
 
-int pack(const float* params, void* packed_s16, hipStream_t s) {
+int pack(const float* params, void* packed_s16, bool fold, hipStream_t s) {
   bf16x8* wf = static_cast<bf16x8*>(packed_s16);
+  if (fold) return pack_folded(params, packed_s16, s);       // mlp_s16f.hip
   return launch<pack_streams_kernel<ViewPairPack, SplitBf16, false>>("nerf_mlp_pack (split-bf16 image)", dim3(pack_blocks<ViewPairPack, false>()),
                                                                      dim3(256), 0, s, params, wf, wf + (size_t)F_FRAGS * 64, nullptr, 0);
 }
 
 int forward(const void* packed_s16, const float* bias_slots, const float* x, const float* rays, const float* z, int64_t M,
-            int n, int freq_mode, float* out, void* acts, int64_t astride16, int persistent_wgs, hipStream_t s) {
+            int n, int freq_mode, float* out, void* acts, int64_t astride16, int persistent_wgs, bool fold, hipStream_t s) {
+  if (fold)                                                  // the folded kernels are a unit of their own: mlp_s16f.hip
+    return forward_folded(packed_s16, bias_slots, x, rays, z, M, n, freq_mode, out, acts, astride16, persistent_wgs, s);
   FwdArgs a;
   a.queue = passq_slot();
   a.wf = reinterpret_cast<const bf16x8*>(packed_s16);
@@ -663,20 +437,21 @@ int forward(const void* packed_s16, const float* bias_slots, const float* x, con
   fill_freqs(a.fr.pos, a.fr.dir, freq_mode);
   const int64_t nsuper = ((M + 31) / 32 + NW - 1) / NW;
   return with_bool(x != nullptr, [&](auto rows) {          // MODE 0: embedded rows, 1: rays + depths
-    return launch<s16_fwd_kernel<decltype(rows)::value ? 0 : 1>>("mlp training forward (split bf16)", dim3(persistent_grid(nsuper, persistent_wgs)),
-                                                                  dim3(64 * NW), FwdRing::LDS_BYTES, s, a);
+    return launch<s16_fwd_kernel<decltype(rows)::value ? 0 : 1, false>>("mlp training forward (split bf16)", dim3(persistent_grid(nsuper, persistent_wgs)),
+                                                                         dim3(64 * NW), FwdRing::LDS_BYTES, s, a);
   });
 }
 
 int backward_chain(const void* packed_s16, const void* acts, const float* d_raw, int64_t M, void* dz, int64_t astride16,
-                   int64_t zstride16, int persistent_wgs, hipStream_t s) {
+                   int64_t zstride16, int persistent_wgs, bool fold, hipStream_t s) {
+  if (fold) return backward_chain_folded(packed_s16, acts, d_raw, M, dz, astride16, zstride16, persistent_wgs, s);
   BwdArgs b;
   b.queue = passq_slot();
   b.wb = reinterpret_cast<const bf16x8*>(static_cast<const char*>(packed_s16) + (size_t)F_FRAGS * 1024);
   b.acts = acts; b.d_raw = d_raw; b.M = M; b.dz = dz; b.astride = astride16; b.zstride = zstride16;
   const int64_t nsuper = ((M + 31) / 32 + NW - 1) / NW;
-  return launch<s16_bwd_kernel>("mlp backward chain (split bf16)", dim3(persistent_grid(nsuper, persistent_wgs)), dim3(64 * NW),
-                                BwdRing::LDS_BYTES, s, b);
+  return launch<s16_bwd_kernel<false>>("mlp backward chain (split bf16)", dim3(persistent_grid(nsuper, persistent_wgs)), dim3(64 * NW),
+                                       BwdRing::LDS_BYTES, s, b);
 }
 
 int g_dw_variant = 1;          // nerf_set_option("dw22_variant"): 1 (default) 256 x 256 jobs on mlp_dww.hip's kernel, the others here; 0 every job here

@@ -58,6 +58,9 @@ class Trainer:
         self.coarse = mk(seed)                                  # identical initial weights on every rank
         self.fine = mk(seed + 1) if N_importance > 0 else None
         self.coarse.name = "coarse"                             # Adam state keys when the state is not shared
+        for net in (self.coarse, self.fine):                    # precision 22: the folded training form (models/NeRF.py, csrc/mlp_s16.h);
+            if net is not None:                                 # ignored by the other precisions
+                net.train_fold = True
         if self.fine is not None:
             self.fine.name = "fine"
         self.opt = Adam(lrate, betas=(0.9, 0.999), shared_state=ref_quirks)

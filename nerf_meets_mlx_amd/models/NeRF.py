@@ -7,6 +7,7 @@ optimiser step.  `forward(x)` is the reference's `NeRF.forward` on embedded rows
 path uses `query(rays, z)` which fuses pts = o + z d, both positional encodings and all 12
 layers into one launch.
 """
+import contextlib
 import ctypes as C
 import math
 from typing import Dict, List, Optional
@@ -44,7 +45,12 @@ class NeRF:
       32 = float32 operands on the fp32 MFMA (csrc/mlp32.hip; 8 x 256 view and image models);
       16 = bf16 MFMA operands with fp32 accumulate: a declared REDUCED-precision mode (opt-in; ~1e-2 of the output scale).
     It is part of the model (`nerf_mlp_arch.precision`): weight image, workspaces and every launch of this object use it;
-    models of different precision can be used side by side."""
+    models of different precision can be used side by side.
+    train_fold (attribute, default False): ask for the FOLDED split-bf16 training image and kernels (csrc/mlp_s16.h: the feature
+    layer folded into dir0 in the training forward and the dZ chain; `nerf_set_option("train_fold")`).  It takes effect for the
+    8 x 256 view model at precision 22 while the weight gradients run the factored job list ("dw_factor" 1 with the two-launch form and
+    no job mask), and is ignored otherwise.  The model remembers the form its image was packed in, re-packs when the effective form
+    changes, and sets the library's process-wide option around its own pack, train-mode forward and backward calls only."""
 
     def __init__(self, n_layers=8, width_layers=256, channel_input=3, channel_input_views=3, channel_output=4,
                  list_skip_connection_layers=[4], is_use_view_directions=False, device="cuda", seed: Optional[int] = None,
@@ -81,6 +87,11 @@ class NeRF:
         self._gen = 0                       # generation of the activation workspace (one per train-mode forward)
         self._acts_gen = -1
         self._acts_M = -1
+        self.train_fold = False
+        self._packed_form = 0               # 1: the packed image holds the folded training streams
+        self._acts_form = 0                 # ... and so do the stored activations of the last train-mode forward
+        self._can_fold = (precision == 22 and bool(is_use_view_directions) and n_layers == 8 and width_layers == 256
+                          and channel_input == 63 and channel_input_views == 27 and self.list_skip_connection_layers == [4])
 
     # ---- parameter views (the reference's tree: list_linears_pos / list_linears_dir / ... ) ----
     def parameters(self) -> Dict[str, object]:
@@ -114,6 +125,33 @@ class NeRF:
     def activation_generation(self) -> int:
         return self._acts_gen
 
+    # ---- folded training form (csrc/mlp_s16.h) ---------------------------------------------------
+    def train_form(self) -> int:
+        """1 when this model's training kernels run the folded form now (see the class docstring), else 0."""
+        if not (self.train_fold and self._can_fold):
+            return 0
+        lib = N.lib()
+        return int(lib.nerf_get_option(b"train_fold") in (0, 1) and lib.nerf_get_option(b"dw_factor") == 1
+                   and lib.nerf_get_option(b"dw22_variant") != 0 and lib.nerf_get_option(b"dw_job_mask") == 0)
+
+    @contextlib.contextmanager
+    def _form(self, form: int):
+        """The library's process-wide "train_fold" option set to `form` for the calls inside, and back to what it was (0 unless
+        the caller set it) behind them."""
+        if not self._can_fold:
+            yield
+            return
+        lib = N.lib()
+        before = lib.nerf_get_option(b"train_fold")
+        if before not in (0, 1):            # a library from before the option (NERF_HIP_LIB): it has the unfolded form only
+            yield
+            return
+        N.check(lib.nerf_set_option(b"train_fold", int(form)))
+        try:
+            yield
+        finally:
+            lib.nerf_set_option(b"train_fold", before)
+
     # ---- packed bf16 fragment image ------------------------------------------------------------
     def packed(self) -> torch.Tensor:
         lib = N.lib()
@@ -126,10 +164,13 @@ class NeRF:
             self._packed = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
         # re-pack when the master parameters changed: kernels that write through raw pointers (Adam) say so with
         # mark_updated(); torch in-place ops on `params` or on the views of parameters() bump the version counter
-        if self._dirty or self.params._version != self._packed_version:
-            N.check(lib.nerf_mlp_pack(C.byref(self.arch), N.ptr(self.params), N.ptr(self._packed), N.stream()))
+        form = self.train_form()
+        if self._dirty or self.params._version != self._packed_version or form != self._packed_form:
+            with self._form(form):
+                N.check(lib.nerf_mlp_pack(C.byref(self.arch), N.ptr(self.params), N.ptr(self._packed), N.stream()))
             self._dirty = False
             self._packed_version = self.params._version
+            self._packed_form = form
         return self._packed
 
     def _begin_train_pass(self, M: int) -> torch.Tensor:
@@ -157,8 +198,12 @@ class NeRF:
         acts = None
         if train:
             acts = self._begin_train_pass(M)
-        N.check(N.lib().nerf_mlp_forward_train(C.byref(self.arch), N.ptr(self.packed()), N.ptr(x), M, N.ptr(out),
-                                               N.ptr(acts), N.stream()))
+        packed = self.packed()
+        with self._form(self._packed_form):
+            N.check(N.lib().nerf_mlp_forward_train(C.byref(self.arch), N.ptr(packed), N.ptr(x), M, N.ptr(out),
+                                                   N.ptr(acts), N.stream()))
+        if train:
+            self._acts_form = self._packed_form
         return out
 
     __call__ = forward
@@ -170,8 +215,12 @@ class NeRF:
         acts = None
         if train:
             acts = self._begin_train_pass(B * n)
-        N.check(N.lib().nerf_query_fused(C.byref(self.arch), N.ptr(self.packed()), N.ptr(rays), N.ptr(z), B, n,
-                                         0 if ref_quirks else 1, N.ptr(raw), N.ptr(acts), N.stream()))
+        packed = self.packed()
+        with self._form(self._packed_form):
+            N.check(N.lib().nerf_query_fused(C.byref(self.arch), N.ptr(packed), N.ptr(rays), N.ptr(z), B, n,
+                                             0 if ref_quirks else 1, N.ptr(raw), N.ptr(acts), N.stream()))
+        if train:
+            self._acts_form = self._packed_form
         return raw
 
     def backward(self, d_raw: torch.Tensor, need_input_grad: bool = False, generation: Optional[int] = None):
@@ -189,13 +238,18 @@ class NeRF:
                                "backward before the next train-mode forward, or use a second model object)")
         assert M == self._acts_M, "backward() needs a matching query/forward(train=True) first"
         dz = self._workspace("dz", N.lib().nerf_mlp_dz_bytes(C.byref(self.arch), M))
+        packed = self.packed()
+        if self._packed_form != getattr(self, "_acts_form", 0):
+            raise RuntimeError("NeRF.backward: the training form (train_fold / the options it depends on) changed between the "
+                               "train-mode forward and backward; run the forward again")
         if need_input_grad:
             d_x = torch.empty(M, self.channel_input_pos, dtype=torch.float32, device=d_raw.device)
             N.check(N.lib().nerf_mlp_backward_inputs(C.byref(self.arch), N.ptr(self.packed()), N.ptr(self._ws["acts"]),
                                                      N.ptr(d_raw), M, N.ptr(dz), N.ptr(self.grads), N.ptr(d_x), N.stream()))
             return self.grads, d_x
-        N.check(N.lib().nerf_mlp_backward(C.byref(self.arch), N.ptr(self.packed()), N.ptr(self._ws["acts"]),
-                                          N.ptr(d_raw), M, N.ptr(dz), N.ptr(self.grads), N.stream()))
+        with self._form(self._packed_form):
+            N.check(N.lib().nerf_mlp_backward(C.byref(self.arch), N.ptr(packed), N.ptr(self._ws["acts"]),
+                                              N.ptr(d_raw), M, N.ptr(dz), N.ptr(self.grads), N.stream()))
         return self.grads
 
 
@@ -203,6 +257,9 @@ def debug_layer(model: NeRF, kind: str, layer: int) -> torch.Tensor:
     """Test hook (`nerf_mlp_debug_read`): the stored activation ("acts") or dZ ("dz") of `layer` from the model's last
     train-mode forward / backward as a row-major [M, width] float32 tensor."""
     k = {"acts": 0, "dz": 1}[kind]
+    if layer == 8 and getattr(model, "_acts_form", 0):
+        raise ValueError("debug_layer: a folded model (train_fold) neither computes nor stores the feature layer's activations and "
+                         "dZ (layer 8): its dir0 reads h7 through W' = W_D[:, :256] W_F")
     w = N.lib().nerf_mlp_debug_width(C.byref(model.arch), k, layer)
     if w < 0:
         raise ValueError("debug_layer: no such (kind, layer) in this model's training stores (include/nerf_hip.h, nerf_mlp_debug_read)")

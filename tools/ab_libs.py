@@ -25,6 +25,13 @@
         workgroups: digested only where there is one (B <= 4, count <= 256).  Exit 1 unless all digests are the same.  A float
         output is printed as bits/values, the second digest taken with every NaN replaced by 0: where only that one is the same
         in every library, the mismatch is reported as one of NaN sign / payload bits (it still counts).
+    python tools/ab_libs.py --train-fold tools/diag/libnerf_parent.so default
+        the folded split-bf16 training form (NeRF.train_fold, csrc/mlp_s16.h) of the view model at precision 22: training forward and
+        backward at M = 65 and 2049 embedded rows and at 64 x 3 rays + depths, sha256 per array -- alpha, colours, every stored
+        activation and dZ layer, every gradient tensor (dir0's weight in its feature and direction columns).  Three children: the first
+        library (the parent commit's) and the second with the option off must agree in every digest; the second with the option on
+        must differ from it in exactly the arrays downstream of dir0' (colours, dir0, dZ7..0, the weight gradients that read them, and
+        dW_F, db_F, dW_D[:, :256], which the post step now forms from the fp32 masters) and in no other.  Exit 1 otherwise.
 Every child runs under a time limit, and after a child that failed or ran out of time no further child is started."""
 import argparse, json, os, subprocess, sys, tempfile
 CHILD = r'''
@@ -130,6 +137,49 @@ for n in (3, 64):
         N.check(lib.nerf_set_option(b"ngp_ray_major", 1))
 print(json.dumps(res))
 '''
+CHILD_FOLD = r'''
+import sys, json, hashlib, torch
+sys.path.insert(0, ".")
+from nerf_meets_mlx_amd.models.NeRF import NeRF, debug_layer, layer_shapes
+from oracle import nerf_oracle as O
+fold, dev, res = bool(int(sys.argv[1])), "cuda", {}
+sha = lambda t: hashlib.sha256(t.contiguous().cpu().numpy().tobytes()).hexdigest()[:16]
+def digests(m, raw, d_raw):
+    grads = m.backward(d_raw)
+    d = {"alpha": sha(raw.reshape(-1, 4)[:, 3]), "colours": sha(raw.reshape(-1, 4)[:, :3])}
+    for l in [0, 1, 2, 3, 4, 5, 6, 7, 9, 10, 11] + ([] if m._acts_form else [8]):
+        d[f"acts{l}"], d[f"dz{l}"] = sha(debug_layer(m, "acts", l)), sha(debug_layer(m, "dz", l))
+    off = 0
+    for name, o, i in layer_shapes(8, 256, 63, 27, (4,), True, 4):
+        w = grads[off:off + o * i].view(o, i)
+        if name == "dir0": d["dW_dir0[:, :256]"], d["dW_dir0[:, 256:]"] = sha(w[:, :256]), sha(w[:, 256:])
+        else: d[f"dW_{name}"] = sha(w)
+        d[f"db_{name}"] = sha(grads[off + o * i:off + o * i + o])
+        off += o * i + o
+    assert bool(torch.isfinite(grads).all()) and float(grads.abs().max()) > 0
+    return d
+for M in (65, 2049):
+    g = torch.Generator().manual_seed(22000 + M)
+    m = NeRF(channel_input=63, channel_input_views=27, is_use_view_directions=True, device=dev, seed=4, precision=22)
+    m.load_flat(torch.randn(m.n_params, generator=g) * 0.05)
+    m.train_fold = fold
+    x, d_raw = (torch.randn(M, 90, generator=g) * 0.5).to(dev), torch.randn(M, 4, generator=g).to(dev)
+    res[f"rows M={M}"] = digests(m, m.forward(x, train=True), d_raw)
+    assert m._acts_form == int(fold)
+g = torch.Generator().manual_seed(7)
+m = NeRF(channel_input=63, channel_input_views=27, is_use_view_directions=True, device=dev, seed=4, precision=22)
+m.train_fold = fold
+o = torch.nn.functional.normalize(torch.randn(64, 3, generator=g), dim=-1) * 4.0
+rays = O.pack_rays(o, -o / 4.0 + 0.25 * torch.randn(64, 3, generator=g), 2.0, 6.0).to(dev)
+z = (torch.sort(torch.rand(64, 3, generator=g), -1).values * 4 + 2).to(dev)
+res["query B=64 n=3"] = digests(m, m.query(rays, z, train=True), torch.randn(192, 4, generator=g).to(dev))
+torch.cuda.synchronize()
+print(json.dumps(res))
+'''
+# --train-fold: the arrays the folded form may (and must) change; every other digest stays
+FOLD_MOVES = {"colours", "acts9", "dW_feature", "db_feature", "dW_dir0[:, :256]", "dW_rgb"} | {f"dz{l}" for l in range(8)} \
+             | {f"dW_pos{l}" for l in range(8)} | {f"db_pos{l}" for l in range(8)}
+FOLD_GONE = {"acts8", "dz8"}
 CHILD_VOLUMES = r'''
 import sys, json, hashlib, numpy as np, torch
 sys.path.insert(0, ".")
@@ -324,9 +374,39 @@ ap = argparse.ArgumentParser(); ap.add_argument("libs", nargs="+"); ap.add_argum
 ap.add_argument("--models", action="store_true", help="digests of every MLP model instead of the render-chunk timing")
 ap.add_argument("--volumes", action="store_true", help="digests of every volume entry (mesh, components, opening, TSDF, simplifier)")
 ap.add_argument("--rays", action="store_true", help="digests of the ray, sampling, compositing, Adam and closed-form encoder entries")
+ap.add_argument("--train-fold", action="store_true", help="digests of the view model's precision-22 training with NeRF.train_fold off and on (two libraries: parent, new)")
 ap.add_argument("--timeout", type=float, default=300.0, help="seconds per child process")
 ap.add_argument("--fold-differs", action="store_true", help="the builds differ in NERF_F22_FOLD: colour differences are reported, not failed")
 a = ap.parse_args()
+if a.train_fold:
+    if len(a.libs) != 2: sys.exit("--train-fold: two libraries (the parent commit's, the new one)")
+    runs = {}
+    for tag, l, v in (("parent", a.libs[0], 0), ("new, train_fold 0", a.libs[1], 0), ("new, train_fold 1", a.libs[1], 1)):
+        env = dict(os.environ)
+        if l != "default": env["NERF_HIP_LIB"] = os.path.abspath(l)
+        else: env.pop("NERF_HIP_LIB", None)
+        try:
+            out = subprocess.run([sys.executable, "-c", CHILD_FOLD, str(v)], capture_output=True, text=True, env=env, timeout=a.timeout)
+        except subprocess.TimeoutExpired:
+            sys.exit(f"{tag}: child ran past {a.timeout:.0f} s and was killed; no further child is started")
+        line = [x for x in out.stdout.splitlines() if x.startswith("{")]
+        if out.returncode != 0 or not line:
+            sys.exit(f"{tag}: child FAILED (exit {out.returncode}); no further child is started\n{out.stderr[-2000:]}")
+        runs[tag] = json.loads(line[-1])
+    bad = 0
+    for case, ref in runs["parent"].items():
+        off, on = runs["new, train_fold 0"][case], runs["new, train_fold 1"][case]
+        differs0 = sorted(k for k in ref if off.get(k) != ref[k]) + sorted(k for k in off if k not in ref)
+        moved = {k for k in ref if k not in FOLD_GONE and on.get(k) != ref[k]}
+        unexpected, unmoved = sorted(moved - FOLD_MOVES), sorted(FOLD_MOVES - moved)
+        missing = sorted(k for k in FOLD_GONE if k in on)
+        bad += bool(differs0) + bool(unexpected) + bool(unmoved) + bool(missing)
+        print(f"{case}: {len(ref)} arrays; option off against the parent: " + ("all digests equal" if not differs0 else "DIFFERS in " + ", ".join(differs0))
+              + f"; option on: {len(moved)} arrays move" + ("" if not unexpected else "; UNEXPECTED: " + ", ".join(unexpected))
+              + ("" if not unmoved else "; EXPECTED TO MOVE BUT EQUAL: " + ", ".join(unmoved)) + ("" if not missing else "; STILL READABLE: " + ", ".join(missing)))
+        print("    " + " ".join(f"{k}={ref[k]}|{on.get(k, '-')}" for k in ref))
+    print(f"{len(runs['parent'])} cases: {bad} failing")
+    sys.exit(1 if bad else 0)
 digests_of = CHILD_MODELS if a.models else CHILD_VOLUMES if a.volumes else CHILD_RAYS if a.rays else None
 rounds = a.rounds if a.rounds is not None else (1 if digests_of else 3)
 acc = {l: [] for l in a.libs}

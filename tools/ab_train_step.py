@@ -1,6 +1,8 @@
 """A/B of a nerf_set_option setting in the bench's own step (train N_rand 4096 rays + render one 32 768-ray chunk, precision 22 by
 default): the settings alternate in blocks of `--steps` steps on ONE trainer, so that both see the same clocks / temperature; prints
-the training and the render phase per block (HIP events).   python tools/ab_train_step.py dw22_variant 0 1 [--precision 16]"""
+the training and the render phase per block (HIP events).   python tools/ab_train_step.py dw22_variant 0 1 [--precision 16]
+The key "train_fold" is a setting of the MODELS (NeRF.train_fold: the folded split-bf16 training form, csrc/mlp_s16.h), not of the
+process: it is set on the trainer's two networks, which re-pack when it changes.   python tools/ab_train_step.py train_fold 0 1 --rounds 5"""
 import argparse, sys, numpy as np, torch
 sys.path.insert(0, ".")
 from nerf_meets_mlx_amd import _native, sampling
@@ -37,7 +39,10 @@ block(5)
 res = {v: [] for v in a.values}
 for r in range(a.rounds):
     for v in a.values:
-        _native.check(_native.lib().nerf_set_option(a.key.encode(), v))
+        if a.key == "train_fold":
+            tr.coarse.train_fold = tr.fine.train_fold = bool(v)
+        else:
+            _native.check(_native.lib().nerf_set_option(a.key.encode(), v))
         block(2)
         res[v].append(block(a.steps))
 for v in a.values:
