@@ -279,8 +279,24 @@ typedef struct nerf_mlp_arch {
                      * activations (nerf_mlp_forward, nerf_query_fused / nerf_render_rays_fused with acts == NULL) run the
                      * split-fp16 kernel of csrc/mlp22.hip: every float32 operand x = hi + lo 2^-11 as two fp16 numbers
                      * (22 significand bits), a product = hi hi + 2^-11 (hi lo + lo hi) on v_mfma_f32_16x16x32_f16 with
-                     * fp32 accumulate, encodings within 6e-7 of the float64 sine; operands must stay inside the fp16 range
-                     * (|activation| < 65504: an overflow becomes inf / NaN in the output, never a silent wrong value).
+                     * fp32 accumulate, encodings within 6e-7 of the float64 sine.  RANGE of the split-fp16 kernel: both
+                     * operand kinds, weights and layer inputs (activations, encodings), live in fp16's exponent range.
+                     *   High end: |w| and |activation| must stay <= 65504.  The conversions overflow (nothing saturates): a
+                     *     larger operand becomes inf, its lo part NaN, and every output that depends on it is inf / NaN --
+                     *     never a silent wrong value.
+                     *   Low end: a weight below 2^-14 goes to the lo part whole and carries 11 significand bits, not 22
+                     *     (absolute error <= 2^-26); an activation below 2^-14 has a subnormal hi part, which the
+                     *     conversion and the matrix unit keep (absolute error <= 2^-36).  Nothing is flushed to zero.
+                     *   Window: the 1e-4 forward tolerance is promised while the hidden layers' activation scales, and with
+                     *     them the weights, stay within a factor 2^7 either way of the unit operating point (weights of
+                     *     order 1 / sqrt(fan-in), activations of order 1): measured <= 7e-6 of the output scale there.  Up
+                     *     to 2^14 either way every output is finite and the error grows to 3.5e-4 (the 11-bit small
+                     *     weights); from 2^15 upwards activations overflow.  tests/test_gpu_range.py holds the kernel to
+                     *     a CPU emulation of these formats over that whole range (DESIGN.md "Operand range").
+                     *   The other MLP paths -- split bf16 (below), bf16 (precision 16) and fp32 (precision 32) -- carry
+                     *     float32's exponent range and are exponent-shift invariant: rescaling the hidden layers by exact
+                     *     powers of two (2^-20 .. 2^20 tested) changes no bit of the forward output, no ReLU decision and,
+                     *     mapped back through the same powers of two, no bit of the gradients.
                      * Everything that keeps activations (training forward with acts != NULL, nerf_mlp_backward) runs the
                      * split-bf16 kernels of csrc/mlp_s16.hip: x = hi + lo as two bf16 numbers (16 significand bits at
                      * float32's exponent range -- gradients do not fit fp16's), a product = hi hi + hi lo + lo hi on
