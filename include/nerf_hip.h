@@ -1030,6 +1030,54 @@ int nerf_bvh_query(const float* points, int64_t n, const float* verts, int64_t V
 int nerf_closest_points(const float* points, int64_t n, const float* verts, int64_t V, const int32_t* faces, int64_t F,
                         const int32_t* face, float* closest, void* stream);
 
+/* ---------------------------------------------------------------- mesh winding number (no reference counterpart)
+ * On which side of a mesh a point lies: the generalized winding number (Jacobson, Kavan and Sorkine-Hornung 2013), summed over
+ * the hierarchy of "mesh BVH" with far subtrees replaced by their dipole (Barill, Dickson, Schmidt, Levin and Jacobson 2018, the
+ * first-order term).  It is defined for open, duplicated and self-intersecting meshes: 1 inside a closed mesh whose faces are
+ * counter-clockwise seen from outside (n = (b - a) x (c - a) points outward, the orientation of "mesh extraction"), 0 outside,
+ * and in between near a hole.  It changes no mesh.  Additive: NERF_ABI_VERSION stays 3.  All arithmetic is IEEE double on the
+ * float32 corners a, b, c and the float32 point q, one rounding per operation (no contraction), in exactly the order written
+ * here; dot(u, v) = (u0 v0 + u1 v1) + u2 v2 and u x v = (u1 v2 - u2 v1, u2 v0 - u0 v2, u0 v1 - u1 v0).  tests/_winding_ref.py follows
+ * it operator for operator; the one operation a device may round differently is atan2.  Validity of a face is that of "mesh
+ * distance".
+ *   exact     x = a - q, y = b - q, z = c - q; lx = sqrt(dot(x, x)), ly, lz alike; det = dot(x, y x z);
+ *             den = (((lx ly) lz + dot(x, y) lz) + dot(y, z) lx) + dot(z, x) ly; Omega = 2 atan2(det, den), and Omega = 0 where
+ *             det == 0: q lies in the plane of the face.  w = (sum of Omega) / (4 pi), 4 pi = 12.566370614359172.  Inside is
+ *             w > 0.5.  The value at a point of the surface itself is this convention and nothing more.
+ *   moments   one record of 12 doubles per node of the hierarchy, heap order: N [0..2], c [3..5], r [6], A [7], S [8..10], 0.  A
+ *             leaf starts from zeros and visits its valid faces in sorted order: n_f = 0.5 ((b - a) x (c - a)), a_f =
+ *             sqrt(dot(n_f, n_f)); N += n_f; S_k += (a_f ((a_k + b_k) + c_k)) / 3; A += a_f.  An internal node is left + right,
+ *             in that order, for N, S and A.  c = S / A, and where A == 0 the midpoint ((double)min + (double)max) 0.5 of the
+ *             node's box; e_k = fmax(c_k - min_k, max_k - c_k), r = sqrt(dot(e, e)): from c to the farthest corner of the node's
+ *             float32 box.  A node without a valid face, and node 0, are twelve zeros.
+ *   query     one lane per point, stackless, no trail word: the lane keeps the node index alone, and the order of the sum is
+ *             fixed.  Start at node 1.  An empty node (min > max) is skipped.  A leaf adds Omega of each of its valid faces in
+ *             sorted order.  An internal node with d = c - q, d2 = dot(d, d) adds the dipole dot(N, d) / (d2 sqrt(d2)) iff
+ *             d2 > (beta beta) (r r), strictly and in double, so that a NaN product never approximates; otherwise the walk
+ *             descends to the left child 2 i.  Next: while the node is odd, halve it; stop at 0 (so also on reaching 1 again);
+ *             otherwise add 1.  beta = +inf is the exact sum in the tree's order.
+ *   result    w [n] float64; visits [n, 2] int32 = (faces evaluated exactly, nodes approximated).  A point with a non-finite
+ *             coordinate: (NaN 0x7FF8000000000000, 0, 0).  A mesh without a valid face: (0, 0, 0).
+ * Calls:
+ *   nerf_winding_build     the moments from a built hierarchy (bvh_workspace: what nerf_bvh_build wrote for this mesh; every face
+ *                          its order names is tested again): one launch for the leaves, one per level upward, the levels of at
+ *                          most 256 nodes in one launch of one workgroup: nerf_bvh_build's count, a function of F alone.  No
+ *                          atomics, no LDS, no host read, no workgroup waits for another.  F = 0: nothing is launched.
+ *   nerf_winding_query     w [n], visits [n, 2] of a chunk of points [n, 3]; beta a double >= 1 or +inf.  Both workspaces are only
+ *                          read, so one build serves any number of chunks, and no result depends on the chunking.  n = 0:
+ *                          nothing is launched.
+ * workspace (build, query): nerf_winding_workspace_bytes(F) bytes (-1 for an F out of range) = 2 P 96, starting on a multiple of
+ * 16 bytes; its content on entry is unspecified.  One writer per output element: bit-reproducible.
+ * Out of range (V, F outside [0, 2^24], n outside [0, 2^30], a beta that is NaN or below 1, a misaligned workspace):
+ * NERF_E_SHAPE; NULL: NERF_E_NULL; all argument checks run before any device work.
+ * Not done: no quadrupole or higher terms (the dipole's error at beta = 2 is about 0.015 of a turn); no narrow band, so every
+ * lattice point of a volume is evaluated; no culling of faces that lie inside the solid; still no ray casting.                    */
+int64_t nerf_winding_workspace_bytes(int64_t F);
+int nerf_winding_build(const float* verts, int64_t V, const int32_t* faces, int64_t F, const void* bvh_workspace, void* workspace,
+                       void* stream);
+int nerf_winding_query(const float* points, int64_t n, const float* verts, int64_t V, const int32_t* faces, int64_t F,
+                       const void* bvh_workspace, const void* workspace, double beta, double* w, int32_t* visits, void* stream);
+
 /* ---------------------------------------------------------------- texture atlas (no reference counterpart)
  * A texture for a finished mesh, baked by one field query per texel: a simplified mesh then carries the field's appearance at
  * a resolution of its own, not one colour per surviving vertex.  A separate step behind the export pipeline; it changes no

@@ -7,7 +7,8 @@ is Instant-NGP's.  One module per stage, and every name of theirs is a name of t
   texture (atlas bake and lookup, mip pyramid) <- raster (rasterize, face_lod, render_mesh, render_mesh_mip) <- project
   (project_texture); texture <- files (PLY, OBJ, PNG); _base <- distance (sample_surface, MeshIndex, mesh_distance).
   distance also holds the second index, MeshBVH (a bounding-volume hierarchy with the grid's answers bit for bit), and
-  closest_points."""
+  closest_points.  distance <- volume <- winding (MeshWinding, winding_number, winding_volume, remesh, signed_distance): the
+  generalized winding number on MeshBVH's tree, the inside test the distance lacks."""
 from ._base import CHUNK, MAX_RES, SIMPLIFY_MAX_ITEMS, Mesh, _box, _check_mesh_tensors, _mark, check_mesh_args
 from .distance import (DISTANCE_INDEXES, DISTANCE_MAX_ENTRIES, DISTANCE_MAX_GRID, DISTANCE_MAX_SAMPLES, DistanceStats, MeshBVH,
                        MeshDistance, MeshIndex, check_distance_args, check_distance_index, closest_points, default_distance_grid,
@@ -25,3 +26,5 @@ from .volume import (EXP, MAX_OPENING_RADIUS, RELU, Components, _check_radius, _
                      _rows_into, check_component_args, check_opening_args, check_volume_options, connected_components, density_volume,
                      erode, extract, filter_components, filter_volume, lattice_rows, marching_cubes, mesh_volume, open_components,
                      reconstruct, vertex_colors)
+from .winding import (WINDING_INSIDE, WINDING_NODE_DOUBLES, MeshWinding, check_winding_args, remesh, signed_distance, winding_number,
+                      winding_volume)

@@ -255,6 +255,25 @@ class Trainer:
         lo, hi = self._mesh_box(aabb)
         return M.mesh_distance(mesh, other, n, lo, hi, seed=seed, tau=tau)
 
+    def remesh(self, mesh, resolution: int = 256, aabb=None, beta: float = 2.0, min_component: int = 0, largest_only: bool = False,
+               opening_radius: int = 0):
+        """A closed engine.mesh.Mesh from one that may be open, duplicated or self-intersecting: marching cubes at 0.5 over the
+        mesh's generalized winding number on the lattice of the export's box (`aabb` as in mesh_distance), the volume filtered
+        as in extract_mesh (engine.mesh.remesh).  No colours: vertex_colors, texture_mesh or
+        project_texture colour the result.  Runs on this rank only: no collective."""
+        from . import mesh as M
+        lo, hi = self._mesh_box(aabb)
+        return M.remesh(mesh, resolution, lo, hi, beta=beta, min_component=min_component, largest_only=largest_only,
+                        opening_radius=opening_radius)
+
+    def signed_distance(self, mesh, points, aabb=None, beta: float = 2.0):
+        """(sd float32 [n], face int32 [n], w float64 [n]) of points [n, 3] against an engine.mesh.Mesh: the distance to the closest
+        face, negative where the winding number w exceeds 0.5 (engine.mesh.signed_distance; `aabb` as in
+        mesh_distance).  Runs on this rank only: no collective."""
+        from . import mesh as M
+        lo, hi = self._mesh_box(aabb)
+        return M.signed_distance(points, mesh, lo, hi, beta=beta)
+
     def texture_mesh(self, mesh, texels: int = 8):
         """engine.mesh.Texture of a finished engine.mesh.Mesh (extract_mesh's, simplified or not): an atlas with a right triangle
         of `texels` texels a leg per face, every texel the field's colour at its point of the face looking along minus the

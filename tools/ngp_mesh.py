@@ -64,6 +64,13 @@ device ms of bake_texture beside the pyramid's reduce and uv per level, the pyra
 level-0 render and of the mip render (its lod and lookup stages among them), the PSNR of both pictures from the held-out pose,
 and the histogram of floor(lod) over the faces the picture sees.  Without --mip nothing changes.
 
+With --winding [--winding-beta B], at --ply-res, one line per mesh (marching cubes, with --tsdf the TSDF mesh, the G = 64 and 128
+simplifications) for the generalized winding number of DESIGN.md section 40: the edges with one incident face and with more than
+two and the enclosed volume, before and after engine.mesh.remesh at the same R; the device ms of the index stages (the moments
+among them) and of the winding volume, the mean visits per lattice point; for the marching-cubes mesh also the volume at beta = 3
+and the exact sum on 4096 lattice points; for every other mesh the mean signed distance (in h) and the share inside of its
+--distance-n surface samples against the marching-cubes mesh.
+
     rocprofv3 --kernel-trace --output-format csv -d DIR -o mesh -- python tools/ngp_mesh.py --ckpt /tmp/ngp.npz --reps 1 --no-ply
     python tools/ngp_mesh.py --stats DIR/.../mesh_kernel_trace.csv --from profiles/ngp_mesh.jsonl --out profiles/ngp_mesh_kernels.jsonl
 
@@ -758,6 +765,89 @@ def _distance_arms(mesh, m, tsdf_mesh, teacher, R, lo, hi, a, rec, bound):
     return out
 
 
+def _edge_census(faces):
+    """(edges with one incident face, edges with more than two): torch plumbing on the undirected edges."""
+    f = faces.long()
+    if f.shape[0] == 0:
+        return 0, 0
+    e = torch.cat([f[:, [0, 1]], f[:, [1, 2]], f[:, [2, 0]]]).sort(1).values
+    _, c = torch.unique(e[:, 0] * (int(f.max()) + 1) + e[:, 1], return_counts=True)
+    return int((c == 1).sum()), int((c > 2).sum())
+
+
+def _winding_arms(mesh, m, tsdf_mesh, R, lo, hi, a, rec):
+    """JSON lines of --winding: per mesh (marching cubes, the TSDF mesh, the simplified meshes) the open and non-manifold edges
+    and the enclosed volume before and after engine.mesh.remesh at the same R, the device ms of the moments build and of the
+    winding volume, the mean visits per lattice point; for the marching-cubes mesh also the volume at beta = 3 and the exact sum
+    (beta = inf) on 4096 lattice points; and every other mesh's samples signed against the marching-cubes mesh."""
+    beta, n = a.winding_beta, a.distance_n
+    arms = [("marching cubes", m)] + ([("tsdf", tsdf_mesh)] if tsdf_mesh is not None else [])
+    arms += [(f"simplify {G}", mesh.simplify(m, G, lo, hi)) for G in (64, 128) if G < R]
+    base = {"tool": "ngp_mesh winding", "R": R, "iters": rec["iters"], "seed": rec["seed"], "beta": beta, "device": rec["device"]}
+    out = []
+
+    def line(r):
+        print(json.dumps(r), flush=True)
+        out.append(r)
+
+    def volume(wd, b, count=None):
+        """(volume or None, device ms, mean (faces, nodes) per point) over the whole lattice, or over its first `count` points."""
+        ts = []
+        for _ in range(a.reps + 1):                                      # the first run warms the allocator
+            st = _Stages()
+            if count is None:
+                vol, total = mesh.winding._winding_volume(wd, R, b, mark=st)
+                pts = R ** 3
+            else:
+                rows, _ = mesh.lattice_rows(R, lo, hi, 0, count, device=m.verts.device)
+                p = rows[:, :3].contiguous()
+                st("volume")
+                vol, total, pts = None, wd.query(p, b, sort=False)[1].sum(0), count
+            st("end")
+            ts.append(st.total_ms()["volume"])
+        return vol, float(np.mean(ts[1:])), [float(x) / pts for x in total.tolist()]
+
+    mc_wd = None
+    for name, x in arms:
+        if not x.faces.shape[0]:
+            continue
+        x = x._replace(colors=None)
+        builds = []
+        for _ in range(a.reps + 1):
+            st = _Stages()
+            wd = mesh.MeshWinding(x, lo, hi, mark=st)
+            st("end")
+            builds.append(st.total_ms())
+        build = {k: float(np.mean([q[k] for q in builds[1:]])) for k in builds[0]}
+        vol, vol_ms, visits = volume(wd, beta)
+        closed = mesh.marching_cubes(vol, 0.5, lo, hi)
+        r = {**base, "mesh": name, "V": int(x.verts.shape[0]), "F": int(x.faces.shape[0]), "build_ms": build,
+             "moments_ms": build["moments"], "volume_ms": vol_ms, "mean_visits": visits,
+             "edges_before": dict(zip(("open", "non_manifold"), _edge_census(x.faces))),
+             "edges_after": dict(zip(("open", "non_manifold"), _edge_census(closed.faces))),
+             "enclosed_volume_before": _enclosed_volume(x.verts, x.faces),
+             "enclosed_volume_after": _enclosed_volume(closed.verts, closed.faces),
+             "remesh": {"V": int(closed.verts.shape[0]), "F": int(closed.faces.shape[0])}}
+        if name == "marching cubes":
+            mc_wd = wd
+            if beta != 3.0:
+                _, ms3, visits3 = volume(wd, 3.0)
+                r["beta_3"] = {"volume_ms": ms3, "mean_visits": visits3}
+            _, ms_inf, visits_inf = volume(wd, float("inf"), min(4096, R ** 3))
+            r["exact_scan"] = {"points": min(4096, R ** 3), "ms": ms_inf, "mean_visits": visits_inf,
+                               "extrapolated_to_volume_ms": ms_inf * R ** 3 / min(4096, R ** 3)}
+        else:                                                            # this stage's surface, signed against marching cubes
+            pts, _ = mesh.sample_surface(x, n, lo, hi, 0)
+            w, _ = mc_wd.query(pts, beta)
+            d2, _ = mc_wd.bvh.query(pts)
+            sd = torch.where(w > 0.5, -d2.double().sqrt(), d2.double().sqrt())
+            r["signed_against_marching_cubes"] = {"n": n, "mean_signed_h": float(sd.mean()) / ((float(hi[0]) - float(lo[0])) / R),
+                                                  "share_inside": float((w > 0.5).double().mean())}
+        line(r)
+        del vol, closed
+    return out
+
+
 def _teacher_volume(R, lo, hi, dev):
     from nerf_meets_mlx_amd.dataset import synthetic
     from nerf_meets_mlx_amd.engine import mesh
@@ -844,6 +934,13 @@ def parser():
     ap.add_argument("--distance-index", choices=("grid", "bvh"), default="grid",
                     help="--distance: the face index of the pairs, the uniform grid or the bounding-volume hierarchy (DESIGN.md "
                          "section 38); the figures are the same bit for bit, the stage times are not")
+    ap.add_argument("--winding", action="store_true",
+                    help="at --ply-res: the generalized winding number (DESIGN.md section 40) of the marching-cubes mesh, the simplified "
+                         "(G = 64, 128) and, with --tsdf, TSDF meshes: open and non-manifold edges and enclosed volume before and "
+                         "after the remesh at the same R, moments build and volume times, mean visits, and every stage's samples "
+                         "(--distance-n) signed against the marching-cubes mesh")
+    ap.add_argument("--winding-beta", type=float, default=2.0, metavar="B",
+                    help="--winding: a subtree is replaced by its dipole beyond B radii from its centre (>= 1; inf: the exact sum)")
     ap.add_argument("--smooth-lambda", type=float, default=0.5)
     ap.add_argument("--smooth-mu", type=float, default=-0.53, help="0: plain Laplacian smoothing")
     ap.add_argument("--ckpt", default=None, help="load this checkpoint instead of training")
@@ -973,7 +1070,7 @@ def main():
                 del sm, srows
         lines += _simplify_arms(m._replace(colors=None), "density", R, lo, hi, a, rec, bound, boxes)
         lines += _smooth_arms(m._replace(colors=None), "density", R, lo, hi, a, rec, bound, boxes)
-        dist_m = m._replace(colors=None) if a.distance and R == a.ply_res else None
+        dist_m = m._replace(colors=None) if (a.distance or a.winding) and R == a.ply_res else None
         del vol, m, rows, col
         torch.cuda.empty_cache()
         tm = None
@@ -982,7 +1079,9 @@ def main():
             print(json.dumps(trec), flush=True)
             lines.append(trec)
             lines += _simplify_arms(tm, "tsdf", R, lo, hi, a, {**rec, "marching_cubes_ms": trec["marching_cubes_ms"]}, bound, boxes)
-        if dist_m is not None and dist_m.faces.shape[0]:
+        if a.winding and dist_m is not None and dist_m.faces.shape[0]:
+            lines += _winding_arms(mesh, dist_m, tm, R, lo, hi, a, rec)
+        if a.distance and dist_m is not None and dist_m.faces.shape[0]:
             teacher = mesh.marching_cubes(_teacher_volume(R, lo, hi, dev), 25.0, lo, hi)
             lines += _distance_arms(mesh, dist_m, tm, teacher, R, lo, hi, a, rec, bound)
             del teacher
