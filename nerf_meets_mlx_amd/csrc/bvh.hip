@@ -6,19 +6,17 @@
 //            caller sorts the keys (they are unique: no sort order is left open).
 //   leaves   one lane per leaf: the face ids of its four sorted keys (-1 for an invalid face) and the exact min / max of their
 //            float32 corners.
-//   level    one lane per node of a level: the union of its two children.  One launch per level; the levels of at most 256 nodes
-//            share the last launch, one workgroup with a barrier between levels.
+//   level    one lane per node of a level: the union of its two children (bvh_tree.h's pass with BvhOp).  One launch per level; the
+//            levels of at most 256 nodes share the last launch, one workgroup with a barrier between levels.
 //   query    one lane per point: a stackless depth-first walk, the nearer child first; the lane keeps the node index and one
 //            32-bit trail word with a bit per level where the far sibling is still pending.
 //   closest  one lane per point: the region tests of distance.h on the given face, the computed q written out.
 // Register use and what was measured: DESIGN.md section 38.
-#include "bvh_ws.h"
+#include "bvh_tree.h"
 #include "distance.h"
 
 namespace nerf {
 namespace {
-
-constexpr int64_t BVH_MAX_POINTS = 1ll << 30;
 
 struct BvhBox {
   double lo[3], ext[3];                                             // ext = (double)hi - (double)lo
@@ -111,23 +109,15 @@ __device__ __forceinline__ void bvh_merge(float* nodes, int64_t i) {
   bvh_store(nodes, i, mn, mx);
 }
 
-// ---- one level [first, 2 first): 48 B read and 24 B written per node
-__global__ void __launch_bounds__(BVH_BLOCK) bvh_level_kernel(float* nodes, int first) {
-  const int k = blockIdx.x * BVH_BLOCK + threadIdx.x;
-  if (k < first) bvh_merge(nodes, (int64_t)first + k);
-}
-// ---- the levels top .. 0 (top <= 8: at most 256 nodes) in one workgroup, and the unused node 0
-__global__ void __launch_bounds__(BVH_BLOCK) bvh_top_kernel(float* nodes, int top) {
-  for (int l = top; l >= 0; --l) {
-    const int first = 1 << l;
-    if ((int)threadIdx.x < first) bvh_merge(nodes, (int64_t)first + threadIdx.x);
-    __syncthreads();                                               // the level below is read from memory by other lanes
-  }
-  if (threadIdx.x == 0) {
+// bvh_tree.h's Op: 48 B read and 24 B written per node; node 0 is an empty box
+struct BvhOp {
+  float* nodes;
+  __device__ __forceinline__ void merge(int64_t i) const { bvh_merge(nodes, i); }
+  __device__ __forceinline__ void unused(int lane) const {
     const float mn[3] = {INFINITY, INFINITY, INFINITY}, mx[3] = {-INFINITY, -INFINITY, -INFINITY};
-    bvh_store(nodes, 0, mn, mx);
+    if (lane == 0) bvh_store(nodes, 0, mn, mx);
   }
-}
+};
 
 // the squared float64 distance from p to the box (mn, mx); +inf for an empty box
 __device__ __forceinline__ double bvh_box_d2(const double* p, float mn0, float mn1, float mn2, float mx0, float mx1, float mx2) {
@@ -138,15 +128,12 @@ __device__ __forceinline__ double bvh_box_d2(const double* p, float mn0, float m
   return (d0 * d0 + d1 * d1) + d2 * d2;
 }
 
-// The pruning rule: a node whose box is m = sqrt(m2) from the point is skipped only if it is empty, or m > slack and
-// (m - slack)^2 (1 - 2^-20) is strictly greater than the best D.  (m - slack)^2 (1 - 2^-20) < m^2, so m2 <= D never skips: the square
-// root is taken only where it can matter.
+// The pruning rule: a node whose box is m = sqrt(m2) from the point is skipped only if it is empty or distance.h's dist_stop says
+// so of m.  (m - slack)^2 (1 - 2^-20) < m^2, so m2 <= D never skips: the square root is taken only where it can matter.
 __device__ __forceinline__ bool bvh_skip(double m2, double slack, uint64_t best) {
   if (m2 == INFINITY) return true;
-  const double D = (double)__uint_as_float((uint32_t)(best >> 32));
-  if (m2 <= D) return false;
-  const double s = sqrt(m2) - slack;
-  return s > 0.0 && (s * s) * (1.0 - 0x1p-20) > D;
+  if (m2 <= (double)__uint_as_float((uint32_t)(best >> 32))) return false;
+  return dist_stop(sqrt(m2), slack, best);
 }
 
 // ---- the query: 12 B read and 8 B written per point; per internal node visited 48 B of its children, per leaf 16 B of ids and per
@@ -157,35 +144,29 @@ __global__ void __launch_bounds__(BVH_BLOCK) bvh_query_kernel(const float* __res
                                                              float* __restrict__ dist2, int* __restrict__ face) {
   const int64_t i = (int64_t)blockIdx.x * BVH_BLOCK + threadIdx.x;
   if (i >= n) return;
-  const float p[3] = {points[3 * i], points[3 * i + 1], points[3 * i + 2]};
-  if (!(isfinite(p[0]) && isfinite(p[1]) && isfinite(p[2]))) {
-    dist2[i] = __uint_as_float(0x7FC00000u);
-    face[i] = -1;
+  float p[3];
+  if (!dist_point(points, i, p, [&] {
+        dist2[i] = __uint_as_float(DIST_NAN32);
+        face[i] = -1;
+      }))
     return;
-  }
   const double pd[3] = {(double)p[0], (double)p[1], (double)p[2]};
   uint64_t best = DIST_NONE;
   const float* r = nodes + BVH_NODE_FLOATS;                          // the root, node 1
   const float r0 = r[0], r1 = r[1], r2 = r[2], r3 = r[3], r4 = r[4], r5 = r[5];
   if (r0 <= r3) {                                                    // a mesh with a valid face
-    // S: the largest |coordinate| of the point, the root box (every valid face's corners) and the box; slack as the grid's
-    float S = fmaxf(fmaxf(fabsf(p[0]), fabsf(p[1])), fabsf(p[2]));
-    S = fmaxf(S, fmaxf(fmaxf(fmaxf(fabsf(r0), fabsf(r1)), fabsf(r2)), fmaxf(fmaxf(fabsf(r3), fabsf(r4)), fabsf(r5))));
-    S = fmaxf(S, box_abs);
-    const double slack = (double)S * 0x1p-18;
+    // the valid faces' largest |coordinate| is the root box's, which holds every corner
+    const double slack = dist_slack(p, fmaxf(fmaxf(fmaxf(fabsf(r0), fabsf(r1)), fabsf(r2)), fmaxf(fmaxf(fabsf(r3), fabsf(r4)), fabsf(r5))),
+                                    box_abs);
     uint32_t node = 1u, trail = 0u;                                  // trail bit j: the sibling of the ancestor j levels up is pending
     for (;;) {
       bool up = false;
       if (node >= (uint32_t)P) {                                     // a leaf: its valid faces into the minimum
-        const int s0 = BVH_LEAF * (int)(node - (uint32_t)P);
-#pragma unroll
-        for (int k = 0; k < BVH_LEAF; ++k) {
-          const int f = s0 + k < F ? order[s0 + k] : -1;
-          if (f < 0) continue;
+        tree_leaf_faces(order, F, P, node, [&](int f) {
           Tri t;
           dist_load(verts, faces, f, t);
           best = dist_fold(best, point_triangle_d2(p, t), f);
-        }
+        });
         up = true;
       } else {                                                       // the nearer child first, left on a tie
         const float4* c = reinterpret_cast<const float4*>(nodes + (size_t)2 * node * BVH_NODE_FLOATS);
@@ -234,7 +215,7 @@ __global__ void __launch_bounds__(BVH_BLOCK) bvh_closest_kernel(const float* __r
   if (i >= n) return;
   const int f = face[i];
   const float p[3] = {points[3 * i], points[3 * i + 1], points[3 * i + 2]};
-  float q[3] = {__uint_as_float(0x7FC00000u), __uint_as_float(0x7FC00000u), __uint_as_float(0x7FC00000u)};
+  float q[3] = {__uint_as_float(DIST_NAN32), __uint_as_float(DIST_NAN32), __uint_as_float(DIST_NAN32)};
   Tri t;
   float d;
   if (f >= 0 && f < F && dist_face(verts, faces, f, V, t, &d)) point_triangle_closest(p, t, q);
@@ -243,22 +224,15 @@ __global__ void __launch_bounds__(BVH_BLOCK) bvh_closest_kernel(const float* __r
 }
 
 int bvh_box(const char* who, int64_t V, int64_t F, const float* lo, const float* hi, BvhBox* bx) {
-  int rc = mesh_check(who, V, F);
-  if (rc) return rc;
-  rc = box_check(who, lo, hi);
-  if (rc) return rc;
-  float babs = 0.0f;
+  NERF_TRY(mesh_check(who, V, F));
+  NERF_TRY(box_check(who, lo, hi));
   for (int a = 0; a < 3; ++a) {
     bx->lo[a] = (double)lo[a];
     bx->ext[a] = (double)hi[a] - (double)lo[a];
-    babs = std::fmax(babs, std::fmax(std::fabs(lo[a]), std::fabs(hi[a])));
   }
-  bx->box_abs = babs;
+  bx->box_abs = box_abs(lo, hi);
   return NERF_OK;
 }
-inline bool bvh_aligned(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
-
-#define BVH_LAUNCH(what, kernel, blocks, ...) NERF_LAUNCH(what, kernel, blocks, BVH_BLOCK, st, __VA_ARGS__)
 
 }  // namespace
 }  // namespace nerf
@@ -270,55 +244,48 @@ extern "C" int64_t nerf_bvh_workspace_bytes(int64_t F) { return bvh_workspace_by
 extern "C" int nerf_bvh_keys(const float* verts, int64_t V, const int32_t* faces, int64_t F, const float* lo, const float* hi,
                              int64_t* keys, void* stream) {
   BvhBox bx;
-  const int rc = bvh_box("nerf_bvh_keys", V, F, lo, hi, &bx);
-  if (rc) return rc;
+  NERF_TRY(bvh_box("nerf_bvh_keys", V, F, lo, hi, &bx));
   if (F == 0) return NERF_OK;
   NERF_REQUIRE(faces && keys && (verts || V == 0), NERF_E_NULL, "nerf_bvh_keys: NULL pointer");
   hipStream_t st = as_stream(stream);
-  BVH_LAUNCH("nerf_bvh_keys", bvh_keys_kernel, blocks(F, BVH_BLOCK), verts, (int)V, faces, (int)F, bx, keys);
+  DIST_LAUNCH("nerf_bvh_keys", bvh_keys_kernel, blocks(F, BVH_BLOCK), verts, (int)V, faces, (int)F, bx, keys);
   return NERF_OK;
 }
 
 extern "C" int nerf_bvh_build(const float* verts, int64_t V, const int32_t* faces, int64_t F, const int64_t* sorted_keys,
                               void* workspace, void* stream) {
-  const int rc = mesh_check("nerf_bvh_build", V, F);
-  if (rc) return rc;
+  NERF_TRY(mesh_check("nerf_bvh_build", V, F));
   NERF_REQUIRE(workspace && (F == 0 || (faces && sorted_keys && verts)), NERF_E_NULL, "nerf_bvh_build: NULL pointer");
-  NERF_REQUIRE(bvh_aligned(workspace), NERF_E_SHAPE, "nerf_bvh_build: the workspace must start on a multiple of 16 bytes");
+  NERF_TRY(ws_aligned16_check("nerf_bvh_build", workspace));
   const BvhWs w = bvh_ws(workspace, F);
   hipStream_t st = as_stream(stream);
-  BVH_LAUNCH("nerf_bvh_build (leaves)", bvh_leaves_kernel, blocks(w.P, BVH_BLOCK), verts, (int)V, faces, (int)F, sorted_keys, (int)w.P, w.nodes,
+  DIST_LAUNCH("nerf_bvh_build (leaves)", bvh_leaves_kernel, blocks(w.P, BVH_BLOCK), verts, (int)V, faces, (int)F, sorted_keys, (int)w.P, w.nodes,
              w.order);
-  for (int l = w.depth - 1; l >= BVH_TOP_LEVELS; --l)
-    BVH_LAUNCH("nerf_bvh_build (level)", bvh_level_kernel, blocks(bvh_level_nodes(l), BVH_BLOCK), w.nodes, (int)bvh_level_first(l));
-  BVH_LAUNCH("nerf_bvh_build (top)", bvh_top_kernel, 1, w.nodes, (w.depth < BVH_TOP_LEVELS ? w.depth : BVH_TOP_LEVELS) - 1);
-  return NERF_OK;
+  return tree_reduce("nerf_bvh_build (level)", "nerf_bvh_build (top)", BvhOp{w.nodes}, w.depth, st);
 }
 
 extern "C" int nerf_bvh_query(const float* points, int64_t n, const float* verts, int64_t V, const int32_t* faces, int64_t F,
                               const float* lo, const float* hi, const void* workspace, float* dist2, int32_t* face, void* stream) {
   BvhBox bx;
-  const int rc = bvh_box("nerf_bvh_query", V, F, lo, hi, &bx);
-  if (rc) return rc;
-  NERF_REQUIRE(n >= 0 && n <= BVH_MAX_POINTS, NERF_E_SHAPE, "nerf_bvh_query: need 0 <= n <= 2^30 (got %lld)", (long long)n);
+  NERF_TRY(bvh_box("nerf_bvh_query", V, F, lo, hi, &bx));
+  NERF_TRY(points_check("nerf_bvh_query", n));
   if (n == 0) return NERF_OK;
   NERF_REQUIRE(points && workspace && dist2 && face && (F == 0 || (verts && faces)), NERF_E_NULL, "nerf_bvh_query: NULL pointer");
-  NERF_REQUIRE(bvh_aligned(workspace), NERF_E_SHAPE, "nerf_bvh_query: the workspace must start on a multiple of 16 bytes");
+  NERF_TRY(ws_aligned16_check("nerf_bvh_query", workspace));
   const BvhWs w = bvh_ws(const_cast<void*>(workspace), F);
   hipStream_t st = as_stream(stream);
-  BVH_LAUNCH("nerf_bvh_query", bvh_query_kernel, blocks(n, BVH_BLOCK), points, n, verts, faces, (int)F, bx.box_abs, (int)w.P,
+  DIST_LAUNCH("nerf_bvh_query", bvh_query_kernel, blocks(n, BVH_BLOCK), points, n, verts, faces, (int)F, bx.box_abs, (int)w.P,
              (const float*)w.nodes, (const int*)w.order, dist2, face);
   return NERF_OK;
 }
 
 extern "C" int nerf_closest_points(const float* points, int64_t n, const float* verts, int64_t V, const int32_t* faces, int64_t F,
                                    const int32_t* face, float* closest, void* stream) {
-  const int rc = mesh_check("nerf_closest_points", V, F);
-  if (rc) return rc;
-  NERF_REQUIRE(n >= 0 && n <= BVH_MAX_POINTS, NERF_E_SHAPE, "nerf_closest_points: need 0 <= n <= 2^30 (got %lld)", (long long)n);
+  NERF_TRY(mesh_check("nerf_closest_points", V, F));
+  NERF_TRY(points_check("nerf_closest_points", n));
   if (n == 0) return NERF_OK;
   NERF_REQUIRE(points && face && closest && (F == 0 || faces) && (V == 0 || verts), NERF_E_NULL, "nerf_closest_points: NULL pointer");
   hipStream_t st = as_stream(stream);
-  BVH_LAUNCH("nerf_closest_points", bvh_closest_kernel, blocks(n, BVH_BLOCK), points, n, verts, (int)V, faces, (int)F, face, closest);
+  DIST_LAUNCH("nerf_closest_points", bvh_closest_kernel, blocks(n, BVH_BLOCK), points, n, verts, (int)V, faces, (int)F, face, closest);
   return NERF_OK;
 }

@@ -43,7 +43,7 @@ inline BvhWs bvh_ws(void* ws, int64_t F) {
     w.P <<= 1;
     ++w.depth;
   }
-  // the internal levels depth - 1 .. 0; those below BVH_TOP_LEVELS share the last launch
+  // the leaves' launch, then bvh_tree.h's tree_reduce: the internal levels depth - 1 .. 0, those below BVH_TOP_LEVELS in one launch
   w.launches = 2 + (w.depth > BVH_TOP_LEVELS ? w.depth - BVH_TOP_LEVELS : 0);
   uintptr_t p = reinterpret_cast<uintptr_t>(ws);
   const uintptr_t p0 = p;

@@ -125,6 +125,13 @@ static inline unsigned blocks(int64_t n, int block) { return (unsigned)((n + blo
     if (!(cond)) return nerf::fail(code, __VA_ARGS__); \
   } while (0)
 
+// a check or a launch helper that returns a code: a failure returns it from the calling entry
+#define NERF_TRY(call)             \
+  do {                             \
+    const int rc_ = (call);        \
+    if (rc_) return rc_;           \
+  } while (0)
+
 // Launches `kernel` with `blocks` workgroups of `threads` on hipStream_t `st`; a failed launch returns its code from the calling entry.
 #define NERF_LAUNCH(what, kernel, blocks, threads, st, ...)                                        \
   do {                                                                                             \

@@ -1,14 +1,18 @@
-// What the two face indices of the mesh distance share (distance.hip's grid, bvh.hip's hierarchy): the face-validity rule, Ericson's
-// point-triangle region tests and the 64-bit (distance, face) key.  Semantics in include/nerf_hip.h "mesh distance".  float32, every
-// operation rounded separately (the units that include this build with -ffp-contract=off), the divisions correctly rounded;
-// tests/_distance_ref.py reproduces every bit.
+// What the point queries against a mesh share (distance.hip's grid, bvh.hip's hierarchy, winding.hip's moments on it): the face-validity
+// rule, Ericson's point-triangle region tests, the 64-bit (distance, face) key, the load of a point, the stop rule of the two indices,
+// the host checks and the launch.  Semantics in include/nerf_hip.h "mesh distance".  float32, every operation rounded separately (the
+// units that include this build with -ffp-contract=off), the divisions correctly rounded; tests/_distance_ref.py reproduces every bit.
 #pragma once
 #include "lattice.h"
 
 namespace nerf {
 namespace {
 
+constexpr int DIST_BLOCK = 256;                                    // lanes per workgroup of every kernel here (= BVH_BLOCK)
 constexpr uint64_t DIST_NONE = 0x7F800000FFFFFFFFull;              // (+inf, face -1)
+constexpr uint32_t DIST_NAN32 = 0x7FC00000u;                       // the quiet NaNs written where there is no answer
+constexpr int64_t DIST_NAN64 = 0x7FF8000000000000ll;
+constexpr int64_t MESH_MAX_POINTS = 1ll << 30;                     // points of a query, samples of a draw
 
 __device__ __forceinline__ float dot3(const float* x, const float* y) { return (x[0] * y[0] + x[1] * y[1]) + x[2] * y[2]; }
 
@@ -113,6 +117,48 @@ __device__ __forceinline__ uint64_t dist_fold(uint64_t best, float d, int f) {
   const uint64_t key = ((uint64_t)__float_as_uint(d) << 32) | (uint32_t)f;
   return key < best ? key : best;
 }
+
+// Point i of points [n][3] into p; false, behind bad() writing the kernel's answer, when a coordinate is not finite.  (A callback
+// keeps the three tests branches around it; returned as one plain bool they are evaluated together and the grid query takes 88 VGPRs.)
+template <class Bad>
+__device__ __forceinline__ bool dist_point(const float* __restrict__ points, int64_t i, float* p, Bad bad) {
+#pragma unroll
+  for (int k = 0; k < 3; ++k) p[k] = points[3 * i + k];
+  if (isfinite(p[0]) && isfinite(p[1]) && isfinite(p[2])) return true;
+  bad();
+  return false;
+}
+
+// slack = S 2^-18, S the largest |coordinate| of the point, the valid faces and the box (why: distance.hip's query)
+__device__ __forceinline__ double dist_slack(const float* p, float faces_max, float box_max) {
+  const float S = fmaxf(fmaxf(fmaxf(fabsf(p[0]), fabsf(p[1])), fabsf(p[2])), fmaxf(faces_max, box_max));
+  return (double)S * 0x1p-18;
+}
+// The stop rule of both indices.  Every face not yet seen is at least m from the point, so its float32 distance is at least
+// (m - slack)^2 (1 - 2^-20): stop only when m > slack and that is strictly greater than the best D; on equality a lower face
+// index may still tie.
+__device__ __forceinline__ bool dist_stop(double m, double slack, uint64_t best) {
+  const double s = m - slack;
+  return s > 0.0 && (s * s) * (1.0 - 0x1p-20) > (double)__uint_as_float((uint32_t)(best >> 32));
+}
+
+// ---- host side: the checks of the query entries, each with its one text, and their launch
+inline float box_abs(const float* lo, const float* hi) {           // the largest |corner coordinate|
+  float m = 0.0f;
+  for (int a = 0; a < 3; ++a) m = std::fmax(m, std::fmax(std::fabs(lo[a]), std::fabs(hi[a])));
+  return m;
+}
+inline int points_check(const char* who, int64_t n) {
+  NERF_REQUIRE(n >= 0 && n <= MESH_MAX_POINTS, NERF_E_SHAPE, "%s: need 0 <= n <= 2^30 (got %lld)", who, (long long)n);
+  return NERF_OK;
+}
+inline bool ws_aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
+inline int ws_aligned16_check(const char* who, const void* ws, const void* ws2 = nullptr) {
+  NERF_REQUIRE(ws_aligned16(ws) && ws_aligned16(ws2), NERF_E_SHAPE, "%s: the workspace%s must start on a multiple of 16 bytes", who,
+               ws2 ? "s" : "");
+  return NERF_OK;
+}
+#define DIST_LAUNCH(what, kernel, blocks, ...) NERF_LAUNCH(what, kernel, blocks, DIST_BLOCK, st, __VA_ARGS__)
 
 }  // namespace
 }  // namespace nerf

@@ -15,10 +15,8 @@
 namespace nerf {
 namespace {
 
-constexpr int DIST_BLOCK = 256;
 constexpr int DIST_MAX_GRID = 256;                                 // G^3 <= 2^24 cells
 constexpr int64_t DIST_MAX_ENTRIES = 1ll << 30;                    // offsets are ints
-constexpr int64_t DIST_MAX_SAMPLES = 1ll << 30;
 constexpr double DIST_W_LIM = 16.0, DIST_W_SCALE = 17179869184.0;  // weight = max(1, rint(min(d / U, 16) 2^34))
 
 struct DistBox {
@@ -50,31 +48,6 @@ __device__ __forceinline__ int dist_cell(const DistBox& bx, int a, float x) {
   return (int)t;
 }
 
-// ---- int64 forms of scan.h's block_sum / block_offset (a weight does not fit an int); every lane of the workgroup must call them
-__device__ __forceinline__ int64_t dist_block_sum(int64_t v) {
-  __shared__ int64_t sh[DIST_BLOCK / WAVE];
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, WAVE);
-  if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
-  __syncthreads();
-  int64_t t = 0;
-  if (threadIdx.x == 0)
-    for (int k = 0; k < DIST_BLOCK / WAVE; ++k) t += sh[k];
-  return t;
-}
-__device__ __forceinline__ int64_t dist_block_inclusive(int64_t v, int64_t base) {
-  __shared__ int64_t sh[DIST_BLOCK / WAVE];
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  int64_t x = v;
-  for (int o = 1; o < WAVE; o <<= 1) {
-    const int64_t t = __shfl_up(x, o, WAVE);
-    if (lane >= o) x += t;
-  }
-  if (lane == 63) sh[w] = x;
-  __syncthreads();
-  for (int k = 0; k < w; ++k) base += sh[k];
-  return base + x;
-}
-
 // ---- weights: 12 B of indices and 36 B of corners read per face, 8 B written; the workgroup's sum to blk
 __global__ void __launch_bounds__(DIST_BLOCK) dist_weight_kernel(const float* __restrict__ verts, int V, const int* __restrict__ faces,
                                                                 int F, double unit, int64_t* __restrict__ cdf,
@@ -87,13 +60,14 @@ __global__ void __launch_bounds__(DIST_BLOCK) dist_weight_kernel(const float* __
     if (dist_face(verts, faces, f, V, t, &d)) w = dist_weight(d, unit);
     cdf[f] = w;
   }
-  const int64_t s = dist_block_sum(w);
+  const int64_t s = block_sum<DIST_BLOCK, int64_t>(w);              // a weight does not fit an int
   if (threadIdx.x == 0) blk[blockIdx.x] = s;
 }
 // ---- weights -> inclusive CDF in place (every lane reads and writes its own element only)
 __global__ void __launch_bounds__(DIST_BLOCK) dist_cdf_kernel(int64_t* __restrict__ cdf, int F, const int64_t* __restrict__ blk) {
   const int f = blockIdx.x * DIST_BLOCK + threadIdx.x;
-  const int64_t c = dist_block_inclusive(f < F ? cdf[f] : 0, blk[blockIdx.x]);
+  const int64_t v = f < F ? cdf[f] : 0;
+  const int64_t c = block_offset<DIST_BLOCK, int64_t>(v, blk[blockIdx.x]) + v;
   if (f < F) cdf[f] = c;
 }
 
@@ -116,7 +90,7 @@ __global__ void __launch_bounds__(DIST_BLOCK) dist_sample_kernel(const float* __
   float d;
   if (!dist_face(verts, faces, lo, V, t, &d)) {                     // only with a cdf or total that are not this mesh's
 #pragma unroll
-    for (int k = 0; k < 3; ++k) points[3 * i + k] = __uint_as_float(0x7FC00000u);
+    for (int k = 0; k < 3; ++k) points[3 * i + k] = __uint_as_float(DIST_NAN32);
     face[i] = -1;
     return;
   }
@@ -206,12 +180,12 @@ __global__ void __launch_bounds__(DIST_BLOCK) dist_query_kernel(const float* __r
                                                                int* __restrict__ face) {
   const int64_t i = (int64_t)blockIdx.x * DIST_BLOCK + threadIdx.x;
   if (i >= n) return;
-  const float p[3] = {points[3 * i], points[3 * i + 1], points[3 * i + 2]};
-  if (!(isfinite(p[0]) && isfinite(p[1]) && isfinite(p[2]))) {
-    dist2[i] = __uint_as_float(0x7FC00000u);
-    face[i] = -1;
+  float p[3];
+  if (!dist_point(points, i, p, [&] {
+        dist2[i] = __uint_as_float(DIST_NAN32);
+        face[i] = -1;
+      }))
     return;
-  }
   const int G = bx.G;
   int c[3];
   double q[3];                                                       // the point projected onto the box
@@ -224,8 +198,7 @@ __global__ void __launch_bounds__(DIST_BLOCK) dist_query_kernel(const float* __r
   // error below 2^-21: ten float32 operations on operands of at most 4 S each lead to the closest point and to the difference,
   // S the largest |coordinate| of the point, the valid faces and the box.  64 * 2^-24 S covers them and the double roundings of
   // the cell planes.
-  const float S = fmaxf(fmaxf(fmaxf(fabsf(p[0]), fabsf(p[1])), fabsf(p[2])), fmaxf(__uint_as_float(scale[0]), bx.box_abs));
-  const double slack = (double)S * 0x1p-18;
+  const double slack = dist_slack(p, __uint_as_float(scale[0]), bx.box_abs);
   uint64_t best = DIST_NONE;
   for (int r = 0;; ++r) {
     const int z0 = max(c[2] - r, 0), z1 = min(c[2] + r, G - 1), y0 = max(c[1] - r, 0), y1 = min(c[1] + r, G - 1);
@@ -254,8 +227,7 @@ __global__ void __launch_bounds__(DIST_BLOCK) dist_query_kernel(const float* __r
     //    every cell its clamped bounding box overlaps: for every point x of a face not yet seen, the projection of x onto the box
     //    lies in one of the face's cells, all of them unvisited, so |q - proj(x)| >= m.
     //  * Projection onto the box is non-expansive: |p - x| >= |q - proj(x)| >= m, for p inside the box (q = p) and outside.
-    // So every unseen face has a true distance of at least m and a float32 distance of at least (m - slack)^2 (1 - 2^-20).  Stop
-    // only when that is strictly greater than the best: on equality a lower face index may still tie.
+    // So every unseen face has a true distance of at least m, which is what dist_stop asks for.
     double m = INFINITY;
 #pragma unroll
     for (int a = 0; a < 3; ++a) {
@@ -263,8 +235,7 @@ __global__ void __launch_bounds__(DIST_BLOCK) dist_query_kernel(const float* __r
       if (c[a] + r + 1 < G) m = fmin(m, (bx.lo[a] + bx.h[a] * (double)(c[a] + r + 1)) - q[a]);
     }
     if (m == INFINITY) break;                                        // every cell has been visited
-    const double s = m - slack;
-    if (s > 0.0 && (s * s) * (1.0 - 0x1p-20) > (double)__uint_as_float((uint32_t)(best >> 32))) break;
+    if (dist_stop(m, slack, best)) break;
   }
   dist2[i] = __uint_as_float((uint32_t)(best >> 32));
   face[i] = (int)(uint32_t)(best & 0xFFFFFFFFull);
@@ -302,28 +273,22 @@ inline DistWs dist_ws(void* ws, int G) {
 }
 
 int dist_box(const char* who, int64_t V, int64_t F, const float* lo, const float* hi, int G, DistBox* bx) {
-  int rc = mesh_check(who, V, F);
-  if (rc) return rc;
+  NERF_TRY(mesh_check(who, V, F));
   NERF_REQUIRE(dist_grid_ok(G), NERF_E_SHAPE, "%s: need 1 <= grid <= %d (got %d)", who, DIST_MAX_GRID, G);
-  rc = box_check(who, lo, hi);
-  if (rc) return rc;
+  NERF_TRY(box_check(who, lo, hi));
   double emax = 0.0;
-  float babs = 0.0f;
   for (int a = 0; a < 3; ++a) {
     const double ext = (double)hi[a] - (double)lo[a];
     bx->lo[a] = (double)lo[a];
     bx->h[a] = ext / (double)G;
     bx->inv[a] = (double)G / ext;
     emax = ext > emax ? ext : emax;
-    babs = std::fmax(babs, std::fmax(std::fabs(lo[a]), std::fabs(hi[a])));
   }
   bx->unit = emax * emax;
-  bx->box_abs = babs;
+  bx->box_abs = box_abs(lo, hi);
   bx->G = G;
   return NERF_OK;
 }
-
-#define DIST_LAUNCH(what, kernel, blocks, ...) NERF_LAUNCH(what, kernel, blocks, DIST_BLOCK, st, __VA_ARGS__)
 
 }  // namespace
 }  // namespace nerf
@@ -337,25 +302,22 @@ extern "C" int64_t nerf_surface_cdf_workspace_bytes(int64_t F) {
 extern "C" int nerf_surface_cdf(const float* verts, int64_t V, const int32_t* faces, int64_t F, const float* lo, const float* hi,
                                 void* workspace, int64_t* cdf, void* stream) {
   DistBox bx;
-  const int rc = dist_box("nerf_surface_cdf", V, F, lo, hi, 1, &bx);
-  if (rc) return rc;
+  NERF_TRY(dist_box("nerf_surface_cdf", V, F, lo, hi, 1, &bx));
   if (F == 0) return NERF_OK;
   NERF_REQUIRE(faces && workspace && cdf && (verts || V == 0), NERF_E_NULL, "nerf_surface_cdf: NULL pointer");
   hipStream_t st = as_stream(stream);
   const int64_t nblk = blocks(F, DIST_BLOCK);
   int64_t* blk = static_cast<int64_t*>(workspace);
   DIST_LAUNCH("nerf_surface_cdf (weights)", dist_weight_kernel, nblk, verts, (int)V, faces, (int)F, bx.unit, cdf, blk);
-  const int rs = scan_launch("nerf_surface_cdf (scan)", blk, nblk, blk + nblk, st);
-  if (rs) return rs;
+  NERF_TRY(scan_launch("nerf_surface_cdf (scan)", blk, nblk, blk + nblk, st));
   DIST_LAUNCH("nerf_surface_cdf (write)", dist_cdf_kernel, nblk, cdf, (int)F, (const int64_t*)blk);
   return NERF_OK;
 }
 
 extern "C" int nerf_surface_sample(const float* verts, int64_t V, const int32_t* faces, int64_t F, const int64_t* cdf, int64_t total,
                                    int64_t n, uint64_t seed, float* points, int32_t* face, void* stream) {
-  const int rc = mesh_check("nerf_surface_sample", V, F);
-  if (rc) return rc;
-  NERF_REQUIRE(n >= 0 && n <= DIST_MAX_SAMPLES, NERF_E_SHAPE, "nerf_surface_sample: need 0 <= n <= 2^30 (got %lld)", (long long)n);
+  NERF_TRY(mesh_check("nerf_surface_sample", V, F));
+  NERF_TRY(points_check("nerf_surface_sample", n));
   if (n == 0) return NERF_OK;
   NERF_REQUIRE(total > 0 && F > 0, NERF_E_SHAPE, "nerf_surface_sample: the mesh has no area (total weight %lld over %lld faces)",
                (long long)total, (long long)F);
@@ -373,8 +335,7 @@ extern "C" int64_t nerf_meshdist_workspace_bytes(int64_t F, int grid) {
 extern "C" int nerf_meshdist_count(const float* verts, int64_t V, const int32_t* faces, int64_t F, const float* lo, const float* hi,
                                    int grid, void* workspace, int64_t* total_out, void* stream) {
   DistBox bx;
-  const int rc = dist_box("nerf_meshdist_count", V, F, lo, hi, grid, &bx);
-  if (rc) return rc;
+  NERF_TRY(dist_box("nerf_meshdist_count", V, F, lo, hi, grid, &bx));
   NERF_REQUIRE(workspace && total_out && (faces || F == 0) && (verts || V == 0), NERF_E_NULL, "nerf_meshdist_count: NULL pointer");
   const DistWs w = dist_ws(workspace, grid);
   hipStream_t st = as_stream(stream);
@@ -384,8 +345,7 @@ extern "C" int nerf_meshdist_count(const float* verts, int64_t V, const int32_t*
   if (F > 0)
     DIST_LAUNCH("nerf_meshdist_count (count)", dist_count_kernel, blocks(F, DIST_BLOCK), verts, (int)V, faces, (int)F, bx, w.cur, w.scale);
   DIST_LAUNCH("nerf_meshdist_count (cell counts)", dist_cells_count_kernel, w.nblk, (const int*)w.cur, (int)w.cells, w.blk);
-  const int rs = scan_launch("nerf_meshdist_count (scan of the cells)", w.blk, w.nblk, w.total, st);
-  if (rs) return rs;
+  NERF_TRY(scan_launch("nerf_meshdist_count (scan of the cells)", w.blk, w.nblk, w.total, st));
   DIST_LAUNCH("nerf_meshdist_count (cell offsets)", dist_cells_write_kernel, w.nblk, w.cur, (int)w.cells, (const int64_t*)w.blk,
               (const int64_t*)w.total, w.off, total_out);
   return NERF_OK;
@@ -394,8 +354,7 @@ extern "C" int nerf_meshdist_count(const float* verts, int64_t V, const int32_t*
 extern "C" int nerf_meshdist_build(const float* verts, int64_t V, const int32_t* faces, int64_t F, const float* lo, const float* hi,
                                    int grid, void* workspace, int32_t* entries, int64_t E, void* stream) {
   DistBox bx;
-  const int rc = dist_box("nerf_meshdist_build", V, F, lo, hi, grid, &bx);
-  if (rc) return rc;
+  NERF_TRY(dist_box("nerf_meshdist_build", V, F, lo, hi, grid, &bx));
   NERF_REQUIRE(E >= 0, NERF_E_SHAPE, "nerf_meshdist_build: need entries >= 0 (got %lld)", (long long)E);
   NERF_REQUIRE(E <= DIST_MAX_ENTRIES, NERF_E_SHAPE, "nerf_meshdist_build: %lld entries exceed 2^30; use a coarser grid", (long long)E);
   if (E == 0 || F == 0) return NERF_OK;
@@ -410,9 +369,8 @@ extern "C" int nerf_meshdist_query(const float* points, int64_t n, const float* 
                                    const float* lo, const float* hi, int grid, const void* workspace, const int32_t* entries, int64_t E,
                                    float* dist2, int32_t* face, void* stream) {
   DistBox bx;
-  const int rc = dist_box("nerf_meshdist_query", V, F, lo, hi, grid, &bx);
-  if (rc) return rc;
-  NERF_REQUIRE(n >= 0 && n <= DIST_MAX_SAMPLES, NERF_E_SHAPE, "nerf_meshdist_query: need 0 <= n <= 2^30 (got %lld)", (long long)n);
+  NERF_TRY(dist_box("nerf_meshdist_query", V, F, lo, hi, grid, &bx));
+  NERF_TRY(points_check("nerf_meshdist_query", n));
   NERF_REQUIRE(E >= 0 && E <= DIST_MAX_ENTRIES, NERF_E_SHAPE, "nerf_meshdist_query: need 0 <= entries <= 2^30 (got %lld)", (long long)E);
   if (n == 0) return NERF_OK;
   NERF_REQUIRE(points && workspace && dist2 && face && (E == 0 || (verts && faces && entries)), NERF_E_NULL,

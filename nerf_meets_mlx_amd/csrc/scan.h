@@ -3,19 +3,21 @@
 // (occ_cull_scan_kernel, launched by scan_launch), rank inside the workgroup (block_offset).  Fixed order, no atomics; and the
 // host's layout of the workspace a count / write pair shares.
 #pragma once
+#include <type_traits>
 #include "common.h"
 
 namespace nerf {
 namespace {
 
 // Both helpers below contain a __syncthreads(): EVERY lane of the workgroup must reach them, lanes past the end of the data
-// included (with v = 0), and none may have returned before.  BLOCK = the workgroup's threads; N counters are carried at once.
+// included (with v = 0), and none may have returned before.  BLOCK = the workgroup's threads; N counters of type T (int, or int64_t
+// for distance.hip's weights) are carried at once.
 
 // total[c] = the sum of v[c] over the workgroup in thread 0 (0 in every other): wave butterfly, lane 0 to LDS, thread 0 adds the waves.
-template <int BLOCK, int N>
-__device__ __forceinline__ void block_sum(const int (&v)[N], int64_t (&total)[N]) {
-  __shared__ int sh[N][BLOCK / WAVE];
-  int t[N];
+template <int BLOCK, int N, class T = int>
+__device__ __forceinline__ void block_sum(const T (&v)[N], int64_t (&total)[N]) {
+  __shared__ T sh[N][BLOCK / WAVE];
+  T t[N];
 #pragma unroll
   for (int c = 0; c < N; ++c) t[c] = v[c];
   for (int o = 32; o > 0; o >>= 1) {
@@ -37,17 +39,17 @@ __device__ __forceinline__ void block_sum(const int (&v)[N], int64_t (&total)[N]
 
 // off[c] += the exclusive prefix of v[c] over the workgroup's lanes in thread order (off[c] comes in as the workgroup's base):
 // inclusive wave scan, last lane to LDS, the waves below added in order.
-template <int BLOCK, int N>
-__device__ __forceinline__ void block_offset(const int (&v)[N], int64_t (&off)[N]) {
-  __shared__ int sh[N][BLOCK / WAVE];
+template <int BLOCK, int N, class T = int>
+__device__ __forceinline__ void block_offset(const T (&v)[N], int64_t (&off)[N]) {
+  __shared__ T sh[N][BLOCK / WAVE];
   const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  int x[N];
+  T x[N];
 #pragma unroll
   for (int c = 0; c < N; ++c) x[c] = v[c];
   for (int o = 1; o < WAVE; o <<= 1) {
 #pragma unroll
     for (int c = 0; c < N; ++c) {
-      const int t = __shfl_up(x[c], o, WAVE);
+      const T t = __shfl_up(x[c], o, WAVE);
       if (lane >= o) x[c] += t;
     }
   }
@@ -63,17 +65,17 @@ __device__ __forceinline__ void block_offset(const int (&v)[N], int64_t (&off)[N
   }
 }
 
-// the one-counter forms
-template <int BLOCK>
-__device__ __forceinline__ int64_t block_sum(int v) {
+// the one-counter forms (T is named, never deduced: an argument of another type converts to it)
+template <int BLOCK, class T = int>
+__device__ __forceinline__ int64_t block_sum(std::common_type_t<T> v) {
   int64_t t[1];
-  block_sum<BLOCK>({v}, t);
+  block_sum<BLOCK, 1, T>({v}, t);
   return t[0];
 }
-template <int BLOCK>
-__device__ __forceinline__ int64_t block_offset(int v, int64_t base) {
+template <int BLOCK, class T = int>
+__device__ __forceinline__ int64_t block_offset(std::common_type_t<T> v, int64_t base) {
   int64_t o[1] = {base};
-  block_offset<BLOCK>({v}, o);
+  block_offset<BLOCK, 1, T>({v}, o);
   return o[0];
 }
 

@@ -3,18 +3,18 @@
 // operator.  No reference counterpart.  All arithmetic is float64 on the float32 corners and points, every operation rounded
 // separately (-ffp-contract=off).  Nothing here needs a workgroup to wait for another, a per-lane stack, an atomic or a host read:
 //   leaves   one lane per leaf: the area vectors, areas and area-weighted centroids of its valid faces, in sorted order.
-//   level    one lane per node of a level: left + right, then the centre and the radius.  One launch per level; the levels of at
-//            most 256 nodes share the last launch, one workgroup with a barrier between levels (the hierarchy's launch shape).
+//   level    one lane per node of a level: left + right, then the centre and the radius (bvh_tree.h's pass with WindOp: the
+//            hierarchy's own launches).
 //   query    one lane per point: a depth-first walk in heap order, left before right, that replaces a far subtree by its dipole.
 //            The lane keeps the node index and nothing else; the order of the float64 sum is fixed by the tree.
 // Register use and what was measured: DESIGN.md section 40.
 #include "winding_ws.h"
+#include "bvh_tree.h"
 #include "distance.h"
 
 namespace nerf {
 namespace {
 
-constexpr int64_t WIND_MAX_POINTS = 1ll << 30;
 constexpr double WIND_FOUR_PI = 12.566370614359172;                 // 4 pi rounded to double
 
 struct WindMom {
@@ -105,20 +105,13 @@ __device__ __forceinline__ void wind_merge(const float* nodes, double* mom, int6
   wind_store(mom, i, m, box);
 }
 
-// ---- one level [first, 2 first): 192 B of records and 24 B of box read, 96 B written per node
-__global__ void __launch_bounds__(BVH_BLOCK) wind_level_kernel(const float* nodes, double* mom, int first) {
-  const int k = blockIdx.x * BVH_BLOCK + threadIdx.x;
-  if (k < first) wind_merge(nodes, mom, (int64_t)first + k);
-}
-// ---- the levels top .. 0 (top <= 8: at most 256 nodes) in one workgroup, and the unused node 0
-__global__ void __launch_bounds__(BVH_BLOCK) wind_top_kernel(const float* nodes, double* mom, int top) {
-  for (int l = top; l >= 0; --l) {
-    const int first = 1 << l;
-    if ((int)threadIdx.x < first) wind_merge(nodes, mom, (int64_t)first + threadIdx.x);
-    __syncthreads();                                               // the level below is read from memory by other lanes
-  }
-  if ((int)threadIdx.x < WIND_NODE_DOUBLES) mom[threadIdx.x] = 0.0;
-}
+// bvh_tree.h's Op: 192 B of records and 24 B of box read, 96 B written per node; node 0 is twelve zeros
+struct WindOp {
+  const float* nodes;
+  double* mom;
+  __device__ __forceinline__ void merge(int64_t i) const { wind_merge(nodes, mom, i); }
+  __device__ __forceinline__ void unused(int lane) const { if (lane < WIND_NODE_DOUBLES) mom[lane] = 0.0; }
+};
 
 // the solid angle of the triangle seen from q: 2 atan2(det, den), 0 where q lies in its plane
 __device__ __forceinline__ double wind_solid_angle(const double* q, const Tri& t) {
@@ -146,13 +139,13 @@ __global__ void __launch_bounds__(BVH_BLOCK) wind_query_kernel(const float* __re
                                                               int* __restrict__ visits) {
   const int64_t i = (int64_t)blockIdx.x * BVH_BLOCK + threadIdx.x;
   if (i >= n) return;
-  const float p[3] = {points[3 * i], points[3 * i + 1], points[3 * i + 2]};
-  if (!(isfinite(p[0]) && isfinite(p[1]) && isfinite(p[2]))) {
-    w[i] = __longlong_as_double(0x7FF8000000000000ll);
-    visits[2 * i] = 0;
-    visits[2 * i + 1] = 0;
+  float p[3];
+  if (!dist_point(points, i, p, [&] {
+        w[i] = __longlong_as_double(DIST_NAN64);
+        visits[2 * i] = 0;
+        visits[2 * i + 1] = 0;
+      }))
     return;
-  }
   const double q[3] = {(double)p[0], (double)p[1], (double)p[2]};
   double sum = 0.0;
   int exact = 0, approx = 0;
@@ -162,16 +155,12 @@ __global__ void __launch_bounds__(BVH_BLOCK) wind_query_kernel(const float* __re
     bool down = false;
     if (b[0] > b[3]) {                                               // an empty node: nothing below it
     } else if (node >= (uint32_t)P) {                                // a leaf: the exact term of each valid face
-      const int s0 = BVH_LEAF * (int)(node - (uint32_t)P);
-#pragma unroll
-      for (int k = 0; k < BVH_LEAF; ++k) {
-        const int f = s0 + k < F ? order[s0 + k] : -1;
-        if (f < 0) continue;
+      tree_leaf_faces(order, F, P, node, [&](int f) {
         Tri t;
         dist_load(verts, faces, f, t);
         sum += wind_solid_angle(q, t);
         ++exact;
-      }
+      });
     } else {                                                         // the dipole iff d^2 > beta^2 r^2, strictly
       const double* m = mom + (size_t)node * WIND_NODE_DOUBLES;
       const double d[3] = {m[WIND_C] - q[0], m[WIND_C + 1] - q[1], m[WIND_C + 2] - q[2]};
@@ -197,10 +186,6 @@ __global__ void __launch_bounds__(BVH_BLOCK) wind_query_kernel(const float* __re
   visits[2 * i + 1] = approx;
 }
 
-inline bool wind_aligned(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
-
-#define WIND_LAUNCH(what, kernel, blocks, ...) NERF_LAUNCH(what, kernel, blocks, BVH_BLOCK, st, __VA_ARGS__)
-
 }  // namespace
 }  // namespace nerf
 
@@ -210,41 +195,32 @@ extern "C" int64_t nerf_winding_workspace_bytes(int64_t F) { return wind_workspa
 
 extern "C" int nerf_winding_build(const float* verts, int64_t V, const int32_t* faces, int64_t F, const void* bvh_workspace,
                                   void* workspace, void* stream) {
-  const int rc = mesh_check("nerf_winding_build", V, F);
-  if (rc) return rc;
+  NERF_TRY(mesh_check("nerf_winding_build", V, F));
   if (F == 0) return NERF_OK;                                        // no face: the query finds the hierarchy's empty root
   NERF_REQUIRE(workspace && bvh_workspace && faces && verts, NERF_E_NULL, "nerf_winding_build: NULL pointer");
-  NERF_REQUIRE(wind_aligned(workspace) && wind_aligned(bvh_workspace), NERF_E_SHAPE,
-               "nerf_winding_build: the workspaces must start on a multiple of 16 bytes");
+  NERF_TRY(ws_aligned16_check("nerf_winding_build", workspace, bvh_workspace));
   const BvhWs b = bvh_ws(const_cast<void*>(bvh_workspace), F);
   const WindWs w = wind_ws(workspace, F);
   hipStream_t st = as_stream(stream);
-  WIND_LAUNCH("nerf_winding_build (leaves)", wind_leaves_kernel, blocks(w.P, BVH_BLOCK), verts, (int)V, faces, (int)F, (int)w.P,
+  DIST_LAUNCH("nerf_winding_build (leaves)", wind_leaves_kernel, blocks(w.P, BVH_BLOCK), verts, (int)V, faces, (int)F, (int)w.P,
               (const float*)b.nodes, (const int*)b.order, w.moments);
-  for (int l = w.depth - 1; l >= BVH_TOP_LEVELS; --l)
-    WIND_LAUNCH("nerf_winding_build (level)", wind_level_kernel, blocks(bvh_level_nodes(l), BVH_BLOCK), (const float*)b.nodes, w.moments,
-                (int)bvh_level_first(l));
-  WIND_LAUNCH("nerf_winding_build (top)", wind_top_kernel, 1, (const float*)b.nodes, w.moments,
-              (w.depth < BVH_TOP_LEVELS ? w.depth : BVH_TOP_LEVELS) - 1);
-  return NERF_OK;
+  return tree_reduce("nerf_winding_build (level)", "nerf_winding_build (top)", WindOp{b.nodes, w.moments}, w.depth, st);
 }
 
 extern "C" int nerf_winding_query(const float* points, int64_t n, const float* verts, int64_t V, const int32_t* faces, int64_t F,
                                   const void* bvh_workspace, const void* workspace, double beta, double* w, int32_t* visits,
                                   void* stream) {
-  const int rc = mesh_check("nerf_winding_query", V, F);
-  if (rc) return rc;
-  NERF_REQUIRE(n >= 0 && n <= WIND_MAX_POINTS, NERF_E_SHAPE, "nerf_winding_query: need 0 <= n <= 2^30 (got %lld)", (long long)n);
+  NERF_TRY(mesh_check("nerf_winding_query", V, F));
+  NERF_TRY(points_check("nerf_winding_query", n));
   NERF_REQUIRE(beta >= 1.0, NERF_E_SHAPE, "nerf_winding_query: need beta >= 1 or +inf (got %g)", beta);
   if (n == 0) return NERF_OK;
   NERF_REQUIRE(points && bvh_workspace && workspace && w && visits && (F == 0 || (verts && faces)), NERF_E_NULL,
                "nerf_winding_query: NULL pointer");
-  NERF_REQUIRE(wind_aligned(workspace) && wind_aligned(bvh_workspace), NERF_E_SHAPE,
-               "nerf_winding_query: the workspaces must start on a multiple of 16 bytes");
+  NERF_TRY(ws_aligned16_check("nerf_winding_query", workspace, bvh_workspace));
   const BvhWs b = bvh_ws(const_cast<void*>(bvh_workspace), F);
   const WindWs m = wind_ws(const_cast<void*>(workspace), F);
   hipStream_t st = as_stream(stream);
-  WIND_LAUNCH("nerf_winding_query", wind_query_kernel, blocks(n, BVH_BLOCK), points, n, verts, faces, (int)F, (int)m.P,
+  DIST_LAUNCH("nerf_winding_query", wind_query_kernel, blocks(n, BVH_BLOCK), points, n, verts, faces, (int)F, (int)m.P,
               (const float*)b.nodes, (const int*)b.order, (const double*)m.moments, beta * beta, w, visits);
   return NERF_OK;
 }

@@ -56,6 +56,34 @@ def _mark(mark, stage):
         mark(stage)
 
 
+def _rows(points) -> int:
+    """The rows of a [n, k] tensor; 0 for anything else, which the caller's need_tensor then refuses by name."""
+    return points.shape[0] if torch.is_tensor(points) and points.dim() == 2 else 0
+
+
+def _query_in_order(points, order, outs, run, mark=None):
+    """The shell of the point queries (MeshIndex, MeshBVH, MeshWinding): run(points, *outs) fills the empty tensors `outs`, one row
+    per point (stage "query").  With a permutation `order` (int64 [n], or a function of the points, computed inside stage "sort")
+    run gets the points in that order and the answers are scattered back, out[order] = value (stage "scatter").  Returns `outs`,
+    at once and without calling anything when there is no point."""
+    if points.shape[0] == 0:
+        return outs
+    if order is None:
+        _mark(mark, "query")
+        run(points, *outs)
+        return outs
+    _mark(mark, "sort")
+    if callable(order):
+        order = order(points)
+    points, sorted_outs = points[order].contiguous(), tuple(torch.empty_like(o) for o in outs)
+    _mark(mark, "query")
+    run(points, *sorted_outs)
+    _mark(mark, "scatter")
+    for o, s in zip(outs, sorted_outs):
+        o[order] = s
+    return outs
+
+
 def _check_mesh_tensors(who, mesh):
     """(V, F) of a Mesh whose tensors are contiguous verts float32 [V, 3], faces int32 [F, 3], normals float32 [V, 3] and colors
     None or float32 [V, 3] on one device, with V, F <= 2^24; ValueError otherwise (check_simplify_args, check_smooth_args,

@@ -19,7 +19,7 @@ from typing import NamedTuple, Optional, Sequence
 import torch
 
 from ... import _native as N
-from ._base import Mesh, _box, _check_mesh_tensors, _mark, check_mesh_args
+from ._base import Mesh, _box, _check_mesh_tensors, _mark, _query_in_order, _rows, check_mesh_args
 from ._checks import need_int, need_real, need_tensor
 
 DISTANCE_MAX_GRID = 256
@@ -125,29 +125,13 @@ class MeshIndex:
         with a non-finite coordinate, +inf and -1 when the mesh has no valid face (nerf_meshdist_query: no host read, any number
         of calls per index).  `sort`: query in cell-sorted order and scatter back, the same bits (None: DISTANCE_SORTED_QUERY).
         mark: _mark's hook ("sort", "query")."""
-        n = points.shape[0] if torch.is_tensor(points) and points.dim() == 2 else 0
+        n = _rows(points)
         check_distance_args(self.mesh, n, self.lo, self.hi, points=points)
-        dev = points.device
-        dist2 = torch.empty(n, dtype=torch.float32, device=dev)
-        face = torch.empty(n, dtype=torch.int32, device=dev)
-        if n == 0:
-            return dist2, face
+        outs = (torch.empty(n, dtype=torch.float32, device=points.device), torch.empty(n, dtype=torch.int32, device=points.device))
         sort = DISTANCE_SORTED_QUERY if sort is None else bool(sort)
-        order = None
-        if sort and self.grid > 1:
-            _mark(mark, "sort")
-            order = self._cell_order(points)
-            points = points[order].contiguous()
-        m = self.mesh
-        _mark(mark, "query")
-        N.check(N.lib().nerf_meshdist_query(N.ptr(points), n, N.ptr(m.verts), self.V, N.ptr(m.faces), self.F, *self._box, self.grid,
-                                            N.ptr(self._ws), N.ptr(self._ent), self.entries, N.ptr(dist2), N.ptr(face), N.stream()))
-        if order is not None:
-            _mark(mark, "scatter")
-            d, f = torch.empty_like(dist2), torch.empty_like(face)
-            d[order], f[order] = dist2, face
-            dist2, face = d, f
-        return dist2, face
+        return _query_in_order(points, self._cell_order if sort and self.grid > 1 else None, outs, lambda p, dist2, face: N.check(
+            N.lib().nerf_meshdist_query(N.ptr(p), n, N.ptr(self.mesh.verts), self.V, N.ptr(self.mesh.faces), self.F, *self._box, self.grid,
+                                        N.ptr(self._ws), N.ptr(self._ent), self.entries, N.ptr(dist2), N.ptr(face), N.stream())), mark)
 
 
 BVH_SORTED_QUERY = True           # query in Morton order of the points (measured 1.4 - 1.9 times faster: DESIGN.md section 38)
@@ -166,6 +150,11 @@ def _morton_codes(points, lo, hi):
     c = (c | (c << 4)) & 0x00000030C30C30C3
     c = (c | (c << 2)) & 0x0000009249249249
     return c[:, 0] | (c[:, 1] << 1) | (c[:, 2] << 2)
+
+
+def _morton_order(lo, hi):
+    """points -> the permutation that sorts them by their Morton codes on the box: the `order` of _query_in_order."""
+    return lambda points: torch.sort(_morton_codes(points, lo, hi)).indices
 
 
 class MeshBVH:
@@ -208,29 +197,13 @@ class MeshBVH:
         """(dist2 float32 [n], face int32 [n]) of points [n, 3]: MeshIndex.query's contract and its bits (nerf_bvh_query: no host
         read, any number of calls per index).  `sort`: query the points in the order of their own 36-bit Morton codes and scatter
         the answers back, the same bits (None: BVH_SORTED_QUERY).  mark: _mark's hook ("sort", "query", "scatter")."""
-        n = points.shape[0] if torch.is_tensor(points) and points.dim() == 2 else 0
+        n = _rows(points)
         check_distance_args(self.mesh, n, self.lo, self.hi, points=points)
-        dev = points.device
-        dist2 = torch.empty(n, dtype=torch.float32, device=dev)
-        face = torch.empty(n, dtype=torch.int32, device=dev)
-        if n == 0:
-            return dist2, face
+        outs = (torch.empty(n, dtype=torch.float32, device=points.device), torch.empty(n, dtype=torch.int32, device=points.device))
         sort = BVH_SORTED_QUERY if sort is None else bool(sort)
-        order = None
-        if sort:
-            _mark(mark, "sort")
-            order = torch.sort(_morton_codes(points, self.lo, self.hi)).indices
-            points = points[order].contiguous()
-        m = self.mesh
-        _mark(mark, "query")
-        N.check(N.lib().nerf_bvh_query(N.ptr(points), n, N.ptr(m.verts), self.V, N.ptr(m.faces), self.F, *self._box, N.ptr(self._ws),
-                                       N.ptr(dist2), N.ptr(face), N.stream()))
-        if order is not None:
-            _mark(mark, "scatter")
-            d, f = torch.empty_like(dist2), torch.empty_like(face)
-            d[order], f[order] = dist2, face
-            dist2, face = d, f
-        return dist2, face
+        return _query_in_order(points, _morton_order(self.lo, self.hi) if sort else None, outs, lambda p, dist2, face: N.check(
+            N.lib().nerf_bvh_query(N.ptr(p), n, N.ptr(self.mesh.verts), self.V, N.ptr(self.mesh.faces), self.F, *self._box, N.ptr(self._ws),
+                                   N.ptr(dist2), N.ptr(face), N.stream())), mark)
 
 
 def check_distance_index(index) -> str:
@@ -259,7 +232,7 @@ def closest_points(mesh: Mesh, points: torch.Tensor, face: torch.Tensor):
     invalid (nerf_closest_points: one lane per point, no index needed)."""
     _check_mesh_tensors("distance", mesh)
     dev = mesh.verts.device
-    n = points.shape[0] if torch.is_tensor(points) and points.dim() == 2 else 0
+    n = _rows(points)
     need_tensor(points, "distance: points", torch.float32, (n, 3), dev, "[n, 3]")
     need_tensor(face, "distance: face", torch.int32, (n,), dev, "[n]")
     if n > DISTANCE_MAX_SAMPLES:

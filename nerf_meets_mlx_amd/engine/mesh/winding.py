@@ -17,9 +17,9 @@ from typing import Optional
 import torch
 
 from ... import _native as N
-from ._base import CHUNK, Mesh, _check_mesh_tensors, _clamped, _mark, check_mesh_args
+from ._base import CHUNK, Mesh, _check_mesh_tensors, _clamped, _mark, _query_in_order, check_mesh_args
 from ._checks import is_number, need_tensor
-from .distance import BVH_SORTED_QUERY, DISTANCE_MAX_SAMPLES, MeshBVH, _index, _morton_codes, check_distance_index
+from .distance import BVH_SORTED_QUERY, DISTANCE_MAX_SAMPLES, MeshBVH, _index, _morton_order, check_distance_index
 from .volume import _rows_into, check_volume_options, filter_volume, marching_cubes
 
 WINDING_NODE_DOUBLES = 12         # N [0:3], c [3:6], r [6], A [7], S [8:11], 0
@@ -76,26 +76,11 @@ class MeshWinding:
         order, the same bits back (None: BVH_SORTED_QUERY).  mark: _mark's hook ("sort", "query", "scatter")."""
         beta, _, _, _ = check_winding_args(self.mesh, self.lo, self.hi, beta, points=points)
         n, dev = points.shape[0], points.device
-        w = torch.empty(n, dtype=torch.float64, device=dev)
-        visits = torch.empty(n, 2, dtype=torch.int32, device=dev)
-        if n == 0:
-            return w, visits
+        outs = (torch.empty(n, dtype=torch.float64, device=dev), torch.empty(n, 2, dtype=torch.int32, device=dev))
         sort = BVH_SORTED_QUERY if sort is None else bool(sort)
-        order = None
-        if sort:
-            _mark(mark, "sort")
-            order = torch.sort(_morton_codes(points, self.lo, self.hi)).indices
-            points = points[order].contiguous()
-        m = self.mesh
-        _mark(mark, "query")
-        N.check(N.lib().nerf_winding_query(N.ptr(points), n, N.ptr(m.verts), self.V, N.ptr(m.faces), self.F, N.ptr(self.bvh._ws),
-                                           N.ptr(self._ws), beta, N.ptr(w), N.ptr(visits), N.stream()))
-        if order is not None:
-            _mark(mark, "scatter")
-            ww, vv = torch.empty_like(w), torch.empty_like(visits)
-            ww[order], vv[order] = w, visits
-            w, visits = ww, vv
-        return w, visits
+        return _query_in_order(points, _morton_order(self.lo, self.hi) if sort else None, outs, lambda p, w, visits: N.check(
+            N.lib().nerf_winding_query(N.ptr(p), n, N.ptr(self.mesh.verts), self.V, N.ptr(self.mesh.faces), self.F, N.ptr(self.bvh._ws),
+                                       N.ptr(self._ws), beta, N.ptr(w), N.ptr(visits), N.stream())), mark)
 
 
 def winding_number(points: torch.Tensor, mesh: Mesh, lo, hi, beta=2.0):

@@ -104,9 +104,9 @@ def test_morton_codes_interleave_x_lowest():
     lo, hi = D.LO, D.HI
     c = B.cells_of(np.array([lo, hi, [(l + h) / 2 for l, h in zip(lo, hi)], [l - 5 for l in lo], [h + 5 for h in hi]]), lo, hi)
     assert c.tolist() == [[0] * 3, [4095] * 3, [2048] * 3, [0] * 3, [4095] * 3]
-    assert [B.tree_shape(F) for F in (0, 1, 3, 4, 5, 8, 9, 17, 4064, 1 << 24)] == \
+    assert [B.tree_shape(F) for F in (0, 1, 3, 4, 5, 8, 9, 17, 4064, 8128, 1 << 24)] == \
         [(0, 1, 0, 2), (1, 1, 0, 2), (1, 1, 0, 2), (1, 1, 0, 2), (2, 2, 1, 2), (2, 2, 1, 2), (3, 4, 2, 2), (5, 8, 3, 2),
-         (1016, 1024, 10, 3), (1 << 22, 1 << 22, 22, 15)]
+         (1016, 1024, 10, 3), (2032, 2048, 11, 4), (1 << 22, 1 << 22, 22, 15)]
 
 
 @pytest.mark.parametrize("name", sorted(D.MESHES))
@@ -282,19 +282,27 @@ def test_header_section_bindings_and_makefile():
     srcs = next(ln for ln in mk.splitlines() if ln.startswith("SRCS"))
     hdrs = next(ln for ln in mk.splitlines() if ln.startswith("HDRS"))
     assert "bvh.hip" in srcs.split() and "distance.hip" in srcs.split()
-    assert "distance.h" in hdrs.split() and "bvh_ws.h" in hdrs.split()
+    assert "distance.h" in hdrs.split() and "bvh_ws.h" in hdrs.split() and "bvh_tree.h" in hdrs.split()
     assert not re.search(r"FLAGS_bvh", mk)                                               # the default flags, -ffp-contract=off among them
     src = open(os.path.join(csrc, "bvh.hip")).read()
     kernels = sorted(set(re.findall(r"\b(\w+_kernel)\(", src)))
-    assert kernels == ["bvh_closest_kernel", "bvh_keys_kernel", "bvh_leaves_kernel", "bvh_level_kernel", "bvh_query_kernel",
-                       "bvh_top_kernel"]
+    assert kernels == ["bvh_closest_kernel", "bvh_keys_kernel", "bvh_leaves_kernel", "bvh_query_kernel"]
     assert not re.search(r"\batomic\w*\(", src) and "__shared__" not in src                # no atomics at all, no LDS
+    # the bottom-up pass is written once, in bvh_tree.h (a barrier between the top levels, no LDS), for both units on the tree
+    tree = open(os.path.join(csrc, "bvh_tree.h")).read()
+    wind = open(os.path.join(csrc, "winding.hip")).read()
+    assert sorted(set(re.findall(r"\b(\w+_kernel)\(", tree))) == ["tree_level_kernel", "tree_top_kernel"]
+    for name in ("tree_level_kernel", "tree_top_kernel"):
+        assert len(re.findall(r"\b" + name + r"\(", tree)) == 1 and name not in src and name not in wind, name
+    assert not re.search(r"\batomic\w*\(", tree) and "__shared__" not in tree and tree.count("__syncthreads()") == 1
+    assert '#include "bvh_tree.h"' in src and '#include "bvh_tree.h"' in wind
     # the shared device code lives in one place, and distance.hip still has its eight kernels
     shared = open(os.path.join(csrc, "distance.h")).read()
     dist = open(os.path.join(csrc, "distance.hip")).read()
-    for name in ("dist_face", "dist_load", "point_triangle_closest", "point_triangle_d2", "dist_fold", "DIST_NONE"):
-        define = re.compile(r"(?:inline__|constexpr)\s+\w+\s+" + name + r"\b")
-        assert len(define.findall(shared)) == 1 and not define.search(dist), name
+    for name in ("dist_face", "dist_load", "point_triangle_closest", "point_triangle_d2", "dist_fold", "DIST_NONE", "dist_point",
+                 "dist_stop", "box_abs", "points_check"):
+        define = re.compile(r"(?:inline(?:__)?|constexpr)\s+\w+\s+" + name + r"\b")
+        assert len(define.findall(shared)) == 1 and not define.search(dist) and not define.search(src) and not define.search(wind), name
     assert '#include "distance.h"' in dist and '#include "distance.h"' in src
     dk = sorted(set(re.findall(r"\b(\w+_kernel)\(", dist)))
     assert len(dk) == 8 and all(k.startswith("dist_") for k in dk)

@@ -44,12 +44,14 @@ def _points(v, f, n=257, seed=5):
 MESHES = dict(D.MESHES)
 MESHES.update({f"small{F}": functools.partial(B.small, F) for F in (0, 1, 3, 4, 5, 8, 9, 17)})
 MESHES.update({"all_invalid": B.all_invalid, "doubled": B.doubled})
+# for the build alone: 8128 faces, depth 11, so two per-level launches run (the mirror's exact walk would take too long in a query test)
+BUILD_MESHES = dict(MESHES, doubled_sphere24=functools.partial(B.doubled, "sphere24"))
 
 
 @functools.lru_cache(maxsize=None)
 def _case(name):
     """(verts, faces, points, dist2, face of the brute force): computed once, shared, read-only."""
-    v, f = MESHES[name]()
+    v, f = BUILD_MESHES[name]()
     v, f = np.asarray(v, np.float32).reshape(-1, 3), np.asarray(f, np.int32).reshape(-1, 3)
     pts = _points(v, f) if len(v) else np.concatenate([D.query_points(D.cube()[0], D.cube()[1], 257, 5), B.far_points()])
     d2, fc = D.brute_force(pts, v, f)
@@ -138,10 +140,13 @@ def test_query_matches_the_brute_force_bit_for_bit(name):
         assert (fc[fin] < len(f) // 2).all()
 
 
-@pytest.mark.parametrize("name", ["sphere24", "junk", "spanning", "outside", "small5", "small17", "small0", "all_invalid"])
+@pytest.mark.parametrize("name", ["sphere24", "junk", "spanning", "outside", "small5", "small17", "small0", "all_invalid",
+                                  "doubled_sphere24"])
 def test_keys_order_and_nodes_match_the_mirror_bit_for_bit(name):
     v, f, _, _, _ = _case(name)
     t = _Tree(v, f, BIG_BYTES)
+    if name == "doubled_sphere24":
+        assert (t.nL, t.P, t.depth, t.launches) == (2032, 2048, 11, 4)
     assert np.array_equal(t.keys, B.keys(v, f, D.LO, D.HI))
     assert np.array_equal(t.order, B.order(v, f, D.LO, D.HI))
     assert np.array_equal(_bits(t.nodes), _bits(B.nodes(v, f, D.LO, D.HI)))

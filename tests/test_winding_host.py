@@ -332,12 +332,17 @@ def test_header_section_bindings_and_makefile():
     srcs = next(ln for ln in mk.splitlines() if ln.startswith("SRCS"))
     hdrs = next(ln for ln in mk.splitlines() if ln.startswith("HDRS"))
     assert "winding.hip" in srcs.split() and "bvh.hip" in srcs.split()
-    assert "winding_ws.h" in hdrs.split() and "bvh_ws.h" in hdrs.split() and "distance.h" in hdrs.split()
+    assert "winding_ws.h" in hdrs.split() and "bvh_ws.h" in hdrs.split() and "distance.h" in hdrs.split() and "bvh_tree.h" in hdrs.split()
     assert not re.search(r"FLAGS_winding", mk)                                            # the default flags, -ffp-contract=off among them
     src = open(os.path.join(csrc, "winding.hip")).read()
     kernels = sorted(set(re.findall(r"\b(\w+_kernel)\(", src)))
-    assert kernels == ["wind_leaves_kernel", "wind_level_kernel", "wind_query_kernel", "wind_top_kernel"]
+    assert kernels == ["wind_leaves_kernel", "wind_query_kernel"]
     assert not re.search(r"\batomic\w*\(", src) and "__shared__" not in src                # no atomics at all, no LDS
+    # the level and top kernels are the hierarchy's, written once in bvh_tree.h and held to the same two assertions
+    tree = open(os.path.join(csrc, "bvh_tree.h")).read()
+    assert '#include "bvh_tree.h"' in src and "tree_reduce(" in src and "tree_level_kernel" not in src and "tree_top_kernel" not in src
+    assert sorted(set(re.findall(r"\b(\w+_kernel)\(", tree))) == ["tree_level_kernel", "tree_top_kernel"]
+    assert not re.search(r"\batomic\w*\(", tree) and "__shared__" not in tree
     assert '#include "distance.h"' in src and '#include "bvh_ws.h"' in open(os.path.join(csrc, "winding_ws.h")).read()
     assert "dist_face(" in src and "dist_load(" in src
     ws = open(os.path.join(csrc, "winding_ws.h")).read()
