@@ -1019,7 +1019,7 @@ int nerf_meshdist_query(const float* points, int64_t n, const float* verts, int6
  * Out of range (V, F outside [0, 2^24], n outside [0, 2^30], lo >= hi or a non-finite corner, a misaligned workspace):
  * NERF_E_SHAPE; NULL: NERF_E_NULL; all argument checks run before any device work.
  * Not done: no surface-area-heuristic or Karras (longest-common-prefix) splits -- the tree is the implicit median split of the
- * Morton order; no signed distance; no ray casting.                                                                               */
+ * Morton order; no signed distance; no ray casting (see mesh ray casting).                                                        */
 int64_t nerf_bvh_workspace_bytes(int64_t F);
 int nerf_bvh_keys(const float* verts, int64_t V, const int32_t* faces, int64_t F, const float* lo_host, const float* hi_host,
                   int64_t* keys, void* stream);
@@ -1071,12 +1071,96 @@ int nerf_closest_points(const float* points, int64_t n, const float* verts, int6
  * Out of range (V, F outside [0, 2^24], n outside [0, 2^30], a beta that is NaN or below 1, a misaligned workspace):
  * NERF_E_SHAPE; NULL: NERF_E_NULL; all argument checks run before any device work.
  * Not done: no quadrupole or higher terms (the dipole's error at beta = 2 is about 0.015 of a turn); no narrow band, so every
- * lattice point of a volume is evaluated; no culling of faces that lie inside the solid; still no ray casting.                    */
+ * lattice point of a volume is evaluated; no culling of faces that lie inside the solid; still no ray casting (see
+ * mesh ray casting).                                                                                                              */
 int64_t nerf_winding_workspace_bytes(int64_t F);
 int nerf_winding_build(const float* verts, int64_t V, const int32_t* faces, int64_t F, const void* bvh_workspace, void* workspace,
                        void* stream);
 int nerf_winding_query(const float* points, int64_t n, const float* verts, int64_t V, const int32_t* faces, int64_t F,
                        const void* bvh_workspace, const void* workspace, double beta, double* w, int32_t* visits, void* stream);
+
+/* ---------------------------------------------------------------- mesh ray casting (no reference counterpart)
+ * Where a ray meets a mesh: the nearest hit, or whether there is one, on the hierarchy of "mesh BVH".  The rays are the rows
+ * nerf_ray_gen writes for the field, unchanged: rays [n, NERF_RAY_STRIDE] float32 with o in columns 0-2, d in 3-5 (not normalised:
+ * t counts in units of d), tmin in 6, tmax in 7; columns 8-10 are not read.  It changes no mesh.  Additive: NERF_ABI_VERSION stays 3.
+ * All arithmetic of the face test and of the box test is IEEE double on the float32 corners and rays, one rounding per operation
+ * (no contraction), in exactly the order written here; a / b is correctly rounded, and so are the casts to float32.
+ * tests/_raycast_ref.py follows it operator for operator.  Validity of a face is that of "mesh distance".
+ *   ray       valid iff o and d are finite, d != 0, tmin and tmax are not NaN and tmin >= 0 (tmax = +inf is allowed).  Any other
+ *             ray answers t = NaN (0x7FC00000), face = -1, bary = (NaN, NaN), visits = (0, 0), hit = 0.  tmin > tmax is a valid ray
+ *             that misses.
+ *   frame     (Woop, Benthin and Wald 2013) kz is the axis of the largest |d_a|, the lowest axis on a tie; kx = (kz + 1) mod 3 and
+ *             ky = (kx + 1) mod 3, swapped if d[kz] < 0.  Sx = d[kx] / d[kz], Sy = d[ky] / d[kz], Sz = 1 / d[kz].
+ *   face      for the corners a, b, c: A = a - o per component; Ax = A[kx] - Sx A[kz], Ay = A[ky] - Sy A[kz], Az = Sz A[kz]; B and
+ *             C alike.  U = Cx By - Cy Bx, V = Ax Cy - Ay Cx, W = Bx Ay - By Ax.  The ray misses the face if one of U, V, W is < 0
+ *             while another is > 0 (zeros are inclusive).  det = (U + V) + W; det == 0 misses.  t64 = ((U Az + V Bz) + W Cz) / det;
+ *             t = (float)t64 + 0.0f (a -0 becomes +0); the hit is accepted iff tmin <= t and t <= tmax, compared in float32.
+ *             bary = ((float)(V / det), (float)(W / det)): the weights of the second and third corner, as "mesh rendering" and
+ *             nerf_texture_sample take them.
+ *   edges     the edge function of the edge (p, q) is px qy - py qx up to its sign, whatever face it is computed for and in
+ *             whichever order the face lists p and q: the same two products (a product does not depend on the order of its
+ *             factors), subtracted one way or the other, so the two faces that share an edge get values that are exact negatives
+ *             of each other.  A ray that passes through the shared edge of two faces of a closed, consistently oriented surface
+ *             therefore sees 0 in both, or a value on the inner side of one of them: no ray slips between them.
+ *   result    nerf_raycast answers the minimum over all valid faces of the key (bits of t) 2^32 + f among the accepted hits: the
+ *             nearest hit, the lowest face index on equal t.  t [n] float32, face [n] int32, bary [n, 2] float32 of that face,
+ *             visits [n, 2] int32 = (faces tested, boxes tested).  A miss: (+inf, -1, NaN, NaN).  Neither the order of the walk
+ *             nor the shape of the tree enters t, face or bary; visits is a function of the tree and the ray alone.
+ *             nerf_raycast_any answers hit [n] uint8 = 1 iff nerf_raycast would answer face >= 0; its walk stops at the first
+ *             accepted hit.
+ *   walk      that of "mesh BVH", query: one lane per ray, stackless, the node index and one 32-bit trail word.  At an internal
+ *             node both children are read (three 16-byte words) and tested; of two that stay, the one whose entry parameter is
+ *             smaller is entered first (the left one on a tie) and the other is marked pending; going up, the lane pops to the
+ *             lowest set bit k, the pending sibling is (node >> k) ^ 1, and it is tested again, for the best hit may have come
+ *             nearer.  A leaf tests each of its valid faces in sorted order.  boxes tested counts the root (once), two per
+ *             internal node entered and one per pop; faces tested counts the face tests.
+ *   box       S is the largest |coordinate| among the ray's origin, the root box and the box [lo, hi]; eta = 2^-30 S.  A node
+ *             (min, max) is widened to lo_a = (double)min_a - eta, hi_a = (double)max_a + eta.  Per axis with d_a != 0:
+ *             inv_a = 1 / d_a, t0 = (lo_a - o_a) inv_a, t1 = (hi_a - o_a) inv_a, swapped if inv_a < 0; enter = the largest t0,
+ *             exit = the smallest t1 (starting from -inf and +inf).  An axis with d_a == 0 has no parameters (no 0 inf is ever
+ *             formed): it only asks whether lo_a <= o_a <= hi_a.  The line meets the widened box iff every such axis says yes and
+ *             enter <= exit.
+ *   rule      a node is skipped only if it is empty (min > max), or the line does not meet its widened box, or
+ *             (float)exit < tmin, or (float)enter > tmax, or (float)enter is strictly greater than the best t.  On equality
+ *             with the best t the node is entered: a lower face index may still tie.
+ *   proof     Let a face below the node be accepted with U, V, W >= 0 (or all <= 0) and det != 0.  (1) Along kz: rounding is
+ *             monotone, so Az = fl(Sz fl(a_kz - o_kz)) lies, for every corner, between the node's own t0 and t1 of that axis
+ *             (the same two operations on min_kz - eta and max_kz + eta, and inv_kz is Sz).  The products U Az, V Bz, W Cz have
+ *             weights of one sign, so t64 is a convex combination of Az, Bz, Cz up to five roundings: |t64 - c| <= 2^-49 M with
+ *             M = max |Az, Bz, Cz| <= 2 S |Sz|, while the widening moved t0 and t1 outward by eta |Sz| = 2^-30 S |Sz|, 2^18 times
+ *             as much.  So t0 <= t64 <= t1 on the axis kz whatever the shape of the face.  (2) Across: U A' + V B' + W C' = 0 holds
+ *             exactly for the exact edge functions of the sheared corners A' = (Ax, Ay), ..., so with the computed ones, each
+ *             within 2^-51 R^2 of exact (two products and a difference of numbers below R^2, R <= 4 S the largest sheared
+ *             coordinate, |Sx|, |Sy| <= 1), the sheared origin lies inside the sheared triangle or outside it by no more than
+ *             2^-48 R, unless the three sheared corners are themselves collinear with the origin to that relative precision (see
+ *             Not done).  The sheared coordinates of a point are its offsets from the ray's point of the same kz, so the ray
+ *             passes within 2^-46 S of a point P of the face at the parameter c, and P lies in every ancestor's box.  With (1),
+ *             the ray's point at t64 is within 2^-45 S of the box on every axis; each computed t0, t1 is the exact parameter of
+ *             a plane moved by at most 2^-50 S (two roundings of numbers below 2 S); together far inside eta.  Hence
+ *             enter <= t64 <= exit as computed, and, the cast to float32 being monotone (and + 0.0f changing no order),
+ *             (float)enter <= t <= (float)exit.  A node skipped by the rule has (float)enter > min(tmax, best t) or
+ *             (float)exit < tmin, so no face below it can be accepted with a key at or below the best.  tests/_raycast_ref.py
+ *             emulates the walk and holds it to the scan over every face bit for bit.
+ * Calls:
+ *   nerf_raycast           t [n], face [n], bary [n, 2], visits [n, 2] of a chunk of rays [n, 11]; the mesh and the box of the
+ *                          build (the box enters S only); bvh_workspace: what nerf_bvh_build wrote for this mesh.  One lane per
+ *                          ray; no atomics, no LDS, no scratch, no host read, no workgroup waits for another.  The workspace is
+ *                          only read and there is no other: one build serves any number of chunks, and no result depends on the
+ *                          chunking or the launch shape.  n = 0: nothing is launched.
+ *   nerf_raycast_any       hit [n] uint8 of the same arguments.  n = 0: nothing is launched.
+ * One writer per output element: bit-reproducible; under a renumbering of the faces t and bary are unchanged where the nearest
+ * hit is on one face only, and face follows the renumbering.
+ * Out of range (V, F outside [0, 2^24], n outside [0, 2^30], lo >= hi or a non-finite corner, a misaligned workspace):
+ * NERF_E_SHAPE; NULL: NERF_E_NULL; all argument checks run before any device work.
+ * Not done: no all-hits or parity counting (an inside test by crossings: "mesh winding number" is the inside test); no agreement
+ * with the rasteriser that is exact at the near plane (a face that crosses it is cut here and dropped there) or at silhouettes
+ * (it snaps to 1/256 pixel); no packet or wave-cooperative traversal (one lane per ray, divergent lanes wait for each other); no
+ * better splits than the Morton median; a face that the ray sees exactly edge-on to double precision, its sheared corners
+ * collinear with the ray, is outside the proof of the rule (exactly edge-on it has det == 0 and misses).                          */
+int nerf_raycast(const float* rays, int64_t n, const float* verts, int64_t V, const int32_t* faces, int64_t F, const float* lo_host,
+                 const float* hi_host, const void* bvh_workspace, float* t, int32_t* face, float* bary, int32_t* visits, void* stream);
+int nerf_raycast_any(const float* rays, int64_t n, const float* verts, int64_t V, const int32_t* faces, int64_t F,
+                     const float* lo_host, const float* hi_host, const void* bvh_workspace, uint8_t* hit, void* stream);
 
 /* ---------------------------------------------------------------- texture atlas (no reference counterpart)
  * A texture for a finished mesh, baked by one field query per texel: a simplified mesh then carries the field's appearance at

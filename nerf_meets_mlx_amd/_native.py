@@ -152,6 +152,8 @@ SIGNATURES = {
     "nerf_winding_workspace_bytes": (_I64, [_I64]),
     "nerf_winding_build": (_I, [_P, _I64, _P, _I64, _P, _P, _P]),
     "nerf_winding_query": (_I, [_P, _I64, _P, _I64, _P, _I64, _P, _P, C.c_double, _P, _P, _P]),
+    "nerf_raycast": (_I, [_P, _I64, _P, _I64, _P, _I64, C.POINTER(C.c_float), C.POINTER(C.c_float), _P, _P, _P, _P, _P, _P]),
+    "nerf_raycast_any": (_I, [_P, _I64, _P, _I64, _P, _I64, C.POINTER(C.c_float), C.POINTER(C.c_float), _P, _P, _P]),
 }
 
 

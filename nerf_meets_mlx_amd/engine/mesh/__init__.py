@@ -8,7 +8,9 @@ is Instant-NGP's.  One module per stage, and every name of theirs is a name of t
   (project_texture); texture <- files (PLY, OBJ, PNG); _base <- distance (sample_surface, MeshIndex, mesh_distance).
   distance also holds the second index, MeshBVH (a bounding-volume hierarchy with the grid's answers bit for bit), and
   closest_points.  distance <- volume <- winding (MeshWinding, winding_number, winding_volume, remesh, signed_distance): the
-  generalized winding number on MeshBVH's tree, the inside test the distance lacks."""
+  generalized winding number on MeshBVH's tree, the inside test the distance lacks.  distance, raster <- raycast (MeshRaycast,
+  pack_rays, raycast_frame, render_mesh_rays): nearest hit and occlusion of rays on the same tree, and the rasteriser's frame by
+  rays."""
 from ._base import CHUNK, MAX_RES, SIMPLIFY_MAX_ITEMS, Mesh, _box, _check_mesh_tensors, _mark, check_mesh_args
 from .distance import (DISTANCE_INDEXES, DISTANCE_MAX_ENTRIES, DISTANCE_MAX_GRID, DISTANCE_MAX_SAMPLES, DistanceStats, MeshBVH,
                        MeshDistance, MeshIndex, check_distance_args, check_distance_index, closest_points, default_distance_grid,
@@ -17,6 +19,8 @@ from .files import _PNG_MAGIC, _png_chunk, _replace_file, png_array, png_bytes, 
 from .project import PROJECT_COS_MIN, PROJECT_DEPTH_TOL_CELLS, PROJECT_MAX_VIEWS, PROJECT_MODES, check_project_args, project_texture
 from .raster import (RASTER_MAX_SIDE, RASTER_NEAR, RASTER_SMALL_MAX, MeshFrame, _raster_background, _raster_view, check_lod_scale,
                      check_raster_args, face_lod, rasterize, render_mesh, render_mesh_mip)
+from .raycast import (RAY_STRIDE, RAYCAST_SLACK, RAYCAST_SORTED_QUERY, MeshRaycast, RayHits, check_raycast_args, pack_rays,
+                      raycast_frame, render_mesh_rays)
 from .surface import (PLACEMENTS, SIMPLIFY_MAX_CLUSTERS, SMOOTH_MAX_ITERATIONS, _simplify, _smooth, check_simplify_args,
                       check_simplify_grid, check_smooth_args, check_smooth_params, check_surface_options, simplify, smooth)
 from .texture import (MIP_MAX_LEVELS, TEXTURE_MAX_SIDE, TEXTURE_MAX_TEXELS, Texture, TexturePyramid, _check_pyramid, _check_texture,

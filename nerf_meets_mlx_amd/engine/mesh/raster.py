@@ -119,16 +119,20 @@ def face_lod(mesh: Mesh, c2w, K, near: float = RASTER_NEAR, texels: int = 8, sca
     return lod
 
 
-def _render(who, mesh, c2w, K, H, W, prepare, background, near, cull_backfaces, mark, small_max) -> MeshFrame:
-    """The body of render_mesh and render_mesh_mip.  prepare(): the caller's own checks, made between the raster arguments and the
-    background; it returns None for the vertex colours or lookup(face [H W], bary [H W, 2], near) -> rgb [H W, 3], which is called
-    behind rasterize when there are faces and calls `mark` for its own stages."""
+def _render(who, mesh, c2w, K, H, W, prepare, background, near, cull_backfaces, mark, small_max, visibility=None) -> MeshFrame:
+    """The body of render_mesh, render_mesh_mip and render_mesh_rays.  prepare(): the caller's own checks, made between the raster
+    arguments and the background; it returns None for the vertex colours or lookup(face [H W], bary [H W, 2], near) -> rgb [H W, 3],
+    which is called behind rasterize when there are faces and calls `mark` for its own stages.  visibility(near) -> (face, bary,
+    depth, acc, ...) stands in for rasterize (raycast.py's raycast_frame); None: rasterize."""
     _check_mesh_tensors(who, mesh)
     H, W, near, cull_backfaces, small_max = check_raster_args(H, W, near, cull_backfaces, small_max)
     lookup = prepare()
     dev, V, F = mesh.verts.device, mesh.verts.shape[0], mesh.faces.shape[0]
     bg, per_pixel = _raster_background(background, H, W, dev)
-    face, bary, depth, acc, _ = rasterize(mesh, c2w, K, H, W, near, cull_backfaces, mark, small_max)
+    if visibility is None:
+        face, bary, depth, acc, _ = rasterize(mesh, c2w, K, H, W, near, cull_backfaces, mark, small_max)
+    else:
+        face, bary, depth, acc, _ = visibility(near)
     if F == 0:
         rgb = (bg.reshape(H, W, 3) if per_pixel else bg.expand(H, W, 3)).clone()
         return MeshFrame(rgb, depth, acc, face, bary)

@@ -459,6 +459,29 @@ class NGPTrainer(Trainer):
         o = self.render_rays(rays, aux=True)
         return o["depth"].reshape(self.H, self.W), o["acc"].reshape(self.H, self.W)
 
+    def mesh_depth_error(self, mesh, c2w, acc_min: float = 0.5, resolution: int = 256, aabb=None) -> dict:
+        """A mesh against the field it came from, ray for ray over the frame at pose c2w: engine.mesh.raycast_frame along the rays
+        render_depth renders (near, far, K as the trainer's) against render_depth's depth / acc where acc >= `acc_min`.  Returns
+        {"mean", "rms"}: the mean and root-mean-square |mesh depth - field depth| over the pixels where both see a surface, in
+        units of h = the longest side of the scene box (`aabb` as in extract_mesh) / `resolution`, NaN when there is no such
+        pixel; {"both", "mesh_only", "field_only", "neither"}: the shares of the frame's pixels, which sum to 1; and "h".
+        This rank only, no collective."""
+        from . import mesh as M
+        lo, hi = self._mesh_box(aabb)
+        R = M.check_mesh_args(resolution, lo, hi)[0]
+        if not isinstance(acc_min, (int, float)) or isinstance(acc_min, bool) or not 0.0 < float(acc_min) <= 1.0:
+            raise ValueError(f"mesh_depth_error: acc_min must be a number in (0, 1], got {acc_min!r}")
+        h = max(b - a for a, b in zip(lo, hi)) / R
+        _, _, m_depth, m_acc, _ = M.raycast_frame(mesh, c2w, self.K, self.H, self.W, near=float(self.near), far=float(self.far))
+        f_depth, f_acc = self.render_depth(c2w)
+        seen_m, seen_f = m_acc > 0, f_acc >= float(acc_min)
+        both = seen_m & seen_f
+        n, nb = float(seen_m.numel()), int(both.sum())
+        diff = (m_depth.double() - f_depth.double() / f_acc.double().clamp_min(1e-12))[both].abs() / h
+        return {"mean": float(diff.mean()) if nb else float("nan"), "rms": float(diff.pow(2).mean().sqrt()) if nb else float("nan"),
+                "both": nb / n, "mesh_only": int((seen_m & ~seen_f).sum()) / n, "field_only": int((~seen_m & seen_f).sum()) / n,
+                "neither": int((~seen_m & ~seen_f).sum()) / n, "h": h}
+
     def extract_mesh_tsdf(self, resolution: int = 256, aabb=None, poses=None, trunc=None, acc_min: float = 0.5, carve: bool = True,
                           min_views: int = 1, colors: bool = True, min_component: int = 0, largest_only: bool = False,
                           opening_radius: int = 0, simplify_grid: int = 0, simplify_placement: str = "quadric",

@@ -327,6 +327,14 @@ class Trainer:
         from .mesh import render_mesh
         return render_mesh(mesh, c2w, self.K, self.H, self.W, texture=texture, background=background, near=float(self.near))
 
+    def raycast_mesh(self, mesh, c2w, texture=None, background=None):
+        """render_mesh by rays: engine.mesh.MeshFrame of a finished mesh along the very rays render_frame renders at pose c2w
+        (this trainer's H, W, K, near and far), the nearest face by a watertight ray cast on the mesh's BVH instead of the
+        rasteriser's snapped coverage (engine.mesh.render_mesh_rays).  This rank only."""
+        from .mesh import render_mesh_rays
+        return render_mesh_rays(mesh, c2w, self.K, self.H, self.W, texture=texture, background=background, near=float(self.near),
+                                far=float(self.far))
+
     def mesh_psnr(self, mesh, c2w, gt: torch.Tensor, texture=None, background=None) -> float:
         """PSNR of render_mesh's picture against gt [H, W, 3], computed as `psnr` computes the field's.  This rank only."""
         img = self.render_mesh(mesh, c2w, texture=texture, background=background).rgb

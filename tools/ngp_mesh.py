@@ -848,6 +848,63 @@ def _winding_arms(mesh, m, tsdf_mesh, R, lo, hi, a, rec):
     return out
 
 
+def _raycast_arms(tr, mesh, m, tsdf_mesh, R, lo, hi, a, rec, held_pose, side=800, many=1024):
+    """JSON lines of --raycast: per mesh (marching cubes, the TSDF mesh, the simplified meshes) the device ms of the hierarchy
+    build, of the nearest-hit cast and of the any-hit cast for one side^2 held-out frame beside the rasteriser's, the mean (faces,
+    boxes) tested per ray, the shares of pixels where the ray-cast and the rasterised frame differ in face and in coverage, the
+    same many^2 rays in pixel order, shuffled, and shuffled with sort=True, and NGPTrainer.mesh_depth_error."""
+    from nerf_meets_mlx_amd.dataset import synthetic
+    from nerf_meets_mlx_amd.rendering.ray import gen_rays
+    arms = [("marching cubes", m)] + ([("tsdf", tsdf_mesh)] if tsdf_mesh is not None else [])
+    arms += [(f"simplify {G}", mesh.simplify(m, G, lo, hi)) for G in (64, 128) if G < R]
+    base = {"tool": "ngp_mesh raycast", "R": R, "iters": rec["iters"], "seed": rec["seed"], "device": rec["device"], "frame": side}
+    dev, out = m.verts.device, []
+    K, Kmany = synthetic.intrinsics(side, side)[0], synthetic.intrinsics(many, many)[0]
+
+    def timed(fn):
+        ts = []
+        for _ in range(a.reps + 1):                                      # the first run warms the allocator
+            ev = _events()
+            ev[0].record()
+            got = fn()
+            ev[1].record()
+            torch.cuda.synchronize()
+            ts.append(ev[0].elapsed_time(ev[1]))
+        return got, float(np.mean(ts[1:]))
+
+    for name, x in arms:
+        if not x.faces.shape[0]:
+            continue
+        x = x._replace(colors=None)
+        caster, build_ms = timed(lambda: mesh.MeshRaycast(x, lo, hi))
+        rays = gen_rays(side, side, K, held_pose, float(tr.near), float(tr.far), None, dev)
+        hits, cast_ms = timed(lambda: caster.cast(rays, sort=False))
+        occ, any_ms = timed(lambda: caster.occluded(rays, sort=False))
+        ras, raster_ms = timed(lambda: mesh.rasterize(x, held_pose, K, side, side, near=float(tr.near)))
+        assert torch.equal(occ, hits.face >= 0)
+        rface, racc = ras[0].reshape(-1), ras[3].reshape(-1) > 0
+        cacc = hits.face >= 0
+        both = racc & cacc
+        order = {}
+        big = gen_rays(many, many, Kmany, held_pose, float(tr.near), float(tr.far), None, dev)
+        shuffled = big[torch.randperm(big.shape[0], device=dev, generator=torch.Generator(device=dev).manual_seed(0))].contiguous()
+        ref, order["pixel_order_ms"] = timed(lambda: caster.cast(big, sort=False))
+        _, order["shuffled_ms"] = timed(lambda: caster.cast(shuffled, sort=False))
+        _, order["shuffled_sorted_ms"] = timed(lambda: caster.cast(shuffled, sort=True))
+        _, order["pixel_order_sorted_ms"] = timed(lambda: caster.cast(big, sort=True))
+        r = {**base, "mesh": name, "V": int(x.verts.shape[0]), "F": int(x.faces.shape[0]), "bvh_build_ms": build_ms,
+             "cast_ms": cast_ms, "any_ms": any_ms, "rasterize_ms": raster_ms, "ns_per_ray": 1e6 * cast_ms / rays.shape[0],
+             "mean_visits": hits.visits.double().mean(0).tolist(), "max_visits": hits.visits.max(0).values.tolist(),
+             "mean_visits_hit": hits.visits[cacc].double().mean(0).tolist() if bool(cacc.any()) else None,
+             "covered_share": float(cacc.double().mean()), "coverage_differs_share": float((racc != cacc).double().mean()),
+             "face_differs_share_of_both": float((rface[both] != hits.face[both]).double().mean()) if bool(both.any()) else None,
+             "rays_2_20": {"n": int(big.shape[0]), **order, "mean_visits": ref.visits.double().mean(0).tolist()},
+             "mesh_depth_error": tr.mesh_depth_error(x, held_pose)}
+        print(json.dumps(r), flush=True)
+        out.append(r)
+    return out
+
+
 def _teacher_volume(R, lo, hi, dev):
     from nerf_meets_mlx_amd.dataset import synthetic
     from nerf_meets_mlx_amd.engine import mesh
@@ -941,6 +998,11 @@ def parser():
                          "(--distance-n) signed against the marching-cubes mesh")
     ap.add_argument("--winding-beta", type=float, default=2.0, metavar="B",
                     help="--winding: a subtree is replaced by its dipole beyond B radii from its centre (>= 1; inf: the exact sum)")
+    ap.add_argument("--raycast", action="store_true",
+                    help="at --ply-res: ray casting on the mesh BVH (DESIGN.md section 42) of the marching-cubes mesh, the simplified "
+                         "(G = 64, 128) and, with --tsdf, TSDF meshes: nearest-hit and any-hit time for one 800^2 held-out frame beside "
+                         "the rasteriser's, faces and boxes tested per ray, agreement with the rasteriser, 2^20 rays in pixel, "
+                         "shuffled and sorted order, and the depth error against the field")
     ap.add_argument("--smooth-lambda", type=float, default=0.5)
     ap.add_argument("--smooth-mu", type=float, default=-0.53, help="0: plain Laplacian smoothing")
     ap.add_argument("--ckpt", default=None, help="load this checkpoint instead of training")
@@ -971,11 +1033,11 @@ def main():
     H = W = a.hw
     if a.ckpt:
         imgs, poses, K = torch.zeros(1, 8, 8, 4 if a.random_bg else 3), synthetic.train_poses(1), synthetic.intrinsics(8, 8)[0]
-        if a.tsdf or a.render or a.project:                  # the depth renders and the pictures need the cameras at full size
+        if a.tsdf or a.render or a.project or a.raycast:     # the depth renders and the pictures need the cameras at full size
             imgs, poses, K = torch.zeros(1, H, W, imgs.shape[-1]), synthetic.train_poses(5)[:4], synthetic.intrinsics(H, W)[0]
         if a.project:                                        # and the projective bake the training pictures themselves
             imgs = torch.stack([synthetic.render_gt(H, W, p, device=dev, rgba=a.random_bg) for p in poses], 0)
-        if a.render or a.project:
+        if a.render or a.project or a.raycast:
             held_pose, held_gt = synthetic.train_poses(5)[4], synthetic.render_gt(H, W, synthetic.train_poses(5)[4], device=dev)
     else:
         imgs, poses, _, _, K = synthetic.make_dataset(H, W, 5, seed=0, device=dev, rgba=a.random_bg)
@@ -1070,7 +1132,7 @@ def main():
                 del sm, srows
         lines += _simplify_arms(m._replace(colors=None), "density", R, lo, hi, a, rec, bound, boxes)
         lines += _smooth_arms(m._replace(colors=None), "density", R, lo, hi, a, rec, bound, boxes)
-        dist_m = m._replace(colors=None) if (a.distance or a.winding) and R == a.ply_res else None
+        dist_m = m._replace(colors=None) if (a.distance or a.winding or a.raycast) and R == a.ply_res else None
         del vol, m, rows, col
         torch.cuda.empty_cache()
         tm = None
@@ -1081,6 +1143,8 @@ def main():
             lines += _simplify_arms(tm, "tsdf", R, lo, hi, a, {**rec, "marching_cubes_ms": trec["marching_cubes_ms"]}, bound, boxes)
         if a.winding and dist_m is not None and dist_m.faces.shape[0]:
             lines += _winding_arms(mesh, dist_m, tm, R, lo, hi, a, rec)
+        if a.raycast and dist_m is not None and dist_m.faces.shape[0]:
+            lines += _raycast_arms(tr, mesh, dist_m, tm, R, lo, hi, a, rec, held_pose)
         if a.distance and dist_m is not None and dist_m.faces.shape[0]:
             teacher = mesh.marching_cubes(_teacher_volume(R, lo, hi, dev), 25.0, lo, hi)
             lines += _distance_arms(mesh, dist_m, tm, teacher, R, lo, hi, a, rec, bound)
