@@ -888,6 +888,104 @@ int nerf_smooth_run(const float* verts_in, int64_t V, const float* lo_host, cons
 int nerf_smooth_normals(const float* verts, int64_t V, const float* lo_host, const float* hi_host, void* workspace,
                         float* normals_out, float* color_rows, void* stream);
 
+/* ---------------------------------------------------------------- edge-collapse decimation (no reference counterpart)
+ * Decimation to a target face count: greedy quadric-error edge collapse (Garland-Heckbert, "Surface simplification using quadric
+ * error metrics", 1997), made parallel by collapsing an independent set of edges per round.  What the clustering simplifier above
+ * cannot do: its output size follows from the grid alone.  Additive: NERF_ABI_VERSION stays 3.  All arithmetic is IEEE double, one
+ * rounding per operation, in exactly the order and grouping written here; tests/_decimate_ref.py reproduces every output bit for bit.
+ *   input     verts [V, 3] float32, colors [V, 3] float32 or NULL, faces [F, 3] int32; box lo[3] < hi[3] (host floats, finite);
+ *             1 <= V, F <= 2^24.  ctr_a = ((double)lo_a + (double)hi_a) * 0.5; hs = max_a((double)hi_a - (double)lo_a) * 0.5.
+ *             u_a = ((double)v_a - ctr_a) / hs: coordinates relative to the box centre, in units of half the longest side.  A
+ *             vertex is finite when its three float32 coordinates are.
+ *   state     across rounds: positions float32 [V, 3] (rounded once when written), per vertex the quadric Q of 10 doubles
+ *             (Axx, Axy, Axz, Ayy, Ayz, Azz, bx, by, bz, c), a colour sum of 3 doubles (the float32 colours as doubles at first)
+ *             and a merge count (1 at first); the face list.  Vertex indices are stable, vertices are compacted only at the end, in
+ *             index order; faces are compacted every round, in input order.
+ *   faces     a face with an index outside [0, V) is dropped before anything else and nothing is read through that index; so
+ *             is a face with two equal corners.
+ *   quadrics  for every face whose three corners are finite: e1 = u1 - u0, e2 = u2 - u0 (u0 the face's first corner),
+ *             n = (e1y e2z - e1z e2y, e1z e2x - e1x e2z, e1x e2y - e1y e2x), d = -((nx u0x + ny u0y) + nz u0z),
+ *             K = (nx nx, nx ny, nx nz, ny ny, ny nz, nz nz, nx d, ny d, nz d, d d): area^2-weighted.  Q[v] = the K of the faces
+ *             of v added one by one to 0 in ascending face index -- the rows come from one sort of the 3 F keys
+ *             (vertex << 27) | (face << 2) | corner, without atomics.  A fixed-order double sum: reproducible, and it DOES
+ *             depend on the order of the faces.
+ *   round 1. edges.  Corner c of face f gives the half-edge key (min << 25) | (max << 1) | (g_c > g_c+1) of (g_c, g_c+1).  In the
+ *             sorted keys a run with one (min, max) is one edge (a, b), a < b; its rank among the runs is its id e.  A vertex is
+ *             free iff it is finite and every edge at it is a run of exactly two half-edges of opposite direction.  Vertices on
+ *             open, non-manifold or inconsistently oriented edges are frozen: this version never moves them.
+ *         2. candidates.  Edge (a, b) is a candidate iff (i) both ends are free; (ii) the link condition holds: over the faces
+ *             (a, n, p) at a and (b, n', p') at b, written from the end's corner on, n = n' for exactly two pairs (two common
+ *             neighbours), and no face at a without b and face at b without a have {n, p} = {n', p'} (no ring edge is opposite both
+ *             ends: what stops a tetrahedron collapsing to a double face); (iii) every face at a or b that does not hold both keeps
+ *             dot > 0, dot = (n0x n1x + n0y n1y) + n0z n1z of its normal n0 = (p1 - p0) x (p2 - p0) (as n above) and the same
+ *             with the moved corner at xbar.
+ *             placement: q = Q[a] + Q[b]; m = (ua + ub) * 0.5; len2 = (dx dx + dy dy) + dz dz of d = ua - ub.  With
+ *             NERF_DECIMATE_MIDPOINT, or when tr = (Axx + Ayy) + Azz <= 0: xbar = m.  Otherwise mu = (tr / 3) * 2^-10 and
+ *             (A + mu I) x = mu m - b by Cramer's rule exactly as "mesh simplification" writes it out (a00 ... c22, det, x0, x1,
+ *             x2 with r_a = mu m_a - b_a); x is taken when its three components are finite and
+ *             (ex ex + ey ey) + ez ez <= len2 for e = x - m, else xbar = m.
+ *             cost: Ax_0 = (Axx x0 + Axy x1) + Axz x2, Ax_1 = (Axy x0 + Ayy x1) + Ayz x2, Ax_2 = (Axz x0 + Ayz x1) + Azz x2;
+ *             cost = ((x0 Ax_0 + x1 Ax_1) + x2 Ax_2 + 2 ((bx x0 + by x1) + bz x2)) + c, grouped as ((xAx) + (2 (b.x))) + c; 0
+ *             unless cost > 0.  key = (the bits of (float)cost << 32) | ((e * 0x9E3779B1) mod 2^32).  The multiplier is odd, the
+ *             low word a bijection of e: keys are unique, and exact cost ties -- the rule on coplanar marching-cubes faces -- do
+ *             not order themselves along the vertex numbering.
+ *         3. selection, `passes` times (1 <= passes <= 16); no vertex is blocked at first.  An edge takes part when it is a candidate and neither end
+ *             is blocked.  m1[v] = the minimum key over the edges at v that take part (64-bit unsigned atomic minimum);
+ *             m2[v] = min(m1[v], m1[u] over every edge (v, u)); an edge that takes part is selected iff its key equals m2[a] and
+ *             m2[b].  Then every vertex that shares an edge with an end of a newly selected edge is blocked, the ends included.
+ *             Independence: two selected edges of a round never share or adjoin a vertex.  In one pass: key(e) >= m1[a] >= m2[a]
+ *             for an edge e at a that takes part, so a selected e has key(e) = m2 of both ends.  If selected e = (a, b) and e' = (c,
+ *             d) shared a vertex v, key(e) = m2[v] = key(e'), and keys are unique: e = e'.  If an edge joined a to c,
+ *             key(e) = m2[a] <= m1[c] <= key(e') and key(e') = m2[c] <= m1[a] <= key(e): again e = e'.  Across passes: a later
+ *             edge takes part only with both ends unblocked, so neither is an end of an earlier selected edge or joined to one.
+ *             A collapse of (a, b) reads and writes only a, b, their faces and their neighbours' positions; a face that holds an end
+ *             of e and an end of e' would join them.  So every ring a collapse reads is untouched by the others, no collapse of
+ *             the round creates an edge between two neighbours of a or b, and the round equals the same collapses done one after
+ *             another in any order.
+ *         4. trim.  With S selected edges and F faces, if F - 2 S < target only the k = ceil((F - target) / 2) smallest keys
+ *             stay (one sort of the selected keys).  Every collapse removes exactly two faces (the link condition), so the result
+ *             has `target` or `target - 1` faces.
+ *         5. apply, one lane per selected edge, one writer per vertex: pos[a] = (float)(ctr + xbar * hs) per axis;
+ *             Q[a] = Q[a] + Q[b], and so the colour sums and the merge counts; b becomes a in every face, faces with two equal
+ *             corners are dropped, the face list is compacted in order (count -> scan -> write).
+ *         6. one host read of (F', collapses, candidates, frozen vertices).  The caller stops when F <= target ("target"), when a
+ *             round selected nothing ("selected nothing") or after max_rounds rounds ("max_rounds").
+ *   finish    the vertices the faces use, in index order, with positions as they stand and colours (float)(sum_a / count);
+ *             normals by the rule of "mesh smoothing" (nerf_smooth_build, nerf_smooth_normals on the output).
+ * Calls, with the same (V, F) -- the input's -- and workspace throughout; F_cap >= the current face count bounds the launches
+ * (the kernels take the face count itself from device memory), `list` (0 first, then alternating) names the current one of the two face lists:
+ *   nerf_decimate_begin     the state and face list 0; totals int64 [1] = the faces that stay, read once by the caller.
+ *   nerf_decimate_keys      keys int64 [2][3 F_cap]: the half-edge keys and the incidence keys, INT64_MAX behind the 3 F in use.
+ *   (the caller)            each row sorted ascending (one sort along the last axis).
+ *   nerf_decimate_edges     rows, edges, ranks, frozen flags.
+ *   nerf_decimate_quadrics  the initial quadrics; once, behind the first nerf_decimate_edges.
+ *   nerf_decimate_select    candidates and the passes; sel_keys int64 [3 F_cap]: the selected keys, INT64_MAX elsewhere.
+ *   (the caller)            sel_keys sorted ascending.
+ *   nerf_decimate_apply     trim, collapses, face remap into the other list; totals int64 [4] as in step 6.
+ *   nerf_decimate_count     totals int64 [2] = (V', F') of the current list.
+ *   nerf_decimate_write     verts_out [V', 3], colors_out [V', 3] or NULL, faces_out [F', 3]; nothing is written past V_out / F_out.
+ * No float atomics; the only atomics are 64-bit integer minima, besides stores of equal values.  workspace:
+ * nerf_decimate_workspace_bytes(V, F) bytes (-1 out of range), kept from begin to write; its content on entry is unspecified.
+ * Out of range: NERF_E_SHAPE; NULL: NERF_E_NULL; all argument checks run before any device work.
+ * Not done: collapsing boundary or non-manifold vertices, invariance to the face order, a geometric error bound as a stopping
+ * rule, texture or UV carry-over, a multi-rank path.                                                                            */
+#define NERF_DECIMATE_MIDPOINT 0
+#define NERF_DECIMATE_QUADRIC 1
+int64_t nerf_decimate_workspace_bytes(int64_t V, int64_t F);
+int nerf_decimate_begin(const float* verts, const float* colors, int64_t V, const int32_t* faces, int64_t F, void* workspace,
+                        int64_t* totals, void* stream);
+int nerf_decimate_keys(int64_t V, int64_t F, int64_t F_cap, int list, void* workspace, int64_t* keys, void* stream);
+int nerf_decimate_edges(int64_t V, int64_t F, int64_t F_cap, const int64_t* sorted_keys, void* workspace, void* stream);
+int nerf_decimate_quadrics(int64_t V, int64_t F, int list, const float* lo_host, const float* hi_host, void* workspace, void* stream);
+int nerf_decimate_select(int64_t V, int64_t F, int64_t F_cap, int list, const float* lo_host, const float* hi_host, int placement,
+                         int passes, void* workspace, int64_t* sel_keys, void* stream);
+int nerf_decimate_apply(int64_t V, int64_t F, int64_t F_cap, int list, const float* lo_host, const float* hi_host, int placement,
+                        int has_colors, int64_t target, const int64_t* sorted_sel_keys, void* workspace, int64_t* totals,
+                        void* stream);
+int nerf_decimate_count(int64_t V, int64_t F, int64_t F_cap, int list, void* workspace, int64_t* totals, void* stream);
+int nerf_decimate_write(int64_t V, int64_t F, int list, int has_colors, void* workspace, int64_t V_out, int64_t F_out,
+                        float* verts_out, float* colors_out, int32_t* faces_out, void* stream);
+
 /* ---------------------------------------------------------------- mesh distance (no reference counterpart)
  * How far one mesh is from another: points drawn on a surface in proportion to area, and for each point the closest point of
  * another mesh (the Metro measurement of Cignoni, Rocchini and Scopigno, 1998).  It changes no mesh.  Additive: NERF_ABI_VERSION

@@ -116,6 +116,15 @@ SIGNATURES = {
     "nerf_simplify_count": (_I, [_P, _P, _I64, _P, _I64, _I, _P, _P, _P]),
     "nerf_simplify_write": (_I, [_I64, _P, _I64, C.POINTER(C.c_float), C.POINTER(C.c_float), _I, _I, _P, _I64, _I64, _P, _P, _P, _P,
                                 _P, _P]),
+    "nerf_decimate_workspace_bytes": (_I64, [_I64, _I64]),
+    "nerf_decimate_begin": (_I, [_P, _P, _I64, _P, _I64, _P, _P, _P]),
+    "nerf_decimate_keys": (_I, [_I64, _I64, _I64, _I, _P, _P, _P]),
+    "nerf_decimate_edges": (_I, [_I64, _I64, _I64, _P, _P, _P]),
+    "nerf_decimate_quadrics": (_I, [_I64, _I64, _I, C.POINTER(C.c_float), C.POINTER(C.c_float), _P, _P]),
+    "nerf_decimate_select": (_I, [_I64, _I64, _I64, _I, C.POINTER(C.c_float), C.POINTER(C.c_float), _I, _I, _P, _P, _P]),
+    "nerf_decimate_apply": (_I, [_I64, _I64, _I64, _I, C.POINTER(C.c_float), C.POINTER(C.c_float), _I, _I, _I64, _P, _P, _P, _P]),
+    "nerf_decimate_count": (_I, [_I64, _I64, _I64, _I, _P, _P, _P]),
+    "nerf_decimate_write": (_I, [_I64, _I64, _I, _I, _P, _I64, _I64, _P, _P, _P, _P]),
     "nerf_smooth_workspace_bytes": (_I64, [_I64, _I64]),
     "nerf_smooth_build": (_I, [_I64, _P, _I64, _P, _P]),
     "nerf_smooth_run": (_I, [_P, _I64, C.POINTER(C.c_float), C.POINTER(C.c_float), _I, _F, _F, _P, _P, _P]),

@@ -5,13 +5,15 @@ is Instant-NGP's.  One module per stage, and every name of theirs is a name of t
   _checks (the three argument tests) <- _base (Mesh, the lattice arguments, the stage hook) <- surface (simplify, smooth) <- volume
   (density volume, marching cubes, components, opening, extract / mesh_volume); _base <- tsdf (TSDFVolume, tsdf_views); _base <-
   texture (atlas bake and lookup, mip pyramid) <- raster (rasterize, face_lod, render_mesh, render_mesh_mip) <- project
-  (project_texture); texture <- files (PLY, OBJ, PNG); _base <- distance (sample_surface, MeshIndex, mesh_distance).
+  (project_texture); _base <- decimate (decimate: edge collapse to a target face count); texture <- files (PLY, OBJ, PNG); _base <- distance (sample_surface, MeshIndex, mesh_distance).
   distance also holds the second index, MeshBVH (a bounding-volume hierarchy with the grid's answers bit for bit), and
   closest_points.  distance <- volume <- winding (MeshWinding, winding_number, winding_volume, remesh, signed_distance): the
   generalized winding number on MeshBVH's tree, the inside test the distance lacks.  distance, raster <- raycast (MeshRaycast,
   pack_rays, raycast_frame, render_mesh_rays): nearest hit and occlusion of rays on the same tree, and the rasteriser's frame by
   rays."""
 from ._base import CHUNK, MAX_RES, SIMPLIFY_MAX_ITEMS, Mesh, _box, _check_mesh_tensors, _mark, check_mesh_args
+from .decimate import (DECIMATE_MAX_PASSES, DECIMATE_MAX_ROUNDS, DECIMATE_PLACEMENTS, DECIMATE_STOPS, DecimateStats, _decimate,
+                       check_decimate_args, decimate)
 from .distance import (DISTANCE_INDEXES, DISTANCE_MAX_ENTRIES, DISTANCE_MAX_GRID, DISTANCE_MAX_SAMPLES, DistanceStats, MeshBVH,
                        MeshDistance, MeshIndex, check_distance_args, check_distance_index, closest_points, default_distance_grid,
                        mesh_distance, point_mesh_distance, sample_surface)

@@ -255,6 +255,15 @@ class Trainer:
         lo, hi = self._mesh_box(aabb)
         return M.mesh_distance(mesh, other, n, lo, hi, seed=seed, tau=tau)
 
+    def decimate_mesh(self, mesh, target_faces: int, aabb=None, placement: str = "quadric", passes: int = 4, max_rounds: int = 1024):
+        """(engine.mesh.Mesh, engine.mesh.DecimateStats): an engine.mesh.Mesh (extract_mesh's) collapsed to `target_faces` faces, or
+        one fewer, by quadric-error edge collapse on the box of the export (`aabb` as in extract_mesh; engine.mesh.decimate,
+        DESIGN.md section 44).  A step of its own behind the export, as texture_mesh: colours are carried as means, a texture is
+        baked afterwards.  Runs on this rank only: no collective."""
+        from . import mesh as M
+        lo, hi = self._mesh_box(aabb)
+        return M.decimate(mesh, target_faces, lo, hi, placement=placement, passes=passes, max_rounds=max_rounds)
+
     def remesh(self, mesh, resolution: int = 256, aabb=None, beta: float = 2.0, min_component: int = 0, largest_only: bool = False,
                opening_radius: int = 0):
         """A closed engine.mesh.Mesh from one that may be open, duplicated or self-intersecting: marching cubes at 0.5 over the

@@ -31,6 +31,13 @@ the clusters, the device ms of the simplifier alone (cluster, the sort, count wi
 it, and the geometry figures of the simplified vertices (the share within h of a box face, the count beyond 2 h; h is the
 marching-cubes lattice's) beside the input mesh's.
 
+With --decimate N (repeatable), lines with "tool": "ngp_mesh decimate" for the coloured density mesh at --ply-res: the mesh
+collapsed to N faces by quadric edge collapse (--decimate-passes), with quadric and with midpoint placement
+-- rounds, collapses and candidates per round, frozen vertices, why it stopped, the device ms per stage (host reads included),
+V and F, open and non-manifold edges, engine.mesh.mesh_distance against its input with tau = h (mean and Hausdorff from both
+sides, the share of the input's area beyond h) and the held-out mesh_psnr with the carried vertex colours -- and the same columns
+for each --simplify G beside them: pass the G whose mesh has N faces to compare at equal face count.
+
 With --smooth N (repeatable), one more line per N and R for the density mesh: N pairs of Taubin's lambda|mu filter (DESIGN.md
 section 30; --smooth-lambda, --smooth-mu, mu 0 for plain Laplacian) -- the device ms of the build, of the half-steps (and of one),
 of the normals, V and F, the geometry figures, the enclosed volume and the roughness (the mean distance of a vertex from the mean
@@ -775,6 +782,53 @@ def _edge_census(faces):
     return int((c == 1).sum()), int((c > 2).sum())
 
 
+def _decimate_arms(tr, mesh, m, R, lo, hi, a, rec, held_pose, held_gt):
+    """JSON lines of --decimate N: engine.mesh.decimate of the coloured marching-cubes mesh `m` to N faces -- rounds, collapses, the
+    stages' device ms (host reads included), V / F, open / non-manifold edges, mesh_distance against `m` with tau = h, held-out
+    mesh_psnr with the carried vertex colours -- and, beside it, the same columns for engine.mesh.simplify at every --simplify G."""
+    h = (hi[0] - lo[0]) / R
+    out = []
+    base = {"tool": "ngp_mesh decimate", "R": R, "iters": rec["iters"], "seed": rec["seed"], "h": h, "device": rec["device"],
+            "V_in": int(m.verts.shape[0]), "F_in": int(m.faces.shape[0])}
+
+    def judge(x):
+        r = mesh.mesh_distance(x, m, a.distance_n, lo, hi, seed=0, tau=h)
+        units = lambda s: {"mean_h": s.mean / h, "hausdorff_h": s.max / h}
+        o, nm = _edge_census(x.faces)
+        return {"V": int(x.verts.shape[0]), "F": int(x.faces.shape[0]), "open_edges": o, "nonmanifold_edges": nm,
+                "to_input": units(r.a_to_b), "from_input": units(r.b_to_a), "input_area_beyond_h": 1.0 - r.recall,
+                "own_area_beyond_h": 1.0 - r.precision, "heldout_mesh_psnr": tr.mesh_psnr(x, held_pose, held_gt)}
+
+    def line(r):
+        print(json.dumps(r), flush=True)
+        out.append(r)
+
+    o, nm = _edge_census(m.faces)
+    line({**base, "arm": "input", "open_edges": o, "nonmanifold_edges": nm, "heldout_mesh_psnr": tr.mesh_psnr(m, held_pose, held_gt)})
+    for target in a.decimate:
+        for placement in ("quadric", "midpoint"):
+            ts = []
+            for _ in range(a.reps + 1):                                  # the first run warms the allocator and the sorts
+                st = _Stages()
+                dm, stats = mesh._decimate(m, target, lo, hi, placement, a.decimate_passes, mark=st)
+                st("end")
+                ts.append(st.total_ms())
+            t = {k: float(np.mean([q[k] for q in ts[1:]])) for k in ts[0]}
+            line({**base, "arm": f"decimate {target}", "placement": placement, "passes": a.decimate_passes, "rounds": stats.rounds,
+                  "stopped": stats.stopped, "frozen": stats.frozen, "collapses": stats.collapses, "candidates": stats.candidates,
+                  "stage_ms": t, "decimate_ms": float(sum(t.values())),
+                  "decimate_ms_range": [float(min(sum(q.values()) for q in ts[1:])), float(max(sum(q.values()) for q in ts[1:]))],
+                  **judge(dm)})
+            del dm
+    for G in a.simplify or []:
+        _simplify_timed(m, G, lo, hi, "quadric")
+        ts = [_simplify_timed(m, G, lo, hi, "quadric") for _ in range(a.reps)]
+        line({**base, "arm": f"simplify {G}", "placement": "quadric", "simplify_ms": float(np.mean([sum(x[2]) for x in ts])),
+              **judge(ts[-1][0])})
+    torch.cuda.empty_cache()
+    return out
+
+
 def _winding_arms(mesh, m, tsdf_mesh, R, lo, hi, a, rec):
     """JSON lines of --winding: per mesh (marching cubes, the TSDF mesh, the simplified meshes) the open and non-manifold edges
     and the enclosed volume before and after engine.mesh.remesh at the same R, the device ms of the moments build and of the
@@ -961,6 +1015,11 @@ def parser():
     ap.add_argument("--simplify", type=int, action="append", default=None,
                     help="also cluster every mesh on a grid of this size (DESIGN.md section 27); repeatable: one JSON line per "
                          "grid and meshed volume")
+    ap.add_argument("--decimate", type=int, action="append", default=None, metavar="N",
+                    help="also collapse the coloured density mesh at --ply-res to N faces by quadric edge collapse (DESIGN.md section "
+                         "44) and judge it against its input: edges, mesh_distance, held-out mesh_psnr, the stages' times; each "
+                         "--simplify G is judged beside it.  Repeatable: one JSON line per value and placement")
+    ap.add_argument("--decimate-passes", type=int, default=4, metavar="P", help="--decimate: selection passes per round")
     ap.add_argument("--smooth", type=int, action="append", default=None,
                     help="also smooth the density mesh by this many Taubin pairs (DESIGN.md section 30); repeatable: one JSON "
                          "line per value and R, and with --simplify the simplifier's lines for the smoothed mesh")
@@ -1033,11 +1092,11 @@ def main():
     H = W = a.hw
     if a.ckpt:
         imgs, poses, K = torch.zeros(1, 8, 8, 4 if a.random_bg else 3), synthetic.train_poses(1), synthetic.intrinsics(8, 8)[0]
-        if a.tsdf or a.render or a.project or a.raycast:     # the depth renders and the pictures need the cameras at full size
+        if a.tsdf or a.render or a.project or a.raycast or a.decimate:     # the depth renders and the pictures need the cameras at full size
             imgs, poses, K = torch.zeros(1, H, W, imgs.shape[-1]), synthetic.train_poses(5)[:4], synthetic.intrinsics(H, W)[0]
         if a.project:                                        # and the projective bake the training pictures themselves
             imgs = torch.stack([synthetic.render_gt(H, W, p, device=dev, rgba=a.random_bg) for p in poses], 0)
-        if a.render or a.project or a.raycast:
+        if a.render or a.project or a.raycast or a.decimate:
             held_pose, held_gt = synthetic.train_poses(5)[4], synthetic.render_gt(H, W, synthetic.train_poses(5)[4], device=dev)
     else:
         imgs, poses, _, _, K = synthetic.make_dataset(H, W, 5, seed=0, device=dev, rgba=a.random_bg)
@@ -1130,6 +1189,11 @@ def main():
                 sm = sm._replace(colors=mesh.vertex_colors(query, srows))
                 lines += _mip_arms(tr, query, sm, f"density simplify {G}", R, a, rec, heldout, 2.0 * bound / R, train)
                 del sm, srows
+        if a.decimate and R == a.ply_res and m.faces.shape[0]:
+            gt = held_gt[..., :3].to(dev).float()
+            if a.random_bg and not (a.render or a.project):
+                gt = (held_gt[..., :3] * held_gt[..., 3:] + (1.0 - held_gt[..., 3:])).to(dev).float()
+            lines += _decimate_arms(tr, mesh, m, R, lo, hi, a, rec, held_pose, gt)
         lines += _simplify_arms(m._replace(colors=None), "density", R, lo, hi, a, rec, bound, boxes)
         lines += _smooth_arms(m._replace(colors=None), "density", R, lo, hi, a, rec, bound, boxes)
         dist_m = m._replace(colors=None) if (a.distance or a.winding or a.raycast) and R == a.ply_res else None
