@@ -4,7 +4,7 @@
 // is unused and written as an empty box.  Every region starts on a multiple of 16 bytes (a pair of children is read as three
 // 16-byte words).  Compiles without HIP (tests/bvh_ws_check.cpp carves it under a host compiler).
 #pragma once
-#include <stdint.h>
+#include "mesh_ws.h"
 
 namespace nerf {
 namespace {
@@ -13,7 +13,6 @@ constexpr int BVH_BLOCK = 256;                      // lanes per workgroup: leav
 constexpr int BVH_LEAF = 4;                         // sorted faces per leaf
 constexpr int BVH_NODE_FLOATS = 6;                  // min x y z, max x y z
 constexpr int BVH_TOP_LEVELS = 9;                   // the levels 0 .. 8 (at most 256 nodes each) are merged by one workgroup
-constexpr int64_t BVH_MAX_FACES = 1ll << 24;
 constexpr int BVH_CELLS = 4096;                     // Morton cells per axis: 12 bits, a 36-bit code
 constexpr int64_t BVH_INVALID_CODE = 1ll << 36;     // the code of an invalid face: behind every valid one
 constexpr int BVH_KEY_SHIFT = 24;                   // key = code 2^24 + face
@@ -28,8 +27,7 @@ struct BvhWs {
   int64_t bytes;
 };
 
-inline bool bvh_faces_ok(int64_t F) { return F >= 0 && F <= BVH_MAX_FACES; }
-inline int64_t bvh_blocks(int64_t n) { return (n + BVH_BLOCK - 1) / BVH_BLOCK; }
+inline bool bvh_faces_ok(int64_t F) { return F >= 0 && F <= MESH_MAX_ITEMS; }
 // the first node of level l and how many it has
 inline int64_t bvh_level_first(int l) { return (int64_t)1 << l; }
 inline int64_t bvh_level_nodes(int l) { return (int64_t)1 << l; }
@@ -45,16 +43,10 @@ inline BvhWs bvh_ws(void* ws, int64_t F) {
   }
   // the leaves' launch, then bvh_tree.h's tree_reduce: the internal levels depth - 1 .. 0, those below BVH_TOP_LEVELS in one launch
   w.launches = 2 + (w.depth > BVH_TOP_LEVELS ? w.depth - BVH_TOP_LEVELS : 0);
-  uintptr_t p = reinterpret_cast<uintptr_t>(ws);
-  const uintptr_t p0 = p;
-  auto take = [&p](int64_t bytes) {
-    const uintptr_t at = p;
-    p += (uintptr_t)((bytes + 15) & ~(int64_t)15);
-    return at;
-  };
-  w.nodes = reinterpret_cast<float*>(take(2 * w.P * BVH_NODE_FLOATS * 4));
-  w.order = reinterpret_cast<int32_t*>(take(F * 4));
-  w.bytes = (int64_t)(p - p0);
+  WsCarver<16> c(ws);
+  w.nodes = c.take<float>(2 * w.P * BVH_NODE_FLOATS);
+  w.order = c.take<int32_t>(F);
+  w.bytes = c.bytes();
   return w;
 }
 

@@ -132,6 +132,13 @@ static inline unsigned blocks(int64_t n, int block) { return (unsigned)((n + blo
     if (rc_) return rc_;           \
   } while (0)
 
+// a HIP runtime call (a memset, a copy): a failure returns NERF_E_HIP with "<who>: <HIP's text>" from the calling entry
+#define NERF_HIP(who, call)                                                                       \
+  do {                                                                                            \
+    const hipError_t e_ = (call);                                                                 \
+    if (e_ != hipSuccess) return nerf::fail(NERF_E_HIP, "%s: %s", who, hipGetErrorString(e_));    \
+  } while (0)
+
 // Launches `kernel` with `blocks` workgroups of `threads` on hipStream_t `st`; a failed launch returns its code from the calling entry.
 #define NERF_LAUNCH(what, kernel, blocks, threads, st, ...)                                        \
   do {                                                                                             \

@@ -14,6 +14,7 @@
 //             compacted into the other list, the round's totals.
 // No float atomics; the only atomics are 64-bit integer minima, and plain stores of equal values.  Launch- and cache-bound.
 #include "lattice.h"
+#include "quadric.h"
 #include "scan.h"
 
 namespace nerf {
@@ -62,47 +63,39 @@ struct DecWs {
   int64_t bytes;
 };
 
-inline int64_t dec_blocks(int64_t n) { return (n + DEC_BLOCK - 1) / DEC_BLOCK; }
-
 DecWs dec_ws(void* ws, int64_t V, int64_t F) {
   DecWs w;
   const int64_t H = 3 * F;
-  w.nblk_v = dec_blocks(V);
-  w.nblk_f = dec_blocks(F);
-  w.nblk_h = dec_blocks(H);
-  uintptr_t p = reinterpret_cast<uintptr_t>(ws);
-  const uintptr_t p0 = p;
-  auto take = [&p](int64_t bytes) {
-    const uintptr_t at = p;
-    p += (uintptr_t)((bytes + 7) & ~(int64_t)7);
-    return at;
-  };
-  w.cnt = reinterpret_cast<int64_t*>(take(DEC_CNT * 8));
-  w.blk_v = reinterpret_cast<int64_t*>(take(w.nblk_v * 8));
-  w.blk_f = reinterpret_cast<int64_t*>(take(w.nblk_f * 8));
-  w.blk_h = reinterpret_cast<int64_t*>(take(w.nblk_h * 8));
-  w.Q = reinterpret_cast<double*>(take(V * DEC_Q * 8));
-  w.col = reinterpret_cast<double*>(take(V * 3 * 8));
-  w.m1 = reinterpret_cast<u64*>(take(V * 8));
-  w.m2 = reinterpret_cast<u64*>(take(V * 8));
-  w.ekey = reinterpret_cast<u64*>(take(H * 8));
-  w.pos = reinterpret_cast<float*>(take(V * 12));
-  w.faces[0] = reinterpret_cast<int*>(take(F * 12));
-  w.faces[1] = reinterpret_cast<int*>(take(F * 12));
-  w.mcnt = reinterpret_cast<int*>(take(V * 4));
-  w.remap = reinterpret_cast<int*>(take(V * 4));
-  w.vstart = reinterpret_cast<int*>(take(2 * V * 4));
+  w.nblk_v = mesh_blocks(V, DEC_BLOCK);
+  w.nblk_f = mesh_blocks(F, DEC_BLOCK);
+  w.nblk_h = mesh_blocks(H, DEC_BLOCK);
+  WsCarver<8> c(ws);
+  w.cnt = c.take<int64_t>(DEC_CNT);
+  w.blk_v = c.take<int64_t>(w.nblk_v);
+  w.blk_f = c.take<int64_t>(w.nblk_f);
+  w.blk_h = c.take<int64_t>(w.nblk_h);
+  w.Q = c.take<double>(V * DEC_Q);
+  w.col = c.take<double>(V * 3);
+  w.m1 = c.take<u64>(V);
+  w.m2 = c.take<u64>(V);
+  w.ekey = c.take<u64>(H);
+  w.pos = c.take<float>(V * 3);
+  w.faces[0] = c.take<int>(F * 3);
+  w.faces[1] = c.take<int>(F * 3);
+  w.mcnt = c.take<int>(V);
+  w.remap = c.take<int>(V);
+  w.vstart = c.take<int>(2 * V);
   w.vend = w.vstart + V;
-  w.frozen = reinterpret_cast<int*>(take(V * 4));
-  w.blocked = reinterpret_cast<int*>(take(V * 4));
-  w.selend = reinterpret_cast<int*>(take(V * 4));
-  w.used = reinterpret_cast<int*>(take(V * 4));
-  w.newid = reinterpret_cast<int*>(take(V * 4));
-  w.ea = reinterpret_cast<int*>(take(H * 4));
-  w.eb = reinterpret_cast<int*>(take(H * 4));
-  w.sel = reinterpret_cast<int*>(take(H * 4));
-  w.inc = reinterpret_cast<int*>(take(H * 4));
-  w.bytes = (int64_t)(p - p0);
+  w.frozen = c.take<int>(V);
+  w.blocked = c.take<int>(V);
+  w.selend = c.take<int>(V);
+  w.used = c.take<int>(V);
+  w.newid = c.take<int>(V);
+  w.ea = c.take<int>(H);
+  w.eb = c.take<int>(H);
+  w.sel = c.take<int>(H);
+  w.inc = c.take<int>(H);
+  w.bytes = c.bytes();
   return w;
 }
 
@@ -132,7 +125,7 @@ __device__ __forceinline__ bool dec_face(const int* __restrict__ faces, int f, i
   if (!mesh_corners(faces + 3 * f, V, g)) return false;
 #pragma unroll
   for (int c = 0; c < 3; ++c) g[c] = remap[g[c]];
-  return g[0] != g[1] && g[1] != g[2] && g[0] != g[2];
+  return mesh_distinct(g);
 }
 
 // ---- the state of the vertices: 12 (+ 12) B read, 12 + 8 (+ 24) B written per vertex
@@ -273,21 +266,12 @@ __device__ __forceinline__ double dec_place(const double* q, const double* ua, c
   if (quadric) {
     const double d0 = ua[0] - ub[0], d1 = ua[1] - ub[1], d2 = ua[2] - ub[2];
     const double len2 = (d0 * d0 + d1 * d1) + d2 * d2;
-    const double tr = (q[0] + q[3]) + q[5];
-    if (tr > 0.0) {
-      const double mu = (tr / 3.0) * 0.0009765625;
-      const double a00 = q[0] + mu, a01 = q[1], a02 = q[2], a11 = q[3] + mu, a12 = q[4], a22 = q[5] + mu;
-      const double r0 = mu * m[0] - q[6], r1 = mu * m[1] - q[7], r2 = mu * m[2] - q[8];
-      const double c00 = a11 * a22 - a12 * a12, c01 = a02 * a12 - a01 * a22, c02 = a01 * a12 - a02 * a11;
-      const double c11 = a00 * a22 - a02 * a02, c12 = a01 * a02 - a00 * a12, c22 = a00 * a11 - a01 * a01;
-      const double det = (a00 * c00 + a01 * c01) + a02 * c02;
-      const double s0 = ((c00 * r0 + c01 * r1) + c02 * r2) / det;
-      const double s1 = ((c01 * r0 + c11 * r1) + c12 * r2) / det;
-      const double s2 = ((c02 * r0 + c12 * r1) + c22 * r2) / det;
-      const double e0 = s0 - m[0], e1 = s1 - m[1], e2 = s2 - m[2];
+    double s[3];                                     // accepted no farther from the midpoint than the edge is long
+    if (quadric_solve(q, m, s)) {
+      const double e0 = s[0] - m[0], e1 = s[1] - m[1], e2 = s[2] - m[2];
       const double dist2 = (e0 * e0 + e1 * e1) + e2 * e2;
-      if (isfinite(s0) && isfinite(s1) && isfinite(s2) && dist2 <= len2) {
-        x[0] = s0; x[1] = s1; x[2] = s2;
+      if (isfinite(s[0]) && isfinite(s[1]) && isfinite(s[2]) && dist2 <= len2) {
+        x[0] = s[0]; x[1] = s[1]; x[2] = s[2];
       }
     }
   }
@@ -372,16 +356,11 @@ __global__ void __launch_bounds__(DEC_BLOCK) dec_candidates_kernel(const float* 
   ekey[e] = key;
 }
 
-// ---- counts for the statistics: candidate keys over the E edges, flags over n items
+// ---- counts for the statistics: candidate keys over the E edges (the frozen and the used vertices: scan.h's flag count)
 __global__ void __launch_bounds__(DEC_BLOCK) dec_count_keys_kernel(const u64* __restrict__ ekey, const int64_t* __restrict__ cnt,
                                                                   int64_t* __restrict__ blk) {
   const int64_t e = (int64_t)blockIdx.x * DEC_BLOCK + threadIdx.x;
   const int64_t t = block_sum<DEC_BLOCK>(e < cnt[1] && ekey[e] != DEC_NO_KEY ? 1 : 0);
-  if (threadIdx.x == 0) blk[blockIdx.x] = t;
-}
-__global__ void __launch_bounds__(DEC_BLOCK) dec_count_flags_kernel(const int* __restrict__ flags, int64_t n, int64_t* __restrict__ blk) {
-  const int64_t i = (int64_t)blockIdx.x * DEC_BLOCK + threadIdx.x;
-  const int64_t t = block_sum<DEC_BLOCK>(i < n && flags[i] != 0 ? 1 : 0);
   if (threadIdx.x == 0) blk[blockIdx.x] = t;
 }
 
@@ -555,11 +534,6 @@ int dec_placement(const char* who, int placement) {
 }
 
 #define DEC_LAUNCH(what, kernel, blocks, ...) NERF_LAUNCH(what, kernel, blocks, DEC_BLOCK, st, __VA_ARGS__)
-#define DEC_HIP(who, call)                                                              \
-  do {                                                                                  \
-    const hipError_t e_ = (call);                                                       \
-    if (e_ != hipSuccess) return fail(NERF_E_HIP, "%s: %s", who, hipGetErrorString(e_)); \
-  } while (0)
 
 }  // namespace
 }  // namespace nerf
@@ -585,7 +559,7 @@ extern "C" int nerf_decimate_begin(const float* verts, const float* colors, int6
   NERF_TRY(scan_launch("nerf_decimate_begin (scan of the faces)", w.blk_f, w.nblk_f, w.cnt, st));
   DEC_LAUNCH("nerf_decimate_begin (faces)", dec_faces_write_kernel, w.nblk_f, faces, (const int64_t*)nullptr, F, (int)V,
              (const int*)w.remap, (const int64_t*)w.blk_f, F, w.faces[0]);
-  DEC_HIP(who, hipMemcpyAsync(totals, w.cnt, sizeof(int64_t), hipMemcpyDeviceToDevice, st));
+  NERF_HIP(who, hipMemcpyAsync(totals, w.cnt, sizeof(int64_t), hipMemcpyDeviceToDevice, st));
   return NERF_OK;
 }
 
@@ -596,7 +570,7 @@ extern "C" int nerf_decimate_keys(int64_t V, int64_t F, int64_t F_cap, int parit
   const DecWs w = dec_ws(workspace, V, F);
   hipStream_t st = as_stream(stream);
   const int64_t cap = 3 * F_cap;
-  DEC_LAUNCH(who, dec_keys_kernel, dec_blocks(cap), (const int*)w.faces[parity], (const int64_t*)w.cnt, cap, keys, keys + cap);
+  DEC_LAUNCH(who, dec_keys_kernel, mesh_blocks(cap, DEC_BLOCK), (const int*)w.faces[parity], (const int64_t*)w.cnt, cap, keys, keys + cap);
   return NERF_OK;
 }
 
@@ -606,9 +580,9 @@ extern "C" int nerf_decimate_edges(int64_t V, int64_t F, int64_t F_cap, const in
   NERF_REQUIRE(workspace && sorted_keys, NERF_E_NULL, "%s: NULL pointer", who);
   const DecWs w = dec_ws(workspace, V, F);
   hipStream_t st = as_stream(stream);
-  const int64_t cap = 3 * F_cap, nblk = dec_blocks(cap);
-  DEC_HIP(who, hipMemsetAsync(w.vstart, 0, 2 * V * sizeof(int), st));
-  DEC_HIP(who, hipMemsetAsync(w.frozen, 0, V * sizeof(int), st));
+  const int64_t cap = 3 * F_cap, nblk = mesh_blocks(cap, DEC_BLOCK);
+  NERF_HIP(who, hipMemsetAsync(w.vstart, 0, 2 * V * sizeof(int), st));
+  NERF_HIP(who, hipMemsetAsync(w.frozen, 0, V * sizeof(int), st));
   DEC_LAUNCH("nerf_decimate_edges (rows)", dec_rows_kernel, nblk, sorted_keys + cap, (const int64_t*)w.cnt, (int)V, w.inc, w.vstart, w.vend);
   DEC_LAUNCH("nerf_decimate_edges (run counts)", dec_edges_count_kernel, nblk, sorted_keys, (const int64_t*)w.cnt, w.blk_h);
   NERF_TRY(scan_launch("nerf_decimate_edges (scan of the runs)", w.blk_h, nblk, w.cnt + 1, st));
@@ -641,21 +615,22 @@ extern "C" int nerf_decimate_select(int64_t V, int64_t F, int64_t F_cap, int par
   NERF_REQUIRE(workspace && sel_keys, NERF_E_NULL, "%s: NULL pointer", who);
   const DecWs w = dec_ws(workspace, V, F);
   hipStream_t st = as_stream(stream);
-  const int64_t cap = 3 * F_cap, nblk = dec_blocks(cap);
+  const int64_t cap = 3 * F_cap, nblk = mesh_blocks(cap, DEC_BLOCK);
   const int64_t* cnt = w.cnt;
   const int *ea = w.ea, *eb = w.eb;
-  DEC_HIP(who, hipMemsetAsync(w.blocked, 0, V * sizeof(int), st));
-  DEC_HIP(who, hipMemsetAsync(w.sel, 0, cap * sizeof(int), st));
+  NERF_HIP(who, hipMemsetAsync(w.blocked, 0, V * sizeof(int), st));
+  NERF_HIP(who, hipMemsetAsync(w.sel, 0, cap * sizeof(int), st));
   DEC_LAUNCH("nerf_decimate_select (candidates)", dec_candidates_kernel, nblk, (const float*)w.pos, (const double*)w.Q,
              (const int*)w.faces[parity], (const int*)w.inc, (const int*)w.vstart, (const int*)w.vend, ea, eb, (const int*)w.frozen, cnt,
              bx, placement, w.ekey);
   DEC_LAUNCH("nerf_decimate_select (candidate counts)", dec_count_keys_kernel, nblk, (const u64*)w.ekey, cnt, w.blk_h);
   NERF_TRY(scan_launch("nerf_decimate_select (scan of the candidates)", w.blk_h, nblk, w.cnt + 3, st));
-  DEC_LAUNCH("nerf_decimate_select (frozen counts)", dec_count_flags_kernel, w.nblk_v, (const int*)w.frozen, V, w.blk_v);
+  DEC_LAUNCH("nerf_decimate_select (frozen counts)", scan_flags_count_kernel<DEC_BLOCK>, w.nblk_v, (const int*)w.frozen,
+             (const int64_t*)nullptr, V, w.blk_v);
   NERF_TRY(scan_launch("nerf_decimate_select (scan of the frozen)", w.blk_v, w.nblk_v, w.cnt + 4, st));
   for (int p = 0; p < passes; ++p) {
-    DEC_HIP(who, hipMemsetAsync(w.m1, 0xFF, 2 * V * sizeof(u64), st));      // m1 and m2 are neighbours in the workspace
-    DEC_HIP(who, hipMemsetAsync(w.selend, 0, V * sizeof(int), st));
+    NERF_HIP(who, hipMemsetAsync(w.m1, 0xFF, 2 * V * sizeof(u64), st));      // m1 and m2 are neighbours in the workspace
+    NERF_HIP(who, hipMemsetAsync(w.selend, 0, V * sizeof(int), st));
     DEC_LAUNCH("nerf_decimate_select (vertex minima)", dec_min1_kernel, nblk, (const u64*)w.ekey, ea, eb, (const int*)w.blocked, cnt, w.m1);
     DEC_LAUNCH("nerf_decimate_select (ring minima)", dec_min2_kernel, nblk, ea, eb, cnt, (const u64*)w.m1, w.m2);
     DEC_LAUNCH("nerf_decimate_select (pick)", dec_pick_kernel, nblk, (const u64*)w.ekey, ea, eb, (const int*)w.blocked, cnt,
@@ -678,7 +653,7 @@ extern "C" int nerf_decimate_apply(int64_t V, int64_t F, int64_t F_cap, int pari
   NERF_REQUIRE(workspace && sorted_sel_keys && totals, NERF_E_NULL, "%s: NULL pointer", who);
   const DecWs w = dec_ws(workspace, V, F);
   hipStream_t st = as_stream(stream);
-  const int64_t cap = 3 * F_cap, nblk = dec_blocks(cap), nblk_f = dec_blocks(F_cap);
+  const int64_t cap = 3 * F_cap, nblk = mesh_blocks(cap, DEC_BLOCK), nblk_f = mesh_blocks(F_cap, DEC_BLOCK);
   const int64_t* cnt = w.cnt;
   hipLaunchKernelGGL(dec_trim_kernel, dim3(1), dim3(64), 0, st, sorted_sel_keys, cap, target, w.cnt);
   NERF_TRY(check_launch("nerf_decimate_apply (trim)"));
@@ -699,13 +674,14 @@ extern "C" int nerf_decimate_count(int64_t V, int64_t F, int64_t F_cap, int pari
   NERF_REQUIRE(workspace && totals, NERF_E_NULL, "%s: NULL pointer", who);
   const DecWs w = dec_ws(workspace, V, F);
   hipStream_t st = as_stream(stream);
-  DEC_HIP(who, hipMemsetAsync(w.used, 0, V * sizeof(int), st));
-  DEC_LAUNCH("nerf_decimate_count (used vertices)", dec_used_kernel, dec_blocks(3 * F_cap), (const int*)w.faces[parity],
+  NERF_HIP(who, hipMemsetAsync(w.used, 0, V * sizeof(int), st));
+  DEC_LAUNCH("nerf_decimate_count (used vertices)", dec_used_kernel, mesh_blocks(3 * F_cap, DEC_BLOCK), (const int*)w.faces[parity],
              (const int64_t*)w.cnt, w.used);
-  DEC_LAUNCH("nerf_decimate_count (vertex counts)", dec_count_flags_kernel, w.nblk_v, (const int*)w.used, V, w.blk_v);
+  DEC_LAUNCH("nerf_decimate_count (vertex counts)", scan_flags_count_kernel<DEC_BLOCK>, w.nblk_v, (const int*)w.used,
+             (const int64_t*)nullptr, V, w.blk_v);
   NERF_TRY(scan_launch("nerf_decimate_count (scan of the vertices)", w.blk_v, w.nblk_v, w.cnt + 5, st));
-  DEC_HIP(who, hipMemcpyAsync(totals, w.cnt + 5, sizeof(int64_t), hipMemcpyDeviceToDevice, st));
-  DEC_HIP(who, hipMemcpyAsync(totals + 1, w.cnt, sizeof(int64_t), hipMemcpyDeviceToDevice, st));
+  NERF_HIP(who, hipMemcpyAsync(totals, w.cnt + 5, sizeof(int64_t), hipMemcpyDeviceToDevice, st));
+  NERF_HIP(who, hipMemcpyAsync(totals + 1, w.cnt, sizeof(int64_t), hipMemcpyDeviceToDevice, st));
   return NERF_OK;
 }
 
@@ -723,7 +699,7 @@ extern "C" int nerf_decimate_write(int64_t V, int64_t F, int parity, int has_col
   DEC_LAUNCH("nerf_decimate_write (vertices)", dec_verts_write_kernel, w.nblk_v, (const int*)w.used, (int)V, (const int64_t*)w.blk_v,
              (const float*)w.pos, (const double*)w.col, (const int*)w.mcnt, V_out, w.newid, verts_out, colors_out);
   if (F_out > 0)
-    DEC_LAUNCH("nerf_decimate_write (faces)", dec_faces_out_kernel, dec_blocks(3 * F_out), (const int*)w.faces[parity],
+    DEC_LAUNCH("nerf_decimate_write (faces)", dec_faces_out_kernel, mesh_blocks(3 * F_out, DEC_BLOCK), (const int*)w.faces[parity],
                (const int64_t*)w.cnt, (const int*)w.newid, F_out, faces_out);
   return NERF_OK;
 }

@@ -132,28 +132,8 @@ __global__ void __launch_bounds__(DIST_BLOCK) dist_count_kernel(const float* __r
       for (int x = c0[0]; x <= c1[0]; ++x) atomicAdd(&cnt[x + bx.G * (y + bx.G * z)], 1);
 }
 
-// ---- cell offsets, as smooth.hip's rows
-__global__ void __launch_bounds__(DIST_BLOCK) dist_cells_count_kernel(const int* __restrict__ cnt, int C, int64_t* __restrict__ blk) {
-  const int c = blockIdx.x * DIST_BLOCK + threadIdx.x;
-  const int64_t t = block_sum<DIST_BLOCK>(c < C ? cnt[c] : 0);
-  if (threadIdx.x == 0) blk[blockIdx.x] = t;
-}
-__global__ void __launch_bounds__(DIST_BLOCK) dist_cells_write_kernel(int* __restrict__ cur, int C, const int64_t* __restrict__ blk,
-                                                                     const int64_t* __restrict__ total, int* __restrict__ off,
-                                                                     int64_t* __restrict__ total_out) {
-  const int c = blockIdx.x * DIST_BLOCK + threadIdx.x;
-  const int64_t o = block_offset<DIST_BLOCK>(c < C ? cur[c] : 0, blk[blockIdx.x]);
-  const int64_t tot = total[0];
-  // a total beyond the cap is refused by the caller before anything reads the offsets: they are clamped, not wrapped
-  if (c == 0) {
-    off[C] = (int)(tot < DIST_MAX_ENTRIES ? tot : DIST_MAX_ENTRIES);
-    total_out[0] = tot;
-  }
-  if (c >= C) return;
-  const int oc = (int)(o < DIST_MAX_ENTRIES ? o : DIST_MAX_ENTRIES);
-  off[c] = oc;
-  cur[c] = oc;
-}
+// (cell offsets: scan.h's counts-to-offsets pair, clamped at DIST_MAX_ENTRIES -- a total beyond it is refused by the caller before
+// anything reads the offsets -- with the total copied out)
 
 // ---- entries: one cursor atomic and one 4-byte store per overlapped cell; nothing is written at or past E
 __global__ void __launch_bounds__(DIST_BLOCK) dist_fill_kernel(const float* __restrict__ verts, int V, const int* __restrict__ faces, int F,
@@ -255,20 +235,14 @@ inline bool dist_grid_ok(int G) { return G >= 1 && G <= DIST_MAX_GRID; }
 inline DistWs dist_ws(void* ws, int G) {
   DistWs w;
   w.cells = (int64_t)G * G * G;
-  w.nblk = (w.cells + DIST_BLOCK - 1) / DIST_BLOCK;
-  uintptr_t p = reinterpret_cast<uintptr_t>(ws);
-  const uintptr_t p0 = p;
-  auto take = [&p](int64_t bytes) {
-    const uintptr_t at = p;
-    p += (uintptr_t)((bytes + 7) & ~(int64_t)7);
-    return at;
-  };
-  w.blk = reinterpret_cast<int64_t*>(take(w.nblk * 8));
-  w.total = reinterpret_cast<int64_t*>(take(8));
-  w.scale = reinterpret_cast<uint32_t*>(take(8));
-  w.off = reinterpret_cast<int32_t*>(take((w.cells + 1) * 4));
-  w.cur = reinterpret_cast<int32_t*>(take(w.cells * 4));
-  w.bytes = (int64_t)(p - p0);
+  w.nblk = mesh_blocks(w.cells, DIST_BLOCK);
+  WsCarver<8> c(ws);
+  w.blk = c.take<int64_t>(w.nblk);
+  w.total = c.take<int64_t>(1);
+  w.scale = c.take<uint32_t>(2);
+  w.off = c.take<int32_t>(w.cells + 1);
+  w.cur = c.take<int32_t>(w.cells);
+  w.bytes = c.bytes();
   return w;
 }
 
@@ -339,15 +313,14 @@ extern "C" int nerf_meshdist_count(const float* verts, int64_t V, const int32_t*
   NERF_REQUIRE(workspace && total_out && (faces || F == 0) && (verts || V == 0), NERF_E_NULL, "nerf_meshdist_count: NULL pointer");
   const DistWs w = dist_ws(workspace, grid);
   hipStream_t st = as_stream(stream);
-  hipError_t e = hipMemsetAsync(w.cur, 0, w.cells * sizeof(int32_t), st);
-  if (e == hipSuccess) e = hipMemsetAsync(w.scale, 0, 8, st);
-  if (e != hipSuccess) return fail(NERF_E_HIP, "nerf_meshdist_count: %s", hipGetErrorString(e));
+  NERF_HIP("nerf_meshdist_count", hipMemsetAsync(w.cur, 0, w.cells * sizeof(int32_t), st));
+  NERF_HIP("nerf_meshdist_count", hipMemsetAsync(w.scale, 0, 8, st));
   if (F > 0)
     DIST_LAUNCH("nerf_meshdist_count (count)", dist_count_kernel, blocks(F, DIST_BLOCK), verts, (int)V, faces, (int)F, bx, w.cur, w.scale);
-  DIST_LAUNCH("nerf_meshdist_count (cell counts)", dist_cells_count_kernel, w.nblk, (const int*)w.cur, (int)w.cells, w.blk);
+  DIST_LAUNCH("nerf_meshdist_count (cell counts)", scan_offsets_count_kernel<DIST_BLOCK>, w.nblk, (const int*)w.cur, (int)w.cells, w.blk);
   NERF_TRY(scan_launch("nerf_meshdist_count (scan of the cells)", w.blk, w.nblk, w.total, st));
-  DIST_LAUNCH("nerf_meshdist_count (cell offsets)", dist_cells_write_kernel, w.nblk, w.cur, (int)w.cells, (const int64_t*)w.blk,
-              (const int64_t*)w.total, w.off, total_out);
+  DIST_LAUNCH("nerf_meshdist_count (cell offsets)", scan_offsets_write_kernel<DIST_BLOCK>, w.nblk, w.cur, (int)w.cells,
+              (const int64_t*)w.blk, (const int64_t*)w.total, DIST_MAX_ENTRIES, w.off, total_out);
   return NERF_OK;
 }
 

@@ -9,11 +9,12 @@
 // NERF_REQUIRE itself).  Not here, on purpose: simplify.hip's double-precision SBox (another lattice, of G^3 cells), morph.hip's
 // word geometry (it counts 64-voxel words) and ccl.hip's union-find.
 // Below the lattice, the triangle mesh as the surface kernels take it (texture.hip, raster.hip, project.hip, mip.hip; smooth.hip for
-// the corners): verts float32 [V, 3], faces int32 [F, 3], 0 <= V, F <= MESH_MAX_ITEMS, nothing read through an index outside [0, V).
-// Not simplify.hip's checks (one message for V and F) or its fetch, which tests only >= 0.
+// the corners): verts float32 [V, 3], faces int32 [F, 3], 0 <= V, F <= MESH_MAX_ITEMS (mesh_ws.h), nothing read through an index
+// outside [0, V).  Not simplify.hip's checks (one message for V and F) or its fetch, which tests only >= 0.
 #pragma once
 #include <cmath>
 #include <stdint.h>
+#include "mesh_ws.h"
 #if defined(__HIPCC__)
 #include "common.h"
 #else
@@ -75,7 +76,6 @@ inline int lattice_box(const char* who, int R, const float* lo, const float* hi,
   return NERF_OK;
 }
 
-constexpr int64_t MESH_MAX_ITEMS = 1 << 24;                    // vertices, faces
 inline int mesh_check(const char* who, int64_t V, int64_t F) {             // (an entry without vertices passes V = 0)
   NERF_REQUIRE(V >= 0 && V <= MESH_MAX_ITEMS, NERF_E_SHAPE, "%s: need 0 <= V <= 2^24 (got %lld)", who, (long long)V);
   NERF_REQUIRE(F >= 0 && F <= MESH_MAX_ITEMS, NERF_E_SHAPE, "%s: need 0 <= F <= 2^24 (got %lld)", who, (long long)F);
@@ -86,6 +86,8 @@ __host__ __device__ __forceinline__ bool mesh_corners(const int* __restrict__ id
   g[0] = idx[0], g[1] = idx[1], g[2] = idx[2];
   return g[0] >= 0 && g[0] < V && g[1] >= 0 && g[1] < V && g[2] >= 0 && g[2] < V;
 }
+// no two of the three corners are one vertex (smooth.hip and decimate.hip ignore a face that fails this)
+__host__ __device__ __forceinline__ bool mesh_distinct(const int* g) { return g[0] != g[1] && g[1] != g[2] && g[0] != g[2]; }
 
 // correctly rounded float32 division / square root: the double result rounded once (exact enough for one float rounding)
 __host__ __device__ __forceinline__ float div_rn(float a, float b) { return (float)((double)a / (double)b); }

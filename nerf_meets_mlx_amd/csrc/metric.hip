@@ -100,8 +100,7 @@ extern "C" int nerf_ssim_sums(const float* pred, const float* gt, int N, int C, 
   const int OW = W - w_size + 1, OH = H - w_size + 1;
   const int IW = SSIM_TX + w_size - 1, IH = SSIM_TY + w_size - 1;
   const size_t lds = sizeof(float) * ((size_t)2 * IH * IW + (size_t)5 * IH * SSIM_TX);
-  hipError_t e = hipMemsetAsync(sums, 0, sizeof(double) * 2 * N, as_stream(stream));
-  if (e != hipSuccess) return fail(NERF_E_HIP, "nerf_ssim_sums: memset: %s", hipGetErrorString(e));
+  NERF_HIP("nerf_ssim_sums: memset", hipMemsetAsync(sums, 0, sizeof(double) * 2 * N, as_stream(stream)));
   const int ntile = ((OW + SSIM_TX - 1) / SSIM_TX) * ((OH + SSIM_TY - 1) / SSIM_TY);
   const dim3 grid(ntile < 64 ? ntile : 64, 1, N * C), block(SSIM_TX, SSIM_TY);
   hipLaunchKernelGGL(ssim_kernel, grid, block, lds, as_stream(stream), pred, gt, H, W, w_size, win, c1, c2, sums, C);

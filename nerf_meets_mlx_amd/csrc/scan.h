@@ -1,7 +1,9 @@
-// The three passes shared by the compactions of occupancy.hip (cull, march, early termination), mesh.hip (marching cubes) and
-// morph.hip (the steps' statistics): count per workgroup (block_sum), scan of the workgroup sums by one workgroup
-// (occ_cull_scan_kernel, launched by scan_launch), rank inside the workgroup (block_offset).  Fixed order, no atomics; and the
-// host's layout of the workspace a count / write pair shares.
+// The three passes shared by the compactions of occupancy.hip (cull, march, early termination), mesh.hip (marching cubes),
+// morph.hip (the steps' statistics) and the mesh surface units (simplify.hip, decimate.hip, smooth.hip, distance.hip): count per
+// workgroup (block_sum), scan of the workgroup sums by one workgroup (occ_cull_scan_kernel, launched by scan_launch), rank inside
+// the workgroup (block_offset).  Fixed order, no atomics; the host's layout of the workspace a count / write pair shares; and,
+// as templates that a unit emits only when it launches them, the two count / write forms that do the same work per item wherever
+// they are used: counts to offsets (smooth.hip's rows, distance.hip's cells) and the count of set flags (simplify.hip, decimate.hip).
 #pragma once
 #include <type_traits>
 #include "common.h"
@@ -79,7 +81,44 @@ __device__ __forceinline__ int64_t block_offset(std::common_type_t<T> v, int64_t
   return o[0];
 }
 
-#ifndef NERF_SCAN_HELPERS_ONLY                       // (a kernel defined here is emitted by every unit that includes it)
+// ---- counts -> exclusive offsets: count (the sum of cnt over each workgroup of BLOCK items) and, behind the scan of those sums,
+// write (ranked inside the workgroup).  The write leaves the first slot of item i in off[i] and in cur[i], the fill cursor that held
+// the count, and the total in off[n]; offsets and total are clamped at cap, not wrapped (a caller whose total can pass it refuses
+// before anything reads them), and the unclamped total goes to total_out when that is not NULL.
+template <int BLOCK>
+__global__ void __launch_bounds__(BLOCK) scan_offsets_count_kernel(const int* __restrict__ cnt, int n, int64_t* __restrict__ blk) {
+  const int i = blockIdx.x * BLOCK + threadIdx.x;
+  const int64_t t = block_sum<BLOCK>(i < n ? cnt[i] : 0);
+  if (threadIdx.x == 0) blk[blockIdx.x] = t;
+}
+template <int BLOCK>
+__global__ void __launch_bounds__(BLOCK) scan_offsets_write_kernel(int* __restrict__ cur, int n, const int64_t* __restrict__ blk,
+                                                                  const int64_t* __restrict__ total, int64_t cap,
+                                                                  int* __restrict__ off, int64_t* __restrict__ total_out) {
+  const int i = blockIdx.x * BLOCK + threadIdx.x;
+  const int64_t o = block_offset<BLOCK>(i < n ? cur[i] : 0, blk[blockIdx.x]);
+  if (i == 0) {
+    const int64_t tot = total[0];
+    off[n] = (int)(tot < cap ? tot : cap);
+    if (total_out) total_out[0] = tot;
+  }
+  if (i >= n) return;
+  const int oc = (int)(o < cap ? o : cap);
+  off[i] = oc;
+  cur[i] = oc;
+}
+
+// ---- the count of a compaction by flags: the items with flags[i] != 0 per workgroup, over n_dev[0] items, or n_host with n_dev NULL
+template <int BLOCK>
+__global__ void __launch_bounds__(BLOCK) scan_flags_count_kernel(const int* __restrict__ flags, const int64_t* __restrict__ n_dev,
+                                                                int64_t n_host, int64_t* __restrict__ blk) {
+  const int64_t n = n_dev ? n_dev[0] : n_host;
+  const int64_t i = (int64_t)blockIdx.x * BLOCK + threadIdx.x;
+  const int64_t t = block_sum<BLOCK>(i < n ? (flags[i] != 0) : 0);
+  if (threadIdx.x == 0) blk[blockIdx.x] = t;
+}
+
+#ifndef NERF_SCAN_HELPERS_ONLY                      // (a kernel defined here is emitted by every unit that includes it)
 // counts -> exclusive offsets in place, the total to count_out.  8 + 8 B per count.
 __global__ void __launch_bounds__(1024) occ_cull_scan_kernel(int64_t* __restrict__ offs, int64_t nblk, int64_t* __restrict__ count_out) {
   __shared__ int64_t sh[1024 / 64];
@@ -126,8 +165,8 @@ inline PairWs pair_ws(void* ws, int rows, int64_t nblk, int64_t item_bytes) {
 
 // "nothing to do": n int64 zeros on the stream, or HIP's text
 inline int zero_i64(const char* who, int64_t* p, int n, void* stream) {
-  const hipError_t e = hipMemsetAsync(p, 0, n * sizeof(int64_t), as_stream(stream));
-  return e == hipSuccess ? NERF_OK : fail(NERF_E_HIP, "%s: %s", who, hipGetErrorString(e));
+  NERF_HIP(who, hipMemsetAsync(p, 0, n * sizeof(int64_t), as_stream(stream)));
+  return NERF_OK;
 }
 
 #endif

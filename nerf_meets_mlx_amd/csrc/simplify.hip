@@ -10,6 +10,7 @@
 //   write    the placement solve of the used clusters and the renumbered surviving faces, ranked inside the workgroup.
 // All HBM- or launch-bound.
 #include "lattice.h"
+#include "quadric.h"
 #include "scan.h"
 
 namespace nerf {
@@ -18,7 +19,6 @@ namespace {
 constexpr int SIMP_BLOCK = 256;
 constexpr int SIMP_ACC = 19;                        // n, S[3], N[3], C[3], Q[9]
 constexpr int SIMP_KEY_BITS = 21;
-constexpr int64_t SIMP_MAX_ITEMS = 1ll << 24;       // V, F
 constexpr int64_t SIMP_NO_KEY = INT64_MAX;          // a dropped face: sorts behind every triple (three equal ids are never a key)
 
 typedef unsigned long long u64;
@@ -51,41 +51,33 @@ struct SimpWs {
   int64_t bytes;
 };
 
-inline int64_t blocks_of(int64_t n) { return (n + SIMP_BLOCK - 1) / SIMP_BLOCK; }
-
 SimpWs simp_ws(void* ws, int64_t V, int64_t F, int G) {
   SimpWs w;
   const int64_t cells = (int64_t)G * G * G;
   w.W = (cells + 63) >> 6;
-  w.nblk_w = blocks_of(w.W);
+  w.nblk_w = mesh_blocks(w.W, SIMP_BLOCK);
   w.K_max = V < cells ? V : cells;
-  w.nblk_c = blocks_of(w.K_max);
-  w.nblk_f = blocks_of(F);
-  uintptr_t p = reinterpret_cast<uintptr_t>(ws);
-  const uintptr_t p0 = p;
-  auto take = [&p](int64_t bytes) {
-    const uintptr_t at = p;
-    p += (uintptr_t)((bytes + 7) & ~(int64_t)7);
-    return at;
-  };
-  w.mask = reinterpret_cast<u64*>(take(w.W * 8));
-  w.acc = reinterpret_cast<int64_t*>(take(w.K_max * SIMP_ACC * 8));
-  w.cnt = reinterpret_cast<int64_t*>(take(4 * 8));
-  w.blk_w = reinterpret_cast<int64_t*>(take(w.nblk_w * 8));
-  w.blk_c = reinterpret_cast<int64_t*>(take(w.nblk_c * 8));
-  w.blk_s = reinterpret_cast<int64_t*>(take(2 * w.nblk_f * 8));
-  w.blk_f = reinterpret_cast<int64_t*>(take(w.nblk_f * 8));
-  w.wpre = reinterpret_cast<int*>(take(w.W * 4));
-  w.vcid = reinterpret_cast<int*>(take(V * 4));
-  w.ckey = reinterpret_cast<int*>(take(w.K_max * 4));
-  w.used = reinterpret_cast<int*>(take(w.K_max * 4));
-  w.newid = reinterpret_cast<int*>(take(w.K_max * 4));
-  w.odd = reinterpret_cast<int*>(take((F + 1) * 4));
-  w.rid = reinterpret_cast<int*>(take(F * 4));
-  w.heads = reinterpret_cast<int*>(take((F + 1) * 4));
-  w.keep = reinterpret_cast<int*>(take(F * 4));
-  w.par = reinterpret_cast<uint8_t*>(take(F));
-  w.bytes = (int64_t)(p - p0);
+  w.nblk_c = mesh_blocks(w.K_max, SIMP_BLOCK);
+  w.nblk_f = mesh_blocks(F, SIMP_BLOCK);
+  WsCarver<8> c(ws);
+  w.mask = c.take<u64>(w.W);
+  w.acc = c.take<int64_t>(w.K_max * SIMP_ACC);
+  w.cnt = c.take<int64_t>(4);
+  w.blk_w = c.take<int64_t>(w.nblk_w);
+  w.blk_c = c.take<int64_t>(w.nblk_c);
+  w.blk_s = c.take<int64_t>(2 * w.nblk_f);
+  w.blk_f = c.take<int64_t>(w.nblk_f);
+  w.wpre = c.take<int>(w.W);
+  w.vcid = c.take<int>(V);
+  w.ckey = c.take<int>(w.K_max);
+  w.used = c.take<int>(w.K_max);
+  w.newid = c.take<int>(w.K_max);
+  w.odd = c.take<int>(F + 1);
+  w.rid = c.take<int>(F);
+  w.heads = c.take<int>(F + 1);
+  w.keep = c.take<int>(F);
+  w.par = c.take<uint8_t>(F);
+  w.bytes = c.bytes();
   return w;
 }
 
@@ -102,11 +94,6 @@ __device__ __forceinline__ bool cell_of(const float* __restrict__ verts, int v, 
 }
 __device__ __forceinline__ int key_of(const double* q, int G) { return ((int)q[2] * G + (int)q[1]) * G + (int)q[0]; }
 
-// rint(clamp(x, -lim, lim) scale) as int64, NaN counting as 0
-__device__ __forceinline__ int64_t fixed(double x, double lim, double scale) {
-  if (x != x) return 0;
-  return (int64_t)rint(fmin(fmax(x, -lim), lim) * scale);
-}
 __device__ __forceinline__ void add64(int64_t* p, int64_t v) {
   if (v) atomicAdd(reinterpret_cast<u64*>(p), (u64)v);
 }
@@ -354,14 +341,7 @@ __global__ void __launch_bounds__(SIMP_BLOCK) simp_survivors_kernel(const int64_
   for (int c = 0; c < 3; ++c) used[g[c]] = 1;       // every writer stores the same value
 }
 
-// ---- the two compactions' counts: used clusters (over K_max slots, K from device memory) and kept faces
-__global__ void __launch_bounds__(SIMP_BLOCK) simp_flags_count_kernel(const int* __restrict__ flags, const int64_t* __restrict__ n_dev,
-                                                                     int64_t n_host, int64_t* __restrict__ blk) {
-  const int64_t n = n_dev ? n_dev[0] : n_host;
-  const int64_t i = (int64_t)blockIdx.x * SIMP_BLOCK + threadIdx.x;
-  const int64_t t = block_sum<SIMP_BLOCK>(i < n ? (flags[i] != 0) : 0);
-  if (threadIdx.x == 0) blk[blockIdx.x] = t;
-}
+// (the two compactions' counts, used clusters over K_max slots with K from device memory and kept faces: scan.h's flag count)
 
 // ---- solve: per used cluster its vertex (12 B), normal (12 B), colour (12 B) and colour query row (44 B), at its new id
 __global__ void __launch_bounds__(SIMP_BLOCK) simp_solve_kernel(const int64_t* __restrict__ acc, const int* __restrict__ ckey,
@@ -386,20 +366,10 @@ __global__ void __launch_bounds__(SIMP_BLOCK) simp_solve_kernel(const int64_t* _
     double Q[9];
 #pragma unroll
     for (int k = 0; k < 9; ++k) Q[k] = (double)A[10 + k] / 4294967296.0;
-    const double tr = (Q[0] + Q[3]) + Q[5];
-    if (tr > 0.0) {
-      const double mu = (tr / 3.0) * 0.0009765625;
-      const double a00 = Q[0] + mu, a01 = Q[1], a02 = Q[2], a11 = Q[3] + mu, a12 = Q[4], a22 = Q[5] + mu;
-      const double r0 = mu * ub[0] - Q[6], r1 = mu * ub[1] - Q[7], r2 = mu * ub[2] - Q[8];
-      const double c00 = a11 * a22 - a12 * a12, c01 = a02 * a12 - a01 * a22, c02 = a01 * a12 - a02 * a11;
-      const double c11 = a00 * a22 - a02 * a02, c12 = a01 * a02 - a00 * a12, c22 = a00 * a11 - a01 * a01;
-      const double det = (a00 * c00 + a01 * c01) + a02 * c02;
-      const double s0 = ((c00 * r0 + c01 * r1) + c02 * r2) / det;
-      const double s1 = ((c01 * r0 + c11 * r1) + c12 * r2) / det;
-      const double s2 = ((c02 * r0 + c12 * r1) + c22 * r2) / det;
-      if (isfinite(s0) && isfinite(s1) && isfinite(s2) && fabs(s0) <= 0.5 && fabs(s1) <= 0.5 && fabs(s2) <= 0.5) {
-        x[0] = s0; x[1] = s1; x[2] = s2;
-      }
+    double s[3];                                     // accepted inside its cell only
+    if (quadric_solve(Q, ub, s) && isfinite(s[0]) && isfinite(s[1]) && isfinite(s[2]) && fabs(s[0]) <= 0.5 && fabs(s[1]) <= 0.5 &&
+        fabs(s[2]) <= 0.5) {
+      x[0] = s[0]; x[1] = s[1]; x[2] = s[2];
     }
   }
   const int key = ckey[c];
@@ -434,22 +404,19 @@ __global__ void __launch_bounds__(SIMP_BLOCK) simp_faces_write_kernel(const int*
 
 // the grid and the item counts: all that nerf_simplify_count takes
 int simp_size_check(const char* who, int64_t V, int64_t F, int G) {
-  const int rc = lattice_res_check(who, G, "grid");
-  if (rc) return rc;
-  NERF_REQUIRE(V >= 0 && V <= SIMP_MAX_ITEMS && F >= 0 && F <= SIMP_MAX_ITEMS, NERF_E_SHAPE,
+  NERF_TRY(lattice_res_check(who, G, "grid"));
+  NERF_REQUIRE(V >= 0 && V <= MESH_MAX_ITEMS && F >= 0 && F <= MESH_MAX_ITEMS, NERF_E_SHAPE,
                "%s: need 0 <= V, F <= 2^24 (got %lld, %lld)", who, (long long)V, (long long)F);
   return NERF_OK;
 }
 
 int simp_check(const char* who, int64_t V, int64_t F, const float* lo, const float* hi, int G, SBox* bx) {
-  int rc = simp_size_check(who, V, F, G);
-  if (rc) return rc;
+  NERF_TRY(simp_size_check(who, V, F, G));
   NERF_REQUIRE(lo && hi, NERF_E_NULL, "%s: NULL lo / hi", who);
   const int64_t cells = lattice_n3(G);
   NERF_REQUIRE((V < cells ? V : cells) <= (1ll << SIMP_KEY_BITS), NERF_E_SHAPE,
                "%s: min(V, grid^3) = %lld clusters do not fit %d bits", who, (long long)(V < cells ? V : cells), SIMP_KEY_BITS);
-  rc = box_check(who, lo, hi);
-  if (rc) return rc;
+  NERF_TRY(box_check(who, lo, hi));
   for (int a = 0; a < 3; ++a) {
     const double ext = (double)hi[a] - (double)lo[a];
     bx->lo[a] = (double)lo[a];
@@ -468,7 +435,7 @@ int simp_check(const char* who, int64_t V, int64_t F, const float* lo, const flo
 using namespace nerf;
 
 extern "C" int64_t nerf_simplify_workspace_bytes(int64_t V, int64_t F, int grid) {
-  if (!lattice_res_ok(grid) || V < 0 || V > SIMP_MAX_ITEMS || F < 0 || F > SIMP_MAX_ITEMS) return -1;
+  if (!lattice_res_ok(grid) || V < 0 || V > MESH_MAX_ITEMS || F < 0 || F > MESH_MAX_ITEMS) return -1;
   return simp_ws(nullptr, V, F, grid).bytes;
 }
 
@@ -476,33 +443,29 @@ extern "C" int nerf_simplify_cluster(const float* verts, const float* normals, c
                                      int64_t F, const float* lo, const float* hi, int grid, void* workspace, int64_t* tri_keys,
                                      void* stream) {
   SBox bx;
-  int rc = simp_check("nerf_simplify_cluster", V, F, lo, hi, grid, &bx);
-  if (rc) return rc;
+  NERF_TRY(simp_check("nerf_simplify_cluster", V, F, lo, hi, grid, &bx));
   if (V == 0 || F == 0) return NERF_OK;
   NERF_REQUIRE(verts && normals && faces && workspace && tri_keys, NERF_E_NULL, "nerf_simplify_cluster: NULL pointer");
   const SimpWs w = simp_ws(workspace, V, F, grid);
   hipStream_t st = as_stream(stream);
-  const hipError_t e = hipMemsetAsync(w.mask, 0, w.W * sizeof(u64), st);
-  if (e != hipSuccess) return fail(NERF_E_HIP, "nerf_simplify_cluster: %s", hipGetErrorString(e));
-  SIMP_LAUNCH("nerf_simplify_cluster (keys)", simp_keys_kernel, blocks_of(V), verts, (int)V, bx, w.mask, w.vcid);
+  NERF_HIP("nerf_simplify_cluster", hipMemsetAsync(w.mask, 0, w.W * sizeof(u64), st));
+  SIMP_LAUNCH("nerf_simplify_cluster (keys)", simp_keys_kernel, mesh_blocks(V, SIMP_BLOCK), verts, (int)V, bx, w.mask, w.vcid);
   SIMP_LAUNCH("nerf_simplify_cluster (word counts)", simp_words_count_kernel, w.nblk_w, (const u64*)w.mask, w.W, w.blk_w);
-  rc = scan_launch("nerf_simplify_cluster (scan of the words)", w.blk_w, w.nblk_w, w.cnt, st);
-  if (rc) return rc;
+  NERF_TRY(scan_launch("nerf_simplify_cluster (scan of the words)", w.blk_w, w.nblk_w, w.cnt, st));
   SIMP_LAUNCH("nerf_simplify_cluster (word prefixes)", simp_words_write_kernel, w.nblk_w, (const u64*)w.mask, w.W,
               (const int64_t*)w.blk_w, w.wpre);
   SIMP_LAUNCH("nerf_simplify_cluster (zero)", simp_zero_kernel, grid_for(w.K_max * SIMP_ACC, SIMP_BLOCK), (const int64_t*)w.cnt, w.acc,
               w.used);
-  SIMP_LAUNCH("nerf_simplify_cluster (vertices)", simp_vertices_kernel, blocks_of(V), verts, normals, colors, (int)V, bx,
+  SIMP_LAUNCH("nerf_simplify_cluster (vertices)", simp_vertices_kernel, mesh_blocks(V, SIMP_BLOCK), verts, normals, colors, (int)V, bx,
               (const u64*)w.mask, (const int*)w.wpre, w.vcid, w.ckey, w.acc);
-  SIMP_LAUNCH("nerf_simplify_cluster (faces)", simp_faces_kernel, blocks_of(F), verts, faces, (int)V, (int)F, bx, (const int*)w.vcid,
-              w.acc, tri_keys, w.par);
+  SIMP_LAUNCH("nerf_simplify_cluster (faces)", simp_faces_kernel, mesh_blocks(F, SIMP_BLOCK), verts, faces, (int)V, (int)F, bx,
+              (const int*)w.vcid, w.acc, tri_keys, w.par);
   return NERF_OK;
 }
 
 extern "C" int nerf_simplify_count(const int64_t* sorted_keys, const int64_t* perm, int64_t V, const int32_t* faces, int64_t F,
                                    int grid, void* workspace, int64_t* totals, void* stream) {
-  int rc = simp_size_check("nerf_simplify_count", V, F, grid);
-  if (rc) return rc;
+  NERF_TRY(simp_size_check("nerf_simplify_count", V, F, grid));
   NERF_REQUIRE(totals, NERF_E_NULL, "nerf_simplify_count: NULL totals");
   if (V == 0 || F == 0) return zero_i64("nerf_simplify_count", totals, 3, stream);
   NERF_REQUIRE(sorted_keys && perm && faces && workspace, NERF_E_NULL, "nerf_simplify_count: NULL pointer");
@@ -511,32 +474,27 @@ extern "C" int nerf_simplify_count(const int64_t* sorted_keys, const int64_t* pe
   const int n = (int)F;
   const uint8_t* par = w.par;
   SIMP_LAUNCH("nerf_simplify_count (runs)", simp_runs_count_kernel, w.nblk_f, sorted_keys, perm, par, n, w.blk_s, w.nblk_f);
-  rc = scan_launch("nerf_simplify_count (scan of the run heads)", w.blk_s, w.nblk_f, w.cnt + 1, st);
-  if (rc) return rc;
-  rc = scan_launch("nerf_simplify_count (scan of the odd faces)", w.blk_s + w.nblk_f, w.nblk_f, w.cnt + 2, st);
-  if (rc) return rc;
+  NERF_TRY(scan_launch("nerf_simplify_count (scan of the run heads)", w.blk_s, w.nblk_f, w.cnt + 1, st));
+  NERF_TRY(scan_launch("nerf_simplify_count (scan of the odd faces)", w.blk_s + w.nblk_f, w.nblk_f, w.cnt + 2, st));
   SIMP_LAUNCH("nerf_simplify_count (run ranks)", simp_runs_write_kernel, w.nblk_f, sorted_keys, perm, par, n,
               (const int64_t*)w.blk_s, w.nblk_f, (const int64_t*)w.cnt, w.rid, w.heads, w.odd);
   SIMP_LAUNCH("nerf_simplify_count (survivors)", simp_survivors_kernel, w.nblk_f, sorted_keys, perm, par, faces, n,
               (const int*)w.rid, (const int*)w.heads, (const int*)w.odd, (const int*)w.vcid, (int)V, w.keep, w.used);
-  SIMP_LAUNCH("nerf_simplify_count (used clusters)", simp_flags_count_kernel, w.nblk_c, (const int*)w.used, (const int64_t*)w.cnt,
-              (int64_t)0, w.blk_c);
-  rc = scan_launch("nerf_simplify_count (scan of the clusters)", w.blk_c, w.nblk_c, totals, st);
-  if (rc) return rc;
-  SIMP_LAUNCH("nerf_simplify_count (kept faces)", simp_flags_count_kernel, w.nblk_f, (const int*)w.keep, (const int64_t*)nullptr, F,
-              w.blk_f);
-  rc = scan_launch("nerf_simplify_count (scan of the faces)", w.blk_f, w.nblk_f, totals + 1, st);
-  if (rc) return rc;
-  const hipError_t e = hipMemcpyAsync(totals + 2, w.cnt, sizeof(int64_t), hipMemcpyDeviceToDevice, st);
-  return e == hipSuccess ? NERF_OK : fail(NERF_E_HIP, "nerf_simplify_count: %s", hipGetErrorString(e));
+  SIMP_LAUNCH("nerf_simplify_count (used clusters)", scan_flags_count_kernel<SIMP_BLOCK>, w.nblk_c, (const int*)w.used,
+              (const int64_t*)w.cnt, (int64_t)0, w.blk_c);
+  NERF_TRY(scan_launch("nerf_simplify_count (scan of the clusters)", w.blk_c, w.nblk_c, totals, st));
+  SIMP_LAUNCH("nerf_simplify_count (kept faces)", scan_flags_count_kernel<SIMP_BLOCK>, w.nblk_f, (const int*)w.keep,
+              (const int64_t*)nullptr, F, w.blk_f);
+  NERF_TRY(scan_launch("nerf_simplify_count (scan of the faces)", w.blk_f, w.nblk_f, totals + 1, st));
+  NERF_HIP("nerf_simplify_count", hipMemcpyAsync(totals + 2, w.cnt, sizeof(int64_t), hipMemcpyDeviceToDevice, st));
+  return NERF_OK;
 }
 
 extern "C" int nerf_simplify_write(int64_t V, const int32_t* faces, int64_t F, const float* lo, const float* hi, int grid,
                                    int placement, void* workspace, int64_t V_out, int64_t F_out, float* verts_out,
                                    float* normals_out, float* colors_out, float* color_rows, int32_t* faces_out, void* stream) {
   SBox bx;
-  int rc = simp_check("nerf_simplify_write", V, F, lo, hi, grid, &bx);
-  if (rc) return rc;
+  NERF_TRY(simp_check("nerf_simplify_write", V, F, lo, hi, grid, &bx));
   NERF_REQUIRE(placement == NERF_SIMPLIFY_MEAN || placement == NERF_SIMPLIFY_QUADRIC, NERF_E_SHAPE,
                "nerf_simplify_write: placement must be 0 (mean) or 1 (quadric), got %d", placement);
   NERF_REQUIRE(V_out >= 0 && V_out <= V && F_out >= 0 && F_out <= F, NERF_E_SHAPE,

@@ -12,6 +12,7 @@
 //   normals  one lane per vertex over the same rows.
 // All launch- or cache-bound.
 #include "lattice.h"
+#include "quadric.h"
 #include "scan.h"
 #include "smooth_ws.h"
 
@@ -25,12 +26,6 @@ constexpr int SMOOTH_MAX_ITERATIONS = 1024;
 struct SmoothBox {
   double c[3], ext[3];
 };
-
-// rint(clamp(x, -lim, lim) scale) as int64, NaN counting as 0
-__device__ __forceinline__ int64_t smooth_fix(double x, double lim, double scale) {
-  if (x != x) return 0;
-  return (int64_t)rint(fmin(fmax(x, -lim), lim) * scale);
-}
 
 // the three coordinates of vertex v as doubles; true when all are finite
 __device__ __forceinline__ bool smooth_load(const float* __restrict__ verts, int v, double* x) {
@@ -46,7 +41,7 @@ __device__ __forceinline__ bool smooth_load(const float* __restrict__ verts, int
 
 // the corners of face f; false for an ignored face (an index outside [0, V) or two equal corners)
 __device__ __forceinline__ bool smooth_face(const int* __restrict__ faces, int f, int V, int* g) {
-  return mesh_corners(faces + 3 * f, V, g) && g[0] != g[1] && g[1] != g[2] && g[0] != g[2];
+  return mesh_corners(faces + 3 * f, V, g) && mesh_distinct(g);
 }
 
 // ---- entries per vertex: 12 B read and three integer atomics per face.  cnt comes in zeroed.
@@ -58,22 +53,8 @@ __global__ void __launch_bounds__(SMOOTH_BLOCK) smooth_count_kernel(const int* _
   for (int c = 0; c < 3; ++c) atomicAdd(&cnt[g[c]], 1);
 }
 
-// ---- row offsets: count (entries per workgroup of 256 vertices) and write (ranked inside the workgroup).  The write leaves the
-// row's first entry in off and in cur, the fill cursor.
-__global__ void __launch_bounds__(SMOOTH_BLOCK) smooth_rows_count_kernel(const int* __restrict__ cnt, int V, int64_t* __restrict__ blk) {
-  const int v = blockIdx.x * SMOOTH_BLOCK + threadIdx.x;
-  const int64_t t = block_sum<SMOOTH_BLOCK>(v < V ? cnt[v] : 0);
-  if (threadIdx.x == 0) blk[blockIdx.x] = t;
-}
-__global__ void __launch_bounds__(SMOOTH_BLOCK) smooth_rows_write_kernel(int* __restrict__ cur, int V, const int64_t* __restrict__ blk,
-                                                                        const int64_t* __restrict__ total, int* __restrict__ off) {
-  const int v = blockIdx.x * SMOOTH_BLOCK + threadIdx.x;
-  const int64_t o = block_offset<SMOOTH_BLOCK>(v < V ? cur[v] : 0, blk[blockIdx.x]);
-  if (v == 0) off[V] = (int)total[0];
-  if (v >= V) return;
-  off[v] = (int)o;
-  cur[v] = (int)o;
-}
+// (row offsets, entries per workgroup of 256 vertices and the row's first entry in off and in cur, the fill cursor: scan.h's
+// counts-to-offsets pair.  At most 3 F <= 3 2^24 entries: no cap.)
 
 // ---- entries: 12 B read per face, three cursor atomics, three 8-byte stores.  Row a receives (b, c), row b (c, a), row c (a, b).
 __global__ void __launch_bounds__(SMOOTH_BLOCK) smooth_fill_kernel(const int* __restrict__ faces, int F, int V, int* __restrict__ cur,
@@ -108,7 +89,7 @@ __global__ void __launch_bounds__(SMOOTH_BLOCK) smooth_step_kernel(const float* 
         if (!smooth_load(in, nb[j], y)) continue;
         ++n;
 #pragma unroll
-        for (int a = 0; a < 3; ++a) S[a] += smooth_fix((y[a] - bx.c[a]) / bx.ext[a], SMOOTH_POS_LIM, SMOOTH_POS_SCALE);
+        for (int a = 0; a < 3; ++a) S[a] += fixed((y[a] - bx.c[a]) / bx.ext[a], SMOOTH_POS_LIM, SMOOTH_POS_SCALE);
       }
     }
   }
@@ -145,9 +126,9 @@ __global__ void __launch_bounds__(SMOOTH_BLOCK) smooth_normals_kernel(const floa
         d1[a] = (yb[a] - x[a]) / bx.ext[a];
         d2[a] = (yc[a] - x[a]) / bx.ext[a];
       }
-      N[0] += smooth_fix(d1[1] * d2[2] - d1[2] * d2[1], SMOOTH_NRM_LIM, SMOOTH_NRM_SCALE);
-      N[1] += smooth_fix(d1[2] * d2[0] - d1[0] * d2[2], SMOOTH_NRM_LIM, SMOOTH_NRM_SCALE);
-      N[2] += smooth_fix(d1[0] * d2[1] - d1[1] * d2[0], SMOOTH_NRM_LIM, SMOOTH_NRM_SCALE);
+      N[0] += fixed(d1[1] * d2[2] - d1[2] * d2[1], SMOOTH_NRM_LIM, SMOOTH_NRM_SCALE);
+      N[1] += fixed(d1[2] * d2[0] - d1[0] * d2[2], SMOOTH_NRM_LIM, SMOOTH_NRM_SCALE);
+      N[2] += fixed(d1[0] * d2[1] - d1[1] * d2[0], SMOOTH_NRM_LIM, SMOOTH_NRM_SCALE);
     }
   }
   const double s[3] = {((double)N[0] / SMOOTH_NRM_SCALE) * (bx.ext[1] * bx.ext[2]), ((double)N[1] / SMOOTH_NRM_SCALE) * (bx.ext[2] * bx.ext[0]),
@@ -164,9 +145,8 @@ __global__ void __launch_bounds__(SMOOTH_BLOCK) smooth_normals_kernel(const floa
 }
 
 int smooth_box(const char* who, int64_t V, const float* lo, const float* hi, SmoothBox* bx) {
-  NERF_REQUIRE(V >= 0 && V <= SMOOTH_MAX_ITEMS, NERF_E_SHAPE, "%s: need 0 <= V <= 2^24 (got %lld)", who, (long long)V);
-  const int rc = box_check(who, lo, hi);
-  if (rc) return rc;
+  NERF_REQUIRE(V >= 0 && V <= MESH_MAX_ITEMS, NERF_E_SHAPE, "%s: need 0 <= V <= 2^24 (got %lld)", who, (long long)V);
+  NERF_TRY(box_check(who, lo, hi));
   for (int a = 0; a < 3; ++a) {
     bx->ext[a] = (double)hi[a] - (double)lo[a];
     bx->c[a] = ((double)lo[a] + (double)hi[a]) * 0.5;
@@ -191,24 +171,23 @@ extern "C" int nerf_smooth_build(int64_t V, const int32_t* faces, int64_t F, voi
   const SmoothWs w = smooth_ws(workspace, V, F);
   hipStream_t st = as_stream(stream);
   // F = 0: every row is empty, and the zeroed offsets say so; nothing is launched
-  const hipError_t e = F == 0 ? hipMemsetAsync(w.off, 0, (V + 1) * sizeof(int32_t), st) : hipMemsetAsync(w.cur, 0, V * sizeof(int32_t), st);
-  if (e != hipSuccess) return fail(NERF_E_HIP, "nerf_smooth_build: %s", hipGetErrorString(e));
+  NERF_HIP("nerf_smooth_build", F == 0 ? hipMemsetAsync(w.off, 0, (V + 1) * sizeof(int32_t), st)
+                                       : hipMemsetAsync(w.cur, 0, V * sizeof(int32_t), st));
   if (F == 0) return NERF_OK;
-  SMOOTH_LAUNCH("nerf_smooth_build (count)", smooth_count_kernel, smooth_blocks(F), faces, (int)F, (int)V, w.cur);
-  SMOOTH_LAUNCH("nerf_smooth_build (row counts)", smooth_rows_count_kernel, w.nblk_v, (const int*)w.cur, (int)V, w.blk);
-  const int rc = scan_launch("nerf_smooth_build (scan of the rows)", w.blk, w.nblk_v, w.total, st);
-  if (rc) return rc;
-  SMOOTH_LAUNCH("nerf_smooth_build (row offsets)", smooth_rows_write_kernel, w.nblk_v, w.cur, (int)V, (const int64_t*)w.blk,
-                (const int64_t*)w.total, w.off);
-  SMOOTH_LAUNCH("nerf_smooth_build (fill)", smooth_fill_kernel, smooth_blocks(F), faces, (int)F, (int)V, w.cur, w.ent);
+  const int64_t nblk_f = mesh_blocks(F, SMOOTH_BLOCK);
+  SMOOTH_LAUNCH("nerf_smooth_build (count)", smooth_count_kernel, nblk_f, faces, (int)F, (int)V, w.cur);
+  SMOOTH_LAUNCH("nerf_smooth_build (row counts)", scan_offsets_count_kernel<SMOOTH_BLOCK>, w.nblk_v, (const int*)w.cur, (int)V, w.blk);
+  NERF_TRY(scan_launch("nerf_smooth_build (scan of the rows)", w.blk, w.nblk_v, w.total, st));
+  SMOOTH_LAUNCH("nerf_smooth_build (row offsets)", scan_offsets_write_kernel<SMOOTH_BLOCK>, w.nblk_v, w.cur, (int)V,
+                (const int64_t*)w.blk, (const int64_t*)w.total, (int64_t)INT64_MAX, w.off, (int64_t*)nullptr);
+  SMOOTH_LAUNCH("nerf_smooth_build (fill)", smooth_fill_kernel, nblk_f, faces, (int)F, (int)V, w.cur, w.ent);
   return NERF_OK;
 }
 
 extern "C" int nerf_smooth_run(const float* verts_in, int64_t V, const float* lo, const float* hi, int iterations, float lambda,
                                float mu, void* workspace, float* verts_out, void* stream) {
   SmoothBox bx;
-  const int rc = smooth_box("nerf_smooth_run", V, lo, hi, &bx);
-  if (rc) return rc;
+  NERF_TRY(smooth_box("nerf_smooth_run", V, lo, hi, &bx));
   NERF_REQUIRE(iterations >= 1 && iterations <= SMOOTH_MAX_ITERATIONS, NERF_E_SHAPE, "nerf_smooth_run: need 1 <= iterations <= %d (got %d)",
                SMOOTH_MAX_ITERATIONS, iterations);
   NERF_REQUIRE(lambda > 0.0f && lambda <= 1.0f, NERF_E_SHAPE, "nerf_smooth_run: need 0 < lambda <= 1 (got %g)", (double)lambda);
@@ -233,8 +212,7 @@ extern "C" int nerf_smooth_run(const float* verts_in, int64_t V, const float* lo
 extern "C" int nerf_smooth_normals(const float* verts, int64_t V, const float* lo, const float* hi, void* workspace, float* normals_out,
                                    float* color_rows, void* stream) {
   SmoothBox bx;
-  const int rc = smooth_box("nerf_smooth_normals", V, lo, hi, &bx);
-  if (rc) return rc;
+  NERF_TRY(smooth_box("nerf_smooth_normals", V, lo, hi, &bx));
   if (V == 0) return NERF_OK;
   NERF_REQUIRE(verts && workspace && normals_out, NERF_E_NULL, "nerf_smooth_normals: NULL pointer");
   const SmoothWs w = smooth_ws(workspace, V, 0);

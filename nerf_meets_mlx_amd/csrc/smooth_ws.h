@@ -3,13 +3,12 @@
 // from V; the entries, 3 F of them at most, come last.  Every region starts on a multiple of 8 bytes.  Compiles without HIP
 // (tests/smooth_ws_check.cpp carves it under a host compiler).
 #pragma once
-#include <stdint.h>
+#include "mesh_ws.h"
 
 namespace nerf {
 namespace {
 
 constexpr int SMOOTH_BLOCK = 256;                   // vertices (or faces) per workgroup
-constexpr int64_t SMOOTH_MAX_ITEMS = 1ll << 24;     // V, F: 3 F entries fit an int
 
 struct SmoothEntry {                                // one face at one of its corners: the other two, in face order
   int32_t b, c;
@@ -26,26 +25,19 @@ struct SmoothWs {
   int64_t bytes;
 };
 
-inline bool smooth_sizes_ok(int64_t V, int64_t F) { return V >= 0 && V <= SMOOTH_MAX_ITEMS && F >= 0 && F <= SMOOTH_MAX_ITEMS; }
-inline int64_t smooth_blocks(int64_t n) { return (n + SMOOTH_BLOCK - 1) / SMOOTH_BLOCK; }
+inline bool smooth_sizes_ok(int64_t V, int64_t F) { return V >= 0 && V <= MESH_MAX_ITEMS && F >= 0 && F <= MESH_MAX_ITEMS; }
 
 inline SmoothWs smooth_ws(void* ws, int64_t V, int64_t F) {
   SmoothWs w;
-  w.nblk_v = smooth_blocks(V);
-  uintptr_t p = reinterpret_cast<uintptr_t>(ws);
-  const uintptr_t p0 = p;
-  auto take = [&p](int64_t bytes) {
-    const uintptr_t at = p;
-    p += (uintptr_t)((bytes + 7) & ~(int64_t)7);
-    return at;
-  };
-  w.blk = reinterpret_cast<int64_t*>(take(w.nblk_v * 8));
-  w.total = reinterpret_cast<int64_t*>(take(8));
-  w.tmp = reinterpret_cast<float*>(take(V * 12));
-  w.off = reinterpret_cast<int32_t*>(take((V + 1) * 4));
-  w.cur = reinterpret_cast<int32_t*>(take(V * 4));
-  w.ent = reinterpret_cast<SmoothEntry*>(take(3 * F * 8));
-  w.bytes = (int64_t)(p - p0);
+  w.nblk_v = mesh_blocks(V, SMOOTH_BLOCK);
+  WsCarver<8> c(ws);
+  w.blk = c.take<int64_t>(w.nblk_v);
+  w.total = c.take<int64_t>(1);
+  w.tmp = c.take<float>(V * 3);
+  w.off = c.take<int32_t>(V + 1);
+  w.cur = c.take<int32_t>(V);
+  w.ent = c.take<SmoothEntry>(3 * F);
+  w.bytes = c.bytes();
   return w;
 }
 

@@ -11,7 +11,7 @@ is Instant-NGP's.  One module per stage, and every name of theirs is a name of t
   generalized winding number on MeshBVH's tree, the inside test the distance lacks.  distance, raster <- raycast (MeshRaycast,
   pack_rays, raycast_frame, render_mesh_rays): nearest hit and occlusion of rays on the same tree, and the rasteriser's frame by
   rays."""
-from ._base import CHUNK, MAX_RES, SIMPLIFY_MAX_ITEMS, Mesh, _box, _check_mesh_tensors, _mark, check_mesh_args
+from ._base import CHUNK, MAX_RES, MESH_MAX_ITEMS, Mesh, _box, _check_mesh_tensors, _mark, check_mesh_args
 from .decimate import (DECIMATE_MAX_PASSES, DECIMATE_MAX_ROUNDS, DECIMATE_PLACEMENTS, DECIMATE_STOPS, DecimateStats, _decimate,
                        check_decimate_args, decimate)
 from .distance import (DISTANCE_INDEXES, DISTANCE_MAX_ENTRIES, DISTANCE_MAX_GRID, DISTANCE_MAX_SAMPLES, DistanceStats, MeshBVH,

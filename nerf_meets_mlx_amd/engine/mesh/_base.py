@@ -11,7 +11,7 @@ from ._checks import is_tensor, need_int, need_real, need_tensor
 
 MAX_RES = 512                # NERF_MESH_MAX_RES
 CHUNK = 1 << 19              # lattice points (or vertices) per query, as OccupancyGrid.update
-SIMPLIFY_MAX_ITEMS = 1 << 24  # vertices, faces
+MESH_MAX_ITEMS = 1 << 24  # vertices, faces
 
 
 class Mesh(NamedTuple):
@@ -97,6 +97,6 @@ def _check_mesh_tensors(who, mesh):
     if mesh.colors is not None and not is_tensor(mesh.colors, torch.float32, (V, 3), dev):
         raise ValueError(f"{who}: colors must be None or a contiguous float32 [V, 3] tensor on the vertices' device")
     F = mesh.faces.shape[0]
-    if V > SIMPLIFY_MAX_ITEMS or F > SIMPLIFY_MAX_ITEMS:
+    if V > MESH_MAX_ITEMS or F > MESH_MAX_ITEMS:
         raise ValueError(f"{who}: at most 2^24 vertices and faces, got {V} and {F}")
     return V, F

@@ -296,7 +296,7 @@ def test_header_section_bindings_and_makefile():
         assert len(re.findall(r"\b" + name + r"\(", tree)) == 1 and name not in src and name not in wind, name
     assert not re.search(r"\batomic\w*\(", tree) and "__shared__" not in tree and tree.count("__syncthreads()") == 1
     assert '#include "bvh_tree.h"' in src and '#include "bvh_tree.h"' in wind
-    # the shared device code lives in one place, and distance.hip still has its eight kernels
+    # the shared device code lives in one place, and distance.hip still has its own six kernels (its two offset kernels are scan.h's)
     shared = open(os.path.join(csrc, "distance.h")).read()
     dist = open(os.path.join(csrc, "distance.hip")).read()
     for name in ("dist_face", "dist_load", "point_triangle_closest", "point_triangle_d2", "dist_fold", "DIST_NONE", "dist_point",
@@ -305,7 +305,7 @@ def test_header_section_bindings_and_makefile():
         assert len(define.findall(shared)) == 1 and not define.search(dist) and not define.search(src) and not define.search(wind), name
     assert '#include "distance.h"' in dist and '#include "distance.h"' in src
     dk = sorted(set(re.findall(r"\b(\w+_kernel)\(", dist)))
-    assert len(dk) == 8 and all(k.startswith("dist_") for k in dk)
+    assert len(dk) == 6 and all(k.startswith("dist_") for k in dk) and dist.count("scan_offsets_") == 2
     for name in ("MeshBVH", "closest_points", "check_distance_index", "DISTANCE_INDEXES"):
         assert hasattr(E, name) and name in open(os.path.join(ROOT, "nerf_meets_mlx_amd", "engine", "mesh", "distance.py")).read()
     assert "distance (sample_surface, MeshIndex, mesh_distance)" in E.__doc__ and "MeshBVH" in E.__doc__

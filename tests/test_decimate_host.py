@@ -155,6 +155,22 @@ def test_argument_checks():
     assert E.DECIMATE_PLACEMENTS == D.PLACEMENTS and E.DECIMATE_STOPS == D.STOPS
 
 
+@pytest.mark.parametrize("V,F", [(1, 1), (3, 1), (255, 257), (1 << 24, 1 << 24)])
+def test_workspace_bytes_region_by_region(V, F):
+    """nerf_decimate_workspace_bytes in closed form: the regions of the workspace in their order, each rounded up to 8 bytes;
+    H = 3 F half-edges, nb(n) workgroups of 256 items."""
+    from nerf_meets_mlx_amd import _native as N
+    r8 = lambda b: (b + 7) & ~7
+    nb = lambda n: (n + 255) // 256
+    H = 3 * F
+    want = (r8(8 * 8) + r8(8 * nb(V)) + r8(8 * nb(F)) + r8(8 * nb(H))            # cnt, blk_v, blk_f, blk_h
+            + r8(8 * 10 * V) + r8(8 * 3 * V) + 2 * r8(8 * V) + r8(8 * H)         # Q, col, m1, m2, ekey
+            + r8(12 * V) + 2 * r8(12 * F)                                        # pos, the two face lists
+            + 2 * r8(4 * V) + r8(4 * 2 * V) + 5 * r8(4 * V)                      # mcnt, remap, vstart + vend, frozen ... newid
+            + 4 * r8(4 * H))                                                     # ea, eb, sel, inc
+    assert N.lib().nerf_decimate_workspace_bytes(V, F) == want
+
+
 def test_header_section_and_bindings():
     from nerf_meets_mlx_amd import _native as N
     h = open(os.path.join(ROOT, "include", "nerf_hip.h")).read()

@@ -269,7 +269,12 @@ def test_header_section_bindings_and_makefile():
     assert not re.search(r"FLAGS_distance", mk)                                          # the default flags, -ffp-contract=off among them
     src = open(os.path.join(ROOT, "nerf_meets_mlx_amd", "csrc", "distance.hip")).read()
     kernels = sorted(set(re.findall(r"\b(\w+_kernel)\(", src)))
-    assert len(kernels) == 8 and all(k.startswith("dist_") for k in kernels)
+    assert kernels == ["dist_cdf_kernel", "dist_count_kernel", "dist_fill_kernel", "dist_query_kernel", "dist_sample_kernel",
+                       "dist_weight_kernel"]
+    # the cell offsets are csrc/scan.h's counts-to-offsets pair, defined there once and launched here: eight kernels as before
+    scan = open(os.path.join(ROOT, "nerf_meets_mlx_amd", "csrc", "scan.h")).read()
+    for name in ("scan_offsets_count_kernel", "scan_offsets_write_kernel"):
+        assert len(re.findall(r"\b" + name + r"\(", scan)) == 1 and src.count(name + "<DIST_BLOCK>,") == 1, name
     assert "atomicAdd(float" not in src and not re.search(r"atomic\w*\(\s*\(float", src)
     for name in ("sample_surface", "MeshIndex", "point_mesh_distance", "mesh_distance", "MeshDistance", "check_distance_args"):
         assert hasattr(E, name) and name in open(os.path.join(ROOT, "nerf_meets_mlx_amd", "engine", "mesh", "distance.py")).read()

@@ -113,6 +113,21 @@ def test_query_matches_the_brute_force_bit_for_bit_at_every_grid(name, n):
             assert idx.E == int(D.corners(v, f)[0].sum())             # the brute-force scan: every valid face once
 
 
+@pytest.mark.parametrize("G", [6, 7])
+def test_query_at_cell_counts_around_one_workgroup(G):
+    """The cell offsets come from csrc/scan.h's counts-to-offsets pair, 256 cells a workgroup: 216 cells sit just under one
+    workgroup and 343 just over (one cell is GRIDS[0]; no cube is 256).  The query against the brute force, and the offsets
+    themselves: an exclusive scan that ends at E, every cursor left at the end of its cell by the fill."""
+    v, f, pts, d2, fc = _case("sphere12", 257)
+    idx = _Index(v, f, G)
+    _assert_same(idx.query(pts), (d2, fc), ("sphere12", 257, G))
+    cells, nblk = G ** 3, -(-G ** 3 // 256)
+    at = 8 * nblk + 16                                                # behind blk [nblk], total and scale
+    off = idx.ws[at:at + 4 * (cells + 1)].view(torch.int32).cpu().numpy()
+    cur = idx.ws[at + 8 * ((cells + 2) // 2):][:4 * cells].view(torch.int32).cpu().numpy()      # off's cells + 1 ints, rounded to 8 B
+    assert off[0] == 0 and off[cells] == idx.E and (np.diff(off) >= 0).all() and np.array_equal(cur, off[1:])
+
+
 def test_the_nan_point_an_empty_mesh_and_a_mesh_of_invalid_faces():
     v, f, pts, d2, fc = _case("junk", 257)
     i = int(np.nonzero(np.isnan(pts).any(1))[0][0])

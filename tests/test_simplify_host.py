@@ -172,6 +172,23 @@ def test_header_section_and_bindings():
     assert "simplify.hip" in src
 
 
+@pytest.mark.parametrize("G", [2, 512])
+@pytest.mark.parametrize("V,F", [(1, 1), (3, 1), (255, 257), (1 << 24, 1 << 24)])
+def test_workspace_bytes_region_by_region(V, F, G):
+    """nerf_simplify_workspace_bytes in closed form: the regions of the header's workspace in their order, each rounded up to 8
+    bytes; nb(n) workgroups of 256 items."""
+    from nerf_meets_mlx_amd import _native
+    r8 = lambda b: (b + 7) & ~7
+    nb = lambda n: (n + 255) // 256
+    cells = G ** 3
+    W, K = (cells + 63) >> 6, min(V, cells)
+    want = (r8(8 * W) + r8(8 * 19 * K) + r8(8 * 4)                               # mask, acc, cnt
+            + r8(8 * nb(W)) + r8(8 * nb(K)) + r8(8 * 2 * nb(F)) + r8(8 * nb(F))  # blk_w, blk_c, blk_s, blk_f
+            + r8(4 * W) + r8(4 * V) + 3 * r8(4 * K)                              # wpre, vcid, ckey, used, newid
+            + r8(4 * (F + 1)) + r8(4 * F) + r8(4 * (F + 1)) + r8(4 * F) + r8(F))  # odd, rid, heads, keep, par
+    assert _native.lib().nerf_simplify_workspace_bytes(V, F, G) == want
+
+
 def test_mesh_tool_stats_know_the_simplifier_kernels(tmp_path, capsys):
     import argparse
     import importlib.util

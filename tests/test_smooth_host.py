@@ -163,7 +163,11 @@ def test_header_section_bindings_and_makefile():
     assert "smooth.hip" in srcs.split() and "smooth_ws.h" in mk
     src = open(os.path.join(ROOT, "nerf_meets_mlx_amd", "csrc", "smooth.hip")).read()
     kernels = sorted(set(re.findall(r"\b(\w+_kernel)\(", src)))
-    assert len(kernels) == 6 and all(k.startswith("smooth_") for k in kernels)
+    assert kernels == ["smooth_count_kernel", "smooth_fill_kernel", "smooth_normals_kernel", "smooth_step_kernel"]
+    # the row offsets are csrc/scan.h's counts-to-offsets pair, defined there once and launched here: six kernels as before
+    scan = open(os.path.join(ROOT, "nerf_meets_mlx_amd", "csrc", "scan.h")).read()
+    for name in ("scan_offsets_count_kernel", "scan_offsets_write_kernel"):
+        assert len(re.findall(r"\b" + name + r"\(", scan)) == 1 and src.count(name + "<SMOOTH_BLOCK>,") == 1, name
 
 
 def test_pipeline_keywords_and_defaults():

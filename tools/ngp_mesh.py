@@ -1374,7 +1374,7 @@ def stats(a):
     draw_seen = {}
     project_seen = 0
     for r in rows:
-        m = re.search(r"(mesh_\w+_kernel|ccl_\w+_kernel|morph_\w+_kernel|tsdf_\w+_kernel|simp_\w+_kernel|smooth_\w+_kernel|tex_\w+_kernel|raster_\w+_kernel|project_\w+_kernel|mip_\w+_kernel|occ_cull_scan_kernel|occ_merge_exp_kernel)", r[name_k])
+        m = re.search(r"(mesh_\w+_kernel|ccl_\w+_kernel|morph_\w+_kernel|tsdf_\w+_kernel|simp_\w+_kernel|smooth_\w+_kernel|scan_\w+_kernel|tex_\w+_kernel|raster_\w+_kernel|project_\w+_kernel|mip_\w+_kernel|occ_cull_scan_kernel|occ_merge_exp_kernel)", r[name_k])
         if not m:
             continue
         k = m.group(1)
@@ -1411,7 +1411,8 @@ def stats(a):
             mip_items.setdefault(k, []).append(grid)
             groups.setdefault((k, None), []).append((int(r[e_k]) - int(r[s_k])) * 1e-3)
             continue
-        if k.startswith(("simp_", "smooth_")):         # sized by the mesh: one lane per vertex or face of the run at R; else pooled
+        if k.startswith(("simp_", "smooth_", "scan_")):    # (scan_: the flag count and the row offsets of those two, csrc/scan.h)
+            # sized by the mesh: one lane per vertex or face of the run at R; else pooled
             R = next((R for R, run in runs.items() if grid in (-(-run["V"] // BLOCK) * BLOCK, -(-run["F"] // BLOCK) * BLOCK)), None)
         elif k.startswith("tex_") or k in ("mesh_points_kernel", "occ_merge_exp_kernel", "occ_cull_scan_kernel", "ccl_finish_kernel"):
             R = None                                                       # chunked / one workgroup: pooled per kernel
