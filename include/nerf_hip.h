@@ -15,7 +15,17 @@
  *     A/B measurement knobs of nerf_set_option (kernel-variant selection; they never change results' layout,
  *     buffer sizes or which weight image a launch reads).
  *   - `stream` is a hipStream_t passed as void*; all work is enqueued on it, no hidden
- *     synchronisation, safe to capture into a hipGraph.
+ *     synchronisation, safe to capture into a hipGraph.  A captured call freezes every BY-VALUE argument: each replay
+ *     reads the device buffers as they are then, but runs with the host values of capture time -- Adam's `lr` and `step`
+ *     and the bias-correction factors c1, c2 derived from `step` on the host, the seeds and offsets of the sampling
+ *     entries, the level weights (copied into the launch), sizes, flags, and the A/B options of nerf_set_option as they
+ *     stood.  The ring kernels' pass-queue slot is frozen too: eager launches take the 256 slots of their translation
+ *     unit round-robin, a captured launch keeps its slot for the life of the graph.  Launches on one stream are safe (the
+ *     last workgroup clears the slot before the next launch starts); a graph holding ring-kernel launches must not be
+ *     replayed CONCURRENTLY with 256 or more later launches of the same unit on other streams -- or capture it with
+ *     nerf_set_option("pass_queue", 0), which changes no result.  The host package refuses the captures a replay would
+ *     get silently wrong (bias-corrected Adam, optimiser state created inside the capture) and records its lazy
+ *     conversions (weight image, fp16 table shadow) into every graph: DESIGN.md "Graph capture".
  *   - tensors are dense row-major float32 unless stated; index tensors are int64.
  *   - return value: 0 = NERF_OK, negative = NERF_E_*;  nerf_last_error() gives text.
  *   - thread-compatible (not thread-safe); one process per GPU.

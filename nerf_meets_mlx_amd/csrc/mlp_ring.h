@@ -311,7 +311,10 @@ __device__ __forceinline__ bf16x8 next_frag(WS& ws, int f, int lane) { return ws
 //     not read yet.  All LDS traffic is inline asm: through a C++ pointer hipcc loses the address space and emits flat_store /
 //     flat_load + vmcnt(0).
 //   * The counter lives in a slot of a small device array (PASSQ_SLOTS per translation unit and device, taken round-robin by the
-//     host: launches in flight at the same time never share one); the last workgroup to leave a launch clears its slot.
+//     host: eager launches in flight at the same time share one only if PASSQ_SLOTS later launches of the unit are in flight with
+//     them); the last workgroup to leave a launch clears its slot.  A launch captured into a hipGraph keeps the slot it took at
+//     capture for the life of the graph: a replay must not run concurrently with PASSQ_SLOTS or more later launches of this unit on
+//     other streams (include/nerf_hip.h, conventions); on one stream the slot is clear before the next launch starts.
 //   * nerf_set_option("pass_queue", 0) = static split (queue pointer null): same kernel, same results -- which workgroup computes a
 //     pass changes nothing a pass computes.
 // ------------------------------------------------------------------------------------------

@@ -26,7 +26,7 @@ from .. import _native as N
 from .. import parallel, sampling
 from ..encoding.multi_hash import MultiHashEncoding
 from ..encoding.spherical_harmonics import SphericalHarmonicsEncoding
-from ..models.NeRF import Adam, NeRF
+from ..models.NeRF import Adam, NeRF, capturing_now
 from ..rendering import ray, render
 from .trainer import Trainer
 
@@ -45,14 +45,20 @@ class _Flat:
     def mark_updated(self, shadow_written: bool = False):
         """Called by Adam after it wrote the master through raw pointers (no torch version bump): with shadow_written it
         wrote EVERY shadow entry in the same pass, so the shadow is current; otherwise it is stale."""
-        self._half_version = self.params._version if shadow_written else -1
+        self._half_version = self.params._version if shadow_written and not capturing_now() else -1     # (a recorded pass wrote nothing yet)
 
     def shadow(self) -> Optional[torch.Tensor]:
         """The fp16 image, current with the float32 master (None when the model was built without one).  Rebuilt by one
-        conversion pass after construction, load_flat, or a torch in-place edit of the tables (version counter)."""
+        conversion pass after construction, load_flat, or a torch in-place edit of the tables (version counter).  Under stream
+        capture the conversion is always enqueued -- the graph carries its own -- and the shadow keeps counting as stale, since
+        a recorded conversion has not run (DESIGN.md "Graph capture").  (Replays need no flag here: the Adam pass that writes
+        the master, recorded or not, writes every shadow entry with it.)"""
         if self.half is None:
             return None
-        if self._half_version != self.params._version:
+        if capturing_now():
+            self.half.copy_(self.params)
+            self._half_version = -1
+        elif self._half_version != self.params._version:
             self.half.copy_(self.params)
             self._half_version = self.params._version
         return self.half

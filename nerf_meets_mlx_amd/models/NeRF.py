@@ -21,6 +21,11 @@ from . import embedding
 _LAYERS = None
 
 
+def capturing_now() -> bool:
+    """True while the current stream records into a hipGraph (torch.cuda.graph): one cheap host query, no device work."""
+    return torch.cuda.is_current_stream_capturing()
+
+
 def layer_shapes(n_layers=8, width=256, cin=63, cdir=27, skips=(4,), use_viewdirs=True, cout=4):
     """(name, out, in) in flat-buffer order (include/nerf_hip.h "Parameter layout")."""
     s = [("pos0", width, cin)]
@@ -82,6 +87,7 @@ class NeRF:
         self._packed = None
         self._dirty = True
         self._packed_version = -1           # params._version the packed image was built from
+        self._graph_writes = False          # an optimiser step of this model was recorded into a graph (mark_updated)
         self._ws: Dict[str, torch.Tensor] = {}
         self.name: Optional[str] = None     # stable key for optimiser state / checkpoints ("coarse", "fine", ...)
         self._gen = 0                       # generation of the activation workspace (one per train-mode forward)
@@ -121,6 +127,10 @@ class NeRF:
 
     def mark_updated(self):
         self._dirty = True
+        if capturing_now():
+            # an optimiser step recorded into a graph writes the parameters at every replay, and no replay tells the host: from
+            # here on this model's image is never trusted again, every eager packed() packs (DESIGN.md "Graph capture")
+            self._graph_writes = True
 
     def activation_generation(self) -> int:
         return self._acts_gen
@@ -165,11 +175,16 @@ class NeRF:
         # re-pack when the master parameters changed: kernels that write through raw pointers (Adam) say so with
         # mark_updated(); torch in-place ops on `params` or on the views of parameters() bump the version counter
         form = self.train_form()
-        if self._dirty or self.params._version != self._packed_version or form != self._packed_form:
+        # Under stream capture (DESIGN.md "Graph capture") the pack is ALWAYS enqueued, so that a graph carries its own and every
+        # replay reads the weights of replay time; and since a recorded pack has not run, the bookkeeping keeps saying "stale":
+        # the next eager call packs again instead of reading an image nobody wrote.
+        capturing = capturing_now()
+        if (capturing or self._graph_writes or self._dirty or self.params._version != self._packed_version
+                or form != self._packed_form):
             with self._form(form):
                 N.check(lib.nerf_mlp_pack(C.byref(self.arch), N.ptr(self.params), N.ptr(self._packed), N.stream()))
-            self._dirty = False
-            self._packed_version = self.params._version
+            self._dirty = capturing
+            self._packed_version = -1 if capturing else self.params._version
             self._packed_form = form
         return self._packed
 
@@ -294,12 +309,27 @@ class Adam:
             return str(name)
         return self._auto_names.setdefault(id(model), f"model{len(self._auto_names)}")
 
+    def _refuse_capture(self, key: str, who: str):
+        """A captured launch freezes its by-value arguments (DESIGN.md "Graph capture"): refuse the two steps a replay would get
+        silently wrong, before anything is recorded or counted."""
+        if not capturing_now():
+            return
+        if self.bias_correction:
+            raise ValueError(f"Adam.{who}: cannot be captured into a graph with bias_correction=True: the correction factors are "
+                             "computed on the host from the step count and passed by value, so every replay would apply the "
+                             "factors of the captured step")
+        if key not in self.state:
+            raise ValueError(f"Adam.{who}: cannot be captured into a graph before the state of key {key!r} exists: the zeroed "
+                             "moments would be allocated and cleared inside the graph, and every replay would clear them again; "
+                             "run one eager step first")
+
     def update(self, model: NeRF, grads: Optional[torch.Tensor] = None, grad_scale: float = 1.0, zero_grads: bool = False):
         """zero_grads: clear the gradient buffer in the same pass (`nerf_adam_step_ex`: read g, write 0) -- for gradients
         that are ACCUMULATED by a scatter (the hash tables); an int64 `grads` tensor is taken as the fixed-point accumulators
         of the deterministic scatter (nerf_hashgrid_backward_rays_ex)."""
         g = model.grads if grads is None else grads
         key = self.key_of(model)
+        self._refuse_capture(key, "update")
         if key not in self.state:
             self.state[key] = [torch.zeros_like(model.params), torch.zeros_like(model.params)]
         self.step_count[key] = self.step_count.get(key, 0) + 1
@@ -326,6 +356,7 @@ class Adam:
         shards of a flat buffer this rank owns: NGPTrainer's reduce-scatter update).  Moments of the other elements are left
         alone; the step count advances once.  float32 or int64 fixed-point gradients, not cleared."""
         key = self.key_of(model)
+        self._refuse_capture(key, "update_spans")
         if key not in self.state:
             self.state[key] = [torch.zeros_like(model.params), torch.zeros_like(model.params)]
         self.step_count[key] = self.step_count.get(key, 0) + 1
